@@ -15,6 +15,10 @@ After it, one more (untimed) job runs with HIP events around every kernel
 launch: the `roofline` object comes from those, the `cpu_baseline` object from
 the oracle (tests' checker) timed on the host cores over a bounded sample.
 
+`--dump-outputs DIR` leaves what the last timed step handed its caller -- the segments of the finished grain table -- as
+DIR/<name>.npy (float64), so that two builds can be compared output for output: the frames are seeded, the same arguments
+feed the same samples.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -31,11 +35,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# The HIP runtime gives a process 4 hardware queues by default; the generator's four streams and torch's own then share them
-# and kernels of different streams wait for each other (the same build: 544 - 593 k Mpx/s from run to run; with 8 queues
-# 590 - 595 k: profiles/r04_streams.txt).  Read by the runtime when it starts: set before anything touches the GPU.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -50,6 +49,24 @@ WORKLOADS = {
 }
 
 
+def dump_outputs(dirpath: str, segs) -> None:
+    """The segments of a finished job (what `finish()` returns: the whole of the path's output, a few hundred integers) as
+    float64 arrays, every integer of the table exact below 2^53 (the open end of the last segment, 2^63 - 1, reads 2^63).  Rows are segments; the scaling points of all segments
+    are stacked in order, `segments.npy` says how many belong to each."""
+    os.makedirs(dirpath, exist_ok=True)
+    scalars = ["random_seed", "start_time", "end_time", "scaling_shift", "ar_coeff_lag", "ar_coeff_shift", "cb_mult", "cb_luma_mult",
+               "cb_offset", "cr_mult", "cr_luma_mult", "cr_offset", "chroma_scaling_from_luma", "grain_scale_shift", "overlap_flag"]
+    points = ["scaling_points_y", "scaling_points_cb", "scaling_points_cr"]
+    arrays = {"segments": np.array([[float(getattr(s, k)) for k in scalars] + [float(len(getattr(s, k))) for k in points] for s in segs],
+                                   dtype=np.float64).reshape(len(segs), len(scalars) + len(points))}
+    for k in points:
+        arrays[k] = np.array([xy for s in segs for xy in getattr(s, k)], dtype=np.float64).reshape(-1, 2)
+    for k in ("ar_coeffs_y", "ar_coeffs_cb", "ar_coeffs_cr"):
+        arrays[k] = np.array([getattr(s, k) for s in segs], dtype=np.float64).reshape(len(segs), -1)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` with no launcher around it: re-run this command line as N ranks under torch.distributed.run
     (what the driver's own N > 1 command is), one rank per GPU, and pass the children's output through."""
@@ -60,7 +77,6 @@ def self_launch(n: int) -> int:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = dict(os.environ)
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # (dmabuf IPC: what RCCL needs on this host driver)
     env.setdefault("OMP_NUM_THREADS", "1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
@@ -109,6 +125,8 @@ def main() -> None:
     ap.add_argument("--cpu-frames", type=int, default=2)
     ap.add_argument("--no-table-check", action="store_true", help="skip the untimed half-batch job the timed job's table is checked against "
                     "(profiling runs: its launches are half the size and would halve the profiler's per-kernel averages)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the grain table segments the last timed step returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -206,13 +224,14 @@ def main() -> None:
     stats_total = None
     kernel_times = {}
     last_tbl = None
+    last_segs = None  # what the last job's finish() returned (rank 0 at N > 1)
     tbl_digests = []  # SHA-256 of the table of every job that ended in one (rank 0 at N > 1), in order
     window_samples = None  # per plane, of the last frame of the timed-kernels step
     exchange_s, exchange_rounds = 0.0, 0  # N > 1: the feeding thread's time in the rounds' exchange
 
     def one_step(timing, cycles: int = 0, prep=None, batch: int = 0):  # timing: False | True (an event a kernel) | 2 (one pair a batch)
         """one job: the resident frames `cycles` times over through a fresh generator, up to the finished table"""
-        nonlocal stats_total, last_tbl, window_samples, kernel_times, exchange_s, exchange_rounds
+        nonlocal stats_total, last_tbl, last_segs, window_samples, kernel_times, exchange_s, exchange_rounds
         cycles = cycles or args.cycles
         prep = prep if prep is not None else prepared
         if multi:
@@ -242,6 +261,7 @@ def main() -> None:
         if timing is True:
             kernel_times = sd.generator.kernel_times()
         if segs is not None:
+            last_segs = segs
             last_tbl = format_tbl(segs)
             tbl_digests.append(hashlib.sha256(last_tbl).hexdigest())
         if timing:
@@ -279,6 +299,8 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     host_cores_busy = (sum(os.times()[:2]) - cpu0) / max(elapsed, 1e-9)
     timed_digests = tbl_digests[n_untimed:]
+    if args.dump_outputs and rank == 0 and args.steps > 0:  # (before the untimed jobs below end in segments of their own)
+        dump_outputs(args.dump_outputs, last_segs)
     if not multi and not args.no_table_check:  # (behind the timed region: nothing but the W warm-up steps runs in front of it)
         one_step(False, batch=max(1, B // 2))
         check_tbl = tbl_digests.pop()

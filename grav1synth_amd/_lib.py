@@ -10,9 +10,8 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (GPU_MAX_HW_QUEUES=8 -- a hardware queue per stream, INTEGRATION.md section 3 -- is the PROCESS' choice: the entry points
-#  set it (bench.py, the command in cli.py, tests/conftest.py), importing this package changes nobody's environment; the
-#  engine says so once on stderr when a generator's streams are made with fewer queues than they want)
+# (importing this package changes nobody's environment: the number of hardware queues the HIP runtime gives the process,
+#  INTEGRATION.md section 3, is the host's setting)
 LIB_PATH = os.environ.get("G1S_LIB") or os.path.join(_HERE, "libg1s_diff.so")  # (G1S_LIB: an instrumented build, tools/ only)
 
 G1S_OK = 0

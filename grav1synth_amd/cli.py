@@ -135,8 +135,6 @@ def estimate_command(source: str, output: str, overwrite: bool = False, device: 
 
 
 def main(argv: Optional[List[str]] = None) -> int:
-    # a hardware queue per stream of the generator (the HIP runtime reads this when it starts: before the first GPU call)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
     if args.command == "diff":

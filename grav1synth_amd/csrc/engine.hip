@@ -364,19 +364,11 @@ bool acquire_streams(int device, StreamSet &out) {
   out = StreamSet{};
   out.device = device;
   // the side stream (the finder chain: small latency-bound kernels) outranks the main stream's big kernels, next to which it
-  // runs.  What matters more than the order of the two: that the streams do not share a hardware queue.  The runtime gives a
-  // process 4 by default (GPU_MAX_HW_QUEUES); the 4 - 6 streams here plus the host application's own then share, by creation
-  // order, and kernels of different streams wait for each other: the same build read 544 - 593 k Mpx/s from run to run, 590 -
-  // 595 k with GPU_MAX_HW_QUEUES=8, and 393 - 406 k with every stream in one priority class on 4 queues
-  // (profiles/r04_streams.txt).  bench.py and the command set the variable before the runtime starts; the streams only some
-  // jobs use (the second side stream, the device half's) are made when they are first needed.
-  {
-    static std::atomic<bool> said{false};
-    const char *q = getenv("GPU_MAX_HW_QUEUES");
-    if ((!q || atoi(q) < 8) && !said.exchange(true))
-      fprintf(stderr, "g1s: GPU_MAX_HW_QUEUES is %s: the generator's streams will share hardware queues (slower, not wrong); set "
-                      "GPU_MAX_HW_QUEUES=8 before the process' first HIP call\n", q ? q : "unset");
-  }
+  // runs.  The 4 - 6 streams here and the host application's own share the hardware queues the runtime gives the process, by
+  // creation order, and kernels of streams on one queue wait for each other (slower, not wrong: 393 - 406 k Mpx/s with every
+  // stream in one priority class on 4 queues against 544 - 593 k with the priorities, profiles/r04_streams.txt).  How many
+  // queues a process gets is the host's setting and is left alone; the streams only some jobs use (the second side stream,
+  // the device half's) are made when they are first needed.
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);  // numerically lower = more urgent
   if (const char *e = getenv("G1S_PRIO")) {  // tuning aid: 1 = the main stream outranks the side stream, 2 = no priorities

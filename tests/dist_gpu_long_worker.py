@@ -1,19 +1,19 @@
 """python -m tests.dist_gpu_long_worker OUTDIR -- one rank of BASELINE.json configs[3] at its stated size: 3840x2160 10-bit 4:2:0,
-lag 3, chroma, 1000 frames in eight shards (tests/test_gpu_long.py launches eight of these on ONE device over gloo, the way
-G1S_BENCH_SHARE_GPU=1 runs bench.py --gpus 8 on a single-GPU box).
+lag 3, chroma, 1000 frames in one shard a rank (tests/test_gpu_long.py launches four of these on ONE device over gloo, the way
+G1S_BENCH_SHARE_GPU=1 runs bench.py --gpus 4 on a single-GPU box; sizes below are for four ranks).
 
 Three jobs over the same 1000 frames (tests/golden/make_golden.py LONG: scene cuts at frames 500 and 768), rank 0 writes a table each:
 
   streaming_host.tbl    StreamingShardedDiff (what bench.py --gpus N runs): 64-frame batches dealt round-robin (16 batches, the last
-                        one 40 frames: rank r feeds batches r and r + 8), the per-frame half of the fold on each rank's host pool,
+                        one 40 frames: rank r feeds batches r, r + 4, r + 8 and r + 12), the per-frame half of the fold on each rank's host pool,
                         one gather of latest states a round, the ordered merge on rank 0.  Frame 768 is a batch boundary, frame 500
                         lies inside batch 7.
   streaming_device.tbl  the same with the per-frame half on the device (k4_latest, G1S_LATEST=device: what a 16-core quota takes).
-  contiguous.tbl        ShardedDiff: 125 consecutive frames a rank ("125 per GPU x 8"), ONE all-gather of the integer records at
-                        the end, the whole fold on rank 0.  Frame 500 is a shard boundary, frame 768 lies inside shard 6.
+  contiguous.tbl        ShardedDiff: 250 consecutive frames a rank, ONE all-gather of the integer records at
+                        the end, the whole fold on rank 0.  Frame 500 is a shard boundary, frame 768 lies inside shard 3.
 
-G1S_LONG_NAME picks the job (tests/golden/make_golden.py LONG).  The second one is configs[4]'s format in eight shards: 7680x4320 10-bit
-4:4:4, 32 frames, batches and shards of 4 (one batch a rank), cuts at frame 16 (a boundary of both) and 22 (inside batch / shard 5).
+G1S_LONG_NAME picks the job (tests/golden/make_golden.py LONG).  The second one is configs[4]'s format: 7680x4320 10-bit
+4:4:4, 32 frames, batches of 4 (two a rank) and shards of 8, cuts at frame 16 (a boundary of both) and 22 (inside batch 5 / shard 2).
 """
 import os
 import sys
@@ -26,7 +26,7 @@ from grav1synth_amd.dist import ShardedDiff, StreamingShardedDiff
 from grav1synth_amd.synth import make_pair
 from tests.golden import make_golden
 
-NAME = os.environ.get("G1S_LONG_NAME", "oracle_full_3840x2160_10b_420_lag3_1000frames.tbl")  # (the 8K 4:4:4 job of configs[4]: 32 frames, 4 a batch and shard)
+NAME = os.environ.get("G1S_LONG_NAME", "oracle_full_3840x2160_10b_420_lag3_1000frames.tbl")  # (the 8K 4:4:4 job of configs[4]: 32 frames, 4 a batch)
 BATCH = int(make_golden.LONG[NAME].get("batch", 64))
 
 

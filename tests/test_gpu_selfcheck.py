@@ -143,12 +143,13 @@ def test_bench_launches_its_own_ranks():
     assert out["config"]["backend"] == "gloo" and out["scaling"] == "weak"
 
 
-def test_bench_eight_ranks_on_one_device_end_in_the_one_rank_jobs_table():
-    """The rehearsal of `python bench.py --gpus 8` a one-GPU box allows: eight ranks on this device (gloo), the per-frame half of the
+def test_bench_four_ranks_on_one_device_end_in_the_one_rank_jobs_table():
+    """The rehearsal of `python bench.py --gpus 8` a one-GPU box allows: four ranks on this device (a shared GPU takes six
+    processes at once, this one included; gloo), the per-frame half of the
     fold on the device (G1S_LATEST=device: what bench.py picks when a 16-core quota gives a rank two cores), three timed steps.
     finish() refuses a job whose merged frame count is not what the ranks fed; the line's tbl_sha256 (every timed step ended in
     these bytes) must be the one-rank job's over the same video: rank r's 64 resident frames are frames 64 r .. 64 r + 63 of a
-    512-frame cycle, so `--gpus 1 --frames 512` feeds the same frames in the same order."""
+    256-frame cycle, so `--gpus 1 --frames 256` feeds the same frames in the same order."""
     def line(gpus, frames, extra_env):
         env = dict(os.environ, **extra_env)
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -161,12 +162,12 @@ def test_bench_eight_ranks_on_one_device_end_in_the_one_rank_jobs_table():
         assert len(lines) == 1, p.stdout[-2000:]
         return json.loads(lines[0])
 
-    eight = line(8, 64, {"G1S_BENCH_SHARE_GPU": "1", "G1S_LATEST": "device"})
-    assert eight["n_gpus"] == 8 and eight["config"]["backend"] == "gloo" and eight["config"]["per_frame_fold_half"].startswith("device")
-    assert eight["config"]["frames_per_rank_per_step"] == 192 and eight["value"] > 0
-    one = line(1, 512, {})
+    four = line(4, 64, {"G1S_BENCH_SHARE_GPU": "1", "G1S_LATEST": "device"})
+    assert four["n_gpus"] == 4 and four["config"]["backend"] == "gloo" and four["config"]["per_frame_fold_half"].startswith("device")
+    assert four["config"]["frames_per_rank_per_step"] == 192 and four["value"] > 0
+    one = line(1, 256, {})
     assert one["tbl_sha256"] == one["tbl_sha256_untimed_half_batch_job"]
-    assert eight["tbl_sha256"] == one["tbl_sha256"] and eight["tbl_bytes"] == one["tbl_bytes"] > 100
+    assert four["tbl_sha256"] == one["tbl_sha256"] and four["tbl_bytes"] == one["tbl_bytes"] > 100
 
 
 @pytest.mark.parametrize("half", ["host", "device"])
@@ -195,33 +196,41 @@ def test_bench_one_rank_through_the_rccl_code_path(half):
     assert len(out["tbl_sha256"]) == 64
 
 
+_CHAIN_CODE = (
+    "import hashlib, json\n"
+    "from fractions import Fraction\n"
+    "from grav1synth_amd.diff import DiffGenerator, format_tbl\n"
+    "from grav1synth_amd.synth import SynthSpec, make_pair\n"
+    "spec = SynthSpec(1280, 704, 10)\n"
+    "pairs = [make_pair(spec, k, device='cuda') for k in range(8)]\n"
+    "out = {}\n"
+    "for mode in (False, True, 2):\n"
+    "    g = DiffGenerator(Fraction(24, 1), 10, 10, batch_frames=4)\n"
+    "    for s, d in pairs[:4]:  # (one untimed batch first: the first launch of a kernel in a process loads its code object)\n"
+    "        g.diff_frame(s, d, 1, 1)\n"
+    "    g.sync()\n"
+    "    g.set_timing(mode)\n"
+    "    for rep in range(3):\n"
+    "        for s, d in pairs:\n"
+    "            g.diff_frame(s, d, 1, 1)\n"
+    "    g.sync()\n"
+    "    st = g.stats()\n"
+    "    kt = g.kernel_times() if mode is True else {}\n"
+    "    out[str(mode)] = (hashlib.sha256(format_tbl(g.finish())).hexdigest(), st.ms_chain, st.chain_batches, sum(v[0] for v in kt.values()))\n"
+    "    g.close()\n"
+    "print(json.dumps(out))\n"
+)
+
+
 def test_chain_timing_brackets_a_batch_and_changes_nothing():
     """g1s_diff_set_timing(g, 2): one pair of HIP events around a batch's whole chain of kernels (bench.py's roofline.frac).
     Every timed batch is counted, the bracket is no longer than the sum of the per-kernel event pairs of the same batches
-    (each of which puts a barrier packet between two launches), and the table is the untimed job's."""
-    from fractions import Fraction
-
-    from grav1synth_amd.diff import DiffGenerator, format_tbl
-    from grav1synth_amd.synth import SynthSpec, make_pair
-
-    spec = SynthSpec(1280, 704, 10)
-    pairs = [make_pair(spec, k, device="cuda") for k in range(8)]
-    out = {}
-    for mode in (False, True, 2):
-        g = DiffGenerator(Fraction(24, 1), 10, 10, batch_frames=4)
-        for s, d in pairs[:4]:  # (one untimed batch first: the first launch of a kernel in a process loads its code object)
-            g.diff_frame(s, d, 1, 1)
-        g.sync()
-        g.set_timing(mode)
-        for rep in range(3):
-            for s, d in pairs:
-                g.diff_frame(s, d, 1, 1)
-        g.sync()
-        st = g.stats()
-        kt = g.kernel_times() if mode is True else {}
-        out[mode] = (format_tbl(g.finish()), st.ms_chain, st.chain_batches, sum(v[0] for v in kt.values()))
-        g.close()
-    assert out[False][0] == out[True][0] == out[2][0]
+    (each of which puts a barrier packet between two launches), and the table is the untimed job's.  In its own interpreter
+    like everything here, which is also where bench.py takes this reading: in the suite's process, behind the other files'
+    tests, the six brackets read 1.23 ms where a fresh process reads 0.56 ms (per-kernel sum 0.76 ms in both)."""
+    out = json.loads(_run(_CHAIN_CODE, {}))
+    out = {False: out["False"], True: out["True"], 2: out["2"]}
+    assert len(out[False][0]) == 64 and out[False][0] == out[True][0] == out[2][0]
     assert out[False][2] == 0 and out[True][2] == 0, "only set_timing(2) counts chain batches"
     assert out[2][2] == 6 and out[2][1] > 0.0
     assert out[2][1] < out[True][3] * 1.10, (out[2][1], out[True][3])

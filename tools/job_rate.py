@@ -3,7 +3,6 @@
 (for timing experiments whose switches may leave the results wrong)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from fractions import Fraction
 import torch
 from grav1synth_amd.diff import DiffGenerator

@@ -15,7 +15,6 @@ lib = os.path.join(ROOT, "grav1synth_amd", "libg1s_v_lprof.so")
 if not os.path.exists(lib):  # (no profiling build: the job's rate and cores only)
     lib = os.path.join(ROOT, "grav1synth_amd", "libg1s_diff.so")
 os.environ["G1S_LIB"] = lib
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from fractions import Fraction  # noqa: E402
 
 import torch  # noqa: E402

@@ -4,7 +4,6 @@ the time its stream reached it and the time the stream reached the next mark (= 
 the host's submit times; prints the batches in the middle of the job."""
 import os, sys, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 path = os.environ.setdefault("G1S_TRACE", "/tmp/g1s_trace.txt")
 if os.path.exists(path):
     os.remove(path)
