@@ -52,20 +52,40 @@ constexpr int kK3Chunks = 48;
 // Both are bit-exact against the oracle; tests/test_gpu_selfcheck.py compares them with each other.  (Rounds 1 and 2's chains --
 // the lag-structured v_dot4 kernels behind the pixel pass K0, K0's planes in front of the matrix-core kernel, the 32x32x32 form
 // of the fused pass -- were removed in round 4: git history)
-// timing experiments: G1S_DBG_SKIP=name[,name...] leaves kernels out (wrong results; never set in tests or bench lines)
-bool dbg_skip(const char *name) {
-  static const std::string v = getenv("G1S_DBG_SKIP") ? std::string(",") + getenv("G1S_DBG_SKIP") + "," : std::string();
-  return !v.empty() && v.find(std::string(",") + name + ",") != std::string::npos;
-}
-int k3_mode() {
-  static const int v = [] {
-    const char *e = getenv("G1S_K3");
-    if (e && std::strcmp(e, "stream") == 0) return 3;
-    return 4;
+//
+// The process-wide switches: read once, when the library first asks for one.  Every one selects an arrangement that gives the
+// same records as the default, and is here because a test, bench.py or a measurement tool sets it.
+// (Read at every call instead, where they are used: G1S_F_WGS, G1S_W_WGS[_C], G1S_F_REUSE; per generator: G1S_LATEST.)
+struct Switches {
+  bool wide;        // G1S_K3 is not "stream": the wide chain, the stream chain where it does not serve (tests, bench.py)
+  bool w_off;       // G1S_W_OFF: the wide chain serves nothing while its buffers and zero fills stay (tests)
+  bool one_stream;  // G1S_ONE_STREAM: every kernel of a batch on the main stream, no deferred back half (tests, profiling tools)
+  bool no_defer;    // G1S_NO_DEFER: a batch's back half is queued with its own front half (tests)
+  bool side2;       // G1S_SIDE2=1: a second side stream, the finder chains of the odd slots on it (tests; no gain: profiles/r03b)
+  bool w_aside;     // G1S_W_ASIDE: the wide chain's chroma launch and what follows on the copy stream, round 3's placement (tests)
+  bool f_serial;    // G1S_F_SERIAL: the stream chain's chroma launch stays on the main stream (tests)
+  bool d2h_sync;    // G1S_D2H_SYNC: launch_back waits for the batch's copy (profiling tools, with G1S_ONE_STREAM)
+  int w_rev;        // G1S_W_REV: bit 0 the luma launch, bit 1 the chroma launch of the wide chain walk the frames last to first (tests)
+  int k1_literal;   // G1S_K1_LITERAL=1|2: the finder evaluates every block literally, a lane / a wave a block (tests)
+};
+const Switches &switches() {
+  static const Switches s = [] {
+    Switches v;
+    const char *k3 = getenv("G1S_K3");
+    v.wide = !(k3 && std::strcmp(k3, "stream") == 0);
+    v.w_off = getenv("G1S_W_OFF") != nullptr;
+    v.one_stream = getenv("G1S_ONE_STREAM") != nullptr;
+    v.no_defer = getenv("G1S_NO_DEFER") != nullptr;
+    v.side2 = getenv("G1S_SIDE2") && atoi(getenv("G1S_SIDE2")) != 0;
+    v.w_aside = getenv("G1S_W_ASIDE") != nullptr;
+    v.f_serial = getenv("G1S_F_SERIAL") != nullptr;
+    v.d2h_sync = getenv("G1S_D2H_SYNC") != nullptr;
+    v.w_rev = getenv("G1S_W_REV") ? atoi(getenv("G1S_W_REV")) : 0;
+    v.k1_literal = getenv("G1S_K1_LITERAL") ? atoi(getenv("G1S_K1_LITERAL")) : 0;
+    return v;
   }();
-  return v;
+  return s;
 }
-bool use_wide() { return k3_mode() == 4;}
 constexpr int kMTargetWgs = 1024;  // accumulation workgroups per launch: 4 per CU, one round
 // workgroups per frame for a launch of B frames: enough to fill the chip, and few enough units each for int32.
 // kind 0: the luma launch, 1: the chroma launch.  The luma launch likes workgroups of ~64 units of the list (4 096 - 6 144
@@ -74,12 +94,10 @@ constexpr int kMTargetWgs = 1024;  // accumulation workgroups per launch: 4 per 
 int m_wgs_per_frame(int nunits, int B, int kind = 1) {
   const int gmin = (nunits + (kMMaxUnits - 16) - 1) / (kMMaxUnits - 16);  // (two lists, each dealt with its own rounding)
   const char *e = getenv("G1S_F_WGS");  // tuning / test aid (read at every call: a test sets it for its own generator)
-  const char *el = kind == 0 ? getenv("G1S_F_WGS_L") : nullptr;  // ... the luma launch alone
   // (at least 32 workgroups to a frame: 64-frame launches are two resident rounds)
   int target = std::max(kMTargetWgs, 32 * B);
   if (kind == 0) target = std::max(target, std::min(64 * B, (int)((long long)B * nunits / 64)));
   if (e) target = std::max(8, atoi(e));
-  if (el) target = std::max(8, atoi(el));
   return (std::max(gmin, (target + B - 1) / std::max(B, 1)) + 7) & ~7;  // (a multiple of 8: workgroup b of a frame on XCD b % 8)
 }
 
@@ -338,15 +356,10 @@ struct StreamSet {
   // chains per frame and twice as long next to the accumulation launches as alone -- on ONE stream, with the blobs' copy behind
   // it, a batch's half would only start when the half of the batch before had been copied out (period >= 1 040 us at 4K)
   hipStream_t latest = nullptr, latest2 = nullptr;
-  hipStream_t mom = nullptr;  // (G1S_MOM_STREAM: a tuning aid)
-  hipStream_t coread = nullptr;  // (G1S_DBG_COREAD: a measurement aid)
-  hipEvent_t coread_go = nullptr;
   hipEvent_t latest_done[kSlots] = {};
   int prio_side = 0;
   hipEvent_t kernels_done[kSlots] = {};
   hipEvent_t mask_done[kSlots] = {};
-  hipEvent_t pix_done[kSlots] = {};
-  hipEvent_t k0_done[kSlots] = {};
   hipEvent_t table_done[kSlots] = {};
 };
 std::vector<StreamSet> g_stream_cache;
@@ -371,23 +384,15 @@ bool acquire_streams(int device, StreamSet &out) {
   // the device half's) are made when they are first needed.
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);  // numerically lower = more urgent
-  if (const char *e = getenv("G1S_PRIO")) {  // tuning aid: 1 = the main stream outranks the side stream, 2 = no priorities
-    const int m = atoi(e);
-    if (m == 1) std::swap(prio_lo, prio_hi);
-    else if (m == 2) prio_lo = prio_hi = (prio_lo + prio_hi) / 2;
-  }
-  static const bool want_flat2 = getenv("G1S_SIDE2") && atoi(getenv("G1S_SIDE2")) != 0;
   out.prio_side = prio_hi;
   bool ok = hipStreamCreateWithPriority(&out.compute, hipStreamNonBlocking, prio_lo) == hipSuccess &&
             hipStreamCreateWithFlags(&out.copy, hipStreamNonBlocking) == hipSuccess &&
             hipStreamCreateWithPriority(&out.flat, hipStreamNonBlocking, prio_hi) == hipSuccess &&
-            (!want_flat2 || hipStreamCreateWithPriority(&out.flat2, hipStreamNonBlocking, prio_hi) == hipSuccess) &&
+            (!switches().side2 || hipStreamCreateWithPriority(&out.flat2, hipStreamNonBlocking, prio_hi) == hipSuccess) &&
             hipStreamCreateWithFlags(&out.upload, hipStreamNonBlocking) == hipSuccess;
   for (int i = 0; i < kSlots && ok; ++i)
     ok = hipEventCreateWithFlags(&out.kernels_done[i], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&out.mask_done[i], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&out.pix_done[i], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&out.k0_done[i], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&out.table_done[i], hipEventDisableTiming) == hipSuccess;
   return ok;
 }
@@ -530,7 +535,10 @@ struct g1s_diff {
   uint64_t frames_copied(uint64_t wait_for);
   int submit(int si);        // front half now; back half now or with the next batch's front half
   int launch_front(int si);  // zero, pixel pass, flat-block finder, window planes, area lists
-  int launch_back(int si);   // accumulation kernels, records D2H, hand-over to the drainer
+  int launch_back(int si);   // accumulation kernels, records D2H, hand-over to the drainer; its parts, in order:
+  int accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);    // (`stream`: by reference, a chain may move
+  int accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);  //  its chroma launch and the rest to ss.copy)
+  int copy_out(Slot &sl, int si, hipStream_t stream);
   static bool wide_gen(const Geom &g);  // the wide chain's general residual form (mixed sample sizes / shifts)
   int flush_pending();
   Geom batch_geom(const Slot &sl) const;
@@ -646,13 +654,13 @@ int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
     o = (o + 15) & ~size_t(15);
     o += 256;  // (a workgroup parks three entries past its slice)
     w_off_lbad = o, w_lbad_bytes = ((size_t)batch * w_ncell[0] + 15) & ~size_t(15), o += w_lbad_bytes;
-    w_bytes = use_wide() ? o : 0;
+    w_bytes = switches().wide ? o : 0;
   }
-  if (use_wide())
+  if (switches().wide)
     for (uint32_t b = 1; b <= batch; ++b)
       m_wg_cap = std::max(m_wg_cap, (size_t)b * std::max(w_wgs_per_frame(w_ncell[0], (int)b, 0), w_wgs_per_frame(std::max(w_ncell[1], 1), (int)b, 1)));
   const size_t mpart_bytes2 = sizeof(long long) * 3 * kMRec * m_wg_cap;
-  const size_t lplane_bytes = (size_t)std::max(m_lframe, use_wide() ? w_lframe : 0u) * batch;
+  const size_t lplane_bytes = (size_t)std::max(m_lframe, switches().wide ? w_lframe : 0u) * batch;
   slot_key = SlotKey{device, sizeof(FramePlanes) * batch, L.size * batch, (size_t)g.nblocks * batch,
                      partial_bytes, defer_bytes, frame_bytes * batch, k0_bytes, pgl_bytes, mu_bytes + w_bytes, mpart_bytes2, lplane_bytes,
                      g.W, g.H, g.xdec, g.ydec, g.nplanes};
@@ -824,8 +832,6 @@ Geom g1s_diff::batch_geom(const Slot &sl) const {
 int g1s_diff::submit(int si) {
   Slot &sl = slots[si];
   if (sl.count == 0) return G1S_OK;
-  static const bool one_stream = getenv("G1S_ONE_STREAM") != nullptr;  // debugging aid
-  static const bool no_defer = getenv("G1S_NO_DEFER") != nullptr;     // debugging aid
   {
     std::lock_guard<std::mutex> lk(dm);
     slot_busy[si] = true;  // until the drainer has folded it
@@ -841,7 +847,7 @@ int g1s_diff::submit(int si) {
     if (rc) return rc;
     trace_host("back queued", prev);
   }
-  if (one_stream || no_defer || timing || !ss.flat) {
+  if (switches().one_stream || switches().no_defer || timing || !ss.flat) {
     rc = flush_pending();
     if (rc) return rc;
   }
@@ -866,31 +872,17 @@ int g1s_diff::launch_front(int si) {
   Slot &sl = slots[si];
   const uint32_t B = sl.count;
   Geom g = batch_geom(sl);
-  static const bool one_stream = getenv("G1S_ONE_STREAM") != nullptr;  // debugging aid
-  hipStream_t stream = ss.compute;                                        // main stream (shadows the member)
-  // Two side streams, a batch's chain on the one of its slot's parity: the latency-bound tail of a chain (certify, the
-  // literal blocks, select, unit lists) then runs next to the moments kernel of the batch after it -- one waits on dependent
-  // loads, the other streams through HBM -- instead of in front of it (G1S_SIDE2=1; the timeline shows them overlap either way)
-  static const bool side2 = getenv("G1S_SIDE2") && atoi(getenv("G1S_SIDE2")) != 0;  // (measured: no gain, profiles/r03b; off)
-  hipStream_t fstream = (one_stream || timing || !ss.flat) ? stream : ((si & 1) && side2 && ss.flat2 ? ss.flat2 : ss.flat);  // per-kernel timing: one stream
-  // the pixel pass of round 1's chain (K0) runs on the main stream; the fused pass has no K0: its only pixel pass before
-  // the mask is the finder's luma-source moments kernel, which joins the finder chain on the side stream and runs next to
-  // the accumulation of the batch before
+  hipStream_t stream = ss.compute;  // main stream (shadows the member)
+  // The finder chain -- the moments kernel (the only pass over the pixels in front of the mask) and the small latency-bound
+  // kernels behind it -- runs on the side stream, next to the accumulation of the batch before; per-kernel timing and
+  // G1S_ONE_STREAM: on the main stream.
   // (measured and dropped: k1_moments on the main stream in front of the accumulation of the batch before, the rest of the
-  //  finder chain beside that accumulation: -3 to -10 % at 4K, +11 % at 1080p, -4 % at 8K; profiles/r04_streams.txt)
-  hipStream_t pstream = fstream;
-  // G1S_MOM_STREAM=1|2 (tuning aid): k1_moments on a stream of its own in the main stream's priority class (1) / the default
-  // class (2), the latency-bound rest of the finder chain alone on the high-priority side stream
-  static const int mom_mode = getenv("G1S_MOM_STREAM") ? atoi(getenv("G1S_MOM_STREAM")) : 0;
-  if (mom_mode && fstream != stream) {
-    if (!ss.mom) {
-      int plo = 0, phi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-      if (mom_mode == 1) HIP_TRY(hipStreamCreateWithPriority(&ss.mom, hipStreamNonBlocking, plo));
-      else HIP_TRY(hipStreamCreateWithFlags(&ss.mom, hipStreamNonBlocking));
-    }
-    pstream = ss.mom;
-  }
+  //  finder chain beside that accumulation: -3 to -10 % at 4K, +11 % at 1080p, -4 % at 8K; profiles/r04_streams.txt.
+  //  k1_moments on a stream of its own: profiles/r05o_streams.txt)
+  // G1S_SIDE2=1: two side streams, a batch's chain on the one of its slot's parity: the latency-bound tail of a chain (certify,
+  // the literal blocks, select, unit lists) then runs next to the moments kernel of the batch after it -- one waits on dependent
+  // loads, the other streams through HBM -- instead of in front of it (the timeline shows them overlap either way)
+  hipStream_t fstream = (switches().one_stream || timing || !ss.flat) ? stream : ((si & 1) && switches().side2 && ss.flat2 ? ss.flat2 : ss.flat);
   // the frame table: pinned host copy -> device, on the upload stream (idle: done long before the main
   // stream gets here); per-kernel timing / one-stream mode: in line
   FrameTable ft;
@@ -920,7 +912,7 @@ int g1s_diff::launch_front(int si) {
     z.ndw[1] = 3 * (uint32_t)batch;
     z.ptr[3] = reinterpret_cast<uint32_t *>(sl.d_mu) + (size_t)batch * m_nunits * kMUnitDwords + 3 * (size_t)batch;  // deferred-block flags
     z.ndw[3] = (uint32_t)(m_only_bytes / 4);
-    if (use_wide() && sl.d_wu) {
+    if (switches().wide && sl.d_wu) {
       z.ptr[6] = reinterpret_cast<uint32_t *>(sl.d_wu + w_off_lbad);  // luma units whose L left int8
       z.ndw[6] = (uint32_t)(w_lbad_bytes / 4);
     }
@@ -934,40 +926,32 @@ int g1s_diff::launch_front(int si) {
   if (up != stream) {
     HIP_TRY(hipEventRecord(ss.table_done[si], up));
     HIP_TRY(hipStreamWaitEvent(stream, ss.table_done[si], 0));
-    if (pstream != stream) HIP_TRY(hipStreamWaitEvent(pstream, ss.table_done[si], 0));
+    HIP_TRY(hipStreamWaitEvent(fstream, ss.table_done[si], 0));  // (the table goes by the upload stream only when the finder chain has a side stream)
   }
-  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[0], pstream));
-  // (the fused pass serves every format; round 1's chain has no structured path for 4:4:0)
+  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[0], fstream));
   {
     // flat-block features: integer moments + certified evaluation; the literal f64 kernel only for
     // the blocks the certificate leaves open (G1S_K1_LITERAL=1 / g1s_diff_set_flat_finder: for every block)
-    static const int env_literal = getenv("G1S_K1_LITERAL") ? atoi(getenv("G1S_K1_LITERAL")) : 0;
-    const int literal_mode = flat_literal ? flat_literal : env_literal;
+    const int literal_mode = flat_literal ? flat_literal : switches().k1_literal;
     const int force_literal = literal_mode ? 1 : 0;
     int32_t *mom = sl.d_k1;
-    bool pix_recorded = false;
     CertifyLists cl;
     cl.list = reinterpret_cast<uint32_t *>(sl.d_k1) + (size_t)g.nblocks * batch * kMomInts;
     cl.count = cl.list + (size_t)g.nblocks * batch;
     cl.global = literal_mode == 0 ? 1 : 0;  // (the default chain: one sequence for the launch; "every block literally": per-frame lists)
     {
       // the finder's moments of the luma source: the only pass over pixels that are not in a flat block's tile
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[5], pstream));
+      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[5], fstream));
       {  // (also when every block is evaluated literally: the record's luma_sum comes from the moments)
         const dim3 mg((g.nblocks + 7) / 8, B);
-        kmark(sl, pstream, g.src_bps == 1 ? "k1_moments<1>" : "k1_moments<2>");
-        if (dbg_skip("moments")) {
-        } else if (g.src_bps == 1) hipLaunchKernelGGL(k1_moments<1>, mg, dim3(256), 0, pstream, ft, g, mom);
-        else hipLaunchKernelGGL(k1_moments<2>, mg, dim3(256), 0, pstream, ft, g, mom);
+        kmark(sl, fstream, g.src_bps == 1 ? "k1_moments<1>" : "k1_moments<2>");
+        if (g.src_bps == 1) hipLaunchKernelGGL(k1_moments<1>, mg, dim3(256), 0, fstream, ft, g, mom);
+        else hipLaunchKernelGGL(k1_moments<2>, mg, dim3(256), 0, fstream, ft, g, mom);
       }
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[4], pstream));
-    }
-    if (pstream != fstream) {  // the finder chain: on the side stream, behind the pixel pass (its luma half)
-      if (!pix_recorded) HIP_TRY(hipEventRecord(ss.pix_done[si], pstream));
-      HIP_TRY(hipStreamWaitEvent(fstream, ss.pix_done[si], 0));
+      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[4], fstream));
     }
     kmark(sl, fstream, "k1_certify");
-    if (!dbg_skip("certify")) hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
+    hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
                        sl.d_records, sl.d_flags, cl, force_literal);
     kmark(sl, fstream, literal_mode == 1 ? "k1_flat_features" : "k1_flat_block");
     if (literal_mode == 1) {  // every block: one lane per block
@@ -978,7 +962,7 @@ int g1s_diff::launch_front(int si) {
       else
         hipLaunchKernelGGL((k1_flat_features<2, true>), grid, dim3(64), 0, fstream, ft, g, fc, d_lut, sl.d_records, sl.d_flags,
                            (const uint32_t *)cl.list, (const uint32_t *)cl.count);
-    } else if (!dbg_skip("flatblock")) {  // the few blocks the certificate leaves open (mode 2, a test aid: every block): one wave per block
+    } else {  // the few blocks the certificate leaves open (mode 2, a test aid: every block): one wave per block
       dim3 grid(kFbGrid);
 #define G1S_FB(BP, GL) hipLaunchKernelGGL((k1_flat_block<BP, GL>), grid, dim3(64), 0, fstream, ft, g, fc, d_lut, sl.d_records, sl.d_flags, \
                                           (const uint32_t *)cl.list, (const uint32_t *)cl.count, (int)B)
@@ -1007,7 +991,7 @@ int g1s_diff::launch_front(int si) {
   }
   kmark(sl, fstream, w_lists ? "k2w_select_units" : "k2_flat_select");
   if (w_lists) hipLaunchKernelGGL(k2w_select_units, dim3(B, g.nplanes == 3 ? 2 : 1), dim3(kK2Threads), 0, fstream, g, sl.d_records, (const uint8_t *)sl.d_flags, wup);
-  else if (!dbg_skip("k2")) hipLaunchKernelGGL(k2_flat_select, dim3(B), dim3(kK2Threads), 0, fstream, g, sl.d_records, sl.d_flags);
+  else hipLaunchKernelGGL(k2_flat_select, dim3(B), dim3(kK2Threads), 0, fstream, g, sl.d_records, sl.d_flags);
   if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[2], fstream));
   if (!w_lists) {
     // the unit lists (chunks with a flat block) need the flat mask (the wide chain: k2w_select_units has built them)
@@ -1024,9 +1008,7 @@ int g1s_diff::launch_front(int si) {
 // the wide chain serves: equal sample widths, every plane's rows 16-byte aligned, whole 8-sample words in every plane,
 // (unaligned planes, odd widths and mixed depths run the stream chain)
 bool g1s_diff::wide_ok(const Geom &g) const {
-  if (!use_wide()) return false;
-  static const bool off = getenv("G1S_W_OFF") != nullptr;  // debugging aid
-  if (off) return false;
+  if (!switches().wide || switches().w_off) return false;
   if (g.lag < 1) return false;
   // inputs of one sample size and one narrowing shift <= 4: the residual in place (w_residual); any other pair of depths: the
   // general form (w_residual_gen), built for 4:2:0 and for frames without chroma planes (the other subsamplings of such a pair
@@ -1043,8 +1025,6 @@ bool g1s_diff::wide_gen(const Geom &g) { return g.src_bps != g.den_bps || g.src_
 
 MParams g1s_diff::make_mparams(const Slot &sl) const {
   MParams mp;
-  // (the fused pass finds the residuals outside int8 itself; K0 flags them per block)
-  mp.bad = nullptr;  // (no pixel pass flags residuals outside int8: the accumulation launches find them themselves)
   mp.units = reinterpret_cast<uint32_t *>(sl.d_mu);
   mp.unit_count = mp.units + (size_t)batch * m_nunits * kMUnitDwords;
   mp.only_any = mp.unit_count + 2 * batch;
@@ -1054,55 +1034,46 @@ MParams g1s_diff::make_mparams(const Slot &sl) const {
   return mp;
 }
 
-int g1s_diff::launch_back(int si) {
-  Slot &sl = slots[si];
+// the wide chain (k3w.hip.h): luma launch (leaves L behind), chroma launch, k3w_tail = the reducer + the exact kernel for
+// deferred blocks
+int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
   const uint32_t B = sl.count;
-  Geom g = batch_geom(sl);
-  static const bool one_stream = getenv("G1S_ONE_STREAM") != nullptr;  // debugging aid
-  hipStream_t stream = ss.compute;
-  const bool side = !(one_stream || sl.timed || !ss.flat);
-  const bool acc_aside = false;
-  if (side) HIP_TRY(hipStreamWaitEvent(stream, ss.mask_done[si], 0));  // the mask, the unit lists
   FrameTable ft;
   ft.f = reinterpret_cast<const FramePlanes *>(sl.d_planes);  // (uploaded by the front half)
-  if (wide_ok(g)) {
-    // the wide chain (k3w.hip.h): luma launch (leaves L behind), chroma launch, the reducer, the exact kernel for deferred blocks
-    const MParams mp = make_mparams(sl);
-    const bool chroma = g.nplanes == 3;
-    WParams wq;
-    wq.ft = ft;
-    wq.records = sl.d_records;
-    wq.partials = mp.partials;
-    wq.only = mp.only;
-    wq.only_any = mp.only_any;
-    wq.lbad = sl.d_wu + w_off_lbad;
-    wq.lplane = sl.d_lplane;
-    wq.lpitch = w_lpitch;
-    wq.lframe_bytes = w_lframe;
-    wq.ncell_y = w_ncell[0];
-    wq.gx_y = w_gx[0];
-    wq.frames = (int)B;
-    static const int w_dbg = getenv("G1S_W_DBG") ? atoi(getenv("G1S_W_DBG")) : 0;  // timing experiments (a -DG1S_W_DBG_BUILD library)
-    wq.dbg = w_dbg;
-    static const int w_rev = getenv("G1S_W_REV") ? atoi(getenv("G1S_W_REV")) : 0;  // tuning aid: bit 0 the luma launch, bit 1 the chroma launch walk the frames last to first
-    int Gk[2] = {w_wgs_per_frame(w_ncell[0], (int)B, 0), w_wgs_per_frame(std::max(w_ncell[1], 1), (int)B, 1)};
-    for (int k = 0; k < 2; ++k) {
-      if ((size_t)Gk[k] * B <= m_wg_cap) continue;
-      // the environment (G1S_W_WGS / G1S_W_WGS_C) changed after the slots were sized: what the slots hold -- but never fewer
-      // workgroups than the int32 accumulators and the parked entries of a workgroup allow
-      Gk[k] = (int)(m_wg_cap / B) & ~7;
-      const int ncell_k = k == 0 ? w_ncell[0] : std::max(w_ncell[1], 1), cap_k = k == 1 ? kWMaxUnitsC : kWMaxUnits;
-      if (Gk[k] <= 0 || Gk[k] < (ncell_k + cap_k - 1) / cap_k)
-        return fail(G1S_ERR_STATE, "the wide launches' workgroup count was raised (G1S_W_WGS / G1S_W_WGS_C) after this generator's buffers were sized");
-    }
-    const int G_cap = std::max(Gk[0], Gk[1]);
-    wq.wg_cap = G_cap;
-    auto set_kind = [&](int k) {
-      wq.units = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_units[k]);
-      wq.count = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_count) + k;  // (stride 2: see the kernel)
-      wq.ncell = w_ncell[k];
-      wq.wgs = Gk[k];
-    };
+  const MParams mp = make_mparams(sl);
+  const bool chroma = g.nplanes == 3;
+  WParams wq;
+  wq.ft = ft;
+  wq.records = sl.d_records;
+  wq.partials = mp.partials;
+  wq.only = mp.only;
+  wq.only_any = mp.only_any;
+  wq.lbad = sl.d_wu + w_off_lbad;
+  wq.lplane = sl.d_lplane;
+  wq.lpitch = w_lpitch;
+  wq.lframe_bytes = w_lframe;
+  wq.ncell_y = w_ncell[0];
+  wq.gx_y = w_gx[0];
+  wq.frames = (int)B;
+  const int w_rev = switches().w_rev;
+  int Gk[2] = {w_wgs_per_frame(w_ncell[0], (int)B, 0), w_wgs_per_frame(std::max(w_ncell[1], 1), (int)B, 1)};
+  for (int k = 0; k < 2; ++k) {
+    if ((size_t)Gk[k] * B <= m_wg_cap) continue;
+    // the environment (G1S_W_WGS / G1S_W_WGS_C) changed after the slots were sized: what the slots hold -- but never fewer
+    // workgroups than the int32 accumulators and the parked entries of a workgroup allow
+    Gk[k] = (int)(m_wg_cap / B) & ~7;
+    const int ncell_k = k == 0 ? w_ncell[0] : std::max(w_ncell[1], 1), cap_k = k == 1 ? kWMaxUnitsC : kWMaxUnits;
+    if (Gk[k] <= 0 || Gk[k] < (ncell_k + cap_k - 1) / cap_k)
+      return fail(G1S_ERR_STATE, "the wide launches' workgroup count was raised (G1S_W_WGS / G1S_W_WGS_C) after this generator's buffers were sized");
+  }
+  const int G_cap = std::max(Gk[0], Gk[1]);
+  wq.wg_cap = G_cap;
+  auto set_kind = [&](int k) {
+    wq.units = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_units[k]);
+    wq.count = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_count) + k;  // (stride 2: see the kernel)
+    wq.ncell = w_ncell[k];
+    wq.wgs = Gk[k];
+  };
 #define G1S_WG(KIND, BP, SX, SY, BD, GEN)                                                                              \
   do {                                                                                                                 \
     constexpr int lds_ = w_lds_bytes(KIND, WShape<KIND, SX, SY>::BH);                                                  \
@@ -1137,130 +1108,75 @@ int g1s_diff::launch_back(int si) {
     else if (g.ydec == 1) G1S_WB(KIND, 0, 1);        \
     else G1S_WB(KIND, 0, 0);                         \
   } while (0)
-    const bool gen = wide_gen(g);
-    // G1S_DBG_COREAD=1|2|3 (a measurement aid, profiles/r06b_coread.txt): a pass over the batch's luma source by a kernel of few
-    // registers on a stream of its own, started with the luma launch (1), the chroma launch (2) or both (3): what a finder pass
-    // costs UNDER an accumulation launch when one of its waves fits beside the launch's four on a SIMD -- three times its own length
-    static const int coread = getenv("G1S_DBG_COREAD") ? atoi(getenv("G1S_DBG_COREAD")) : 0;
-    auto coread_with_next_launch = [&]() -> int {
-      if (!ss.coread) {
-        HIP_TRY(hipStreamCreateWithFlags(&ss.coread, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ss.coread_go, hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventRecord(ss.coread_go, stream));
-      HIP_TRY(hipStreamWaitEvent(ss.coread, ss.coread_go, 0));
-      hipLaunchKernelGGL(k_dbg_coread, dim3((g.nblocks + 7) / 8, B), dim3(256), 0, ss.coread, ft, g, sl.d_k1);
-      return G1S_OK;
-    };
-    if (coread & 1) {
-      const int rc = coread_with_next_launch();
-      if (rc) return rc;
+  const bool gen = wide_gen(g);
+  if (!chroma) {
+    if (gen) G1S_WGEN(0, -1, -1);
+    else G1S_WB(0, -1, -1);
+  } else {
+    if (gen) G1S_WGEN(0, 1, 1);
+    else G1S_WK(0);
+    // The chroma launch stays on the main stream behind the luma launch.  Round 3's chain moved it (and what follows) to the
+    // copy stream, next to the luma launch of the batch after; with this chain both launches fill every register of the
+    // chip and only stretch each other: serial is +2 - 5 % on the 4K job, +10 % at 8K 4:4:4 (profiles/r04_streams.txt).
+    if (side && switches().w_aside) {  // the chroma launch and what follows: next to the luma launch of the batch after
+      HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
+      HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
+      stream = ss.copy;
     }
-    if (!chroma) {
-      if (gen) G1S_WGEN(0, -1, -1);
-      else G1S_WB(0, -1, -1);
-    } else {
-      if (gen) G1S_WGEN(0, 1, 1);
-      else G1S_WK(0);
-      if (coread & 2) {
-        const int rc = coread_with_next_launch();
-        if (rc) return rc;
-      }
-      // The chroma launch stays on the main stream behind the luma launch.  Round 3's chain moved it (and what follows) to the
-      // copy stream, next to the luma launch of the batch after; with this chain both launches fill every register of the
-      // chip and only stretch each other: serial is +2 - 5 % on the 4K job, +10 % at 8K 4:4:4 (profiles/r04_streams.txt).
-      static const bool chroma_aside = getenv("G1S_W_ASIDE") != nullptr;  // tuning aid: round 3's placement
-      if (side && chroma_aside) {  // the chroma launch and what follows: next to the luma launch of the batch after
-        HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-        HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
-        stream = ss.copy;
-      }
-      if (gen) G1S_WGEN(1, 1, 1);
-      else G1S_WK(1);
-    }
+    if (gen) G1S_WGEN(1, 1, 1);
+    else G1S_WK(1);
+  }
 #undef G1S_WGEN
 #undef G1S_WG
 #undef G1S_WK
 #undef G1S_WB
 #undef G1S_W
-    {
-      // debugging aid (G1S_DBG_ONLY=1): how many flat blocks the accumulation launches left to the exact kernel
-      static const bool count_only = getenv("G1S_DBG_ONLY") != nullptr;
-      if (count_only) {
-        std::vector<uint8_t> h(m_only_bytes);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), mp.only, m_only_bytes, hipMemcpyDeviceToHost);
-        size_t n[3] = {0, 0, 0};
-        for (uint32_t f = 0; f < B; ++f)
-          for (int c = 0; c < 3; ++c)
-            for (int b = 0; b < g.nblocks; ++b) n[c] += h[((size_t)f * 3 + c) * g.nblocks + b] != 0;
-        fprintf(stderr, "deferred to k3_ar_generic: %zu luma, %zu Cb, %zu Cr blocks of %u frames x %d blocks\n", n[0], n[1], n[2], B, g.nblocks);
-        // ... and what the wide lists hold: units, plain units, units off the plane's interior, flat blocks in them
-        for (int k = 0; k < (chroma ? 2 : 1); ++k) {
-          std::vector<uint32_t> cnt(2 * B), ent((size_t)B * w_ncell[k] * kWEntry);
-          (void)hipMemcpy(cnt.data(), sl.d_wu + w_off_count, cnt.size() * 4, hipMemcpyDeviceToHost);
-          (void)hipMemcpy(ent.data(), sl.d_wu + w_off_units[k], ent.size() * 4, hipMemcpyDeviceToHost);
-          size_t units = 0, plain = 0, border = 0, flat = 0, top = 0, runs = 0;
-          for (uint32_t f = 0; f < B; ++f)
-            for (uint32_t u = 0; u < cnt[2 * f + k]; ++u) {
-              const uint32_t *e = &ent[((size_t)f * w_ncell[k] + u) * kWEntry];
-              ++units, plain += (e[0] >> 24) & 1u, border += !((e[0] >> 25) & 1u), top += (e[0] >> 26) & 1u, runs += !((e[0] >> 22) & 1u);
-              flat += (size_t)__builtin_popcount(e[1]);
-            }
-          fprintf(stderr, "wide list %d: %zu units (%zu cells), %zu plain, %zu off the interior, %zu with a top halo, %zu runs, %zu flat blocks\n", k, units,
-                  (size_t)B * w_ncell[k], plain, border, top, runs, flat);
-        }
-      }
-    }
-    // (the record's block statistics and AR sums: k3_ar_generic adds to / overwrites what the launches and the reduction wrote,
-    //  and the exact kernel reads the frame number relative to the launch: frame0 is 0 here)
-    kmark(sl, stream, "k3w_tail");
-    hipLaunchKernelGGL(k3w_tail, dim3(kWTailParts + std::min(kWTailChunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
-                       sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any, (const long long *)mp.partials, G_cap, Gk[0], Gk[1]);
-  } else {
-    // the fused pass: planes of the flat blocks' tiles -> residuals, block statistics, exact int8 SYRK on the matrix
-    // cores, one partial system per workgroup; the reducer; then the exact int32 kernel for the few blocks next to a
-    // residual outside int8
-    const MParams mp = make_mparams(sl);
-    FParams fq;
-    fq.ft = ft;
-    fq.units = mp.units;
-    fq.unit_count = mp.unit_count;
-    fq.partials = mp.partials;
-    fq.ustats = reinterpret_cast<int32_t *>(mp.only + m_only_bytes);
-    fq.nunits = m_nunits;
-    int G_kind[2] = {m_wgs_per_frame(m_nunits, (int)B, 0), m_wgs_per_frame(m_nunits, (int)B, 1)};  // luma launch, chroma launch
-    for (int &Gk : G_kind)
-      if ((size_t)Gk * B > m_wg_cap) Gk = m_wgs_per_frame(m_nunits, 1 << 20);  // (G1S_F_WGS raised after the slots were sized: the fewest that hold the units)
-    const int G_cap = std::max(G_kind[0], G_kind[1]);
-    int G = G_kind[0];
-    fq.phase_cycles = nullptr;
-    const int cbw = g.nplanes == 3 ? (kBlock >> g.xdec) : 0, cbh = g.nplanes == 3 ? (kBlock >> g.ydec) : 0;
-    fq.lplane = sl.d_lplane;
-    fq.lpitch = m_lpitch;
-    fq.lframe_bytes = m_lframe;
-    static const size_t lds_pad = getenv("G1S_F_LDS_PAD") ? (size_t)atoi(getenv("G1S_F_LDS_PAD")) : 0;  // tuning aid: fewer workgroups to a CU
-    fq.frames = (int)B;
-    fq.wgs = G;
-    fq.wg_cap = G_cap;
-    // units to workgroups: contiguous runs of the lists (measured +2..4 % over round-robin in the pipelined job, although a
-    // kernel alone on the chip is 5 % slower: the runs' loads disturb the kernels next to it less)
-    static const int deal_env = getenv("G1S_F_DEAL") ? atoi(getenv("G1S_F_DEAL")) : 1;  // tuning aid
-    fq.deal = deal_env;
-    { const char *e = getenv("G1S_F_REUSE"); fq.reuse = e ? atoi(e) : 1; }  // test / tuning aid (0: every halo word is read)
-    static const int s_dbg = getenv("G1S_S_DBG") ? atoi(getenv("G1S_S_DBG")) : 0;  // timing experiments: parts of k3s_fused left out (wrong results)
-    fq.dbg = s_dbg;
-    dim3 gr((uint32_t)G * B);
-    const int bpsm = g.src_bps == g.den_bps ? g.src_bps : 0;  // bytes per sample at compile time unless the depths are mixed
-    // two launches: the luma plane (which leaves L behind), then the two chroma planes
-    // (the stream chain is what the wide chain falls back on -- unaligned planes, odd widths, mixed or deep bit depths: ONE
-    //  instantiation per format and launch, sample widths at run time)
+  // (the record's block statistics and AR sums: k3_ar_generic adds to / overwrites what the launches and the reduction wrote,
+  //  and the exact kernel reads the frame number relative to the launch: frame0 is 0 here)
+  kmark(sl, stream, "k3w_tail");
+  hipLaunchKernelGGL(k3w_tail, dim3(kWTailParts + std::min(kWTailChunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
+                     sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any, (const long long *)mp.partials, G_cap, Gk[0], Gk[1]);
+  return G1S_OK;
+}
+
+// the stream chain (k3s.hip.h), what the wide chain falls back on: the fused pass -- planes of the flat blocks' tiles ->
+// residuals, block statistics, exact int8 SYRK on the matrix cores, one partial system per workgroup; the reducer; then the
+// exact int32 kernel for the few blocks next to a residual outside int8
+int g1s_diff::accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
+  const uint32_t B = sl.count;
+  FrameTable ft;
+  ft.f = reinterpret_cast<const FramePlanes *>(sl.d_planes);  // (uploaded by the front half)
+  const MParams mp = make_mparams(sl);
+  FParams fq;
+  fq.ft = ft;
+  fq.units = mp.units;
+  fq.unit_count = mp.unit_count;
+  fq.partials = mp.partials;
+  fq.ustats = reinterpret_cast<int32_t *>(mp.only + m_only_bytes);
+  fq.nunits = m_nunits;
+  int G_kind[2] = {m_wgs_per_frame(m_nunits, (int)B, 0), m_wgs_per_frame(m_nunits, (int)B, 1)};  // luma launch, chroma launch
+  for (int &Gk : G_kind)
+    if ((size_t)Gk * B > m_wg_cap) Gk = m_wgs_per_frame(m_nunits, 1 << 20);  // (G1S_F_WGS raised after the slots were sized: the fewest that hold the units)
+  const int G_cap = std::max(G_kind[0], G_kind[1]);
+  int G = G_kind[0];
+  const int cbw = g.nplanes == 3 ? (kBlock >> g.xdec) : 0, cbh = g.nplanes == 3 ? (kBlock >> g.ydec) : 0;
+  fq.lplane = sl.d_lplane;
+  fq.lpitch = m_lpitch;
+  fq.lframe_bytes = m_lframe;
+  fq.frames = (int)B;
+  fq.wgs = G;
+  fq.wg_cap = G_cap;
+  { const char *e = getenv("G1S_F_REUSE"); fq.reuse = e ? atoi(e) : 1; }  // test / tuning aid (0: every halo word is read)
+  dim3 gr((uint32_t)G * B);
+  // two launches: the luma plane (which leaves L behind), then the two chroma planes
+  // (unaligned planes, odd widths, mixed or deep bit depths: ONE instantiation per format and launch, sample widths at run time)
 #define G1S_FS(CW, CH, PL)                                                                                           \
   do {                                                                                                               \
     static const hipError_t attr_rs = hipFuncSetAttribute(reinterpret_cast<const void *>(&k3s_fused<CW, CH, 0, PL>), \
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);   \
     (void)attr_rs;                                                                                                   \
-    const size_t lds = std::min((size_t)s_lds_bytes(CW, CH, PL) + lds_pad, (size_t)144 * 1024);                      \
+    constexpr size_t lds = s_lds_bytes(CW, CH, PL);                                                                  \
+    static_assert(lds <= 144 * 1024, "the tile buffers fit the LDS the kernel may ask for");                         \
     char kn_[64];                                                                                                    \
     snprintf(kn_, sizeof(kn_), "k3s_fused<%d, %d, %d, %d>", CW, CH, 0, PL);                                          \
     kmark(sl, stream, kn_);                                                                                          \
@@ -1269,148 +1185,147 @@ int g1s_diff::launch_back(int si) {
     gr = dim3((uint32_t)G * B);                                                                                      \
     hipLaunchKernelGGL((k3s_fused<CW, CH, 0, PL>), gr, dim3(kFThreads), lds, stream, g, fq);                         \
   } while (0)
-    // (the chroma launch, the finisher and what follows go to the copy stream -- next to the luma launch of the batch after)
-    static const bool chroma_aside = getenv("G1S_F_SERIAL") == nullptr;  // tuning aid
+  // (the chroma launch, the finisher and what follows go to the copy stream -- next to the luma launch of the batch after)
+  const bool chroma_aside = !switches().f_serial;
 #define G1S_FP(CW, CH)                                                    \
   do {                                                                    \
     G1S_FS(CW, CH, 0);                                                    \
-    if (side && chroma_aside && !acc_aside) {                             \
+    if (side && chroma_aside) {                                           \
       HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));               \
       HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));       \
       stream = ss.copy;                                                   \
     }                                                                     \
     G1S_FS(CW, CH, 1);                                                    \
   } while (0)
-    if (cbw == 0) G1S_FS(0, 0, 0);
-    else if (cbw == 16 && cbh == 16) G1S_FP(16, 16);
-    else if (cbw == 16) G1S_FP(16, 32);
-    else if (cbh == 32) G1S_FP(32, 32);
-    else G1S_FP(32, 16);
+  if (cbw == 0) G1S_FS(0, 0, 0);
+  else if (cbw == 16 && cbh == 16) G1S_FP(16, 16);
+  else if (cbw == 16) G1S_FP(16, 32);
+  else if (cbh == 32) G1S_FP(32, 32);
+  else G1S_FP(32, 16);
 #undef G1S_FP
 #undef G1S_FS
-    kmark(sl, stream, "k3m_finish");
-    if (!dbg_skip("finish")) hipLaunchKernelGGL(k3m_finish, dim3(kMFinishParts * g.nplanes + kMFinishWgs, B), dim3(256), 0, stream, g, mp, G_kind[0], G_kind[1], G_cap,
-                       (const int32_t *)fq.ustats, sl.d_records);
-    {
-      // debugging aid (G1S_DBG_ONLY=1): how many flat blocks the accumulation launches left to the exact kernel
-      static const bool count_only = getenv("G1S_DBG_ONLY") != nullptr;
-      if (count_only) {
-        std::vector<uint8_t> h(m_only_bytes);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), mp.only, m_only_bytes, hipMemcpyDeviceToHost);
-        size_t n[3] = {0, 0, 0};
-        for (uint32_t f = 0; f < B; ++f)
-          for (int c = 0; c < 3; ++c)
-            for (int b = 0; b < g.nblocks; ++b) n[c] += h[((size_t)f * 3 + c) * g.nblocks + b] != 0;
-        fprintf(stderr, "deferred to k3_ar_generic: %zu luma, %zu Cb, %zu Cr blocks of %u frames x %d blocks\n", n[0], n[1], n[2], B, g.nblocks);
-      }
-    }
-    kmark(sl, stream, "k3_ar_generic");
-    if (!dbg_skip("generic"))
-      hipLaunchKernelGGL(k3_ar_generic, dim3(std::min(kK3Chunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
-                         sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any);
+  kmark(sl, stream, "k3m_finish");
+  hipLaunchKernelGGL(k3m_finish, dim3(kMFinishParts * g.nplanes + kMFinishWgs, B), dim3(256), 0, stream, g, mp, G_kind[0], G_kind[1], G_cap,
+                     (const int32_t *)fq.ustats, sl.d_records);
+  kmark(sl, stream, "k3_ar_generic");
+  hipLaunchKernelGGL(k3_ar_generic, dim3(std::min(kK3Chunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
+                     sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any);
+  return G1S_OK;
+}
+
+// the batch's results to the host, on the copy stream behind the tail kernels (the main stream goes straight on to the next
+// batch): the records -- or, when the per-frame half of the fold runs on the device, that half and its blobs
+int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
+  const uint32_t B = sl.count;
+  HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
+  HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
+  if (!device_latest) {
+    HIP_TRY(hipMemcpyAsync(sl.h_records, sl.d_records, L.size * B, hipMemcpyDeviceToHost, ss.copy));
+    HIP_TRY(hipEventRecord(sl.done, ss.copy));
+    return G1S_OK;
   }
+  // the per-frame half of the fold where the records lie: the host gets 27 KB of latest state a frame instead of the record
+  // (the batch's last record still comes back: g1s_diff_last_record)
+  const size_t blob = latest_blob_size(lag), scr = latest_scratch_bytes((uint32_t)L.nblocks);
+  if (sl.latest_cap < blob * batch) {
+    if (sl.d_latest) (void)hipFree(sl.d_latest);
+    if (sl.h_latest) (void)hipHostFree(sl.h_latest);
+    sl.d_latest = sl.h_latest = nullptr;
+    sl.latest_cap = 0;
+    HIP_TRY(hipMalloc((void **)&sl.d_latest, blob * batch));
+    HIP_TRY(hipHostMalloc((void **)&sl.h_latest, blob * batch, hipHostMallocDefault));
+    sl.latest_cap = blob * batch;
+  }
+  if (sl.lscratch_cap < scr * batch) {
+    if (sl.d_lscratch) (void)hipFree(sl.d_lscratch);
+    sl.d_lscratch = nullptr;
+    sl.lscratch_cap = 0;
+    HIP_TRY(hipMalloc((void **)&sl.d_lscratch, scr * batch));
+    sl.lscratch_cap = scr * batch;
+  }
+  LatestJob job{};
+  job.records = sl.d_records;
+  job.L = L;
+  job.blobs = sl.d_latest;
+  job.blob_bytes = blob;
+  job.scratch = sl.d_lscratch;
+  job.scratch_bytes = scr;
+  job.lag = (int)lag;
+  job.n = (int)n;
+  job.nplanes = geom.nplanes;
+  job.W = geom.W;
+  job.H = geom.H;
+  job.xdec = geom.xdec;
+  job.ydec = geom.ydec;
+  job.nbw = geom.nbw;
+  job.nbh = geom.nbh;
+  if (sl.timed) {  // (per-kernel timing: everything on the one stream)
+    kmark(sl, stream, latest_kernel_name());
+    HIP_TRY(launch_latest(job, B, stream));
+    kmark(sl, stream, nullptr);
+    HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
+    HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
+  } else {
+    if (!ss.latest) {
+      // two streams in the main stream's priority class (the least urgent: the kernel fills in; measured 4 % better than the
+      // runtime's default class and than the side stream's, profiles/r05_device_latest.txt)
+      int plo = 0, phi = 0;
+      (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
+      // (made into locals and handed to the stream set -- which goes back to the process-wide cache -- only when ALL of them
+      //  exist: a failure half way must not leave a set that looks complete with a null stream or event in it)
+      hipStream_t made[2] = {nullptr, nullptr};
+      hipEvent_t made_ev[kSlots] = {};
+      bool ok = true;
+      for (hipStream_t &st : made) ok = ok && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, plo) == hipSuccess;
+      for (int i = 0; i < kSlots; ++i) ok = ok && hipEventCreateWithFlags(&made_ev[i], hipEventDisableTiming) == hipSuccess;
+      if (!ok) {
+        for (hipStream_t st : made)
+          if (st) (void)hipStreamDestroy(st);
+        for (hipEvent_t e : made_ev)
+          if (e) (void)hipEventDestroy(e);
+        return fail_hip("the device half's streams / events could not be created");
+      }
+      ss.latest = made[0], ss.latest2 = made[1];
+      for (int i = 0; i < kSlots; ++i) ss.latest_done[i] = made_ev[i];
+    }
+    hipStream_t lst = (si & 1) ? ss.latest2 : ss.latest;  // (why two: StreamSet)
+    HIP_TRY(hipStreamWaitEvent(lst, ss.kernels_done[si], 0));
+    kmark(sl, lst, latest_kernel_name());  // (trace mode)
+    HIP_TRY(launch_latest(job, B, lst));
+    kmark(sl, lst, nullptr);
+    // the blobs' copy: on the copy stream, behind the kernel
+    HIP_TRY(hipEventRecord(ss.latest_done[si], lst));
+    HIP_TRY(hipStreamWaitEvent(ss.copy, ss.latest_done[si], 0));
+  }
+  hipStream_t ls = ss.copy;
+  if (!sl.timed) kmark(sl, ls, "blobs D2H");
+  HIP_TRY(hipMemcpyAsync(sl.h_latest, sl.d_latest, blob * B, hipMemcpyDeviceToHost, ls));
+  HIP_TRY(hipMemcpyAsync(sl.h_records + L.size * (B - 1), sl.d_records + L.size * (B - 1), L.size, hipMemcpyDeviceToHost, ls));
+  if (!sl.timed) kmark(sl, ls, nullptr);
+  HIP_TRY(hipEventRecord(sl.done, ls));
+  return G1S_OK;
+}
+
+int g1s_diff::launch_back(int si) {
+  Slot &sl = slots[si];
+  const Geom g = batch_geom(sl);
+  hipStream_t stream = ss.compute;
+  const bool side = !(switches().one_stream || sl.timed || !ss.flat);
+  if (side) HIP_TRY(hipStreamWaitEvent(stream, ss.mask_done[si], 0));  // the mask, the unit lists
+  // (`stream` comes back as the copy stream when the chain moved its chroma launch and what follows there)
+  int rc = wide_ok(g) ? accumulate_wide(sl, si, g, stream, side) : accumulate_stream(sl, si, g, stream, side);
+  if (rc) return rc;
   kmark(sl, stream, nullptr);
   if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[3], stream));
   HIP_TRY(hipGetLastError());
-  // records D2H on the copy stream (behind the tail kernels): the main stream goes straight on to the next batch
-  HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-  HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
-  if (device_latest) {
-    // the per-frame half of the fold where the records lie: the host gets 27 KB of latest state a frame instead of the record
-    // (the batch's last record still comes back: g1s_diff_last_record)
-    const size_t blob = latest_blob_size(lag), scr = latest_scratch_bytes((uint32_t)L.nblocks);
-    if (sl.latest_cap < blob * batch) {
-      if (sl.d_latest) (void)hipFree(sl.d_latest);
-      if (sl.h_latest) (void)hipHostFree(sl.h_latest);
-      sl.d_latest = sl.h_latest = nullptr;
-      sl.latest_cap = 0;
-      HIP_TRY(hipMalloc((void **)&sl.d_latest, blob * batch));
-      HIP_TRY(hipHostMalloc((void **)&sl.h_latest, blob * batch, hipHostMallocDefault));
-      sl.latest_cap = blob * batch;
-    }
-    if (sl.lscratch_cap < scr * batch) {
-      if (sl.d_lscratch) (void)hipFree(sl.d_lscratch);
-      sl.d_lscratch = nullptr;
-      sl.lscratch_cap = 0;
-      HIP_TRY(hipMalloc((void **)&sl.d_lscratch, scr * batch));
-      sl.lscratch_cap = scr * batch;
-    }
-    LatestJob job{};
-    job.records = sl.d_records;
-    job.L = L;
-    job.blobs = sl.d_latest;
-    job.blob_bytes = blob;
-    job.scratch = sl.d_lscratch;
-    job.scratch_bytes = scr;
-    job.lag = (int)lag;
-    job.n = (int)n;
-    job.nplanes = g.nplanes;
-    job.W = g.W;
-    job.H = g.H;
-    job.xdec = g.xdec;
-    job.ydec = g.ydec;
-    job.nbw = g.nbw;
-    job.nbh = g.nbh;
-    if (sl.timed) {  // (per-kernel timing: everything on the one stream)
-      kmark(sl, stream, latest_kernel_name());
-      HIP_TRY(launch_latest(job, B, stream));
-      kmark(sl, stream, nullptr);
-      HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-      HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
-    } else {
-      if (!ss.latest) {
-        // the main stream's priority class (the least urgent: the kernel fills in; measured 4 % better than the runtime's default
-        // class, profiles/r05_device_latest.txt).  G1S_LATEST_PRIO (tuning aid): 0 the runtime's default class, 1 the main
-        // stream's, 2 the side stream's
-        static const int lp = getenv("G1S_LATEST_PRIO") ? atoi(getenv("G1S_LATEST_PRIO")) : 1;
-        int plo = 0, phi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-        // (made into locals and handed to the stream set -- which goes back to the process-wide cache -- only when ALL of them
-        //  exist: a failure half way must not leave a set that looks complete with a null stream or event in it)
-        hipStream_t made[2] = {nullptr, nullptr};
-        hipEvent_t made_ev[kSlots] = {};
-        bool ok = true;
-        for (hipStream_t &st : made)
-          ok = ok && (lp == 0 ? hipStreamCreateWithFlags(&st, hipStreamNonBlocking) : hipStreamCreateWithPriority(&st, hipStreamNonBlocking, lp == 1 ? plo : phi)) == hipSuccess;
-        for (int i = 0; i < kSlots; ++i) ok = ok && hipEventCreateWithFlags(&made_ev[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-          for (hipStream_t st : made)
-            if (st) (void)hipStreamDestroy(st);
-          for (hipEvent_t e : made_ev)
-            if (e) (void)hipEventDestroy(e);
-          return fail_hip("the device half's streams / events could not be created");
-        }
-        ss.latest = made[0], ss.latest2 = made[1];
-        for (int i = 0; i < kSlots; ++i) ss.latest_done[i] = made_ev[i];
-      }
-      static const bool one_latest = getenv("G1S_LATEST_ONE_STREAM") != nullptr;  // (tuning aid: round 4's placement)
-      hipStream_t lst = (si & 1) && !one_latest ? ss.latest2 : ss.latest;
-      HIP_TRY(hipStreamWaitEvent(lst, ss.kernels_done[si], 0));
-      kmark(sl, lst, latest_kernel_name());  // (trace mode)
-      HIP_TRY(launch_latest(job, B, lst));
-      kmark(sl, lst, nullptr);
-      // the blobs' copy: on the copy stream, behind the kernel
-      HIP_TRY(hipEventRecord(ss.latest_done[si], lst));
-      HIP_TRY(hipStreamWaitEvent(ss.copy, ss.latest_done[si], 0));
-    }
-    hipStream_t ls = ss.copy;
-    if (!sl.timed) kmark(sl, ls, "blobs D2H");
-    HIP_TRY(hipMemcpyAsync(sl.h_latest, sl.d_latest, blob * B, hipMemcpyDeviceToHost, ls));
-    HIP_TRY(hipMemcpyAsync(sl.h_records + L.size * (B - 1), sl.d_records + L.size * (B - 1), L.size, hipMemcpyDeviceToHost, ls));
-    if (!sl.timed) kmark(sl, ls, nullptr);
-    HIP_TRY(hipEventRecord(sl.done, ls));
-  } else {
-    HIP_TRY(hipMemcpyAsync(sl.h_records, sl.d_records, L.size * B, hipMemcpyDeviceToHost, ss.copy));
-    HIP_TRY(hipEventRecord(sl.done, ss.copy));
-  }
+  rc = copy_out(sl, si, stream);
+  if (rc) return rc;
   // profiling aid (G1S_D2H_SYNC=1, with G1S_ONE_STREAM=1): the records copy has ended before the next batch's first kernel
   // starts -- under rocprofv3 the copy is a blit kernel that otherwise shares the chip with k1_moments and doubles its time
   // A timed batch (g1s_diff_set_timing: every kernel between two events, "alone on the chip") waits for it too: the copy of
   // batch N next to the kernels of batch N + 1 costs the luma launch 4 % at 8K, and on some boxes of the pool the event pair of
   // the batch's last kernel read 280 - 500 us instead of 45 - 75 with it in flight (profiles/r04_rot.txt vs r04_hwq.txt).
-  static const bool d2h_sync = getenv("G1S_D2H_SYNC") != nullptr;
-  if (d2h_sync) HIP_TRY(hipStreamSynchronize(ss.copy));
+  if (switches().d2h_sync) HIP_TRY(hipStreamSynchronize(ss.copy));
   else if (sl.timed) HIP_TRY(hipEventSynchronize(sl.done));  // (the copy's end, whichever stream carried it)
   stats.launches_flat_features++;
   stats.launches_flat_select++;
@@ -1693,9 +1608,7 @@ void g1s_diff::release() {
   if (ss.latest2) (void)hipStreamSynchronize(ss.latest2);
   if (ss.flat) (void)hipStreamSynchronize(ss.flat);
   if (ss.flat2) (void)hipStreamSynchronize(ss.flat2);
-  if (ss.mom) (void)hipStreamSynchronize(ss.mom);
   if (ss.upload) (void)hipStreamSynchronize(ss.upload);
-  if (ss.coread) (void)hipStreamSynchronize(ss.coread);
   // (the trace: written when nothing can add to it any more -- the drainer and the folder are joined, the streams idle)
   if (trace) {
     std::lock_guard<std::mutex> lk(trace_mutex);

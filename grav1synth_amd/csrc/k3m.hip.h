@@ -41,7 +41,6 @@ constexpr int kMUnitDwords = 4;   // list entry: [0] chunk | block row << 12 | f
 constexpr int kMMaxUnits = 240;   // units per workgroup: 240 * 2 blocks * 8 steps * 32 samples * 127^2 < 2^31
 
 struct MParams {
-  const uint8_t *bad;     // [batch][2][nblocks]  residual (kind 1: or L) outside int8, when a pixel pass has flagged them; or null
   uint8_t *only;          // [batch][2][nblocks]  flat blocks left to k3_ar_generic (zeroed per batch)
   uint32_t *only_any;     // [batch]
   uint32_t *units;        // [batch][nunits][kMUnitDwords]  (two lists, see k3m_units)
@@ -65,9 +64,8 @@ __device__ __forceinline__ MWin m_unpack(uint32_t w, int lag) {
 }
 
 // ---------------------------------------------------------------------------------
-// k3m_units: per frame, the chunks with a flat block, the windows of their blocks per plane kind, and
-// which of them go to the exact kernel instead.  grid = (ceil(nunits / 256), batch), block = 256;
-// one atomic per wave.
+// k3m_units: per frame, the chunks with a flat block and the windows of their blocks per plane kind.
+// grid = (ceil(nunits / 256), batch), block = 256; one atomic per wave.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k3m_units(Geom g, const uint8_t *__restrict__ records, MParams mp) {
   const int frame = g.frame0 + (int)blockIdx.y;
@@ -117,26 +115,8 @@ __global__ __launch_bounds__(256) void k3m_units(Geom g, const uint8_t *__restri
     if (w.xe <= w.xs || w.ye <= w.ys) w.flat = 0;  // empty window
     if (!w.flat || w.xs != 0 || w.ys != 0 || w.xe != bw || w.ye != bh) plain = false;
     if (!w.flat) continue;
-    // (a pixel pass may have flagged residuals outside int8: the tile reaches into the left / right / upper neighbours;
-    //  the fused pass finds them itself)
-    bool defer = false;
-    if (mp.bad) {
-      const uint8_t *bad = mp.bad + ((size_t)frame * 2 + kind) * g.nblocks;
-      for (int dy = -1; dy <= 0; ++dy)
-        for (int dx = -1; dx <= 1; ++dx) {
-          const int x = bx + dx, y = by + dy;
-          if (x >= 0 && x < g.nbw && y >= 0 && y < g.nbh && bad[y * g.nbw + x]) defer = true;
-        }
-    }
-    if (defer) {
-      // (the exact kernel's lists are per plane: a chroma deferral of this chain concerns both chroma planes)
-      mp.only[((size_t)frame * 3 + kind) * g.nblocks + by * g.nbw + bx] = 1;
-      if (kind) mp.only[((size_t)frame * 3 + 2) * g.nblocks + by * g.nbw + bx] = 1;
-      mp.only_any[frame] = 1u;
-      plain = false;
-    } else {
-      win[t] = (uint32_t)w.xe | ((uint32_t)w.ye << 6) | (w.ys ? 1u << 13 : 0u) | (w.xs ? 1u << 14 : 0u) | (1u << 15);
-    }
+    // (residuals outside int8: the accumulation launches find them themselves and leave the block to the exact kernel)
+    win[t] = (uint32_t)w.xe | ((uint32_t)w.ye << 6) | (w.ys ? 1u << 13 : 0u) | (w.xs ? 1u << 14 : 0u) | (1u << 15);
   }
   // two lists in the frame's array: the general units from the front, the plain ones from the back
   const int lane = threadIdx.x & 63;

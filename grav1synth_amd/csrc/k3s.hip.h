@@ -84,14 +84,6 @@ __host__ __device__ constexpr int s_lds_bytes(int CBW, int CBH, int PL) { return
 
 typedef int v4i32s __attribute__((ext_vector_type(4)));
 
-// timing experiments (FParams::dbg, G1S_S_DBG): parts of the kernel left out -- only in builds with -DG1S_S_DBG_BUILD (a
-// wave-uniform test costs the hot loop three instructions a time)
-#ifdef G1S_S_DBG_BUILD
-#define G1S_S_DBGBIT(bit) ((dbg & (bit)) != 0)
-#else
-#define G1S_S_DBGBIT(bit) false
-#endif
-
 // a raw 8-sample word -> packed 16-bit pairs 0x00vv00vv of the narrowed samples (f_narrow with plain 32-bit shifts: what the
 // shift drags from the upper sample into the lower one is masked away)
 template <int BPS>
@@ -229,22 +221,18 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nx = G, jx = wg;
   const uint32_t cnt_g = fpar.unit_count[2 * frame], cnt_p = fpar.unit_count[2 * frame + 1];
-  const uint32_t ustride = fpar.deal ? 1u : (uint32_t)nx;
+  // units to workgroups: contiguous runs of the lists (measured +2..4 % over round-robin in the pipelined job, although a
+  // kernel alone on the chip is 5 % slower: the runs' loads disturb the kernels next to it less; profiles/r02_pmc_traffic.txt)
   auto share = [&](uint32_t cnt, uint32_t &first, int &n) {
-    if (fpar.deal) {
-      first = (uint32_t)((unsigned long long)cnt * (uint32_t)jx / (uint32_t)nx);
-      n = (int)((uint32_t)((unsigned long long)cnt * (uint32_t)(jx + 1) / (uint32_t)nx) - first);
-    } else {
-      first = (uint32_t)jx;
-      n = cnt > first ? (int)((cnt - first + (uint32_t)nx - 1) / (uint32_t)nx) : 0;
-    }
+    first = (uint32_t)((unsigned long long)cnt * (uint32_t)jx / (uint32_t)nx);
+    n = (int)((uint32_t)((unsigned long long)cnt * (uint32_t)(jx + 1) / (uint32_t)nx) - first);
   };
   uint32_t first_p, first_g;
   int n_p, n_g;
   share(cnt_p, first_p, n_p);
   share(cnt_g, first_g, n_g);
   auto upos = [&](int k) {
-    return k < n_p ? (uint32_t)fpar.nunits - 1u - (first_p + (uint32_t)k * ustride) : first_g + (uint32_t)(k - n_p) * ustride;
+    return k < n_p ? (uint32_t)fpar.nunits - 1u - (first_p + (uint32_t)k) : first_g + (uint32_t)(k - n_p);
   };
   const uint32_t *units = fpar.units + (size_t)frame * fpar.nunits * kMUnitDwords;
   int32_t *ustats = fpar.ustats + (size_t)frame * fpar.nunits * kMStatInts;
@@ -257,8 +245,6 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
   // the fast path and the halo words from the neighbours' registers: only where every word is a vector load (planes 16-byte
   // aligned, no word straddling the right plane edge)
   const bool reuse = LUMA && fpar.reuse && vec_all && (g.W & 7) == 0;
-  const int dbg = fpar.dbg;
-  (void)dbg;
 
   // ---- this lane's operand address inside a buffer ----
   const int mi = lane & 15, mg = lane >> 4;
@@ -397,7 +383,6 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
 
   // ux: the unit's control .x (chunk, block row, fast, right, left)
   auto request = [&](uint32_t ux) __attribute__((always_inline)) {
-    if (G1S_S_DBGBIT(1)) return;
     const int bx0 = kMUnitBlocks * (int)(ux & 0xfffu), by = (int)((ux >> 12) & 0xfffu);
     const int X0y = bx0 * 32 - 8, Y0y = by * kBlock - 4, X0c = bx0 * CW_ - 8, Y0c = by * CH_ - 3;
     if constexpr (CHROMA) {
@@ -478,21 +463,6 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
   // aL / fast: of unit k.
   auto form = [&](int k, bool aL, bool fast) __attribute__((always_inline)) {
     const int slot = k & 3;
-    if (G1S_S_DBGBIT(2)) {
-      if (LUMA && y_wave) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          Dn[r][0] = ys_[r].x ^ yd_[r].x;
-          Dn[r][1] = ys_[r].y ^ yd_[r].y;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < CROUNDS; ++q) {
-        Cn[q][0] = cs_[q].x ^ cd_[q].x;
-        Cn[q][1] = cs_[q].y ^ cd_[q].y;
-      }
-      return;
-    }
     if (LUMA && y_wave) {
       uint32_t racc = 0, lacc = 0, d16[2][4];
       int sd = 0, sd2 = 0, ls = 0;
@@ -512,11 +482,9 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
         ls = (int)__builtin_amdgcn_sad_u8(pk_bytes(hs[0], hs[1]), 0u, (uint32_t)ls);
         ls = (int)__builtin_amdgcn_sad_u8(pk_bytes(hs[2], hs[3]), 0u, (uint32_t)ls);
       }
-      if (!G1S_S_DBGBIT(4)) {
-        // int8 arithmetic: a block that holds a residual outside int8 is redone by the exact kernel, statistics included
-        unsigned long long *tgt = &s_sum[slot][y_stat ? 0 : 3][y_bq];
-        atomicAdd(tgt, ((unsigned long long)(uint32_t)sd2 << 37) | ((unsigned long long)(uint32_t)ls << 19) | (unsigned long long)(uint32_t)(sd + kFBiasY));
-      }
+      // int8 arithmetic: a block that holds a residual outside int8 is redone by the exact kernel, statistics included
+      unsigned long long *tgt = &s_sum[slot][y_stat ? 0 : 3][y_bq];
+      atomicAdd(tgt, ((unsigned long long)(uint32_t)sd2 << 37) | ((unsigned long long)(uint32_t)ls << 19) | (unsigned long long)(uint32_t)(sd + kFBiasY));
       if constexpr (CH) {
         // ---- the chroma regressor L (chroma resolution) -> the unit's L tile in LDS (wave 3 stores it) ----
         uint8_t *ltile = reinterpret_cast<uint8_t *>(&s_L[slot][0]);
@@ -568,14 +536,12 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
         s_residual(hs, hv, d16, racc);
         Cn[q][0] = pk_bytes(d16[0], d16[1]);
         Cn[q][1] = pk_bytes(d16[2], d16[3]);
-        if (!G1S_S_DBGBIT(4)) {
-          int sd = __builtin_amdgcn_sdot4((int)Cn[q][0], 0x01010101, 0, false);
-          sd = __builtin_amdgcn_sdot4((int)Cn[q][1], 0x01010101, sd, false);
-          int sd2 = __builtin_amdgcn_sdot4((int)Cn[q][0], (int)Cn[q][0], 0, false);
-          sd2 = __builtin_amdgcn_sdot4((int)Cn[q][1], (int)Cn[q][1], sd2, false);
-          unsigned long long *tgt = &s_sum[slot][c_stat[q] ? cplane : 3][c_bq];
-          atomicAdd(tgt, ((unsigned long long)(uint32_t)sd2 << 37) | (unsigned long long)(uint32_t)(sd + kFBiasC));
-        }
+        int sd = __builtin_amdgcn_sdot4((int)Cn[q][0], 0x01010101, 0, false);
+        sd = __builtin_amdgcn_sdot4((int)Cn[q][1], 0x01010101, sd, false);
+        int sd2 = __builtin_amdgcn_sdot4((int)Cn[q][0], (int)Cn[q][0], 0, false);
+        sd2 = __builtin_amdgcn_sdot4((int)Cn[q][1], (int)Cn[q][1], sd2, false);
+        unsigned long long *tgt = &s_sum[slot][c_stat[q] ? cplane : 3][c_bq];
+        atomicAdd(tgt, ((unsigned long long)(uint32_t)sd2 << 37) | (unsigned long long)(uint32_t)(sd + kFBiasC));
         rall |= cpl[q] ? racc : 0u;
       }
       if (__builtin_expect(__builtin_amdgcn_ballot_w64((rall & 0xff00ff00u) != 0) != 0, 0)) {
@@ -602,7 +568,6 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
   // neighbour is the unit before it (aL), its right neighbour's first dwords are in Dn when it is the unit after it (aR);
   // otherwise they are in the halo lanes of Dc1 (general path).  wy: the unit's two windows of this launch's plane kind.
   auto write_copies = [&](int k1, bool aL, bool aR, uint32_t wy) __attribute__((always_inline)) {
-    if (G1S_S_DBGBIT(8)) return;
     const bool plain = k1 < n_p;
     const uint32_t wins[2] = {wy & 0xffffu, wy >> 16};
     uint8_t *buf = m_smem + (k1 & 1) * BUF;
@@ -712,7 +677,7 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
         if (__builtin_expect((mine & fbits) != 0, 0)) {
           // (chroma: bits 2, 3 Cb, bits 4, 5 Cr: k3m_finish reads them per plane)
           defer |= LUMA ? fbits : (PL == 1 ? (fbits << kMUnitBlocks) | (fbits << (2 * kMUnitBlocks)) : fbits << ((PL - 1) * kMUnitBlocks));
-        } else if (!G1S_S_DBGBIT(16)) {
+        } else {
           const uint8_t *buf = m_smem + (k & 1) * BUF;
           if constexpr (PLAIN) {
             s_multiply<NSTEP, RS, MP, false, G1S_S_READS>(aSS, aPP, aPQ, aQQ, buf, m_addr, ~0u);
@@ -727,7 +692,7 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
         }
       }
       // ---- wave 3: the unit's statistics record (a four-unit ring, stored four at a time), the next unit's L tile ----
-      if (wave == kFWaves - 1 && !G1S_S_DBGBIT(32)) {
+      if (wave == kFWaves - 1) {
         auto mine_entry = [](int t) {
           const int b = t >= 7 ? 1 : 0, e = t - 7 * b, c = e < 3 ? 0 : (e < 5 ? 1 : 2);
           return t < 14 ? (LUMA ? c == 0 : (SINGLE ? c == PL - 1 : c != 0)) : t == (LUMA ? 14 : 15);
@@ -757,7 +722,7 @@ __global__ __launch_bounds__(kFThreads, s_occupancy(CBW, CBH, PL)) void k3s_fuse
       }
       ux1 = ux2;
       ux2 = ux3;
-      if (!G1S_S_DBGBIT(64)) __syncthreads();
+      __syncthreads();
     }
   };
   run(std::true_type{}, 0, n_p);

@@ -28,10 +28,7 @@ struct FParams {
   uint32_t lpitch, lframe_bytes;
   int frames, wgs;        // the launch: frames x workgroups per frame, as a 1-D grid (see the kernel)
   int wg_cap;             // workgroups per frame the partial systems are laid out for (>= wgs: the luma and the chroma launch may differ)
-  int deal;               // units to workgroups: 0 round-robin, 1 contiguous runs
   int reuse;              // 1: (luma launch) the left halo word of a unit whose left neighbour was the unit before it in the run is not read
-  int dbg;                  // timing experiments (G1S_S_DBG, k3s.hip.h): bit 0 no global loads, 1 no residual arithmetic, 2 no statistics atomics, 3 no copy writes, 4 no multiplies, 5 no statistics / L stores, 6 no barrier in the loop; wrong results
-  long long *phase_cycles;  // profiling aid (built with -DG1S_F_PHASES, run with G1S_F_PHASES=1): [workgroup][wave][8] cycles: tile copies, barrier 2, multiply, barrier 1, wait for the words, residuals, requests, stores; or null
 };
 
 // BPS: bytes per sample known at compile time (1, 2), or 0: given at run time (mixed depths)

@@ -63,13 +63,7 @@ struct WParams {
   int gx_y;                 // luma cells a block row
   int frames, wgs, wg_cap;
   int rev;                  // 1: the launch walks the batch's frames last to first (what the kernel before it touched last is read first)
-  int dbg;                  // timing experiments (G1S_W_DBG, builds with -DG1S_W_DBG_BUILD only): 1 no global loads, 2 no residual arithmetic, 4 no statistics / L, 8 no copy writes, 16 no multiplies, 32 no barriers in the loop, 64 no statistics stores, 128 no L loads; wrong results
 };
-#ifdef G1S_W_DBG_BUILD
-#define G1S_W_DBGBIT(bit) ((wp.dbg & (bit)) != 0)
-#else
-#define G1S_W_DBGBIT(bit) false
-#endif
 
 // ---- matrix rows (as k3s.hip.h): lane l of an operand holds 16 bytes of row i = l & 15 for the k-group l >> 4.
 // i -> (u, s): u = which of the operand's two `a`, s = 0..6 the copy (cx = s - 3), s = 7 the chroma regressor L (u = 0 of P)
@@ -544,7 +538,6 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
     return r;
   };
   auto request = [&](uint32_t ex) __attribute__((always_inline)) {
-    if (G1S_W_DBGBIT(1)) return;
     const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
     const int X0 = c * kWUnitW, Y0 = by * BH - 4;
     if ((ex >> 25) & 1u) {  // every row and word of the tile inside the plane (Y0 >= 0)
@@ -593,7 +586,6 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
   w_u2 Lc[CHR ? (BH / 16) : 1];
   (void)Lc;
   auto load_L = [&](uint32_t ex) __attribute__((always_inline)) {
-    if (G1S_W_DBGBIT(128)) return;
     if constexpr (CHR) {
       const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
       const uint32_t so = (uint32_t)(by * BH) * wp.lpitch + (uint32_t)(c * kWUnitW);
@@ -608,14 +600,9 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
   auto form = [&](int j, uint32_t ex, bool real) __attribute__((always_inline)) {
     const int slot = (j + 1) & 3;
     uint32_t racc = 0, lacc = 0;
-    if (G1S_W_DBGBIT(2)) {
-#pragma unroll
-      for (int i = 0; i < NOWN; ++i)
-#pragma unroll
-        for (int r = 0; r < 2; ++r) Dn[i][r][0] = rs[i][r].x ^ rv[i][r].x, Dn[i][r][1] = rs[i][r].y ^ rv[i][r].y;
-      Hn[0] = hs.x ^ hv.x, Hn[1] = hs.y ^ hv.y;
-      return;
-    }
+    // (names the closure's captures in this order and does nothing else: the order decides how the compiler lays the closure out,
+    //  and with it the schedule of the unit loop -- this one is the schedule every measurement in profiles/ was taken on)
+    (void)Dn, (void)rs, (void)rv, (void)Hn, (void)hs, (void)hv;
 #pragma unroll
     for (int i = 0; i < NOWN; ++i) {
       uint32_t T[2][4];
@@ -626,7 +613,7 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
         w_pack<LAY>(T[r], Dn[i][r][0], Dn[i][r][1]);
         __builtin_amdgcn_sched_barrier(0);  // (row by row: the scheduler would otherwise keep both rows' temporaries alive)
       }
-      if (real && !G1S_W_DBGBIT(4)) {
+      if (real) {
         int sd = 0, sd2 = 0;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
@@ -723,7 +710,6 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
     next0 = (uint32_t)__builtin_amdgcn_update_dpp(hr, (int)d0, 0x101, 0xf, 0xf, false);  // row_shl:1
   };
   auto write_copies = [&](uint32_t ex) __attribute__((always_inline)) {
-    if (G1S_W_DBGBIT(8)) return;
     uint8_t *base = w_smem + (CHR && s_plane ? SH::OFF_P1 : 0) + 2 * p * kWUnitW + 8 * w;
 #pragma unroll
     for (int i = 0; i < NOWN; ++i)
@@ -760,7 +746,6 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
   // raw words a wait for the store (measured: +130 us on the luma launch).
   uint32_t defer_prev = 0;
   auto stats_out = [&](int j, uint32_t dfr) __attribute__((always_inline)) {
-    if (G1S_W_DBGBIT(64)) return;
     if (tid < NPL * UB) {
       const int slot = (j + 1) & 3;
       const int pl = tid / UB, b = tid - pl * UB;
@@ -850,7 +835,7 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
     if (k > 0) stats_out(k - 1, defer_prev);
     // ---- this unit's copies -> the tile buffer (free since the barrier at the end of the iteration before) ----
     write_copies(ex);
-    if (!G1S_W_DBGBIT(32)) __syncthreads();
+    __syncthreads();
     // ------------------------------- multiply unit k -------------------------------
     const int slot = (k + 1) & 3;
     const uint32_t b0 = __builtin_amdgcn_readfirstlane(s_bad[slot]), bl = __builtin_amdgcn_readfirstlane(s_bad[k & 3]),
@@ -870,7 +855,7 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
     //  354 - 358 us, chroma 212 - 219 -> 209 - 214, the chain - 5 to - 20 by the box; priorities 1 / 2 / 3, the halo wave raised while it
     //  stages, or the staging phase raised instead: all within 3 us of each other.  profiles/r06h_setprio.txt)
     __builtin_amdgcn_s_setprio(1);
-    if (!mine_deferred && !G1S_W_DBGBIT(16)) {
+    if (!mine_deferred) {
       if ((ex >> 24) & 1u) {
         w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
       } else if ([&]() {
@@ -921,7 +906,7 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
     }
     advance();
     defer_prev = defer;
-    if (!G1S_W_DBGBIT(32)) __syncthreads();
+    __syncthreads();
   }
   if (nmine > 0) stats_out(nmine - 1, defer_prev);
 

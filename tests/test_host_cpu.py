@@ -54,6 +54,26 @@ def test_product_does_not_reference_the_oracle():
                     assert b not in txt, f"{f} references {b}"
 
 
+def test_design_lists_exactly_the_switches_the_code_reads():
+    """DESIGN.md section 8's switch paragraph against the sources: every environment variable the library reads is named there,
+    and every name there still occurs in the package or in bench.py."""
+    design = open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8").read()
+    para = design.split("### Debugging / tuning switches", 1)[1].split("\n## ", 1)[0]
+    documented = set(re.findall(r"G1S_[A-Z0-9_]+", para))
+    texts = [open(os.path.join(ROOT, "bench.py"), errors="ignore").read()]
+    read = set()
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "grav1synth_amd")):
+        for f in files:
+            if f.endswith((".py", ".cpp", ".h", ".hip", "Makefile")):
+                texts.append(open(os.path.join(dirpath, f), errors="ignore").read())
+                if os.path.basename(dirpath) == "csrc":
+                    read |= set(re.findall(r'getenv\("(G1S_[A-Z0-9_]+)"\)', texts[-1]))
+    assert len(read) > 20
+    missing = sorted(read - documented)
+    gone = sorted(n for n in documented if not any(re.search(n + r"(?![A-Z0-9_])", t) for t in texts))
+    assert not missing and not gone, f"read by the library, missing from DESIGN.md: {missing}; named there, nowhere in the code: {gone}"
+
+
 CASES = [
     (SynthSpec(320, 192, 8), 3, True, 3),
     (SynthSpec(320, 200, 10, xdec=1, ydec=0), 3, True, 2),

@@ -89,19 +89,6 @@ for k in range(n):
                 C, Cw = contrib(bx_, by_, D), contrib(bx_, by_, wrap)
                 for name, M in (("+exact", C), ("+wrapped", Cw), ("wrapped - exact", Cw - C), ("-exact", -C)):
                     if M.any() and np.array_equal(np.triu(M), E): print("     gpu - oracle == block", (bx_, by_), name); found = True
-        if os.environ.get("G1S_DBG_SKIP") == "generic":
-            # planes mode, no generic kernel: the GPU holds the matrix-core part only = the blocks outside the 6-neighbourhood of a bad block
-            badb = set()
-            for c_, x_, y_, dv in hits:
-                if c_ == 0 and abs(dv) > 127: badb.add((x_ // 32, y_ // 32))
-            deferred = set((bx_ + dx, by_ + dy) for bx_, by_ in badb for dx in (-1, 0, 1) for dy in (0, 1))
-            exp = sum((contrib(bx_, by_, D) for by_ in range(nbh_) for bx_ in range(nbw_) if fl[by_, bx_] and (bx_, by_) not in deferred), np.zeros((len(offs), len(offs)), np.int64))
-            G_ = np.triu(S2.astype(np.int64)); X_ = np.triu(exp)
-            print("     matrix-core part == numpy over the non-deferred blocks:", np.array_equal(G_, X_), "bad blocks", badb, "max |diff|", int(np.abs(G_ - X_).max()))
-            for by_ in range(nbh_):
-                for bx_ in range(nbw_):
-                    if fl[by_, bx_] and np.array_equal(np.triu(contrib(bx_, by_, D)), X_ - G_): print("       numpy - gpu == block", (bx_, by_), "deferred" if (bx_, by_) in deferred else "NOT deferred")
-                    if fl[by_, bx_] and np.array_equal(np.triu(contrib(bx_, by_, D)), G_ - X_): print("       gpu - numpy == block", (bx_, by_), "deferred" if (bx_, by_) in deferred else "NOT deferred")
         if not found:
             blocks = [(bx_, by_) for by_ in range(nbh_) for bx_ in range(nbw_) if fl[by_, bx_]]
             iu = np.triu_indices(len(offs))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/ktime.py [batches] -- per-kernel HIP-event times of the 4K 10-bit bench workload (64-frame batches, one stream), errors of
-the fold ignored: for timing experiments that leave parts of a kernel out (G1S_S_DBG, G1S_DBG_SKIP)."""
+the fold ignored (the kernels are timed whatever the fold makes of the content)."""
 import os, sys, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fractions import Fraction
