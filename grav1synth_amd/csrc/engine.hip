@@ -258,7 +258,10 @@ Pool *merge_pool() {
 }
 std::mutex g_merge_pool_mutex;
 
-constexpr bool kDeviceLatestDefault = false;
+// G1S_LATEST unset: the per-frame half of the fold runs on the device for frames of this many blocks or more.  The device half's solves
+// cost the same whatever the frame's size and the host half's cost goes with the blocks: same box, 1080p (2 040 blocks) the host half
+// 1.08 - 1.10 x the device half, 4K (8 160 blocks) the device half 1.13 x the host half (profiles/r07_device_latest.txt)
+constexpr int kDeviceLatestMinBlocks = 4096;
 constexpr int kSlots = 6;  // batches in flight: being filled, pixel pass + finder, accumulation, (the per-frame half on the device,) D2H, fold
 
 struct Slot {
@@ -412,6 +415,7 @@ struct g1s_diff {
   bool luma_only, records_only;
   bool latest_only = false;  // keep the per-frame latest states (blobs) instead of folding them here
   bool device_latest = false;  // the per-frame half of the fold runs on the device (k4_latest): blobs come back, not records
+  bool latest_by_size = false;  // G1S_LATEST is unset: set_geometry chooses (kDeviceLatestMinBlocks)
   uint32_t batch;
   bool batch_auto = false;  // no batch size asked for: sized to the frames at the first frame pair
   int device = 0;
@@ -601,6 +605,7 @@ int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
   g.nbw = (g.W + kBlock - 1) / kBlock;
   g.nbh = (g.H + kBlock - 1) / kBlock;
   g.nblocks = g.nbw * g.nbh;
+  if (latest_by_size) device_latest = !records_only && g.nblocks >= kDeviceLatestMinBlocks;
   g.src_bps = s->bytes_per_sample;
   g.den_bps = d->bytes_per_sample;
   g.src_shift = s->bytes_per_sample == 2 ? (int)src_bd - 8 : 0;
@@ -1711,10 +1716,11 @@ g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_d
   g->records_only = records_only;
   g->latest_only = latest_only;
   {
-    // G1S_LATEST=host|device: where the per-frame half of the fold runs (records_only generators hand out records: host)
+    // G1S_LATEST=host|device: where the per-frame half of the fold runs (records_only generators hand out records: host);
+    // unset: by the frame's size, once it is known
     const char *e = getenv("G1S_LATEST");
-    const bool dev = e ? std::string(e) == "device" : kDeviceLatestDefault;
-    g->device_latest = dev && !records_only;
+    g->latest_by_size = !e;
+    g->device_latest = e && std::string(e) == "device" && !records_only;
   }
   g->batch = batch;
   g->batch_auto = batch_auto;

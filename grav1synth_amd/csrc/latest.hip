@@ -20,8 +20,8 @@
 //     and b[k] only ever meet blocks of bins k - 1 and k: the blocks are taken 512 at a time, their terms computed a thread a
 //     block, partitioned by bin IN ORDER into lists in LDS (ballots and popcounts: a stable partition), and lane k adds its
 //     list front to back -- one LDS read and one addition an element, no selection, no memory latency in the chain; `total`
-//     is one sum over all blocks: a wave reads 64 terms at a time and adds them lane by lane (v_readlane).  Both chroma
-//     planes go through one pass (same blocks, same bins).
+//     is one sum over all blocks: one more list (every measured block, in block order), one more lane.  Both chroma planes go
+//     through one pass (same blocks, same bins).
 #include "latest_dev.h"
 
 #include "fold.h"
@@ -36,19 +36,18 @@ constexpr int kChunk = 512, kRounds = kChunk / kT;  // blocks a chunk; a thread'
 constexpr double kTinyD = 1.0e-16;                  // TINY_NEAR_ZERO
 constexpr double kNorm2D = 255.0 * 255.0;           // BLOCK_NORMALIZATION^2
 constexpr int kNL = 2 * kNumBins;                   // lists of a chunk: D 0 .. 19 (bins k - 1 and k), L 20 .. 38 (bin k alone), T 39 (every block)
-constexpr int kArenaD = 2 * kChunk + 8 * kNumBins + 8, kArenaL = kChunk + 8 * kNumBins + 8;
+constexpr int kArenaD = 2 * kChunk + 8 * kNumBins + 8, kArenaL = kChunk + 8 * kNumBins + 8, kArenaT = kChunk + 8;
 static_assert(kNumBins == 20 && kMaxN == 25, "latest.hip: the solvers' static sizes");
 
 struct Shared {
   // a chunk's partitioned terms
   // (a list's slots start at a multiple of 8 and are zero-filled up to the next one: the chains add whole groups of eight --
   //  a +0.0 changes no sum that is >= +0 or NaN -- and read one group ahead)
-  double D[kArenaD];      // matrix diagonal terms, list k at [beg[k], end[k])
+  alignas(16) double D[kArenaD];  // matrix diagonal terms, list k at [beg[k], end[k])
   double Lw[kArenaL];     // off-diagonal terms, list 20 + k
   double Bv[2][kArenaD];  // b terms of the pass' planes, the D lists' slots
-  double Tv[2][kChunk];   // noise stds in block order (list 39)
+  double Tv[2][kArenaT];  // noise stds in block order (list 39)
   uint16_t cnt[kRounds][kWaves][kNL];  // (16-bit: the workgroup's LDS stays under a quarter of a CU's, and with it the kernel at four waves a SIMD)
-  uint16_t off[kRounds][kWaves][kNL];
   uint32_t beg[kNL], end[kNL];
   // results
   double arx[3][kMaxN + 1];
@@ -205,10 +204,10 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
     corr[q] = is_chroma ? sh.arx[c0 + q][job.n] : 0;
   }
   const double luma_gain = sh.gain[0];
-  // the chains' accumulators: wave 0 lane k < 20: (k, k) and b[k] of every plane; lanes 20 .. 38: (k + 1, k); wave 1: the totals
+  // the chains' accumulators
   // (one chain a lane -- wave 0: lanes 0 .. 19 the (k, k) sums, 20 .. 39 plane 0's b[k], 40 .. 59 plane 1's; wave 2 lanes 0 .. 18
-  //  the (k + 1, k) sums; waves 1 and 3 the planes' totals: an addition waits for the one before it, the chains next to each other
-  //  in a wave cost nothing)
+  //  the (k + 1, k) sums, lanes 19 and 20 the planes' totals: an addition waits for the one before it, the chains next to each
+  //  other in a wave cost nothing)
   double acc = 0;
   uint32_t ne = 0;
 
@@ -316,17 +315,22 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
     __syncthreads();
     K4_TICK(7);
     // ---- offsets: list l's slots of (round, wave), rounds first (block order) ----
-    if (wave == 0) {
-      uint32_t run = 0;
-      if (lane < kNL) {
+    // (every wave works them out for itself from the counts, lane l list l, and keeps its own rounds' in registers: no
+    //  barrier between the offsets and the scatter; wave 0 leaves the lists' bounds and the zeros behind them for the chains)
+    uint32_t my_off[kRounds];
+    uint32_t run = 0;
 #pragma unroll
-        for (int r = 0; r < kRounds; ++r)
+    for (int r = 0; r < kRounds; ++r) my_off[r] = 0;
+    if (lane < kNL) {
 #pragma unroll
-          for (int w = 0; w < kWaves; ++w) {
-            sh.off[r][w][lane] = (uint16_t)run;
-            run += sh.cnt[r][w][lane];
-          }
-      }
+      for (int r = 0; r < kRounds; ++r)
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+          if (w == wave) my_off[r] = run;
+          run += sh.cnt[r][w][lane];
+        }
+    }
+    {
       // the lists' bases inside their arenas (each list's room a multiple of 8): D lists 0 .. 19 one behind the other, L lists
       // 20 .. 38 likewise, T at 0
       const uint32_t room = (run + 7u) & ~7u;
@@ -340,7 +344,9 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
       uint32_t bse = incl - room;
       if (lane >= kNumBins) bse -= upto19;
       if (lane == kNL - 1) bse = 0;
-      if (lane < kNL) {
+#pragma unroll
+      for (int r = 0; r < kRounds; ++r) my_off[r] += bse;
+      if (wave == 0 && lane < kNL) {
         sh.beg[lane] = bse;
         sh.end[lane] = bse + run;
         // the zeros behind the list
@@ -352,29 +358,37 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
           }
         } else if (lane < kNL - 1) {
           for (uint32_t i = bse + run; i < bse + room; ++i) sh.Lw[i] = 0.0;
+        } else {
+          for (uint32_t i = run; i < room; ++i) {
+#pragma unroll
+            for (int q = 0; q < NP; ++q) sh.Tv[q][i] = 0.0;
+          }
         }
       }
     }
-    __syncthreads();
     K4_TICK(8);
-    // ---- the terms into their lists ----
+    // ---- the terms into their lists (a list's base for this wave's round: from the lane that holds it) ----
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
-      const int kk = key[r];
+      const int kk = key[r], kq = max(kk, 0);
+      const uint32_t o_own = (uint32_t)__shfl((int)my_off[r], kq, 64);
+      const uint32_t o_prev = (uint32_t)__shfl((int)my_off[r], min(kq + 1, kNumBins - 1), 64);
+      const uint32_t o_low = (uint32_t)__shfl((int)my_off[r], kNumBins + min(kq, kNumBins - 2), 64);
+      const uint32_t o_all = (uint32_t)__shfl((int)my_off[r], kNL - 1, 64);
       if (kk < 0) continue;
-      const uint32_t so = sh.beg[kk] + sh.off[r][wave][kk] + rk_own[r];
+      const uint32_t so = o_own + rk_own[r];
       sh.D[so] = tU[r];
 #pragma unroll
       for (int q = 0; q < NP; ++q) sh.Bv[q][so] = tP[r][q];
       if (kk < kNumBins - 1) {
-        const uint32_t sp = sh.beg[kk + 1] + sh.off[r][wave][kk + 1] + rk_prev[r];
+        const uint32_t sp = o_prev + rk_prev[r];
         sh.D[sp] = tV[r];
 #pragma unroll
         for (int q = 0; q < NP; ++q) sh.Bv[q][sp] = tQ[r][q];
-        const uint32_t sl = sh.beg[kNumBins + kk] + sh.off[r][wave][kNumBins + kk] + rk_low[r];
+        const uint32_t sl = o_low + rk_low[r];
         sh.Lw[sl] = tW[r];
       }
-      const uint32_t st = sh.off[r][wave][kNL - 1] + rk_all[r];
+      const uint32_t st = o_all + rk_all[r];
 #pragma unroll
       for (int q = 0; q < NP; ++q) sh.Tv[q][st] = tS[r][q];
     }
@@ -383,11 +397,13 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
     // ---- the chains: a list front to back ----
     if (wave == 0 || wave == 2) {
       // wave 0: lanes 0 .. 19 the diagonal terms of list k, 20 .. 39 / 40 .. 59 the planes' b terms; wave 2: lanes 0 .. 18 the
-      // off-diagonal terms.  Groups of eight, the next group's reads in flight while this one is added.
-      const int arr = wave == 0 ? lane / kNumBins : 3;
-      const int li = wave == 2 ? kNumBins + lane : lane % kNumBins;
-      const bool on = wave == 2 ? lane < kNumBins - 1 : arr <= NP;
-      const double2 *src = reinterpret_cast<const double2 *>(arr == 0 ? sh.D : arr == 1 ? sh.Bv[0] : arr == 2 ? sh.Bv[NP - 1] : sh.Lw);
+      // off-diagonal terms, lanes 19 / 20 the planes' totals (list 39: every measured block, in block order).  Groups of eight,
+      // the next group's reads in flight while this one is added.
+      constexpr int kLowLanes = kNumBins - 1;
+      const int arr = wave == 0 ? lane / kNumBins : (lane < kLowLanes ? 3 : 4 + (lane - kLowLanes));
+      const int li = wave == 0 ? lane % kNumBins : (lane < kLowLanes ? kNumBins + lane : kNL - 1);
+      const bool on = wave == 0 ? arr <= NP : lane < kLowLanes + NP;
+      const double2 *src = reinterpret_cast<const double2 *>(arr == 0 ? sh.D : arr == 1 ? sh.Bv[0] : arr == 2 ? sh.Bv[NP - 1] : arr == 3 ? sh.Lw : arr == 4 ? sh.Tv[0] : sh.Tv[NP - 1]);
       if (on) {
         uint32_t i = sh.beg[li] >> 1;
         const uint32_t e = (sh.end[li] + 1) >> 1;
@@ -408,22 +424,8 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
             i += 4;
           }
         }
+        if (wave == 2 && lane == kLowLanes) ne += sh.end[kNL - 1];
       }
-    } else if (wave == 1 || NP == 2) {
-      // the totals: waves 1 and 3, a plane each; 64 stds at a time, added lane by lane
-      const int q = wave == 1 ? 0 : NP - 1;
-      const uint32_t e = sh.end[kNL - 1];
-      for (uint32_t b0 = 0; b0 < e; b0 += 64) {
-        const double v = b0 + lane < e ? sh.Tv[q][b0 + lane] : 0.0;
-        const int cntc = (int)min(64u, e - b0);
-        if (cntc == 64) {
-#pragma unroll
-          for (int j = 0; j < 64; ++j) acc += readlane_f64(v, j);
-        } else {
-          for (int j = 0; j < cntc; ++j) acc += readlane_f64(v, j);
-        }
-      }
-      if (wave == 1) ne += e;
     }
     __syncthreads();  // (the lists are written again by the next chunk)
     K4_TICK(10);
@@ -434,9 +436,8 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
     else if (arr <= NP) sh.bsum[arr - 1][k] = acc;
   } else if (wave == 2) {
     if (lane < kNumBins - 1) sh.low[lane] = acc;
-  } else if (lane == 0 && (wave == 1 || NP == 2)) {
-    sh.total[wave == 1 ? 0 : NP - 1] = acc;
-    if (wave == 1) sh.ne = ne;
+    else if (lane < kNumBins - 1 + NP) sh.total[lane - (kNumBins - 1)] = acc;
+    if (lane == kNumBins - 1) sh.ne = ne;
   }
   __syncthreads();
 }
