@@ -21,6 +21,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/g1s_diff.h"
@@ -262,96 +264,108 @@ std::mutex g_merge_pool_mutex;
 // cost the same whatever the frame's size and the host half's cost goes with the blocks: same box, 1080p (2 040 blocks) the host half
 // 1.08 - 1.10 x the device half, 4K (8 160 blocks) the device half 1.13 x the host half (profiles/r07_device_latest.txt)
 constexpr int kDeviceLatestMinBlocks = 4096;
-constexpr int kSlots = 6;  // batches in flight: being filled, pixel pass + finder, accumulation, (the per-frame half on the device,) D2H, fold
+constexpr int kSlots = 6;  // batches in flight: being filled, finder chain, accumulation, (the per-frame half on the device,) D2H, fold
+
+// What a slot owns: a HIP allocation or event, released when its holder goes.  Move-only; reads as the raw pointer it holds.
+template <class T, auto FREE>
+struct Owned {
+  T *p = nullptr;
+  Owned() = default;
+  Owned(Owned &&o) noexcept : p(o.p) { o.p = nullptr; }
+  Owned &operator=(Owned &&o) noexcept { return std::swap(p, o.p), *this; }  // (what this one held goes with `o`)
+  ~Owned() { if (p) (void)FREE(p); }
+  operator T *() const { return p; }
+};
+template <class T> using DevBuf = Owned<T, hipFree>;
+template <class T> using PinnedBuf = Owned<T, hipHostFree>;
+using Event = Owned<std::remove_pointer<hipEvent_t>::type, hipEventDestroy>;
+
+// A slot's memory: the bytes of every per-slot allocation and, for the buffers that hold several things, where each region
+// lies (byte offsets).  set_geometry_alloc works it out once and says there what each region is; whatever
+// allocates, zeroes or points a kernel into a slot reads this.
+struct SlotLayout {
+  size_t planes, records, flags, stage_frame;  // h_planes / d_planes, d_records / h_records, d_flags; d_stage is [batch] x stage_frame
+  size_t k1, k1_moments, k1_list, k1_count;
+  size_t mu, mu_units, mu_count, mu_any, mu_only, mu_only_bytes, mu_ustats;
+  size_t wu, wu_units[2], wu_count, wu_lbad, wu_lbad_bytes;
+  size_t mpart, lplane;
+  bool operator==(const SlotLayout &o) const { return std::memcmp(this, &o, sizeof(*this)) == 0; }
+};
+static_assert(std::has_unique_object_representations<SlotLayout>::value, "SlotLayout is compared as bytes: no padding in it");
+
+enum SlotEv { kEvStart, kEvMomStart, kEvMomEnd, kEvFinderEnd, kEvSelectEnd, kEvEnd, kSlotEvs };  // a timed batch's events, as they are recorded
 
 struct Slot {
-  FramePlanes *h_planes = nullptr;  // pinned
-  FramePlanes *d_planes = nullptr;
-  uint8_t *d_records = nullptr;
-  uint8_t *h_records = nullptr;  // pinned
-  uint8_t *d_flags = nullptr;
-  int32_t *d_partials = nullptr;   // k3_interior chunk partials, then k3_mixed chunk partials
-  uint8_t *d_defer = nullptr;      // area classes, bad-block flags, area lists and their counts
-  uint8_t *d_k0 = nullptr;         // K0 int8 planes [batch] x PlaneSet::frame_bytes
-  int32_t *d_k1 = nullptr;         // flat-block fast path: moments [batch][nblocks][16], literal list [batch][nblocks], counts [batch]
-  uint32_t *d_pgl = nullptr;       // partial-group lists [batch][2][pg_cap] + counts [batch][2]
-  uint8_t *d_mu = nullptr;         // MFMA path: unit lists [batch][nunits], unit counts, deferred-block flags
-  long long *d_mpart = nullptr;    // MFMA path: partial systems of the accumulation workgroups
-  uint8_t *d_lplane = nullptr;     // MFMA path: L at chroma resolution, int8 (luma launch -> chroma launch)
-  uint8_t *d_wu = nullptr;         // wide chain: unit lists, counts, per-unit statistics records, L-outside-int8 flags
-  uint8_t *d_stage = nullptr;  // device copies of host-resident frames
+  PinnedBuf<FramePlanes> h_planes;  // the batch's frame table, as append() fills it
+  DevBuf<FramePlanes> d_planes;     // ... uploaded by launch_front
+  DevBuf<uint8_t> d_records;        // the batch's records: zeroed, then written by every kernel of the batch
+  PinnedBuf<uint8_t> h_records;     // ... on the host (the device half: only the batch's last record)
+  DevBuf<uint8_t> d_flags;          // the finder's verdict on each block (k1_certify / the literal kernel -> the select kernel)
+  DevBuf<uint8_t> d_k1;             // the finder's moments, literal list and counts (SlotLayout::k1_*)
+  DevBuf<uint8_t> d_mu;             // the stream chain's unit lists and statistics, both chains' deferral flags (SlotLayout::mu_*)
+  DevBuf<long long> d_mpart;        // partial systems of the accumulation workgroups
+  DevBuf<uint8_t> d_wu;             // the wide chain's unit lists, counts and L-outside-int8 flags (SlotLayout::wu_*)
+  DevBuf<uint8_t> d_lplane;         // L at chroma resolution, int8 (luma launch -> chroma launch)
+  DevBuf<uint8_t> d_stage;          // device copies of host-resident frames (made when the first one comes: append)
   // the per-frame half of the fold on the device (latest.hip): the frames' latest-state blobs and the kernel's scratch
-  uint8_t *d_latest = nullptr, *h_latest = nullptr /* pinned */, *d_lscratch = nullptr;
+  DevBuf<uint8_t> d_latest, d_lscratch;
+  PinnedBuf<uint8_t> h_latest;
   size_t latest_cap = 0, lscratch_cap = 0;
-  size_t stage_bytes_per_frame = 0;
-  hipEvent_t done = nullptr;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // timing: finder start, k2 start, k3 start, k3 end, k0 end, k0 start
+  Event done;            // the batch's results are on the host
+  Event ev[kSlotEvs];    // timing: SlotEv
   uint32_t count = 0;
   bool timed = false;
   bool chain = false;  // a timed batch with ONE pair of events, around the batch's whole chain of kernels (g1s_diff_set_timing(g, 2))
   bool async_in = false;  // the batch holds frames whose H2D copies were queued on the upload stream
   // per-kernel timing (g1s_diff_set_timing): an event before each launch, the name of the kernel it precedes
-  std::vector<hipEvent_t> kev;
+  std::vector<Event> kev;
   std::vector<std::string> kname;
   std::vector<hipStream_t> kstream;
   size_t nk = 0;
+  // the device half's buffers: made when a batch first runs that half, made again if one ever asks for more
+  hipError_t ensure_latest(size_t blob_bytes, size_t scratch_bytes) {
+    if (latest_cap < blob_bytes) {
+      d_latest = {}, h_latest = {}, latest_cap = 0;
+      if (hipError_t e = hipMalloc((void **)&d_latest.p, blob_bytes)) return e;
+      if (hipError_t e = hipHostMalloc((void **)&h_latest.p, blob_bytes, hipHostMallocDefault)) return e;
+      latest_cap = blob_bytes;
+    }
+    if (lscratch_cap < scratch_bytes) {
+      d_lscratch = {}, lscratch_cap = 0;
+      if (hipError_t e = hipMalloc((void **)&d_lscratch.p, scratch_bytes)) return e;
+      lscratch_cap = scratch_bytes;
+    }
+    return hipSuccess;
+  }
 };
-
-static void free_slot(Slot &sl) {
-  if (sl.h_planes) (void)hipHostFree(sl.h_planes);
-  if (sl.d_planes) (void)hipFree(sl.d_planes);
-  if (sl.d_records) (void)hipFree(sl.d_records);
-  if (sl.h_records) (void)hipHostFree(sl.h_records);
-  if (sl.d_flags) (void)hipFree(sl.d_flags);
-  if (sl.d_k1) (void)hipFree(sl.d_k1);
-  if (sl.d_partials) (void)hipFree(sl.d_partials);
-  if (sl.d_defer) (void)hipFree(sl.d_defer);
-  if (sl.d_k0) (void)hipFree(sl.d_k0);
-  if (sl.d_pgl) (void)hipFree(sl.d_pgl);
-  if (sl.d_mu) (void)hipFree(sl.d_mu);
-  if (sl.d_mpart) (void)hipFree(sl.d_mpart);
-  if (sl.d_lplane) (void)hipFree(sl.d_lplane);
-  if (sl.d_wu) (void)hipFree(sl.d_wu);
-  if (sl.d_stage) (void)hipFree(sl.d_stage);
-  if (sl.d_latest) (void)hipFree(sl.d_latest);
-  if (sl.h_latest) (void)hipHostFree(sl.h_latest);
-  if (sl.d_lscratch) (void)hipFree(sl.d_lscratch);
-  if (sl.done) (void)hipEventDestroy(sl.done);
-  for (auto &e : sl.ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : sl.kev) (void)hipEventDestroy(e);
-  sl = Slot{};
-}
+static_assert(!std::is_copy_constructible<Slot>::value && std::is_nothrow_move_assignable<Slot>::value,
+              "a slot owns what it holds: handed over whole (generator <-> cache), freed by `sl = Slot{}`");
 
 // Process-wide cache of slot buffers: pinned-host and device allocations cost
 // hundreds of microseconds each; consecutive generators of the same geometry
 // (one per video, or one per bench step) reuse them.
-struct SlotKey {
-  int device;
-  size_t planes, records, flags, partials, defer, stage, k0, pgl, mu, mpart, lplane;
-  int W, H, xdec, ydec, nplanes;  // the zeroed padding of the K0 planes depends on the exact geometry
-  bool operator==(const SlotKey &o) const {
-    return device == o.device && planes == o.planes && records == o.records && flags == o.flags &&
-           partials == o.partials && defer == o.defer && stage == o.stage && k0 == o.k0 && pgl == o.pgl && mu == o.mu &&
-           mpart == o.mpart && lplane == o.lplane &&
-           W == o.W && H == o.H && xdec == o.xdec && ydec == o.ydec && nplanes == o.nplanes;
-  }
-};
 struct CachedSlot {
-  SlotKey key;
+  int device;
+  SlotLayout lay;
+  // Not needed for the buffers to fit (the layout says that), and compared all the same: without them slots would move between
+  // geometries whose layouts happen to be equal, and whether a kernel reads bytes of a slot that nobody wrote for THIS
+  // geometry (the L plane's slack row, the parked entries around a d_wu slice) has not been examined.
+  int W, H, xdec, ydec, nplanes;
   Slot slot;
 };
 std::mutex g_cache_mutex;
-std::vector<CachedSlot> g_slot_cache;
+// (never destroyed: a parked slot is not freed at exit, when the runtime it would call may be gone already)
+std::vector<CachedSlot> &g_slot_cache = *new std::vector<CachedSlot>;
 
 // Streams and their events are process-wide too (0.1-0.2 ms to create each); a generator borrows a set and
 // hands it back when it is freed:
-//   compute  main stream: pixel pass (K0) and the four lag kernels of alternating batches, back to back
-//   flat     side stream (high priority): finder chain, window planes, area lists of a batch, next to the
-//            lag kernels of the batch before
-//   copy     tail of the accumulation (partial-group kernel, reducer, generic kernel) next to the pixel pass
-//            of the batch after next, then the records D2H
-//   upload   the frame tables (72 bytes a frame pair), ahead of everything
+//   compute  main stream: the accumulation of one batch after the other, back to back -- k3w_pass x 2 and k3w_tail
+//            (the stream chain: its luma launch)
+//   flat     side stream (high priority): a batch's finder chain, select kernel and unit lists, next to the accumulation
+//            of the batch before (flat2: those of the odd slots under G1S_SIDE2)
+//   copy     the results' D2H, behind the accumulation; in front of it the wide chain's chroma launch and tail under
+//            G1S_W_ASIDE, the stream chain's chroma launch and what follows unless G1S_F_SERIAL
+//   upload   the frame table (72 bytes a frame pair), k_zero and the queued copies of pinned host frames, ahead of everything
 struct StreamSet {
   int device = -1;
   hipStream_t compute = nullptr, copy = nullptr, flat = nullptr, flat2 = nullptr, upload = nullptr;
@@ -399,6 +413,30 @@ bool acquire_streams(int device, StreamSet &out) {
          hipEventCreateWithFlags(&out.table_done[i], hipEventDisableTiming) == hipSuccess;
   return ok;
 }
+// The device half's two streams and their events, when a generator first runs that half.  All of them or none: made into
+// locals and handed to the set -- which goes back to the process-wide cache -- only when ALL exist, so that a failure half
+// way cannot leave a set that looks complete with a null stream or event in it.  In the main stream's priority class (the
+// least urgent: the kernel fills in; 4 % better than the runtime's default class and the side stream's, profiles/r05_device_latest.txt)
+bool ensure_latest_streams(StreamSet &ss) {
+  if (ss.latest) return true;
+  int plo = 0, phi = 0;
+  (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
+  hipStream_t made[2] = {nullptr, nullptr};
+  hipEvent_t made_ev[kSlots] = {};
+  bool ok = true;
+  for (hipStream_t &st : made) ok = ok && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, plo) == hipSuccess;
+  for (int i = 0; i < kSlots; ++i) ok = ok && hipEventCreateWithFlags(&made_ev[i], hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    for (hipStream_t st : made)
+      if (st) (void)hipStreamDestroy(st);
+    for (hipEvent_t e : made_ev)
+      if (e) (void)hipEventDestroy(e);
+    return false;
+  }
+  ss.latest = made[0], ss.latest2 = made[1];
+  for (int i = 0; i < kSlots; ++i) ss.latest_done[i] = made_ev[i];
+  return true;
+}
 void release_streams(StreamSet &ss) {
   if (!ss.compute) return;
   std::lock_guard<std::mutex> lk(g_cache_mutex);
@@ -427,18 +465,15 @@ struct g1s_diff {
   RecLayout L{};
   FlatConsts fc{};
   double *d_lut = nullptr;
-  size_t defer_bytes = 0;
   uint32_t m_lpitch = 0, m_lframe = 0;  // MFMA path: L plane geometry
   int m_nunits = 0;          // MFMA path: chunks per frame
   size_t m_wg_cap = 0;       // ... workgroups (partial systems) the slots hold
-  size_t m_only_bytes = 0;   // ... deferred-block flags [batch][3][nblocks] (one list a plane), 16-byte rounded
-  // the wide chain (k3w.hip.h): blocks a chroma unit, cells a block row / a frame per kind, L geometry, layout of Slot::d_wu
+  // the wide chain (k3w.hip.h): blocks a chroma unit, cells a block row / a frame per kind, L geometry
   int w_ub_c = 4, w_gx[2] = {0, 0}, w_ncell[2] = {0, 0};
   uint32_t w_lpitch = 0, w_lframe = 0;
-  size_t w_off_units[2] = {0, 0}, w_off_count = 0, w_off_lbad = 0, w_lbad_bytes = 0, w_bytes = 0;
   bool wide_ok(const Geom &g) const;
   MParams make_mparams(const Slot &sl) const;
-  SlotKey slot_key{};
+  SlotLayout lay{};  // the slots' memory (set_geometry)
   Slot slots[kSlots];
   int cur = 0;
   int pending = -1;  // slot whose front half is queued and whose back half is not
@@ -495,9 +530,9 @@ struct g1s_diff {
     if (sl.chain) return G1S_OK;  // (a chain-timed batch: nothing between two of its launches, trace mode or not)
     if (!sl.timed && !trace) return G1S_OK;
     if (sl.nk == sl.kev.size()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) return fail(G1S_ERR_HIP, "hipEventCreate failed");
-      sl.kev.push_back(e);
+      Event e;
+      if (hipEventCreate(&e.p) != hipSuccess) return fail(G1S_ERR_HIP, "hipEventCreate failed");
+      sl.kev.push_back(std::move(e));
       sl.kname.emplace_back();
       sl.kstream.push_back(nullptr);
     }
@@ -538,7 +573,7 @@ struct g1s_diff {
   int append(const g1s_frame_t *s, const g1s_frame_t *d);
   uint64_t frames_copied(uint64_t wait_for);
   int submit(int si);        // front half now; back half now or with the next batch's front half
-  int launch_front(int si);  // zero, pixel pass, flat-block finder, window planes, area lists
+  int launch_front(int si);  // frame table, zero fills, flat-block finder, select kernel, unit lists
   int launch_back(int si);   // accumulation kernels, records D2H, hand-over to the drainer; its parts, in order:
   int accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);    // (`stream`: by reference, a chain may move
   int accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);  //  its chroma launch and the rest to ss.copy)
@@ -581,7 +616,7 @@ static void make_flat_consts(FlatConsts &fc) {
 int g1s_diff::set_geometry(const g1s_frame_t *s, const g1s_frame_t *d) {
   const int rc = set_geometry_alloc(s, d);
   if (rc)
-    for (Slot &sl : slots) free_slot(sl);
+    for (Slot &sl : slots) sl = Slot{};
   return rc;
 }
 int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
@@ -622,20 +657,7 @@ int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
   g.off_scores = (uint32_t)L.off_scores;
   g.off_mask = (uint32_t)L.off_mask;
 
-  size_t frame_bytes = 0;  // tight device copy of one frame pair (host-resident input)
-  for (uint32_t c = 0; c < np; ++c) {
-    const size_t pw = c ? (s->width >> s->xdec) : s->width, ph = c ? (s->height >> s->ydec) : s->height;
-    frame_bytes += ((pw * s->bytes_per_sample + 15) & ~size_t(15)) * ph;
-    frame_bytes += ((pw * d->bytes_per_sample + 15) & ~size_t(15)) * ph;
-  }
-  const size_t partial_bytes = 0, k0_bytes = 0, pgl_bytes = 0;  // (buffers of the chains removed in round 4: the slot key keeps its fields)
-  defer_bytes = 0;
   m_nunits = ((g.nbw + kMUnitBlocks - 1) / kMUnitBlocks) * g.nbh;
-  m_only_bytes = ((size_t)g.nblocks * 3 * batch + 15) & ~size_t(15);
-  // [units][unit counts][any-deferred flags][deferred-block flags]
-  // ... [per-unit statistics records]
-  const size_t mu_bytes = sizeof(uint32_t) * ((size_t)batch * m_nunits * kMUnitDwords + 3 * (size_t)batch) + m_only_bytes +
-                          sizeof(int32_t) * (size_t)batch * m_nunits * kMStatInts;
   // one partial system per accumulation workgroup and plane: the most workgroups a launch of 1 .. batch frames asks for
   m_wg_cap = 0;
   for (uint32_t b = 1; b <= batch; ++b)
@@ -643,7 +665,7 @@ int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
   // L plane of a frame: block rows x chunk columns at chroma resolution (+ a slack row)
   m_lpitch = g.nplanes == 3 ? (uint32_t)((((g.nbw + kMUnitBlocks - 1) / kMUnitBlocks) * kMUnitBlocks * (kBlock >> g.xdec) + 15) & ~15) : 0u;
   m_lframe = m_lpitch * (uint32_t)(g.nbh * (kBlock >> g.ydec) + 1);
-  // the wide chain (k3w.hip.h): its own lists, statistics records and L geometry
+  // the wide chain (k3w.hip.h): its own lists and L geometry
   w_ub_c = g.nplanes == 3 ? (kWUnitW / (kBlock >> g.xdec)) : 4;
   w_gx[0] = (g.nbw + 3) / 4;
   w_gx[1] = (g.nbw + w_ub_c - 1) / w_ub_c;
@@ -651,52 +673,73 @@ int g1s_diff::set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d) {
   w_ncell[1] = g.nplanes == 3 ? w_gx[1] * g.nbh : 0;
   w_lpitch = g.nplanes == 3 ? (uint32_t)((std::max(w_gx[0] * 4 * (kBlock >> g.xdec), w_gx[1] * kWUnitW) + 15) & ~15) : 0u;
   w_lframe = w_lpitch * (uint32_t)(g.nbh * (kBlock >> g.ydec) + 1);
-  {
-    size_t o = 64;  // (a workgroup parks the entry in front of its slice too)
-    w_off_units[0] = o, o += sizeof(uint32_t) * (size_t)batch * w_ncell[0] * kWEntry;
-    w_off_units[1] = o, o += sizeof(uint32_t) * (size_t)batch * w_ncell[1] * kWEntry;
-    w_off_count = o, o += sizeof(uint32_t) * 2 * (size_t)batch;
-    o = (o + 15) & ~size_t(15);
-    o += 256;  // (a workgroup parks three entries past its slice)
-    w_off_lbad = o, w_lbad_bytes = ((size_t)batch * w_ncell[0] + 15) & ~size_t(15), o += w_lbad_bytes;
-    w_bytes = switches().wide ? o : 0;
-  }
   if (switches().wide)
     for (uint32_t b = 1; b <= batch; ++b)
       m_wg_cap = std::max(m_wg_cap, (size_t)b * std::max(w_wgs_per_frame(w_ncell[0], (int)b, 0), w_wgs_per_frame(std::max(w_ncell[1], 1), (int)b, 1)));
-  const size_t mpart_bytes2 = sizeof(long long) * 3 * kMRec * m_wg_cap;
-  const size_t lplane_bytes = (size_t)std::max(m_lframe, switches().wide ? w_lframe : 0u) * batch;
-  slot_key = SlotKey{device, sizeof(FramePlanes) * batch, L.size * batch, (size_t)g.nblocks * batch,
-                     partial_bytes, defer_bytes, frame_bytes * batch, k0_bytes, pgl_bytes, mu_bytes + w_bytes, mpart_bytes2, lplane_bytes,
-                     g.W, g.H, g.xdec, g.ydec, g.nplanes};
+  // Where things lie in a slot: the one place that says so.  Regions of a buffer in the order they are laid down, none re-aligned.
+  const size_t B = batch, nblocks = (size_t)g.nblocks;
+  lay = SlotLayout{};
+  SlotLayout &l = lay;
+  l.planes = sizeof(FramePlanes) * B;  // the frame table
+  l.records = L.size * B;              // record.h
+  l.flags = nblocks * B;               // flat or not, a byte a block
+  for (uint32_t c = 0; c < np; ++c) {  // the tight device copy of one host-resident frame pair
+    const size_t pw = c ? (s->width >> s->xdec) : s->width, ph = c ? (s->height >> s->ydec) : s->height;
+    l.stage_frame += ((pw * s->bytes_per_sample + 15) & ~size_t(15)) * ph;
+    l.stage_frame += ((pw * d->bytes_per_sample + 15) & ~size_t(15)) * ph;
+  }
+  // d_k1, the flat-block finder
+  size_t o = 0;
+  l.k1_moments = o, o += sizeof(int32_t) * B * nblocks * kMomInts;  // [batch][nblocks][kMomInts], k1_moments -> k1_certify
+  l.k1_list = o, o += sizeof(uint32_t) * B * nblocks;               // [batch][nblocks]: the blocks left to the literal kernel
+  l.k1_count = o, o += sizeof(uint32_t) * B;                        // [batch]: how many; zeroed per batch
+  l.k1 = o;
+  // d_mu: the stream chain's unit lists and statistics, around the deferral flags of both chains
+  o = 0;
+  l.mu_units = o, o += sizeof(uint32_t) * B * m_nunits * kMUnitDwords;  // [batch][nunits][kMUnitDwords], k3m_units -> k3s_fused
+  l.mu_count = o, o += sizeof(uint32_t) * 2 * B;                        // [batch][2]: general, plain units; zeroed per batch in one fill with
+  l.mu_any = o, o += sizeof(uint32_t) * B;                              // [batch]: the frame has a deferred block
+  l.mu_only = o, l.mu_only_bytes = (nblocks * 3 * B + 15) & ~size_t(15), o += l.mu_only_bytes;  // [batch][3][nblocks] bytes: blocks left to the exact kernel; zeroed per batch
+  l.mu_ustats = o, o += sizeof(int32_t) * B * m_nunits * kMStatInts;    // [batch][nunits][kMStatInts], k3s_fused -> k3m_finish
+  l.mu = o;
+  l.mpart = sizeof(long long) * 3 * kMRec * m_wg_cap;  // a partial system per accumulation workgroup and plane
+  // d_wu, the wide chain (k3w.hip.h); not allocated under G1S_K3=stream
+  o = 64;  // (a workgroup parks the entry in front of its slice too)
+  l.wu_units[0] = o, o += sizeof(uint32_t) * B * w_ncell[0] * kWEntry;  // [batch][cells][kWEntry] luma, then chroma: k2w_select_units -> k3w_pass
+  l.wu_units[1] = o, o += sizeof(uint32_t) * B * w_ncell[1] * kWEntry;
+  l.wu_count = o, o += sizeof(uint32_t) * 2 * B;                        // [batch][2]
+  o = ((o + 15) & ~size_t(15)) + 256;  // (a workgroup parks three entries past its slice)
+  l.wu_lbad = o, l.wu_lbad_bytes = (B * w_ncell[0] + 15) & ~size_t(15), o += l.wu_lbad_bytes;  // a byte a luma unit: its L left int8; zeroed per batch
+  l.wu = switches().wide ? o : 0;
+  l.lplane = (size_t)std::max(m_lframe, switches().wide ? w_lframe : 0u) * B;  // L at chroma resolution, int8 (luma launch -> chroma launch)
   for (Slot &sl : slots) {
     {
       std::lock_guard<std::mutex> lk(g_cache_mutex);
       for (size_t i = 0; i < g_slot_cache.size(); ++i) {
-        if (g_slot_cache[i].key == slot_key) {
-          sl = g_slot_cache[i].slot;
+        CachedSlot &c = g_slot_cache[i];
+        if (c.device == device && c.lay == lay && c.W == g.W && c.H == g.H && c.xdec == g.xdec && c.ydec == g.ydec && c.nplanes == g.nplanes) {
+          sl = std::move(c.slot);
           g_slot_cache.erase(g_slot_cache.begin() + i);
           break;
         }
       }
     }
-    sl.stage_bytes_per_frame = frame_bytes;
     sl.count = 0;
     if (sl.h_planes) continue;  // reused
-    HIP_TRY(hipHostMalloc((void **)&sl.h_planes, slot_key.planes, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&sl.d_planes, slot_key.planes));
-    HIP_TRY(hipMalloc((void **)&sl.d_records, slot_key.records));
-    HIP_TRY(hipHostMalloc((void **)&sl.h_records, slot_key.records, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&sl.d_flags, slot_key.flags));
-    HIP_TRY(hipMalloc((void **)&sl.d_k1, sizeof(int32_t) * ((size_t)g.nblocks * batch * (kMomInts + 1) + batch)));
-    if (mu_bytes) HIP_TRY(hipMalloc((void **)&sl.d_mu, mu_bytes));
-    if (mpart_bytes2) HIP_TRY(hipMalloc((void **)&sl.d_mpart, mpart_bytes2));
-    if (w_bytes) HIP_TRY(hipMalloc((void **)&sl.d_wu, w_bytes));
-    if (lplane_bytes) HIP_TRY(hipMalloc((void **)&sl.d_lplane, lplane_bytes));
+    HIP_TRY(hipHostMalloc((void **)&sl.h_planes.p, lay.planes, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&sl.d_planes.p, lay.planes));
+    HIP_TRY(hipMalloc((void **)&sl.d_records.p, lay.records));
+    HIP_TRY(hipHostMalloc((void **)&sl.h_records.p, lay.records, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&sl.d_flags.p, lay.flags));
+    HIP_TRY(hipMalloc((void **)&sl.d_k1.p, lay.k1));
+    if (lay.mu) HIP_TRY(hipMalloc((void **)&sl.d_mu.p, lay.mu));
+    if (lay.mpart) HIP_TRY(hipMalloc((void **)&sl.d_mpart.p, lay.mpart));
+    if (lay.wu) HIP_TRY(hipMalloc((void **)&sl.d_wu.p, lay.wu));
+    if (lay.lplane) HIP_TRY(hipMalloc((void **)&sl.d_lplane.p, lay.lplane));
     // (blocking: the drainer SLEEPS until a batch's records have landed instead of spinning on the event -- a core a rank, which an
     //  8-rank node inside a 16-core quota does not have; five more batches are in flight, the wake-up costs the job nothing)
-    HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
-    for (auto &e : sl.ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreateWithFlags(&sl.done.p, hipEventDisableTiming | hipEventBlockingSync));
+    for (Event &e : sl.ev) HIP_TRY(hipEventCreate(&e.p));
   }
   geometry_set = true;
   return G1S_OK;
@@ -731,8 +774,8 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
   const bool any_host = s->on_device != 1 || d->on_device != 1;
   bool any_async = false;
   if (any_host && !sl.d_stage)
-    HIP_TRY(hipMalloc((void **)&sl.d_stage, sl.stage_bytes_per_frame * batch));
-  uint8_t *stage = any_host ? sl.d_stage + sl.stage_bytes_per_frame * sl.count : nullptr;
+    HIP_TRY(hipMalloc((void **)&sl.d_stage.p, lay.stage_frame * batch));
+  uint8_t *stage = any_host ? sl.d_stage + lay.stage_frame * sl.count : nullptr;
   for (int side = 0; side < 2; ++side) {
     const g1s_frame_t *f = side ? d : s;
     for (uint32_t c = 0; c < np; ++c) {
@@ -827,13 +870,13 @@ Geom g1s_diff::batch_geom(const Slot &sl) const {
   return g;
 }
 
-// A batch runs in two halves.  Front: zero fills and the pixel pass (K0, HBM bound) on the main stream,
-// then the flat-block finder, the window planes and the area lists -- small latency-bound kernels -- on the
-// side stream.  Back: the accumulation kernels on the main stream, the records D2H, the hand-over to the
-// drainer.  The back half of batch N is queued behind the front half of batch N + 1: the main stream runs
-// K0(N + 1), accumulation(N), K0(N + 2), ... back to back (the big kernels never share the chip, which
-// only stretches them), and the side stream's chain of N + 1 -- a few thousand waves, ~0.1 ms of latency --
-// runs next to accumulation(N) and is long done when accumulation(N + 1) comes up.
+// A batch runs in two halves.  Front: the frame table and the zero fills on the upload stream, then the finder chain
+// (k1_moments -- the only pass over pixels outside the flat blocks' tiles --, certify, the literal blocks, select, the unit
+// lists: after the first, small latency-bound kernels) on the side stream.  Back: the accumulation kernels on the main
+// stream, the results' D2H, the hand-over to the drainer.  The back half of batch N is queued behind the front half of
+// batch N + 1: the main stream runs accumulation(N), accumulation(N + 1), ... back to back (the big kernels never share
+// the chip, which only stretches them), and the side stream's chain of N + 1 runs next to accumulation(N) and is long
+// done when accumulation(N + 1) comes up.
 int g1s_diff::submit(int si) {
   Slot &sl = slots[si];
   if (sl.count == 0) return G1S_OK;
@@ -890,8 +933,7 @@ int g1s_diff::launch_front(int si) {
   hipStream_t fstream = (switches().one_stream || timing || !ss.flat) ? stream : ((si & 1) && switches().side2 && ss.flat2 ? ss.flat2 : ss.flat);
   // the frame table: pinned host copy -> device, on the upload stream (idle: done long before the main
   // stream gets here); per-kernel timing / one-stream mode: in line
-  FrameTable ft;
-  ft.f = reinterpret_cast<const FramePlanes *>(sl.d_planes);
+  const FrameTable ft{sl.d_planes};
   hipStream_t up = (fstream == stream || !ss.upload) ? stream : ss.upload;
   if (sl.async_in) {  // queued frame copies: on the upload stream; everything below waits for `up`
     hipStream_t cs = ss.upload ? ss.upload : stream;
@@ -909,20 +951,15 @@ int g1s_diff::launch_front(int si) {
   HIP_TRY(hipMemcpyAsync(sl.d_planes, sl.h_planes, sizeof(FramePlanes) * B, hipMemcpyHostToDevice, up));
   if (!sl.timed) kmark(sl, up, "k_zero");
   {
-    // all per-batch zero fills in one launch: records, lag / masked accumulators, bad flags + list counters
+    // all per-batch zero fills in one launch: the records, the counters and flags the kernels add to or set
     ZeroJob z{};
-    z.ptr[0] = reinterpret_cast<uint32_t *>(sl.d_records);
-    z.ndw[0] = (uint32_t)(L.size * B / 4);
-    z.ptr[1] = reinterpret_cast<uint32_t *>(sl.d_mu) + (size_t)batch * m_nunits * kMUnitDwords;  // unit counts (2 lists), any-deferred flags
-    z.ndw[1] = 3 * (uint32_t)batch;
-    z.ptr[3] = reinterpret_cast<uint32_t *>(sl.d_mu) + (size_t)batch * m_nunits * kMUnitDwords + 3 * (size_t)batch;  // deferred-block flags
-    z.ndw[3] = (uint32_t)(m_only_bytes / 4);
-    if (switches().wide && sl.d_wu) {
-      z.ptr[6] = reinterpret_cast<uint32_t *>(sl.d_wu + w_off_lbad);  // luma units whose L left int8
-      z.ndw[6] = (uint32_t)(w_lbad_bytes / 4);
-    }
-    z.ptr[5] = reinterpret_cast<uint32_t *>(sl.d_k1) + (size_t)g.nblocks * batch * (kMomInts + 1);  // literal-list counts
-    z.ndw[5] = (uint32_t)batch;
+    int nz = 0;
+    auto fill = [&](uint8_t *base, size_t off, size_t bytes) { z.ptr[nz] = reinterpret_cast<uint32_t *>(base + off), z.ndw[nz++] = (uint32_t)(bytes / 4); };
+    fill(sl.d_records, 0, L.size * B);
+    fill(sl.d_mu, lay.mu_count, lay.mu_only - lay.mu_count);  // unit counts (2 lists) and, behind them, the any-deferred flags
+    fill(sl.d_mu, lay.mu_only, lay.mu_only_bytes);            // deferred-block flags
+    fill(sl.d_k1, lay.k1_count, lay.k1 - lay.k1_count);       // literal-list counts
+    if (switches().wide && sl.d_wu) fill(sl.d_wu, lay.wu_lbad, lay.wu_lbad_bytes);  // luma units whose L left int8
     // (on the upload stream too: the slot is free, its buffers can be zeroed while the main stream is still busy
     //  with earlier batches)
     hipLaunchKernelGGL(k_zero, dim3(256), dim3(256), 0, up, z);
@@ -933,27 +970,27 @@ int g1s_diff::launch_front(int si) {
     HIP_TRY(hipStreamWaitEvent(stream, ss.table_done[si], 0));
     HIP_TRY(hipStreamWaitEvent(fstream, ss.table_done[si], 0));  // (the table goes by the upload stream only when the finder chain has a side stream)
   }
-  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[0], fstream));
+  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvStart], fstream));
   {
     // flat-block features: integer moments + certified evaluation; the literal f64 kernel only for
     // the blocks the certificate leaves open (G1S_K1_LITERAL=1 / g1s_diff_set_flat_finder: for every block)
     const int literal_mode = flat_literal ? flat_literal : switches().k1_literal;
     const int force_literal = literal_mode ? 1 : 0;
-    int32_t *mom = sl.d_k1;
+    int32_t *mom = reinterpret_cast<int32_t *>(sl.d_k1 + lay.k1_moments);
     CertifyLists cl;
-    cl.list = reinterpret_cast<uint32_t *>(sl.d_k1) + (size_t)g.nblocks * batch * kMomInts;
-    cl.count = cl.list + (size_t)g.nblocks * batch;
+    cl.list = reinterpret_cast<uint32_t *>(sl.d_k1 + lay.k1_list);
+    cl.count = reinterpret_cast<uint32_t *>(sl.d_k1 + lay.k1_count);
     cl.global = literal_mode == 0 ? 1 : 0;  // (the default chain: one sequence for the launch; "every block literally": per-frame lists)
     {
       // the finder's moments of the luma source: the only pass over pixels that are not in a flat block's tile
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[5], fstream));
+      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomStart], fstream));
       {  // (also when every block is evaluated literally: the record's luma_sum comes from the moments)
         const dim3 mg((g.nblocks + 7) / 8, B);
         kmark(sl, fstream, g.src_bps == 1 ? "k1_moments<1>" : "k1_moments<2>");
         if (g.src_bps == 1) hipLaunchKernelGGL(k1_moments<1>, mg, dim3(256), 0, fstream, ft, g, mom);
         else hipLaunchKernelGGL(k1_moments<2>, mg, dim3(256), 0, fstream, ft, g, mom);
       }
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[4], fstream));
+      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomEnd], fstream));
     }
     kmark(sl, fstream, "k1_certify");
     hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
@@ -981,23 +1018,23 @@ int g1s_diff::launch_front(int si) {
 #undef G1S_FB
     }
   }
-  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[1], fstream));
+  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvFinderEnd], fstream));
   const bool w_lists = wide_ok(g);  // the wide chain: the unit lists come out of the select kernel
   WUnitParams wup{};
   if (w_lists) {
     for (int k = 0; k < 2; ++k) {
-      wup.units[k] = reinterpret_cast<uint32_t *>(sl.d_wu + w_off_units[k]);
+      wup.units[k] = reinterpret_cast<uint32_t *>(sl.d_wu + lay.wu_units[k]);
       wup.ncell[k] = w_ncell[k];
       wup.gx[k] = w_gx[k];
     }
-    wup.count = reinterpret_cast<uint32_t *>(sl.d_wu + w_off_count);
+    wup.count = reinterpret_cast<uint32_t *>(sl.d_wu + lay.wu_count);
     wup.ub[0] = 4;
     wup.ub[1] = w_ub_c;
   }
   kmark(sl, fstream, w_lists ? "k2w_select_units" : "k2_flat_select");
   if (w_lists) hipLaunchKernelGGL(k2w_select_units, dim3(B, g.nplanes == 3 ? 2 : 1), dim3(kK2Threads), 0, fstream, g, sl.d_records, (const uint8_t *)sl.d_flags, wup);
   else hipLaunchKernelGGL(k2_flat_select, dim3(B), dim3(kK2Threads), 0, fstream, g, sl.d_records, sl.d_flags);
-  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[2], fstream));
+  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvSelectEnd], fstream));
   if (!w_lists) {
     // the unit lists (chunks with a flat block) need the flat mask (the wide chain: k2w_select_units has built them)
     const MParams mp = make_mparams(sl);
@@ -1030,10 +1067,10 @@ bool g1s_diff::wide_gen(const Geom &g) { return g.src_bps != g.den_bps || g.src_
 
 MParams g1s_diff::make_mparams(const Slot &sl) const {
   MParams mp;
-  mp.units = reinterpret_cast<uint32_t *>(sl.d_mu);
-  mp.unit_count = mp.units + (size_t)batch * m_nunits * kMUnitDwords;
-  mp.only_any = mp.unit_count + 2 * batch;
-  mp.only = reinterpret_cast<uint8_t *>(mp.only_any + batch);
+  mp.units = reinterpret_cast<uint32_t *>(sl.d_mu + lay.mu_units);
+  mp.unit_count = reinterpret_cast<uint32_t *>(sl.d_mu + lay.mu_count);
+  mp.only_any = reinterpret_cast<uint32_t *>(sl.d_mu + lay.mu_any);
+  mp.only = sl.d_mu + lay.mu_only;
   mp.partials = sl.d_mpart;
   mp.nunits = m_nunits;
   return mp;
@@ -1043,8 +1080,7 @@ MParams g1s_diff::make_mparams(const Slot &sl) const {
 // deferred blocks
 int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
   const uint32_t B = sl.count;
-  FrameTable ft;
-  ft.f = reinterpret_cast<const FramePlanes *>(sl.d_planes);  // (uploaded by the front half)
+  const FrameTable ft{sl.d_planes};  // (uploaded by the front half)
   const MParams mp = make_mparams(sl);
   const bool chroma = g.nplanes == 3;
   WParams wq;
@@ -1053,7 +1089,7 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
   wq.partials = mp.partials;
   wq.only = mp.only;
   wq.only_any = mp.only_any;
-  wq.lbad = sl.d_wu + w_off_lbad;
+  wq.lbad = sl.d_wu + lay.wu_lbad;
   wq.lplane = sl.d_lplane;
   wq.lpitch = w_lpitch;
   wq.lframe_bytes = w_lframe;
@@ -1074,8 +1110,8 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
   const int G_cap = std::max(Gk[0], Gk[1]);
   wq.wg_cap = G_cap;
   auto set_kind = [&](int k) {
-    wq.units = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_units[k]);
-    wq.count = reinterpret_cast<const uint32_t *>(sl.d_wu + w_off_count) + k;  // (stride 2: see the kernel)
+    wq.units = reinterpret_cast<const uint32_t *>(sl.d_wu + lay.wu_units[k]);
+    wq.count = reinterpret_cast<const uint32_t *>(sl.d_wu + lay.wu_count) + k;  // (stride 2: see the kernel)
     wq.ncell = w_ncell[k];
     wq.wgs = Gk[k];
   };
@@ -1149,15 +1185,14 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
 // exact int32 kernel for the few blocks next to a residual outside int8
 int g1s_diff::accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
   const uint32_t B = sl.count;
-  FrameTable ft;
-  ft.f = reinterpret_cast<const FramePlanes *>(sl.d_planes);  // (uploaded by the front half)
+  const FrameTable ft{sl.d_planes};  // (uploaded by the front half)
   const MParams mp = make_mparams(sl);
   FParams fq;
   fq.ft = ft;
   fq.units = mp.units;
   fq.unit_count = mp.unit_count;
   fq.partials = mp.partials;
-  fq.ustats = reinterpret_cast<int32_t *>(mp.only + m_only_bytes);
+  fq.ustats = reinterpret_cast<int32_t *>(sl.d_mu + lay.mu_ustats);
   fq.nunits = m_nunits;
   int G_kind[2] = {m_wgs_per_frame(m_nunits, (int)B, 0), m_wgs_per_frame(m_nunits, (int)B, 1)};  // luma launch, chroma launch
   for (int &Gk : G_kind)
@@ -1232,22 +1267,7 @@ int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
   // the per-frame half of the fold where the records lie: the host gets 27 KB of latest state a frame instead of the record
   // (the batch's last record still comes back: g1s_diff_last_record)
   const size_t blob = latest_blob_size(lag), scr = latest_scratch_bytes((uint32_t)L.nblocks);
-  if (sl.latest_cap < blob * batch) {
-    if (sl.d_latest) (void)hipFree(sl.d_latest);
-    if (sl.h_latest) (void)hipHostFree(sl.h_latest);
-    sl.d_latest = sl.h_latest = nullptr;
-    sl.latest_cap = 0;
-    HIP_TRY(hipMalloc((void **)&sl.d_latest, blob * batch));
-    HIP_TRY(hipHostMalloc((void **)&sl.h_latest, blob * batch, hipHostMallocDefault));
-    sl.latest_cap = blob * batch;
-  }
-  if (sl.lscratch_cap < scr * batch) {
-    if (sl.d_lscratch) (void)hipFree(sl.d_lscratch);
-    sl.d_lscratch = nullptr;
-    sl.lscratch_cap = 0;
-    HIP_TRY(hipMalloc((void **)&sl.d_lscratch, scr * batch));
-    sl.lscratch_cap = scr * batch;
-  }
+  HIP_TRY(sl.ensure_latest(blob * batch, scr * batch));
   LatestJob job{};
   job.records = sl.d_records;
   job.L = L;
@@ -1271,28 +1291,7 @@ int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
     HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
     HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
   } else {
-    if (!ss.latest) {
-      // two streams in the main stream's priority class (the least urgent: the kernel fills in; measured 4 % better than the
-      // runtime's default class and than the side stream's, profiles/r05_device_latest.txt)
-      int plo = 0, phi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-      // (made into locals and handed to the stream set -- which goes back to the process-wide cache -- only when ALL of them
-      //  exist: a failure half way must not leave a set that looks complete with a null stream or event in it)
-      hipStream_t made[2] = {nullptr, nullptr};
-      hipEvent_t made_ev[kSlots] = {};
-      bool ok = true;
-      for (hipStream_t &st : made) ok = ok && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, plo) == hipSuccess;
-      for (int i = 0; i < kSlots; ++i) ok = ok && hipEventCreateWithFlags(&made_ev[i], hipEventDisableTiming) == hipSuccess;
-      if (!ok) {
-        for (hipStream_t st : made)
-          if (st) (void)hipStreamDestroy(st);
-        for (hipEvent_t e : made_ev)
-          if (e) (void)hipEventDestroy(e);
-        return fail_hip("the device half's streams / events could not be created");
-      }
-      ss.latest = made[0], ss.latest2 = made[1];
-      for (int i = 0; i < kSlots; ++i) ss.latest_done[i] = made_ev[i];
-    }
+    if (!ensure_latest_streams(ss)) return fail_hip("the device half's streams / events could not be created");
     hipStream_t lst = (si & 1) ? ss.latest2 : ss.latest;  // (why two: StreamSet)
     HIP_TRY(hipStreamWaitEvent(lst, ss.kernels_done[si], 0));
     kmark(sl, lst, latest_kernel_name());  // (trace mode)
@@ -1321,7 +1320,7 @@ int g1s_diff::launch_back(int si) {
   int rc = wide_ok(g) ? accumulate_wide(sl, si, g, stream, side) : accumulate_stream(sl, si, g, stream, side);
   if (rc) return rc;
   kmark(sl, stream, nullptr);
-  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[3], stream));
+  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvEnd], stream));
   HIP_TRY(hipGetLastError());
   rc = copy_out(sl, si, stream);
   if (rc) return rc;
@@ -1419,21 +1418,21 @@ int g1s_diff::drain_front(int si) {
     // (one pair of events around the batch's chain: what the chain takes alone on the chip with nothing between its kernels
     //  but their own dependencies -- the per-kernel events below each put a barrier packet and a signal between two launches)
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[0], sl.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvStart], sl.ev[kEvEnd]));
     stats.ms_chain += ms;
     stats.chain_batches += 1;
   } else if (sl.timed) {
     float ms = 0;
     float ms_mom = 0;  // the finder's moments pass
-    HIP_TRY(hipEventElapsedTime(&ms_mom, sl.ev[5], sl.ev[4]));
-    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_mom, sl.ev[kEvMomStart], sl.ev[kEvMomEnd]));
+    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvStart], sl.ev[kEvFinderEnd]));
     stats.ms_flat_features += ms;
     stats.ms_residual += ms_mom;
-    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[1], sl.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvFinderEnd], sl.ev[kEvSelectEnd]));
     stats.ms_flat_select += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[2], sl.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvSelectEnd], sl.ev[kEvEnd]));
     stats.ms_ar_accumulate += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[0], sl.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvStart], sl.ev[kEvEnd]));
     stats.ms_total_gpu += ms;
     {
       std::lock_guard<std::mutex> lk(ktimes_mutex);
@@ -1447,8 +1446,7 @@ int g1s_diff::drain_front(int si) {
     }
     {
       std::vector<uint32_t> cnt(batch);
-      HIP_TRY(hipMemcpy(cnt.data(), reinterpret_cast<uint32_t *>(sl.d_k1) + (size_t)geom.nblocks * batch * (kMomInts + 1),
-                        sizeof(uint32_t) * batch, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(cnt.data(), sl.d_k1 + lay.k1_count, sizeof(uint32_t) * batch, hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < sl.count; ++i) stats.literal_blocks += cnt[i];
     }
   }
@@ -1500,7 +1498,7 @@ int g1s_diff::drain_front(int si) {
       h->reserved = 0;  // (the kernel's note to this function; the blob a rank sends is the blob the host half would make)
       if (!latest_only && view_of_blob(b, bl, lag, views[i]) != G1S_OK) rc = G1S_ERR_INVALID;
     }
-    if (latest_only) latest_stage.assign(sl.h_latest, sl.h_latest + bl * sl.count);
+    if (latest_only) latest_stage.assign(sl.h_latest.p, sl.h_latest + bl * sl.count);
     if (sl.count) finish_record((int)sl.count - 1);
     ms_fold_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc) {
@@ -1631,12 +1629,11 @@ void g1s_diff::release() {
       std::lock_guard<std::mutex> lk(g_cache_mutex);
       if (g_slot_cache.size() < 8) {
         sl.count = 0;
-        g_slot_cache.push_back(CachedSlot{slot_key, sl});
-        sl = Slot{};
+        g_slot_cache.push_back(CachedSlot{device, lay, geom.W, geom.H, geom.xdec, geom.ydec, geom.nplanes, std::move(sl)});
         continue;
       }
     }
-    free_slot(sl);
+    sl = Slot{};  // (frees what the slot holds)
   }
   for (auto &pe : h2d_pending) (void)hipEventDestroy(pe.second);
   h2d_pending.clear();

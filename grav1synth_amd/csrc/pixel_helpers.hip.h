@@ -290,7 +290,7 @@ __device__ __forceinline__ void half_sums_split16(const int (&v)[16], int (&x)[4
 // k_zero: every per-batch zero fill in ONE launch (records, accumulators, flags, counters);
 // separate memset nodes each cost a dispatch gap in the launch chain.
 // ---------------------------------------------------------------------------------
-constexpr int kZeroBufs = 7;
+constexpr int kZeroBufs = 5;
 struct ZeroJob {
   uint32_t *ptr[kZeroBufs];
   uint32_t ndw[kZeroBufs];  // dwords
