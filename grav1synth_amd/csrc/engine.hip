@@ -348,8 +348,11 @@ struct CachedSlot {
   int device;
   SlotLayout lay;
   // Not needed for the buffers to fit (the layout says that), and compared all the same: without them slots would move between
-  // geometries whose layouts happen to be equal, and whether a kernel reads bytes of a slot that nobody wrote for THIS
-  // geometry (the L plane's slack row, the parked entries around a d_wu slice) has not been examined.
+  // geometries whose layouts happen to be equal.  What has been examined is reuse at ONE geometry (tests/test_gpu_records.py,
+  // every record of every frame against the oracle, both chains): a slot used again inside a generator and a slot handed from a
+  // closed generator to the next, going from damaged (deferred blocks, literal lists) and busy content to flat and plane-distinct
+  // content and back, full batches followed by short ones.  A slot that moves to ANOTHER geometry of the same layout (the L
+  // plane's slack row, the parked entries around a d_wu slice would then hold that geometry's bytes) has not been examined.
   int W, H, xdec, ydec, nplanes;
   Slot slot;
 };

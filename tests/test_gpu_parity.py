@@ -14,7 +14,7 @@ import torch
 
 from grav1synth_amd.diff import DiffGenerator, Frame, format_tbl
 from grav1synth_amd.synth import SynthSpec, make_pair
-from tests.helpers import np_pair, oracle_run
+from tests.helpers import np_pair, oracle_run, oracle_shadow, record_mismatches
 
 pytestmark = pytest.mark.gpu
 
@@ -66,27 +66,7 @@ def test_records_and_table_match_oracle(case):
         g.diff_frame(Frame(s, spec.xdec, spec.ydec), Frame(d, spec.xdec, spec.ydec))
         g.sync()
         r = g.last_record()
-        om, rm = o.flat_mask(), r.flat_mask()
-        if not np.array_equal(om, rm):
-            mismatches.append(f"frame {k}: flat mask differs at {np.argwhere(om != rm)[:5].tolist()}")
-        osc, rsc = o.scores(), r.scores()
-        if not np.array_equal(osc.view(np.uint32), rsc.view(np.uint32)):
-            mismatches.append(f"frame {k}: score bits differ ({(osc.view(np.uint32) != rsc.view(np.uint32)).sum()} blocks)")
-        flat = om.ravel() != 0
-        for c in range(nplanes):
-            S, Sb, nobs = o.ar_sums(c)
-            S2, Sb2, nobs2 = r.ar_sums(c)
-            if nobs != nobs2 or not np.array_equal(S, S2) or not np.array_equal(Sb, Sb2):
-                mismatches.append(f"frame {k} plane {c}: AR sums differ (nobs {nobs} vs {nobs2})")
-            ls, sd, sd2 = o.block_stats(c)
-            ls2, sd_2, sd2_2 = r.block_stats(c)
-            # the oracle records statistics only for blocks it measures (flat, > 32 samples)
-            # (per plane: a chroma corner block of <= 32 samples is skipped while its luma block is measured)
-            meas = flat & ((sd2 != 0) | (sd != 0) | ((ls != 0) if c == 0 else False))
-            if c == 0 and not np.array_equal(ls[meas], ls2[meas]):
-                mismatches.append(f"frame {k}: luma block sums differ")
-            if not np.array_equal(sd[meas], sd_2[meas]) or not np.array_equal(sd2[meas], sd2_2[meas]):
-                mismatches.append(f"frame {k} plane {c}: block noise sums differ")
+        mismatches.extend(record_mismatches(oracle_shadow(o, nplanes), r, f"frame {k}"))
 
     tbl, _ = oracle_run(spec, range(nframes), lag, chroma, collect=collect)
     mine = format_tbl(g.finish())

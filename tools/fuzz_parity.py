@@ -2,7 +2,9 @@
 """tools/fuzz_parity.py [N] [SEED] [WMAX HMAX] -- random geometries / depths / subsamplings / lags through the oracle comparison
 of tests/test_gpu_parity.py (records and table, bit for bit).  Prints the failing specs, if any.
 FUZZ_ALIGN=16: widths rounded down to multiples of 16 -- every case then runs the WIDE chain (whole 8-sample words in every
-plane: engine.hip wide_ok); with random widths one case in sixteen does, the others take the fallback chain."""
+plane: engine.hip wide_ok); with random widths one case in sixteen does, the others take the fallback chain.
+FUZZ_CONTENT=distinct: the second sweep draws its frames from tests/content.py (per-plane taps, gain laws and luma weights; a random
+kind for every frame) instead of synth.py; the first sweep is tests/test_gpu_parity.py's own case and stays on synth.py."""
 import os, random, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from grav1synth_amd.synth import SynthSpec
@@ -12,6 +14,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 WMAX, HMAX = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (420, 300)
 ALIGN = int(os.environ.get("FUZZ_ALIGN", "1"))
+CONTENT = os.environ.get("FUZZ_CONTENT", "synth")
 bad = 0
 t0 = time.time()
 for k in range(n):
@@ -37,6 +40,7 @@ print(f"{n} single-batch cases, {bad} failures, {time.time() - t0:.0f} s")
 from fractions import Fraction
 import numpy as np
 from grav1synth_amd.diff import DiffGenerator, Frame, format_tbl
+from tests.content import make_frames
 from tests.helpers import np_pair
 from tests.oracle_binding import OracleDiff, format_tbl as oracle_tbl
 
@@ -57,9 +61,13 @@ for k in range(n // 4):
         cut = rng.randint(1, nf - 1) if rng.random() < 0.35 else nf   # noise gain changes there: a new segment
         ss2 = SynthSpec(w, h, sbd, xdec=xd, ydec=yd, textured=ss.textured, gain_scale=3)
         for f in range(nf):
-            s, _ = np_pair(ss if f < cut else ss2, f)
-            _, d = np_pair(ds, f)
-            if damage:
+            if CONTENT == "distinct":
+                kind = rng.choice(["distinct", "flat", "busy", "clamped", "damaged"] if damage else ["distinct", "flat", "busy", "clamped"])
+                s, d = make_frames(kind, w, h, sbd, xd, yd, f, seed=k)[0], make_frames(kind, w, h, dbd, xd, yd, f, seed=k)[1]
+            else:
+                s, _ = np_pair(ss if f < cut else ss2, f)
+                _, d = np_pair(ds, f)
+            if damage and CONTENT != "distinct":
                 nr = np.random.default_rng(rng.randint(0, 1 << 30))
                 d = [p.copy() for p in d]
                 for c in range(len(d)):
