@@ -131,6 +131,16 @@ class G1SFilterDesc(C.Structure):
     ]
 
 
+class G1SGrainOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("device", C.c_int32),
+        ("batch_frames", C.c_uint32),
+        ("clip_to_restricted_range", C.c_uint32),
+        ("mc_identity", C.c_uint32),
+    ]
+
+
 NEXT_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(G1SFrame))
 
 # every symbol include/g1s_diff.h declares: (name, restype, argtypes)
@@ -219,6 +229,16 @@ SYMBOLS = [
     ("g1s_diff_y4m_files_sharded", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.c_char_p,
                                               C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                               C.c_char_p, C.c_size_t]),
+    ("g1s_grain_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SGrainOpts)]),
+    ("g1s_grain_frame", C.c_int, [C.c_void_p, C.POINTER(G1SSegment), C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
+    ("g1s_grain_sync", C.c_int, [C.c_void_p]),
+    ("g1s_grain_templates", C.c_int, [C.c_void_p, C.POINTER(G1SSegment), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    ("g1s_grain_gaussian_sequence", C.POINTER(C.c_int16), []),
+    ("g1s_grain_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_grain_last_error", C.c_char_p, [C.c_void_p]),
+    ("g1s_grain_free", None, [C.c_void_p]),
+    ("g1s_grain_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SGrainOpts), C.c_char_p, C.c_size_t]),
 ]
 
 _lib = None

@@ -79,6 +79,15 @@ def build_parser() -> argparse.ArgumentParser:
     e.add_argument("-o", "--output", required=True, help="The path to the output file.")
     e.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
     e.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    r = sub.add_parser("render", help="Synthesizes the film grain of a table onto a video (y4m input and output): what a decoder "
+                                      "shows for the clip encoded with the table (AV1 specification, film grain synthesis process).")
+    r.add_argument("input", help="The (denoised) file to put grain on.")
+    r.add_argument("-g", "--grain", required=True, help="The film grain table.")
+    r.add_argument("-o", "--output", required=True, help="The path to the output .y4m.")
+    r.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
+    r.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    r.add_argument("--clip-restricted", action="store_true",
+                   help="clip the output to the restricted (studio) range, the sequence's clip_to_restricted_range")
     return ap
 
 
@@ -134,6 +143,23 @@ def estimate_command(source: str, output: str, overwrite: bool = False, device: 
     return frames
 
 
+def render_command(input: str, table: str, output: str, overwrite: bool = False, device: int = -1, clip_restricted: bool = False,
+                   confirm=_confirm) -> int:
+    """The refusals of `diff` and `estimate`, then every frame of the input through the table's lookup and the film grain
+    synthesis process.  Returns the frame count, -1 after a refusal."""
+    from .grain import render_y4m_file
+
+    if _same_path(input, output) or _same_path(table, output):
+        log.error(SAME_AS_OUTPUT)
+        return -1
+    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
+        log.warning(NOT_OVERWRITING)
+        return -1
+    frames = render_y4m_file(input, table, output, device=device, clip_to_restricted_range=clip_restricted)
+    log.info("Done, wrote output file to %s", output)
+    return frames
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
@@ -155,6 +181,12 @@ def main(argv: Optional[List[str]] = None) -> int:
     elif args.command == "estimate":
         try:
             estimate_command(args.source, args.output, args.overwrite, args.device)
+        except Exception as e:
+            log.error("%s", e)
+            return 1
+    elif args.command == "render":
+        try:
+            render_command(args.input, args.grain, args.output, args.overwrite, args.device, args.clip_restricted)
         except Exception as e:
             log.error("%s", e)
             return 1

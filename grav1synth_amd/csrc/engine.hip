@@ -1655,6 +1655,8 @@ void g1s_diff::release() {
 extern "C" {
 
 const char *g1s_last_global_error(void) { return g_global_error.c_str(); }
+// (grain.hip) g1s_grain_new reports through the same thread-local text
+void g1s_set_global_error_(const char *text) { g_global_error = text ? text : ""; }
 
 g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_depth,
                          uint32_t denoised_bit_depth, const g1s_opts_t *opts) {

@@ -840,7 +840,7 @@ int NoiseFold::push_latest(FrameLatest &fl) {
     }
   }
   if (y_model_different) {
-    const uint64_t cur = frame_count_ * 10000000ULL * (uint64_t)fps_den_ / (uint64_t)fps_num_;
+    const uint64_t cur = frame_time(frame_count_, fps_num_, fps_den_);
     table_.push_back(grain_parameters(prev_timestamp_, cur));
     save_latest();
     prev_timestamp_ = cur;
@@ -1055,7 +1055,7 @@ int NoiseFold::push_latest_many(const FrameView *fl, size_t n, const ParallelFor
     }
     if (cut) {  // a new segment starts with frame m; the states behind it were built on a combined model that is gone
       for (int c = 0; c < 3; ++c) load_plane(latest_[c], fl[i + m].st[c]);
-      const uint64_t cur = frame_count_ * 10000000ULL * (uint64_t)fps_den_ / (uint64_t)fps_num_;
+      const uint64_t cur = frame_time(frame_count_, fps_num_, fps_den_);
       table_.push_back(grain_parameters(prev_timestamp_, cur));
       save_latest();
       prev_timestamp_ = cur;

@@ -19,6 +19,12 @@ namespace g1s {
 
 constexpr int kNumBins = 20;
 
+// Presentation time of frame `frame` (0-based) in the table's 10 MHz units: where the fold cuts its segments, and so
+// the time `render` looks a frame up by -- frame k of the video a table was made from falls into the segment it came from.
+inline uint64_t frame_time(uint64_t frame, int64_t fps_num, int64_t fps_den) {
+  return frame * 10000000ULL * (uint64_t)fps_den / (uint64_t)fps_num;
+}
+
 // Dense square system A x = b with the elimination order of the reference
 // solver (libaom linsolve == av1-grain solver::util::linsolve).
 struct LinearSystem {

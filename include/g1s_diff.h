@@ -391,6 +391,52 @@ void g1s_estimate_free(g1s_estimate_t *);
 /* The command's output (src/main.rs:596-603): "filmgrn1\n" then "{:.3}\n" per frame.  Bytes written or G1S_ERR_CAPACITY. */
 long g1s_format_estimates(const double *estimates, size_t n, char *buf, size_t cap);
 
+/* ---- `render`: AV1 film grain synthesis on the device (the inverse of `diff`: a table's grain onto frames) ----
+ * The film grain synthesis process of the AV1 specification (clause 7.18.3: random number process, generate grain
+ * process, scaling lookup initialisation, add noise synthesis process), integer-exact, written from the standard.
+ * A g1s_segment_t carries the film grain parameters as a table does: AR coefficients as signed values, ar_coeff_shift
+ * (6..9) and scaling_shift (8..11) as the shifts themselves, cb_mult / cb_luma_mult / cb_offset as coded (128, 128 and
+ * 256 are subtracted where the standard does).  Scaling points must have strictly increasing values.
+ * Frames queue up to batch_frames (0 = 32; at most 256) and go out as two kernel launches per batch on the
+ * synthesizer's own stream.  Errors are sticky: after a failure every call returns it (g1s_grain_last_error). */
+typedef struct {
+  uint32_t struct_size;              /* sizeof(g1s_grain_opts_t) */
+  int32_t device;                    /* HIP device ordinal; -1 = current device */
+  uint32_t batch_frames;
+  uint32_t clip_to_restricted_range; /* the sequence's clip_to_restricted_range: 16..235 (240 chroma) << (bit depth - 8) */
+  uint32_t mc_identity;              /* matrix_coefficients == MC_IDENTITY: chroma clips like luma under the flag above */
+} g1s_grain_opts_t;
+typedef struct g1s_grain g1s_grain_t;
+/* bit_depth 8, 10 or 12.  NULL on failure, reason from g1s_last_global_error().  opts == NULL: current device, defaults. */
+g1s_grain_t *g1s_grain_new(uint32_t bit_depth, const g1s_grain_opts_t *opts);
+/* One frame.  params->random_seed is THE grain_seed of this frame (g1s_tbl_segment_for has already advanced it); the
+ * struct is copied.  params == NULL (no segment covers the frame: apply_grain = 0): *out becomes a copy of *in.
+ * in / out follow g1s_frame_t.on_device independently: 0 = host (in: copied before the call returns; out: written by
+ * g1s_grain_sync at the latest), 1 = device, 2 = pinned host (copies queued).  Device and pinned planes of in must stay
+ * valid and unmodified, and every plane of out must stay valid, until g1s_grain_sync.  in and out must be DISTINCT,
+ * non-overlapping buffers: a chroma sample is scaled by the co-located INPUT luma, which another workgroup may already
+ * have replaced if the kernel wrote in place.  in and out have the same geometry; a frame whose geometry differs from the
+ * one before it drains the queue first (the host planes of queued out frames are then complete). */
+int g1s_grain_frame(g1s_grain_t *, const g1s_segment_t *params, const g1s_frame_t *in, g1s_frame_t *out);
+/* Launches what is queued and waits: the out planes of every frame handed over are complete. */
+int g1s_grain_sync(g1s_grain_t *);
+/* Stage 1 alone, for tests: the grain templates (luma 73 x 82; cb, cr 38 or 73 rows x 44 or 82 columns by ydec / xdec,
+ * row-major, no padding) and the three 256-entry scaling tables for these parameters.  Any output may be NULL. */
+int g1s_grain_templates(g1s_grain_t *, const g1s_segment_t *params, uint32_t xdec, uint32_t ydec,
+                        int16_t *luma, int16_t *cb, int16_t *cr, uint8_t lut[3][256]);
+/* Gaussian_Sequence[2048] of the specification's "Additional tables". */
+const int16_t *g1s_grain_gaussian_sequence(void);
+/* HIP-event time of the kernels so far, milliseconds, and the frames they covered (enable = 1: timed from the next
+ * batch on; a timed batch is waited for).  tools/bench_grain.py. */
+int g1s_grain_set_timing(g1s_grain_t *, int enable, double *ms_template, double *ms_apply, uint64_t *frames);
+const char *g1s_grain_last_error(const g1s_grain_t *);
+void g1s_grain_free(g1s_grain_t *);
+/* `render INPUT -g TABLE -o OUTPUT`: every frame of a .y4m through the table's lookup (g1s_parse_tbl,
+ * g1s_tbl_segment_for at the frame's presentation time: frame k of a video lies at the time the fold gives a segment
+ * that starts with frame k), written as .y4m (the input's header line, "FRAME\n", the planes without padding).
+ * Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
+int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, const g1s_grain_opts_t *opts, char *err, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
