@@ -264,6 +264,7 @@ std::mutex g_merge_pool_mutex;
 // cost the same whatever the frame's size and the host half's cost goes with the blocks: same box, 1080p (2 040 blocks) the host half
 // 1.08 - 1.10 x the device half, 4K (8 160 blocks) the device half 1.13 x the host half (profiles/r07_device_latest.txt)
 constexpr int kDeviceLatestMinBlocks = 4096;
+constexpr uint32_t kLatestWindowMinBatch = 64;  // frames a launch from which k4_latest gets a window of its own (g1s_diff::submit)
 constexpr int kSlots = 6;  // batches in flight: being filled, finder chain, accumulation, (the per-frame half on the device,) D2H, fold
 
 // What a slot owns: a HIP allocation or event, released when its holder goes.  Move-only; reads as the raw pointer it holds.
@@ -363,20 +364,24 @@ std::vector<CachedSlot> &g_slot_cache = *new std::vector<CachedSlot>;
 // Streams and their events are process-wide too (0.1-0.2 ms to create each); a generator borrows a set and
 // hands it back when it is freed:
 //   compute  main stream: the accumulation of one batch after the other, back to back -- k3w_pass x 2 and k3w_tail
-//            (the stream chain: its luma launch)
+//            (the stream chain: its luma launch); behind a batch's tail its k4_latest when the per-frame half of the fold
+//            runs on the device and the launches are wide (submit)
 //   flat     side stream (high priority): a batch's finder chain, select kernel and unit lists, next to the accumulation
-//            of the batch before (flat2: those of the odd slots under G1S_SIDE2)
+//            of the batch before (flat2: those of the odd slots under G1S_SIDE2) -- with the device half: next to the
+//            k4_latest of the batch before, and to nothing else (submit)
 //   copy     the results' D2H, behind the accumulation; in front of it the wide chain's chroma launch and tail under
 //            G1S_W_ASIDE, the stream chain's chroma launch and what follows unless G1S_F_SERIAL
 //   upload   the frame table (72 bytes a frame pair), k_zero and the queued copies of pinned host frames, ahead of everything
 struct StreamSet {
   int device = -1;
   hipStream_t compute = nullptr, copy = nullptr, flat = nullptr, flat2 = nullptr, upload = nullptr;
-  // k4_latest of the even / odd slots (made when a generator first runs the half on the device): the kernel is a few serial
-  // chains per frame and twice as long next to the accumulation launches as alone -- on ONE stream, with the blobs' copy behind
-  // it, a batch's half would only start when the half of the batch before had been copied out (period >= 1 040 us at 4K)
+  // k4_latest of the even / odd slots where it does NOT run on the main stream (launches of fewer than kLatestWindowMinBatch
+  // frames; made when a generator first needs them).  On a stream of its own the kernel's workgroups are not dispatched while
+  // another queue's launch still has workgroups to place: 615 us a 64-frame 4K launch in the job whatever the kernel takes
+  // alone (343 or 278), 520 us next to k1_moments alone (profiles/r09_latest_window.txt) -- on ONE stream, with the blobs' copy
+  // behind it, a batch's half would only start when the half of the batch before had been copied out
   hipStream_t latest = nullptr, latest2 = nullptr;
-  hipEvent_t latest_done[kSlots] = {};
+  hipEvent_t latest_done[kSlots] = {};  // a batch's k4_latest has ended: the blobs' copy waits for it
   int prio_side = 0;
   hipEvent_t kernels_done[kSlots] = {};
   hipEvent_t mask_done[kSlots] = {};
@@ -413,31 +418,26 @@ bool acquire_streams(int device, StreamSet &out) {
   for (int i = 0; i < kSlots && ok; ++i)
     ok = hipEventCreateWithFlags(&out.kernels_done[i], hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&out.mask_done[i], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&out.table_done[i], hipEventDisableTiming) == hipSuccess;
+         hipEventCreateWithFlags(&out.table_done[i], hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&out.latest_done[i], hipEventDisableTiming) == hipSuccess;
   return ok;
 }
-// The device half's two streams and their events, when a generator first runs that half.  All of them or none: made into
-// locals and handed to the set -- which goes back to the process-wide cache -- only when ALL exist, so that a failure half
-// way cannot leave a set that looks complete with a null stream or event in it.  In the main stream's priority class (the
-// least urgent: the kernel fills in; 4 % better than the runtime's default class and the side stream's, profiles/r05_device_latest.txt)
+// The device half's two streams, when a generator first runs that half outside the window.  Both or none.  In the main stream's
+// priority class (the least urgent: the kernel fills in; 4 % better than the runtime's default class and the side stream's,
+// profiles/r05_device_latest.txt)
 bool ensure_latest_streams(StreamSet &ss) {
   if (ss.latest) return true;
   int plo = 0, phi = 0;
   (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
   hipStream_t made[2] = {nullptr, nullptr};
-  hipEvent_t made_ev[kSlots] = {};
   bool ok = true;
   for (hipStream_t &st : made) ok = ok && hipStreamCreateWithPriority(&st, hipStreamNonBlocking, plo) == hipSuccess;
-  for (int i = 0; i < kSlots; ++i) ok = ok && hipEventCreateWithFlags(&made_ev[i], hipEventDisableTiming) == hipSuccess;
   if (!ok) {
     for (hipStream_t st : made)
       if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : made_ev)
-      if (e) (void)hipEventDestroy(e);
     return false;
   }
   ss.latest = made[0], ss.latest2 = made[1];
-  for (int i = 0; i < kSlots; ++i) ss.latest_done[i] = made_ev[i];
   return true;
 }
 void release_streams(StreamSet &ss) {
@@ -479,7 +479,9 @@ struct g1s_diff {
   SlotLayout lay{};  // the slots' memory (set_geometry)
   Slot slots[kSlots];
   int cur = 0;
-  int pending = -1;  // slot whose front half is queued and whose back half is not
+  int pending = -1;  // slot whose front half is queued and whose back half is not (not in the window: submit)
+  int last_back = -1;  // slot of the batch whose back half was queued last; -1: none since everything queued was drained
+  bool latest_window() const { return device_latest && batch >= kLatestWindowMinBatch; }  // (submit)
   // The API thread queues frames and launches batches; the drainer thread waits for a batch's records,
   // runs the fold on them and frees the slot.  Everything below dm is shared between the two.
   std::thread drainer;  // waits for a batch's records, runs the per-frame half of the fold on the pool
@@ -880,6 +882,18 @@ Geom g1s_diff::batch_geom(const Slot &sl) const {
 // batch N + 1: the main stream runs accumulation(N), accumulation(N + 1), ... back to back (the big kernels never share
 // the chip, which only stretches them), and the side stream's chain of N + 1 runs next to accumulation(N) and is long
 // done when accumulation(N + 1) comes up.
+// With the per-frame half of the fold on the device (device_latest) nothing is deferred and nothing runs beside an
+// accumulation launch: back(N) is queued with front(N), k4_latest(N) follows the tail of N on the main stream, and the first
+// pixel kernel of front(N + 1) waits for kernels_done[N] -- back(N) has to be queued before front(N + 1) can name that event.
+// The main stream runs luma(N), chroma(N), tail(N) alone on the chip, then k4_latest(N) (64 workgroups of serial f64 chains)
+// while the side stream runs the finder chain of N + 1 (a pass over HBM and small kernels): the two want different things and
+// are about as long, 270 and 260 us at 4K.  Period 850 - 865 us a 64-frame batch against 965 - 985 with the chain beside the
+// luma launch and k4_latest on a stream of its own (profiles/r09_latest_window.txt, which also has the three forms that lost).
+// That is for launches of kLatestWindowMinBatch frames or more (latest_window): k4_latest's time goes with a frame's blocks and
+// not with the launch's frames (a workgroup a frame), the chain's and the accumulation's with both, so in a narrow launch the
+// kernel is the longer side of the window and the chip waits for 32 workgroups -- 8K 4:4:4 in 32-frame launches: k4_latest
+// 845 us against a chain of 585, 324 k Mpx/s with the window against 342 - 359 k without.  Narrower launches keep the schedule
+// above with k4_latest on a stream of its own.
 int g1s_diff::submit(int si) {
   Slot &sl = slots[si];
   if (sl.count == 0) return G1S_OK;
@@ -898,7 +912,7 @@ int g1s_diff::submit(int si) {
     if (rc) return rc;
     trace_host("back queued", prev);
   }
-  if (switches().one_stream || switches().no_defer || timing || !ss.flat) {
+  if (switches().one_stream || switches().no_defer || timing || !ss.flat || latest_window()) {
     rc = flush_pending();
     if (rc) return rc;
   }
@@ -973,6 +987,8 @@ int g1s_diff::launch_front(int si) {
     HIP_TRY(hipStreamWaitEvent(stream, ss.table_done[si], 0));
     HIP_TRY(hipStreamWaitEvent(fstream, ss.table_done[si], 0));  // (the table goes by the upload stream only when the finder chain has a side stream)
   }
+  // the window: the chain starts when the accumulation of the batch before has ended (submit)
+  if (latest_window() && fstream != stream && last_back >= 0) HIP_TRY(hipStreamWaitEvent(fstream, ss.kernels_done[last_back], 0));
   if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvStart], fstream));
   {
     // flat-block features: integer moments + certified evaluation; the literal f64 kernel only for
@@ -1287,23 +1303,20 @@ int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
   job.ydec = geom.ydec;
   job.nbw = geom.nbw;
   job.nbh = geom.nbh;
-  if (sl.timed) {  // (per-kernel timing: everything on the one stream)
-    kmark(sl, stream, latest_kernel_name());
-    HIP_TRY(launch_latest(job, B, stream));
-    kmark(sl, stream, nullptr);
-    HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-    HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
-  } else {
-    if (!ensure_latest_streams(ss)) return fail_hip("the device half's streams / events could not be created");
-    hipStream_t lst = (si & 1) ? ss.latest2 : ss.latest;  // (why two: StreamSet)
+  // The window (and per-kernel timing: everything on the one stream): behind the tail on the stream that ran it, so in the queue
+  // ahead of the next batch's finder chain, which waits for kernels_done[si] (recorded above, in FRONT of this kernel) on the
+  // side stream.  Otherwise on a stream of its own.  The blobs' copy on the copy stream behind it.
+  hipStream_t lst = stream;
+  if (!sl.timed && !latest_window()) {
+    if (!ensure_latest_streams(ss)) return fail_hip("the device half's streams could not be created");
+    lst = (si & 1) ? ss.latest2 : ss.latest;  // (why two: StreamSet)
     HIP_TRY(hipStreamWaitEvent(lst, ss.kernels_done[si], 0));
-    kmark(sl, lst, latest_kernel_name());  // (trace mode)
-    HIP_TRY(launch_latest(job, B, lst));
-    kmark(sl, lst, nullptr);
-    // the blobs' copy: on the copy stream, behind the kernel
-    HIP_TRY(hipEventRecord(ss.latest_done[si], lst));
-    HIP_TRY(hipStreamWaitEvent(ss.copy, ss.latest_done[si], 0));
   }
+  kmark(sl, lst, latest_kernel_name());
+  HIP_TRY(launch_latest(job, B, lst));
+  kmark(sl, lst, nullptr);
+  HIP_TRY(hipEventRecord(ss.latest_done[si], lst));
+  HIP_TRY(hipStreamWaitEvent(ss.copy, ss.latest_done[si], 0));
   hipStream_t ls = ss.copy;
   if (!sl.timed) kmark(sl, ls, "blobs D2H");
   HIP_TRY(hipMemcpyAsync(sl.h_latest, sl.d_latest, blob * B, hipMemcpyDeviceToHost, ls));
@@ -1337,6 +1350,7 @@ int g1s_diff::launch_back(int si) {
   stats.launches_flat_features++;
   stats.launches_flat_select++;
   stats.launches_ar_accumulate++;
+  last_back = si;
   {
     std::unique_lock<std::mutex> lk(dm);
     in_flight.push_back(si);
@@ -1804,6 +1818,7 @@ int g1s_diff_sync(g1s_diff_t *g) {
     rc = g->flush_pending();
     if (rc) return rc;
     (void)g->drain_all();
+    g->last_back = -1;
   }
   return take_deferred(g);
 }

@@ -17,7 +17,7 @@
 //     shuffle steps; the pivot row travels by v_readlane; back substitution by every lane on its own row, the wanted lane's
 //     result broadcast.  No barrier, no LDS.  The three planes' AR systems are solved by three waves at once;
 //   * the strength system's entries are sums over the measured blocks in raster order.  Entry (k, k), (k + 1, k) = (k, k + 1)
-//     and b[k] only ever meet blocks of bins k - 1 and k: the blocks are taken 512 at a time, their terms computed a thread a
+//     and b[k] only ever meet blocks of bins k - 1 and k: the blocks are taken 1 024 at a time, their terms computed a thread a
 //     block, partitioned by bin IN ORDER into lists in LDS (ballots and popcounts: a stable partition), and lane k adds its
 //     list front to back -- one LDS read and one addition an element, no selection, no memory latency in the chain; `total`
 //     is one sum over all blocks: one more list (every measured block, in block order), one more lane.  Both chroma planes go
@@ -31,8 +31,13 @@
 namespace g1s {
 namespace {
 
-constexpr int kT = 256, kWaves = kT / 64;
-constexpr int kChunk = 512, kRounds = kChunk / kT;  // blocks a chunk; a thread's blocks of a chunk: base + kT * r + tid
+// (512 threads and 1 024 blocks a chunk: the terms, the ranks and the scatter of a chunk go twice as wide and the barriers, the
+//  offsets and the lists' zero padding come half as often as with 256 threads and 512 blocks -- 343 - 369 -> 273 - 278 us a 64-frame
+//  4K launch alone on the chip, passes 113 + 120 -> 82 + 86 us by the stamps; the chains, two lanes' worth of waves 0 and 2, are
+//  what they were.  The lists' order is the blocks' order either way: rounds first, then waves, then lanes.
+//  profiles/r09_latest_window.txt)
+constexpr int kT = 512, kWaves = kT / 64;
+constexpr int kChunk = 1024, kRounds = kChunk / kT;  // blocks a chunk; a thread's blocks of a chunk: base + kT * r + tid
 constexpr double kTinyD = 1.0e-16;                  // TINY_NEAR_ZERO
 constexpr double kNorm2D = 255.0 * 255.0;           // BLOCK_NORMALIZATION^2
 constexpr int kNL = 2 * kNumBins;                   // lists of a chunk: D 0 .. 19 (bins k - 1 and k), L 20 .. 38 (bin k alone), T 39 (every block)
@@ -47,7 +52,7 @@ struct Shared {
   double Lw[kArenaL];     // off-diagonal terms, list 20 + k
   double Bv[2][kArenaD];  // b terms of the pass' planes, the D lists' slots
   double Tv[2][kArenaT];  // noise stds in block order (list 39)
-  uint16_t cnt[kRounds][kWaves][kNL];  // (16-bit: the workgroup's LDS stays under a quarter of a CU's, and with it the kernel at four waves a SIMD)
+  uint16_t cnt[kRounds][kWaves][kNL];  // (at most 64 each.  The workgroup's LDS: 83 KB of a CU's 160, one workgroup a CU)
   uint32_t beg[kNL], end[kNL];
   // results
   double arx[3][kMaxN + 1];
@@ -520,7 +525,9 @@ __global__ __launch_bounds__(kT) void k4_latest(LatestJob job) {
   for (int d = 32; d > 0; d >>= 1) nflat_t += (uint32_t)__shfl_down((int)nflat_t, d, 64);
   if (lane == 0) sh.wsum[wave] = nflat_t;
   __syncthreads();  // (also: the zeros of the blob are behind every later store of this workgroup)
-  const uint32_t num_flat = sh.wsum[0] + sh.wsum[1] + sh.wsum[2] + sh.wsum[3];
+  uint32_t num_flat = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) num_flat += sh.wsum[w];
   if (tid == 0) {
     hdr->magic = kLatestMagic;
     hdr->lag = (uint32_t)job.lag;
