@@ -141,6 +141,18 @@ class G1SGrainOpts(C.Structure):
     ]
 
 
+class G1SDenoiseOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("device", C.c_int32),
+        ("batch_frames", C.c_uint32),
+        ("search_radius", C.c_uint32),
+        ("patch_radius", C.c_uint32),
+        ("strength", C.c_double),
+        ("chroma_strength", C.c_double),
+    ]
+
+
 NEXT_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(G1SFrame))
 
 # every symbol include/g1s_diff.h declares: (name, restype, argtypes)
@@ -239,6 +251,16 @@ SYMBOLS = [
     ("g1s_grain_last_error", C.c_char_p, [C.c_void_p]),
     ("g1s_grain_free", None, [C.c_void_p]),
     ("g1s_grain_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SGrainOpts), C.c_char_p, C.c_size_t]),
+    ("g1s_denoise_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts)]),
+    ("g1s_denoise_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
+    ("g1s_denoise_sync", C.c_int, [C.c_void_p]),
+    ("g1s_denoise_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_denoise_last_error", C.c_char_p, [C.c_void_p]),
+    ("g1s_denoise_free", None, [C.c_void_p]),
+    ("g1s_denoise_weights", C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("g1s_denoise_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts),
+                                             C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
 ]
 
 _lib = None

@@ -1,4 +1,5 @@
-"""`python -m grav1synth_amd diff SOURCE DENOISED -o OUT [-y] [-f FILTERS]` -- the front door of the path.
+"""`python -m grav1synth_amd diff SOURCE [DENOISED | --denoise] -o OUT [-y] [-f FILTERS]` -- the front door of the path
+(and `estimate`, `render`, `denoise`).
 
 The `diff` command of the reference (Commands::Diff, /root/reference/src/main.rs:347-533, arguments :846-870) for .y4m
 inputs, around g1s_diff_y4m_files_filtered: the same refusals in the same order, with the same texts, and like the
@@ -25,6 +26,11 @@ SAME_AS_OUTPUT = ("Input and output paths are the same. This is probably a typo,
 SAME_INPUTS = ("Source and denoised paths are the same. This is probably a typo, because this would always compute an "
                "empty diff. Exiting.")
 NOT_OVERWRITING = "Not overwriting existing file. Exiting."
+NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
+BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
+DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser runs on the source as it is read). Exiting."
+DENOISE_ONE_DEVICE = "--denoise does not combine with --gpus / --devices (one denoiser, one generator, one device). Exiting."
+KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs --denoise. Exiting."
 
 
 def _confirm(prompt: str) -> bool:
@@ -53,12 +59,25 @@ def _same_path(a: str, b: str) -> bool:
     return components(a) == components(b)
 
 
+def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
+    """The filter's parameters, shared by `denoise` and `diff --denoise` (0 = the library's default)."""
+    p.add_argument("--search-radius", type=int, default=0, help="search radius A, 1..7 (default 3): offsets up to A samples each way")
+    p.add_argument("--patch-radius", type=int, default=0, help="patch radius S, 1..4 (default 2): patches of (2S+1) x (2S+1) samples")
+    p.add_argument("--strength", type=float, default=0.0, help="filter strength h in 8-bit code values (default 4.0)")
+    p.add_argument("--chroma-strength", type=float, default=0.0, help="strength for the chroma planes (default: --strength)")
+
+
+def _denoise_parameters(args) -> dict:
+    return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
+                chroma_strength=args.chroma_strength)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="grav1synth_amd", description="MI355X-native `grav1synth diff`")
     sub = ap.add_subparsers(dest="command", required=True)
     d = sub.add_parser("diff", help="Compares a source video to a denoised video and generates a film grain table (y4m inputs).")
     d.add_argument("source", help="The untouched source file to inspect.")
-    d.add_argument("denoised", help="The denoised file to inspect.")
+    d.add_argument("denoised", nargs="?", default=None, help="The denoised file to inspect (or --denoise).")
     d.add_argument("-o", "--output", required=True, help="The path to the output film grain table.")
     d.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
     d.add_argument("-f", "--filters", default=None,
@@ -73,6 +92,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "reading them (about 25 GB/s, 560 4K 10-bit frames a second) long before a second device matters; "
                         "does not combine with a resize filter or with --device")
     d.add_argument("--devices", default=None, help="the same with an explicit list of HIP ordinals, e.g. 0,2,3")
+    d.add_argument("--denoise", action="store_true",
+                   help="make the denoised clip on the device (the project's own integer non-local-means filter, see `denoise`) "
+                        "instead of reading a DENOISED file; does not combine with --filters, --gpus or --devices")
+    d.add_argument("--keep-denoised", default=None, metavar="PATH", help="with --denoise: also write the denoised clip as .y4m")
+    _add_denoise_parameters(d)
     e = sub.add_parser("estimate", help="Estimates the amount of noise in a source video, frame by frame (y4m input; the reference's "
                                         "`estimate`, feature \"unstable\").")
     e.add_argument("source", help="The source file to inspect.")
@@ -88,15 +112,49 @@ def build_parser() -> argparse.ArgumentParser:
     r.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
     r.add_argument("--clip-restricted", action="store_true",
                    help="clip the output to the restricted (studio) range, the sequence's clip_to_restricted_range")
+    n = sub.add_parser("denoise", help="Denoises a video (y4m input and output) with the project's own integer-exact non-local-means "
+                                       "filter: the structure of ffmpeg's nlmeans / KNLMeansCL, not their output.")
+    n.add_argument("input", help="The file to denoise.")
+    n.add_argument("-o", "--output", required=True, help="The path to the output .y4m.")
+    n.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
+    n.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    _add_denoise_parameters(n)
     return ap
 
 
-def diff_command(source: str, denoised: str, output: str, overwrite: bool = False, filters: Optional[str] = None,
-                 device: int = -1, confirm=_confirm, devices: Optional[List[int]] = None) -> int:
+def diff_denoise_command(source: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
+                         keep_denoised: Optional[str] = None, **parameters) -> int:
+    """`diff SOURCE --denoise -o OUT [--keep-denoised PATH]`: the refusals of `diff` for the paths there are, then the loop of
+    g1s_diff_y4m_file_denoised.  Returns the number of frames, -1 after a refusal."""
+    from .ingest import diff_y4m_file_denoised
+
+    if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
+        log.error(SAME_AS_OUTPUT)
+        return -1
+    for path in (output, keep_denoised):
+        if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
+            log.warning(NOT_OVERWRITING)
+            return -1
+    frames = diff_y4m_file_denoised(source, output, keep_denoised=keep_denoised, device=device, **parameters)
+    log.info("Done, wrote output file to %s", output)
+    return frames
+
+
+def diff_command(source: str, denoised: Optional[str], output: str, overwrite: bool = False, filters: Optional[str] = None,
+                 device: int = -1, confirm=_confirm, devices: Optional[List[int]] = None, denoise: bool = False,
+                 keep_denoised: Optional[str] = None, **parameters) -> int:
     """Returns the number of frame pairs diffed, or -1 when the command refused to run (a logged line, exit 0)."""
     from .filters import FilterChain, FilterError, Resize
     from .ingest import diff_y4m_files
 
+    if denoise or denoised is None or keep_denoised is not None:
+        for refused, line in ((denoised is None and not denoise, NO_DENOISED), (denoised is not None and denoise, BOTH_DENOISED),
+                              (not denoise, KEEP_NEEDS_DENOISE), (filters is not None, DENOISE_NO_FILTERS),
+                              (devices is not None, DENOISE_ONE_DEVICE)):
+            if refused:
+                log.error(line)
+                return -1
+        return diff_denoise_command(source, output, overwrite, device, confirm, keep_denoised, **parameters)
     if _same_path(source, output) or _same_path(denoised, output):
         log.error(SAME_AS_OUTPUT)
         return -1
@@ -160,6 +218,22 @@ def render_command(input: str, table: str, output: str, overwrite: bool = False,
     return frames
 
 
+def denoise_command(input: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm, **parameters) -> int:
+    """The refusals of the other commands, then every frame of the input through the filter.  Returns the frame count, -1
+    after a refusal."""
+    from .denoise import denoise_y4m_file
+
+    if _same_path(input, output):
+        log.error(SAME_AS_OUTPUT)
+        return -1
+    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
+        log.warning(NOT_OVERWRITING)
+        return -1
+    frames = denoise_y4m_file(input, output, device=device, **parameters)
+    log.info("Done, wrote output file to %s", output)
+    return frames
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
@@ -174,7 +248,11 @@ def main(argv: Optional[List[str]] = None) -> int:
                 devices = [int(x) for x in args.devices.split(",") if x.strip() != ""]
             elif args.gpus > 1:
                 devices = list(range(args.gpus))
-            diff_command(args.source, args.denoised, args.output, args.overwrite, args.filters, args.device, devices=devices)
+            if args.denoise or args.denoised is None or args.keep_denoised is not None:
+                diff_command(args.source, args.denoised, args.output, args.overwrite, args.filters, args.device, devices=devices,
+                             denoise=args.denoise, keep_denoised=args.keep_denoised, **_denoise_parameters(args))
+            else:
+                diff_command(args.source, args.denoised, args.output, args.overwrite, args.filters, args.device, devices=devices)
         except Exception as e:  # `?` out of main: the error, a non-zero exit
             log.error("%s", e)
             return 1
@@ -187,6 +265,12 @@ def main(argv: Optional[List[str]] = None) -> int:
     elif args.command == "render":
         try:
             render_command(args.input, args.grain, args.output, args.overwrite, args.device, args.clip_restricted)
+        except Exception as e:
+            log.error("%s", e)
+            return 1
+    elif args.command == "denoise":
+        try:
+            denoise_command(args.input, args.output, args.overwrite, args.device, **_denoise_parameters(args))
         except Exception as e:
             log.error("%s", e)
             return 1

@@ -1,0 +1,204 @@
+// denoise_tile.hip.h -- the phases a workgroup of kd_nlm runs on one tile of one plane (denoise.hip).
+//
+// The filter is the one include/g1s_diff.h defines under "denoise" (rules 1 - 4).  A tile is kTW x kTH output samples;
+// with search radius A and patch radius S the workgroup keeps in LDS
+//
+//   L   the tile and its halo of R = A + S samples, plane edges replicated while staging: (kTW + 2R) x (kTH + 2R) u16,
+//   Hb  for the offset d in hand, the horizontal (2S+1)-sums of the squared differences, u32,
+//   Wb  for the offset d in hand, the weight of the pair {p, p + d} at p, u16 (0 where the pair takes no part),
+//   T   the 1024-entry weight table.
+//
+// Only the offsets of the upper half plane are visited (dy > 0, or dy = 0 and dx > 0): D(p, d) = D(p + d, -d), so the
+// weight image of d, computed over the union of the tile and the tile moved by -d, serves both ends of every pair --
+// a sample p reads Wb at p for its neighbour p + d and at p - d for its neighbour p - d.  Per offset: dn_hsum, barrier,
+// dn_weights, barrier, dn_accumulate (into registers; the next dn_hsum writes Hb only, so no third barrier).
+//
+// Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
+// run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.
+#pragma once
+#include <stdint.h>
+
+namespace g1s_dn {
+
+constexpr int kThreads = 256;
+constexpr int kTW = 64, kTH = 48;   // tile
+constexpr int kSPT = kTH / 4;       // output samples a thread owns: column tid & 63, rows (tid >> 6) + 4 j
+constexpr int kMaxA = 7, kMaxS = 4;
+constexpr int kTable = 1024;
+
+#if defined(__HIPCC__)
+#define G1S_DN_HD __host__ __device__ inline
+#else
+#define G1S_DN_HD inline
+#endif
+
+struct TileGeom {
+  int A, S, R;
+  int LH, LW, LS;  // staged samples: LH rows of LW, row stride LS (u16); LS / 2 is odd: rows fall on distinct banks
+  int HS, HR;      // Hb: HR rows, stride HS (u32, odd)
+  int WS, WR;      // Wb: WR rows, stride WS (u16)
+  int offH, offL, offW, offT, bytes;
+};
+
+G1S_DN_HD TileGeom tile_geom(int A, int S) {
+  TileGeom g;
+  g.A = A, g.S = S, g.R = A + S;
+  g.LW = kTW + 2 * g.R, g.LH = kTH + 2 * g.R;
+  g.LS = (g.LW + 1) & ~1;
+  if (!((g.LS >> 1) & 1)) g.LS += 2;
+  g.HS = (kTW + A) | 1, g.HR = kTH + A + 2 * S;
+  g.WS = (kTW + A + 1) & ~1, g.WR = kTH + A;
+  g.offH = 0;
+  g.offL = g.offH + g.HS * g.HR * 4;
+  g.offW = (g.offL + g.LS * g.LH * 2 + 15) & ~15;
+  g.offT = (g.offW + g.WS * g.WR * 2 + 15) & ~15;
+  g.bytes = g.offT + kTable * 2;
+  return g;
+}
+
+G1S_DN_HD int imin(int a, int b) { return a < b ? a : b; }
+G1S_DN_HD int imax(int a, int b) { return a > b ? a : b; }
+// i / n == (i * magic(n)) >> 16 for 0 <= i < 512, 1 <= n <= 128
+G1S_DN_HD uint32_t magic(int n) { return (65536u + (uint32_t)n - 1u) / (uint32_t)n; }
+
+// the tile at (x0, y0) of a W x H plane and its halo into L; coordinates clamp to the plane (rule 1)
+template <int BPS>
+G1S_DN_HD void dn_stage(int tid, const TileGeom &g, uint16_t *L, const uint8_t *in, uint32_t stride, int W, int H, int x0, int y0) {
+  for (int r = tid >> 7; r < g.LH; r += kThreads >> 7) {
+    const int gy = imin(imax(y0 - g.R + r, 0), H - 1);
+    const uint8_t *row = in + (size_t)gy * stride;
+    for (int c = tid & 127; c < g.LW; c += 128) {
+      const int gx = imin(imax(x0 - g.R + c, 0), W - 1);
+      L[r * g.LS + c] = BPS == 2 ? reinterpret_cast<const uint16_t *>(row)[gx] : (uint16_t)row[gx];
+    }
+  }
+}
+
+// Hb(row, x) = sum over |kx| <= S of (L(x + kx, r) - L(x + dx + kx, r + dy))^2 for the region's columns x (RW of them, from
+// -max(dx, 0)) and its rows r = -dy - S + row, row < NR = kTH + dy + 2S.  A task is 8 consecutive columns of a row (the last
+// task of a row starts at RW - 8 and overlaps its neighbour); lanes run down the rows.  mNR = magic(NR).
+template <int S>
+G1S_DN_HD void dn_hsum(int tid, const TileGeom &g, const uint16_t *L, uint32_t *Hb, int dx, int dy, int RW, int NR, uint32_t mNR) {
+  const int ntasks = ((RW + 7) >> 3) * NR;
+  const int ox = -imax(dx, 0);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = imin(seg * 8, RW - 8);
+    const uint16_t *a = L + (row + g.A - dy) * g.LS + (ox + xs - S + g.R);
+    const uint16_t *b = a + dy * g.LS + dx;
+    int sq[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) {
+      const int t = (int)a[j] - (int)b[j];
+      sq[j] = t * t;
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += (uint32_t)sq[j];
+    uint32_t *o = Hb + row * g.HS + xs;
+    o[0] = s;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      s += (uint32_t)sq[j + 2 * S] - (uint32_t)sq[j - 1];
+      o[j] = s;
+    }
+  }
+}
+
+// Wb(y, x) = T[min(D >> q, 1023)] with D = the sum of Hb over the 2S + 1 rows from y, for the region's RW x RH samples
+// p = (x0 - max(dx, 0) + x, y0 - dy + y); 0 where p or p + d lies outside the plane (rule 2).  A task is 8 consecutive rows
+// of a column; lanes run along the columns.
+template <int S>
+G1S_DN_HD void dn_weights(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int RW,
+                          int RH, uint32_t mRW, int x0, int y0, int W, int H) {
+  const int ntasks = ((RH + 7) >> 3) * RW;
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mRW) >> 16), x = i - seg * RW;
+    const int ys = imin(seg * 8, RH - 8);
+    const uint32_t *h = Hb + ys * g.HS + x;
+    uint32_t v[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += v[j];
+    const int px = x0 - imax(dx, 0) + x, py = y0 - dy + ys;
+    const bool col_ok = px >= 0 && px < W && px + dx >= 0 && px + dx < W;
+    uint16_t *o = Wb + ys * g.WS + x;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j) s += v[j + 2 * S] - v[j - 1];
+      const uint32_t k = s >> q;
+      const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
+      const bool ok = col_ok && py + j >= 0 && py + j + dy < H;  // (dy >= 0: the other two row bounds follow)
+      o[j * g.WS] = ok ? w : (uint16_t)0;
+    }
+  }
+}
+
+// the two pairs of offset d at each sample the thread owns: {p, p + d}, weight at p, and {p - d, p}, weight at p - d
+G1S_DN_HD void dn_accumulate(int tid, const TileGeom &g, const uint16_t *L, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint32_t *au) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w1 = Wb + (yb + dy) * g.WS + x + imax(dx, 0);
+  const uint16_t *w2 = Wb + yb * g.WS + x + imax(-dx, 0);
+  const uint16_t *u1 = L + (yb + dy + g.R) * g.LS + x + dx + g.R;
+  const uint16_t *u2 = L + (yb - dy + g.R) * g.LS + x - dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w1[4 * j * g.WS], b = w2[4 * j * g.WS];
+    aw[j] += a + b;
+    au[j] += a * u1[4 * j * g.LS] + b * u2[4 * j * g.LS];
+  }
+}
+
+// d = 0: weight T[0] = 4096 on the sample itself
+G1S_DN_HD void dn_init(int tid, const TileGeom &g, const uint16_t *L, uint32_t *aw, uint32_t *au) {
+  const uint16_t *u = L + ((tid >> 6) + g.R) * g.LS + (tid & 63) + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) aw[j] = 4096u, au[j] = 4096u * u[4 * j * g.LS];
+}
+
+// rule 4: one rounded division per sample
+template <int BPS>
+G1S_DN_HD void dn_store(int tid, uint8_t *out, uint32_t stride, int W, int H, int x0, int y0, const uint32_t *aw, const uint32_t *au) {
+  const int x = x0 + (tid & 63);
+  if (x >= W) return;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const int y = y0 + (tid >> 6) + 4 * j;
+    if (y >= H) break;
+    const uint32_t v = (au[j] + (aw[j] >> 1)) / aw[j];
+    uint8_t *row = out + (size_t)y * stride;
+    if (BPS == 2) reinterpret_cast<uint16_t *>(row)[x] = (uint16_t)v;
+    else row[x] = (uint8_t)v;
+  }
+}
+
+// one tile, start to end, for thread `tid` of a workgroup whose barrier is `sync` (LDS buffers as laid out by tile_geom)
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
+                       uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + g.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + g.offL), *Wb = reinterpret_cast<uint16_t *>(lds + g.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + g.offT);
+  dn_stage<BPS>(tid, g, L, in, in_stride, W, H, x0, y0);
+  for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
+  sync();
+  uint32_t aw[kSPT], au[kSPT];
+  dn_init(tid, g, L, aw, au);
+  for (int dy = 0; dy <= g.A; ++dy) {
+    const int NR = kTH + dy + 2 * S, RH = kTH + dy;
+    const uint32_t mNR = magic(NR);
+    for (int dx = dy ? -g.A : 1; dx <= g.A; ++dx) {
+      const int RW = kTW + (dx < 0 ? -dx : dx);
+      dn_hsum<S>(tid, g, L, Hb, dx, dy, RW, NR, mNR);
+      sync();
+      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, W, H);
+      sync();
+      dn_accumulate(tid, g, L, Wb, dx, dy, aw, au);
+    }
+  }
+  dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+}  // namespace g1s_dn

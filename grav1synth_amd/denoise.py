@@ -1,0 +1,126 @@
+"""`denoise`: the project's integer-exact non-local-means filter on an MI355X -- the clip `diff` compares the source with.
+
+HIP kernels behind g1s_denoise_* (include/g1s_diff.h, where the filter is defined); no CPU fallback.  This is the
+project's own definition of non-local means: the structure of ffmpeg's nlmeans and of KNLMeansCL, not their bits.
+
+>>> dn = Denoiser(10, strength=4.0)
+>>> clean = dn.apply([y, u, v])                 # torch device tensors stay on the device; numpy in, numpy out
+>>> denoise_y4m_file("grainy.y4m", "clean.y4m")
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import G1SDenoiseOpts, G1SError
+from .diff import Frame
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+log = logging.getLogger("grav1synth")
+
+
+def denoise_opts(device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0, strength: float = 0.0,
+                 chroma_strength: float = 0.0) -> G1SDenoiseOpts:
+    """g1s_denoise_opts_t; a zero field means its default (A = 3, S = 2, h = 4.0, chroma = luma)."""
+    o = G1SDenoiseOpts()
+    o.struct_size = C.sizeof(G1SDenoiseOpts)
+    o.device = device
+    o.batch_frames = batch_frames
+    o.search_radius = search_radius
+    o.patch_radius = patch_radius
+    o.strength = strength
+    o.chroma_strength = chroma_strength
+    return o
+
+
+def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0) -> Tuple[np.ndarray, int]:
+    """(T, q): the 1024 uint16 weights and the shift the kernels use for these parameters (host only, no device needed)."""
+    L = _lib.lib()
+    t = np.zeros(1024, np.uint16)
+    q = C.c_uint32()
+    rc = L.g1s_denoise_weights(bit_depth, patch_radius, float(strength), t.ctypes.data, C.byref(q))
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return t, int(q.value)
+
+
+class Denoiser:
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
+                 strength: float = 0.0, chroma_strength: float = 0.0):
+        self._L = _lib.lib()
+        self.bit_depth = bit_depth
+        opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
+        self._h = self._L.g1s_denoise_new(bit_depth, C.byref(opts))
+        if not self._h:
+            raise G1SError(-1, self._L.g1s_last_global_error().decode())
+        self._keep: list = []  # planes the queued kernels still read or write
+
+    def _check(self, rc: int) -> None:
+        if rc:
+            raise G1SError(rc, self._L.g1s_denoise_last_error(self._h).decode())
+
+    def apply(self, frame_planes: Sequence, xdec: int = 1, ydec: int = 1, *, sync: bool = True, out: Optional[Sequence] = None) -> List:
+        """One frame through the filter: new planes of the same kind -- torch device tensors stay on the device, host planes
+        go through host frames.  sync = False queues the frame (a batch goes out as one launch per plane class): the
+        returned planes are complete after sync()."""
+        planes = list(frame_planes)
+        if out is None:
+            if torch is not None and isinstance(planes[0], torch.Tensor):
+                out = [torch.empty(p.shape, dtype=p.dtype, device=p.device) for p in planes]
+            else:
+                planes = [np.asarray(p) for p in planes]
+                out = [np.empty(p.shape, p.dtype) for p in planes]
+        out = list(out)
+        keep: list = []
+        fin = Frame(planes, xdec, ydec).to_c(keep)
+        fout = Frame(out, xdec, ydec).to_c(keep)
+        if fin.on_device == 1:
+            torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
+        self._keep.append((keep, planes, out))
+        self._check(self._L.g1s_denoise_frame(self._h, C.byref(fin), C.byref(fout)))
+        if sync:
+            self.sync()
+        return out
+
+    def sync(self) -> None:
+        self._check(self._L.g1s_denoise_sync(self._h))
+        self._keep.clear()
+
+    def kernel_times(self, enable: bool = True):
+        """(ms in kd_nlm, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        a, n = C.c_double(), C.c_uint64()
+        self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
+        return a.value, n.value
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.g1s_denoise_free(self._h)
+            self._h = None
+            self._keep.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
+                     strength: float = 0.0, chroma_strength: float = 0.0) -> int:
+    """`denoise INPUT -o OUTPUT` for a .y4m input.  Returns the number of frames."""
+    L = _lib.lib()
+    opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
+    err = C.create_string_buffer(512)
+    n = L.g1s_denoise_y4m_file(input.encode(), output.encode(), C.byref(opts), err, len(err))
+    if n < 0:
+        raise G1SError(int(n), err.value.decode())
+    log.info("Denoised %d frames", n)
+    return int(n)

@@ -437,6 +437,62 @@ void g1s_grain_free(g1s_grain_t *);
  * Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
 int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, const g1s_grain_opts_t *opts, char *err, size_t cap);
 
+/* ---- `denoise`: an integer-exact non-local-means filter on the device (the clip `diff` compares the source with) ----
+ * This is the project's OWN definition of non-local means: it has the structure of ffmpeg's nlmeans and of KNLMeansCL,
+ * not their bits, and its output is not any other tool's.  Every plane is filtered on its own grid.  Bit depth B in
+ * {8, 10, 12}, samples u(x, y) of a W x H plane, clamp() replicates the plane's edge samples; search radius A (1..7),
+ * patch radius S (1..4), n = (2S + 1)^2, strength h > 0 in 8-bit code values:
+ *   1. D(p, d) = sum over |kx|, |ky| <= S of (u(clamp(p + k)) - u(clamp(p + d + k)))^2 for |dx|, |dy| <= A (exact in 32 bits).
+ *   2. An offset takes part at p only if p + d lies inside the plane (skipped, not clamped; only patch coordinates
+ *      clamp), so D(p, d) = D(p + d, -d) for every pair that takes part.  d = 0 always takes part, with D = 0.
+ *   3. w(p, d) = T[min(D >> q, 1023)]: 1024 uint16 entries, T[0] = 4096, non-increasing, T[1023] = 0;
+ *      T[i] = round(4096 exp(-((i + 1/2) 2^q) / (n h^2 4^(B - 8)))) for i >= 1, q the smallest shift >= 0 that gives
+ *      T[1023] = 0.  g1s_denoise_weights returns the table the kernels use.
+ *   4. out(p) = (sum_d w u(p + d) + (sum_d w >> 1)) / sum_d w, integer division (uint32 suffices for A <= 7).
+ * No temporal part, no luma-guided chroma, no dithering.  Samples above the bit depth's maximum are the caller's error.
+ * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
+ * chroma planes) on the denoiser's own stream.  Errors are sticky (g1s_denoise_last_error). */
+typedef struct {
+  uint32_t struct_size;    /* sizeof(g1s_denoise_opts_t) */
+  int32_t device;          /* HIP device ordinal; -1 = current device */
+  uint32_t batch_frames;
+  uint32_t search_radius;  /* A: 1..7; 0 = default (3) */
+  uint32_t patch_radius;   /* S: 1..4; 0 = default (2) */
+  double strength;         /* h, in 8-bit code values, 0 < h <= 1000; 0 = default (4.0) */
+  double chroma_strength;  /* the same for the chroma planes; 0 = the luma strength */
+} g1s_denoise_opts_t;
+typedef struct g1s_denoise g1s_denoise_t;
+/* bit_depth 8, 10 or 12.  Parameters out of range and other bit depths are refusals, not clamps: NULL, the reason from
+ * g1s_last_global_error() (they are checked before a device is looked for).  opts == NULL: current device, defaults. */
+g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts);
+/* One frame.  in / out follow g1s_frame_t.on_device independently, as in g1s_grain_frame: 0 = host (in: copied before
+ * the call returns; out: written by g1s_denoise_sync at the latest), 1 = device, 2 = pinned host (copies queued).  Device
+ * and pinned planes of in must stay valid and unmodified, and every plane of out must stay valid, until
+ * g1s_denoise_sync.  in and out must be DISTINCT, non-overlapping buffers (a workgroup reads the samples around its
+ * tile, which another one would already have replaced).  Same geometry on both sides; a frame whose geometry differs
+ * from the one before it drains the queue first. */
+int g1s_denoise_frame(g1s_denoise_t *, const g1s_frame_t *in, g1s_frame_t *out);
+/* Launches what is queued and waits: the out planes of every frame handed over are complete. */
+int g1s_denoise_sync(g1s_denoise_t *);
+/* HIP-event time of the kernels so far, milliseconds, and the frames they covered (enable = 1: timed from the next
+ * batch on; a timed batch is waited for).  tools/bench_denoise.py. */
+int g1s_denoise_set_timing(g1s_denoise_t *, int enable, double *ms_kernel, uint64_t *frames);
+const char *g1s_denoise_last_error(const g1s_denoise_t *);
+void g1s_denoise_free(g1s_denoise_t *);
+/* (q, T) of rule 3 as the kernels use them.  Host only: needs no device.  G1S_ERR_INVALID (reason from
+ * g1s_last_global_error()) for a bit depth, patch radius or strength out of range. */
+int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double strength, uint16_t T[1024], uint32_t *q);
+/* `denoise INPUT -o OUTPUT`: every frame of a .y4m through the filter, written as .y4m (the input's header line,
+ * "FRAME\n", the planes without padding).  Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
+int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap);
+/* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
+ * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
+ * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
+ * on the generator's device (dopts->device is ignored).  keep_denoised != NULL: the denoised clip is also written
+ * there as .y4m.  The table is the one g1s_diff_y4m_files makes from SOURCE and that clip. */
+int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                               const g1s_denoise_opts_t *dopts, uint64_t *frames, char *err, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernel kd_nlm over device-resident frames,
+4K 10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 64, at the defaults (A = 3, S = 2) and at A = 7, S = 3.  Per case: HIP-event
+time per batch around the two launches (timed batches run alone and are waited for), frames a second from it, the kernel's
+arithmetic as the specification counts it -- samples x unordered pairs A + A (2A + 1) -- and the job rate through
+g1s_denoise_frame with the timing off.  One JSON line per case.  For the kernel trace:
+rocprofv3 --kernel-trace --stats -- python tools/bench_denoise.py 1 (a run of its own)."""
+import json, os, sys, time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from grav1synth_amd.denoise import Denoiser
+from grav1synth_amd.synth import SynthSpec, make_pair
+
+assert torch.cuda.is_available(), "bench_denoise.py needs a GPU"
+batches = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+BATCH = 64
+
+for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", SynthSpec(1920, 1080, 8))):
+    # 8 distinct noisy frames in, 64 distinct frames out (a batch writes every out plane once)
+    ins = [make_pair(spec, k, device="cuda")[0] for k in range(8)]
+    outs = [[torch.empty_like(p) for p in ins[0]] for _ in range(BATCH)]
+    torch.cuda.synchronize()
+    samples = sum(p.numel() for p in ins[0])
+    for A, S in ((3, 2), (7, 3)):
+        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S)
+
+        def run(nb):
+            for k in range(nb * BATCH):
+                dn.apply(ins[k % 8], spec.xdec, spec.ydec, sync=False, out=outs[k % BATCH])
+            dn.sync()
+
+        run(1)  # warm-up: code objects, buffers
+        t0 = time.perf_counter()
+        run(batches)
+        dt = time.perf_counter() - t0
+        dn.kernel_times(True)
+        run(batches)
+        ms, fr = dn.kernel_times(False)
+        dn.close()
+        pairs = A + A * (2 * A + 1)
+        print(json.dumps({
+            "format": name, "search_radius": A, "patch_radius": S, "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            "samples_per_frame": samples, "unordered_pairs": pairs,
+            "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
+            "sample_pairs_per_ns": samples * pairs * fr / (ms * 1e6),
+            "job_frames_per_s_untimed": batches * BATCH / dt,
+        }), flush=True)
