@@ -765,6 +765,19 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
     return fail(G1S_ERR_INVALID, "unsupported frame format");
   if ((s->bytes_per_sample == 1) != (src_bd == 8) || (d->bytes_per_sample == 1) != (den_bd == 8))
     return fail(G1S_ERR_INVALID, "bytes_per_sample does not match the bit depth given to g1s_diff_new");
+  // what g1s_grain_frame and g1s_denoise_frame refuse for a plane, before anything is allocated, copied or queued: the kernels
+  // take the pointer as it is and the stride as a uint32_t.  Sticky: the job has lost a frame, no table from here on.
+  for (int side = 0; side < 2; ++side) {
+    const g1s_frame_t *f = side ? d : s;
+    for (uint32_t c = 0; c < (luma_only ? 1u : (uint32_t)s->nplanes); ++c) {  // (the planes that are read)
+      const size_t rowb = (c ? (size_t)(f->width >> f->xdec) : (size_t)f->width) * f->bytes_per_sample;
+      if (!f->data[c] || f->stride_bytes[c] < rowb || f->stride_bytes[c] > 0xffffffffu || (f->bytes_per_sample == 2 && (f->stride_bytes[c] & 1))) {
+        int ok = G1S_OK;
+        sticky.compare_exchange_strong(ok, G1S_ERR_INVALID);
+        return fail(G1S_ERR_INVALID, std::string(side ? "denoised" : "source") + " frame, plane " + std::to_string(c) + ": bad plane pointer or row stride");
+      }
+    }
+  }
   if (!geometry_set) {
     const int rc = set_geometry(s, d);
     if (rc) return rc;

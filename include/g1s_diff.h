@@ -120,7 +120,13 @@ const char *g1s_last_global_error(void);
 /* DiffGenerator::diff_frame (src/main.rs:442).  Frames are consumed in call
  * order.  Work is queued and may still be running when the call returns;
  * errors of queued frames (not enough flat blocks, singular system) surface on
- * a later diff_frame / sync / finish call, exactly once. */
+ * a later diff_frame / sync / finish call, exactly once.
+ * Device planes (on_device == 1) are read in place, through the pointer and the row stride given: any base the sample
+ * size allows and any stride from the row upwards; 16-byte-aligned bases and strides in all six planes of a batch take
+ * the fastest kernels, the others give the same table.  Refused for either frame and any plane, with G1S_ERR_INVALID
+ * and the frame and plane in g1s_diff_last_error, before anything is copied or queued: a null plane pointer, a stride
+ * smaller than the plane's row in bytes, an odd stride under 2-byte samples, a stride above 0xffffffff.  The refusal is
+ * sticky (the job has lost a frame): every later call returns it. */
 int g1s_diff_frame(g1s_diff_t *, const g1s_frame_t *source, const g1s_frame_t *denoised);
 /* n frame pairs in one call (same semantics as n diff_frame calls). */
 int g1s_diff_frames(g1s_diff_t *, const g1s_frame_t *source, const g1s_frame_t *denoised, size_t n);
