@@ -252,6 +252,8 @@ SYMBOLS = [
     ("g1s_grain_free", None, [C.c_void_p]),
     ("g1s_grain_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SGrainOpts), C.c_char_p, C.c_size_t]),
     ("g1s_denoise_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts)]),
+    ("g1s_denoise_new_temporal", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts), C.c_uint32]),
+    ("g1s_denoise_drain", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("g1s_denoise_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
     ("g1s_denoise_sync", C.c_int, [C.c_void_p]),
     ("g1s_denoise_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -259,6 +261,9 @@ SYMBOLS = [
     ("g1s_denoise_free", None, [C.c_void_p]),
     ("g1s_denoise_weights", C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("g1s_denoise_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_char_p, C.c_size_t]),
+    ("g1s_denoise_y4m_file_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised_temporal", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32,
+                                             C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("g1s_diff_y4m_file_denoised", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts),
                                              C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
 ]

@@ -30,6 +30,7 @@ NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing
 BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
 DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser runs on the source as it is read). Exiting."
 DENOISE_ONE_DEVICE = "--denoise does not combine with --gpus / --devices (one denoiser, one generator, one device). Exiting."
+BAD_TEMPORAL_RADIUS = "--temporal-radius must be 0..3 (frames before and after the one in hand). Exiting."
 KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs --denoise. Exiting."
 
 
@@ -65,11 +66,13 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
     p.add_argument("--patch-radius", type=int, default=0, help="patch radius S, 1..4 (default 2): patches of (2S+1) x (2S+1) samples")
     p.add_argument("--strength", type=float, default=0.0, help="filter strength h in 8-bit code values (default 4.0)")
     p.add_argument("--chroma-strength", type=float, default=0.0, help="strength for the chroma planes (default: --strength)")
+    p.add_argument("--temporal-radius", type=int, default=0, metavar="D",
+                   help="temporal radius D, 0..3 (default 0): the mean also runs over the search windows of the D frames before and after")
 
 
 def _denoise_parameters(args) -> dict:
     return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
-                chroma_strength=args.chroma_strength)
+                chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -128,6 +131,9 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
     g1s_diff_y4m_file_denoised.  Returns the number of frames, -1 after a refusal."""
     from .ingest import diff_y4m_file_denoised
 
+    if not 0 <= parameters.get("temporal_radius", 0) <= 3:
+        log.error(BAD_TEMPORAL_RADIUS)
+        return -1
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
         return -1
@@ -223,6 +229,9 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     after a refusal."""
     from .denoise import denoise_y4m_file
 
+    if not 0 <= parameters.get("temporal_radius", 0) <= 3:
+        log.error(BAD_TEMPORAL_RADIUS)
+        return -1
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)
         return -1

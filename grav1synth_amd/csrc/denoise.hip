@@ -2,10 +2,15 @@
 //
 // The filter is defined in include/g1s_diff.h ("denoise", rules 1 - 4); tests/denoise_ref.py restates it in numpy.  It is
 // this project's own definition of non-local means: ffmpeg's nlmeans and KNLMeansCL have the same structure, not the
-// same bits.  One kernel, kd_nlm<S, BPS>: a workgroup per (tile, plane of the class, frame), the phases of
-// denoise_tile.hip.h.  A batch of frames goes out as one launch per plane class (luma; the two chroma planes) on the
-// denoiser's own stream.  Planes are independent, but `out` must not overlap `in`: a tile reads the halo its neighbours
-// write.
+// same bits.  Two kernels, a workgroup per (tile, plane of the class, frame), the phases of denoise_tile.hip.h:
+// kd_nlm<S, BPS> for one frame on its own (temporal radius 0, rules 1 - 4) and kd_nlm_t<S, BPS>, which goes on over the
+// frames around it (rules 5 - 7).  A batch of frames goes out as one launch per plane class (luma; the two chroma planes)
+// on the denoiser's own stream.  Planes are independent, but `out` must not overlap `in`: a tile reads the halo its
+// neighbours write.
+//
+// The engine numbers the frames handed over since the denoiser was made.  With temporal radius D a frame is launched once
+// the D frames after it are there (or the clip ends), so the queue holds the frames not yet launched and, in front of
+// them, the last D that were: their planes are the neighbours of what comes next.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,6 +49,33 @@ struct DenoiseParams {
   int plane0;         // first plane of the class: 0 luma, 1 chroma
 };
 
+// the temporal kernel's job: the frame and, per plane, the 2 D frames around it (null: the clip has no such frame)
+struct DenoiseJobT {
+  DenoiseJob f;
+  const uint8_t *nb[3][2 * kMaxD];
+  uint32_t nb_stride[3][2 * kMaxD];
+};
+
+struct DenoiseParamsT {
+  const DenoiseJobT *jobs;
+  const uint16_t *table;
+  int q, A;
+  int W, H, tiles_x;
+  int plane0;
+  int nnb;  // 2 D
+};
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_t(DenoiseParamsT p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobT &job = p.jobs[blockIdx.z];
+  const int c = p.plane0 + (int)blockIdx.y;
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  dn_tile_t<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, job.f.in[c], job.f.in_stride[c], job.nb[c], job.nb_stride[c], p.nnb, job.f.out[c],
+                    job.f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH, [] { __syncthreads(); });
+}
+
 template <int S, int BPS>
 __global__ __launch_bounds__(kThreads) void kd_nlm(DenoiseParams p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
@@ -78,23 +110,29 @@ std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTab
 struct g1s_denoise {
   int device = 0;
   uint32_t bit_depth = 8, bps = 1, batch = 32;
-  uint32_t A = 3, S = 2;
+  uint32_t A = 3, S = 2, D = 0;
   uint32_t q[2] = {0, 0};  // luma, chroma
   hipStream_t stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool have_geom = false;
   int W = 0, H = 0, subx = 0, suby = 0, nplanes = 0;
   size_t plane_row[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, stage_frame = 0;  // staging layout of a host frame on the device
-  std::vector<DenoiseJob> jobs;  // the batch being filled
-  struct HostOut {
-    uint32_t slot;
-    void *data[3];
-    size_t stride[3];
+  // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
+  // output goes (out[c] is null for a host frame: a slot of the output staging buffer is chosen at the launch)
+  struct Queued {
+    const uint8_t *in[3];
+    uint8_t *out[3];
+    uint32_t in_stride[3], out_stride[3];
+    bool host_out;
+    void *host_data[3];
+    size_t host_stride[3];
   };
-  std::vector<HostOut> host_outs;  // frames whose out planes are host memory: copied back behind the kernels
+  // frames [first_queued, frames_in): what is not launched yet and, in front of it, up to D launched frames of the same clip
+  std::deque<Queued> queue;
+  uint64_t frames_in = 0, first_queued = 0, next_launch = 0, clip_first = 0, frames_complete = 0;
   // the jobs of a batch, two sets in turn: pinned on the host, uploaded on the stream, free again when the event behind
   // the batch's kernels has passed -- the next batch is filled while this one runs
-  DenoiseJob *d_jobs[2] = {nullptr, nullptr}, *h_jobs[2] = {nullptr, nullptr};
+  uint8_t *d_jobs[2] = {nullptr, nullptr}, *h_jobs[2] = {nullptr, nullptr};
   hipEvent_t done[2] = {nullptr, nullptr};
   uint64_t batches = 0;
   uint16_t *d_tables = nullptr;  // [2][1024]
@@ -111,9 +149,16 @@ struct g1s_denoise {
   }
   size_t pw(int c) const { return c ? (size_t)((W + subx) >> subx) : (size_t)W; }
   size_t ph(int c) const { return c ? (size_t)((H + suby) >> suby) : (size_t)H; }
+  size_t job_bytes() const { return D ? sizeof(DenoiseJobT) : sizeof(DenoiseJob); }
+  // host and pinned inputs wait on the device in a ring: a slot is written again B + 2D frames later, and by then every
+  // frame that reads it (up to D frames on) has been launched in front of that copy on the stream
+  uint32_t ring() const { return batch + 2 * D; }
+  const Queued &frame(uint64_t n) const { return queue[(size_t)(n - first_queued)]; }
   void set_geometry(const g1s_frame_t &f);
   int launch(int set, uint32_t nframes, int plane0, int nplanes_in_class);
-  int flush();
+  int flush(uint32_t nframes);
+  int launch_up_to(uint64_t limit);
+  int end_clip();
 };
 
 #define DN_TRY(expr)                                                                                         \
@@ -136,10 +181,30 @@ void g1s_denoise::set_geometry(const g1s_frame_t &f) {
 
 int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_class) {
   DenoiseParams p{};
-  p.jobs = d_jobs[set], p.table = d_tables + (plane0 ? kTable : 0), p.q = (int)q[plane0 ? 1 : 0], p.A = (int)A;
+  p.jobs = reinterpret_cast<const DenoiseJob *>(d_jobs[set]), p.table = d_tables + (plane0 ? kTable : 0), p.q = (int)q[plane0 ? 1 : 0], p.A = (int)A;
   p.W = (int)pw(plane0), p.H = (int)ph(plane0), p.tiles_x = (p.W + kTW - 1) / kTW, p.plane0 = plane0;
   const dim3 grid((unsigned)(p.tiles_x * ((p.H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
-  const size_t lds = (size_t)tile_geom((int)A, (int)S).bytes;
+  const TileGeom geom = tile_geom((int)A, (int)S);
+  if (D) {
+    DenoiseParamsT t{};
+    t.jobs = reinterpret_cast<const DenoiseJobT *>(d_jobs[set]), t.table = p.table, t.q = p.q, t.A = p.A, t.W = p.W, t.H = p.H, t.tiles_x = p.tiles_x,
+    t.plane0 = plane0, t.nnb = (int)(2 * D);
+    const size_t lds = (size_t)geom.bytes_t;
+    switch (S * 2 + (bps - 1)) {
+#define DN_CASE(s)                                                                                  \
+  case (s) * 2: hipLaunchKernelGGL((kd_nlm_t<s, 1>), grid, dim3(kThreads), lds, stream, t); break; \
+  case (s) * 2 + 1: hipLaunchKernelGGL((kd_nlm_t<s, 2>), grid, dim3(kThreads), lds, stream, t); break;
+      DN_CASE(1)
+      DN_CASE(2)
+      DN_CASE(3)
+      DN_CASE(4)
+#undef DN_CASE
+      default: return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
+    }
+    DN_TRY(hipGetLastError());
+    return G1S_OK;
+  }
+  const size_t lds = (size_t)geom.bytes;
   switch (S * 2 + (bps - 1)) {
 #define DN_CASE(s)                                                                          \
   case (s) * 2: hipLaunchKernelGGL((kd_nlm<s, 1>), grid, dim3(kThreads), lds, stream, p); break; \
@@ -155,34 +220,93 @@ int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_cl
   return G1S_OK;
 }
 
-int g1s_denoise::flush() {
-  const uint32_t B = (uint32_t)jobs.size();
-  if (!B) return G1S_OK;
+// frames next_launch .. next_launch + nframes - 1 as one batch (nframes <= batch); their neighbours are in the queue
+int g1s_denoise::flush(uint32_t nframes) {
+  if (!nframes) return G1S_OK;
   const int set = (int)(batches & 1);
   if (batches >= 2) DN_TRY(hipEventSynchronize(done[set]));
   ++batches;
-  std::memcpy(h_jobs[set], jobs.data(), sizeof(DenoiseJob) * B);
-  DN_TRY(hipMemcpyAsync(d_jobs[set], h_jobs[set], sizeof(DenoiseJob) * B, hipMemcpyHostToDevice, stream));
+  bool host_outs = false;
+  for (uint32_t i = 0; i < nframes; ++i) {
+    const uint64_t n = next_launch + i;
+    const Queued &f = frame(n);
+    DenoiseJob job{};
+    for (int c = 0; c < nplanes; ++c) {
+      job.in[c] = f.in[c], job.in_stride[c] = f.in_stride[c];
+      job.out[c] = f.host_out ? d_stage_out + stage_frame * i + plane_off[c] : f.out[c];
+      job.out_stride[c] = f.host_out ? (uint32_t)plane_row[c] : f.out_stride[c];
+    }
+    host_outs = host_outs || f.host_out;
+    if (!D) {
+      reinterpret_cast<DenoiseJob *>(h_jobs[set])[i] = job;
+      continue;
+    }
+    DenoiseJobT t{};
+    t.f = job;
+    int k = 0;
+    for (int64_t m = (int64_t)n - (int64_t)D; m <= (int64_t)(n + D); ++m) {
+      if (m == (int64_t)n) continue;
+      if (m >= (int64_t)clip_first && m < (int64_t)frames_in)  // rule 5: the frames the clip has
+        for (int c = 0; c < nplanes; ++c) t.nb[c][k] = frame((uint64_t)m).in[c], t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
+      ++k;
+    }
+    reinterpret_cast<DenoiseJobT *>(h_jobs[set])[i] = t;
+  }
+  DN_TRY(hipMemcpyAsync(d_jobs[set], h_jobs[set], job_bytes() * nframes, hipMemcpyHostToDevice, stream));
   if (timing) DN_TRY(hipEventRecord(ev[0], stream));
-  int rc = launch(set, B, 0, 1);
+  int rc = launch(set, nframes, 0, 1);
   if (rc) return rc;
-  if (nplanes == 3 && (rc = launch(set, B, 1, 2)) != 0) return rc;
+  if (nplanes == 3 && (rc = launch(set, nframes, 1, 2)) != 0) return rc;
   if (timing) DN_TRY(hipEventRecord(ev[1], stream));
   DN_TRY(hipEventRecord(done[set], stream));
-  for (const HostOut &h : host_outs)
-    for (int c = 0; c < nplanes; ++c)
-      DN_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], d_stage_out + stage_frame * h.slot + plane_off[c], plane_row[c], pw(c) * bps, ph(c),
-                              hipMemcpyDeviceToHost, stream));
+  if (host_outs)
+    for (uint32_t i = 0; i < nframes; ++i) {
+      const Queued &f = frame(next_launch + i);
+      if (!f.host_out) continue;
+      for (int c = 0; c < nplanes; ++c)
+        DN_TRY(hipMemcpy2DAsync(f.host_data[c], f.host_stride[c], d_stage_out + stage_frame * i + plane_off[c], plane_row[c], pw(c) * bps, ph(c),
+                                hipMemcpyDeviceToHost, stream));
+    }
   if (timing) {
     DN_TRY(hipStreamSynchronize(stream));
     float a = 0;
     DN_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-    ms_kernel += a, frames_timed += B;
+    ms_kernel += a, frames_timed += nframes;
   }
-  jobs.clear();
-  host_outs.clear();
+  next_launch += nframes;
+  // what stays in front of the frames to come: the D frames before the next one to launch
+  while (first_queued + D < next_launch) queue.pop_front(), ++first_queued;
   return G1S_OK;
 }
+
+// every frame below `limit` that is not launched yet, a batch at a time
+int g1s_denoise::launch_up_to(uint64_t limit) {
+  while (next_launch < limit) {
+    const int rc = flush((uint32_t)std::min<uint64_t>(batch, limit - next_launch));
+    if (rc) return rc;
+  }
+  return G1S_OK;
+}
+
+// the clip ends here: what is queued goes out with the neighbours it has and is waited for
+int g1s_denoise::end_clip() {
+  const int rc = launch_up_to(frames_in);
+  if (rc) return rc;
+  if (hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
+  queue.clear();
+  first_queued = clip_first = frames_complete = frames_in;
+  return G1S_OK;
+}
+
+namespace {
+
+// the bytes of plane c of a frame of the denoiser's geometry at `base`
+bool planes_overlap(const g1s_denoise &g, const uint8_t *a, uint32_t a_stride, int ca, const uint8_t *b, uint32_t b_stride, int cb) {
+  const uint8_t *ae = a + (size_t)a_stride * (g.ph(ca) - 1) + g.pw(ca) * g.bps, *be = b + (size_t)b_stride * (g.ph(cb) - 1) + g.pw(cb) * g.bps;
+  return a < be && b < ae;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -196,7 +320,9 @@ int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double streng
   return G1S_OK;
 }
 
-g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) {
+g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return g1s_denoise_new_temporal(bit_depth, opts, 0); }
+
+g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius) {
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -207,6 +333,10 @@ g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opt
   const double h = opts && opts->strength != 0.0 ? opts->strength : 4.0, hc = opts && opts->chroma_strength != 0.0 ? opts->chroma_strength : h;
   if (A < 1 || A > (uint32_t)kMaxA) {
     g1s_set_global_error_("search_radius must be 1..7");
+    return nullptr;
+  }
+  if (temporal_radius > (uint32_t)kMaxD) {
+    g1s_set_global_error_("temporal_radius must be 0..3");
     return nullptr;
   }
   std::vector<uint16_t> tables(2 * kTable);
@@ -235,14 +365,14 @@ g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opt
   g->bit_depth = bit_depth;
   g->bps = bit_depth > 8 ? 2 : 1;
   g->batch = opts && opts->batch_frames ? std::min(opts->batch_frames, 256u) : 32u;
-  g->A = A, g->S = S, g->q[0] = q[0], g->q[1] = q[1];
-  const uint32_t B = g->batch;
+  g->A = A, g->S = S, g->D = temporal_radius, g->q[0] = q[0], g->q[1] = q[1];
+  const size_t jobs_bytes = g->job_bytes() * g->batch;
   bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess;
   for (auto &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
   for (int k = 0; k < 2; ++k)
     ok = ok && hipEventCreateWithFlags(&g->done[k], hipEventDisableTiming) == hipSuccess &&
-         hipMalloc((void **)&g->d_jobs[k], sizeof(DenoiseJob) * B) == hipSuccess &&
-         hipHostMalloc((void **)&g->h_jobs[k], sizeof(DenoiseJob) * B, hipHostMallocDefault) == hipSuccess;
+         hipMalloc((void **)&g->d_jobs[k], jobs_bytes) == hipSuccess &&
+         hipHostMalloc((void **)&g->h_jobs[k], jobs_bytes, hipHostMallocDefault) == hipSuccess;
   ok = ok && hipMalloc((void **)&g->d_tables, tables.size() * 2) == hipSuccess &&
        hipMemcpy(g->d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
@@ -267,71 +397,89 @@ int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out)
   if (!g->have_geom) {
     g->set_geometry(*in);
   } else if (g->W != (int)in->width || g->H != (int)in->height || g->nplanes != in->nplanes || g->subx != in->xdec || g->suby != in->ydec) {
-    // a new geometry: what is queued goes out and finishes first, the staging buffers are sized again
-    const int rc = g->flush();
+    // a new geometry: the clip ends, what is queued goes out and finishes first, the staging buffers are sized again
+    const int rc = g->end_clip();
     if (rc) return rc;
-    if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, "hipStreamSynchronize failed");
     if (g->d_stage_in) (void)hipFree(g->d_stage_in), g->d_stage_in = nullptr;
     if (g->d_stage_out) (void)hipFree(g->d_stage_out), g->d_stage_out = nullptr;
     g->set_geometry(*in);
   }
-  DenoiseJob job{};
-  const uint32_t slot = (uint32_t)g->jobs.size();
+  g1s_denoise::Queued f{};
+  const uint32_t slot = (uint32_t)(g->frames_in % g->ring());
+  f.host_out = out->on_device != 1;
   for (int c = 0; c < g->nplanes; ++c) {
     const size_t pw = g->pw(c), ph = g->ph(c);
     if (!in->data[c] || !out->data[c] || in->stride_bytes[c] < pw * g->bps || out->stride_bytes[c] < pw * g->bps ||
         in->stride_bytes[c] > 0xffffffffu || out->stride_bytes[c] > 0xffffffffu || (g->bps == 2 && ((in->stride_bytes[c] | out->stride_bytes[c]) & 1)))
       return g->fail(G1S_ERR_INVALID, "bad plane pointer or row stride");
     if (in->on_device == 1) {
-      job.in[c] = static_cast<const uint8_t *>(in->data[c]);
-      job.in_stride[c] = (uint32_t)in->stride_bytes[c];
+      f.in[c] = static_cast<const uint8_t *>(in->data[c]);
+      f.in_stride[c] = (uint32_t)in->stride_bytes[c];
     } else {
-      if (!g->d_stage_in && hipMalloc((void **)&g->d_stage_in, g->stage_frame * g->batch) != hipSuccess)
+      if (!g->d_stage_in && hipMalloc((void **)&g->d_stage_in, g->stage_frame * g->ring()) != hipSuccess)
         return g->fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
       uint8_t *dst = g->d_stage_in + g->stage_frame * slot + g->plane_off[c];
       // host planes are read before the call returns (the stream copy is waited for below); pinned planes are queued
       if (hipMemcpy2DAsync(dst, g->plane_row[c], in->data[c], in->stride_bytes[c], pw * g->bps, ph, hipMemcpyHostToDevice, g->stream) != hipSuccess)
         return g->fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
-      job.in[c] = dst;
-      job.in_stride[c] = (uint32_t)g->plane_row[c];
+      f.in[c] = dst;
+      f.in_stride[c] = (uint32_t)g->plane_row[c];
     }
-    if (out->on_device == 1) {
-      job.out[c] = static_cast<uint8_t *>(const_cast<void *>(out->data[c]));
-      job.out_stride[c] = (uint32_t)out->stride_bytes[c];
-    } else {
+    if (f.host_out) {
       if (!g->d_stage_out && hipMalloc((void **)&g->d_stage_out, g->stage_frame * g->batch) != hipSuccess)
         return g->fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
-      job.out[c] = g->d_stage_out + g->stage_frame * slot + g->plane_off[c];
-      job.out_stride[c] = (uint32_t)g->plane_row[c];
+      f.host_data[c] = const_cast<void *>(out->data[c]), f.host_stride[c] = out->stride_bytes[c];
+    } else {
+      f.out[c] = static_cast<uint8_t *>(const_cast<void *>(out->data[c]));
+      f.out_stride[c] = (uint32_t)out->stride_bytes[c];
     }
   }
-  // in != out: no plane of the output may overlap a plane of the input
-  for (int c = 0; c < g->nplanes; ++c) {
-    const uint8_t *ob = job.out[c], *oe = ob + (size_t)job.out_stride[c] * (g->ph(c) - 1) + g->pw(c) * g->bps;
-    for (int d = 0; d < g->nplanes; ++d) {
-      const uint8_t *ib = job.in[d], *ie = ib + (size_t)job.in_stride[d] * (g->ph(d) - 1) + g->pw(d) * g->bps;
-      if (ob < ie && ib < oe) return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_denoise_frame needs distinct buffers");
-    }
+  // in != out: no device plane of the output may overlap a plane of the input -- nor, with a temporal radius, a plane the
+  // queue still reads, and no plane of the input may be one that a frame of the queue is going to write
+  if (!f.host_out) {
+    for (int c = 0; c < g->nplanes; ++c)
+      for (int d = 0; d < g->nplanes; ++d) {
+        bool bad = planes_overlap(*g, f.out[c], f.out_stride[c], c, f.in[d], f.in_stride[d], d);
+        if (g->D)
+          for (const g1s_denoise::Queued &o : g->queue) bad = bad || planes_overlap(*g, f.out[c], f.out_stride[c], c, o.in[d], o.in_stride[d], d);
+        if (bad) return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_denoise_frame needs distinct buffers");
+      }
+  }
+  for (uint64_t n = g->next_launch; g->D && n < g->frames_in; ++n) {
+    const g1s_denoise::Queued &o = g->frame(n);
+    if (o.host_out) continue;
+    for (int c = 0; c < g->nplanes; ++c)
+      for (int d = 0; d < g->nplanes; ++d)
+        if (planes_overlap(*g, o.out[c], o.out_stride[c], c, f.in[d], f.in_stride[d], d))
+          return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_denoise_frame needs distinct buffers");
   }
   if (in->on_device == 0 && hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
-  if (out->on_device != 1) {
-    g1s_denoise::HostOut h{};
-    h.slot = slot;
-    for (int c = 0; c < g->nplanes; ++c) h.data[c] = const_cast<void *>(out->data[c]), h.stride[c] = out->stride_bytes[c];
-    g->host_outs.push_back(h);
-  }
-  g->jobs.push_back(job);
-  return g->jobs.size() >= g->batch ? g->flush() : G1S_OK;
+  g->queue.push_back(f);
+  ++g->frames_in;
+  // a full batch of frames whose D later neighbours are all there goes out; the last D frames wait for theirs
+  if (g->frames_in >= g->next_launch + g->D + g->batch) return g->flush(g->batch);
+  return G1S_OK;
+}
+
+int g1s_denoise_drain(g1s_denoise_t *g, uint64_t *frames_complete) {
+  if (!g) return G1S_ERR_INVALID;
+  if (frames_complete) *frames_complete = g->frames_complete;
+  if (g->err_code) return g->err_code;
+  (void)hipSetDevice(g->device);
+  const uint64_t limit = g->frames_in >= g->clip_first + g->D ? g->frames_in - g->D : g->clip_first;
+  const int rc = g->launch_up_to(limit);
+  if (rc) return rc;
+  if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
+  g->frames_complete = g->next_launch;
+  if (frames_complete) *frames_complete = g->frames_complete;
+  return G1S_OK;
 }
 
 int g1s_denoise_sync(g1s_denoise_t *g) {
   if (!g) return G1S_ERR_INVALID;
   if (g->err_code) return g->err_code;
   (void)hipSetDevice(g->device);
-  const int rc = g->flush();
-  if (rc) return rc;
-  if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
-  return G1S_OK;
+  return g->end_clip();
 }
 
 int g1s_denoise_set_timing(g1s_denoise_t *g, int enable, double *ms_kernel, uint64_t *frames) {
@@ -398,6 +546,11 @@ struct PlaneLayout {
 extern "C" {
 
 int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap) {
+  return g1s_denoise_y4m_file_temporal(in, out, opts, 0, err, cap);
+}
+
+int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
+                                      size_t cap) {
   auto refuse = [&](int code, const std::string &m) -> int64_t {
     if (err && cap) snprintf(err, cap, "%s", m.c_str());
     return code;
@@ -408,7 +561,7 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
   if (!y) return G1S_ERR_INVALID;
   g1s_y4m_info_t info;
   g1s_y4m_get_info(y, &info);
-  g1s_denoise_t *g = g1s_denoise_new(info.bit_depth, opts);
+  g1s_denoise_t *g = g1s_denoise_new_temporal(info.bit_depth, opts, temporal_radius);
   if (!g) {
     g1s_y4m_close(y);
     return refuse(G1S_ERR_INVALID, g1s_last_global_error());
@@ -420,29 +573,29 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
     return refuse(G1S_ERR_INVALID, std::string("cannot create ") + out);
   }
   const PlaneLayout lay(info);
-  // a batch of output frames in pinned memory: denoised, waited for, written
-  const uint32_t batch = g->batch;
+  // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
+  // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
+  const uint32_t batch = g->batch, ring = batch + g->D;
   uint8_t *obuf = nullptr;
-  int64_t frames = 0;
+  int64_t frames = 0, written = 0;
   int rc = G1S_OK;
   std::string why;
   bool ok = std::fwrite(header.data(), 1, header.size(), fo) == header.size();
   if (!ok) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-  if (ok && hipHostMalloc((void **)&obuf, lay.fbytes * batch, hipHostMallocDefault) != hipSuccess)
+  if (ok && hipHostMalloc((void **)&obuf, lay.fbytes * ring, hipHostMallocDefault) != hipSuccess)
     ok = false, rc = G1S_ERR_HIP, why = "hipHostMalloc of the output frames failed";
-  uint32_t pending = 0;
-  auto drain = [&]() {
-    rc = g1s_denoise_sync(g);
+  auto drain = [&](bool end) {
+    uint64_t complete = (uint64_t)frames;
+    rc = end ? g1s_denoise_sync(g) : g1s_denoise_drain(g, &complete);
     if (rc) {
       why = g1s_denoise_last_error(g);
       return false;
     }
-    for (uint32_t k = 0; k < pending; ++k)
-      if (std::fwrite("FRAME\n", 1, 6, fo) != 6 || std::fwrite(obuf + lay.fbytes * k, 1, lay.fbytes, fo) != lay.fbytes) {
+    for (; written < (int64_t)complete; ++written)
+      if (std::fwrite("FRAME\n", 1, 6, fo) != 6 || std::fwrite(obuf + lay.fbytes * (size_t)(written % ring), 1, lay.fbytes, fo) != lay.fbytes) {
         rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
         return false;
       }
-    pending = 0;
     return true;
   };
   while (ok) {
@@ -454,7 +607,7 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
     }
     if (got == 0) break;
     g1s_frame_t fout = fin;
-    lay.point(fout, obuf + lay.fbytes * pending, info);
+    lay.point(fout, obuf + lay.fbytes * (size_t)(frames % ring), info);
     fin.on_device = 0;  // (the reader lends the frame until its next call: copied before g1s_denoise_frame returns)
     fout.on_device = 2;
     rc = g1s_denoise_frame(g, &fin, &fout);
@@ -462,10 +615,10 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
       ok = false, why = "frame " + std::to_string(frames) + ": " + g1s_denoise_last_error(g);
       break;
     }
-    ++frames, ++pending;
-    if (pending == batch) ok = drain();
+    ++frames;
+    if (frames % batch == 0) ok = drain(false);
   }
-  if (ok) ok = drain();
+  if (ok) ok = drain(true);
   if (std::fclose(fo) != 0 && ok) ok = false, rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
   g1s_denoise_free(g);
   if (obuf) (void)hipHostFree(obuf);
@@ -476,9 +629,16 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
 // output beside it and the generator takes the pair as device frames.  A pair's two buffers belong to the generator
-// until g1s_diff_frames_released() covers the frame; then they are used again.
+// until g1s_diff_frames_released() covers the frame, and its source buffer is a neighbour of the D frames after it until the
+// denoiser is past those; then they are used again.  The file is one clip: the denoiser is drained once a group, not
+// synchronised, and only the frames it has completed go on to the generator.
 int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                const g1s_denoise_opts_t *dopts, uint64_t *frames_out, char *err, size_t cap) {
+  return g1s_diff_y4m_file_denoised_temporal(source, out_tbl, keep_denoised, opts, dopts, 0, frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                        const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames_out, char *err, size_t cap) {
   auto refuse = [&](int code, const std::string &m) {
     if (err && cap) snprintf(err, cap, "%s", m.c_str());
     return code;
@@ -500,10 +660,11 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
   };
   std::vector<Pair> pairs;                          // every pair of buffers allocated so far
   std::deque<std::pair<uint64_t, size_t>> lent;     // (frame index, pair) handed to the generator, oldest first
-  std::vector<size_t> group;                        // pairs of the frames the denoiser holds
+  std::deque<size_t> held;                          // pairs of the frames the denoiser has not completed, oldest first
   std::vector<size_t> spare;
   size_t pair_cap = 0;
-  uint64_t frames = 0;
+  uint64_t frames = 0, taken = 0, complete = 0;     // frames handed to the generator; to the denoiser; completed by it
+  uint32_t D = 0;
   int rc = G1S_OK;
   std::string why;
   std::vector<g1s_segment_t> segs(64);
@@ -519,7 +680,7 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
     if (dopts) d = *dopts;
     d.struct_size = sizeof d;
     d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = g1s_denoise_new(info.bit_depth, &d);
+    dn = g1s_denoise_new_temporal(info.bit_depth, &d, temporal_radius);
   }
   if (!dn) {
     rc = G1S_ERR_INVALID, why = g1s_last_global_error();
@@ -534,33 +695,39 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
       goto done;
     }
   }
-  // buffers for two groups until the generator has said how many frames it can hold (after the first hand-over)
-  pair_cap = 2 * (size_t)dn->batch;
+  // buffers for two groups until the generator has said how many frames it can hold (after the first hand-over), and for
+  // the window: the D frames the denoiser holds back and the D before them that are still their neighbours
+  D = dn->D;
+  pair_cap = 2 * (size_t)dn->batch + 2 * D;
   for (bool eof = false; !eof && !rc;) {
-    // ---- one group: up to batch_frames frames to the device and through the denoiser
-    group.clear();
-    while (group.size() < dn->batch) {
+    // ---- one group: up to batch_frames frames to the device and to the denoiser
+    for (uint32_t in_group = 0; in_group < dn->batch; ++in_group) {
       g1s_frame_t fin;
       const int got = g1s_y4m_next(y, &fin);
       if (got < 0) {
-        rc = got, why = "frame " + std::to_string(frames + group.size()) + ": source reader failed (" + g1s_y4m_last_error(y) + ")";
+        rc = got, why = "frame " + std::to_string(taken) + ": source reader failed (" + g1s_y4m_last_error(y) + ")";
         break;
       }
       if (got == 0) {
         eof = true;
         break;
       }
-      // a pair of buffers: one the generator has released, a new one, or -- the ring is full -- wait for the generator
+      // a pair of buffers: one that the generator has released and the denoiser is past (frame t + D complete), a new one,
+      // or -- the ring is full -- wait for the generator
       size_t k;
-      const uint64_t released = g1s_diff_frames_released(g);
-      while (!lent.empty() && lent.front().first < released) spare.push_back(lent.front().second), lent.pop_front();
+      uint64_t released = g1s_diff_frames_released(g);
+      auto reclaim = [&] {
+        while (!lent.empty() && lent.front().first < released && lent.front().first + D < complete) spare.push_back(lent.front().second), lent.pop_front();
+      };
+      reclaim();
       if (spare.empty() && pairs.size() >= pair_cap) {
         rc = g1s_diff_sync(g);
         if (rc) {
           why = std::string("diff_frame: ") + g1s_diff_last_error(g);
           break;
         }
-        while (!lent.empty()) spare.push_back(lent.front().second), lent.pop_front();
+        released = frames;
+        reclaim();
       }
       if (!spare.empty()) {
         k = spare.back(), spare.pop_back();
@@ -589,19 +756,23 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
       s.on_device = d.on_device = 1;
       rc = g1s_denoise_frame(dn, &s, &d);
       if (rc) {
-        why = "frame " + std::to_string(frames + group.size()) + ": denoise: " + g1s_denoise_last_error(dn);
+        why = "frame " + std::to_string(taken) + ": denoise: " + g1s_denoise_last_error(dn);
         break;
       }
-      group.push_back(k);
+      held.push_back(k), ++taken;
     }
     if (rc) break;
-    rc = g1s_denoise_sync(dn);
+    // the end of the file is the end of the clip; before it the last D frames stay with the denoiser
+    rc = eof ? g1s_denoise_sync(dn) : g1s_denoise_drain(dn, &complete);
     if (rc) {
       why = std::string("denoise: ") + g1s_denoise_last_error(dn);
       break;
     }
-    // ---- the group's pairs to the generator, the denoised frames to the kept file
-    for (size_t k : group) {
+    if (eof) complete = taken;
+    // ---- the completed frames' pairs to the generator, the denoised frames to the kept file
+    while (frames < complete) {
+      const size_t k = held.front();
+      held.pop_front();
       g1s_frame_t s{}, d{};
       s.width = info.width, s.height = info.height, s.bytes_per_sample = info.bit_depth > 8 ? 2 : 1, s.xdec = (uint8_t)info.xdec, s.ydec = (uint8_t)info.ydec,
       s.nplanes = (uint8_t)info.nplanes, s.on_device = 1;
@@ -621,7 +792,7 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
       ++frames;
     }
     if (rc) break;
-    if (const uint32_t inside = g1s_diff_frames_in_flight_max_(g)) pair_cap = std::max(pair_cap, (size_t)dn->batch + inside + inside / 4);
+    if (const uint32_t inside = g1s_diff_frames_in_flight_max_(g)) pair_cap = std::max(pair_cap, (size_t)dn->batch + inside + inside / 4 + 2 * D);
   }
   if (rc) goto done;
   rc = g1s_diff_finish(g, segs.data(), segs.size(), &nseg);

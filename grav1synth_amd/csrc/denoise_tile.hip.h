@@ -13,6 +13,17 @@
 // a sample p reads Wb at p for its neighbour p + d and at p - d for its neighbour p - d.  Per offset: dn_hsum, barrier,
 // dn_weights, barrier, dn_accumulate (into registers; the next dn_hsum writes Hb only, so no third barrier).
 //
+// The temporal filter (rules 5 - 7, kd_nlm_t) adds
+//
+//   N   the same tile and halo of ONE neighbour frame, in the layout of L; the neighbours that take part are staged one
+//       after the other, so LDS does not grow with the temporal radius.
+//
+// After the offsets of the frame itself, for every neighbour that takes part and every one of its (2A+1)^2 offsets:
+// dn_hsum_t (one operand from L, one from N), barrier, dn_weights_t, barrier, dn_accumulate_t.  The region is the tile
+// itself (kTW x kTH), whatever the offset: the pair {(t, p), (t + k, p + d)} serves two different output frames, so there
+// is no half plane to save, and the weight is read at p only.  Hb and Wb as sized for the frame itself are large enough.
+// The numerator of rule 7 needs 64 bits (dn_store_t).
+//
 // Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
 // run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.
 #pragma once
@@ -25,6 +36,7 @@ constexpr int kTW = 64, kTH = 48;   // tile
 constexpr int kSPT = kTH / 4;       // output samples a thread owns: column tid & 63, rows (tid >> 6) + 4 j
 constexpr int kMaxA = 7, kMaxS = 4;
 constexpr int kTable = 1024;
+constexpr int kMaxD = 3;            // temporal radius: at most kMaxD frames before and kMaxD after
 
 #if defined(__HIPCC__)
 #define G1S_DN_HD __host__ __device__ inline
@@ -38,6 +50,7 @@ struct TileGeom {
   int HS, HR;      // Hb: HR rows, stride HS (u32, odd)
   int WS, WR;      // Wb: WR rows, stride WS (u16)
   int offH, offL, offW, offT, bytes;
+  int offN, bytes_t;  // the temporal kernel's LDS: the same buffers and N behind them
 };
 
 G1S_DN_HD TileGeom tile_geom(int A, int S) {
@@ -53,6 +66,8 @@ G1S_DN_HD TileGeom tile_geom(int A, int S) {
   g.offW = (g.offL + g.LS * g.LH * 2 + 15) & ~15;
   g.offT = (g.offW + g.WS * g.WR * 2 + 15) & ~15;
   g.bytes = g.offT + kTable * 2;
+  g.offN = (g.bytes + 15) & ~15;
+  g.bytes_t = g.offN + g.LS * g.LH * 2;
   return g;
 }
 
@@ -174,17 +189,118 @@ G1S_DN_HD void dn_store(int tid, uint8_t *out, uint32_t stride, int W, int H, in
   }
 }
 
-// one tile, start to end, for thread `tid` of a workgroup whose barrier is `sync` (LDS buffers as laid out by tile_geom)
+// ---- the temporal part: one neighbour frame, staged into N by dn_stage --------------------------------------------
+
+// Hb(row, x) = sum over |kx| <= S of (L(x + kx, r) - N(x + dx + kx, r + dy))^2 for the tile's columns x < kTW and the rows
+// r = row - S, row < kTH + 2S; dx and dy of either sign.  Tasks as in dn_hsum.
+template <int S>
+G1S_DN_HD void dn_hsum_t(int tid, const TileGeom &g, const uint16_t *L, const uint16_t *N, uint32_t *Hb, int dx, int dy) {
+  constexpr int NR = kTH + 2 * S, ntasks = (kTW >> 3) * NR;
+  const uint32_t mNR = magic(NR);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = seg * 8;
+    const uint16_t *a = L + (row + g.A) * g.LS + (xs + g.A);
+    const uint16_t *b = N + (row + g.A + dy) * g.LS + (xs + g.A + dx);
+    int sq[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) {
+      const int t = (int)a[j] - (int)b[j];
+      sq[j] = t * t;
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += (uint32_t)sq[j];
+    uint32_t *o = Hb + row * g.HS + xs;
+    o[0] = s;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      s += (uint32_t)sq[j + 2 * S] - (uint32_t)sq[j - 1];
+      o[j] = s;
+    }
+  }
+}
+
+// Wb(y, x) = T[min(D_k >> q, 1023)] for the tile's samples p = (x0 + x, y0 + y); 0 where p or p + d lies outside the plane
+// (rule 6).  Tasks as in dn_weights.
+template <int S>
+G1S_DN_HD void dn_weights_t(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int x0,
+                            int y0, int W, int H) {
+  constexpr int ntasks = (kTH >> 3) * kTW;
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int x = i % kTW, ys = i / kTW * 8;
+    const uint32_t *h = Hb + ys * g.HS + x;
+    uint32_t v[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += v[j];
+    const int px = x0 + x, py = y0 + ys;
+    const bool col_ok = px < W && px + dx >= 0 && px + dx < W;
+    uint16_t *o = Wb + ys * g.WS + x;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j) s += v[j + 2 * S] - v[j - 1];
+      const uint32_t k = s >> q;
+      const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
+      const bool ok = col_ok && py + j < H && py + j + dy >= 0 && py + j + dy < H;
+      o[j * g.WS] = ok ? w : (uint16_t)0;
+    }
+  }
+}
+
+// the pair {(t, p), (t + k, p + d)} at each sample the thread owns: weight at p, sample from N
+G1S_DN_HD void dn_accumulate_t(int tid, const TileGeom &g, const uint16_t *N, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint64_t *au) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w = Wb + yb * g.WS + x;
+  const uint16_t *u = N + (yb + dy + g.R) * g.LS + x + dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w[4 * j * g.WS];
+    aw[j] += a;
+    au[j] += (uint64_t)a * u[4 * j * g.LS];
+  }
+}
+
+// (n + (d >> 1)) / d for a quotient below 2^16 (a weighted mean of samples), d < 2^24: the float quotient is within one
+// of the integer one (its relative error is a few 2^-24), and one step either way makes it exact
+G1S_DN_HD uint32_t dn_rounded_mean(uint64_t n, uint32_t d) {
+  n += d >> 1;
+  uint32_t v = (uint32_t)((float)n * (1.0f / (float)d));
+  const int64_t r = (int64_t)n - (int64_t)((uint64_t)v * d);
+  if (r < 0) --v;
+  else if (r >= (int64_t)d) ++v;
+  return v;
+}
+
+// rule 7: one rounded division per sample, the numerator in 64 bits
+template <int BPS>
+G1S_DN_HD void dn_store_t(int tid, uint8_t *out, uint32_t stride, int W, int H, int x0, int y0, const uint32_t *aw, const uint64_t *au) {
+  const int x = x0 + (tid & 63);
+  if (x >= W) return;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const int y = y0 + (tid >> 6) + 4 * j;
+    if (y >= H) break;
+    const uint32_t v = dn_rounded_mean(au[j], aw[j]);
+    uint8_t *row = out + (size_t)y * stride;
+    if (BPS == 2) reinterpret_cast<uint16_t *>(row)[x] = (uint16_t)v;
+    else row[x] = (uint8_t)v;
+  }
+}
+
+// the frame's own offsets (rules 1 - 3) of one tile for thread `tid` of a workgroup whose barrier is `sync` (LDS buffers as
+// laid out by tile_geom): L and T staged, the sums of rule 4 in aw and au
 template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
-                       uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
+G1S_DN_HD void dn_tile_spatial(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, int W,
+                               int H, int x0, int y0, Sync sync, uint32_t *aw, uint32_t *au) {
   uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + g.offH);
   uint16_t *L = reinterpret_cast<uint16_t *>(lds + g.offL), *Wb = reinterpret_cast<uint16_t *>(lds + g.offW),
            *T = reinterpret_cast<uint16_t *>(lds + g.offT);
   dn_stage<BPS>(tid, g, L, in, in_stride, W, H, x0, y0);
   for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
   sync();
-  uint32_t aw[kSPT], au[kSPT];
   dn_init(tid, g, L, aw, au);
   for (int dy = 0; dy <= g.A; ++dy) {
     const int NR = kTH + dy + 2 * S, RH = kTH + dy;
@@ -198,7 +314,47 @@ G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t 
       dn_accumulate(tid, g, L, Wb, dx, dy, aw, au);
     }
   }
+}
+
+// one tile, start to end
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
+                       uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
+  uint32_t aw[kSPT], au[kSPT];
+  dn_tile_spatial<S, BPS>(tid, g, lds, table, q, in, in_stride, W, H, x0, y0, sync, aw, au);
   dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+// one tile of the temporal filter: `nb` / `nb_stride` are the same plane of the 2 D frames around the frame in hand, a null
+// pointer where the clip has no such frame (rule 5) -- the same for every thread of the workgroup.  The order of the
+// neighbours does not show in the result: the sums are exact.
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile_t(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride,
+                         const uint8_t *const *nb, const uint32_t *nb_stride, int nnb, uint8_t *out, uint32_t out_stride, int W, int H, int x0, int y0,
+                         Sync sync) {
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + g.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + g.offL), *Wb = reinterpret_cast<uint16_t *>(lds + g.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + g.offT), *N = reinterpret_cast<uint16_t *>(lds + g.offN);
+  uint32_t aw[kSPT], au32[kSPT];
+  dn_tile_spatial<S, BPS>(tid, g, lds, table, q, in, in_stride, W, H, x0, y0, sync, aw, au32);  // (fits 32 bits, as in dn_tile)
+  uint64_t au[kSPT];
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) au[j] = au32[j];
+  for (int k = 0; k < nnb; ++k) {
+    if (!nb[k]) continue;
+    sync();  // the last dn_accumulate_t has read N
+    dn_stage<BPS>(tid, g, N, nb[k], nb_stride[k], W, H, x0, y0);
+    sync();
+    for (int dy = -g.A; dy <= g.A; ++dy)
+      for (int dx = -g.A; dx <= g.A; ++dx) {
+        dn_hsum_t<S>(tid, g, L, N, Hb, dx, dy);
+        sync();
+        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, W, H);
+        sync();
+        dn_accumulate_t(tid, g, N, Wb, dx, dy, aw, au);
+      }
+  }
+  dn_store_t<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
 }
 
 }  // namespace g1s_dn

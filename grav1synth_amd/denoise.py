@@ -5,7 +5,8 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 
 >>> dn = Denoiser(10, strength=4.0)
 >>> clean = dn.apply([y, u, v])                 # torch device tensors stay on the device; numpy in, numpy out
->>> denoise_y4m_file("grainy.y4m", "clean.y4m")
+>>> clips = Denoiser(10, temporal_radius=2).denoise_clip(frames)   # the mean also runs over 2 frames either side
+>>> denoise_y4m_file("grainy.y4m", "clean.y4m", temporal_radius=1)
 """
 from __future__ import annotations
 
@@ -54,14 +55,18 @@ def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0) -
 
 class Denoiser:
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                 strength: float = 0.0, chroma_strength: float = 0.0):
+                 strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0):
+        """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
+        runs over the D frames before and the D frames after it that the clip has."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
+        self.temporal_radius = temporal_radius
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
-        self._h = self._L.g1s_denoise_new(bit_depth, C.byref(opts))
+        self._h = self._L.g1s_denoise_new_temporal(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF)
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
-        self._keep: list = []  # planes the queued kernels still read or write
+        self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
+        self._frames = 0       # handed over since the denoiser was made, as g1s_denoise_drain counts
 
     def _check(self, rc: int) -> None:
         if rc:
@@ -70,7 +75,9 @@ class Denoiser:
     def apply(self, frame_planes: Sequence, xdec: int = 1, ydec: int = 1, *, sync: bool = True, out: Optional[Sequence] = None) -> List:
         """One frame through the filter: new planes of the same kind -- torch device tensors stay on the device, host planes
         go through host frames.  sync = False queues the frame (a batch goes out as one launch per plane class): the
-        returned planes are complete after sync()."""
+        returned planes are complete after sync(), or once drain() has counted the frame.  sync = True ends the clip with
+        this frame: with a temporal radius it is a one-frame clip unless frames were queued before it (denoise_clip takes
+        a whole clip)."""
         planes = list(frame_planes)
         if out is None:
             if torch is not None and isinstance(planes[0], torch.Tensor):
@@ -84,18 +91,35 @@ class Denoiser:
         fout = Frame(out, xdec, ydec).to_c(keep)
         if fin.on_device == 1:
             torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
-        self._keep.append((keep, planes, out))
+        self._keep.append((self._frames, (keep, planes, out)))
         self._check(self._L.g1s_denoise_frame(self._h, C.byref(fin), C.byref(fout)))
+        self._frames += 1
         if sync:
             self.sync()
         return out
 
+    def denoise_clip(self, frames: Sequence[Sequence], xdec: int = 1, ydec: int = 1) -> List[List]:
+        """The frames of one clip through the filter, in order: queued, then sync().  Returns the output frames."""
+        outs = [self.apply(f, xdec, ydec, sync=False) for f in frames]
+        self.sync()
+        return outs
+
+    def drain(self) -> int:
+        """Launches every queued frame whose later neighbours are there and waits; the clip goes on.  Returns how many frames
+        since the denoiser was made are complete (with temporal radius D the last D frames wait for sync() or more frames)."""
+        n = C.c_uint64()
+        self._check(self._L.g1s_denoise_drain(self._h, C.byref(n)))
+        # frame k's input is a neighbour of the frames up to k + D
+        self._keep = [e for e in self._keep if e[0] + self.temporal_radius >= n.value]
+        return int(n.value)
+
     def sync(self) -> None:
+        """Launches what is queued and waits.  The clip ends here."""
         self._check(self._L.g1s_denoise_sync(self._h))
         self._keep.clear()
 
     def kernel_times(self, enable: bool = True):
-        """(ms in kd_nlm, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        """(ms in kd_nlm / kd_nlm_t, frames) of the timed batches so far (HIP events); enables / disables the timing."""
         a, n = C.c_double(), C.c_uint64()
         self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
         return a.value, n.value
@@ -114,12 +138,12 @@ class Denoiser:
 
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                     strength: float = 0.0, chroma_strength: float = 0.0) -> int:
-    """`denoise INPUT -o OUTPUT` for a .y4m input.  Returns the number of frames."""
+                     strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0) -> int:
+    """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
-    n = L.g1s_denoise_y4m_file(input.encode(), output.encode(), C.byref(opts), err, len(err))
+    n = L.g1s_denoise_y4m_file_temporal(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

@@ -455,7 +455,22 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *      T[i] = round(4096 exp(-((i + 1/2) 2^q) / (n h^2 4^(B - 8)))) for i >= 1, q the smallest shift >= 0 that gives
  *      T[1023] = 0.  g1s_denoise_weights returns the table the kernels use.
  *   4. out(p) = (sum_d w u(p + d) + (sum_d w >> 1)) / sum_d w, integer division (uint32 suffices for A <= 7).
- * No temporal part, no luma-guided chroma, no dithering.  Samples above the bit depth's maximum are the caller's error.
+ * The temporal part: with a temporal radius D (0..3; g1s_denoise_new_temporal) the mean of rule 4 also runs over the
+ * search windows of the D frames before and the D frames after the frame in hand.  A CLIP is the run of frames handed
+ * to one denoiser between two clip ends, numbered t = 0 .. N - 1, all of one geometry; a clip ends at
+ * g1s_denoise_sync, at a frame whose geometry differs from the one before it (that frame starts the next clip) and at
+ * g1s_denoise_free.  For plane u_t of frame t, with the same A, S, q and T:
+ *   5. For k in -D .. D, frame t + k takes part only if 0 <= t + k < N: skipped, not clamped (rule 2's idea in time; a
+ *      one-frame clip is filtered as with D = 0).
+ *   6. For k != 0: D_k(p, d) = sum over |kx|, |ky| <= S of (u_t(clamp(p + k)) - u_{t+k}(clamp(p + d + k)))^2 for ALL
+ *      |dx|, |dy| <= A, d = 0 included (with its real distance, not a forced 0).  (p, d, k) takes part only if p + d
+ *      lies inside the plane.  w = T[min(D_k >> q, 1023)]: the same table, no attenuation with |k|.  For k = 0 rules
+ *      1 - 3 as they stand.
+ *   7. out_t(p) = (sum_{k,d} w u_{t+k}(p + d) + (sum w >> 1)) / sum w, integer division, the sums over everything that
+ *      takes part; (k = 0, d = 0) carries 4096 as in rule 4.  sum w <= (2D + 1)(2A + 1)^2 4096 fits 32 bits; the
+ *      numerator does not (12 bit, A = 7, D = 1: 1.1e10) and is kept in 64.  Exact for every accepted (B, A, D).
+ * D = 0 is rules 1 - 4.  No motion compensation, no luma-guided chroma, no dithering.  Samples above the bit depth's
+ * maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes) on the denoiser's own stream.  Errors are sticky (g1s_denoise_last_error). */
 typedef struct {
@@ -471,15 +486,29 @@ typedef struct g1s_denoise g1s_denoise_t;
 /* bit_depth 8, 10 or 12.  Parameters out of range and other bit depths are refusals, not clamps: NULL, the reason from
  * g1s_last_global_error() (they are checked before a device is looked for).  opts == NULL: current device, defaults. */
 g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts);
+/* The same with a temporal radius D (rules 5 - 7); g1s_denoise_new is temporal_radius = 0.  A radius above 3 is a
+ * refusal like the others ("temporal_radius must be 0..3"). */
+g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius);
 /* One frame.  in / out follow g1s_frame_t.on_device independently, as in g1s_grain_frame: 0 = host (in: copied before
  * the call returns; out: written by g1s_denoise_sync at the latest), 1 = device, 2 = pinned host (copies queued).  Device
  * and pinned planes of in must stay valid and unmodified, and every plane of out must stay valid, until
  * g1s_denoise_sync.  in and out must be DISTINCT, non-overlapping buffers (a workgroup reads the samples around its
  * tile, which another one would already have replaced).  Same geometry on both sides; a frame whose geometry differs
- * from the one before it drains the queue first. */
+ * from the one before it ends the clip: what is queued goes out and finishes first.
+ * With a temporal radius D > 0 a frame is launched once the D frames after it have been handed over: a full batch goes
+ * out without the last D frames, which wait for their neighbours (or the end of the clip).  Frame n, counted since the
+ * denoiser was made as g1s_denoise_drain counts, is read by the frames up to n + D: device and pinned planes of in must
+ * stay valid and unmodified until frames_complete exceeds n + D, or until g1s_denoise_sync.  Host planes are still copied
+ * before the call returns (the denoiser keeps a batch and the 2 D frames around it on the device).  out as above: valid
+ * until frames_complete exceeds n, or until g1s_denoise_sync; it must not overlap a plane the queue still reads. */
 int g1s_denoise_frame(g1s_denoise_t *, const g1s_frame_t *in, g1s_frame_t *out);
-/* Launches what is queued and waits: the out planes of every frame handed over are complete. */
+/* Launches what is queued and waits: the out planes of every frame handed over are complete.  This ends the clip: with a
+ * temporal radius the last D frames go out with the neighbours they have, and the next frame starts a new clip. */
 int g1s_denoise_sync(g1s_denoise_t *);
+/* Launches every queued frame whose D later neighbours have been handed over, waits, and reports in *frames_complete
+ * (may be NULL) how many frames since the denoiser was made have complete out planes.  It does NOT end the clip.  With
+ * temporal radius 0 it completes what g1s_denoise_sync completes. */
+int g1s_denoise_drain(g1s_denoise_t *, uint64_t *frames_complete);
 /* HIP-event time of the kernels so far, milliseconds, and the frames they covered (enable = 1: timed from the next
  * batch on; a timed batch is waited for).  tools/bench_denoise.py. */
 int g1s_denoise_set_timing(g1s_denoise_t *, int enable, double *ms_kernel, uint64_t *frames);
@@ -491,6 +520,9 @@ int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double streng
 /* `denoise INPUT -o OUTPUT`: every frame of a .y4m through the filter, written as .y4m (the input's header line,
  * "FRAME\n", the planes without padding).  Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
 int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap);
+/* The same with a temporal radius; the whole file is one clip.  g1s_denoise_y4m_file is temporal_radius = 0. */
+int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
+                                      size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -498,6 +530,10 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
  * there as .y4m.  The table is the one g1s_diff_y4m_files makes from SOURCE and that clip. */
 int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                const g1s_denoise_opts_t *dopts, uint64_t *frames, char *err, size_t cap);
+/* The same with a temporal radius; the whole file is one clip, and a source buffer is used again only when the denoiser
+ * is past the D frames after it as well.  g1s_diff_y4m_file_denoised is temporal_radius = 0. */
+int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                        const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames, char *err, size_t cap);
 
 #ifdef __cplusplus
 }

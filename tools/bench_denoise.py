@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernel kd_nlm over device-resident frames,
-4K 10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 64, at the defaults (A = 3, S = 2) and at A = 7, S = 3.  Per case: HIP-event
-time per batch around the two launches (timed batches run alone and are waited for), frames a second from it, the kernel's
-arithmetic as the specification counts it -- samples x unordered pairs A + A (2A + 1) -- and the job rate through
-g1s_denoise_frame with the timing off.  One JSON line per case.  For the kernel trace:
+"""tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernels kd_nlm and kd_nlm_t over
+device-resident frames, 4K 10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 64, at the defaults (A = 3, S = 2) and at A = 7, S = 3
+with temporal radius 0, and at the defaults with temporal radius 1 and 2.  Per case: HIP-event time per batch around the two
+launches (timed batches run alone and are waited for), frames a second from it, the kernel's arithmetic as the specification
+counts it -- samples x pairs: the unordered pairs A + A (2A + 1) of the frame itself and, per neighbour frame, the (2A + 1)^2
+one-sided pairs of rule 6 (a frame at the end of a clip has fewer; the runs are clips of many batches) -- and the job rate
+through g1s_denoise_frame with the timing off.  One JSON line per case.  For the kernel trace:
 rocprofv3 --kernel-trace --stats -- python tools/bench_denoise.py 1 (a run of its own)."""
 import json, os, sys, time
 
@@ -22,8 +24,8 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
     outs = [[torch.empty_like(p) for p in ins[0]] for _ in range(BATCH)]
     torch.cuda.synchronize()
     samples = sum(p.numel() for p in ins[0])
-    for A, S in ((3, 2), (7, 3)):
-        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S)
+    for A, S, D in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (3, 2, 2)):
+        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D)
 
         def run(nb):
             for k in range(nb * BATCH):
@@ -38,11 +40,11 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
         run(batches)
         ms, fr = dn.kernel_times(False)
         dn.close()
-        pairs = A + A * (2 * A + 1)
+        pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
-            "format": name, "search_radius": A, "patch_radius": S, "batch_frames": BATCH, "timed_batches": fr / BATCH,
-            "samples_per_frame": samples, "unordered_pairs": pairs,
+            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            "samples_per_frame": samples, "unordered_pairs": pairs, "temporal_pairs": temporal_pairs,
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
-            "sample_pairs_per_ns": samples * pairs * fr / (ms * 1e6),
+            "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
             "job_frames_per_s_untimed": batches * BATCH / dt,
         }), flush=True)
