@@ -407,7 +407,9 @@ int g1s_estimate::flush() {
   const bool packed = bit_depth <= 12 && !(mode && std::strcmp(mode, "wide") == 0);
   ep.col_strips = ((int)W - 1 + kColsPerWave - 1) / kColsPerWave;
   int strip_rows = kStripRows;
-  if (packed && H >= 3) {
+  // a plane without interior pixels (one or two samples wide or high; one sample wide: no column strip at all) launches nothing
+  const bool launch = W >= 3 && H >= 3;
+  if (packed && launch) {
     // whole resident rounds: k rounds of `resident` waves, the smallest k whose strips are at most kPkMaxStripRows rows
     int cus = 256, wgs_per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -424,7 +426,7 @@ int g1s_estimate::flush() {
   }
   ep.strip_rows = strip_rows;
   ep.row_strips = ((int)H - 2 + strip_rows - 1) / strip_rows;
-  if (W >= 3 && H >= 3) {
+  if (launch) {
     const dim3 grid((ep.col_strips * ep.row_strips + kWavesPerWg - 1) / kWavesPerWg, B);
     if (timing) EST_TRY(hipEventRecord(ev0, stream));
     if (packed && bps == 2) hipLaunchKernelGGL(k_estimate_pk<2>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
@@ -436,7 +438,7 @@ int g1s_estimate::flush() {
   EST_TRY(hipMemcpyAsync(h_sums, d_sums, sizeof(unsigned long long) * 2 * B, hipMemcpyDeviceToHost, stream));
   EST_TRY(hipStreamSynchronize(stream));
   EST_TRY(hipGetLastError());
-  if (timing && W >= 3 && H >= 3) {
+  if (timing && launch) {
     float ms = 0;
     EST_TRY(hipEventElapsedTime(&ms, ev0, ev1));
     ms_kernel += ms;

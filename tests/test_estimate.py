@@ -158,6 +158,25 @@ def test_hip_estimates_equal_the_oracle(spec, where):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 3), (1, 40), (2, 40), (40, 1), (40, 2), (1, 1)])
+def test_hip_estimate_of_a_plane_without_interior_pixels(w, h):
+    """A plane one or two samples wide or high has no interior pixel: None, as the oracle says (a width of 1 with three or
+    more rows used to divide by its zero column strips on the host: found by the sweep, tests/test_gpu_sweep.py)."""
+    import torch
+
+    from grav1synth_amd.estimate import NoiseEstimator
+
+    for bd in (8, 10):
+        p = np.full((h, w), 5 << (bd - 8), np.uint8 if bd == 8 else np.uint16)
+        assert estimate_plane_noise(p, bd) is None
+        est = NoiseEstimator(bd, batch_frames=2)
+        for _ in range(3):
+            est.estimate_frame(torch.from_numpy(p).cuda())
+        assert est.finish() == [None, None, None]
+        est.close()
+
+
+@pytest.mark.gpu
 def test_estimate_command_on_a_y4m_file(tmp_path):
     from grav1synth_amd import cli
     from grav1synth_amd.ingest import write_y4m

@@ -1,7 +1,7 @@
 """The device half of the per-frame fold (csrc/latest.hip, G1S_LATEST=device) at the edges of its chunked lists: the strength
-pass takes a frame's blocks 512 at a time, partitions their terms by bin into lists in LDS and adds every list front to back --
-the totals included, as the list of every measured block.  The cases here fill a chunk's lists to the brim (every one of 512
-blocks measured, and all of them in one bin), leave a short last chunk, and go through the refusals; each compares the device
+pass takes a frame's blocks 1 024 at a time, partitions their terms by bin into lists in LDS and adds every list front to back --
+the totals included, as the list of every measured block.  The cases here fill a chunk's lists to the brim (every one of 1 024
+blocks measured, and all of them in one bin), leave a short last chunk (tests/test_gpu_latest_wide.py has the chunk edges block by block) and go through the refusals; each compares the device
 half's blobs with the host half's, byte for byte.  The last case holds the engine's own choice of the half (G1S_LATEST unset) to
 the frame size it is made by."""
 from fractions import Fraction
@@ -52,11 +52,12 @@ def _grey_pair(w, h, seed, level=100, amp=3):
 
 
 @pytest.mark.parametrize("spec,lag,chroma", [
-    (SynthSpec(1056, 560, 8, textured=False), 3, True),   # 594 blocks, all flat: a full chunk of 512 and a short one; ragged bottom edge
+    (SynthSpec(1056, 560, 8, textured=False), 3, True),   # 594 blocks, all flat: one short chunk; ragged bottom edge
+    (SynthSpec(1504, 1000, 8, textured=False), 2, False), # 1 504 blocks, luma only: a full chunk and a short one; ragged bottom edge
     (SynthSpec(1190, 602, 10, textured=False), 2, True),  # ragged in both directions
     (SynthSpec(1056, 560, 8, textured=False), 3, False),  # luma only
     (SynthSpec(1056, 560, 8), 3, False),                  # luma only, textured: chunks with a few measured blocks
-], ids=["all_flat_594", "all_flat_ragged", "all_flat_luma_only", "textured_luma_only"])
+], ids=["all_flat_594", "all_flat_1504_luma_only", "all_flat_ragged", "all_flat_luma_only", "textured_luma_only"])
 def test_full_and_short_chunks_give_the_host_halfs_bytes(monkeypatch, spec, lag, chroma):
     frames = [make_pair(spec, k, device="cuda") for k in range(3)]
     host = _blobs(monkeypatch, "host", frames, spec.bit_depth, lag, chroma, spec.xdec, spec.ydec)
@@ -67,14 +68,14 @@ def test_full_and_short_chunks_give_the_host_halfs_bytes(monkeypatch, spec, lag,
 
 
 def test_every_block_in_one_bin_gives_the_host_halfs_bytes(monkeypatch):
-    """1024 x 544: 544 blocks of one mean, nearly all of them flat -- ONE diagonal list and one b list take a chunk's terms, every
-    other list is empty."""
-    frames = [_grey_pair(1024, 544, seed) for seed in (1, 2)]
+    """1024 x 1120: 1 120 blocks of one mean, nearly all of them flat -- ONE diagonal list and one b list take a whole chunk's
+    1 024 terms and a short chunk's, every other list is empty."""
+    frames = [_grey_pair(1024, 1120, seed) for seed in (1, 2)]
     host = _blobs(monkeypatch, "host", frames)
     dev = _blobs(monkeypatch, "device", frames)
     _same(host, dev, len(frames))
     assert all(_status(b) == 0 for b in host), [_status(b) for b in host]
-    assert all(_measured(b) > 512 for b in host), [_measured(b) for b in host]
+    assert all(_measured(b) > 1024 for b in host), [_measured(b) for b in host]
 
 
 def test_fewer_than_two_flat_blocks_is_the_host_halfs_refusal(monkeypatch):
