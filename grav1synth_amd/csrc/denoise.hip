@@ -25,6 +25,7 @@
 
 #include "../../include/g1s_diff.h"
 #include "denoise_tile.hip.h"
+#include "frame_op.h"
 
 extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
 extern "C" void g1s_diff_set_error_text_(g1s_diff_t *, const char *);
@@ -87,7 +88,31 @@ __global__ __launch_bounds__(kThreads) void kd_nlm(DenoiseParams p) {
                   ty * kTH, [] { __syncthreads(); });
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the two kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
+struct Plain {
+  using Params = DenoiseParams;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+struct Temporal {
+  using Params = DenoiseParamsT;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_t<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+
+// the family's kernel for patch radius S and `bps` bytes a sample; false: there is none
+template <class Family>
+bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t st, const typename Family::Params &p) {
+  switch (S * 2 + (bps - 1)) {
+#define DN_CASE(s)                                                             \
+  case (s) * 2: Family::template launch<s, 1>(grid, lds, st, p); return true; \
+  case (s) * 2 + 1: Family::template launch<s, 2>(grid, lds, st, p); return true;
+    DN_CASE(1)
+    DN_CASE(2)
+    DN_CASE(3)
+    DN_CASE(4)
+#undef DN_CASE
+  }
+  return false;
+}
 
 // rule 3.  "" when fine.
 std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTable], uint32_t *q_out) {
@@ -107,16 +132,13 @@ std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTab
 }  // namespace
 
 // =============================================================== host engine =====
-struct g1s_denoise {
-  int device = 0;
-  uint32_t bit_depth = 8, bps = 1, batch = 32;
+using namespace g1s_op;
+
+// (the stream, the sticky error, the parameter sets' turn and the staging of host frames: BatchedOp, frame_op.h)
+struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
   uint32_t q[2] = {0, 0};  // luma, chroma
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool have_geom = false;
-  int W = 0, H = 0, subx = 0, suby = 0, nplanes = 0;
-  size_t plane_row[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, stage_frame = 0;  // staging layout of a host frame on the device
+  Event ev[2];
   // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
   // output goes (out[c] is null for a host frame: a slot of the output staging buffer is chosen at the launch)
   struct Queued {
@@ -124,121 +146,68 @@ struct g1s_denoise {
     uint8_t *out[3];
     uint32_t in_stride[3], out_stride[3];
     bool host_out;
-    void *host_data[3];
-    size_t host_stride[3];
+    HostPlanes host;
   };
   // frames [first_queued, frames_in): what is not launched yet and, in front of it, up to D launched frames of the same clip
   std::deque<Queued> queue;
   uint64_t frames_in = 0, first_queued = 0, next_launch = 0, clip_first = 0, frames_complete = 0;
-  // the jobs of a batch, two sets in turn: pinned on the host, uploaded on the stream, free again when the event behind
-  // the batch's kernels has passed -- the next batch is filled while this one runs
-  uint8_t *d_jobs[2] = {nullptr, nullptr}, *h_jobs[2] = {nullptr, nullptr};
-  hipEvent_t done[2] = {nullptr, nullptr};
-  uint64_t batches = 0;
-  uint16_t *d_tables = nullptr;  // [2][1024]
-  uint8_t *d_stage_in = nullptr, *d_stage_out = nullptr;
-  int err_code = 0;
-  std::string err;
-  bool timing = false;
+  ParamSets<uint8_t> p_jobs;  // DenoiseJob or, with a temporal radius, DenoiseJobT
+  DevBuf<uint16_t> d_tables;  // [2][1024]
   double ms_kernel = 0;
   uint64_t frames_timed = 0;
 
-  int fail(int code, const std::string &m) {
-    if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
-    return err_code;
-  }
-  size_t pw(int c) const { return c ? (size_t)((W + subx) >> subx) : (size_t)W; }
-  size_t ph(int c) const { return c ? (size_t)((H + suby) >> suby) : (size_t)H; }
   size_t job_bytes() const { return D ? sizeof(DenoiseJobT) : sizeof(DenoiseJob); }
   // host and pinned inputs wait on the device in a ring: a slot is written again B + 2D frames later, and by then every
   // frame that reads it (up to D frames on) has been launched in front of that copy on the stream
   uint32_t ring() const { return batch + 2 * D; }
   const Queued &frame(uint64_t n) const { return queue[(size_t)(n - first_queued)]; }
-  void set_geometry(const g1s_frame_t &f);
   int launch(int set, uint32_t nframes, int plane0, int nplanes_in_class);
   int flush(uint32_t nframes);
   int launch_up_to(uint64_t limit);
   int end_clip();
 };
 
-#define DN_TRY(expr)                                                                                         \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
-
-void g1s_denoise::set_geometry(const g1s_frame_t &f) {
-  W = (int)f.width, H = (int)f.height, subx = f.xdec, suby = f.ydec, nplanes = f.nplanes;
-  size_t off = 0;
-  for (int c = 0; c < nplanes; ++c) {
-    plane_row[c] = align_up(pw(c) * bps, 16);
-    plane_off[c] = off;
-    off += align_up(plane_row[c] * ph(c), 256);
-  }
-  stage_frame = off;
-  have_geom = true;
-}
-
 int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_class) {
-  DenoiseParams p{};
-  p.jobs = reinterpret_cast<const DenoiseJob *>(d_jobs[set]), p.table = d_tables + (plane0 ? kTable : 0), p.q = (int)q[plane0 ? 1 : 0], p.A = (int)A;
-  p.W = (int)pw(plane0), p.H = (int)ph(plane0), p.tiles_x = (p.W + kTW - 1) / kTW, p.plane0 = plane0;
-  const dim3 grid((unsigned)(p.tiles_x * ((p.H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
-  const TileGeom geom = tile_geom((int)A, (int)S);
+  const int W = (int)geom.pw(plane0), H = (int)geom.ph(plane0), tiles_x = (W + kTW - 1) / kTW;
+  auto fill = [&](auto &p) {
+    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p), p.table = d_tables + (plane0 ? kTable : 0), p.q = (int)q[plane0 ? 1 : 0], p.A = (int)A;
+    p.W = W, p.H = H, p.tiles_x = tiles_x, p.plane0 = plane0;
+  };
+  const dim3 grid((unsigned)(tiles_x * ((H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
+  const TileGeom tg = tile_geom((int)A, (int)S);
+  bool found;
   if (D) {
     DenoiseParamsT t{};
-    t.jobs = reinterpret_cast<const DenoiseJobT *>(d_jobs[set]), t.table = p.table, t.q = p.q, t.A = p.A, t.W = p.W, t.H = p.H, t.tiles_x = p.tiles_x,
-    t.plane0 = plane0, t.nnb = (int)(2 * D);
-    const size_t lds = (size_t)geom.bytes_t;
-    switch (S * 2 + (bps - 1)) {
-#define DN_CASE(s)                                                                                  \
-  case (s) * 2: hipLaunchKernelGGL((kd_nlm_t<s, 1>), grid, dim3(kThreads), lds, stream, t); break; \
-  case (s) * 2 + 1: hipLaunchKernelGGL((kd_nlm_t<s, 2>), grid, dim3(kThreads), lds, stream, t); break;
-      DN_CASE(1)
-      DN_CASE(2)
-      DN_CASE(3)
-      DN_CASE(4)
-#undef DN_CASE
-      default: return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
-    }
-    DN_TRY(hipGetLastError());
-    return G1S_OK;
+    fill(t), t.nnb = (int)(2 * D);
+    found = launch_family<Temporal>(S, bps, grid, (size_t)tg.bytes_t, stream, t);
+  } else {
+    DenoiseParams p{};
+    fill(p);
+    found = launch_family<Plain>(S, bps, grid, (size_t)tg.bytes, stream, p);
   }
-  const size_t lds = (size_t)geom.bytes;
-  switch (S * 2 + (bps - 1)) {
-#define DN_CASE(s)                                                                          \
-  case (s) * 2: hipLaunchKernelGGL((kd_nlm<s, 1>), grid, dim3(kThreads), lds, stream, p); break; \
-  case (s) * 2 + 1: hipLaunchKernelGGL((kd_nlm<s, 2>), grid, dim3(kThreads), lds, stream, p); break;
-    DN_CASE(1)
-    DN_CASE(2)
-    DN_CASE(3)
-    DN_CASE(4)
-#undef DN_CASE
-    default: return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
-  }
-  DN_TRY(hipGetLastError());
+  if (!found) return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
+  G1S_OP_TRY(hipGetLastError());
   return G1S_OK;
 }
 
 // frames next_launch .. next_launch + nframes - 1 as one batch (nframes <= batch); their neighbours are in the queue
 int g1s_denoise::flush(uint32_t nframes) {
   if (!nframes) return G1S_OK;
-  const int set = (int)(batches & 1);
-  if (batches >= 2) DN_TRY(hipEventSynchronize(done[set]));
-  ++batches;
+  int set, rc = next_set(&set);
+  if (rc) return rc;
   bool host_outs = false;
   for (uint32_t i = 0; i < nframes; ++i) {
     const uint64_t n = next_launch + i;
     const Queued &f = frame(n);
     DenoiseJob job{};
-    for (int c = 0; c < nplanes; ++c) {
+    for (int c = 0; c < geom.nplanes; ++c) {
       job.in[c] = f.in[c], job.in_stride[c] = f.in_stride[c];
-      job.out[c] = f.host_out ? d_stage_out + stage_frame * i + plane_off[c] : f.out[c];
-      job.out_stride[c] = f.host_out ? (uint32_t)plane_row[c] : f.out_stride[c];
+      job.out[c] = f.host_out ? stage_out(i, c) : f.out[c];
+      job.out_stride[c] = f.host_out ? (uint32_t)stage.row[c] : f.out_stride[c];
     }
     host_outs = host_outs || f.host_out;
     if (!D) {
-      reinterpret_cast<DenoiseJob *>(h_jobs[set])[i] = job;
+      reinterpret_cast<DenoiseJob *>(p_jobs.h[set].p)[i] = job;
       continue;
     }
     DenoiseJobT t{};
@@ -247,30 +216,23 @@ int g1s_denoise::flush(uint32_t nframes) {
     for (int64_t m = (int64_t)n - (int64_t)D; m <= (int64_t)(n + D); ++m) {
       if (m == (int64_t)n) continue;
       if (m >= (int64_t)clip_first && m < (int64_t)frames_in)  // rule 5: the frames the clip has
-        for (int c = 0; c < nplanes; ++c) t.nb[c][k] = frame((uint64_t)m).in[c], t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
+        for (int c = 0; c < geom.nplanes; ++c) t.nb[c][k] = frame((uint64_t)m).in[c], t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
       ++k;
     }
-    reinterpret_cast<DenoiseJobT *>(h_jobs[set])[i] = t;
+    reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p)[i] = t;
   }
-  DN_TRY(hipMemcpyAsync(d_jobs[set], h_jobs[set], job_bytes() * nframes, hipMemcpyHostToDevice, stream));
-  if (timing) DN_TRY(hipEventRecord(ev[0], stream));
-  int rc = launch(set, nframes, 0, 1);
-  if (rc) return rc;
-  if (nplanes == 3 && (rc = launch(set, nframes, 1, 2)) != 0) return rc;
-  if (timing) DN_TRY(hipEventRecord(ev[1], stream));
-  DN_TRY(hipEventRecord(done[set], stream));
-  if (host_outs)
-    for (uint32_t i = 0; i < nframes; ++i) {
-      const Queued &f = frame(next_launch + i);
-      if (!f.host_out) continue;
-      for (int c = 0; c < nplanes; ++c)
-        DN_TRY(hipMemcpy2DAsync(f.host_data[c], f.host_stride[c], d_stage_out + stage_frame * i + plane_off[c], plane_row[c], pw(c) * bps, ph(c),
-                                hipMemcpyDeviceToHost, stream));
-    }
+  G1S_OP_TRY(p_jobs.upload(set, job_bytes() * nframes, stream));
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
+  if ((rc = launch(set, nframes, 0, 1)) != 0) return rc;
+  if (geom.nplanes == 3 && (rc = launch(set, nframes, 1, 2)) != 0) return rc;
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
+  if ((rc = set_done(set)) != 0) return rc;
+  for (uint32_t i = 0; host_outs && i < nframes; ++i)
+    if (frame(next_launch + i).host_out && (rc = copy_back(i, frame(next_launch + i).host)) != 0) return rc;
   if (timing) {
-    DN_TRY(hipStreamSynchronize(stream));
+    G1S_OP_TRY(hipStreamSynchronize(stream));
     float a = 0;
-    DN_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+    G1S_OP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
     ms_kernel += a, frames_timed += nframes;
   }
   next_launch += nframes;
@@ -290,23 +252,12 @@ int g1s_denoise::launch_up_to(uint64_t limit) {
 
 // the clip ends here: what is queued goes out with the neighbours it has and is waited for
 int g1s_denoise::end_clip() {
-  const int rc = launch_up_to(frames_in);
-  if (rc) return rc;
-  if (hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
+  int rc = launch_up_to(frames_in);
+  if (rc || (rc = wait()) != 0) return rc;
   queue.clear();
   first_queued = clip_first = frames_complete = frames_in;
   return G1S_OK;
 }
-
-namespace {
-
-// the bytes of plane c of a frame of the denoiser's geometry at `base`
-bool planes_overlap(const g1s_denoise &g, const uint8_t *a, uint32_t a_stride, int ca, const uint8_t *b, uint32_t b_stride, int cb) {
-  const uint8_t *ae = a + (size_t)a_stride * (g.ph(ca) - 1) + g.pw(ca) * g.bps, *be = b + (size_t)b_stride * (g.ph(cb) - 1) + g.pw(cb) * g.bps;
-  return a < be && b < ae;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -350,30 +301,17 @@ g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_op
     g1s_set_global_error_(why.c_str());
     return nullptr;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g1s_set_global_error_("no HIP device available: denoise has no CPU fallback");
-    return nullptr;
-  }
-  int device = opts ? opts->device : -1;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) {
-    g1s_set_global_error_("hipGetDevice failed");
+  int device = 0;
+  why = pick_device(opts ? opts->device : -1, "denoise", &device);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
     return nullptr;
   }
   g1s_denoise *g = new g1s_denoise;
-  g->device = device;
-  g->bit_depth = bit_depth;
-  g->bps = bit_depth > 8 ? 2 : 1;
-  g->batch = opts && opts->batch_frames ? std::min(opts->batch_frames, 256u) : 32u;
   g->A = A, g->S = S, g->D = temporal_radius, g->q[0] = q[0], g->q[1] = q[1];
-  const size_t jobs_bytes = g->job_bytes() * g->batch;
-  bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess;
-  for (auto &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  for (int k = 0; k < 2; ++k)
-    ok = ok && hipEventCreateWithFlags(&g->done[k], hipEventDisableTiming) == hipSuccess &&
-         hipMalloc((void **)&g->d_jobs[k], jobs_bytes) == hipSuccess &&
-         hipHostMalloc((void **)&g->h_jobs[k], jobs_bytes, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc((void **)&g->d_tables, tables.size() * 2) == hipSuccess &&
+  bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
+  for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  ok = ok && g->p_jobs.alloc(g->job_bytes() * g->batch) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
        hipMemcpy(g->d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
@@ -387,73 +325,45 @@ int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out)
   if (!g || !in || !out) return G1S_ERR_INVALID;
   if (g->err_code) return g->err_code;
   (void)hipSetDevice(g->device);
-  if (in->bytes_per_sample != g->bps || out->bytes_per_sample != g->bps)
-    return g->fail(G1S_ERR_INVALID, "bytes_per_sample does not match the bit depth given to g1s_denoise_new");
-  if (in->width < 1 || in->height < 1 || in->width > 65536u || in->height > 65536u || (in->nplanes != 1 && in->nplanes != 3) || in->xdec > 1 ||
-      in->ydec > in->xdec)
-    return g->fail(G1S_ERR_INVALID, "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)");
-  if (out->width != in->width || out->height != in->height || out->nplanes != in->nplanes || out->xdec != in->xdec || out->ydec != in->ydec)
-    return g->fail(G1S_ERR_DIM_MISMATCH, "input and output frame geometry differ");
-  if (!g->have_geom) {
-    g->set_geometry(*in);
-  } else if (g->W != (int)in->width || g->H != (int)in->height || g->nplanes != in->nplanes || g->subx != in->xdec || g->suby != in->ydec) {
+  const Refusal no = check_frame_pair(*in, *out, g->bps, 65536u, "g1s_denoise_new",
+                                      "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)");
+  if (no.code) return g->fail(no.code, no.text);
+  int rc;
+  if (g->have_geom && !g->geom.same_shape(*in)) {
     // a new geometry: the clip ends, what is queued goes out and finishes first, the staging buffers are sized again
-    const int rc = g->end_clip();
-    if (rc) return rc;
-    if (g->d_stage_in) (void)hipFree(g->d_stage_in), g->d_stage_in = nullptr;
-    if (g->d_stage_out) (void)hipFree(g->d_stage_out), g->d_stage_out = nullptr;
-    g->set_geometry(*in);
+    if ((rc = g->end_clip()) != 0) return rc;
+    g->have_geom = false;
   }
+  if (!g->have_geom) g->set_frame_geometry(*in);
+  const PlaneGeom &gm = g->geom;
   g1s_denoise::Queued f{};
-  const uint32_t slot = (uint32_t)(g->frames_in % g->ring());
+  // the input ring's slot: a launched frame stays a neighbour.  The output buffer is `batch` slots, chosen at the launch
+  if ((rc = g->stage_in(*in, (uint32_t)(g->frames_in % g->ring()), g->ring(), f.in, f.in_stride)) != 0) return rc;
   f.host_out = out->on_device != 1;
-  for (int c = 0; c < g->nplanes; ++c) {
-    const size_t pw = g->pw(c), ph = g->ph(c);
-    if (!in->data[c] || !out->data[c] || in->stride_bytes[c] < pw * g->bps || out->stride_bytes[c] < pw * g->bps ||
-        in->stride_bytes[c] > 0xffffffffu || out->stride_bytes[c] > 0xffffffffu || (g->bps == 2 && ((in->stride_bytes[c] | out->stride_bytes[c]) & 1)))
-      return g->fail(G1S_ERR_INVALID, "bad plane pointer or row stride");
-    if (in->on_device == 1) {
-      f.in[c] = static_cast<const uint8_t *>(in->data[c]);
-      f.in_stride[c] = (uint32_t)in->stride_bytes[c];
-    } else {
-      if (!g->d_stage_in && hipMalloc((void **)&g->d_stage_in, g->stage_frame * g->ring()) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
-      uint8_t *dst = g->d_stage_in + g->stage_frame * slot + g->plane_off[c];
-      // host planes are read before the call returns (the stream copy is waited for below); pinned planes are queued
-      if (hipMemcpy2DAsync(dst, g->plane_row[c], in->data[c], in->stride_bytes[c], pw * g->bps, ph, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
-      f.in[c] = dst;
-      f.in_stride[c] = (uint32_t)g->plane_row[c];
-    }
-    if (f.host_out) {
-      if (!g->d_stage_out && hipMalloc((void **)&g->d_stage_out, g->stage_frame * g->batch) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
-      f.host_data[c] = const_cast<void *>(out->data[c]), f.host_stride[c] = out->stride_bytes[c];
-    } else {
-      f.out[c] = static_cast<uint8_t *>(const_cast<void *>(out->data[c]));
-      f.out_stride[c] = (uint32_t)out->stride_bytes[c];
-    }
-  }
+  if (f.host_out && (rc = g->need_stage_out(g->batch)) != 0) return rc;
+  if (f.host_out) f.host = host_planes(*out);
+  for (int c = 0; !f.host_out && c < gm.nplanes; ++c)
+    f.out[c] = static_cast<uint8_t *>(const_cast<void *>(out->data[c])), f.out_stride[c] = (uint32_t)out->stride_bytes[c];
   // in != out: no device plane of the output may overlap a plane of the input -- nor, with a temporal radius, a plane the
   // queue still reads, and no plane of the input may be one that a frame of the queue is going to write
   if (!f.host_out) {
-    for (int c = 0; c < g->nplanes; ++c)
-      for (int d = 0; d < g->nplanes; ++d) {
-        bool bad = planes_overlap(*g, f.out[c], f.out_stride[c], c, f.in[d], f.in_stride[d], d);
+    for (int c = 0; c < gm.nplanes; ++c)
+      for (int d = 0; d < gm.nplanes; ++d) {
+        bool bad = planes_overlap(gm, f.out[c], f.out_stride[c], c, f.in[d], f.in_stride[d], d);
         if (g->D)
-          for (const g1s_denoise::Queued &o : g->queue) bad = bad || planes_overlap(*g, f.out[c], f.out_stride[c], c, o.in[d], o.in_stride[d], d);
+          for (const g1s_denoise::Queued &o : g->queue) bad = bad || planes_overlap(gm, f.out[c], f.out_stride[c], c, o.in[d], o.in_stride[d], d);
         if (bad) return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_denoise_frame needs distinct buffers");
       }
   }
   for (uint64_t n = g->next_launch; g->D && n < g->frames_in; ++n) {
     const g1s_denoise::Queued &o = g->frame(n);
     if (o.host_out) continue;
-    for (int c = 0; c < g->nplanes; ++c)
-      for (int d = 0; d < g->nplanes; ++d)
-        if (planes_overlap(*g, o.out[c], o.out_stride[c], c, f.in[d], f.in_stride[d], d))
+    for (int c = 0; c < gm.nplanes; ++c)
+      for (int d = 0; d < gm.nplanes; ++d)
+        if (planes_overlap(gm, o.out[c], o.out_stride[c], c, f.in[d], f.in_stride[d], d))
           return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_denoise_frame needs distinct buffers");
   }
-  if (in->on_device == 0 && hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
+  if ((rc = g->wait_host_input(*in)) != 0) return rc;
   g->queue.push_back(f);
   ++g->frames_in;
   // a full batch of frames whose D later neighbours are all there goes out; the last D frames wait for theirs
@@ -467,9 +377,8 @@ int g1s_denoise_drain(g1s_denoise_t *g, uint64_t *frames_complete) {
   if (g->err_code) return g->err_code;
   (void)hipSetDevice(g->device);
   const uint64_t limit = g->frames_in >= g->clip_first + g->D ? g->frames_in - g->D : g->clip_first;
-  const int rc = g->launch_up_to(limit);
-  if (rc) return rc;
-  if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
+  int rc = g->launch_up_to(limit);
+  if (rc || (rc = g->wait()) != 0) return rc;
   g->frames_complete = g->next_launch;
   if (frames_complete) *frames_complete = g->frames_complete;
   return G1S_OK;
@@ -492,58 +401,7 @@ int g1s_denoise_set_timing(g1s_denoise_t *g, int enable, double *ms_kernel, uint
 
 const char *g1s_denoise_last_error(const g1s_denoise_t *g) { return g ? g->err.c_str() : ""; }
 
-void g1s_denoise_free(g1s_denoise_t *g) {
-  if (!g) return;
-  (void)hipSetDevice(g->device);
-  if (g->stream) (void)hipStreamSynchronize(g->stream);
-  void *bufs[] = {g->d_jobs[0], g->d_jobs[1], g->d_tables, g->d_stage_in, g->d_stage_out};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  for (int k = 0; k < 2; ++k) {
-    if (g->h_jobs[k]) (void)hipHostFree(g->h_jobs[k]);
-    if (g->done[k]) (void)hipEventDestroy(g->done[k]);
-  }
-  for (auto &e : g->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (g->stream) (void)hipStreamDestroy(g->stream);
-  delete g;
-}
-
-}  // extern "C"
-
-namespace {
-
-// the first line of a .y4m file: goes out as it came in
-std::string y4m_header_line(const char *path) {
-  std::string header;
-  if (FILE *f = std::fopen(path, "rb")) {
-    char line[1024];
-    if (std::fgets(line, sizeof line, f)) header = line;
-    std::fclose(f);
-  }
-  return header;
-}
-
-struct PlaneLayout {
-  size_t prow[3] = {0, 0, 0}, pbytes[3] = {0, 0, 0}, ph[3] = {0, 0, 0}, fbytes = 0;
-  explicit PlaneLayout(const g1s_y4m_info_t &info) {
-    const size_t bps = info.bit_depth > 8 ? 2 : 1;
-    for (uint32_t c = 0; c < info.nplanes; ++c) {
-      const size_t pw = c ? (info.width + (1u << info.xdec) - 1) >> info.xdec : info.width;
-      ph[c] = c ? (info.height + (1u << info.ydec) - 1) >> info.ydec : info.height;
-      prow[c] = pw * bps, pbytes[c] = pw * ph[c] * bps, fbytes += pbytes[c];
-    }
-  }
-  // the planes of a frame stored without padding from `base`
-  void point(g1s_frame_t &f, uint8_t *base, const g1s_y4m_info_t &info) const {
-    size_t off = 0;
-    for (uint32_t c = 0; c < info.nplanes; ++c) f.data[c] = base + off, f.stride_bytes[c] = prow[c], off += pbytes[c];
-  }
-};
-
-}  // namespace
-
-extern "C" {
+void g1s_denoise_free(g1s_denoise_t *g) { free_op(g); }
 
 int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap) {
   return g1s_denoise_y4m_file_temporal(in, out, opts, 0, err, cap);
@@ -551,80 +409,22 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
 
 int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
                                       size_t cap) {
-  auto refuse = [&](int code, const std::string &m) -> int64_t {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (!in || !out) return refuse(G1S_ERR_INVALID, "null path");
-  const std::string header = y4m_header_line(in);
-  g1s_y4m_t *y = g1s_y4m_open(in, err, cap);
-  if (!y) return G1S_ERR_INVALID;
-  g1s_y4m_info_t info;
-  g1s_y4m_get_info(y, &info);
-  g1s_denoise_t *g = g1s_denoise_new_temporal(info.bit_depth, opts, temporal_radius);
-  if (!g) {
-    g1s_y4m_close(y);
-    return refuse(G1S_ERR_INVALID, g1s_last_global_error());
-  }
-  FILE *fo = std::fopen(out, "wb");
-  if (!fo) {
-    g1s_denoise_free(g);
-    g1s_y4m_close(y);
-    return refuse(G1S_ERR_INVALID, std::string("cannot create ") + out);
-  }
-  const PlaneLayout lay(info);
   // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
   // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
-  const uint32_t batch = g->batch, ring = batch + g->D;
-  uint8_t *obuf = nullptr;
-  int64_t frames = 0, written = 0;
-  int rc = G1S_OK;
-  std::string why;
-  bool ok = std::fwrite(header.data(), 1, header.size(), fo) == header.size();
-  if (!ok) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-  if (ok && hipHostMalloc((void **)&obuf, lay.fbytes * ring, hipHostMallocDefault) != hipSuccess)
-    ok = false, rc = G1S_ERR_HIP, why = "hipHostMalloc of the output frames failed";
-  auto drain = [&](bool end) {
-    uint64_t complete = (uint64_t)frames;
-    rc = end ? g1s_denoise_sync(g) : g1s_denoise_drain(g, &complete);
-    if (rc) {
-      why = g1s_denoise_last_error(g);
-      return false;
-    }
-    for (; written < (int64_t)complete; ++written)
-      if (std::fwrite("FRAME\n", 1, 6, fo) != 6 || std::fwrite(obuf + lay.fbytes * (size_t)(written % ring), 1, lay.fbytes, fo) != lay.fbytes) {
-        rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-        return false;
-      }
-    return true;
+  struct Driver {
+    const g1s_denoise_opts_t *opts;
+    uint32_t D;
+    g1s_denoise_t *g = nullptr;
+    const int new_failed = G1S_ERR_INVALID;
+    bool open(const g1s_y4m_info_t &i) { return (g = g1s_denoise_new_temporal(i.bit_depth, opts, D)) != nullptr; }
+    uint32_t batch() const { return g->batch; }
+    uint32_t ring() const { return g->batch + g->D; }
+    int frame(int64_t, const g1s_frame_t *fin, g1s_frame_t *fout) { return g1s_denoise_frame(g, fin, fout); }
+    int drain(bool end, uint64_t *complete) { return end ? g1s_denoise_sync(g) : g1s_denoise_drain(g, complete); }
+    const char *last_error() const { return g1s_denoise_last_error(g); }
+    void close() { g1s_denoise_free(g); }
   };
-  while (ok) {
-    g1s_frame_t fin;
-    const int got = g1s_y4m_next(y, &fin);
-    if (got < 0) {
-      ok = false, rc = got, why = g1s_y4m_last_error(y);
-      break;
-    }
-    if (got == 0) break;
-    g1s_frame_t fout = fin;
-    lay.point(fout, obuf + lay.fbytes * (size_t)(frames % ring), info);
-    fin.on_device = 0;  // (the reader lends the frame until its next call: copied before g1s_denoise_frame returns)
-    fout.on_device = 2;
-    rc = g1s_denoise_frame(g, &fin, &fout);
-    if (rc) {
-      ok = false, why = "frame " + std::to_string(frames) + ": " + g1s_denoise_last_error(g);
-      break;
-    }
-    ++frames;
-    if (frames % batch == 0) ok = drain(false);
-  }
-  if (ok) ok = drain(true);
-  if (std::fclose(fo) != 0 && ok) ok = false, rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-  g1s_denoise_free(g);
-  if (obuf) (void)hipHostFree(obuf);
-  g1s_y4m_close(y);
-  if (!ok) return refuse(rc ? rc : G1S_ERR_INVALID, why);
-  return frames;
+  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius});
 }
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
@@ -650,13 +450,14 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
   if (!y) return G1S_ERR_INVALID;
   g1s_y4m_info_t info;
   g1s_y4m_get_info(y, &info);
-  const PlaneLayout lay(info);
+  const PlaneGeom pg(info);
+  const Layout lay = packed_layout(pg);
   g1s_diff_t *g = nullptr;
   g1s_denoise_t *dn = nullptr;
   FILE *fk = nullptr;
-  uint8_t *kbuf = nullptr;
+  PinnedBuf<uint8_t> kbuf;
   struct Pair {
-    uint8_t *src = nullptr, *den = nullptr;
+    DevBuf<uint8_t> src, den;
   };
   std::vector<Pair> pairs;                          // every pair of buffers allocated so far
   std::deque<std::pair<uint64_t, size_t>> lent;     // (frame index, pair) handed to the generator, oldest first
@@ -690,7 +491,7 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
   if (keep_denoised) {
     fk = std::fopen(keep_denoised, "wb");
     if (!fk || std::fwrite(header.data(), 1, header.size(), fk) != header.size() ||
-        hipHostMalloc((void **)&kbuf, lay.fbytes, hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc((void **)&kbuf.p, lay.frame, hipHostMallocDefault) != hipSuccess) {
       rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
       goto done;
     }
@@ -733,26 +534,22 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
         k = spare.back(), spare.pop_back();
       } else {
         Pair p;
-        if (hipMalloc((void **)&p.src, lay.fbytes) != hipSuccess || hipMalloc((void **)&p.den, lay.fbytes) != hipSuccess) {
-          if (p.src) (void)hipFree(p.src);
+        if (hipMalloc((void **)&p.src.p, lay.frame) != hipSuccess || hipMalloc((void **)&p.den.p, lay.frame) != hipSuccess) {
           rc = G1S_ERR_HIP, why = "hipMalloc of a frame pair failed";
           break;
         }
-        pairs.push_back(p), k = pairs.size() - 1;
+        pairs.push_back(std::move(p)), k = pairs.size() - 1;
       }
       // the reader lends the frame until its next call: on the device before that
-      size_t off = 0;
       bool copied = true;
-      for (uint32_t c = 0; c < info.nplanes; ++c) {
-        copied = copied && hipMemcpy2D(pairs[k].src + off, lay.prow[c], fin.data[c], fin.stride_bytes[c], lay.prow[c], lay.ph[c], hipMemcpyHostToDevice) == hipSuccess;
-        off += lay.pbytes[c];
-      }
+      for (int c = 0; c < pg.nplanes; ++c)
+        copied = copied && hipMemcpy2D(pairs[k].src + lay.off[c], lay.row[c], fin.data[c], fin.stride_bytes[c], lay.row[c], pg.ph(c), hipMemcpyHostToDevice) == hipSuccess;
       if (!copied) {
         rc = G1S_ERR_HIP, why = "copy of a source frame to the device failed";
         break;
       }
       g1s_frame_t s = fin, d = fin;
-      lay.point(s, pairs[k].src, info), lay.point(d, pairs[k].den, info);
+      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
       s.on_device = d.on_device = 1;
       rc = g1s_denoise_frame(dn, &s, &d);
       if (rc) {
@@ -777,15 +574,15 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
       s.width = info.width, s.height = info.height, s.bytes_per_sample = info.bit_depth > 8 ? 2 : 1, s.xdec = (uint8_t)info.xdec, s.ydec = (uint8_t)info.ydec,
       s.nplanes = (uint8_t)info.nplanes, s.on_device = 1;
       d = s;
-      lay.point(s, pairs[k].src, info), lay.point(d, pairs[k].den, info);
+      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
       rc = g1s_diff_frame(g, &s, &d);
       if (rc) {
         why = "frame " + std::to_string(frames) + ": diff_frame: " + g1s_diff_last_error(g);
         break;
       }
       lent.emplace_back(frames, k);
-      if (fk && (hipMemcpy(kbuf, pairs[k].den, lay.fbytes, hipMemcpyDeviceToHost) != hipSuccess || std::fwrite("FRAME\n", 1, 6, fk) != 6 ||
-                 std::fwrite(kbuf, 1, lay.fbytes, fk) != lay.fbytes)) {
+      if (fk && (hipMemcpy(kbuf, pairs[k].den, lay.frame, hipMemcpyDeviceToHost) != hipSuccess || std::fwrite("FRAME\n", 1, 6, fk) != 6 ||
+                 std::fwrite(kbuf, 1, lay.frame, fk) != lay.frame)) {
         rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
         break;
       }
@@ -809,9 +606,7 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
 done:
   if (fk && std::fclose(fk) != 0 && !rc) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
   if (dn) g1s_denoise_free(dn);
-  if (g) g1s_diff_free(g);  // (waits for the kernels that read the pairs)
-  for (Pair &p : pairs) (void)hipFree(p.src), (void)hipFree(p.den);
-  if (kbuf) (void)hipHostFree(kbuf);
+  if (g) g1s_diff_free(g);  // (waits for the kernels that read the pairs, which go when this call returns)
   g1s_y4m_close(y);
   if (frames_out) *frames_out = frames;
   if (rc) return refuse(rc, why);

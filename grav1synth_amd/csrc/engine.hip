@@ -27,6 +27,7 @@
 
 #include "../../include/g1s_diff.h"
 #include "fold.h"
+#include "frame_op.h"
 #include "kernels.hip.h"
 #include "k1f.hip.h"
 #include "k3m.hip.h"
@@ -37,6 +38,9 @@
 #include "record.h"
 
 using namespace g1s;
+using g1s_op::DevBuf;
+using g1s_op::Event;
+using g1s_op::PinnedBuf;
 
 namespace {
 
@@ -266,20 +270,6 @@ std::mutex g_merge_pool_mutex;
 constexpr int kDeviceLatestMinBlocks = 4096;
 constexpr uint32_t kLatestWindowMinBatch = 64;  // frames a launch from which k4_latest gets a window of its own (g1s_diff::submit)
 constexpr int kSlots = 6;  // batches in flight: being filled, finder chain, accumulation, (the per-frame half on the device,) D2H, fold
-
-// What a slot owns: a HIP allocation or event, released when its holder goes.  Move-only; reads as the raw pointer it holds.
-template <class T, auto FREE>
-struct Owned {
-  T *p = nullptr;
-  Owned() = default;
-  Owned(Owned &&o) noexcept : p(o.p) { o.p = nullptr; }
-  Owned &operator=(Owned &&o) noexcept { return std::swap(p, o.p), *this; }  // (what this one held goes with `o`)
-  ~Owned() { if (p) (void)FREE(p); }
-  operator T *() const { return p; }
-};
-template <class T> using DevBuf = Owned<T, hipFree>;
-template <class T> using PinnedBuf = Owned<T, hipHostFree>;
-using Event = Owned<std::remove_pointer<hipEvent_t>::type, hipEventDestroy>;
 
 // A slot's memory: the bytes of every per-slot allocation and, for the buffers that hold several things, where each region
 // lies (byte offsets).  set_geometry_alloc works it out once and says there what each region is; whatever

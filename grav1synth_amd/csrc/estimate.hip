@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "frame_op.h"
 
 namespace {
 
@@ -359,23 +360,26 @@ constexpr double kSqrtPiBy2 = 1.2533141373155003;  // SQRT_PI_BY_2
 
 }  // namespace
 
+using namespace g1s_op;
+
 struct g1s_estimate {
+  Stream stream;  // (first: it goes last, after what was used on it)
   int device = 0;
   uint32_t bit_depth = 8;
   uint32_t W = 0, H = 0, bps = 0;
   uint32_t batch = 32;
-  hipStream_t stream = nullptr;
   std::vector<EstFrame> h_frames;  // the batch being filled
-  EstFrame *d_frames = nullptr;
-  unsigned long long *d_sums = nullptr, *h_sums = nullptr;
-  uint8_t *d_stage = nullptr;      // device copies of host frames
-  size_t stage_frame = 0;
+  DevBuf<EstFrame> d_frames;
+  DevBuf<unsigned long long> d_sums;
+  PinnedBuf<unsigned long long> h_sums;
+  DevBuf<uint8_t> d_stage;         // device copies of host frames: rows as in the staging layout, no gap between frames
+  size_t stage_row = 0;
   std::vector<double> estimates;   // one per frame: sigma, or -1 (None)
   std::string err;
   uint64_t frames_kernel = 0;
   double ms_kernel = 0;
   bool timing = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Event ev0, ev1;
 
   int fail(int code, const std::string &m) {
     err = m;
@@ -384,17 +388,11 @@ struct g1s_estimate {
   int flush();
 };
 
-#define EST_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) return fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
-
 int g1s_estimate::flush() {
   const uint32_t B = (uint32_t)h_frames.size();
   if (!B) return G1S_OK;
-  EST_TRY(hipMemcpyAsync(d_frames, h_frames.data(), sizeof(EstFrame) * B, hipMemcpyHostToDevice, stream));
-  EST_TRY(hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * B, stream));
+  G1S_OP_TRY(hipMemcpyAsync(d_frames, h_frames.data(), sizeof(EstFrame) * B, hipMemcpyHostToDevice, stream));
+  G1S_OP_TRY(hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * B, stream));
   EstParams ep;
   ep.frames = d_frames;
   ep.sums = d_sums;
@@ -428,19 +426,19 @@ int g1s_estimate::flush() {
   ep.row_strips = ((int)H - 2 + strip_rows - 1) / strip_rows;
   if (launch) {
     const dim3 grid((ep.col_strips * ep.row_strips + kWavesPerWg - 1) / kWavesPerWg, B);
-    if (timing) EST_TRY(hipEventRecord(ev0, stream));
+    if (timing) G1S_OP_TRY(hipEventRecord(ev0, stream));
     if (packed && bps == 2) hipLaunchKernelGGL(k_estimate_pk<2>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
     else if (packed) hipLaunchKernelGGL(k_estimate_pk<1>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
     else if (bps == 2) hipLaunchKernelGGL(k_estimate<2>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
     else hipLaunchKernelGGL(k_estimate<1>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
-    if (timing) EST_TRY(hipEventRecord(ev1, stream));
+    if (timing) G1S_OP_TRY(hipEventRecord(ev1, stream));
   }
-  EST_TRY(hipMemcpyAsync(h_sums, d_sums, sizeof(unsigned long long) * 2 * B, hipMemcpyDeviceToHost, stream));
-  EST_TRY(hipStreamSynchronize(stream));
-  EST_TRY(hipGetLastError());
+  G1S_OP_TRY(hipMemcpyAsync(h_sums, d_sums, sizeof(unsigned long long) * 2 * B, hipMemcpyDeviceToHost, stream));
+  G1S_OP_TRY(hipStreamSynchronize(stream));
+  G1S_OP_TRY(hipGetLastError());
   if (timing && launch) {
     float ms = 0;
-    EST_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    G1S_OP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
     ms_kernel += ms;
     frames_kernel += B;
   }
@@ -457,19 +455,16 @@ extern "C" {
 
 g1s_estimate_t *g1s_estimate_new(uint32_t bit_depth, int32_t device, uint32_t batch_frames) {
   if (bit_depth < 8 || bit_depth > 16) return nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return nullptr;  // no CPU fallback
+  if (!pick_device(device, "estimate", &device).empty()) return nullptr;  // (no global error: the caller sees only the null)
   g1s_estimate *e = new g1s_estimate;
-  if (device < 0) (void)hipGetDevice(&device);
   e->device = device;
   e->bit_depth = bit_depth;
   e->bps = bit_depth > 8 ? 2 : 1;
   e->batch = batch_frames ? std::min(batch_frames, 256u) : 32u;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void **)&e->d_frames, sizeof(EstFrame) * e->batch) != hipSuccess ||
-      hipMalloc((void **)&e->d_sums, sizeof(unsigned long long) * 2 * e->batch) != hipSuccess ||
-      hipHostMalloc((void **)&e->h_sums, sizeof(unsigned long long) * 2 * e->batch, hipHostMallocDefault) != hipSuccess ||
-      hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess) {
+  if (!open_stream(device, e->stream) || hipMalloc((void **)&e->d_frames.p, sizeof(EstFrame) * e->batch) != hipSuccess ||
+      hipMalloc((void **)&e->d_sums.p, sizeof(unsigned long long) * 2 * e->batch) != hipSuccess ||
+      hipHostMalloc((void **)&e->h_sums.p, sizeof(unsigned long long) * 2 * e->batch, hipHostMallocDefault) != hipSuccess ||
+      hipEventCreate(&e->ev0.p) != hipSuccess || hipEventCreate(&e->ev1.p) != hipSuccess) {
     g1s_estimate_free(e);
     return nullptr;
   }
@@ -485,7 +480,7 @@ int g1s_estimate_frame(g1s_estimate_t *e, const g1s_frame_t *f) {
   if (!e->W) {
     e->W = f->width;
     e->H = f->height;
-    e->stage_frame = (((size_t)e->W * e->bps + 15) & ~size_t(15)) * e->H;
+    e->stage_row = align_up((size_t)e->W * e->bps, kStageRowAlign);
   } else if (e->W != f->width || e->H != f->height) {
     return e->fail(G1S_ERR_DIM_MISMATCH, "frame geometry changed mid-stream");
   }
@@ -494,10 +489,10 @@ int g1s_estimate_frame(g1s_estimate_t *e, const g1s_frame_t *f) {
     ef.y = static_cast<const uint8_t *>(f->data[0]);
     ef.stride = (uint32_t)f->stride_bytes[0];
   } else {  // host planes: copied before the call returns (the `&frame.y_plane` borrow)
-    if (!e->d_stage && hipMalloc((void **)&e->d_stage, e->stage_frame * e->batch) != hipSuccess)
+    const size_t row = e->stage_row, stage_frame = row * e->H;
+    if (!e->d_stage && hipMalloc((void **)&e->d_stage.p, stage_frame * e->batch) != hipSuccess)
       return e->fail(G1S_ERR_HIP, "hipMalloc of the staging buffer failed");
-    const size_t row = ((size_t)e->W * e->bps + 15) & ~size_t(15);
-    uint8_t *dst = e->d_stage + e->stage_frame * e->h_frames.size();
+    uint8_t *dst = e->d_stage + stage_frame * e->h_frames.size();
     if (hipMemcpy2D(dst, row, f->data[0], f->stride_bytes[0], (size_t)e->W * e->bps, e->H, hipMemcpyHostToDevice) != hipSuccess)
       return e->fail(G1S_ERR_HIP, "hipMemcpy2D of a host frame failed");
     ef.y = dst;
@@ -528,19 +523,7 @@ int g1s_estimate_set_timing(g1s_estimate_t *e, int enable, double *ms_kernel, ui
 
 const char *g1s_estimate_last_error(const g1s_estimate_t *e) { return e ? e->err.c_str() : ""; }
 
-void g1s_estimate_free(g1s_estimate_t *e) {
-  if (!e) return;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->d_frames) (void)hipFree(e->d_frames);
-  if (e->d_sums) (void)hipFree(e->d_sums);
-  if (e->h_sums) (void)hipHostFree(e->h_sums);
-  if (e->d_stage) (void)hipFree(e->d_stage);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
-}
+void g1s_estimate_free(g1s_estimate_t *e) { free_op(e); }
 
 long g1s_format_estimates(const double *estimates, size_t n, char *buf, size_t cap) {
   // writeln!("filmgrn1"), then writeln!("{:.3}", estimate.unwrap_or(-1f64)) per frame (src/main.rs:597-600)

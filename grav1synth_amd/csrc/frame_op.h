@@ -1,0 +1,345 @@
+// frame_op.h -- the host scaffold the frame operations share (render: grain.hip, denoise: denoise.hip, estimate:
+// estimate.hip; the generator takes the owners).  Host code only.  The first part -- plane geometry, the two layouts of a
+// frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP and builds with a host compiler
+// alone; the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro and the
+// base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
+#pragma once
+#include <stdint.h>
+
+#include <cstdio>
+#include <string>
+#include <type_traits>
+#include <utility>
+
+#include "../../include/g1s_diff.h"
+
+namespace g1s_op {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the planes of a frame: luma W x H, chroma decimated by (subx, suby) <= 1, `bps` bytes a sample
+struct PlaneGeom {
+  int W = 0, H = 0, subx = 0, suby = 0, nplanes = 0;
+  uint32_t bps = 1;
+  PlaneGeom() = default;
+  PlaneGeom(const g1s_frame_t &f, uint32_t bps_) : W((int)f.width), H((int)f.height), subx(f.xdec), suby(f.ydec), nplanes(f.nplanes), bps(bps_) {}
+  explicit PlaneGeom(const g1s_y4m_info_t &i)
+      : W((int)i.width), H((int)i.height), subx((int)i.xdec), suby((int)i.ydec), nplanes((int)i.nplanes), bps(i.bit_depth > 8 ? 2 : 1) {}
+  size_t pw(int c) const { return c ? (size_t)((W + subx) >> subx) : (size_t)W; }
+  size_t ph(int c) const { return c ? (size_t)((H + suby) >> suby) : (size_t)H; }
+  size_t row_bytes(int c) const { return pw(c) * bps; }
+  bool same_shape(const g1s_frame_t &f) const {
+    return W == (int)f.width && H == (int)f.height && nplanes == f.nplanes && subx == f.xdec && suby == f.ydec;
+  }
+};
+
+// a frame's planes one after the other in one buffer: rows of plane c are row[c] bytes apart, the plane starts at off[c]
+struct Layout {
+  size_t row[3] = {0, 0, 0}, off[3] = {0, 0, 0}, frame = 0;
+  Layout() = default;
+  Layout(const PlaneGeom &g, size_t row_align, size_t plane_align) {
+    for (int c = 0; c < g.nplanes; ++c) {
+      row[c] = align_up(g.row_bytes(c), row_align);
+      off[c] = frame;
+      frame += align_up(row[c] * g.ph(c), plane_align);
+    }
+  }
+  // the planes of a frame stored from `base`
+  void point(g1s_frame_t &f, uint8_t *base, int nplanes) const {
+    for (int c = 0; c < nplanes; ++c) f.data[c] = base + off[c], f.stride_bytes[c] = row[c];
+  }
+};
+constexpr size_t kStageRowAlign = 16, kStagePlaneAlign = 256;
+// a host frame's copy on the device: rows to 16 bytes, planes to 256
+inline Layout staging_layout(const PlaneGeom &g) { return Layout(g, kStageRowAlign, kStagePlaneAlign); }
+// a frame of a .y4m file: no padding anywhere
+inline Layout packed_layout(const PlaneGeom &g) { return Layout(g, 1, 1); }
+
+struct Refusal {
+  int code = G1S_OK;
+  std::string text;
+};
+
+// The checks of a frame pair handed to an operation made by `new_name` for `bps` bytes a sample: sample size, a geometry
+// the operation takes (`geometry_text` says which), two frames of one shape, and per plane a pointer and a row stride
+// that holds a row, fits 32 bits and, for 16-bit samples, is even.  code G1S_OK: fine.
+inline Refusal check_frame_pair(const g1s_frame_t &in, const g1s_frame_t &out, uint32_t bps, uint32_t max_width, const char *new_name,
+                                const char *geometry_text) {
+  if (in.bytes_per_sample != bps || out.bytes_per_sample != bps)
+    return {G1S_ERR_INVALID, std::string("bytes_per_sample does not match the bit depth given to ") + new_name};
+  if (in.width < 1 || in.height < 1 || in.width > max_width || in.height > 65536u || (in.nplanes != 1 && in.nplanes != 3) || in.xdec > 1 ||
+      in.ydec > in.xdec)
+    return {G1S_ERR_INVALID, geometry_text};
+  if (out.width != in.width || out.height != in.height || out.nplanes != in.nplanes || out.xdec != in.xdec || out.ydec != in.ydec)
+    return {G1S_ERR_DIM_MISMATCH, "input and output frame geometry differ"};
+  const PlaneGeom g(in, bps);
+  for (int c = 0; c < g.nplanes; ++c)
+    if (!in.data[c] || !out.data[c] || in.stride_bytes[c] < g.row_bytes(c) || out.stride_bytes[c] < g.row_bytes(c) ||
+        in.stride_bytes[c] > 0xffffffffu || out.stride_bytes[c] > 0xffffffffu || (bps == 2 && ((in.stride_bytes[c] | out.stride_bytes[c]) & 1)))
+      return {G1S_ERR_INVALID, "bad plane pointer or row stride"};
+  return {};
+}
+
+// do the bytes of plane ca at `a` and of plane cb at `b` (frames of geometry g) share an address?
+inline bool planes_overlap(const PlaneGeom &g, const uint8_t *a, size_t a_stride, int ca, const uint8_t *b, size_t b_stride, int cb) {
+  const uint8_t *ae = a + a_stride * (g.ph(ca) - 1) + g.row_bytes(ca), *be = b + b_stride * (g.ph(cb) - 1) + g.row_bytes(cb);
+  return a < be && b < ae;
+}
+
+// the first line of a .y4m file: goes out as it came in ("" when the file cannot be read: the reader says why)
+inline std::string y4m_header_line(const char *path) {
+  std::string header;
+  if (FILE *f = std::fopen(path, "rb")) {
+    char line[1024];
+    if (std::fgets(line, sizeof line, f)) header = line;
+    std::fclose(f);
+  }
+  return header;
+}
+
+}  // namespace g1s_op
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+namespace g1s_op {
+
+// What a slot or an operation owns: a HIP allocation, event or stream, released when its holder goes.  Move-only; reads as
+// the raw pointer it holds.
+template <class T, auto FREE>
+struct Owned {
+  T *p = nullptr;
+  Owned() = default;
+  Owned(Owned &&o) noexcept : p(o.p) { o.p = nullptr; }
+  Owned &operator=(Owned &&o) noexcept { return std::swap(p, o.p), *this; }  // (what this one held goes with `o`)
+  ~Owned() { if (p) (void)FREE(p); }
+  operator T *() const { return p; }
+};
+template <class T> using DevBuf = Owned<T, hipFree>;
+template <class T> using PinnedBuf = Owned<T, hipHostFree>;
+using Event = Owned<std::remove_pointer<hipEvent_t>::type, hipEventDestroy>;
+using Stream = Owned<std::remove_pointer<hipStream_t>::type, hipStreamDestroy>;
+
+// inside a member of something with fail(code, text): a HIP call that must succeed
+#define G1S_OP_TRY(expr)                                                                                     \
+  do {                                                                                                       \
+    hipError_t e_ = (expr);                                                                                  \
+    if (e_ != hipSuccess) return fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
+  } while (0)
+
+// the device an operation runs on: `want`, or the current one when `want` is negative.  "" when there is one, else why not
+inline std::string pick_device(int want, const char *operation, int *device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return std::string("no HIP device available: ") + operation + " has no CPU fallback";
+  if (want < 0 && hipGetDevice(&want) != hipSuccess) return "hipGetDevice failed";
+  *device = want;
+  return "";
+}
+
+// the operation's own stream on `device`, which becomes the thread's current device
+inline bool open_stream(int device, Stream &s) { return hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&s.p, hipStreamNonBlocking) == hipSuccess; }
+
+// one array of a batch's parameters, two sets in turn: pinned on the host, uploaded on the stream
+template <class T>
+struct ParamSets {
+  PinnedBuf<T> h[2];
+  DevBuf<T> d[2];
+  bool alloc(size_t n) {
+    bool ok = true;
+    for (int k = 0; k < 2; ++k)
+      ok = ok && hipMalloc((void **)&d[k].p, sizeof(T) * n) == hipSuccess && hipHostMalloc((void **)&h[k].p, sizeof(T) * n, hipHostMallocDefault) == hipSuccess;
+    return ok;
+  }
+  hipError_t upload(int set, size_t n, hipStream_t s) { return hipMemcpyAsync(d[set], h[set], sizeof(T) * n, hipMemcpyHostToDevice, s); }
+};
+
+// where the output of a frame with host planes goes once its kernels are through
+struct HostPlanes {
+  void *data[3];
+  size_t stride[3];
+};
+inline HostPlanes host_planes(const g1s_frame_t &f) {
+  HostPlanes h{};
+  for (int c = 0; c < 3; ++c) h.data[c] = const_cast<void *>(f.data[c]), h.stride[c] = f.stride_bytes[c];
+  return h;
+}
+
+// The base of an operation that takes frames one at a time and launches them a batch at a time on a stream of its own.
+// (The stream comes first: it goes last, after the wait in *_free and after everything that was used on it.)
+struct BatchedOp {
+  Stream stream;
+  int device = 0;
+  uint32_t bit_depth = 8, bps = 1, batch = 32;
+  int err_code = 0;
+  std::string err;
+  bool timing = false;
+  // the parameters of a batch, two sets in turn (ParamSets): a set is free again when the event behind the kernels of the
+  // batch that read it has passed -- the next batch is filled while this one runs
+  Event done[2];
+  uint64_t batches = 0;
+  // the geometry of the frames so far and the device copies of host frames: an input ring and an output buffer, made when
+  // the first such frame comes, each a number of slots of the staging layout
+  bool have_geom = false;
+  PlaneGeom geom;
+  Layout stage;
+  DevBuf<uint8_t> d_stage_in, d_stage_out;
+
+  int fail(int code, const std::string &m) {
+    if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
+    return err_code;
+  }
+  bool open(int device_, uint32_t bit_depth_, uint32_t batch_frames) {
+    device = device_, bit_depth = bit_depth_, bps = bit_depth_ > 8 ? 2 : 1, batch = batch_frames ? (batch_frames < 256u ? batch_frames : 256u) : 32u;
+    bool ok = open_stream(device, stream);
+    for (Event &e : done) ok = ok && hipEventCreateWithFlags(&e.p, hipEventDisableTiming) == hipSuccess;
+    return ok;
+  }
+  // the set to fill next; waits for the launch two batches back, which read it
+  int next_set(int *set) {
+    *set = (int)(batches & 1);
+    if (batches >= 2) G1S_OP_TRY(hipEventSynchronize(done[*set]));
+    ++batches;
+    return G1S_OK;
+  }
+  int set_done(int set) {
+    G1S_OP_TRY(hipEventRecord(done[set], stream));
+    return G1S_OK;
+  }
+  // (a new geometry: nothing may be in flight; the staging buffers are sized again when they are next needed)
+  void set_frame_geometry(const g1s_frame_t &f) {
+    geom = PlaneGeom(f, bps), stage = staging_layout(geom), have_geom = true;
+    d_stage_in = DevBuf<uint8_t>(), d_stage_out = DevBuf<uint8_t>();
+  }
+  // Where the kernels read `in`: the caller's device planes, or slot `slot` of the input ring of `slots` slots, the copies
+  // queued on the stream.  Host planes are read before the call returns (wait_host_input); pinned planes are queued.
+  int stage_in(const g1s_frame_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3]) {
+    for (int c = 0; c < geom.nplanes; ++c) {
+      if (in.on_device == 1) {
+        plane[c] = static_cast<const uint8_t *>(in.data[c]), stride[c] = (uint32_t)in.stride_bytes[c];
+        continue;
+      }
+      if (!d_stage_in && hipMalloc((void **)&d_stage_in.p, stage.frame * slots) != hipSuccess)
+        return fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
+      uint8_t *dst = d_stage_in + stage.frame * slot + stage.off[c];
+      if (hipMemcpy2DAsync(dst, stage.row[c], in.data[c], in.stride_bytes[c], geom.row_bytes(c), geom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
+      plane[c] = dst, stride[c] = (uint32_t)stage.row[c];
+    }
+    return G1S_OK;
+  }
+  int wait_host_input(const g1s_frame_t &in) {
+    if (in.on_device == 0 && hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
+    return G1S_OK;
+  }
+  int need_stage_out(uint32_t slots) {
+    if (!d_stage_out && hipMalloc((void **)&d_stage_out.p, stage.frame * slots) != hipSuccess)
+      return fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
+    return G1S_OK;
+  }
+  uint8_t *stage_out(uint32_t slot, int c) const { return d_stage_out + stage.frame * slot + stage.off[c]; }
+  // slot `slot` of the output buffer back to the host planes, behind what the stream holds
+  int copy_back(uint32_t slot, const HostPlanes &h) {
+    for (int c = 0; c < geom.nplanes; ++c)
+      G1S_OP_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], stage_out(slot, c), stage.row[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToHost, stream));
+    return G1S_OK;
+  }
+  int wait() {
+    if (hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
+    return G1S_OK;
+  }
+};
+
+// *_free of anything with a device and a stream that owns the rest through the owners above
+template <class Op>
+void free_op(Op *g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->stream) (void)hipStreamSynchronize(g->stream);
+  delete g;
+}
+
+// A .y4m file through an operation into another .y4m file: the header line as it came, every frame handed over as a host
+// frame with a slot of a pinned ring of packed frames as its output, and after every `batch` frames and at the end the
+// completed frames written out.  `Driver` says what differs:
+//   bool open(const g1s_y4m_info_t &)   makes the operation (false: refused with new_failed and the global error text)
+//   uint32_t batch(), ring()            frames between two drains; frames that can be unwritten at once
+//   int frame(int64_t n, const g1s_frame_t *in, g1s_frame_t *out)
+//   int drain(bool end, uint64_t *complete)   waits; *complete (preset to the frames handed over) = frames that can be written
+//   const char *last_error(); void close()
+// Returns the number of frames, or the code of what went wrong with its text in err.
+template <class Driver>
+int64_t rewrite_y4m(const char *in, const char *out, char *err, size_t cap, Driver &&op) {
+  auto refuse = [&](int code, const std::string &m) -> int64_t {
+    if (err && cap) snprintf(err, cap, "%s", m.c_str());
+    return code;
+  };
+  if (!in || !out) return refuse(G1S_ERR_INVALID, "null path");
+  const std::string header = y4m_header_line(in);
+  g1s_y4m_t *y = g1s_y4m_open(in, err, cap);
+  if (!y) return G1S_ERR_INVALID;
+  g1s_y4m_info_t info;
+  g1s_y4m_get_info(y, &info);
+  if (!op.open(info)) {
+    g1s_y4m_close(y);
+    return refuse(op.new_failed, g1s_last_global_error());
+  }
+  FILE *fo = std::fopen(out, "wb");
+  if (!fo) {
+    op.close();
+    g1s_y4m_close(y);
+    return refuse(G1S_ERR_INVALID, std::string("cannot create ") + out);
+  }
+  const Layout lay = packed_layout(PlaneGeom(info));
+  const uint32_t batch = op.batch(), ring = op.ring();
+  PinnedBuf<uint8_t> obuf;
+  int64_t frames = 0, written = 0;
+  int rc = G1S_OK;
+  std::string why;
+  bool ok = std::fwrite(header.data(), 1, header.size(), fo) == header.size();
+  if (!ok) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
+  if (ok && hipHostMalloc((void **)&obuf.p, lay.frame * ring, hipHostMallocDefault) != hipSuccess)
+    ok = false, rc = G1S_ERR_HIP, why = "hipHostMalloc of the output frames failed";
+  auto drain = [&](bool end) {
+    uint64_t complete = (uint64_t)frames;
+    rc = op.drain(end, &complete);
+    if (rc) {
+      why = op.last_error();
+      return false;
+    }
+    for (; written < (int64_t)complete; ++written)
+      if (std::fwrite("FRAME\n", 1, 6, fo) != 6 || std::fwrite(obuf + lay.frame * (size_t)(written % ring), 1, lay.frame, fo) != lay.frame) {
+        rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
+        return false;
+      }
+    return true;
+  };
+  while (ok) {
+    g1s_frame_t fin;
+    const int got = g1s_y4m_next(y, &fin);
+    if (got < 0) {
+      ok = false, rc = got, why = g1s_y4m_last_error(y);
+      break;
+    }
+    if (got == 0) break;
+    g1s_frame_t fout = fin;
+    lay.point(fout, obuf + lay.frame * (size_t)(frames % ring), (int)info.nplanes);
+    fin.on_device = 0;  // (the reader lends the frame until its next call: copied before the operation's call returns)
+    fout.on_device = 2;
+    rc = op.frame(frames, &fin, &fout);
+    if (rc) {
+      ok = false, why = "frame " + std::to_string(frames) + ": " + op.last_error();
+      break;
+    }
+    ++frames;
+    if (frames % batch == 0) ok = drain(false);
+  }
+  if (ok) ok = drain(true);
+  if (std::fclose(fo) != 0 && ok) ok = false, rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
+  op.close();
+  g1s_y4m_close(y);
+  if (!ok) return refuse(rc ? rc : G1S_ERR_INVALID, why);
+  return frames;
+}
+
+}  // namespace g1s_op
+#endif  // __HIPCC__

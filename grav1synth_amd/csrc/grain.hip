@@ -24,6 +24,7 @@
 #include "../../include/g1s_diff.h"
 #include "av1_gaussian_sequence.h"
 #include "fold.h"
+#include "frame_op.h"
 
 extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
 
@@ -437,60 +438,38 @@ size_t apply_lds_bytes(const GrainGeom &g) {
   return (size_t)((kLumaW * kLumaH + 2 * ctpl + 7) & ~7) * 2 + 768 * 2 + 2 * kMaxBlocksX;
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
+using namespace g1s_op;
+
 // =============================================================== host engine =====
-struct g1s_grain {
-  int device = 0;
-  uint32_t bit_depth = 8, bps = 1, batch = 32;
+// (the stream, the sticky error, the parameter sets' turn and the staging of host frames: BatchedOp, frame_op.h)
+struct g1s_grain : BatchedOp {
   bool clip_restricted = false, mc_identity = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  bool have_geom = false;
-  GrainGeom geom{};
-  size_t plane_row[3] = {0, 0, 0}, plane_off[3] = {0, 0, 0}, stage_frame = 0;  // staging layout of a host frame on the device
+  Event ev[3];
+  GrainGeom geom_k{};  // what the kernels take: BatchedOp::geom and the block counts, the template sizes
   // the batch being filled
   std::vector<GrainJob> jobs;
   std::vector<GrainSeg> segs;
   struct HostOut {
     uint32_t slot;
-    void *data[3];
-    size_t stride[3];
+    HostPlanes planes;
   };
   std::vector<HostOut> host_outs;  // frames whose out planes are host memory: copied back behind the kernels
   // device buffers
-  // the parameters of a batch, two sets in turn: pinned on the host, uploaded on the stream, free again when the event
-  // behind the batch's kernels has passed -- the next batch is filled while this one runs
-  GrainJob *d_jobs[2] = {nullptr, nullptr}, *h_jobs[2] = {nullptr, nullptr};
-  GrainSeg *d_segs[2] = {nullptr, nullptr}, *h_segs[2] = {nullptr, nullptr};
-  hipEvent_t done[2] = {nullptr, nullptr};
-  uint64_t batches = 0;
-  uint16_t *d_jump = nullptr;
-  int16_t *d_tpl = nullptr;
-  uint8_t *d_offs = nullptr, *d_luts = nullptr, *d_stage_in = nullptr, *d_stage_out = nullptr;
+  ParamSets<GrainJob> p_jobs;
+  ParamSets<GrainSeg> p_segs;
+  DevBuf<uint16_t> d_jump;
+  DevBuf<int16_t> d_tpl;
+  DevBuf<uint8_t> d_offs, d_luts;
   size_t offs_cap = 0;
-  int err_code = 0;
-  std::string err;
-  bool timing = false;
   double ms_template = 0, ms_apply = 0;
   uint64_t frames_timed = 0;
 
-  int fail(int code, const std::string &m) {
-    if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
-    return err_code;
-  }
   int set_geometry(const g1s_frame_t &f);
   int flush();
   int launch_templates(int set, uint32_t nframes, uint32_t nsegs, const GrainGeom &g);
 };
-
-#define GRAIN_TRY(expr)                                                                                      \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -540,76 +519,60 @@ int g1s_grain::set_geometry(const g1s_frame_t &f) {
   GrainGeom g = template_geom(bit_depth, f.xdec, f.ydec, f.nplanes);
   g.W = (int)f.width, g.H = (int)f.height;
   g.nbx = (((g.W + 1) >> 1) + 15) / 16, g.nstripes = (((g.H + 1) >> 1) + 15) / 16;
-  geom = g;
-  size_t off = 0;
-  for (int c = 0; c < g.nplanes; ++c) {
-    const size_t pw = c ? (size_t)((g.W + g.subx) >> g.subx) : (size_t)g.W, ph = c ? (size_t)((g.H + g.suby) >> g.suby) : (size_t)g.H;
-    plane_row[c] = align_up(pw * bps, 16);
-    plane_off[c] = off;
-    off += align_up(plane_row[c] * ph, 256);
-  }
-  stage_frame = off;
+  geom_k = g;
+  set_frame_geometry(f);
   const size_t need = (size_t)g.nstripes * g.nbx * batch;
   if (need > offs_cap) {
-    if (d_offs) (void)hipFree(d_offs), d_offs = nullptr;
-    GRAIN_TRY(hipMalloc((void **)&d_offs, need));
+    d_offs = DevBuf<uint8_t>();
+    G1S_OP_TRY(hipMalloc((void **)&d_offs.p, need));
     offs_cap = need;
   }
-  have_geom = true;
   return G1S_OK;
 }
 
 int g1s_grain::launch_templates(int set, uint32_t nframes, uint32_t nsegs, const GrainGeom &g) {
   TemplateParams tp{};
-  tp.jobs = d_jobs[set], tp.segs = d_segs[set], tp.jump = d_jump, tp.tpl = d_tpl, tp.offs = d_offs, tp.luts = d_luts;
+  tp.jobs = p_jobs.d[set], tp.segs = p_segs.d[set], tp.jump = d_jump, tp.tpl = d_tpl, tp.offs = d_offs, tp.luts = d_luts;
   tp.nframes = (int)nframes, tp.nsegs = (int)nsegs, tp.g = g;
   hipLaunchKernelGGL(kg_template, dim3(nframes + nsegs), dim3(kThreads), 0, stream, tp);
-  GRAIN_TRY(hipGetLastError());
+  G1S_OP_TRY(hipGetLastError());
   return G1S_OK;
 }
 
 int g1s_grain::flush() {
   const uint32_t B = (uint32_t)jobs.size();
   if (!B) return G1S_OK;
-  const int set = (int)(batches & 1);
-  if (batches >= 2) GRAIN_TRY(hipEventSynchronize(done[set]));
-  ++batches;
-  std::memcpy(h_jobs[set], jobs.data(), sizeof(GrainJob) * B);
-  GRAIN_TRY(hipMemcpyAsync(d_jobs[set], h_jobs[set], sizeof(GrainJob) * B, hipMemcpyHostToDevice, stream));
+  int set, rc = next_set(&set);
+  if (rc) return rc;
+  std::memcpy(p_jobs.h[set], jobs.data(), sizeof(GrainJob) * B);
+  G1S_OP_TRY(p_jobs.upload(set, B, stream));
   if (!segs.empty()) {
-    std::memcpy(h_segs[set], segs.data(), sizeof(GrainSeg) * segs.size());
-    GRAIN_TRY(hipMemcpyAsync(d_segs[set], h_segs[set], sizeof(GrainSeg) * segs.size(), hipMemcpyHostToDevice, stream));
+    std::memcpy(p_segs.h[set], segs.data(), sizeof(GrainSeg) * segs.size());
+    G1S_OP_TRY(p_segs.upload(set, segs.size(), stream));
   }
-  if (timing) GRAIN_TRY(hipEventRecord(ev[0], stream));
-  if (!segs.empty()) {
-    const int rc = launch_templates(set, B, (uint32_t)segs.size(), geom);
-    if (rc) return rc;
-  }
-  if (timing) GRAIN_TRY(hipEventRecord(ev[1], stream));
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
+  if (!segs.empty() && (rc = launch_templates(set, B, (uint32_t)segs.size(), geom_k)) != 0) return rc;
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
   ApplyParams ap{};
-  ap.jobs = d_jobs[set], ap.segs = d_segs[set], ap.tpl = d_tpl, ap.offs = d_offs, ap.luts = d_luts, ap.g = geom;
+  ap.jobs = p_jobs.d[set], ap.segs = p_segs.d[set], ap.tpl = d_tpl, ap.offs = d_offs, ap.luts = d_luts, ap.g = geom_k;
   const int sh = (int)bit_depth - 8;
   ap.min_value = clip_restricted ? 16 << sh : 0;
   ap.max_luma = clip_restricted ? 235 << sh : (256 << sh) - 1;
   ap.max_chroma = clip_restricted ? (mc_identity ? 235 << sh : 240 << sh) : (256 << sh) - 1;
-  const dim3 grid((unsigned)geom.nstripes, B);
-  const size_t lds = apply_lds_bytes(geom);
+  const dim3 grid((unsigned)geom_k.nstripes, B);
+  const size_t lds = apply_lds_bytes(geom_k);
   if (bps == 2) hipLaunchKernelGGL(kg_apply<2>, grid, dim3(kThreads), lds, stream, ap);
   else hipLaunchKernelGGL(kg_apply<1>, grid, dim3(kThreads), lds, stream, ap);
-  GRAIN_TRY(hipGetLastError());
-  if (timing) GRAIN_TRY(hipEventRecord(ev[2], stream));
-  GRAIN_TRY(hipEventRecord(done[set], stream));
+  G1S_OP_TRY(hipGetLastError());
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[2], stream));
+  if ((rc = set_done(set)) != 0) return rc;
   for (const HostOut &h : host_outs)
-    for (int c = 0; c < geom.nplanes; ++c) {
-      const size_t pw = c ? (size_t)((geom.W + geom.subx) >> geom.subx) : (size_t)geom.W, ph = c ? (size_t)((geom.H + geom.suby) >> geom.suby) : (size_t)geom.H;
-      GRAIN_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], d_stage_out + stage_frame * h.slot + plane_off[c], plane_row[c], pw * bps, ph,
-                                 hipMemcpyDeviceToHost, stream));
-    }
+    if ((rc = copy_back(h.slot, h.planes)) != 0) return rc;
   if (timing) {
-    GRAIN_TRY(hipStreamSynchronize(stream));
+    G1S_OP_TRY(hipStreamSynchronize(stream));
     float a = 0, b = 0;
-    GRAIN_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
-    GRAIN_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+    G1S_OP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+    G1S_OP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
     ms_template += a, ms_apply += b, frames_timed += B;
   }
   jobs.clear();
@@ -632,21 +595,13 @@ g1s_grain_t *g1s_grain_new(uint32_t bit_depth, const g1s_grain_opts_t *opts) {
     g1s_set_global_error_("g1s_grain_opts_t.struct_size mismatch");
     return nullptr;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g1s_set_global_error_("no HIP device available: film grain synthesis has no CPU fallback");
-    return nullptr;
-  }
-  int device = opts ? opts->device : -1;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) {
-    g1s_set_global_error_("hipGetDevice failed");
+  int device = 0;
+  const std::string no_device = pick_device(opts ? opts->device : -1, "film grain synthesis", &device);
+  if (!no_device.empty()) {
+    g1s_set_global_error_(no_device.c_str());
     return nullptr;
   }
   g1s_grain *g = new g1s_grain;
-  g->device = device;
-  g->bit_depth = bit_depth;
-  g->bps = bit_depth > 8 ? 2 : 1;
-  g->batch = opts && opts->batch_frames ? std::min(opts->batch_frames, 256u) : 32u;
   g->clip_restricted = opts && opts->clip_to_restricted_range;
   g->mc_identity = opts && opts->mc_identity;
   // the jump table: column b of M^(24 l) is the register 24 l steps after the seed 1 << b
@@ -658,16 +613,11 @@ g1s_grain_t *g1s_grain_new(uint32_t bit_depth, const g1s_grain_opts_t *opts) {
       for (int k = 0; k < kDrawsPerLane; ++k) r = lfsr_step(r);
     }
   }
+  bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
   const uint32_t B = g->batch;
-  bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess;
-  for (auto &e : g->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  for (int k = 0; k < 2; ++k)
-    ok = ok && hipEventCreateWithFlags(&g->done[k], hipEventDisableTiming) == hipSuccess &&
-         hipMalloc((void **)&g->d_jobs[k], sizeof(GrainJob) * B) == hipSuccess && hipMalloc((void **)&g->d_segs[k], sizeof(GrainSeg) * B) == hipSuccess &&
-         hipHostMalloc((void **)&g->h_jobs[k], sizeof(GrainJob) * B, hipHostMallocDefault) == hipSuccess &&
-         hipHostMalloc((void **)&g->h_segs[k], sizeof(GrainSeg) * B, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc((void **)&g->d_jump, jump.size() * 2) == hipSuccess && hipMalloc((void **)&g->d_tpl, sizeof(int16_t) * 3 * kTplSlot * B) == hipSuccess &&
-       hipMalloc((void **)&g->d_luts, (size_t)768 * B) == hipSuccess &&
+  for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  ok = ok && g->p_jobs.alloc(B) && g->p_segs.alloc(B) && hipMalloc((void **)&g->d_jump.p, jump.size() * 2) == hipSuccess &&
+       hipMalloc((void **)&g->d_tpl.p, sizeof(int16_t) * 3 * kTplSlot * B) == hipSuccess && hipMalloc((void **)&g->d_luts.p, (size_t)768 * B) == hipSuccess &&
        hipMemcpy(g->d_jump, jump.data(), jump.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
@@ -681,28 +631,17 @@ int g1s_grain_frame(g1s_grain_t *g, const g1s_segment_t *params, const g1s_frame
   if (!g || !in || !out) return G1S_ERR_INVALID;
   if (g->err_code) return g->err_code;
   (void)hipSetDevice(g->device);
-  if (in->bytes_per_sample != g->bps || out->bytes_per_sample != g->bps)
-    return g->fail(G1S_ERR_INVALID, "bytes_per_sample does not match the bit depth given to g1s_grain_new");
-  if (in->width < 1 || in->height < 1 || in->width > 32u * kMaxBlocksX || in->height > 65536u || (in->nplanes != 1 && in->nplanes != 3) ||
-      in->xdec > 1 || in->ydec > in->xdec)
-    return g->fail(G1S_ERR_INVALID, "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, width up to 16384)");
-  if (out->width != in->width || out->height != in->height || out->nplanes != in->nplanes || out->xdec != in->xdec || out->ydec != in->ydec)
-    return g->fail(G1S_ERR_DIM_MISMATCH, "input and output frame geometry differ");
-  if (!g->have_geom) {
-    const int rc = g->set_geometry(*in);
-    if (rc) return rc;
-  } else if (g->geom.W != (int)in->width || g->geom.H != (int)in->height || g->geom.nplanes != in->nplanes || g->geom.subx != in->xdec ||
-             g->geom.suby != in->ydec) {
+  const Refusal no = check_frame_pair(*in, *out, g->bps, 32u * kMaxBlocksX, "g1s_grain_new",
+                                      "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, width up to 16384)");
+  if (no.code) return g->fail(no.code, no.text);
+  int rc;
+  if (g->have_geom && !g->geom.same_shape(*in)) {
     // a new geometry: what is queued goes out and finishes first, the staging buffers are sized again
-    int rc = g->flush();
-    if (rc) return rc;
+    if ((rc = g->flush()) != 0) return rc;
     if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, "hipStreamSynchronize failed");
-    if (g->d_stage_in) (void)hipFree(g->d_stage_in), g->d_stage_in = nullptr;
-    if (g->d_stage_out) (void)hipFree(g->d_stage_out), g->d_stage_out = nullptr;
-    rc = g->set_geometry(*in);
-    if (rc) return rc;
+    g->have_geom = false;
   }
-  const GrainGeom &gm = g->geom;
+  if (!g->have_geom && (rc = g->set_geometry(*in)) != 0) return rc;
   GrainJob job{};
   job.seg = kNoSegment;
   if (params) {
@@ -715,49 +654,21 @@ int g1s_grain_frame(g1s_grain_t *g, const g1s_segment_t *params, const g1s_frame
     job.seg = (uint32_t)k;
     job.seed = params->random_seed;
   }
+  // input and output staging are `batch` slots each; a frame's slot is its place in the batch being filled
   const uint32_t slot = (uint32_t)g->jobs.size();
-  for (int c = 0; c < gm.nplanes; ++c) {
-    const size_t pw = c ? (size_t)((gm.W + gm.subx) >> gm.subx) : (size_t)gm.W, ph = c ? (size_t)((gm.H + gm.suby) >> gm.suby) : (size_t)gm.H;
-    if (!in->data[c] || !out->data[c] || in->stride_bytes[c] < pw * g->bps || out->stride_bytes[c] < pw * g->bps ||
-        in->stride_bytes[c] > 0xffffffffu || out->stride_bytes[c] > 0xffffffffu || (g->bps == 2 && ((in->stride_bytes[c] | out->stride_bytes[c]) & 1)))
-      return g->fail(G1S_ERR_INVALID, "bad plane pointer or row stride");
-    if (in->on_device == 1) {
-      job.in[c] = static_cast<const uint8_t *>(in->data[c]);
-      job.in_stride[c] = (uint32_t)in->stride_bytes[c];
-    } else {
-      if (!g->d_stage_in && hipMalloc((void **)&g->d_stage_in, g->stage_frame * g->batch) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
-      uint8_t *dst = g->d_stage_in + g->stage_frame * slot + g->plane_off[c];
-      // host planes are read before the call returns (the stream copy is waited for below); pinned planes are queued
-      if (hipMemcpy2DAsync(dst, g->plane_row[c], in->data[c], in->stride_bytes[c], pw * g->bps, ph, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
-      job.in[c] = dst;
-      job.in_stride[c] = (uint32_t)g->plane_row[c];
-    }
-    if (out->on_device == 1) {
-      job.out[c] = static_cast<uint8_t *>(const_cast<void *>(out->data[c]));
-      job.out_stride[c] = (uint32_t)out->stride_bytes[c];
-    } else {
-      if (!g->d_stage_out && hipMalloc((void **)&g->d_stage_out, g->stage_frame * g->batch) != hipSuccess)
-        return g->fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
-      job.out[c] = g->d_stage_out + g->stage_frame * slot + g->plane_off[c];
-      job.out_stride[c] = (uint32_t)g->plane_row[c];
-    }
+  if ((rc = g->stage_in(*in, slot, g->batch, job.in, job.in_stride)) != 0) return rc;
+  const bool host_out = out->on_device != 1;
+  if (host_out && (rc = g->need_stage_out(g->batch)) != 0) return rc;
+  for (int c = 0; c < g->geom.nplanes; ++c) {
+    job.out[c] = host_out ? g->stage_out(slot, c) : static_cast<uint8_t *>(const_cast<void *>(out->data[c]));
+    job.out_stride[c] = host_out ? (uint32_t)g->stage.row[c] : (uint32_t)out->stride_bytes[c];
     // in != out: a plane of the output must not overlap the same plane of the input or its luma
-    const uint8_t *ob = job.out[c], *oe = ob + (size_t)job.out_stride[c] * (ph - 1) + pw * g->bps;
-    for (int d = 0; d <= c; d += c ? c : 1) {
-      const size_t dh = d ? ph : (size_t)gm.H, dw = d ? pw : (size_t)gm.W;
-      const uint8_t *ib = job.in[d], *ie = ib + (size_t)job.in_stride[d] * (dh - 1) + dw * g->bps;
-      if (ob < ie && ib < oe) return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_grain_frame needs distinct buffers");
-    }
+    if (planes_overlap(g->geom, job.out[c], job.out_stride[c], c, job.in[0], job.in_stride[0], 0) ||
+        planes_overlap(g->geom, job.out[c], job.out_stride[c], c, job.in[c], job.in_stride[c], c))
+      return g->fail(G1S_ERR_INVALID, "input and output planes overlap: g1s_grain_frame needs distinct buffers");
   }
-  if (in->on_device == 0 && hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
-  if (out->on_device != 1) {
-    g1s_grain::HostOut h{};
-    h.slot = slot;
-    for (int c = 0; c < gm.nplanes; ++c) h.data[c] = const_cast<void *>(out->data[c]), h.stride[c] = out->stride_bytes[c];
-    g->host_outs.push_back(h);
-  }
+  if ((rc = g->wait_host_input(*in)) != 0) return rc;
+  if (host_out) g->host_outs.push_back({slot, host_planes(*out)});
   g->jobs.push_back(job);
   return g->jobs.size() >= g->batch ? g->flush() : G1S_OK;
 }
@@ -767,10 +678,9 @@ int g1s_grain_sync(g1s_grain_t *g) {
   if (g->err_code) return g->err_code;
   (void)hipSetDevice(g->device);
   const int rc = g->flush();
-  if (rc) return rc;
-  if (hipStreamSynchronize(g->stream) != hipSuccess) return g->fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
-  return G1S_OK;
+  return rc ? rc : g->wait();
 }
+
 
 int g1s_grain_templates(g1s_grain_t *g, const g1s_segment_t *params, uint32_t xdec, uint32_t ydec, int16_t *luma, int16_t *cb, int16_t *cr,
                         uint8_t lut[3][256]) {
@@ -787,9 +697,8 @@ int g1s_grain_templates(g1s_grain_t *g, const g1s_segment_t *params, uint32_t xd
   job.seg = 0, job.seed = params->random_seed;
   const GrainGeom tg = template_geom(g->bit_depth, (int)xdec, (int)ydec, 3);
   // (everything queued has finished: set 0 is free)
-  *g->h_jobs[0] = job, *g->h_segs[0] = sg;
-  if (hipMemcpyAsync(g->d_jobs[0], g->h_jobs[0], sizeof job, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
-      hipMemcpyAsync(g->d_segs[0], g->h_segs[0], sizeof sg, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+  *g->p_jobs.h[0] = job, *g->p_segs.h[0] = sg;
+  if (g->p_jobs.upload(0, 1, g->stream) != hipSuccess || g->p_segs.upload(0, 1, g->stream) != hipSuccess)
     return g->fail(G1S_ERR_HIP, "upload of the template job failed");
   rc = g->launch_templates(0, 1, 1, tg);
   if (rc) return rc;
@@ -815,23 +724,7 @@ int g1s_grain_set_timing(g1s_grain_t *g, int enable, double *ms_template, double
 
 const char *g1s_grain_last_error(const g1s_grain_t *g) { return g ? g->err.c_str() : ""; }
 
-void g1s_grain_free(g1s_grain_t *g) {
-  if (!g) return;
-  (void)hipSetDevice(g->device);
-  if (g->stream) (void)hipStreamSynchronize(g->stream);
-  void *bufs[] = {g->d_jobs[0], g->d_jobs[1], g->d_segs[0], g->d_segs[1], g->d_jump, g->d_tpl, g->d_offs, g->d_luts, g->d_stage_in, g->d_stage_out};
-  for (void *b : bufs)
-    if (b) (void)hipFree(b);
-  for (int k = 0; k < 2; ++k) {
-    if (g->h_jobs[k]) (void)hipHostFree(g->h_jobs[k]);
-    if (g->h_segs[k]) (void)hipHostFree(g->h_segs[k]);
-    if (g->done[k]) (void)hipEventDestroy(g->done[k]);
-  }
-  for (auto &e : g->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (g->stream) (void)hipStreamDestroy(g->stream);
-  delete g;
-}
+void g1s_grain_free(g1s_grain_t *g) { free_op(g); }
 
 int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, const g1s_grain_opts_t *opts, char *err, size_t cap) {
   auto refuse = [&](int code, const std::string &m) -> int64_t {
@@ -858,88 +751,26 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
     rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
   }
   if (rc) return refuse(rc, std::string("grain table: ") + perr);
-  // the input's header line goes out as it came in
-  std::string header;
-  {
-    FILE *f = std::fopen(in, "rb");
-    if (!f) return refuse(G1S_ERR_INVALID, std::string("y4m: cannot open ") + in);
-    char line[1024];
-    if (std::fgets(line, sizeof line, f)) header = line;
-    std::fclose(f);
-  }
-  g1s_y4m_t *y = g1s_y4m_open(in, err, cap);
-  if (!y) return G1S_ERR_INVALID;
-  g1s_y4m_info_t info;
-  g1s_y4m_get_info(y, &info);
-  g1s_grain_t *g = g1s_grain_new(info.bit_depth, opts);
-  if (!g) {
-    g1s_y4m_close(y);
-    return refuse(G1S_ERR_NO_DEVICE, g1s_last_global_error());
-  }
-  FILE *fo = std::fopen(out, "wb");
-  if (!fo) {
-    g1s_grain_free(g);
-    g1s_y4m_close(y);
-    return refuse(G1S_ERR_INVALID, std::string("cannot create ") + out);
-  }
-  const size_t bps = info.bit_depth > 8 ? 2 : 1;
-  size_t pbytes[3] = {0, 0, 0}, prow[3] = {0, 0, 0}, fbytes = 0;
-  for (uint32_t c = 0; c < info.nplanes; ++c) {
-    const size_t pw = c ? (info.width + (1u << info.xdec) - 1) >> info.xdec : info.width, ph = c ? (info.height + (1u << info.ydec) - 1) >> info.ydec : info.height;
-    prow[c] = pw * bps, pbytes[c] = pw * ph * bps, fbytes += pbytes[c];
-  }
-  // a batch of output frames in pinned memory: rendered, waited for, written
-  const uint32_t batch = g->batch;
-  uint8_t *obuf = nullptr;
-  int64_t frames = 0;
-  std::string why;
-  bool ok = std::fwrite(header.data(), 1, header.size(), fo) == header.size();
-  if (!ok) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-  if (ok && hipHostMalloc((void **)&obuf, fbytes * batch, hipHostMallocDefault) != hipSuccess) ok = false, rc = G1S_ERR_HIP, why = "hipHostMalloc of the output frames failed";
-  uint32_t pending = 0;
-  auto drain = [&]() {
-    rc = g1s_grain_sync(g);
-    if (rc) {
-      why = g1s_grain_last_error(g);
-      return false;
+  // a batch of output frames in pinned memory: rendered, waited for (everything handed over is then complete), written
+  struct Driver {
+    const g1s_grain_opts_t *opts;
+    std::vector<g1s_segment_t> &segs;
+    size_t nseg;
+    g1s_y4m_info_t info{};
+    g1s_grain_t *g = nullptr;
+    const int new_failed = G1S_ERR_NO_DEVICE;
+    bool open(const g1s_y4m_info_t &i) { return info = i, (g = g1s_grain_new(i.bit_depth, opts)) != nullptr; }
+    uint32_t batch() const { return g->batch; }
+    uint32_t ring() const { return g->batch; }
+    int frame(int64_t n, const g1s_frame_t *fin, g1s_frame_t *fout) {
+      const long si = g1s_tbl_segment_for(segs.data(), nseg, g1s::frame_time((uint64_t)n, info.fps_num, info.fps_den));
+      return g1s_grain_frame(g, si < 0 ? nullptr : &segs[(size_t)si], fin, fout);
     }
-    for (uint32_t k = 0; k < pending; ++k)
-      if (std::fwrite("FRAME\n", 1, 6, fo) != 6 || std::fwrite(obuf + fbytes * k, 1, fbytes, fo) != fbytes) {
-        rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-        return false;
-      }
-    pending = 0;
-    return true;
+    int drain(bool, uint64_t *) { return g1s_grain_sync(g); }
+    const char *last_error() const { return g1s_grain_last_error(g); }
+    void close() { g1s_grain_free(g); }
   };
-  while (ok) {
-    g1s_frame_t fin;
-    const int got = g1s_y4m_next(y, &fin);
-    if (got < 0) {
-      ok = false, rc = got, why = g1s_y4m_last_error(y);
-      break;
-    }
-    if (got == 0) break;
-    g1s_frame_t fout = fin;
-    size_t off = fbytes * pending;
-    for (uint32_t c = 0; c < info.nplanes; ++c) fout.data[c] = obuf + off, fout.stride_bytes[c] = prow[c], off += pbytes[c];
-    fin.on_device = 0;   // (the reader lends the frame until its next call: copied before g1s_grain_frame returns)
-    fout.on_device = 2;
-    const long si = g1s_tbl_segment_for(segs.data(), nseg, g1s::frame_time((uint64_t)frames, info.fps_num, info.fps_den));
-    rc = g1s_grain_frame(g, si < 0 ? nullptr : &segs[(size_t)si], &fin, &fout);
-    if (rc) {
-      ok = false, why = "frame " + std::to_string(frames) + ": " + g1s_grain_last_error(g);
-      break;
-    }
-    ++frames, ++pending;
-    if (pending == batch) ok = drain();
-  }
-  if (ok) ok = drain();
-  if (std::fclose(fo) != 0 && ok) ok = false, rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
-  g1s_grain_free(g);
-  if (obuf) (void)hipHostFree(obuf);
-  g1s_y4m_close(y);
-  if (!ok) return refuse(rc ? rc : G1S_ERR_INVALID, why);
-  return frames;
+  return rewrite_y4m(in, out, err, cap, Driver{opts, segs, nseg});
 }
 
 }  // extern "C"

@@ -18,12 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import G1SDenoiseOpts, G1SError
-from .diff import Frame
-
-try:
-    import torch
-except Exception:  # pragma: no cover
-    torch = None
+from ._frame_op import FrameOp
 
 log = logging.getLogger("grav1synth")
 
@@ -53,7 +48,9 @@ def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0) -
     return t, int(q.value)
 
 
-class Denoiser:
+class Denoiser(FrameOp):
+    _name = "denoise"
+
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                  strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
@@ -68,29 +65,13 @@ class Denoiser:
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
         self._frames = 0       # handed over since the denoiser was made, as g1s_denoise_drain counts
 
-    def _check(self, rc: int) -> None:
-        if rc:
-            raise G1SError(rc, self._L.g1s_denoise_last_error(self._h).decode())
-
     def apply(self, frame_planes: Sequence, xdec: int = 1, ydec: int = 1, *, sync: bool = True, out: Optional[Sequence] = None) -> List:
         """One frame through the filter: new planes of the same kind -- torch device tensors stay on the device, host planes
         go through host frames.  sync = False queues the frame (a batch goes out as one launch per plane class): the
         returned planes are complete after sync(), or once drain() has counted the frame.  sync = True ends the clip with
         this frame: with a temporal radius it is a one-frame clip unless frames were queued before it (denoise_clip takes
         a whole clip)."""
-        planes = list(frame_planes)
-        if out is None:
-            if torch is not None and isinstance(planes[0], torch.Tensor):
-                out = [torch.empty(p.shape, dtype=p.dtype, device=p.device) for p in planes]
-            else:
-                planes = [np.asarray(p) for p in planes]
-                out = [np.empty(p.shape, p.dtype) for p in planes]
-        out = list(out)
-        keep: list = []
-        fin = Frame(planes, xdec, ydec).to_c(keep)
-        fout = Frame(out, xdec, ydec).to_c(keep)
-        if fin.on_device == 1:
-            torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
+        planes, out, keep, fin, fout = self._frame_pair(frame_planes, xdec, ydec, out)
         self._keep.append((self._frames, (keep, planes, out)))
         self._check(self._L.g1s_denoise_frame(self._h, C.byref(fin), C.byref(fout)))
         self._frames += 1
@@ -123,18 +104,6 @@ class Denoiser:
         a, n = C.c_double(), C.c_uint64()
         self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
         return a.value, n.value
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._L.g1s_denoise_free(self._h)
-            self._h = None
-            self._keep.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,

@@ -17,12 +17,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import G1SError, G1SGrainOpts
-from .diff import Frame, GrainTableSegment
-
-try:
-    import torch
-except Exception:  # pragma: no cover
-    torch = None
+from ._frame_op import FrameOp
+from .diff import GrainTableSegment
 
 log = logging.getLogger("grav1synth")
 
@@ -42,7 +38,9 @@ def _opts(device: int, batch_frames: int, clip_to_restricted_range: bool, mc_ide
     return o
 
 
-class GrainSynthesizer:
+class GrainSynthesizer(FrameOp):
+    _name = "grain"
+
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, clip_to_restricted_range: bool = False,
                  mc_identity: bool = False):
         self._L = _lib.lib()
@@ -53,28 +51,12 @@ class GrainSynthesizer:
             raise G1SError(-5, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # planes the queued kernels still read or write
 
-    def _check(self, rc: int) -> None:
-        if rc:
-            raise G1SError(rc, self._L.g1s_grain_last_error(self._h).decode())
-
     def apply(self, frame_planes: Sequence, segment: Optional[GrainTableSegment], xdec: int = 1, ydec: int = 1, *, sync: bool = True,
               out: Optional[Sequence] = None) -> List:
         """The grain of `segment` (its random_seed is the frame's grain_seed) on one frame: new planes of the same kind -- torch
         device tensors stay on the device, host planes go through host frames.  segment = None: a copy (apply_grain = 0).
         sync = False queues the frame (a batch goes out as one launch): the returned planes are complete after sync()."""
-        planes = list(frame_planes)
-        if out is None:
-            if torch is not None and isinstance(planes[0], torch.Tensor):
-                out = [torch.empty(p.shape, dtype=p.dtype, device=p.device) for p in planes]
-            else:
-                planes = [np.asarray(p) for p in planes]
-                out = [np.empty(p.shape, p.dtype) for p in planes]
-        out = list(out)
-        keep: list = []
-        fin = Frame(planes, xdec, ydec).to_c(keep)
-        fout = Frame(out, xdec, ydec).to_c(keep)
-        if fin.on_device == 1:
-            torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
+        planes, out, keep, fin, fout = self._frame_pair(frame_planes, xdec, ydec, out)
         seg = segment.to_c() if segment is not None else None
         self._keep.append(keep)
         self._check(self._L.g1s_grain_frame(self._h, C.byref(seg) if seg is not None else None, C.byref(fin), C.byref(fout)))
@@ -102,18 +84,6 @@ class GrainSynthesizer:
         a, b, n = C.c_double(), C.c_double(), C.c_uint64()
         self._L.g1s_grain_set_timing(self._h, int(enable), C.byref(a), C.byref(b), C.byref(n))
         return a.value, b.value, n.value
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._L.g1s_grain_free(self._h)
-            self._h = None
-            self._keep.clear()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def render_y4m_file(input: str, table: str, output: str, *, device: int = -1, batch_frames: int = 0,
