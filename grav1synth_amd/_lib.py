@@ -153,6 +153,23 @@ class G1SDenoiseOpts(C.Structure):
     ]
 
 
+class G1SMeasureOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("device", C.c_int32),
+        ("batch_frames", C.c_uint32),
+    ]
+
+
+class G1SMeasureRecord(C.Structure):
+    _fields_ = [
+        ("n", (C.c_uint64 * 32) * 3),
+        ("s1", (C.c_int64 * 32) * 3),
+        ("s2", (C.c_uint64 * 32) * 3),
+        ("r", (C.c_int64 * 25) * 3),
+    ]
+
+
 NEXT_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(G1SFrame))
 
 # every symbol include/g1s_diff.h declares: (name, restype, argtypes)
@@ -266,6 +283,18 @@ SYMBOLS = [
                                              C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("g1s_diff_y4m_file_denoised", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts),
                                              C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    ("g1s_measure_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SMeasureOpts)]),
+    ("g1s_measure_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
+    ("g1s_measure_finish", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_measure_sum", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_format_measure", C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_uint32] * 6 + [C.c_char_p, C.c_size_t]),
+    ("g1s_measure_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_measure_last_error", C.c_char_p, [C.c_void_p]),
+    ("g1s_measure_free", None, [C.c_void_p]),
+    ("g1s_measure_y4m_files", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts), C.POINTER(C.c_int), C.c_char_p,
+                                          C.c_size_t]),
+    ("g1s_check_y4m_files", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts), C.POINTER(G1SGrainOpts),
+                                        C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
 ]
 
 _lib = None

@@ -1,5 +1,5 @@
 """`python -m grav1synth_amd diff SOURCE [DENOISED | --denoise] -o OUT [-y] [-f FILTERS]` -- the front door of the path
-(and `estimate`, `render`, `denoise`).
+(and `estimate`, `render`, `denoise`, `measure`, `check`).
 
 The `diff` command of the reference (Commands::Diff, /root/reference/src/main.rs:347-533, arguments :846-870) for .y4m
 inputs, around g1s_diff_y4m_files_filtered: the same refusals in the same order, with the same texts, and like the
@@ -122,6 +122,23 @@ def build_parser() -> argparse.ArgumentParser:
     n.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
     n.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
     _add_denoise_parameters(n)
+    m = sub.add_parser("measure", help="Measures the grain of NOISY against CLEAN (y4m inputs): strength per intensity bin and "
+                                       "correlation over the table's lag-3 neighbourhood, exact integers, as a text profile.")
+    m.add_argument("noisy", help="The clip with the grain.")
+    m.add_argument("clean", help="The clip without it (the intensity the grain is binned by).")
+    m.add_argument("-o", "--output", required=True, help="The path to the output profile.")
+    m.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
+    m.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    c = sub.add_parser("check", help="Says how well a grain table fits: the profile of SOURCE - DENOISED beside the profile of the "
+                                     "table's grain rendered onto DENOISED (y4m inputs).  Reports; passes no verdict.")
+    c.add_argument("source", help="The untouched source file.")
+    c.add_argument("denoised", help="The denoised file the table was made with.")
+    c.add_argument("-g", "--grain", required=True, help="The film grain table.")
+    c.add_argument("-o", "--output", required=True, help="The path to the output profile.")
+    c.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
+    c.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    c.add_argument("--clip-restricted", action="store_true",
+                   help="render with the output clipped to the restricted (studio) range, as `render --clip-restricted`")
     return ap
 
 
@@ -243,6 +260,45 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     return frames
 
 
+def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm) -> int:
+    """The refusals of `diff` for two inputs and an output, then the frame pairs until the shorter file ends and the
+    profile.  Returns the frame count, -1 after a refusal."""
+    from .measure import measure_y4m_files
+
+    if _same_path(noisy, output) or _same_path(clean, output):
+        log.error(SAME_AS_OUTPUT)
+        return -1
+    if _same_path(noisy, clean):
+        log.error(SAME_INPUTS)
+        return -1
+    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
+        log.warning(NOT_OVERWRITING)
+        return -1
+    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device)
+    log.info("Done, wrote output file to %s", output)
+    return frames
+
+
+def check_command(source: str, denoised: str, table: str, output: str, overwrite: bool = False, device: int = -1,
+                  clip_restricted: bool = False, confirm=_confirm) -> int:
+    """The same refusals (the table is an input too), then the two profiles side by side.  No verdict, no threshold.
+    Returns the frame count, -1 after a refusal."""
+    from .measure import check_y4m_files
+
+    if _same_path(source, output) or _same_path(denoised, output) or _same_path(table, output):
+        log.error(SAME_AS_OUTPUT)
+        return -1
+    if _same_path(source, denoised):
+        log.error(SAME_INPUTS)
+        return -1
+    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
+        log.warning(NOT_OVERWRITING)
+        return -1
+    frames, _unequal = check_y4m_files(source, denoised, table, output, device=device, clip_to_restricted_range=clip_restricted)
+    log.info("Done, wrote output file to %s", output)
+    return frames
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s %(message)s", stream=sys.stderr)
@@ -280,6 +336,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     elif args.command == "denoise":
         try:
             denoise_command(args.input, args.output, args.overwrite, args.device, **_denoise_parameters(args))
+        except Exception as e:
+            log.error("%s", e)
+            return 1
+    elif args.command == "measure":
+        try:
+            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device)
+        except Exception as e:
+            log.error("%s", e)
+            return 1
+    elif args.command == "check":
+        try:
+            check_command(args.source, args.denoised, args.grain, args.output, args.overwrite, args.device, args.clip_restricted)
         except Exception as e:
             log.error("%s", e)
             return 1

@@ -62,16 +62,17 @@ struct Refusal {
 
 // The checks of a frame pair handed to an operation made by `new_name` for `bps` bytes a sample: sample size, a geometry
 // the operation takes (`geometry_text` says which), two frames of one shape, and per plane a pointer and a row stride
-// that holds a row, fits 32 bits and, for 16-bit samples, is even.  code G1S_OK: fine.
+// that holds a row, fits 32 bits and, for 16-bit samples, is even.  code G1S_OK: fine.  `pair_names`: what the two
+// frames are to the operation, for the text of a geometry mismatch (an operation with two inputs names them).
 inline Refusal check_frame_pair(const g1s_frame_t &in, const g1s_frame_t &out, uint32_t bps, uint32_t max_width, const char *new_name,
-                                const char *geometry_text) {
+                                const char *geometry_text, const char *pair_names = "input and output") {
   if (in.bytes_per_sample != bps || out.bytes_per_sample != bps)
     return {G1S_ERR_INVALID, std::string("bytes_per_sample does not match the bit depth given to ") + new_name};
   if (in.width < 1 || in.height < 1 || in.width > max_width || in.height > 65536u || (in.nplanes != 1 && in.nplanes != 3) || in.xdec > 1 ||
       in.ydec > in.xdec)
     return {G1S_ERR_INVALID, geometry_text};
   if (out.width != in.width || out.height != in.height || out.nplanes != in.nplanes || out.xdec != in.xdec || out.ydec != in.ydec)
-    return {G1S_ERR_DIM_MISMATCH, "input and output frame geometry differ"};
+    return {G1S_ERR_DIM_MISMATCH, std::string(pair_names) + " frame geometry differ"};
   const PlaneGeom g(in, bps);
   for (int c = 0; c < g.nplanes; ++c)
     if (!in.data[c] || !out.data[c] || in.stride_bytes[c] < g.row_bytes(c) || out.stride_bytes[c] < g.row_bytes(c) ||
@@ -177,12 +178,13 @@ struct BatchedOp {
   // batch that read it has passed -- the next batch is filled while this one runs
   Event done[2];
   uint64_t batches = 0;
-  // the geometry of the frames so far and the device copies of host frames: an input ring and an output buffer, made when
-  // the first such frame comes, each a number of slots of the staging layout
+  // the geometry of the frames so far and the device copies of host frames: an input ring (a second one for an operation
+  // that takes two frames a call) and an output buffer, made when the first such frame comes, each a number of slots of
+  // the staging layout
   bool have_geom = false;
   PlaneGeom geom;
   Layout stage;
-  DevBuf<uint8_t> d_stage_in, d_stage_out;
+  DevBuf<uint8_t> d_stage_in[2], d_stage_out;
 
   int fail(int code, const std::string &m) {
     if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
@@ -208,19 +210,19 @@ struct BatchedOp {
   // (a new geometry: nothing may be in flight; the staging buffers are sized again when they are next needed)
   void set_frame_geometry(const g1s_frame_t &f) {
     geom = PlaneGeom(f, bps), stage = staging_layout(geom), have_geom = true;
-    d_stage_in = DevBuf<uint8_t>(), d_stage_out = DevBuf<uint8_t>();
+    d_stage_in[0] = DevBuf<uint8_t>(), d_stage_in[1] = DevBuf<uint8_t>(), d_stage_out = DevBuf<uint8_t>();
   }
-  // Where the kernels read `in`: the caller's device planes, or slot `slot` of the input ring of `slots` slots, the copies
+  // Where the kernels read `in`: the caller's device planes, or slot `slot` of input ring `ring` of `slots` slots, the copies
   // queued on the stream.  Host planes are read before the call returns (wait_host_input); pinned planes are queued.
-  int stage_in(const g1s_frame_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3]) {
+  int stage_in(const g1s_frame_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3], int ring = 0) {
     for (int c = 0; c < geom.nplanes; ++c) {
       if (in.on_device == 1) {
         plane[c] = static_cast<const uint8_t *>(in.data[c]), stride[c] = (uint32_t)in.stride_bytes[c];
         continue;
       }
-      if (!d_stage_in && hipMalloc((void **)&d_stage_in.p, stage.frame * slots) != hipSuccess)
+      if (!d_stage_in[ring] && hipMalloc((void **)&d_stage_in[ring].p, stage.frame * slots) != hipSuccess)
         return fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
-      uint8_t *dst = d_stage_in + stage.frame * slot + stage.off[c];
+      uint8_t *dst = d_stage_in[ring] + stage.frame * slot + stage.off[c];
       if (hipMemcpy2DAsync(dst, stage.row[c], in.data[c], in.stride_bytes[c], geom.row_bytes(c), geom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
         return fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
       plane[c] = dst, stride[c] = (uint32_t)stage.row[c];

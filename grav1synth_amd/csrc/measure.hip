@@ -1,0 +1,704 @@
+// measure.hip -- `measure` and `check`: exact grain statistics of a frame pair on the device.
+//
+// The statistics are defined in include/g1s_diff.h ("measure", rules 1 - 6); tests/measure_ref.py restates them in numpy.
+// Two kernels:
+//
+//   km_measure<BPS>  a workgroup per (tile, plane of the class, frame pair).  The tile's d = a - b goes into LDS as int16
+//                    with a halo of 3 columns either side and 3 rows above (zeros outside the plane: a product with a
+//                    sample outside it is skipped by being 0), the tile's bins beside it as bytes.  A wave walks 32 rows
+//                    of the tile top to bottom, a lane a column, with the 4 x 7 window of rule 4 in registers: 7 LDS
+//                    reads and 25 multiply-adds a sample.  Every sample of a and b comes from HBM once, apart from halos
+//                    (and the clean luma a chroma sample is binned by).  The workgroup's partial record goes out with
+//                    plain stores.
+//   km_tail          a workgroup per (plane, frame pair) sums the partial records into the pair's record.
+//
+// The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
+//   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
+//     lanes they are added as two 16-bit halves (each wave sum below 2^23), put together in 64 bits.
+//   * a lane's bin sums run while its column stays in one bin, 32 rows at the most: n <= 32, |s1| < 2^17, s2 < 2^29;
+//     across the lanes s2 goes as two halves like the lag sums.
+// The bins: a lane keeps the sums of the bin its column is in and hands them on when the bin changes.  Handing on is
+// done by the wave, not by the lane: for every distinct bin among the lanes that hand on, one masked DPP reduction and one
+// LDS update by one lane -- a frame of one intensity costs a wave one such update a tile, not 64 additions to one word.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/g1s_diff.h"
+#include "fold.h"
+#include "frame_op.h"
+
+extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
+
+namespace {
+
+constexpr int kTW = 64, kTH = 128, kHalo = 3;
+constexpr int kLW = kTW + 2 * kHalo, kLH = kTH + kHalo;  // the LDS tile: halo left, right and above
+constexpr int kWaves = 4, kThreads = 64 * kWaves, kRowsPerWave = kTH / kWaves;
+constexpr int kBins = 32, kLags = 25;
+constexpr int kEntries = 3 * kBins + kLags;  // a partial record: n[32], s1[32], s2[32], r[25]
+constexpr int kNoBin = 0xff;
+constexpr int kTailGroups = 4;
+static_assert(kRowsPerWave <= 127, "a 32-bit lag sum holds 127 products of 12-bit residuals");
+
+struct MeasureJob {
+  const uint8_t *a[3], *b[3];
+  uint32_t a_stride[3], b_stride[3];  // bytes
+};
+
+struct MeasureParams {
+  const MeasureJob *jobs;
+  unsigned long long *partials;  // [pair][tiles_frame][kEntries]
+  int pw, ph, tiles_x;           // the class's plane size
+  int plane0;                    // first plane of the class: 0 luma, 1 chroma
+  int W, xdec, ydec, shift;      // luma width, chroma decimation, B - 5
+  uint32_t tiles_frame, tile_base, tiles_plane;
+};
+
+struct TailParams {
+  const unsigned long long *partials;
+  unsigned long long *records;  // [pair] g1s_measure_record_t
+  uint32_t tiles_frame, tiles[3], tile_base[3];
+};
+
+template <int BPS>
+__device__ __forceinline__ int sample(const uint8_t *plane, uint32_t stride, int x, int y) {
+  const uint8_t *row = plane + (size_t)y * stride;
+  return BPS == 2 ? (int)reinterpret_cast<const uint16_t *>(row)[x] : (int)row[x];
+}
+
+// full-wave integer sum in the VALU (DPP), every lane taking part; the total is read from lane 63
+__device__ __forceinline__ int wave_sum(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
+  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast31 -> rows 2, 3
+  return __builtin_amdgcn_readlane(v, 63);
+}
+// the same for lane values up to 2^31 in size: v = (v >> 16) 2^16 + (v & 0xffff), the halves summed apart
+__device__ __forceinline__ long long wave_sum_wide(int v) {
+  const int lo = wave_sum(v & 0xffff), hi = wave_sum(v >> 16);
+  return (long long)hi * 65536 + lo;
+}
+
+template <int BPS>
+__global__ __launch_bounds__(kThreads) void km_measure(MeasureParams p) {
+  __shared__ int16_t s_d[kLH * kLW];
+  __shared__ uint8_t s_bin[kTH * kTW];
+  __shared__ unsigned long long s_acc[kWaves][kEntries];  // (two's complement: the signed sums are added as unsigned)
+  const MeasureJob &job = p.jobs[blockIdx.z];
+  const int c = p.plane0 + (int)blockIdx.y;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const int x0 = tx * kTW, y0 = ty * kTH;
+  const uint8_t *pa = job.a[c], *pb = job.b[c], *py = job.b[0];
+  const uint32_t sa = job.a_stride[c], sb = job.b_stride[c], sy = job.b_stride[0];
+
+  for (int i = tid; i < kWaves * kEntries; i += kThreads) (&s_acc[0][0])[i] = 0;
+  // the tile of d with its halo, and the bins of the tile's own samples
+  for (int i = tid; i < kLH * kLW; i += kThreads) {
+    const int ly = i / kLW, lx = i - ly * kLW;
+    const int x = x0 + lx - kHalo, y = y0 + ly - kHalo;
+    const bool inside = x >= 0 && x < p.pw && y >= 0 && y < p.ph;
+    const bool own = lx >= kHalo && lx < kHalo + kTW && ly >= kHalo;
+    int d = 0, bin = kNoBin;
+    if (inside) {
+      const int b = sample<BPS>(pb, sb, x, y);
+      d = sample<BPS>(pa, sa, x, y) - b;
+      if (own) {
+        int I = b;
+        if (c) {  // averageLuma of the clean frame
+          const int xs = x << p.xdec, ys = y << p.ydec;
+          I = sample<BPS>(py, sy, xs, ys);
+          if (p.xdec) I = (I + sample<BPS>(py, sy, min(xs + 1, p.W - 1), ys) + 1) >> 1;
+        }
+        bin = min(I >> p.shift, kBins - 1);  // (a sample above the depth's maximum: the caller's error, not a wild index)
+      }
+    }
+    s_d[i] = (int16_t)d;
+    if (own) s_bin[(ly - kHalo) * kTW + (lx - kHalo)] = (uint8_t)bin;
+  }
+  __syncthreads();
+
+  // the wave's rows of the tile that the plane has (uniform)
+  const int row0 = wave * kRowsPerWave, rows = min(kRowsPerWave, p.ph - (y0 + row0));
+  if (rows > 0) {
+    int acc[kLags];
+#pragma unroll
+    for (int i = 0; i < kLags; ++i) acc[i] = 0;
+    // the window: rows y - 3 .. y of the LDS tile, columns x - 3 .. x + 3 (LDS row ly = tile row + 3, column lx = lane + 3 + dx)
+    int w[4][7];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 7; ++k) w[r + 1][k] = s_d[(row0 + r) * kLW + lane + k];
+    int cur = -1, bn = 0, bs1 = 0, bs2 = 0;  // the bin the lane's column is in and its sums so far (cur < 0: none)
+    unsigned long long *mine = s_acc[wave];
+    // hands on the bin sums of the lanes with `go` set: a reduction and an update a distinct bin
+    auto hand_on = [&](bool go) __attribute__((always_inline)) {
+      unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
+      while (todo) {
+        const int b = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(todo));
+        const bool m = go && cur == b;
+        todo &= ~__builtin_amdgcn_ballot_w64(m);
+        const int n = wave_sum(m ? bn : 0), s1 = wave_sum(m ? bs1 : 0);
+        const long long s2 = wave_sum_wide(m ? bs2 : 0);
+        if (lane == 0) {
+          mine[b] += (unsigned long long)(long long)n;
+          mine[kBins + b] += (unsigned long long)(long long)s1;
+          mine[2 * kBins + b] += (unsigned long long)s2;
+        }
+        if (m) cur = -1, bn = bs1 = bs2 = 0;
+      }
+    };
+    for (int r = 0; r < rows; ++r) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) w[q][k] = w[q + 1][k];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) w[3][k] = s_d[(row0 + r + kHalo) * kLW + lane + k];
+      const int d = w[3][3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) acc[q * 7 + k] += __mul24(d, w[q][k]);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[21 + k] += __mul24(d, w[3][k]);
+      const int dd = __mul24(d, d);
+      acc[24] += dd;
+      const int k = s_bin[(row0 + r) * kTW + lane];
+      const bool change = cur >= 0 && k != cur;
+      if (__builtin_amdgcn_ballot_w64(change)) hand_on(change);
+      if (k != kNoBin) cur = k, bn += 1, bs1 += d, bs2 += dd;
+    }
+    hand_on(cur >= 0);
+#pragma unroll
+    for (int i = 0; i < kLags; ++i) {
+      const long long t = wave_sum_wide(acc[i]);
+      if (lane == 0) mine[3 * kBins + i] = (unsigned long long)t;
+    }
+  }
+  __syncthreads();
+  if (tid < kEntries) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) t += s_acc[v][tid];
+    const size_t at = (size_t)blockIdx.z * p.tiles_frame + p.tile_base + (size_t)blockIdx.y * p.tiles_plane + blockIdx.x;
+    p.partials[at * kEntries + tid] = t;
+  }
+}
+
+// the pair's record from its workgroups' partial records: grid (plane, pair)
+__global__ __launch_bounds__(128 * kTailGroups) void km_tail(TailParams p) {
+  __shared__ unsigned long long s_sum[kTailGroups][128];
+  const int c = (int)blockIdx.x, i = (int)threadIdx.x & 127, g = (int)threadIdx.x >> 7;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kEntries;
+  unsigned long long t = 0;
+  if (i < kEntries)
+    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += kTailGroups) t += src[(size_t)k * kEntries + i];
+  s_sum[g][i] = t;
+  __syncthreads();
+  if (g == 0 && i < kEntries) {
+    for (int v = 1; v < kTailGroups; ++v) t += s_sum[v][i];
+    // g1s_measure_record_t as 64-bit words: n[3][32], s1[3][32], s2[3][32], r[3][25]
+    unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_record_t) / 8);
+    const int field = i < 3 * kBins ? i / kBins : 3, k = i - field * kBins;
+    rec[field < 3 ? field * 3 * kBins + c * kBins + k : 9 * kBins + c * kLags + k] = t;
+  }
+}
+
+// rule 4's offsets in the table's coefficient order, (0, 0) last
+void lag_offset(int i, int *dx, int *dy) {
+  if (i == 24) *dx = 0, *dy = 0;
+  else *dy = i / 7 - 3, *dx = i % 7 - 3;
+}
+
+}  // namespace
+
+// =============================================================== host engine =====
+using namespace g1s_op;
+
+struct g1s_measure : BatchedOp {
+  Event ev[2];
+  std::vector<MeasureJob> jobs;  // the batch being filled
+  ParamSets<MeasureJob> p_jobs;
+  DevBuf<unsigned long long> d_partials;
+  size_t partials_cap = 0;
+  uint32_t tiles[3] = {0, 0, 0}, tile_base[3] = {0, 0, 0}, tiles_frame = 0;
+  DevBuf<g1s_measure_record_t> d_recs;
+  PinnedBuf<g1s_measure_record_t> h_recs;
+  std::vector<g1s_measure_record_t> records;  // since the last hand-over
+  double ms_kernel = 0;
+  uint64_t frames_timed = 0;
+
+  int set_geometry(const g1s_frame_t &f);
+  int flush();
+};
+
+int g1s_measure::set_geometry(const g1s_frame_t &f) {
+  set_frame_geometry(f);
+  tiles_frame = 0;
+  for (int c = 0; c < 3; ++c) {
+    tiles[c] = c < geom.nplanes ? (uint32_t)(((geom.pw(c) + kTW - 1) / kTW) * ((geom.ph(c) + kTH - 1) / kTH)) : 0u;
+    tile_base[c] = tiles_frame;
+    tiles_frame += tiles[c];
+  }
+  const size_t need = (size_t)tiles_frame * kEntries * batch;
+  if (need > partials_cap) {
+    d_partials = DevBuf<unsigned long long>();
+    G1S_OP_TRY(hipMalloc((void **)&d_partials.p, need * sizeof(unsigned long long)));
+    partials_cap = need;
+  }
+  return G1S_OK;
+}
+
+// the queued pairs as one batch: a launch per plane class, the summing launch, the records back, all waited for
+int g1s_measure::flush() {
+  const uint32_t B = (uint32_t)jobs.size();
+  if (!B) return G1S_OK;
+  int set, rc = next_set(&set);
+  if (rc) return rc;
+  std::memcpy(p_jobs.h[set], jobs.data(), sizeof(MeasureJob) * B);
+  G1S_OP_TRY(p_jobs.upload(set, B, stream));
+  G1S_OP_TRY(hipMemsetAsync(d_recs, 0, sizeof(g1s_measure_record_t) * B, stream));  // (the planes a frame does not have)
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
+  for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
+    MeasureParams mp{};
+    mp.jobs = p_jobs.d[set], mp.partials = d_partials;
+    mp.pw = (int)geom.pw(plane0), mp.ph = (int)geom.ph(plane0), mp.tiles_x = (mp.pw + kTW - 1) / kTW, mp.plane0 = plane0;
+    mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
+    mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
+    const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, B);
+    if (bps == 2) hipLaunchKernelGGL(km_measure<2>, grid, dim3(kThreads), 0, stream, mp);
+    else hipLaunchKernelGGL(km_measure<1>, grid, dim3(kThreads), 0, stream, mp);
+    G1S_OP_TRY(hipGetLastError());
+  }
+  TailParams tp{};
+  tp.partials = d_partials, tp.records = reinterpret_cast<unsigned long long *>(d_recs.p), tp.tiles_frame = tiles_frame;
+  for (int c = 0; c < 3; ++c) tp.tiles[c] = tiles[c], tp.tile_base[c] = tile_base[c];
+  hipLaunchKernelGGL(km_tail, dim3((unsigned)geom.nplanes, B), dim3(128 * kTailGroups), 0, stream, tp);
+  G1S_OP_TRY(hipGetLastError());
+  if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
+  G1S_OP_TRY(hipMemcpyAsync(h_recs, d_recs, sizeof(g1s_measure_record_t) * B, hipMemcpyDeviceToHost, stream));
+  if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
+  if (timing) {
+    float ms = 0;
+    G1S_OP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ms_kernel += ms, frames_timed += B;
+  }
+  records.insert(records.end(), h_recs.p, h_recs.p + B);
+  jobs.clear();
+  return G1S_OK;
+}
+
+namespace {
+
+bool checked_add(uint64_t &t, uint64_t v) { return !__builtin_add_overflow(t, v, &t); }
+bool checked_add(int64_t &t, int64_t v) { return !__builtin_add_overflow(t, v, &t); }
+
+// "%.4f" of v, or "-"
+std::string value(bool defined, double v) {
+  if (!defined) return "-";
+  char s[64];
+  snprintf(s, sizeof s, "%.4f", v);
+  return s;
+}
+
+struct Profile {
+  bool has[kBins];
+  double mean[kBins], sigma[kBins];
+  bool has_rho[24];
+  double rho[24];
+};
+
+// the printed values of plane c of a clip's record (one division or one square root a step, in this order)
+Profile profile_of(const g1s_measure_record_t &t, int c, const double terms[kLags]) {
+  Profile p{};
+  for (int k = 0; k < kBins; ++k) {
+    p.has[k] = t.n[c][k] > 0;
+    if (!p.has[k]) continue;
+    const double n = (double)t.n[c][k];
+    p.mean[k] = (double)t.s1[c][k] / n;
+    const double var = (double)t.s2[c][k] / n - p.mean[k] * p.mean[k];
+    p.sigma[k] = std::sqrt(var > 0.0 ? var : 0.0);
+  }
+  for (int i = 0; i < 24; ++i) {
+    p.has_rho[i] = t.r[c][24] != 0 && terms[i] > 0.0;
+    if (p.has_rho[i]) p.rho[i] = ((double)t.r[c][i] / terms[i]) / ((double)t.r[c][24] / terms[24]);
+  }
+  return p;
+}
+
+int refuse(char *err, size_t cap, int code, const std::string &m) {
+  if (err && cap) snprintf(err, cap, "%s", m.c_str());
+  return code;
+}
+
+bool read_file(const char *path, std::string &text) {
+  FILE *f = std::fopen(path, "rb");
+  if (!f) return false;
+  char buf[65536];
+  size_t n;
+  while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+  std::fclose(f);
+  return true;
+}
+
+// the report of a clip's record(s) into a file.  "" when fine
+std::string write_report(const char *path, const g1s_measure_record_t &total, const g1s_measure_record_t *synth, uint64_t frames,
+                         const g1s_y4m_info_t &info) {
+  std::vector<char> buf(1 << 16);
+  const long n = g1s_format_measure(&total, synth, frames, info.bit_depth, info.width, info.height, info.xdec, info.ydec, info.nplanes, buf.data(),
+                                    buf.size());
+  if (n < 0) return "formatting the report failed";
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return std::string("cannot create ") + path;
+  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
+  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
+  return "";
+}
+
+bool same_clip_shape(const g1s_y4m_info_t &a, const g1s_y4m_info_t &b) {
+  return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.xdec == b.xdec && a.ydec == b.ydec && a.nplanes == b.nplanes;
+}
+
+// the records the meter holds, added to `total`.  "" when fine
+std::string take_records(g1s_measure_t *m, std::vector<g1s_measure_record_t> &scratch, g1s_measure_record_t &total) {
+  size_t n = 0;
+  int rc = g1s_measure_finish(m, nullptr, 0, &n);
+  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
+  scratch.resize(n + 1);
+  scratch[n] = total;
+  if (n && (rc = g1s_measure_finish(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
+  if (g1s_measure_sum(scratch.data(), n + 1, &total) != 0) return "the clip's sums leave 64 bits";
+  return "";
+}
+
+}  // namespace
+
+extern "C" {
+
+g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts) {
+  g1s_set_global_error_("");
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
+    g1s_set_global_error_("measure is defined for bit depths 8, 10 and 12");
+    return nullptr;
+  }
+  if (opts && opts->struct_size != sizeof(g1s_measure_opts_t)) {
+    g1s_set_global_error_("g1s_measure_opts_t.struct_size mismatch");
+    return nullptr;
+  }
+  int device = 0;
+  const std::string no_device = pick_device(opts ? opts->device : -1, "measure", &device);
+  if (!no_device.empty()) {
+    g1s_set_global_error_(no_device.c_str());
+    return nullptr;
+  }
+  g1s_measure *m = new g1s_measure;
+  bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
+  const uint32_t B = m->batch;
+  for (Event &e : m->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  ok = ok && m->p_jobs.alloc(B) && hipMalloc((void **)&m->d_recs.p, sizeof(g1s_measure_record_t) * B) == hipSuccess &&
+       hipHostMalloc((void **)&m->h_recs.p, sizeof(g1s_measure_record_t) * B, hipHostMallocDefault) == hipSuccess;
+  if (!ok) {
+    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
+    g1s_measure_free(m);
+    return nullptr;
+  }
+  return m;
+}
+
+int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_frame_t *clean) {
+  if (!m || !noisy || !clean) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  (void)hipSetDevice(m->device);
+  const Refusal no = check_frame_pair(*noisy, *clean, m->bps, 65536u, "g1s_measure_new",
+                                      "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)", "noisy and clean");
+  if (no.code) return m->fail(no.code, no.text);
+  int rc;
+  if (m->have_geom && !m->geom.same_shape(*noisy)) {
+    // a new geometry: what is queued goes out and finishes first, the buffers are sized again
+    if ((rc = m->flush()) != 0) return rc;
+    m->have_geom = false;
+  }
+  if (!m->have_geom && (rc = m->set_geometry(*noisy)) != 0) return rc;
+  MeasureJob job{};
+  const uint32_t slot = (uint32_t)m->jobs.size();
+  if ((rc = m->stage_in(*noisy, slot, m->batch, job.a, job.a_stride, 0)) != 0) return rc;
+  if ((rc = m->stage_in(*clean, slot, m->batch, job.b, job.b_stride, 1)) != 0) return rc;
+  if ((rc = m->wait_host_input(noisy->on_device == 0 ? *noisy : *clean)) != 0) return rc;
+  m->jobs.push_back(job);
+  return m->jobs.size() >= m->batch ? m->flush() : G1S_OK;
+}
+
+int g1s_measure_finish(g1s_measure_t *m, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  (void)hipSetDevice(m->device);
+  const int rc = m->flush();
+  if (rc) return rc;
+  if (n_out) *n_out = m->records.size();
+  if (m->records.size() > cap || (!per_frame && !m->records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
+  if (!m->records.empty()) std::memcpy(per_frame, m->records.data(), sizeof(g1s_measure_record_t) * m->records.size());
+  m->records.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_sum(const g1s_measure_record_t *recs, size_t n, g1s_measure_record_t *total) {
+  if (!total || (n && !recs)) return G1S_ERR_INVALID;
+  g1s_measure_record_t t;
+  std::memset(&t, 0, sizeof t);
+  bool ok = true;
+  for (size_t f = 0; f < n; ++f)
+    for (int c = 0; c < 3; ++c) {
+      for (int k = 0; k < kBins; ++k)
+        ok = checked_add(t.n[c][k], recs[f].n[c][k]) && checked_add(t.s1[c][k], recs[f].s1[c][k]) && checked_add(t.s2[c][k], recs[f].s2[c][k]) && ok;
+      for (int i = 0; i < kLags; ++i) ok = checked_add(t.r[c][i], recs[f].r[c][i]) && ok;
+    }
+  if (!ok) return G1S_ERR_INVALID;
+  *total = t;
+  return G1S_OK;
+}
+
+long g1s_format_measure(const g1s_measure_record_t *total, const g1s_measure_record_t *synth, uint64_t frames, uint32_t bit_depth, uint32_t width,
+                        uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap) {
+  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
+  g1s_frame_t shape{};
+  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = (uint8_t)nplanes;
+  const PlaneGeom g(shape, 1);
+  std::string s = "grainprofile1\n";
+  s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
+  for (int c = 0; c < (int)nplanes; ++c) {
+    s += "plane " + std::to_string(c) + "\n";
+    double terms[kLags];
+    for (int i = 0; i < kLags; ++i) {
+      int dx, dy;
+      lag_offset(i, &dx, &dy);
+      const int64_t tw = (int64_t)g.pw(c) - std::abs(dx), th = (int64_t)g.ph(c) - std::abs(dy);
+      terms[i] = tw > 0 && th > 0 ? (double)tw * (double)th * (double)frames : 0.0;
+    }
+    const Profile a = profile_of(*total, c, terms);
+    Profile b{};
+    if (synth) b = profile_of(*synth, c, terms);
+    for (int k = 0; k < kBins; ++k) {
+      if (!a.has[k]) continue;
+      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[c][k]) + " " + value(true, a.mean[k]) + " " + value(true, a.sigma[k]);
+      if (synth) s += " " + value(b.has[k], b.mean[k]) + " " + value(b.has[k], b.sigma[k]);
+      s += "\n";
+    }
+    for (int i = 0; i < 24; ++i) {
+      int dx, dy;
+      lag_offset(i, &dx, &dy);
+      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a.has_rho[i], a.rho[i]);
+      if (synth) s += " " + value(b.has_rho[i], b.rho[i]);
+      s += "\n";
+    }
+    if (synth) {
+      bool any = false;
+      double worst = 0.0, num = 0.0, den = 0.0;
+      for (int i = 0; i < 24; ++i)
+        if (a.has_rho[i] && b.has_rho[i]) {
+          const double e = std::fabs(b.rho[i] - a.rho[i]);
+          worst = !any || e > worst ? e : worst, any = true;
+        }
+      s += "max_rho_diff " + value(any, worst) + "\n";
+      for (int k = 0; k < kBins; ++k)
+        if (a.has[k] && b.has[k] && a.sigma[k] > 0.0 && b.sigma[k] > 0.0) {
+          const double n = (double)total->n[c][k];
+          num += n * (b.sigma[k] / a.sigma[k]), den += n;
+        }
+      s += "sigma_ratio " + value(den > 0.0, den > 0.0 ? num / den : 0.0) + "\n";
+    }
+  }
+  if (s.size() > cap) return G1S_ERR_CAPACITY;
+  std::memcpy(buf, s.data(), s.size());
+  return (long)s.size();
+}
+
+int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {
+  if (!m) return G1S_ERR_INVALID;
+  m->timing = enable != 0;
+  if (ms_kernel) *ms_kernel = m->ms_kernel;
+  if (frames) *frames = m->frames_timed;
+  return G1S_OK;
+}
+
+const char *g1s_measure_last_error(const g1s_measure_t *m) { return m ? m->err.c_str() : ""; }
+
+void g1s_measure_free(g1s_measure_t *m) { free_op(m); }
+
+int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *out_report, const g1s_measure_opts_t *opts, int *unequal, char *err,
+                              size_t cap) {
+  if (unequal) *unequal = 0;
+  if (!noisy || !clean || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
+  g1s_y4m_t *ya = g1s_y4m_open(noisy, err, cap);
+  if (!ya) return G1S_ERR_INVALID;
+  g1s_y4m_t *yb = g1s_y4m_open(clean, err, cap);
+  if (!yb) {
+    g1s_y4m_close(ya);
+    return G1S_ERR_INVALID;
+  }
+  g1s_y4m_info_t ia, ib;
+  g1s_y4m_get_info(ya, &ia), g1s_y4m_get_info(yb, &ib);
+  g1s_measure_t *m = nullptr;
+  int rc = G1S_OK;
+  std::string why;
+  int64_t frames = 0;
+  g1s_measure_record_t total;
+  std::memset(&total, 0, sizeof total);
+  std::vector<g1s_measure_record_t> scratch;
+  if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
+  if (!rc && !(m = g1s_measure_new(ia.bit_depth, opts))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  while (!rc) {
+    g1s_frame_t fa, fb;
+    const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
+    if (ga < 0 || gb < 0) {
+      rc = ga < 0 ? ga : gb, why = "frame " + std::to_string(frames) + ": " + (ga < 0 ? g1s_y4m_last_error(ya) : g1s_y4m_last_error(yb));
+      break;
+    }
+    if (ga == 0 || gb == 0) {  // the shorter file ends the clip; one alone: the warning of `diff`
+      if (unequal) *unequal = (ga == 0) != (gb == 0);
+      break;
+    }
+    fa.on_device = fb.on_device = 0;  // (the readers lend the frames until their next call: copied before the call returns)
+    if ((rc = g1s_measure_frame(m, &fa, &fb)) != 0) {
+      why = "frame " + std::to_string(frames) + ": " + g1s_measure_last_error(m);
+      break;
+    }
+    ++frames;
+    if (frames % m->batch == 0 && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
+  }
+  if (!rc && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && !(why = write_report(out_report, total, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
+  g1s_measure_free(m);
+  g1s_y4m_close(ya);
+  g1s_y4m_close(yb);
+  return rc ? refuse(err, cap, rc, why) : frames;
+}
+
+int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
+                            const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
+  if (unequal) *unequal = 0;
+  if (!source || !denoised || !tbl || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
+  // the table, as g1s_grain_y4m_file reads it
+  std::string text;
+  if (!read_file(tbl, text)) return refuse(err, cap, G1S_ERR_INVALID, std::string("cannot open ") + tbl);
+  size_t nseg = 0;
+  char perr[256] = "";
+  std::vector<g1s_segment_t> segs(64);
+  int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
+  if (rc == G1S_ERR_CAPACITY) {
+    segs.resize(nseg);
+    rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
+  }
+  if (rc) return refuse(err, cap, rc, std::string("grain table: ") + perr);
+  g1s_y4m_t *ys = g1s_y4m_open(source, err, cap);
+  if (!ys) return G1S_ERR_INVALID;
+  g1s_y4m_t *yd = g1s_y4m_open(denoised, err, cap);
+  if (!yd) {
+    g1s_y4m_close(ys);
+    return G1S_ERR_INVALID;
+  }
+  g1s_y4m_info_t is, id;
+  g1s_y4m_get_info(ys, &is), g1s_y4m_get_info(yd, &id);
+  const PlaneGeom pg(id);
+  const Layout lay = staging_layout(pg);
+  g1s_measure_t *ms = nullptr, *mr = nullptr;  // source - denoised; rendered - denoised
+  g1s_grain_t *gr = nullptr;
+  DevBuf<uint8_t> d_src, d_den, d_ren;  // a group of frames each: the source, the denoised, the rendered
+  std::string why;
+  int64_t frames = 0;
+  uint32_t group = 0, in_group = 0;
+  g1s_measure_record_t total_s, total_r;
+  std::memset(&total_s, 0, sizeof total_s), std::memset(&total_r, 0, sizeof total_r);
+  std::vector<g1s_measure_record_t> scratch;
+  if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
+  if (!rc && (!(ms = g1s_measure_new(id.bit_depth, opts)) || !(mr = g1s_measure_new(id.bit_depth, opts)))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc) {
+    g1s_grain_opts_t go{};
+    if (gopts) go = *gopts;
+    go.struct_size = sizeof go, go.device = ms->device, go.batch_frames = ms->batch;  // one device, one group size
+    if (!(gr = g1s_grain_new(id.bit_depth, &go))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  }
+  if (!rc) {
+    group = ms->batch;
+    (void)hipSetDevice(ms->device);
+    if (hipMalloc((void **)&d_src.p, lay.frame * group) != hipSuccess || hipMalloc((void **)&d_den.p, lay.frame * group) != hipSuccess ||
+        hipMalloc((void **)&d_ren.p, lay.frame * group) != hipSuccess)
+      rc = G1S_ERR_HIP, why = "hipMalloc of the frame buffers failed";
+  }
+  g1s_frame_t shape{};
+  shape.width = id.width, shape.height = id.height, shape.xdec = (uint8_t)id.xdec, shape.ydec = (uint8_t)id.ydec, shape.nplanes = (uint8_t)id.nplanes;
+  shape.bytes_per_sample = (uint8_t)pg.bps, shape.on_device = 1;
+  auto slot = [&](const DevBuf<uint8_t> &buf, uint32_t k) {
+    g1s_frame_t f = shape;
+    lay.point(f, buf + lay.frame * k, pg.nplanes);
+    return f;
+  };
+  // a group is through: its renders complete (the synthesizer has a stream of its own) before the meters read them, both
+  // meters' batches out and waited for, so that the group's buffers are free again
+  auto end_group = [&]() {
+    if ((rc = g1s_grain_sync(gr)) != 0) why = std::string("render: ") + g1s_grain_last_error(gr);
+    for (uint32_t k = 0; k < in_group && !rc; ++k) {
+      const g1s_frame_t s = slot(d_src, k), d = slot(d_den, k), r = slot(d_ren, k);
+      if ((rc = g1s_measure_frame(ms, &s, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(ms);
+      else if ((rc = g1s_measure_frame(mr, &r, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(mr);
+    }
+    for (int k = 0; k < 2 && !rc; ++k)
+      if (!(why = take_records(k ? mr : ms, scratch, k ? total_r : total_s)).empty()) rc = G1S_ERR_INVALID;
+    in_group = 0;
+  };
+  while (!rc) {
+    g1s_frame_t fs, fd;
+    const int gs = g1s_y4m_next(ys, &fs), gd = g1s_y4m_next(yd, &fd);
+    if (gs < 0 || gd < 0) {
+      rc = gs < 0 ? gs : gd, why = "frame " + std::to_string(frames) + ": " + (gs < 0 ? g1s_y4m_last_error(ys) : g1s_y4m_last_error(yd));
+      break;
+    }
+    if (gs == 0 || gd == 0) {
+      if (unequal) *unequal = (gs == 0) != (gd == 0);
+      break;
+    }
+    // both frames to the device, once (the readers lend them until their next call)
+    const g1s_frame_t s = slot(d_src, in_group), d = slot(d_den, in_group);
+    g1s_frame_t r = slot(d_ren, in_group);
+    bool copied = true;
+    for (int c = 0; c < pg.nplanes; ++c)
+      copied = copied &&
+               hipMemcpy2D(const_cast<void *>(s.data[c]), lay.row[c], fs.data[c], fs.stride_bytes[c], pg.row_bytes(c), pg.ph(c), hipMemcpyHostToDevice) == hipSuccess &&
+               hipMemcpy2D(const_cast<void *>(d.data[c]), lay.row[c], fd.data[c], fd.stride_bytes[c], pg.row_bytes(c), pg.ph(c), hipMemcpyHostToDevice) == hipSuccess;
+    if (!copied) {
+      rc = G1S_ERR_HIP, why = "copy of a frame pair to the device failed";
+      break;
+    }
+    // the table's lookup at the frame's presentation time, as `render` makes it; no segment: rendered = denoised
+    const long si = g1s_tbl_segment_for(segs.data(), nseg, g1s::frame_time((uint64_t)frames, id.fps_num, id.fps_den));
+    if ((rc = g1s_grain_frame(gr, si < 0 ? nullptr : &segs[(size_t)si], &d, &r)) != 0) {
+      why = "frame " + std::to_string(frames) + ": render: " + g1s_grain_last_error(gr);
+      break;
+    }
+    ++frames;
+    if (++in_group == group) end_group();
+  }
+  if (!rc && in_group) end_group();
+  if (!rc && !(why = write_report(out_report, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
+  if (ms) (void)hipSetDevice(ms->device);
+  g1s_grain_free(gr);
+  g1s_measure_free(mr);
+  g1s_measure_free(ms);
+  g1s_y4m_close(ys);
+  g1s_y4m_close(yd);
+  return rc ? refuse(err, cap, rc, why) : frames;
+}
+
+}  // extern "C"

@@ -1,0 +1,149 @@
+"""`measure` and `check`: exact grain statistics of a frame pair on an MI355X -- how well a grain table fits.
+
+HIP kernels behind g1s_measure_* (include/g1s_diff.h, where the statistics are defined: rules 1 - 6); no CPU fallback.
+A record holds, per plane, the residual noisy - clean binned by the clean frame's intensity (count, sum, sum of squares
+in 32 bins) and its lagged products over the table's causal lag-3 neighbourhood: the two things a grain table describes.
+
+>>> meter = GrainMeter(10)
+>>> meter.measure([y, u, v], [cy, cu, cv])      # numpy arrays or torch device tensors, as Denoiser.apply takes them
+>>> records = meter.finish()                    # numpy structured array, one entry a pair: n, s1, s2 (3 x 32), r (3 x 25)
+>>> text = format_profile(sum_records(records), len(records), 10, width, height)
+>>> measure_y4m_files("grainy.y4m", "clean.y4m", "profile.txt")
+>>> check_y4m_files("source.y4m", "denoised.y4m", "table.tbl", "fit.txt")   # source - denoised beside rendered - denoised
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord
+from ._frame_op import FrameOp
+from .diff import Frame
+from .ingest import UNEQUAL_WARNING
+
+log = logging.getLogger("grav1synth")
+
+# g1s_measure_record_t
+RECORD = np.dtype([("n", "<u8", (3, 32)), ("s1", "<i8", (3, 32)), ("s2", "<u8", (3, 32)), ("r", "<i8", (3, 25))])
+assert RECORD.itemsize == C.sizeof(G1SMeasureRecord)
+
+
+def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
+    return G1SMeasureOpts(C.sizeof(G1SMeasureOpts), device, batch_frames)
+
+
+class GrainMeter(FrameOp):
+    _name = "measure"
+
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0):
+        self._L = _lib.lib()
+        self.bit_depth = bit_depth
+        opts = _opts(device, batch_frames)
+        self._h = self._L.g1s_measure_new(bit_depth, C.byref(opts))
+        if not self._h:
+            raise G1SError(-5, self._L.g1s_last_global_error().decode())
+        self._keep: list = []  # planes the queued kernels still read
+
+    def measure(self, noisy_planes: Sequence, clean_planes: Sequence, xdec: int = 1, ydec: int = 1, *, async_host: bool = False) -> None:
+        """Queues one pair (a batch goes out as one launch per plane class); its record comes with finish().  Host planes
+        are copied before the call returns; async_host = True queues the copies of pinned torch tensors instead: they
+        must stay as they are until finish()."""
+        keep: list = []
+        pair = []
+        for planes in (noisy_planes, clean_planes):
+            planes = list(planes)
+            if not hasattr(planes[0], "is_cuda"):
+                planes = [np.asarray(p) for p in planes]
+            keep.append(planes)
+            pinned = async_host and hasattr(planes[0], "is_pinned") and not planes[0].is_cuda and planes[0].is_pinned()
+            pair.append(Frame(planes, xdec, ydec, async_host=pinned).to_c(keep))
+        if pair[0].on_device == 1 or pair[1].on_device == 1:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
+        self._keep.append(keep)
+        self._check(self._L.g1s_measure_frame(self._h, C.byref(pair[0]), C.byref(pair[1])))
+
+    def finish(self, cap: Optional[int] = None) -> np.ndarray:
+        """Launches what is queued, waits, and returns the records since the last finish(), one a pair, in order.  The
+        meter can be used again.  cap: the size of the buffer handed to the library (a test aid; too small raises
+        G1S_ERR_CAPACITY and loses nothing)."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_measure_finish(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), RECORD)
+        rc = self._L.g1s_measure_finish(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def kernel_times(self, enable: bool = True) -> Tuple[float, int]:
+        """(ms in km_measure and km_tail, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        a, n = C.c_double(), C.c_uint64()
+        self._L.g1s_measure_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
+        return a.value, n.value
+
+
+def sum_records(records: np.ndarray) -> np.ndarray:
+    """Rule 6: a clip's record from its frames' (g1s_measure_sum; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, RECORD).reshape(-1)
+    total = np.zeros((), RECORD)
+    rc = _lib.lib().g1s_measure_sum(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's sums leave 64 bits")
+    return total
+
+
+def format_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1, nplanes: int = 3,
+                   synth: Optional[np.ndarray] = None) -> bytes:
+    """The report of a clip's record (g1s_format_measure; host only): one value column, or two with `synth`."""
+    total = np.ascontiguousarray(total, RECORD)
+    synth = None if synth is None else np.ascontiguousarray(synth, RECORD)
+    buf = C.create_string_buffer(1 << 16)
+    w = _lib.lib().g1s_format_measure(total.ctypes.data, None if synth is None else synth.ctypes.data, frames, bit_depth, width, height, xdec,
+                                      ydec, nplanes, buf, len(buf))
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_measure failed")
+    return buf.raw[:w]
+
+
+def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, batch_frames: int = 0) -> Tuple[int, bool]:
+    """`measure NOISY CLEAN -o REPORT` for two .y4m files.  Returns (frames, unequal)."""
+    opts = _opts(device, batch_frames)
+    err = C.create_string_buffer(512)
+    unequal = C.c_int(0)
+    n = _lib.lib().g1s_measure_y4m_files(str(noisy).encode(), str(clean).encode(), str(output).encode(), C.byref(opts), C.byref(unequal), err,
+                                         len(err))
+    if n < 0:
+        raise G1SError(int(n), err.value.decode())
+    if unequal.value:
+        log.warning(UNEQUAL_WARNING)
+    log.info("Measured %d frames", n)
+    return int(n), bool(unequal.value)
+
+
+def check_y4m_files(source: str, denoised: str, table: str, output: str, *, device: int = -1, batch_frames: int = 0,
+                    clip_to_restricted_range: bool = False) -> Tuple[int, bool]:
+    """`check SOURCE DENOISED -g TABLE -o REPORT`: source - denoised beside render(denoised, table) - denoised.  Returns
+    (frames, unequal)."""
+    opts = _opts(device, batch_frames)
+    gopts = G1SGrainOpts(C.sizeof(G1SGrainOpts), device, batch_frames, int(clip_to_restricted_range), 0)
+    err = C.create_string_buffer(512)
+    unequal = C.c_int(0)
+    n = _lib.lib().g1s_check_y4m_files(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(), C.byref(opts),
+                                       C.byref(gopts), C.byref(unequal), err, len(err))
+    if n < 0:
+        raise G1SError(int(n), err.value.decode())
+    if unequal.value:
+        log.warning(UNEQUAL_WARNING)
+    log.info("Checked %d frames", n)
+    return int(n), bool(unequal.value)

@@ -535,6 +535,88 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
 int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                         const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames, char *err, size_t cap);
 
+/* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
+ * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal
+ * lag-3 neighbourhood.  `measure` takes those two things of a residual noisy - clean, whole-plane, at full bit depth,
+ * in exact integers; `check` takes them twice, of source - denoised and of render(denoised, table) - denoised.
+ * Two frames of one geometry and one bit depth B in {8, 10, 12}: a (noisy) and b (clean), luma only or three planes
+ * (xdec <= 1, ydec <= xdec).  For every plane c of size pw x ph:
+ *   1. d(p) = a(p) - b(p), signed, |d| < 2^B.  A sample above the bit depth's maximum is the caller's error.
+ *   2. The intensity I(p): for luma b_Y(p); for chroma the specification's averageLuma of the CLEAN frame: with
+ *      ys = y << ydec, xs = x << xdec: (b_Y(xs, ys) + b_Y(min(xs + 1, W - 1), ys) + 1) >> 1 if xdec, else b_Y(xs, ys).
+ *      The bin is k(p) = I(p) >> (B - 5): 32 bins.
+ *   3. Per bin k, over all p of the plane with k(p) = k: n[k] the count (u64), s1[k] = sum of d (i64), s2[k] = sum of
+ *      d^2 (u64).
+ *   4. Lagged products over 25 offsets (dx, dy): the first 24 are the lag-3 causal neighbourhood in the table's
+ *      coefficient order (dy = -3 .. 0, dx = -3 .. 3, raster, stopping before (0, 0)); (0, 0) is index 24.
+ *      r[i] = sum of d(p) d(p + delta_i) (i64) over every p for which p AND p + delta_i lie inside the plane: skipped,
+ *      not clamped.  The number of terms is (pw - |dx|)(ph - |dy|), or 0 where that is not positive; it is not stored.
+ *   5. A frame's record is the three planes' {n[32], s1[32], s2[32], r[25]}, zeros for the planes the frame does not
+ *      have.  Everything is exact: s2 <= 2^24 2^32 for the largest frame the checks admit (65536 x 65536).
+ *   6. A clip's record is the sum of its frames' records, formed on the host with checked 64-bit additions
+ *      (g1s_measure_sum): an overflow is a refusal, not a wrap.
+ * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
+ * chroma planes) and a small summing launch, on the meter's own stream.  Errors are sticky (g1s_measure_last_error). */
+typedef struct {
+  uint64_t n[3][32];
+  int64_t s1[3][32];
+  uint64_t s2[3][32];
+  int64_t r[3][25];
+} g1s_measure_record_t;
+typedef struct {
+  uint32_t struct_size; /* sizeof(g1s_measure_opts_t) */
+  int32_t device;       /* HIP device ordinal; -1 = current device */
+  uint32_t batch_frames;
+} g1s_measure_opts_t;
+typedef struct g1s_measure g1s_measure_t;
+/* bit_depth 8, 10 or 12.  NULL on failure, the reason from g1s_last_global_error() ("no HIP device available: measure
+ * has no CPU fallback" without a device).  opts == NULL: current device, defaults. */
+g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts);
+/* One frame pair; both are only read.  Each follows g1s_frame_t.on_device on its own: 0 = host (copied before the call
+ * returns), 1 = device, 2 = pinned host (the copy is queued).  Device and pinned planes must stay valid and unmodified
+ * until the batch they are in has gone out: batch_frames pairs later, or at g1s_measure_finish.  A pair whose geometry
+ * differs from the one before it sends the queued pairs out first. */
+int g1s_measure_frame(g1s_measure_t *, const g1s_frame_t *noisy, const g1s_frame_t *clean);
+/* Launches what is queued, waits, and hands over one record per pair since the last hand-over, in order.  cap too
+ * small (or per_frame NULL): G1S_ERR_CAPACITY, *n_out = the count, the records stay (the error is not sticky).  After
+ * G1S_OK the meter holds no records; more pairs may follow. */
+int g1s_measure_finish(g1s_measure_t *, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out);
+/* Rule 6 (host only, needs no device): *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_measure_sum(const g1s_measure_record_t *recs, size_t n, g1s_measure_record_t *total);
+/* The report (host only): plain text from a clip's record of `frames` frames of one geometry.  synth == NULL: one value
+ * column; else two (total = source - denoised, synth = rendered - denoised) and two summary lines a plane.  Every value is
+ * formed in f64 from the exact integers and printed "%.4f"; "-" where it is undefined.  Grammar:
+ *   grainprofile1
+ *   frames N bit_depth B planes P
+ *   plane c                                      for c in 0 .. P - 1
+ *   bin k n mean sigma [mean' sigma']            the bins with n > 0 (n is total's): mean = s1 / n,
+ *                                                sigma = sqrt(max(s2 / n - mean mean, 0))
+ *   lag dx dy rho [rho']                         the 24 lags: rho = (r[i] / terms_i) / (r[24] / terms_24), terms_i =
+ *                                                frames (pw - |dx|)(ph - |dy|); "-" when r[24] = 0 or terms_i = 0
+ *   max_rho_diff v                               (two columns) the largest |rho' - rho| over the lags where both exist
+ *   sigma_ratio v                                (two columns) the n-weighted mean of sigma' / sigma over the bins where
+ *                                                both are positive
+ * Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a geometry rule 5 does not have). */
+long g1s_format_measure(const g1s_measure_record_t *total, const g1s_measure_record_t *synth, uint64_t frames, uint32_t bit_depth,
+                        uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap);
+/* HIP-event time of the kernels so far, milliseconds, and the frames they covered (enable = 1: timed from the next
+ * batch on).  tools/bench_measure.py. */
+int g1s_measure_set_timing(g1s_measure_t *, int enable, double *ms_kernel, uint64_t *frames);
+const char *g1s_measure_last_error(const g1s_measure_t *);
+void g1s_measure_free(g1s_measure_t *);
+/* `measure NOISY CLEAN -o REPORT` for two .y4m files of one geometry and bit depth: the frame pairs until the shorter
+ * file ends (*unequal = 1 when only one ended), the clip's record, the report.  Returns the number of frames, or a
+ * negative G1S_ERR_* with the reason in err. */
+int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *out_report, const g1s_measure_opts_t *opts, int *unequal,
+                              char *err, size_t cap);
+/* `check SOURCE DENOISED -g TABLE -o REPORT`: per frame k the table's lookup as g1s_grain_y4m_file makes it, the grain
+ * rendered onto the denoised frame into a device buffer, then measure(source, denoised) and measure(rendered,
+ * denoised): the denoised frame is uploaded once and the rendered frame never leaves the device.  A frame no segment
+ * covers is measured with rendered = denoised.  The two-column report; no verdict.  gopts->device is ignored (one
+ * device: opts->device).  Returns as g1s_measure_y4m_files. */
+int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
+                            const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

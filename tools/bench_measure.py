@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""tools/bench_measure.py [repeats] -- `measure` on the GPU box: km_measure and km_tail over device-resident frame pairs, 4K
+10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 32, on two contents: the plane-distinct content (tests/content.py) and a clean
+frame of one intensity, which puts every sample of a plane into one bin (the worst case for the bin sums).  Per case: HIP-event
+time per batch through g1s_measure_set_timing (a warm-up batch, then `repeats` timed batches, each waited for), median and
+spread, and the bytes that must be read (both frames once) / time as a fraction of the 8 TB/s roofline.  Beside it, from the
+same process, what the project's streaming kernel k_estimate_pk reaches on the same luma plane (its own bytes / its own
+time): the yardstick of this box.  One JSON line per case.  For the kernel trace:
+rocprofv3 --kernel-trace --stats -- python tools/bench_measure.py 2 (a run of its own)."""
+import json, os, statistics, sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+from grav1synth_amd.estimate import NoiseEstimator
+from grav1synth_amd.measure import GrainMeter
+from tests import content as CT
+
+assert torch.cuda.is_available(), "bench_measure.py needs a GPU"
+repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+BATCH, PEAK = 32, 8e12
+
+
+def dev(planes):
+    return [torch.from_numpy(np.ascontiguousarray(p)).to("cuda") for p in planes]
+
+
+for name, (w, h, bd) in (("3840x2160 10-bit 4:2:0", (3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", (1920, 1080, 8))):
+    pairs = [CT.make_frames("distinct", w, h, bd, 1, 1, frame=k) for k in range(4)]
+    for content in ("distinct", "one intensity"):
+        noisy, clean = [], []
+        for src, den in pairs:
+            if content == "one intensity":  # the same residuals on a clean frame of one code value a plane
+                flat = [np.full(p.shape, (100 + 20 * c) << (bd - 8), p.dtype) for c, p in enumerate(den)]
+                src = [np.clip(f.astype(np.int64) + s.astype(np.int64) - d.astype(np.int64), 0, (1 << bd) - 1).astype(d.dtype) for f, s, d in zip(flat, src, den)]
+                den = flat
+            noisy.append(dev(src)), clean.append(dev(den))
+        torch.cuda.synchronize()
+        bps = 1 if bd == 8 else 2
+        frame_bytes = sum(p.numel() for p in noisy[0]) * bps
+        m = GrainMeter(bd, batch_frames=BATCH)
+
+        def batch():
+            for k in range(BATCH):
+                m.measure(noisy[k % 4], clean[k % 4], 1, 1)
+            m.finish()
+
+        batch()  # warm-up: code objects, buffers
+        times = []
+        for _ in range(repeats):
+            a0, _n = m.kernel_times(True)
+            batch()
+            a1, _n = m.kernel_times(False)
+            times.append(a1 - a0)
+        m.close()
+        # the yardstick: k_estimate_pk over the same luma planes, same batches
+        est = NoiseEstimator(bd, batch_frames=BATCH)
+
+        def ebatch():
+            for k in range(BATCH):
+                est.estimate_frame(noisy[k % 4][0])
+            est.finish()
+
+        ebatch()
+        etimes = []
+        for _ in range(repeats):
+            a0, _n = est.kernel_time(True)
+            ebatch()
+            a1, _n = est.kernel_time(False)
+            etimes.append(a1 - a0)
+        est.close()
+        ms, ems = statistics.median(times), statistics.median(etimes)
+        luma_bytes = noisy[0][0].numel() * bps
+        print(json.dumps({
+            "format": name, "content": content, "batch_frames": BATCH, "repeats": repeats,
+            "measure_ms_per_batch_median": ms, "measure_ms_min": min(times), "measure_ms_max": max(times), "measure_us_per_frame": ms * 1e3 / BATCH,
+            "bytes_read_per_frame": 2 * frame_bytes, "measure_TBps": 2 * frame_bytes * BATCH / (ms * 1e-3) / 1e12,
+            "measure_fraction_of_8TBps": 2 * frame_bytes * BATCH / (ms * 1e-3) / PEAK,
+            "estimate_pk_ms_per_batch_median": ems, "estimate_pk_ms_min": min(etimes), "estimate_pk_ms_max": max(etimes),
+            "estimate_pk_TBps": luma_bytes * BATCH / (ems * 1e-3) / 1e12, "estimate_pk_fraction_of_8TBps": luma_bytes * BATCH / (ems * 1e-3) / PEAK,
+        }), flush=True)
