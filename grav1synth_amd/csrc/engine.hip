@@ -464,7 +464,8 @@ struct g1s_diff {
   // the wide chain (k3w.hip.h): blocks a chroma unit, cells a block row / a frame per kind, L geometry
   int w_ub_c = 4, w_gx[2] = {0, 0}, w_ncell[2] = {0, 0};
   uint32_t w_lpitch = 0, w_lframe = 0;
-  bool wide_ok(const Geom &g) const;
+  bool wide_ok(const Geom &g, bool far) const;
+  bool batch_far(const Slot &sl) const;
   MParams make_mparams(const Slot &sl) const;
   SlotLayout lay{};  // the slots' memory (set_geometry)
   Slot slots[kSlots];
@@ -753,6 +754,14 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
       (d->bytes_per_sample != 1 && d->bytes_per_sample != 2) || (s->nplanes != 1 && s->nplanes != 3) ||
       s->width < 1 || s->height < 1 || s->xdec > 1 || s->ydec > 1)
     return fail(G1S_ERR_INVALID, "unsupported frame format");
+  // what the kernels cannot address is refused like a bad plane, and as early (frame_op.h: diff_size_ok, diff_reach)
+  auto lost = [&](const std::string &m) {
+    int ok = G1S_OK;
+    sticky.compare_exchange_strong(ok, G1S_ERR_INVALID);
+    return fail(G1S_ERR_INVALID, m);
+  };
+  if (!g1s_op::diff_size_ok(s->width, s->height))
+    return lost("frame of " + std::to_string(s->width) + " x " + std::to_string(s->height) + " samples: diff takes at most 131072 x 131072");
   if ((s->bytes_per_sample == 1) != (src_bd == 8) || (d->bytes_per_sample == 1) != (den_bd == 8))
     return fail(G1S_ERR_INVALID, "bytes_per_sample does not match the bit depth given to g1s_diff_new");
   // what g1s_grain_frame and g1s_denoise_frame refuse for a plane, before anything is allocated, copied or queued: the kernels
@@ -761,11 +770,11 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
     const g1s_frame_t *f = side ? d : s;
     for (uint32_t c = 0; c < (luma_only ? 1u : (uint32_t)s->nplanes); ++c) {  // (the planes that are read)
       const size_t rowb = (c ? (size_t)(f->width >> f->xdec) : (size_t)f->width) * f->bytes_per_sample;
-      if (!f->data[c] || f->stride_bytes[c] < rowb || f->stride_bytes[c] > 0xffffffffu || (f->bytes_per_sample == 2 && (f->stride_bytes[c] & 1))) {
-        int ok = G1S_OK;
-        sticky.compare_exchange_strong(ok, G1S_ERR_INVALID);
-        return fail(G1S_ERR_INVALID, std::string(side ? "denoised" : "source") + " frame, plane " + std::to_string(c) + ": bad plane pointer or row stride");
-      }
+      const std::string which = std::string(side ? "denoised" : "source") + " frame, plane " + std::to_string(c);
+      if (!f->data[c] || f->stride_bytes[c] < rowb || f->stride_bytes[c] > 0xffffffffu || (f->bytes_per_sample == 2 && (f->stride_bytes[c] & 1)))
+        return lost(which + ": bad plane pointer or row stride");
+      const g1s_op::DiffReach reach = g1s_op::diff_plane_reach(*f, (int)c);
+      if (g1s_op::diff_refused(reach)) return lost(which + ": " + g1s_op::diff_refusal_text(reach));
     }
   }
   if (!geometry_set) {
@@ -876,6 +885,20 @@ Geom g1s_diff::batch_geom(const Slot &sl) const {
   }
   g.vec_mask = vec_mask;
   return g;
+}
+
+// a device plane of the batch reaches past what the wide chain's buffer descriptor covers (frame_op.h: diff_plane_reach; append
+// has refused what no chain reaches; staged host frames are tight copies and never do): the batch is the stream chain's
+bool g1s_diff::batch_far(const Slot &sl) const {
+  const Geom &g = geom;
+  for (uint32_t i = 0; i < sl.count; ++i)
+    for (int c = 0; c < g.nplanes; ++c) {
+      const uint64_t pw = c ? g.W >> g.xdec : g.W, ph = c ? g.H >> g.ydec : g.H;
+      if (g1s_op::diff_plane_reach(sl.h_planes[i].src_stride[c], ph, pw * g.src_bps) != g1s_op::DiffReach::kAnyChain ||
+          g1s_op::diff_plane_reach(sl.h_planes[i].den_stride[c], ph, pw * g.den_bps) != g1s_op::DiffReach::kAnyChain)
+        return true;
+    }
+  return false;
 }
 
 // A batch runs in two halves.  Front: the frame table and the zero fills on the upload stream, then the finder chain
@@ -1041,7 +1064,7 @@ int g1s_diff::launch_front(int si) {
     }
   }
   if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvFinderEnd], fstream));
-  const bool w_lists = wide_ok(g);  // the wide chain: the unit lists come out of the select kernel
+  const bool w_lists = wide_ok(g, batch_far(sl));  // the wide chain: the unit lists come out of the select kernel
   WUnitParams wup{};
   if (w_lists) {
     for (int k = 0; k < 2; ++k) {
@@ -1071,7 +1094,7 @@ int g1s_diff::launch_front(int si) {
 
 // the wide chain serves: equal sample widths, every plane's rows 16-byte aligned, whole 8-sample words in every plane,
 // (unaligned planes, odd widths and mixed depths run the stream chain)
-bool g1s_diff::wide_ok(const Geom &g) const {
+bool g1s_diff::wide_ok(const Geom &g, bool far) const {
   if (!switches().wide || switches().w_off) return false;
   if (g.lag < 1) return false;
   // inputs of one sample size and one narrowing shift <= 4: the residual in place (w_residual); any other pair of depths: the
@@ -1080,6 +1103,7 @@ bool g1s_diff::wide_ok(const Geom &g) const {
   if (wide_gen(g) && !(g.nplanes != 3 || (g.xdec == 1 && g.ydec == 1))) return false;
   const int need = g.nplanes == 3 ? 0x3f : 0x09;
   if ((g.vec_mask & need) != need) return false;
+  if (far) return false;  // a plane of 2 GiB or more from first to last sample (batch_far): the stream chain
   if ((g.W & 7) != 0 || (g.nplanes == 3 && ((g.W >> g.xdec) & 7) != 0)) return false;
   if (g.nbw > 1023 * 4 || g.nbh > 4095) return false;
   return true;
@@ -1336,7 +1360,7 @@ int g1s_diff::launch_back(int si) {
   const bool side = !(switches().one_stream || sl.timed || !ss.flat);
   if (side) HIP_TRY(hipStreamWaitEvent(stream, ss.mask_done[si], 0));  // the mask, the unit lists
   // (`stream` comes back as the copy stream when the chain moved its chroma launch and what follows there)
-  int rc = wide_ok(g) ? accumulate_wide(sl, si, g, stream, side) : accumulate_stream(sl, si, g, stream, side);
+  int rc = wide_ok(g, batch_far(sl)) ? accumulate_wide(sl, si, g, stream, side) : accumulate_stream(sl, si, g, stream, side);
   if (rc) return rc;
   kmark(sl, stream, nullptr);
   if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvEnd], stream));

@@ -81,6 +81,54 @@ inline Refusal check_frame_pair(const g1s_frame_t &in, const g1s_frame_t &out, u
   return {};
 }
 
+// What `diff` can address: the one predicate g1s_diff::append (refusals) and g1s_diff::batch_far (the chain of a batch) in
+// engine.hip ask, per plane.
+//   side:   the unit lists pack a unit's column and block row into bit fields (k3m_units: 12 + 12 bits of 64-sample chunks and
+//           32-row block rows; k2w_select_units: 10 + 12 bits, which wide_ok keeps to fewer blocks still), so a frame is at
+//           most kDiffMaxSide samples wide and high: 4 096 blocks a side.
+//   stride: both accumulation kernels form (row of a tile) * stride in 32 bits, for the up to kDiffTileRows rows of a block's tile
+//           with its halo, also for rows below the plane that are then not loaded: kDiffTileRows * stride must fit 32 bits.
+//   extent: the bytes from a plane's first sample to its last, stride * (rows - 1) + row bytes in 64 bits.  The wide chain
+//           reads a plane through a buffer descriptor of 2^31 - 1 bytes (a load beyond it returns zero), the stream chain
+//           forms (first row of a tile) * stride in 32 bits: up to kDiffWideMaxExtent either chain, up to kDiffMaxExtent the
+//           stream chain, beyond that the plane is refused.
+// A chroma plane is (width >> xdec) x (height >> ydec), as everywhere in `diff`.
+constexpr uint32_t kDiffMaxSide = 131072u, kDiffTileRows = 36u;
+constexpr uint64_t kDiffWideMaxExtent = 0x7fffffffull, kDiffMaxExtent = 0xffffffffull, kDiffMaxStride = 0xffffffffull / kDiffTileRows;
+
+inline uint64_t plane_extent(uint64_t stride_bytes, uint64_t rows, uint64_t row_bytes) { return rows ? stride_bytes * (rows - 1) + row_bytes : 0; }
+
+inline bool diff_size_ok(uint32_t width, uint32_t height) { return width >= 1 && height >= 1 && width <= kDiffMaxSide && height <= kDiffMaxSide; }
+
+enum class DiffReach { kAnyChain, kStreamChain, kRefusedExtent, kRefusedStride };
+inline bool diff_refused(DiffReach r) { return r == DiffReach::kRefusedExtent || r == DiffReach::kRefusedStride; }
+// a plane of `rows` rows of `row_bytes` bytes, `stride_bytes` apart (a stride that holds a row)
+inline DiffReach diff_plane_reach(uint64_t stride_bytes, uint64_t rows, uint64_t row_bytes) {
+  if (stride_bytes > kDiffMaxStride) return DiffReach::kRefusedStride;
+  const uint64_t extent = plane_extent(stride_bytes, rows, row_bytes);
+  return extent <= kDiffWideMaxExtent ? DiffReach::kAnyChain : extent <= kDiffMaxExtent ? DiffReach::kStreamChain : DiffReach::kRefusedExtent;
+}
+inline const char *diff_refusal_text(DiffReach r) {
+  return r == DiffReach::kRefusedStride ? "a row stride above 119304647 bytes (36 rows of it leave 32 bits)"
+                                        : "the plane's extent (row stride x (rows - 1) + a row) is 4 GiB or more";
+}
+static_assert(kDiffMaxStride == 119304647ull, "diff_refusal_text names the bound");
+
+// plane c of a frame handed to `diff`: its extent and its reach
+inline uint64_t diff_plane_rows(const g1s_frame_t &f, int c) { return c ? f.height >> f.ydec : f.height; }
+inline uint64_t diff_plane_row_bytes(const g1s_frame_t &f, int c) { return (uint64_t)(c ? f.width >> f.xdec : f.width) * f.bytes_per_sample; }
+inline uint64_t diff_plane_extent(const g1s_frame_t &f, int c) { return plane_extent(f.stride_bytes[c], diff_plane_rows(f, c), diff_plane_row_bytes(f, c)); }
+inline DiffReach diff_plane_reach(const g1s_frame_t &f, int c) { return diff_plane_reach(f.stride_bytes[c], diff_plane_rows(f, c), diff_plane_row_bytes(f, c)); }
+// the planes 0 .. nplanes - 1 of a frame together: the furthest any of them reaches
+inline DiffReach diff_frame_reach(const g1s_frame_t &f, int nplanes) {
+  DiffReach r = DiffReach::kAnyChain;
+  for (int c = 0; c < nplanes; ++c) {
+    const DiffReach p = diff_plane_reach(f, c);
+    if ((int)p > (int)r) r = p;
+  }
+  return r;
+}
+
 // do the bytes of plane ca at `a` and of plane cb at `b` (frames of geometry g) share an address?
 inline bool planes_overlap(const PlaneGeom &g, const uint8_t *a, size_t a_stride, int ca, const uint8_t *b, size_t b_stride, int cb) {
   const uint8_t *ae = a + a_stride * (g.ph(ca) - 1) + g.row_bytes(ca), *be = b + b_stride * (g.ph(cb) - 1) + g.row_bytes(cb);

@@ -196,6 +196,10 @@ int ResizeState::run(const g1s_frame_t &in, uint32_t bit_depth, uint32_t out_w, 
     err = "resize: unsupported sample format";
     return G1S_ERR_UNSUPPORTED;
   }
+  if (out_w > 65535u || out_h > 65535u) {  // (what the filter parser refuses, for a caller that comes without it)
+    err = "resize: target larger than 65535 x 65535";
+    return G1S_ERR_INVALID;
+  }
   if (in.nplanes == 3 && ((out_w & ((1u << in.xdec) - 1u)) || (out_h & ((1u << in.ydec) - 1u)))) {
     err = "resize: width and height must be multiples of the chroma subsampling";
     return G1S_ERR_INVALID;

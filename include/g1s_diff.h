@@ -126,7 +126,16 @@ const char *g1s_last_global_error(void);
  * the fastest kernels, the others give the same table.  Refused for either frame and any plane, with G1S_ERR_INVALID
  * and the frame and plane in g1s_diff_last_error, before anything is copied or queued: a null plane pointer, a stride
  * smaller than the plane's row in bytes, an odd stride under 2-byte samples, a stride above 0xffffffff.  The refusal is
- * sticky (the job has lost a frame): every later call returns it. */
+ * sticky (the job has lost a frame): every later call returns it.
+ * Limits of what the kernels address, refused the same way (same code, same stickiness, the limit named in the text):
+ *   size    a frame is at most 131 072 x 131 072 luma samples (4 096 blocks of 32 a side: the unit lists of the
+ *           accumulation kernels pack a block's column and row into 12-bit fields).  131 073 either way is refused.
+ *   stride  a row stride is at most 119 304 647 bytes (0xffffffff / 36: the kernels form row x stride in 32 bits for the 36
+ *           rows of a block's tile with its halo), however few rows the plane has.
+ *   extent  the bytes from a plane's first sample to its last, stride_bytes x (rows - 1) + the row's bytes, computed
+ *           in 64 bits for every plane that is read, are at most 2^32 - 1.  Planes of up to 2^31 - 1 bytes run either
+ *           chain of kernels; a batch that holds a device plane of 2^31 bytes or more runs the stream chain (same
+ *           table, slower); 2^32 or more is refused.  Host frames are judged by the stride they are handed over with. */
 int g1s_diff_frame(g1s_diff_t *, const g1s_frame_t *source, const g1s_frame_t *denoised);
 /* n frame pairs in one call (same semantics as n diff_frame calls). */
 int g1s_diff_frames(g1s_diff_t *, const g1s_frame_t *source, const g1s_frame_t *denoised, size_t n);
@@ -329,7 +338,9 @@ int g1s_filters_has_resize(const g1s_filters_t *);
 /* The taps of one axis of a resize (test / documentation aid): output i = sum over k < *taps of coef[i * taps + k] *
  * in[idx[i * taps + k]], k ascending, in f32 without fused multiply-adds; cap = entries idx / coef hold (dst * taps). */
 int g1s_resize_plan(const char *alg, uint32_t src, uint32_t dst, uint32_t *taps, int32_t *idx, float *coef, size_t cap);
-/* One frame (host or device planes) through the device resize, result into host planes (tests, the Python FilterChain). */
+/* One frame (host or device planes) through the device resize, result into host planes (tests, the Python FilterChain).
+ * A target above 65535 x 65535 is refused here as the filter parser refuses it (G1S_ERR_INVALID, the same text); a source
+ * has no limit of its own: any width and height the frame's uint32_t fields and the device's memory hold. */
 int g1s_resize_frame_to_host(const char *alg, const g1s_frame_t *in, uint32_t bit_depth, uint32_t out_w, uint32_t out_h,
                              int32_t device, void *const out_planes[3], const size_t out_stride_bytes[3], char *err, size_t errcap);
 void g1s_filters_free(g1s_filters_t *);

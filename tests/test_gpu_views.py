@@ -379,7 +379,10 @@ REFUSALS = {
     "odd_stride_16bit": lambda f, c, row: f.stride_bytes.__setitem__(c, row + 17),
     "stride_above_32_bits": lambda f, c, row: f.stride_bytes.__setitem__(c, (1 << 32) + 64),
     "null_plane": lambda f, c, row: f.data.__setitem__(c, None),
+    # the smallest even stride that puts the end of the plane's last row (192 luma, 96 chroma rows) 2^32 bytes from its first sample
+    "extent_of_4_gib": lambda f, c, row: f.stride_bytes.__setitem__(c, (-(-((1 << 32) - row) // ((96 if c else 192) - 1)) + 1) & ~1),
 }
+REFUSAL_TEXT = {"extent_of_4_gib": "the plane's extent (row stride x (rows - 1) + a row) is 4 GiB or more"}
 
 
 @pytest.mark.parametrize("on_device", [1, 0], ids=["device", "host"])
@@ -405,7 +408,7 @@ def test_diff_frame_refuses_a_bad_plane_pointer_or_stride(what, side, c, on_devi
     try:
         assert L.g1s_diff_frame(g._h, C.byref(fs), C.byref(fd)) == -1  # G1S_ERR_INVALID
         msg = L.g1s_diff_last_error(g._h).decode()
-        assert msg == f"{SIDES[side]} frame, plane {c}: bad plane pointer or row stride"
+        assert msg == f"{SIDES[side]} frame, plane {c}: " + REFUSAL_TEXT.get(what, "bad plane pointer or row stride")
         assert g.stats().frames == 0
         fs2, fd2 = Frame(s, 1, 1).to_c(keep), Frame(d, 1, 1).to_c(keep)
         assert L.g1s_diff_frame(g._h, C.byref(fs2), C.byref(fd2)) == -1, "the refusal is sticky"

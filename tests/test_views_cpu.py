@@ -3,7 +3,7 @@ may be; the arithmetic of the alternating job of tests/test_gpu_views.py."""
 import numpy as np
 import pytest
 
-from tests.views import device_view
+from tests.views import GAP, device_view, far_view
 
 
 @pytest.mark.parametrize("dtype,top", [(np.uint8, 255), (np.uint16, 1023)])
@@ -43,3 +43,26 @@ def test_alternating_job_takes_every_slot_through_both_chains():
     from tests.test_gpu_views import alternation_covers_every_slot
 
     assert alternation_covers_every_slot()
+
+
+@pytest.mark.parametrize("dtype,top,off", [(np.uint8, 255, 0), (np.uint16, 4095, 48)])
+def test_far_view_places_every_row_by_its_pitch_and_guards_both_ends_of_the_gap(dtype, top, off):
+    """The builder of the gigabyte pitches at a pitch a host can hold: 1 MiB + 16."""
+    plane = (np.arange(5 * 21).reshape(5, 21) * 37 % (top + 1)).astype(dtype)
+    pitch = (1 << 20) + 16
+    v, g = far_view(plane, pitch_bytes=pitch, base_offset_bytes=off, max_code=top, device="cpu")
+    assert v.data_ptr() % 256 == off and v.stride(0) * v.element_size() == pitch and np.array_equal(v.numpy(), plane)
+    assert v[4:].data_ptr() - v.data_ptr() == 4 * pitch
+    g.assert_unchanged("fresh")
+    row = 21 * plane.itemsize
+    lead = v.data_ptr() - g.buffer.data_ptr()
+    assert g.buffer[lead + row + GAP] == 0xA5 and len(set(g.buffer[lead + row:lead + row + GAP].tolist())) > 16
+    v[2, 3] ^= 1
+    g.assert_margin_intact("inside")
+    with pytest.raises(AssertionError):
+        g.assert_unchanged("inside")
+    g.buffer[lead + 3 * pitch - 1] ^= 1        # the last byte in front of row 3
+    with pytest.raises(AssertionError):
+        g.assert_margin_intact("margin")
+    with pytest.raises(ValueError):
+        far_view(plane, pitch_bytes=row + GAP, base_offset_bytes=0, device="cpu")

@@ -92,3 +92,70 @@ def contiguous(plane: np.ndarray, device: str = "cuda"):
     import torch
 
     return torch.from_numpy(np.ascontiguousarray(plane)).to(device)
+
+
+# ---- views with a pitch of megabytes: gigabytes from the first row to the last ---------------------------------------------
+
+GAP = 4096  # bytes behind every row and in front of the next one that hold hostile samples and are looked at afterwards
+
+
+class FarGuard:
+    """What far_view built around a plane: the rows, and of the gap between two rows the first and the last GAP bytes (random
+    samples; the rest of the gap is one byte value and is not looked at: it is gigabytes)."""
+
+    def __init__(self, buffer, spans):
+        self.buffer, self._spans = buffer, spans  # spans: (offset, host bytes, inside the view?)
+
+    def _changed(self, inside_too: bool):
+        out = []
+        for o, host, inside in self._spans:
+            if inside and not inside_too:
+                continue
+            now = self.buffer[o:o + host.size].cpu().numpy()
+            out += [o + int(k) for k in np.flatnonzero(now != host)]
+        return out
+
+    def assert_unchanged(self, what: str) -> None:
+        bad = self._changed(True)
+        assert not bad, f"{what}: {len(bad)} bytes of an input buffer were written, first at offset {bad[0]}"
+
+    def assert_margin_intact(self, what: str) -> None:
+        bad = self._changed(False)
+        assert not bad, f"{what}: {len(bad)} bytes outside the view were written, first at offset {bad[0]}"
+
+
+def far_view(plane: np.ndarray, *, pitch_bytes: int, base_offset_bytes: int, max_code: int = 0, seed: int = 0, device: str = "cuda"):
+    """(view, guard) as device_view gives them, for a pitch so large that the buffer cannot be built on the host: one device
+    allocation of (rows + 1) * pitch_bytes, filled with the byte 0xA5 on the device; the rows, and GAP bytes of random samples
+    (0 .. max_code) on either side of every row, written one by one at offsets computed here in python integers, so that
+    nothing of the placement depends on anybody's 32-bit arithmetic."""
+    import torch
+
+    plane = np.ascontiguousarray(plane)
+    h, w = plane.shape
+    isz = plane.dtype.itemsize
+    row = w * isz
+    if isz not in (1, 2) or pitch_bytes < row + 2 * GAP or pitch_bytes % isz or base_offset_bytes % isz or not 0 <= base_offset_bytes < ALIGN:
+        raise ValueError(f"no far view of a {w}-sample row of {isz}-byte samples with pitch {pitch_bytes} at offset {base_offset_bytes}")
+    top = max_code or (1 << (8 * isz)) - 1
+    lead = GAP + ALIGN
+    total = lead + (h - 1) * pitch_bytes + row + GAP
+    raw = torch.empty(total + ALIGN, dtype=torch.uint8, device=device)
+    skip = (base_offset_bytes - raw.data_ptr() - lead) % ALIGN
+    buffer = raw[skip:skip + total]
+    buffer.fill_(0xA5)
+    rng = np.random.default_rng([seed, h, w, pitch_bytes])
+    spans = []
+    for r in range(h):
+        o = lead + r * pitch_bytes
+        piece = np.concatenate([rng.integers(0, top + 1, GAP // isz).astype(plane.dtype), plane[r], rng.integers(0, top + 1, GAP // isz).astype(plane.dtype)])
+        buffer[o - GAP:o + row + GAP].copy_(torch.from_numpy(piece.view(np.uint8)))
+        b = piece.view(np.uint8)
+        spans += [(o - GAP, b[:GAP].copy(), False), (o, b[GAP:GAP + row].copy(), True), (o + row, b[GAP + row:].copy(), False)]
+    body = buffer[lead:lead + (h - 1) * pitch_bytes + row]
+    if isz == 2:
+        body = body.view(torch.uint16)
+    view = body.as_strided((h, w), (pitch_bytes // isz, 1))
+    assert view.data_ptr() % ALIGN == base_offset_bytes and view.data_ptr() - buffer.data_ptr() == lead
+    assert view.stride(1) == 1 and view.stride(0) * view.element_size() == pitch_bytes
+    return view, FarGuard(buffer, spans)
