@@ -27,7 +27,6 @@
 #include "denoise_tile.hip.h"
 #include "frame_op.h"
 
-extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
 extern "C" void g1s_diff_set_error_text_(g1s_diff_t *, const char *);
 extern "C" int32_t g1s_diff_device_(const g1s_diff_t *);
 extern "C" uint32_t g1s_diff_frames_in_flight_max_(const g1s_diff_t *);

@@ -1,4 +1,6 @@
-// engine.hip -- host engine + C-ABI of libg1s_diff.so (see include/g1s_diff.h).
+// engine.hip -- the generator: host engine + the part of libg1s_diff.so's C ABI (include/g1s_diff.h) that takes a
+// g1s_diff_t *.  The ABI that needs no device (records, fold handle, shard messages, .tbl) is host_abi.cpp; the worker
+// pools are host_pool.h.
 //
 // Frames are queued into a slot of `batch_frames` pairs; a full slot is one
 // K1 -> K2 -> K3 launch group on the engine's HIP stream followed by one D2H
@@ -15,9 +17,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
-#include <iterator>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -28,6 +28,7 @@
 #include "../../include/g1s_diff.h"
 #include "fold.h"
 #include "frame_op.h"
+#include "host_pool.h"
 #include "kernels.hip.h"
 #include "k1f.hip.h"
 #include "k3m.hip.h"
@@ -43,8 +44,6 @@ using g1s_op::Event;
 using g1s_op::PinnedBuf;
 
 namespace {
-
-thread_local std::string g_global_error;
 
 constexpr uint32_t kDefaultBatch = 32;
 constexpr int kK3Chunks = 48;
@@ -137,132 +136,6 @@ int w_wgs_per_frame(int ncell, int B, int kind) {
       return fail_hip(b_);                                                                 \
     }                                                                                      \
   } while (0)
-
-// Minimal persistent worker pool: the per-frame half of the fold (AR solve,
-// block measurements, strength solve) is independent across frames.
-class Pool {
- public:
-  explicit Pool(unsigned n) {
-    for (unsigned i = 0; i < n; ++i) workers_.emplace_back([this] { loop(); });
-  }
-  ~Pool() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto &t : workers_) t.join();
-  }
-  // runs fn(i) for i in [0, n); the caller participates.  Every call has its own job object (function, count, claim and
-  // completion counters): a worker that comes late to an earlier job holds THAT job, finds it exhausted and goes back to
-  // sleep -- it can never claim an index of a newer job or run the newer function with an older count.
-  void parallel_for(int n, const std::function<void(int)> &fn) {
-    if (n <= 0) return;
-    auto job = std::make_shared<Job>();
-    job->fn = &fn;
-    job->n = n;
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      job_ = job;
-      ++epoch_;
-    }
-    cv_.notify_all();
-    work(*job);
-    std::unique_lock<std::mutex> lk(m_);
-    cv_done_.wait(lk, [&] { return job->done.load() == job->n; });
-    if (job_ == job) job_.reset();
-  }
-
- private:
-  struct Job {
-    const std::function<void(int)> *fn = nullptr;
-    int n = 0;
-    std::atomic<int> next{0}, done{0};
-  };
-  void work(Job &job) {
-    int mine = 0;
-    for (;;) {
-      const int i = job.next.fetch_add(1);
-      if (i >= job.n) break;
-      (*job.fn)(i);  // (fn outlives the job: parallel_for returns only when done == n)
-      ++mine;
-    }
-    if (mine && job.done.fetch_add(mine) + mine == job.n) {
-      std::lock_guard<std::mutex> lk(m_);  // (the waiter checks under this lock: no lost wake-up)
-      cv_done_.notify_all();
-    }
-  }
-  void loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      std::shared_ptr<Job> job;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&] { return stop_ || epoch_ != seen; });
-        if (stop_) return;
-        seen = epoch_;
-        job = job_;
-      }
-      if (job) work(*job);
-    }
-  }
-  std::vector<std::thread> workers_;
-  std::mutex m_;
-  std::condition_variable cv_, cv_done_;
-  std::shared_ptr<Job> job_;
-  uint64_t epoch_ = 0;
-  bool stop_ = false;
-};
-
-// The cores this process may really use: the hardware threads, cut to the cgroup's CPU quota where there is one (a 1-GPU box
-// of the pool this was measured on shows 256 hardware threads and `cpu.max` = 16 cores: 32 pool threads there do 80 k frames/s
-// of the per-frame half where 16 do 95 k -- the quota's throttling stops every thread of the group, the launching one included;
-// profiles/r04_host_budget_8ranks.txt).
-unsigned usable_cpus() {
-  unsigned hw = std::thread::hardware_concurrency();
-  if (!hw) hw = 1;
-  long long quota = -1, period = 100000;
-  if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "<quota|max> <period>"
-    char q[32] = {0};
-    if (fscanf(f, "%31s %lld", q, &period) == 2 && strcmp(q, "max") != 0) quota = atoll(q);
-    fclose(f);
-  } else if (FILE *f1 = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {  // cgroup v1
-    if (fscanf(f1, "%lld", &quota) != 1) quota = -1;
-    fclose(f1);
-    if (FILE *f2 = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
-      if (fscanf(f2, "%lld", &period) != 1) period = 100000;
-      fclose(f2);
-    }
-  }
-  if (quota > 0 && period > 0) hw = std::min<unsigned>(hw, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
-  return hw;
-}
-
-// One pool per process (creating 30 threads per generator would dominate short jobs).
-Pool *shared_pool() {
-  static Pool *p = [] {
-    unsigned hw = usable_cpus();
-    if (const char *e = getenv("G1S_FOLD_THREADS")) hw = (unsigned)atoi(e);
-    if (hw > 32) hw = 32;
-    return hw > 1 ? new Pool(hw - 1) : nullptr;  // the calling thread participates
-  }();
-  return p;
-}
-std::mutex g_pool_mutex;  // parallel_for is not re-entrant: one fold batch at a time
-// The ordered merge of exchanged latest states (rank 0 of a frame-shard job) has a small pool of its own:
-// on that rank the shared pool is busy half of the time with the per-frame half of the rank's own batches,
-// and a merge that waits for it falls behind the eight GPUs it serves.
-Pool *merge_pool() {
-  static Pool *p = [] {
-    unsigned hw = usable_cpus();
-    if (const char *e = getenv("G1S_FOLD_THREADS")) hw = (unsigned)atoi(e);
-    unsigned n = std::min(8u, hw / 2);  // (8: 1.5 - 1.6 us a frame, steady; 16 reaches 1.0 but swings to 2 - 8 on a busy host: profiles/r03_fold_budget.txt)
-    if (const char *e = getenv("G1S_MERGE_POOL")) n = (unsigned)atoi(e);  // (measurement: the pool's size itself)
-    return n > 1 ? new Pool(n - 1) : nullptr;
-  }();
-  return p;
-}
-std::mutex g_merge_pool_mutex;
 
 // G1S_LATEST unset: the per-frame half of the fold runs on the device for frames of this many blocks or more.  The device half's solves
 // cost the same whatever the frame's size and the host half's cost goes with the blocks: same box, 1080p (2 040 blocks) the host half
@@ -494,13 +367,12 @@ struct g1s_diff {
   uint64_t frames_released = 0;         // frame pairs of the drained batches (their inputs are no longer read)
   // asynchronous host -> device copies of pinned frames (on_device == 2): one event per frame pair, in order
   std::mutex h2d_mutex;
-  std::deque<std::pair<uint64_t, hipEvent_t>> h2d_pending;  // (frame pairs handed over up to and including this one, copies done)
-  std::vector<hipEvent_t> h2d_free;
+  std::deque<std::pair<uint64_t, Event>> h2d_pending;  // (frame pairs handed over up to and including this one, copies done)
+  std::vector<Event> h2d_free;
   uint64_t frames_appended = 0;
-  hipEvent_t h2d_order = nullptr;  // copies -> table upload when the two run on different streams
+  Event h2d_order;  // copies -> table upload when the two run on different streams
   bool drainer_stop = false;
   NoiseFold *fold = nullptr;
-  Pool *pool = nullptr;
   std::vector<uint8_t> records_out;
   size_t records_out_frames = 0;
   std::vector<uint8_t> latest_out;  // latest_only: blobs of the drained frames, in frame order
@@ -540,7 +412,7 @@ struct g1s_diff {
   // G1S_TRACE=file (a measurement aid): the PIPELINED job's own timeline -- an event in front of every launch on the stream it
   // is launched on (its end = the next event of that stream), the host's time at every submit; written at finish
   bool trace = false;
-  hipEvent_t trace_base = nullptr;
+  Event trace_base;
   std::chrono::steady_clock::time_point trace_host0;
   std::vector<std::string> trace_lines;
   std::mutex trace_mutex;
@@ -836,15 +708,15 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
     std::lock_guard<std::mutex> lk(h2d_mutex);
     ++frames_appended;
     if (any_async) {
-      hipEvent_t e;
+      Event e;
       if (!h2d_free.empty()) {
-        e = h2d_free.back();
+        e = std::move(h2d_free.back());
         h2d_free.pop_back();
       } else {
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&e.p, hipEventDisableTiming));
       }
       HIP_TRY(hipEventRecord(e, ss.upload ? ss.upload : stream));
-      h2d_pending.emplace_back(frames_appended, e);
+      h2d_pending.emplace_back(frames_appended, std::move(e));
       sl.async_in = true;
     }
   }
@@ -859,10 +731,10 @@ uint64_t g1s_diff::frames_copied(uint64_t wait_for) {
   std::lock_guard<std::mutex> lk(h2d_mutex);
   wait_for = std::min(wait_for, frames_appended);
   while (!h2d_pending.empty()) {
-    const auto front = h2d_pending.front();
+    auto &front = h2d_pending.front();
     if (front.first <= wait_for) (void)hipEventSynchronize(front.second);
     else if (hipEventQuery(front.second) != hipSuccess) break;
-    h2d_free.push_back(front.second);
+    h2d_free.push_back(std::move(front.second));
     h2d_pending.pop_front();
   }
   return h2d_pending.empty() ? frames_appended : h2d_pending.front().first - 1;
@@ -981,7 +853,7 @@ int g1s_diff::launch_front(int si) {
   if (sl.async_in) {  // queued frame copies: on the upload stream; everything below waits for `up`
     hipStream_t cs = ss.upload ? ss.upload : stream;
     if (cs != up) {
-      if (!h2d_order) HIP_TRY(hipEventCreateWithFlags(&h2d_order, hipEventDisableTiming));
+      if (!h2d_order) HIP_TRY(hipEventCreateWithFlags(&h2d_order.p, hipEventDisableTiming));
       HIP_TRY(hipEventRecord(h2d_order, cs));
       HIP_TRY(hipStreamWaitEvent(up, h2d_order, 0));
     }
@@ -1502,18 +1374,7 @@ int g1s_diff::drain_front(int si) {
   if (latest_only) latest_stage.resize(blob * sl.count);
   auto finish_record = [&](int i) {
     uint8_t *rec = sl.h_records + L.size * i;
-    RecHeader h{};
-    h.magic = kRecMagic;
-    h.lag = lag;
-    h.width = shape.width;
-    h.height = shape.height;
-    h.xdec = shape.xdec;
-    h.ydec = shape.ydec;
-    h.nplanes = (uint32_t)geom.nplanes;
-    h.nbw = (uint32_t)geom.nbw;
-    h.nbh = (uint32_t)geom.nbh;
-    h.n = n;
-    h.size_bytes = L.size;
+    RecHeader h = make_header(L, shape.width, shape.height, shape.xdec, shape.ydec, lag);
     const uint8_t *mask = rec + L.off_mask;
     uint32_t nflat = 0;
     for (uint32_t b = 0; b < L.nblocks; ++b) nflat += mask[b] != 0;
@@ -1556,12 +1417,7 @@ int g1s_diff::drain_front(int si) {
     if (!records_only) compute_latest(rec, L.size, lag, latest[i]);
     if (latest_only) latest_to_blob(latest[i], lag, latest_stage.data() + (size_t)i * blob);
   };
-  if (pool && sl.count > 1) {
-    std::lock_guard<std::mutex> lk(g_pool_mutex);
-    pool->parallel_for((int)sl.count, per_frame);
-  } else {
-    for (uint32_t i = 0; i < sl.count; ++i) per_frame((int)i);
-  }
+  on_shared_pool((int)sl.count, per_frame);
   ms_fold_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return G1S_OK;
 }
@@ -1596,16 +1452,8 @@ int g1s_diff::drain_back(int si) {
   }
   if (!records_only && !latest_only && sticky == G1S_OK && sl.count) {
     // the ordered merge of the batch: combined-model solves in parallel, tests and commits in order
-    Pool *mp = merge_pool();  // (the shared pool is busy with the next batch's per-frame half)
-    const NoiseFold::ParallelFor pfor = [&](int m, const std::function<void(int)> &fn) {
-      if (mp) {
-        std::lock_guard<std::mutex> lk(g_merge_pool_mutex);
-        mp->parallel_for(m, fn);
-      } else {
-        for (int i = 0; i < m; ++i) fn(i);
-      }
-    };
-    rc = device_latest ? fold->push_latest_many(views_s[si].data(), sl.count, pfor) : fold->push_latest_many(latest.data(), sl.count, pfor);
+    // (on the merge pool: the shared pool is busy with the next batch's per-frame half)
+    rc = device_latest ? fold->push_latest_many(views_s[si].data(), sl.count, on_merge_pool) : fold->push_latest_many(latest.data(), sl.count, on_merge_pool);
     if (rc) {
       std::lock_guard<std::mutex> lk(dm);
       err = fold->error();
@@ -1679,47 +1527,32 @@ void g1s_diff::release() {
     }
     sl = Slot{};  // (frees what the slot holds)
   }
-  for (auto &pe : h2d_pending) (void)hipEventDestroy(pe.second);
-  h2d_pending.clear();
-  for (auto &e : h2d_free) (void)hipEventDestroy(e);
-  h2d_free.clear();
-  if (h2d_order) (void)hipEventDestroy(h2d_order);
-  h2d_order = nullptr;
+  h2d_pending.clear(), h2d_free.clear(), h2d_order = Event{}, trace_base = Event{};  // (the streams are idle)
   d_lut = nullptr;  // shared per device
   stream = nullptr;
   delete fold;
   fold = nullptr;
-  pool = nullptr;  // shared
 }
 
 // =============================================================== C ABI =====
 extern "C" {
 
-const char *g1s_last_global_error(void) { return g_global_error.c_str(); }
-// (grain.hip) g1s_grain_new reports through the same thread-local text
-void g1s_set_global_error_(const char *text) { g_global_error = text ? text : ""; }
-
 g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_depth,
                          uint32_t denoised_bit_depth, const g1s_opts_t *opts) {
-  g_global_error.clear();
-  if (fps_num <= 0 || fps_den <= 0) {
-    g_global_error = "frame rate must be positive";
+  g1s_set_global_error_("");
+  auto refuse = [](const char *why) -> g1s_diff * {
+    g1s_set_global_error_(why);
     return nullptr;
-  }
+  };
+  if (fps_num <= 0 || fps_den <= 0) return refuse("frame rate must be positive");
   // src/main.rs:515-517: "Bit depths not between 8-16 are not currently supported"
-  if (source_bit_depth < 8 || source_bit_depth > 16 || denoised_bit_depth < 8 || denoised_bit_depth > 16) {
-    g_global_error = "Bit depths not between 8-16 are not currently supported";
-    return nullptr;
-  }
+  if (source_bit_depth < 8 || source_bit_depth > 16 || denoised_bit_depth < 8 || denoised_bit_depth > 16) return refuse("Bit depths not between 8-16 are not currently supported");
   uint32_t lag = 3, batch = kDefaultBatch;
   bool batch_auto = true;
   bool luma_only = false, records_only = false, latest_only = false;
   int device = -1;
   if (opts) {
-    if (opts->struct_size != sizeof(g1s_opts_t)) {
-      g_global_error = "g1s_opts_t.struct_size mismatch";
-      return nullptr;
-    }
+    if (opts->struct_size != sizeof(g1s_opts_t)) return refuse("g1s_opts_t.struct_size mismatch");
     if (opts->ar_coeff_lag) lag = opts->ar_coeff_lag;
     if (opts->batch_frames) {
       batch = std::min<uint32_t>(opts->batch_frames, (uint32_t)kMaxBatch);
@@ -1730,23 +1563,13 @@ g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_d
     latest_only = opts->records_only == 2;
     device = opts->device;
   }
-  if (lag < 1 || lag > 3) {
-    g_global_error = "ar_coeff_lag must be 1..3";
-    return nullptr;
-  }
+  if (lag < 1 || lag > 3) return refuse("ar_coeff_lag must be 1..3");
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    g_global_error = "no HIP device available: the diff estimator has no CPU fallback";
-    return nullptr;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return refuse("no HIP device available: the diff estimator has no CPU fallback");
   if (device >= 0) {
-    if (hipSetDevice(device) != hipSuccess) {
-      g_global_error = "hipSetDevice failed";
-      return nullptr;
-    }
+    if (hipSetDevice(device) != hipSuccess) return refuse("hipSetDevice failed");
   } else if (hipGetDevice(&device) != hipSuccess) {
-    g_global_error = "hipGetDevice failed";
-    return nullptr;
+    return refuse("hipGetDevice failed");
   }
   g1s_diff *g = new g1s_diff();
   g->fps_num = fps_num;
@@ -1789,15 +1612,14 @@ g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_d
     g->d_lut = lut_dev[di];
   }
   if (!streams_ok) {
-    g_global_error = std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError());
+    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
     g->release();
     delete g;
     return nullptr;
   }
   if (!records_only && !latest_only) g->fold = new NoiseFold(fps_num, fps_den, lag);
-  g->pool = shared_pool();
   if (getenv("G1S_TRACE")) {
-    g->trace = hipEventCreate(&g->trace_base) == hipSuccess && hipEventRecord(g->trace_base, g->ss.compute) == hipSuccess &&
+    g->trace = hipEventCreate(&g->trace_base.p) == hipSuccess && hipEventRecord(g->trace_base, g->ss.compute) == hipSuccess &&
                hipEventSynchronize(g->trace_base) == hipSuccess;
     g->trace_host0 = std::chrono::steady_clock::now();
   }
@@ -1862,11 +1684,8 @@ int g1s_diff_finish(g1s_diff_t *g, g1s_segment_t *out, size_t cap, size_t *n_out
     g->fold->finish(g->final_segs);
     g->finished = true;  // no more frames
   }
-  const std::vector<g1s_segment_t> &segs = g->final_segs;
-  if (n_out) *n_out = segs.size();
-  if (segs.size() > cap || (!out && !segs.empty())) return g->fail(G1S_ERR_CAPACITY, "segment buffer too small");
-  if (!segs.empty()) std::memcpy(out, segs.data(), sizeof(g1s_segment_t) * segs.size());
-  return G1S_OK;
+  const int rc = copy_segments(g->final_segs, out, cap, n_out);
+  return rc ? g->fail(rc, kSegmentsTooSmall) : G1S_OK;
 }
 
 void g1s_diff_free(g1s_diff_t *g) {
@@ -1884,35 +1703,6 @@ int32_t g1s_diff_device_(const g1s_diff_t *g) { return g ? g->device : -1; }
 uint32_t g1s_diff_frames_in_flight_max_(const g1s_diff_t *g) { return g && g->shape.width ? (uint32_t)kSlots * g->batch : 0; }
 void g1s_diff_set_error_text_(g1s_diff_t *g, const char *msg) {
   if (g && msg) g->err = msg;
-}
-
-size_t g1s_record_size(uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes,
-                       uint32_t lag) {
-  (void)xdec;
-  (void)ydec;
-  return make_layout(width, height, nplanes, lag).size;
-}
-
-int g1s_record_init(void *rec, size_t cap_bytes, uint32_t width, uint32_t height, uint32_t xdec,
-                    uint32_t ydec, uint32_t nplanes, uint32_t lag) {
-  if (!rec || lag < 1 || lag > 3 || (nplanes != 1 && nplanes != 3)) return G1S_ERR_INVALID;
-  const RecLayout L = make_layout(width, height, nplanes, lag);
-  if (L.size > cap_bytes) return G1S_ERR_CAPACITY;
-  std::memset(rec, 0, L.size);
-  RecHeader h{};
-  h.magic = kRecMagic;
-  h.lag = lag;
-  h.width = width;
-  h.height = height;
-  h.xdec = xdec;
-  h.ydec = ydec;
-  h.nplanes = nplanes;
-  h.nbw = (width + kBlock - 1) / kBlock;
-  h.nbh = (height + kBlock - 1) / kBlock;
-  h.n = num_coeffs(lag);
-  h.size_bytes = L.size;
-  std::memcpy(rec, &h, sizeof(h));
-  return G1S_OK;
 }
 
 int g1s_diff_take_records(g1s_diff_t *g, void *buf, size_t cap_bytes, size_t *n_frames) {
@@ -1964,38 +1754,7 @@ int g1s_diff_take_latest(g1s_diff_t *g, int sync, void *buf, size_t cap_bytes, s
   return G1S_OK;
 }
 
-// ---- frame-shard rounds: the exchange protocol (what goes into a round's message, which batch, in which order the root
-//      merges) lives here; the transport (RCCL / MPI / torch.distributed gather of fixed-size buffers) stays with the host
-namespace {
-constexpr uint32_t kShardMagic = 0x4d315347u;  // "GS1M"
-constexpr uint32_t kShardNoIndex = 0xffffffffu;  // a message without a batch index: merged in arrival order
-struct ShardHeader {
-  uint32_t magic, count, lag, batch_frames;
-  // which of the SENDING rank's batches this is (0, 1, ...): global batch = local_batch * world + rank.  The root merges
-  // by this index, not by arrival: ranks that have fed different numbers of batches (an idle rank in a short last round)
-  // send different local batches in the same round
-  uint32_t local_batch, reserved;
-};
-}  // namespace
-size_t g1s_shard_msg_size(uint32_t ar_coeff_lag, uint32_t batch_frames) {
-  return ar_coeff_lag >= 1 && ar_coeff_lag <= 3 ? sizeof(ShardHeader) + (size_t)batch_frames * latest_blob_size(ar_coeff_lag) : 0;
-}
-int g1s_shard_msg_from_latest_at(const void *blobs, size_t n, uint32_t ar_coeff_lag, uint32_t batch_frames, uint64_t local_batch,
-                                 void *msg, size_t cap_bytes) {
-  if (!msg || (!blobs && n) || ar_coeff_lag < 1 || ar_coeff_lag > 3 || n > batch_frames) return G1S_ERR_INVALID;
-  if (local_batch != G1S_SHARD_NO_INDEX && local_batch >= kShardNoIndex) return G1S_ERR_INVALID;
-  const size_t total = g1s_shard_msg_size(ar_coeff_lag, batch_frames), bs = latest_blob_size(ar_coeff_lag);
-  if (cap_bytes < total) return G1S_ERR_CAPACITY;
-  std::memset(msg, 0, total);
-  const ShardHeader h{kShardMagic, (uint32_t)n, ar_coeff_lag, batch_frames,
-                      local_batch == G1S_SHARD_NO_INDEX ? kShardNoIndex : (uint32_t)local_batch, 0u};
-  std::memcpy(msg, &h, sizeof(h));
-  if (n) std::memcpy((uint8_t *)msg + sizeof(h), blobs, n * bs);
-  return G1S_OK;
-}
-int g1s_shard_msg_from_latest(const void *blobs, size_t n, uint32_t ar_coeff_lag, uint32_t batch_frames, void *msg, size_t cap_bytes) {
-  return g1s_shard_msg_from_latest_at(blobs, n, ar_coeff_lag, batch_frames, G1S_SHARD_NO_INDEX, msg, cap_bytes);
-}
+// ---- frame-shard rounds: a rank's side of the exchange (the messages and the root's merge: host_abi.cpp)
 int g1s_shard_pack(g1s_diff_t *g, int flush, void *msg, size_t cap_bytes) {
   if (!g || !msg) return G1S_ERR_INVALID;
   if (!g->latest_only) return g->fail(G1S_ERR_STATE, "not a latest_only generator (records_only = 2)");
@@ -2029,310 +1788,6 @@ int g1s_shard_pack(g1s_diff_t *g, int flush, void *msg, size_t cap_bytes) {
 }
 
 unsigned g1s_shard_flush_rounds(void) { return (unsigned)kSlots; }
-
-size_t g1s_latest_size(uint32_t ar_coeff_lag) { return ar_coeff_lag >= 1 && ar_coeff_lag <= 3 ? latest_blob_size(ar_coeff_lag) : 0; }
-
-int g1s_latest_from_record(const void *record, size_t size_bytes, uint32_t ar_coeff_lag, void *blob, size_t cap_bytes) {
-  if (!record || !blob || ar_coeff_lag < 1 || ar_coeff_lag > 3) return G1S_ERR_INVALID;
-  if (cap_bytes < latest_blob_size(ar_coeff_lag)) return G1S_ERR_CAPACITY;
-  FrameLatest fl;
-  compute_latest((const uint8_t *)record, size_bytes, ar_coeff_lag, fl);  // a failure travels inside the blob
-  latest_to_blob(fl, ar_coeff_lag, (uint8_t *)blob);
-  return G1S_OK;
-}
-
-// The per-frame half of a batch of records on the process' per-frame pool (G1S_FOLD_THREADS; the calling thread takes part):
-// what a generator's drainer does with a batch, as a call of its own -- a host that runs the half next to a foreign transport,
-// and tools/host_budget_8ranks.py, which replays eight ranks' worth of it.
-int g1s_latest_from_records(const void *records, size_t stride_bytes, size_t n, uint32_t ar_coeff_lag, void *blobs, size_t blob_stride_bytes) {
-  if ((!records || !blobs) && n) return G1S_ERR_INVALID;
-  if (ar_coeff_lag < 1 || ar_coeff_lag > 3) return G1S_ERR_INVALID;
-  const size_t bs = latest_blob_size(ar_coeff_lag);
-  if (blob_stride_bytes < bs) return G1S_ERR_CAPACITY;
-  auto one = [&](int i) {
-    static thread_local FrameLatest fl;  // (kept per thread: its vectors are sized once, not once a frame)
-    compute_latest((const uint8_t *)records + (size_t)i * stride_bytes, stride_bytes, ar_coeff_lag, fl);
-    latest_to_blob(fl, ar_coeff_lag, (uint8_t *)blobs + (size_t)i * blob_stride_bytes);
-  };
-  Pool *p = shared_pool();
-  if (p && n > 1) {
-    std::lock_guard<std::mutex> lk(g_pool_mutex);
-    p->parallel_for((int)n, one);
-  } else {
-    for (size_t i = 0; i < n; ++i) one((int)i);
-  }
-  return G1S_OK;
-}
-
-unsigned g1s_usable_cpus(void) { return usable_cpus(); }
-
-struct g1s_fold {
-  NoiseFold fold;
-  uint32_t lag;
-  std::string err;
-  bool finished = false;
-  std::vector<g1s_segment_t> final_segs;  // what finish() returned (kept: a too-small buffer can be retried)
-  Pool *pool = nullptr;
-  std::vector<FrameLatest> latest;
-  std::vector<FrameView> views;  // g1s_fold_push_latest: the blobs of a pass, read in place
-  // g1s_shard_merge: indexed batches that arrived ahead of the next one in the global order (global batch -> its states)
-  std::map<uint64_t, std::vector<uint8_t>> early;
-  uint64_t next_batch = 0;
-  g1s_fold(int64_t a, int64_t b, uint32_t lag_) : fold(a, b, lag_), lag(lag_) {}
-};
-
-g1s_fold_t *g1s_fold_new(int64_t fps_num, int64_t fps_den, uint32_t lag) {
-  if (fps_num <= 0 || fps_den <= 0 || lag < 1 || lag > 3) return nullptr;
-  return new g1s_fold(fps_num, fps_den, lag);
-}
-int g1s_fold_push(g1s_fold_t *f, const void *record, size_t size_bytes) {
-  if (!f || !record) return G1S_ERR_INVALID;
-  if (f->finished) return G1S_ERR_STATE;
-  const int rc = f->fold.push((const uint8_t *)record, size_bytes);
-  if (rc) f->err = f->fold.error();
-  return rc;
-}
-int g1s_fold_push_many(g1s_fold_t *f, const void *records, size_t stride_bytes, size_t n) {
-  if (!f || (!records && n)) return G1S_ERR_INVALID;
-  if (f->finished) return G1S_ERR_STATE;
-  if (!f->pool) f->pool = shared_pool();
-  const uint8_t *base = (const uint8_t *)records;
-  const size_t chunk = 64;
-  for (size_t o = 0; o < n; o += chunk) {
-    const size_t m = std::min(chunk, n - o);
-    if (f->latest.size() < m) f->latest.resize(m);
-    auto one = [&](int i) { compute_latest(base + (o + i) * stride_bytes, stride_bytes, f->lag, f->latest[i]); };
-    if (f->pool && m > 1) {
-      std::lock_guard<std::mutex> lk(g_pool_mutex);
-      f->pool->parallel_for((int)m, one);
-    } else
-      for (size_t i = 0; i < m; ++i) one((int)i);
-    for (size_t i = 0; i < m; ++i) {
-      const int rc = f->fold.push_latest(f->latest[i]);
-      if (rc) {
-        f->err = f->fold.error();
-        return rc;
-      }
-    }
-  }
-  return G1S_OK;
-}
-// Runs of latest-state blobs, merged in the order given.  The frames of ALL runs are taken in windows of kChunk frames (the
-// solves of a window run on the merge pool, fold.cpp: push_latest_many): a round of a frame-shard job -- eight messages of
-// one batch each -- is merged as two windows of 256, not eight of 64 (the pool's hand-over per window is what a small
-// window pays: 3.8 -> 5.5 us a frame single-threaded at 64, profiles/r04_host_budget_8ranks.txt).
-struct BlobRun {
-  const uint8_t *base;
-  size_t stride, n;
-};
-static int fold_push_runs(g1s_fold_t *f, const BlobRun *runs, size_t nruns) {
-  if (f->finished) return G1S_ERR_STATE;
-  Pool *mp = merge_pool();
-  constexpr size_t kChunk = 256;  // frames parsed and merged per pass (bounds the staging memory)
-  const NoiseFold::ParallelFor pfor = [&](int m, const std::function<void(int)> &fn) {
-    if (mp && m > 1) {
-      std::lock_guard<std::mutex> lk(g_merge_pool_mutex);
-      mp->parallel_for(m, fn);
-    } else {
-      for (int i = 0; i < m; ++i) fn(i);
-    }
-  };
-  static struct ParseProfile {  // G1S_FOLD_PROFILE=1: the whole call next to the fold's own stage timers
-    bool on = getenv("G1S_FOLD_PROFILE") != nullptr;
-    double s = 0, all = 0;
-    size_t frames = 0;
-    ~ParseProfile() {
-      if (on && frames) fprintf(stderr, "ordered merge, us per frame: blob headers %.2f, whole call %.2f (%zu frames)\n", s * 1e6 / frames, all * 1e6 / frames, frames);
-    }
-  } pp;
-  if (f->views.size() < kChunk) f->views.resize(kChunk);
-  size_t run = 0, at = 0;  // the next frame to take: frame `at` of run `run`
-  for (;;) {
-    while (run < nruns && at == runs[run].n) {
-      ++run;
-      at = 0;
-    }
-    if (run == nruns) return G1S_OK;
-    const auto t_p0 = std::chrono::steady_clock::now();
-    size_t good = 0;
-    int bad_rc = G1S_OK;
-    while (good < kChunk && run < nruns) {
-      if (at == runs[run].n) {
-        ++run;
-        at = 0;
-        continue;
-      }
-      const BlobRun &R = runs[run];
-      const uint8_t *b = R.base + at * R.stride;
-      // The blobs are read where they lie (fold.h, FrameView); only a caller's unaligned buffer is copied first.
-      int rc;
-      if (!((reinterpret_cast<uintptr_t>(R.base) | R.stride) & 7)) {
-        rc = view_of_blob(b, R.stride, f->lag, f->views[good]);
-      } else {
-        if (f->latest.size() < kChunk) f->latest.resize(kChunk);
-        rc = latest_from_blob(b, R.stride, f->lag, f->latest[good]);
-        if (!rc) view_of(f->latest[good], f->views[good]);
-      }
-      if (rc) {
-        bad_rc = rc;
-        break;
-      }
-      ++good;
-      ++at;
-    }
-    const auto t_p1 = std::chrono::steady_clock::now();
-    const int rc = f->fold.push_latest_many(f->views.data(), good, pfor);  // (the frames before a bad blob still count)
-    if (pp.on) {
-      pp.s += std::chrono::duration<double>(t_p1 - t_p0).count();
-      pp.all += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_p0).count();
-      pp.frames += good;
-    }
-    if (rc) {
-      f->err = f->fold.error();
-      return rc;
-    }
-    if (bad_rc) {
-      f->err = "bad latest blob";
-      return bad_rc;
-    }
-  }
-}
-int g1s_fold_push_latest(g1s_fold_t *f, const void *blobs, size_t stride_bytes, size_t n) {
-  if (!f || (!blobs && n)) return G1S_ERR_INVALID;
-  const BlobRun r{(const uint8_t *)blobs, stride_bytes, n};
-  return fold_push_runs(f, &r, 1);
-}
-int g1s_fold_finish(g1s_fold_t *f, g1s_segment_t *out, size_t cap, size_t *n_out) {
-  if (!f) return G1S_ERR_INVALID;
-  if (!f->early.empty()) {  // (a caller that stopped before the flush rounds, or a rank that skipped a batch)
-    f->err = "frame-shard merge: batch " + std::to_string(f->next_batch) + " never arrived (" + std::to_string(f->early.size()) +
-             " later batch(es) are waiting for it)";
-    return G1S_ERR_STATE;
-  }
-  if (!f->finished) {
-    f->fold.finish(f->final_segs);
-    f->finished = true;  // no more records; the segments stay here, so a too-small buffer can be retried
-  }
-  const std::vector<g1s_segment_t> &segs = f->final_segs;
-  if (n_out) *n_out = segs.size();
-  if (segs.size() > cap || (!out && !segs.empty())) {
-    f->err = "segment buffer too small";
-    return G1S_ERR_CAPACITY;
-  }
-  if (!segs.empty()) std::memcpy(out, segs.data(), sizeof(g1s_segment_t) * segs.size());
-  return G1S_OK;
-}
-int g1s_shard_merge(g1s_fold_t *f, const void *msgs, size_t stride_bytes, uint32_t world) {
-  if (!f || !msgs || !world) return G1S_ERR_INVALID;
-  // Global frame order: batch j of the video went to rank j % world, and a message says which of its rank's batches it
-  // carries, so global batch = local_batch * world + rank.  Batches are merged strictly in that order; one that arrives
-  // before its predecessors (a rank that has fed fewer batches sends an older local batch in the same round) waits here.
-  // Messages without an index (g1s_shard_msg_from_latest) are merged as they come: rounds in order, ranks in order.
-  for (uint32_t r = 0; r < world; ++r) {  // (validate the whole round before merging any of it)
-    const uint8_t *m = (const uint8_t *)msgs + (size_t)r * stride_bytes;
-    ShardHeader h;
-    std::memcpy(&h, m, sizeof(h));
-    if (h.magic != kShardMagic || h.lag != f->lag || h.count > h.batch_frames ||
-        stride_bytes < g1s_shard_msg_size(h.lag, h.batch_frames)) {
-      f->err = "bad shard message from rank " + std::to_string(r);
-      return G1S_ERR_INVALID;
-    }
-  }
-  const size_t bs = latest_blob_size(f->lag);
-  // The batches of this round that are next in the global order -- straight from the messages, or from `early` once their
-  // predecessors have come -- are collected as runs and merged in one go (fold_push_runs: windows across messages).
-  std::vector<BlobRun> runs;
-  uint64_t next = f->next_batch;  // the global batch the next run must be
-  size_t from_early = 0;          // how many of `early`'s first entries are in `runs`
-  auto drain_early = [&] {
-    auto it = f->early.begin();
-    std::advance(it, from_early);
-    while (it != f->early.end() && it->first == next) {
-      runs.push_back(BlobRun{it->second.data(), bs, it->second.size() / bs});
-      ++it;
-      ++from_early;
-      ++next;
-    }
-  };
-  auto flush = [&]() -> int {
-    const int rc = runs.empty() ? G1S_OK : fold_push_runs(f, runs.data(), runs.size());
-    runs.clear();
-    f->next_batch = next;
-    for (; from_early; --from_early) f->early.erase(f->early.begin());
-    return rc;
-  };
-  for (uint32_t r = 0; r < world; ++r) {
-    const uint8_t *m = (const uint8_t *)msgs + (size_t)r * stride_bytes;
-    ShardHeader h;
-    std::memcpy(&h, m, sizeof(h));
-    if (!h.count) continue;
-    if (h.local_batch == kShardNoIndex) {
-      if (const int rc = flush()) return rc;
-      if (!f->early.empty()) {
-        f->err = "frame-shard merge: a message without a batch index while indexed batches are waiting";
-        return G1S_ERR_STATE;
-      }
-      const int rc = g1s_fold_push_latest(f, m + sizeof(h), bs, h.count);
-      if (rc) return rc;
-      continue;
-    }
-    const uint64_t j = (uint64_t)h.local_batch * world + r;
-    if (j < next || f->early.count(j)) {
-      flush();
-      f->err = "frame-shard merge: batch " + std::to_string(j) + " arrived twice (rank " + std::to_string(r) + ")";
-      return G1S_ERR_STATE;
-    }
-    if (j == next) {
-      runs.push_back(BlobRun{m + sizeof(h), bs, h.count});
-      ++next;
-    } else {
-      f->early.emplace(j, std::vector<uint8_t>(m + sizeof(h), m + sizeof(h) + (size_t)h.count * bs));
-    }
-    drain_early();
-  }
-  return flush();
-}
-void g1s_fold_free(g1s_fold_t *f) { delete f; }
-const char *g1s_fold_last_error(const g1s_fold_t *f) { return f ? f->err.c_str() : ""; }
-uint64_t g1s_fold_frames(const g1s_fold_t *f) { return f ? f->fold.frames() : 0; }
-
-long g1s_format_tbl(const g1s_segment_t *segs, size_t n, char *buf, size_t cap) {
-  return format_tbl(segs, n, buf, cap);
-}
-int g1s_parse_tbl(const char *text, size_t len, g1s_segment_t *out, size_t cap, size_t *n_out, char *err, size_t errcap) {
-  if (!text && len) return G1S_ERR_INVALID;
-  std::vector<g1s_segment_t> segs;
-  std::string msg;
-  const int rc = parse_tbl(text, len, segs, msg);
-  if (rc) {
-    if (err && errcap) snprintf(err, errcap, "%s", msg.c_str());
-    return rc;
-  }
-  if (n_out) *n_out = segs.size();
-  if (segs.size() > cap) return G1S_ERR_CAPACITY;
-  if (!segs.empty()) std::memcpy(out, segs.data(), sizeof(g1s_segment_t) * segs.size());
-  return G1S_OK;
-}
-long g1s_tbl_segment_for(g1s_segment_t *segs, size_t n, uint64_t packet_ts) {
-  if (!segs) return -1;
-  for (size_t i = 0; i < n; ++i) {
-    if (segs[i].start_time <= packet_ts && packet_ts < segs[i].end_time) {
-      segs[i].random_seed = (uint16_t)(segs[i].random_seed + 10956u);  // DEFAULT_GRAIN_SEED, wrapping
-      return (long)i;
-    }
-  }
-  return -1;
-}
-int g1s_write_tbl(const char *path, const g1s_segment_t *segs, size_t n) {
-  std::vector<char> buf(1024 + 2048 * n);
-  const long k = format_tbl(segs, n, buf.data(), buf.size());
-  if (k < 0) return (int)k;
-  FILE *f = fopen(path, "wb");
-  if (!f) return G1S_ERR_INVALID;
-  const size_t w = fwrite(buf.data(), 1, (size_t)k, f);
-  const int c = fclose(f);
-  return (w == (size_t)k && c == 0) ? G1S_OK : G1S_ERR_INVALID;
-}
 
 int g1s_diff_get_stats(const g1s_diff_t *g, g1s_stats_t *out) {
   if (!g || !out) return G1S_ERR_INVALID;
@@ -2384,58 +1839,6 @@ int g1s_diff_last_record(const g1s_diff_t *g, void *buf, size_t cap_bytes) {
   if (g->last_record.size() > cap_bytes) return G1S_ERR_CAPACITY;
   std::memcpy(buf, g->last_record.data(), g->last_record.size());
   return G1S_OK;
-}
-
-static bool rec_layout(const void *rec, RecHeader &h, RecLayout &L) {
-  if (!rec) return false;
-  std::memcpy(&h, rec, sizeof(h));
-  if (h.magic != kRecMagic) return false;
-  L = make_layout(h.width, h.height, h.nplanes, h.lag);
-  return L.size == h.size_bytes;
-}
-int g1s_record_geometry(const void *rec, uint32_t *nbw, uint32_t *nbh, uint32_t *nplanes, uint32_t *lag) {
-  RecHeader h;
-  RecLayout L;
-  if (!rec_layout(rec, h, L)) return G1S_ERR_INVALID;
-  if (nbw) *nbw = h.nbw;
-  if (nbh) *nbh = h.nbh;
-  if (nplanes) *nplanes = h.nplanes;
-  if (lag) *lag = h.lag;
-  return G1S_OK;
-}
-const uint8_t *g1s_record_flat_mask(const void *rec) {
-  RecHeader h;
-  RecLayout L;
-  if (!rec_layout(rec, h, L)) return nullptr;
-  return (const uint8_t *)rec + L.off_mask;
-}
-const float *g1s_record_scores(const void *rec) {
-  RecHeader h;
-  RecLayout L;
-  if (!rec_layout(rec, h, L)) return nullptr;
-  return reinterpret_cast<const float *>((const uint8_t *)rec + L.off_scores);
-}
-int g1s_record_ar_sums(const void *rec, uint32_t c, const int64_t **S, const int64_t **Sb, int64_t *nobs) {
-  RecHeader h;
-  RecLayout L;
-  if (!rec_layout(rec, h, L) || c >= h.nplanes) return G1S_ERR_INVALID;
-  const int nc = (int)h.n + (c > 0);
-  const int64_t *p = reinterpret_cast<const int64_t *>((const uint8_t *)rec + L.off_ar[c]);
-  if (S) *S = p;
-  if (Sb) *Sb = p + (size_t)nc * nc;
-  if (nobs) *nobs = p[(size_t)nc * nc + nc];
-  return nc;
-}
-int g1s_record_block_stats(const void *rec, uint32_t c, const uint32_t **luma_sum, const int32_t **sum_d,
-                           const uint32_t **sum_d2) {
-  RecHeader h;
-  RecLayout L;
-  if (!rec_layout(rec, h, L) || c >= h.nplanes) return G1S_ERR_INVALID;
-  const uint8_t *r = (const uint8_t *)rec;
-  if (luma_sum) *luma_sum = reinterpret_cast<const uint32_t *>(r + L.off_luma_sum);
-  if (sum_d) *sum_d = reinterpret_cast<const int32_t *>(r + L.off_sum_d[c]);
-  if (sum_d2) *sum_d2 = reinterpret_cast<const uint32_t *>(r + L.off_sum_d2[c]);
-  return (int)L.nblocks;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // product's own implementation; the test oracle under oracle/ is separate.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -182,6 +183,16 @@ class NoiseFold {
   std::vector<uint8_t> snap_cut_;  // ... whether frame j starts a new segment, given no cut before it
   std::vector<FrameView> views_;
 };
+
+// What a *_finish call hands out: the count always, the segments when the buffer takes them -- otherwise G1S_ERR_CAPACITY,
+// and the caller stores kSegmentsTooSmall as its error text
+constexpr const char *kSegmentsTooSmall = "segment buffer too small";
+inline int copy_segments(const std::vector<g1s_segment_t> &segs, g1s_segment_t *out, size_t cap, size_t *n_out) {
+  if (n_out) *n_out = segs.size();
+  if (segs.size() > cap || (!out && !segs.empty())) return G1S_ERR_CAPACITY;
+  if (!segs.empty()) std::memcpy(out, segs.data(), sizeof(g1s_segment_t) * segs.size());
+  return G1S_OK;
+}
 
 long format_tbl(const g1s_segment_t *segs, size_t n, char *buf, size_t cap);
 int parse_tbl(const char *text, size_t len, std::vector<g1s_segment_t> &out, std::string &err);

@@ -1,5 +1,5 @@
 // frame_op.h -- the host scaffold the frame operations share (render: grain.hip, denoise: denoise.hip, estimate:
-// estimate.hip; the generator takes the owners).  Host code only.  The first part -- plane geometry, the two layouts of a
+// estimate.hip, measure: measure.hip; the generator, engine.hip, takes the owners and the addressing predicate).  Host code only.  The first part -- plane geometry, the two layouts of a
 // frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP and builds with a host compiler
 // alone; the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro and the
 // base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
@@ -12,6 +12,9 @@
 #include <utility>
 
 #include "../../include/g1s_diff.h"
+
+// (host_abi.cpp) the text g1s_last_global_error() returns on this thread: what a *_new call that returns NULL sets
+extern "C" void g1s_set_global_error_(const char *);
 
 namespace g1s_op {
 

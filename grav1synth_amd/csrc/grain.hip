@@ -26,8 +26,6 @@
 #include "fold.h"
 #include "frame_op.h"
 
-extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
-
 namespace {
 
 const int16_t kGaussHost[2048] = {G1S_GAUSSIAN_SEQUENCE_VALUES};

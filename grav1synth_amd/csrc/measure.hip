@@ -35,8 +35,6 @@
 #include "fold.h"
 #include "frame_op.h"
 
-extern "C" void g1s_set_global_error_(const char *);  // (engine.hip)
-
 namespace {
 
 constexpr int kTW = 64, kTH = 128, kHalo = 3;

@@ -76,4 +76,10 @@ inline RecLayout make_layout(uint32_t width, uint32_t height, uint32_t nplanes, 
   return L;
 }
 
+// the header of a record of layout L = make_layout(width, height, nplanes, lag); `status` is the caller's to set
+inline RecHeader make_header(const RecLayout &L, uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t lag) {
+  const uint32_t nbw = (width + kBlock - 1) / kBlock, nbh = (height + kBlock - 1) / kBlock;
+  return RecHeader{kRecMagic, lag, width, height, xdec, ydec, L.nplanes, nbw, nbh, L.n, /*status*/ 0, /*reserved*/ 0, L.size};
+}
+
 }  // namespace g1s
