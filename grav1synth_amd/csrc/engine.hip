@@ -2,10 +2,8 @@
 // g1s_diff_t *.  The ABI that needs no device (records, fold handle, shard messages, .tbl) is host_abi.cpp; the worker
 // pools are host_pool.h.
 //
-// Frames are queued into a slot of `batch_frames` pairs; a full slot is one
-// K1 -> K2 -> K3 launch group on the engine's HIP stream followed by one D2H
-// copy of the slot's integer records.  Two slots alternate, so the GPU works on
-// batch k+1 while the host folds batch k in frame order (fold.cpp).
+// Frames are queued into a slot of `batch_frames` pairs; a full slot is one batch: its schedule is decided once (schedule.h,
+// plan_batch), its kernels and the D2H copy of its results follow that plan, the host folds it in frame order (fold.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,11 +35,15 @@
 #include "k3w.hip.h"
 #include "latest_dev.h"
 #include "record.h"
+#include "schedule.h"
 
 using namespace g1s;
 using g1s_op::DevBuf;
 using g1s_op::Event;
 using g1s_op::PinnedBuf;
+using g1s_sched::HostWait;
+using g1s_sched::Role;
+using g1s_sched::Switches;
 
 namespace {
 
@@ -58,21 +60,8 @@ constexpr int kK3Chunks = 48;
 // the lag-structured v_dot4 kernels behind the pixel pass K0, K0's planes in front of the matrix-core kernel, the 32x32x32 form
 // of the fused pass -- were removed in round 4: git history)
 //
-// The process-wide switches: read once, when the library first asks for one.  Every one selects an arrangement that gives the
-// same records as the default, and is here because a test, bench.py or a measurement tool sets it.
+// The process-wide switches (schedule.h: Switches): read once, when the library first asks for one.
 // (Read at every call instead, where they are used: G1S_F_WGS, G1S_W_WGS[_C], G1S_F_REUSE; per generator: G1S_LATEST.)
-struct Switches {
-  bool wide;        // G1S_K3 is not "stream": the wide chain, the stream chain where it does not serve (tests, bench.py)
-  bool w_off;       // G1S_W_OFF: the wide chain serves nothing while its buffers and zero fills stay (tests)
-  bool one_stream;  // G1S_ONE_STREAM: every kernel of a batch on the main stream, no deferred back half (tests, profiling tools)
-  bool no_defer;    // G1S_NO_DEFER: a batch's back half is queued with its own front half (tests)
-  bool side2;       // G1S_SIDE2=1: a second side stream, the finder chains of the odd slots on it (tests; no gain: profiles/r03b)
-  bool w_aside;     // G1S_W_ASIDE: the wide chain's chroma launch and what follows on the copy stream, round 3's placement (tests)
-  bool f_serial;    // G1S_F_SERIAL: the stream chain's chroma launch stays on the main stream (tests)
-  bool d2h_sync;    // G1S_D2H_SYNC: launch_back waits for the batch's copy (profiling tools, with G1S_ONE_STREAM)
-  int w_rev;        // G1S_W_REV: bit 0 the luma launch, bit 1 the chroma launch of the wide chain walk the frames last to first (tests)
-  int k1_literal;   // G1S_K1_LITERAL=1|2: the finder evaluates every block literally, a lane / a wave a block (tests)
-};
 const Switches &switches() {
   static const Switches s = [] {
     Switches v;
@@ -141,7 +130,6 @@ int w_wgs_per_frame(int ncell, int B, int kind) {
 // cost the same whatever the frame's size and the host half's cost goes with the blocks: same box, 1080p (2 040 blocks) the host half
 // 1.08 - 1.10 x the device half, 4K (8 160 blocks) the device half 1.13 x the host half (profiles/r07_device_latest.txt)
 constexpr int kDeviceLatestMinBlocks = 4096;
-constexpr uint32_t kLatestWindowMinBatch = 64;  // frames a launch from which k4_latest gets a window of its own (g1s_diff::submit)
 constexpr int kSlots = 6;  // batches in flight: being filled, finder chain, accumulation, (the per-frame half on the device,) D2H, fold
 
 // A slot's memory: the bytes of every per-slot allocation and, for the buffers that hold several things, where each region
@@ -156,6 +144,40 @@ struct SlotLayout {
   bool operator==(const SlotLayout &o) const { return std::memcmp(this, &o, sizeof(*this)) == 0; }
 };
 static_assert(std::has_unique_object_representations<SlotLayout>::value, "SlotLayout is compared as bytes: no padding in it");
+
+// A batch's schedule (schedule.h has the table and the decision): filled by plan_batch when the batch is submitted, followed by
+// everything that queues work for it.  It lives in the slot: a deferred back half is queued one submit later and follows the
+// plan its front half was queued under.
+struct BatchPlan {
+  Geom g;      // batch_geom
+  bool wide;   // the chain: wide_ok(g, batch_far)
+  bool timed;  // every kernel of the batch on the main stream, events around them (g1s_diff_set_timing)
+  bool chain;  // a timed batch with ONE pair of events, around the batch's whole chain of kernels (g1s_diff_set_timing(g, 2))
+  hipStream_t table, finder, accum, rest, latest, d2h;
+  bool back_now;
+  int after;
+  HostWait host_waits;
+};
+
+// Per-kernel timing (g1s_diff_set_timing) and the trace (G1S_TRACE): an event in front of each launch on the stream it goes to,
+// the name of the kernel it precedes (none: the end of the one before).  A mark that cannot be made is left out.
+struct Marks {
+  struct Mark { Event ev; std::string name; hipStream_t stream = nullptr; };
+  std::vector<Mark> m;
+  size_t n = 0;
+  // (plan_batch) timed: a timed batch that is not chain-timed -- nothing between two launches of a chain-timed batch;
+  // trace: an untimed batch of a generator that writes a trace
+  bool timed = false, trace = false;
+  void mark(hipStream_t st, const char *name) {
+    if (!timed && !trace) return;
+    if (n == m.size()) m.emplace_back();
+    Mark &k = m[n];
+    if ((!k.ev && hipEventCreate(&k.ev.p) != hipSuccess) || hipEventRecord(k.ev, st) != hipSuccess) return;
+    k.stream = st, k.name = name ? name : "", ++n;
+  }
+  // only for the trace: the timed batches' table of kernels stays what it was
+  void mark_trace(hipStream_t st, const char *name) { if (trace) mark(st, name); }
+};
 
 enum SlotEv { kEvStart, kEvMomStart, kEvMomEnd, kEvFinderEnd, kEvSelectEnd, kEvEnd, kSlotEvs };  // a timed batch's events, as they are recorded
 
@@ -178,15 +200,10 @@ struct Slot {
   Event done;            // the batch's results are on the host
   Event ev[kSlotEvs];    // timing: SlotEv
   uint32_t count = 0;
-  bool timed = false;
-  bool chain = false;  // a timed batch with ONE pair of events, around the batch's whole chain of kernels (g1s_diff_set_timing(g, 2))
   bool async_in = false;  // the batch holds frames whose H2D copies were queued on the upload stream
-  // per-kernel timing (g1s_diff_set_timing): an event before each launch, the name of the kernel it precedes
-  std::vector<Event> kev;
-  std::vector<std::string> kname;
-  std::vector<hipStream_t> kstream;
-  size_t nk = 0;
-  // the device half's buffers: made when a batch first runs that half, made again if one ever asks for more
+  BatchPlan plan{};
+  Marks marks;
+  // (the device half's buffers: made when a batch first runs that half, made again if one ever asks for more)
   hipError_t ensure_latest(size_t blob_bytes, size_t scratch_bytes) {
     if (latest_cap < blob_bytes) {
       d_latest = {}, h_latest = {}, latest_cap = 0;
@@ -224,17 +241,10 @@ std::mutex g_cache_mutex;
 // (never destroyed: a parked slot is not freed at exit, when the runtime it would call may be gone already)
 std::vector<CachedSlot> &g_slot_cache = *new std::vector<CachedSlot>;
 
-// Streams and their events are process-wide too (0.1-0.2 ms to create each); a generator borrows a set and
-// hands it back when it is freed:
-//   compute  main stream: the accumulation of one batch after the other, back to back -- k3w_pass x 2 and k3w_tail
-//            (the stream chain: its luma launch); behind a batch's tail its k4_latest when the per-frame half of the fold
-//            runs on the device and the launches are wide (submit)
-//   flat     side stream (high priority): a batch's finder chain, select kernel and unit lists, next to the accumulation
-//            of the batch before (flat2: those of the odd slots under G1S_SIDE2) -- with the device half: next to the
-//            k4_latest of the batch before, and to nothing else (submit)
-//   copy     the results' D2H, behind the accumulation; in front of it the wide chain's chroma launch and tail under
-//            G1S_W_ASIDE, the stream chain's chroma launch and what follows unless G1S_F_SERIAL
-//   upload   the frame table (72 bytes a frame pair), k_zero and the queued copies of pinned host frames, ahead of everything
+// Streams and their events are process-wide too (0.1-0.2 ms to create each); a generator borrows a set and hands it back
+// when it is freed.  What runs on which: schedule.h.  compute is the main stream (the accumulation of one batch after the
+// other, back to back), flat the side stream (high priority: the finder chains, next to the accumulation of the batch before),
+// copy carries the results' D2H, upload the frame table, k_zero and the queued copies of pinned host frames, ahead of everything.
 struct StreamSet {
   int device = -1;
   hipStream_t compute = nullptr, copy = nullptr, flat = nullptr, flat2 = nullptr, upload = nullptr;
@@ -323,7 +333,6 @@ struct g1s_diff {
   uint32_t batch;
   bool batch_auto = false;  // no batch size asked for: sized to the frames at the first frame pair
   int device = 0;
-  hipStream_t stream = nullptr;       // == ss.compute
   StreamSet ss;                       // borrowed from the process-wide cache
   bool geometry_set = false;
   g1s_frame_t shape{};  // geometry of the first frame
@@ -345,7 +354,6 @@ struct g1s_diff {
   int cur = 0;
   int pending = -1;  // slot whose front half is queued and whose back half is not (not in the window: submit)
   int last_back = -1;  // slot of the batch whose back half was queued last; -1: none since everything queued was drained
-  bool latest_window() const { return device_latest && batch >= kLatestWindowMinBatch; }  // (submit)
   // The API thread queues frames and launches batches; the drainer thread waits for a batch's records,
   // runs the fold on them and frees the slot.  Everything below dm is shared between the two.
   std::thread drainer;  // waits for a batch's records, runs the per-frame half of the fold on the pool
@@ -393,22 +401,6 @@ struct g1s_diff {
   g1s_stats_t stats{};
   std::map<std::string, std::pair<double, uint64_t>> ktimes;  // timed batches: kernel name -> (ms, launches)
   std::mutex ktimes_mutex;
-  // timed batches run on one stream: an event before each launch (and one after the last), named after the kernel
-  int kmark(Slot &sl, hipStream_t st, const char *name) {
-    if (sl.chain) return G1S_OK;  // (a chain-timed batch: nothing between two of its launches, trace mode or not)
-    if (!sl.timed && !trace) return G1S_OK;
-    if (sl.nk == sl.kev.size()) {
-      Event e;
-      if (hipEventCreate(&e.p) != hipSuccess) return fail(G1S_ERR_HIP, "hipEventCreate failed");
-      sl.kev.push_back(std::move(e));
-      sl.kname.emplace_back();
-      sl.kstream.push_back(nullptr);
-    }
-    if (hipEventRecord(sl.kev[sl.nk], st) != hipSuccess) return fail(G1S_ERR_HIP, "hipEventRecord failed");
-    sl.kstream[sl.nk] = st;
-    sl.kname[sl.nk++] = name ? name : "";
-    return G1S_OK;
-  }
   // G1S_TRACE=file (a measurement aid): the PIPELINED job's own timeline -- an event in front of every launch on the stream it
   // is launched on (its end = the next event of that stream), the host's time at every submit; written at finish
   bool trace = false;
@@ -440,12 +432,14 @@ struct g1s_diff {
   int set_geometry_alloc(const g1s_frame_t *s, const g1s_frame_t *d);
   int append(const g1s_frame_t *s, const g1s_frame_t *d);
   uint64_t frames_copied(uint64_t wait_for);
-  int submit(int si);        // front half now; back half now or with the next batch's front half
+  int submit(int si);        // plan, front half now; back half now or with the next batch's front half
+  int plan_batch(int si);    // the batch's schedule: slots[si].plan
   int launch_front(int si);  // frame table, zero fills, flat-block finder, select kernel, unit lists
   int launch_back(int si);   // accumulation kernels, records D2H, hand-over to the drainer; its parts, in order:
-  int accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);    // (`stream`: by reference, a chain may move
-  int accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side);  //  its chroma launch and the rest to ss.copy)
-  int copy_out(Slot &sl, int si, hipStream_t stream);
+  int accumulate_wide(Slot &sl, int si);
+  int accumulate_stream(Slot &sl, int si);
+  int to_rest(const BatchPlan &p, int si);  // (between a chain's luma and chroma launch)
+  int copy_out(Slot &sl, int si);
   static bool wide_gen(const Geom &g);  // the wide chain's general residual form (mixed sample sizes / shifts)
   int flush_pending();
   Geom batch_geom(const Slot &sl) const;
@@ -680,11 +674,10 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
           // pinned host memory the caller keeps valid until g1s_diff_frames_copied() covers this frame: queued on the
           // upload stream (the table upload of the batch follows on that stream, the kernels wait for that), the call
           // returns at once -- file reads, copies and the kernels of earlier batches overlap
-          hipStream_t cs = ss.upload ? ss.upload : stream;
           if (f->stride_bytes[c] == row && pw * f->bytes_per_sample == row)
-            HIP_TRY(hipMemcpyAsync(stage, f->data[c], row * ph, hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpyAsync(stage, f->data[c], row * ph, hipMemcpyHostToDevice, ss.upload));
           else
-            HIP_TRY(hipMemcpy2DAsync(stage, row, f->data[c], f->stride_bytes[c], pw * f->bytes_per_sample, ph, hipMemcpyHostToDevice, cs));
+            HIP_TRY(hipMemcpy2DAsync(stage, row, f->data[c], f->stride_bytes[c], pw * f->bytes_per_sample, ph, hipMemcpyHostToDevice, ss.upload));
           any_async = true;
         } else {
           // the `&Frame` borrow ends when this call returns: copy now
@@ -715,7 +708,7 @@ int g1s_diff::append(const g1s_frame_t *s, const g1s_frame_t *d) {
       } else {
         HIP_TRY(hipEventCreateWithFlags(&e.p, hipEventDisableTiming));
       }
-      HIP_TRY(hipEventRecord(e, ss.upload ? ss.upload : stream));
+      HIP_TRY(hipEventRecord(e, ss.upload));
       h2d_pending.emplace_back(frames_appended, std::move(e));
       sl.async_in = true;
     }
@@ -773,25 +766,22 @@ bool g1s_diff::batch_far(const Slot &sl) const {
   return false;
 }
 
-// A batch runs in two halves.  Front: the frame table and the zero fills on the upload stream, then the finder chain
-// (k1_moments -- the only pass over pixels outside the flat blocks' tiles --, certify, the literal blocks, select, the unit
-// lists: after the first, small latency-bound kernels) on the side stream.  Back: the accumulation kernels on the main
-// stream, the results' D2H, the hand-over to the drainer.  The back half of batch N is queued behind the front half of
-// batch N + 1: the main stream runs accumulation(N), accumulation(N + 1), ... back to back (the big kernels never share
-// the chip, which only stretches them), and the side stream's chain of N + 1 runs next to accumulation(N) and is long
-// done when accumulation(N + 1) comes up.
-// With the per-frame half of the fold on the device (device_latest) nothing is deferred and nothing runs beside an
-// accumulation launch: back(N) is queued with front(N), k4_latest(N) follows the tail of N on the main stream, and the first
-// pixel kernel of front(N + 1) waits for kernels_done[N] -- back(N) has to be queued before front(N + 1) can name that event.
-// The main stream runs luma(N), chroma(N), tail(N) alone on the chip, then k4_latest(N) (64 workgroups of serial f64 chains)
-// while the side stream runs the finder chain of N + 1 (a pass over HBM and small kernels): the two want different things and
-// are about as long, 270 and 260 us at 4K.  Period 850 - 865 us a 64-frame batch against 965 - 985 with the chain beside the
-// luma launch and k4_latest on a stream of its own (profiles/r09_latest_window.txt, which also has the three forms that lost).
-// That is for launches of kLatestWindowMinBatch frames or more (latest_window): k4_latest's time goes with a frame's blocks and
-// not with the launch's frames (a workgroup a frame), the chain's and the accumulation's with both, so in a narrow launch the
-// kernel is the longer side of the window and the chip waits for 32 workgroups -- 8K 4:4:4 in 32-frame launches: k4_latest
-// 845 us against a chain of 585, 324 k Mpx/s with the window against 342 - 359 k without.  Narrower launches keep the schedule
-// above with k4_latest on a stream of its own.
+// A batch runs in two halves, each where its plan says (schedule.h has the table; here is why it reads as it does).  Front: the
+// frame table and the zero fills, then the finder chain (k1_moments -- the only pass over pixels outside the flat blocks' tiles
+// --, certify, the literal blocks, select, the unit lists: small latency-bound kernels).  Back: the accumulation kernels, the
+// results' D2H, the hand-over to the drainer.
+// Deferred (the default without the device half): back(N) is queued behind front(N + 1), so the main stream runs
+// accumulation(N), accumulation(N + 1), ... back to back (the big kernels never share the chip, which only stretches them), and
+// the side stream's chain of N + 1 runs next to accumulation(N) and is long done when accumulation(N + 1) comes up.
+// The window (the device half, launches of kLatestWindowMinBatch frames or more): nothing is deferred and nothing runs beside
+// an accumulation launch.  k4_latest(N) follows the tail of N on the stream that ran it and the finder chain of N + 1 waits for
+// kernels_done[N] -- back(N) has to be queued before front(N + 1) can name that event -- so 64 workgroups of serial f64 chains
+// run beside a pass over HBM and small kernels: the two want different things and are about as long, 270 and 260 us at 4K.
+// Period 850 - 865 us a 64-frame batch against 965 - 985 with the chain beside the luma launch and k4_latest on a stream of
+// its own (profiles/r09_latest_window.txt, which also has the three forms that lost).  Not for narrower launches: k4_latest's
+// time goes with a frame's blocks (a workgroup a frame), the chain's and the accumulation's with the launch's frames too, so
+// there the kernel is the longer side of the window and the chip waits for 32 workgroups -- 8K 4:4:4 in 32-frame launches:
+// k4_latest 845 us against a chain of 585, 324 k Mpx/s with the window against 342 - 359 k without.
 int g1s_diff::submit(int si) {
   Slot &sl = slots[si];
   if (sl.count == 0) return G1S_OK;
@@ -800,7 +790,9 @@ int g1s_diff::submit(int si) {
     slot_busy[si] = true;  // until the drainer has folded it
   }
   trace_host("submit", si);
-  int rc = launch_front(si);
+  int rc = plan_batch(si);
+  if (rc) return rc;
+  rc = launch_front(si);
   if (rc) return rc;
   trace_host("front queued", si);
   const int prev = pending;
@@ -810,7 +802,7 @@ int g1s_diff::submit(int si) {
     if (rc) return rc;
     trace_host("back queued", prev);
   }
-  if (switches().one_stream || switches().no_defer || timing || !ss.flat || latest_window()) {
+  if (sl.plan.back_now) {
     rc = flush_pending();
     if (rc) return rc;
   }
@@ -824,6 +816,26 @@ int g1s_diff::submit(int si) {
   return G1S_OK;
 }
 
+// The batch's schedule, decided once: what the chains depend on (the frame table cannot change once the batch is submitted)
+// and the stream of every part (schedule.h).  The only reader of the stream switches and of `timing`.
+int g1s_diff::plan_batch(int si) {
+  Slot &sl = slots[si];
+  BatchPlan &p = sl.plan;
+  p.g = batch_geom(sl);
+  p.wide = wide_ok(p.g, batch_far(sl));
+  p.timed = timing;
+  p.chain = timing && timing_chain;
+  const g1s_sched::Schedule s = g1s_sched::schedule(switches(), {p.timed, device_latest, p.wide, batch, si, p.g.nplanes, last_back});
+  // (the device half's streams: made when a generator first runs that half outside the window)
+  if ((s.latest == Role::latest || s.latest == Role::latest2) && !ensure_latest_streams(ss)) return fail_hip("the device half's streams could not be created");
+  const hipStream_t of[] = {ss.compute, ss.flat, ss.flat2, ss.copy, ss.upload, ss.latest, ss.latest2};  // (Role's order)
+  p.table = of[(int)s.table], p.finder = of[(int)s.finder], p.accum = of[(int)s.accum], p.rest = of[(int)s.rest];
+  p.latest = of[(int)s.latest], p.d2h = of[(int)s.d2h];
+  p.back_now = s.back_now, p.after = s.after, p.host_waits = s.host_waits;
+  sl.marks.n = 0, sl.marks.timed = p.timed && !p.chain, sl.marks.trace = trace && !p.timed;
+  return G1S_OK;
+}
+
 int g1s_diff::flush_pending() {
   if (pending < 0) return G1S_OK;
   const int si = pending;
@@ -833,38 +845,28 @@ int g1s_diff::flush_pending() {
 
 int g1s_diff::launch_front(int si) {
   Slot &sl = slots[si];
+  const BatchPlan &p = sl.plan;
+  const Geom &g = p.g;
   const uint32_t B = sl.count;
-  Geom g = batch_geom(sl);
-  hipStream_t stream = ss.compute;  // main stream (shadows the member)
-  // The finder chain -- the moments kernel (the only pass over the pixels in front of the mask) and the small latency-bound
-  // kernels behind it -- runs on the side stream, next to the accumulation of the batch before; per-kernel timing and
-  // G1S_ONE_STREAM: on the main stream.
-  // (measured and dropped: k1_moments on the main stream in front of the accumulation of the batch before, the rest of the
-  //  finder chain beside that accumulation: -3 to -10 % at 4K, +11 % at 1080p, -4 % at 8K; profiles/r04_streams.txt.
-  //  k1_moments on a stream of its own: profiles/r05o_streams.txt)
-  // G1S_SIDE2=1: two side streams, a batch's chain on the one of its slot's parity: the latency-bound tail of a chain (certify,
-  // the literal blocks, select, unit lists) then runs next to the moments kernel of the batch after it -- one waits on dependent
+  // The finder chain's place beside the accumulation of the batch before -- measured and dropped: k1_moments on the main
+  // stream in front of that accumulation, the rest of the chain beside it: -3 to -10 % at 4K, +11 % at 1080p, -4 % at 8K
+  // (profiles/r04_streams.txt); k1_moments on a stream of its own: profiles/r05o_streams.txt.
+  // G1S_SIDE2=1: a batch's chain on the side stream of its slot's parity: the latency-bound tail of a chain (certify, the
+  // literal blocks, select, unit lists) then runs next to the moments kernel of the batch after it -- one waits on dependent
   // loads, the other streams through HBM -- instead of in front of it (the timeline shows them overlap either way)
-  hipStream_t fstream = (switches().one_stream || timing || !ss.flat) ? stream : ((si & 1) && switches().side2 && ss.flat2 ? ss.flat2 : ss.flat);
-  // the frame table: pinned host copy -> device, on the upload stream (idle: done long before the main
-  // stream gets here); per-kernel timing / one-stream mode: in line
-  const FrameTable ft{sl.d_planes};
-  hipStream_t up = (fstream == stream || !ss.upload) ? stream : ss.upload;
+  const hipStream_t up = p.table, fstream = p.finder;
+  const FrameTable ft{sl.d_planes};  // pinned host copy -> device on `up`: the upload stream is idle, done long before the main stream gets here
   if (sl.async_in) {  // queued frame copies: on the upload stream; everything below waits for `up`
-    hipStream_t cs = ss.upload ? ss.upload : stream;
-    if (cs != up) {
+    if (up != ss.upload) {
       if (!h2d_order) HIP_TRY(hipEventCreateWithFlags(&h2d_order.p, hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(h2d_order, cs));
+      HIP_TRY(hipEventRecord(h2d_order, ss.upload));
       HIP_TRY(hipStreamWaitEvent(up, h2d_order, 0));
     }
     sl.async_in = false;
   }
-  sl.timed = timing;
-  sl.chain = timing && timing_chain;
-  sl.nk = 0;
-  if (!sl.timed) kmark(sl, up, "table H2D");  // (trace mode only: the timed batches' table of kernels stays what it was)
+  sl.marks.mark_trace(up, "table H2D");
   HIP_TRY(hipMemcpyAsync(sl.d_planes, sl.h_planes, sizeof(FramePlanes) * B, hipMemcpyHostToDevice, up));
-  if (!sl.timed) kmark(sl, up, "k_zero");
+  sl.marks.mark_trace(up, "k_zero");
   {
     // all per-batch zero fills in one launch: the records, the counters and flags the kernels add to or set
     ZeroJob z{};
@@ -879,15 +881,15 @@ int g1s_diff::launch_front(int si) {
     //  with earlier batches)
     hipLaunchKernelGGL(k_zero, dim3(256), dim3(256), 0, up, z);
   }
-  if (!sl.timed) kmark(sl, up, nullptr);
-  if (up != stream) {
+  sl.marks.mark_trace(up, nullptr);
+  if (up != p.accum) {
     HIP_TRY(hipEventRecord(ss.table_done[si], up));
-    HIP_TRY(hipStreamWaitEvent(stream, ss.table_done[si], 0));
+    HIP_TRY(hipStreamWaitEvent(p.accum, ss.table_done[si], 0));
     HIP_TRY(hipStreamWaitEvent(fstream, ss.table_done[si], 0));  // (the table goes by the upload stream only when the finder chain has a side stream)
   }
   // the window: the chain starts when the accumulation of the batch before has ended (submit)
-  if (latest_window() && fstream != stream && last_back >= 0) HIP_TRY(hipStreamWaitEvent(fstream, ss.kernels_done[last_back], 0));
-  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvStart], fstream));
+  if (p.after >= 0) HIP_TRY(hipStreamWaitEvent(fstream, ss.kernels_done[p.after], 0));
+  if (p.timed) HIP_TRY(hipEventRecord(sl.ev[kEvStart], fstream));
   {
     // flat-block features: integer moments + certified evaluation; the literal f64 kernel only for
     // the blocks the certificate leaves open (G1S_K1_LITERAL=1 / g1s_diff_set_flat_finder: for every block)
@@ -900,19 +902,19 @@ int g1s_diff::launch_front(int si) {
     cl.global = literal_mode == 0 ? 1 : 0;  // (the default chain: one sequence for the launch; "every block literally": per-frame lists)
     {
       // the finder's moments of the luma source: the only pass over pixels that are not in a flat block's tile
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomStart], fstream));
+      if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomStart], fstream));
       {  // (also when every block is evaluated literally: the record's luma_sum comes from the moments)
         const dim3 mg((g.nblocks + 7) / 8, B);
-        kmark(sl, fstream, g.src_bps == 1 ? "k1_moments<1>" : "k1_moments<2>");
+        sl.marks.mark(fstream, g.src_bps == 1 ? "k1_moments<1>" : "k1_moments<2>");
         if (g.src_bps == 1) hipLaunchKernelGGL(k1_moments<1>, mg, dim3(256), 0, fstream, ft, g, mom);
         else hipLaunchKernelGGL(k1_moments<2>, mg, dim3(256), 0, fstream, ft, g, mom);
       }
-      if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomEnd], fstream));
+      if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomEnd], fstream));
     }
-    kmark(sl, fstream, "k1_certify");
+    sl.marks.mark(fstream, "k1_certify");
     hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
                        sl.d_records, sl.d_flags, cl, force_literal);
-    kmark(sl, fstream, literal_mode == 1 ? "k1_flat_features" : "k1_flat_block");
+    sl.marks.mark(fstream, literal_mode == 1 ? "k1_flat_features" : "k1_flat_block");
     if (literal_mode == 1) {  // every block: one lane per block
       dim3 grid((g.nblocks + 63) / 64, B);
       if (g.src_bps == 1)
@@ -935,8 +937,8 @@ int g1s_diff::launch_front(int si) {
 #undef G1S_FB
     }
   }
-  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvFinderEnd], fstream));
-  const bool w_lists = wide_ok(g, batch_far(sl));  // the wide chain: the unit lists come out of the select kernel
+  if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvFinderEnd], fstream));
+  const bool w_lists = p.wide;  // the wide chain: the unit lists come out of the select kernel
   WUnitParams wup{};
   if (w_lists) {
     for (int k = 0; k < 2; ++k) {
@@ -948,18 +950,18 @@ int g1s_diff::launch_front(int si) {
     wup.ub[0] = 4;
     wup.ub[1] = w_ub_c;
   }
-  kmark(sl, fstream, w_lists ? "k2w_select_units" : "k2_flat_select");
+  sl.marks.mark(fstream, w_lists ? "k2w_select_units" : "k2_flat_select");
   if (w_lists) hipLaunchKernelGGL(k2w_select_units, dim3(B, g.nplanes == 3 ? 2 : 1), dim3(kK2Threads), 0, fstream, g, sl.d_records, (const uint8_t *)sl.d_flags, wup);
   else hipLaunchKernelGGL(k2_flat_select, dim3(B), dim3(kK2Threads), 0, fstream, g, sl.d_records, sl.d_flags);
-  if (sl.timed && !sl.chain) HIP_TRY(hipEventRecord(sl.ev[kEvSelectEnd], fstream));
+  if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvSelectEnd], fstream));
   if (!w_lists) {
     // the unit lists (chunks with a flat block) need the flat mask (the wide chain: k2w_select_units has built them)
     const MParams mp = make_mparams(sl);
-    kmark(sl, fstream, "k3m_units");
+    sl.marks.mark(fstream, "k3m_units");
     hipLaunchKernelGGL(k3m_units, dim3((m_nunits + 255) / 256, B), dim3(256), 0, fstream, g, (const uint8_t *)sl.d_records, mp);
   }
-  kmark(sl, fstream, nullptr);
-  if (fstream != stream) HIP_TRY(hipEventRecord(ss.mask_done[si], fstream));
+  sl.marks.mark(fstream, nullptr);
+  if (fstream != p.accum) HIP_TRY(hipEventRecord(ss.mask_done[si], fstream));
   HIP_TRY(hipGetLastError());
   return G1S_OK;
 }
@@ -994,9 +996,19 @@ MParams g1s_diff::make_mparams(const Slot &sl) const {
   return mp;
 }
 
+// the luma launch is queued on plan.accum: the chroma launch and what follows go to plan.rest
+int g1s_diff::to_rest(const BatchPlan &p, int si) {
+  if (p.rest == p.accum) return G1S_OK;
+  HIP_TRY(hipEventRecord(ss.kernels_done[si], p.accum));
+  HIP_TRY(hipStreamWaitEvent(p.rest, ss.kernels_done[si], 0));
+  return G1S_OK;
+}
+
 // the wide chain (k3w.hip.h): luma launch (leaves L behind), chroma launch, k3w_tail = the reducer + the exact kernel for
 // deferred blocks
-int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
+int g1s_diff::accumulate_wide(Slot &sl, int si) {
+  const BatchPlan &p = sl.plan;
+  const Geom &g = p.g;
   const uint32_t B = sl.count;
   const FrameTable ft{sl.d_planes};  // (uploaded by the front half)
   const MParams mp = make_mparams(sl);
@@ -1042,10 +1054,11 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
     char kn_[64];                                                                                                      \
     if (GEN) snprintf(kn_, sizeof(kn_), "k3w_pass<%d, %d, %d, %d, %d, true>", KIND, BP, SX, SY, BD);                   \
     else snprintf(kn_, sizeof(kn_), "k3w_pass<%d, %d, %d, %d>", KIND, BP, SX, SY);                                     \
-    kmark(sl, stream, kn_);                                                                                            \
+    const hipStream_t st_ = KIND ? p.rest : p.accum;                                                                   \
+    sl.marks.mark(st_, kn_);                                                                                           \
     set_kind(KIND);                                                                                                    \
     wq.rev = (w_rev >> KIND) & 1;                                                                                      \
-    hipLaunchKernelGGL((k3w_pass<KIND, BP, SX, SY, BD, GEN>), dim3((uint32_t)Gk[KIND] * B), dim3(kWThreads), lds_, stream, g, wq); \
+    hipLaunchKernelGGL((k3w_pass<KIND, BP, SX, SY, BD, GEN>), dim3((uint32_t)Gk[KIND] * B), dim3(kWThreads), lds_, st_, g, wq); \
   } while (0)
 #define G1S_W(KIND, BP, SX, SY) G1S_WG(KIND, BP, SX, SY, BP, false)
 #define G1S_WB(KIND, SX, SY)                   \
@@ -1077,11 +1090,8 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
     // The chroma launch stays on the main stream behind the luma launch.  Round 3's chain moved it (and what follows) to the
     // copy stream, next to the luma launch of the batch after; with this chain both launches fill every register of the
     // chip and only stretch each other: serial is +2 - 5 % on the 4K job, +10 % at 8K 4:4:4 (profiles/r04_streams.txt).
-    if (side && switches().w_aside) {  // the chroma launch and what follows: next to the luma launch of the batch after
-      HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-      HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
-      stream = ss.copy;
-    }
+    // (G1S_W_ASIDE: the chroma launch and what follows next to the luma launch of the batch after)
+    if (int rc = to_rest(p, si)) return rc;
     if (gen) G1S_WGEN(1, 1, 1);
     else G1S_WK(1);
   }
@@ -1092,8 +1102,8 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
 #undef G1S_W
   // (the record's block statistics and AR sums: k3_ar_generic adds to / overwrites what the launches and the reduction wrote,
   //  and the exact kernel reads the frame number relative to the launch: frame0 is 0 here)
-  kmark(sl, stream, "k3w_tail");
-  hipLaunchKernelGGL(k3w_tail, dim3(kWTailParts + std::min(kWTailChunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
+  sl.marks.mark(p.rest, "k3w_tail");
+  hipLaunchKernelGGL(k3w_tail, dim3(kWTailParts + std::min(kWTailChunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, p.rest, ft, g,
                      sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any, (const long long *)mp.partials, G_cap, Gk[0], Gk[1]);
   return G1S_OK;
 }
@@ -1101,7 +1111,9 @@ int g1s_diff::accumulate_wide(Slot &sl, int si, const Geom &g, hipStream_t &stre
 // the stream chain (k3s.hip.h), what the wide chain falls back on: the fused pass -- planes of the flat blocks' tiles ->
 // residuals, block statistics, exact int8 SYRK on the matrix cores, one partial system per workgroup; the reducer; then the
 // exact int32 kernel for the few blocks next to a residual outside int8
-int g1s_diff::accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &stream, bool side) {
+int g1s_diff::accumulate_stream(Slot &sl, int si) {
+  const BatchPlan &p = sl.plan;
+  const Geom &g = p.g;
   const uint32_t B = sl.count;
   const FrameTable ft{sl.d_planes};  // (uploaded by the front half)
   const MParams mp = make_mparams(sl);
@@ -1137,23 +1149,20 @@ int g1s_diff::accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &st
     static_assert(lds <= 144 * 1024, "the tile buffers fit the LDS the kernel may ask for");                         \
     char kn_[64];                                                                                                    \
     snprintf(kn_, sizeof(kn_), "k3s_fused<%d, %d, %d, %d>", CW, CH, 0, PL);                                          \
-    kmark(sl, stream, kn_);                                                                                          \
+    const hipStream_t st_ = PL ? p.rest : p.accum;                                                                   \
+    sl.marks.mark(st_, kn_);                                                                                         \
     G = G_kind[PL ? 1 : 0];                                                                                          \
     fq.wgs = G;                                                                                                      \
     gr = dim3((uint32_t)G * B);                                                                                      \
-    hipLaunchKernelGGL((k3s_fused<CW, CH, 0, PL>), gr, dim3(kFThreads), lds, stream, g, fq);                         \
+    hipLaunchKernelGGL((k3s_fused<CW, CH, 0, PL>), gr, dim3(kFThreads), lds, st_, g, fq);                            \
   } while (0)
-  // (the chroma launch, the finisher and what follows go to the copy stream -- next to the luma launch of the batch after)
-  const bool chroma_aside = !switches().f_serial;
-#define G1S_FP(CW, CH)                                                    \
-  do {                                                                    \
-    G1S_FS(CW, CH, 0);                                                    \
-    if (side && chroma_aside) {                                           \
-      HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));               \
-      HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));       \
-      stream = ss.copy;                                                   \
-    }                                                                     \
-    G1S_FS(CW, CH, 1);                                                    \
+  // (the chroma launch, the finisher and what follows go to the copy stream -- next to the luma launch of the batch after --
+  //  unless G1S_F_SERIAL)
+#define G1S_FP(CW, CH)                      \
+  do {                                      \
+    G1S_FS(CW, CH, 0);                      \
+    if (int rc = to_rest(p, si)) return rc; \
+    G1S_FS(CW, CH, 1);                      \
   } while (0)
   if (cbw == 0) G1S_FS(0, 0, 0);
   else if (cbw == 16 && cbh == 16) G1S_FP(16, 16);
@@ -1162,24 +1171,25 @@ int g1s_diff::accumulate_stream(Slot &sl, int si, const Geom &g, hipStream_t &st
   else G1S_FP(32, 16);
 #undef G1S_FP
 #undef G1S_FS
-  kmark(sl, stream, "k3m_finish");
-  hipLaunchKernelGGL(k3m_finish, dim3(kMFinishParts * g.nplanes + kMFinishWgs, B), dim3(256), 0, stream, g, mp, G_kind[0], G_kind[1], G_cap,
+  sl.marks.mark(p.rest, "k3m_finish");
+  hipLaunchKernelGGL(k3m_finish, dim3(kMFinishParts * g.nplanes + kMFinishWgs, B), dim3(256), 0, p.rest, g, mp, G_kind[0], G_kind[1], G_cap,
                      (const int32_t *)fq.ustats, sl.d_records);
-  kmark(sl, stream, "k3_ar_generic");
-  hipLaunchKernelGGL(k3_ar_generic, dim3(std::min(kK3Chunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, stream, ft, g,
+  sl.marks.mark(p.rest, "k3_ar_generic");
+  hipLaunchKernelGGL(k3_ar_generic, dim3(std::min(kK3Chunks, g.nblocks), g.nplanes, B), dim3(kK3Threads), 0, p.rest, ft, g,
                      sl.d_records, (const uint8_t *)mp.only, (const uint32_t *)mp.only_any);
   return G1S_OK;
 }
 
 // the batch's results to the host, on the copy stream behind the tail kernels (the main stream goes straight on to the next
 // batch): the records -- or, when the per-frame half of the fold runs on the device, that half and its blobs
-int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
+int g1s_diff::copy_out(Slot &sl, int si) {
+  const BatchPlan &p = sl.plan;
   const uint32_t B = sl.count;
-  HIP_TRY(hipEventRecord(ss.kernels_done[si], stream));
-  HIP_TRY(hipStreamWaitEvent(ss.copy, ss.kernels_done[si], 0));
+  HIP_TRY(hipEventRecord(ss.kernels_done[si], p.rest));
+  HIP_TRY(hipStreamWaitEvent(p.d2h, ss.kernels_done[si], 0));
   if (!device_latest) {
-    HIP_TRY(hipMemcpyAsync(sl.h_records, sl.d_records, L.size * B, hipMemcpyDeviceToHost, ss.copy));
-    HIP_TRY(hipEventRecord(sl.done, ss.copy));
+    HIP_TRY(hipMemcpyAsync(sl.h_records, sl.d_records, L.size * B, hipMemcpyDeviceToHost, p.d2h));
+    HIP_TRY(hipEventRecord(sl.done, p.d2h));
     return G1S_OK;
   }
   // the per-frame half of the fold where the records lie: the host gets 27 KB of latest state a frame instead of the record
@@ -1202,50 +1212,40 @@ int g1s_diff::copy_out(Slot &sl, int si, hipStream_t stream) {
   job.ydec = geom.ydec;
   job.nbw = geom.nbw;
   job.nbh = geom.nbh;
-  // The window (and per-kernel timing: everything on the one stream): behind the tail on the stream that ran it, so in the queue
-  // ahead of the next batch's finder chain, which waits for kernels_done[si] (recorded above, in FRONT of this kernel) on the
-  // side stream.  Otherwise on a stream of its own.  The blobs' copy on the copy stream behind it.
-  hipStream_t lst = stream;
-  if (!sl.timed && !latest_window()) {
-    if (!ensure_latest_streams(ss)) return fail_hip("the device half's streams could not be created");
-    lst = (si & 1) ? ss.latest2 : ss.latest;  // (why two: StreamSet)
-    HIP_TRY(hipStreamWaitEvent(lst, ss.kernels_done[si], 0));
-  }
-  kmark(sl, lst, latest_kernel_name());
-  HIP_TRY(launch_latest(job, B, lst));
-  kmark(sl, lst, nullptr);
-  HIP_TRY(hipEventRecord(ss.latest_done[si], lst));
-  HIP_TRY(hipStreamWaitEvent(ss.copy, ss.latest_done[si], 0));
-  hipStream_t ls = ss.copy;
-  if (!sl.timed) kmark(sl, ls, "blobs D2H");
-  HIP_TRY(hipMemcpyAsync(sl.h_latest, sl.d_latest, blob * B, hipMemcpyDeviceToHost, ls));
-  HIP_TRY(hipMemcpyAsync(sl.h_records + L.size * (B - 1), sl.d_records + L.size * (B - 1), L.size, hipMemcpyDeviceToHost, ls));
-  if (!sl.timed) kmark(sl, ls, nullptr);
-  HIP_TRY(hipEventRecord(sl.done, ls));
+  // (the window: behind the tail on the stream that ran it, so in the queue ahead of the next batch's finder chain, which waits
+  //  for kernels_done[si] -- recorded above, in FRONT of this kernel -- on the side stream)
+  if (p.latest != p.rest) HIP_TRY(hipStreamWaitEvent(p.latest, ss.kernels_done[si], 0));  // (why two of them: StreamSet)
+  sl.marks.mark(p.latest, latest_kernel_name());
+  HIP_TRY(launch_latest(job, B, p.latest));
+  sl.marks.mark(p.latest, nullptr);
+  HIP_TRY(hipEventRecord(ss.latest_done[si], p.latest));
+  HIP_TRY(hipStreamWaitEvent(p.d2h, ss.latest_done[si], 0));
+  sl.marks.mark_trace(p.d2h, "blobs D2H");
+  HIP_TRY(hipMemcpyAsync(sl.h_latest, sl.d_latest, blob * B, hipMemcpyDeviceToHost, p.d2h));
+  HIP_TRY(hipMemcpyAsync(sl.h_records + L.size * (B - 1), sl.d_records + L.size * (B - 1), L.size, hipMemcpyDeviceToHost, p.d2h));
+  sl.marks.mark_trace(p.d2h, nullptr);
+  HIP_TRY(hipEventRecord(sl.done, p.d2h));
   return G1S_OK;
 }
 
 int g1s_diff::launch_back(int si) {
   Slot &sl = slots[si];
-  const Geom g = batch_geom(sl);
-  hipStream_t stream = ss.compute;
-  const bool side = !(switches().one_stream || sl.timed || !ss.flat);
-  if (side) HIP_TRY(hipStreamWaitEvent(stream, ss.mask_done[si], 0));  // the mask, the unit lists
-  // (`stream` comes back as the copy stream when the chain moved its chroma launch and what follows there)
-  int rc = wide_ok(g, batch_far(sl)) ? accumulate_wide(sl, si, g, stream, side) : accumulate_stream(sl, si, g, stream, side);
+  const BatchPlan &p = sl.plan;
+  if (p.finder != p.accum) HIP_TRY(hipStreamWaitEvent(p.accum, ss.mask_done[si], 0));  // the mask, the unit lists
+  int rc = p.wide ? accumulate_wide(sl, si) : accumulate_stream(sl, si);
   if (rc) return rc;
-  kmark(sl, stream, nullptr);
-  if (sl.timed) HIP_TRY(hipEventRecord(sl.ev[kEvEnd], stream));
+  sl.marks.mark(p.rest, nullptr);
+  if (p.timed) HIP_TRY(hipEventRecord(sl.ev[kEvEnd], p.rest));
   HIP_TRY(hipGetLastError());
-  rc = copy_out(sl, si, stream);
+  rc = copy_out(sl, si);
   if (rc) return rc;
   // profiling aid (G1S_D2H_SYNC=1, with G1S_ONE_STREAM=1): the records copy has ended before the next batch's first kernel
   // starts -- under rocprofv3 the copy is a blit kernel that otherwise shares the chip with k1_moments and doubles its time
   // A timed batch (g1s_diff_set_timing: every kernel between two events, "alone on the chip") waits for it too: the copy of
   // batch N next to the kernels of batch N + 1 costs the luma launch 4 % at 8K, and on some boxes of the pool the event pair of
   // the batch's last kernel read 280 - 500 us instead of 45 - 75 with it in flight (profiles/r04_rot.txt vs r04_hwq.txt).
-  if (switches().d2h_sync) HIP_TRY(hipStreamSynchronize(ss.copy));
-  else if (sl.timed) HIP_TRY(hipEventSynchronize(sl.done));  // (the copy's end, whichever stream carried it)
+  if (p.host_waits == HostWait::copy_stream) HIP_TRY(hipStreamSynchronize(p.d2h));
+  else if (p.host_waits == HostWait::done_event) HIP_TRY(hipEventSynchronize(sl.done));  // (the copy's end, whichever stream carried it)
   stats.launches_flat_features++;
   stats.launches_flat_select++;
   stats.launches_ar_accumulate++;
@@ -1319,25 +1319,27 @@ int g1s_diff::drain_front(int si) {
   std::vector<uint32_t> &nflat_v = nflat_s[si];
   std::vector<uint8_t> &latest_stage = stage_s[si];
   HIP_TRY(hipEventSynchronize(sl.done));
-  if (trace && !sl.timed && trace_base) {
+  const std::vector<Marks::Mark> &km = sl.marks.m;
+  const size_t nk = sl.marks.n;
+  if (sl.marks.trace && trace_base) {
     std::lock_guard<std::mutex> lk(trace_mutex);
-    for (size_t i = 0; i < sl.nk; ++i) {
+    for (size_t i = 0; i < nk; ++i) {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, trace_base, sl.kev[i]) != hipSuccess) continue;
+      if (hipEventElapsedTime(&ms, trace_base, km[i].ev) != hipSuccess) continue;
       char b[160];
-      snprintf(b, sizeof(b), "G %12.1f slot %d stream %p %s", ms * 1e3, si, (void *)sl.kstream[i], sl.kname[i].empty() ? "-" : sl.kname[i].c_str());
+      snprintf(b, sizeof(b), "G %12.1f slot %d stream %p %s", ms * 1e3, si, (void *)km[i].stream, km[i].name.empty() ? "-" : km[i].name.c_str());
       trace_lines.emplace_back(b);
     }
     trace_lines.emplace_back(std::string("H ") + std::to_string(trace_now()) + " drained slot " + std::to_string(si));
   }
-  if (sl.timed && sl.chain) {
+  if (sl.plan.chain) {
     // (one pair of events around the batch's chain: what the chain takes alone on the chip with nothing between its kernels
     //  but their own dependencies -- the per-kernel events below each put a barrier packet and a signal between two launches)
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, sl.ev[kEvStart], sl.ev[kEvEnd]));
     stats.ms_chain += ms;
     stats.chain_batches += 1;
-  } else if (sl.timed) {
+  } else if (sl.plan.timed) {
     float ms = 0;
     float ms_mom = 0;  // the finder's moments pass
     HIP_TRY(hipEventElapsedTime(&ms_mom, sl.ev[kEvMomStart], sl.ev[kEvMomEnd]));
@@ -1352,10 +1354,10 @@ int g1s_diff::drain_front(int si) {
     stats.ms_total_gpu += ms;
     {
       std::lock_guard<std::mutex> lk(ktimes_mutex);
-      for (size_t i = 0; i + 1 < sl.nk; ++i) {
-        if (sl.kname[i].empty()) continue;  // (the gap between the two halves of a batch)
-        HIP_TRY(hipEventElapsedTime(&ms, sl.kev[i], sl.kev[i + 1]));
-        auto &kt = ktimes[sl.kname[i]];
+      for (size_t i = 0; i + 1 < nk; ++i) {
+        if (km[i].name.empty()) continue;  // (the gap between the two halves of a batch)
+        HIP_TRY(hipEventElapsedTime(&ms, km[i].ev, km[i + 1].ev));
+        auto &kt = ktimes[km[i].name];
         kt.first += ms;
         kt.second += 1;
       }
@@ -1497,13 +1499,8 @@ void g1s_diff::release() {
     cv_fold.notify_all();
     folder.join();
   }
-  if (ss.compute) (void)hipStreamSynchronize(ss.compute);
-  if (ss.copy) (void)hipStreamSynchronize(ss.copy);
-  if (ss.latest) (void)hipStreamSynchronize(ss.latest);
-  if (ss.latest2) (void)hipStreamSynchronize(ss.latest2);
-  if (ss.flat) (void)hipStreamSynchronize(ss.flat);
-  if (ss.flat2) (void)hipStreamSynchronize(ss.flat2);
-  if (ss.upload) (void)hipStreamSynchronize(ss.upload);
+  for (hipStream_t st : {ss.compute, ss.copy, ss.latest, ss.latest2, ss.flat, ss.flat2, ss.upload})  // (whichever were made)
+    if (st) (void)hipStreamSynchronize(st);
   // (the trace: written when nothing can add to it any more -- the drainer and the folder are joined, the streams idle)
   if (trace) {
     std::lock_guard<std::mutex> lk(trace_mutex);
@@ -1529,7 +1526,6 @@ void g1s_diff::release() {
   }
   h2d_pending.clear(), h2d_free.clear(), h2d_order = Event{}, trace_base = Event{};  // (the streams are idle)
   d_lut = nullptr;  // shared per device
-  stream = nullptr;
   delete fold;
   fold = nullptr;
 }
@@ -1592,8 +1588,7 @@ g1s_diff_t *g1s_diff_new(int64_t fps_num, int64_t fps_den, uint32_t source_bit_d
   g->batch_auto = batch_auto;
   g->device = device;
   make_flat_consts(g->fc);
-  bool streams_ok = acquire_streams(device, g->ss);
-  g->stream = g->ss.compute;
+  bool streams_ok = acquire_streams(device, g->ss);  // (a generator without its streams is never handed out: below)
   // the p/255 table is the same for every generator: one device copy per device, kept
   {
     static std::mutex lut_mutex;
