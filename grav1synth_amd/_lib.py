@@ -170,6 +170,30 @@ class G1SMeasureRecord(C.Structure):
     ]
 
 
+class G1SSurface(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("bytes_per_sample", C.c_uint8),
+        ("xdec", C.c_uint8),
+        ("ydec", C.c_uint8),
+        ("nplanes", C.c_uint8),
+        ("bit_depth", C.c_uint8),
+        ("msb_aligned", C.c_uint8),
+        ("data", C.c_void_p * 3),
+        ("stride_bytes", C.c_size_t * 3),
+        ("on_device", C.c_int32),
+    ]
+
+
+class G1SSurfaceOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("device", C.c_int32),
+        ("batch_frames", C.c_uint32),
+    ]
+
+
 NEXT_FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(G1SFrame))
 
 # every symbol include/g1s_diff.h declares: (name, restype, argtypes)
@@ -295,6 +319,13 @@ SYMBOLS = [
                                           C.c_size_t]),
     ("g1s_check_y4m_files", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts), C.POINTER(G1SGrainOpts),
                                         C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_surface_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SSurfaceOpts)]),
+    ("g1s_surface_unpack", C.c_int, [C.c_void_p, C.POINTER(G1SSurface), C.POINTER(G1SFrame)]),
+    ("g1s_surface_pack", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SSurface)]),
+    ("g1s_surface_sync", C.c_int, [C.c_void_p]),
+    ("g1s_surface_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_surface_last_error", C.c_char_p, [C.c_void_p]),
+    ("g1s_surface_free", None, [C.c_void_p]),
 ]
 
 _lib = None

@@ -40,7 +40,8 @@ struct PlaneGeom {
 struct Layout {
   size_t row[3] = {0, 0, 0}, off[3] = {0, 0, 0}, frame = 0;
   Layout() = default;
-  Layout(const PlaneGeom &g, size_t row_align, size_t plane_align) {
+  template <class Geom>  // (PlaneGeom, or SurfaceGeom below: nplanes, row_bytes(c), ph(c))
+  Layout(const Geom &g, size_t row_align, size_t plane_align) {
     for (int c = 0; c < g.nplanes; ++c) {
       row[c] = align_up(g.row_bytes(c), row_align);
       off[c] = frame;
@@ -54,7 +55,8 @@ struct Layout {
 };
 constexpr size_t kStageRowAlign = 16, kStagePlaneAlign = 256;
 // a host frame's copy on the device: rows to 16 bytes, planes to 256
-inline Layout staging_layout(const PlaneGeom &g) { return Layout(g, kStageRowAlign, kStagePlaneAlign); }
+template <class Geom>
+inline Layout staging_layout(const Geom &g) { return Layout(g, kStageRowAlign, kStagePlaneAlign); }
 // a frame of a .y4m file: no padding anywhere
 inline Layout packed_layout(const PlaneGeom &g) { return Layout(g, 1, 1); }
 
@@ -81,6 +83,58 @@ inline Refusal check_frame_pair(const g1s_frame_t &in, const g1s_frame_t &out, u
     if (!in.data[c] || !out.data[c] || in.stride_bytes[c] < g.row_bytes(c) || out.stride_bytes[c] < g.row_bytes(c) ||
         in.stride_bytes[c] > 0xffffffffu || out.stride_bytes[c] > 0xffffffffu || (bps == 2 && ((in.stride_bytes[c] | out.stride_bytes[c]) & 1)))
       return {G1S_ERR_INVALID, "bad plane pointer or row stride"};
+  return {};
+}
+
+// The planes of a decoder surface (g1s_surface_t, rule 1): luma W x H; with two planes, plane 1 is rows of 2 cw interleaved
+// Cb, Cr samples; with three, the planes of a frame.
+struct SurfaceGeom {
+  PlaneGeom frame;  // the frame the surface unpacks to (nplanes 1 or 3)
+  int nplanes = 0;  // the surface's own: 1, 2 or 3
+  SurfaceGeom() = default;
+  SurfaceGeom(const g1s_surface_t &s, uint32_t bps) : nplanes(s.nplanes) {
+    frame.W = (int)s.width, frame.H = (int)s.height, frame.subx = s.xdec, frame.suby = s.ydec, frame.nplanes = s.nplanes == 1 ? 1 : 3, frame.bps = bps;
+  }
+  bool interleaved() const { return nplanes == 2; }
+  size_t ph(int c) const { return frame.ph(c); }
+  size_t row_bytes(int c) const { return c && interleaved() ? 2 * frame.row_bytes(1) : frame.row_bytes(c); }
+};
+
+inline bool spans_overlap(const uint8_t *a, size_t a_stride, size_t a_rows, size_t a_row, const uint8_t *b, size_t b_stride, size_t b_rows, size_t b_row) {
+  const uint8_t *ae = a + a_stride * (a_rows - 1) + a_row, *be = b + b_stride * (b_rows - 1) + b_row;
+  return a < be && b < ae;
+}
+
+// The checks of a surface and a frame handed to a converter made by g1s_surface_new for `bit_depth`; `unpack`: the surface
+// is the input.  Sample size and depth, msb_aligned, the plane counts of the two sides, the geometry of the input, the two
+// geometries against each other, per plane a pointer and a row stride that holds the row (2 cw samples for the interleaved
+// plane), fits 32 bits and, for 16-bit samples, is even -- and no byte of one side inside the extent of a plane of the other.
+inline Refusal check_surface_pair(const g1s_surface_t &s, const g1s_frame_t &f, uint32_t bit_depth, bool unpack) {
+  const uint32_t bps = bit_depth > 8 ? 2 : 1;
+  if (s.bytes_per_sample != bps || f.bytes_per_sample != bps)
+    return {G1S_ERR_INVALID, "bytes_per_sample does not match the bit depth given to g1s_surface_new"};
+  if (s.bit_depth != bit_depth) return {G1S_ERR_INVALID, "the surface's bit_depth is not the one given to g1s_surface_new"};
+  if (s.msb_aligned && bps == 1) return {G1S_ERR_INVALID, "msb_aligned needs two-byte samples"};
+  if (f.nplanes != 1 && f.nplanes != 3) return {G1S_ERR_INVALID, "a frame has 1 or 3 planes: two planes are a surface's layout"};
+  if (s.nplanes < 1 || s.nplanes > 3) return {G1S_ERR_INVALID, "a surface has 1, 2 or 3 planes"};
+  const uint32_t iw = unpack ? s.width : f.width, ih = unpack ? s.height : f.height, ix = unpack ? s.xdec : f.xdec, iy = unpack ? s.ydec : f.ydec;
+  if (iw < 1 || ih < 1 || iw > 65536u || ih > 65536u || ix > 1 || iy > ix)
+    return {G1S_ERR_INVALID, "unsupported surface geometry (4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)"};
+  if ((s.nplanes == 1) != (f.nplanes == 1))
+    return {G1S_ERR_DIM_MISMATCH, "surface and frame planes do not correspond (1 and 1; 2 or 3 on the surface and 3 on the frame)"};
+  if (s.width != f.width || s.height != f.height || s.xdec != f.xdec || s.ydec != f.ydec) return {G1S_ERR_DIM_MISMATCH, "surface and frame geometry differ"};
+  const SurfaceGeom g(s, bps);
+  for (int c = 0; c < g.nplanes; ++c)
+    if (!s.data[c] || s.stride_bytes[c] < g.row_bytes(c) || s.stride_bytes[c] > 0xffffffffu || (bps == 2 && (s.stride_bytes[c] & 1)))
+      return {G1S_ERR_INVALID, "bad surface plane pointer or row stride"};
+  for (int c = 0; c < g.frame.nplanes; ++c)
+    if (!f.data[c] || f.stride_bytes[c] < g.frame.row_bytes(c) || f.stride_bytes[c] > 0xffffffffu || (bps == 2 && (f.stride_bytes[c] & 1)))
+      return {G1S_ERR_INVALID, "bad frame plane pointer or row stride"};
+  for (int a = 0; a < g.nplanes; ++a)
+    for (int b = 0; b < g.frame.nplanes; ++b)
+      if (spans_overlap(static_cast<const uint8_t *>(s.data[a]), s.stride_bytes[a], g.ph(a), g.row_bytes(a), static_cast<const uint8_t *>(f.data[b]),
+                        f.stride_bytes[b], g.frame.ph(b), g.frame.row_bytes(b)))
+        return {G1S_ERR_INVALID, "surface and frame planes overlap: a converter needs distinct buffers"};
   return {};
 }
 
@@ -215,6 +269,11 @@ inline HostPlanes host_planes(const g1s_frame_t &f) {
   for (int c = 0; c < 3; ++c) h.data[c] = const_cast<void *>(f.data[c]), h.stride[c] = f.stride_bytes[c];
   return h;
 }
+inline HostPlanes host_planes(const g1s_surface_t &f) {
+  HostPlanes h{};
+  for (int c = 0; c < f.nplanes; ++c) h.data[c] = const_cast<void *>(f.data[c]), h.stride[c] = f.stride_bytes[c];
+  return h;
+}
 
 // The base of an operation that takes frames one at a time and launches them a batch at a time on a stream of its own.
 // (The stream comes first: it goes last, after the wait in *_free and after everything that was used on it.)
@@ -236,6 +295,10 @@ struct BatchedOp {
   PlaneGeom geom;
   Layout stage;
   DevBuf<uint8_t> d_stage_in[2], d_stage_out;
+  // the surface side of a converter (surface.hip), set beside the frame's: its planes and their staging layout; a host
+  // surface that comes in takes input ring 0, one that goes out the output buffer, in the surface's layout
+  SurfaceGeom sgeom;
+  Layout sstage;
 
   int fail(int code, const std::string &m) {
     if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
@@ -284,6 +347,28 @@ struct BatchedOp {
     if (in.on_device == 0 && hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
     return G1S_OK;
   }
+  // (after set_frame_geometry of the frame the surface corresponds to)
+  void set_surface_geometry(const g1s_surface_t &s) { sgeom = SurfaceGeom(s, bps), sstage = staging_layout(sgeom); }
+  // stage_in for a surface: the interleaved plane's rows are 2 cw samples long
+  int stage_in(const g1s_surface_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3]) {
+    for (int c = 0; c < sgeom.nplanes; ++c) {
+      if (in.on_device == 1) {
+        plane[c] = static_cast<const uint8_t *>(in.data[c]), stride[c] = (uint32_t)in.stride_bytes[c];
+        continue;
+      }
+      if (!d_stage_in[0] && hipMalloc((void **)&d_stage_in[0].p, sstage.frame * slots) != hipSuccess)
+        return fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
+      uint8_t *dst = d_stage_in[0] + sstage.frame * slot + sstage.off[c];
+      if (hipMemcpy2DAsync(dst, sstage.row[c], in.data[c], in.stride_bytes[c], sgeom.row_bytes(c), sgeom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
+      plane[c] = dst, stride[c] = (uint32_t)sstage.row[c];
+    }
+    return G1S_OK;
+  }
+  int wait_host_input(const g1s_surface_t &in) {
+    if (in.on_device == 0 && hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, "copy of a host surface to the device failed");
+    return G1S_OK;
+  }
   int need_stage_out(uint32_t slots) {
     if (!d_stage_out && hipMalloc((void **)&d_stage_out.p, stage.frame * slots) != hipSuccess)
       return fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
@@ -294,6 +379,18 @@ struct BatchedOp {
   int copy_back(uint32_t slot, const HostPlanes &h) {
     for (int c = 0; c < geom.nplanes; ++c)
       G1S_OP_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], stage_out(slot, c), stage.row[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToHost, stream));
+    return G1S_OK;
+  }
+  // the output buffer in the surface's layout, and a slot of it back to a host surface's planes
+  int need_surface_stage_out(uint32_t slots) {
+    if (!d_stage_out && hipMalloc((void **)&d_stage_out.p, sstage.frame * slots) != hipSuccess)
+      return fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
+    return G1S_OK;
+  }
+  uint8_t *surface_stage_out(uint32_t slot, int c) const { return d_stage_out + sstage.frame * slot + sstage.off[c]; }
+  int copy_back_surface(uint32_t slot, const HostPlanes &h) {
+    for (int c = 0; c < sgeom.nplanes; ++c)
+      G1S_OP_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], surface_stage_out(slot, c), sstage.row[c], sgeom.row_bytes(c), sgeom.ph(c), hipMemcpyDeviceToHost, stream));
     return G1S_OK;
   }
   int wait() {

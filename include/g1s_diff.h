@@ -628,6 +628,70 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
 int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
                             const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap);
 
+/* ---- decoder surfaces: NV12, P010 / P012 / P016 and MSB-aligned planes, to and from g1s_frame_t on the device ----
+ * A hardware decoder (and an encoder on the same device) does not hold planar frames with the sample in the low bits: it
+ * holds SEMI-PLANAR surfaces, one luma plane and one plane of interleaved Cb, Cr pairs, and above 8 bits the sample sits in
+ * the HIGH bits of its little-endian 16-bit word.  A converter turns such a surface into the g1s_frame_t every operation
+ * here takes (unpack) and a frame into such a surface (pack): a permutation and a shift of integers, exact.
+ *   1. Chroma size.  Chroma is cw = (width + xdec) >> xdec by ch = (height + ydec) >> ydec samples.  A row of the
+ *      interleaved plane holds 2 cw samples: Cb[0], Cr[0], Cb[1], Cr[1], ...; its stride must hold 2 cw bytes_per_sample
+ *      bytes.
+ *   2. Shift.  sh = msb_aligned ? 16 - bit_depth : 0.
+ *   3. Unpack (surface to frame): frame = word >> sh.  The low sh bits of a word are ignored, whatever they hold.  With
+ *      sh == 0 a word is copied as it is, and nothing is masked.
+ *   4. Pack (frame to surface): word = (sample << sh) & 0xffff.  The low sh bits are written as zeros.
+ *   5. Untouched bytes.  No byte outside the rows' samples is written, in either direction: not the pitch's padding and
+ *      not the margin.
+ *   6. No overlap.  in and out must not overlap.
+ *   nplanes  msb_aligned  layouts
+ *      2         0        NV12 / NV16 / NV24 (8-bit)
+ *      2         1        P010 / P012 / P016, P210 / P216, P410 / P416
+ *      3         1        planar MSB-aligned 16-bit 4:4:4 and its relatives
+ *      1       0 or 1     monochrome, either alignment
+ *   (nplanes 3 with msb_aligned 0 is a plain copy and is accepted.)
+ * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per batch on the converter's own
+ * stream: a frame goes to another operation only after g1s_surface_sync.  Errors are sticky (g1s_surface_last_error). */
+typedef struct {
+  uint32_t width, height;      /* luma size in samples */
+  uint8_t  bytes_per_sample;   /* 1 or 2 */
+  uint8_t  xdec, ydec;         /* as g1s_frame_t */
+  uint8_t  nplanes;            /* 1: luma only; 2: luma + one plane of interleaved Cb,Cr pairs; 3: planar */
+  uint8_t  bit_depth;          /* 8..16; must be the converter's */
+  uint8_t  msb_aligned;        /* 1: a sample sits in the HIGH bit_depth bits of its 16-bit word (bytes_per_sample 2 only) */
+  const void *data[3];         /* nplanes == 2: data[1] is the CbCr plane, data[2] is ignored */
+  size_t   stride_bytes[3];
+  int32_t  on_device;          /* as g1s_frame_t: 0 host, 1 device, 2 pinned host */
+} g1s_surface_t;
+typedef struct {
+  uint32_t struct_size; /* sizeof(g1s_surface_opts_t) */
+  int32_t device;       /* HIP device ordinal; -1 = current device */
+  uint32_t batch_frames;
+} g1s_surface_opts_t;
+typedef struct g1s_surface_conv g1s_surface_conv_t;
+/* bit_depth 8 .. 16 (8: one-byte samples; above: two-byte).  NULL on failure, the reason from g1s_last_global_error().
+ * opts == NULL: current device, defaults. */
+g1s_surface_conv_t *g1s_surface_new(uint32_t bit_depth, const g1s_surface_opts_t *opts);
+/* One surface into one frame (rule 3) / one frame into one surface (rule 4).  in / out follow on_device independently, as
+ * in g1s_grain_frame: 0 = host (in: copied before the call returns; out: written by g1s_surface_sync at the latest),
+ * 1 = device, 2 = pinned host (copies queued).  Device and pinned planes of in must stay valid and unmodified, and every
+ * plane of out must stay valid, until g1s_surface_sync.  in and out have the same geometry, and their nplanes
+ * correspond: 1 and 1; 2 or 3 on the surface and 3 on the frame.  One converter may mix the two calls and mix layouts: a
+ * call whose direction, geometry or layout differs from the one before it drains the queue first (the host planes of
+ * queued out frames are then complete).  Refused with G1S_ERR_INVALID (G1S_ERR_DIM_MISMATCH where in and out differ in
+ * geometry or their nplanes do not correspond): bytes_per_sample or bit_depth that are not the converter's; msb_aligned
+ * with one-byte samples; a frame of 2 planes; width or height 0 or above 65536; xdec > 1 or ydec > xdec; a null plane;
+ * a stride that does not hold the row (rule 1), is above 0xffffffff or, for 16-bit samples, is odd; overlapping in
+ * and out (rule 6). */
+int g1s_surface_unpack(g1s_surface_conv_t *, const g1s_surface_t *in, g1s_frame_t *out);
+int g1s_surface_pack(g1s_surface_conv_t *, const g1s_frame_t *in, g1s_surface_t *out);
+/* Launches what is queued and waits: the out planes of every call so far are complete. */
+int g1s_surface_sync(g1s_surface_conv_t *);
+/* HIP-event time of the kernels so far, milliseconds, and the frames they covered (enable = 1: timed from the next
+ * batch on; a timed batch is waited for).  tools/bench_surface.py. */
+int g1s_surface_set_timing(g1s_surface_conv_t *, int enable, double *ms, uint64_t *frames);
+const char *g1s_surface_last_error(const g1s_surface_conv_t *);
+void g1s_surface_free(g1s_surface_conv_t *);
+
 #ifdef __cplusplus
 }
 #endif
