@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("G1S_LIB") or os.path.join(_HERE, "libg1s_diff.so")  # (G1S_LIB: an instrumented build, tools/ only)
 
 G1S_OK = 0
+G1S_DENOISE_JOINT_CHROMA = 1
 G1S_ERR_CAPACITY = -8
 ERRORS = {
     -1: "G1S_ERR_INVALID",
@@ -294,6 +295,11 @@ SYMBOLS = [
     ("g1s_grain_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SGrainOpts), C.c_char_p, C.c_size_t]),
     ("g1s_denoise_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts)]),
     ("g1s_denoise_new_temporal", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts), C.c_uint32]),
+    ("g1s_denoise_new_ex", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32]),
+    ("g1s_denoise_weights_ex", C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("g1s_denoise_y4m_file_ex", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("g1s_denoise_drain", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("g1s_denoise_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
     ("g1s_denoise_sync", C.c_int, [C.c_void_p]),

@@ -68,11 +68,14 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
     p.add_argument("--chroma-strength", type=float, default=0.0, help="strength for the chroma planes (default: --strength)")
     p.add_argument("--temporal-radius", type=int, default=0, metavar="D",
                    help="temporal radius D, 0..3 (default 0): the mean also runs over the search windows of the D frames before and after")
+    p.add_argument("--joint-chroma", action="store_true",
+                   help="luma-guided joint chroma: Cb and Cr share one weight, taken from both and the luma at the same place "
+                        "(KNLMeansCL's channels=\"YUV\" in structure; off by default)")
 
 
 def _denoise_parameters(args) -> dict:
     return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
-                chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius)
+                chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma)
 
 
 def build_parser() -> argparse.ArgumentParser:

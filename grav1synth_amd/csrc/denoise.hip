@@ -5,8 +5,10 @@
 // same bits.  Two kernels, a workgroup per (tile, plane of the class, frame), the phases of denoise_tile.hip.h:
 // kd_nlm<S, BPS> for one frame on its own (temporal radius 0, rules 1 - 4) and kd_nlm_t<S, BPS>, which goes on over the
 // frames around it (rules 5 - 7).  A batch of frames goes out as one launch per plane class (luma; the two chroma planes)
-// on the denoiser's own stream.  Planes are independent, but `out` must not overlap `in`: a tile reads the halo its
-// neighbours write.
+// on the denoiser's own stream.  Under G1S_DENOISE_JOINT_CHROMA (rules 8 - 11) the chroma launch is kd_nlm_j<S, BPS> or
+// kd_nlm_jt<S, BPS> instead: a workgroup per (chroma tile, frame) that filters both chroma planes with one weight.
+// Planes are independent (under the flag the chroma launch also reads the luma input), but `out` must not overlap `in`: a
+// tile reads the halo its neighbours write.
 //
 // The engine numbers the frames handed over since the denoiser was made.  With temporal radius D a frame is launched once
 // the D frames after it are there (or the clip ends), so the queue holds the frames not yet launched and, in front of
@@ -87,7 +89,48 @@ __global__ __launch_bounds__(kThreads) void kd_nlm(DenoiseParams p) {
                   ty * kTH, [] { __syncthreads(); });
 }
 
-// the two kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
+// the joint chroma kernels (rules 8 - 11t): a workgroup per (chroma tile, frame) filters Cb and Cr with one weight
+struct DenoiseParamsJ {
+  const DenoiseJob *jobs;
+  const uint16_t *table;  // rule 10's 1024 weights
+  int q, A;
+  JointShape s;
+  int tiles_x;
+};
+
+struct DenoiseParamsJT {
+  const DenoiseJobT *jobs;
+  const uint16_t *table;
+  int q, A;
+  JointShape s;
+  int tiles_x;
+  int nnb;  // 2 D
+};
+
+__device__ inline JointPlanes joint_planes(const DenoiseJob &f) { return JointPlanes{f.in[1], f.in[2], f.in[0], f.in_stride[1], f.in_stride[2], f.in_stride[0]}; }
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_j(DenoiseParamsJ p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJob &job = p.jobs[blockIdx.z];
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  dn_tile_j<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job), p.s, job.out[1], job.out_stride[1], job.out[2],
+                    job.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); });
+}
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_jt(DenoiseParamsJT p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobT &job = p.jobs[blockIdx.z];
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
+  dn_tile_jt<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, p.s, job.f.out[1], job.f.out_stride[1],
+                     job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); });
+}
+
+// the kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
 struct Plain {
   using Params = DenoiseParams;
   template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
@@ -95,6 +138,15 @@ struct Plain {
 struct Temporal {
   using Params = DenoiseParamsT;
   template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_t<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+
+struct Joint {
+  using Params = DenoiseParamsJ;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_j<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+struct JointTemporal {
+  using Params = DenoiseParamsJT;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jt<S, BPS>), grid, dim3(kThreads), lds, st, p); }
 };
 
 // the family's kernel for patch radius S and `bps` bytes a sample; false: there is none
@@ -113,12 +165,12 @@ bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t 
   return false;
 }
 
-// rule 3.  "" when fine.
-std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTable], uint32_t *q_out) {
+// rule 3, for patches of `planes` planes (rule 10: 3).  "" when fine.
+std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTable], uint32_t *q_out, uint32_t planes = 1) {
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return "denoise is defined for bit depths 8, 10 and 12";
   if (S < 1 || S > (uint32_t)kMaxS) return "patch_radius must be 1..4";
   if (!(h > 0.0) || !(h <= 1000.0)) return "strength must be greater than 0 and at most 1000";
-  const double n = (double)((2 * S + 1) * (2 * S + 1)), den = n * h * h * std::pow(4.0, (double)bit_depth - 8.0);
+  const double n = (double)(planes * (2 * S + 1) * (2 * S + 1)), den = n * h * h * std::pow(4.0, (double)bit_depth - 8.0);
   auto entry = [&](int i, uint32_t q) { return std::floor(4096.0 * std::exp(-(((double)i + 0.5) * std::ldexp(1.0, (int)q)) / den) + 0.5); };
   uint32_t q = 0;
   while (entry(kTable - 1, q) != 0.0) ++q;
@@ -136,7 +188,8 @@ using namespace g1s_op;
 // (the stream, the sticky error, the parameter sets' turn and the staging of host frames: BatchedOp, frame_op.h)
 struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
-  uint32_t q[2] = {0, 0};  // luma, chroma
+  bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j / kd_nlm_jt for their chroma
+  uint32_t q[3] = {0, 0, 0};  // luma, chroma, joint chroma
   Event ev[2];
   // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
   // output goes (out[c] is null for a host frame: a slot of the output staging buffer is chosen at the launch)
@@ -151,7 +204,7 @@ struct g1s_denoise : BatchedOp {
   std::deque<Queued> queue;
   uint64_t frames_in = 0, first_queued = 0, next_launch = 0, clip_first = 0, frames_complete = 0;
   ParamSets<uint8_t> p_jobs;  // DenoiseJob or, with a temporal radius, DenoiseJobT
-  DevBuf<uint16_t> d_tables;  // [2][1024]
+  DevBuf<uint16_t> d_tables;  // [3][1024]
   double ms_kernel = 0;
   uint64_t frames_timed = 0;
 
@@ -161,6 +214,7 @@ struct g1s_denoise : BatchedOp {
   uint32_t ring() const { return batch + 2 * D; }
   const Queued &frame(uint64_t n) const { return queue[(size_t)(n - first_queued)]; }
   int launch(int set, uint32_t nframes, int plane0, int nplanes_in_class);
+  int launch_joint(int set, uint32_t nframes);
   int flush(uint32_t nframes);
   int launch_up_to(uint64_t limit);
   int end_clip();
@@ -183,6 +237,30 @@ int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_cl
     DenoiseParams p{};
     fill(p);
     found = launch_family<Plain>(S, bps, grid, (size_t)tg.bytes, stream, p);
+  }
+  if (!found) return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
+  G1S_OP_TRY(hipGetLastError());
+  return G1S_OK;
+}
+
+// both chroma planes of the batch's frames through the joint kernel: grid (tiles, 1, frames)
+int g1s_denoise::launch_joint(int set, uint32_t nframes) {
+  const int cw = (int)geom.pw(1), ch = (int)geom.ph(1), tiles_x = (cw + kTW - 1) / kTW;
+  auto fill = [&](auto &p) {
+    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p), p.table = d_tables + 2 * kTable, p.q = (int)q[2], p.A = (int)A;
+    p.s = JointShape{geom.W, geom.H, geom.subx, geom.suby, cw, ch}, p.tiles_x = tiles_x;
+  };
+  const dim3 grid((unsigned)(tiles_x * ((ch + kTH - 1) / kTH)), 1u, nframes);
+  const JointGeom jg = joint_geom(tile_geom((int)A, (int)S));
+  bool found;
+  if (D) {
+    DenoiseParamsJT t{};
+    fill(t), t.nnb = (int)(2 * D);
+    found = launch_family<JointTemporal>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
+  } else {
+    DenoiseParamsJ p{};
+    fill(p);
+    found = launch_family<Joint>(S, bps, grid, (size_t)jg.bytes, stream, p);
   }
   if (!found) return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
   G1S_OP_TRY(hipGetLastError());
@@ -223,7 +301,7 @@ int g1s_denoise::flush(uint32_t nframes) {
   G1S_OP_TRY(p_jobs.upload(set, job_bytes() * nframes, stream));
   if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
   if ((rc = launch(set, nframes, 0, 1)) != 0) return rc;
-  if (geom.nplanes == 3 && (rc = launch(set, nframes, 1, 2)) != 0) return rc;
+  if (geom.nplanes == 3 && (rc = joint ? launch_joint(set, nframes) : launch(set, nframes, 1, 2)) != 0) return rc;
   if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
   if ((rc = set_done(set)) != 0) return rc;
   for (uint32_t i = 0; host_outs && i < nframes; ++i)
@@ -261,8 +339,13 @@ int g1s_denoise::end_clip() {
 extern "C" {
 
 int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double strength, uint16_t T[1024], uint32_t *q) {
+  return g1s_denoise_weights_ex(bit_depth, patch_radius, strength, 0, T, q);
+}
+
+int g1s_denoise_weights_ex(uint32_t bit_depth, uint32_t patch_radius, double strength, uint32_t flags, uint16_t T[1024], uint32_t *q) {
   if (!T || !q) return G1S_ERR_INVALID;
-  const std::string why = make_table(bit_depth, patch_radius, strength, T, q);
+  const std::string why = flags & ~G1S_DENOISE_JOINT_CHROMA ? std::string("unknown denoise flags")
+                                                            : make_table(bit_depth, patch_radius, strength, T, q, flags & G1S_DENOISE_JOINT_CHROMA ? 3 : 1);
   if (!why.empty()) {
     g1s_set_global_error_(why.c_str());
     return G1S_ERR_INVALID;
@@ -273,6 +356,10 @@ int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double streng
 g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return g1s_denoise_new_temporal(bit_depth, opts, 0); }
 
 g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius) {
+  return g1s_denoise_new_ex(bit_depth, opts, temporal_radius, 0);
+}
+
+g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags) {
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -289,11 +376,16 @@ g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_op
     g1s_set_global_error_("temporal_radius must be 0..3");
     return nullptr;
   }
-  std::vector<uint16_t> tables(2 * kTable);
-  uint32_t q[2];
+  if (flags & ~G1S_DENOISE_JOINT_CHROMA) {
+    g1s_set_global_error_("unknown denoise flags");
+    return nullptr;
+  }
+  std::vector<uint16_t> tables(3 * kTable);
+  uint32_t q[3];
   std::string why = make_table(bit_depth, S, h, tables.data(), &q[0]);
   if (why.empty()) {
     why = make_table(bit_depth, S, hc, tables.data() + kTable, &q[1]);
+    if (why.empty()) why = make_table(bit_depth, S, hc, tables.data() + 2 * kTable, &q[2], 3);
     if (!why.empty()) why = "chroma_" + why;
   }
   if (!why.empty()) {
@@ -306,8 +398,22 @@ g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_op
     g1s_set_global_error_(why.c_str());
     return nullptr;
   }
+  // the LDS a workgroup of the largest kernel these parameters select asks for, against what the device gives one
+  {
+    const TileGeom tg = tile_geom((int)A, (int)S);
+    const JointGeom jg = joint_geom(tg);
+    const bool joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
+    const int need = temporal_radius ? (joint ? jg.bytes_t : tg.bytes_t) : (joint ? jg.bytes : tg.bytes);
+    int limit = 0;
+    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || need > limit) {
+      g1s_set_global_error_(("these parameters need " + std::to_string(need) + " bytes of LDS a workgroup" + (joint ? " (joint chroma)" : "") +
+                             "; the device allows " + std::to_string(limit)).c_str());
+      return nullptr;
+    }
+  }
   g1s_denoise *g = new g1s_denoise;
-  g->A = A, g->S = S, g->D = temporal_radius, g->q[0] = q[0], g->q[1] = q[1];
+  g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
+  for (int i = 0; i < 3; ++i) g->q[i] = q[i];
   bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
   for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
   ok = ok && g->p_jobs.alloc(g->job_bytes() * g->batch) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
@@ -408,14 +514,19 @@ int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_
 
 int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
                                       size_t cap) {
+  return g1s_denoise_y4m_file_ex(in, out, opts, temporal_radius, 0, err, cap);
+}
+
+int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, char *err,
+                                size_t cap) {
   // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
   // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
   struct Driver {
     const g1s_denoise_opts_t *opts;
-    uint32_t D;
+    uint32_t D, flags;
     g1s_denoise_t *g = nullptr;
     const int new_failed = G1S_ERR_INVALID;
-    bool open(const g1s_y4m_info_t &i) { return (g = g1s_denoise_new_temporal(i.bit_depth, opts, D)) != nullptr; }
+    bool open(const g1s_y4m_info_t &i) { return (g = g1s_denoise_new_ex(i.bit_depth, opts, D, flags)) != nullptr; }
     uint32_t batch() const { return g->batch; }
     uint32_t ring() const { return g->batch + g->D; }
     int frame(int64_t, const g1s_frame_t *fin, g1s_frame_t *fout) { return g1s_denoise_frame(g, fin, fout); }
@@ -423,7 +534,7 @@ int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s
     const char *last_error() const { return g1s_denoise_last_error(g); }
     void close() { g1s_denoise_free(g); }
   };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius});
+  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags});
 }
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
@@ -438,12 +549,19 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
 
 int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                         const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames_out, char *err, size_t cap) {
+  return g1s_diff_y4m_file_denoised_ex(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, 0, frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, uint64_t *frames_out, char *err,
+                                  size_t cap) {
   auto refuse = [&](int code, const std::string &m) {
     if (err && cap) snprintf(err, cap, "%s", m.c_str());
     return code;
   };
   if (frames_out) *frames_out = 0;
   if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
+  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
   const std::string header = y4m_header_line(source);
   g1s_y4m_t *y = g1s_y4m_open(source, err, cap);
   if (!y) return G1S_ERR_INVALID;
@@ -480,7 +598,7 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
     if (dopts) d = *dopts;
     d.struct_size = sizeof d;
     d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = g1s_denoise_new_temporal(info.bit_depth, &d, temporal_radius);
+    dn = g1s_denoise_new_ex(info.bit_depth, &d, temporal_radius, flags);
   }
   if (!dn) {
     rc = G1S_ERR_INVALID, why = g1s_last_global_error();

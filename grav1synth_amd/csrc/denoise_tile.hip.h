@@ -24,6 +24,8 @@
 // is no half plane to save, and the weight is read at p only.  Hb and Wb as sized for the frame itself are large enough.
 // The numerator of rule 7 needs 64 bits (dn_store_t).
 //
+// The joint chroma filter (rules 8 - 11t, kd_nlm_j and kd_nlm_jt) is at the end of this file.
+//
 // Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
 // run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.
 #pragma once
@@ -355,6 +357,238 @@ G1S_DN_HD void dn_tile_t(int tid, const TileGeom &g, uint8_t *lds, const uint16_
       }
   }
   dn_store_t<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+// ---- luma-guided joint chroma (rules 8 - 11t, kd_nlm_j and kd_nlm_jt): Cb, Cr and the guide G as one weight ---------
+//
+// Three sample arrays in the layout of L, JointGeom::LP samples apart: Cb, Cr, G.  G is the frame's input luma at chroma
+// resolution (rule 8), formed while staging.  Hb, Wb and T are the ones of tile_geom: the squared differences of the three
+// arrays are summed in registers before the sliding sum (rule 9, exact in uint32_t; dn_weights and dn_weights_t work in
+// uint32_t already), the weights are made once, and one read of Wb feeds the accumulators of both chroma planes.  The
+// temporal kernel keeps the three arrays of one neighbour frame behind them.
+struct JointGeom {
+  int LP;  // samples from one array to the next
+  int offH, offL, offW, offT, bytes;
+  int offN, bytes_t;
+};
+
+G1S_DN_HD JointGeom joint_geom(const TileGeom &g) {
+  JointGeom j;
+  j.LP = (g.LS * g.LH + 7) & ~7;
+  j.offH = 0;
+  j.offL = g.HS * g.HR * 4;
+  j.offW = (j.offL + 3 * j.LP * 2 + 15) & ~15;
+  j.offT = (j.offW + g.WS * g.WR * 2 + 15) & ~15;
+  j.bytes = j.offT + kTable * 2;
+  j.offN = (j.bytes + 15) & ~15;
+  j.bytes_t = j.offN + 3 * j.LP * 2;
+  return j;
+}
+
+template <int BPS>
+G1S_DN_HD uint32_t dn_sample(const uint8_t *row, int x) {
+  return BPS == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(row)[x] : (uint32_t)row[x];
+}
+
+// rule 8 into L: the tile at (x0, y0) of the cw x ch chroma grid and its halo, chroma coordinates clamped to that grid;
+// each sample the rounded mean of a (1 << xdec) x (1 << ydec) box of the W x H luma plane, luma coordinates clamped to it
+template <int BPS>
+G1S_DN_HD void dn_stage_guide(int tid, const TileGeom &g, uint16_t *L, const uint8_t *luma, uint32_t stride, int W, int H, int xdec, int ydec, int cw,
+                              int ch, int x0, int y0) {
+  const int sh = xdec + ydec;
+  const uint32_t half = (1u << sh) >> 1;
+  for (int r = tid >> 7; r < g.LH; r += kThreads >> 7) {
+    const int gy = imin(imax(y0 - g.R + r, 0), ch - 1) << ydec;
+    const uint8_t *row0 = luma + (size_t)imin(gy, H - 1) * stride, *row1 = luma + (size_t)imin(gy + ydec, H - 1) * stride;
+    for (int c = tid & 127; c < g.LW; c += 128) {
+      const int gx = imin(imax(x0 - g.R + c, 0), cw - 1) << xdec;
+      const int xa = imin(gx, W - 1), xb = imin(gx + xdec, W - 1);
+      uint32_t s = dn_sample<BPS>(row0, xa);
+      if (xdec) s += dn_sample<BPS>(row0, xb);
+      if (ydec) {
+        s += dn_sample<BPS>(row1, xa);
+        if (xdec) s += dn_sample<BPS>(row1, xb);
+      }
+      L[r * g.LS + c] = (uint16_t)((s + half) >> sh);
+    }
+  }
+}
+
+// dn_hsum over the three arrays: Hb(row, x) = sum over Cb, Cr, G and |kx| <= S of the squared differences
+template <int S>
+G1S_DN_HD void dn_hsum_j(int tid, const TileGeom &g, int LP, const uint16_t *L, uint32_t *Hb, int dx, int dy, int RW, int NR, uint32_t mNR) {
+  const int ntasks = ((RW + 7) >> 3) * NR;
+  const int ox = -imax(dx, 0);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = imin(seg * 8, RW - 8);
+    const uint16_t *a = L + (row + g.A - dy) * g.LS + (ox + xs - S + g.R);
+    const uint16_t *b = a + dy * g.LS + dx;
+    uint32_t sq[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) {
+      const int t0 = (int)a[j] - (int)b[j], t1 = (int)a[LP + j] - (int)b[LP + j], t2 = (int)a[2 * LP + j] - (int)b[2 * LP + j];
+      sq[j] = (uint32_t)(t0 * t0) + (uint32_t)(t1 * t1) + (uint32_t)(t2 * t2);
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += sq[j];
+    uint32_t *o = Hb + row * g.HS + xs;
+    o[0] = s;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      s += sq[j + 2 * S] - sq[j - 1];
+      o[j] = s;
+    }
+  }
+}
+
+// dn_accumulate for both chroma planes: the weights are read once
+G1S_DN_HD void dn_accumulate_j(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint32_t *aub,
+                               uint32_t *aur) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w1 = Wb + (yb + dy) * g.WS + x + imax(dx, 0);
+  const uint16_t *w2 = Wb + yb * g.WS + x + imax(-dx, 0);
+  const uint16_t *u1 = L + (yb + dy + g.R) * g.LS + x + dx + g.R;
+  const uint16_t *u2 = L + (yb - dy + g.R) * g.LS + x - dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w1[4 * j * g.WS], b = w2[4 * j * g.WS];
+    aw[j] += a + b;
+    aub[j] += a * u1[4 * j * g.LS] + b * u2[4 * j * g.LS];
+    aur[j] += a * u1[LP + 4 * j * g.LS] + b * u2[LP + 4 * j * g.LS];
+  }
+}
+
+// dn_hsum_t over the three arrays of the frame (L) and of the neighbour (N)
+template <int S>
+G1S_DN_HD void dn_hsum_jt(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *N, uint32_t *Hb, int dx, int dy) {
+  constexpr int NR = kTH + 2 * S, ntasks = (kTW >> 3) * NR;
+  const uint32_t mNR = magic(NR);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = seg * 8;
+    const uint16_t *a = L + (row + g.A) * g.LS + (xs + g.A);
+    const uint16_t *b = N + (row + g.A + dy) * g.LS + (xs + g.A + dx);
+    uint32_t sq[8 + 2 * S];
+#pragma unroll
+    for (int j = 0; j < 8 + 2 * S; ++j) {
+      const int t0 = (int)a[j] - (int)b[j], t1 = (int)a[LP + j] - (int)b[LP + j], t2 = (int)a[2 * LP + j] - (int)b[2 * LP + j];
+      sq[j] = (uint32_t)(t0 * t0) + (uint32_t)(t1 * t1) + (uint32_t)(t2 * t2);
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j <= 2 * S; ++j) s += sq[j];
+    uint32_t *o = Hb + row * g.HS + xs;
+    o[0] = s;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      s += sq[j + 2 * S] - sq[j - 1];
+      o[j] = s;
+    }
+  }
+}
+
+// dn_accumulate_t for both chroma planes
+G1S_DN_HD void dn_accumulate_jt(int tid, const TileGeom &g, int LP, const uint16_t *N, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint64_t *aub,
+                                uint64_t *aur) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w = Wb + yb * g.WS + x;
+  const uint16_t *u = N + (yb + dy + g.R) * g.LS + x + dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w[4 * j * g.WS];
+    aw[j] += a;
+    aub[j] += (uint64_t)a * u[4 * j * g.LS];
+    aur[j] += (uint64_t)a * u[LP + 4 * j * g.LS];
+  }
+}
+
+// what a joint tile reads and writes: the two chroma planes (cw x ch), the luma plane the guide comes from (W x H)
+struct JointPlanes {
+  const uint8_t *cb, *cr, *luma;
+  uint32_t cb_stride, cr_stride, luma_stride;
+};
+struct JointShape {
+  int W, H, xdec, ydec, cw, ch;
+};
+
+// Cb, Cr and G of one frame's tile into the three arrays from L
+template <int BPS>
+G1S_DN_HD void dn_stage_j(int tid, const TileGeom &g, int LP, uint16_t *L, const JointPlanes &p, const JointShape &s, int x0, int y0) {
+  dn_stage<BPS>(tid, g, L, p.cb, p.cb_stride, s.cw, s.ch, x0, y0);
+  dn_stage<BPS>(tid, g, L + LP, p.cr, p.cr_stride, s.cw, s.ch, x0, y0);
+  dn_stage_guide<BPS>(tid, g, L + 2 * LP, p.luma, p.luma_stride, s.W, s.H, s.xdec, s.ydec, s.cw, s.ch, x0, y0);
+}
+
+// the frame's own offsets (rules 8 - 10) of one chroma tile: the arrays and T staged, the sums of rule 11 in aw, aub, aur
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile_j_spatial(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+                                 const JointShape &s, int x0, int y0, Sync sync, uint32_t *aw, uint32_t *aub, uint32_t *aur) {
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + jg.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + jg.offL), *Wb = reinterpret_cast<uint16_t *>(lds + jg.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + jg.offT);
+  dn_stage_j<BPS>(tid, g, jg.LP, L, p, s, x0, y0);
+  for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
+  sync();
+  dn_init(tid, g, L, aw, aub);
+  dn_init(tid, g, L + jg.LP, aw, aur);
+  for (int dy = 0; dy <= g.A; ++dy) {
+    const int NR = kTH + dy + 2 * S, RH = kTH + dy;
+    const uint32_t mNR = magic(NR);
+    for (int dx = dy ? -g.A : 1; dx <= g.A; ++dx) {
+      const int RW = kTW + (dx < 0 ? -dx : dx);
+      dn_hsum_j<S>(tid, g, jg.LP, L, Hb, dx, dy, RW, NR, mNR);
+      sync();
+      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, s.cw, s.ch);
+      sync();
+      dn_accumulate_j(tid, g, jg.LP, L, Wb, dx, dy, aw, aub, aur);
+    }
+  }
+}
+
+// one chroma tile of the joint filter, start to end
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile_j(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+                         const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0,
+                         Sync sync) {
+  uint32_t aw[kSPT], aub[kSPT], aur[kSPT];
+  dn_tile_j_spatial<S, BPS>(tid, g, jg, lds, table, q, p, s, x0, y0, sync, aw, aub, aur);
+  dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
+  dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
+}
+
+// one chroma tile of the temporal joint filter (rule 11t): nb(k) gives the planes of the k-th of the 2 D frames around the
+// frame in hand, .luma a null pointer where the clip has no such frame -- the same for every thread of the workgroup
+template <int S, int BPS, class Nb, class Sync>
+G1S_DN_HD void dn_tile_jt(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+                          Nb nb, int nnb, const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr,
+                          uint32_t out_cr_stride, int x0, int y0, Sync sync) {
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + jg.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + jg.offL), *Wb = reinterpret_cast<uint16_t *>(lds + jg.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + jg.offT), *N = reinterpret_cast<uint16_t *>(lds + jg.offN);
+  uint32_t aw[kSPT], aub32[kSPT], aur32[kSPT];
+  dn_tile_j_spatial<S, BPS>(tid, g, jg, lds, table, q, p, s, x0, y0, sync, aw, aub32, aur32);
+  uint64_t aub[kSPT], aur[kSPT];
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
+  for (int k = 0; k < nnb; ++k) {
+    const JointPlanes n = nb(k);
+    if (!n.luma) continue;
+    sync();  // the last dn_accumulate_jt has read N
+    dn_stage_j<BPS>(tid, g, jg.LP, N, n, s, x0, y0);
+    sync();
+    for (int dy = -g.A; dy <= g.A; ++dy)
+      for (int dx = -g.A; dx <= g.A; ++dx) {
+        dn_hsum_jt<S>(tid, g, jg.LP, L, N, Hb, dx, dy);
+        sync();
+        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, s.cw, s.ch);
+        sync();
+        dn_accumulate_jt(tid, g, jg.LP, N, Wb, dx, dy, aw, aub, aur);
+      }
+  }
+  dn_store_t<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
+  dn_store_t<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }
 
 }  // namespace g1s_dn

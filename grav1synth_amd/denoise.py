@@ -7,6 +7,7 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 >>> clean = dn.apply([y, u, v])                 # torch device tensors stay on the device; numpy in, numpy out
 >>> clips = Denoiser(10, temporal_radius=2).denoise_clip(frames)   # the mean also runs over 2 frames either side
 >>> denoise_y4m_file("grainy.y4m", "clean.y4m", temporal_radius=1)
+>>> Denoiser(10, joint_chroma=True).apply([y, u, v])   # Cb and Cr share one weight, guided by the luma at the same place
 """
 from __future__ import annotations
 
@@ -37,12 +38,17 @@ def denoise_opts(device: int = -1, batch_frames: int = 0, search_radius: int = 0
     return o
 
 
-def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0) -> Tuple[np.ndarray, int]:
-    """(T, q): the 1024 uint16 weights and the shift the kernels use for these parameters (host only, no device needed)."""
+def _flags(joint_chroma: bool) -> int:
+    return _lib.G1S_DENOISE_JOINT_CHROMA if joint_chroma else 0
+
+
+def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0, joint_chroma: bool = False) -> Tuple[np.ndarray, int]:
+    """(T, q): the 1024 uint16 weights and the shift the kernels use for these parameters (host only, no device needed).
+    joint_chroma: the table of the joint chroma filter (rule 10; `strength` is the chroma strength)."""
     L = _lib.lib()
     t = np.zeros(1024, np.uint16)
     q = C.c_uint32()
-    rc = L.g1s_denoise_weights(bit_depth, patch_radius, float(strength), t.ctypes.data, C.byref(q))
+    rc = L.g1s_denoise_weights_ex(bit_depth, patch_radius, float(strength), _flags(joint_chroma), t.ctypes.data, C.byref(q))
     if rc:
         raise G1SError(rc, L.g1s_last_global_error().decode())
     return t, int(q.value)
@@ -52,14 +58,17 @@ class Denoiser(FrameOp):
     _name = "denoise"
 
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                 strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0):
+                 strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
-        runs over the D frames before and the D frames after it that the clip has."""
+        runs over the D frames before and the D frames after it that the clip has.  joint_chroma: the two chroma planes
+        share one weight, taken from Cb, Cr and the input luma at chroma resolution (rules 8 - 11 of include/g1s_diff.h);
+        luma, and a luma-only frame, are filtered as without it."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal_radius = temporal_radius
+        self.joint_chroma = bool(joint_chroma)
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
-        self._h = self._L.g1s_denoise_new_temporal(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF)
+        self._h = self._L.g1s_denoise_new_ex(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma))
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
@@ -100,19 +109,19 @@ class Denoiser(FrameOp):
         self._keep.clear()
 
     def kernel_times(self, enable: bool = True):
-        """(ms in kd_nlm / kd_nlm_t, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        """(ms in kd_nlm / kd_nlm_t and their joint chroma forms, frames) of the timed batches so far (HIP events); enables / disables the timing."""
         a, n = C.c_double(), C.c_uint64()
         self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
         return a.value, n.value
 
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                     strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0) -> int:
+                     strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
-    n = L.g1s_denoise_y4m_file_temporal(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, err, len(err))
+    n = L.g1s_denoise_y4m_file_ex(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

@@ -456,7 +456,8 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
 
 /* ---- `denoise`: an integer-exact non-local-means filter on the device (the clip `diff` compares the source with) ----
  * This is the project's OWN definition of non-local means: it has the structure of ffmpeg's nlmeans and of KNLMeansCL,
- * not their bits, and its output is not any other tool's.  Every plane is filtered on its own grid.  Bit depth B in
+ * not their bits, and its output is not any other tool's.  Every plane is filtered on its own grid (rules 8 - 11 below are
+ * the exception, behind a flag).  Bit depth B in
  * {8, 10, 12}, samples u(x, y) of a W x H plane, clamp() replicates the plane's edge samples; search radius A (1..7),
  * patch radius S (1..4), n = (2S + 1)^2, strength h > 0 in 8-bit code values:
  *   1. D(p, d) = sum over |kx|, |ky| <= S of (u(clamp(p + k)) - u(clamp(p + d + k)))^2 for |dx|, |dy| <= A (exact in 32 bits).
@@ -480,10 +481,29 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *   7. out_t(p) = (sum_{k,d} w u_{t+k}(p + d) + (sum w >> 1)) / sum w, integer division, the sums over everything that
  *      takes part; (k = 0, d = 0) carries 4096 as in rule 4.  sum w <= (2D + 1)(2A + 1)^2 4096 fits 32 bits; the
  *      numerator does not (12 bit, A = 7, D = 1: 1.1e10) and is kept in 64.  Exact for every accepted (B, A, D).
- * D = 0 is rules 1 - 4.  No motion compensation, no luma-guided chroma, no dithering.  Samples above the bit depth's
- * maximum are the caller's error.
+ * D = 0 is rules 1 - 4.
+ * Luma-guided joint chroma: with the flag G1S_DENOISE_JOINT_CHROMA (g1s_denoise_new_ex) the two chroma planes of a frame
+ * with three planes share one weight, taken from Cb, Cr and the luma at the same place.  Luma is filtered by rules 1 - 7
+ * as without the flag; a luma-only frame is filtered as without it.  Chroma size cw x ch, cw = (W + xdec) >> xdec,
+ * ch = (H + ydec) >> ydec:
+ *   8. The guide G is the frame's INPUT luma Y at chroma resolution, a rounded box mean:
+ *      G(x, y) = (sum over j <= ydec, i <= xdec of Y(min((x << xdec) + i, W - 1), min((y << ydec) + j, H - 1))
+ *                 + ((1 << (xdec + ydec)) >> 1)) >> (xdec + ydec).  For 4:4:4 G = Y.  The input luma, not the denoised
+ *      one: the chroma launch depends on no other launch's output.
+ *   9. D_J(p, d) = D_Cb(p, d) + D_Cr(p, d) + D_G(p, d), each term rule 1 on the cw x ch grid with the clamp at the chroma
+ *      plane's edges (G is a cw x ch plane).  Rule 2 holds unchanged, so D_J(p, d) = D_J(p + d, -d).  Exact in UNSIGNED
+ *      32 bits (3 x 81 x 4095^2 = 4 074 873 075 < 2^32); it does not fit int32.
+ *  10. w(p, d) = T_J[min(D_J >> q_J, 1023)]: (T_J, q_J) is rule 3 with n replaced by 3n and h = the chroma strength, the
+ *      same rounding and the same non-increasing clamp.  g1s_denoise_weights_ex returns it.
+ *  11. out_Cb(p) and out_Cr(p) are each rule 4 with the one shared w.  11t: with a temporal radius rules 5 - 7 hold with D_k
+ *      the sum over Cb, Cr and G of rule 6's distance between frame t and frame t + k (G of frame t + k from that
+ *      frame's input luma), the same T_J, and both numerators in 64 bits.
+ * No motion compensation, no dithering.  Samples above the bit depth's maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
- * chroma planes) on the denoiser's own stream.  Errors are sticky (g1s_denoise_last_error). */
+ * chroma planes -- under the flag one workgroup filters both) on the denoiser's own stream.  A workgroup's LDS grows
+ * with A, S, a temporal radius and the flag; a parameter set that needs more than the device gives a workgroup is
+ * refused when the denoiser is made.  Errors are sticky (g1s_denoise_last_error). */
+#define G1S_DENOISE_JOINT_CHROMA 1u
 typedef struct {
   uint32_t struct_size;    /* sizeof(g1s_denoise_opts_t) */
   int32_t device;          /* HIP device ordinal; -1 = current device */
@@ -500,6 +520,9 @@ g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opt
 /* The same with a temporal radius D (rules 5 - 7); g1s_denoise_new is temporal_radius = 0.  A radius above 3 is a
  * refusal like the others ("temporal_radius must be 0..3"). */
 g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius);
+/* The same with flags (G1S_DENOISE_*; rules 8 - 11); g1s_denoise_new_temporal is flags = 0.  An unknown flag bit is a
+ * refusal like the others ("unknown denoise flags"), checked before a device is looked for. */
+g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags);
 /* One frame.  in / out follow g1s_frame_t.on_device independently, as in g1s_grain_frame: 0 = host (in: copied before
  * the call returns; out: written by g1s_denoise_sync at the latest), 1 = device, 2 = pinned host (copies queued).  Device
  * and pinned planes of in must stay valid and unmodified, and every plane of out must stay valid, until
@@ -511,7 +534,8 @@ g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_op
  * denoiser was made as g1s_denoise_drain counts, is read by the frames up to n + D: device and pinned planes of in must
  * stay valid and unmodified until frames_complete exceeds n + D, or until g1s_denoise_sync.  Host planes are still copied
  * before the call returns (the denoiser keeps a batch and the 2 D frames around it on the device).  out as above: valid
- * until frames_complete exceeds n, or until g1s_denoise_sync; it must not overlap a plane the queue still reads. */
+ * until frames_complete exceeds n, or until g1s_denoise_sync; it must not overlap a plane the queue still reads.
+ * Under G1S_DENOISE_JOINT_CHROMA the chroma launch also reads the luma plane of in, which must already stay valid. */
 int g1s_denoise_frame(g1s_denoise_t *, const g1s_frame_t *in, g1s_frame_t *out);
 /* Launches what is queued and waits: the out planes of every frame handed over are complete.  This ends the clip: with a
  * temporal radius the last D frames go out with the neighbours they have, and the next frame starts a new clip. */
@@ -528,12 +552,18 @@ void g1s_denoise_free(g1s_denoise_t *);
 /* (q, T) of rule 3 as the kernels use them.  Host only: needs no device.  G1S_ERR_INVALID (reason from
  * g1s_last_global_error()) for a bit depth, patch radius or strength out of range. */
 int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double strength, uint16_t T[1024], uint32_t *q);
+/* The same with flags: rule 10's (q_J, T_J) under G1S_DENOISE_JOINT_CHROMA (strength = the chroma strength), rule 3's
+ * without it.  An unknown flag bit is G1S_ERR_INVALID ("unknown denoise flags"). */
+int g1s_denoise_weights_ex(uint32_t bit_depth, uint32_t patch_radius, double strength, uint32_t flags, uint16_t T[1024], uint32_t *q);
 /* `denoise INPUT -o OUTPUT`: every frame of a .y4m through the filter, written as .y4m (the input's header line,
  * "FRAME\n", the planes without padding).  Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
 int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap);
 /* The same with a temporal radius; the whole file is one clip.  g1s_denoise_y4m_file is temporal_radius = 0. */
 int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
                                       size_t cap);
+/* The same with flags (G1S_DENOISE_*); g1s_denoise_y4m_file_temporal is flags = 0. */
+int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, char *err,
+                                size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -545,6 +575,10 @@ int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const ch
  * is past the D frames after it as well.  g1s_diff_y4m_file_denoised is temporal_radius = 0. */
 int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                         const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames, char *err, size_t cap);
+/* The same with flags (G1S_DENOISE_*); g1s_diff_y4m_file_denoised_temporal is flags = 0. */
+int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, uint64_t *frames, char *err,
+                                  size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

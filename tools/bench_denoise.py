@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernels kd_nlm and kd_nlm_t over
 device-resident frames, 4K 10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 64, at the defaults (A = 3, S = 2) and at A = 7, S = 3
-with temporal radius 0, and at the defaults with temporal radius 1 and 2.  Per case: HIP-event time per batch around the two
+with temporal radius 0 and 1, and at the defaults with temporal radius 2; every case without and with joint chroma
+(kd_nlm_j / kd_nlm_jt take the chroma launch's place; "joint_chroma" in the line).  Per case: HIP-event time per batch around the two
 launches (timed batches run alone and are waited for), frames a second from it, the kernel's arithmetic as the specification
 counts it -- samples x pairs: the unordered pairs A + A (2A + 1) of the frame itself and, per neighbour frame, the (2A + 1)^2
 one-sided pairs of rule 6 (a frame at the end of a clip has fewer; the runs are clips of many batches) -- and the job rate
@@ -24,8 +25,8 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
     outs = [[torch.empty_like(p) for p in ins[0]] for _ in range(BATCH)]
     torch.cuda.synchronize()
     samples = sum(p.numel() for p in ins[0])
-    for A, S, D in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (3, 2, 2)):
-        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D)
+    for A, S, D, joint in [(a, s, d, j) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (7, 3, 1), (3, 2, 2)) for j in (False, True)]:
+        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint)
 
         def run(nb):
             for k in range(nb * BATCH):
@@ -42,7 +43,7 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
         dn.close()
         pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
-            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, "batch_frames": BATCH, "timed_batches": fr / BATCH,
             "samples_per_frame": samples, "unordered_pairs": pairs, "temporal_pairs": temporal_pairs,
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
             "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
