@@ -27,7 +27,9 @@
 // The joint chroma filter (rules 8 - 11t, kd_nlm_j and kd_nlm_jt) is at the end of this file.
 //
 // Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
-// run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.
+// run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.  The tile functions (dn_tile, dn_tile_t,
+// dn_tile_j, dn_tile_jt), too, are run on the host as they stand, with a real barrier for `sync` and hostile thread orders
+// (tests/denoise_wg_host.cpp): that is what checks where the barriers stand, the one left out above included.
 #pragma once
 #include <stdint.h>
 

@@ -3,6 +3,7 @@
 // compares its output with tests/denoise_joint_ref.py).  Every phase of the header takes the thread index as an argument, so
 // a workgroup is each phase run for tid = 0 .. 255 in turn, in the order dn_tile_j / dn_tile_jt give the phases; the end of
 // such a loop is the barrier.  NNB = 0 runs the spatial tile (32-bit sums, dn_store), NNB > 0 the temporal one.
+// (Where the barriers of dn_tile_j / dn_tile_jt themselves stand is checked by denoise_wg_host.cpp, with a real barrier.)
 //
 //   denoise_joint_tile_host BPS S A q W H XDEC YDEC NNB TABLE IN OUT
 //

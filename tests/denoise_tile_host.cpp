@@ -2,6 +2,7 @@
 // (tests/test_denoise_temporal_cpu.py builds it with the address and undefined-behaviour sanitizers and compares its output
 // with tests/denoise_temporal_ref.py).  Every phase of the header takes the thread index as an argument, so a workgroup is
 // each phase run for tid = 0 .. 255 in turn, in the order dn_tile_t gives the phases; the end of such a loop is the barrier.
+// (Where the barriers of dn_tile_t itself stand is checked by denoise_wg_host.cpp, which runs it with a real barrier.)
 //
 //   denoise_tile_host BPS S A q W H NNB TABLE IN OUT
 //
