@@ -32,6 +32,11 @@ DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser ru
 DENOISE_ONE_DEVICE = "--denoise does not combine with --gpus / --devices (one denoiser, one generator, one device). Exiting."
 BAD_TEMPORAL_RADIUS = "--temporal-radius must be 0..3 (frames before and after the one in hand). Exiting."
 KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs --denoise. Exiting."
+PRIOR_NEEDS_TABLE = "--prior-range and --prior-segment say how --grain-prior is used: they need --grain-prior. Exiting."
+PRIOR_12_BIT = ("--grain-prior filters luma in a 12-bit domain: a 12-bit input has no headroom there (8 and 10 bits are "
+                "supported). Exiting.")
+PRIOR_BAD_TABLE = "Invalid grain prior: %s. Exiting."
+PRIOR_BAD_SEGMENT = "--prior-segment %d is not in the grain prior (%d segments). Exiting."
 
 
 def _confirm(prompt: str) -> bool:
@@ -71,11 +76,54 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
     p.add_argument("--joint-chroma", action="store_true",
                    help="luma-guided joint chroma: Cb and Cr share one weight, taken from both and the luma at the same place "
                         "(KNLMeansCL's channels=\"YUV\" in structure; off by default)")
+    p.add_argument("--grain-prior", default=None, metavar="TABLE",
+                   help="a film grain table (typically a first `diff SOURCE --denoise`) whose luma scaling function the luma strength "
+                        "follows: luma is filtered where that grain has one size at every intensity; 8- and 10-bit inputs; off by default")
+    p.add_argument("--prior-range", type=int, default=0, metavar="R",
+                   help="with --grain-prior: the strongest luma strength over the weakest, 1..16 at 8 bits, 1..4 at 10 (default 4)")
+    p.add_argument("--prior-segment", type=int, default=None, metavar="K",
+                   help="with --grain-prior: use the table's segment K (from 0) alone instead of the mean of all segments")
 
 
 def _denoise_parameters(args) -> dict:
     return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
-                chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma)
+                chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
+                grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment)
+
+
+def _prior_refused(input: str, outputs, parameters: dict) -> bool:
+    """The refusals of --grain-prior / --prior-range / --prior-segment, each a logged line: True when one was logged."""
+    from .ingest import Y4MReader
+    from .tbl import TblError, parse_tbl_native
+
+    prior, k = parameters.get("grain_prior"), parameters.get("prior_segment")
+    if prior is None:
+        if parameters.get("prior_range", 0) or k is not None:
+            log.error(PRIOR_NEEDS_TABLE)
+            return True
+        return False
+    if any(o is not None and _same_path(prior, o) for o in outputs):
+        log.error(SAME_AS_OUTPUT)
+        return True
+    try:
+        with open(prior, "rb") as f:
+            segments = parse_tbl_native(f.read())
+    except (OSError, TblError) as e:
+        log.error(PRIOR_BAD_TABLE, e)
+        return True
+    if k is not None and not 0 <= k < len(segments):
+        log.error(PRIOR_BAD_SEGMENT, k, len(segments))
+        return True
+    try:
+        y = Y4MReader(input)
+    except ValueError:
+        return False  # (the command says what is wrong with its input)
+    bit_depth = y.details.bit_depth
+    y.close()
+    if bit_depth == 12:
+        log.error(PRIOR_12_BIT)
+        return True
+    return False
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -156,6 +204,8 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
         return -1
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
+        return -1
+    if _prior_refused(source, (output, keep_denoised), parameters):
         return -1
     for path in (output, keep_denoised):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
@@ -254,6 +304,8 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
         return -1
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)
+        return -1
+    if _prior_refused(input, (output,), parameters):
         return -1
     if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
         log.warning(NOT_OVERWRITING)

@@ -1,0 +1,96 @@
+// curve.h -- the variance-stabilising curve of `denoise` from the segments of a grain table (include/g1s_diff.h, rules 12
+// and 13), and the checks of a pair (f, g) that a caller hands to g1s_denoise_new_curve.  Host code only: it calls nothing
+// of HIP and builds with a host compiler alone.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/g1s_diff.h"
+
+namespace g1s_cv {
+
+constexpr uint32_t kStabBits = 12, kStabTop = (1u << kStabBits) - 1, kInvEntries = 1u << kStabBits;  // the stabilised domain
+
+// 7.18.3.4 for the luma points of a segment: 256 entries through the points, flat outside them, zero without points
+inline void scaling_lut(const g1s_segment_t &sg, int lut[256]) {
+  for (int x = 0; x < 256; ++x) lut[x] = 0;
+  const int n = sg.num_y_points;
+  if (!n) return;
+  const uint8_t(*p)[2] = sg.scaling_points_y;
+  for (int x = 0; x < p[0][0]; ++x) lut[x] = p[0][1];
+  for (int i = 0; i + 1 < n; ++i) {
+    const int dy = (int)p[i + 1][1] - (int)p[i][1], dx = (int)p[i + 1][0] - (int)p[i][0];
+    const int delta = dy * ((65536 + (dx >> 1)) / dx);
+    for (int x = 0; x < dx; ++x) lut[p[i][0] + x] = p[i][1] + ((x * delta + 32768) >> 16);
+  }
+  for (int x = p[n - 1][0]; x < 256; ++x) lut[x] = p[n - 1][1];
+}
+
+// 7.18.3.5 scale_lut at `index` of a plane of `bit_depth` bits
+inline int scale_lut(const int lut[256], int index, uint32_t bit_depth) {
+  const int sh = (int)bit_depth - 8, x = index >> sh;
+  if (!sh || x == 255) return lut[x];
+  const int rem = index - (x << sh), start = lut[x], end = lut[x + 1];
+  return start + (((end - start) * rem + (1 << (sh - 1))) >> sh);
+}
+
+// Rules 12 and 13: fwd[1 << B], inv[4096].  "" when fine, else the refusal.
+inline std::string build(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  if (bit_depth == 12) return "a grain prior needs headroom above the clip's bit depth: the stabilised domain is 12 bits, so a 12-bit clip is refused";
+  if (bit_depth != 8 && bit_depth != 10) return "a grain prior is defined for bit depths 8 and 10";
+  const uint32_t rmax = 1u << (kStabBits - bit_depth);
+  if (range > rmax) return "prior range must be 1.." + std::to_string(rmax) + " at " + std::to_string(bit_depth) + " bits (0 = the default)";
+  if (!segs || n < 1) return "a grain prior needs at least one segment";
+  for (size_t i = 0; i < n; ++i) {
+    if (segs[i].num_y_points > G1S_NUM_Y_POINTS) return "segment " + std::to_string(i) + ": more than 14 luma scaling points";
+    for (int k = 0; k + 1 < segs[i].num_y_points; ++k)
+      if (segs[i].scaling_points_y[k + 1][0] <= segs[i].scaling_points_y[k][0])
+        return "segment " + std::to_string(i) + ": luma scaling points must have increasing values";
+  }
+  const uint32_t R = range ? range : (rmax < 4u ? rmax : 4u), M = (1u << bit_depth) - 1;
+  std::vector<uint64_t> s((size_t)M + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    int lut[256];
+    scaling_lut(segs[i], lut);
+    for (uint32_t v = 0; v <= M; ++v) s[v] += (uint64_t)scale_lut(lut, (int)v, bit_depth);
+  }
+  uint64_t top = 0;
+  for (uint32_t v = 0; v <= M; ++v) s[v] = (s[v] + (n >> 1)) / n, top = s[v] > top ? s[v] : top;
+  const uint64_t floor = top ? (top + R - 1) / R : 1;  // max(1, ceil(max s / R))
+  std::vector<uint64_t> Cs((size_t)M + 2, 0);          // C(x) = sum over v < x of r(v)
+  for (uint32_t v = 0; v <= M; ++v) Cs[v + 1] = Cs[v] + ((1ull << 24) / (s[v] > floor ? s[v] : floor));
+  const uint64_t CM = Cs[M];
+  for (uint32_t x = 0; x <= M; ++x) fwd[x] = (uint16_t)((kStabTop * Cs[x] + (CM >> 1)) / CM);
+  if (fwd[0] != 0 || fwd[M] != kStabTop) return "internal error: the curve does not span the stabilised domain";
+  for (uint32_t x = 0; x < M; ++x)
+    if (fwd[x + 1] <= fwd[x]) return "internal error: the curve is not strictly increasing";
+  // rule 13: the smallest x with |f(x) - y| minimal
+  uint32_t x = 0;
+  for (uint32_t y = 0; y < kInvEntries; ++y) {
+    while (x < M && fwd[x + 1] <= y) ++x;  // f(x) <= y < f(x + 1), or x = M
+    inv[y] = (uint16_t)(x < M && (uint32_t)fwd[x + 1] - y < y - (uint32_t)fwd[x] ? x + 1 : x);
+  }
+  return "";
+}
+
+// what g1s_denoise_new_curve asks of a pair it is handed.  "" when fine.
+inline std::string check(uint32_t bit_depth, const uint16_t *fwd, const uint16_t *inv) {
+  if (bit_depth == 12) return "a grain prior needs headroom above the clip's bit depth: the stabilised domain is 12 bits, so a 12-bit clip is refused";
+  if (bit_depth != 8 && bit_depth != 10) return "a grain prior is defined for bit depths 8 and 10";
+  if (!fwd || !inv) return "g1s_denoise_new_curve needs both tables of the curve";
+  const uint32_t M = (1u << bit_depth) - 1;
+  if (fwd[0] != 0 || fwd[M] != kStabTop) return "curve: fwd must run from 0 to 4095";
+  for (uint32_t x = 0; x < M; ++x)
+    if (fwd[x + 1] <= fwd[x]) return "curve: fwd must be strictly increasing (at " + std::to_string(x + 1) + ")";
+  for (uint32_t y = 0; y < kInvEntries; ++y) {
+    if (inv[y] > M) return "curve: inv must stay within the clip's bit depth (at " + std::to_string(y) + ")";
+    if (y && inv[y] < inv[y - 1]) return "curve: inv must be non-decreasing (at " + std::to_string(y) + ")";
+  }
+  for (uint32_t x = 0; x <= M; ++x)
+    if (inv[fwd[x]] != x) return "curve: inv[fwd[x]] must be x (at " + std::to_string(x) + ")";
+  return "";
+}
+
+}  // namespace g1s_cv

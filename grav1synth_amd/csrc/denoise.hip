@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "curve.h"
+#include "curve_row.hip.h"
 #include "denoise_tile.hip.h"
 #include "frame_op.h"
 
@@ -189,7 +191,7 @@ using namespace g1s_op;
 struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
   bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j / kd_nlm_jt for their chroma
-  uint32_t q[3] = {0, 0, 0};  // luma, chroma, joint chroma
+  uint32_t q[4] = {0, 0, 0, 0};  // luma, chroma, joint chroma, luma in the stabilised domain
   Event ev[2];
   // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
   // output goes (out[c] is null for a host frame: a slot of the output staging buffer is chosen at the launch)
@@ -204,26 +206,45 @@ struct g1s_denoise : BatchedOp {
   std::deque<Queued> queue;
   uint64_t frames_in = 0, first_queued = 0, next_launch = 0, clip_first = 0, frames_complete = 0;
   ParamSets<uint8_t> p_jobs;  // DenoiseJob or, with a temporal radius, DenoiseJobT
-  DevBuf<uint16_t> d_tables;  // [3][1024]
+  DevBuf<uint16_t> d_tables;  // [4][1024]
+  // a grain prior's curve (rules 12 - 15): luma goes forward into a ring of 12-bit u16 planes, one slot a frame of the
+  // input ring, is filtered there into `batch` planes and comes back through the inverse
+  bool curve = false;
+  DevBuf<uint16_t> d_curve;  // fwd[1 << B], inv[4096]
+  DevBuf<uint8_t> d_stab, d_filt;
+  size_t stab_row = 0, stab_plane = 0;
+  uint64_t next_stab = 0;  // the first frame whose luma is not in its slot yet
   double ms_kernel = 0;
   uint64_t frames_timed = 0;
 
   size_t job_bytes() const { return D ? sizeof(DenoiseJobT) : sizeof(DenoiseJob); }
+  // a parameter set: the batch's jobs and, with a curve, the luma launch's jobs in the stabilised planes, the forward
+  // launch's (a first batch brings its D later neighbours along) and the inverse launch's
+  size_t off_luma() const { return align_up(job_bytes() * batch, 16); }
+  size_t off_fwd() const { return 2 * off_luma(); }
+  size_t off_inv() const { return off_fwd() + align_up(sizeof(g1s_cv::CurveJob) * (batch + D), 16); }
+  size_t set_bytes() const { return curve ? off_inv() + sizeof(g1s_cv::CurveJob) * batch : job_bytes() * batch; }
+  uint8_t *stab_slot(uint64_t n) const { return d_stab + stab_plane * (size_t)(n % ring()); }
+  int need_stab();
   // host and pinned inputs wait on the device in a ring: a slot is written again B + 2D frames later, and by then every
   // frame that reads it (up to D frames on) has been launched in front of that copy on the stream
   uint32_t ring() const { return batch + 2 * D; }
   const Queued &frame(uint64_t n) const { return queue[(size_t)(n - first_queued)]; }
-  int launch(int set, uint32_t nframes, int plane0, int nplanes_in_class);
+  int launch(int set, uint32_t nframes, int plane0, int nplanes_in_class, bool stabilised = false);
   int launch_joint(int set, uint32_t nframes);
   int flush(uint32_t nframes);
   int launch_up_to(uint64_t limit);
   int end_clip();
 };
 
-int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_class) {
+// the planes of a class through kd_nlm / kd_nlm_t; `stabilised`: luma as the forward curve left it -- 12-bit u16 planes,
+// the jobs that point into them and rule 14's table
+int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_class, bool stabilised) {
   const int W = (int)geom.pw(plane0), H = (int)geom.ph(plane0), tiles_x = (W + kTW - 1) / kTW;
+  const int ti = stabilised ? 3 : plane0 ? 1 : 0;
+  const uint32_t bps = stabilised ? 2u : this->bps;
   auto fill = [&](auto &p) {
-    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p), p.table = d_tables + (plane0 ? kTable : 0), p.q = (int)q[plane0 ? 1 : 0], p.A = (int)A;
+    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p + (stabilised ? off_luma() : 0)), p.table = d_tables + ti * kTable, p.q = (int)q[ti], p.A = (int)A;
     p.W = W, p.H = H, p.tiles_x = tiles_x, p.plane0 = plane0;
   };
   const dim3 grid((unsigned)(tiles_x * ((H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
@@ -267,12 +288,29 @@ int g1s_denoise::launch_joint(int set, uint32_t nframes) {
   return G1S_OK;
 }
 
+// the ring of stabilised luma planes and the planes the luma launch writes, for the geometry in hand
+int g1s_denoise::need_stab() {
+  if (d_stab) return G1S_OK;
+  stab_row = align_up((size_t)geom.W * 2, kStageRowAlign), stab_plane = align_up(stab_row * (size_t)geom.H, kStagePlaneAlign);
+  if (hipMalloc((void **)&d_stab.p, stab_plane * ring()) != hipSuccess || hipMalloc((void **)&d_filt.p, stab_plane * batch) != hipSuccess)
+    return fail(G1S_ERR_HIP, "hipMalloc of the stabilised luma planes failed");
+  return G1S_OK;
+}
+
 // frames next_launch .. next_launch + nframes - 1 as one batch (nframes <= batch); their neighbours are in the queue
 int g1s_denoise::flush(uint32_t nframes) {
   if (!nframes) return G1S_OK;
   int set, rc = next_set(&set);
   if (rc) return rc;
   bool host_outs = false;
+  // with a curve: every frame this batch reads that is not in its slot yet goes forward -- the batch's own and the up to D
+  // behind them.  A slot is written again batch + 2D frames later, by a batch that starts beyond every frame that read it.
+  uint32_t nfwd = 0;
+  if (curve) {
+    g1s_cv::CurveJob *cf = reinterpret_cast<g1s_cv::CurveJob *>(p_jobs.h[set].p + off_fwd());
+    for (const uint64_t upto = std::min<uint64_t>(frames_in, next_launch + nframes + D); next_stab < upto; ++next_stab)
+      cf[nfwd++] = g1s_cv::CurveJob{frame(next_stab).in[0], stab_slot(next_stab), frame(next_stab).in_stride[0], (uint32_t)stab_row};
+  }
   for (uint32_t i = 0; i < nframes; ++i) {
     const uint64_t n = next_launch + i;
     const Queued &f = frame(n);
@@ -283,24 +321,44 @@ int g1s_denoise::flush(uint32_t nframes) {
       job.out_stride[c] = f.host_out ? (uint32_t)stage.row[c] : f.out_stride[c];
     }
     host_outs = host_outs || f.host_out;
+    // (rule 14) the luma launch's job: from the frame's slot into plane i of the filtered ones, which the inverse takes
+    // to where the frame's luma goes
+    DenoiseJob lj{};
+    if (curve) {
+      lj.in[0] = stab_slot(n), lj.out[0] = d_filt + stab_plane * i, lj.in_stride[0] = lj.out_stride[0] = (uint32_t)stab_row;
+      reinterpret_cast<g1s_cv::CurveJob *>(p_jobs.h[set].p + off_inv())[i] = g1s_cv::CurveJob{lj.out[0], job.out[0], (uint32_t)stab_row, job.out_stride[0]};
+    }
     if (!D) {
       reinterpret_cast<DenoiseJob *>(p_jobs.h[set].p)[i] = job;
+      if (curve) reinterpret_cast<DenoiseJob *>(p_jobs.h[set].p + off_luma())[i] = lj;
       continue;
     }
-    DenoiseJobT t{};
-    t.f = job;
+    DenoiseJobT t{}, lt{};
+    t.f = job, lt.f = lj;
     int k = 0;
     for (int64_t m = (int64_t)n - (int64_t)D; m <= (int64_t)(n + D); ++m) {
       if (m == (int64_t)n) continue;
-      if (m >= (int64_t)clip_first && m < (int64_t)frames_in)  // rule 5: the frames the clip has
+      if (m >= (int64_t)clip_first && m < (int64_t)frames_in) {  // rule 5: the frames the clip has
         for (int c = 0; c < geom.nplanes; ++c) t.nb[c][k] = frame((uint64_t)m).in[c], t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
+        if (curve) lt.nb[0][k] = stab_slot((uint64_t)m), lt.nb_stride[0][k] = (uint32_t)stab_row;
+      }
       ++k;
     }
     reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p)[i] = t;
+    if (curve) reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p + off_luma())[i] = lt;
   }
-  G1S_OP_TRY(p_jobs.upload(set, job_bytes() * nframes, stream));
+  G1S_OP_TRY(p_jobs.upload(set, curve ? set_bytes() : job_bytes() * nframes, stream));
   if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
-  if ((rc = launch(set, nframes, 0, 1)) != 0) return rc;
+  if (curve) {
+    const uint8_t *dj = p_jobs.d[set].p;
+    G1S_OP_TRY(g1s_cv::launch_curve((int)bps, 2, reinterpret_cast<const g1s_cv::CurveJob *>(dj + off_fwd()), nfwd, d_curve, 1u << bit_depth, (uint32_t)geom.W,
+                                    (uint32_t)geom.H, stream));
+    if ((rc = launch(set, nframes, 0, 1, true)) != 0) return rc;
+    G1S_OP_TRY(g1s_cv::launch_curve(2, (int)bps, reinterpret_cast<const g1s_cv::CurveJob *>(dj + off_inv()), nframes, d_curve + (1u << bit_depth),
+                                    g1s_cv::kInvEntries, (uint32_t)geom.W, (uint32_t)geom.H, stream));
+  } else if ((rc = launch(set, nframes, 0, 1)) != 0) {
+    return rc;
+  }
   if (geom.nplanes == 3 && (rc = joint ? launch_joint(set, nframes) : launch(set, nframes, 1, 2)) != 0) return rc;
   if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
   if ((rc = set_done(set)) != 0) return rc;
@@ -332,34 +390,57 @@ int g1s_denoise::end_clip() {
   int rc = launch_up_to(frames_in);
   if (rc || (rc = wait()) != 0) return rc;
   queue.clear();
-  first_queued = clip_first = frames_complete = frames_in;
+  first_queued = clip_first = frames_complete = next_stab = frames_in;
   return G1S_OK;
 }
 
-extern "C" {
-
-int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double strength, uint16_t T[1024], uint32_t *q) {
-  return g1s_denoise_weights_ex(bit_depth, patch_radius, strength, 0, T, q);
-}
-
-int g1s_denoise_weights_ex(uint32_t bit_depth, uint32_t patch_radius, double strength, uint32_t flags, uint16_t T[1024], uint32_t *q) {
-  if (!T || !q) return G1S_ERR_INVALID;
-  const std::string why = flags & ~G1S_DENOISE_JOINT_CHROMA ? std::string("unknown denoise flags")
-                                                            : make_table(bit_depth, patch_radius, strength, T, q, flags & G1S_DENOISE_JOINT_CHROMA ? 3 : 1);
-  if (!why.empty()) {
-    g1s_set_global_error_(why.c_str());
-    return G1S_ERR_INVALID;
+// A grain prior as the file commands take it: the table at `path`, its segment `segment` alone or (negative) the mean of
+// all of them, range R (0 = the default).  load() reads and parses; make() is g1s_denoise_curve for the clip's depth.
+struct Prior {
+  std::vector<g1s_segment_t> segs;
+  uint32_t range = 0;
+  std::string load(const char *path, uint32_t range_, int32_t segment) {
+    range = range_;
+    std::string text;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return std::string("grain prior: cannot open ") + path;
+    char buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+    std::fclose(f);
+    size_t nseg = 0;
+    char perr[256] = "";
+    segs.resize(64);
+    int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
+    if (rc == G1S_ERR_CAPACITY) {
+      segs.resize(nseg);
+      rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
+    }
+    if (rc) return std::string("grain prior: ") + perr;
+    segs.resize(nseg);
+    if (segment >= 0 && (size_t)segment >= nseg)
+      return "grain prior: segment " + std::to_string(segment) + " is not in the table (" + std::to_string(nseg) + " segments)";
+    if (segment >= 0) segs = {segs[(size_t)segment]};
+    return "";
   }
-  return G1S_OK;
-}
+  std::string make(uint32_t bit_depth, std::vector<uint16_t> &fwd, std::vector<uint16_t> &inv) const {
+    fwd.assign((size_t)1 << (bit_depth <= 12 ? bit_depth : 12), 0), inv.assign(g1s_cv::kInvEntries, 0);
+    return g1s_cv::build(segs.data(), segs.size(), bit_depth, range, fwd.data(), inv.data());
+  }
+  // the denoiser for a clip of this depth; NULL with the global error text set
+  g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags) const {
+    std::vector<uint16_t> fwd, inv;
+    const std::string why = make(bit_depth, fwd, inv);
+    if (!why.empty()) {
+      g1s_set_global_error_(why.c_str());
+      return nullptr;
+    }
+    return g1s_denoise_new_curve(bit_depth, opts, D, flags, fwd.data(), inv.data());
+  }
+};
 
-g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return g1s_denoise_new_temporal(bit_depth, opts, 0); }
-
-g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius) {
-  return g1s_denoise_new_ex(bit_depth, opts, temporal_radius, 0);
-}
-
-g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags) {
+// what every g1s_denoise_new* call makes; `curve`: with the pair (fwd, inv) of rules 12 - 15
+static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, bool curve,
+                                 const uint16_t *fwd, const uint16_t *inv) {
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -380,13 +461,18 @@ g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *
     g1s_set_global_error_("unknown denoise flags");
     return nullptr;
   }
-  std::vector<uint16_t> tables(3 * kTable);
-  uint32_t q[3];
+  std::vector<uint16_t> tables(4 * kTable);
+  uint32_t q[4] = {0, 0, 0, 0};
   std::string why = make_table(bit_depth, S, h, tables.data(), &q[0]);
   if (why.empty()) {
     why = make_table(bit_depth, S, hc, tables.data() + kTable, &q[1]);
     if (why.empty()) why = make_table(bit_depth, S, hc, tables.data() + 2 * kTable, &q[2], 3);
     if (!why.empty()) why = "chroma_" + why;
+  }
+  // the curve: luma is filtered as a 12-bit plane with the luma strength (rule 14)
+  if (why.empty() && curve) {
+    why = g1s_cv::check(bit_depth, fwd, inv);
+    if (why.empty()) why = make_table(g1s_cv::kStabBits, S, h, tables.data() + 3 * kTable, &q[3]);
   }
   if (!why.empty()) {
     g1s_set_global_error_(why.c_str());
@@ -413,17 +499,56 @@ g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *
   }
   g1s_denoise *g = new g1s_denoise;
   g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
-  for (int i = 0; i < 3; ++i) g->q[i] = q[i];
+  g->curve = curve;
+  for (int i = 0; i < 4; ++i) g->q[i] = q[i];
   bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
   for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  ok = ok && g->p_jobs.alloc(g->job_bytes() * g->batch) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
+  ok = ok && g->p_jobs.alloc(g->set_bytes()) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
        hipMemcpy(g->d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && curve) {
+    const size_t nf = (size_t)1 << bit_depth;
+    ok = hipMalloc((void **)&g->d_curve.p, (nf + g1s_cv::kInvEntries) * 2) == hipSuccess &&
+         hipMemcpy(g->d_curve, fwd, nf * 2, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(g->d_curve + nf, inv, g1s_cv::kInvEntries * 2, hipMemcpyHostToDevice) == hipSuccess;
+  }
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    g1s_denoise_free(g);
+    free_op(g);
     return nullptr;
   }
   return g;
+}
+
+extern "C" {
+
+int g1s_denoise_weights(uint32_t bit_depth, uint32_t patch_radius, double strength, uint16_t T[1024], uint32_t *q) {
+  return g1s_denoise_weights_ex(bit_depth, patch_radius, strength, 0, T, q);
+}
+
+int g1s_denoise_weights_ex(uint32_t bit_depth, uint32_t patch_radius, double strength, uint32_t flags, uint16_t T[1024], uint32_t *q) {
+  if (!T || !q) return G1S_ERR_INVALID;
+  const std::string why = flags & ~G1S_DENOISE_JOINT_CHROMA ? std::string("unknown denoise flags")
+                                                            : make_table(bit_depth, patch_radius, strength, T, q, flags & G1S_DENOISE_JOINT_CHROMA ? 3 : 1);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return G1S_OK;
+}
+
+g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return g1s_denoise_new_temporal(bit_depth, opts, 0); }
+
+g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius) {
+  return g1s_denoise_new_ex(bit_depth, opts, temporal_radius, 0);
+}
+
+g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags) {
+  return new_denoiser(bit_depth, opts, temporal_radius, flags, false, nullptr, nullptr);
+}
+
+g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
+                                     const uint16_t *inv) {
+  return new_denoiser(bit_depth, opts, temporal_radius, flags, true, fwd, inv);
 }
 
 int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out) {
@@ -439,7 +564,8 @@ int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out)
     if ((rc = g->end_clip()) != 0) return rc;
     g->have_geom = false;
   }
-  if (!g->have_geom) g->set_frame_geometry(*in);
+  if (!g->have_geom) g->set_frame_geometry(*in), g->d_stab = DevBuf<uint8_t>(), g->d_filt = DevBuf<uint8_t>();
+  if (g->curve && (rc = g->need_stab()) != 0) return rc;
   const PlaneGeom &gm = g->geom;
   g1s_denoise::Queued f{};
   // the input ring's slot: a launched frame stays a neighbour.  The output buffer is `batch` slots, chosen at the launch
@@ -519,14 +645,30 @@ int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s
 
 int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, char *err,
                                 size_t cap) {
+  return g1s_denoise_y4m_file_curve(in, out, opts, temporal_radius, flags, nullptr, 0, -1, err, cap);
+}
+
+int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                   const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, char *err, size_t cap) {
+  Prior prior;
+  if (prior_tbl) {
+    const std::string why = prior.load(prior_tbl, prior_range, prior_segment);
+    if (!why.empty()) {
+      if (err && cap) snprintf(err, cap, "%s", why.c_str());
+      return G1S_ERR_INVALID;
+    }
+  }
   // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
   // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
   struct Driver {
     const g1s_denoise_opts_t *opts;
     uint32_t D, flags;
+    const Prior *prior;
     g1s_denoise_t *g = nullptr;
     const int new_failed = G1S_ERR_INVALID;
-    bool open(const g1s_y4m_info_t &i) { return (g = g1s_denoise_new_ex(i.bit_depth, opts, D, flags)) != nullptr; }
+    bool open(const g1s_y4m_info_t &i) {
+      return (g = prior ? prior->open(i.bit_depth, opts, D, flags) : g1s_denoise_new_ex(i.bit_depth, opts, D, flags)) != nullptr;
+    }
     uint32_t batch() const { return g->batch; }
     uint32_t ring() const { return g->batch + g->D; }
     int frame(int64_t, const g1s_frame_t *fin, g1s_frame_t *fout) { return g1s_denoise_frame(g, fin, fout); }
@@ -534,7 +676,7 @@ int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoi
     const char *last_error() const { return g1s_denoise_last_error(g); }
     void close() { g1s_denoise_free(g); }
   };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags});
+  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior_tbl ? &prior : nullptr});
 }
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
@@ -555,6 +697,12 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
 int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                   const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, uint64_t *frames_out, char *err,
                                   size_t cap) {
+  return g1s_diff_y4m_file_denoised_curve(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, nullptr, 0, -1, frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                     const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                     uint32_t prior_range, int32_t prior_segment, uint64_t *frames_out, char *err, size_t cap) {
   auto refuse = [&](int code, const std::string &m) {
     if (err && cap) snprintf(err, cap, "%s", m.c_str());
     return code;
@@ -562,6 +710,11 @@ int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const
   if (frames_out) *frames_out = 0;
   if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
   if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
+  Prior prior;
+  if (prior_tbl) {
+    const std::string no = prior.load(prior_tbl, prior_range, prior_segment);
+    if (!no.empty()) return refuse(G1S_ERR_INVALID, no);
+  }
   const std::string header = y4m_header_line(source);
   g1s_y4m_t *y = g1s_y4m_open(source, err, cap);
   if (!y) return G1S_ERR_INVALID;
@@ -598,7 +751,7 @@ int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const
     if (dopts) d = *dopts;
     d.struct_size = sizeof d;
     d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = g1s_denoise_new_ex(info.bit_depth, &d, temporal_radius, flags);
+    dn = prior_tbl ? prior.open(info.bit_depth, &d, temporal_radius, flags) : g1s_denoise_new_ex(info.bit_depth, &d, temporal_radius, flags);
   }
   if (!dn) {
     rc = G1S_ERR_INVALID, why = g1s_last_global_error();

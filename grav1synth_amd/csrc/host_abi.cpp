@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "curve.h"
 #include "fold.h"
 #include "host_pool.h"
 #include "record.h"
@@ -475,6 +476,16 @@ int g1s_write_tbl(const char *path, const g1s_segment_t *segs, size_t n) {
   const size_t w = fwrite(buf.data(), 1, (size_t)k, f);
   const int c = fclose(f);
   return (w == (size_t)k && c == 0) ? G1S_OK : G1S_ERR_INVALID;
+}
+
+// rules 12 and 13 of `denoise` (curve.h): needs no device, like the tables of its weights
+int g1s_denoise_curve(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  const std::string why = !fwd || !inv ? std::string("g1s_denoise_curve needs both output tables") : g1s_cv::build(segs, n, bit_depth, range, fwd, inv);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return G1S_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 >>> clips = Denoiser(10, temporal_radius=2).denoise_clip(frames)   # the mean also runs over 2 frames either side
 >>> denoise_y4m_file("grainy.y4m", "clean.y4m", temporal_radius=1)
 >>> Denoiser(10, joint_chroma=True).apply([y, u, v])   # Cb and Cr share one weight, guided by the luma at the same place
+>>> Denoiser(10, curve=grain_curve(segments, 10)).apply([y, u, v])   # luma strength follows a grain table's scaling function
+>>> denoise_y4m_file("grainy.y4m", "clean.y4m", grain_prior="first_pass.tbl")
 """
 from __future__ import annotations
 
@@ -54,21 +56,50 @@ def weight_table(bit_depth: int, patch_radius: int = 2, strength: float = 4.0, j
     return t, int(q.value)
 
 
+def grain_curve(segments: Sequence, bit_depth: int, range: int = 0, segment: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(fwd, inv): the variance-stabilising curve of a grain table's luma scaling function and its inverse (rules 12 and 13
+    of include/g1s_diff.h; host only, no device needed).  segments: GrainTableSegment objects; the curve is made from
+    their unweighted mean, or from segments[segment] alone.  range R: the strongest strength over the weakest, 1 ..
+    2^(12 - bit_depth), 0 = min(4, that).  fwd has 1 << bit_depth uint16 entries, inv 4096."""
+    L = _lib.lib()
+    segments = list(segments)
+    if segment is not None:
+        if not 0 <= segment < len(segments):
+            raise G1SError(-1, f"grain prior: segment {segment} is not in the table ({len(segments)} segments)")
+        segments = [segments[segment]]
+    arr = (_lib.G1SSegment * max(len(segments), 1))(*[s.to_c() for s in segments])
+    fwd = np.zeros(1 << bit_depth if 0 < bit_depth <= 12 else 1, np.uint16)
+    inv = np.zeros(4096, np.uint16)
+    rc = L.g1s_denoise_curve(arr, len(segments), bit_depth, range & 0xFFFFFFFF, fwd.ctypes.data, inv.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return fwd, inv
+
+
 class Denoiser(FrameOp):
     _name = "denoise"
 
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                 strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False):
+                 strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
+                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
         runs over the D frames before and the D frames after it that the clip has.  joint_chroma: the two chroma planes
         share one weight, taken from Cb, Cr and the input luma at chroma resolution (rules 8 - 11 of include/g1s_diff.h);
-        luma, and a luma-only frame, are filtered as without it."""
+        luma, and a luma-only frame, are filtered as without it.  curve = (fwd, inv) of grain_curve(): luma is filtered in
+        the domain where the prior's grain has one size at every intensity (rules 12 - 15); chroma as without it."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal_radius = temporal_radius
         self.joint_chroma = bool(joint_chroma)
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
-        self._h = self._L.g1s_denoise_new_ex(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma))
+        if curve is None:
+            self._h = self._L.g1s_denoise_new_ex(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma))
+        else:
+            fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
+            if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
+                raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
+            self._h = self._L.g1s_denoise_new_curve(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
+                                                    inv.ctypes.data)
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
@@ -109,19 +140,26 @@ class Denoiser(FrameOp):
         self._keep.clear()
 
     def kernel_times(self, enable: bool = True):
-        """(ms in kd_nlm / kd_nlm_t and their joint chroma forms, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        """(ms in kd_nlm / kd_nlm_t and their joint chroma forms -- with a curve also the two kd_curve launches -- , frames) of the timed batches
+        so far (HIP events); enables / disables the timing."""
         a, n = C.c_double(), C.c_uint64()
         self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
         return a.value, n.value
 
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
-                     strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False) -> int:
-    """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  Returns the number of frames."""
+                     strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
+                     grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None) -> int:
+    """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
+    function the luma strength follows (grain_curve() with prior_range and prior_segment).  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
-    n = L.g1s_denoise_y4m_file_ex(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), err, len(err))
+    if grain_prior is None and (prior_range or prior_segment is not None):
+        raise G1SError(-1, "prior_range and prior_segment need grain_prior")
+    n = L.g1s_denoise_y4m_file_curve(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
+                                     str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF,
+                                     -1 if prior_segment is None else prior_segment, err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

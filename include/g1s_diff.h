@@ -498,6 +498,27 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *  11. out_Cb(p) and out_Cr(p) are each rule 4 with the one shared w.  11t: with a temporal radius rules 5 - 7 hold with D_k
  *      the sum over Cb, Cr and G of rule 6's distance between frame t and frame t + k (G of frame t + k from that
  *      frame's input luma), the same T_J, and both numerators in 64 bits.
+ * A grain prior (g1s_denoise_new_curve): luma is filtered in a domain where a grain table's grain has one size at every
+ * intensity -- a variance-stabilising curve f in front of rules 1 - 7 and its inverse g behind them.  B in {8, 10},
+ * M = 2^B - 1; the stabilised domain is always 12 bits (0 .. 4095):
+ *  12. The curve from n >= 1 segments.  s_i(v), v = 0 .. M, is the AV1 specification's scale_lut (7.18.3.5) over the
+ *      luma ScalingLut (7.18.3.4) of segment i, s_i = 0 for a segment without luma points;
+ *      s(v) = (sum_i s_i(v) + (n >> 1)) / n, the unweighted mean (the last segment's end_time is effectively infinite, so
+ *      durations cannot weight it).  Range R in 1 .. 2^(12 - B) (16 at 8 bits, 4 at 10), 0 = min(4, 2^(12 - B)):
+ *      floor = max(1, ceil(max_v s(v) / R)), sigma'(v) = max(s(v), floor), r(v) = floor(2^24 / sigma'(v)),
+ *      C(x) = sum over v < x of r(v) in 64 bits, f(x) = (4095 C(x) + (C(M) >> 1)) / C(M).  f(0) = 0, f(M) = 4095, and the
+ *      bound on R makes every slope at least 1.0006, so f is strictly increasing (the builder checks it: a failure is an
+ *      internal error).  R = 1, or a table without luma grain, gives the flat curve.
+ *  13. The inverse g(y), y = 0 .. 4095, is the smallest x with |f(x) - y| minimal, so g(f(x)) = x: the algebraic inverse,
+ *      no bias correction.
+ *  14. Luma: u' = f[min(u, M)]; u' is filtered by rules 1 - 7 as a 12-bit plane with rule 3's table at B = 12 and the luma
+ *      strength h (g1s_denoise_weights(12, S, h)) into v; out = g[v].  Where the curve's slope is its mean (about
+ *      2^(12 - B)) the strength is h; elsewhere it is h x mean slope / slope(x): proportional to the table's grain, within a
+ *      factor R between the weakest and the strongest.
+ *  15. Chroma is untouched: the two chroma planes are filtered, independently or jointly, exactly as without a curve, and
+ *      rule 8's guide stays the unstabilised input luma.  A 12-bit clip has no headroom in 12-bit kernels and is refused.
+ * With a curve the denoiser keeps (2 batch_frames + 2 D) 12-bit u16 luma planes on the device; the caller's input luma is
+ * never written.
  * No motion compensation, no dithering.  Samples above the bit depth's maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes -- under the flag one workgroup filters both) on the denoiser's own stream.  A workgroup's LDS grows
@@ -523,6 +544,18 @@ g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_op
 /* The same with flags (G1S_DENOISE_*; rules 8 - 11); g1s_denoise_new_temporal is flags = 0.  An unknown flag bit is a
  * refusal like the others ("unknown denoise flags"), checked before a device is looked for. */
 g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags);
+/* The same with a grain prior's curve (rules 12 - 15): fwd[1 << bit_depth] is f, inv[4096] is g, as g1s_denoise_curve
+ * makes them (copied before the call returns).  The pair is checked as given -- bit_depth 8 or 10 (12 is refused: no
+ * headroom), fwd[0] = 0, fwd[M] = 4095, fwd strictly increasing, inv non-decreasing and at most M, inv[fwd[x]] = x -- and
+ * anything else is a refusal with its text, like the others checked before a device is looked for.  Every other
+ * g1s_denoise_new* call is the case without a curve. */
+g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                     const uint16_t *fwd, const uint16_t *inv);
+/* Rules 12 and 13: the pair (f, g) for the luma scaling functions of n >= 1 segments of a grain table, range R (0 = the
+ * default).  fwd: 1 << bit_depth entries, inv: 4096.  Host only: needs no device.  G1S_ERR_INVALID (reason from
+ * g1s_last_global_error()) for bit_depth 12 or any other than 8 and 10, a range above 2^(12 - bit_depth), n = 0, and luma
+ * points whose values do not increase. */
+int g1s_denoise_curve(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv);
 /* One frame.  in / out follow g1s_frame_t.on_device independently, as in g1s_grain_frame: 0 = host (in: copied before
  * the call returns; out: written by g1s_denoise_sync at the latest), 1 = device, 2 = pinned host (copies queued).  Device
  * and pinned planes of in must stay valid and unmodified, and every plane of out must stay valid, until
@@ -564,6 +597,12 @@ int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s
 /* The same with flags (G1S_DENOISE_*); g1s_denoise_y4m_file_temporal is flags = 0. */
 int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, char *err,
                                 size_t cap);
+/* The same with a grain prior (`--grain-prior`): the curve of the table at prior_tbl for the clip's bit depth, range
+ * prior_range (0 = the default), from segment prior_segment alone or, when that is negative, from the mean of all of them.
+ * A table that does not parse, a segment the table does not have and a 12-bit clip are refusals with their text.
+ * prior_tbl == NULL is g1s_denoise_y4m_file_ex. */
+int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                   const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, char *err, size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -579,6 +618,11 @@ int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl,
 int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                   const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, uint64_t *frames, char *err,
                                   size_t cap);
+/* The same with a grain prior, as g1s_denoise_y4m_file_curve takes it: typically the table a first `diff SOURCE --denoise`
+ * made.  prior_tbl == NULL is g1s_diff_y4m_file_denoised_ex. */
+int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                     const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                     uint32_t prior_range, int32_t prior_segment, uint64_t *frames, char *err, size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

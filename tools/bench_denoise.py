@@ -7,7 +7,11 @@ launches (timed batches run alone and are waited for), frames a second from it, 
 counts it -- samples x pairs: the unordered pairs A + A (2A + 1) of the frame itself and, per neighbour frame, the (2A + 1)^2
 one-sided pairs of rule 6 (a frame at the end of a clip has fewer; the runs are clips of many batches) -- and the job rate
 through g1s_denoise_frame with the timing off.  One JSON line per case.  For the kernel trace:
-rocprofv3 --kernel-trace --stats -- python tools/bench_denoise.py 1 (a run of its own)."""
+rocprofv3 --kernel-trace --stats -- python tools/bench_denoise.py 1 (a run of its own).
+
+tools/bench_denoise.py [batches] --prior -- the cost of a grain prior (rules 12 - 15): both formats at the defaults with
+temporal radius 0 and 1, without and with a curve ("grain_prior" in the line) in one process.  With a curve the timed span
+also holds the two kd_curve launches around the luma launch; their own times come from the kernel trace."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,8 +20,19 @@ from grav1synth_amd.denoise import Denoiser
 from grav1synth_amd.synth import SynthSpec, make_pair
 
 assert torch.cuda.is_available(), "bench_denoise.py needs a GPU"
-batches = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+PRIOR = "--prior" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--prior"]
+batches = int(args[0]) if args else 4
 BATCH = 64
+if PRIOR:
+    from grav1synth_amd.denoise import grain_curve
+    from grav1synth_amd.tbl import parse_tbl
+
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference-example-table.tbl"), "rb") as f:
+        PRIOR_SEGMENTS = parse_tbl(f.read())
+    CASES = [(3, 2, d, False, c) for d in (0, 1) for c in (False, True)]
+else:
+    CASES = [(a, s, d, j, False) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (7, 3, 1), (3, 2, 2)) for j in (False, True)]
 
 for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", SynthSpec(1920, 1080, 8))):
     # 8 distinct noisy frames in, 64 distinct frames out (a batch writes every out plane once)
@@ -25,8 +40,9 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
     outs = [[torch.empty_like(p) for p in ins[0]] for _ in range(BATCH)]
     torch.cuda.synchronize()
     samples = sum(p.numel() for p in ins[0])
-    for A, S, D, joint in [(a, s, d, j) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (7, 3, 1), (3, 2, 2)) for j in (False, True)]:
-        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint)
+    for A, S, D, joint, prior in CASES:
+        kw = dict(curve=grain_curve(PRIOR_SEGMENTS, spec.bit_depth)) if prior else {}
+        dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint, **kw)
 
         def run(nb):
             for k in range(nb * BATCH):
@@ -43,7 +59,7 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
         dn.close()
         pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
-            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, **({"grain_prior": prior} if PRIOR else {}), "batch_frames": BATCH, "timed_batches": fr / BATCH,
             "samples_per_frame": samples, "unordered_pairs": pairs, "temporal_pairs": temporal_pairs,
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
             "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
