@@ -22,9 +22,11 @@
 // dn_hsum_t (one operand from L, one from N), barrier, dn_weights_t, barrier, dn_accumulate_t.  The region is the tile
 // itself (kTW x kTH), whatever the offset: the pair {(t, p), (t + k, p + d)} serves two different output frames, so there
 // is no half plane to save, and the weight is read at p only.  Hb and Wb as sized for the frame itself are large enough.
-// The numerator of rule 7 needs 64 bits (dn_store_t).
+// The numerator of rule 7 needs 64 bits (dn_store over uint64_t).
 //
-// The joint chroma filter (rules 8 - 11t, kd_nlm_j and kd_nlm_jt) is at the end of this file.
+// The joint chroma filter (rules 8 - 11t, kd_nlm_j and kd_nlm_jt) runs the same phases over three sample arrays and two output
+// planes (JointGeom).  Every phase is written once, over NA sample arrays and NP output planes LP samples apart (one plane: NA =
+// NP = 1, LP = 0), as the source says (PlaneSrc, JointSrc); dn_spatial and dn_temporal run them; the tile functions own the registers.
 //
 // Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
 // run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.  The tile functions (dn_tile, dn_tile_t,
@@ -75,293 +77,7 @@ G1S_DN_HD TileGeom tile_geom(int A, int S) {
   return g;
 }
 
-G1S_DN_HD int imin(int a, int b) { return a < b ? a : b; }
-G1S_DN_HD int imax(int a, int b) { return a > b ? a : b; }
-// i / n == (i * magic(n)) >> 16 for 0 <= i < 512, 1 <= n <= 128
-G1S_DN_HD uint32_t magic(int n) { return (65536u + (uint32_t)n - 1u) / (uint32_t)n; }
-
-// the tile at (x0, y0) of a W x H plane and its halo into L; coordinates clamp to the plane (rule 1)
-template <int BPS>
-G1S_DN_HD void dn_stage(int tid, const TileGeom &g, uint16_t *L, const uint8_t *in, uint32_t stride, int W, int H, int x0, int y0) {
-  for (int r = tid >> 7; r < g.LH; r += kThreads >> 7) {
-    const int gy = imin(imax(y0 - g.R + r, 0), H - 1);
-    const uint8_t *row = in + (size_t)gy * stride;
-    for (int c = tid & 127; c < g.LW; c += 128) {
-      const int gx = imin(imax(x0 - g.R + c, 0), W - 1);
-      L[r * g.LS + c] = BPS == 2 ? reinterpret_cast<const uint16_t *>(row)[gx] : (uint16_t)row[gx];
-    }
-  }
-}
-
-// Hb(row, x) = sum over |kx| <= S of (L(x + kx, r) - L(x + dx + kx, r + dy))^2 for the region's columns x (RW of them, from
-// -max(dx, 0)) and its rows r = -dy - S + row, row < NR = kTH + dy + 2S.  A task is 8 consecutive columns of a row (the last
-// task of a row starts at RW - 8 and overlaps its neighbour); lanes run down the rows.  mNR = magic(NR).
-template <int S>
-G1S_DN_HD void dn_hsum(int tid, const TileGeom &g, const uint16_t *L, uint32_t *Hb, int dx, int dy, int RW, int NR, uint32_t mNR) {
-  const int ntasks = ((RW + 7) >> 3) * NR;
-  const int ox = -imax(dx, 0);
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
-    const int xs = imin(seg * 8, RW - 8);
-    const uint16_t *a = L + (row + g.A - dy) * g.LS + (ox + xs - S + g.R);
-    const uint16_t *b = a + dy * g.LS + dx;
-    int sq[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) {
-      const int t = (int)a[j] - (int)b[j];
-      sq[j] = t * t;
-    }
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += (uint32_t)sq[j];
-    uint32_t *o = Hb + row * g.HS + xs;
-    o[0] = s;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-      s += (uint32_t)sq[j + 2 * S] - (uint32_t)sq[j - 1];
-      o[j] = s;
-    }
-  }
-}
-
-// Wb(y, x) = T[min(D >> q, 1023)] with D = the sum of Hb over the 2S + 1 rows from y, for the region's RW x RH samples
-// p = (x0 - max(dx, 0) + x, y0 - dy + y); 0 where p or p + d lies outside the plane (rule 2).  A task is 8 consecutive rows
-// of a column; lanes run along the columns.
-template <int S>
-G1S_DN_HD void dn_weights(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int RW,
-                          int RH, uint32_t mRW, int x0, int y0, int W, int H) {
-  const int ntasks = ((RH + 7) >> 3) * RW;
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int seg = (int)(((uint32_t)i * mRW) >> 16), x = i - seg * RW;
-    const int ys = imin(seg * 8, RH - 8);
-    const uint32_t *h = Hb + ys * g.HS + x;
-    uint32_t v[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += v[j];
-    const int px = x0 - imax(dx, 0) + x, py = y0 - dy + ys;
-    const bool col_ok = px >= 0 && px < W && px + dx >= 0 && px + dx < W;
-    uint16_t *o = Wb + ys * g.WS + x;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j) s += v[j + 2 * S] - v[j - 1];
-      const uint32_t k = s >> q;
-      const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
-      const bool ok = col_ok && py + j >= 0 && py + j + dy < H;  // (dy >= 0: the other two row bounds follow)
-      o[j * g.WS] = ok ? w : (uint16_t)0;
-    }
-  }
-}
-
-// the two pairs of offset d at each sample the thread owns: {p, p + d}, weight at p, and {p - d, p}, weight at p - d
-G1S_DN_HD void dn_accumulate(int tid, const TileGeom &g, const uint16_t *L, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint32_t *au) {
-  const int x = tid & 63, yb = tid >> 6;
-  const uint16_t *w1 = Wb + (yb + dy) * g.WS + x + imax(dx, 0);
-  const uint16_t *w2 = Wb + yb * g.WS + x + imax(-dx, 0);
-  const uint16_t *u1 = L + (yb + dy + g.R) * g.LS + x + dx + g.R;
-  const uint16_t *u2 = L + (yb - dy + g.R) * g.LS + x - dx + g.R;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const uint32_t a = w1[4 * j * g.WS], b = w2[4 * j * g.WS];
-    aw[j] += a + b;
-    au[j] += a * u1[4 * j * g.LS] + b * u2[4 * j * g.LS];
-  }
-}
-
-// d = 0: weight T[0] = 4096 on the sample itself
-G1S_DN_HD void dn_init(int tid, const TileGeom &g, const uint16_t *L, uint32_t *aw, uint32_t *au) {
-  const uint16_t *u = L + ((tid >> 6) + g.R) * g.LS + (tid & 63) + g.R;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) aw[j] = 4096u, au[j] = 4096u * u[4 * j * g.LS];
-}
-
-// rule 4: one rounded division per sample
-template <int BPS>
-G1S_DN_HD void dn_store(int tid, uint8_t *out, uint32_t stride, int W, int H, int x0, int y0, const uint32_t *aw, const uint32_t *au) {
-  const int x = x0 + (tid & 63);
-  if (x >= W) return;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const int y = y0 + (tid >> 6) + 4 * j;
-    if (y >= H) break;
-    const uint32_t v = (au[j] + (aw[j] >> 1)) / aw[j];
-    uint8_t *row = out + (size_t)y * stride;
-    if (BPS == 2) reinterpret_cast<uint16_t *>(row)[x] = (uint16_t)v;
-    else row[x] = (uint8_t)v;
-  }
-}
-
-// ---- the temporal part: one neighbour frame, staged into N by dn_stage --------------------------------------------
-
-// Hb(row, x) = sum over |kx| <= S of (L(x + kx, r) - N(x + dx + kx, r + dy))^2 for the tile's columns x < kTW and the rows
-// r = row - S, row < kTH + 2S; dx and dy of either sign.  Tasks as in dn_hsum.
-template <int S>
-G1S_DN_HD void dn_hsum_t(int tid, const TileGeom &g, const uint16_t *L, const uint16_t *N, uint32_t *Hb, int dx, int dy) {
-  constexpr int NR = kTH + 2 * S, ntasks = (kTW >> 3) * NR;
-  const uint32_t mNR = magic(NR);
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
-    const int xs = seg * 8;
-    const uint16_t *a = L + (row + g.A) * g.LS + (xs + g.A);
-    const uint16_t *b = N + (row + g.A + dy) * g.LS + (xs + g.A + dx);
-    int sq[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) {
-      const int t = (int)a[j] - (int)b[j];
-      sq[j] = t * t;
-    }
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += (uint32_t)sq[j];
-    uint32_t *o = Hb + row * g.HS + xs;
-    o[0] = s;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-      s += (uint32_t)sq[j + 2 * S] - (uint32_t)sq[j - 1];
-      o[j] = s;
-    }
-  }
-}
-
-// Wb(y, x) = T[min(D_k >> q, 1023)] for the tile's samples p = (x0 + x, y0 + y); 0 where p or p + d lies outside the plane
-// (rule 6).  Tasks as in dn_weights.
-template <int S>
-G1S_DN_HD void dn_weights_t(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int x0,
-                            int y0, int W, int H) {
-  constexpr int ntasks = (kTH >> 3) * kTW;
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int x = i % kTW, ys = i / kTW * 8;
-    const uint32_t *h = Hb + ys * g.HS + x;
-    uint32_t v[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += v[j];
-    const int px = x0 + x, py = y0 + ys;
-    const bool col_ok = px < W && px + dx >= 0 && px + dx < W;
-    uint16_t *o = Wb + ys * g.WS + x;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (j) s += v[j + 2 * S] - v[j - 1];
-      const uint32_t k = s >> q;
-      const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
-      const bool ok = col_ok && py + j < H && py + j + dy >= 0 && py + j + dy < H;
-      o[j * g.WS] = ok ? w : (uint16_t)0;
-    }
-  }
-}
-
-// the pair {(t, p), (t + k, p + d)} at each sample the thread owns: weight at p, sample from N
-G1S_DN_HD void dn_accumulate_t(int tid, const TileGeom &g, const uint16_t *N, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint64_t *au) {
-  const int x = tid & 63, yb = tid >> 6;
-  const uint16_t *w = Wb + yb * g.WS + x;
-  const uint16_t *u = N + (yb + dy + g.R) * g.LS + x + dx + g.R;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const uint32_t a = w[4 * j * g.WS];
-    aw[j] += a;
-    au[j] += (uint64_t)a * u[4 * j * g.LS];
-  }
-}
-
-// (n + (d >> 1)) / d for a quotient below 2^16 (a weighted mean of samples), d < 2^24: the float quotient is within one
-// of the integer one (its relative error is a few 2^-24), and one step either way makes it exact
-G1S_DN_HD uint32_t dn_rounded_mean(uint64_t n, uint32_t d) {
-  n += d >> 1;
-  uint32_t v = (uint32_t)((float)n * (1.0f / (float)d));
-  const int64_t r = (int64_t)n - (int64_t)((uint64_t)v * d);
-  if (r < 0) --v;
-  else if (r >= (int64_t)d) ++v;
-  return v;
-}
-
-// rule 7: one rounded division per sample, the numerator in 64 bits
-template <int BPS>
-G1S_DN_HD void dn_store_t(int tid, uint8_t *out, uint32_t stride, int W, int H, int x0, int y0, const uint32_t *aw, const uint64_t *au) {
-  const int x = x0 + (tid & 63);
-  if (x >= W) return;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const int y = y0 + (tid >> 6) + 4 * j;
-    if (y >= H) break;
-    const uint32_t v = dn_rounded_mean(au[j], aw[j]);
-    uint8_t *row = out + (size_t)y * stride;
-    if (BPS == 2) reinterpret_cast<uint16_t *>(row)[x] = (uint16_t)v;
-    else row[x] = (uint8_t)v;
-  }
-}
-
-// the frame's own offsets (rules 1 - 3) of one tile for thread `tid` of a workgroup whose barrier is `sync` (LDS buffers as
-// laid out by tile_geom): L and T staged, the sums of rule 4 in aw and au
-template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile_spatial(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, int W,
-                               int H, int x0, int y0, Sync sync, uint32_t *aw, uint32_t *au) {
-  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + g.offH);
-  uint16_t *L = reinterpret_cast<uint16_t *>(lds + g.offL), *Wb = reinterpret_cast<uint16_t *>(lds + g.offW),
-           *T = reinterpret_cast<uint16_t *>(lds + g.offT);
-  dn_stage<BPS>(tid, g, L, in, in_stride, W, H, x0, y0);
-  for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
-  sync();
-  dn_init(tid, g, L, aw, au);
-  for (int dy = 0; dy <= g.A; ++dy) {
-    const int NR = kTH + dy + 2 * S, RH = kTH + dy;
-    const uint32_t mNR = magic(NR);
-    for (int dx = dy ? -g.A : 1; dx <= g.A; ++dx) {
-      const int RW = kTW + (dx < 0 ? -dx : dx);
-      dn_hsum<S>(tid, g, L, Hb, dx, dy, RW, NR, mNR);
-      sync();
-      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, W, H);
-      sync();
-      dn_accumulate(tid, g, L, Wb, dx, dy, aw, au);
-    }
-  }
-}
-
-// one tile, start to end
-template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
-                       uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
-  uint32_t aw[kSPT], au[kSPT];
-  dn_tile_spatial<S, BPS>(tid, g, lds, table, q, in, in_stride, W, H, x0, y0, sync, aw, au);
-  dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
-}
-
-// one tile of the temporal filter: `nb` / `nb_stride` are the same plane of the 2 D frames around the frame in hand, a null
-// pointer where the clip has no such frame (rule 5) -- the same for every thread of the workgroup.  The order of the
-// neighbours does not show in the result: the sums are exact.
-template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile_t(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride,
-                         const uint8_t *const *nb, const uint32_t *nb_stride, int nnb, uint8_t *out, uint32_t out_stride, int W, int H, int x0, int y0,
-                         Sync sync) {
-  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + g.offH);
-  uint16_t *L = reinterpret_cast<uint16_t *>(lds + g.offL), *Wb = reinterpret_cast<uint16_t *>(lds + g.offW),
-           *T = reinterpret_cast<uint16_t *>(lds + g.offT), *N = reinterpret_cast<uint16_t *>(lds + g.offN);
-  uint32_t aw[kSPT], au32[kSPT];
-  dn_tile_spatial<S, BPS>(tid, g, lds, table, q, in, in_stride, W, H, x0, y0, sync, aw, au32);  // (fits 32 bits, as in dn_tile)
-  uint64_t au[kSPT];
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) au[j] = au32[j];
-  for (int k = 0; k < nnb; ++k) {
-    if (!nb[k]) continue;
-    sync();  // the last dn_accumulate_t has read N
-    dn_stage<BPS>(tid, g, N, nb[k], nb_stride[k], W, H, x0, y0);
-    sync();
-    for (int dy = -g.A; dy <= g.A; ++dy)
-      for (int dx = -g.A; dx <= g.A; ++dx) {
-        dn_hsum_t<S>(tid, g, L, N, Hb, dx, dy);
-        sync();
-        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, W, H);
-        sync();
-        dn_accumulate_t(tid, g, N, Wb, dx, dy, aw, au);
-      }
-  }
-  dn_store_t<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
-}
-
-// ---- luma-guided joint chroma (rules 8 - 11t, kd_nlm_j and kd_nlm_jt): Cb, Cr and the guide G as one weight ---------
+// Luma-guided joint chroma (rules 8 - 11t, kd_nlm_j and kd_nlm_jt): Cb, Cr and the guide G as one weight.
 //
 // Three sample arrays in the layout of L, JointGeom::LP samples apart: Cb, Cr, G.  G is the frame's input luma at chroma
 // resolution (rule 8), formed while staging.  Hb, Wb and T are the ones of tile_geom: the squared differences of the three
@@ -387,10 +103,29 @@ G1S_DN_HD JointGeom joint_geom(const TileGeom &g) {
   return j;
 }
 
+G1S_DN_HD int dn_lp(const TileGeom &) { return 0; }  // samples from one array to the next under either layout
+G1S_DN_HD int dn_lp(const JointGeom &j) { return j.LP; }
+
+G1S_DN_HD int imin(int a, int b) { return a < b ? a : b; }
+G1S_DN_HD int imax(int a, int b) { return a > b ? a : b; }
+// i / n == (i * magic(n)) >> 16 for 0 <= i < 512, 1 <= n <= 128
+G1S_DN_HD uint32_t magic(int n) { return (65536u + (uint32_t)n - 1u) / (uint32_t)n; }
+
+// the tile at (x0, y0) of a W x H plane and its halo into L; coordinates clamp to the plane (rule 1)
 template <int BPS>
-G1S_DN_HD uint32_t dn_sample(const uint8_t *row, int x) {
-  return BPS == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(row)[x] : (uint32_t)row[x];
+G1S_DN_HD void dn_stage(int tid, const TileGeom &g, uint16_t *L, const uint8_t *in, uint32_t stride, int W, int H, int x0, int y0) {
+  for (int r = tid >> 7; r < g.LH; r += kThreads >> 7) {
+    const int gy = imin(imax(y0 - g.R + r, 0), H - 1);
+    const uint8_t *row = in + (size_t)gy * stride;
+    for (int c = tid & 127; c < g.LW; c += 128) {
+      const int gx = imin(imax(x0 - g.R + c, 0), W - 1);
+      L[r * g.LS + c] = BPS == 2 ? reinterpret_cast<const uint16_t *>(row)[gx] : (uint16_t)row[gx];
+    }
+  }
 }
+
+template <int BPS>
+G1S_DN_HD uint32_t dn_sample(const uint8_t *row, int x) { return BPS == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(row)[x] : (uint32_t)row[x]; }
 
 // rule 8 into L: the tile at (x0, y0) of the cw x ch chroma grid and its halo, chroma coordinates clamped to that grid;
 // each sample the rounded mean of a (1 << xdec) x (1 << ydec) box of the W x H luma plane, luma coordinates clamped to it
@@ -416,96 +151,6 @@ G1S_DN_HD void dn_stage_guide(int tid, const TileGeom &g, uint16_t *L, const uin
   }
 }
 
-// dn_hsum over the three arrays: Hb(row, x) = sum over Cb, Cr, G and |kx| <= S of the squared differences
-template <int S>
-G1S_DN_HD void dn_hsum_j(int tid, const TileGeom &g, int LP, const uint16_t *L, uint32_t *Hb, int dx, int dy, int RW, int NR, uint32_t mNR) {
-  const int ntasks = ((RW + 7) >> 3) * NR;
-  const int ox = -imax(dx, 0);
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
-    const int xs = imin(seg * 8, RW - 8);
-    const uint16_t *a = L + (row + g.A - dy) * g.LS + (ox + xs - S + g.R);
-    const uint16_t *b = a + dy * g.LS + dx;
-    uint32_t sq[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) {
-      const int t0 = (int)a[j] - (int)b[j], t1 = (int)a[LP + j] - (int)b[LP + j], t2 = (int)a[2 * LP + j] - (int)b[2 * LP + j];
-      sq[j] = (uint32_t)(t0 * t0) + (uint32_t)(t1 * t1) + (uint32_t)(t2 * t2);
-    }
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += sq[j];
-    uint32_t *o = Hb + row * g.HS + xs;
-    o[0] = s;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-      s += sq[j + 2 * S] - sq[j - 1];
-      o[j] = s;
-    }
-  }
-}
-
-// dn_accumulate for both chroma planes: the weights are read once
-G1S_DN_HD void dn_accumulate_j(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint32_t *aub,
-                               uint32_t *aur) {
-  const int x = tid & 63, yb = tid >> 6;
-  const uint16_t *w1 = Wb + (yb + dy) * g.WS + x + imax(dx, 0);
-  const uint16_t *w2 = Wb + yb * g.WS + x + imax(-dx, 0);
-  const uint16_t *u1 = L + (yb + dy + g.R) * g.LS + x + dx + g.R;
-  const uint16_t *u2 = L + (yb - dy + g.R) * g.LS + x - dx + g.R;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const uint32_t a = w1[4 * j * g.WS], b = w2[4 * j * g.WS];
-    aw[j] += a + b;
-    aub[j] += a * u1[4 * j * g.LS] + b * u2[4 * j * g.LS];
-    aur[j] += a * u1[LP + 4 * j * g.LS] + b * u2[LP + 4 * j * g.LS];
-  }
-}
-
-// dn_hsum_t over the three arrays of the frame (L) and of the neighbour (N)
-template <int S>
-G1S_DN_HD void dn_hsum_jt(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *N, uint32_t *Hb, int dx, int dy) {
-  constexpr int NR = kTH + 2 * S, ntasks = (kTW >> 3) * NR;
-  const uint32_t mNR = magic(NR);
-  for (int i = tid; i < ntasks; i += kThreads) {
-    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
-    const int xs = seg * 8;
-    const uint16_t *a = L + (row + g.A) * g.LS + (xs + g.A);
-    const uint16_t *b = N + (row + g.A + dy) * g.LS + (xs + g.A + dx);
-    uint32_t sq[8 + 2 * S];
-#pragma unroll
-    for (int j = 0; j < 8 + 2 * S; ++j) {
-      const int t0 = (int)a[j] - (int)b[j], t1 = (int)a[LP + j] - (int)b[LP + j], t2 = (int)a[2 * LP + j] - (int)b[2 * LP + j];
-      sq[j] = (uint32_t)(t0 * t0) + (uint32_t)(t1 * t1) + (uint32_t)(t2 * t2);
-    }
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j <= 2 * S; ++j) s += sq[j];
-    uint32_t *o = Hb + row * g.HS + xs;
-    o[0] = s;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) {
-      s += sq[j + 2 * S] - sq[j - 1];
-      o[j] = s;
-    }
-  }
-}
-
-// dn_accumulate_t for both chroma planes
-G1S_DN_HD void dn_accumulate_jt(int tid, const TileGeom &g, int LP, const uint16_t *N, const uint16_t *Wb, int dx, int dy, uint32_t *aw, uint64_t *aub,
-                                uint64_t *aur) {
-  const int x = tid & 63, yb = tid >> 6;
-  const uint16_t *w = Wb + yb * g.WS + x;
-  const uint16_t *u = N + (yb + dy + g.R) * g.LS + x + dx + g.R;
-#pragma unroll
-  for (int j = 0; j < kSPT; ++j) {
-    const uint32_t a = w[4 * j * g.WS];
-    aw[j] += a;
-    aub[j] += (uint64_t)a * u[4 * j * g.LS];
-    aur[j] += (uint64_t)a * u[LP + 4 * j * g.LS];
-  }
-}
-
 // what a joint tile reads and writes: the two chroma planes (cw x ch), the luma plane the guide comes from (W x H)
 struct JointPlanes {
   const uint8_t *cb, *cr, *luma;
@@ -523,39 +168,294 @@ G1S_DN_HD void dn_stage_j(int tid, const TileGeom &g, int LP, uint16_t *L, const
   dn_stage_guide<BPS>(tid, g, L + 2 * LP, p.luma, p.luma_stride, s.W, s.H, s.xdec, s.ydec, s.cw, s.ch, x0, y0);
 }
 
-// the frame's own offsets (rules 8 - 10) of one chroma tile: the arrays and T staged, the sums of rule 11 in aw, aub, aur
-template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile_j_spatial(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
-                                 const JointShape &s, int x0, int y0, Sync sync, uint32_t *aw, uint32_t *aub, uint32_t *aur) {
-  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + jg.offH);
-  uint16_t *L = reinterpret_cast<uint16_t *>(lds + jg.offL), *Wb = reinterpret_cast<uint16_t *>(lds + jg.offW),
-           *T = reinterpret_cast<uint16_t *>(lds + jg.offT);
-  dn_stage_j<BPS>(tid, g, jg.LP, L, p, s, x0, y0);
+// A source is what one frame's tile is staged from: NA sample arrays LP apart, the first NP of them output planes; the
+// grid its weights are bounded by; whether the clip has the frame at all (a null pointer: it has not, rule 5).
+struct PlaneSrc {  // one plane
+  static constexpr int NP = 1, NA = 1;
+  const uint8_t *in;
+  uint32_t stride;
+  int W, H;
+  G1S_DN_HD bool present() const { return in != nullptr; }
+  G1S_DN_HD int grid_w() const { return W; }
+  G1S_DN_HD int grid_h() const { return H; }
+  template <int BPS>
+  G1S_DN_HD void stage(int tid, const TileGeom &g, int, uint16_t *L, int x0, int y0) const { dn_stage<BPS>(tid, g, L, in, stride, W, H, x0, y0); }
+};
+struct JointSrc {  // Cb and Cr, and the guide beside them
+  static constexpr int NP = 2, NA = 3;
+  JointPlanes p;
+  const JointShape &s;
+  G1S_DN_HD bool present() const { return p.luma != nullptr; }
+  G1S_DN_HD int grid_w() const { return s.cw; }
+  G1S_DN_HD int grid_h() const { return s.ch; }
+  template <int BPS>
+  G1S_DN_HD void stage(int tid, const TileGeom &g, int LP, uint16_t *L, int x0, int y0) const { dn_stage_j<BPS>(tid, g, LP, L, p, s, x0, y0); }
+};
+
+// o[j] = sum over the NA arrays and |kx| <= S of (a[j + S + kx] - b[j + S + kx])^2 for j < 8: the squared differences of a
+// column summed in registers (exact in uint32_t), then the sliding sum
+template <int S, int NA>
+G1S_DN_HD void dn_slide8(const uint16_t *a, const uint16_t *b, int LP, uint32_t *o) {
+  uint32_t sq[8 + 2 * S];
+#pragma unroll
+  for (int j = 0; j < 8 + 2 * S; ++j) {
+    sq[j] = 0;
+#pragma unroll
+    for (int n = 0; n < NA; ++n) {
+      const int t = (int)a[n * LP + j] - (int)b[n * LP + j];
+      sq[j] += (uint32_t)(t * t);
+    }
+  }
+  uint32_t s = 0;
+#pragma unroll
+  for (int j = 0; j <= 2 * S; ++j) s += sq[j];
+  o[0] = s;
+#pragma unroll
+  for (int j = 1; j < 8; ++j) {
+    s += sq[j + 2 * S] - sq[j - 1];
+    o[j] = s;
+  }
+}
+
+// Hb(row, x) = sum over the arrays and |kx| <= S of (L(x + kx, r) - L(x + dx + kx, r + dy))^2 for the region's columns x (RW
+// of them, from -max(dx, 0)) and its rows r = -dy - S + row, row < NR = kTH + dy + 2S.  A task is 8 consecutive columns of a
+// row (the last task of a row starts at RW - 8 and overlaps its neighbour); lanes run down the rows.  mNR = magic(NR).
+template <int S, int NA>
+G1S_DN_HD void dn_hsum(int tid, const TileGeom &g, int LP, const uint16_t *L, uint32_t *Hb, int dx, int dy, int RW, int NR, uint32_t mNR) {
+  const int ntasks = ((RW + 7) >> 3) * NR;
+  const int ox = -imax(dx, 0);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = imin(seg * 8, RW - 8);
+    const uint16_t *a = L + (row + g.A - dy) * g.LS + (ox + xs - S + g.R);
+    dn_slide8<S, NA>(a, a + dy * g.LS + dx, LP, Hb + row * g.HS + xs);
+  }
+}
+
+// Hb(row, x) = sum over the arrays and |kx| <= S of (L(x + kx, r) - N(x + dx + kx, r + dy))^2 for the tile's columns x < kTW and
+// the rows r = row - S, row < kTH + 2S; dx and dy of either sign.  Tasks as in dn_hsum, but none overlaps another: 8 divides kTW.
+template <int S, int NA>
+G1S_DN_HD void dn_hsum_t(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *N, uint32_t *Hb, int dx, int dy) {
+  constexpr int NR = kTH + 2 * S, ntasks = (kTW >> 3) * NR;
+  const uint32_t mNR = magic(NR);
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mNR) >> 16), row = i - seg * NR;
+    const int xs = seg * 8;
+    dn_slide8<S, NA>(L + (row + g.A) * g.LS + (xs + g.A), N + (row + g.A + dy) * g.LS + (xs + g.A + dx), LP, Hb + row * g.HS + xs);
+  }
+}
+
+// o[j WS] = T[min(D >> q, 1023)] with D = the sum of Hb over the 2S + 1 rows from h + j HS, for 8 consecutive rows of a
+// column; 0 where the pair takes no part, which is what ok(j) says
+template <int S, class Ok>
+G1S_DN_HD void dn_weights8(const TileGeom &g, const uint32_t *h, uint16_t *o, const uint16_t *T, int q, Ok ok) {
+  uint32_t v[8 + 2 * S];
+#pragma unroll
+  for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
+  uint32_t s = 0;
+#pragma unroll
+  for (int j = 0; j <= 2 * S; ++j) s += v[j];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j) s += v[j + 2 * S] - v[j - 1];
+    const uint32_t k = s >> q;
+    const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
+    o[j * g.WS] = ok(j) ? w : (uint16_t)0;
+  }
+}
+
+// Wb(y, x) = the weight of the pair {p, p + d} for the region's RW x RH samples p = (x0 - max(dx, 0) + x, y0 - dy + y); 0
+// where p or p + d lies outside the W x H grid (rule 2).  A task is 8 consecutive rows of a column (the last task of a
+// column starts at RH - 8 and overlaps its neighbour); lanes run along the columns.
+template <int S>
+G1S_DN_HD void dn_weights(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int RW,
+                          int RH, uint32_t mRW, int x0, int y0, int W, int H) {
+  const int ntasks = ((RH + 7) >> 3) * RW;
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int seg = (int)(((uint32_t)i * mRW) >> 16), x = i - seg * RW;
+    const int ys = imin(seg * 8, RH - 8);
+    const int px = x0 - imax(dx, 0) + x, py = y0 - dy + ys;
+    const bool col_ok = px >= 0 && px < W && px + dx >= 0 && px + dx < W;
+    dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
+                   [=](int j) { return col_ok && py + j >= 0 && py + j + dy < H; });  // (dy >= 0: the other two row bounds follow)
+  }
+}
+
+// Wb(y, x) = the weight of the pair {(t, p), (t + k, p + d)} for the tile's samples p = (x0 + x, y0 + y); 0 where p or p + d
+// lies outside the W x H grid (rule 6).  Tasks as in dn_weights, and no task overlaps another: 8 divides kTH.
+template <int S>
+G1S_DN_HD void dn_weights_t(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int x0,
+                            int y0, int W, int H) {
+  constexpr int ntasks = (kTH >> 3) * kTW;
+  for (int i = tid; i < ntasks; i += kThreads) {
+    const int x = i % kTW, ys = i / kTW * 8;
+    const int px = x0 + x, py = y0 + ys;
+    const bool col_ok = px < W && px + dx >= 0 && px + dx < W;
+    dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
+                   [=](int j) { return col_ok && py + j < H && py + j + dy >= 0 && py + j + dy < H; });
+  }
+}
+
+// the two pairs of offset d at each sample the thread owns: {p, p + d}, weight at p, and {p - d, p}, weight at p - d
+template <int NP>
+G1S_DN_HD void dn_accumulate(int tid, const TileGeom &g, int LP, const uint16_t *L, const uint16_t *Wb, int dx, int dy, uint32_t *aw,
+                             uint32_t *const (&au)[NP]) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w1 = Wb + (yb + dy) * g.WS + x + imax(dx, 0);
+  const uint16_t *w2 = Wb + yb * g.WS + x + imax(-dx, 0);
+  const uint16_t *u1 = L + (yb + dy + g.R) * g.LS + x + dx + g.R;
+  const uint16_t *u2 = L + (yb - dy + g.R) * g.LS + x - dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w1[4 * j * g.WS], b = w2[4 * j * g.WS];
+    aw[j] += a + b;
+#pragma unroll
+    for (int n = 0; n < NP; ++n) au[n][j] += a * u1[n * LP + 4 * j * g.LS] + b * u2[n * LP + 4 * j * g.LS];  // (the weights: read once)
+  }
+}
+
+// the pair {(t, p), (t + k, p + d)} at each sample the thread owns: weight at p, sample from N
+template <int NP>
+G1S_DN_HD void dn_accumulate_t(int tid, const TileGeom &g, int LP, const uint16_t *N, const uint16_t *Wb, int dx, int dy, uint32_t *aw,
+                               uint64_t *const (&au)[NP]) {
+  const int x = tid & 63, yb = tid >> 6;
+  const uint16_t *w = Wb + yb * g.WS + x;
+  const uint16_t *u = N + (yb + dy + g.R) * g.LS + x + dx + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const uint32_t a = w[4 * j * g.WS];
+    aw[j] += a;
+#pragma unroll
+    for (int n = 0; n < NP; ++n) au[n][j] += (uint64_t)a * u[n * LP + 4 * j * g.LS];
+  }
+}
+
+// d = 0: weight T[0] = 4096 on the sample itself
+template <int NP>
+G1S_DN_HD void dn_init(int tid, const TileGeom &g, int LP, const uint16_t *L, uint32_t *aw, uint32_t *const (&au)[NP]) {
+  const uint16_t *u = L + ((tid >> 6) + g.R) * g.LS + (tid & 63) + g.R;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    aw[j] = 4096u;
+#pragma unroll
+    for (int n = 0; n < NP; ++n) au[n][j] = 4096u * u[n * LP + 4 * j * g.LS];
+  }
+}
+
+// (n + (d >> 1)) / d for a quotient below 2^16 (a weighted mean of samples), d < 2^24: the float quotient is within one
+// of the integer one (its relative error is a few 2^-24), and one step either way makes it exact
+G1S_DN_HD uint32_t dn_rounded_mean(uint64_t n, uint32_t d) {
+  n += d >> 1;
+  uint32_t v = (uint32_t)((float)n * (1.0f / (float)d));
+  const int64_t r = (int64_t)n - (int64_t)((uint64_t)v * d);
+  if (r < 0) --v;
+  else if (r >= (int64_t)d) ++v;
+  return v;
+}
+
+// rules 4 and 7: one rounded division per sample; the numerator of rule 7 (Num = uint64_t) needs 64 bits
+template <int BPS, class Num>
+G1S_DN_HD void dn_store(int tid, uint8_t *out, uint32_t stride, int W, int H, int x0, int y0, const uint32_t *aw, const Num *au) {
+  const int x = x0 + (tid & 63);
+  if (x >= W) return;
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) {
+    const int y = y0 + (tid >> 6) + 4 * j;
+    if (y >= H) break;
+    const uint32_t v = sizeof(Num) == 8 ? dn_rounded_mean(au[j], aw[j]) : (uint32_t)((au[j] + (aw[j] >> 1)) / aw[j]);
+    uint8_t *row = out + (size_t)y * stride;
+    if (BPS == 2) reinterpret_cast<uint16_t *>(row)[x] = (uint16_t)v;
+    else row[x] = (uint8_t)v;
+  }
+}
+
+// ---- the two drivers: a source `src`, LDS laid out by `o` (tile_geom for PlaneSrc, joint_geom for JointSrc) ------------
+// the frame's own offsets (rules 1 - 3, 8 - 10) of one tile for thread `tid` of a workgroup whose barrier is `sync`: the
+// sample arrays and T staged, the sums of rule 4 / 11 in aw and au
+template <int S, int BPS, class Src, class Layout, class Sync>
+G1S_DN_HD void dn_spatial(int tid, const TileGeom &g, const Layout &o, uint8_t *lds, const uint16_t *table, int q, const Src &src, int x0, int y0,
+                          Sync sync, uint32_t *aw, uint32_t *const (&au)[Src::NP]) {
+  const int LP = dn_lp(o);
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + o.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + o.offL), *Wb = reinterpret_cast<uint16_t *>(lds + o.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + o.offT);
+  src.template stage<BPS>(tid, g, LP, L, x0, y0);
   for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
   sync();
-  dn_init(tid, g, L, aw, aub);
-  dn_init(tid, g, L + jg.LP, aw, aur);
+  dn_init<Src::NP>(tid, g, LP, L, aw, au);
   for (int dy = 0; dy <= g.A; ++dy) {
     const int NR = kTH + dy + 2 * S, RH = kTH + dy;
     const uint32_t mNR = magic(NR);
     for (int dx = dy ? -g.A : 1; dx <= g.A; ++dx) {
       const int RW = kTW + (dx < 0 ? -dx : dx);
-      dn_hsum_j<S>(tid, g, jg.LP, L, Hb, dx, dy, RW, NR, mNR);
+      dn_hsum<S, Src::NA>(tid, g, LP, L, Hb, dx, dy, RW, NR, mNR);
       sync();
-      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, s.cw, s.ch);
+      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, src.grid_w(), src.grid_h());
       sync();
-      dn_accumulate_j(tid, g, jg.LP, L, Wb, dx, dy, aw, aub, aur);
+      dn_accumulate<Src::NP>(tid, g, LP, L, Wb, dx, dy, aw, au);
     }
   }
 }
 
-// one chroma tile of the joint filter, start to end
+// after dn_spatial, the 2 D frames around the frame in hand (rules 5 - 7, 11t): nb(k) is the source of the k-th, absent
+// where the clip has no such frame -- the same for every thread of the workgroup.  The order of the neighbours does not
+// show in the result: the sums are exact.
+template <int S, int BPS, int NP, class Layout, class Nb, class Sync>
+G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t *lds, int q, Nb nb, int nnb, int x0, int y0, Sync sync, uint32_t *aw,
+                           uint64_t *const (&au)[NP]) {
+  const int LP = dn_lp(o);
+  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + o.offH);
+  uint16_t *L = reinterpret_cast<uint16_t *>(lds + o.offL), *Wb = reinterpret_cast<uint16_t *>(lds + o.offW),
+           *T = reinterpret_cast<uint16_t *>(lds + o.offT), *N = reinterpret_cast<uint16_t *>(lds + o.offN);
+  for (int k = 0; k < nnb; ++k) {
+    const auto n = nb(k);
+    static_assert(decltype(n)::NP == NP, "a neighbour has the frame's planes");
+    if (!n.present()) continue;
+    sync();  // the last dn_accumulate_t has read N
+    n.template stage<BPS>(tid, g, LP, N, x0, y0);
+    sync();
+    for (int dy = -g.A; dy <= g.A; ++dy)
+      for (int dx = -g.A; dx <= g.A; ++dx) {
+        dn_hsum_t<S, decltype(n)::NA>(tid, g, LP, L, N, Hb, dx, dy);
+        sync();
+        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h());
+        sync();
+        dn_accumulate_t<NP>(tid, g, LP, N, Wb, dx, dy, aw, au);
+      }
+  }
+}
+
+// the four tile functions, start to end (what kd_nlm, kd_nlm_t, kd_nlm_j and kd_nlm_jt call); this one: one plane on its own
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
+                       uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
+  uint32_t aw[kSPT], au[kSPT];
+  dn_spatial<S, BPS>(tid, g, g, lds, table, q, PlaneSrc{in, in_stride, W, H}, x0, y0, sync, aw, {au});
+  dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+// the temporal filter: `nb` / `nb_stride` are the same plane of the 2 D frames around the frame in hand, a null pointer
+// where the clip has no such frame (rule 5)
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile_t(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride,
+                         const uint8_t *const *nb, const uint32_t *nb_stride, int nnb, uint8_t *out, uint32_t out_stride, int W, int H, int x0, int y0,
+                         Sync sync) {
+  uint32_t aw[kSPT], au32[kSPT];
+  dn_spatial<S, BPS>(tid, g, g, lds, table, q, PlaneSrc{in, in_stride, W, H}, x0, y0, sync, aw, {au32});  // (fits 32 bits, as in dn_tile)
+  uint64_t au[kSPT];
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) au[j] = au32[j];
+  dn_temporal<S, BPS>(tid, g, g, lds, q, [=](int k) { return PlaneSrc{nb[k], nb_stride[k], W, H}; }, nnb, x0, y0, sync, aw, {au});
+  dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+// one chroma tile of the joint filter
 template <int S, int BPS, class Sync>
 G1S_DN_HD void dn_tile_j(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
                          const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0,
                          Sync sync) {
   uint32_t aw[kSPT], aub[kSPT], aur[kSPT];
-  dn_tile_j_spatial<S, BPS>(tid, g, jg, lds, table, q, p, s, x0, y0, sync, aw, aub, aur);
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub, aur});
   dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
   dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }
@@ -566,31 +466,14 @@ template <int S, int BPS, class Nb, class Sync>
 G1S_DN_HD void dn_tile_jt(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
                           Nb nb, int nnb, const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr,
                           uint32_t out_cr_stride, int x0, int y0, Sync sync) {
-  uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + jg.offH);
-  uint16_t *L = reinterpret_cast<uint16_t *>(lds + jg.offL), *Wb = reinterpret_cast<uint16_t *>(lds + jg.offW),
-           *T = reinterpret_cast<uint16_t *>(lds + jg.offT), *N = reinterpret_cast<uint16_t *>(lds + jg.offN);
   uint32_t aw[kSPT], aub32[kSPT], aur32[kSPT];
-  dn_tile_j_spatial<S, BPS>(tid, g, jg, lds, table, q, p, s, x0, y0, sync, aw, aub32, aur32);
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32});
   uint64_t aub[kSPT], aur[kSPT];
 #pragma unroll
   for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
-  for (int k = 0; k < nnb; ++k) {
-    const JointPlanes n = nb(k);
-    if (!n.luma) continue;
-    sync();  // the last dn_accumulate_jt has read N
-    dn_stage_j<BPS>(tid, g, jg.LP, N, n, s, x0, y0);
-    sync();
-    for (int dy = -g.A; dy <= g.A; ++dy)
-      for (int dx = -g.A; dx <= g.A; ++dx) {
-        dn_hsum_jt<S>(tid, g, jg.LP, L, N, Hb, dx, dy);
-        sync();
-        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, s.cw, s.ch);
-        sync();
-        dn_accumulate_jt(tid, g, jg.LP, N, Wb, dx, dy, aw, aub, aur);
-      }
-  }
-  dn_store_t<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
-  dn_store_t<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
+  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur});
+  dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
+  dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }
 
 }  // namespace g1s_dn

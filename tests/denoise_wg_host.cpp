@@ -1,15 +1,19 @@
 // denoise_wg_host.cpp -- the four tile functions of grav1synth_amd/csrc/denoise_tile.hip.h (dn_tile, dn_tile_t, dn_tile_j,
 // dn_tile_jt: what kd_nlm, kd_nlm_t, kd_nlm_j and kd_nlm_jt call) on the host as they stand, with a real barrier for `sync`
 // (tests/wg_host.h): 256 logical threads a tile, run one at a time between two barriers in an order the caller names, the
-// LDS buffer filled with a pattern before every tile.  tests/test_denoise_schedule_cpu.py builds it with the address and
-// undefined-behaviour sanitizers and compares its output with the numpy references; what it is there for is the
-// composition -- the order of the phases, the loops' ranges and where every barrier stands -- which the two neighbours
-// (denoise_tile_host.cpp, denoise_joint_tile_host.cpp) restate by hand and so cannot check.
+// LDS buffer filled with a pattern before every tile.  tests/denoise_wg.py builds it with the address and undefined-behaviour
+// sanitizers; tests/test_denoise_schedule_cpu.py compares its output with the numpy references under every schedule and fill
+// -- the composition: the order of the phases, the loops' ranges and where every barrier stands -- and
+// tests/test_denoise_temporal_cpu.py and tests/test_denoise_joint_cpu.py over their own content, threads ascending.
 //
 //   denoise_wg_host KIND BPS S A q W H XDEC YDEC NNB TABLE IN OUT SCHEDULE SEED FILL SKIP
 //
-// KIND      tile | tile_t: one plane, IN and OUT as denoise_tile_host.cpp has them (XDEC, YDEC ignored; tile: NNB = 0);
-//           tile_j | tile_jt: a frame's chroma, IN and OUT as denoise_joint_tile_host.cpp has them (tile_j: NNB = 0).
+// KIND      tile | tile_t: one plane, W x H (XDEC, YDEC ignored; tile: NNB = 0);
+//           tile_j | tile_jt: a frame's chroma, (W + XDEC >> XDEC) x (H + YDEC >> YDEC), W x H the luma plane (tile_j: NNB = 0).
+// TABLE     1024 u16.
+// IN        the frame -- the plane, or Y, Cb, Cr -- in samples of BPS bytes, then NNB neighbours, each a byte that says whether
+//           it takes part (0: null pointers) and its plane(s).
+// OUT       the plane, or Cb then Cr: every tile.
 // SCHEDULE  ascending | descending | waves-reversed | random | stragglers, with SEED (wg_host.h).
 // FILL      zero | ones | random: the bytes every tile finds in LDS (random from SEED).
 // SKIP      -1, or k: the k-th sync() call (from 0) of every thread of every tile is no barrier.

@@ -1,13 +1,10 @@
 """Luma-guided joint chroma (`denoise`, rules 8 - 11t) without a device: the numpy restatement against the rules written out,
-the table of rule 10, the joint tile of denoise_tile.hip.h run thread by thread on the host, what the filter is for, the
-refusals and the commands' wiring."""
+the table of rule 10, the joint tiles of denoise_tile.hip.h (dn_tile_j and dn_tile_jt as they stand) run on a host workgroup,
+what the filter is for, the refusals and the commands' wiring."""
 from __future__ import annotations
 
 import ctypes as C
 import inspect
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +13,8 @@ from grav1synth_amd import _lib
 from tests import denoise_joint_ref as J
 from tests import denoise_ref as R
 from tests import denoise_temporal_ref as TR
+from tests import denoise_wg as WG
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUB = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
 
 
@@ -178,30 +175,16 @@ def test_refusals_of_the_table_and_the_constructor_need_no_device():
 # ---------------------------------------------------------------------------------------------- the tile on the host
 @pytest.fixture(scope="module")
 def tile_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
+    if WG.compiler() is None:
         pytest.skip("no C++ compiler")
-    exe = tmp_path_factory.mktemp("jtile") / "denoise_joint_tile_host"
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
-           os.path.join(ROOT, "tests", "denoise_joint_tile_host.cpp")]
-    # (the sanitizer's runtime inside the program where the compiler can do that: it then starts under any preloaded library)
-    if subprocess.call(cmd + ["-static-libasan"], stderr=subprocess.DEVNULL) != 0:
-        subprocess.check_call(cmd)
+    exe = tmp_path_factory.mktemp("jtile") / "denoise_wg_host"
+    WG.build(exe)
 
     def run(frames, present, xdec, ydec, A, S, T, q):
         """The frame frames[0] and its neighbours frames[1:] (present[k]: takes part) through every tile: (out_Cb, out_Cr)."""
-        d = exe.parent
-        bps = frames[0][0].dtype.itemsize
-        h, w = frames[0][0].shape
-        ch, cw = frames[0][1].shape
-        (d / "t.bin").write_bytes(np.asarray(T, np.uint16).tobytes())
-        blob = b"".join(p.tobytes() for p in frames[0]) + b"".join(bytes([int(ok)]) + b"".join(p.tobytes() for p in f) for ok, f in zip(present, frames[1:]))
-        (d / "in.bin").write_bytes(blob)
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        p = subprocess.run([str(exe), str(bps), str(S), str(A), str(q), str(w), str(h), str(xdec), str(ydec), str(len(frames) - 1), str(d / "t.bin"),
-                            str(d / "in.bin"), str(d / "out.bin")], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-3000:]
-        out = np.frombuffer((d / "out.bin").read_bytes(), frames[0][1].dtype).reshape(2, ch, cw)
+        kind = "tile_jt" if len(frames) > 1 else "tile_j"
+        out = WG.run_tiles(exe, kind, frames, present, xdec, ydec, A, S, T, q)
+        out = np.frombuffer(out, frames[0][1].dtype).reshape((2,) + frames[0][1].shape)
         return out[0], out[1]
 
     return run

@@ -1,13 +1,10 @@
 """The temporal radius of `denoise` without a device: the numpy restatement of rules 5 - 7 against the rules written out,
-its properties, the temporal tile of denoise_tile.hip.h run thread by thread on the host, the refusals and the commands'
-wiring."""
+its properties, the temporal tile of denoise_tile.hip.h (dn_tile_t as it stands) run on a host workgroup, the refusals and
+the commands' wiring."""
 from __future__ import annotations
 
 import ctypes as C
 import inspect
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +12,8 @@ import pytest
 from grav1synth_amd import _lib
 from tests import denoise_ref as R
 from tests import denoise_temporal_ref as TR
+from tests import denoise_wg as WG
 from tests.test_denoise_cpu import plane
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def clip(n, w, h, bd, seed=0, shift=(2, 1)):
@@ -152,29 +148,16 @@ def test_python_refuses_a_radius_of_4_without_a_device():
 # ---------------------------------------------------------------------------------------------- the tile on the host
 @pytest.fixture(scope="module")
 def tile_host(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    if cxx is None:
+    if WG.compiler() is None:
         pytest.skip("no C++ compiler")
-    exe = tmp_path_factory.mktemp("tile") / "denoise_tile_host"
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
-           os.path.join(ROOT, "tests", "denoise_tile_host.cpp")]
-    # (the sanitizer's runtime inside the program where the compiler can do that: it then starts under any preloaded library)
-    if subprocess.call(cmd + ["-static-libasan"], stderr=subprocess.DEVNULL) != 0:
-        subprocess.check_call(cmd)
+    exe = tmp_path_factory.mktemp("tile") / "denoise_wg_host"
+    WG.build(exe)
 
     def run(planes, present, A, S, T, q):
         """The frame planes[0] and its neighbours planes[1:] (present[k]: takes part) through every tile of the plane."""
-        d = exe.parent
-        bps = planes[0].dtype.itemsize
-        h, w = planes[0].shape
-        (d / "t.bin").write_bytes(np.asarray(T, np.uint16).tobytes())
-        blob = planes[0].tobytes() + b"".join(bytes([int(ok)]) + p.tobytes() for ok, p in zip(present, planes[1:]))
-        (d / "in.bin").write_bytes(blob)
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        p = subprocess.run([str(exe), str(bps), str(S), str(A), str(q), str(w), str(h), str(len(planes) - 1), str(d / "t.bin"), str(d / "in.bin"),
-                            str(d / "out.bin")], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-3000:]
-        return np.frombuffer((d / "out.bin").read_bytes(), planes[0].dtype).reshape(h, w)
+        kind = "tile_t" if len(planes) > 1 else "tile"
+        out = WG.run_tiles(exe, kind, [[p] for p in planes], present, 0, 0, A, S, T, q)
+        return np.frombuffer(out, planes[0].dtype).reshape(planes[0].shape)
 
     return run
 
