@@ -69,18 +69,31 @@ def make_frames(kind: str, width: int, height: int, bit_depth: int, xdec: int, y
     """(source_planes, denoised_planes) of frame `frame`: three planes each, chroma decimated by (xdec, ydec)."""
     if kind not in KINDS:
         raise ValueError(f"unknown content kind {kind!r}")
-    w, h, up, maxv = width, height, bit_depth - 8, (1 << bit_depth) - 1
-    dt = np.uint8 if bit_depth == 8 else np.uint16
+    w, h = width, height
     ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
-    base8 = 24 + (xs * 200) // w + (ys * 20) // h
-    if kind == "clamped":
-        base8 = _thirds(base8, xs, w)
-    gain = 3 + (base8 >> 6)  # Y: rising, 3 .. 6
     tex = np.zeros((h, w), bool)
     if kind in ("distinct", "damaged", "clamped"):
         tex = (xs >= ((5 * w // 8) & ~31) + 12) & (ys >= ((h // 3) & ~31) + 20)
     elif kind == "busy":
         tex = ~((xs < min(6 * 32, (w // 2) & ~31) + 12) & (ys < min(4 * 32, (h // 2) & ~31) + 20))
+    src, den = textured_frames(tex, width, height, bit_depth, xdec, ydec, frame, seed, thirds=kind == "clamped")
+    if kind == "damaged":
+        for c in range(3):
+            _damage(np.random.default_rng([seed, frame, 8 + c]), src[c], den[c], bit_depth - 8)
+    return src, den
+
+
+def textured_frames(tex: np.ndarray, width: int, height: int, bit_depth: int, xdec: int, ydec: int, frame: int, seed: int = 1,
+                    thirds: bool = False) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+    """The frame pair every kind is made of: the ramps, gain laws, taps and luma-into-chroma weights above, and the checker texture
+    on the luma samples where `tex` (bool, height x width) is set.  tests/mask_content.py places the texture block by block."""
+    w, h, up, maxv = width, height, bit_depth - 8, (1 << bit_depth) - 1
+    dt = np.uint8 if bit_depth == 8 else np.uint16
+    ys, xs = np.arange(h, dtype=np.int64)[:, None], np.arange(w, dtype=np.int64)[None, :]
+    base8 = 24 + (xs * 200) // w + (ys * 20) // h
+    if thirds:
+        base8 = _thirds(base8, xs, w)
+    gain = 3 + (base8 >> 6)  # Y: rising, 3 .. 6
     checker = ((((xs >> 3) + (ys >> 3)) & 1) * 48 - 24) + (xs & 1) * 8
     den8 = np.clip(base8 + tex * checker, 0, 255)
     d = den8 << up
@@ -92,7 +105,7 @@ def make_frames(kind: str, width: int, height: int, bit_depth: int, xdec: int, y
     cys, cxs = np.arange(ch, dtype=np.int64)[:, None], np.arange(cw, dtype=np.int64)[None, :]
     for c in (1, 2):
         cb8 = (64 + (cxs * 128) // cw + 0 * cys) if c == 1 else (200 - (cys * 128) // ch + 0 * cxs)
-        if kind == "clamped":
+        if thirds:
             cb8 = _thirds(cb8, cxs, cw)
         g = (2 + (cb8 >> 6)) if c == 1 else 2 * (6 - (cb8 >> 6))  # Cb: rising slowly; Cr: falling
         lw = (lco >> 1) if c == 1 else -(lco >> 2)
@@ -102,7 +115,4 @@ def make_frames(kind: str, width: int, height: int, bit_depth: int, xdec: int, y
         den.append(dc)
     src = [np.ascontiguousarray(p.astype(dt)) for p in src]
     den = [np.ascontiguousarray(p.astype(dt)) for p in den]
-    if kind == "damaged":
-        for c in range(3):
-            _damage(np.random.default_rng([seed, frame, 8 + c]), src[c], den[c], up)
     return src, den
