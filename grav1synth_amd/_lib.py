@@ -171,6 +171,16 @@ class G1SMeasureRecord(C.Structure):
     ]
 
 
+class G1SMeasureTRecord(C.Structure):
+    _fields_ = [
+        ("n", (C.c_uint64 * 32) * 3),
+        ("x", (C.c_int64 * 32) * 3),
+        ("u", (C.c_uint64 * 32) * 3),
+        ("v", (C.c_uint64 * 32) * 3),
+        ("c", (C.c_int64 * 25) * 3),
+    ]
+
+
 class G1SSurface(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -331,6 +341,16 @@ SYMBOLS = [
                                           C.c_size_t]),
     ("g1s_check_y4m_files", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts), C.POINTER(G1SGrainOpts),
                                         C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_measure_new_temporal", C.c_void_p, [C.c_uint32, C.POINTER(G1SMeasureOpts)]),
+    ("g1s_measure_cut", C.c_int, [C.c_void_p]),
+    ("g1s_measure_finish_temporal", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_measure_sum_temporal", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_format_measure_temporal", C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_uint32] * 6 + [C.c_char_p, C.c_size_t]),
+    ("g1s_measure_temporal_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_measure_y4m_files_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts), C.POINTER(C.c_int),
+                                                   C.c_char_p, C.c_size_t]),
+    ("g1s_check_y4m_files_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts),
+                                                 C.POINTER(G1SGrainOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     ("g1s_surface_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SSurfaceOpts)]),
     ("g1s_surface_unpack", C.c_int, [C.c_void_p, C.POINTER(G1SSurface), C.POINTER(G1SFrame)]),
     ("g1s_surface_pack", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SSurface)]),

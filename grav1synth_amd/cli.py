@@ -26,6 +26,7 @@ SAME_AS_OUTPUT = ("Input and output paths are the same. This is probably a typo,
 SAME_INPUTS = ("Source and denoised paths are the same. This is probably a typo, because this would always compute an "
                "empty diff. Exiting.")
 NOT_OVERWRITING = "Not overwriting existing file. Exiting."
+SAME_OUTPUTS = "--temporal and -o name the same file: the two reports would overwrite each other. Exiting."
 NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
 BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
 DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser runs on the source as it is read). Exiting."
@@ -180,6 +181,8 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("-o", "--output", required=True, help="The path to the output profile.")
     m.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
     m.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    m.add_argument("--temporal", metavar="PATH", default=None,
+                   help="also write the temporal profile: the correlation of the residual with the residual of the frame before")
     c = sub.add_parser("check", help="Says how well a grain table fits: the profile of SOURCE - DENOISED beside the profile of the "
                                      "table's grain rendered onto DENOISED (y4m inputs).  Reports; passes no verdict.")
     c.add_argument("source", help="The untouched source file.")
@@ -190,6 +193,8 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
     c.add_argument("--clip-restricted", action="store_true",
                    help="render with the output clipped to the restricted (studio) range, as `render --clip-restricted`")
+    c.add_argument("--temporal", metavar="PATH", default=None,
+                   help="also write the two-column temporal profile: frame-to-frame correlation of both residuals")
     return ap
 
 
@@ -315,9 +320,23 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     return frames
 
 
-def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm) -> int:
+def _temporal_refused(inputs, output: str, temporal: Optional[str]) -> bool:
+    """--temporal PATH is an output like -o's: not an input, and not -o's own path."""
+    if temporal is None:
+        return False
+    if any(_same_path(p, temporal) for p in inputs):
+        log.error(SAME_AS_OUTPUT)
+        return True
+    if _same_path(output, temporal):
+        log.error(SAME_OUTPUTS)
+        return True
+    return False
+
+
+def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
+                    temporal: Optional[str] = None) -> int:
     """The refusals of `diff` for two inputs and an output, then the frame pairs until the shorter file ends and the
-    profile.  Returns the frame count, -1 after a refusal."""
+    profile (with `temporal`, the temporal profile beside it).  Returns the frame count, -1 after a refusal."""
     from .measure import measure_y4m_files
 
     if _same_path(noisy, output) or _same_path(clean, output):
@@ -326,16 +345,21 @@ def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False
     if _same_path(noisy, clean):
         log.error(SAME_INPUTS)
         return -1
-    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
-        log.warning(NOT_OVERWRITING)
+    if _temporal_refused((noisy, clean), output, temporal):
         return -1
-    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device)
+    for path in (output, temporal):
+        if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
+            log.warning(NOT_OVERWRITING)
+            return -1
+    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device, temporal_output=temporal)
     log.info("Done, wrote output file to %s", output)
+    if temporal is not None:
+        log.info("Done, wrote temporal profile to %s", temporal)
     return frames
 
 
 def check_command(source: str, denoised: str, table: str, output: str, overwrite: bool = False, device: int = -1,
-                  clip_restricted: bool = False, confirm=_confirm) -> int:
+                  clip_restricted: bool = False, confirm=_confirm, temporal: Optional[str] = None) -> int:
     """The same refusals (the table is an input too), then the two profiles side by side.  No verdict, no threshold.
     Returns the frame count, -1 after a refusal."""
     from .measure import check_y4m_files
@@ -346,11 +370,17 @@ def check_command(source: str, denoised: str, table: str, output: str, overwrite
     if _same_path(source, denoised):
         log.error(SAME_INPUTS)
         return -1
-    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
-        log.warning(NOT_OVERWRITING)
+    if _temporal_refused((source, denoised, table), output, temporal):
         return -1
-    frames, _unequal = check_y4m_files(source, denoised, table, output, device=device, clip_to_restricted_range=clip_restricted)
+    for path in (output, temporal):
+        if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
+            log.warning(NOT_OVERWRITING)
+            return -1
+    frames, _unequal = check_y4m_files(source, denoised, table, output, device=device, clip_to_restricted_range=clip_restricted,
+                                       temporal_output=temporal)
     log.info("Done, wrote output file to %s", output)
+    if temporal is not None:
+        log.info("Done, wrote temporal profile to %s", temporal)
     return frames
 
 
@@ -396,13 +426,14 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
     elif args.command == "measure":
         try:
-            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device)
+            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device, temporal=args.temporal)
         except Exception as e:
             log.error("%s", e)
             return 1
     elif args.command == "check":
         try:
-            check_command(args.source, args.denoised, args.grain, args.output, args.overwrite, args.device, args.clip_restricted)
+            check_command(args.source, args.denoised, args.grain, args.output, args.overwrite, args.device, args.clip_restricted,
+                          temporal=args.temporal)
         except Exception as e:
             log.error("%s", e)
             return 1

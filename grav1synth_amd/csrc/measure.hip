@@ -11,6 +11,7 @@
 //                    (and the clean luma a chroma sample is binned by).  The workgroup's partial record goes out with
 //                    plain stores.
 //   km_tail          a workgroup per (plane, frame pair) sums the partial records into the pair's record.
+// A temporal meter (rules 7 - 11) runs km_measure_t and km_tail_t behind them: they stand below km_tail with their own notes.
 //
 // The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
 //   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
@@ -215,6 +216,171 @@ __global__ __launch_bounds__(128 * kTailGroups) void km_tail(TailParams p) {
   }
 }
 
+// ---- the temporal record (rules 7 - 11): the residual of pair t against the residual of pair t - 1 ----
+//   km_measure_t<BPS>  a workgroup per (tile, plane of the class, temporal job), km_measure's tile, waves and plane classes.
+//                      LDS: d_t of the tile as int16 without a halo; d_{t-1} as int16 with a halo of 2 on all four sides
+//                      (zeros outside the plane: a skipped product is a product with 0); the tile's bins as bytes, from
+//                      pair t's clean frame; the waves' accumulators.  A wave walks its 32 rows, a lane a column, with the
+//                      5 x 5 window of d_{t-1} in registers: 5 LDS reads of d_{t-1} and 25 multiply-adds a sample.
+//   km_tail_t          km_tail for the partial records of km_measure_t.
+// The 32-bit sums follow km_measure's schedule: a lane's 25 lag sums and its bin sums (n, x, u, v) take one product a row
+// for the wave's 32 rows at the most (below 2^29 in size) and go on in 64 bits through wave_sum_wide, which carries the
+// signed x and c as it carries km_measure's lag sums.
+constexpr int kTHalo = 2, kTWin = 2 * kTHalo + 1;
+constexpr int kPW = kTW + 2 * kTHalo, kPH = kTH + 2 * kTHalo;  // the LDS tile of d_{t-1}
+constexpr int kTLags = kTWin * kTWin;
+constexpr int kTEntries = 4 * kBins + kTLags;  // a partial temporal record: n[32], x[32], u[32], v[32], c[25]
+constexpr int kTTailWidth = 256, kTTailGroups = 2;
+static_assert(kRowsPerWave <= 127, "a 32-bit sum of km_measure_t holds 127 products of 12-bit residuals, one a row");
+static_assert(kTLags == 25 && kTEntries <= kTTailWidth, "g1s_measure_trecord_t has 25 offsets; km_tail_t gives an entry a thread");
+static_assert(sizeof(g1s_measure_trecord_t) == 8 * 3 * kTEntries, "km_tail_t writes the record as 64-bit words");
+
+struct TemporalJob {
+  MeasureJob cur, prev;  // pair t and pair t - 1 of the run
+};
+
+struct TemporalParams {
+  const TemporalJob *jobs;
+  unsigned long long *partials;  // [job][tiles_frame][kTEntries]
+  int pw, ph, tiles_x;
+  int plane0;
+  int W, xdec, ydec, shift;
+  uint32_t tiles_frame, tile_base, tiles_plane;
+};
+
+template <int BPS>
+__global__ __launch_bounds__(kThreads) void km_measure_t(TemporalParams p) {
+  __shared__ int16_t s_d[kTH * kTW];
+  __shared__ int16_t s_p[kPH * kPW];
+  __shared__ uint8_t s_bin[kTH * kTW];
+  __shared__ unsigned long long s_acc[kWaves][kTEntries];  // (two's complement, as km_measure's)
+  const TemporalJob &job = p.jobs[blockIdx.z];
+  const int c = p.plane0 + (int)blockIdx.y;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const int x0 = tx * kTW, y0 = ty * kTH;
+  const uint8_t *pa = job.cur.a[c], *pb = job.cur.b[c], *py = job.cur.b[0], *qa = job.prev.a[c], *qb = job.prev.b[c];
+  const uint32_t sa = job.cur.a_stride[c], sb = job.cur.b_stride[c], sy = job.cur.b_stride[0];
+  const uint32_t ta = job.prev.a_stride[c], tb = job.prev.b_stride[c];
+
+  for (int i = tid; i < kWaves * kTEntries; i += kThreads) (&s_acc[0][0])[i] = 0;
+  // d_{t-1} of the tile with its halo; for the tile's own samples d_t and the bin beside it
+  for (int i = tid; i < kPH * kPW; i += kThreads) {
+    const int ly = i / kPW, lx = i - ly * kPW;
+    const int x = x0 + lx - kTHalo, y = y0 + ly - kTHalo;
+    const bool inside = x >= 0 && x < p.pw && y >= 0 && y < p.ph;
+    const bool own = lx >= kTHalo && lx < kTHalo + kTW && ly >= kTHalo && ly < kTHalo + kTH;
+    int d = 0, e = 0, bin = kNoBin;
+    if (inside) {
+      e = sample<BPS>(qa, ta, x, y) - sample<BPS>(qb, tb, x, y);
+      if (own) {
+        const int b = sample<BPS>(pb, sb, x, y);
+        d = sample<BPS>(pa, sa, x, y) - b;
+        int I = b;
+        if (c) {  // averageLuma of pair t's clean frame
+          const int xs = x << p.xdec, ys = y << p.ydec;
+          I = sample<BPS>(py, sy, xs, ys);
+          if (p.xdec) I = (I + sample<BPS>(py, sy, min(xs + 1, p.W - 1), ys) + 1) >> 1;
+        }
+        bin = min(I >> p.shift, kBins - 1);
+      }
+    }
+    s_p[i] = (int16_t)e;
+    if (own) {
+      const int at = (ly - kTHalo) * kTW + (lx - kTHalo);
+      s_d[at] = (int16_t)d;
+      s_bin[at] = (uint8_t)bin;
+    }
+  }
+  __syncthreads();
+
+  const int row0 = wave * kRowsPerWave, rows = min(kRowsPerWave, p.ph - (y0 + row0));
+  if (rows > 0) {
+    int acc[kTLags];
+#pragma unroll
+    for (int i = 0; i < kTLags; ++i) acc[i] = 0;
+    // the window: rows y - 2 .. y + 2 of d_{t-1}, columns x - 2 .. x + 2 (LDS row ly = tile row + 2 + dy, column lx = lane + 2 + dx)
+    int w[kTWin][kTWin];
+#pragma unroll
+    for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) w[q + 1][k] = s_p[(row0 + q) * kPW + lane + k];
+    int cur = -1, bn = 0, bx = 0, bu = 0, bv = 0;  // the bin the lane's column is in and its sums so far (cur < 0: none)
+    unsigned long long *mine = s_acc[wave];
+    auto hand_on = [&](bool go) __attribute__((always_inline)) {
+      unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
+      while (todo) {
+        const int b = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(todo));
+        const bool m = go && cur == b;
+        todo &= ~__builtin_amdgcn_ballot_w64(m);
+        const int n = wave_sum(m ? bn : 0);
+        const long long x = wave_sum_wide(m ? bx : 0), u = wave_sum_wide(m ? bu : 0), v = wave_sum_wide(m ? bv : 0);
+        if (lane == 0) {
+          mine[b] += (unsigned long long)(long long)n;
+          mine[kBins + b] += (unsigned long long)x;
+          mine[2 * kBins + b] += (unsigned long long)u;
+          mine[3 * kBins + b] += (unsigned long long)v;
+        }
+        if (m) cur = -1, bn = bx = bu = bv = 0;
+      }
+    };
+    for (int r = 0; r < rows; ++r) {
+#pragma unroll
+      for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+        for (int k = 0; k < kTWin; ++k) w[q][k] = w[q + 1][k];
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) w[kTWin - 1][k] = s_p[(row0 + r + kTWin - 1) * kPW + lane + k];
+      const int d = s_d[(row0 + r) * kTW + lane];
+#pragma unroll
+      for (int q = 0; q < kTWin; ++q)
+#pragma unroll
+        for (int k = 0; k < kTWin; ++k) acc[q * kTWin + k] += __mul24(d, w[q][k]);
+      const int e = w[kTHalo][kTHalo];
+      const int k = s_bin[(row0 + r) * kTW + lane];
+      const bool change = cur >= 0 && k != cur;
+      if (__builtin_amdgcn_ballot_w64(change)) hand_on(change);
+      if (k != kNoBin) cur = k, bn += 1, bx += __mul24(d, e), bu += __mul24(d, d), bv += __mul24(e, e);
+    }
+    hand_on(cur >= 0);
+#pragma unroll
+    for (int i = 0; i < kTLags; ++i) {
+      const long long t = wave_sum_wide(acc[i]);
+      if (lane == 0) mine[4 * kBins + i] = (unsigned long long)t;
+    }
+  }
+  __syncthreads();
+  if (tid < kTEntries) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) t += s_acc[v][tid];
+    const size_t at = (size_t)blockIdx.z * p.tiles_frame + p.tile_base + (size_t)blockIdx.y * p.tiles_plane + blockIdx.x;
+    p.partials[at * kTEntries + tid] = t;
+  }
+}
+
+// the job's temporal record from its workgroups' partial records: grid (plane, job)
+__global__ __launch_bounds__(kTTailWidth * kTTailGroups) void km_tail_t(TailParams p) {
+  __shared__ unsigned long long s_sum[kTTailGroups][kTTailWidth];
+  const int c = (int)blockIdx.x, i = (int)threadIdx.x % kTTailWidth, g = (int)threadIdx.x / kTTailWidth;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kTEntries;
+  unsigned long long t = 0;
+  if (i < kTEntries)
+    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += kTTailGroups) t += src[(size_t)k * kTEntries + i];
+  s_sum[g][i] = t;
+  __syncthreads();
+  if (g == 0 && i < kTEntries) {
+    for (int v = 1; v < kTTailGroups; ++v) t += s_sum[v][i];
+    // g1s_measure_trecord_t as 64-bit words: n[3][32], x[3][32], u[3][32], v[3][32], c[3][25]
+    unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_trecord_t) / 8);
+    const int field = i < 4 * kBins ? i / kBins : 4, k = i - field * kBins;
+    rec[field < 4 ? field * 3 * kBins + c * kBins + k : 12 * kBins + c * kTLags + k] = t;
+  }
+}
+
+// rule 8's offsets: raster order, (0, 0) is index 12
+void temporal_offset(int i, int *dx, int *dy) { *dy = i / kTWin - kTHalo, *dx = i % kTWin - kTHalo; }
+
 // rule 4's offsets in the table's coefficient order, (0, 0) last
 void lag_offset(int i, int *dx, int *dy) {
   if (i == 24) *dx = 0, *dy = 0;
@@ -238,9 +404,27 @@ struct g1s_measure : BatchedOp {
   std::vector<g1s_measure_record_t> records;  // since the last hand-over
   double ms_kernel = 0;
   uint64_t frames_timed = 0;
+  // a temporal meter: the run's last pair as the kernels read it (its planes: the caller's, or a slot of the input rings,
+  // which then have batch + 1 slots filled round-robin), the batch's temporal jobs, the temporal records
+  bool temporal = false, have_prev = false;
+  MeasureJob prev{};
+  bool prev_staged[2] = {false, false};  // (are the planes of prev.a / prev.b the meter's own: a ring's or d_keep's?)
+  uint32_t ring_at = 0;
+  DevBuf<uint8_t> d_keep[2];  // a frame each: the caller's device planes of the run's last pair, kept over a hand-over
+  Event ev_t[2];
+  std::vector<TemporalJob> tjobs;
+  ParamSets<TemporalJob> p_tjobs;
+  DevBuf<unsigned long long> d_tpartials;
+  size_t tpartials_cap = 0;
+  DevBuf<g1s_measure_trecord_t> d_trecs;
+  PinnedBuf<g1s_measure_trecord_t> h_trecs;
+  std::vector<g1s_measure_trecord_t> trecords;  // since the last hand-over
+  double ms_tkernel = 0;
+  uint64_t pairs_timed = 0;
 
   int set_geometry(const g1s_frame_t &f);
   int flush();
+  int keep_prev();
 };
 
 int g1s_measure::set_geometry(const g1s_frame_t &f) {
@@ -257,6 +441,14 @@ int g1s_measure::set_geometry(const g1s_frame_t &f) {
     G1S_OP_TRY(hipMalloc((void **)&d_partials.p, need * sizeof(unsigned long long)));
     partials_cap = need;
   }
+  const size_t tneed = temporal ? (size_t)tiles_frame * kTEntries * batch : 0;
+  if (tneed > tpartials_cap) {
+    d_tpartials = DevBuf<unsigned long long>();
+    G1S_OP_TRY(hipMalloc((void **)&d_tpartials.p, tneed * sizeof(unsigned long long)));
+    tpartials_cap = tneed;
+  }
+  have_prev = false, ring_at = 0;  // (a new geometry ends the run; the rings are made again)
+  d_keep[0] = DevBuf<uint8_t>(), d_keep[1] = DevBuf<uint8_t>();
   return G1S_OK;
 }
 
@@ -288,15 +480,66 @@ int g1s_measure::flush() {
   G1S_OP_TRY(hipGetLastError());
   if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
   G1S_OP_TRY(hipMemcpyAsync(h_recs, d_recs, sizeof(g1s_measure_record_t) * B, hipMemcpyDeviceToHost, stream));
+  // the batch's temporal jobs behind it on the same stream: the same launches with km_measure_t and km_tail_t
+  const uint32_t T = (uint32_t)tjobs.size();
+  if (T) {
+    std::memcpy(p_tjobs.h[set], tjobs.data(), sizeof(TemporalJob) * T);
+    G1S_OP_TRY(p_tjobs.upload(set, T, stream));
+    G1S_OP_TRY(hipMemsetAsync(d_trecs, 0, sizeof(g1s_measure_trecord_t) * T, stream));
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_t[0], stream));
+    for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
+      TemporalParams mp{};
+      mp.jobs = p_tjobs.d[set], mp.partials = d_tpartials;
+      mp.pw = (int)geom.pw(plane0), mp.ph = (int)geom.ph(plane0), mp.tiles_x = (mp.pw + kTW - 1) / kTW, mp.plane0 = plane0;
+      mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
+      mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
+      const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, T);
+      if (bps == 2) hipLaunchKernelGGL(km_measure_t<2>, grid, dim3(kThreads), 0, stream, mp);
+      else hipLaunchKernelGGL(km_measure_t<1>, grid, dim3(kThreads), 0, stream, mp);
+      G1S_OP_TRY(hipGetLastError());
+    }
+    TailParams ttp = tp;
+    ttp.partials = d_tpartials, ttp.records = reinterpret_cast<unsigned long long *>(d_trecs.p);
+    hipLaunchKernelGGL(km_tail_t, dim3((unsigned)geom.nplanes, T), dim3(kTTailWidth * kTTailGroups), 0, stream, ttp);
+    G1S_OP_TRY(hipGetLastError());
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_t[1], stream));
+    G1S_OP_TRY(hipMemcpyAsync(h_trecs, d_trecs, sizeof(g1s_measure_trecord_t) * T, hipMemcpyDeviceToHost, stream));
+  }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
   if (timing) {
     float ms = 0;
     G1S_OP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     ms_kernel += ms, frames_timed += B;
+    if (T) {
+      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_t[0], ev_t[1]));
+      ms_tkernel += ms, pairs_timed += T;
+    }
   }
   records.insert(records.end(), h_recs.p, h_recs.p + B);
+  trecords.insert(trecords.end(), h_trecs.p, h_trecs.p + T);
   jobs.clear();
+  tjobs.clear();
   return G1S_OK;
+}
+
+// The run's last pair survives a hand-over: the planes of it that are the caller's are copied into a frame of the meter's
+// own, device to device, and read from there by the next pair's temporal job.  (After flush(): nothing is in flight.)
+int g1s_measure::keep_prev() {
+  if (!have_prev) return G1S_OK;
+  for (int side = 0; side < 2; ++side) {
+    if (prev_staged[side]) continue;
+    const uint8_t **plane = side ? prev.b : prev.a;
+    uint32_t *stride = side ? prev.b_stride : prev.a_stride;
+    if (!d_keep[side] && hipMalloc((void **)&d_keep[side].p, stage.frame) != hipSuccess)
+      return fail(G1S_ERR_HIP, "hipMalloc of the kept frame failed");
+    for (int c = 0; c < geom.nplanes; ++c) {
+      uint8_t *dst = d_keep[side] + stage.off[c];
+      G1S_OP_TRY(hipMemcpy2DAsync(dst, stage.row[c], plane[c], stride[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToDevice, stream));
+      plane[c] = dst, stride[c] = (uint32_t)stage.row[c];
+    }
+    prev_staged[side] = true;
+  }
+  return wait();
 }
 
 namespace {
@@ -366,6 +609,20 @@ std::string write_report(const char *path, const g1s_measure_record_t &total, co
   return "";
 }
 
+// the temporal report of a clip's temporal record(s) into a file.  "" when fine
+std::string write_treport(const char *path, const g1s_measure_trecord_t &total, const g1s_measure_trecord_t *synth, uint64_t pairs,
+                          const g1s_y4m_info_t &info) {
+  std::vector<char> buf(1 << 16);
+  const long n = g1s_format_measure_temporal(&total, synth, pairs, info.bit_depth, info.width, info.height, info.xdec, info.ydec, info.nplanes,
+                                             buf.data(), buf.size());
+  if (n < 0) return "formatting the temporal report failed";
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return std::string("cannot create ") + path;
+  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
+  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
+  return "";
+}
+
 bool same_clip_shape(const g1s_y4m_info_t &a, const g1s_y4m_info_t &b) {
   return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.xdec == b.xdec && a.ydec == b.ydec && a.nplanes == b.nplanes;
 }
@@ -382,11 +639,61 @@ std::string take_records(g1s_measure_t *m, std::vector<g1s_measure_record_t> &sc
   return "";
 }
 
-}  // namespace
+// the temporal records the meter holds, added to `total` and counted in `pairs`.  "" when fine
+std::string take_trecords(g1s_measure_t *m, std::vector<g1s_measure_trecord_t> &scratch, g1s_measure_trecord_t &total, uint64_t &pairs) {
+  size_t n = 0;
+  int rc = g1s_measure_finish_temporal(m, nullptr, 0, &n);
+  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
+  scratch.resize(n + 1);
+  scratch[n] = total;
+  if (n && (rc = g1s_measure_finish_temporal(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
+  if (g1s_measure_sum_temporal(scratch.data(), n + 1, &total) != 0) return "the clip's temporal sums leave 64 bits";
+  pairs += n;
+  return "";
+}
 
-extern "C" {
+// the printed values of plane c of a clip's temporal record (one operation a step, in the order of the grammar)
+struct TProfile {
+  bool has_bin[kBins];
+  double bin[kBins];
+  bool has_lag[kTLags];
+  double lag[kTLags];
+  int peak;  // the lag of largest |rho|, the first on ties; -1: none is defined
+};
 
-g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts) {
+TProfile tprofile_of(const g1s_measure_trecord_t &t, int c, const double terms[kTLags]) {
+  TProfile p{};
+  uint64_t U = 0, V = 0;
+  for (int k = 0; k < kBins; ++k) {
+    U += t.u[c][k], V += t.v[c][k];
+    p.has_bin[k] = t.u[c][k] != 0 && t.v[c][k] != 0;
+    if (p.has_bin[k]) p.bin[k] = (double)t.x[c][k] / std::sqrt((double)t.u[c][k] * (double)t.v[c][k]);
+  }
+  const double T = terms[kTLags / 2];
+  p.peak = -1;
+  for (int i = 0; i < kTLags; ++i) {
+    p.has_lag[i] = U != 0 && V != 0 && terms[i] > 0.0;
+    if (!p.has_lag[i]) continue;
+    p.lag[i] = ((double)t.c[c][i] / terms[i]) / std::sqrt(((double)U / T) * ((double)V / T));
+    if (p.peak < 0 || std::fabs(p.lag[i]) > std::fabs(p.lag[p.peak])) p.peak = i;
+  }
+  return p;
+}
+
+std::string peak_text(const TProfile &p) {
+  if (p.peak < 0) return "- - -";
+  int dx, dy;
+  temporal_offset(p.peak, &dx, &dy);
+  return std::to_string(dx) + " " + std::to_string(dy) + " " + value(true, p.lag[p.peak]);
+}
+
+int not_temporal(g1s_measure_t *m) {
+  m->err = "the meter was not made by g1s_measure_new_temporal";  // (not sticky: err_code stays 0)
+  return G1S_ERR_INVALID;
+}
+
+// g1s_measure_new and g1s_measure_new_temporal: the same refusals, the same meter but for the temporal buffers
+g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, bool temporal) {
   g1s_set_global_error_("");
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
     g1s_set_global_error_("measure is defined for bit depths 8, 10 and 12");
@@ -403,11 +710,17 @@ g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opt
     return nullptr;
   }
   g1s_measure *m = new g1s_measure;
+  m->temporal = temporal;
   bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
   const uint32_t B = m->batch;
   for (Event &e : m->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
   ok = ok && m->p_jobs.alloc(B) && hipMalloc((void **)&m->d_recs.p, sizeof(g1s_measure_record_t) * B) == hipSuccess &&
        hipHostMalloc((void **)&m->h_recs.p, sizeof(g1s_measure_record_t) * B, hipHostMallocDefault) == hipSuccess;
+  if (temporal) {
+    for (Event &e : m->ev_t) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    ok = ok && m->p_tjobs.alloc(B) && hipMalloc((void **)&m->d_trecs.p, sizeof(g1s_measure_trecord_t) * B) == hipSuccess &&
+         hipHostMalloc((void **)&m->h_trecs.p, sizeof(g1s_measure_trecord_t) * B, hipHostMallocDefault) == hipSuccess;
+  }
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
     g1s_measure_free(m);
@@ -415,6 +728,14 @@ g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opt
   }
   return m;
 }
+
+}  // namespace
+
+extern "C" {
+
+g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, false); }
+
+g1s_measure_t *g1s_measure_new_temporal(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, true); }
 
 int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_frame_t *clean) {
   if (!m || !noisy || !clean) return G1S_ERR_INVALID;
@@ -431,20 +752,57 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
   }
   if (!m->have_geom && (rc = m->set_geometry(*noisy)) != 0) return rc;
   MeasureJob job{};
-  const uint32_t slot = (uint32_t)m->jobs.size();
-  if ((rc = m->stage_in(*noisy, slot, m->batch, job.a, job.a_stride, 0)) != 0) return rc;
-  if ((rc = m->stage_in(*clean, slot, m->batch, job.b, job.b_stride, 1)) != 0) return rc;
+  // a plain meter: the batch's slots; a temporal meter: rings of batch + 1 slots, so that the pair before the batch's first
+  // pair is still there
+  const uint32_t slots = m->temporal ? m->batch + 1 : m->batch, slot = m->temporal ? m->ring_at : (uint32_t)m->jobs.size();
+  if ((rc = m->stage_in(*noisy, slot, slots, job.a, job.a_stride, 0)) != 0) return rc;
+  if ((rc = m->stage_in(*clean, slot, slots, job.b, job.b_stride, 1)) != 0) return rc;
   if ((rc = m->wait_host_input(noisy->on_device == 0 ? *noisy : *clean)) != 0) return rc;
   m->jobs.push_back(job);
+  if (m->temporal) {
+    if (m->have_prev) m->tjobs.push_back(TemporalJob{job, m->prev});
+    m->prev = job, m->have_prev = true, m->ring_at = (slot + 1) % slots;
+    m->prev_staged[0] = noisy->on_device != 1, m->prev_staged[1] = clean->on_device != 1;
+  }
   return m->jobs.size() >= m->batch ? m->flush() : G1S_OK;
+}
+
+int g1s_measure_cut(g1s_measure_t *m) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  if (!m->temporal) return not_temporal(m);
+  (void)hipSetDevice(m->device);
+  m->have_prev = false;
+  return m->flush();
+}
+
+int g1s_measure_finish_temporal(g1s_measure_t *m, g1s_measure_trecord_t *per_pair, size_t cap, size_t *n_out) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  if (!m->temporal) return not_temporal(m);
+  (void)hipSetDevice(m->device);
+  int rc = m->flush();
+  if (rc || (rc = m->keep_prev()) != 0) return rc;
+  if (n_out) *n_out = m->trecords.size();
+  if (m->trecords.size() > cap || (!per_pair && !m->trecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
+  if (!m->trecords.empty()) std::memcpy(per_pair, m->trecords.data(), sizeof(g1s_measure_trecord_t) * m->trecords.size());
+  m->trecords.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_temporal_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
+  if (!m) return G1S_ERR_INVALID;
+  if (ms_kernel) *ms_kernel = m->ms_tkernel;
+  if (pairs) *pairs = m->pairs_timed;
+  return G1S_OK;
 }
 
 int g1s_measure_finish(g1s_measure_t *m, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out) {
   if (!m) return G1S_ERR_INVALID;
   if (m->err_code) return m->err_code;
   (void)hipSetDevice(m->device);
-  const int rc = m->flush();
-  if (rc) return rc;
+  int rc = m->flush();
+  if (rc || (rc = m->keep_prev()) != 0) return rc;
   if (n_out) *n_out = m->records.size();
   if (m->records.size() > cap || (!per_frame && !m->records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
   if (!m->records.empty()) std::memcpy(per_frame, m->records.data(), sizeof(g1s_measure_record_t) * m->records.size());
@@ -523,6 +881,68 @@ long g1s_format_measure(const g1s_measure_record_t *total, const g1s_measure_rec
   return (long)s.size();
 }
 
+int g1s_measure_sum_temporal(const g1s_measure_trecord_t *recs, size_t n, g1s_measure_trecord_t *total) {
+  if (!total || (n && !recs)) return G1S_ERR_INVALID;
+  g1s_measure_trecord_t t;
+  std::memset(&t, 0, sizeof t);
+  bool ok = true;
+  for (size_t f = 0; f < n; ++f)
+    for (int c = 0; c < 3; ++c) {
+      for (int k = 0; k < kBins; ++k)
+        ok = checked_add(t.n[c][k], recs[f].n[c][k]) && checked_add(t.x[c][k], recs[f].x[c][k]) && checked_add(t.u[c][k], recs[f].u[c][k]) &&
+             checked_add(t.v[c][k], recs[f].v[c][k]) && ok;
+      for (int i = 0; i < kTLags; ++i) ok = checked_add(t.c[c][i], recs[f].c[c][i]) && ok;
+    }
+  if (!ok) return G1S_ERR_INVALID;
+  *total = t;
+  return G1S_OK;
+}
+
+long g1s_format_measure_temporal(const g1s_measure_trecord_t *total, const g1s_measure_trecord_t *synth, uint64_t pairs, uint32_t bit_depth,
+                                 uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap) {
+  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
+  g1s_frame_t shape{};
+  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = (uint8_t)nplanes;
+  const PlaneGeom g(shape, 1);
+  std::string s = "graintemporal1\n";
+  s += "pairs " + std::to_string(pairs) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
+  for (int c = 0; c < (int)nplanes; ++c) {
+    s += "plane " + std::to_string(c) + "\n";
+    if (!pairs) continue;
+    double terms[kTLags];
+    for (int i = 0; i < kTLags; ++i) {
+      int dx, dy;
+      temporal_offset(i, &dx, &dy);
+      const int64_t tw = (int64_t)g.pw(c) - std::abs(dx), th = (int64_t)g.ph(c) - std::abs(dy);
+      terms[i] = tw > 0 && th > 0 ? (double)pairs * (double)tw * (double)th : 0.0;
+    }
+    const TProfile a = tprofile_of(*total, c, terms);
+    TProfile b{};
+    if (synth) b = tprofile_of(*synth, c, terms);
+    for (int k = 0; k < kBins; ++k) {
+      if (!total->n[c][k]) continue;
+      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[c][k]) + " " + value(a.has_bin[k], a.bin[k]);
+      if (synth) s += " " + value(b.has_bin[k], b.bin[k]);
+      s += "\n";
+    }
+    for (int i = 0; i < kTLags; ++i) {
+      int dx, dy;
+      temporal_offset(i, &dx, &dy);
+      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a.has_lag[i], a.lag[i]);
+      if (synth) s += " " + value(b.has_lag[i], b.lag[i]);
+      s += "\n";
+    }
+    s += "temporal_rho " + value(a.has_lag[kTLags / 2], a.lag[kTLags / 2]);
+    if (synth) s += " " + value(b.has_lag[kTLags / 2], b.lag[kTLags / 2]);
+    s += "\npeak_rho " + peak_text(a);
+    if (synth) s += " " + peak_text(b);
+    s += "\n";
+  }
+  if (s.size() > cap) return G1S_ERR_CAPACITY;
+  std::memcpy(buf, s.data(), s.size());
+  return (long)s.size();
+}
+
 int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {
   if (!m) return G1S_ERR_INVALID;
   m->timing = enable != 0;
@@ -537,6 +957,11 @@ void g1s_measure_free(g1s_measure_t *m) { free_op(m); }
 
 int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *out_report, const g1s_measure_opts_t *opts, int *unequal, char *err,
                               size_t cap) {
+  return g1s_measure_y4m_files_temporal(noisy, clean, out_report, nullptr, opts, unequal, err, cap);
+}
+
+int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, const char *out_report, const char *out_treport,
+                                       const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
   if (unequal) *unequal = 0;
   if (!noisy || !clean || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   g1s_y4m_t *ya = g1s_y4m_open(noisy, err, cap);
@@ -555,8 +980,13 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
   g1s_measure_record_t total;
   std::memset(&total, 0, sizeof total);
   std::vector<g1s_measure_record_t> scratch;
+  g1s_measure_trecord_t ttotal;
+  std::memset(&ttotal, 0, sizeof ttotal);
+  std::vector<g1s_measure_trecord_t> tscratch;
+  uint64_t pairs = 0;
   if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
-  if (!rc && !(m = g1s_measure_new(ia.bit_depth, opts))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && !(m = out_treport ? g1s_measure_new_temporal(ia.bit_depth, opts) : g1s_measure_new(ia.bit_depth, opts)))
+    rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   while (!rc) {
     g1s_frame_t fa, fb;
     const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
@@ -574,10 +1004,15 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
       break;
     }
     ++frames;
-    if (frames % m->batch == 0 && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
+    if (frames % m->batch == 0) {
+      if (!(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
+    }
   }
   if (!rc && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && !(why = write_report(out_report, total, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_treport && !(why = write_treport(out_treport, ttotal, nullptr, pairs, ia)).empty()) rc = G1S_ERR_INVALID;
   g1s_measure_free(m);
   g1s_y4m_close(ya);
   g1s_y4m_close(yb);
@@ -586,6 +1021,11 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
 
 int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
                             const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
+  return g1s_check_y4m_files_temporal(source, denoised, tbl, out_report, nullptr, opts, gopts, unequal, err, cap);
+}
+
+int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                     const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
   if (unequal) *unequal = 0;
   if (!source || !denoised || !tbl || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   // the table, as g1s_grain_y4m_file reads it
@@ -620,8 +1060,13 @@ int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char
   g1s_measure_record_t total_s, total_r;
   std::memset(&total_s, 0, sizeof total_s), std::memset(&total_r, 0, sizeof total_r);
   std::vector<g1s_measure_record_t> scratch;
+  g1s_measure_trecord_t ttotal_s, ttotal_r;
+  std::memset(&ttotal_s, 0, sizeof ttotal_s), std::memset(&ttotal_r, 0, sizeof ttotal_r);
+  std::vector<g1s_measure_trecord_t> tscratch;
+  uint64_t pairs_s = 0, pairs_r = 0;
+  auto meter = [&]() { return out_treport ? g1s_measure_new_temporal(id.bit_depth, opts) : g1s_measure_new(id.bit_depth, opts); };
   if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
-  if (!rc && (!(ms = g1s_measure_new(id.bit_depth, opts)) || !(mr = g1s_measure_new(id.bit_depth, opts)))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && (!(ms = meter()) || !(mr = meter()))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   if (!rc) {
     g1s_grain_opts_t go{};
     if (gopts) go = *gopts;
@@ -652,8 +1097,10 @@ int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char
       if ((rc = g1s_measure_frame(ms, &s, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(ms);
       else if ((rc = g1s_measure_frame(mr, &r, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(mr);
     }
+    // (a temporal meter keeps a copy of the group's last pair on the device: the group's buffers are free again all the same)
     for (int k = 0; k < 2 && !rc; ++k)
       if (!(why = take_records(k ? mr : ms, scratch, k ? total_r : total_s)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_treport && !(why = take_trecords(k ? mr : ms, tscratch, k ? ttotal_r : ttotal_s, k ? pairs_r : pairs_s)).empty()) rc = G1S_ERR_INVALID;
     in_group = 0;
   };
   while (!rc) {
@@ -690,6 +1137,7 @@ int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char
   }
   if (!rc && in_group) end_group();
   if (!rc && !(why = write_report(out_report, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_treport && !(why = write_treport(out_treport, ttotal_s, &ttotal_r, pairs_s, id)).empty()) rc = G1S_ERR_INVALID;
   if (ms) (void)hipSetDevice(ms->device);
   g1s_grain_free(gr);
   g1s_measure_free(mr);

@@ -10,6 +10,15 @@ in 32 bins) and its lagged products over the table's causal lag-3 neighbourhood:
 >>> text = format_profile(sum_records(records), len(records), 10, width, height)
 >>> measure_y4m_files("grainy.y4m", "clean.y4m", "profile.txt")
 >>> check_y4m_files("source.y4m", "denoised.y4m", "table.tbl", "fit.txt")   # source - denoised beside rendered - denoised
+
+A temporal meter also says whether the residual is independent from frame to frame (rules 7 - 11): from the second pair of
+a run on, every pair has a temporal record against the pair before it.
+
+>>> meter = GrainMeter(10, temporal=True)
+>>> for noisy, clean in pairs: meter.measure(noisy, clean)
+>>> trecords = meter.finish_temporal()          # one entry a pair but the run's first: n, x, u, v (3 x 32), c (3 x 25)
+>>> text = format_temporal_profile(sum_temporal_records(trecords), len(trecords), 10, width, height)
+>>> measure_y4m_files("grainy.y4m", "clean.y4m", "profile.txt", temporal_output="temporal.txt")
 """
 from __future__ import annotations
 
@@ -20,7 +29,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord
+from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord, G1SMeasureTRecord
 from ._frame_op import FrameOp
 from .diff import Frame
 from .ingest import UNEQUAL_WARNING
@@ -30,6 +39,9 @@ log = logging.getLogger("grav1synth")
 # g1s_measure_record_t
 RECORD = np.dtype([("n", "<u8", (3, 32)), ("s1", "<i8", (3, 32)), ("s2", "<u8", (3, 32)), ("r", "<i8", (3, 25))])
 assert RECORD.itemsize == C.sizeof(G1SMeasureRecord)
+# g1s_measure_trecord_t
+TRECORD = np.dtype([("n", "<u8", (3, 32)), ("x", "<i8", (3, 32)), ("u", "<u8", (3, 32)), ("v", "<u8", (3, 32)), ("c", "<i8", (3, 25))])
+assert TRECORD.itemsize == C.sizeof(G1SMeasureTRecord)
 
 
 def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
@@ -39,11 +51,12 @@ def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
 class GrainMeter(FrameOp):
     _name = "measure"
 
-    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0):
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False):
         self._L = _lib.lib()
         self.bit_depth = bit_depth
+        self.temporal = temporal
         opts = _opts(device, batch_frames)
-        self._h = self._L.g1s_measure_new(bit_depth, C.byref(opts))
+        self._h = (self._L.g1s_measure_new_temporal if temporal else self._L.g1s_measure_new)(bit_depth, C.byref(opts))
         if not self._h:
             raise G1SError(-5, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # planes the queued kernels still read
@@ -86,6 +99,34 @@ class GrainMeter(FrameOp):
         self._keep.clear()
         return out[:n.value]
 
+    def cut(self) -> None:
+        """Ends the run of a temporal meter: what is queued goes out, and the next pair has no temporal record."""
+        self._check(self._L.g1s_measure_cut(self._h))
+        self._keep.clear()
+
+    def finish_temporal(self, cap: Optional[int] = None) -> np.ndarray:
+        """As finish(), for the temporal records of a temporal meter: one for every pair that has a predecessor in its run,
+        in order, since the last finish_temporal().  The ordinary records stay until finish() fetches them."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_measure_finish_temporal(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), TRECORD)
+        rc = self._L.g1s_measure_finish_temporal(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def temporal_kernel_times(self) -> Tuple[float, int]:
+        """(ms in km_measure_t and km_tail_t, temporal records) of the batches kernel_times() had timed."""
+        a, n = C.c_double(), C.c_uint64()
+        self._L.g1s_measure_temporal_timing(self._h, C.byref(a), C.byref(n))
+        return a.value, n.value
+
     def kernel_times(self, enable: bool = True) -> Tuple[float, int]:
         """(ms in km_measure and km_tail, frames) of the timed batches so far (HIP events); enables / disables the timing."""
         a, n = C.c_double(), C.c_uint64()
@@ -116,13 +157,39 @@ def format_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, h
     return buf.raw[:w]
 
 
-def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, batch_frames: int = 0) -> Tuple[int, bool]:
-    """`measure NOISY CLEAN -o REPORT` for two .y4m files.  Returns (frames, unequal)."""
+def sum_temporal_records(records: np.ndarray) -> np.ndarray:
+    """Rule 10: a clip's temporal record from its pairs' (g1s_measure_sum_temporal; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, TRECORD).reshape(-1)
+    total = np.zeros((), TRECORD)
+    rc = _lib.lib().g1s_measure_sum_temporal(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's temporal sums leave 64 bits")
+    return total
+
+
+def format_temporal_profile(total: np.ndarray, pairs: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1, nplanes: int = 3,
+                            synth: Optional[np.ndarray] = None, cap: int = 1 << 16) -> bytes:
+    """The temporal report of a clip's temporal record (g1s_format_measure_temporal; host only): one value column, or two
+    with `synth`.  cap: the size of the buffer handed to the library (a test aid)."""
+    total = np.ascontiguousarray(total, TRECORD)
+    synth = None if synth is None else np.ascontiguousarray(synth, TRECORD)
+    buf = C.create_string_buffer(max(cap, 1))
+    w = _lib.lib().g1s_format_measure_temporal(total.ctypes.data, None if synth is None else synth.ctypes.data, pairs, bit_depth, width, height,
+                                               xdec, ydec, nplanes, buf, cap)
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_measure_temporal failed")
+    return buf.raw[:w]
+
+
+def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, batch_frames: int = 0,
+                      temporal_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`measure NOISY CLEAN -o REPORT [--temporal PATH]` for two .y4m files.  Returns (frames, unequal)."""
     opts = _opts(device, batch_frames)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_measure_y4m_files(str(noisy).encode(), str(clean).encode(), str(output).encode(), C.byref(opts), C.byref(unequal), err,
-                                         len(err))
+    n = _lib.lib().g1s_measure_y4m_files_temporal(str(noisy).encode(), str(clean).encode(), str(output).encode(),
+                                                  None if temporal_output is None else str(temporal_output).encode(), C.byref(opts),
+                                                  C.byref(unequal), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:
@@ -132,15 +199,16 @@ def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, 
 
 
 def check_y4m_files(source: str, denoised: str, table: str, output: str, *, device: int = -1, batch_frames: int = 0,
-                    clip_to_restricted_range: bool = False) -> Tuple[int, bool]:
-    """`check SOURCE DENOISED -g TABLE -o REPORT`: source - denoised beside render(denoised, table) - denoised.  Returns
-    (frames, unequal)."""
+                    clip_to_restricted_range: bool = False, temporal_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`check SOURCE DENOISED -g TABLE -o REPORT [--temporal PATH]`: source - denoised beside render(denoised, table) -
+    denoised.  Returns (frames, unequal)."""
     opts = _opts(device, batch_frames)
     gopts = G1SGrainOpts(C.sizeof(G1SGrainOpts), device, batch_frames, int(clip_to_restricted_range), 0)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_check_y4m_files(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(), C.byref(opts),
-                                       C.byref(gopts), C.byref(unequal), err, len(err))
+    n = _lib.lib().g1s_check_y4m_files_temporal(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(),
+                                                None if temporal_output is None else str(temporal_output).encode(), C.byref(opts),
+                                                C.byref(gopts), C.byref(unequal), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:

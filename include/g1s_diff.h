@@ -644,6 +644,22 @@ int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, co
  *      have.  Everything is exact: s2 <= 2^24 2^32 for the largest frame the checks admit (65536 x 65536).
  *   6. A clip's record is the sum of its frames' records, formed on the host with checked 64-bit additions
  *      (g1s_measure_sum): an overflow is a refusal, not a wrap.
+ * A temporal meter (g1s_measure_new_temporal) also says whether the residual is independent from frame to frame, as grain
+ * is and picture detail a denoiser removed is not.  A RUN is the sequence of pairs given one after another to one temporal
+ * meter with one geometry; a change of geometry or g1s_measure_cut ends it.  Pair t of a run, t >= 1, has a TEMPORAL RECORD
+ * against pair t - 1; d_t and d_{t-1} are rule 1 of their own pairs.  For every plane c:
+ *   7. Bins.  k(p) is rule 2 on the clean frame of pair t.  Per bin k, over the p of the plane with k(p) = k: n[k] the
+ *      count (u64), x[k] = sum of d_t(p) d_{t-1}(p) (i64), u[k] = sum of d_t(p)^2 (u64), v[k] = sum of d_{t-1}(p)^2 (u64).
+ *      So n and u equal the n and s2 of pair t's own record.
+ *   8. Offsets.  25 offsets dy = -2 .. 2, dx = -2 .. 2 in raster order: index i = (dy + 2) 5 + (dx + 2), (0, 0) is index
+ *      12.  The window is not causal: across frames both signs mean something.  c[i] = sum of d_t(p) d_{t-1}(p + delta_i)
+ *      (i64) over every p for which p AND p + delta_i lie inside the plane: skipped, not clamped.  The number of terms is
+ *      (pw - |dx|)(ph - |dy|), or 0 where that is not positive.
+ *   9. Record.  g1s_measure_trecord_t, zeros for the planes the frame does not have.  Everything is exact within rule 5's
+ *      bounds.
+ *  10. Sum.  A clip's temporal record is the checked 64-bit sum of its pairs' temporal records
+ *      (g1s_measure_sum_temporal): an overflow is a refusal.
+ *  11. Report.  g1s_format_measure_temporal writes plain text; the grammar is at its declaration.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes) and a small summing launch, on the meter's own stream.  Errors are sticky (g1s_measure_last_error). */
 typedef struct {
@@ -705,6 +721,62 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
  * device: opts->device).  Returns as g1s_measure_y4m_files. */
 int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
                             const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap);
+
+/* -- the temporal meter (rules 7 - 11 above) -- */
+typedef struct {
+  uint64_t n[3][32];
+  int64_t x[3][32];
+  uint64_t u[3][32];
+  uint64_t v[3][32];
+  int64_t c[3][25];
+} g1s_measure_trecord_t;
+/* A meter in temporal mode: g1s_measure_new with the same refusals.  g1s_measure_frame and g1s_measure_finish do on it
+ * what they do on a plain meter (the ordinary records are the same); from the second pair of a run on, g1s_measure_frame
+ * also queues the temporal job against the pair before.  Lifetime on a temporal meter: device and pinned planes of a pair
+ * must stay valid and unmodified until the batch that holds the NEXT pair has gone out, or until g1s_measure_cut,
+ * g1s_measure_finish or g1s_measure_finish_temporal (which keep a device copy of the run's last pair).  Host frames go
+ * into rings of batch_frames + 1 slots, so that the pair before a batch's first pair is still there: no pair is
+ * uploaded twice. */
+g1s_measure_t *g1s_measure_new_temporal(uint32_t bit_depth, const g1s_measure_opts_t *opts);
+/* Ends the run: what is queued goes out, and the next pair has no temporal record.  Scene cuts are the caller's knowledge
+ * (the .y4m commands never call this).  On a plain meter: G1S_ERR_INVALID, the text names g1s_measure_new_temporal; not
+ * sticky, the meter goes on working. */
+int g1s_measure_cut(g1s_measure_t *);
+/* As g1s_measure_finish, for the temporal records: one per pair that has a predecessor in its run, in order, since the last
+ * hand-over.  G1S_ERR_CAPACITY is not sticky and the records stay.  g1s_measure_finish and g1s_measure_finish_temporal each
+ * flush; each keeps the other's records until they are fetched.  On a plain meter as g1s_measure_cut. */
+int g1s_measure_finish_temporal(g1s_measure_t *, g1s_measure_trecord_t *per_pair, size_t cap, size_t *n_out);
+/* Rule 10 (host only, needs no device): *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_measure_sum_temporal(const g1s_measure_trecord_t *recs, size_t n, g1s_measure_trecord_t *total);
+/* Rule 11 (host only): plain text from a clip's temporal record of `pairs` records of one geometry.  synth == NULL: one
+ * value column; else two (total = source - denoised, synth = rendered - denoised).  Every value is formed in f64 from the
+ * exact integers in exactly the order written here, without fused multiply-add, and printed "%.4f"; "-" where undefined.
+ *   graintemporal1
+ *   pairs N bit_depth B planes P
+ *   plane c                          for c in 0 .. P - 1; with pairs = 0 nothing stands under it (a clip of one frame)
+ *   bin k n rho [rho']               the bins with n > 0 (n is total's): rho = (double)x / sqrt((double)u * (double)v);
+ *                                    "-" when u == 0 or v == 0
+ *   lag dx dy rho [rho']             the 25 lags in index order: rho = ((double)c[i] / terms_i) / sqrt(((double)U / T) *
+ *                                    ((double)V / T)), U = sum of u[k], V = sum of v[k] (u64 sums), T = pairs pw ph,
+ *                                    terms_i = pairs (pw - |dx|)(ph - |dy|); "-" when U == 0, V == 0 or terms_i == 0
+ *   temporal_rho v [v']              the (0, 0) lag
+ *   peak_rho dx dy v [dx' dy' v']    the lag of largest |rho|, the first in index order on ties; "- - -" when no lag is
+ *                                    defined
+ * There is no verdict.  Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a geometry rule 5 does not have). */
+long g1s_format_measure_temporal(const g1s_measure_trecord_t *total, const g1s_measure_trecord_t *synth, uint64_t pairs, uint32_t bit_depth,
+                                 uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap);
+/* HIP-event time of km_measure_t and km_tail_t in the batches g1s_measure_set_timing had timed, milliseconds, and the
+ * temporal records they made.  tools/bench_measure.py --temporal. */
+int g1s_measure_temporal_timing(g1s_measure_t *, double *ms_kernel, uint64_t *pairs);
+/* g1s_measure_y4m_files that also writes the clip's temporal report to out_treport (one run: frames - 1 records).
+ * out_treport == NULL is exactly g1s_measure_y4m_files. */
+int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, const char *out_report, const char *out_treport,
+                                       const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap);
+/* g1s_check_y4m_files that also writes the two-column temporal report to out_treport: total = source - denoised, synth =
+ * rendered - denoised.  The previous rendered and the previous denoised frame stay on the device for one more frame:
+ * nothing extra crosses PCIe.  out_treport == NULL is exactly g1s_check_y4m_files. */
+int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                     const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap);
 
 /* ---- decoder surfaces: NV12, P010 / P012 / P016 and MSB-aligned planes, to and from g1s_frame_t on the device ----
  * A hardware decoder (and an encoder on the same device) does not hold planar frames with the sample in the low bits: it

@@ -6,7 +6,13 @@ time per batch through g1s_measure_set_timing (a warm-up batch, then `repeats` t
 spread, and the bytes that must be read (both frames once) / time as a fraction of the 8 TB/s roofline.  Beside it, from the
 same process, what the project's streaming kernel k_estimate_pk reaches on the same luma plane (its own bytes / its own
 time): the yardstick of this box.  One JSON line per case.  For the kernel trace:
-rocprofv3 --kernel-trace --stats -- python tools/bench_measure.py 2 (a run of its own)."""
+rocprofv3 --kernel-trace --stats -- python tools/bench_measure.py 2 (a run of its own).
+
+tools/bench_measure.py --temporal [repeats]: the plain and the temporal meter on the plane-distinct content of both formats,
+in one process, in the order plain, temporal, plain, temporal.  A round of a meter is a warm-up batch and `repeats` timed
+batches.  Per format one JSON line: km_measure's time a frame (the yardstick; from the plain meter, and beside it from the
+temporal meter's own ordinary launches), km_measure_t's time a temporal record, their ratio, and the temporal kernel's bytes
+(four planes: both frames of both pairs, once) / time as a fraction of the 8 TB/s roofline."""
 import json, os, statistics, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,12 +24,61 @@ from grav1synth_amd.measure import GrainMeter
 from tests import content as CT
 
 assert torch.cuda.is_available(), "bench_measure.py needs a GPU"
-repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+argv = [a for a in sys.argv[1:] if a != "--temporal"]
+repeats = int(argv[0]) if argv else 7
 BATCH, PEAK = 32, 8e12
 
 
 def dev(planes):
     return [torch.from_numpy(np.ascontiguousarray(p)).to("cuda") for p in planes]
+
+
+def temporal_bench():
+    for name, (w, h, bd) in (("3840x2160 10-bit 4:2:0", (3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", (1920, 1080, 8))):
+        pairs = [CT.make_frames("distinct", w, h, bd, 1, 1, frame=k) for k in range(4)]
+        noisy, clean = [dev(s) for s, _d in pairs], [dev(d) for _s, d in pairs]
+        torch.cuda.synchronize()
+        frame_bytes = sum(p.numel() for p in noisy[0]) * (1 if bd == 8 else 2)
+        plain_us, ordinary_us, temporal_us = [], [], []  # a timed batch each: microseconds a frame / a temporal record
+        for rounds in range(2):
+            for temporal in (False, True):
+                m = GrainMeter(bd, batch_frames=BATCH, temporal=temporal)
+
+                def batch():
+                    for k in range(BATCH):
+                        m.measure(noisy[k % 4], clean[k % 4], 1, 1)
+                    m.finish()
+                    if temporal:
+                        m.finish_temporal()
+
+                batch()  # warm-up: code objects, buffers; the run goes on, so every timed batch has BATCH temporal records
+                for _ in range(repeats):
+                    a0, n0 = m.kernel_times(True)
+                    t0, p0 = m.temporal_kernel_times()
+                    batch()
+                    a1, n1 = m.kernel_times(False)
+                    t1, p1 = m.temporal_kernel_times()
+                    (ordinary_us if temporal else plain_us).append((a1 - a0) * 1e3 / (n1 - n0))
+                    if temporal:
+                        assert p1 - p0 == BATCH
+                        temporal_us.append((t1 - t0) * 1e3 / (p1 - p0))
+                m.close()
+        med = statistics.median
+        print(json.dumps({
+            "format": name, "content": "distinct", "batch_frames": BATCH, "repeats": repeats, "order": "plain, temporal, plain, temporal",
+            "km_measure_us_per_frame_median": med(plain_us), "km_measure_us_min": min(plain_us), "km_measure_us_max": max(plain_us),
+            "km_measure_in_temporal_meter_us_per_frame_median": med(ordinary_us),
+            "km_measure_t_us_per_record_median": med(temporal_us), "km_measure_t_us_min": min(temporal_us), "km_measure_t_us_max": max(temporal_us),
+            "ratio_km_measure_t_over_km_measure": med(temporal_us) / med(plain_us),
+            "km_measure_bytes_per_frame": 2 * frame_bytes, "km_measure_fraction_of_8TBps": 2 * frame_bytes / (med(plain_us) * 1e-6) / PEAK,
+            "km_measure_t_bytes_per_record": 4 * frame_bytes, "km_measure_t_TBps": 4 * frame_bytes / (med(temporal_us) * 1e-6) / 1e12,
+            "km_measure_t_fraction_of_8TBps": 4 * frame_bytes / (med(temporal_us) * 1e-6) / PEAK,
+        }), flush=True)
+
+
+if "--temporal" in sys.argv[1:]:
+    temporal_bench()
+    sys.exit(0)
 
 
 for name, (w, h, bd) in (("3840x2160 10-bit 4:2:0", (3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", (1920, 1080, 8))):
