@@ -32,6 +32,8 @@ BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not co
 DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser runs on the source as it is read). Exiting."
 DENOISE_ONE_DEVICE = "--denoise does not combine with --gpus / --devices (one denoiser, one generator, one device). Exiting."
 BAD_TEMPORAL_RADIUS = "--temporal-radius must be 0..3 (frames before and after the one in hand). Exiting."
+BAD_MOTION_RANGE = "--motion-range must be even and 0..64 (samples a tile may move between two frames). Exiting."
+MOTION_NEEDS_TEMPORAL = "--motion-range moves the neighbour frames of --temporal-radius: it needs a temporal radius above 0. Exiting."
 KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs --denoise. Exiting."
 PRIOR_NEEDS_TABLE = "--prior-range and --prior-segment say how --grain-prior is used: they need --grain-prior. Exiting."
 PRIOR_12_BIT = ("--grain-prior filters luma in a 12-bit domain: a 12-bit input has no headroom there (8 and 10 bits are "
@@ -74,6 +76,9 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
     p.add_argument("--chroma-strength", type=float, default=0.0, help="strength for the chroma planes (default: --strength)")
     p.add_argument("--temporal-radius", type=int, default=0, metavar="D",
                    help="temporal radius D, 0..3 (default 0): the mean also runs over the search windows of the D frames before and after")
+    p.add_argument("--motion-range", type=int, default=0, metavar="PIXELS",
+                   help="with --temporal-radius: every 64 x 48 tile gets one vector of up to PIXELS samples each way (even, 0..64) towards "
+                        "every neighbour frame and reads the neighbour there; for pans and other motion beyond the search radius (default 0: off)")
     p.add_argument("--joint-chroma", action="store_true",
                    help="luma-guided joint chroma: Cb and Cr share one weight, taken from both and the luma at the same place "
                         "(KNLMeansCL's channels=\"YUV\" in structure; off by default)")
@@ -89,7 +94,19 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
 def _denoise_parameters(args) -> dict:
     return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
                 chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
-                grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment)
+                grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range)
+
+
+def _motion_refused(parameters: dict) -> bool:
+    """The refusals of --motion-range, each a logged line: True when one was logged."""
+    mr = parameters.get("motion_range", 0)
+    if mr % 2 or not 0 <= mr <= 64:
+        log.error(BAD_MOTION_RANGE)
+        return True
+    if mr and not parameters.get("temporal_radius", 0):
+        log.error(MOTION_NEEDS_TEMPORAL)
+        return True
+    return False
 
 
 def _prior_refused(input: str, outputs, parameters: dict) -> bool:
@@ -207,6 +224,8 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
         return -1
+    if _motion_refused(parameters):
+        return -1
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
         return -1
@@ -306,6 +325,8 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
 
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
+        return -1
+    if _motion_refused(parameters):
         return -1
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)

@@ -69,6 +69,74 @@ struct DenoiseParamsT {
   int nnb;  // 2 D
 };
 
+// the same under motion (rules 16 - 20): the frame's vectors, per plane [2 D][blocks of the plane] pairs of int8 (mx, my);
+// kd_motion writes them, kd_nlm_tm and kd_nlm_jtm read them.  Under the joint flag mv[2] is mv[1].
+struct DenoiseJobTM {
+  DenoiseJobT t;
+  int8_t *mv[3];
+};
+
+struct DenoiseParamsTM {
+  const DenoiseJobTM *jobs;
+  const uint16_t *table;
+  int q, A;
+  int W, H, tiles_x;
+  int plane0;
+  int nnb;
+  int blocks;  // tiles of the class's plane
+};
+
+struct DenoiseParamsJTM {
+  const DenoiseJobTM *jobs;
+  const uint16_t *table;
+  int q, A;
+  JointShape s;
+  int tiles_x;
+  int nnb;
+  int blocks;
+};
+
+// a workgroup per (block, plane of the class or joint chroma pair, frame and neighbour): the block's vector towards that neighbour
+struct MotionParams {
+  const DenoiseJobTM *jobs;
+  int M;
+  int W, H, tiles_x;  // the class's plane size
+  int plane0;
+  int nnb;
+  int blocks;
+};
+
+template <int BPS, int NA>
+__global__ __launch_bounds__(kThreads) void kd_motion(MotionParams p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const int f = (int)blockIdx.z / p.nnb, k = (int)blockIdx.z - f * p.nnb;
+  const DenoiseJobTM &job = p.jobs[f];
+  const int c = p.plane0 + (int)blockIdx.y;
+  int8_t *mv = job.mv[c] + 2 * (k * p.blocks + (int)blockIdx.x);
+  if (!job.t.nb[c][k]) {  // rule 5: the clip has no such frame (the same for the whole workgroup)
+    if (threadIdx.x == 0) mv[0] = 0, mv[1] = 0;
+    return;
+  }
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  MotionPlanes cur, ref;
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+    cur.p[a] = job.t.f.in[c + a], cur.stride[a] = job.t.f.in_stride[c + a], ref.p[a] = job.t.nb[c + a][k], ref.stride[a] = job.t.nb_stride[c + a][k];
+  dn_motion_tile<BPS, NA>((int)threadIdx.x, motion_geom(p.M, NA), dn_lds, cur, ref, p.W, p.H, tx, ty, [] { __syncthreads(); }, mv);
+}
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_tm(DenoiseParamsTM p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobTM &job = p.jobs[blockIdx.z];
+  const int c = p.plane0 + (int)blockIdx.y;
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  dn_tile_tm<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, job.t.f.in[c], job.t.f.in_stride[c], job.t.nb[c], job.t.nb_stride[c], p.nnb,
+                     job.mv[c] + 2 * (int)blockIdx.x, 2 * p.blocks, job.t.f.out[c], job.t.f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH,
+                     [] { __syncthreads(); });
+}
+
 template <int S, int BPS>
 __global__ __launch_bounds__(kThreads) void kd_nlm_t(DenoiseParamsT p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
@@ -132,6 +200,19 @@ __global__ __launch_bounds__(kThreads) void kd_nlm_jt(DenoiseParamsJT p) {
                      job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); });
 }
 
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_jtm(DenoiseParamsJTM p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobTM &jm = p.jobs[blockIdx.z];
+  const DenoiseJobT &job = jm.t;
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
+  dn_tile_jtm<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, jm.mv[1] + 2 * (int)blockIdx.x,
+                      2 * p.blocks, p.s, job.f.out[1], job.f.out_stride[1], job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH,
+                      [] { __syncthreads(); });
+}
+
 // the kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
 struct Plain {
   using Params = DenoiseParams;
@@ -151,6 +232,15 @@ struct JointTemporal {
   template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jt<S, BPS>), grid, dim3(kThreads), lds, st, p); }
 };
 
+struct TemporalMotion {
+  using Params = DenoiseParamsTM;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_tm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+struct JointTemporalMotion {
+  using Params = DenoiseParamsJTM;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+
 // the family's kernel for patch radius S and `bps` bytes a sample; false: there is none
 template <class Family>
 bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t st, const typename Family::Params &p) {
@@ -166,6 +256,13 @@ bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t 
   }
   return false;
 }
+
+// G1S_OP_TRY outside a member: the operation is `g`
+#define G1S_OP_TRY_(g, expr)                                                                                       \
+  do {                                                                                                             \
+    hipError_t e_ = (expr);                                                                                        \
+    if (e_ != hipSuccess) return (g)->fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
+  } while (0)
 
 // rule 3, for patches of `planes` planes (rule 10: 3).  "" when fine.
 std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTable], uint32_t *q_out, uint32_t planes = 1) {
@@ -190,9 +287,10 @@ using namespace g1s_op;
 // (the stream, the sticky error, the parameter sets' turn and the staging of host frames: BatchedOp, frame_op.h)
 struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
+  uint32_t M = 0;  // the motion range on the search plane (rules 16 - 20); 0: no motion, the launches of rules 1 - 15
   bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j / kd_nlm_jt for their chroma
   uint32_t q[4] = {0, 0, 0, 0};  // luma, chroma, joint chroma, luma in the stabilised domain
-  Event ev[2];
+  Event ev[3];
   // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
   // output goes (out[c] is null for a host frame: a slot of the output staging buffer is chosen at the launch)
   struct Queued {
@@ -214,10 +312,28 @@ struct g1s_denoise : BatchedOp {
   DevBuf<uint8_t> d_stab, d_filt;
   size_t stab_row = 0, stab_plane = 0;
   uint64_t next_stab = 0;  // the first frame whose luma is not in its slot yet
-  double ms_kernel = 0;
+  double ms_kernel = 0, ms_motion = 0;
   uint64_t frames_timed = 0;
+  // under motion: a set's vectors, a frame after the other: per plane [2 D][blocks of the plane] pairs of int8
+  DevBuf<int8_t> d_mv[2];
+  size_t mv_off[3] = {0, 0, 0}, mv_frame = 0;
+  int blocks_of(const PlaneGeom &pg, int c) const { return (int)((pg.pw(c) + kTW - 1) / kTW * ((pg.ph(c) + kTH - 1) / kTH)); }
+  // where plane c's vectors start in a frame's; under the joint flag the chroma planes share plane 1's.  Returns a frame's bytes.
+  size_t mv_layout(const PlaneGeom &pg, uint32_t nnb, size_t off[3]) const {
+    size_t at = 0;
+    for (int c = 0; c < pg.nplanes; ++c) {
+      if (c == 2 && joint) {
+        off[2] = off[1];
+        continue;
+      }
+      off[c] = at, at += align_up((size_t)2 * nnb * (size_t)blocks_of(pg, c), 16);
+    }
+    return at;
+  }
+  int need_mv();
+  int launch_motion(const DenoiseJobTM *jobs, const PlaneGeom &pg, uint32_t nframes, uint32_t nnb, int plane0, uint32_t bps_, hipStream_t st);
 
-  size_t job_bytes() const { return D ? sizeof(DenoiseJobT) : sizeof(DenoiseJob); }
+  size_t job_bytes() const { return D ? (M ? sizeof(DenoiseJobTM) : sizeof(DenoiseJobT)) : sizeof(DenoiseJob); }
   // a parameter set: the batch's jobs and, with a curve, the luma launch's jobs in the stabilised planes, the forward
   // launch's (a first batch brings its D later neighbours along) and the inverse launch's
   size_t off_luma() const { return align_up(job_bytes() * batch, 16); }
@@ -250,7 +366,11 @@ int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_cl
   const dim3 grid((unsigned)(tiles_x * ((H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
   const TileGeom tg = tile_geom((int)A, (int)S);
   bool found;
-  if (D) {
+  if (D && M) {
+    DenoiseParamsTM t{};
+    fill(t), t.nnb = (int)(2 * D), t.blocks = (int)grid.x;
+    found = launch_family<TemporalMotion>(S, bps, grid, (size_t)tg.bytes_t, stream, t);
+  } else if (D) {
     DenoiseParamsT t{};
     fill(t), t.nnb = (int)(2 * D);
     found = launch_family<Temporal>(S, bps, grid, (size_t)tg.bytes_t, stream, t);
@@ -274,7 +394,11 @@ int g1s_denoise::launch_joint(int set, uint32_t nframes) {
   const dim3 grid((unsigned)(tiles_x * ((ch + kTH - 1) / kTH)), 1u, nframes);
   const JointGeom jg = joint_geom(tile_geom((int)A, (int)S));
   bool found;
-  if (D) {
+  if (D && M) {
+    DenoiseParamsJTM t{};
+    fill(t), t.nnb = (int)(2 * D), t.blocks = (int)grid.x;
+    found = launch_family<JointTemporalMotion>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
+  } else if (D) {
     DenoiseParamsJT t{};
     fill(t), t.nnb = (int)(2 * D);
     found = launch_family<JointTemporal>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
@@ -294,6 +418,35 @@ int g1s_denoise::need_stab() {
   stab_row = align_up((size_t)geom.W * 2, kStageRowAlign), stab_plane = align_up(stab_row * (size_t)geom.H, kStagePlaneAlign);
   if (hipMalloc((void **)&d_stab.p, stab_plane * ring()) != hipSuccess || hipMalloc((void **)&d_filt.p, stab_plane * batch) != hipSuccess)
     return fail(G1S_ERR_HIP, "hipMalloc of the stabilised luma planes failed");
+  return G1S_OK;
+}
+
+// the two sets' vectors for the geometry in hand
+int g1s_denoise::need_mv() {
+  if (d_mv[0]) return G1S_OK;
+  mv_frame = mv_layout(geom, 2 * D, mv_off);
+  for (DevBuf<int8_t> &b : d_mv)
+    if (hipMalloc((void **)&b.p, mv_frame * batch) != hipSuccess) return fail(G1S_ERR_HIP, "hipMalloc of the motion vectors failed");
+  return G1S_OK;
+}
+
+// kd_motion for the planes of a class (plane0 = 0: luma, in samples of bps_ bytes; 1: the chroma planes, or under the joint
+// flag the pair) of `nframes` jobs with nnb neighbours each
+int g1s_denoise::launch_motion(const DenoiseJobTM *jobs, const PlaneGeom &pg, uint32_t nframes, uint32_t nnb, int plane0, uint32_t bps_, hipStream_t st) {
+  MotionParams p{};
+  p.jobs = jobs, p.M = (int)M, p.W = (int)pg.pw(plane0), p.H = (int)pg.ph(plane0), p.tiles_x = (p.W + kTW - 1) / kTW, p.plane0 = plane0, p.nnb = (int)nnb;
+  p.blocks = blocks_of(pg, plane0);
+  const bool pair = plane0 && joint;
+  const dim3 grid((unsigned)p.blocks, plane0 && !pair ? 2u : 1u, nframes * nnb);
+  const size_t lds = (size_t)motion_geom((int)M, pair ? 2 : 1).bytes;
+  if (pair) {
+    if (bps_ == 2) hipLaunchKernelGGL((kd_motion<2, 2>), grid, dim3(kThreads), lds, st, p);
+    else hipLaunchKernelGGL((kd_motion<1, 2>), grid, dim3(kThreads), lds, st, p);
+  } else {
+    if (bps_ == 2) hipLaunchKernelGGL((kd_motion<2, 1>), grid, dim3(kThreads), lds, st, p);
+    else hipLaunchKernelGGL((kd_motion<1, 1>), grid, dim3(kThreads), lds, st, p);
+  }
+  G1S_OP_TRY(hipGetLastError());
   return G1S_OK;
 }
 
@@ -344,15 +497,38 @@ int g1s_denoise::flush(uint32_t nframes) {
       }
       ++k;
     }
+    if (M) {
+      // (the stabilised luma's vectors are the luma's: one search, on the planes the filter filters -- rule 20)
+      DenoiseJobTM tm{}, ltm{};
+      tm.t = t, ltm.t = lt;
+      for (int c = 0; c < geom.nplanes; ++c) tm.mv[c] = d_mv[set] + mv_frame * i + mv_off[c];
+      ltm.mv[0] = tm.mv[0];
+      reinterpret_cast<DenoiseJobTM *>(p_jobs.h[set].p)[i] = tm;
+      if (curve) reinterpret_cast<DenoiseJobTM *>(p_jobs.h[set].p + off_luma())[i] = ltm;
+      continue;
+    }
     reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p)[i] = t;
     if (curve) reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p + off_luma())[i] = lt;
   }
   G1S_OP_TRY(p_jobs.upload(set, curve ? set_bytes() : job_bytes() * nframes, stream));
   if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
+  if (curve)
+    G1S_OP_TRY(g1s_cv::launch_curve((int)bps, 2, reinterpret_cast<const g1s_cv::CurveJob *>(p_jobs.d[set].p + off_fwd()), nfwd, d_curve, 1u << bit_depth,
+                                    (uint32_t)geom.W, (uint32_t)geom.H, stream));
+  if (D && M) {
+    // the batch's vectors, in front of its filter launches: luma on what the luma launch filters, then chroma
+    const uint8_t *dj = p_jobs.d[set].p;
+    if (timing) G1S_OP_TRY(hipEventRecord(ev[2], stream));
+    if ((rc = launch_motion(reinterpret_cast<const DenoiseJobTM *>(dj + (curve ? off_luma() : 0)), geom, nframes, 2 * D, 0, curve ? 2u : bps, stream)) != 0) return rc;
+    if (geom.nplanes == 3 && (rc = launch_motion(reinterpret_cast<const DenoiseJobTM *>(dj), geom, nframes, 2 * D, 1, bps, stream)) != 0) return rc;
+    if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
+    if (timing) G1S_OP_TRY(hipStreamSynchronize(stream));
+    float a = 0;
+    if (timing) G1S_OP_TRY(hipEventElapsedTime(&a, ev[2], ev[1]));
+    ms_motion += a;
+  }
   if (curve) {
     const uint8_t *dj = p_jobs.d[set].p;
-    G1S_OP_TRY(g1s_cv::launch_curve((int)bps, 2, reinterpret_cast<const g1s_cv::CurveJob *>(dj + off_fwd()), nfwd, d_curve, 1u << bit_depth, (uint32_t)geom.W,
-                                    (uint32_t)geom.H, stream));
     if ((rc = launch(set, nframes, 0, 1, true)) != 0) return rc;
     G1S_OP_TRY(g1s_cv::launch_curve(2, (int)bps, reinterpret_cast<const g1s_cv::CurveJob *>(dj + off_inv()), nframes, d_curve + (1u << bit_depth),
                                     g1s_cv::kInvEntries, (uint32_t)geom.W, (uint32_t)geom.H, stream));
@@ -427,20 +603,20 @@ struct Prior {
     return g1s_cv::build(segs.data(), segs.size(), bit_depth, range, fwd.data(), inv.data());
   }
   // the denoiser for a clip of this depth; NULL with the global error text set
-  g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags) const {
+  g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags, uint32_t motion_range = 0) const {
     std::vector<uint16_t> fwd, inv;
     const std::string why = make(bit_depth, fwd, inv);
     if (!why.empty()) {
       g1s_set_global_error_(why.c_str());
       return nullptr;
     }
-    return g1s_denoise_new_curve(bit_depth, opts, D, flags, fwd.data(), inv.data());
+    return g1s_denoise_new_motion(bit_depth, opts, D, flags, fwd.data(), inv.data(), motion_range);
   }
 };
 
 // what every g1s_denoise_new* call makes; `curve`: with the pair (fwd, inv) of rules 12 - 15
 static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, bool curve,
-                                 const uint16_t *fwd, const uint16_t *inv) {
+                                 const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range = 0) {
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -459,6 +635,14 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   }
   if (flags & ~G1S_DENOISE_JOINT_CHROMA) {
     g1s_set_global_error_("unknown denoise flags");
+    return nullptr;
+  }
+  if ((motion_range & 1) || motion_range > 2u * (uint32_t)kMaxM) {
+    g1s_set_global_error_("motion_range must be even and 0..64");
+    return nullptr;
+  }
+  if (motion_range && !temporal_radius) {
+    g1s_set_global_error_("motion_range needs a temporal radius");
     return nullptr;
   }
   std::vector<uint16_t> tables(4 * kTable);
@@ -499,7 +683,7 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   }
   g1s_denoise *g = new g1s_denoise;
   g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
-  g->curve = curve;
+  g->curve = curve, g->M = motion_range / 2;
   for (int i = 0; i < 4; ++i) g->q[i] = q[i];
   bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
   for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
@@ -551,6 +735,88 @@ g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_
   return new_denoiser(bit_depth, opts, temporal_radius, flags, true, fwd, inv);
 }
 
+g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
+                                      const uint16_t *inv, uint32_t motion_range) {
+  return new_denoiser(bit_depth, opts, temporal_radius, flags, fwd || inv, fwd, inv, motion_range);
+}
+
+// stage 1 alone: both frames on the device (a host frame in an allocation of this call), luma through the forward curve
+// where there is one, one job with `ref` as its only neighbour, kd_motion, the vectors back
+int g1s_denoise_motion_search(g1s_denoise_t *g, const g1s_frame_t *cur, const g1s_frame_t *ref, int16_t *mv[3], size_t cap_pairs[3]) {
+  if (!g || !cur || !ref || !mv || !cap_pairs) return G1S_ERR_INVALID;
+  if (g->err_code) return g->err_code;
+  if (!g->M) return g->fail(G1S_ERR_INVALID, "g1s_denoise_motion_search needs a denoiser with a motion range");
+  (void)hipSetDevice(g->device);
+  const Refusal no = check_frame_pair(*cur, *ref, g->bps, 65536u, "g1s_denoise_new_motion",
+                                      "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)", "the two");
+  if (no.code) return g->fail(no.code, no.text);
+  const PlaneGeom pg(*cur, g->bps);
+  size_t off[3] = {0, 0, 0};
+  const size_t bytes = g->mv_layout(pg, 1, off);
+  bool fits = true;
+  for (int c = 0; c < pg.nplanes; ++c) {
+    const size_t need = (size_t)g->blocks_of(pg, c);
+    fits = fits && mv[c] && cap_pairs[c] >= need;
+    cap_pairs[c] = need;
+  }
+  if (!fits) return G1S_ERR_CAPACITY;
+  // the planes kd_motion reads: the caller's device planes, or copies; luma with a curve: its stabilised form
+  const Layout lay = staging_layout(pg);
+  const size_t stab_row = align_up((size_t)pg.W * 2, kStageRowAlign), stab_plane = align_up(stab_row * (size_t)pg.H, kStagePlaneAlign);
+  DevBuf<uint8_t> copy[2], stab;
+  DevBuf<uint8_t> d_job;
+  DevBuf<int8_t> d_v;
+  DenoiseJobTM job{};
+  g1s_cv::CurveJob cj[2];
+  const g1s_frame_t *fr[2] = {cur, ref};
+  if (hipMalloc((void **)&d_job.p, sizeof job + sizeof cj) != hipSuccess || hipMalloc((void **)&d_v.p, bytes) != hipSuccess ||
+      (g->curve && hipMalloc((void **)&stab.p, 2 * stab_plane) != hipSuccess))
+    return g->fail(G1S_ERR_HIP, "hipMalloc for the motion search failed");
+  for (int i = 0; i < 2; ++i) {
+    const uint8_t *pl[3] = {nullptr, nullptr, nullptr};
+    uint32_t st[3] = {0, 0, 0};
+    if (fr[i]->on_device != 1 && hipMalloc((void **)&copy[i].p, lay.frame) != hipSuccess) return g->fail(G1S_ERR_HIP, "hipMalloc for the motion search failed");
+    for (int c = 0; c < pg.nplanes; ++c) {
+      if (fr[i]->on_device == 1) {
+        pl[c] = static_cast<const uint8_t *>(fr[i]->data[c]), st[c] = (uint32_t)fr[i]->stride_bytes[c];
+        continue;
+      }
+      uint8_t *dst = copy[i] + lay.off[c];
+      G1S_OP_TRY_(g, hipMemcpy2DAsync(dst, lay.row[c], fr[i]->data[c], fr[i]->stride_bytes[c], pg.row_bytes(c), pg.ph(c), hipMemcpyHostToDevice, g->stream));
+      pl[c] = dst, st[c] = (uint32_t)lay.row[c];
+    }
+    if (g->curve) {
+      cj[i] = g1s_cv::CurveJob{pl[0], stab + stab_plane * (size_t)i, st[0], (uint32_t)stab_row};
+      pl[0] = stab + stab_plane * (size_t)i, st[0] = (uint32_t)stab_row;
+    }
+    for (int c = 0; c < pg.nplanes; ++c) {
+      if (i == 0) job.t.f.in[c] = pl[c], job.t.f.in_stride[c] = st[c], job.mv[c] = d_v + off[c];
+      else job.t.nb[c][0] = pl[c], job.t.nb_stride[c][0] = st[c];
+    }
+  }
+  G1S_OP_TRY_(g, hipMemcpyAsync(d_job, &job, sizeof job, hipMemcpyHostToDevice, g->stream));
+  if (g->curve) {
+    G1S_OP_TRY_(g, hipMemcpyAsync(d_job + sizeof job, cj, sizeof cj, hipMemcpyHostToDevice, g->stream));
+    G1S_OP_TRY_(g, g1s_cv::launch_curve((int)g->bps, 2, reinterpret_cast<const g1s_cv::CurveJob *>(d_job + sizeof job), 2, g->d_curve, 1u << g->bit_depth,
+                                        (uint32_t)pg.W, (uint32_t)pg.H, g->stream));
+  }
+  int rc = g->launch_motion(reinterpret_cast<const DenoiseJobTM *>(d_job.p), pg, 1, 1, 0, g->curve ? 2u : g->bps, g->stream);
+  if (!rc && pg.nplanes == 3) rc = g->launch_motion(reinterpret_cast<const DenoiseJobTM *>(d_job.p), pg, 1, 1, 1, g->bps, g->stream);
+  if (rc) return rc;
+  std::vector<int8_t> v(bytes);
+  G1S_OP_TRY_(g, hipMemcpyAsync(v.data(), d_v, bytes, hipMemcpyDeviceToHost, g->stream));
+  if ((rc = g->wait()) != 0) return rc;  // (the job, the copies and the pageable copies above are this call's: through before it returns)
+  for (int c = 0; c < pg.nplanes; ++c)
+    for (size_t i = 0; i < 2 * cap_pairs[c]; ++i) mv[c][i] = v[off[c] + i];
+  return G1S_OK;
+}
+
+int g1s_denoise_motion_time(g1s_denoise_t *g, double *ms_motion) {
+  if (!g || !ms_motion) return G1S_ERR_INVALID;
+  *ms_motion = g->ms_motion;
+  return G1S_OK;
+}
+
 int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out) {
   if (!g || !in || !out) return G1S_ERR_INVALID;
   if (g->err_code) return g->err_code;
@@ -564,8 +830,10 @@ int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out)
     if ((rc = g->end_clip()) != 0) return rc;
     g->have_geom = false;
   }
-  if (!g->have_geom) g->set_frame_geometry(*in), g->d_stab = DevBuf<uint8_t>(), g->d_filt = DevBuf<uint8_t>();
+  if (!g->have_geom)
+    g->set_frame_geometry(*in), g->d_stab = DevBuf<uint8_t>(), g->d_filt = DevBuf<uint8_t>(), g->d_mv[0] = DevBuf<int8_t>(), g->d_mv[1] = DevBuf<int8_t>();
   if (g->curve && (rc = g->need_stab()) != 0) return rc;
+  if (g->M && (rc = g->need_mv()) != 0) return rc;
   const PlaneGeom &gm = g->geom;
   g1s_denoise::Queued f{};
   // the input ring's slot: a launched frame stays a neighbour.  The output buffer is `batch` slots, chosen at the launch
@@ -650,6 +918,11 @@ int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoi
 
 int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, char *err, size_t cap) {
+  return g1s_denoise_y4m_file_motion(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, 0, err, cap);
+}
+
+int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err, size_t cap) {
   Prior prior;
   if (prior_tbl) {
     const std::string why = prior.load(prior_tbl, prior_range, prior_segment);
@@ -664,10 +937,11 @@ int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_de
     const g1s_denoise_opts_t *opts;
     uint32_t D, flags;
     const Prior *prior;
+    uint32_t Mr;
     g1s_denoise_t *g = nullptr;
     const int new_failed = G1S_ERR_INVALID;
     bool open(const g1s_y4m_info_t &i) {
-      return (g = prior ? prior->open(i.bit_depth, opts, D, flags) : g1s_denoise_new_ex(i.bit_depth, opts, D, flags)) != nullptr;
+      return (g = prior ? prior->open(i.bit_depth, opts, D, flags, Mr) : g1s_denoise_new_motion(i.bit_depth, opts, D, flags, nullptr, nullptr, Mr)) != nullptr;
     }
     uint32_t batch() const { return g->batch; }
     uint32_t ring() const { return g->batch + g->D; }
@@ -676,7 +950,7 @@ int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_de
     const char *last_error() const { return g1s_denoise_last_error(g); }
     void close() { g1s_denoise_free(g); }
   };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior_tbl ? &prior : nullptr});
+  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range});
 }
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
@@ -703,6 +977,14 @@ int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const
 int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                      uint32_t prior_range, int32_t prior_segment, uint64_t *frames_out, char *err, size_t cap) {
+  return g1s_diff_y4m_file_denoised_motion(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, 0,
+                                           frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint64_t *frames_out, char *err,
+                                      size_t cap) {
   auto refuse = [&](int code, const std::string &m) {
     if (err && cap) snprintf(err, cap, "%s", m.c_str());
     return code;
@@ -751,7 +1033,8 @@ int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, co
     if (dopts) d = *dopts;
     d.struct_size = sizeof d;
     d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = prior_tbl ? prior.open(info.bit_depth, &d, temporal_radius, flags) : g1s_denoise_new_ex(info.bit_depth, &d, temporal_radius, flags);
+    dn = prior_tbl ? prior.open(info.bit_depth, &d, temporal_radius, flags, motion_range)
+                   : g1s_denoise_new_motion(info.bit_depth, &d, temporal_radius, flags, nullptr, nullptr, motion_range);
   }
   if (!dn) {
     rc = G1S_ERR_INVALID, why = g1s_last_global_error();

@@ -282,17 +282,19 @@ G1S_DN_HD void dn_weights(int tid, const TileGeom &g, const uint32_t *Hb, uint16
 }
 
 // Wb(y, x) = the weight of the pair {(t, p), (t + k, p + d)} for the tile's samples p = (x0 + x, y0 + y); 0 where p or p + d
-// lies outside the W x H grid (rule 6).  Tasks as in dn_weights, and no task overlaps another: 8 divides kTH.
+// lies outside the W x H grid (rule 6).  Tasks as in dn_weights, and no task overlaps another: 8 divides kTH.  Under motion
+// (rule 19) the neighbour was staged from the tile moved by (mx, my), and it is p + m + d that has to lie inside.
 template <int S>
 G1S_DN_HD void dn_weights_t(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int x0,
-                            int y0, int W, int H) {
+                            int y0, int W, int H, int mx = 0, int my = 0) {
   constexpr int ntasks = (kTH >> 3) * kTW;
+  const int ox = mx + dx, oy = my + dy;
   for (int i = tid; i < ntasks; i += kThreads) {
     const int x = i % kTW, ys = i / kTW * 8;
     const int px = x0 + x, py = y0 + ys;
-    const bool col_ok = px < W && px + dx >= 0 && px + dx < W;
+    const bool col_ok = px < W && px + ox >= 0 && px + ox < W;
     dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
-                   [=](int j) { return col_ok && py + j < H && py + j + dy >= 0 && py + j + dy < H; });
+                   [=](int j) { return col_ok && py + j < H && py + j + oy >= 0 && py + j + oy < H; });
   }
 }
 
@@ -399,10 +401,18 @@ G1S_DN_HD void dn_spatial(int tid, const TileGeom &g, const Layout &o, uint8_t *
 
 // after dn_spatial, the 2 D frames around the frame in hand (rules 5 - 7, 11t): nb(k) is the source of the k-th, absent
 // where the clip has no such frame -- the same for every thread of the workgroup.  The order of the neighbours does not
-// show in the result: the sums are exact.
-template <int S, int BPS, int NP, class Layout, class Nb, class Sync>
+// show in the result: the sums are exact.  mv(k) is the tile's motion vector towards the k-th (rule 19), the same for every
+// thread of the workgroup: the neighbour's tile is staged from the moved origin and one bounds test moves with it.
+struct MotionVec {
+  int x, y;
+};
+struct NoMotion {
+  G1S_DN_HD MotionVec operator()(int) const { return MotionVec{0, 0}; }
+};
+
+template <int S, int BPS, int NP, class Layout, class Nb, class Sync, class Mv = NoMotion>
 G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t *lds, int q, Nb nb, int nnb, int x0, int y0, Sync sync, uint32_t *aw,
-                           uint64_t *const (&au)[NP]) {
+                           uint64_t *const (&au)[NP], Mv mv = Mv()) {
   const int LP = dn_lp(o);
   uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + o.offH);
   uint16_t *L = reinterpret_cast<uint16_t *>(lds + o.offL), *Wb = reinterpret_cast<uint16_t *>(lds + o.offW),
@@ -412,13 +422,14 @@ G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t 
     static_assert(decltype(n)::NP == NP, "a neighbour has the frame's planes");
     if (!n.present()) continue;
     sync();  // the last dn_accumulate_t has read N
-    n.template stage<BPS>(tid, g, LP, N, x0, y0);
+    const MotionVec m = mv(k);
+    n.template stage<BPS>(tid, g, LP, N, x0 + m.x, y0 + m.y);
     sync();
     for (int dy = -g.A; dy <= g.A; ++dy)
       for (int dx = -g.A; dx <= g.A; ++dx) {
         dn_hsum_t<S, decltype(n)::NA>(tid, g, LP, L, N, Hb, dx, dy);
         sync();
-        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h());
+        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h(), m.x, m.y);
         sync();
         dn_accumulate_t<NP>(tid, g, LP, N, Wb, dx, dy, aw, au);
       }
@@ -472,6 +483,175 @@ G1S_DN_HD void dn_tile_jt(int tid, const TileGeom &g, const JointGeom &jg, uint8
 #pragma unroll
   for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
   dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur});
+  dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
+  dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
+}
+
+// ---- motion (rules 16 - 20): one vector per tile and neighbour frame ------------------------------------------------------
+// The filter's tiles are the motion blocks.  kd_motion finds a block's vector towards one neighbour on the search plane (the
+// rounded 2 x 2 box mean, rule 16: dn_stage_guide at xdec = ydec = 1), where a block is kMBW x kMBH samples.  In LDS
+//
+//   C   the block of u'_t, kMBW x kMBH u16 (what lies outside the search plane is staged clamped and never summed),
+//   Wd  the (kMBW + 2M) x (kMBH + 2M) window of u'_{t+k} around it, the search plane's edges replicated,
+//   K   a 64-bit key a thread, P one a group of 16 threads,
+//
+// C and Wd once per plane that takes part (NA = 2: Cb and Cr of a joint chroma tile, whose SADs add, rule 20).  The (2M + 1)^2
+// candidates are dealt to the threads by `tid`; a thread keeps a row of C in registers and walks its candidates' rows of Wd.
+// The minimum of rule 18's key is exact, so the order of the reduction cannot show.
+constexpr int kMBW = kTW / 2, kMBH = kTH / 2;
+constexpr int kMaxM = 32;  // on the search plane; the motion range is 2 M
+constexpr int kMaxCand = ((2 * kMaxM + 1) * (2 * kMaxM + 1) + kThreads - 1) / kThreads;  // candidates a thread
+constexpr int kKeyGroup = 16;
+
+struct MotionGeom {
+  int M, WW, WH, WS;  // the window: WH rows of WW samples, row stride WS (u16)
+  int LPc, LPw;       // samples from one plane's C / Wd to the next
+  int offC, offW, offK, offP, bytes;
+};
+
+G1S_DN_HD MotionGeom motion_geom(int M, int NA) {
+  MotionGeom m;
+  m.M = M, m.WW = kMBW + 2 * M, m.WH = kMBH + 2 * M;
+  m.WS = m.WW | 1;
+  m.LPc = kMBW * kMBH, m.LPw = (m.WS * m.WH + 7) & ~7;
+  m.offC = 0;
+  m.offW = m.offC + NA * m.LPc * 2;
+  m.offK = (m.offW + NA * m.LPw * 2 + 15) & ~15;
+  m.offP = m.offK + kThreads * 8;
+  m.bytes = m.offP + kKeyGroup * 8;
+  return m;
+}
+
+// what a motion block is searched on: the NA planes (W x H each) of frame t and of frame t + k
+struct MotionPlanes {
+  const uint8_t *p[2];
+  uint32_t stride[2];
+};
+
+// rule 16 into `dst`: rows x cols samples of the search plane of a W x H plane from (x0, y0), coordinates clamped to it
+template <int BPS>
+G1S_DN_HD void dn_stage_half(int tid, uint16_t *dst, int rows, int cols, int stride, const uint8_t *in, uint32_t in_stride, int W, int H, int x0,
+                             int y0) {
+  TileGeom g{};
+  g.R = 0, g.LH = rows, g.LW = cols, g.LS = stride;
+  dn_stage_guide<BPS>(tid, g, dst, in, in_stride, W, H, 1, 1, (W + 1) >> 1, (H + 1) >> 1, x0, y0);
+}
+
+// SAD of rule 17 for the thread's candidates over the block's bw x bh samples; RAGGED: bw < kMBW.  sad[j] is candidate
+// tid + j kThreads, whose window starts at base[j]; nj candidates a thread are looked at.
+template <int NA, bool RAGGED>
+G1S_DN_HD void dn_motion_sad(const MotionGeom &m, const uint16_t *C, const uint16_t *Wd, int bw, int bh, int nj, const int *base, uint32_t *sad) {
+  for (int a = 0; a < NA; ++a)
+    for (int r = 0; r < bh; ++r) {
+      int c[kMBW];
+#pragma unroll
+      for (int x = 0; x < kMBW; ++x) c[x] = (int)C[a * m.LPc + r * kMBW + x];
+#pragma unroll
+      for (int j = 0; j < kMaxCand; ++j)
+        if (j < nj) {  // (the same for the whole workgroup)
+          const uint16_t *w = Wd + a * m.LPw + base[j] + r * m.WS;
+          uint32_t s = 0;
+#pragma unroll
+          for (int x = 0; x < kMBW; ++x) {
+            const int d = c[x] - (int)w[x];
+            const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
+            s += !RAGGED || x < bw ? ad : 0u;
+          }
+          sad[j] += s;
+        }
+    }
+}
+
+// rule 18's key of a candidate (cx, cy) = m' + (M, M)
+G1S_DN_HD uint64_t dn_motion_key(uint32_t sad, int cx, int cy, int M) {
+  const int ax = cx < M ? M - cx : cx - M, ay = cy < M ? M - cy : cy - M;
+  return ((uint64_t)sad << 21) | ((uint64_t)(ax + ay) << 14) | ((uint64_t)cy << 7) | (uint64_t)cx;
+}
+
+// the vector of the block at (bx, by) (in blocks) of frame t towards frame t + k, for thread `tid` of a workgroup whose
+// barrier is `sync`: mv[0], mv[1] = (mx, my) in full-resolution samples
+template <int BPS, int NA, class Sync>
+G1S_DN_HD void dn_motion_tile(int tid, const MotionGeom &m, uint8_t *lds, const MotionPlanes &cur, const MotionPlanes &ref, int W, int H, int bx,
+                              int by, Sync sync, int8_t *mv) {
+  uint16_t *C = reinterpret_cast<uint16_t *>(lds + m.offC), *Wd = reinterpret_cast<uint16_t *>(lds + m.offW);
+  uint64_t *K = reinterpret_cast<uint64_t *>(lds + m.offK), *P = reinterpret_cast<uint64_t *>(lds + m.offP);
+  const int x0 = bx * kMBW, y0 = by * kMBH;
+  const int bw = imin(kMBW, ((W + 1) >> 1) - x0), bh = imin(kMBH, ((H + 1) >> 1) - y0);
+  for (int a = 0; a < NA; ++a) {
+    dn_stage_half<BPS>(tid, C + a * m.LPc, kMBH, kMBW, kMBW, cur.p[a], cur.stride[a], W, H, x0, y0);
+    dn_stage_half<BPS>(tid, Wd + a * m.LPw, m.WH, m.WW, m.WS, ref.p[a], ref.stride[a], W, H, x0 - m.M, y0 - m.M);
+  }
+  sync();
+  const int n1 = 2 * m.M + 1, ncand = n1 * n1, nj = (ncand + kThreads - 1) / kThreads;
+  uint32_t sad[kMaxCand];
+  int base[kMaxCand];
+#pragma unroll
+  for (int j = 0; j < kMaxCand; ++j) {
+    const int i = tid + j * kThreads, ii = i < ncand ? i : 0, cy = ii / n1;  // (a thread without a j-th candidate walks the first)
+    base[j] = cy * m.WS + (ii - cy * n1), sad[j] = 0;
+  }
+  if (bw < kMBW) dn_motion_sad<NA, true>(m, C, Wd, bw, bh, nj, base, sad);
+  else dn_motion_sad<NA, false>(m, C, Wd, bw, bh, nj, base, sad);
+  uint64_t best = ~(uint64_t)0;
+#pragma unroll
+  for (int j = 0; j < kMaxCand; ++j) {
+    const int i = tid + j * kThreads;
+    if (i < ncand) {
+      const int cy = i / n1;
+      const uint64_t key = dn_motion_key(sad[j], i - cy * n1, cy, m.M);
+      best = key < best ? key : best;
+    }
+  }
+  K[tid] = best;
+  sync();
+  if (tid < kKeyGroup) {
+    uint64_t b = K[tid * (kThreads / kKeyGroup)];
+    for (int i = 1; i < kThreads / kKeyGroup; ++i) {
+      const uint64_t k = K[tid * (kThreads / kKeyGroup) + i];
+      b = k < b ? k : b;
+    }
+    P[tid] = b;
+  }
+  sync();
+  if (tid == 0) {
+    uint64_t b = P[0];
+    for (int i = 1; i < kKeyGroup; ++i) b = P[i] < b ? P[i] : b;
+    mv[0] = (int8_t)(2 * ((int)(b & 127) - m.M)), mv[1] = (int8_t)(2 * ((int)((b >> 7) & 127) - m.M));
+  }
+}
+
+// the temporal tile functions under motion (what kd_nlm_tm and kd_nlm_jtm call): `mv` is the tile's vectors, a pair of
+// int8 for each of the nnb neighbours, `mv_stride` bytes from one neighbour's to the next
+struct TileVectors {
+  const int8_t *mv;
+  int stride;
+  G1S_DN_HD MotionVec operator()(int k) const { return MotionVec{(int)mv[k * stride], (int)mv[k * stride + 1]}; }
+};
+
+template <int S, int BPS, class Sync>
+G1S_DN_HD void dn_tile_tm(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride,
+                          const uint8_t *const *nb, const uint32_t *nb_stride, int nnb, const int8_t *mv, int mv_stride, uint8_t *out,
+                          uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
+  uint32_t aw[kSPT], au32[kSPT];
+  dn_spatial<S, BPS>(tid, g, g, lds, table, q, PlaneSrc{in, in_stride, W, H}, x0, y0, sync, aw, {au32});
+  uint64_t au[kSPT];
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) au[j] = au32[j];
+  dn_temporal<S, BPS>(tid, g, g, lds, q, [=](int k) { return PlaneSrc{nb[k], nb_stride[k], W, H}; }, nnb, x0, y0, sync, aw, {au},
+                      TileVectors{mv, mv_stride});
+  dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
+}
+
+template <int S, int BPS, class Nb, class Sync>
+G1S_DN_HD void dn_tile_jtm(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+                           Nb nb, int nnb, const int8_t *mv, int mv_stride, const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride,
+                           uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0, Sync sync) {
+  uint32_t aw[kSPT], aub32[kSPT], aur32[kSPT];
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32});
+  uint64_t aub[kSPT], aur[kSPT];
+#pragma unroll
+  for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
+  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur}, TileVectors{mv, mv_stride});
   dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
   dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }

@@ -10,6 +10,7 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 >>> Denoiser(10, joint_chroma=True).apply([y, u, v])   # Cb and Cr share one weight, guided by the luma at the same place
 >>> Denoiser(10, curve=grain_curve(segments, 10)).apply([y, u, v])   # luma strength follows a grain table's scaling function
 >>> denoise_y4m_file("grainy.y4m", "clean.y4m", grain_prior="first_pass.tbl")
+>>> Denoiser(10, temporal_radius=1, motion_range=32).denoise_clip(frames)   # a pan: each tile reads its neighbours where it finds them
 """
 from __future__ import annotations
 
@@ -81,25 +82,36 @@ class Denoiser(FrameOp):
 
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                  strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
-                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None):
+                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None, motion_range: int = 0):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
         runs over the D frames before and the D frames after it that the clip has.  joint_chroma: the two chroma planes
         share one weight, taken from Cb, Cr and the input luma at chroma resolution (rules 8 - 11 of include/g1s_diff.h);
         luma, and a luma-only frame, are filtered as without it.  curve = (fwd, inv) of grain_curve(): luma is filtered in
-        the domain where the prior's grain has one size at every intensity (rules 12 - 15); chroma as without it."""
+        the domain where the prior's grain has one size at every intensity (rules 12 - 15); chroma as without it.
+        motion_range Mr (even, 0..64, needs a temporal radius): every 64 x 48 tile gets one vector of up to Mr samples each
+        way towards every neighbour frame, found by a coarse search on the device, and reads the neighbour there (rules
+        16 - 20); 0 is the filter without it."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal_radius = temporal_radius
         self.joint_chroma = bool(joint_chroma)
+        self.motion_range = motion_range
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
-        if curve is None:
+        if curve is None and motion_range:
+            self._h = self._L.g1s_denoise_new_motion(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), None, None,
+                                                     motion_range & 0xFFFFFFFF)
+        elif curve is None:
             self._h = self._L.g1s_denoise_new_ex(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma))
         else:
             fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
             if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
                 raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
-            self._h = self._L.g1s_denoise_new_curve(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
-                                                    inv.ctypes.data)
+            if motion_range:
+                self._h = self._L.g1s_denoise_new_motion(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
+                                                         inv.ctypes.data, motion_range & 0xFFFFFFFF)
+            else:
+                self._h = self._L.g1s_denoise_new_curve(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
+                                                        inv.ctypes.data)
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
@@ -139,6 +151,25 @@ class Denoiser(FrameOp):
         self._check(self._L.g1s_denoise_sync(self._h))
         self._keep.clear()
 
+    def motion_vectors(self, cur: Sequence, ref: Sequence, xdec: int = 1, ydec: int = 1) -> List[np.ndarray]:
+        """Stage 1 alone: the vectors of frame `cur` towards frame `ref` (rules 16 - 18 and 20), one int16 array of shape
+        (block rows, block columns, 2) a plane, (mx, my) in full-resolution samples of that plane.  Under joint_chroma the two
+        chroma planes carry the same shared vectors.  Does not touch a clip in progress."""
+        a, b, keep, fa, fb = self._frame_pair(cur, xdec, ydec, list(ref))
+        shapes = [(-(-p.shape[0] // 48), -(-p.shape[1] // 64)) for p in a]
+        mv = [np.zeros(s + (2,), np.int16) for s in shapes]
+        ptrs = (C.c_void_p * 3)(*[m.ctypes.data for m in mv])
+        caps = (C.c_size_t * 3)(*[s[0] * s[1] for s in shapes])
+        self._check(self._L.g1s_denoise_motion_search(self._h, C.byref(fa), C.byref(fb), ptrs, caps))
+        del keep
+        return mv
+
+    def motion_time(self) -> float:
+        """ms in kd_motion of the timed batches so far (a part of kernel_times()' first value)."""
+        a = C.c_double()
+        self._L.g1s_denoise_motion_time(self._h, C.byref(a))
+        return a.value
+
     def kernel_times(self, enable: bool = True):
         """(ms in kd_nlm / kd_nlm_t and their joint chroma forms -- with a curve also the two kd_curve launches -- , frames) of the timed batches
         so far (HIP events); enables / disables the timing."""
@@ -149,17 +180,22 @@ class Denoiser(FrameOp):
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                      strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
-                     grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None) -> int:
+                     grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
-    function the luma strength follows (grain_curve() with prior_range and prior_segment).  Returns the number of frames."""
+    function the luma strength follows (grain_curve() with prior_range and prior_segment).  motion_range: as Denoiser takes
+    it.  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
     if grain_prior is None and (prior_range or prior_segment is not None):
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
-    n = L.g1s_denoise_y4m_file_curve(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
-                                     str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF,
-                                     -1 if prior_segment is None else prior_segment, err, len(err))
+    prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
+    if motion_range:
+        n = L.g1s_denoise_y4m_file_motion(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                          motion_range & 0xFFFFFFFF, err, len(err))
+    else:
+        n = L.g1s_denoise_y4m_file_curve(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                         err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

@@ -519,7 +519,30 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *      rule 8's guide stays the unstabilised input luma.  A 12-bit clip has no headroom in 12-bit kernels and is refused.
  * With a curve the denoiser keeps (2 batch_frames + 2 D) 12-bit u16 luma planes on the device; the caller's input luma is
  * never written.
- * No motion compensation, no dithering.  Samples above the bit depth's maximum are the caller's error.
+ * Motion (g1s_denoise_new_motion): rules 5 - 7 work while the picture stands still to within A; on a pan the neighbour
+ * frames hold the right samples further away.  With a motion range Mr (full-resolution samples of the plane, even, 0 .. 64;
+ * M = Mr / 2; Mr = 0 is the filter of rules 1 - 15) every tile of the filter gets one integer vector towards every
+ * neighbour frame, found by a coarse search, and rule 6 reads the neighbour there.  Integers throughout:
+ *  16. The search plane.  For a W x H plane u, u' is w' x h' with w' = (W + 1) >> 1, h' = (H + 1) >> 1; u'(x, y) =
+ *      (u(min(2x, W-1), min(2y, H-1)) + u(min(2x+1, W-1), min(2y, H-1)) + u(min(2x, W-1), min(2y+1, H-1)) +
+ *      u(min(2x+1, W-1), min(2y+1, H-1)) + 2) >> 2: rule 8's box at xdec = ydec = 1.
+ *  17. Motion blocks are the filter's tiles: 64 x 48 samples aligned at the plane's origin, 32 x 24 on the search plane,
+ *      ragged at the right and bottom edges.  For frame t, neighbour k != 0, block b and every candidate m' = (mx', my')
+ *      with |mx'|, |my'| <= M: SAD(m') = the sum over the block's search-plane samples p' inside w' x h' of
+ *      |u'_t(p') - u'_{t+k}(clamp(p' + m'))|, the clamp to the search plane's edges.  Every (t, k) is searched directly,
+ *      never by chaining vectors.
+ *  18. The vector minimises key = SAD 2^21 + (|mx'| + |my'|) 2^14 + (my' + M) 2^7 + (mx' + M).  SAD <= 768 x 4095 < 2^22
+ *      (twice that for rule 20's pair): the key fits 64 bits and is injective -- no ties, and the zero vector wins among
+ *      equal SADs.  m_{t,k}(b) = 2 m'.
+ *  19. Rule 6 under motion.  For p in block b and m = m_{t,k}(b): D_k(p, d) = sum over |kx|, |ky| <= S of (u_t(clamp(p + k)) -
+ *      u_{t+k}(clamp(p + m + d + k)))^2; (p, d, k) takes part only if p + m + d lies inside the plane; the sample averaged
+ *      in is u_{t+k}(p + m + d).  Rules 5 and 7, the table, q and the 64-bit numerator are unchanged.
+ *  20. Every plane searches on its own samples and its own grid.  Under G1S_DENOISE_JOINT_CHROMA a chroma tile has one
+ *      vector for Cb, Cr and the guide: its SAD is the sum of Cb's and Cr's, the guide takes no part in the search, and the
+ *      guide of frame t + k is staged at the moved place by rule 8 as it stands.  With a grain prior the luma search runs
+ *      on the stabilised 12-bit planes, which are what the filter filters.
+ * Sub-tile and sub-sample vectors, smoothing of the vector field and scene-cut detection are not part of it.
+ * No dithering.  Samples above the bit depth's maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes -- under the flag one workgroup filters both) on the denoiser's own stream.  A workgroup's LDS grows
  * with A, S, a temporal radius and the flag; a parameter set that needs more than the device gives a workgroup is
@@ -551,6 +574,22 @@ g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *
  * g1s_denoise_new* call is the case without a curve. */
 g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                      const uint16_t *fwd, const uint16_t *inv);
+/* The same with a motion range (rules 16 - 20).  fwd = inv = NULL: no curve.  motion_range = 0 is g1s_denoise_new_curve
+ * (or, without a curve, g1s_denoise_new_ex): the same launches, the same bytes.  Two more refusals, checked before a
+ * device is looked for: "motion_range must be even and 0..64" and, for a range above 0 with temporal radius 0,
+ * "motion_range needs a temporal radius".  The vectors are found on the denoiser's stream in front of each batch's
+ * filter launches (kd_motion) and kept on the device: 2 D pairs of int8 a tile and plane. */
+g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                      const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range);
+/* Stage 1 alone (rules 16 - 18, 20), as g1s_grain_templates is for render: the vectors of frame `cur` towards frame `ref`
+ * of the same geometry, for a denoiser made with a motion range.  mv[c] takes plane c's vectors as pairs (mx, my) in
+ * full-resolution samples of that plane, blocks in raster order; cap_pairs[c] is its capacity in pairs going in and the
+ * plane's block count coming out (G1S_ERR_CAPACITY, nothing written, when one is too small).  Under the joint flag planes
+ * 1 and 2 carry the same shared vectors.  Frames follow on_device as elsewhere; the call waits for the denoiser's stream
+ * and does not touch a clip in progress. */
+int g1s_denoise_motion_search(g1s_denoise_t *, const g1s_frame_t *cur, const g1s_frame_t *ref, int16_t *mv[3], size_t cap_pairs[3]);
+/* ms spent in kd_motion by the timed batches so far (a part of g1s_denoise_set_timing's ms_kernel). */
+int g1s_denoise_motion_time(g1s_denoise_t *, double *ms_motion);
 /* Rules 12 and 13: the pair (f, g) for the luma scaling functions of n >= 1 segments of a grain table, range R (0 = the
  * default).  fwd: 1 << bit_depth entries, inv: 4096.  Host only: needs no device.  G1S_ERR_INVALID (reason from
  * g1s_last_global_error()) for bit_depth 12 or any other than 8 and 10, a range above 2^(12 - bit_depth), n = 0, and luma
@@ -603,6 +642,11 @@ int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoi
  * prior_tbl == NULL is g1s_denoise_y4m_file_ex. */
 int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, char *err, size_t cap);
+/* The same with a motion range (rules 16 - 20, as g1s_denoise_new_motion takes it); motion_range = 0 is
+ * g1s_denoise_y4m_file_curve. */
+int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err,
+                                    size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -623,6 +667,11 @@ int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const
 int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                      uint32_t prior_range, int32_t prior_segment, uint64_t *frames, char *err, size_t cap);
+/* The same with a motion range; motion_range = 0 is g1s_diff_y4m_file_denoised_curve. */
+int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint64_t *frames, char *err,
+                                      size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

@@ -11,7 +11,13 @@ rocprofv3 --kernel-trace --stats -- python tools/bench_denoise.py 1 (a run of it
 
 tools/bench_denoise.py [batches] --prior -- the cost of a grain prior (rules 12 - 15): both formats at the defaults with
 temporal radius 0 and 1, without and with a curve ("grain_prior" in the line) in one process.  With a curve the timed span
-also holds the two kd_curve launches around the luma launch; their own times come from the kernel trace."""
+also holds the two kd_curve launches around the luma launch; their own times come from the kernel trace.
+
+tools/bench_denoise.py [batches] --motion-range R[,R...] -- motion for the temporal radius (rules 16 - 20): 4K 10-bit 4:2:0 at
+the defaults with temporal radius 1, once for every range R of the list (0: the denoiser without motion, made by the calls
+that were there before it).  The timed span holds kd_motion in front of the filter launches; "kd_motion_us_per_frame" is its
+own HIP-event time, "filter_us_per_frame" the rest, "motion_candidate_samples" the count that explains the first: per
+frame, blocks x neighbours x (R + 1)^2 candidates x up to 768 search-plane samples."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +28,11 @@ from grav1synth_amd.synth import SynthSpec, make_pair
 assert torch.cuda.is_available(), "bench_denoise.py needs a GPU"
 PRIOR = "--prior" in sys.argv[1:]
 args = [a for a in sys.argv[1:] if a != "--prior"]
+MOTION = None
+if "--motion-range" in args:
+    i = args.index("--motion-range")
+    MOTION = [int(r) for r in args[i + 1].split(",")]
+    del args[i:i + 2]
 batches = int(args[0]) if args else 4
 BATCH = 64
 if PRIOR:
@@ -31,17 +42,23 @@ if PRIOR:
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference-example-table.tbl"), "rb") as f:
         PRIOR_SEGMENTS = parse_tbl(f.read())
     CASES = [(3, 2, d, False, c) for d in (0, 1) for c in (False, True)]
+elif MOTION is not None:
+    CASES = [(3, 2, 1, False, False, r) for r in MOTION]
 else:
     CASES = [(a, s, d, j, False) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (7, 3, 1), (3, 2, 2)) for j in (False, True)]
 
-for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", SynthSpec(1920, 1080, 8))):
+FORMATS = (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", SynthSpec(1920, 1080, 8)))
+for name, spec in FORMATS[:1] if MOTION is not None else FORMATS:
     # 8 distinct noisy frames in, 64 distinct frames out (a batch writes every out plane once)
     ins = [make_pair(spec, k, device="cuda")[0] for k in range(8)]
     outs = [[torch.empty_like(p) for p in ins[0]] for _ in range(BATCH)]
     torch.cuda.synchronize()
     samples = sum(p.numel() for p in ins[0])
-    for A, S, D, joint, prior in CASES:
+    for A, S, D, joint, prior, *rest in CASES:
         kw = dict(curve=grain_curve(PRIOR_SEGMENTS, spec.bit_depth)) if prior else {}
+        mr = rest[0] if rest else 0
+        if mr:
+            kw["motion_range"] = mr
         dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint, **kw)
 
         def run(nb):
@@ -56,6 +73,7 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
         dn.kernel_times(True)
         run(batches)
         ms, fr = dn.kernel_times(False)
+        ms_motion = dn.motion_time() if mr else 0.0
         dn.close()
         pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
@@ -64,4 +82,7 @@ for name, spec in (("3840x2160 10-bit 4:2:0", SynthSpec(3840, 2160, 10)), ("1920
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
             "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
             "job_frames_per_s_untimed": batches * BATCH / dt,
+            **({"motion_range": mr, "kd_motion_us_per_frame": ms_motion * 1e3 / fr, "filter_us_per_frame": (ms - ms_motion) * 1e3 / fr,
+                "motion_candidate_samples": sum(-(-p.shape[0] // 48) * -(-p.shape[1] // 64) * min(p.shape[0] + 1 >> 1, 24) * min(p.shape[1] + 1 >> 1, 32)
+                                                for p in ins[0]) * 2 * D * (mr + 1) ** 2} if MOTION is not None else {}),
         }), flush=True)
