@@ -102,7 +102,13 @@ int w_wgs_per_frame(int ncell, int B, int kind) {
   const int gmin = (ncell + cap - 1) / cap;
   const char *e = getenv(kind ? "G1S_W_WGS_C" : "G1S_W_WGS");  // tuning / test aid
   int target = std::max(kMTargetWgs, (kind ? 16 : 32) * B);
-  if (e) target = std::max(8, atoi(e));
+  if (e) {
+    // (1 .. 7: that many workgroups a FRAME, as they are: slices of a few units on frames of a handful of units, for the tests of a
+    //  slice's ends -- tests/test_gpu_k3w_slices.py; anything else is a launch's workgroups, as it always was)
+    const int v = atoi(e);
+    if (v >= 1 && v < 8) return std::max(gmin, v);
+    target = std::max(8, v);
+  }
   int G = (std::max(gmin, (target + B - 1) / std::max(B, 1)) + 7) & ~7;
   // (luma launch of a small frame: slices of at least 64 cells -- a slice pays two ghost units, its entries' parking and a partial
   //  system whatever its length -- as long as a launch still has a workgroup for every slot of the chip.  1080p, 128 frames a

@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "k3m.hip.h"
 #include "kernels.hip.h"
 
@@ -497,418 +499,428 @@ __global__ __launch_bounds__(kWThreads, KIND == 1 ? (SY == 0 ? 2 : G1S_W_OCC_C) 
   if (tid < 4) s_bad[tid] = 0u;
   __syncthreads();
 
-  // ---- pipeline registers ----
-  w_u4 rs[NOWN][2], rv[NOWN][2];                      // raw words in flight: own iterations
-  w_u4 hs = {}, hv = {};                              // ... the halo row
-  uint32_t Dc[NOWN][2][2] = {}, Dn[NOWN][2][2] = {}, Dl[NOWN][2] = {};   // residual words: unit k, unit k + 1; last dwords of unit k - 1
-  uint32_t Hc[2] = {}, Hn[2] = {}, Hl = 0;
+  // What follows is compiled twice: for the waves that stage a halo row (HW) and for those that do not.  Under a run-time
+  // `if (h_wave)` the halo row's raw words and residual words were values that merge at every join of the loop: sixteen register
+  // copies a unit around the loads, on every wave, and four tests of the flag (profiles/k3w_loop_overhead.txt).
+  auto pass = [&](auto hw_) __attribute__((always_inline)) {
+    constexpr bool HW = decltype(hw_)::value;
+    // ---- pipeline registers ----
+    w_u4 rs[NOWN][2], rv[NOWN][2];                      // raw words in flight: own iterations
+    w_u4 hs = {}, hv = {};                              // ... the halo row
+    uint32_t Dc[NOWN][2][2] = {}, Dn[NOWN][2][2] = {}, Dl[NOWN][2] = {};   // residual words: unit k, unit k + 1; last dwords of unit k - 1
+    uint32_t Hc[2] = {}, Hn[2] = {}, Hl = 0;
 
-  auto entry_x = [&](int j) -> uint32_t { return __builtin_amdgcn_readfirstlane(s_ent[2 * (j + 1)].x); };
+    auto entry_x = [&](int j) -> uint32_t { return __builtin_amdgcn_readfirstlane(s_ent[2 * (j + 1)].x); };
 
-  // the raw words of the unit with entry word ex, into rs / rv (and hs / hv)
-  // (16-bit planes are read with the non-temporal hint: a launch walks gigabytes it touches once, and read that way the lines the
-  //  finder's moments kernel left in the caches -- the luma source of the batch's last frames -- survive until this launch asks
-  //  for them.  4K 10-bit: luma launch 391 -> 377 us, chroma 220 -> 212 with its L tiles read the same way; all-flat 578 -> 560,
-  //  324 -> 305.  A 1080p 8-bit batch is about the size of the Infinity Cache: plain loads there (178 vs 184 us).
-  //  profiles/r05e_nontemporal.txt)
-  auto load8 = [&](const uint8_t *base, uint32_t off, bool wide) __attribute__((always_inline)) -> w_u4 {
-    w_u4 r = {0u, 0u, 0u, 0u};
-    asm volatile("" : "+v"(off));  // (opaque: scalar base + 32-bit lane offset, not a 64-bit lane address)
-    if (wide) {
-      r = __builtin_nontemporal_load((gptr_u4)(as_global(base) + off));
-    } else {
-      const u32x2 a = *(gptr_u2)(as_global(base) + off);
-      r.x = a.x, r.y = a.y;
-    }
-    return r;
-  };
-  // (buffer form of the same loads for the units that lie inside the plane: descriptor of the plane in SGPRs, the lane's constant
-  //  offset as the instruction's VGPR offset, the row's 32-bit offset from the plane's origin as its SGPR offset -- no 64-bit
-  //  address arithmetic a row and no copy of the lane offset into the destination registers)
-  const __amdgpu_buffer_rsrc_t bsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(psrc), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t bden = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(pden), 0, 0x7fffffff, 0x00020000);
-  auto bload8 = [&](__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, bool wide) __attribute__((always_inline)) -> w_u4 {
-    w_u4 r = {0u, 0u, 0u, 0u};
-    if (wide) {
-      r = __builtin_bit_cast(w_u4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 2));  // (aux 2: non-temporal)
-    } else {
-      const w_u2 a = __builtin_bit_cast(w_u2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, (int)soff, 0));
-      r.x = a.x, r.y = a.y;
-    }
-    return r;
-  };
-  auto request = [&](uint32_t ex) __attribute__((always_inline)) {
-    const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
-    const int X0 = c * kWUnitW, Y0 = by * BH - 4;
-    if ((ex >> 25) & 1u) {  // every row and word of the tile inside the plane (Y0 >= 0)
-      const uint32_t so_s = (uint32_t)Y0 * sst + (uint32_t)(X0 * BPS), so_v = (uint32_t)Y0 * dst_ + (uint32_t)(X0 * BPD);
-#pragma unroll
-      for (int i = 0; i < NOWN; ++i)
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          rs[i][r] = bload8(bsrc, lo_s, so_s + (uint32_t)(8 * i + r) * sst, BPS == 2);
-          rv[i][r] = bload8(bden, lo_v, so_v + (uint32_t)(8 * i + r) * dst_, BPD == 2);
-        }
-      if (h_wave) {
-        hs = bload8(bsrc, lo_hs, so_s, BPS == 2);
-        hv = bload8(bden, lo_hv, so_v, BPD == 2);
+    // the raw words of the unit with entry word ex, into rs / rv (and hs / hv)
+    // (16-bit planes are read with the non-temporal hint: a launch walks gigabytes it touches once, and read that way the lines the
+    //  finder's moments kernel left in the caches -- the luma source of the batch's last frames -- survive until this launch asks
+    //  for them.  4K 10-bit: luma launch 391 -> 377 us, chroma 220 -> 212 with its L tiles read the same way; all-flat 578 -> 560,
+    //  324 -> 305.  A 1080p 8-bit batch is about the size of the Infinity Cache: plain loads there (178 vs 184 us).
+    //  profiles/r05e_nontemporal.txt)
+    auto load8 = [&](const uint8_t *base, uint32_t off, bool wide) __attribute__((always_inline)) -> w_u4 {
+      w_u4 r = {0u, 0u, 0u, 0u};
+      asm volatile("" : "+v"(off));  // (opaque: scalar base + 32-bit lane offset, not a 64-bit lane address)
+      if (wide) {
+        r = __builtin_nontemporal_load((gptr_u4)(as_global(base) + off));
+      } else {
+        const u32x2 a = *(gptr_u2)(as_global(base) + off);
+        r.x = a.x, r.y = a.y;
       }
-      return;
-    }
-    // (scalar origin + the lane's constant offset)
-    const uint8_t *sb = psrc + ((ptrdiff_t)Y0 * (ptrdiff_t)sst + (ptrdiff_t)(X0 * BPS));
-    const uint8_t *vb = pden + ((ptrdiff_t)Y0 * (ptrdiff_t)dst_ + (ptrdiff_t)(X0 * BPD));
-    {
-      const bool xok = X0 + 8 * w + 8 <= pw;
+      return r;
+    };
+    // (buffer form of the same loads for the units that lie inside the plane: descriptor of the plane in SGPRs, the lane's constant
+    //  offset as the instruction's VGPR offset, the row's 32-bit offset from the plane's origin as its SGPR offset -- no 64-bit
+    //  address arithmetic a row and no copy of the lane offset into the destination registers)
+    const __amdgpu_buffer_rsrc_t bsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(psrc), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t bden = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(pden), 0, 0x7fffffff, 0x00020000);
+    auto bload8 = [&](__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, bool wide) __attribute__((always_inline)) -> w_u4 {
+      w_u4 r = {0u, 0u, 0u, 0u};
+      if (wide) {
+        r = __builtin_bit_cast(w_u4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 2));  // (aux 2: non-temporal)
+      } else {
+        const w_u2 a = __builtin_bit_cast(w_u2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)voff, (int)soff, 0));
+        r.x = a.x, r.y = a.y;
+      }
+      return r;
+    };
+    auto request = [&](uint32_t ex) __attribute__((always_inline)) {
+      const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
+      const int X0 = c * kWUnitW, Y0 = by * BH - 4;
+      if ((ex >> 25) & 1u) {  // every row and word of the tile inside the plane (Y0 >= 0)
+        const uint32_t so_s = (uint32_t)Y0 * sst + (uint32_t)(X0 * BPS), so_v = (uint32_t)Y0 * dst_ + (uint32_t)(X0 * BPD);
 #pragma unroll
-      for (int i = 0; i < NOWN; ++i)
+        for (int i = 0; i < NOWN; ++i)
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int t = 4 + own_row0 + 8 * i + 2 * p + r;
-          rs[i][r] = w_u4{0u, 0u, 0u, 0u};
-          rv[i][r] = w_u4{0u, 0u, 0u, 0u};
-          if (xok && Y0 + t < ph) {
-            rs[i][r] = load8(sb + (size_t)(8 * i + r) * sst, lo_s, BPS == 2);
-            rv[i][r] = load8(vb + (size_t)(8 * i + r) * dst_, lo_v, BPD == 2);
+          for (int r = 0; r < 2; ++r) {
+            rs[i][r] = bload8(bsrc, lo_s, so_s + (uint32_t)(8 * i + r) * sst, BPS == 2);
+            rv[i][r] = bload8(bden, lo_v, so_v + (uint32_t)(8 * i + r) * dst_, BPD == 2);
+          }
+        if constexpr (HW) {
+          hs = bload8(bsrc, lo_hs, so_s, BPS == 2);
+          hv = bload8(bden, lo_hv, so_v, BPD == 2);
+        }
+        return;
+      }
+      // (scalar origin + the lane's constant offset)
+      const uint8_t *sb = psrc + ((ptrdiff_t)Y0 * (ptrdiff_t)sst + (ptrdiff_t)(X0 * BPS));
+      const uint8_t *vb = pden + ((ptrdiff_t)Y0 * (ptrdiff_t)dst_ + (ptrdiff_t)(X0 * BPD));
+      {
+        const bool xok = X0 + 8 * w + 8 <= pw;
+#pragma unroll
+        for (int i = 0; i < NOWN; ++i)
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            const int t = 4 + own_row0 + 8 * i + 2 * p + r;
+            rs[i][r] = w_u4{0u, 0u, 0u, 0u};
+            rv[i][r] = w_u4{0u, 0u, 0u, 0u};
+            if (xok && Y0 + t < ph) {
+              rs[i][r] = load8(sb + (size_t)(8 * i + r) * sst, lo_s, BPS == 2);
+              rv[i][r] = load8(vb + (size_t)(8 * i + r) * dst_, lo_v, BPD == 2);
+            }
+          }
+        if constexpr (HW) {
+          hs = w_u4{0u, 0u, 0u, 0u};
+          hv = w_u4{0u, 0u, 0u, 0u};
+          if (xok && Y0 + ph_ >= 0 && Y0 + ph_ < ph) {
+            hs = load8(sb, lo_hs, BPS == 2);
+            hv = load8(vb, lo_hv, BPD == 2);
           }
         }
-      if (h_wave) {
-        hs = w_u4{0u, 0u, 0u, 0u};
-        hv = w_u4{0u, 0u, 0u, 0u};
-        if (xok && Y0 + ph_ >= 0 && Y0 + ph_ < ph) {
-          hs = load8(sb, lo_hs, BPS == 2);
-          hv = load8(vb, lo_hv, BPD == 2);
-        }
       }
-    }
-  };
-  // chroma launch: this thread's words of the unit's L tile (BH rows of 128 bytes, one 8-byte word a thread and 16 rows)
-  w_u2 Lc[CHR ? (BH / 16) : 1];
-  (void)Lc;
-  auto load_L = [&](uint32_t ex) __attribute__((always_inline)) {
-    if constexpr (CHR) {
-      const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
-      const uint32_t so = (uint32_t)(by * BH) * wp.lpitch + (uint32_t)(c * kWUnitW);
+    };
+    // chroma launch: this thread's words of the unit's L tile (BH rows of 128 bytes, one 8-byte word a thread and 16 rows)
+    w_u2 Lc[CHR ? (BH / 16) : 1];
+    (void)Lc;
+    auto load_L = [&](uint32_t ex) __attribute__((always_inline)) {
+      if constexpr (CHR) {
+        const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
+        const uint32_t so = (uint32_t)(by * BH) * wp.lpitch + (uint32_t)(c * kWUnitW);
 #pragma unroll
-      for (int q = 0; q < BH / 16; ++q)
-        Lc[q] = __builtin_bit_cast(w_u2, __builtin_amdgcn_raw_buffer_load_b64(bL, (int)l_off[q], (int)so, BPS == 2 ? 2 : 0));  // (16-bit jobs: non-temporal)
-    }
-  };
+        for (int q = 0; q < BH / 16; ++q)
+          Lc[q] = __builtin_bit_cast(w_u2, __builtin_amdgcn_raw_buffer_load_b64(bL, (int)l_off[q], (int)so, BPS == 2 ? 2 : 0));  // (16-bit jobs: non-temporal)
+      }
+    };
 
-  // raw words -> residual words of the unit at sequence position j (D = Dn, H = Hn); REAL: statistics, L, flags of a unit
-  // of this workgroup's own (a ghost leaves nothing behind but its words and its edge flags)
-  auto form = [&](int j, uint32_t ex, bool real) __attribute__((always_inline)) {
-    const int slot = (j + 1) & 3;
-    uint32_t racc = 0, lacc = 0;
-    // (names the closure's captures in this order and does nothing else: the order decides how the compiler lays the closure out,
-    //  and with it the schedule of the unit loop -- this one is the schedule every measurement in profiles/ was taken on)
-    (void)Dn, (void)rs, (void)rv, (void)Hn, (void)hs, (void)hv;
+    // raw words -> residual words of the unit at sequence position j (D = Dn, H = Hn); REAL: statistics, L, flags of a unit
+    // of this workgroup's own (a ghost leaves nothing behind but its words and its edge flags)
+    auto form = [&](int j, uint32_t ex, bool real) __attribute__((always_inline)) {
+      const int slot = (j + 1) & 3;
+      uint32_t racc = 0, lacc = 0;
+      // (names the closure's captures in this order and does nothing else: the order decides how the compiler lays the closure out,
+      //  and with it the schedule of the unit loop -- this one is the schedule every measurement in profiles/ was taken on)
+      (void)Dn, (void)rs, (void)rv, (void)Hn, (void)hs, (void)hv;
 #pragma unroll
-    for (int i = 0; i < NOWN; ++i) {
-      uint32_t T[2][4];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        if constexpr (GEN) w_residual_gen<BPS, BPD>(rs[i][r], rv[i][r], ssh, g.den_shift, T[r], racc);
-        else w_residual<BPS>(rs[i][r], rv[i][r], ssh, r_km, r_bm, T[r], racc);
-        w_pack<LAY>(T[r], Dn[i][r][0], Dn[i][r][1]);
-        __builtin_amdgcn_sched_barrier(0);  // (row by row: the scheduler would otherwise keep both rows' temporaries alive)
-      }
-      if (real) {
-        int sd = 0, sd2 = 0;
+      for (int i = 0; i < NOWN; ++i) {
+        uint32_t T[2][4];
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          sd = __builtin_amdgcn_sdot4((int)Dn[i][r][0], 0x01010101, sd, false);
-          sd = __builtin_amdgcn_sdot4((int)Dn[i][r][1], 0x01010101, sd, false);
-          sd2 = __builtin_amdgcn_sdot4((int)Dn[i][r][0], (int)Dn[i][r][0], sd2, false);
-          sd2 = __builtin_amdgcn_sdot4((int)Dn[i][r][1], (int)Dn[i][r][1], sd2, false);
+          if constexpr (GEN) w_residual_gen<BPS, BPD>(rs[i][r], rv[i][r], ssh, g.den_shift, T[r], racc);
+          else w_residual<BPS>(rs[i][r], rv[i][r], ssh, r_km, r_bm, T[r], racc);
+          w_pack<LAY>(T[r], Dn[i][r][0], Dn[i][r][1]);
+          __builtin_amdgcn_sched_barrier(0);  // (row by row: the scheduler would otherwise keep both rows' temporaries alive)
         }
-        const unsigned long long pk = ((unsigned long long)(uint32_t)sd2 << 32) | (unsigned long long)(uint32_t)(sd + 16 * 128);
-        atomicAdd(&s_sum[slot][s_plane][w / SH::WPB], pk);
-        if constexpr (LOUT) {
-          // ---- the chroma regressor L of this lane's samples -> the L plane ----
-          const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
-          const uint32_t lso = (uint32_t)(by * SH::LBH) * wp.lpitch + (uint32_t)(c * (kWUnitW >> (SX > 0 ? 1 : 0)));
-          if (SX == 0 && SY == 0) {
+        if (real) {
+          int sd = 0, sd2 = 0;
 #pragma unroll
-            for (int r = 0; r < 2; ++r)
-              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(w_store2, w_u2{Dn[i][r][0], Dn[i][r][1]}), bL, (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
-            lacc = racc;  // (L is the residual itself: outside int8 exactly where the residual is)
-          } else {
+          for (int r = 0; r < 2; ++r) {
+            sd = __builtin_amdgcn_sdot4((int)Dn[i][r][0], 0x01010101, sd, false);
+            sd = __builtin_amdgcn_sdot4((int)Dn[i][r][1], 0x01010101, sd, false);
+            sd2 = __builtin_amdgcn_sdot4((int)Dn[i][r][0], (int)Dn[i][r][0], sd2, false);
+            sd2 = __builtin_amdgcn_sdot4((int)Dn[i][r][1], (int)Dn[i][r][1], sd2, false);
+          }
+          const unsigned long long pk = ((unsigned long long)(uint32_t)sd2 << 32) | (unsigned long long)(uint32_t)(sd + 16 * 128);
+          atomicAdd(&s_sum[slot][s_plane][w / SH::WPB], pk);
+          if constexpr (LOUT) {
+            // ---- the chroma regressor L of this lane's samples -> the L plane ----
+            const int c = (int)(ex & 0x3ffu), by = (int)((ex >> 10) & 0xfffu);
+            const uint32_t lso = (uint32_t)(by * SH::LBH) * wp.lpitch + (uint32_t)(c * (kWUnitW >> (SX > 0 ? 1 : 0)));
+            if (SX == 0 && SY == 0) {
 #pragma unroll
-            for (int r = 0; r < (SY ? 1 : 2); ++r) {
-              uint32_t V[4];
+              for (int r = 0; r < 2; ++r)
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(w_store2, w_u2{Dn[i][r][0], Dn[i][r][1]}), bL, (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
+              lacc = racc;  // (L is the residual itself: outside int8 exactly where the residual is)
+            } else {
 #pragma unroll
-              for (int q = 0; q < 4; ++q) V[q] = SY ? T[0][q] + T[1][q] : T[r][q];
-              constexpr uint32_t bias1 = SY ? 256u : 128u;
-              if (SX) {
-                uint32_t x01, x23;
-                if (LAY == 2) {
-                  uint32_t h[4];
+              for (int r = 0; r < (SY ? 1 : 2); ++r) {
+                uint32_t V[4];
 #pragma unroll
-                  for (int q = 0; q < 4; ++q) h[q] = V[q] + (V[q] >> 16);
-                  x01 = __builtin_amdgcn_perm(h[1], h[0], 0x05040100u);
-                  x23 = __builtin_amdgcn_perm(h[3], h[2], 0x05040100u);
+                for (int q = 0; q < 4; ++q) V[q] = SY ? T[0][q] + T[1][q] : T[r][q];
+                constexpr uint32_t bias1 = SY ? 256u : 128u;
+                if (SX) {
+                  uint32_t x01, x23;
+                  if (LAY == 2) {
+                    uint32_t h[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) h[q] = V[q] + (V[q] >> 16);
+                    x01 = __builtin_amdgcn_perm(h[1], h[0], 0x05040100u);
+                    x23 = __builtin_amdgcn_perm(h[3], h[2], 0x05040100u);
+                  } else {
+                    x01 = V[0] + V[1];
+                    x23 = V[2] + V[3];
+                  }
+                  constexpr uint32_t add = (640u - 2u * bias1) * 0x00010001u;
+                  const uint32_t y01 = x01 + add, y23 = x23 + add;  // halves: L + 640; inside int8 <=> high byte 2
+                  lacc |= (y01 ^ 0x02000200u) | (y23 ^ 0x02000200u);
+                  __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(y23, y01, 0x06040200u) ^ 0x80808080u, bL, (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
                 } else {
-                  x01 = V[0] + V[1];
-                  x23 = V[2] + V[3];
-                }
-                constexpr uint32_t add = (640u - 2u * bias1) * 0x00010001u;
-                const uint32_t y01 = x01 + add, y23 = x23 + add;  // halves: L + 640; inside int8 <=> high byte 2
-                lacc |= (y01 ^ 0x02000200u) | (y23 ^ 0x02000200u);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(y23, y01, 0x06040200u) ^ 0x80808080u, bL, (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
-              } else {
-                // (SY = 1, SX = 0: eight values a row pair, laid out like T)
-                constexpr uint32_t add = (640u - bias1) * 0x00010001u;
-                uint32_t y[4];
+                  // (SY = 1, SX = 0: eight values a row pair, laid out like T)
+                  constexpr uint32_t add = (640u - bias1) * 0x00010001u;
+                  uint32_t y[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  y[q] = V[q] + add;
-                  lacc |= y[q] ^ 0x02000200u;
+                  for (int q = 0; q < 4; ++q) {
+                    y[q] = V[q] + add;
+                    lacc |= y[q] ^ 0x02000200u;
+                  }
+                  constexpr uint32_t sel = LAY == 2 ? 0x06040200u : 0x06020400u;
+                  __builtin_amdgcn_raw_buffer_store_b64(
+                      __builtin_bit_cast(w_store2, w_u2{__builtin_amdgcn_perm(y[1], y[0], sel) ^ 0x80808080u, __builtin_amdgcn_perm(y[3], y[2], sel) ^ 0x80808080u}), bL,
+                      (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
                 }
-                constexpr uint32_t sel = LAY == 2 ? 0x06040200u : 0x06020400u;
-                __builtin_amdgcn_raw_buffer_store_b64(
-                    __builtin_bit_cast(w_store2, w_u2{__builtin_amdgcn_perm(y[1], y[0], sel) ^ 0x80808080u, __builtin_amdgcn_perm(y[3], y[2], sel) ^ 0x80808080u}), bL,
-                    (int)l_off[i], (int)(lso + (uint32_t)r * wp.lpitch), 0);
               }
             }
           }
         }
       }
-    }
-    uint32_t hacc = 0;
-    if (h_wave) {
-      uint32_t T[4];
-      if constexpr (GEN) w_residual_gen<BPS, BPD>(hs, hv, ssh, g.den_shift, T, hacc);
-      else w_residual<BPS>(hs, hv, ssh, r_km, r_bm, T, hacc);
-      w_pack<LAY>(T, Hn[0], Hn[1]);
-    }
-    // ---- residuals (or L) outside int8: rare; one wave-uniform test on the usual way ----
-    const uint32_t out = (racc | hacc | lacc) & 0xff00ff00u;
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(out != 0) != 0, 0)) {
-      const int sh0 = CHR ? 4 * s_plane : 0;
-      uint32_t bits = 0;
-      if ((racc & 0xff00ff00u) != 0) bits |= (1u | (w == 0 ? 2u : 0u) | (w == 15 ? 4u : 0u)) << sh0;
-      if ((lacc & 0xff00ff00u) != 0) bits |= 8u;
-      if ((hacc & 0xff00ff00u) != 0) bits |= (1u | (w == 0 ? 2u : 0u) | (w == 15 ? 4u : 0u)) << sh0;
-      if (!real) bits &= ~(1u | 16u | 8u);  // a ghost: only what its edge words mean to the neighbour
-      if (bits) atomicOr(&s_bad[slot], bits);
-    }
-  };
-
-  // the copies of unit k (Dc / Hc; left halo dwords Dl / Hl, right halo dwords in Dn / Hn) -> the tile buffer.
-  // The dword left of word w is word w - 1's second dword (row_shr:1; lane 0 of the row keeps what the first move put there: the
-  // unit before's last dword, rotated in from lane 15), the dword right of it word w + 1's first (row_shl:1; lane 15 likewise).
-  // (What lane 0 / lane 15 get when the unit has NO neighbour on that side -- words of some other unit, or zeros -- is never
-  //  multiplied into a sum: a block without a flat neighbour keeps `lag` columns from that edge out of its window, the window
-  //  masks the A operand, and a sample inside the window reads at most `lag` columns to its side: words of its own unit.  The
-  //  plain products need every block's whole window, i.e. real neighbours.  Round 4 zeroed them: two v_and a row.)
-  auto neighbours = [&](uint32_t dl, uint32_t d0, uint32_t d1, uint32_t dn0, uint32_t &prev1, uint32_t &next0)
-                        __attribute__((always_inline)) {
-    const int hl = __builtin_amdgcn_mov_dpp((int)dl, 0x121, 0xf, 0xf, true);   // row_ror:1:  lane 0 <- lane 15
-    const int hr = __builtin_amdgcn_mov_dpp((int)dn0, 0x12f, 0xf, 0xf, true);  // row_ror:15: lane 15 <- lane 0
-    prev1 = (uint32_t)__builtin_amdgcn_update_dpp(hl, (int)d1, 0x111, 0xf, 0xf, false);  // row_shr:1
-    next0 = (uint32_t)__builtin_amdgcn_update_dpp(hr, (int)d0, 0x101, 0xf, 0xf, false);  // row_shl:1
-  };
-  auto write_copies = [&](uint32_t ex) __attribute__((always_inline)) {
-    uint8_t *base = w_smem + (CHR && s_plane ? SH::OFF_P1 : 0) + 2 * p * kWUnitW + 8 * w;
-#pragma unroll
-    for (int i = 0; i < NOWN; ++i)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        uint32_t prev1, next0;
-        neighbours(Dl[i][r], Dc[i][r][0], Dc[i][r][1], Dn[i][r][0], prev1, next0);
-        w_write_copies<CS>(base + (4 + own_row0 + 8 * i + r) * kWUnitW, prev1, Dc[i][r][0], Dc[i][r][1], next0);
+      uint32_t hacc = 0;
+      if constexpr (HW) {
+        uint32_t T[4];
+        if constexpr (GEN) w_residual_gen<BPS, BPD>(hs, hv, ssh, g.den_shift, T, hacc);
+        else w_residual<BPS>(hs, hv, ssh, r_km, r_bm, T, hacc);
+        w_pack<LAY>(T, Hn[0], Hn[1]);
       }
-    if (h_wave) {  // (tile row p, word w)
-      uint32_t prev1, next0;
-      neighbours(Hl, Hc[0], Hc[1], Hn[0], prev1, next0);
-      w_write_copies<CS>(base - p * kWUnitW, prev1, Hc[0], Hc[1], next0);
-    }
-  };
-  // unit k <- unit k + 1
-  auto advance = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < NOWN; ++i)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        Dl[i][r] = Dc[i][r][1];
-        Dc[i][r][0] = Dn[i][r][0];
-        Dc[i][r][1] = Dn[i][r][1];
+      // ---- residuals (or L) outside int8: rare; one wave-uniform test on the usual way ----
+      const uint32_t out = (racc | hacc | lacc) & 0xff00ff00u;
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(out != 0) != 0, 0)) {
+        const int sh0 = CHR ? 4 * s_plane : 0;
+        uint32_t bits = 0;
+        if ((racc & 0xff00ff00u) != 0) bits |= (1u | (w == 0 ? 2u : 0u) | (w == 15 ? 4u : 0u)) << sh0;
+        if ((lacc & 0xff00ff00u) != 0) bits |= 8u;
+        if ((hacc & 0xff00ff00u) != 0) bits |= (1u | (w == 0 ? 2u : 0u) | (w == 15 ? 4u : 0u)) << sh0;
+        if (!real) bits &= ~(1u | 16u | 8u);  // a ghost: only what its edge words mean to the neighbour
+        if (bits) atomicOr(&s_bad[slot], bits);
       }
-    Hl = Hc[1];
-    Hc[0] = Hn[0];
-    Hc[1] = Hn[1];
-  };
+    };
 
-  // the block statistics of unit j (sequence position) -> the frame's record (flat blocks); its deferred blocks -> the exact
-  // kernel's list; the observation count of the blocks that were multiplied.  Called right behind the loads of the iteration after
-  // the unit's own: global stores share the loads' counter, and a store issued late in an iteration makes the next wait for the
-  // raw words a wait for the store (measured: +130 us on the luma launch).
-  uint32_t defer_prev = 0;
-  auto stats_out = [&](int j, uint32_t dfr) __attribute__((always_inline)) {
-    if (tid < NPL * UB) {
-      const int slot = (j + 1) & 3;
-      const int pl = tid / UB, b = tid - pl * UB;
-      const unsigned long long pk = s_sum[slot][pl][b];
-      s_sum[slot][pl][b] = 0ull;
-      const uint4 ta = s_ent[2 * (j + 1)];
-      if ((ta.y >> b) & 1u) {
-        const int c = (int)(ta.x & 0x3ffu), by = (int)((ta.x >> 10) & 0xfffu);
-        const int blk = by * g.nbw + c * UB + b, plane = CHR ? 1 + pl : 0;
-        const int samples = BW * BH;
-        if (!CHR) {
-          reinterpret_cast<int32_t *>(rec + g.off_sum_d[0])[blk] = (int)(uint32_t)(pk & 0xffffffffu) - samples * 128;
-          reinterpret_cast<uint32_t *>(rec + g.off_sum_d2[0])[blk] = (uint32_t)(pk >> 32);
-        } else {
-          // (arithmetic, not an indexed read of the kernel arguments: that is a global load and a wait in the loop)
-          const uint32_t od = g.off_sum_d[1] + (uint32_t)pl * (g.off_sum_d[2] - g.off_sum_d[1]), od2 = g.off_sum_d2[1] + (uint32_t)pl * (g.off_sum_d2[2] - g.off_sum_d2[1]);
-          reinterpret_cast<int32_t *>(rec + od)[blk] = (int)(uint32_t)(pk & 0xffffffffu) - samples * 128;
-          reinterpret_cast<uint32_t *>(rec + od2)[blk] = (uint32_t)(pk >> 32);
-        }
-        if ((dfr >> pl) & 1u) {
-          wp.only[((size_t)frame * 3 + plane) * g.nblocks + blk] = 1;  // (rare)
-          wp.only_any[frame] = 1u;
-        } else {
-          const uint32_t wd = reinterpret_cast<const uint32_t *>(s_ent)[8 * (j + 1) + 4 + (b >> 1)];
-          const MWin mw = m_unpack((wd >> (16 * (b & 1))) & 0xffffu, g.lag);
-          if (mw.go) nobs_acc += (uint32_t)((mw.xe - mw.xs) * (mw.ye - mw.ys));
-        }
-      }
-    }
-  };
-
-  // ---- prologue: the ghost in front of the slice (when the first unit has a left neighbour), unit 0 ----
-  if (nmine > 0) {
-    const uint32_t e0 = entry_x(0);
-    if ((e0 >> 22) & 1u) {
-      const uint32_t eg = entry_x(-1);
-      request(eg);
-      form(-1, eg, false);
-      advance();  // (the ghost -> the k registers)
-    }
-    request(e0);
-    form(0, e0, true);
-    advance();  // ghost (or zeros) -> the k - 1 registers, unit 0 -> the k registers
-    load_L(e0);
-    // the words of unit 1 (or of the ghost behind a one-unit slice)
-    if (nmine > 1 || ((e0 >> 23) & 1u)) request(entry_x(1));
-  }
-  __syncthreads();
-
-  for (int k = 0; k < nmine; ++k) {
-    // the entry of unit k and the first words of the next two: LDS -> SGPRs
-    w_u4 ea, eb;
-    {
-      const uint4 ta = s_ent[2 * (k + 1)], tb = s_ent[2 * (k + 1) + 1];
-      ea.x = __builtin_amdgcn_readfirstlane(ta.x), ea.y = __builtin_amdgcn_readfirstlane(ta.y), ea.z = __builtin_amdgcn_readfirstlane(ta.z), ea.w = CHR ? __builtin_amdgcn_readfirstlane(ta.w) : 0u;
-      eb.x = __builtin_amdgcn_readfirstlane(tb.x), eb.y = __builtin_amdgcn_readfirstlane(tb.y);
-      eb.z = UB > 4 ? __builtin_amdgcn_readfirstlane(tb.z) : 0u, eb.w = UB > 4 ? __builtin_amdgcn_readfirstlane(tb.w) : 0u;
-    }
-    const uint32_t x1 = entry_x(k + 1), x2 = entry_x(k + 2);
-    // (no explicit wait for the loads here: measured, profiles/r04d -- it costs the chroma launch 24 us: it also waits for the
-    //  block-statistics stores of the iteration before, which nothing needs)
-    const uint32_t ex = ea.x;
-    const bool last = k + 1 == nmine;
-    // ---- the next unit's residual words (its raw words have had an iteration to land); the unit after it is requested ----
-    if (!last || ((ex >> 23) & 1u)) {
-      form(k + 1, x1, !last);
-    } else {
+    // the copies of unit k (Dc / Hc; left halo dwords Dl / Hl, right halo dwords in Dn / Hn) -> the tile buffer.
+    // The dword left of word w is word w - 1's second dword (row_shr:1; lane 0 of the row keeps what the first move put there: the
+    // unit before's last dword, rotated in from lane 15), the dword right of it word w + 1's first (row_shl:1; lane 15 likewise).
+    // (What lane 0 / lane 15 get when the unit has NO neighbour on that side -- words of some other unit, or zeros -- is never
+    //  multiplied into a sum: a block without a flat neighbour keeps `lag` columns from that edge out of its window, the window
+    //  masks the A operand, and a sample inside the window reads at most `lag` columns to its side: words of its own unit.  The
+    //  plain products need every block's whole window, i.e. real neighbours.  Round 4 zeroed them: two v_and a row.)
+    auto neighbours = [&](uint32_t dl, uint32_t d0, uint32_t d1, uint32_t dn0, uint32_t &prev1, uint32_t &next0)
+                          __attribute__((always_inline)) {
+      const int hl = __builtin_amdgcn_mov_dpp((int)dl, 0x121, 0xf, 0xf, true);   // row_ror:1:  lane 0 <- lane 15
+      const int hr = __builtin_amdgcn_mov_dpp((int)dn0, 0x12f, 0xf, 0xf, true);  // row_ror:15: lane 15 <- lane 0
+      prev1 = (uint32_t)__builtin_amdgcn_update_dpp(hl, (int)d1, 0x111, 0xf, 0xf, false);  // row_shr:1
+      next0 = (uint32_t)__builtin_amdgcn_update_dpp(hr, (int)d0, 0x101, 0xf, 0xf, false);  // row_shl:1
+    };
+    auto write_copies = [&](uint32_t ex) __attribute__((always_inline)) {
+      uint8_t *base = w_smem + (CHR && s_plane ? SH::OFF_P1 : 0) + 2 * p * kWUnitW + 8 * w;
 #pragma unroll
       for (int i = 0; i < NOWN; ++i)
 #pragma unroll
-        for (int r = 0; r < 2; ++r) Dn[i][r][0] = Dn[i][r][1] = 0u;
-      Hn[0] = Hn[1] = 0u;
-    }
-    // (every wait for memory is behind us: what follows only issues -- the L tile of this unit into the buffer, the stores of the
-    //  unit before, the loads of the units ahead -- and nothing in the rest of the iteration waits for a load or a store)
-    if constexpr (CHR) {
-#pragma unroll
-      for (int q = 0; q < BH / 16; ++q) {
-        const int row = 16 * q + (tid >> 4);
-        *reinterpret_cast<uint2 *>(w_smem + SH::OFF_L + (row + 4) * kWUnitW + 8 * (tid & 15)) = make_uint2(Lc[q].x, Lc[q].y);
+        for (int r = 0; r < 2; ++r) {
+          uint32_t prev1, next0;
+          neighbours(Dl[i][r], Dc[i][r][0], Dc[i][r][1], Dn[i][r][0], prev1, next0);
+          w_write_copies<CS>(base + (4 + own_row0 + 8 * i + r) * kWUnitW, prev1, Dc[i][r][0], Dc[i][r][1], next0);
+        }
+      if constexpr (HW) {  // (tile row p, word w)
+        uint32_t prev1, next0;
+        neighbours(Hl, Hc[0], Hc[1], Hn[0], prev1, next0);
+        w_write_copies<CS>(base - p * kWUnitW, prev1, Hc[0], Hc[1], next0);
       }
-    }
-    if (!last) load_L(x1);  // (the next unit's L tile, an iteration ahead)
-    if (!last && (k + 2 < nmine || ((x1 >> 23) & 1u))) request(x2);
-    // (the stores BEHIND the loads: the compiler guards the loads' destination registers with a wait that would take the stores
-    //  with it; the next wait for memory, form's in the next iteration, is a whole iteration away)
-    if (k > 0) stats_out(k - 1, defer_prev);
-    // ---- this unit's copies -> the tile buffer (free since the barrier at the end of the iteration before) ----
-    write_copies(ex);
-    __syncthreads();
-    // ------------------------------- multiply unit k -------------------------------
-    const int slot = (k + 1) & 3;
-    const uint32_t b0 = __builtin_amdgcn_readfirstlane(s_bad[slot]), bl = __builtin_amdgcn_readfirstlane(s_bad[k & 3]),
-                   br = __builtin_amdgcn_readfirstlane(s_bad[(k + 2) & 3]);
-    uint32_t defer;  // bit pl: plane pl of this launch is left to the exact kernel; luma bit 3: L left int8
-    {
-      const uint32_t aL = (ex >> 22) & 1u, aR = (ex >> 23) & 1u;
-      const uint32_t d0 = (b0 & 1u) | (aL & (bl >> 2)) | (aR & (br >> 1));
-      defer = d0 & 1u;
-      if (CHR) defer |= (((b0 >> 4) & 1u) | (aL & (bl >> 6)) | (aR & (br >> 5))) << 1;
-      if (LOUT) defer |= b0 & 8u;
-    }
-    if (CHR && ea.w) defer |= 3u;  // L outside int8 in a luma unit under this unit: both planes
-    const bool mine_deferred = ((defer >> (CHR ? s_plane : 0)) & 1u) != 0;
-    // (round 6: a wave that multiplies outranks, at its SIMD's arbiter, the three waves of other workgroups that stage beside it -- the
-    //  matrix pipe is the scarcer issue slot, and a product issued late is a barrier reached late by four waves.  luma 362 - 365 ->
-    //  354 - 358 us, chroma 212 - 219 -> 209 - 214, the chain - 5 to - 20 by the box; priorities 1 / 2 / 3, the halo wave raised while it
-    //  stages, or the staging phase raised instead: all within 3 us of each other.  profiles/r06h_setprio.txt)
-    __builtin_amdgcn_s_setprio(1);
-    if (!mine_deferred) {
-      if ((ex >> 24) & 1u) {
-        w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
-      } else if ([&]() {
-                   // the windows of this wave's strip (64 columns: 64 / BW blocks), in SGPRs: every one of them the whole block
-                   // -> the plain products, without building a mask
-                   constexpr int DPS = (64 / BW + 1) / 2;  // dwords of window codes a strip
-                   constexpr uint32_t whole1 = (uint32_t)BW | ((uint32_t)BH << 6) | (1u << 15), whole2 = whole1 | (whole1 << 16);
-                   const uint32_t wsel[4] = {eb.x, eb.y, eb.z, eb.w};
-                   bool all = true;
+    };
+    // unit k <- unit k + 1
+    auto advance = [&]() __attribute__((always_inline)) {
 #pragma unroll
-                   for (int q = 0; q < DPS; ++q) all = all && wsel[m_strip * DPS + q] == whole2;
-                   return all;
-                 }()) {
-        w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
+      for (int i = 0; i < NOWN; ++i)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          Dl[i][r] = Dc[i][r][1];
+          Dc[i][r][0] = Dn[i][r][0];
+          Dc[i][r][1] = Dn[i][r][1];
+        }
+      if constexpr (HW) {
+        Hl = Hc[1];
+        Hc[0] = Hn[0];
+        Hc[1] = Hn[1];
+      }
+    };
+
+    // the block statistics of unit j (sequence position) -> the frame's record (flat blocks); its deferred blocks -> the exact
+    // kernel's list; the observation count of the blocks that were multiplied.  Called right behind the loads of the iteration after
+    // the unit's own: global stores share the loads' counter, and a store issued late in an iteration makes the next wait for the
+    // raw words a wait for the store (measured: +130 us on the luma launch).
+    uint32_t defer_prev = 0;
+    auto stats_out = [&](int j, uint32_t dfr) __attribute__((always_inline)) {
+      if (tid < NPL * UB) {
+        const int slot = (j + 1) & 3;
+        const int pl = tid / UB, b = tid - pl * UB;
+        const unsigned long long pk = s_sum[slot][pl][b];
+        s_sum[slot][pl][b] = 0ull;
+        const uint4 ta = s_ent[2 * (j + 1)];
+        if ((ta.y >> b) & 1u) {
+          const int c = (int)(ta.x & 0x3ffu), by = (int)((ta.x >> 10) & 0xfffu);
+          const int blk = by * g.nbw + c * UB + b, plane = CHR ? 1 + pl : 0;
+          const int samples = BW * BH;
+          if (!CHR) {
+            reinterpret_cast<int32_t *>(rec + g.off_sum_d[0])[blk] = (int)(uint32_t)(pk & 0xffffffffu) - samples * 128;
+            reinterpret_cast<uint32_t *>(rec + g.off_sum_d2[0])[blk] = (uint32_t)(pk >> 32);
+          } else {
+            // (arithmetic, not an indexed read of the kernel arguments: that is a global load and a wait in the loop)
+            const uint32_t od = g.off_sum_d[1] + (uint32_t)pl * (g.off_sum_d[2] - g.off_sum_d[1]), od2 = g.off_sum_d2[1] + (uint32_t)pl * (g.off_sum_d2[2] - g.off_sum_d2[1]);
+            reinterpret_cast<int32_t *>(rec + od)[blk] = (int)(uint32_t)(pk & 0xffffffffu) - samples * 128;
+            reinterpret_cast<uint32_t *>(rec + od2)[blk] = (uint32_t)(pk >> 32);
+          }
+          if ((dfr >> pl) & 1u) {
+            wp.only[((size_t)frame * 3 + plane) * g.nblocks + blk] = 1;  // (rare)
+            wp.only_any[frame] = 1u;
+          } else {
+            const uint32_t wd = reinterpret_cast<const uint32_t *>(s_ent)[8 * (j + 1) + 4 + (b >> 1)];
+            const MWin mw = m_unpack((wd >> (16 * (b & 1))) & 0xffffu, g.lag);
+            if (mw.go) nobs_acc += (uint32_t)((mw.xe - mw.xs) * (mw.ye - mw.ys));
+          }
+        }
+      }
+    };
+
+    // ---- prologue: the ghost in front of the slice (when the first unit has a left neighbour), unit 0 ----
+    if (nmine > 0) {
+      const uint32_t e0 = entry_x(0);
+      if ((e0 >> 22) & 1u) {
+        const uint32_t eg = entry_x(-1);
+        request(eg);
+        form(-1, eg, false);
+        advance();  // (the ghost -> the k registers)
+      }
+      request(e0);
+      form(0, e0, true);
+      advance();  // ghost (or zeros) -> the k - 1 registers, unit 0 -> the k registers
+      load_L(e0);
+      // the words of unit 1 (or of the ghost behind a one-unit slice)
+      if (nmine > 1 || ((e0 >> 23) & 1u)) request(entry_x(1));
+    }
+    __syncthreads();
+
+    for (int k = 0; k < nmine; ++k) {
+      // the entry of unit k and the first words of the next two: LDS -> SGPRs
+      w_u4 ea, eb;
+      {
+        const uint4 ta = s_ent[2 * (k + 1)], tb = s_ent[2 * (k + 1) + 1];
+        ea.x = __builtin_amdgcn_readfirstlane(ta.x), ea.y = __builtin_amdgcn_readfirstlane(ta.y), ea.z = __builtin_amdgcn_readfirstlane(ta.z), ea.w = CHR ? __builtin_amdgcn_readfirstlane(ta.w) : 0u;
+        eb.x = __builtin_amdgcn_readfirstlane(tb.x), eb.y = __builtin_amdgcn_readfirstlane(tb.y);
+        eb.z = UB > 4 ? __builtin_amdgcn_readfirstlane(tb.z) : 0u, eb.w = UB > 4 ? __builtin_amdgcn_readfirstlane(tb.w) : 0u;
+      }
+      const uint32_t x1 = entry_x(k + 1), x2 = entry_x(k + 2);
+      // (no explicit wait for the loads here: measured, profiles/r04d -- it costs the chroma launch 24 us: it also waits for the
+      //  block-statistics stores of the iteration before, which nothing needs)
+      const uint32_t ex = ea.x;
+      const bool last = k + 1 == nmine;
+      // ---- the next unit's residual words (its raw words have had an iteration to land); the unit after it is requested ----
+      if (!last || ((ex >> 23) & 1u)) {
+        form(k + 1, x1, !last);
       } else {
-        // this lane's window: block m_blk of the unit
-        const uint32_t wsel[4] = {eb.x, eb.y, eb.z, eb.w};
-        uint32_t wd = wsel[0];
 #pragma unroll
-        for (int q = 1; q < (UB + 1) / 2; ++q) wd = (m_blk >> 1) == q ? wsel[q] : wd;
-        const MWin mw = m_unpack((wd >> (16 * (m_blk & 1))) & 0xffffu, g.lag);
-        const int lo = mw.go ? min(max(mw.xs - m_xo, 0), 16) : 0, hi = mw.go ? min(max(mw.xe - m_xo, 0), 16) : 0;
-        // bytes [lo, hi) of the lane's 16
-        w_v4 cm;
+        for (int i = 0; i < NOWN; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int hj = min(max(hi - 4 * j, 0), 4), lj = min(max(lo - 4 * j, 0), 4);
-          cm[j] = (int)((uint32_t)((1ull << (8 * hj)) - 1ull) & ~(uint32_t)((1ull << (8 * lj)) - 1ull));
-        }
-        constexpr uint32_t full = NSTEP >= 32 ? ~0u : (1u << NSTEP) - 1u;
-        const uint32_t rm = mw.go ? (m_rowmask(mw.ys, mw.ye) >> m_row0) & full : 0u;
-        // what the chain needs, wave-uniform: nothing (no window sample in its strip), the plain products (every lane's window
-        // covers its 16 samples and the chain's rows), column masks only, or the general form
-        const bool empty = hi <= lo || rm == 0u;
-        const bool whole = lo == 0 && hi == 16;
-        const bool rows_in = rm == full || empty;
-        if (__builtin_amdgcn_ballot_w64(!empty) != 0) {
-          if (__builtin_amdgcn_ballot_w64(!rows_in) != 0) w_multiply<NSTEP, 2>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, cm, rm);
-          else if (__builtin_amdgcn_ballot_w64(!(whole && !empty)) != 0) w_multiply<NSTEP, 1>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, empty ? w_v4{0, 0, 0, 0} : cm, 0u);
-          else w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
+          for (int r = 0; r < 2; ++r) Dn[i][r][0] = Dn[i][r][1] = 0u;
+        Hn[0] = Hn[1] = 0u;
+      }
+      // (every wait for memory is behind us: what follows only issues -- the L tile of this unit into the buffer, the stores of the
+      //  unit before, the loads of the units ahead -- and nothing in the rest of the iteration waits for a load or a store)
+      if constexpr (CHR) {
+#pragma unroll
+        for (int q = 0; q < BH / 16; ++q) {
+          const int row = 16 * q + (tid >> 4);
+          *reinterpret_cast<uint2 *>(w_smem + SH::OFF_L + (row + 4) * kWUnitW + 8 * (tid & 15)) = make_uint2(Lc[q].x, Lc[q].y);
         }
       }
+      if (!last) load_L(x1);  // (the next unit's L tile, an iteration ahead)
+      if (!last && (k + 2 < nmine || ((x1 >> 23) & 1u))) request(x2);
+      // (the stores BEHIND the loads: the compiler guards the loads' destination registers with a wait that would take the stores
+      //  with it; the next wait for memory, form's in the next iteration, is a whole iteration away)
+      if (k > 0) stats_out(k - 1, defer_prev);
+      // ---- this unit's copies -> the tile buffer (free since the barrier at the end of the iteration before) ----
+      write_copies(ex);
+      __syncthreads();
+      // ------------------------------- multiply unit k -------------------------------
+      const int slot = (k + 1) & 3;
+      const uint32_t b0 = __builtin_amdgcn_readfirstlane(s_bad[slot]), bl = __builtin_amdgcn_readfirstlane(s_bad[k & 3]),
+                     br = __builtin_amdgcn_readfirstlane(s_bad[(k + 2) & 3]);
+      uint32_t defer;  // bit pl: plane pl of this launch is left to the exact kernel; luma bit 3: L left int8
+      {
+        const uint32_t aL = (ex >> 22) & 1u, aR = (ex >> 23) & 1u;
+        const uint32_t d0 = (b0 & 1u) | (aL & (bl >> 2)) | (aR & (br >> 1));
+        defer = d0 & 1u;
+        if (CHR) defer |= (((b0 >> 4) & 1u) | (aL & (bl >> 6)) | (aR & (br >> 5))) << 1;
+        if (LOUT) defer |= b0 & 8u;
+      }
+      if (CHR && ea.w) defer |= 3u;  // L outside int8 in a luma unit under this unit: both planes
+      const bool mine_deferred = ((defer >> (CHR ? s_plane : 0)) & 1u) != 0;
+      // (round 6: a wave that multiplies outranks, at its SIMD's arbiter, the three waves of other workgroups that stage beside it -- the
+      //  matrix pipe is the scarcer issue slot, and a product issued late is a barrier reached late by four waves.  luma 362 - 365 ->
+      //  354 - 358 us, chroma 212 - 219 -> 209 - 214, the chain - 5 to - 20 by the box; priorities 1 / 2 / 3, the halo wave raised while it
+      //  stages, or the staging phase raised instead: all within 3 us of each other.  profiles/r06h_setprio.txt)
+      __builtin_amdgcn_s_setprio(1);
+      if (!mine_deferred) {
+        if ((ex >> 24) & 1u) {
+          w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
+        } else if ([&]() {
+                     // the windows of this wave's strip (64 columns: 64 / BW blocks), in SGPRs: every one of them the whole block
+                     // -> the plain products, without building a mask
+                     constexpr int DPS = (64 / BW + 1) / 2;  // dwords of window codes a strip
+                     constexpr uint32_t whole1 = (uint32_t)BW | ((uint32_t)BH << 6) | (1u << 15), whole2 = whole1 | (whole1 << 16);
+                     const uint32_t wsel[4] = {eb.x, eb.y, eb.z, eb.w};
+                     bool all = true;
+#pragma unroll
+                     for (int q = 0; q < DPS; ++q) all = all && wsel[m_strip * DPS + q] == whole2;
+                     return all;
+                   }()) {
+          w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
+        } else {
+          // this lane's window: block m_blk of the unit
+          const uint32_t wsel[4] = {eb.x, eb.y, eb.z, eb.w};
+          uint32_t wd = wsel[0];
+#pragma unroll
+          for (int q = 1; q < (UB + 1) / 2; ++q) wd = (m_blk >> 1) == q ? wsel[q] : wd;
+          const MWin mw = m_unpack((wd >> (16 * (m_blk & 1))) & 0xffffu, g.lag);
+          const int lo = mw.go ? min(max(mw.xs - m_xo, 0), 16) : 0, hi = mw.go ? min(max(mw.xe - m_xo, 0), 16) : 0;
+          // bytes [lo, hi) of the lane's 16
+          w_v4 cm;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int hj = min(max(hi - 4 * j, 0), 4), lj = min(max(lo - 4 * j, 0), 4);
+            cm[j] = (int)((uint32_t)((1ull << (8 * hj)) - 1ull) & ~(uint32_t)((1ull << (8 * lj)) - 1ull));
+          }
+          constexpr uint32_t full = NSTEP >= 32 ? ~0u : (1u << NSTEP) - 1u;
+          const uint32_t rm = mw.go ? (m_rowmask(mw.ys, mw.ye) >> m_row0) & full : 0u;
+          // what the chain needs, wave-uniform: nothing (no window sample in its strip), the plain products (every lane's window
+          // covers its 16 samples and the chain's rows), column masks only, or the general form
+          const bool empty = hi <= lo || rm == 0u;
+          const bool whole = lo == 0 && hi == 16;
+          const bool rows_in = rm == full || empty;
+          if (__builtin_amdgcn_ballot_w64(!empty) != 0) {
+            if (__builtin_amdgcn_ballot_w64(!rows_in) != 0) w_multiply<NSTEP, 2>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, cm, rm);
+            else if (__builtin_amdgcn_ballot_w64(!(whole && !empty)) != 0) w_multiply<NSTEP, 1>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, empty ? w_v4{0, 0, 0, 0} : cm, 0u);
+            else w_multiply<NSTEP, 0>(aSS, aPP, aPQ, aQQ, w_smem, m_addr, w_v4{0, 0, 0, 0}, 0u);
+          }
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      if (tid == 64) {
+        if (LOUT && (defer & 8u)) wp.lbad[(size_t)frame * wp.ncell_y + ea.z] = 1;
+        s_bad[(k + 3) & 3] = 0u;  // (the slot of unit k - 2 = of unit k + 2: dead since the iteration before, written again in the next)
+      }
+      advance();
+      defer_prev = defer;
+      __syncthreads();
     }
-    __builtin_amdgcn_s_setprio(0);
-    if (tid == 64) {
-      if (LOUT && (defer & 8u)) wp.lbad[(size_t)frame * wp.ncell_y + ea.z] = 1;
-      s_bad[(k + 3) & 3] = 0u;  // (the slot of unit k - 2 = of unit k + 2: dead since the iteration before, written again in the next)
-    }
-    advance();
-    defer_prev = defer;
-    __syncthreads();
-  }
-  if (nmine > 0) stats_out(nmine - 1, defer_prev);
+    if (nmine > 0) stats_out(nmine - 1, defer_prev);
+  };
+  if (h_wave) pass(std::true_type{});
+  else pass(std::false_type{});
 
   // ---- the workgroup's partial systems: waves add into LDS (int64), one plain store per entry ----
   long long *s_S = reinterpret_cast<long long *>(w_smem);
