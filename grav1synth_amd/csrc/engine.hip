@@ -906,7 +906,30 @@ int g1s_diff::launch_front(int si) {
     cl.list = reinterpret_cast<uint32_t *>(sl.d_k1 + lay.k1_list);
     cl.count = reinterpret_cast<uint32_t *>(sl.d_k1 + lay.k1_count);
     cl.global = literal_mode == 0 ? 1 : 0;  // (the default chain: one sequence for the launch; "every block literally": per-frame lists)
-    {
+    // Aligned rows of whole blocks, the default finder: the moments as a pass over column strips that certifies its own
+    // blocks (k1_moments_strips); anything else -- unaligned rows, a ragged last block column, the literal modes -- the
+    // row-per-lane kernel and k1_certify behind it.  G1S_K1_ROWS=1 (a test and measurement aid, read at every batch): the
+    // latter for every batch.
+    const char *k1_rows = getenv("G1S_K1_ROWS");
+    const bool strips = g.fast_rows && g.W % kBlock == 0 && literal_mode == 0 && !(k1_rows && atoi(k1_rows) != 0);
+    if (strips) {
+      constexpr int kR2 = G1S_STRIP_ROWS2, kRif = G1S_STRIP_RIF;
+      constexpr bool kNt = G1S_STRIP_NT != 0, kFold = G1S_STRIP_FOLD != 0;
+      if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomStart], fstream));
+      // (the batch's last luma planes, as many as the last-level cache holds, keep the plain loads; G1S_K1_KEEP_MB: that size, a test
+      //  and measurement aid -- 0: the hint on every frame)
+      const char *keep_e = getenv("G1S_K1_KEEP_MB");
+      const size_t keep_bytes = (size_t)(keep_e ? std::max(atoi(keep_e), 0) : kStripKeepMB) << 20;
+      const size_t keep = std::min<size_t>(keep_bytes / ((size_t)g.W * g.src_bps * g.H), B);
+      const int nt_frames = kNt ? (int)(B - keep) : 0;
+      const dim3 sg((strip_tiles<kR2>(g.nbw, g.nbh) + 3) / 4, B);
+      sl.marks.mark(fstream, g.src_bps == 1 ? "k1_moments_strips<1>" : "k1_moments_strips<2>");
+      if (g.src_bps == 1)
+        hipLaunchKernelGGL((k1_moments_strips<1, kR2, kRif, kNt, kFold>), sg, dim3(256), 0, fstream, ft, g, fc, mom, sl.d_records, sl.d_flags, cl, nt_frames);
+      else
+        hipLaunchKernelGGL((k1_moments_strips<2, kR2, kRif, kNt, kFold>), sg, dim3(256), 0, fstream, ft, g, fc, mom, sl.d_records, sl.d_flags, cl, nt_frames);
+      if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomEnd], fstream));
+    } else {
       // the finder's moments of the luma source: the only pass over pixels that are not in a flat block's tile
       if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomStart], fstream));
       {  // (also when every block is evaluated literally: the record's luma_sum comes from the moments)
@@ -917,9 +940,11 @@ int g1s_diff::launch_front(int si) {
       }
       if (p.timed && !p.chain) HIP_TRY(hipEventRecord(sl.ev[kEvMomEnd], fstream));
     }
-    sl.marks.mark(fstream, "k1_certify");
-    hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
-                       sl.d_records, sl.d_flags, cl, force_literal);
+    if (!strips || !G1S_STRIP_FOLD) {
+      sl.marks.mark(fstream, "k1_certify");
+      hipLaunchKernelGGL(k1_certify, dim3((g.nblocks + 255) / 256, B), dim3(256), 0, fstream, g, fc, (const int32_t *)mom,
+                         sl.d_records, sl.d_flags, cl, force_literal);
+    }
     sl.marks.mark(fstream, literal_mode == 1 ? "k1_flat_features" : "k1_flat_block");
     if (literal_mode == 1) {  // every block: one lane per block
       dim3 grid((g.nblocks + 63) / 64, B);

@@ -15,6 +15,9 @@
 //                analysis of its sequential sums, carried through every later operation).  A block whose four threshold tests
 //                and whose f32 score are unambiguous within that bound gets them written;
 //                any other block goes on a list;
+//   k1_moments_strips   both of the above in ONE launch for aligned rows of whole blocks (the default path): the sums as a
+//                pass over column strips, a lane = 8 consecutive samples of a row, and every workgroup certifies the 64
+//                blocks it covered (certify_block, the body k1_certify calls too); no moments buffer;
 //   k1_flat_features<.., true>   the literal kernel, for the listed blocks only.
 // The result is bit for bit the literal kernel's wherever the bound holds; the bound carries a
 // safety factor, and the tests compare every block of every test frame with the oracle.
@@ -172,18 +175,17 @@ struct CertifyLists {
 };
 
 // ---------------------------------------------------------------------------------
-// k1_certify: one thread per block.  grid = (ceil(nblocks / 256), batch), block = 256.
+// certify_block: the certificate of one block from its sixteen ints of the moments' layout, a lane a block.  Writes the
+// record's luma_sum and, where the bound decides them, the score and the flag; appends every other block to the literal
+// list (a ballot and one atomic a wave: EVERY lane of the wave calls it, `live` or not).
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k1_certify(Geom g, FlatConsts fc, const int32_t *__restrict__ mom,
-                                                  uint8_t *__restrict__ records, uint8_t *__restrict__ flags,
-                                                  CertifyLists cl, int force_literal) {
-  const int frame = blockIdx.y;
-  const int blk = (int)blockIdx.x * 256 + (int)threadIdx.x;
+__device__ __forceinline__ void certify_block(const Geom &g, const FlatConsts &fc, const int32_t (&m)[kMomInts], const int frame,
+                                              const int blk, const bool live, uint8_t *__restrict__ records,
+                                              uint8_t *__restrict__ flags, const CertifyLists &cl, const int force_literal) {
   bool certain = false;
   float score_out = 0.0f;
   uint8_t flag_out = 0;
-  if (blk < g.nblocks && !force_literal) {
-    const int32_t *m = mom + ((size_t)frame * g.nblocks + blk) * kMomInts;
+  if (live && !force_literal) {
     const double S0 = m[kM_S0], SX = (double)m[kM_SXU] - 16.0 * m[kM_S0], SY = (double)m[kM_SYU] - 16.0 * m[kM_S0];
     const double SAX = m[kM_SAX], SAY = m[kM_SAY];
     const double I0 = m[kM_I0], IX = (double)m[kM_IXU] - 16.0 * m[kM_I0], IY = (double)m[kM_IYU] - 16.0 * m[kM_I0];
@@ -317,18 +319,18 @@ __global__ __launch_bounds__(256) void k1_certify(Geom g, FlatConsts fc, const i
       }
     }
   }
-  if (blk < g.nblocks) {
+  if (live) {
     uint8_t *rec = records + (size_t)frame * g.rec_size;
     // the record's luma_sum (get_block_mean as an exact sum) comes from the finder's moments: the accumulation launches do
     // not form it (4 additions a row word of the luma launch)
-    reinterpret_cast<uint32_t *>(rec + g.off_luma_sum)[blk] = (uint32_t)mom[((size_t)frame * g.nblocks + blk) * kMomInts + kM_CLIP];
+    reinterpret_cast<uint32_t *>(rec + g.off_luma_sum)[blk] = (uint32_t)m[kM_CLIP];
     if (certain) {
       reinterpret_cast<float *>(rec + g.off_scores)[blk] = score_out;
       flags[(size_t)frame * g.nblocks + blk] = flag_out;
     }
   }
   // the rest: compacted for the literal kernel (one atomic per wave)
-  const bool todo = blk < g.nblocks && !certain;
+  const bool todo = live && !certain;
   const unsigned long long bal = __ballot(todo);
   if (bal != 0) {
     const int lane = threadIdx.x & 63;
@@ -340,6 +342,169 @@ __global__ __launch_bounds__(256) void k1_certify(Geom g, FlatConsts fc, const i
       if (cl.global) cl.list[at] = (uint32_t)frame * (uint32_t)g.nblocks + (uint32_t)blk;
       else cl.list[(size_t)frame * g.nblocks + at] = (uint32_t)blk;
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// k1_certify: one thread per block.  grid = (ceil(nblocks / 256), batch), block = 256.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k1_certify(Geom g, FlatConsts fc, const int32_t *__restrict__ mom,
+                                                  uint8_t *__restrict__ records, uint8_t *__restrict__ flags,
+                                                  CertifyLists cl, int force_literal) {
+  const int frame = blockIdx.y;
+  const int blk = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  const bool live = blk < g.nblocks;
+  int32_t m[kMomInts];
+#pragma unroll
+  for (int k = 0; k < kMomInts; ++k) m[k] = live ? mom[((size_t)frame * g.nblocks + blk) * kMomInts + k] : 0;
+  certify_block(g, fc, m, frame, blk, live, records, flags, cl, force_literal);
+}
+
+// ---------------------------------------------------------------------------------
+// k1_moments_strips<BPS, ROWS2, RIF, NT, FOLD>: the moments of aligned planes whose width is whole blocks, as a pass over
+// column strips, and the certificate of the same blocks in the same launch.
+//   lane = 8 consecutive samples of a row (one 16-byte load at 10 / 16 bits, 8 bytes at 8), consecutive lanes consecutive
+//   words: a wave's load instruction is whole 128-byte lines.  A quad of lanes = a block's 32 columns.  A wave walks the 32
+//   rows of its blocks with RIF rows' loads in flight; the row loop is unrolled, so a row's class (end row, interior, its yi
+//   factors) is the instruction stream's and the rows above and below are the registers of the iterations beside it.  The
+//   fifteen sums stay in the lane's registers until the block ends; then one quad reduction.
+//   ROWS2 = 0: a wave = 16 blocks of one block row (512 samples); 1: 8 blocks of each of two block rows (a half-wave each).
+//   A workgroup = four waves = four consecutive tiles of the frame's raster of tiles; grid = (ceil(tiles / 4), batch),
+//   frame slowest (the batch's last frames are the lines the caches hold when the luma launch starts).
+//   FOLD: the workgroup parks its 64 blocks' totals in LDS and, behind ONE workgroup barrier, its first wave certifies them
+//   a lane a block (certify_block): no moments buffer, no second launch, nothing handed from workgroup to workgroup.
+//   !FOLD: the totals go to the moments buffer for k1_certify.
+//   NT: frames below nt_frames are read with the non-temporal hint -- every load is whole lines that nothing reads twice, and
+//   lines that do not stay in the caches leave k4_latest, which runs beside this launch, its own (profiles/finder_strips.txt);
+//   the batch's last frames, as many as the last-level cache holds (kStripKeepMB), keep the plain loads: they are what the
+//   luma launch finds there.
+// ---------------------------------------------------------------------------------
+#ifndef G1S_STRIP_ROWS2
+#define G1S_STRIP_ROWS2 0
+#endif
+#ifndef G1S_STRIP_RIF
+#define G1S_STRIP_RIF 4
+#endif
+#ifndef G1S_STRIP_NT  // the non-temporal hint on the loads of the frames below the kernel's nt_frames
+#define G1S_STRIP_NT 1
+#endif
+#ifndef G1S_STRIP_FOLD
+#define G1S_STRIP_FOLD 1
+#endif
+constexpr int kStripWgBlocks = 64;  // blocks a workgroup covers: 16 a wave
+constexpr int kStripKeepMB = 256;   // MI355X: 256 MB of Infinity Cache
+template <int ROWS2>
+__host__ __device__ __forceinline__ int strip_tiles_x(int nbw) { return ROWS2 ? (nbw + 7) / 8 : (nbw + 15) / 16; }
+template <int ROWS2>
+__host__ __device__ __forceinline__ int strip_tiles(int nbw, int nbh) { return strip_tiles_x<ROWS2>(nbw) * (ROWS2 ? (nbh + 1) / 2 : nbh); }
+// block q (0 .. 15) of a tile: its column and row of blocks
+template <int ROWS2>
+__device__ __forceinline__ void strip_block_of(int tile, int q, int nbw, int &bx, int &by) {
+  const int nx = strip_tiles_x<ROWS2>(nbw);
+  const int tx = tile % nx, ty = tile / nx;
+  bx = ROWS2 ? tx * 8 + (q & 7) : tx * 16 + q;
+  by = ROWS2 ? ty * 2 + (q >> 3) : ty;
+}
+template <int BPS, bool NT>
+__device__ __forceinline__ u32x4 strip_load(gptr_u8 p) {
+  if constexpr (BPS == 2) {
+    return NT ? __builtin_nontemporal_load((gptr_u4)p) : *(gptr_u4)p;
+  } else {
+    const u32x2 v = NT ? __builtin_nontemporal_load((gptr_u2)p) : *(gptr_u2)p;
+    return u32x4{v.x, v.y, 0u, 0u};
+  }
+}
+template <int BPS>
+__device__ __forceinline__ void strip_narrow(const u32x4 raw, int shift, uint32_t (&pk)[2]) {
+  if constexpr (BPS == 2) {  // (`(v >> shift) as u8` of four samples: see load_row32)
+    pk[0] = __builtin_amdgcn_perm(raw.y >> shift, raw.x >> shift, 0x06040200u);
+    pk[1] = __builtin_amdgcn_perm(raw.w >> shift, raw.z >> shift, 0x06040200u);
+  } else {
+    pk[0] = raw.x;
+    pk[1] = raw.y;
+  }
+}
+
+// the 32 rows of a wave's blocks, RIF rows' loads in flight: row_ptr(yi) -> the lane's 8 samples of row yi
+template <int BPS, int RIF, bool NT, class RowPtr>
+__device__ __forceinline__ void strip_walk(const RowPtr &row_ptr, const int shift, const StripLane &L, StripSums &a) {
+  u32x4 raw[RIF];
+#pragma unroll
+  for (int k = 0; k < RIF; ++k) raw[k] = strip_load<BPS, NT>(row_ptr(k));
+  uint32_t pu[2] = {0u, 0u}, pui[2] = {0u, 0u}, pk[2], pd[2] = {0u, 0u}, pi[2];
+  strip_narrow<BPS>(raw[0], shift, pk);
+  raw[0] = strip_load<BPS, NT>(row_ptr(RIF));
+#pragma unroll
+  for (int yi = 0; yi < kBlock; ++yi) {
+    if (yi + 1 < kBlock) {
+      strip_narrow<BPS>(raw[(yi + 1) % RIF], shift, pd);
+      if (yi + 1 + RIF < kBlock) raw[(yi + 1) % RIF] = strip_load<BPS, NT>(row_ptr(yi + 1 + RIF));
+    }
+    strip_row(L, yi, pu, pui, pk, pd, pi, a);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) pu[k] = pk[k], pui[k] = pi[k], pk[k] = pd[k];
+  }
+}
+
+template <int BPS, int ROWS2, int RIF, bool NT, bool FOLD>
+__global__ __launch_bounds__(256) void k1_moments_strips(const FrameTable ft, Geom g, FlatConsts fc, int32_t *__restrict__ mom,
+                                                         uint8_t *__restrict__ records, uint8_t *__restrict__ flags,
+                                                         CertifyLists cl, int nt_frames) {
+  __shared__ int32_t park[kStripWgBlocks * kMomInts];
+  const int frame = blockIdx.y;
+  const int lane = (int)(threadIdx.x & 63), c = lane & 3;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int ntiles = strip_tiles<ROWS2>(g.nbw, g.nbh);
+  const int tile = (int)blockIdx.x * 4 + wave;
+  if (tile < ntiles) {
+    int bx, by;
+    strip_block_of<ROWS2>(tile, lane >> 2, g.nbw, bx, by);
+    const bool live = bx < g.nbw && by < g.nbh;
+    if (!live) bx = 0, by = 0;  // (an idle quad reads the frame's first block: addresses inside the plane, totals dropped)
+    const FramePlanes fp = ft.f[frame];
+    const uint32_t stride = fp.src_stride[0];
+    const int shift = g.src_shift;
+    // (one block row a wave: the row's address is the wave's, a lane adds its 32-bit column offset)
+    const int oy = ROWS2 ? by * kBlock : (tile / strip_tiles_x<ROWS2>(g.nbw)) * kBlock;
+    const uint32_t xoff = (uint32_t)(bx * kBlock + c * 8) * BPS;
+    // rows past the bottom of the plane are row H - 1, as load_row32's callers clamp them
+    auto row_ptr = [&](int yi) {
+      const uintptr_t row = (uintptr_t)fp.src[0] + (size_t)min(oy + yi, g.H - 1) * stride;
+      if constexpr (ROWS2) return (gptr_u8)row + xoff;
+      else  // (wave-uniform, said so: a scalar base and the lane's offset, the load's own addressing)
+        return (gptr_u8)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(row >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)row)) + xoff;
+    };
+    const StripLane L = strip_lane(c);
+    StripSums a{};
+    if (NT && frame < nt_frames) strip_walk<BPS, RIF, true>(row_ptr, shift, L, a);
+    else strip_walk<BPS, RIF, false>(row_ptr, shift, L, a);
+    int v16[16], x[4];
+    strip_totals(a, c, max(oy + kBlock - g.H, 0), v16);
+    quad_sums_split16(v16, x);
+    if constexpr (FOLD) {
+      int32_t *out = park + (wave * 16 + (lane >> 2)) * kMomInts;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) out[4 * j + c] = x[j];
+    } else if (live) {
+      int32_t *out = mom + ((size_t)frame * g.nblocks + (by * g.nbw + bx)) * kMomInts;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) out[4 * j + c] = x[j];
+    }
+  }
+  if constexpr (FOLD) {
+    __syncthreads();
+    if (wave != 0) return;
+    // lane = one of the workgroup's 64 blocks (a tile past the frame's last, or a block past the plane's edge: not live;
+    // its words of `park` are then unwritten or an idle quad's, and are not used)
+    const int t = (int)blockIdx.x * 4 + (lane >> 4);
+    int bx, by;
+    strip_block_of<ROWS2>(t, lane & 15, g.nbw, bx, by);
+    const bool live = t < ntiles && bx < g.nbw && by < g.nbh;
+    int32_t m[kMomInts];
+#pragma unroll
+    for (int k = 0; k < kMomInts; ++k) m[k] = live ? park[lane * kMomInts + k] : 0;
+    certify_block(g, fc, m, frame, live ? by * g.nbw + bx : 0, live, records, flags, cl, 0);
   }
 }
 

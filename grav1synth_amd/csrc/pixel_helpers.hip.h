@@ -228,6 +228,124 @@ __device__ __forceinline__ void row_moments(const uint32_t (&pk)[8], const uint3
   }
 }
 
+// ---- the same sums with a lane = 8 consecutive samples of a row, four lanes (a DPP quad) = a block's 32 columns, the rows
+// of a block walked one after the other by the same lane (k1_moments_strips, k1f.hip.h) ----
+// Per-lane constants of c = lane & 3, the lane's place in its block's row (xi = 8 c .. 8 c + 7).
+struct StripLane {
+  uint32_t xw[2];   // xi as bytes
+  uint32_t aw[2];   // |xi - 16|
+  uint32_t mi[2];   // the interior columns 1 .. 30 as a byte mask
+  uint32_t wn, wp;  // bytes of 1 on columns 0, 1 (first dword of c == 0) / on columns 30, 31 (second dword of c == 3)
+};
+__device__ __forceinline__ StripLane strip_lane(int c) {
+  StripLane L;
+  L.xw[0] = 0x03020100u + 0x08080808u * (uint32_t)c;
+  L.xw[1] = L.xw[0] + 0x04040404u;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) L.aw[k] = c < 2 ? 0x10101010u - L.xw[k] : L.xw[k] - 0x10101010u;  // (no byte borrows: xi < 16 / xi >= 16)
+  L.mi[0] = c == 0 ? 0xffffff00u : 0xffffffffu;
+  L.mi[1] = c == 3 ? 0x00ffffffu : 0xffffffffu;
+  L.wn = c == 0 ? 0x00000101u : 0u;
+  L.wp = c == 3 ? 0x01010000u : 0u;
+  return L;
+}
+// A lane's running shares of a block's sums.  Where a sum's row factor depends on yi the rows are kept apart by class, so
+// that a row adds to an accumulator through the instruction's own operand and the factors are applied once a block:
+//   s0_*: row sums of yi = 0 / 1 .. 15 / 16 .. 30 / 31;  syu_*: yi x row sum of yi < 16 / yi >= 16 (SAY comes from the two);
+//   sxu_in / sxu_e: interior / end rows;  q2 / qb / qa: interior-column squares of yi = 2 .. 29 / 1, 30 / 0, 31.
+struct StripSums {
+  uint32_t s0_r0, s0_lo, s0_hi, s0_r31, sxu_in, sxu_e, syu_lo, syu_hi, sax, i0, iyu, q2, qb, qa;
+  uint32_t rr, rl, du, pos, neg, dxn, dxp, dyn, dyp;
+};
+// Row yi of the block: pk its 8 packed samples, pu / pd the rows above / below (read for yi = 1 .. 30 only), pui the row
+// above masked to the interior columns (the pi this function returned for it).  The left and right neighbour bytes come
+// from the quad's other lanes; the bytes a quad's end lanes get wrong are columns 0 and 31, which the masks drop.
+//   sum_{x=1..30} (p(x+1) - p(x-1))^2 = sum pr^2 + sum pl^2 - 2 sum pr pl   (pr, pl masked to the interior columns)
+__device__ __forceinline__ void strip_row(const StripLane &L, const int yi, const uint32_t (&pu)[2], const uint32_t (&pui)[2],
+                                          const uint32_t (&pk)[2], const uint32_t (&pd)[2], uint32_t (&pi)[2], StripSums &a) {
+  const bool inner = yi >= 1 && yi <= kBlock - 2;
+  const uint32_t r = sad4(pk[1], sad4(pk[0], 0u));
+  pi[0] = pk[0] & L.mi[0];
+  pi[1] = pk[1] & L.mi[1];
+  const uint32_t i0 = sad4(pi[1], sad4(pi[0], 0u));
+  if (yi == 0) a.s0_r0 += r;
+  else if (yi < 16) a.s0_lo += r;
+  else if (yi < kBlock - 1) a.s0_hi += r;
+  else a.s0_r31 += r;
+  if (yi < 16) a.syu_lo += __umul24(r, (uint32_t)yi);  // (a row sum of 8 bytes: v_mad_u32_u24)
+  else a.syu_hi += __umul24(r, (uint32_t)yi);
+  uint32_t &sxu = inner ? a.sxu_in : a.sxu_e;
+  uint32_t &q = (yi >= 2 && yi <= kBlock - 3) ? a.q2 : (inner ? a.qb : a.qa);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    sxu = udot4(pk[k], L.xw[k], sxu);
+    a.sax = udot4(pk[k], L.aw[k], a.sax);
+    q = udot4(pi[k], pi[k], q);
+  }
+  if (yi <= 1) a.dyn += i0;
+  if (yi >= kBlock - 2) a.dyp += i0;
+  if (inner) {
+    a.i0 += i0;
+    a.iyu += __umul24(i0, (uint32_t)yi);
+    a.dxn = udot4(pk[0], L.wn, a.dxn);
+    a.dxp = udot4(pk[1], L.wp, a.dxp);
+    const uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)pk[0], 0xF9, 0xf, 0xf, true);  // quad_perm [1, 2, 3, 3]: the lane to the right
+    const uint32_t pv = (uint32_t)__builtin_amdgcn_mov_dpp((int)pk[1], 0x90, 0xf, 0xf, true);  // quad_perm [0, 0, 1, 2]: the lane to the left
+    const uint32_t pr[2] = {__builtin_amdgcn_alignbyte(pk[1], pk[0], 1) & L.mi[0], __builtin_amdgcn_alignbyte(nx, pk[1], 1) & L.mi[1]};
+    const uint32_t pl[2] = {__builtin_amdgcn_alignbyte(pk[0], pv, 3) & L.mi[0], __builtin_amdgcn_alignbyte(pk[1], pk[0], 3) & L.mi[1]};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      a.rr = udot4(pr[k], pr[k], a.rr);
+      a.rr = udot4(pl[k], pl[k], a.rr);
+      a.rl = udot4(pr[k], pl[k], a.rl);
+      a.du = udot4(pui[k], pd[k], a.du);
+      a.pos = udot4(pr[k], pd[k], a.pos);
+      a.pos = udot4(pl[k], pu[k], a.pos);
+      a.neg = udot4(pr[k], pu[k], a.neg);
+      a.neg = udot4(pl[k], pd[k], a.neg);
+    }
+  }
+}
+// The lane's shares of the block's fifteen values, in the moments buffer's order.  nrep: the block's rows past the bottom of
+// the plane, which are copies of row H - 1 -- and so is row 31 then: CLIP leaves them out.
+__device__ __forceinline__ void strip_totals(const StripSums &a, int c, int nrep, int (&v)[16]) {
+  const uint32_t s0 = a.s0_r0 + a.s0_lo + a.s0_hi + a.s0_r31;
+  v[kM_S0] = (int)s0;
+  v[kM_SXU] = (int)(a.sxu_in + a.sxu_e);
+  v[kM_SYU] = (int)(a.syu_lo + a.syu_hi);
+  v[kM_SAX] = (int)a.sax;
+  v[kM_SAY] = (int)((a.syu_hi - 16u * (a.s0_hi + a.s0_r31)) + (16u * (a.s0_r0 + a.s0_lo) - a.syu_lo));
+  v[kM_I0] = (int)a.i0;
+  // (sum p xi over columns 1 .. 30 = over 0 .. 31 less 31 p31; the interior rows' p31 = their row sums less their interior sums in lane 3)
+  v[kM_IXU] = (int)(a.sxu_in - (c == 3 ? 31u * (a.s0_lo + a.s0_hi - a.i0) : 0u));
+  v[kM_IYU] = (int)a.iyu;
+  v[kM_IPP] = (int)(a.q2 + a.qb);
+  v[kM_DXX] = (int)(a.rr - 2u * a.rl);
+  v[kM_DYY] = (int)(2u * a.q2 + a.qb + a.qa - 2u * a.du);
+  v[kM_DXY] = (int)(a.pos - a.neg);
+  v[kM_DX] = (int)(a.dxp - a.dxn);
+  v[kM_DY] = (int)(a.dyp - a.dyn);
+  v[kM_CLIP] = (int)(s0 - (uint32_t)nrep * a.s0_r31);
+  v[15] = 0;
+}
+// sums over the quads of 16 values, split between the lanes as in half_sums_split16's first two stages: on return lane c of a
+// quad holds in x[j] the quad's total of v[4 j + c]
+__device__ __forceinline__ void quad_sums_split16(const int (&v)[16], int (&x)[4]) {
+  const int lane = (int)(threadIdx.x & 63);
+  const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
+  int w[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int keep = b0 ? v[2 * i + 1] : v[2 * i], send = b0 ? v[2 * i] : v[2 * i + 1];
+    w[i] = keep + __builtin_amdgcn_update_dpp(0, send, 0xB1, 0xf, 0xf, false);  // quad_perm [1, 0, 3, 2]
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int keep = b1 ? w[2 * j + 1] : w[2 * j], send = b1 ? w[2 * j] : w[2 * j + 1];
+    x[j] = keep + __builtin_amdgcn_update_dpp(0, send, 0x4E, 0xf, 0xf, false);  // quad_perm [2, 3, 0, 1]
+  }
+}
+
 // the bytes of a packed 32-pixel row from column wv (1 .. 31) on := the byte of column wv - 1
 __device__ __forceinline__ void replicate_columns(uint32_t (&p)[8], int wv) {
   const int lk = (wv - 1) >> 2, lb = (wv - 1) & 3;
