@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("G1S_LIB") or os.path.join(_HERE, "libg1s_diff.so")  #
 
 G1S_OK = 0
 G1S_DENOISE_JOINT_CHROMA = 1
+G1S_AUTO_PRIOR, G1S_AUTO_STRENGTH = 1, 2
 G1S_ERR_CAPACITY = -8
 ERRORS = {
     -1: "G1S_ERR_INVALID",
@@ -181,6 +182,22 @@ class G1SMeasureTRecord(C.Structure):
     ]
 
 
+class G1SNlfOpts(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("device", C.c_int32),
+        ("batch_frames", C.c_uint32),
+    ]
+
+
+class G1SNlfRecord(C.Structure):
+    _fields_ = [
+        ("n", (C.c_uint64 * 32) * 3),
+        ("a", (C.c_uint64 * 32) * 3),
+        ("q", (C.c_uint64 * 32) * 3),
+    ]
+
+
 class G1SSurface(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -280,6 +297,18 @@ SYMBOLS = [
     ("g1s_estimate_last_error", C.c_char_p, [C.c_void_p]),
     ("g1s_estimate_free", None, [C.c_void_p]),
     ("g1s_format_estimates", C.c_long, [C.POINTER(C.c_double), C.c_size_t, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SNlfOpts)]),
+    ("g1s_nlf_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame)]),
+    ("g1s_nlf_finish", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_nlf_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_nlf_last_error", C.c_char_p, [C.c_void_p]),
+    ("g1s_nlf_free", None, [C.c_void_p]),
+    ("g1s_nlf_sum", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_nlf_sigma", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    ("g1s_nlf_strength", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
+    ("g1s_denoise_curve_sigma", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("g1s_format_noise_levels", C.c_long, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SNlfOpts), C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
     ("g1s_y4m_open", C.c_void_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
     ("g1s_y4m_get_info", C.c_int, [C.c_void_p, C.POINTER(G1SY4MInfo)]),
     ("g1s_y4m_next", C.c_int, [C.c_void_p, C.POINTER(G1SFrame)]),
@@ -323,6 +352,11 @@ SYMBOLS = [
                                                 C.c_uint32, C.c_char_p, C.c_size_t]),
     ("g1s_diff_y4m_file_denoised_motion", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32,
                                                     C.c_char_p, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    ("g1s_denoise_y4m_file_auto", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int32,
+                                              C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised_auto", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32,
+                                                  C.c_char_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.c_char_p, C.c_size_t]),
     ("g1s_denoise_drain", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("g1s_denoise_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
     ("g1s_denoise_sync", C.c_int, [C.c_void_p]),

@@ -27,6 +27,7 @@ SAME_INPUTS = ("Source and denoised paths are the same. This is probably a typo,
                "empty diff. Exiting.")
 NOT_OVERWRITING = "Not overwriting existing file. Exiting."
 SAME_OUTPUTS = "--temporal and -o name the same file: the two reports would overwrite each other. Exiting."
+SAME_LEVELS = "--levels and -o name the same file: the two outputs would overwrite each other. Exiting."
 NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
 BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
 DENOISE_NO_FILTERS = "--denoise does not combine with --filters (the denoiser runs on the source as it is read). Exiting."
@@ -38,6 +39,11 @@ KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs 
 PRIOR_NEEDS_TABLE = "--prior-range and --prior-segment say how --grain-prior is used: they need --grain-prior. Exiting."
 PRIOR_12_BIT = ("--grain-prior filters luma in a 12-bit domain: a 12-bit input has no headroom there (8 and 10 bits are "
                 "supported). Exiting.")
+AUTO_PRIOR_AND_TABLE = "--auto-prior measures the prior that --grain-prior would read from a table: they do not combine. Exiting."
+AUTO_STRENGTH_AND_STRENGTH = "--auto-strength measures what --strength and --chroma-strength would set: they do not combine. Exiting."
+AUTO_NEEDS_FLAG = "--profile-frames and --levels-min-count say how --auto-prior and --auto-strength measure: they need one of them. Exiting."
+AUTO_BAD_NUMBER = "--profile-frames and --levels-min-count must not be negative. Exiting."
+AUTO_NEEDS_FILE = "--auto-prior and --auto-strength read the input twice: %s is not a regular file. Exiting."
 PRIOR_BAD_TABLE = "Invalid grain prior: %s. Exiting."
 PRIOR_BAD_SEGMENT = "--prior-segment %d is not in the grain prior (%d segments). Exiting."
 
@@ -91,10 +97,66 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
                    help="with --grain-prior: use the table's segment K (from 0) alone instead of the mean of all segments")
 
 
+    p.add_argument("--auto-prior", action="store_true",
+                   help="measure the clip's noise level at each intensity in a pre-pass and let the luma strength follow it: "
+                        "--grain-prior without a table (8- and 10-bit inputs; --prior-range applies)")
+    p.add_argument("--auto-strength", action="store_true",
+                   help="set --strength and --chroma-strength from the noise the pre-pass measures: h = sqrt(2) sigma")
+    p.add_argument("--profile-frames", type=int, default=0, metavar="N",
+                   help="with --auto-prior / --auto-strength: measure the first N frames only (default 0: all)")
+    p.add_argument("--levels-min-count", type=int, default=0, metavar="N",
+                   help="with --auto-prior / --auto-strength: smooth samples an intensity bin needs to take part (default 4096)")
+
+
 def _denoise_parameters(args) -> dict:
     return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
                 chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
-                grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range)
+                grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range,
+                auto_prior=args.auto_prior, auto_strength=args.auto_strength, profile_frames=args.profile_frames,
+                levels_min_count=args.levels_min_count)
+
+
+def _auto_refused(input: str, parameters: dict) -> bool:
+    """The refusals of --auto-prior / --auto-strength / --profile-frames / --levels-min-count, each a logged line: True when
+    one was logged."""
+    import stat
+
+    prior, strength = parameters.get("auto_prior", False), parameters.get("auto_strength", False)
+    frames, count = parameters.get("profile_frames", 0), parameters.get("levels_min_count", 0)
+    if frames < 0 or count < 0:
+        log.error(AUTO_BAD_NUMBER)
+        return True
+    if not prior and not strength:
+        if frames or count:
+            log.error(AUTO_NEEDS_FLAG)
+            return True
+        return False
+    if prior and parameters.get("grain_prior") is not None:
+        log.error(AUTO_PRIOR_AND_TABLE)
+        return True
+    if strength and (parameters.get("strength", 0.0) or parameters.get("chroma_strength", 0.0)):
+        log.error(AUTO_STRENGTH_AND_STRENGTH)
+        return True
+    try:
+        regular = stat.S_ISREG(os.stat(input).st_mode)
+    except OSError:
+        return False  # (the command says what is wrong with its input)
+    if not regular:
+        log.error(AUTO_NEEDS_FILE, input)
+        return True
+    if prior:
+        from .ingest import Y4MReader
+
+        try:
+            y = Y4MReader(input)
+        except ValueError:
+            return False
+        bit_depth = y.details.bit_depth
+        y.close()
+        if bit_depth == 12:
+            log.error(PRIOR_12_BIT.replace("--grain-prior", "--auto-prior"))
+            return True
+    return False
 
 
 def _motion_refused(parameters: dict) -> bool:
@@ -175,6 +237,9 @@ def build_parser() -> argparse.ArgumentParser:
     e.add_argument("-o", "--output", required=True, help="The path to the output file.")
     e.add_argument("-y", "--overwrite", action="store_true", help="Overwrite the output file without prompting.")
     e.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
+    e.add_argument("--levels", metavar="PATH", default=None,
+                   help="also write the clip's noise levels: sigma per intensity bin and plane and the strength they imply for "
+                        "`denoise`, from the same read of the clip")
     r = sub.add_parser("render", help="Synthesizes the film grain of a table onto a video (y4m input and output): what a decoder "
                                       "shows for the clip encoded with the table (AV1 specification, film grain synthesis process).")
     r.add_argument("input", help="The (denoised) file to put grain on.")
@@ -229,7 +294,7 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
         return -1
-    if _prior_refused(source, (output, keep_denoised), parameters):
+    if _prior_refused(source, (output, keep_denoised), parameters) or _auto_refused(source, parameters):
         return -1
     for path in (output, keep_denoised):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
@@ -285,19 +350,27 @@ def diff_command(source: str, denoised: Optional[str], output: str, overwrite: b
     return frames
 
 
-def estimate_command(source: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm) -> int:
+def estimate_command(source: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
+                     levels: Optional[str] = None) -> int:
     """Commands::Estimate (src/main.rs:534-608): the refusals of :541-560, one estimate_plane_noise per frame, "filmgrn1" and a
-    "{:.3}" line per frame (-1 for None), "Done, wrote output file to ...".  Returns the frame count, -1 after a refusal."""
+    "{:.3}" line per frame (-1 for None), "Done, wrote output file to ...".  --levels PATH is a second output, the clip's
+    noise levels.  Returns the frame count, -1 after a refusal."""
     from .estimate import estimate_y4m_file
 
-    if _same_path(source, output):
+    if _same_path(source, output) or (levels is not None and _same_path(source, levels)):
         log.error(SAME_AS_OUTPUT)
         return -1
-    if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
-        log.warning(NOT_OVERWRITING)
+    if levels is not None and _same_path(output, levels):
+        log.error(SAME_LEVELS)
         return -1
-    frames = estimate_y4m_file(source, output, device=device)
+    for path in (output, levels):
+        if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
+            log.warning(NOT_OVERWRITING)
+            return -1
+    frames = estimate_y4m_file(source, output, device=device, levels=levels)
     log.info("Done, wrote output file to %s", output)
+    if levels is not None:
+        log.info("Done, wrote noise levels to %s", levels)
     return frames
 
 
@@ -331,7 +404,7 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)
         return -1
-    if _prior_refused(input, (output,), parameters):
+    if _prior_refused(input, (output,), parameters) or _auto_refused(input, parameters):
         return -1
     if os.path.exists(output) and not overwrite and not confirm(f"File {output} exists. Overwrite?"):
         log.warning(NOT_OVERWRITING)
@@ -429,7 +502,7 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
     elif args.command == "estimate":
         try:
-            estimate_command(args.source, args.output, args.overwrite, args.device)
+            estimate_command(args.source, args.output, args.overwrite, args.device, levels=args.levels)
         except Exception as e:
             log.error("%s", e)
             return 1

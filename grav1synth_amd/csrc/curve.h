@@ -36,12 +36,17 @@ inline int scale_lut(const int lut[256], int index, uint32_t bit_depth) {
   return start + (((end - start) * rem + (1 << (sh - 1))) >> sh);
 }
 
-// Rules 12 and 13: fwd[1 << B], inv[4096].  "" when fine, else the refusal.
-inline std::string build(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+// the bit depths and ranges rule 12 has.  "" when fine, else the refusal.
+inline std::string check_depth_range(uint32_t bit_depth, uint32_t range) {
   if (bit_depth == 12) return "a grain prior needs headroom above the clip's bit depth: the stabilised domain is 12 bits, so a 12-bit clip is refused";
   if (bit_depth != 8 && bit_depth != 10) return "a grain prior is defined for bit depths 8 and 10";
   const uint32_t rmax = 1u << (kStabBits - bit_depth);
   if (range > rmax) return "prior range must be 1.." + std::to_string(rmax) + " at " + std::to_string(bit_depth) + " bits (0 = the default)";
+  return "";
+}
+
+// Rule 12 up to s(v): the mean scaling function of the segments, v = 0 .. M.  "" when fine, else the refusal.
+inline std::string s_from_segments(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, std::vector<uint64_t> &s) {
   if (!segs || n < 1) return "a grain prior needs at least one segment";
   for (size_t i = 0; i < n; ++i) {
     if (segs[i].num_y_points > G1S_NUM_Y_POINTS) return "segment " + std::to_string(i) + ": more than 14 luma scaling points";
@@ -49,15 +54,24 @@ inline std::string build(const g1s_segment_t *segs, size_t n, uint32_t bit_depth
       if (segs[i].scaling_points_y[k + 1][0] <= segs[i].scaling_points_y[k][0])
         return "segment " + std::to_string(i) + ": luma scaling points must have increasing values";
   }
-  const uint32_t R = range ? range : (rmax < 4u ? rmax : 4u), M = (1u << bit_depth) - 1;
-  std::vector<uint64_t> s((size_t)M + 1, 0);
+  const uint32_t M = (1u << bit_depth) - 1;
+  s.assign((size_t)M + 1, 0);
   for (size_t i = 0; i < n; ++i) {
     int lut[256];
     scaling_lut(segs[i], lut);
     for (uint32_t v = 0; v <= M; ++v) s[v] += (uint64_t)scale_lut(lut, (int)v, bit_depth);
   }
+  for (uint32_t v = 0; v <= M; ++v) s[v] = (s[v] + (n >> 1)) / n;
+  return "";
+}
+
+// Rule 12 from "floor = ..." onwards and rule 13, on s(v), v = 0 .. M (a bit depth and a range check_depth_range passed):
+// fwd[1 << B], inv[4096].  "" when fine, else the refusal.
+inline std::string curve_from_s(const std::vector<uint64_t> &s, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  const uint32_t rmax = 1u << (kStabBits - bit_depth);
+  const uint32_t R = range ? range : (rmax < 4u ? rmax : 4u), M = (1u << bit_depth) - 1;
   uint64_t top = 0;
-  for (uint32_t v = 0; v <= M; ++v) s[v] = (s[v] + (n >> 1)) / n, top = s[v] > top ? s[v] : top;
+  for (uint32_t v = 0; v <= M; ++v) top = s[v] > top ? s[v] : top;
   const uint64_t floor = top ? (top + R - 1) / R : 1;  // max(1, ceil(max s / R))
   std::vector<uint64_t> Cs((size_t)M + 2, 0);          // C(x) = sum over v < x of r(v)
   for (uint32_t v = 0; v <= M; ++v) Cs[v + 1] = Cs[v] + ((1ull << 24) / (s[v] > floor ? s[v] : floor));
@@ -73,6 +87,23 @@ inline std::string build(const g1s_segment_t *segs, size_t n, uint32_t bit_depth
     inv[y] = (uint16_t)(x < M && (uint32_t)fwd[x + 1] - y < y - (uint32_t)fwd[x] ? x + 1 : x);
   }
   return "";
+}
+
+// Rules 12 and 13: fwd[1 << B], inv[4096].  "" when fine, else the refusal.
+inline std::string build(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  std::string why = check_depth_range(bit_depth, range);
+  std::vector<uint64_t> s;
+  if (why.empty()) why = s_from_segments(segs, n, bit_depth, s);
+  return why.empty() ? curve_from_s(s, bit_depth, range, fwd, inv) : why;
+}
+
+// The same from a given s[1 << B] (noise levels, rule N6): the refusals of the bit depth and the range, then the curve.
+inline std::string build_sigma(const uint8_t *s8, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  const std::string why = check_depth_range(bit_depth, range);
+  if (!why.empty()) return why;
+  if (!s8) return "a curve needs the scaling function it is made from";
+  const std::vector<uint64_t> s(s8, s8 + ((size_t)1 << bit_depth));
+  return curve_from_s(s, bit_depth, range, fwd, inv);
 }
 
 // what g1s_denoise_new_curve asks of a pair it is handed.  "" when fine.

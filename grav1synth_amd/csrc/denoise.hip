@@ -15,6 +15,7 @@
 // them, the last D that were: their planes are the neighbours of what comes next.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <cmath>
@@ -30,6 +31,7 @@
 #include "curve_row.hip.h"
 #include "denoise_tile.hip.h"
 #include "frame_op.h"
+#include "nlf.h"
 
 extern "C" void g1s_diff_set_error_text_(g1s_diff_t *, const char *);
 extern "C" int32_t g1s_diff_device_(const g1s_diff_t *);
@@ -572,9 +574,11 @@ int g1s_denoise::end_clip() {
 
 // A grain prior as the file commands take it: the table at `path`, its segment `segment` alone or (negative) the mean of
 // all of them, range R (0 = the default).  load() reads and parses; make() is g1s_denoise_curve for the clip's depth.
+// measure() is the other way to one: the noise levels of the clip itself (rules N5 - N6) through g1s_denoise_curve_sigma.
 struct Prior {
   std::vector<g1s_segment_t> segs;
   uint32_t range = 0;
+  std::vector<uint16_t> pair_fwd, pair_inv;  // a curve that is there already (a measured prior): make() hands it on
   std::string load(const char *path, uint32_t range_, int32_t segment) {
     range = range_;
     std::string text;
@@ -599,8 +603,20 @@ struct Prior {
     return "";
   }
   std::string make(uint32_t bit_depth, std::vector<uint16_t> &fwd, std::vector<uint16_t> &inv) const {
+    if (!pair_fwd.empty()) {
+      fwd = pair_fwd, inv = pair_inv;
+      return "";
+    }
     fwd.assign((size_t)1 << (bit_depth <= 12 ? bit_depth : 12), 0), inv.assign(g1s_cv::kInvEntries, 0);
     return g1s_cv::build(segs.data(), segs.size(), bit_depth, range, fwd.data(), inv.data());
+  }
+  std::string measure(const g1s_nlf_record_t &total, uint32_t bit_depth, uint32_t range_, uint64_t min_count) {
+    std::string why = g1s_cv::check_depth_range(bit_depth, range_);
+    if (!why.empty()) return why;
+    std::vector<uint8_t> sg((size_t)1 << bit_depth);
+    if (!(why = g1s_nl::sigma(total, bit_depth, min_count, sg.data())).empty()) return why;
+    pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
+    return g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data());
   }
   // the denoiser for a clip of this depth; NULL with the global error text set
   g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags, uint32_t motion_range = 0) const {
@@ -921,16 +937,9 @@ int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_de
   return g1s_denoise_y4m_file_motion(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, 0, err, cap);
 }
 
-int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err, size_t cap) {
-  Prior prior;
-  if (prior_tbl) {
-    const std::string why = prior.load(prior_tbl, prior_range, prior_segment);
-    if (!why.empty()) {
-      if (err && cap) snprintf(err, cap, "%s", why.c_str());
-      return G1S_ERR_INVALID;
-    }
-  }
+// what g1s_denoise_y4m_file_motion and g1s_denoise_y4m_file_auto do once they have their prior (or none)
+static int64_t denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                const Prior *prior, uint32_t motion_range, char *err, size_t cap) {
   // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
   // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
   struct Driver {
@@ -950,7 +959,77 @@ int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_d
     const char *last_error() const { return g1s_denoise_last_error(g); }
     void close() { g1s_denoise_free(g); }
   };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range});
+  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior, motion_range});
+}
+
+int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err, size_t cap) {
+  Prior prior;
+  if (prior_tbl) {
+    const std::string why = prior.load(prior_tbl, prior_range, prior_segment);
+    if (!why.empty()) {
+      if (err && cap) snprintf(err, cap, "%s", why.c_str());
+      return G1S_ERR_INVALID;
+    }
+  }
+  return denoise_y4m_file(in, out, opts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range, err, cap);
+}
+
+// The pre-pass of the *_auto file commands: the refusals of the flags, the noise levels of the first profile_frames frames of
+// `source` on `device`, then the prior's curve into *prior (G1S_AUTO_PRIOR) and the two strengths into *d (G1S_AUTO_STRENGTH).
+// "" when fine.
+static std::string auto_prepass(const char *source, int32_t device, uint32_t auto_flags, uint64_t profile_frames, uint64_t min_count, const char *prior_tbl,
+                                uint32_t prior_range, Prior *prior, g1s_denoise_opts_t *d) {
+  if (auto_flags & ~(G1S_AUTO_PRIOR | G1S_AUTO_STRENGTH)) return "unknown auto flags";
+  if ((auto_flags & G1S_AUTO_PRIOR) && prior_tbl) return "an auto prior does not combine with a grain prior table";
+  if ((auto_flags & G1S_AUTO_STRENGTH) && (d->strength != 0.0 || d->chroma_strength != 0.0)) return "an auto strength does not combine with a given strength";
+  if (!source) return "null path";
+  struct stat st;
+  if (stat(source, &st) == 0 && !S_ISREG(st.st_mode)) return std::string(source) + " cannot be read twice (not a regular file): the auto flags need a pre-pass";
+  g1s_nlf_opts_t no{};
+  no.struct_size = sizeof no, no.device = device;
+  g1s_nlf_record_t total;
+  char err[512] = "";
+  const int64_t n = g1s_nlf_y4m_file(source, nullptr, &no, profile_frames, &total, err, sizeof err);
+  if (n < 0) return err;
+  g1s_y4m_t *y = g1s_y4m_open(source, err, sizeof err);
+  if (!y) return err;
+  g1s_y4m_info_t info;
+  g1s_y4m_get_info(y, &info);
+  g1s_y4m_close(y);
+  if (auto_flags & G1S_AUTO_PRIOR) {
+    const std::string why = prior->measure(total, info.bit_depth, prior_range, min_count);
+    if (!why.empty()) return why;
+  }
+  if (auto_flags & G1S_AUTO_STRENGTH) {
+    const std::string why = g1s_nl::strength(total, info.bit_depth, min_count, 0, &d->strength);
+    if (!why.empty()) return why;
+    double hc = 0;
+    if (g1s_nl::strength(total, info.bit_depth, min_count, 1, &hc).empty()) d->chroma_strength = hc;  // (else: the luma strength)
+  }
+  return "";
+}
+
+int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                  const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                  uint64_t profile_frames, uint64_t min_count, char *err, size_t cap) {
+  if (!auto_flags) return g1s_denoise_y4m_file_motion(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, err, cap);
+  if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
+    if (err && cap) snprintf(err, cap, "%s", "g1s_denoise_opts_t.struct_size mismatch");
+    return G1S_ERR_INVALID;
+  }
+  Prior prior;
+  g1s_denoise_opts_t d{};
+  if (opts) d = *opts;
+  d.struct_size = sizeof d;
+  if (!opts) d.device = -1;
+  std::string why = auto_prepass(in, d.device, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
+  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
+  if (!why.empty()) {
+    if (err && cap) snprintf(err, cap, "%s", why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return denoise_y4m_file(in, out, &d, temporal_radius, flags, prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, err, cap);
 }
 
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
@@ -981,6 +1060,10 @@ int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, co
                                            frames_out, err, cap);
 }
 
+static int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const Prior *prior_or_null,
+                                  uint32_t motion_range, uint64_t *frames_out, char *err, size_t cap);
+
 int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                       const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                       uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint64_t *frames_out, char *err,
@@ -997,6 +1080,44 @@ int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, c
     const std::string no = prior.load(prior_tbl, prior_range, prior_segment);
     if (!no.empty()) return refuse(G1S_ERR_INVALID, no);
   }
+  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range, frames_out,
+                                err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                    const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                    uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                    uint64_t min_count, uint64_t *frames_out, char *err, size_t cap) {
+  if (!auto_flags)
+    return g1s_diff_y4m_file_denoised_motion(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment,
+                                             motion_range, frames_out, err, cap);
+  auto refuse = [&](int code, const std::string &m) {
+    if (err && cap) snprintf(err, cap, "%s", m.c_str());
+    return code;
+  };
+  if (frames_out) *frames_out = 0;
+  if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
+  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
+  if (dopts && dopts->struct_size != sizeof(g1s_denoise_opts_t)) return refuse(G1S_ERR_INVALID, "g1s_denoise_opts_t.struct_size mismatch");
+  Prior prior;
+  g1s_denoise_opts_t d{};
+  if (dopts) d = *dopts;
+  d.struct_size = sizeof d;
+  std::string why = auto_prepass(source, opts ? opts->device : -1, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
+  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
+  if (!why.empty()) return refuse(G1S_ERR_INVALID, why);
+  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, &d, temporal_radius, flags,
+                                prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, frames_out, err, cap);
+}
+
+// what g1s_diff_y4m_file_denoised_motion and g1s_diff_y4m_file_denoised_auto do once they have their prior (or none)
+static int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const Prior *prior_or_null,
+                                  uint32_t motion_range, uint64_t *frames_out, char *err, size_t cap) {
+  auto refuse = [&](int code, const std::string &m) {
+    if (err && cap) snprintf(err, cap, "%s", m.c_str());
+    return code;
+  };
   const std::string header = y4m_header_line(source);
   g1s_y4m_t *y = g1s_y4m_open(source, err, cap);
   if (!y) return G1S_ERR_INVALID;
@@ -1033,8 +1154,8 @@ int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, c
     if (dopts) d = *dopts;
     d.struct_size = sizeof d;
     d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = prior_tbl ? prior.open(info.bit_depth, &d, temporal_radius, flags, motion_range)
-                   : g1s_denoise_new_motion(info.bit_depth, &d, temporal_radius, flags, nullptr, nullptr, motion_range);
+    dn = prior_or_null ? prior_or_null->open(info.bit_depth, &d, temporal_radius, flags, motion_range)
+                       : g1s_denoise_new_motion(info.bit_depth, &d, temporal_radius, flags, nullptr, nullptr, motion_range);
   }
   if (!dn) {
     rc = G1S_ERR_INVALID, why = g1s_last_global_error();

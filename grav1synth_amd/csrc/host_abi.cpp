@@ -16,6 +16,7 @@
 #include "curve.h"
 #include "fold.h"
 #include "host_pool.h"
+#include "nlf.h"
 #include "record.h"
 
 namespace g1s {
@@ -486,6 +487,54 @@ int g1s_denoise_curve(const g1s_segment_t *segs, size_t n, uint32_t bit_depth, u
     return G1S_ERR_INVALID;
   }
   return G1S_OK;
+}
+
+// the same from a scaling function that is given (noise levels, rule N6)
+int g1s_denoise_curve_sigma(const uint8_t *s, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv) {
+  const std::string why = !fwd || !inv ? std::string("g1s_denoise_curve_sigma needs both output tables") : g1s_cv::build_sigma(s, bit_depth, range, fwd, inv);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return G1S_OK;
+}
+
+// noise levels, rules N4 - N8 (nlf.h): what is done with a record needs no device
+int g1s_nlf_sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) {
+  if (!total || (n && !recs)) return G1S_ERR_INVALID;
+  return g1s_nl::sum(recs, n, total) ? G1S_OK : G1S_ERR_INVALID;
+}
+
+int g1s_nlf_sigma(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
+  std::string why = !total || !s ? std::string("g1s_nlf_sigma needs a record and the output table") : g1s_cv::check_depth_range(bit_depth, 0);
+  if (why.empty()) why = g1s_nl::sigma(*total, bit_depth, min_count, s);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return G1S_OK;
+}
+
+int g1s_nlf_strength(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
+  std::string why;
+  if (!total || !h) why = "g1s_nlf_strength needs a record and the output value";
+  else if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) why = "noise levels are defined for bit depths 8, 10 and 12";
+  else if (plane_class > 1) why = "plane_class is 0 (luma) or 1 (chroma)";
+  else why = g1s_nl::strength(*total, bit_depth, min_count, plane_class, h);
+  if (!why.empty()) {
+    g1s_set_global_error_(why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return G1S_OK;
+}
+
+long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, uint64_t min_count, char *buf,
+                             size_t cap) {
+  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
+  const std::string s = g1s_nl::report(*total, frames, bit_depth, nplanes, min_count);
+  if (s.size() > cap) return G1S_ERR_CAPACITY;
+  std::memcpy(buf, s.data(), s.size());
+  return (long)s.size();
 }
 
 }  // extern "C"

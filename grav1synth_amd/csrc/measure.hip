@@ -35,6 +35,7 @@
 #include "../../include/g1s_diff.h"
 #include "fold.h"
 #include "frame_op.h"
+#include "wave_sum.hip.h"
 
 namespace {
 
@@ -71,22 +72,6 @@ template <int BPS>
 __device__ __forceinline__ int sample(const uint8_t *plane, uint32_t stride, int x, int y) {
   const uint8_t *row = plane + (size_t)y * stride;
   return BPS == 2 ? (int)reinterpret_cast<const uint16_t *>(row)[x] : (int)row[x];
-}
-
-// full-wave integer sum in the VALU (DPP), every lane taking part; the total is read from lane 63
-__device__ __forceinline__ int wave_sum(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast31 -> rows 2, 3
-  return __builtin_amdgcn_readlane(v, 63);
-}
-// the same for lane values up to 2^31 in size: v = (v >> 16) 2^16 + (v & 0xffff), the halves summed apart
-__device__ __forceinline__ long long wave_sum_wide(int v) {
-  const int lo = wave_sum(v & 0xffff), hi = wave_sum(v >> 16);
-  return (long long)hi * 65536 + lo;
 }
 
 template <int BPS>

@@ -180,17 +180,24 @@ class Denoiser(FrameOp):
 
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                      strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
-                     grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0) -> int:
+                     grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0,
+                     auto_prior: bool = False, auto_strength: bool = False, profile_frames: int = 0, levels_min_count: int = 0) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
     function the luma strength follows (grain_curve() with prior_range and prior_segment).  motion_range: as Denoiser takes
-    it.  Returns the number of frames."""
+    it.  auto_prior / auto_strength: the curve and the strengths from the clip's own noise levels (rules N5 - N7), measured
+    in a pre-pass over its first profile_frames frames (0 = all) with levels_min_count as Nmin (0 = 4096).  Returns the
+    number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
     if grain_prior is None and (prior_range or prior_segment is not None):
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
     prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
-    if motion_range:
+    if auto_prior or auto_strength:
+        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
+        n = L.g1s_denoise_y4m_file_auto(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                        motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, err, len(err))
+    elif motion_range:
         n = L.g1s_denoise_y4m_file_motion(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
                                           motion_range & 0xFFFFFFFF, err, len(err))
     else:

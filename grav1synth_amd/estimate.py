@@ -4,16 +4,33 @@
 >>> est.estimate_frame(y_plane)                 # numpy / torch (host or cuda), u8 or u16; only the luma plane is read
 >>> estimates = est.finish()                    # List[Optional[float]]: None where the reference has None
 >>> open(out, "wb").write(format_estimates(estimates))     # "filmgrn1" + one "{:.3}" line per frame (-1 for None)
+
+Noise levels (include/g1s_diff.h, rules N1 - N8): the same stencil summed per intensity bin and per plane, and what a
+clip's record says about the clip -- the curve of a grain prior and the strength, for `Denoiser`.
+
+>>> meter = NoiseLevelMeter(10)
+>>> meter.frame([y, u, v], xdec=1, ydec=1)      # numpy arrays or torch tensors, as GrainMeter.measure takes them
+>>> total = noise_levels_sum(meter.finish())    # numpy structured array, one entry a frame: n, a, q (3 x 32)
+>>> fwd, inv = noise_prior(total, 10)           # rules N5 - N6 and the curve of rules 12 - 13
+>>> h_luma, h_chroma = auto_strength(total, 10) # rule N7
+>>> Denoiser(10, curve=(fwd, inv), strength=h_luma, chroma_strength=h_chroma or 0.0)
 """
 from __future__ import annotations
 
 import ctypes as C
 import logging
-from typing import List, Optional
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
 
 from . import _lib
-from ._lib import G1SError
+from ._frame_op import FrameOp
+from ._lib import G1SError, G1SNlfOpts, G1SNlfRecord
 from .diff import Frame
+
+# g1s_nlf_record_t
+NLF_RECORD = np.dtype([("n", "<u8", (3, 32)), ("a", "<u8", (3, 32)), ("q", "<u8", (3, 32))])
+assert NLF_RECORD.itemsize == C.sizeof(G1SNlfRecord)
 
 log = logging.getLogger("grav1synth")
 
@@ -84,21 +101,159 @@ def format_estimates(estimates) -> bytes:
     return buf.raw[:w]
 
 
-def estimate_y4m_file(source: str, output: str, *, device: int = -1) -> int:
-    """`grav1synth estimate SOURCE -o OUTPUT` for a .y4m input.  Returns the number of frames."""
+def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Optional[str] = None) -> int:
+    """`grav1synth estimate SOURCE -o OUTPUT [--levels PATH]` for a .y4m input: with `levels` the noise-level report of
+    the clip is written there, from the same read of the clip.  Returns the number of frames."""
     from .ingest import Y4MReader
 
     rd = Y4MReader(source)
-    est = NoiseEstimator(rd.details.bit_depth, device=device)
+    d = rd.details
+    est = NoiseEstimator(d.bit_depth, device=device)
+    meter = NoiseLevelMeter(d.bit_depth, device=device) if levels is not None else None
+    total = np.zeros((), NLF_RECORD)
     n = 0
     while True:
         planes = rd.get_frame()
         if planes is None:
             break
         est.estimate_frame(planes[0])
+        if meter is not None:
+            meter.frame(planes, d.xdec, d.ydec)
+            if (n + 1) % 32 == 0:
+                total = noise_levels_sum(np.concatenate([total.reshape(1), meter.finish()]))
         n += 1
     with open(output, "wb") as f:
         f.write(format_estimates(est.finish()))
+    if meter is not None:
+        total = noise_levels_sum(np.concatenate([total.reshape(1), meter.finish()]))
+        with open(levels, "wb") as f:
+            f.write(format_noise_levels(total, n, d.bit_depth, d.nplanes))
+        meter.close()
     est.close()
     rd.close()
     return n
+
+
+class NoiseLevelMeter(FrameOp):
+    """g1s_nlf_*: the noise level function of frames on the device (rules N1 - N4); no CPU fallback."""
+    _name = "nlf"
+
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0):
+        self._L = _lib.lib()
+        self.bit_depth = bit_depth
+        opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
+        self._h = self._L.g1s_nlf_new(bit_depth, C.byref(opts))
+        if not self._h:
+            raise G1SError(-5, self._L.g1s_last_global_error().decode())
+        self._keep: list = []  # planes the queued kernels still read
+
+    def frame(self, planes: Sequence, xdec: int = 1, ydec: int = 1, *, async_host: bool = False) -> None:
+        """Queues one frame ([y] or [y, u, v]); its record comes with finish().  Host planes are copied before the call
+        returns; async_host = True queues the copies of pinned torch tensors instead: they must stay as they are until
+        finish()."""
+        planes = list(planes)
+        if not hasattr(planes[0], "is_cuda"):
+            planes = [np.asarray(p) for p in planes]
+        keep: list = [planes]
+        pinned = async_host and hasattr(planes[0], "is_pinned") and not planes[0].is_cuda and planes[0].is_pinned()
+        f = Frame(planes, xdec, ydec, async_host=pinned).to_c(keep)
+        if f.on_device == 1:
+            import torch
+
+            torch.cuda.current_stream().synchronize()  # (the planes were produced on torch's stream)
+        self._keep.append(keep)
+        self._check(self._L.g1s_nlf_frame(self._h, C.byref(f)))
+
+    def finish(self, cap: Optional[int] = None) -> np.ndarray:
+        """Launches what is queued, waits, and returns the records since the last finish(), one a frame, in order.  cap:
+        the size of the buffer handed to the library (a test aid; too small raises G1S_ERR_CAPACITY and loses nothing)."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_nlf_finish(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), NLF_RECORD)
+        rc = self._L.g1s_nlf_finish(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def kernel_times(self, enable: bool = True) -> Tuple[float, float, int]:
+        """(ms in the luma launches, ms in the chroma launches, frames) of the timed batches so far (HIP events)."""
+        a, b, n = C.c_double(), C.c_double(), C.c_uint64()
+        self._L.g1s_nlf_set_timing(self._h, int(enable), C.byref(a), C.byref(b), C.byref(n))
+        return a.value, b.value, n.value
+
+
+def noise_levels_sum(records: np.ndarray) -> np.ndarray:
+    """Rule N4: a clip's record from its frames' (g1s_nlf_sum; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, NLF_RECORD).reshape(-1)
+    total = np.zeros((), NLF_RECORD)
+    rc = _lib.lib().g1s_nlf_sum(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's sums leave 64 bits")
+    return total
+
+
+def noise_sigma(record: np.ndarray, bit_depth: int, min_count: int = 0) -> np.ndarray:
+    """Rules N5 - N6: the scaling function s[1 << bit_depth] of a clip's record (g1s_nlf_sigma; host only)."""
+    L = _lib.lib()
+    record = np.ascontiguousarray(record, NLF_RECORD)
+    s = np.zeros(1 << min(max(bit_depth, 0), 16), np.uint8)
+    rc = L.g1s_nlf_sigma(record.ctypes.data, bit_depth, min_count, s.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return s
+
+
+def noise_prior(record: np.ndarray, bit_depth: int, range: int = 0, min_count: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """(fwd, inv): the variance-stabilising curve of a clip's record, rules N5 - N6 then rules 12 - 13 of `denoise`, as
+    Denoiser(curve=...) takes it (host only)."""
+    L = _lib.lib()
+    s = noise_sigma(record, bit_depth, min_count)
+    fwd, inv = np.zeros(1 << bit_depth, np.uint16), np.zeros(4096, np.uint16)
+    rc = L.g1s_denoise_curve_sigma(s.ctypes.data, bit_depth, range, fwd.ctypes.data, inv.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return fwd, inv
+
+
+def auto_strength(record: np.ndarray, bit_depth: int, min_count: int = 0) -> Tuple[float, Optional[float]]:
+    """Rule N7: (h_luma, h_chroma) in 8-bit code values; h_chroma is None where the rule refuses (a luma-only clip); a
+    refusal for luma raises (host only)."""
+    L = _lib.lib()
+    record = np.ascontiguousarray(record, NLF_RECORD)
+    h = C.c_double()
+    if L.g1s_nlf_strength(record.ctypes.data, bit_depth, min_count, 0, C.byref(h)):
+        raise G1SError(-1, L.g1s_last_global_error().decode())
+    h_luma = h.value
+    h_chroma = None if L.g1s_nlf_strength(record.ctypes.data, bit_depth, min_count, 1, C.byref(h)) else h.value
+    return h_luma, h_chroma
+
+
+def format_noise_levels(total: np.ndarray, frames: int, bit_depth: int, nplanes: int = 3, min_count: int = 0, cap: int = 1 << 16) -> bytes:
+    """The report of a clip's record (g1s_format_noise_levels; host only).  cap: the size of the buffer handed to the
+    library (a test aid)."""
+    total = np.ascontiguousarray(total, NLF_RECORD)
+    buf = C.create_string_buffer(max(cap, 1))
+    w = _lib.lib().g1s_format_noise_levels(total.ctypes.data, frames, bit_depth, nplanes, min_count, buf, cap)
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_noise_levels failed")
+    return buf.raw[:w]
+
+
+def noise_levels_y4m_file(source: str, output: Optional[str] = None, *, device: int = -1, batch_frames: int = 0,
+                          max_frames: int = 0) -> Tuple[int, np.ndarray]:
+    """The noise levels of the first max_frames frames (0 = all) of a .y4m file (g1s_nlf_y4m_file): the report into
+    `output` when it is given.  Returns (frames, the clip's record)."""
+    opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
+    err = C.create_string_buffer(512)
+    total = np.zeros((), NLF_RECORD)
+    n = _lib.lib().g1s_nlf_y4m_file(str(source).encode(), None if output is None else str(output).encode(), C.byref(opts), max_frames,
+                                    total.ctypes.data, err, len(err))
+    if n < 0:
+        raise G1SError(int(n), err.value.decode())
+    return int(n), total

@@ -408,6 +408,106 @@ void g1s_estimate_free(g1s_estimate_t *);
 /* The command's output (src/main.rs:596-603): "filmgrn1\n" then "{:.3}\n" per frame.  Bytes written or G1S_ERR_CAPACITY. */
 long g1s_format_estimates(const double *estimates, size_t n, char *buf, size_t cap);
 
+/* ---- noise levels, rules N1 - N8: how much noise a single clip has at each intensity, per plane ----
+ * The estimator above folds a luma plane into one number.  A noise level function keeps its stencil and its gate and sums per
+ * intensity bin and per plane, so that one clip alone says what `denoise` otherwise has to be told: the shape of the grain
+ * over intensity (a prior's curve, rules 12 - 13 of `denoise`) and its size (the strength h).  Everything is integer except
+ * where a rule says otherwise.  A frame has bit depth B in {8, 10, 12}, one plane or three (xdec <= 1, ydec <= xdec);
+ * sh = B - 8, half = sh ? 1 << (sh - 1) : 0.  Plane c has size pw x ph and samples u; its INTERIOR is 1 <= x <= pw - 2,
+ * 1 <= y <= ph - 2, empty when either side is shorter than 3.
+ *  N1. Stencil.  At an interior p with 3 x 3 neighbourhood m_ij (row i, column j): Gx = (m00 - m02) + (m20 - m22) +
+ *      2 (m10 - m12), Gy = (m00 - m20) + (m02 - m22) + 2 (m01 - m21), L = 4 m11 - 2 (m01 + m21 + m10 + m12) + (m00 + m02 +
+ *      m20 + m22), all at full bit depth: the estimator's.  p COUNTS iff (|Gx| + |Gy| + half) >> sh < 50.
+ *  N2. Intensity, 32 bins.  Luma: S9(p) = the plain sum of the nine samples, k(p) = floor(S9 / (9 2^(B - 5))).  The box sum
+ *      is orthogonal to the Laplacian mask (the mask's weights sum to zero), so binning by it does not select on the noise
+ *      being measured; binning by the sample itself would.  Chroma: rule 2 of `measure` on the frame's own luma: averageLuma
+ *      at (xs, ys) = (x << xdec, y << ydec), (Y(xs, ys) + Y(min(xs + 1, W - 1), ys) + 1) >> 1 if xdec, else Y(xs, ys); then
+ *      >> (B - 5).
+ *  N3. Sums.  Per plane and bin, over the counting p: n[k] the count (u64), a[k] = sum of (|L| + half) >> sh (u64: the
+ *      estimator's term), q[k] = sum of L^2 (u64).  |L| <= 8 (2^B - 1) (the centre and the corners against the four
+ *      neighbours: a checkerboard of 0 and 2^B - 1 reaches it and passes the gate), so one L^2 reaches 32760^2 =
+ *      1 073 217 600: four fit u32 and five do not.  Everything is exact for the largest frame the checks admit
+ *      (65536 x 65536: below 2^32 samples of less than 2^31 each).
+ *  N4. Record.  g1s_nlf_record_t, zeros for the planes a frame lacks.  A clip's record is the checked 64-bit sum of its
+ *      frames' (g1s_nlf_sum): an overflow is a refusal.  Identity: sum_k n[0][k] and sum_k a[0][k] are the estimator's two
+ *      sums of the frame, so a / (6 n) sqrt(pi / 2), formed with the same three operations, is g1s_estimate_finish's f64
+ *      bit for bit.
+ *  N5. Levels.  For a bin with n >= Nmin (min_count; 0 = 4096): t[k] = isqrt(floor(2^16 q[k] / (36 n[k]))), the product
+ *      formed in 128 bits.  The mask's squared weights sum to 36, so t = 256 sigma for white noise.
+ *  N6. Prior.  No valid luma bin: refused ("no luma bin has enough smooth samples for a prior").  Else, tmax the largest
+ *      valid t: y[k] = max(1, floor(255 t[k] / max(tmax, 1))); bin centres c_k = (k << (B - 5)) + (1 << (B - 6)); s(v),
+ *      v = 0 .. 2^B - 1: at or below the first valid centre that bin's y, at or above the last valid centre that bin's y,
+ *      between adjacent valid centres c_i < c_j: y_i + floor(((y_j - y_i)(v - c_i) 2 + (c_j - c_i)) / (2 (c_j - c_i))),
+ *      floor towards minus infinity.  s lies in 1 .. 255, the domain rule 12 of `denoise` already has; the curve is rule 12
+ *      from "floor = ..." onwards and rule 13 on this s unchanged (g1s_denoise_curve_sigma), so their proofs hold as they
+ *      stand.  A 12-bit clip is refused with rule 12's text.
+ *  N7. Strength.  h_luma = sqrt(2 Q / (36 N)) / 2^(B - 8), Q and N the q and n of plane 0 summed over all bins, taken as f64
+ *      from the exact integers (2 Q and 36 N are formed in f64).  Rule 3 of `denoise` gives a patch that differs only by
+ *      noise an expected weight of exp(-2 sigma^2 / h^2); h = sqrt(2) sigma puts it at 1/e: that is the derivation, there is
+ *      no tuning constant.  h_chroma: the same over planes 1 and 2 pooled.  Refused when N < Nmin or the result is outside
+ *      rule 3's 0 < h <= 1000.  Under a curve rule 14 makes h the strength at the curve's mean slope.
+ *  N8. Report.  g1s_format_noise_levels writes plain text; the grammar is at its declaration.
+ * The gate is the estimator's and has its bias: above about sigma = 5 eight-bit code values it thins the sample and keeps
+ * the quieter part.  In a numpy run of N1 - N3 on a noisy ramp it kept 64 % of the samples at sigma = 8, and the per-bin
+ * sigma stayed within 2.3 % of the truth.  The gate is not corrected for.
+ * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two chroma
+ * planes) and a small summing launch, on the meter's own stream.  Errors are sticky (g1s_nlf_last_error). */
+typedef struct {
+  uint64_t n[3][32];
+  uint64_t a[3][32];
+  uint64_t q[3][32];
+} g1s_nlf_record_t;
+typedef struct {
+  uint32_t struct_size; /* sizeof(g1s_nlf_opts_t) */
+  int32_t device;       /* HIP device ordinal; -1 = current device */
+  uint32_t batch_frames;
+} g1s_nlf_opts_t;
+typedef struct g1s_nlf g1s_nlf_t;
+/* bit_depth 8, 10 or 12.  NULL on failure, the reason from g1s_last_global_error() ("no HIP device available: noise levels
+ * has no CPU fallback" without a device).  opts == NULL: current device, defaults. */
+g1s_nlf_t *g1s_nlf_new(uint32_t bit_depth, const g1s_nlf_opts_t *opts);
+/* One frame, only read.  on_device: 0 = host (copied before the call returns), 1 = device, 2 = pinned host (the copy is
+ * queued).  Device and pinned planes must stay valid and unmodified until the batch they are in has gone out: batch_frames
+ * frames later, or at g1s_nlf_finish.  A frame whose geometry differs from the one before it sends the queue out first. */
+int g1s_nlf_frame(g1s_nlf_t *, const g1s_frame_t *frame);
+/* Launches what is queued, waits, and hands over one record per frame since the last hand-over, in order.  cap too small
+ * (or per_frame NULL): G1S_ERR_CAPACITY, *n_out = the count, the records stay (the error is not sticky). */
+int g1s_nlf_finish(g1s_nlf_t *, g1s_nlf_record_t *per_frame, size_t cap, size_t *n_out);
+/* HIP-event time of the luma and of the chroma launches so far, milliseconds, and the frames they covered (enable = 1:
+ * timed from the next batch on).  tools/bench_estimate.py --levels. */
+int g1s_nlf_set_timing(g1s_nlf_t *, int enable, double *ms_luma, double *ms_chroma, uint64_t *frames);
+const char *g1s_nlf_last_error(const g1s_nlf_t *);
+void g1s_nlf_free(g1s_nlf_t *);
+/* The five below are host only: they need no device. */
+/* N4: *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_nlf_sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total);
+/* N5 - N6: s[1 << bit_depth] from the luma bins of a clip's record.  G1S_ERR_INVALID with the reason from
+ * g1s_last_global_error(): a bit depth other than 8 and 10 (rule 12's texts), no valid luma bin. */
+int g1s_nlf_sigma(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s);
+/* N7 for one plane class (0: luma; 1: the two chroma planes pooled): *h.  G1S_ERR_INVALID with the reason from
+ * g1s_last_global_error() ("too few smooth samples for a strength", "the measured strength is outside 0 < h <= 1000"). */
+int g1s_nlf_strength(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h);
+/* Rule 12 from "floor = ..." onwards and rule 13 on a given s[1 << bit_depth] (N6's, or any other): the pair (f, g) as
+ * g1s_denoise_curve makes it from a table's s.  The same refusals for bit depth and range. */
+int g1s_denoise_curve_sigma(const uint8_t *s, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv);
+/* N8: the report of a clip's record of `frames` frames.  Every value is formed in f64 from the exact integers in the order
+ * written here and printed "%.4f", in code values of the clip's depth.  Grammar:
+ *   noiselevels1
+ *   frames N bit_depth B planes P
+ *   plane c                          for c in 0 .. P - 1
+ *   bin k n sigma_q sigma_a          the bins with n > 0: sigma_q = sqrt((double)q / (double)(36 n)),
+ *                                    sigma_a = (double)a / (double)(6 n) * sqrt(pi / 2) * 2^(B - 8)
+ *   plane_sigma v                    sigma_q of the plane's bins summed; "-" when no sample counts
+ *   auto_strength h_luma h_chroma    after the planes: N7's two values, each "-" where N7 refuses
+ * Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a bit depth or plane count the rules do not have). */
+long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, uint64_t min_count, char *buf,
+                             size_t cap);
+/* `estimate SOURCE --levels PATH` for a .y4m file: the first max_frames frames (0 = all), the clip's record into *total
+ * (may be NULL), the report into out_report (may be NULL).  Returns the number of frames, or a negative G1S_ERR_* with the
+ * reason in err. */
+int64_t g1s_nlf_y4m_file(const char *source, const char *out_report, const g1s_nlf_opts_t *opts, uint64_t max_frames, g1s_nlf_record_t *total,
+                         char *err, size_t cap);
+
 /* ---- `render`: AV1 film grain synthesis on the device (the inverse of `diff`: a table's grain onto frames) ----
  * The film grain synthesis process of the AV1 specification (clause 7.18.3: random number process, generate grain
  * process, scaling lookup initialisation, add noise synthesis process), integer-exact, written from the standard.
@@ -647,6 +747,18 @@ int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_de
 int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                     const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err,
                                     size_t cap);
+/* The same with what the clip itself says (noise levels, rules N5 - N7), from a pre-pass over the first profile_frames frames
+ * (0 = all) of the file, which is then opened again and filtered as by g1s_denoise_y4m_file_motion.  G1S_AUTO_PRIOR: the curve
+ * of rules 12 - 13 from the clip's own levels (N6; prior_range as for a table) instead of a table's; G1S_AUTO_STRENGTH: the
+ * strength and the chroma strength from N7 (where N7 refuses for chroma, a luma-only clip, the luma strength).  min_count is
+ * N5's and N7's Nmin (0 = 4096).  Refusals, each with its text: an unknown flag bit, G1S_AUTO_PRIOR with prior_tbl,
+ * G1S_AUTO_STRENGTH with a non-zero strength or chroma_strength in opts, a source that is not a regular file (a pipe is read
+ * once), and what N6 and N7 refuse.  auto_flags = 0 is g1s_denoise_y4m_file_motion. */
+#define G1S_AUTO_PRIOR 1u
+#define G1S_AUTO_STRENGTH 2u
+int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                  const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                  uint64_t profile_frames, uint64_t min_count, char *err, size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -672,6 +784,12 @@ int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, c
                                       const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                       uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint64_t *frames, char *err,
                                       size_t cap);
+/* The same with the auto flags of g1s_denoise_y4m_file_auto (the pre-pass runs on the generator's device); auto_flags = 0 is
+ * g1s_diff_y4m_file_denoised_motion. */
+int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                    const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                    uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                    uint64_t min_count, uint64_t *frames, char *err, size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

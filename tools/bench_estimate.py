@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""tools/bench_estimate.py [frames] -- N4 on the GPU box: `estimate`'s per-frame noise estimator over HBM-resident 4K 10-bit luma
+"""tools/bench_estimate.py [frames] [--levels] -- N4 on the GPU box: `estimate`'s per-frame noise estimator over HBM-resident 4K 10-bit luma
 planes: whole-loop rate (FFI call per frame, one launch + one 16-byte D2H per batch of 32) and the kernel alone (HIP events),
-against the 8 TB/s HBM roofline (2 bytes per luma pixel: the plane is read once), with the oracle's scalar rate beside it."""
+against the 8 TB/s HBM roofline (2 bytes per luma pixel: the plane is read once), with the oracle's scalar rate beside it.
+--levels: the two launches of the noise level function (k_nlf on luma; on both chroma planes with the luma under them) on the
+same 4:2:0 frames in the same process, beside k_estimate: microseconds a frame, the bytes each must read (luma once; luma
+again and both chroma planes) and the fraction of the HBM roofline that implies."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,9 +13,12 @@ from grav1synth_amd.estimate import NoiseEstimator
 from grav1synth_amd.synth import SynthSpec, make_pair
 from tests.oracle_binding import estimate_plane_noise
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
+args = [a for a in sys.argv[1:] if a != "--levels"]
+levels = "--levels" in sys.argv[1:]
+n = int(args[0]) if args else 2048
 spec = SynthSpec(3840, 2160, 10)
-planes = [make_pair(spec, k, device="cuda")[0][0] for k in range(64)]
+frames = [make_pair(spec, k, device="cuda")[0] for k in range(64)]
+planes = [f[0] for f in frames]
 torch.cuda.synchronize()
 out = {}
 for rep in range(3):
@@ -37,4 +43,27 @@ want = estimate_plane_noise(p0, 10)
 out["oracle_Mpx_s_one_thread"] = px / (time.perf_counter() - t0) / 1e6
 assert got[0] == want, (got[0], want)
 out["estimate_frame0"] = got[0]
+if levels:
+    from grav1synth_amd.estimate import NoiseLevelMeter
+
+    for rep in range(3):
+        meter = NoiseLevelMeter(10, batch_frames=32)
+        meter.kernel_times(True)
+        for k in range(n):
+            meter.frame(frames[k % 64], spec.xdec, spec.ydec)
+            if (k + 1) % 256 == 0 or k + 1 == n:
+                recs = meter.finish()  # (the last call's records are looked at below)
+        ms_l, ms_c, fr = meter.kernel_times(True)
+        meter.close()
+    cpx = sum(int(p.numel()) for p in frames[0][1:])
+    luma_bytes, chroma_bytes = 2 * px, 2 * px + 2 * cpx
+    out["levels_luma_us_per_frame"] = ms_l * 1e3 / fr
+    out["levels_chroma_us_per_frame"] = ms_c * 1e3 / fr
+    out["levels_luma_bytes"], out["levels_chroma_bytes"] = luma_bytes, chroma_bytes
+    out["levels_luma_roofline_frac"] = luma_bytes * fr / (ms_l * 1e-3) / 1e9 / 8000.0
+    out["levels_chroma_roofline_frac"] = chroma_bytes * fr / (ms_c * 1e-3) / 1e9 / 8000.0
+    out["levels_luma_over_estimate"] = out["levels_luma_us_per_frame"] / out["kernel_us_per_frame"]
+    n0, a0 = int(recs[-1]["n"][0].sum()), int(recs[-1]["a"][0].sum())
+    k_last = (n - 1) % 64
+    assert float(a0) / float(6 * n0) * 1.2533141373155003 == got[k_last], "the luma totals are the estimator's sums"
 print(json.dumps(out))
