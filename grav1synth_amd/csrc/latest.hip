@@ -9,19 +9,25 @@
 //   * every f64 operation is the host's operation on the host's operands (-ffp-contract=off on both sides; IEEE divide and
 //     square root; int64 -> f64 in one rounding);
 //   * every f64 SUM runs in the host's order.
-// Round 5 rebuilt the kernel around SHORT serial chains (round 3's took 1.1 ms a launch: barriers around every elimination step,
-// chains of dependent L2 round trips):
+// The kernel is built around SHORT serial chains:
 //   * a linear system is solved by ONE wave with the rows in registers (lane = row, columns statically indexed): the
 //     reference's "bubble the larger magnitude up" pivoting is a suffix arg-max over the column (the element carried past
-//     position i is the first maximum of positions i .. n - 1, position i keeps the loser of its comparison), taken with five
-//     shuffle steps; the pivot row travels by v_readlane; back substitution by every lane on its own row, the wanted lane's
-//     result broadcast.  No barrier, no LDS.  The three planes' AR systems are solved by three waves at once;
+//     position i is the first maximum of positions i .. n - 1, position i keeps the loser of its comparison), taken with four
+//     DPP row shifts and one v_readlane step across the two rows of 16 -- nothing in the search waits for LDS but the gather
+//     of the column by position and the winner's row; the pivot row travels by v_readlane; back substitution by every lane on
+//     its own row, the wanted lane's result broadcast.  No barrier.  The three planes' AR systems are solved by three waves at
+//     once;
 //   * the strength system's entries are sums over the measured blocks in raster order.  Entry (k, k), (k + 1, k) = (k, k + 1)
-//     and b[k] only ever meet blocks of bins k - 1 and k: the blocks are taken 1 024 at a time, their terms computed a thread a
-//     block, partitioned by bin IN ORDER into lists in LDS (ballots and popcounts: a stable partition), and lane k adds its
-//     list front to back -- one LDS read and one addition an element, no selection, no memory latency in the chain; `total`
+//     and b[k] only ever meet blocks of bins k - 1 and k: the blocks are taken a STAGE of 512 at a time, their terms computed a
+//     thread a block, partitioned by bin IN ORDER into lists in LDS (ballots and popcounts: a stable partition), and lane k adds
+//     its list front to back -- one LDS read and one addition an element, no selection, no memory latency in the chain; `total`
 //     is one sum over all blocks: one more list (every measured block, in block order), one more lane.  Both chroma planes go
-//     through one pass (same blocks, same bins).
+//     through one pass (same blocks, same bins);
+//   * the partition and the chains are a two-stage pipeline with ONE barrier a stage: eight partition waves (512 threads) place
+//     stage t + 1's terms into list buffer (t + 1) & 1 and then measure and rank stage t + 2 (those stay in registers across
+//     the barrier; only the counts go to LDS, double-buffered), while two chain waves add the lists of stage t from buffer
+//     t & 1.  The chains are the true serial part (one dependent f64 addition a measured block); the partition of a stage
+//     depends on nothing the chains produce.  DESIGN 4.8, profiles/latest_pipeline.txt.
 #include "latest_dev.h"
 
 #include "fold.h"
@@ -31,29 +37,31 @@
 namespace g1s {
 namespace {
 
-// (512 threads and 1 024 blocks a chunk: the terms, the ranks and the scatter of a chunk go twice as wide and the barriers, the
-//  offsets and the lists' zero padding come half as often as with 256 threads and 512 blocks -- 343 - 369 -> 273 - 278 us a 64-frame
-//  4K launch alone on the chip, passes 113 + 120 -> 82 + 86 us by the stamps; the chains, two lanes' worth of waves 0 and 2, are
-//  what they were.  The lists' order is the blocks' order either way: rounds first, then waves, then lanes.
-//  profiles/r09_latest_window.txt)
-constexpr int kT = 512, kWaves = kT / 64;
-constexpr int kChunk = 1024, kRounds = kChunk / kT;  // blocks a chunk; a thread's blocks of a chunk: base + kT * r + tid
+// (640 threads: eight partition waves, whose blocks of a stage are base + kPT * r + tid as before, and two chain waves, 8 and 9,
+//  that do nothing but add lists.  A stage is 512 blocks: two list buffers of 1 024-block stages for two chroma planes would
+//  be 158 KB of a CU's 160; two of 512 are today's footprint.  The lists' order is the blocks' order: rounds first, then waves,
+//  then lanes.  profiles/latest_pipeline.txt)
+constexpr int kPT = 512, kPW = kPT / 64;            // the partition's threads and waves
+constexpr int kCW = 2;                              // chain waves, behind the partition's
+constexpr int kT = kPT + 64 * kCW, kWaves = kT / 64;
+constexpr int kStage = 512, kRounds = kStage / kPT;  // blocks a stage; a thread's blocks of a stage: base + kPT * r + tid
 constexpr double kTinyD = 1.0e-16;                  // TINY_NEAR_ZERO
 constexpr double kNorm2D = 255.0 * 255.0;           // BLOCK_NORMALIZATION^2
-constexpr int kNL = 2 * kNumBins;                   // lists of a chunk: D 0 .. 19 (bins k - 1 and k), L 20 .. 38 (bin k alone), T 39 (every block)
-constexpr int kArenaD = 2 * kChunk + 8 * kNumBins + 8, kArenaL = kChunk + 8 * kNumBins + 8, kArenaT = kChunk + 8;
+constexpr int kNL = 2 * kNumBins;                   // lists of a stage: D 0 .. 19 (bins k - 1 and k), L 20 .. 38 (bin k alone), T 39 (every block)
+constexpr int kArenaD = 2 * kStage + 8 * kNumBins + 8, kArenaL = kStage + 8 * kNumBins + 8, kArenaT = kStage + 8;
 static_assert(kNumBins == 20 && kMaxN == 25, "latest.hip: the solvers' static sizes");
+static_assert(kArenaD % 2 == 0 && kArenaL % 2 == 0 && kArenaT % 2 == 0, "latest.hip: the chains read the arenas as double2");
 
 struct Shared {
-  // a chunk's partitioned terms
+  // a stage's partitioned terms, in two buffers: stage t's in buffer t & 1
   // (a list's slots start at a multiple of 8 and are zero-filled up to the next one: the chains add whole groups of eight --
   //  a +0.0 changes no sum that is >= +0 or NaN -- and read one group ahead)
-  alignas(16) double D[kArenaD];  // matrix diagonal terms, list k at [beg[k], end[k])
-  double Lw[kArenaL];     // off-diagonal terms, list 20 + k
-  double Bv[2][kArenaD];  // b terms of the pass' planes, the D lists' slots
-  double Tv[2][kArenaT];  // noise stds in block order (list 39)
-  uint16_t cnt[kRounds][kWaves][kNL];  // (at most 64 each.  The workgroup's LDS: 83 KB of a CU's 160, one workgroup a CU)
-  uint32_t beg[kNL], end[kNL];
+  alignas(16) double D[2][kArenaD];  // matrix diagonal terms, list k at [beg[k], end[k])
+  double Lw[2][kArenaL];     // off-diagonal terms, list 20 + k
+  double Bv[2][2][kArenaD];  // [buffer][plane of the pass]: b terms, the D lists' slots
+  double Tv[2][2][kArenaT];  // [buffer][plane of the pass]: noise stds in block order (list 39)
+  uint16_t cnt[2][kRounds][kPW][kNL];  // (at most 64 each.  The workgroup's LDS: 90 KB of a CU's 160, one workgroup a CU)
+  uint32_t beg[2][kNL], end[2][kNL];
   // results
   double arx[3][kMaxN + 1];
   double gain[3];
@@ -72,7 +80,29 @@ __device__ __forceinline__ double readlane_f64(double v, int j) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), j);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// DPP moves of an f64 and of an index (a compile-time control word; lanes whose source lies outside keep `old`)
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int old, int v) {
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double old, double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v), o = (unsigned long long)__double_as_longlong(old);
+  const uint32_t lo = (uint32_t)dpp_i32<CTRL>((int)(uint32_t)o, (int)(uint32_t)u), hi = (uint32_t)dpp_i32<CTRL>((int)(uint32_t)(o >> 32), (int)(uint32_t)(u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// one step of the suffix arg-max inside a row of 16: the pair D lanes up (row_shl: lane i <- lane i + D; past the row's end
+// the -1.0 that no magnitude is below), taken only if strictly larger: the smaller position wins a tie
+template <int D>
+__device__ __forceinline__ void argmax_step(double &val, int &idx) {
+  const double v2 = dpp_f64<0x100 + D>(-1.0, val);
+  const int i2 = dpp_i32<0x100 + D>(0, idx);
+  if (v2 > val) {
+    val = v2;
+    idx = i2;
+  }
+}
 
 // gauss_solve of fold.cpp by one wave: lane r < n holds row r (a[j], j < n) and b of the system; x comes back in every lane
 // (x must come in as what a failed solve leaves behind: the caller's cleared x).  The rows stay in their lanes; `rap` (lane p:
@@ -80,10 +110,13 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 //   bubble pass over column k, bottom up:  before step i position i holds w(i), the first maximum of |column| over positions
 //   i .. n - 1 (`!(up < carried)` moves on to the upper element on a tie), position i - 1 its own element; the larger moves
 //   to i - 1.  So after the pass position k holds w(k) and position i > k holds (|c[i - 1]| < |c[w(i)]|) ? row(i - 1) : w(i).
-//   w(.) is a suffix arg-max with the smaller position winning ties: five shuffle steps.  (No NaN can arise: the pivot is the
-//   column's largest magnitude, every multiplier is <= 1 in magnitude.)
+//   w(.) is a suffix arg-max with the smaller position winning ties.  n <= 32: four row shifts give it inside each row of 16
+//   lanes, the first row then meets lane 16's (the second row's whole suffix) by v_readlane; the neighbour above comes by
+//   wave_shr:1.  Per step two things still go through LDS: |column k| gathered by position and the winner's row.  (No NaN can
+//   arise: the pivot is the column's largest magnitude, every multiplier is <= 1 in magnitude.)
 template <int NMAX>
 __device__ __forceinline__ bool wave_gauss(const int n, double (&a)[NMAX], double b, double (&x)[NMAX], const int lane) {
+  static_assert(NMAX <= 32, "wave_gauss: the pivot search covers two rows of 16 lanes");
   int rap = lane;
   bool done = false, ok = true;  // (ok: wave-uniform; a failed solve runs on without touching anything -- no early return out of the unrolled loops, which would send the rows to scratch memory)
 #pragma unroll
@@ -95,20 +128,23 @@ __device__ __forceinline__ bool wave_gauss(const int n, double (&a)[NMAX], doubl
       if (lane < k || lane >= n) cp = -1.0;
       double val = cp;
       int idx = lane;
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const double v2 = __shfl_down(val, d, 64);
-        const int i2 = __shfl_down(idx, d, 64);
-        if (lane + d < 64 && v2 > val) {
+      argmax_step<1>(val, idx);
+      argmax_step<2>(val, idx);
+      argmax_step<4>(val, idx);
+      argmax_step<8>(val, idx);
+      {
+        const double v2 = readlane_f64(val, 16);
+        const int i2 = __builtin_amdgcn_readlane(idx, 16);
+        if (lane < 16 && v2 > val) {
           val = v2;
           idx = i2;
         }
       }
       const int rap_w = __shfl(rap, idx, 64);
-      const int rap_up = __shfl_up(rap, 1, 64);
-      const double cp_up = __shfl_up(cp, 1, 64);
+      const int rap_up = dpp_i32<0x138>(0, rap);       // wave_shr:1: lane i <- lane i - 1
+      const double cp_up = dpp_f64<0x138>(-1.0, cp);
       if (lane >= k && lane < n) rap = (lane == k) ? rap_w : ((cp_up < val) ? rap_up : rap_w);
-      const int pr = uniform(__shfl(rap, k, 64));
+      const int pr = __builtin_amdgcn_readlane(rap, k);
       const double pk = readlane_f64(a[k], pr), bk = readlane_f64(b, pr);
       if (fabs(pk) < kTinyD) {
         ok = false;
@@ -130,7 +166,7 @@ __device__ __forceinline__ bool wave_gauss(const int n, double (&a)[NMAX], doubl
 #pragma unroll
   for (int i = NMAX - 1; i >= 0; --i) {
     if (i < n && ok) {
-      const int r = uniform(__shfl(rap, i, 64));
+      const int r = __builtin_amdgcn_readlane(rap, i);
       const double piv = readlane_f64(a[i], r);
       if (fabs(piv) < kTinyD) {
         ok = false;
@@ -142,7 +178,7 @@ __device__ __forceinline__ bool wave_gauss(const int n, double (&a)[NMAX], doubl
           if (j < n) c += t;
         }
         const double xi = (b - c) / a[i];
-        x[i] = __shfl(xi, r, 64);  // (a broadcast into vector registers: 25 solutions as scalar pairs do not fit the scalar file)
+        x[i] = readlane_f64(xi, r);  // (a broadcast into vector registers: 25 solutions as scalar pairs do not fit the scalar file)
       }
     }
   }
@@ -173,9 +209,18 @@ __device__ inline void put_text(char *dst, const char *msg) {
       k4_t = now_;                                    \
     }                                                 \
   } while (0)
+// a wave's own busy time inside the pipeline: no barrier, added up in a register of the wave's lane 0 and written at the pass' end
+#define K4_BUSY_BEGIN() const unsigned long long busy_t_ = wall_clock64()
+#define K4_BUSY_END(var) (var) += wall_clock64() - busy_t_
 #else
 #define K4_TICK(slot) \
   do {                \
+  } while (0)
+#define K4_BUSY_BEGIN() \
+  do {                  \
+  } while (0)
+#define K4_BUSY_END(var) \
+  do {                   \
   } while (0)
 #endif
 
@@ -188,12 +233,19 @@ struct FrameCtx {
 
 // One pass over the frame's blocks for the planes c0 .. c0 + NP - 1 (one geometry): the strength system's sums.
 // Out: sh.diag / low (the matrix side: bins alone), sh.bsum[q], sh.total[q], sh.ne.
+//
+// A two-stage pipeline, one barrier a step, every wave at every barrier.  In step t (t = -2 .. stages - 1)
+//   the partition waves  PLACE stage t + 1: read its counts (written before the last barrier), work out the offsets, scatter the
+//                        terms they hold in registers into list buffer (t + 1) & 1, leave the lists' bounds and zero padding;
+//                        then MEASURE stage t + 2: keys, terms, ranks into registers, counts into cnt[t & 1];
+//   the chain waves      add the lists of stage t from buffer t & 1.
+// Buffer (t + 1) & 1 was last read by the chains in step t - 1 and cnt[t & 1] by the partition in step t - 1: one barrier
+// between every write and the reads before and after it.
 template <int NP>
 __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, const FrameCtx &fc, const int c0, const int tid, double *k4_dbg, const int frame) {
-#ifdef G1S_LATEST_TIMERS
-  unsigned long long k4_t = wall_clock64();
-#endif
   const int lane = tid & 63, wave = tid >> 6;
+  const bool chain_wave = wave >= kPW;
+  const int cw = wave - kPW;  // chain wave 0: the (k, k) sums and the b sums; 1: the (k + 1, k) sums and the totals
   const bool is_chroma = c0 != 0;
   const int sx = is_chroma ? job.xdec : 0, sy = is_chroma ? job.ydec : 0;
   const int bw = kBlock >> sx, bh = kBlock >> sy;
@@ -209,14 +261,27 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
     corr[q] = is_chroma ? sh.arx[c0 + q][job.n] : 0;
   }
   const double luma_gain = sh.gain[0];
-  // the chains' accumulators
-  // (one chain a lane -- wave 0: lanes 0 .. 19 the (k, k) sums, 20 .. 39 plane 0's b[k], 40 .. 59 plane 1's; wave 2 lanes 0 .. 18
-  //  the (k + 1, k) sums, lanes 19 and 20 the planes' totals: an addition waits for the one before it, the chains next to each
-  //  other in a wave cost nothing)
+  const int stages = (fc.nb + kStage - 1) / kStage;
+#ifdef G1S_LATEST_TIMERS
+  unsigned long long busy_place = 0, busy_measure = 0, busy_chain = 0;
+#endif
+
+  // ---- the chain waves' side ----
+  // (one chain a lane -- chain wave 0: lanes 0 .. 19 the (k, k) sums, 20 .. 39 plane 0's b[k], 40 .. 59 plane 1's; chain wave 1:
+  //  lanes 0 .. 18 the (k + 1, k) sums, lanes 19 and 20 the planes' totals (list 39: every measured block, in block order): an
+  //  addition waits for the one before it, the chains next to each other in a wave cost nothing)
+  constexpr int kLowLanes = kNumBins - 1;
+  const int arr = cw == 0 ? lane / kNumBins : (lane < kLowLanes ? 3 : 4 + (lane - kLowLanes));
+  const int li = cw == 0 ? lane % kNumBins : (lane < kLowLanes ? kNumBins + lane : kNL - 1);
+  const bool on = chain_wave && (cw == 0 ? arr <= NP : lane < kLowLanes + NP);
+  // the lane's arena in buffer 0 and the way to buffer 1, in double2
+  const double2 *const src0 = reinterpret_cast<const double2 *>(arr == 0 ? sh.D[0] : arr == 1 ? sh.Bv[0][0] : arr == 2 ? sh.Bv[0][NP - 1] : arr == 3 ? sh.Lw[0] : arr == 4 ? sh.Tv[0][0] : sh.Tv[0][NP - 1]);
+  const uint32_t buf_stride = (arr == 0 ? kArenaD : arr <= 2 ? 2 * kArenaD : arr == 3 ? kArenaL : 2 * kArenaT) / 2;
   double acc = 0;
   uint32_t ne = 0;
+  if (chain_wave) __builtin_amdgcn_s_setprio(3);  // (the serial part: its additions go ahead of the partition waves on the same SIMD)
 
-  // raw words of a chunk (requested a chunk ahead)
+  // ---- the partition waves' side: raw words of a stage (requested a stage ahead), the measured stage's terms and ranks ----
   struct Raw {
     uint32_t m, ls;
     int32_t sd[NP];
@@ -226,7 +291,7 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
   auto fetch = [&](int base) {
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
-      const int bi = base + kT * r + tid;
+      const int bi = base + kPT * r + tid;
       const bool in = bi < fc.nb;
       nxt[r].m = in ? fc.mask[bi] : 0u;
       nxt[r].ls = in ? fc.luma_sum[bi] : 0u;
@@ -237,181 +302,193 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
       }
     }
   };
-  fetch(0);
-  for (int base = 0; base < fc.nb; base += kChunk) {
-    Raw cur[kRounds];
+  int key[kRounds];
+  double tU[kRounds], tW[kRounds], tV[kRounds], tP[kRounds][NP], tQ[kRounds][NP], tS[kRounds][NP];
+  uint32_t rk_own[kRounds], rk_prev[kRounds], rk_low[kRounds], rk_all[kRounds];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) cur[r] = nxt[r];
-    if (base + kChunk < fc.nb) fetch(base + kChunk);
-    // ---- a thread a block: the measurement and its terms ----
-    int key[kRounds];
-    double tU[kRounds], tW[kRounds], tV[kRounds], tP[kRounds][NP], tQ[kRounds][NP], tS[kRounds][NP];
+  for (int r = 0; r < kRounds; ++r) {
+    key[r] = -1;
+    tU[r] = tW[r] = tV[r] = 0;
+    rk_own[r] = rk_prev[r] = rk_low[r] = rk_all[r] = 0;
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-      const int bi = base + kT * r + tid;
-      key[r] = -1;
-      tU[r] = tW[r] = tV[r] = 0;
+    for (int q = 0; q < NP; ++q) tP[r][q] = tQ[r][q] = tS[r][q] = 0;
+  }
+  if (!chain_wave) fetch(0);
+
+  for (int t = -2; t < stages; ++t) {
+    if (!chain_wave) {
+      if (t >= -1 && t + 1 < stages) {
+        // ======== PLACE stage t + 1 ========
+        K4_BUSY_BEGIN();
+        const int pb = (t + 1) & 1;
+        // ---- offsets: list l's slots of (round, wave), rounds first (block order) ----
+        // (every wave works them out for itself from the counts, lane l list l, and keeps its own rounds' in registers: no
+        //  barrier between the offsets and the scatter; wave 0 leaves the lists' bounds and the zeros behind them for the chains)
+        uint32_t my_off[kRounds];
+        uint32_t run = 0;
 #pragma unroll
-      for (int q = 0; q < NP; ++q) tP[r][q] = tQ[r][q] = tS[r][q] = 0;
-      if (cur[r].m == 0) continue;
-      const int by = bi / fc.nbw, bx = bi - by * fc.nbw;
-      const int shh = min(ph - by * bh, bh), sw = min(pw - bx * bw, bw);
-      if (!(sw * shh > kBlock)) continue;
-      const int lw = min(fc.W - bx * kBlock, kBlock), lh = min(fc.H - by * kBlock, kBlock);
-      const double block_mean = div_count((double)cur[r].ls, lw * lh);
-      const double bin = dev_bin_index(block_mean);
-      const int i0 = (int)bin;  // (bin >= 0: the floor)
-      const int i1 = min(kNumBins - 1, i0 + 1);
-      const double a = bin - i0;
-      key[r] = i0;
-      tU[r] = (1.0 - a) * (1.0 - a);
-      tW[r] = a * (1.0 - a);
-      tV[r] = a * a;
-      const double luma_strength = is_chroma ? luma_gain * ((1.0 - a) * sh.luma_x[i0] + a * sh.luma_x[i1]) : 0;
+        for (int r = 0; r < kRounds; ++r) my_off[r] = 0;
+        if (lane < kNL) {
 #pragma unroll
-      for (int q = 0; q < NP; ++q) {
-        double noise_mean = (double)cur[r].sd[q];
-        const double noise_sq = (double)cur[r].sd2[q];
-        noise_mean = div_count(noise_mean, sw * shh);
-        const double noise_var = div_count(noise_sq, sw * shh) - noise_mean * noise_mean;
-        const double cl = corr[q] * luma_strength;
-        const double t0 = noise_var / 16, t1 = noise_var - cl * cl;
-        const double uncorr_std = sqrt(t0 > t1 ? t0 : t1);
-        const double noise_std = uncorr_std / noise_gain[q];
-        tS[r][q] = noise_std;
-        tP[r][q] = (1.0 - a) * noise_std;
-        tQ[r][q] = a * noise_std;
-      }
-    }
-    K4_TICK(6);
-    // ---- stable partition by bin: ranks inside the wave by ballots ----
-    // list k (D): blocks of bin k ("own": the (k, k) term (1 - a)^2, the b term (1 - a) std) and of bin k - 1 ("prev": a^2, a std)
-    // list 20 + k (L): blocks of bin k alone (a (1 - a)); list 39 (T): every measured block.
-    // A block of the last bin is its own neighbour (i1 = i0 = 19) -- and sits exactly on it: bin = 19 means a = 0, so what the
-    // reference adds besides (1 - a)^2 and (1 - a) std are zeros (a (1 - a), a^2, a std with a finite or NaN std), which change
-    // no sum that is >= +0 or NaN: the block goes to list 19 as "own" only.
-    uint32_t rk_own[kRounds], rk_prev[kRounds], rk_low[kRounds], rk_all[kRounds];
+          for (int r = 0; r < kRounds; ++r)
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-      unsigned long long prevB = 0;
-      uint32_t mycnt = 0;
-      rk_own[r] = rk_prev[r] = rk_low[r] = rk_all[r] = 0;
-      const int kk = key[r];
-#pragma unroll
-      for (int k = 0; k < kNumBins; ++k) {
-        const unsigned long long Bk = __ballot(kk == k);
-        const unsigned long long M = Bk | prevB;
-        if (M == 0) continue;  // (a frame's blocks sit in a few bins: most lists of a chunk are empty)
-        const uint32_t preM = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
-        const uint32_t preB = __builtin_amdgcn_mbcnt_hi((uint32_t)(Bk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Bk, 0u));
-        if (kk == k) rk_own[r] = preM, rk_low[r] = preB;
-        if (kk == k - 1) rk_prev[r] = preM;
-        if (lane == k) mycnt = (uint32_t)__popcll(M);
-        if (lane == kNumBins + k) mycnt = (uint32_t)__popcll(Bk);
-        prevB = Bk;
-      }
-      {
-        const unsigned long long Ma = __ballot(kk >= 0);
-        rk_all[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(Ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Ma, 0u));
-        if (lane == kNL - 1) mycnt = (uint32_t)__popcll(Ma);
-      }
-      if (lane < kNL) sh.cnt[r][wave][lane] = (uint16_t)mycnt;
-    }
-    __syncthreads();
-    K4_TICK(7);
-    // ---- offsets: list l's slots of (round, wave), rounds first (block order) ----
-    // (every wave works them out for itself from the counts, lane l list l, and keeps its own rounds' in registers: no
-    //  barrier between the offsets and the scatter; wave 0 leaves the lists' bounds and the zeros behind them for the chains)
-    uint32_t my_off[kRounds];
-    uint32_t run = 0;
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) my_off[r] = 0;
-    if (lane < kNL) {
-#pragma unroll
-      for (int r = 0; r < kRounds; ++r)
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-          if (w == wave) my_off[r] = run;
-          run += sh.cnt[r][w][lane];
+            for (int w = 0; w < kPW; ++w) {
+              if (w == wave) my_off[r] = run;
+              run += sh.cnt[pb][r][w][lane];
+            }
         }
-    }
-    {
-      // the lists' bases inside their arenas (each list's room a multiple of 8): D lists 0 .. 19 one behind the other, L lists
-      // 20 .. 38 likewise, T at 0
-      const uint32_t room = (run + 7u) & ~7u;
-      uint32_t incl = room;
+        {
+          // the lists' bases inside their arenas (each list's room a multiple of 8): D lists 0 .. 19 one behind the other, L lists
+          // 20 .. 38 likewise, T at 0
+          const uint32_t room = (run + 7u) & ~7u;
+          uint32_t incl = room;
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += o;
-      }
-      const uint32_t upto19 = (uint32_t)__shfl((int)incl, kNumBins - 1, 64);
-      uint32_t bse = incl - room;
-      if (lane >= kNumBins) bse -= upto19;
-      if (lane == kNL - 1) bse = 0;
-#pragma unroll
-      for (int r = 0; r < kRounds; ++r) my_off[r] += bse;
-      if (wave == 0 && lane < kNL) {
-        sh.beg[lane] = bse;
-        sh.end[lane] = bse + run;
-        // the zeros behind the list
-        if (lane < kNumBins) {
-          for (uint32_t i = bse + run; i < bse + room; ++i) {
-            sh.D[i] = 0.0;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) sh.Bv[q][i] = 0.0;
+          for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= d) incl += o;
           }
-        } else if (lane < kNL - 1) {
-          for (uint32_t i = bse + run; i < bse + room; ++i) sh.Lw[i] = 0.0;
-        } else {
-          for (uint32_t i = run; i < room; ++i) {
+          const uint32_t upto19 = (uint32_t)__shfl((int)incl, kNumBins - 1, 64);
+          uint32_t bse = incl - room;
+          if (lane >= kNumBins) bse -= upto19;
+          if (lane == kNL - 1) bse = 0;
 #pragma unroll
-            for (int q = 0; q < NP; ++q) sh.Tv[q][i] = 0.0;
+          for (int r = 0; r < kRounds; ++r) my_off[r] += bse;
+          if (wave == 0 && lane < kNL) {
+            sh.beg[pb][lane] = bse;
+            sh.end[pb][lane] = bse + run;
+            // the zeros behind the list
+            if (lane < kNumBins) {
+              for (uint32_t i = bse + run; i < bse + room; ++i) {
+                sh.D[pb][i] = 0.0;
+#pragma unroll
+                for (int q = 0; q < NP; ++q) sh.Bv[pb][q][i] = 0.0;
+              }
+            } else if (lane < kNL - 1) {
+              for (uint32_t i = bse + run; i < bse + room; ++i) sh.Lw[pb][i] = 0.0;
+            } else {
+              for (uint32_t i = run; i < room; ++i) {
+#pragma unroll
+                for (int q = 0; q < NP; ++q) sh.Tv[pb][q][i] = 0.0;
+              }
+            }
           }
         }
+        // ---- the terms into their lists (a list's base for this wave's round: from the lane that holds it) ----
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+          const int kk = key[r], kq = max(kk, 0);
+          const uint32_t o_own = (uint32_t)__shfl((int)my_off[r], kq, 64);
+          const uint32_t o_prev = (uint32_t)__shfl((int)my_off[r], min(kq + 1, kNumBins - 1), 64);
+          const uint32_t o_low = (uint32_t)__shfl((int)my_off[r], kNumBins + min(kq, kNumBins - 2), 64);
+          const uint32_t o_all = (uint32_t)__shfl((int)my_off[r], kNL - 1, 64);
+          if (kk < 0) continue;
+          const uint32_t so = o_own + rk_own[r];
+          sh.D[pb][so] = tU[r];
+#pragma unroll
+          for (int q = 0; q < NP; ++q) sh.Bv[pb][q][so] = tP[r][q];
+          if (kk < kNumBins - 1) {
+            const uint32_t sp = o_prev + rk_prev[r];
+            sh.D[pb][sp] = tV[r];
+#pragma unroll
+            for (int q = 0; q < NP; ++q) sh.Bv[pb][q][sp] = tQ[r][q];
+            const uint32_t sl = o_low + rk_low[r];
+            sh.Lw[pb][sl] = tW[r];
+          }
+          const uint32_t st = o_all + rk_all[r];
+#pragma unroll
+          for (int q = 0; q < NP; ++q) sh.Tv[pb][q][st] = tS[r][q];
+        }
+        K4_BUSY_END(busy_place);
       }
-    }
-    K4_TICK(8);
-    // ---- the terms into their lists (a list's base for this wave's round: from the lane that holds it) ----
+      if (t + 2 < stages) {
+        // ======== MEASURE stage t + 2 ========
+        K4_BUSY_BEGIN();
+        const int base = (t + 2) * kStage, cb = t & 1;
+        Raw cur[kRounds];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-      const int kk = key[r], kq = max(kk, 0);
-      const uint32_t o_own = (uint32_t)__shfl((int)my_off[r], kq, 64);
-      const uint32_t o_prev = (uint32_t)__shfl((int)my_off[r], min(kq + 1, kNumBins - 1), 64);
-      const uint32_t o_low = (uint32_t)__shfl((int)my_off[r], kNumBins + min(kq, kNumBins - 2), 64);
-      const uint32_t o_all = (uint32_t)__shfl((int)my_off[r], kNL - 1, 64);
-      if (kk < 0) continue;
-      const uint32_t so = o_own + rk_own[r];
-      sh.D[so] = tU[r];
+        for (int r = 0; r < kRounds; ++r) cur[r] = nxt[r];
+        if (base + kStage < fc.nb) fetch(base + kStage);
+        // ---- a thread a block: the measurement and its terms ----
 #pragma unroll
-      for (int q = 0; q < NP; ++q) sh.Bv[q][so] = tP[r][q];
-      if (kk < kNumBins - 1) {
-        const uint32_t sp = o_prev + rk_prev[r];
-        sh.D[sp] = tV[r];
+        for (int r = 0; r < kRounds; ++r) {
+          const int bi = base + kPT * r + tid;
+          key[r] = -1;
+          tU[r] = tW[r] = tV[r] = 0;
 #pragma unroll
-        for (int q = 0; q < NP; ++q) sh.Bv[q][sp] = tQ[r][q];
-        const uint32_t sl = o_low + rk_low[r];
-        sh.Lw[sl] = tW[r];
+          for (int q = 0; q < NP; ++q) tP[r][q] = tQ[r][q] = tS[r][q] = 0;
+          if (cur[r].m == 0) continue;
+          const int by = bi / fc.nbw, bx = bi - by * fc.nbw;
+          const int shh = min(ph - by * bh, bh), sw = min(pw - bx * bw, bw);
+          if (!(sw * shh > kBlock)) continue;
+          const int lw = min(fc.W - bx * kBlock, kBlock), lh = min(fc.H - by * kBlock, kBlock);
+          const double block_mean = div_count((double)cur[r].ls, lw * lh);
+          const double bin = dev_bin_index(block_mean);
+          const int i0 = (int)bin;  // (bin >= 0: the floor)
+          const int i1 = min(kNumBins - 1, i0 + 1);
+          const double a = bin - i0;
+          key[r] = i0;
+          tU[r] = (1.0 - a) * (1.0 - a);
+          tW[r] = a * (1.0 - a);
+          tV[r] = a * a;
+          const double luma_strength = is_chroma ? luma_gain * ((1.0 - a) * sh.luma_x[i0] + a * sh.luma_x[i1]) : 0;
+#pragma unroll
+          for (int q = 0; q < NP; ++q) {
+            double noise_mean = (double)cur[r].sd[q];
+            const double noise_sq = (double)cur[r].sd2[q];
+            noise_mean = div_count(noise_mean, sw * shh);
+            const double noise_var = div_count(noise_sq, sw * shh) - noise_mean * noise_mean;
+            const double cl = corr[q] * luma_strength;
+            const double t0 = noise_var / 16, t1 = noise_var - cl * cl;
+            const double uncorr_std = sqrt(t0 > t1 ? t0 : t1);
+            const double noise_std = uncorr_std / noise_gain[q];
+            tS[r][q] = noise_std;
+            tP[r][q] = (1.0 - a) * noise_std;
+            tQ[r][q] = a * noise_std;
+          }
+        }
+        // ---- stable partition by bin: ranks inside the wave by ballots ----
+        // list k (D): blocks of bin k ("own": the (k, k) term (1 - a)^2, the b term (1 - a) std) and of bin k - 1 ("prev": a^2, a std)
+        // list 20 + k (L): blocks of bin k alone (a (1 - a)); list 39 (T): every measured block.
+        // A block of the last bin is its own neighbour (i1 = i0 = 19) -- and sits exactly on it: bin = 19 means a = 0, so what the
+        // reference adds besides (1 - a)^2 and (1 - a) std are zeros (a (1 - a), a^2, a std with a finite or NaN std), which change
+        // no sum that is >= +0 or NaN: the block goes to list 19 as "own" only.
+#pragma unroll
+        for (int r = 0; r < kRounds; ++r) {
+          unsigned long long prevB = 0;
+          uint32_t mycnt = 0;
+          rk_own[r] = rk_prev[r] = rk_low[r] = rk_all[r] = 0;
+          const int kk = key[r];
+#pragma unroll
+          for (int k = 0; k < kNumBins; ++k) {
+            const unsigned long long Bk = __ballot(kk == k);
+            const unsigned long long M = Bk | prevB;
+            if (M == 0) continue;  // (a frame's blocks sit in a few bins: most lists of a stage are empty)
+            const uint32_t preM = __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0u));
+            const uint32_t preB = __builtin_amdgcn_mbcnt_hi((uint32_t)(Bk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Bk, 0u));
+            if (kk == k) rk_own[r] = preM, rk_low[r] = preB;
+            if (kk == k - 1) rk_prev[r] = preM;
+            if (lane == k) mycnt = (uint32_t)__popcll(M);
+            if (lane == kNumBins + k) mycnt = (uint32_t)__popcll(Bk);
+            prevB = Bk;
+          }
+          {
+            const unsigned long long Ma = __ballot(kk >= 0);
+            rk_all[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(Ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)Ma, 0u));
+            if (lane == kNL - 1) mycnt = (uint32_t)__popcll(Ma);
+          }
+          if (lane < kNL) sh.cnt[cb][r][wave][lane] = (uint16_t)mycnt;
+        }
+        K4_BUSY_END(busy_measure);
       }
-      const uint32_t st = o_all + rk_all[r];
-#pragma unroll
-      for (int q = 0; q < NP; ++q) sh.Tv[q][st] = tS[r][q];
-    }
-    __syncthreads();
-    K4_TICK(9);
-    // ---- the chains: a list front to back ----
-    if (wave == 0 || wave == 2) {
-      // wave 0: lanes 0 .. 19 the diagonal terms of list k, 20 .. 39 / 40 .. 59 the planes' b terms; wave 2: lanes 0 .. 18 the
-      // off-diagonal terms, lanes 19 / 20 the planes' totals (list 39: every measured block, in block order).  Groups of eight,
-      // the next group's reads in flight while this one is added.
-      constexpr int kLowLanes = kNumBins - 1;
-      const int arr = wave == 0 ? lane / kNumBins : (lane < kLowLanes ? 3 : 4 + (lane - kLowLanes));
-      const int li = wave == 0 ? lane % kNumBins : (lane < kLowLanes ? kNumBins + lane : kNL - 1);
-      const bool on = wave == 0 ? arr <= NP : lane < kLowLanes + NP;
-      const double2 *src = reinterpret_cast<const double2 *>(arr == 0 ? sh.D : arr == 1 ? sh.Bv[0] : arr == 2 ? sh.Bv[NP - 1] : arr == 3 ? sh.Lw : arr == 4 ? sh.Tv[0] : sh.Tv[NP - 1]);
+    } else if (t >= 0) {
+      // ======== the chains: the lists of stage t front to back ========
+      // Groups of eight, the next group's reads in flight while this one is added.
+      K4_BUSY_BEGIN();
+      const int rb = t & 1;
       if (on) {
-        uint32_t i = sh.beg[li] >> 1;
-        const uint32_t e = (sh.end[li] + 1) >> 1;
+        const double2 *src = src0 + (rb ? buf_stride : 0u);
+        uint32_t i = sh.beg[rb][li] >> 1;
+        const uint32_t e = (sh.end[rb][li] + 1) >> 1;
         double2 va[4], vb[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) va[u] = src[i + u];
@@ -429,21 +506,29 @@ __device__ __forceinline__ void strength_pass(Shared &sh, const LatestJob &job, 
             i += 4;
           }
         }
-        if (wave == 2 && lane == kLowLanes) ne += sh.end[kNL - 1];
+        if (cw == 1 && lane == kLowLanes) ne += sh.end[rb][kNL - 1];
       }
+      K4_BUSY_END(busy_chain);
     }
-    __syncthreads();  // (the lists are written again by the next chunk)
-    K4_TICK(10);
+    __syncthreads();  // (the one barrier of a step)
   }
-  if (wave == 0) {
-    const int k = lane % kNumBins, arr = lane / kNumBins;
+  if (chain_wave) __builtin_amdgcn_s_setprio(0);
+  if (chain_wave && cw == 0) {
+    const int k = lane % kNumBins;
     if (arr == 0) sh.diag[k] = acc;
     else if (arr <= NP) sh.bsum[arr - 1][k] = acc;
-  } else if (wave == 2) {
-    if (lane < kNumBins - 1) sh.low[lane] = acc;
-    else if (lane < kNumBins - 1 + NP) sh.total[lane - (kNumBins - 1)] = acc;
-    if (lane == kNumBins - 1) sh.ne = ne;
+  } else if (chain_wave) {
+    if (lane < kLowLanes) sh.low[lane] = acc;
+    else if (lane < kLowLanes + NP) sh.total[lane - kLowLanes] = acc;
+    if (lane == kLowLanes) sh.ne = ne;
   }
+#ifdef G1S_LATEST_TIMERS
+  // (wave 0's measure and place, the two chain waves' additions: each wave's own clock, no barrier)
+  if (frame == 0 && lane == 0) {
+    if (wave == 0) k4_dbg[6] += (double)busy_measure, k4_dbg[7] += (double)busy_place;
+    if (chain_wave) k4_dbg[8 + cw] += (double)busy_chain;
+  }
+#endif
   __syncthreads();
 }
 
@@ -730,9 +815,9 @@ hipError_t launch_latest(const LatestJob &job, int frames, hipStream_t stream) {
     double t[16];
     (void)hipStreamSynchronize(stream);
     (void)hipMemcpy(t, job.scratch, sizeof(t), hipMemcpyDeviceToHost);
-    fprintf(stderr, "k4_latest phases, us (frame 0): head %.1f  ar solves %.1f  luma pass %.1f  luma solve %.1f  chroma pass %.1f  chroma solves %.1f | inside both passes: "
-                    "terms %.1f  ranks %.1f  offsets %.1f  scatter %.1f  chains %.1f\n",
-            t[0] / 100, t[1] / 100, t[2] / 100, t[3] / 100, t[4] / 100, t[5] / 100, t[6] / 100, t[7] / 100, t[8] / 100, t[9] / 100, t[10] / 100);
+    fprintf(stderr, "k4_latest phases, us (frame 0): head %.1f  ar solves %.1f  luma pass %.1f  luma solve %.1f  chroma pass %.1f  chroma solves %.1f | busy inside both passes, each wave's own clock: "
+                    "wave 0 measure %.1f  place %.1f  chain wave 8 %.1f  chain wave 9 %.1f\n",
+            t[0] / 100, t[1] / 100, t[2] / 100, t[3] / 100, t[4] / 100, t[5] / 100, t[6] / 100, t[7] / 100, t[8] / 100, t[9] / 100);
   }
 #endif
   return hipGetLastError();
