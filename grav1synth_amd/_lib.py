@@ -182,6 +182,14 @@ class G1SMeasureTRecord(C.Structure):
     ]
 
 
+class G1SMeasureXRecord(C.Structure):
+    # g1s_measure_xrecord_t: the temporal record's layout with the pairing where the plane is
+    _fields_ = list(G1SMeasureTRecord._fields_)
+
+
+G1S_MEASURE_TEMPORAL, G1S_MEASURE_CROSS = 1, 2
+
+
 class G1SNlfOpts(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -392,6 +400,16 @@ SYMBOLS = [
                                                    C.c_char_p, C.c_size_t]),
     ("g1s_check_y4m_files_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts),
                                                  C.POINTER(G1SGrainOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_measure_new_modes", C.c_void_p, [C.c_uint32, C.POINTER(G1SMeasureOpts), C.c_uint32]),
+    ("g1s_measure_finish_cross", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_measure_sum_cross", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_format_measure_cross", C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_uint32] * 5 + [C.c_char_p, C.c_size_t]),
+    ("g1s_measure_cross_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_measure_chroma_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("g1s_measure_y4m_files_modes", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts),
+                                                C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_check_y4m_files_modes", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts),
+                                              C.POINTER(G1SGrainOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     ("g1s_surface_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SSurfaceOpts)]),
     ("g1s_surface_unpack", C.c_int, [C.c_void_p, C.POINTER(G1SSurface), C.POINTER(G1SFrame)]),
     ("g1s_surface_pack", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SSurface)]),

@@ -27,6 +27,9 @@ SAME_INPUTS = ("Source and denoised paths are the same. This is probably a typo,
                "empty diff. Exiting.")
 NOT_OVERWRITING = "Not overwriting existing file. Exiting."
 SAME_OUTPUTS = "--temporal and -o name the same file: the two reports would overwrite each other. Exiting."
+SAME_CROSS_OUTPUT = "--cross and -o name the same file: the two reports would overwrite each other. Exiting."
+SAME_CROSS_TEMPORAL = "--cross and --temporal name the same file: the two reports would overwrite each other. Exiting."
+CROSS_NEEDS_CHROMA = "--cross compares chroma with luma: the clip has no chroma planes"
 SAME_LEVELS = "--levels and -o name the same file: the two outputs would overwrite each other. Exiting."
 NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
 BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
@@ -265,6 +268,8 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: the current device)")
     m.add_argument("--temporal", metavar="PATH", default=None,
                    help="also write the temporal profile: the correlation of the residual with the residual of the frame before")
+    m.add_argument("--cross", metavar="PATH", default=None,
+                   help="also write the cross-plane profile: the chroma residuals against the luma residual under them and against each other")
     c = sub.add_parser("check", help="Says how well a grain table fits: the profile of SOURCE - DENOISED beside the profile of the "
                                      "table's grain rendered onto DENOISED (y4m inputs).  Reports; passes no verdict.")
     c.add_argument("source", help="The untouched source file.")
@@ -277,6 +282,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="render with the output clipped to the restricted (studio) range, as `render --clip-restricted`")
     c.add_argument("--temporal", metavar="PATH", default=None,
                    help="also write the two-column temporal profile: frame-to-frame correlation of both residuals")
+    c.add_argument("--cross", metavar="PATH", default=None,
+                   help="also write the two-column cross-plane profile: chroma against luma (the table's chroma-from-luma coefficient) "
+                        "and Cb against Cr, of both residuals")
     return ap
 
 
@@ -427,8 +435,37 @@ def _temporal_refused(inputs, output: str, temporal: Optional[str]) -> bool:
     return False
 
 
+def _cross_refused(inputs, output: str, temporal: Optional[str], cross: Optional[str], clip: str) -> bool:
+    """--cross PATH is an output too: not an input, not -o's path, not --temporal's; and the clip needs chroma planes."""
+    if cross is None:
+        return False
+    if any(_same_path(p, cross) for p in inputs):
+        log.error(SAME_AS_OUTPUT)
+        return True
+    if _same_path(output, cross):
+        log.error(SAME_CROSS_OUTPUT)
+        return True
+    if temporal is not None and _same_path(temporal, cross):
+        log.error(SAME_CROSS_TEMPORAL)
+        return True
+    if _y4m_is_monochrome(clip):
+        log.error(CROSS_NEEDS_CHROMA)
+        return True
+    return False
+
+
+def _y4m_is_monochrome(path: str) -> bool:
+    """Does the .y4m header name a colour space without chroma planes?  (An unreadable file is the reader's to refuse.)"""
+    try:
+        with open(path, "rb") as f:
+            header = f.read(256).split(b"\n", 1)[0]
+    except OSError:
+        return False
+    return header.startswith(b"YUV4MPEG2") and any(t.startswith(b"Cmono") for t in header.split()[1:])
+
+
 def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
-                    temporal: Optional[str] = None) -> int:
+                    temporal: Optional[str] = None, cross: Optional[str] = None) -> int:
     """The refusals of `diff` for two inputs and an output, then the frame pairs until the shorter file ends and the
     profile (with `temporal`, the temporal profile beside it).  Returns the frame count, -1 after a refusal."""
     from .measure import measure_y4m_files
@@ -439,21 +476,23 @@ def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False
     if _same_path(noisy, clean):
         log.error(SAME_INPUTS)
         return -1
-    if _temporal_refused((noisy, clean), output, temporal):
+    if _temporal_refused((noisy, clean), output, temporal) or _cross_refused((noisy, clean), output, temporal, cross, clean):
         return -1
-    for path in (output, temporal):
+    for path in (output, temporal, cross):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
-    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device, temporal_output=temporal)
+    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device, temporal_output=temporal, cross_output=cross)
     log.info("Done, wrote output file to %s", output)
     if temporal is not None:
         log.info("Done, wrote temporal profile to %s", temporal)
+    if cross is not None:
+        log.info("Done, wrote cross profile to %s", cross)
     return frames
 
 
 def check_command(source: str, denoised: str, table: str, output: str, overwrite: bool = False, device: int = -1,
-                  clip_restricted: bool = False, confirm=_confirm, temporal: Optional[str] = None) -> int:
+                  clip_restricted: bool = False, confirm=_confirm, temporal: Optional[str] = None, cross: Optional[str] = None) -> int:
     """The same refusals (the table is an input too), then the two profiles side by side.  No verdict, no threshold.
     Returns the frame count, -1 after a refusal."""
     from .measure import check_y4m_files
@@ -464,17 +503,19 @@ def check_command(source: str, denoised: str, table: str, output: str, overwrite
     if _same_path(source, denoised):
         log.error(SAME_INPUTS)
         return -1
-    if _temporal_refused((source, denoised, table), output, temporal):
+    if _temporal_refused((source, denoised, table), output, temporal) or _cross_refused((source, denoised, table), output, temporal, cross, denoised):
         return -1
-    for path in (output, temporal):
+    for path in (output, temporal, cross):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
     frames, _unequal = check_y4m_files(source, denoised, table, output, device=device, clip_to_restricted_range=clip_restricted,
-                                       temporal_output=temporal)
+                                       temporal_output=temporal, cross_output=cross)
     log.info("Done, wrote output file to %s", output)
     if temporal is not None:
         log.info("Done, wrote temporal profile to %s", temporal)
+    if cross is not None:
+        log.info("Done, wrote cross profile to %s", cross)
     return frames
 
 
@@ -520,14 +561,14 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
     elif args.command == "measure":
         try:
-            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device, temporal=args.temporal)
+            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device, temporal=args.temporal, cross=args.cross)
         except Exception as e:
             log.error("%s", e)
             return 1
     elif args.command == "check":
         try:
             check_command(args.source, args.denoised, args.grain, args.output, args.overwrite, args.device, args.clip_restricted,
-                          temporal=args.temporal)
+                          temporal=args.temporal, cross=args.cross)
         except Exception as e:
             log.error("%s", e)
             return 1

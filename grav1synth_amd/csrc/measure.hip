@@ -12,6 +12,7 @@
 //                    plain stores.
 //   km_tail          a workgroup per (plane, frame pair) sums the partial records into the pair's record.
 // A temporal meter (rules 7 - 11) runs km_measure_t and km_tail_t behind them: they stand below km_tail with their own notes.
+// A cross meter (rules 12 - 17) runs km_measure_x and km_tail_t behind those: below km_tail_t.
 //
 // The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
 //   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
@@ -363,6 +364,163 @@ __global__ __launch_bounds__(kTTailWidth * kTTailGroups) void km_tail_t(TailPara
   }
 }
 
+// ---- the cross record (rules 12 - 17): the chroma residuals against the luma residual under them, and against each other ----
+//   km_measure_x<BPS>  a workgroup per (chroma tile, pair), km_measure_t's tile and waves with other operands.  LDS: d_Cb of
+//                      the tile as int16 without a halo; d_Cr and L (rule 12: the rounded mean of the luma residual under a
+//                      chroma sample, formed here from the (1 + xdec)(1 + ydec) luma samples of both frames) as int16 with a
+//                      halo of 2 on all four sides, zeros outside the chroma plane; the tile's bins as bytes; ONE set of the
+//                      waves' accumulators.  Everything is loaded once a tile; the three pairings (d_Cb, L), (d_Cr, L),
+//                      (d_Cb, d_Cr) then walk the tile one after another through one set of 25 lag accumulators and one set
+//                      of running bin sums (cross_pass<J>), and the workgroup's partial record of a pairing goes out with
+//                      plain stores before the next one starts.
+//   km_tail_t          sums the partials unchanged: they lie as [pair][pairing][tile][kTEntries], so that a "plane" is a
+//                      pairing and all three tile counts are the chroma plane's.
+// The 32-bit sums are km_measure_t's: |L| <= 2^B - 1 (a rounded mean of residuals), so every product stays below 2^24.
+constexpr int kXLdsBytes = 2 * kTH * kTW + 2 * 2 * kPH * kPW + kTH * kTW + 8 * kWaves * kTEntries;
+static_assert(kRowsPerWave <= 127, "a 32-bit sum of km_measure_x holds 127 products of 12-bit residuals, one a row");
+static_assert(sizeof(g1s_measure_xrecord_t) == 8 * 3 * kTEntries, "km_tail_t writes the cross record as 64-bit words");
+static_assert(kXLdsBytes == 65376 && kXLdsBytes <= 65536, "km_measure_x: 160 bytes under 64 KiB, two workgroups a CU");
+
+struct CrossParams {
+  const MeasureJob *jobs;
+  unsigned long long *partials;  // [pair][pairing][tiles][kTEntries]
+  int cw, ch, tiles_x;           // the chroma plane
+  int W, H, xdec, ydec, shift;   // the luma plane, chroma decimation, B - 5
+  uint32_t tiles;                // of the chroma plane
+};
+
+// one pairing over the wave's rows: J = 0 (d_Cb, L), 1 (d_Cr, L), 2 (d_Cb, d_Cr).  km_measure_t's row loop: a = the tile's
+// own sample, b = the 5 x 5 window round it in a plane with a halo.
+template <int J>
+__device__ __forceinline__ void cross_pass(const int16_t *s_d, const int16_t *s_r, const int16_t *s_l, const uint8_t *s_bin,
+                                           unsigned long long *mine, int row0, int rows, int lane) {
+  const int16_t *s_b = J == 2 ? s_r : s_l;
+  int acc[kTLags];
+#pragma unroll
+  for (int i = 0; i < kTLags; ++i) acc[i] = 0;
+  int w[kTWin][kTWin];
+#pragma unroll
+  for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+    for (int k = 0; k < kTWin; ++k) w[q + 1][k] = s_b[(row0 + q) * kPW + lane + k];
+  int cur = -1, bn = 0, bx = 0, bu = 0, bv = 0;  // the bin the lane's column is in and its sums so far (cur < 0: none)
+  auto hand_on = [&](bool go) __attribute__((always_inline)) {
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
+    while (todo) {
+      const int b = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(todo));
+      const bool m = go && cur == b;
+      todo &= ~__builtin_amdgcn_ballot_w64(m);
+      const int n = wave_sum(m ? bn : 0);
+      const long long x = wave_sum_wide(m ? bx : 0), u = wave_sum_wide(m ? bu : 0), v = wave_sum_wide(m ? bv : 0);
+      if (lane == 0) {
+        mine[b] += (unsigned long long)(long long)n;
+        mine[kBins + b] += (unsigned long long)x;
+        mine[2 * kBins + b] += (unsigned long long)u;
+        mine[3 * kBins + b] += (unsigned long long)v;
+      }
+      if (m) cur = -1, bn = bx = bu = bv = 0;
+    }
+  };
+  for (int r = 0; r < rows; ++r) {
+#pragma unroll
+    for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) w[q][k] = w[q + 1][k];
+#pragma unroll
+    for (int k = 0; k < kTWin; ++k) w[kTWin - 1][k] = s_b[(row0 + r + kTWin - 1) * kPW + lane + k];
+    const int d = J == 1 ? (int)s_r[(row0 + r + kTHalo) * kPW + lane + kTHalo] : (int)s_d[(row0 + r) * kTW + lane];
+#pragma unroll
+    for (int q = 0; q < kTWin; ++q)
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) acc[q * kTWin + k] += __mul24(d, w[q][k]);
+    const int e = w[kTHalo][kTHalo];
+    const int k = s_bin[(row0 + r) * kTW + lane];
+    const bool change = cur >= 0 && k != cur;
+    if (__builtin_amdgcn_ballot_w64(change)) hand_on(change);
+    if (k != kNoBin) cur = k, bn += 1, bx += __mul24(d, e), bu += __mul24(d, d), bv += __mul24(e, e);
+  }
+  hand_on(cur >= 0);
+#pragma unroll
+  for (int i = 0; i < kTLags; ++i) {
+    const long long t = wave_sum_wide(acc[i]);
+    if (lane == 0) mine[4 * kBins + i] = (unsigned long long)t;
+  }
+}
+
+template <int BPS>
+__global__ __launch_bounds__(kThreads) void km_measure_x(CrossParams p) {
+  __shared__ int16_t s_d[kTH * kTW];
+  __shared__ int16_t s_r[kPH * kPW];
+  __shared__ int16_t s_l[kPH * kPW];
+  __shared__ uint8_t s_bin[kTH * kTW];
+  __shared__ unsigned long long s_acc[kWaves][kTEntries];  // (two's complement, as km_measure's)
+  static_assert(sizeof(s_d) + sizeof(s_r) + sizeof(s_l) + sizeof(s_bin) + sizeof(s_acc) == kXLdsBytes, "the LDS budget above");
+  const MeasureJob &job = p.jobs[blockIdx.z];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const int x0 = tx * kTW, y0 = ty * kTH;
+  const uint8_t *ya = job.a[0], *yb = job.b[0];
+  const uint32_t sya = job.a_stride[0], syb = job.b_stride[0];
+
+  for (int i = tid; i < kWaves * kTEntries; i += kThreads) (&s_acc[0][0])[i] = 0;
+  // d_Cr and L of the tile with their halo; for the tile's own samples d_Cb and the bin beside them
+  const int round = (1 << (p.xdec + p.ydec)) >> 1;
+  for (int i = tid; i < kPH * kPW; i += kThreads) {
+    const int ly = i / kPW, lx = i - ly * kPW;
+    const int x = x0 + lx - kTHalo, y = y0 + ly - kTHalo;
+    const bool inside = x >= 0 && x < p.cw && y >= 0 && y < p.ch;
+    const bool own = lx >= kTHalo && lx < kTHalo + kTW && ly >= kTHalo && ly < kTHalo + kTH;
+    int d = 0, e = 0, L = 0, bin = kNoBin;
+    if (inside) {
+      e = sample<BPS>(job.a[2], job.a_stride[2], x, y) - sample<BPS>(job.b[2], job.b_stride[2], x, y);
+      // rule 12: the box of the luma residual under the sample, clamped at the luma plane's edges, rounded towards minus infinity
+      const int xs = x << p.xdec, ys = y << p.ydec;
+      const int xs1 = min(xs + p.xdec, p.W - 1), ys1 = min(ys + p.ydec, p.H - 1);
+      const int b00 = sample<BPS>(yb, syb, xs, ys);
+      int S = sample<BPS>(ya, sya, xs, ys) - b00, b01 = b00;
+      if (p.xdec) {
+        b01 = sample<BPS>(yb, syb, xs1, ys);
+        S += sample<BPS>(ya, sya, xs1, ys) - b01;
+        if (p.ydec) S += sample<BPS>(ya, sya, xs, ys1) - sample<BPS>(yb, syb, xs, ys1) + sample<BPS>(ya, sya, xs1, ys1) - sample<BPS>(yb, syb, xs1, ys1);
+      }
+      L = (S + round) >> (p.xdec + p.ydec);
+      if (own) {
+        d = sample<BPS>(job.a[1], job.a_stride[1], x, y) - sample<BPS>(job.b[1], job.b_stride[1], x, y);
+        const int I = p.xdec ? (b00 + b01 + 1) >> 1 : b00;  // averageLuma of the clean frame
+        bin = min(I >> p.shift, kBins - 1);
+      }
+    }
+    s_r[i] = (int16_t)e;
+    s_l[i] = (int16_t)L;
+    if (own) {
+      const int at = (ly - kTHalo) * kTW + (lx - kTHalo);
+      s_d[at] = (int16_t)d;
+      s_bin[at] = (uint8_t)bin;
+    }
+  }
+  __syncthreads();
+
+  const int row0 = wave * kRowsPerWave, rows = min(kRowsPerWave, p.ch - (y0 + row0));
+  // the pairing's partial record out, the accumulators zero again (an entry is read and cleared by one thread)
+  auto hand_over = [&](int j) __attribute__((always_inline)) {
+    __syncthreads();
+    if (tid < kTEntries) {
+      unsigned long long t = 0;
+#pragma unroll
+      for (int v = 0; v < kWaves; ++v) t += s_acc[v][tid], s_acc[v][tid] = 0;
+      const size_t at = ((size_t)blockIdx.z * 3 + (size_t)j) * p.tiles + blockIdx.x;
+      p.partials[at * kTEntries + tid] = t;
+    }
+    __syncthreads();
+  };
+  if (rows > 0) cross_pass<0>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  hand_over(0);
+  if (rows > 0) cross_pass<1>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  hand_over(1);
+  if (rows > 0) cross_pass<2>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  hand_over(2);
+}
+
 // rule 8's offsets: raster order, (0, 0) is index 12
 void temporal_offset(int i, int *dx, int *dy) { *dy = i / kTWin - kTHalo, *dx = i % kTWin - kTHalo; }
 
@@ -406,6 +564,19 @@ struct g1s_measure : BatchedOp {
   std::vector<g1s_measure_trecord_t> trecords;  // since the last hand-over
   double ms_tkernel = 0;
   uint64_t pairs_timed = 0;
+  // a cross meter (rules 12 - 17): a cross record a pair, from the batch's own jobs
+  bool cross = false;
+  Event ev_x[2];
+  DevBuf<unsigned long long> d_xpartials;
+  size_t xpartials_cap = 0;
+  DevBuf<g1s_measure_xrecord_t> d_xrecs;
+  PinnedBuf<g1s_measure_xrecord_t> h_xrecs;
+  std::vector<g1s_measure_xrecord_t> xrecords;  // since the last hand-over
+  double ms_xkernel = 0;
+  uint64_t xpairs_timed = 0;
+  // the chroma launches alone, for tools/bench_measure.py --cross (recorded only while timing is on)
+  Event ev_c[2], ev_tc[2];
+  double ms_chroma = 0, ms_tchroma = 0;
 
   int set_geometry(const g1s_frame_t &f);
   int flush();
@@ -432,6 +603,12 @@ int g1s_measure::set_geometry(const g1s_frame_t &f) {
     G1S_OP_TRY(hipMalloc((void **)&d_tpartials.p, tneed * sizeof(unsigned long long)));
     tpartials_cap = tneed;
   }
+  const size_t xneed = cross && geom.nplanes == 3 ? (size_t)tiles[1] * 3 * kTEntries * batch : 0;
+  if (xneed > xpartials_cap) {
+    d_xpartials = DevBuf<unsigned long long>();
+    G1S_OP_TRY(hipMalloc((void **)&d_xpartials.p, xneed * sizeof(unsigned long long)));
+    xpartials_cap = xneed;
+  }
   have_prev = false, ring_at = 0;  // (a new geometry ends the run; the rings are made again)
   d_keep[0] = DevBuf<uint8_t>(), d_keep[1] = DevBuf<uint8_t>();
   return G1S_OK;
@@ -454,9 +631,11 @@ int g1s_measure::flush() {
     mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
     mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
     const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, B);
+    if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_c[0], stream));
     if (bps == 2) hipLaunchKernelGGL(km_measure<2>, grid, dim3(kThreads), 0, stream, mp);
     else hipLaunchKernelGGL(km_measure<1>, grid, dim3(kThreads), 0, stream, mp);
     G1S_OP_TRY(hipGetLastError());
+    if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_c[1], stream));
   }
   TailParams tp{};
   tp.partials = d_partials, tp.records = reinterpret_cast<unsigned long long *>(d_recs.p), tp.tiles_frame = tiles_frame;
@@ -479,9 +658,11 @@ int g1s_measure::flush() {
       mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
       mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
       const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, T);
+      if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_tc[0], stream));
       if (bps == 2) hipLaunchKernelGGL(km_measure_t<2>, grid, dim3(kThreads), 0, stream, mp);
       else hipLaunchKernelGGL(km_measure_t<1>, grid, dim3(kThreads), 0, stream, mp);
       G1S_OP_TRY(hipGetLastError());
+      if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_tc[1], stream));
     }
     TailParams ttp = tp;
     ttp.partials = d_tpartials, ttp.records = reinterpret_cast<unsigned long long *>(d_trecs.p);
@@ -489,6 +670,29 @@ int g1s_measure::flush() {
     G1S_OP_TRY(hipGetLastError());
     if (timing) G1S_OP_TRY(hipEventRecord(ev_t[1], stream));
     G1S_OP_TRY(hipMemcpyAsync(h_trecs, d_trecs, sizeof(g1s_measure_trecord_t) * T, hipMemcpyDeviceToHost, stream));
+  }
+  // a cross meter: the batch's own jobs once more, one km_measure_x launch and km_tail_t over its partials, where a pairing
+  // stands for a plane (a pair with one plane keeps the zeros of the memset)
+  if (cross) {
+    G1S_OP_TRY(hipMemsetAsync(d_xrecs, 0, sizeof(g1s_measure_xrecord_t) * B, stream));
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_x[0], stream));
+    if (geom.nplanes == 3) {
+      CrossParams xp{};
+      xp.jobs = p_jobs.d[set], xp.partials = d_xpartials;
+      xp.cw = (int)geom.pw(1), xp.ch = (int)geom.ph(1), xp.tiles_x = (xp.cw + kTW - 1) / kTW;
+      xp.W = geom.W, xp.H = (int)geom.ph(0), xp.xdec = geom.subx, xp.ydec = geom.suby, xp.shift = (int)bit_depth - 5;
+      xp.tiles = tiles[1];
+      if (bps == 2) hipLaunchKernelGGL(km_measure_x<2>, dim3(tiles[1], 1u, B), dim3(kThreads), 0, stream, xp);
+      else hipLaunchKernelGGL(km_measure_x<1>, dim3(tiles[1], 1u, B), dim3(kThreads), 0, stream, xp);
+      G1S_OP_TRY(hipGetLastError());
+      TailParams xtp{};
+      xtp.partials = d_xpartials, xtp.records = reinterpret_cast<unsigned long long *>(d_xrecs.p), xtp.tiles_frame = 3 * tiles[1];
+      for (int j = 0; j < 3; ++j) xtp.tiles[j] = tiles[1], xtp.tile_base[j] = (uint32_t)j * tiles[1];
+      hipLaunchKernelGGL(km_tail_t, dim3(3u, B), dim3(kTTailWidth * kTTailGroups), 0, stream, xtp);
+      G1S_OP_TRY(hipGetLastError());
+    }
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_x[1], stream));
+    G1S_OP_TRY(hipMemcpyAsync(h_xrecs, d_xrecs, sizeof(g1s_measure_xrecord_t) * B, hipMemcpyDeviceToHost, stream));
   }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
   if (timing) {
@@ -498,10 +702,23 @@ int g1s_measure::flush() {
     if (T) {
       G1S_OP_TRY(hipEventElapsedTime(&ms, ev_t[0], ev_t[1]));
       ms_tkernel += ms, pairs_timed += T;
+      if (geom.nplanes == 3) {
+        G1S_OP_TRY(hipEventElapsedTime(&ms, ev_tc[0], ev_tc[1]));
+        ms_tchroma += ms;
+      }
+    }
+    if (geom.nplanes == 3) {
+      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_c[0], ev_c[1]));
+      ms_chroma += ms;
+    }
+    if (cross) {
+      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_x[0], ev_x[1]));
+      ms_xkernel += ms, xpairs_timed += B;
     }
   }
   records.insert(records.end(), h_recs.p, h_recs.p + B);
   trecords.insert(trecords.end(), h_trecs.p, h_trecs.p + T);
+  if (cross) xrecords.insert(xrecords.end(), h_xrecs.p, h_xrecs.p + B);
   jobs.clear();
   tjobs.clear();
   return G1S_OK;
@@ -608,6 +825,21 @@ std::string write_treport(const char *path, const g1s_measure_trecord_t &total, 
   return "";
 }
 
+// the cross report of a clip's cross record(s) into a file.  "" when fine
+std::string write_xreport(const char *path, const g1s_measure_xrecord_t &total, const g1s_measure_xrecord_t *synth, uint64_t frames,
+                          const g1s_y4m_info_t &info) {
+  std::vector<char> buf(1 << 16);
+  const long n = g1s_format_measure_cross(&total, synth, frames, info.bit_depth, info.width, info.height, info.xdec, info.ydec, buf.data(), buf.size());
+  if (n < 0) return "formatting the cross report failed";
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return std::string("cannot create ") + path;
+  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
+  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
+  return "";
+}
+
+const char kCrossNeedsChroma[] = "--cross compares chroma with luma: the clip has no chroma planes";
+
 bool same_clip_shape(const g1s_y4m_info_t &a, const g1s_y4m_info_t &b) {
   return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.xdec == b.xdec && a.ydec == b.ydec && a.nplanes == b.nplanes;
 }
@@ -634,6 +866,18 @@ std::string take_trecords(g1s_measure_t *m, std::vector<g1s_measure_trecord_t> &
   if (n && (rc = g1s_measure_finish_temporal(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
   if (g1s_measure_sum_temporal(scratch.data(), n + 1, &total) != 0) return "the clip's temporal sums leave 64 bits";
   pairs += n;
+  return "";
+}
+
+// the cross records the meter holds, added to `total`.  "" when fine
+std::string take_xrecords(g1s_measure_t *m, std::vector<g1s_measure_xrecord_t> &scratch, g1s_measure_xrecord_t &total) {
+  size_t n = 0;
+  int rc = g1s_measure_finish_cross(m, nullptr, 0, &n);
+  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
+  scratch.resize(n + 1);
+  scratch[n] = total;
+  if (n && (rc = g1s_measure_finish_cross(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
+  if (g1s_measure_sum_cross(scratch.data(), n + 1, &total) != 0) return "the clip's cross sums leave 64 bits";
   return "";
 }
 
@@ -677,9 +921,20 @@ int not_temporal(g1s_measure_t *m) {
   return G1S_ERR_INVALID;
 }
 
-// g1s_measure_new and g1s_measure_new_temporal: the same refusals, the same meter but for the temporal buffers
-g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, bool temporal) {
+int not_cross(g1s_measure_t *m) {
+  m->err = "the meter was not made by g1s_measure_new_modes with G1S_MEASURE_CROSS";  // (not sticky: err_code stays 0)
+  return G1S_ERR_INVALID;
+}
+
+// g1s_measure_new, g1s_measure_new_temporal and g1s_measure_new_modes: the same refusals, the same meter but for the buffers
+// of the modes
+g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes) {
   g1s_set_global_error_("");
+  if (modes & ~(uint32_t)(G1S_MEASURE_TEMPORAL | G1S_MEASURE_CROSS)) {
+    g1s_set_global_error_("unknown mode bits: g1s_measure_new_modes takes G1S_MEASURE_TEMPORAL and G1S_MEASURE_CROSS");
+    return nullptr;
+  }
+  const bool temporal = (modes & G1S_MEASURE_TEMPORAL) != 0, cross = (modes & G1S_MEASURE_CROSS) != 0;
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
     g1s_set_global_error_("measure is defined for bit depths 8, 10 and 12");
     return nullptr;
@@ -695,16 +950,23 @@ g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, b
     return nullptr;
   }
   g1s_measure *m = new g1s_measure;
-  m->temporal = temporal;
+  m->temporal = temporal, m->cross = cross;
   bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
   const uint32_t B = m->batch;
   for (Event &e : m->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  for (Event &e : m->ev_c) ok = ok && hipEventCreate(&e.p) == hipSuccess;
   ok = ok && m->p_jobs.alloc(B) && hipMalloc((void **)&m->d_recs.p, sizeof(g1s_measure_record_t) * B) == hipSuccess &&
        hipHostMalloc((void **)&m->h_recs.p, sizeof(g1s_measure_record_t) * B, hipHostMallocDefault) == hipSuccess;
   if (temporal) {
     for (Event &e : m->ev_t) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    for (Event &e : m->ev_tc) ok = ok && hipEventCreate(&e.p) == hipSuccess;
     ok = ok && m->p_tjobs.alloc(B) && hipMalloc((void **)&m->d_trecs.p, sizeof(g1s_measure_trecord_t) * B) == hipSuccess &&
          hipHostMalloc((void **)&m->h_trecs.p, sizeof(g1s_measure_trecord_t) * B, hipHostMallocDefault) == hipSuccess;
+  }
+  if (cross) {
+    for (Event &e : m->ev_x) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    ok = ok && hipMalloc((void **)&m->d_xrecs.p, sizeof(g1s_measure_xrecord_t) * B) == hipSuccess &&
+         hipHostMalloc((void **)&m->h_xrecs.p, sizeof(g1s_measure_xrecord_t) * B, hipHostMallocDefault) == hipSuccess;
   }
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
@@ -718,9 +980,11 @@ g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, b
 
 extern "C" {
 
-g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, false); }
+g1s_measure_t *g1s_measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, 0); }
 
-g1s_measure_t *g1s_measure_new_temporal(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, true); }
+g1s_measure_t *g1s_measure_new_temporal(uint32_t bit_depth, const g1s_measure_opts_t *opts) { return measure_new(bit_depth, opts, G1S_MEASURE_TEMPORAL); }
+
+g1s_measure_t *g1s_measure_new_modes(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes) { return measure_new(bit_depth, opts, modes); }
 
 int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_frame_t *clean) {
   if (!m || !noisy || !clean) return G1S_ERR_INVALID;
@@ -772,6 +1036,34 @@ int g1s_measure_finish_temporal(g1s_measure_t *m, g1s_measure_trecord_t *per_pai
   if (m->trecords.size() > cap || (!per_pair && !m->trecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
   if (!m->trecords.empty()) std::memcpy(per_pair, m->trecords.data(), sizeof(g1s_measure_trecord_t) * m->trecords.size());
   m->trecords.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_finish_cross(g1s_measure_t *m, g1s_measure_xrecord_t *per_pair, size_t cap, size_t *n_out) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  if (!m->cross) return not_cross(m);
+  (void)hipSetDevice(m->device);
+  int rc = m->flush();
+  if (rc || (rc = m->keep_prev()) != 0) return rc;
+  if (n_out) *n_out = m->xrecords.size();
+  if (m->xrecords.size() > cap || (!per_pair && !m->xrecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
+  if (!m->xrecords.empty()) std::memcpy(per_pair, m->xrecords.data(), sizeof(g1s_measure_xrecord_t) * m->xrecords.size());
+  m->xrecords.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_cross_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
+  if (!m) return G1S_ERR_INVALID;
+  if (ms_kernel) *ms_kernel = m->ms_xkernel;
+  if (pairs) *pairs = m->xpairs_timed;
+  return G1S_OK;
+}
+
+int g1s_measure_chroma_timing(g1s_measure_t *m, double *ms_chroma, double *ms_temporal_chroma) {
+  if (!m) return G1S_ERR_INVALID;
+  if (ms_chroma) *ms_chroma = m->ms_chroma;
+  if (ms_temporal_chroma) *ms_temporal_chroma = m->ms_tchroma;
   return G1S_OK;
 }
 
@@ -928,6 +1220,92 @@ long g1s_format_measure_temporal(const g1s_measure_trecord_t *total, const g1s_m
   return (long)s.size();
 }
 
+int g1s_measure_sum_cross(const g1s_measure_xrecord_t *recs, size_t n, g1s_measure_xrecord_t *total) {
+  return g1s_measure_sum_temporal(recs, n, total);  // (one type, one body: the pairing stands where the plane does)
+}
+
+long g1s_format_measure_cross(const g1s_measure_xrecord_t *total, const g1s_measure_xrecord_t *synth, uint64_t frames, uint32_t bit_depth,
+                              uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, char *buf, size_t cap) {
+  if (!total || (!buf && cap) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
+  g1s_frame_t shape{};
+  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = 3;
+  const PlaneGeom g(shape, 1);
+  static const char *const names[3] = {"cb_luma", "cr_luma", "cb_cr"};
+  std::string s = "graincross1\n";
+  s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + "\n";
+  double terms[kTLags];
+  for (int i = 0; i < kTLags; ++i) {
+    int dx, dy;
+    temporal_offset(i, &dx, &dy);
+    const int64_t tw = (int64_t)g.pw(1) - std::abs(dx), th = (int64_t)g.ph(1) - std::abs(dy);
+    terms[i] = tw > 0 && th > 0 ? (double)frames * (double)tw * (double)th : 0.0;
+  }
+  // the printed values of a pairing of a record: rule 11's profile (the layouts are one), the slopes beside it
+  struct XProfile {
+    TProfile t;
+    bool has_slope[kBins], has_beta;
+    double slope[kBins], beta;
+  };
+  auto xprofile_of = [&](const g1s_measure_xrecord_t &r, int j) {
+    XProfile p{};
+    p.t = tprofile_of(r, j, terms);
+    uint64_t V = 0;
+    for (int k = 0; k < kBins; ++k) {
+      V += r.v[j][k];
+      p.has_slope[k] = r.v[j][k] != 0;
+      if (p.has_slope[k]) p.slope[k] = (double)r.x[j][k] / (double)r.v[j][k];
+    }
+    p.has_beta = V != 0;
+    if (p.has_beta) p.beta = (double)r.c[j][kTLags / 2] / (double)V;
+    return p;
+  };
+  // partial_rho of the three zero_rho of a column
+  auto partial = [](const XProfile q[3]) {
+    const int z = kTLags / 2;
+    if (!q[0].t.has_lag[z] || !q[1].t.has_lag[z] || !q[2].t.has_lag[z]) return value(false, 0.0);
+    const double r0 = q[0].t.lag[z], r1 = q[1].t.lag[z], r2 = q[2].t.lag[z];
+    const double f0 = 1.0 - r0 * r0, f1 = 1.0 - r1 * r1;
+    if (f0 <= 0.0 || f1 <= 0.0) return value(false, 0.0);
+    return value(true, (r2 - r0 * r1) / std::sqrt(f0 * f1));
+  };
+  XProfile a[3], b[3];
+  for (int j = 0; j < 3; ++j) {
+    s += std::string("pairing ") + names[j] + "\n";
+    if (!frames) continue;
+    a[j] = xprofile_of(*total, j);
+    if (synth) b[j] = xprofile_of(*synth, j);
+    for (int k = 0; k < kBins; ++k) {
+      if (!total->n[j][k]) continue;
+      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[j][k]) + " " + value(a[j].t.has_bin[k], a[j].t.bin[k]) + " " +
+           value(a[j].has_slope[k], a[j].slope[k]);
+      if (synth) s += " " + value(b[j].t.has_bin[k], b[j].t.bin[k]) + " " + value(b[j].has_slope[k], b[j].slope[k]);
+      s += "\n";
+    }
+    for (int i = 0; i < kTLags; ++i) {
+      int dx, dy;
+      temporal_offset(i, &dx, &dy);
+      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a[j].t.has_lag[i], a[j].t.lag[i]);
+      if (synth) s += " " + value(b[j].t.has_lag[i], b[j].t.lag[i]);
+      s += "\n";
+    }
+    s += "zero_rho " + value(a[j].t.has_lag[kTLags / 2], a[j].t.lag[kTLags / 2]);
+    if (synth) s += " " + value(b[j].t.has_lag[kTLags / 2], b[j].t.lag[kTLags / 2]);
+    s += "\npeak_rho " + peak_text(a[j].t);
+    if (synth) s += " " + peak_text(b[j].t);
+    s += "\nbeta " + value(a[j].has_beta, a[j].beta);
+    if (synth) s += " " + value(b[j].has_beta, b[j].beta);
+    s += "\n";
+    if (j == 2) {
+      s += "partial_rho " + partial(a);
+      if (synth) s += " " + partial(b);
+      s += "\n";
+    }
+  }
+  if (s.size() > cap) return G1S_ERR_CAPACITY;
+  std::memcpy(buf, s.data(), s.size());
+  return (long)s.size();
+}
+
 int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {
   if (!m) return G1S_ERR_INVALID;
   m->timing = enable != 0;
@@ -947,6 +1325,11 @@ int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *
 
 int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, const char *out_report, const char *out_treport,
                                        const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
+  return g1s_measure_y4m_files_modes(noisy, clean, out_report, out_treport, nullptr, opts, unequal, err, cap);
+}
+
+int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
+                                    const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
   if (unequal) *unequal = 0;
   if (!noisy || !clean || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   g1s_y4m_t *ya = g1s_y4m_open(noisy, err, cap);
@@ -969,9 +1352,13 @@ int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, con
   std::memset(&ttotal, 0, sizeof ttotal);
   std::vector<g1s_measure_trecord_t> tscratch;
   uint64_t pairs = 0;
+  g1s_measure_xrecord_t xtotal;
+  std::memset(&xtotal, 0, sizeof xtotal);
+  std::vector<g1s_measure_xrecord_t> xscratch;
+  const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
   if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
-  if (!rc && !(m = out_treport ? g1s_measure_new_temporal(ia.bit_depth, opts) : g1s_measure_new(ia.bit_depth, opts)))
-    rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && out_xreport && ia.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
+  if (!rc && !(m = g1s_measure_new_modes(ia.bit_depth, opts, modes))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   while (!rc) {
     g1s_frame_t fa, fb;
     const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
@@ -992,12 +1379,15 @@ int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, con
     if (frames % m->batch == 0) {
       if (!(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
       else if (out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
     }
   }
   if (!rc && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && !(why = write_report(out_report, total, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = write_treport(out_treport, ttotal, nullptr, pairs, ia)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
   g1s_measure_free(m);
   g1s_y4m_close(ya);
   g1s_y4m_close(yb);
@@ -1011,6 +1401,12 @@ int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char
 
 int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
                                      const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
+  return g1s_check_y4m_files_modes(source, denoised, tbl, out_report, out_treport, nullptr, opts, gopts, unequal, err, cap);
+}
+
+int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                  const char *out_xreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err,
+                                  size_t cap) {
   if (unequal) *unequal = 0;
   if (!source || !denoised || !tbl || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   // the table, as g1s_grain_y4m_file reads it
@@ -1049,8 +1445,13 @@ int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, c
   std::memset(&ttotal_s, 0, sizeof ttotal_s), std::memset(&ttotal_r, 0, sizeof ttotal_r);
   std::vector<g1s_measure_trecord_t> tscratch;
   uint64_t pairs_s = 0, pairs_r = 0;
-  auto meter = [&]() { return out_treport ? g1s_measure_new_temporal(id.bit_depth, opts) : g1s_measure_new(id.bit_depth, opts); };
+  g1s_measure_xrecord_t xtotal_s, xtotal_r;
+  std::memset(&xtotal_s, 0, sizeof xtotal_s), std::memset(&xtotal_r, 0, sizeof xtotal_r);
+  std::vector<g1s_measure_xrecord_t> xscratch;
+  const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
+  auto meter = [&]() { return g1s_measure_new_modes(id.bit_depth, opts, modes); };
   if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
+  if (!rc && out_xreport && id.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
   if (!rc && (!(ms = meter()) || !(mr = meter()))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   if (!rc) {
     g1s_grain_opts_t go{};
@@ -1086,6 +1487,7 @@ int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, c
     for (int k = 0; k < 2 && !rc; ++k)
       if (!(why = take_records(k ? mr : ms, scratch, k ? total_r : total_s)).empty()) rc = G1S_ERR_INVALID;
       else if (out_treport && !(why = take_trecords(k ? mr : ms, tscratch, k ? ttotal_r : ttotal_s, k ? pairs_r : pairs_s)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_xreport && !(why = take_xrecords(k ? mr : ms, xscratch, k ? xtotal_r : xtotal_s)).empty()) rc = G1S_ERR_INVALID;
     in_group = 0;
   };
   while (!rc) {
@@ -1123,6 +1525,7 @@ int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, c
   if (!rc && in_group) end_group();
   if (!rc && !(why = write_report(out_report, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = write_treport(out_treport, ttotal_s, &ttotal_r, pairs_s, id)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal_s, &xtotal_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
   if (ms) (void)hipSetDevice(ms->device);
   g1s_grain_free(gr);
   g1s_measure_free(mr);

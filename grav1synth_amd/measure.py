@@ -19,6 +19,15 @@ a run on, every pair has a temporal record against the pair before it.
 >>> trecords = meter.finish_temporal()          # one entry a pair but the run's first: n, x, u, v (3 x 32), c (3 x 25)
 >>> text = format_temporal_profile(sum_temporal_records(trecords), len(trecords), 10, width, height)
 >>> measure_y4m_files("grainy.y4m", "clean.y4m", "profile.txt", temporal_output="temporal.txt")
+
+A cross meter also looks across the planes (rules 12 - 17): the chroma residuals against the luma residual under them, and
+against each other.  Every pair has a cross record; the two modes combine.
+
+>>> meter = GrainMeter(10, cross=True)
+>>> for noisy, clean in pairs: meter.measure(noisy, clean)
+>>> xrecords = meter.finish_cross()             # one entry a pair: n, x, u, v (3 pairings x 32), c (3 pairings x 25)
+>>> text = format_cross_profile(sum_cross_records(xrecords), len(xrecords), 10, width, height)
+>>> check_y4m_files("source.y4m", "denoised.y4m", "table.tbl", "fit.txt", cross_output="cross.txt")
 """
 from __future__ import annotations
 
@@ -29,7 +38,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord, G1SMeasureTRecord
+from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord, G1SMeasureTRecord, G1SMeasureXRecord
 from ._frame_op import FrameOp
 from .diff import Frame
 from .ingest import UNEQUAL_WARNING
@@ -42,6 +51,9 @@ assert RECORD.itemsize == C.sizeof(G1SMeasureRecord)
 # g1s_measure_trecord_t
 TRECORD = np.dtype([("n", "<u8", (3, 32)), ("x", "<i8", (3, 32)), ("u", "<u8", (3, 32)), ("v", "<u8", (3, 32)), ("c", "<i8", (3, 25))])
 assert TRECORD.itemsize == C.sizeof(G1SMeasureTRecord)
+# g1s_measure_xrecord_t: the same fields, the first index the pairing (cb_luma, cr_luma, cb_cr)
+XRECORD = np.dtype(TRECORD.descr)
+assert XRECORD.itemsize == C.sizeof(G1SMeasureXRecord)
 
 
 def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
@@ -51,12 +63,17 @@ def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
 class GrainMeter(FrameOp):
     _name = "measure"
 
-    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False):
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False, cross: bool = False):
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal = temporal
+        self.cross = cross
         opts = _opts(device, batch_frames)
-        self._h = (self._L.g1s_measure_new_temporal if temporal else self._L.g1s_measure_new)(bit_depth, C.byref(opts))
+        if cross:
+            modes = (_lib.G1S_MEASURE_TEMPORAL if temporal else 0) | _lib.G1S_MEASURE_CROSS
+            self._h = self._L.g1s_measure_new_modes(bit_depth, C.byref(opts), modes)
+        else:
+            self._h = (self._L.g1s_measure_new_temporal if temporal else self._L.g1s_measure_new)(bit_depth, C.byref(opts))
         if not self._h:
             raise G1SError(-5, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # planes the queued kernels still read
@@ -121,6 +138,35 @@ class GrainMeter(FrameOp):
         self._keep.clear()
         return out[:n.value]
 
+    def finish_cross(self, cap: Optional[int] = None) -> np.ndarray:
+        """As finish(), for the cross records of a cross meter: one for every pair, in order, since the last finish_cross()
+        (zeros for a pair with one plane).  The ordinary and the temporal records stay until their own calls fetch them."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_measure_finish_cross(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), XRECORD)
+        rc = self._L.g1s_measure_finish_cross(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def cross_kernel_times(self) -> Tuple[float, int]:
+        """(ms in km_measure_x and its summing launch, cross records) of the batches kernel_times() had timed."""
+        a, n = C.c_double(), C.c_uint64()
+        self._L.g1s_measure_cross_timing(self._h, C.byref(a), C.byref(n))
+        return a.value, n.value
+
+    def chroma_kernel_times(self) -> Tuple[float, float]:
+        """(ms in km_measure's chroma launches, ms in km_measure_t's chroma launches) of the batches kernel_times() had timed."""
+        a, b = C.c_double(), C.c_double()
+        self._L.g1s_measure_chroma_timing(self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
     def temporal_kernel_times(self) -> Tuple[float, int]:
         """(ms in km_measure_t and km_tail_t, temporal records) of the batches kernel_times() had timed."""
         a, n = C.c_double(), C.c_uint64()
@@ -181,15 +227,42 @@ def format_temporal_profile(total: np.ndarray, pairs: int, bit_depth: int, width
     return buf.raw[:w]
 
 
+def sum_cross_records(records: np.ndarray) -> np.ndarray:
+    """Rule 16: a clip's cross record from its pairs' (g1s_measure_sum_cross; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, XRECORD).reshape(-1)
+    total = np.zeros((), XRECORD)
+    rc = _lib.lib().g1s_measure_sum_cross(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's cross sums leave 64 bits")
+    return total
+
+
+def format_cross_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1,
+                         synth: Optional[np.ndarray] = None, cap: int = 1 << 16) -> bytes:
+    """The cross report of a clip's cross record (g1s_format_measure_cross; host only): one value column, or two with
+    `synth`.  cap: the size of the buffer handed to the library (a test aid)."""
+    total = np.ascontiguousarray(total, XRECORD)
+    synth = None if synth is None else np.ascontiguousarray(synth, XRECORD)
+    buf = C.create_string_buffer(max(cap, 1))
+    w = _lib.lib().g1s_format_measure_cross(total.ctypes.data, None if synth is None else synth.ctypes.data, frames, bit_depth, width, height,
+                                            xdec, ydec, buf, cap)
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_measure_cross failed")
+    return buf.raw[:w]
+
+
+def _path(p) -> Optional[bytes]:
+    return None if p is None else str(p).encode()
+
+
 def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, batch_frames: int = 0,
-                      temporal_output: Optional[str] = None) -> Tuple[int, bool]:
-    """`measure NOISY CLEAN -o REPORT [--temporal PATH]` for two .y4m files.  Returns (frames, unequal)."""
+                      temporal_output: Optional[str] = None, cross_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`measure NOISY CLEAN -o REPORT [--temporal PATH] [--cross PATH]` for two .y4m files.  Returns (frames, unequal)."""
     opts = _opts(device, batch_frames)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_measure_y4m_files_temporal(str(noisy).encode(), str(clean).encode(), str(output).encode(),
-                                                  None if temporal_output is None else str(temporal_output).encode(), C.byref(opts),
-                                                  C.byref(unequal), err, len(err))
+    n = _lib.lib().g1s_measure_y4m_files_modes(str(noisy).encode(), str(clean).encode(), str(output).encode(), _path(temporal_output),
+                                               _path(cross_output), C.byref(opts), C.byref(unequal), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:
@@ -199,16 +272,17 @@ def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, 
 
 
 def check_y4m_files(source: str, denoised: str, table: str, output: str, *, device: int = -1, batch_frames: int = 0,
-                    clip_to_restricted_range: bool = False, temporal_output: Optional[str] = None) -> Tuple[int, bool]:
-    """`check SOURCE DENOISED -g TABLE -o REPORT [--temporal PATH]`: source - denoised beside render(denoised, table) -
-    denoised.  Returns (frames, unequal)."""
+                    clip_to_restricted_range: bool = False, temporal_output: Optional[str] = None,
+                    cross_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`check SOURCE DENOISED -g TABLE -o REPORT [--temporal PATH] [--cross PATH]`: source - denoised beside
+    render(denoised, table) - denoised.  Returns (frames, unequal)."""
     opts = _opts(device, batch_frames)
     gopts = G1SGrainOpts(C.sizeof(G1SGrainOpts), device, batch_frames, int(clip_to_restricted_range), 0)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_check_y4m_files_temporal(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(),
-                                                None if temporal_output is None else str(temporal_output).encode(), C.byref(opts),
-                                                C.byref(gopts), C.byref(unequal), err, len(err))
+    n = _lib.lib().g1s_check_y4m_files_modes(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(),
+                                             _path(temporal_output), _path(cross_output), C.byref(opts), C.byref(gopts), C.byref(unequal), err,
+                                             len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:

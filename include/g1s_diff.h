@@ -827,6 +827,27 @@ int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, con
  *  10. Sum.  A clip's temporal record is the checked 64-bit sum of its pairs' temporal records
  *      (g1s_measure_sum_temporal): an overflow is a refusal.
  *  11. Report.  g1s_format_measure_temporal writes plain text; the grammar is at its declaration.
+ * A cross meter (g1s_measure_new_modes with G1S_MEASURE_CROSS) also looks across the planes: how much of the chroma residual
+ * is the luma residual at the same place -- the last AR coefficient of each chroma plane of a table, the one field rules 1 - 11
+ * are blind to -- and whether Cb and Cr are correlated beyond what the shared luma explains.  For a pair with three planes,
+ * luma W x H, chroma cw x ch (cw = (W + xdec) >> xdec, ch = (H + ydec) >> ydec), d_Y, d_Cb, d_Cr as in rule 1:
+ *  12. The luma residual at chroma resolution.  L(x, y) = Round2(S, xdec + ydec), S the sum over i <= ydec, j <= xdec of
+ *      d_Y(min((x << xdec) + j, W - 1), min((y << ydec) + i, H - 1)); Round2(v, s) = (v + ((1 << s) >> 1)) >> s with an
+ *      ARITHMETIC shift: it rounds towards minus infinity, also for negative sums.  For 4:4:4, L = d_Y.  This is the
+ *      specification's own box and rounding for the luma grain under a chroma sample (7.18.3.3), with the clamp of rule 8 of
+ *      `denoise`.  |L| <= 2^B - 1: L is as wide as a residual.  The rounded mean and not the sum, for two reasons: it is what
+ *      the synthesis multiplies the coefficient by, so a slope on L is a number in the table's own units; and it keeps every
+ *      product below 2^24, so that the 32-bit schedule of the temporal kernel holds unchanged.
+ *  13. Three pairings (a_j, b_j) on the chroma grid: j = 0: (d_Cb, L); j = 1: (d_Cr, L); j = 2: (d_Cb, d_Cr).
+ *  14. Bins.  k(p) is rule 2's chroma bin (averageLuma of the clean frame), the same for all three pairings.  Per pairing and
+ *      bin: n[k] the count (u64), x[k] = sum of a b (i64), u[k] = sum of a^2 (u64), v[k] = sum of b^2 (u64).
+ *  15. Offsets.  Rule 8's 25 offsets (dy, dx = -2 .. 2 in raster order, (0, 0) at index 12).  c[i] = sum of a(p) b(p + delta_i)
+ *      (i64) over every p for which p AND p + delta_i lie inside the chroma plane: skipped, not clamped.  L is a cw x ch plane
+ *      like any other: the clamp of rule 12 is inside L, and nothing outside the chroma grid takes part.
+ *  16. Record.  g1s_measure_xrecord_t is g1s_measure_trecord_t with the pairing where the plane is.  All zeros for a pair with
+ *      one plane.  EVERY pair has a cross record: no predecessor is needed.  A clip's record is the checked 64-bit sum
+ *      (g1s_measure_sum_cross).  Everything is exact within rule 5's bounds.
+ *  17. Report.  g1s_format_measure_cross writes plain text; the grammar is at its declaration.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes) and a small summing launch, on the meter's own stream.  Errors are sticky (g1s_measure_last_error). */
 typedef struct {
@@ -944,6 +965,69 @@ int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, con
  * nothing extra crosses PCIe.  out_treport == NULL is exactly g1s_check_y4m_files. */
 int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
                                      const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap);
+
+/* -- the cross meter (rules 12 - 17 above) -- */
+#define G1S_MEASURE_TEMPORAL 1u
+#define G1S_MEASURE_CROSS 2u
+/* the temporal record's layout with the pairing where the plane is: n[3][32], x[3][32], u[3][32], v[3][32], c[3][25] */
+typedef g1s_measure_trecord_t g1s_measure_xrecord_t;
+/* A meter with the modes asked for (G1S_MEASURE_*, or'ed): g1s_measure_new is modes 0, g1s_measure_new_temporal is modes 1.
+ * An unknown bit is refused (NULL, the reason from g1s_last_global_error()) before anything else is looked at, a device
+ * included.  g1s_measure_opts_t is not extended.  A meter launches only what its modes ask for: with G1S_MEASURE_CROSS one
+ * km_measure_x launch and one summing launch a batch, behind the ordinary ones on the meter's stream.  A cross job reads only
+ * the planes of its own pair: the lifetime rules of a plain meter stand for modes 2, those of a temporal meter for modes 3. */
+g1s_measure_t *g1s_measure_new_modes(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes);
+/* As g1s_measure_finish_temporal, for the cross records: one per pair since the last hand-over, in order (zeros for a pair
+ * with one plane).  G1S_ERR_CAPACITY is not sticky and the records stay.  Each of the three finish calls flushes; each keeps
+ * the others' records until they are fetched.  On a meter without G1S_MEASURE_CROSS: G1S_ERR_INVALID, the text names
+ * g1s_measure_new_modes; not sticky, the meter goes on working. */
+int g1s_measure_finish_cross(g1s_measure_t *, g1s_measure_xrecord_t *per_pair, size_t cap, size_t *n_out);
+/* Rule 16 (host only, needs no device): *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_measure_sum_cross(const g1s_measure_xrecord_t *recs, size_t n, g1s_measure_xrecord_t *total);
+/* Rule 17 (host only): plain text from a clip's cross record of `frames` records of one three-plane geometry.  synth == NULL:
+ * one value column; else two (total = source - denoised, synth = rendered - denoised).  Every value is formed in f64 from the
+ * exact integers in exactly the order written here, without fused multiply-add, and printed "%.4f"; "-" where undefined.
+ *   graincross1
+ *   frames N bit_depth B
+ *   pairing cb_luma                  then cr_luma, then cb_cr; with frames = 0 nothing stands under it
+ *   bin k n rho beta [rho' beta']    the bins with n > 0 (n is total's): rho = (double)x / sqrt((double)u * (double)v), "-" when
+ *                                    u == 0 or v == 0; beta = (double)x / (double)v, "-" when v == 0
+ *   lag dx dy rho [rho']             the 25 lags in index order: rho = ((double)c[i] / terms_i) / sqrt(((double)U / T) *
+ *                                    ((double)V / T)), U = sum of u[k], V = sum of v[k] (u64 sums), T = frames cw ch,
+ *                                    terms_i = frames (cw - |dx|)(ch - |dy|); "-" when U == 0, V == 0 or terms_i == 0
+ *   zero_rho v [v']                  the (0, 0) lag
+ *   peak_rho dx dy v [dx' dy' v']    the lag of largest |rho|, the first in index order on ties; "- - -" when none is defined
+ *   beta v [v']                      (double)c[12] / (double)V; "-" when V == 0
+ *   partial_rho v [v']               after the third pairing only (and not with frames = 0): with r0, r1, r2 the three
+ *                                    zero_rho of the column, f0 = 1 - r0 * r0, f1 = 1 - r1 * r1:
+ *                                    (r2 - r0 * r1) / sqrt(f0 * f1); "-" when one of r0, r1, r2 is undefined or f0 <= 0 or f1 <= 0
+ * What the numbers mean: rho is a correlation coefficient about zero (grain has no mean).  beta of a luma pairing is the
+ * least-squares slope of the chroma residual on L alone: for a table whose chroma AR part is zero it is the table's last
+ * chroma coefficient over 2^ar_coeff_shift; with a chroma AR part it is larger, because the filter feeds the luma term back
+ * through the chroma neighbours.  So beta is not the coefficient: `check` puts the same number of the rendered grain beside
+ * it, and that comparison is the one that counts.  A peak_rho of a luma pairing away from (0, 0) is what a chroma siting error
+ * looks like.  beta of cb_cr is the slope of d_Cb on d_Cr; partial_rho is the correlation of Cb and Cr that the shared luma
+ * does not explain: the AV1 model cannot express one, so away from zero it means picture detail was removed.  There is no
+ * verdict and no threshold.  Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a geometry rule 5 does not have). */
+long g1s_format_measure_cross(const g1s_measure_xrecord_t *total, const g1s_measure_xrecord_t *synth, uint64_t frames, uint32_t bit_depth,
+                              uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, char *buf, size_t cap);
+/* HIP-event time of km_measure_x and its summing launch in the batches g1s_measure_set_timing had timed, milliseconds, and
+ * the cross records they made.  tools/bench_measure.py --cross. */
+int g1s_measure_cross_timing(g1s_measure_t *, double *ms_kernel, uint64_t *pairs);
+/* HIP-event time of the chroma launches alone in the timed batches: km_measure's and, on a temporal meter, km_measure_t's (the
+ * yardstick of km_measure_x).  The events are recorded only while timing is on.  tools/bench_measure.py --cross. */
+int g1s_measure_chroma_timing(g1s_measure_t *, double *ms_chroma, double *ms_temporal_chroma);
+/* g1s_measure_y4m_files_temporal that also writes the clip's cross report to out_xreport (one record a frame).  A clip without
+ * chroma planes is refused with out_xreport set ("--cross compares chroma with luma: the clip has no chroma planes") before a
+ * device is looked for or an output is opened.  out_xreport == NULL is exactly g1s_measure_y4m_files_temporal. */
+int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
+                                    const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap);
+/* g1s_check_y4m_files_temporal that also writes the two-column cross report: total = source - denoised, synth = rendered -
+ * denoised, whose L comes from rendered_Y - denoised_Y.  Nothing extra crosses PCIe and the rendered frame stays on the
+ * device.  out_xreport == NULL is exactly g1s_check_y4m_files_temporal. */
+int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                  const char *out_xreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err,
+                                  size_t cap);
 
 /* ---- decoder surfaces: NV12, P010 / P012 / P016 and MSB-aligned planes, to and from g1s_frame_t on the device ----
  * A hardware decoder (and an encoder on the same device) does not hold planar frames with the sample in the low bits: it

@@ -12,7 +12,13 @@ tools/bench_measure.py --temporal [repeats]: the plain and the temporal meter on
 in one process, in the order plain, temporal, plain, temporal.  A round of a meter is a warm-up batch and `repeats` timed
 batches.  Per format one JSON line: km_measure's time a frame (the yardstick; from the plain meter, and beside it from the
 temporal meter's own ordinary launches), km_measure_t's time a temporal record, their ratio, and the temporal kernel's bytes
-(four planes: both frames of both pairs, once) / time as a fraction of the 8 TB/s roofline."""
+(four planes: both frames of both pairs, once) / time as a fraction of the 8 TB/s roofline.
+
+tools/bench_measure.py --cross [repeats]: a plain, a temporal and a cross meter on the plane-distinct content of both formats, in
+one process, in the order plain, temporal, cross, twice.  Per format one JSON line: km_measure_x's time a cross record (the
+launch and its summing launch), the plain CHROMA launch (km_measure on Cb and Cr) and km_measure_t's CHROMA launch -- the
+yardstick: the cross kernel does 75 lag products a chroma sample against its 50 and reads the full-resolution luma of both
+frames in addition -- their ratios, and the cross kernel's bytes (both frames of the pair, once) / time."""
 import json, os, statistics, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +30,7 @@ from grav1synth_amd.measure import GrainMeter
 from tests import content as CT
 
 assert torch.cuda.is_available(), "bench_measure.py needs a GPU"
-argv = [a for a in sys.argv[1:] if a != "--temporal"]
+argv = [a for a in sys.argv[1:] if a not in ("--temporal", "--cross")]
 repeats = int(argv[0]) if argv else 7
 BATCH, PEAK = 32, 8e12
 
@@ -75,6 +81,63 @@ def temporal_bench():
             "km_measure_t_fraction_of_8TBps": 4 * frame_bytes / (med(temporal_us) * 1e-6) / PEAK,
         }), flush=True)
 
+
+def cross_bench():
+    for name, (w, h, bd) in (("3840x2160 10-bit 4:2:0", (3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", (1920, 1080, 8))):
+        pairs = [CT.make_frames("distinct", w, h, bd, 1, 1, frame=k) for k in range(4)]
+        noisy, clean = [dev(s) for s, _d in pairs], [dev(d) for _s, d in pairs]
+        torch.cuda.synchronize()
+        frame_bytes = sum(p.numel() for p in noisy[0]) * (1 if bd == 8 else 2)
+        us = {"plain_chroma": [], "plain_all": [], "temporal_chroma": [], "temporal_all": [], "cross": [], "plain_chroma_in_cross_meter": []}
+        for rounds in range(2):
+            for kind in ("plain", "temporal", "cross"):
+                m = GrainMeter(bd, batch_frames=BATCH, temporal=kind == "temporal", cross=kind == "cross")
+
+                def batch():
+                    for k in range(BATCH):
+                        m.measure(noisy[k % 4], clean[k % 4], 1, 1)
+                    m.finish()
+                    if kind == "temporal":
+                        m.finish_temporal()
+                    if kind == "cross":
+                        m.finish_cross()
+
+                batch()  # warm-up: code objects, buffers; a temporal run goes on, so every timed batch has BATCH temporal records
+                for _ in range(repeats):
+                    a0, n0 = m.kernel_times(True)
+                    t0, p0 = m.temporal_kernel_times()
+                    x0, q0 = m.cross_kernel_times()
+                    c0, tc0 = m.chroma_kernel_times()
+                    batch()
+                    a1, n1 = m.kernel_times(False)
+                    t1, p1 = m.temporal_kernel_times()
+                    x1, q1 = m.cross_kernel_times()
+                    c1, tc1 = m.chroma_kernel_times()
+                    assert n1 - n0 == BATCH
+                    if kind == "plain":
+                        us["plain_all"].append((a1 - a0) * 1e3 / BATCH), us["plain_chroma"].append((c1 - c0) * 1e3 / BATCH)
+                    elif kind == "temporal":
+                        assert p1 - p0 == BATCH
+                        us["temporal_all"].append((t1 - t0) * 1e3 / BATCH), us["temporal_chroma"].append((tc1 - tc0) * 1e3 / BATCH)
+                    else:
+                        assert q1 - q0 == BATCH
+                        us["cross"].append((x1 - x0) * 1e3 / BATCH), us["plain_chroma_in_cross_meter"].append((c1 - c0) * 1e3 / BATCH)
+                m.close()
+        med = statistics.median
+        out = {"format": name, "content": "distinct", "batch_frames": BATCH, "repeats": repeats, "order": "plain, temporal, cross, twice"}
+        for key, v in us.items():
+            out[f"{key}_us_median"], out[f"{key}_us_min"], out[f"{key}_us_max"] = med(v), min(v), max(v)
+        out["ratio_km_measure_x_over_km_measure_t_chroma"] = med(us["cross"]) / med(us["temporal_chroma"])
+        out["ratio_km_measure_x_over_km_measure_chroma"] = med(us["cross"]) / med(us["plain_chroma"])
+        out["km_measure_x_bytes_per_record"] = 2 * frame_bytes
+        out["km_measure_x_TBps"] = 2 * frame_bytes / (med(us["cross"]) * 1e-6) / 1e12
+        out["km_measure_x_fraction_of_8TBps"] = 2 * frame_bytes / (med(us["cross"]) * 1e-6) / PEAK
+        print(json.dumps(out), flush=True)
+
+
+if "--cross" in sys.argv[1:]:
+    cross_bench()
+    sys.exit(0)
 
 if "--temporal" in sys.argv[1:]:
     temporal_bench()
