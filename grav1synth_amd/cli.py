@@ -48,6 +48,9 @@ AUTO_NEEDS_FLAG = "--profile-frames and --levels-min-count say how --auto-prior 
 AUTO_BAD_NUMBER = "--profile-frames and --levels-min-count must not be negative. Exiting."
 AUTO_NEEDS_FILE = "--auto-prior and --auto-strength read the input twice: %s is not a regular file. Exiting."
 PRIOR_BAD_TABLE = "Invalid grain prior: %s. Exiting."
+CHROMA_PRIOR_NEEDS_PRIOR = "--chroma-prior extends the job's grain prior to chroma: it needs --grain-prior or --auto-prior. Exiting."
+CHROMA_PRIOR_NEEDS_JOINT = "--chroma-prior reads the luma under every chroma sample: it needs --joint-chroma. Exiting."
+CHROMA_PRIOR_BAD_RANGE = "--chroma-prior takes a --prior-range of 1..8. Exiting."
 PRIOR_BAD_SEGMENT = "--prior-segment %d is not in the grain prior (%d segments). Exiting."
 
 
@@ -109,6 +112,10 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
                    help="with --auto-prior / --auto-strength: measure the first N frames only (default 0: all)")
     p.add_argument("--levels-min-count", type=int, default=0, metavar="N",
                    help="with --auto-prior / --auto-strength: smooth samples an intensity bin needs to take part (default 4096)")
+    p.add_argument("--chroma-prior", action="store_true",
+                   help="with --joint-chroma and --grain-prior or --auto-prior: the chroma strength follows the grain at the luma under "
+                        "each sample -- the table's chroma scaling functions, or the chroma noise the pre-pass measured per luma bin; "
+                        "--prior-range 1..8 applies; 8-, 10-bit inputs; off by default")
 
 
 def _denoise_parameters(args) -> dict:
@@ -116,7 +123,7 @@ def _denoise_parameters(args) -> dict:
                 chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
                 grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range,
                 auto_prior=args.auto_prior, auto_strength=args.auto_strength, profile_frames=args.profile_frames,
-                levels_min_count=args.levels_min_count)
+                levels_min_count=args.levels_min_count, chroma_prior=args.chroma_prior)
 
 
 def _auto_refused(input: str, parameters: dict) -> bool:
@@ -159,6 +166,22 @@ def _auto_refused(input: str, parameters: dict) -> bool:
         if bit_depth == 12:
             log.error(PRIOR_12_BIT.replace("--grain-prior", "--auto-prior"))
             return True
+    return False
+
+
+def _chroma_prior_refused(parameters: dict) -> bool:
+    """The refusals of --chroma-prior, each a logged line: True when one was logged."""
+    if not parameters.get("chroma_prior", False):
+        return False
+    if parameters.get("grain_prior") is None and not parameters.get("auto_prior", False):
+        log.error(CHROMA_PRIOR_NEEDS_PRIOR)
+        return True
+    if not parameters.get("joint_chroma", False):
+        log.error(CHROMA_PRIOR_NEEDS_JOINT)
+        return True
+    if not 0 <= parameters.get("prior_range", 0) <= 8:
+        log.error(CHROMA_PRIOR_BAD_RANGE)
+        return True
     return False
 
 
@@ -297,7 +320,7 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
         return -1
-    if _motion_refused(parameters):
+    if _motion_refused(parameters) or _chroma_prior_refused(parameters):
         return -1
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
@@ -407,7 +430,7 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
         return -1
-    if _motion_refused(parameters):
+    if _motion_refused(parameters) or _chroma_prior_refused(parameters):
         return -1
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)

@@ -14,11 +14,9 @@ namespace g1s_cv {
 constexpr uint32_t kStabBits = 12, kStabTop = (1u << kStabBits) - 1, kInvEntries = 1u << kStabBits;  // the stabilised domain
 
 // 7.18.3.4 for the luma points of a segment: 256 entries through the points, flat outside them, zero without points
-inline void scaling_lut(const g1s_segment_t &sg, int lut[256]) {
+inline void scaling_lut_points(const uint8_t (*p)[2], int n, int lut[256]) {
   for (int x = 0; x < 256; ++x) lut[x] = 0;
-  const int n = sg.num_y_points;
   if (!n) return;
-  const uint8_t(*p)[2] = sg.scaling_points_y;
   for (int x = 0; x < p[0][0]; ++x) lut[x] = p[0][1];
   for (int i = 0; i + 1 < n; ++i) {
     const int dy = (int)p[i + 1][1] - (int)p[i][1], dx = (int)p[i + 1][0] - (int)p[i][0];
@@ -27,6 +25,7 @@ inline void scaling_lut(const g1s_segment_t &sg, int lut[256]) {
   }
   for (int x = p[n - 1][0]; x < 256; ++x) lut[x] = p[n - 1][1];
 }
+inline void scaling_lut(const g1s_segment_t &sg, int lut[256]) { scaling_lut_points(sg.scaling_points_y, sg.num_y_points, lut); }
 
 // 7.18.3.5 scale_lut at `index` of a plane of `bit_depth` bits
 inline int scale_lut(const int lut[256], int index, uint32_t bit_depth) {
@@ -121,6 +120,84 @@ inline std::string check(uint32_t bit_depth, const uint16_t *fwd, const uint16_t
   }
   for (uint32_t x = 0; x <= M; ++x)
     if (inv[fwd[x]] != x) return "curve: inv[fwd[x]] must be x (at " + std::to_string(x) + ")";
+  return "";
+}
+
+// ---- a chroma gain (rules 21 - 24): the Q8 multiplier m[256] of the joint chroma distance, indexed by the guide's top 8 bits
+constexpr int kGainEntries = 256;
+constexpr uint32_t kGainMax = 16384, kGainRangeMax = 8;
+
+// Rule 21: m from s(i), i = 0 .. 255, and a range R (0 = 4).  "" when fine, else the refusal.
+inline std::string gain_from_s(const uint8_t s[256], uint32_t range, uint16_t gain[256]) {
+  if (range > kGainRangeMax) return "chroma gain range must be 1..8 (0 = the default)";
+  if (!s || !gain) return "a chroma gain needs the scaling function it is made from and the output table";
+  const uint64_t R = range ? range : 4;
+  uint64_t top = 0;
+  for (int i = 0; i < kGainEntries; ++i) top = s[i] > top ? s[i] : top;
+  const uint64_t floor = top ? (top + R - 1) / R : 1;  // max(1, ceil(top / R))
+  uint64_t sum = 0;
+  for (int i = 0; i < kGainEntries; ++i) sum += s[i] > floor ? s[i] : floor;
+  const uint64_t sbar = (sum + 128) >> 8;
+  for (int i = 0; i < kGainEntries; ++i) {
+    const uint64_t v = s[i] > floor ? s[i] : floor, v2 = v * v;
+    const uint64_t m = (256 * sbar * sbar + (v2 >> 1)) / v2;
+    gain[i] = (uint16_t)(m < 1 ? 1 : m > kGainMax ? kGainMax : m);
+  }
+  return "";
+}
+
+// Rule 22: s(v), v = 0 .. 255, the rounded mean of the chroma scaling functions of both chroma planes of n >= 1 segments at
+// the luma v under them.  "" when fine, else the refusal.
+inline std::string chroma_s_from_segments(const g1s_segment_t *segs, size_t n, uint8_t s[256]) {
+  if (!segs || n < 1) return "a grain prior needs at least one segment";
+  for (size_t i = 0; i < n; ++i) {
+    const g1s_segment_t &sg = segs[i];
+    if (sg.num_y_points > G1S_NUM_Y_POINTS) return "segment " + std::to_string(i) + ": more than 14 luma scaling points";
+    if (sg.num_cb_points > G1S_NUM_UV_POINTS || sg.num_cr_points > G1S_NUM_UV_POINTS)
+      return "segment " + std::to_string(i) + ": more than " + std::to_string(G1S_NUM_UV_POINTS) + " chroma scaling points";
+    for (int k = 0; k + 1 < sg.num_y_points; ++k)
+      if (sg.scaling_points_y[k + 1][0] <= sg.scaling_points_y[k][0]) return "segment " + std::to_string(i) + ": luma scaling points must have increasing values";
+    for (int k = 0; k + 1 < sg.num_cb_points; ++k)
+      if (sg.scaling_points_cb[k + 1][0] <= sg.scaling_points_cb[k][0]) return "segment " + std::to_string(i) + ": chroma scaling points must have increasing values";
+    for (int k = 0; k + 1 < sg.num_cr_points; ++k)
+      if (sg.scaling_points_cr[k + 1][0] <= sg.scaling_points_cr[k][0]) return "segment " + std::to_string(i) + ": chroma scaling points must have increasing values";
+  }
+  uint64_t sum[256] = {0};
+  for (size_t i = 0; i < n; ++i) {
+    const g1s_segment_t &sg = segs[i];
+    for (int c = 0; c < 2; ++c) {
+      int lut[256];
+      if (sg.chroma_scaling_from_luma) scaling_lut(sg, lut);
+      else if (c == 0) scaling_lut_points(sg.scaling_points_cb, sg.num_cb_points, lut);
+      else scaling_lut_points(sg.scaling_points_cr, sg.num_cr_points, lut);
+      const int lm = (c ? sg.cr_luma_mult : sg.cb_luma_mult) - 128, mu = (c ? sg.cr_mult : sg.cb_mult) - 128, off = (int)(c ? sg.cr_offset : sg.cb_offset) - 256;
+      for (int v = 0; v < 256; ++v) {
+        int idx = v;
+        if (!sg.chroma_scaling_from_luma) {
+          idx = ((v * lm + 128 * mu) >> 6) + off;  // (>> of a negative int: arithmetic with every compiler this builds with)
+          idx = idx < 0 ? 0 : idx > 255 ? 255 : idx;
+        }
+        sum[v] += (uint64_t)lut[idx];
+      }
+    }
+  }
+  for (int v = 0; v < 256; ++v) s[v] = (uint8_t)((sum[v] + n) / (2 * n));
+  return "";
+}
+
+// Rules 22 + 21.  "" when fine, else the refusal.
+inline std::string build_gain(const g1s_segment_t *segs, size_t n, uint32_t range, uint16_t gain[256]) {
+  if (range > kGainRangeMax) return "chroma gain range must be 1..8 (0 = the default)";
+  if (!gain) return "a chroma gain needs the scaling function it is made from and the output table";
+  uint8_t s[256];
+  const std::string why = chroma_s_from_segments(segs, n, s);
+  return why.empty() ? gain_from_s(s, range, gain) : why;
+}
+
+// what g1s_denoise_new_gain asks of a table it is handed: any 256 entries in 1 .. 16384.  "" when fine.
+inline std::string check_gain(const uint16_t gain[256]) {
+  for (int i = 0; i < kGainEntries; ++i)
+    if (gain[i] < 1 || gain[i] > kGainMax) return "chroma gain must be 1..16384 (at " + std::to_string(i) + ")";
   return "";
 }
 

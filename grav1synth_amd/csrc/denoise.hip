@@ -215,6 +215,47 @@ __global__ __launch_bounds__(kThreads) void kd_nlm_jtm(DenoiseParamsJTM p) {
                       [] { __syncthreads(); });
 }
 
+// the joint chroma kernels under a chroma gain (rules 21 - 24): the same tiles, the weight of a pair scaled by the gain at the
+// guide under both of its ends.  Kernels of their own, so that the ones above stay what they are.
+struct GainArg {
+  const uint16_t *table;  // m[256]
+  int shift;              // B - 8
+};
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_jg(DenoiseParamsJ p, GainArg ga) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJob &job = p.jobs[blockIdx.z];
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  dn_tile_j<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job), p.s, job.out[1], job.out_stride[1], job.out[2],
+                    job.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift});
+}
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_jtg(DenoiseParamsJT p, GainArg ga) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobT &job = p.jobs[blockIdx.z];
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
+  dn_tile_jt<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, p.s, job.f.out[1], job.f.out_stride[1],
+                     job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift});
+}
+
+template <int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm_jtmg(DenoiseParamsJTM p, GainArg ga) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
+  const DenoiseJobTM &jm = p.jobs[blockIdx.z];
+  const DenoiseJobT &job = jm.t;
+  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const TileGeom g = tile_geom(p.A, S);
+  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
+  dn_tile_jtm<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, jm.mv[1] + 2 * (int)blockIdx.x,
+                      2 * p.blocks, p.s, job.f.out[1], job.f.out_stride[1], job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH,
+                      [] { __syncthreads(); }, Gain{ga.table, ga.shift});
+}
+
 // the kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
 struct Plain {
   using Params = DenoiseParams;
@@ -241,6 +282,25 @@ struct TemporalMotion {
 struct JointTemporalMotion {
   using Params = DenoiseParamsJTM;
   template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+};
+
+// the same three under a chroma gain: the joint family's parameters and the gain beside them
+template <class P>
+struct WithGain {
+  P p;
+  GainArg ga;
+};
+struct JointGain {
+  using Params = WithGain<DenoiseParamsJ>;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
+};
+struct JointTemporalGain {
+  using Params = WithGain<DenoiseParamsJT>;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
+};
+struct JointTemporalMotionGain {
+  using Params = WithGain<DenoiseParamsJTM>;
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtmg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
 };
 
 // the family's kernel for patch radius S and `bps` bytes a sample; false: there is none
@@ -291,6 +351,8 @@ struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
   uint32_t M = 0;  // the motion range on the search plane (rules 16 - 20); 0: no motion, the launches of rules 1 - 15
   bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j / kd_nlm_jt for their chroma
+  bool gain = false;          // a chroma gain (rules 21 - 24): the joint launch is kd_nlm_jg / kd_nlm_jtg / kd_nlm_jtmg
+  DevBuf<uint16_t> d_gain;    // m[256]
   uint32_t q[4] = {0, 0, 0, 0};  // luma, chroma, joint chroma, luma in the stabilised domain
   Event ev[3];
   // a frame handed over: its planes on the device (the caller's, or a slot of the input staging ring) and where its
@@ -394,9 +456,23 @@ int g1s_denoise::launch_joint(int set, uint32_t nframes) {
     p.s = JointShape{geom.W, geom.H, geom.subx, geom.suby, cw, ch}, p.tiles_x = tiles_x;
   };
   const dim3 grid((unsigned)(tiles_x * ((ch + kTH - 1) / kTH)), 1u, nframes);
-  const JointGeom jg = joint_geom(tile_geom((int)A, (int)S));
+  const TileGeom tg = tile_geom((int)A, (int)S);
+  const JointGeom jg = gain ? joint_gain_geom(tg) : joint_geom(tg);  // (the gain's layout: the same fields, Mt between T and N)
+  const GainArg ga{d_gain, (int)bit_depth - 8};
   bool found;
-  if (D && M) {
+  if (gain && D && M) {
+    WithGain<DenoiseParamsJTM> t{{}, ga};
+    fill(t.p), t.p.nnb = (int)(2 * D), t.p.blocks = (int)grid.x;
+    found = launch_family<JointTemporalMotionGain>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
+  } else if (gain && D) {
+    WithGain<DenoiseParamsJT> t{{}, ga};
+    fill(t.p), t.p.nnb = (int)(2 * D);
+    found = launch_family<JointTemporalGain>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
+  } else if (gain) {
+    WithGain<DenoiseParamsJ> p{{}, ga};
+    fill(p.p);
+    found = launch_family<JointGain>(S, bps, grid, (size_t)jg.bytes, stream, p);
+  } else if (D && M) {
     DenoiseParamsJTM t{};
     fill(t), t.nnb = (int)(2 * D), t.blocks = (int)grid.x;
     found = launch_family<JointTemporalMotion>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
@@ -579,6 +655,8 @@ struct Prior {
   std::vector<g1s_segment_t> segs;
   uint32_t range = 0;
   std::vector<uint16_t> pair_fwd, pair_inv;  // a curve that is there already (a measured prior): make() hands it on
+  bool chroma = false;         // the prior extends to chroma (rules 21 - 24): load() and measure() also make the gain
+  std::vector<uint16_t> gain;  // m[256] then; else empty
   std::string load(const char *path, uint32_t range_, int32_t segment) {
     range = range_;
     std::string text;
@@ -600,6 +678,10 @@ struct Prior {
     if (segment >= 0 && (size_t)segment >= nseg)
       return "grain prior: segment " + std::to_string(segment) + " is not in the table (" + std::to_string(nseg) + " segments)";
     if (segment >= 0) segs = {segs[(size_t)segment]};
+    if (chroma) {  // rule 22 on the segments in hand, rule 21
+      gain.assign(g1s_cv::kGainEntries, 0);
+      return g1s_cv::build_gain(segs.data(), segs.size(), range, gain.data());
+    }
     return "";
   }
   std::string make(uint32_t bit_depth, std::vector<uint16_t> &fwd, std::vector<uint16_t> &inv) const {
@@ -616,7 +698,11 @@ struct Prior {
     std::vector<uint8_t> sg((size_t)1 << bit_depth);
     if (!(why = g1s_nl::sigma(total, bit_depth, min_count, sg.data())).empty()) return why;
     pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
-    return g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data());
+    if (!(why = g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data())).empty() || !chroma) return why;
+    uint8_t sc[g1s_cv::kGainEntries];  // rule 23 on the same record, rule 21
+    if (!(why = g1s_nl::chroma_sigma(total, min_count, sc)).empty()) return why;
+    gain.assign(g1s_cv::kGainEntries, 0);
+    return g1s_cv::gain_from_s(sc, range_, gain.data());
   }
   // the denoiser for a clip of this depth; NULL with the global error text set
   g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags, uint32_t motion_range = 0) const {
@@ -626,13 +712,13 @@ struct Prior {
       g1s_set_global_error_(why.c_str());
       return nullptr;
     }
-    return g1s_denoise_new_motion(bit_depth, opts, D, flags, fwd.data(), inv.data(), motion_range);
+    return g1s_denoise_new_gain(bit_depth, opts, D, flags, fwd.data(), inv.data(), motion_range, gain.empty() ? nullptr : gain.data());
   }
 };
 
 // what every g1s_denoise_new* call makes; `curve`: with the pair (fwd, inv) of rules 12 - 15
 static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, bool curve,
-                                 const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range = 0) {
+                                 const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range = 0, const uint16_t *chroma_gain = nullptr) {
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -661,6 +747,13 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
     g1s_set_global_error_("motion_range needs a temporal radius");
     return nullptr;
   }
+  if (chroma_gain) {
+    const std::string no = g1s_cv::check_gain(chroma_gain);
+    if (!no.empty() || !(flags & G1S_DENOISE_JOINT_CHROMA)) {
+      g1s_set_global_error_(no.empty() ? "a chroma gain needs joint chroma" : no.c_str());
+      return nullptr;
+    }
+  }
   std::vector<uint16_t> tables(4 * kTable);
   uint32_t q[4] = {0, 0, 0, 0};
   std::string why = make_table(bit_depth, S, h, tables.data(), &q[0]);
@@ -687,7 +780,7 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   // the LDS a workgroup of the largest kernel these parameters select asks for, against what the device gives one
   {
     const TileGeom tg = tile_geom((int)A, (int)S);
-    const JointGeom jg = joint_geom(tg);
+    const JointGeom jg = chroma_gain ? joint_gain_geom(tg) : joint_geom(tg);
     const bool joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
     const int need = temporal_radius ? (joint ? jg.bytes_t : tg.bytes_t) : (joint ? jg.bytes : tg.bytes);
     int limit = 0;
@@ -699,7 +792,7 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   }
   g1s_denoise *g = new g1s_denoise;
   g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
-  g->curve = curve, g->M = motion_range / 2;
+  g->curve = curve, g->M = motion_range / 2, g->gain = chroma_gain != nullptr;
   for (int i = 0; i < 4; ++i) g->q[i] = q[i];
   bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
   for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
@@ -711,6 +804,8 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
          hipMemcpy(g->d_curve, fwd, nf * 2, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(g->d_curve + nf, inv, g1s_cv::kInvEntries * 2, hipMemcpyHostToDevice) == hipSuccess;
   }
+  if (ok && chroma_gain)
+    ok = hipMalloc((void **)&g->d_gain.p, kGain * 2) == hipSuccess && hipMemcpy(g->d_gain, chroma_gain, kGain * 2, hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
     free_op(g);
@@ -754,6 +849,11 @@ g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_
 g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
                                       const uint16_t *inv, uint32_t motion_range) {
   return new_denoiser(bit_depth, opts, temporal_radius, flags, fwd || inv, fwd, inv, motion_range);
+}
+
+g1s_denoise_t *g1s_denoise_new_gain(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
+                                    const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain) {
+  return new_denoiser(bit_depth, opts, temporal_radius, flags, fwd || inv, fwd, inv, motion_range, chroma_gain);
 }
 
 // stage 1 alone: both frames on the device (a host frame in an allocation of this call), luma through the forward curve
@@ -1032,6 +1132,37 @@ int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_den
   return denoise_y4m_file(in, out, &d, temporal_radius, flags, prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, err, cap);
 }
 
+// the refusals of a chroma prior that need neither the table nor the clip.  "" when fine.
+static std::string chroma_prior_refusal(uint32_t chroma_prior, uint32_t flags, const char *prior_tbl, uint32_t auto_flags) {
+  if (chroma_prior > 1) return "chroma_prior is 0 or 1";
+  if (!prior_tbl && !(auto_flags & G1S_AUTO_PRIOR)) return "a chroma prior needs a grain prior (a table or the clip's own levels)";
+  if (!(flags & G1S_DENOISE_JOINT_CHROMA)) return "a chroma gain needs joint chroma";
+  return "";
+}
+
+int64_t g1s_denoise_y4m_file_chroma(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                    uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, char *err, size_t cap) {
+  if (!chroma_prior)
+    return g1s_denoise_y4m_file_auto(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames,
+                                     min_count, err, cap);
+  std::string why = chroma_prior_refusal(chroma_prior, flags, prior_tbl, auto_flags);
+  if (why.empty() && opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) why = "g1s_denoise_opts_t.struct_size mismatch";
+  Prior prior;
+  prior.chroma = true;
+  g1s_denoise_opts_t d{};
+  if (opts) d = *opts;
+  d.struct_size = sizeof d;
+  if (!opts) d.device = -1;
+  if (why.empty() && auto_flags) why = auto_prepass(in, d.device, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
+  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
+  if (!why.empty()) {
+    if (err && cap) snprintf(err, cap, "%s", why.c_str());
+    return G1S_ERR_INVALID;
+  }
+  return denoise_y4m_file(in, out, &d, temporal_radius, flags, &prior, motion_range, err, cap);
+}
+
 // `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
 // output beside it and the generator takes the pair as device frames.  A pair's two buffers belong to the generator
 // until g1s_diff_frames_released() covers the frame, and its source buffer is a neighbour of the D frames after it until the
@@ -1108,6 +1239,33 @@ int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, con
   if (!why.empty()) return refuse(G1S_ERR_INVALID, why);
   return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, &d, temporal_radius, flags,
                                 prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                      uint64_t min_count, uint32_t chroma_prior, uint64_t *frames_out, char *err, size_t cap) {
+  if (!chroma_prior)
+    return g1s_diff_y4m_file_denoised_auto(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment,
+                                           motion_range, auto_flags, profile_frames, min_count, frames_out, err, cap);
+  auto refuse = [&](int code, const std::string &m) {
+    if (err && cap) snprintf(err, cap, "%s", m.c_str());
+    return code;
+  };
+  if (frames_out) *frames_out = 0;
+  if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
+  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
+  std::string why = chroma_prior_refusal(chroma_prior, flags, prior_tbl, auto_flags);
+  if (why.empty() && dopts && dopts->struct_size != sizeof(g1s_denoise_opts_t)) why = "g1s_denoise_opts_t.struct_size mismatch";
+  Prior prior;
+  prior.chroma = true;
+  g1s_denoise_opts_t d{};
+  if (dopts) d = *dopts;
+  d.struct_size = sizeof d;
+  if (why.empty() && auto_flags) why = auto_prepass(source, opts ? opts->device : -1, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
+  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
+  if (!why.empty()) return refuse(G1S_ERR_INVALID, why);
+  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, &d, temporal_radius, flags, &prior, motion_range, frames_out, err, cap);
 }
 
 // what g1s_diff_y4m_file_denoised_motion and g1s_diff_y4m_file_denoised_auto do once they have their prior (or none)

@@ -28,6 +28,14 @@
 // planes (JointGeom).  Every phase is written once, over NA sample arrays and NP output planes LP samples apart (one plane: NA =
 // NP = 1, LP = 0), as the source says (PlaneSrc, JointSrc); dn_spatial and dn_temporal run them; the tile functions own the registers.
 //
+// A chroma gain (rules 21 - 24, kd_nlm_jg, kd_nlm_jtg and kd_nlm_jtmg) adds, to the joint filter alone,
+//
+//   Mt  the 256-entry gain table m, u16, behind T; staged in T's loop, under the same first barrier.
+//
+// The weight phase then reads the guide at both ends of the pair -- G is in LDS already -- and looks both up: D_J is
+// multiplied by the pair's mean gain before the shift (dn_weights8).  The phases, their order and their barriers are the
+// ones above; without a gain (NoGain, the default of every template here) nothing of it is compiled.
+//
 // Every phase is a loop over tasks dealt to the threads by `tid`; nothing here names threadIdx, so a host program can
 // run a phase for tid = 0 .. kThreads - 1 in turn and get the workgroup's result.  The tile functions (dn_tile, dn_tile_t,
 // dn_tile_j, dn_tile_jt), too, are run on the host as they stand, with a real barrier for `sync` and hostile thread orders
@@ -103,8 +111,52 @@ G1S_DN_HD JointGeom joint_geom(const TileGeom &g) {
   return j;
 }
 
+// The same under a chroma gain (rules 21 - 24): the gain table Mt behind T, and N behind that
+constexpr int kGain = 256;  // entries of a chroma gain (rule 21)
+struct JointGainGeom : JointGeom {
+  int offM;
+};
+
+G1S_DN_HD JointGainGeom joint_gain_geom(const TileGeom &g) {
+  JointGainGeom j;
+  static_cast<JointGeom &>(j) = joint_geom(g);
+  j.offM = j.offT + kTable * 2;
+  j.bytes = j.offM + kGain * 2;
+  j.offN = (j.bytes + 15) & ~15;
+  j.bytes_t = j.offN + 3 * j.LP * 2;
+  return j;
+}
+
 G1S_DN_HD int dn_lp(const TileGeom &) { return 0; }  // samples from one array to the next under either layout
 G1S_DN_HD int dn_lp(const JointGeom &j) { return j.LP; }
+
+// A chroma gain (rules 21 - 24) as the phases see it.  Gain is what a tile function is handed: m[256] in global memory and
+// B - 8.  GainLds is the same once staged: Mt in LDS, the guide arrays of the frame (G) and of the neighbour in hand (GN).
+// GainPair is one task of dn_weights8: the guide down a column at both ends of the pair, rows LS apart.  NoGain is
+// empty: a phase instantiated with it is the phase without a gain.  Under a gain the layout is JointGainGeom.
+struct NoGain {
+  static constexpr bool on = false;
+};
+struct Gain {
+  static constexpr bool on = true;
+  const uint16_t *table;
+  int shift;
+};
+struct GainLds {
+  static constexpr bool on = true;
+  const uint16_t *Mt, *G, *GN;
+  int shift;
+};
+struct GainPair {
+  static constexpr bool on = true;
+  const uint16_t *Mt, *ga, *gb;
+  int shift;
+};
+// rule 24's v(p) -> m: a sample above the bit depth's maximum (the caller's error) stays a wrong value, never a wrong address
+G1S_DN_HD uint32_t dn_gain_at(const uint16_t *Mt, uint32_t G, int shift) {
+  const uint32_t v = G >> shift;
+  return Mt[v < (uint32_t)(kGain - 1) ? v : (uint32_t)(kGain - 1)];
+}
 
 G1S_DN_HD int imin(int a, int b) { return a < b ? a : b; }
 G1S_DN_HD int imax(int a, int b) { return a > b ? a : b; }
@@ -246,9 +298,10 @@ G1S_DN_HD void dn_hsum_t(int tid, const TileGeom &g, int LP, const uint16_t *L, 
 }
 
 // o[j WS] = T[min(D >> q, 1023)] with D = the sum of Hb over the 2S + 1 rows from h + j HS, for 8 consecutive rows of a
-// column; 0 where the pair takes no part, which is what ok(j) says
-template <int S, class Ok>
-G1S_DN_HD void dn_weights8(const TileGeom &g, const uint32_t *h, uint16_t *o, const uint16_t *T, int q, Ok ok) {
+// column; 0 where the pair takes no part, which is what ok(j) says.  Under a gain (rule 24) D is multiplied by the pair's
+// mp <= 2^14 first: a 64-bit product below 2^46 (one v_mul_hi_u32 / v_mul_lo_u32 pair), shifted by q + 8.
+template <int S, class Ok, class Gp = NoGain>
+G1S_DN_HD void dn_weights8(const TileGeom &g, const uint32_t *h, uint16_t *o, const uint16_t *T, int q, Ok ok, Gp gp = Gp()) {
   uint32_t v[8 + 2 * S];
 #pragma unroll
   for (int j = 0; j < 8 + 2 * S; ++j) v[j] = h[j * g.HS];
@@ -258,7 +311,14 @@ G1S_DN_HD void dn_weights8(const TileGeom &g, const uint32_t *h, uint16_t *o, co
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     if (j) s += v[j + 2 * S] - v[j - 1];
-    const uint32_t k = s >> q;
+    uint32_t k;
+    if constexpr (Gp::on) {
+      const uint32_t mp = (dn_gain_at(gp.Mt, gp.ga[j * g.LS], gp.shift) + dn_gain_at(gp.Mt, gp.gb[j * g.LS], gp.shift) + 1u) >> 1;
+      const uint64_t kk = ((uint64_t)s * mp) >> (q + 8);
+      k = kk < (uint64_t)(kTable - 1) ? (uint32_t)kk : (uint32_t)(kTable - 1);
+    } else {
+      k = s >> q;
+    }
     const uint16_t w = T[k < (uint32_t)(kTable - 1) ? k : (uint32_t)(kTable - 1)];
     o[j * g.WS] = ok(j) ? w : (uint16_t)0;
   }
@@ -267,34 +327,47 @@ G1S_DN_HD void dn_weights8(const TileGeom &g, const uint32_t *h, uint16_t *o, co
 // Wb(y, x) = the weight of the pair {p, p + d} for the region's RW x RH samples p = (x0 - max(dx, 0) + x, y0 - dy + y); 0
 // where p or p + d lies outside the W x H grid (rule 2).  A task is 8 consecutive rows of a column (the last task of a
 // column starts at RH - 8 and overlaps its neighbour); lanes run along the columns.
-template <int S>
+template <int S, class Gl = NoGain>
 G1S_DN_HD void dn_weights(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int RW,
-                          int RH, uint32_t mRW, int x0, int y0, int W, int H) {
+                          int RH, uint32_t mRW, int x0, int y0, int W, int H, Gl gl = Gl()) {
   const int ntasks = ((RH + 7) >> 3) * RW;
   for (int i = tid; i < ntasks; i += kThreads) {
     const int seg = (int)(((uint32_t)i * mRW) >> 16), x = i - seg * RW;
     const int ys = imin(seg * 8, RH - 8);
     const int px = x0 - imax(dx, 0) + x, py = y0 - dy + ys;
     const bool col_ok = px >= 0 && px < W && px + dx >= 0 && px + dx < W;
-    dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
-                   [=](int j) { return col_ok && py + j >= 0 && py + j + dy < H; });  // (dy >= 0: the other two row bounds follow)
+    if constexpr (Gl::on) {
+      // the guide at p and at p + d: both inside L, whose halo of R covers the region and the region moved by d
+      const uint16_t *ga = gl.G + (ys - dy + g.R) * g.LS + (x - imax(dx, 0) + g.R);
+      dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q, [=](int j) { return col_ok && py + j >= 0 && py + j + dy < H; },
+                     GainPair{gl.Mt, ga, ga + dy * g.LS + dx, gl.shift});
+    } else {
+      dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
+                     [=](int j) { return col_ok && py + j >= 0 && py + j + dy < H; });  // (dy >= 0: the other two row bounds follow)
+    }
   }
 }
 
 // Wb(y, x) = the weight of the pair {(t, p), (t + k, p + d)} for the tile's samples p = (x0 + x, y0 + y); 0 where p or p + d
 // lies outside the W x H grid (rule 6).  Tasks as in dn_weights, and no task overlaps another: 8 divides kTH.  Under motion
-// (rule 19) the neighbour was staged from the tile moved by (mx, my), and it is p + m + d that has to lie inside.
-template <int S>
+// (rule 19) the neighbour was staged from the tile moved by (mx, my), and it is p + m + d that has to lie inside.  Under a gain
+// the neighbour's guide is read at p + d of N, which is G of frame t + k at p + m + d (rule 24).
+template <int S, class Gl = NoGain>
 G1S_DN_HD void dn_weights_t(int tid, const TileGeom &g, const uint32_t *Hb, uint16_t *Wb, const uint16_t *T, int q, int dx, int dy, int x0,
-                            int y0, int W, int H, int mx = 0, int my = 0) {
+                            int y0, int W, int H, int mx = 0, int my = 0, Gl gl = Gl()) {
   constexpr int ntasks = (kTH >> 3) * kTW;
   const int ox = mx + dx, oy = my + dy;
   for (int i = tid; i < ntasks; i += kThreads) {
     const int x = i % kTW, ys = i / kTW * 8;
     const int px = x0 + x, py = y0 + ys;
     const bool col_ok = px < W && px + ox >= 0 && px + ox < W;
-    dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
-                   [=](int j) { return col_ok && py + j < H && py + j + oy >= 0 && py + j + oy < H; });
+    if constexpr (Gl::on) {
+      dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q, [=](int j) { return col_ok && py + j < H && py + j + oy >= 0 && py + j + oy < H; },
+                     GainPair{gl.Mt, gl.G + (ys + g.R) * g.LS + (x + g.R), gl.GN + (ys + dy + g.R) * g.LS + (x + dx + g.R), gl.shift});
+    } else {
+      dn_weights8<S>(g, Hb + ys * g.HS + x, Wb + ys * g.WS + x, T, q,
+                     [=](int j) { return col_ok && py + j < H && py + j + oy >= 0 && py + j + oy < H; });
+    }
   }
 }
 
@@ -373,16 +446,25 @@ G1S_DN_HD void dn_store(int tid, uint8_t *out, uint32_t stride, int W, int H, in
 
 // ---- the two drivers: a source `src`, LDS laid out by `o` (tile_geom for PlaneSrc, joint_geom for JointSrc) ------------
 // the frame's own offsets (rules 1 - 3, 8 - 10) of one tile for thread `tid` of a workgroup whose barrier is `sync`: the
-// sample arrays and T staged, the sums of rule 4 / 11 in aw and au
-template <int S, int BPS, class Src, class Layout, class Sync>
+// sample arrays and T staged, the sums of rule 4 / 11 in aw and au.  gain: rule 24's table, staged beside T (JointSrc only).
+template <int S, int BPS, class Src, class Layout, class Sync, class Gn = NoGain>
 G1S_DN_HD void dn_spatial(int tid, const TileGeom &g, const Layout &o, uint8_t *lds, const uint16_t *table, int q, const Src &src, int x0, int y0,
-                          Sync sync, uint32_t *aw, uint32_t *const (&au)[Src::NP]) {
+                          Sync sync, uint32_t *aw, uint32_t *const (&au)[Src::NP], Gn gain = Gn()) {
   const int LP = dn_lp(o);
   uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + o.offH);
   uint16_t *L = reinterpret_cast<uint16_t *>(lds + o.offL), *Wb = reinterpret_cast<uint16_t *>(lds + o.offW),
            *T = reinterpret_cast<uint16_t *>(lds + o.offT);
   src.template stage<BPS>(tid, g, LP, L, x0, y0);
-  for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
+  if constexpr (Gn::on) {
+    static_assert(Src::NA == 3, "a gain reads the guide");
+    uint16_t *Mt = reinterpret_cast<uint16_t *>(lds + o.offM);
+    for (int i = tid; i < kTable / 2; i += kThreads) {  // (T's loop: the first kGain / 2 turns take a word of the gain along)
+      reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
+      if (i < kGain / 2) reinterpret_cast<uint32_t *>(Mt)[i] = reinterpret_cast<const uint32_t *>(gain.table)[i];
+    }
+  } else {
+    for (int i = tid; i < kTable / 2; i += kThreads) reinterpret_cast<uint32_t *>(T)[i] = reinterpret_cast<const uint32_t *>(table)[i];
+  }
   sync();
   dn_init<Src::NP>(tid, g, LP, L, aw, au);
   for (int dy = 0; dy <= g.A; ++dy) {
@@ -392,7 +474,11 @@ G1S_DN_HD void dn_spatial(int tid, const TileGeom &g, const Layout &o, uint8_t *
       const int RW = kTW + (dx < 0 ? -dx : dx);
       dn_hsum<S, Src::NA>(tid, g, LP, L, Hb, dx, dy, RW, NR, mNR);
       sync();
-      dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, src.grid_w(), src.grid_h());
+      if constexpr (Gn::on)
+        dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, src.grid_w(), src.grid_h(),
+                      GainLds{reinterpret_cast<const uint16_t *>(lds + o.offM), L + 2 * LP, L + 2 * LP, gain.shift});
+      else
+        dn_weights<S>(tid, g, Hb, Wb, T, q, dx, dy, RW, RH, magic(RW), x0, y0, src.grid_w(), src.grid_h());
       sync();
       dn_accumulate<Src::NP>(tid, g, LP, L, Wb, dx, dy, aw, au);
     }
@@ -410,9 +496,9 @@ struct NoMotion {
   G1S_DN_HD MotionVec operator()(int) const { return MotionVec{0, 0}; }
 };
 
-template <int S, int BPS, int NP, class Layout, class Nb, class Sync, class Mv = NoMotion>
+template <int S, int BPS, int NP, class Layout, class Nb, class Sync, class Mv = NoMotion, class Gn = NoGain>
 G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t *lds, int q, Nb nb, int nnb, int x0, int y0, Sync sync, uint32_t *aw,
-                           uint64_t *const (&au)[NP], Mv mv = Mv()) {
+                           uint64_t *const (&au)[NP], Mv mv = Mv(), Gn gain = Gn()) {
   const int LP = dn_lp(o);
   uint32_t *Hb = reinterpret_cast<uint32_t *>(lds + o.offH);
   uint16_t *L = reinterpret_cast<uint16_t *>(lds + o.offL), *Wb = reinterpret_cast<uint16_t *>(lds + o.offW),
@@ -429,7 +515,11 @@ G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t 
       for (int dx = -g.A; dx <= g.A; ++dx) {
         dn_hsum_t<S, decltype(n)::NA>(tid, g, LP, L, N, Hb, dx, dy);
         sync();
-        dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h(), m.x, m.y);
+        if constexpr (Gn::on)  // (Mt: staged by dn_spatial)
+          dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h(), m.x, m.y,
+                          GainLds{reinterpret_cast<const uint16_t *>(lds + o.offM), L + 2 * LP, N + 2 * LP, gain.shift});
+        else
+          dn_weights_t<S>(tid, g, Hb, Wb, T, q, dx, dy, x0, y0, n.grid_w(), n.grid_h(), m.x, m.y);
         sync();
         dn_accumulate_t<NP>(tid, g, LP, N, Wb, dx, dy, aw, au);
       }
@@ -461,28 +551,28 @@ G1S_DN_HD void dn_tile_t(int tid, const TileGeom &g, uint8_t *lds, const uint16_
 }
 
 // one chroma tile of the joint filter
-template <int S, int BPS, class Sync>
-G1S_DN_HD void dn_tile_j(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+template <int S, int BPS, class Sync, class Gn = NoGain, class JG = JointGeom>
+G1S_DN_HD void dn_tile_j(int tid, const TileGeom &g, const JG &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
                          const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0,
-                         Sync sync) {
+                         Sync sync, Gn gain = Gn()) {
   uint32_t aw[kSPT], aub[kSPT], aur[kSPT];
-  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub, aur});
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub, aur}, gain);
   dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
   dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }
 
 // one chroma tile of the temporal joint filter (rule 11t): nb(k) gives the planes of the k-th of the 2 D frames around the
 // frame in hand, .luma a null pointer where the clip has no such frame -- the same for every thread of the workgroup
-template <int S, int BPS, class Nb, class Sync>
-G1S_DN_HD void dn_tile_jt(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+template <int S, int BPS, class Nb, class Sync, class Gn = NoGain, class JG = JointGeom>
+G1S_DN_HD void dn_tile_jt(int tid, const TileGeom &g, const JG &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
                           Nb nb, int nnb, const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride, uint8_t *out_cr,
-                          uint32_t out_cr_stride, int x0, int y0, Sync sync) {
+                          uint32_t out_cr_stride, int x0, int y0, Sync sync, Gn gain = Gn()) {
   uint32_t aw[kSPT], aub32[kSPT], aur32[kSPT];
-  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32});
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32}, gain);
   uint64_t aub[kSPT], aur[kSPT];
 #pragma unroll
   for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
-  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur});
+  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur}, NoMotion(), gain);
   dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
   dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }
@@ -642,16 +732,16 @@ G1S_DN_HD void dn_tile_tm(int tid, const TileGeom &g, uint8_t *lds, const uint16
   dn_store<BPS>(tid, out, out_stride, W, H, x0, y0, aw, au);
 }
 
-template <int S, int BPS, class Nb, class Sync>
-G1S_DN_HD void dn_tile_jtm(int tid, const TileGeom &g, const JointGeom &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
+template <int S, int BPS, class Nb, class Sync, class Gn = NoGain, class JG = JointGeom>
+G1S_DN_HD void dn_tile_jtm(int tid, const TileGeom &g, const JG &jg, uint8_t *lds, const uint16_t *table, int q, const JointPlanes &p,
                            Nb nb, int nnb, const int8_t *mv, int mv_stride, const JointShape &s, uint8_t *out_cb, uint32_t out_cb_stride,
-                           uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0, Sync sync) {
+                           uint8_t *out_cr, uint32_t out_cr_stride, int x0, int y0, Sync sync, Gn gain = Gn()) {
   uint32_t aw[kSPT], aub32[kSPT], aur32[kSPT];
-  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32});
+  dn_spatial<S, BPS>(tid, g, jg, lds, table, q, JointSrc{p, s}, x0, y0, sync, aw, {aub32, aur32}, gain);
   uint64_t aub[kSPT], aur[kSPT];
 #pragma unroll
   for (int j = 0; j < kSPT; ++j) aub[j] = aub32[j], aur[j] = aur32[j];
-  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur}, TileVectors{mv, mv_stride});
+  dn_temporal<S, BPS>(tid, g, jg, lds, q, [&](int k) { return JointSrc{nb(k), s}; }, nnb, x0, y0, sync, aw, {aub, aur}, TileVectors{mv, mv_stride}, gain);
   dn_store<BPS>(tid, out_cb, out_cb_stride, s.cw, s.ch, x0, y0, aw, aub);
   dn_store<BPS>(tid, out_cr, out_cr_stride, s.cw, s.ch, x0, y0, aw, aur);
 }

@@ -499,6 +499,21 @@ int g1s_denoise_curve_sigma(const uint8_t *s, uint32_t bit_depth, uint32_t range
   return G1S_OK;
 }
 
+// a chroma gain, rules 21 - 23 of `denoise` (curve.h, nlf.h): needs no device either
+static int gain_result(const std::string &why) {
+  if (why.empty()) return G1S_OK;
+  g1s_set_global_error_(why.c_str());
+  return G1S_ERR_INVALID;
+}
+
+int g1s_denoise_chroma_gain(const g1s_segment_t *segs, size_t n, uint32_t range, uint16_t gain[256]) { return gain_result(g1s_cv::build_gain(segs, n, range, gain)); }
+
+int g1s_nlf_chroma_sigma(const g1s_nlf_record_t *total, uint64_t min_count, uint8_t s[256]) {
+  return gain_result(!total || !s ? std::string("g1s_nlf_chroma_sigma needs a record and the output table") : g1s_nl::chroma_sigma(*total, min_count, s));
+}
+
+int g1s_denoise_chroma_gain_sigma(const uint8_t s[256], uint32_t range, uint16_t gain[256]) { return gain_result(g1s_cv::gain_from_s(s, range, gain)); }
+
 // noise levels, rules N4 - N8 (nlf.h): what is done with a record needs no device
 int g1s_nlf_sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) {
   if (!total || (n && !recs)) return G1S_ERR_INVALID;

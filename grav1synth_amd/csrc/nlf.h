@@ -43,23 +43,23 @@ inline uint64_t isqrt(unsigned __int128 v) {
   return r;
 }
 
+// N5: t of a bin with sums q and n > 0
+inline uint64_t level_of(unsigned __int128 q, unsigned __int128 n) { return isqrt((q << 16) / ((unsigned __int128)36 * n)); }
 // N5: t[k] of plane c's bin k (a bin with n > 0)
-inline uint64_t level(const g1s_nlf_record_t &r, int c, int k) {
-  return isqrt((((unsigned __int128)r.q[c][k]) << 16) / ((unsigned __int128)36 * r.n[c][k]));
-}
+inline uint64_t level(const g1s_nlf_record_t &r, int c, int k) { return level_of(r.q[c][k], r.n[c][k]); }
 
-// N5 - N6: s[1 << B] from the luma bins.  "" when fine, else the refusal (the bit depths: rule 12's texts, by the caller).
-inline std::string sigma(const g1s_nlf_record_t &r, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
+// N5 - N6 on the bins (n[k], q[k]): s[1 << B].  false when no bin is valid.
+inline bool sigma_of_bins(const unsigned __int128 *n, const unsigned __int128 *q, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
   const uint64_t nmin = min_count_of(min_count);
   int valid[kBins], nvalid = 0;
   uint64_t t[kBins], tmax = 0;
   for (int k = 0; k < kBins; ++k)
-    if (r.n[0][k] >= nmin) {
-      t[k] = level(r, 0, k);
+    if (n[k] >= nmin) {
+      t[k] = level_of(q[k], n[k]);
       tmax = t[k] > tmax ? t[k] : tmax;
       valid[nvalid++] = k;
     }
-  if (!nvalid) return "no luma bin has enough smooth samples for a prior";
+  if (!nvalid) return false;
   int64_t y[kBins], c[kBins];
   for (int i = 0; i < nvalid; ++i) {
     const int k = valid[i];
@@ -81,7 +81,22 @@ inline std::string sigma(const g1s_nlf_record_t &r, uint32_t bit_depth, uint64_t
     }
     s[v] = (uint8_t)sv;
   }
-  return "";
+  return true;
+}
+
+// N5 - N6: s[1 << B] from the luma bins.  "" when fine, else the refusal (the bit depths: rule 12's texts, by the caller).
+inline std::string sigma(const g1s_nlf_record_t &r, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
+  unsigned __int128 n[kBins], q[kBins];
+  for (int k = 0; k < kBins; ++k) n[k] = r.n[0][k], q[k] = r.q[0][k];
+  return sigma_of_bins(n, q, bit_depth, min_count, s) ? "" : "no luma bin has enough smooth samples for a prior";
+}
+
+// N9: s[256] from the bins of the two chroma planes pooled -- N5 and N6 at B = 8 whatever the clip's depth (the bins are bins of
+// averageLuma's top five bits).  "" when fine, else the refusal.
+inline std::string chroma_sigma(const g1s_nlf_record_t &r, uint64_t min_count, uint8_t s[256]) {
+  unsigned __int128 n[kBins], q[kBins];
+  for (int k = 0; k < kBins; ++k) n[k] = (unsigned __int128)r.n[1][k] + r.n[2][k], q[k] = (unsigned __int128)r.q[1][k] + r.q[2][k];
+  return sigma_of_bins(n, q, 8, min_count, s) ? "" : "no chroma bin has enough smooth samples for a prior";
 }
 
 // N7 for a plane class (0: luma; 1: the chroma planes pooled).  "" when fine, else the refusal.

@@ -11,6 +11,8 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 >>> Denoiser(10, curve=grain_curve(segments, 10)).apply([y, u, v])   # luma strength follows a grain table's scaling function
 >>> denoise_y4m_file("grainy.y4m", "clean.y4m", grain_prior="first_pass.tbl")
 >>> Denoiser(10, temporal_radius=1, motion_range=32).denoise_clip(frames)   # a pan: each tile reads its neighbours where it finds them
+>>> Denoiser(10, joint_chroma=True, chroma_gain=chroma_gain(segments)).apply([y, u, v])   # chroma strength follows the grain at the luma under it
+>>> denoise_y4m_file("grainy.y4m", "clean.y4m", grain_prior="first_pass.tbl", joint_chroma=True, chroma_prior=True)
 """
 from __future__ import annotations
 
@@ -77,12 +79,32 @@ def grain_curve(segments: Sequence, bit_depth: int, range: int = 0, segment: Opt
     return fwd, inv
 
 
+def chroma_gain(segments: Sequence, range: int = 0, segment: Optional[int] = None) -> np.ndarray:
+    """m[256]: the chroma gain of a grain table's chroma scaling functions at the luma under them (rules 22 and 21 of
+    include/g1s_diff.h; host only, no device needed), as Denoiser(chroma_gain=...) takes it.  segments: GrainTableSegment
+    objects; the gain is made from the unweighted mean of both chroma planes of all of them, or of segments[segment] alone.
+    range R: the strongest strength over the weakest, 1 .. 8, 0 = 4.  256 uint16 entries, a Q8 multiplier of the distance:
+    256 where the grain has its mean size."""
+    L = _lib.lib()
+    segments = list(segments)
+    if segment is not None:
+        if not 0 <= segment < len(segments):
+            raise G1SError(-1, f"grain prior: segment {segment} is not in the table ({len(segments)} segments)")
+        segments = [segments[segment]]
+    arr = (_lib.G1SSegment * max(len(segments), 1))(*[s.to_c() for s in segments])
+    gain = np.zeros(256, np.uint16)
+    rc = L.g1s_denoise_chroma_gain(arr, len(segments), range & 0xFFFFFFFF, gain.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return gain
+
+
 class Denoiser(FrameOp):
     _name = "denoise"
 
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                  strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
-                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None, motion_range: int = 0):
+                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None, motion_range: int = 0, chroma_gain: Optional[np.ndarray] = None):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
         runs over the D frames before and the D frames after it that the clip has.  joint_chroma: the two chroma planes
         share one weight, taken from Cb, Cr and the input luma at chroma resolution (rules 8 - 11 of include/g1s_diff.h);
@@ -90,14 +112,28 @@ class Denoiser(FrameOp):
         the domain where the prior's grain has one size at every intensity (rules 12 - 15); chroma as without it.
         motion_range Mr (even, 0..64, needs a temporal radius): every 64 x 48 tile gets one vector of up to Mr samples each
         way towards every neighbour frame, found by a coarse search on the device, and reads the neighbour there (rules
-        16 - 20); 0 is the filter without it."""
+        16 - 20); 0 is the filter without it.  chroma_gain: m[256] of chroma_gain() or estimate.noise_chroma_prior(), or any
+        256 values in 1 .. 16384 (needs joint_chroma): the weight of a chroma pair is taken at its distance times the mean of
+        m at the guide under its two ends, over 256 (rules 21 - 24); luma never sees it."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal_radius = temporal_radius
         self.joint_chroma = bool(joint_chroma)
         self.motion_range = motion_range
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
-        if curve is None and motion_range:
+        if chroma_gain is not None:
+            gain = np.ascontiguousarray(chroma_gain, np.uint16)
+            if gain.shape != (256,) or not np.array_equal(gain, np.asarray(chroma_gain)):
+                raise G1SError(-1, "chroma gain: 256 entries in 1..16384")
+            fwd = inv = None
+            if curve is not None:
+                fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
+                if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
+                    raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
+            self._h = self._L.g1s_denoise_new_gain(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
+                                                   None if fwd is None else fwd.ctypes.data, None if inv is None else inv.ctypes.data,
+                                                   motion_range & 0xFFFFFFFF, gain.ctypes.data)
+        elif curve is None and motion_range:
             self._h = self._L.g1s_denoise_new_motion(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), None, None,
                                                      motion_range & 0xFFFFFFFF)
         elif curve is None:
@@ -181,19 +217,26 @@ class Denoiser(FrameOp):
 def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                      strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
                      grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0,
-                     auto_prior: bool = False, auto_strength: bool = False, profile_frames: int = 0, levels_min_count: int = 0) -> int:
+                     auto_prior: bool = False, auto_strength: bool = False, profile_frames: int = 0, levels_min_count: int = 0,
+                     chroma_prior: bool = False) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
     function the luma strength follows (grain_curve() with prior_range and prior_segment).  motion_range: as Denoiser takes
     it.  auto_prior / auto_strength: the curve and the strengths from the clip's own noise levels (rules N5 - N7), measured
-    in a pre-pass over its first profile_frames frames (0 = all) with levels_min_count as Nmin (0 = 4096).  Returns the
-    number of frames."""
+    in a pre-pass over its first profile_frames frames (0 = all) with levels_min_count as Nmin (0 = 4096).  chroma_prior: the
+    job's prior also gives the joint chroma filter its gain (rules 21 - 24): from the table's chroma scaling functions, or from
+    the chroma levels the pre-pass measured; needs joint_chroma and one of grain_prior / auto_prior.  Returns the number of
+    frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
     if grain_prior is None and (prior_range or prior_segment is not None):
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
     prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
-    if auto_prior or auto_strength:
+    if chroma_prior:
+        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
+        n = L.g1s_denoise_y4m_file_chroma(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                          motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1, err, len(err))
+    elif auto_prior or auto_strength:
         auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
         n = L.g1s_denoise_y4m_file_auto(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
                                         motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, err, len(err))

@@ -221,6 +221,30 @@ def noise_prior(record: np.ndarray, bit_depth: int, range: int = 0, min_count: i
     return fwd, inv
 
 
+def noise_chroma_sigma(record: np.ndarray, min_count: int = 0) -> np.ndarray:
+    """Rule N9: the chroma scaling function s[256] over the luma under it, from the two chroma planes of a clip's record
+    pooled (g1s_nlf_chroma_sigma; host only).  The same for every bit depth."""
+    L = _lib.lib()
+    record = np.ascontiguousarray(record, NLF_RECORD)
+    s = np.zeros(256, np.uint8)
+    rc = L.g1s_nlf_chroma_sigma(record.ctypes.data, min_count, s.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return s
+
+
+def noise_chroma_prior(record: np.ndarray, range: int = 0, min_count: int = 0) -> np.ndarray:
+    """m[256]: the chroma gain of a clip's record, rule N9 then rule 21 of `denoise`, as Denoiser(chroma_gain=...) takes it
+    (host only)."""
+    L = _lib.lib()
+    s = noise_chroma_sigma(record, min_count)
+    gain = np.zeros(256, np.uint16)
+    rc = L.g1s_denoise_chroma_gain_sigma(s.ctypes.data, range & 0xFFFFFFFF, gain.ctypes.data)
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return gain
+
+
 def auto_strength(record: np.ndarray, bit_depth: int, min_count: int = 0) -> Tuple[float, Optional[float]]:
     """Rule N7: (h_luma, h_chroma) in 8-bit code values; h_chroma is None where the rule refuses (a luma-only clip); a
     refusal for luma raises (host only)."""

@@ -115,10 +115,10 @@ def diff_y4m_file_denoised(source: str, output: str, *, keep_denoised: Optional[
                            search_radius: int = 0, patch_radius: int = 0, strength: float = 0.0, chroma_strength: float = 0.0,
                            temporal_radius: int = 0, joint_chroma: bool = False, grain_prior: Optional[str] = None, prior_range: int = 0,
                            prior_segment: Optional[int] = None, motion_range: int = 0, auto_prior: bool = False, auto_strength: bool = False,
-                           profile_frames: int = 0, levels_min_count: int = 0) -> int:
+                           profile_frames: int = 0, levels_min_count: int = 0, chroma_prior: bool = False) -> int:
     """`diff SOURCE --denoise -o OUTPUT [--keep-denoised PATH]` for a .y4m input: the denoised frame is made on the device
     (grav1synth_amd.denoise; the file is one clip for its temporal radius; joint_chroma as there) and handed to the generator there.
-    grain_prior, prior_range, prior_segment, motion_range, auto_prior, auto_strength, profile_frames, levels_min_count: as
+    grain_prior, prior_range, prior_segment, motion_range, auto_prior, auto_strength, profile_frames, levels_min_count, chroma_prior: as
     grav1synth_amd.denoise.denoise_y4m_file takes them.  Returns the number of frames."""
     from .denoise import denoise_opts
 
@@ -132,7 +132,10 @@ def diff_y4m_file_denoised(source: str, output: str, *, keep_denoised: Optional[
     head = (str(source).encode(), str(output).encode(), str(keep_denoised).encode() if keep_denoised else None, C.byref(opts), C.byref(dopts),
             temporal_radius & 0xFFFFFFFF, _lib.G1S_DENOISE_JOINT_CHROMA if joint_chroma else 0,
             str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
-    if auto_prior or auto_strength:
+    if chroma_prior:
+        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
+        rc = L.g1s_diff_y4m_file_denoised_chroma(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1, C.byref(frames), err, len(err))
+    elif auto_prior or auto_strength:
         auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
         rc = L.g1s_diff_y4m_file_denoised_auto(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, C.byref(frames), err, len(err))
     elif motion_range:

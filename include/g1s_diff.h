@@ -447,6 +447,10 @@ long g1s_format_estimates(const double *estimates, size_t n, char *buf, size_t c
  *      no tuning constant.  h_chroma: the same over planes 1 and 2 pooled.  Refused when N < Nmin or the result is outside
  *      rule 3's 0 < h <= 1000.  Under a curve rule 14 makes h the strength at the curve's mean slope.
  *  N8. Report.  g1s_format_noise_levels writes plain text; the grammar is at its declaration.
+ *  N9. Chroma prior (rule 23 of `denoise`).  Planes 1 and 2 pooled per bin: n = n[1][k] + n[2][k], q = q[1][k] + q[2][k];
+ *      t[k] by N5 with the same Nmin.  No valid bin: refused ("no chroma bin has enough smooth samples for a prior").  y[k]
+ *      and the interpolation exactly as in N6 with B = 8 -- centres c_k = 8 k + 4, v = 0 .. 255 -- whatever the clip's depth:
+ *      the bins are bins of averageLuma's top five bits.  A 12-bit clip is fine here: a gain needs no headroom.
  * The gate is the estimator's and has its bias: above about sigma = 5 eight-bit code values it thins the sample and keeps
  * the quieter part.  In a numpy run of N1 - N3 on a noisy ramp it kept 64 % of the samples at sigma = 8, and the per-bin
  * sigma stayed within 2.3 % of the truth.  The gate is not corrected for.
@@ -487,6 +491,9 @@ int g1s_nlf_sigma(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t mi
 /* N7 for one plane class (0: luma; 1: the two chroma planes pooled): *h.  G1S_ERR_INVALID with the reason from
  * g1s_last_global_error() ("too few smooth samples for a strength", "the measured strength is outside 0 < h <= 1000"). */
 int g1s_nlf_strength(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h);
+/* N9: s[256] from the chroma bins of a clip's record, whatever its bit depth.  G1S_ERR_INVALID with the reason from
+ * g1s_last_global_error() when no chroma bin is valid. */
+int g1s_nlf_chroma_sigma(const g1s_nlf_record_t *total, uint64_t min_count, uint8_t s[256]);
 /* Rule 12 from "floor = ..." onwards and rule 13 on a given s[1 << bit_depth] (N6's, or any other): the pair (f, g) as
  * g1s_denoise_curve makes it from a table's s.  The same refusals for bit depth and range. */
 int g1s_denoise_curve_sigma(const uint8_t *s, uint32_t bit_depth, uint32_t range, uint16_t *fwd, uint16_t *inv);
@@ -615,7 +622,7 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *      strength h (g1s_denoise_weights(12, S, h)) into v; out = g[v].  Where the curve's slope is its mean (about
  *      2^(12 - B)) the strength is h; elsewhere it is h x mean slope / slope(x): proportional to the table's grain, within a
  *      factor R between the weakest and the strongest.
- *  15. Chroma is untouched: the two chroma planes are filtered, independently or jointly, exactly as without a curve, and
+ *  15. Chroma is untouched unless a chroma gain is given (rules 21 - 24): the two chroma planes are filtered, independently or jointly, exactly as without a curve, and
  *      rule 8's guide stays the unstabilised input luma.  A 12-bit clip has no headroom in 12-bit kernels and is refused.
  * With a curve the denoiser keeps (2 batch_frames + 2 D) 12-bit u16 luma planes on the device; the caller's input luma is
  * never written.
@@ -642,6 +649,32 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *      guide of frame t + k is staged at the moved place by rule 8 as it stands.  With a grain prior the luma search runs
  *      on the stabilised 12-bit planes, which are what the filter filters.
  * Sub-tile and sub-sample vectors, smoothing of the vector field and scene-cut detection are not part of it.
+ * A chroma gain (g1s_denoise_new_gain): chroma grain is a function of the luma under it -- every table `diff` writes has
+ * cb_mult = cr_mult = 128, so its chroma scaling function is indexed by averageLuma alone -- and a curve on the chroma sample
+ * cannot follow that.  The strength of the joint chroma filter becomes a strength per pair of samples, read from the guide.
+ * Integers throughout:
+ *  21. Gain from a scaling function s(i), i = 0 .. 255, values 0 .. 255, and a range R in 1 .. 8 (0 = 4): top = max_i s(i),
+ *      floor = max(1, ceil(top / R)), s'(i) = max(s(i), floor), sbar = (sum_i s'(i) + 128) >> 8,
+ *      m(i) = min(16384, max(1, (256 sbar^2 + (s'(i)^2 >> 1)) / s'(i)^2)): a Q8 multiplier, kept as uint16.  s' >= top / R and
+ *      sbar <= top, so m <= 256 R^2 <= 16384; sbar >= floor >= s' / R, so m >= 256 / R^2 = 4 at R = 8: the clamp only catches
+ *      rounding.  R = 1, or a function that is 0 everywhere, gives m = 256 for every i: the FLAT gain.  The strength at a
+ *      sample is h s'(i) / sbar: proportional to the grain, and h where the grain has its unweighted mean.
+ *  22. s from a table, n >= 1 segments.  For both chroma planes of every segment: the plane's ScalingLut (7.18.3.4; under
+ *      chroma_scaling_from_luma the luma points', all zeros for a plane without points) at idx(v), v = 0 .. 255:
+ *      idx(v) = v under chroma_scaling_from_luma, else Clip3(0, 255, ((v (luma_mult - 128) + 128 (mult - 128)) >> 6) +
+ *      (offset - 256)) with an arithmetic shift -- the 8-bit form of 7.18.3.5 with the chroma sample at mid-grey.
+ *      s(v) = (the sum of the 2 n functions + n) / (2 n), the rounded mean.  Exact for tables with mult = 128, which all of
+ *      `diff`'s own are (luma_mult = 192, offset = 256: idx(v) = v); otherwise it is the function's section at mid-grey.
+ *  23. s from noise levels: rule N9 of "noise levels".
+ *  24. The weight under a gain m[256]; it exists only under G1S_DENOISE_JOINT_CHROMA.  v(p) = min(G(p) >> (B - 8), 255) (the
+ *      clamp only for samples above the bit depth's maximum, which are the caller's error).  For a pair (p, p'):
+ *      mp = (m(v(p)) + m(v(p')) + 1) >> 1, where p' = p + d in the frame itself with G of frame t (rule 9), p' = p + d in a
+ *      neighbour frame with G of frame t + k (rule 11t), p' = p + m_{t,k}(b) + d under motion (rule 19).
+ *      w = T_J[min((D_J mp) >> (q_J + 8), 1023)], the product formed in 64 bits: D_J < 2^32 and mp <= 2^14, so it stays
+ *      below 2^46 < 2^47.  mp is symmetric in the pair, so D(p, d) = D(p + d, -d) still gives one weight for both ends of a
+ *      pair.  Rules 2, 5 - 7, 9, 11, 11t and 19 - 20 are otherwise unchanged; (k = 0, d = 0) carries 4096.  With the flat gain
+ *      the bytes are those of rules 8 - 11t: (D 256) >> (q + 8) = D >> q.  Luma never sees the gain, and a luma-only frame
+ *      is filtered as without it.
  * No dithering.  Samples above the bit depth's maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes -- under the flag one workgroup filters both) on the denoiser's own stream.  A workgroup's LDS grows
@@ -681,6 +714,20 @@ g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_
  * filter launches (kd_motion) and kept on the device: 2 D pairs of int8 a tile and plane. */
 g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                       const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range);
+/* The same with a chroma gain (rules 21 - 24): chroma_gain[256], copied before the call returns, works for 8, 10 and 12 bits,
+ * with or without a curve, a temporal radius or motion.  chroma_gain == NULL is g1s_denoise_new_motion: the same launches, the
+ * same bytes.  Any table with every entry in 1 .. 16384 is accepted; it need not come from the builders below.  Two more
+ * refusals, checked before a device is looked for: "chroma gain must be 1..16384 (at I)" and, without
+ * G1S_DENOISE_JOINT_CHROMA, "a chroma gain needs joint chroma" (chroma filtered plane by plane has no guide in hand).
+ * g1s_denoise_motion_search is unaffected: the guide takes no part in the search. */
+g1s_denoise_t *g1s_denoise_new_gain(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain);
+/* Rules 22 + 21: the gain from both chroma planes of n >= 1 segments of a grain table, range R (0 = 4).  Host only.
+ * G1S_ERR_INVALID (reason from g1s_last_global_error()) for n = 0, a range above 8 ("chroma gain range must be 1..8 (0 = the
+ * default)"), and luma or chroma points whose values do not increase. */
+int g1s_denoise_chroma_gain(const g1s_segment_t *segs, size_t n, uint32_t range, uint16_t gain[256]);
+/* Rule 21 on a given s[256] (N9's, or any other).  Host only.  The same refusal for the range. */
+int g1s_denoise_chroma_gain_sigma(const uint8_t s[256], uint32_t range, uint16_t gain[256]);
 /* Stage 1 alone (rules 16 - 18, 20), as g1s_grain_templates is for render: the vectors of frame `cur` towards frame `ref`
  * of the same geometry, for a denoiser made with a motion range.  mv[c] takes plane c's vectors as pairs (mx, my) in
  * full-resolution samples of that plane, blocks in raster order; cap_pairs[c] is its capacity in pairs going in and the
@@ -759,6 +806,14 @@ int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_d
 int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                   const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
                                   uint64_t profile_frames, uint64_t min_count, char *err, size_t cap);
+/* The same with the job's prior extended to chroma (rules 21 - 24).  chroma_prior = 0 is g1s_denoise_y4m_file_auto; 1: with
+ * prior_tbl the gain of rule 22 on the segments prior_segment selects, with G1S_AUTO_PRIOR the gain of N9 on the pre-pass
+ * record that is summed already (no second pass); prior_range serves both, and a range above 8 is refused with rule 21's text
+ * though luma at 8 bits takes up to 16.  Refusals: a value other than 0 or 1 ("chroma_prior is 0 or 1"), "a chroma prior needs
+ * a grain prior (a table or the clip's own levels)", "a chroma gain needs joint chroma", and what N9 refuses. */
+int64_t g1s_denoise_y4m_file_chroma(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                    uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, char *err, size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -790,6 +845,12 @@ int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, con
                                     const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                     uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
                                     uint64_t min_count, uint64_t *frames, char *err, size_t cap);
+/* The same with chroma_prior as g1s_denoise_y4m_file_chroma takes it; chroma_prior = 0 is g1s_diff_y4m_file_denoised_auto.
+ * This closes the loop table -> prior -> better table for all three planes. */
+int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                      uint64_t min_count, uint32_t chroma_prior, uint64_t *frames, char *err, size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

@@ -17,7 +17,13 @@ tools/bench_denoise.py [batches] --motion-range R[,R...] -- motion for the tempo
 the defaults with temporal radius 1, once for every range R of the list (0: the denoiser without motion, made by the calls
 that were there before it).  The timed span holds kd_motion in front of the filter launches; "kd_motion_us_per_frame" is its
 own HIP-event time, "filter_us_per_frame" the rest, "motion_candidate_samples" the count that explains the first: per
-frame, blocks x neighbours x (R + 1)^2 candidates x up to 768 search-plane samples."""
+frame, blocks x neighbours x (R + 1)^2 candidates x up to 768 search-plane samples.
+
+tools/bench_denoise.py [batches] --gain -- the cost of a chroma gain (rules 21 - 24): both formats under joint chroma at
+(A 3, S 2, D 0), (A 7, S 3, D 0) and (A 3, S 2, D 1), without and with a gain ("chroma_gain" in the line) in one process, one
+denoiser after the other.  The gain is rule 21 at R = 8 on a steep scaling function, so that no entry is the flat gain's and no
+path is skipped.  The timed span holds the luma launch, which the gain does not touch, and the joint launch; "luma_only" cases
+(the same clip's luma planes alone) give the first, so "joint_launch_us_per_frame" = the span less that."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,7 +33,8 @@ from grav1synth_amd.synth import SynthSpec, make_pair
 
 assert torch.cuda.is_available(), "bench_denoise.py needs a GPU"
 PRIOR = "--prior" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a != "--prior"]
+GAIN = "--gain" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--prior", "--gain")]
 MOTION = None
 if "--motion-range" in args:
     i = args.index("--motion-range")
@@ -44,6 +51,16 @@ if PRIOR:
     CASES = [(3, 2, d, False, c) for d in (0, 1) for c in (False, True)]
 elif MOTION is not None:
     CASES = [(3, 2, 1, False, False, r) for r in MOTION]
+elif GAIN:
+    import numpy as np
+
+    from grav1synth_amd import _lib
+
+    _s = np.where(np.arange(256) < 96, 3, 255).astype(np.uint8)
+    STEEP_GAIN = np.zeros(256, np.uint16)
+    assert _lib.lib().g1s_denoise_chroma_gain_sigma(_s.ctypes.data, 8, STEEP_GAIN.ctypes.data) == 0 and (STEEP_GAIN != 256).all()
+    # (A, S, D, joint, prior, motion range, what: "luma" = the luma planes alone, "joint", "gain")
+    CASES = [(a, s, d, True, False, 0, w) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1)) for w in ("luma", "joint", "gain")]
 else:
     CASES = [(a, s, d, j, False) for a, s, d in ((3, 2, 0), (7, 3, 0), (3, 2, 1), (7, 3, 1), (3, 2, 2)) for j in (False, True)]
 
@@ -59,11 +76,15 @@ for name, spec in FORMATS[:1] if MOTION is not None else FORMATS:
         mr = rest[0] if rest else 0
         if mr:
             kw["motion_range"] = mr
+        what = rest[1] if len(rest) > 1 else None
+        if what == "gain":
+            kw["chroma_gain"] = STEEP_GAIN
+        planes = slice(0, 1) if what == "luma" else slice(None)
         dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint, **kw)
 
         def run(nb):
             for k in range(nb * BATCH):
-                dn.apply(ins[k % 8], spec.xdec, spec.ydec, sync=False, out=outs[k % BATCH])
+                dn.apply(ins[k % 8][planes], spec.xdec, spec.ydec, sync=False, out=outs[k % BATCH][planes])
             dn.sync()
 
         run(1)  # warm-up: code objects, buffers
@@ -77,7 +98,8 @@ for name, spec in FORMATS[:1] if MOTION is not None else FORMATS:
         dn.close()
         pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
-            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, **({"grain_prior": prior} if PRIOR else {}), "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, **({"grain_prior": prior} if PRIOR else {}),
+            **({"chroma_gain": what == "gain", "luma_only": what == "luma"} if GAIN else {}), "batch_frames": BATCH, "timed_batches": fr / BATCH,
             "samples_per_frame": samples, "unordered_pairs": pairs, "temporal_pairs": temporal_pairs,
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
             "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
