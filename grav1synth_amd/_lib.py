@@ -190,6 +190,15 @@ class G1SMeasureXRecord(C.Structure):
 G1S_MEASURE_TEMPORAL, G1S_MEASURE_CROSS = 1, 2
 
 
+class G1SMeasureSRecord(C.Structure):
+    # g1s_measure_srecord_t: [plane][k - 1][bin]
+    _fields_ = [
+        ("n", ((C.c_uint64 * 32) * 5) * 3),
+        ("s1", ((C.c_int64 * 32) * 5) * 3),
+        ("s2", ((C.c_uint64 * 32) * 5) * 3),
+    ]
+
+
 class G1SNlfOpts(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -419,6 +428,15 @@ SYMBOLS = [
                                                 C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     ("g1s_check_y4m_files_modes", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SMeasureOpts),
                                               C.POINTER(G1SGrainOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_measure_new_scales", C.c_void_p, [C.c_uint32, C.POINTER(G1SMeasureOpts), C.c_uint32]),
+    ("g1s_measure_finish_scales", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_measure_sum_scales", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_format_measure_scales", C.c_long, [C.c_void_p] * 4 + [C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]),
+    ("g1s_measure_scales_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_measure_y4m_files_scales", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                 C.POINTER(G1SMeasureOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    ("g1s_check_y4m_files_scales", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                               C.POINTER(G1SMeasureOpts), C.POINTER(G1SGrainOpts), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     ("g1s_surface_new", C.c_void_p, [C.c_uint32, C.POINTER(G1SSurfaceOpts)]),
     ("g1s_surface_unpack", C.c_int, [C.c_void_p, C.POINTER(G1SSurface), C.POINTER(G1SFrame)]),
     ("g1s_surface_pack", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SSurface)]),

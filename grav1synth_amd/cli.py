@@ -29,6 +29,9 @@ NOT_OVERWRITING = "Not overwriting existing file. Exiting."
 SAME_OUTPUTS = "--temporal and -o name the same file: the two reports would overwrite each other. Exiting."
 SAME_CROSS_OUTPUT = "--cross and -o name the same file: the two reports would overwrite each other. Exiting."
 SAME_CROSS_TEMPORAL = "--cross and --temporal name the same file: the two reports would overwrite each other. Exiting."
+SAME_SCALES_OUTPUT = "--scales and -o name the same file: the two reports would overwrite each other. Exiting."
+SAME_SCALES_TEMPORAL = "--scales and --temporal name the same file: the two reports would overwrite each other. Exiting."
+SAME_SCALES_CROSS = "--scales and --cross name the same file: the two reports would overwrite each other. Exiting."
 CROSS_NEEDS_CHROMA = "--cross compares chroma with luma: the clip has no chroma planes"
 SAME_LEVELS = "--levels and -o name the same file: the two outputs would overwrite each other. Exiting."
 NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
@@ -293,6 +296,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also write the temporal profile: the correlation of the residual with the residual of the frame before")
     m.add_argument("--cross", metavar="PATH", default=None,
                    help="also write the cross-plane profile: the chroma residuals against the luma residual under them and against each other")
+    m.add_argument("--scales", metavar="PATH", default=None,
+                   help="also write the multi-scale profile: how the residual summed over 2 x 2 .. 32 x 32 boxes grows (grain size)")
     c = sub.add_parser("check", help="Says how well a grain table fits: the profile of SOURCE - DENOISED beside the profile of the "
                                      "table's grain rendered onto DENOISED (y4m inputs).  Reports; passes no verdict.")
     c.add_argument("source", help="The untouched source file.")
@@ -308,6 +313,9 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--cross", metavar="PATH", default=None,
                    help="also write the two-column cross-plane profile: chroma against luma (the table's chroma-from-luma coefficient) "
                         "and Cb against Cr, of both residuals")
+    c.add_argument("--scales", metavar="PATH", default=None,
+                   help="also write the two-column multi-scale profile: the growth of both residuals over 2 x 2 .. 32 x 32 boxes "
+                        "(grain coarser than the table can say, or a denoiser that kept coarse grain)")
     return ap
 
 
@@ -477,6 +485,25 @@ def _cross_refused(inputs, output: str, temporal: Optional[str], cross: Optional
     return False
 
 
+def _scales_refused(inputs, output: str, temporal: Optional[str], cross: Optional[str], scales: Optional[str]) -> bool:
+    """--scales PATH is an output too: not an input, not -o's path, not --temporal's, not --cross's."""
+    if scales is None:
+        return False
+    if any(_same_path(p, scales) for p in inputs):
+        log.error(SAME_AS_OUTPUT)
+        return True
+    if _same_path(output, scales):
+        log.error(SAME_SCALES_OUTPUT)
+        return True
+    if temporal is not None and _same_path(temporal, scales):
+        log.error(SAME_SCALES_TEMPORAL)
+        return True
+    if cross is not None and _same_path(cross, scales):
+        log.error(SAME_SCALES_CROSS)
+        return True
+    return False
+
+
 def _y4m_is_monochrome(path: str) -> bool:
     """Does the .y4m header name a colour space without chroma planes?  (An unreadable file is the reader's to refuse.)"""
     try:
@@ -488,7 +515,7 @@ def _y4m_is_monochrome(path: str) -> bool:
 
 
 def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
-                    temporal: Optional[str] = None, cross: Optional[str] = None) -> int:
+                    temporal: Optional[str] = None, cross: Optional[str] = None, scales: Optional[str] = None) -> int:
     """The refusals of `diff` for two inputs and an output, then the frame pairs until the shorter file ends and the
     profile (with `temporal`, the temporal profile beside it).  Returns the frame count, -1 after a refusal."""
     from .measure import measure_y4m_files
@@ -501,21 +528,27 @@ def measure_command(noisy: str, clean: str, output: str, overwrite: bool = False
         return -1
     if _temporal_refused((noisy, clean), output, temporal) or _cross_refused((noisy, clean), output, temporal, cross, clean):
         return -1
-    for path in (output, temporal, cross):
+    if _scales_refused((noisy, clean), output, temporal, cross, scales):
+        return -1
+    for path in (output, temporal, cross, scales):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
-    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device, temporal_output=temporal, cross_output=cross)
+    frames, _unequal = measure_y4m_files(noisy, clean, output, device=device, temporal_output=temporal, cross_output=cross,
+                                         scales_output=scales)
     log.info("Done, wrote output file to %s", output)
     if temporal is not None:
         log.info("Done, wrote temporal profile to %s", temporal)
     if cross is not None:
         log.info("Done, wrote cross profile to %s", cross)
+    if scales is not None:
+        log.info("Done, wrote scale profile to %s", scales)
     return frames
 
 
 def check_command(source: str, denoised: str, table: str, output: str, overwrite: bool = False, device: int = -1,
-                  clip_restricted: bool = False, confirm=_confirm, temporal: Optional[str] = None, cross: Optional[str] = None) -> int:
+                  clip_restricted: bool = False, confirm=_confirm, temporal: Optional[str] = None, cross: Optional[str] = None,
+                  scales: Optional[str] = None) -> int:
     """The same refusals (the table is an input too), then the two profiles side by side.  No verdict, no threshold.
     Returns the frame count, -1 after a refusal."""
     from .measure import check_y4m_files
@@ -528,17 +561,21 @@ def check_command(source: str, denoised: str, table: str, output: str, overwrite
         return -1
     if _temporal_refused((source, denoised, table), output, temporal) or _cross_refused((source, denoised, table), output, temporal, cross, denoised):
         return -1
-    for path in (output, temporal, cross):
+    if _scales_refused((source, denoised, table), output, temporal, cross, scales):
+        return -1
+    for path in (output, temporal, cross, scales):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
     frames, _unequal = check_y4m_files(source, denoised, table, output, device=device, clip_to_restricted_range=clip_restricted,
-                                       temporal_output=temporal, cross_output=cross)
+                                       temporal_output=temporal, cross_output=cross, scales_output=scales)
     log.info("Done, wrote output file to %s", output)
     if temporal is not None:
         log.info("Done, wrote temporal profile to %s", temporal)
     if cross is not None:
         log.info("Done, wrote cross profile to %s", cross)
+    if scales is not None:
+        log.info("Done, wrote scale profile to %s", scales)
     return frames
 
 
@@ -584,14 +621,14 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
     elif args.command == "measure":
         try:
-            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device, temporal=args.temporal, cross=args.cross)
+            measure_command(args.noisy, args.clean, args.output, args.overwrite, args.device, temporal=args.temporal, cross=args.cross, scales=args.scales)
         except Exception as e:
             log.error("%s", e)
             return 1
     elif args.command == "check":
         try:
             check_command(args.source, args.denoised, args.grain, args.output, args.overwrite, args.device, args.clip_restricted,
-                          temporal=args.temporal, cross=args.cross)
+                          temporal=args.temporal, cross=args.cross, scales=args.scales)
         except Exception as e:
             log.error("%s", e)
             return 1

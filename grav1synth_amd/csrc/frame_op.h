@@ -186,6 +186,14 @@ inline DiffReach diff_frame_reach(const g1s_frame_t &f, int nplanes) {
   return r;
 }
 
+// What a scales meter can sum (rule 21 of `measure`): s2 of the 32 x 32 boxes is at most 4^5 (2^B - 1)^2 pw ph, which leaves 64
+// bits only for a 12-bit plane of more than 2^30 samples.  Luma is a frame's largest plane.
+constexpr uint64_t kScalesMaxSamples12 = 1ull << 30;
+inline bool scales_size_ok(uint32_t bit_depth, uint32_t width, uint32_t height) {
+  return bit_depth < 12 || (uint64_t)width * height <= kScalesMaxSamples12;
+}
+inline const char *scales_refusal_text() { return "a scales meter takes 12-bit planes of at most 2^30 samples"; }
+
 // do the bytes of plane ca at `a` and of plane cb at `b` (frames of geometry g) share an address?
 inline bool planes_overlap(const PlaneGeom &g, const uint8_t *a, size_t a_stride, int ca, const uint8_t *b, size_t b_stride, int cb) {
   const uint8_t *ae = a + a_stride * (g.ph(ca) - 1) + g.row_bytes(ca), *be = b + b_stride * (g.ph(cb) - 1) + g.row_bytes(cb);

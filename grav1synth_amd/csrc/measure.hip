@@ -13,6 +13,7 @@
 //   km_tail          a workgroup per (plane, frame pair) sums the partial records into the pair's record.
 // A temporal meter (rules 7 - 11) runs km_measure_t and km_tail_t behind them: they stand below km_tail with their own notes.
 // A cross meter (rules 12 - 17) runs km_measure_x and km_tail_t behind those: below km_tail_t.
+// A scales meter (rules 18 - 23) runs km_measure_s and km_tail_s behind those: below km_measure_x, with their own notes.
 //
 // The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
 //   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
@@ -521,6 +522,220 @@ __global__ __launch_bounds__(kThreads) void km_measure_x(CrossParams p) {
   hand_over(2);
 }
 
+// ---- the scale record (rules 18 - 23): the residual summed over aligned 2^k x 2^k boxes, k = 1 .. 5, binned by the box ----
+//   km_measure_s<BPS>  a workgroup per (strip of kSTiles tiles of km_measure side by side: 512 x 128 samples, plane of the class,
+//                      pair).  Boxes are aligned at the origin and 32 divides the tile's sides: no box crosses a tile, there is
+//                      no halo, and no sample goes through LDS.  A wave takes a band of 32 rows of the strip and walks it tile
+//                      by tile, 64 x 8 samples a step: a lane (lx = lane & 7, ly = lane >> 3) loads the 8 consecutive samples
+//                      x = 8 lx .. 8 lx + 7 of row ly of a and of b -- one 16-byte (8-byte at 8 bits) load where the address
+//                      allows it, sample by sample where it does not or where the plane ends inside -- and for chroma the
+//                      clean luma it is binned by.  It forms d and I and their sums of widths 2, 4 and 8 itself.  Rows are
+//                      combined between lanes: ly ^ 1 by DPP row_ror:8, ly ^ 2 by a swizzle of the 32-lane halves, ly ^ 4 by a
+//                      permute; that gives the boxes of k = 1, 2, 3 of the step in every lane that took part.  k = 4 adds two
+//                      steps in a register and lx ^ 1 by DPP, k = 5 four steps and lx ^ 2.  Every sample comes from HBM once.
+//   km_tail_s          a workgroup per (plane, pair) sums the strips' partial records into the pair's record.
+// Bin sums: a box's (scale, bin) is its key; the lanes that own a box hand it on together, as hand_on does in km_measure: for
+// every distinct key among them one masked DPP reduction and one LDS update by lane 0 (the count is the mask's population).
+// A step has three such rounds: two for k = 1 (its 128 boxes spread over all 64 lanes: even rows take the left two boxes of
+// their lane's four, odd rows the right two) and one for k = 2 .. 5 together, whose owners are distinct lanes (k = 2:
+// ly & 3 < 2, k = 3: ly = 2, k = 4: ly = 3 and even lx, k = 5: ly = 6 and lx & 3 = 0; every lane of a group holds the group's
+// sums after the exchanges).  A tile has N / 3 boxes in all; a flat tile costs 2 + 2 .. 4 hand-ons a step.
+// Exactness: |d| <= 4095, I <= 4095.  A lane's sums over 8 samples are below 2^15; every box sum B and C is below 4^5 2^12 =
+// 2^22 and lives in 32 bits; s1 across a wave is below 2^28 (wave_sum); B^2 < 2^44 is formed in 64 bits and summed across
+// the wave as two 16-bit pieces and the rest (wave_sum_u64, lane values below 2^57); the LDS and the partial sums are 64-bit.
+// The partial records: 480 words a strip and plane.  A strip is 8 tiles wide, so a 4K 4:2:0 pair has 136 + 2 x 36 = 208 of them,
+// 0.8 MB, where km_measure's tile would make 6 MB.
+constexpr int kScales = 5;
+constexpr int kSEntries = kScales * 3 * kBins;  // a partial scale record: [k - 1][n, s1, s2][bin]
+constexpr int kSTiles = 8, kSW = kTW * kSTiles;  // the strip of a workgroup
+constexpr int kSTailThreads = 512;
+static_assert(kRowsPerWave == 32 && kTW == 64, "a wave's band holds whole 32 x 32 boxes, a step is 8 lanes of 8 samples wide");
+static_assert(kSEntries <= kSTailThreads, "km_tail_s gives an entry a thread");
+static_assert(sizeof(g1s_measure_srecord_t) == 8 * 3 * kSEntries, "km_tail_s writes the scale record as 64-bit words");
+
+struct ScaleParams {
+  const MeasureJob *jobs;
+  unsigned long long *partials;  // [pair][strips_frame][kSEntries]
+  int pw, ph, strips_x;          // the class's plane size
+  int plane0;
+  int W, H, xdec, ydec, shift;  // luma size, chroma decimation, B - 5
+  uint32_t strips_frame, strip_base, strips_plane;
+};
+
+// the value of lane ^ M, every lane taking part
+template <int M>
+__device__ __forceinline__ int lane_xor(int v, int lane) {
+  if (M == 1) return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+  if (M == 2) return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+  if (M == 8) return __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);  // row_ror:8
+  if (M == 16) return __builtin_amdgcn_ds_swizzle(v, 0x401F);                    // bit mode: and 0x1f, or 0, xor 0x10
+  return __builtin_amdgcn_ds_bpermute((lane ^ M) << 2, v);
+}
+
+// samples x .. x + 7 of row y of a pw x ph plane; zeros outside it
+template <int BPS>
+__device__ __forceinline__ void load8(const uint8_t *plane, uint32_t stride, int x, int y, int pw, int ph, int v[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = 0;
+  if (x >= pw || y >= ph) return;
+  const uint8_t *at = plane + (size_t)y * stride + (size_t)x * BPS;
+  if (x + 8 <= pw && ((uintptr_t)at & (8 * BPS - 1)) == 0) {
+    if (BPS == 2) {
+      const uint4 q = *reinterpret_cast<const uint4 *>(at);
+      v[0] = (int)(q.x & 0xffffu), v[1] = (int)(q.x >> 16), v[2] = (int)(q.y & 0xffffu), v[3] = (int)(q.y >> 16);
+      v[4] = (int)(q.z & 0xffffu), v[5] = (int)(q.z >> 16), v[6] = (int)(q.w & 0xffffu), v[7] = (int)(q.w >> 16);
+    } else {
+      const uint2 q = *reinterpret_cast<const uint2 *>(at);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (int)((q.x >> (8 * j)) & 0xffu), v[4 + j] = (int)((q.y >> (8 * j)) & 0xffu);
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (x + j < pw) v[j] = BPS == 2 ? (int)reinterpret_cast<const uint16_t *>(at)[j] : (int)at[j];
+}
+
+template <int BPS>
+__global__ __launch_bounds__(kThreads) void km_measure_s(ScaleParams p) {
+  __shared__ unsigned long long s_acc[kWaves][kSEntries];  // (two's complement, as km_measure's)
+  const MeasureJob &job = p.jobs[blockIdx.z];
+  const int c = p.plane0 + (int)blockIdx.y;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ty = (int)blockIdx.x / p.strips_x, tx = (int)blockIdx.x - ty * p.strips_x;
+  const int x0 = tx * kSW, yw = ty * kTH + wave * kRowsPerWave;  // the wave's band of the strip
+  const uint8_t *pa = job.a[c], *pb = job.b[c], *py = job.b[0];
+  const uint32_t sa = job.a_stride[c], sb = job.b_stride[c], sy = job.b_stride[0];
+  const int lx = lane & 7, ly = lane >> 3;
+  unsigned long long *mine = s_acc[wave];
+
+  for (int i = tid; i < kWaves * kSEntries; i += kThreads) (&s_acc[0][0])[i] = 0;
+  __syncthreads();
+
+  // hands on the boxes of the lanes with `go` set: key = (k - 1) 32 + K, a reduction and an update a distinct key
+  auto hand_on = [&](bool go, int key, int B) __attribute__((always_inline)) {
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
+    while (todo) {
+      const int k = __builtin_amdgcn_readlane(key, (int)__builtin_ctzll(todo));
+      const bool m = go && key == k;
+      const unsigned long long who = __builtin_amdgcn_ballot_w64(m);
+      todo &= ~who;
+      const int s1 = wave_sum(m ? B : 0);
+      const unsigned long long s2 = wave_sum_u64(m ? (unsigned long long)((long long)B * (long long)B) : 0ull);
+      if (lane == 0) {
+        unsigned long long *at = mine + (k >> 5) * 3 * kBins + (k & (kBins - 1));
+        at[0] += (unsigned long long)__builtin_popcountll(who);
+        at[kBins] += (unsigned long long)(long long)s1;
+        at[2 * kBins] += s2;
+      }
+    }
+  };
+  // the key of a box of scale k with intensity sum C
+  auto key_of = [&](int k, int C) { return (k - 1) * kBins + min(C >> (2 * k + p.shift), kBins - 1); };
+
+  if (yw < p.ph) {  // (uniform in the wave)
+    for (int sub = 0; sub < kSTiles; ++sub) {
+      const int xt = x0 + sub * kTW;
+      if (xt >= p.pw) break;  // (uniform)
+      const int x = xt + 8 * lx;
+      int b4 = 0, c4 = 0, b5 = 0, c5 = 0;  // the sums of k = 4 over two steps and of k = 5 over four
+      for (int step = 0; step < 4; ++step) {
+        const int y = yw + 8 * step + ly;
+        int d[8], I[8];
+        load8<BPS>(pa, sa, x, y, p.pw, p.ph, d);
+        load8<BPS>(pb, sb, x, y, p.pw, p.ph, I);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] -= I[j];
+        if (c) {  // averageLuma of the clean frame, sample by sample (rule 2)
+          const int ys = y << p.ydec;
+          if (y >= p.ph) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) I[j] = 0;
+          } else if (!p.xdec) {
+            load8<BPS>(py, sy, x, ys, p.W, p.H, I);
+          } else {
+            int l[16];
+            load8<BPS>(py, sy, 2 * x, ys, p.W, p.H, l);
+            load8<BPS>(py, sy, 2 * x + 8, ys, p.W, p.H, l + 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) I[j] = (l[2 * j] + (2 * (x + j) + 1 < p.W ? l[2 * j + 1] : l[2 * j]) + 1) >> 1;
+          }
+        }
+        // the lane's own sums of widths 2, 4 and 8
+        int B1[4], C1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) B1[j] = d[2 * j] + d[2 * j + 1], C1[j] = I[2 * j] + I[2 * j + 1];
+        // k = 1: rows ly and ly ^ 1
+#pragma unroll
+        for (int j = 0; j < 4; ++j) B1[j] += lane_xor<8>(B1[j], lane), C1[j] += lane_xor<8>(C1[j], lane);
+        // k = 2: four columns, rows ly & ~3 .. + 3
+        int B2[2], C2[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          B2[j] = B1[2 * j] + B1[2 * j + 1], C2[j] = C1[2 * j] + C1[2 * j + 1];
+          B2[j] += lane_xor<16>(B2[j], lane), C2[j] += lane_xor<16>(C2[j], lane);
+        }
+        // k = 3: the lane's eight columns, the step's eight rows
+        int B3 = B2[0] + B2[1], C3 = C2[0] + C2[1];
+        B3 += lane_xor<32>(B3, lane), C3 += lane_xor<32>(C3, lane);
+        b4 += B3, c4 += C3;
+        // (a choice between two registers by a mask: written as a choice between two elements it becomes an indexed array)
+        auto pick = [](int mask, int a, int b) { return a ^ ((a ^ b) & mask); };
+        const int y2 = y & ~1, odd = ly & 1;
+        // a whole box: its last column and its last row lie inside the plane
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int xb = x + 4 * odd + 2 * q;
+          hand_on(xb + 2 <= p.pw && y2 + 2 <= p.ph, key_of(1, pick(-odd, C1[q], C1[2 + q])), pick(-odd, B1[q], B1[2 + q]));
+        }
+        // k = 2 .. 5 in one round: distinct owners
+        bool go = false;
+        int key = 0, B = 0;
+        const int y4 = y & ~3, y8 = y & ~7;
+        if ((ly & 3) < 2) {
+          go = x + 4 * (ly & 3) + 4 <= p.pw && y4 + 4 <= p.ph;
+          key = key_of(2, pick(-(ly & 1), C2[0], C2[1])), B = pick(-(ly & 1), B2[0], B2[1]);
+        } else if (ly == 2) {
+          go = x + 8 <= p.pw && y8 + 8 <= p.ph, key = key_of(3, C3), B = B3;
+        }
+        if (step & 1) {  // (uniform)
+          const int B4 = b4 + lane_xor<1>(b4, lane), C4 = c4 + lane_xor<1>(c4, lane);
+          b4 = c4 = 0;
+          b5 += B4, c5 += C4;
+          if (ly == 3 && !(lx & 1)) go = x + 16 <= p.pw && (y8 & ~15) + 16 <= p.ph, key = key_of(4, C4), B = B4;
+          if (step == 3) {
+            // (b5 holds the 16 columns of lx and lx ^ 1 over the band's 32 rows)
+            const int B5 = b5 + lane_xor<2>(b5, lane), C5 = c5 + lane_xor<2>(c5, lane);
+            if (ly == 6 && !(lx & 3)) go = x + 32 <= p.pw && yw + 32 <= p.ph, key = key_of(5, C5), B = B5;
+          }
+        }
+        hand_on(go, key, B);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < kSEntries; i += kThreads) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) t += s_acc[v][i];
+    const size_t at = (size_t)blockIdx.z * p.strips_frame + p.strip_base + (size_t)blockIdx.y * p.strips_plane + blockIdx.x;
+    p.partials[at * kSEntries + i] = t;
+  }
+}
+
+// the pair's scale record from its workgroups' partial records: grid (plane, pair)
+__global__ __launch_bounds__(kSTailThreads) void km_tail_s(TailParams p) {
+  const int c = (int)blockIdx.x, i = (int)threadIdx.x;
+  if (i >= kSEntries) return;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kSEntries;
+  unsigned long long t = 0;
+  for (uint32_t k = 0; k < p.tiles[c]; ++k) t += src[(size_t)k * kSEntries + i];
+  // g1s_measure_srecord_t as 64-bit words: n[3][5][32], s1[3][5][32], s2[3][5][32]; entry i = (scale, field, bin)
+  const int scale = i / (3 * kBins), field = (i / kBins) % 3, bin = i % kBins;
+  unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_srecord_t) / 8);
+  rec[(field * 3 + c) * kScales * kBins + scale * kBins + bin] = t;
+}
+
 // rule 8's offsets: raster order, (0, 0) is index 12
 void temporal_offset(int i, int *dx, int *dy) { *dy = i / kTWin - kTHalo, *dx = i % kTWin - kTHalo; }
 
@@ -574,6 +789,17 @@ struct g1s_measure : BatchedOp {
   std::vector<g1s_measure_xrecord_t> xrecords;  // since the last hand-over
   double ms_xkernel = 0;
   uint64_t xpairs_timed = 0;
+  // a scales meter (rules 18 - 23): a scale record a pair, from the batch's own jobs
+  bool scales = false;
+  Event ev_s[2];
+  DevBuf<unsigned long long> d_spartials;
+  size_t spartials_cap = 0;
+  uint32_t strips[3] = {0, 0, 0}, strip_base[3] = {0, 0, 0}, strips_frame = 0;
+  DevBuf<g1s_measure_srecord_t> d_srecs;
+  PinnedBuf<g1s_measure_srecord_t> h_srecs;
+  std::vector<g1s_measure_srecord_t> srecords;  // since the last hand-over
+  double ms_skernel = 0;
+  uint64_t spairs_timed = 0;
   // the chroma launches alone, for tools/bench_measure.py --cross (recorded only while timing is on)
   Event ev_c[2], ev_tc[2];
   double ms_chroma = 0, ms_tchroma = 0;
@@ -608,6 +834,18 @@ int g1s_measure::set_geometry(const g1s_frame_t &f) {
     d_xpartials = DevBuf<unsigned long long>();
     G1S_OP_TRY(hipMalloc((void **)&d_xpartials.p, xneed * sizeof(unsigned long long)));
     xpartials_cap = xneed;
+  }
+  strips_frame = 0;
+  for (int c = 0; c < 3; ++c) {
+    strips[c] = scales && c < geom.nplanes ? (uint32_t)(((geom.pw(c) + kSW - 1) / kSW) * ((geom.ph(c) + kTH - 1) / kTH)) : 0u;
+    strip_base[c] = strips_frame;
+    strips_frame += strips[c];
+  }
+  const size_t sneed = (size_t)strips_frame * kSEntries * batch;
+  if (sneed > spartials_cap) {
+    d_spartials = DevBuf<unsigned long long>();
+    G1S_OP_TRY(hipMalloc((void **)&d_spartials.p, sneed * sizeof(unsigned long long)));
+    spartials_cap = sneed;
   }
   have_prev = false, ring_at = 0;  // (a new geometry ends the run; the rings are made again)
   d_keep[0] = DevBuf<uint8_t>(), d_keep[1] = DevBuf<uint8_t>();
@@ -694,6 +932,29 @@ int g1s_measure::flush() {
     if (timing) G1S_OP_TRY(hipEventRecord(ev_x[1], stream));
     G1S_OP_TRY(hipMemcpyAsync(h_xrecs, d_xrecs, sizeof(g1s_measure_xrecord_t) * B, hipMemcpyDeviceToHost, stream));
   }
+  // a scales meter: the batch's own jobs once more, a km_measure_s launch a plane class and km_tail_s over the strips' partials
+  if (scales) {
+    G1S_OP_TRY(hipMemsetAsync(d_srecs, 0, sizeof(g1s_measure_srecord_t) * B, stream));  // (the planes a frame does not have)
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_s[0], stream));
+    for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
+      ScaleParams sp{};
+      sp.jobs = p_jobs.d[set], sp.partials = d_spartials;
+      sp.pw = (int)geom.pw(plane0), sp.ph = (int)geom.ph(plane0), sp.strips_x = (sp.pw + kSW - 1) / kSW, sp.plane0 = plane0;
+      sp.W = geom.W, sp.H = geom.H, sp.xdec = geom.subx, sp.ydec = geom.suby, sp.shift = (int)bit_depth - 5;
+      sp.strips_frame = strips_frame, sp.strip_base = strip_base[plane0], sp.strips_plane = strips[plane0];
+      const dim3 grid(strips[plane0], plane0 ? 2u : 1u, B);
+      if (bps == 2) hipLaunchKernelGGL(km_measure_s<2>, grid, dim3(kThreads), 0, stream, sp);
+      else hipLaunchKernelGGL(km_measure_s<1>, grid, dim3(kThreads), 0, stream, sp);
+      G1S_OP_TRY(hipGetLastError());
+    }
+    TailParams stp{};
+    stp.partials = d_spartials, stp.records = reinterpret_cast<unsigned long long *>(d_srecs.p), stp.tiles_frame = strips_frame;
+    for (int c = 0; c < 3; ++c) stp.tiles[c] = strips[c], stp.tile_base[c] = strip_base[c];
+    hipLaunchKernelGGL(km_tail_s, dim3((unsigned)geom.nplanes, B), dim3(kSTailThreads), 0, stream, stp);
+    G1S_OP_TRY(hipGetLastError());
+    if (timing) G1S_OP_TRY(hipEventRecord(ev_s[1], stream));
+    G1S_OP_TRY(hipMemcpyAsync(h_srecs, d_srecs, sizeof(g1s_measure_srecord_t) * B, hipMemcpyDeviceToHost, stream));
+  }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
   if (timing) {
     float ms = 0;
@@ -715,10 +976,15 @@ int g1s_measure::flush() {
       G1S_OP_TRY(hipEventElapsedTime(&ms, ev_x[0], ev_x[1]));
       ms_xkernel += ms, xpairs_timed += B;
     }
+    if (scales) {
+      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_s[0], ev_s[1]));
+      ms_skernel += ms, spairs_timed += B;
+    }
   }
   records.insert(records.end(), h_recs.p, h_recs.p + B);
   trecords.insert(trecords.end(), h_trecs.p, h_trecs.p + T);
   if (cross) xrecords.insert(xrecords.end(), h_xrecs.p, h_xrecs.p + B);
+  if (scales) srecords.insert(srecords.end(), h_srecs.p, h_srecs.p + B);
   jobs.clear();
   tjobs.clear();
   return G1S_OK;
@@ -926,9 +1192,39 @@ int not_cross(g1s_measure_t *m) {
   return G1S_ERR_INVALID;
 }
 
-// g1s_measure_new, g1s_measure_new_temporal and g1s_measure_new_modes: the same refusals, the same meter but for the buffers
+int not_scales(g1s_measure_t *m) {
+  m->err = "the meter was not made by g1s_measure_new_scales";  // (not sticky: err_code stays 0)
+  return G1S_ERR_INVALID;
+}
+
+// the scale records the meter holds, added to `total`.  "" when fine
+std::string take_srecords(g1s_measure_t *m, std::vector<g1s_measure_srecord_t> &scratch, g1s_measure_srecord_t &total) {
+  size_t n = 0;
+  int rc = g1s_measure_finish_scales(m, nullptr, 0, &n);
+  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
+  scratch.resize(n + 1);
+  scratch[n] = total;
+  if (n && (rc = g1s_measure_finish_scales(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
+  if (g1s_measure_sum_scales(scratch.data(), n + 1, &total) != 0) return "the clip's scale sums leave 64 bits";
+  return "";
+}
+
+// the scale report of a clip's plain and scale record(s) into a file.  "" when fine
+std::string write_sreport(const char *path, const g1s_measure_record_t &total, const g1s_measure_srecord_t &stotal, const g1s_measure_record_t *synth,
+                          const g1s_measure_srecord_t *ssynth, uint64_t frames, const g1s_y4m_info_t &info) {
+  std::vector<char> buf(1 << 16);
+  const long n = g1s_format_measure_scales(&total, &stotal, synth, ssynth, frames, info.bit_depth, info.nplanes, buf.data(), buf.size());
+  if (n < 0) return "formatting the scale report failed";
+  FILE *f = std::fopen(path, "wb");
+  if (!f) return std::string("cannot create ") + path;
+  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
+  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
+  return "";
+}
+
+// g1s_measure_new, g1s_measure_new_temporal, g1s_measure_new_modes and g1s_measure_new_scales: the same refusals, the same meter but for the buffers
 // of the modes
-g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes) {
+g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes, bool scales = false) {
   g1s_set_global_error_("");
   if (modes & ~(uint32_t)(G1S_MEASURE_TEMPORAL | G1S_MEASURE_CROSS)) {
     g1s_set_global_error_("unknown mode bits: g1s_measure_new_modes takes G1S_MEASURE_TEMPORAL and G1S_MEASURE_CROSS");
@@ -950,7 +1246,7 @@ g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, u
     return nullptr;
   }
   g1s_measure *m = new g1s_measure;
-  m->temporal = temporal, m->cross = cross;
+  m->temporal = temporal, m->cross = cross, m->scales = scales;
   bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
   const uint32_t B = m->batch;
   for (Event &e : m->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
@@ -967,6 +1263,11 @@ g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, u
     for (Event &e : m->ev_x) ok = ok && hipEventCreate(&e.p) == hipSuccess;
     ok = ok && hipMalloc((void **)&m->d_xrecs.p, sizeof(g1s_measure_xrecord_t) * B) == hipSuccess &&
          hipHostMalloc((void **)&m->h_xrecs.p, sizeof(g1s_measure_xrecord_t) * B, hipHostMallocDefault) == hipSuccess;
+  }
+  if (scales) {
+    for (Event &e : m->ev_s) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    ok = ok && hipMalloc((void **)&m->d_srecs.p, sizeof(g1s_measure_srecord_t) * B) == hipSuccess &&
+         hipHostMalloc((void **)&m->h_srecs.p, sizeof(g1s_measure_srecord_t) * B, hipHostMallocDefault) == hipSuccess;
   }
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
@@ -986,6 +1287,8 @@ g1s_measure_t *g1s_measure_new_temporal(uint32_t bit_depth, const g1s_measure_op
 
 g1s_measure_t *g1s_measure_new_modes(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes) { return measure_new(bit_depth, opts, modes); }
 
+g1s_measure_t *g1s_measure_new_scales(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes) { return measure_new(bit_depth, opts, modes, true); }
+
 int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_frame_t *clean) {
   if (!m || !noisy || !clean) return G1S_ERR_INVALID;
   if (m->err_code) return m->err_code;
@@ -993,6 +1296,7 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
   const Refusal no = check_frame_pair(*noisy, *clean, m->bps, 65536u, "g1s_measure_new",
                                       "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)", "noisy and clean");
   if (no.code) return m->fail(no.code, no.text);
+  if (m->scales && !scales_size_ok(m->bit_depth, noisy->width, noisy->height)) return m->fail(G1S_ERR_INVALID, scales_refusal_text());
   int rc;
   if (m->have_geom && !m->geom.same_shape(*noisy)) {
     // a new geometry: what is queued goes out and finishes first, the buffers are sized again
@@ -1050,6 +1354,27 @@ int g1s_measure_finish_cross(g1s_measure_t *m, g1s_measure_xrecord_t *per_pair, 
   if (m->xrecords.size() > cap || (!per_pair && !m->xrecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
   if (!m->xrecords.empty()) std::memcpy(per_pair, m->xrecords.data(), sizeof(g1s_measure_xrecord_t) * m->xrecords.size());
   m->xrecords.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_finish_scales(g1s_measure_t *m, g1s_measure_srecord_t *per_pair, size_t cap, size_t *n_out) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  if (!m->scales) return not_scales(m);
+  (void)hipSetDevice(m->device);
+  int rc = m->flush();
+  if (rc || (rc = m->keep_prev()) != 0) return rc;
+  if (n_out) *n_out = m->srecords.size();
+  if (m->srecords.size() > cap || (!per_pair && !m->srecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
+  if (!m->srecords.empty()) std::memcpy(per_pair, m->srecords.data(), sizeof(g1s_measure_srecord_t) * m->srecords.size());
+  m->srecords.clear();
+  return G1S_OK;
+}
+
+int g1s_measure_scales_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
+  if (!m) return G1S_ERR_INVALID;
+  if (ms_kernel) *ms_kernel = m->ms_skernel;
+  if (pairs) *pairs = m->spairs_timed;
   return G1S_OK;
 }
 
@@ -1330,6 +1655,11 @@ int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, con
 
 int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
                                     const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
+  return g1s_measure_y4m_files_scales(noisy, clean, out_report, out_treport, out_xreport, nullptr, opts, unequal, err, cap);
+}
+
+int64_t g1s_measure_y4m_files_scales(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
+                                     const char *out_sreport, const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
   if (unequal) *unequal = 0;
   if (!noisy || !clean || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   g1s_y4m_t *ya = g1s_y4m_open(noisy, err, cap);
@@ -1355,10 +1685,14 @@ int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const 
   g1s_measure_xrecord_t xtotal;
   std::memset(&xtotal, 0, sizeof xtotal);
   std::vector<g1s_measure_xrecord_t> xscratch;
+  g1s_measure_srecord_t stotal;
+  std::memset(&stotal, 0, sizeof stotal);
+  std::vector<g1s_measure_srecord_t> sscratch;
   const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
   if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
   if (!rc && out_xreport && ia.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
-  if (!rc && !(m = g1s_measure_new_modes(ia.bit_depth, opts, modes))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && !(m = out_sreport ? g1s_measure_new_scales(ia.bit_depth, opts, modes) : g1s_measure_new_modes(ia.bit_depth, opts, modes)))
+    rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   while (!rc) {
     g1s_frame_t fa, fb;
     const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
@@ -1380,14 +1714,17 @@ int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const 
       if (!(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
       else if (out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
       else if (out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_sreport && !(why = take_srecords(m, sscratch, stotal)).empty()) rc = G1S_ERR_INVALID;
     }
   }
   if (!rc && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_sreport && !(why = take_srecords(m, sscratch, stotal)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && !(why = write_report(out_report, total, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = write_treport(out_treport, ttotal, nullptr, pairs, ia)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_sreport && !(why = write_sreport(out_sreport, total, stotal, nullptr, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
   g1s_measure_free(m);
   g1s_y4m_close(ya);
   g1s_y4m_close(yb);
@@ -1407,6 +1744,12 @@ int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, c
 int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
                                   const char *out_xreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err,
                                   size_t cap) {
+  return g1s_check_y4m_files_scales(source, denoised, tbl, out_report, out_treport, out_xreport, nullptr, opts, gopts, unequal, err, cap);
+}
+
+int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                   const char *out_xreport, const char *out_sreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts,
+                                   int *unequal, char *err, size_t cap) {
   if (unequal) *unequal = 0;
   if (!source || !denoised || !tbl || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   // the table, as g1s_grain_y4m_file reads it
@@ -1448,8 +1791,11 @@ int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, cons
   g1s_measure_xrecord_t xtotal_s, xtotal_r;
   std::memset(&xtotal_s, 0, sizeof xtotal_s), std::memset(&xtotal_r, 0, sizeof xtotal_r);
   std::vector<g1s_measure_xrecord_t> xscratch;
+  g1s_measure_srecord_t stotal_s, stotal_r;
+  std::memset(&stotal_s, 0, sizeof stotal_s), std::memset(&stotal_r, 0, sizeof stotal_r);
+  std::vector<g1s_measure_srecord_t> sscratch;
   const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
-  auto meter = [&]() { return g1s_measure_new_modes(id.bit_depth, opts, modes); };
+  auto meter = [&]() { return out_sreport ? g1s_measure_new_scales(id.bit_depth, opts, modes) : g1s_measure_new_modes(id.bit_depth, opts, modes); };
   if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
   if (!rc && out_xreport && id.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
   if (!rc && (!(ms = meter()) || !(mr = meter()))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
@@ -1488,6 +1834,7 @@ int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, cons
       if (!(why = take_records(k ? mr : ms, scratch, k ? total_r : total_s)).empty()) rc = G1S_ERR_INVALID;
       else if (out_treport && !(why = take_trecords(k ? mr : ms, tscratch, k ? ttotal_r : ttotal_s, k ? pairs_r : pairs_s)).empty()) rc = G1S_ERR_INVALID;
       else if (out_xreport && !(why = take_xrecords(k ? mr : ms, xscratch, k ? xtotal_r : xtotal_s)).empty()) rc = G1S_ERR_INVALID;
+      else if (out_sreport && !(why = take_srecords(k ? mr : ms, sscratch, k ? stotal_r : stotal_s)).empty()) rc = G1S_ERR_INVALID;
     in_group = 0;
   };
   while (!rc) {
@@ -1526,6 +1873,7 @@ int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, cons
   if (!rc && !(why = write_report(out_report, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_treport && !(why = write_treport(out_treport, ttotal_s, &ttotal_r, pairs_s, id)).empty()) rc = G1S_ERR_INVALID;
   if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal_s, &xtotal_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_sreport && !(why = write_sreport(out_sreport, total_s, stotal_s, &total_r, &stotal_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
   if (ms) (void)hipSetDevice(ms->device);
   g1s_grain_free(gr);
   g1s_measure_free(mr);

@@ -28,6 +28,15 @@ against each other.  Every pair has a cross record; the two modes combine.
 >>> xrecords = meter.finish_cross()             # one entry a pair: n, x, u, v (3 pairings x 32), c (3 pairings x 25)
 >>> text = format_cross_profile(sum_cross_records(xrecords), len(xrecords), 10, width, height)
 >>> check_y4m_files("source.y4m", "denoised.y4m", "table.tbl", "fit.txt", cross_output="cross.txt")
+
+A scales meter also looks further than 3 samples (rules 18 - 23): the residual summed over aligned 2^k x 2^k boxes, k = 1 .. 5,
+binned by the box.  Every pair has a scale record; it combines with the other modes.
+
+>>> meter = GrainMeter(10, scales=True)
+>>> for noisy, clean in pairs: meter.measure(noisy, clean)
+>>> srecords, records = meter.finish_scales(), meter.finish()   # n, s1, s2 (3 planes x 5 scales x 32 bins)
+>>> text = format_scale_profile(sum_records(records), sum_scale_records(srecords), len(records), 10)
+>>> check_y4m_files("source.y4m", "denoised.y4m", "table.tbl", "fit.txt", scales_output="scales.txt")
 """
 from __future__ import annotations
 
@@ -38,7 +47,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord, G1SMeasureTRecord, G1SMeasureXRecord
+from ._lib import G1SError, G1SGrainOpts, G1SMeasureOpts, G1SMeasureRecord, G1SMeasureSRecord, G1SMeasureTRecord, G1SMeasureXRecord
 from ._frame_op import FrameOp
 from .diff import Frame
 from .ingest import UNEQUAL_WARNING
@@ -54,6 +63,9 @@ assert TRECORD.itemsize == C.sizeof(G1SMeasureTRecord)
 # g1s_measure_xrecord_t: the same fields, the first index the pairing (cb_luma, cr_luma, cb_cr)
 XRECORD = np.dtype(TRECORD.descr)
 assert XRECORD.itemsize == C.sizeof(G1SMeasureXRecord)
+# g1s_measure_srecord_t: [plane][k - 1][bin]
+SRECORD = np.dtype([("n", "<u8", (3, 5, 32)), ("s1", "<i8", (3, 5, 32)), ("s2", "<u8", (3, 5, 32))])
+assert SRECORD.itemsize == C.sizeof(G1SMeasureSRecord) == 11520
 
 
 def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
@@ -63,13 +75,18 @@ def _opts(device: int, batch_frames: int) -> G1SMeasureOpts:
 class GrainMeter(FrameOp):
     _name = "measure"
 
-    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False, cross: bool = False):
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False, cross: bool = False,
+                 scales: bool = False):
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal = temporal
         self.cross = cross
+        self.scales = scales
         opts = _opts(device, batch_frames)
-        if cross:
+        if scales:
+            modes = (_lib.G1S_MEASURE_TEMPORAL if temporal else 0) | (_lib.G1S_MEASURE_CROSS if cross else 0)
+            self._h = self._L.g1s_measure_new_scales(bit_depth, C.byref(opts), modes)
+        elif cross:
             modes = (_lib.G1S_MEASURE_TEMPORAL if temporal else 0) | _lib.G1S_MEASURE_CROSS
             self._h = self._L.g1s_measure_new_modes(bit_depth, C.byref(opts), modes)
         else:
@@ -154,6 +171,29 @@ class GrainMeter(FrameOp):
         self._check(rc)
         self._keep.clear()
         return out[:n.value]
+
+    def finish_scales(self, cap: Optional[int] = None) -> np.ndarray:
+        """As finish(), for the scale records of a scales meter: one for every pair, in order, since the last finish_scales().
+        The other records stay until their own calls fetch them."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_measure_finish_scales(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), SRECORD)
+        rc = self._L.g1s_measure_finish_scales(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def scales_kernel_times(self) -> Tuple[float, int]:
+        """(ms in km_measure_s and its summing launch, scale records) of the batches kernel_times() had timed."""
+        a, n = C.c_double(), C.c_uint64()
+        self._L.g1s_measure_scales_timing(self._h, C.byref(a), C.byref(n))
+        return a.value, n.value
 
     def cross_kernel_times(self) -> Tuple[float, int]:
         """(ms in km_measure_x and its summing launch, cross records) of the batches kernel_times() had timed."""
@@ -251,18 +291,45 @@ def format_cross_profile(total: np.ndarray, frames: int, bit_depth: int, width: 
     return buf.raw[:w]
 
 
+def sum_scale_records(records: np.ndarray) -> np.ndarray:
+    """Rule 22: a clip's scale record from its pairs' (g1s_measure_sum_scales; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, SRECORD).reshape(-1)
+    total = np.zeros((), SRECORD)
+    rc = _lib.lib().g1s_measure_sum_scales(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's scale sums leave 64 bits")
+    return total
+
+
+def format_scale_profile(total: np.ndarray, stotal: np.ndarray, frames: int, bit_depth: int, nplanes: int = 3,
+                         synth: Optional[np.ndarray] = None, ssynth: Optional[np.ndarray] = None, cap: int = 1 << 16) -> bytes:
+    """The scale report of a clip's plain record and its scale record (g1s_format_measure_scales; host only): one value
+    column, or two with `synth` and `ssynth`.  cap: the size of the buffer handed to the library (a test aid)."""
+    total, stotal = np.ascontiguousarray(total, RECORD), np.ascontiguousarray(stotal, SRECORD)
+    synth = None if synth is None else np.ascontiguousarray(synth, RECORD)
+    ssynth = None if ssynth is None else np.ascontiguousarray(ssynth, SRECORD)
+    buf = C.create_string_buffer(max(cap, 1))
+    w = _lib.lib().g1s_format_measure_scales(total.ctypes.data, stotal.ctypes.data, None if synth is None else synth.ctypes.data,
+                                             None if ssynth is None else ssynth.ctypes.data, frames, bit_depth, nplanes, buf, cap)
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_measure_scales failed")
+    return buf.raw[:w]
+
+
 def _path(p) -> Optional[bytes]:
     return None if p is None else str(p).encode()
 
 
 def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, batch_frames: int = 0,
-                      temporal_output: Optional[str] = None, cross_output: Optional[str] = None) -> Tuple[int, bool]:
-    """`measure NOISY CLEAN -o REPORT [--temporal PATH] [--cross PATH]` for two .y4m files.  Returns (frames, unequal)."""
+                      temporal_output: Optional[str] = None, cross_output: Optional[str] = None,
+                      scales_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`measure NOISY CLEAN -o REPORT [--temporal PATH] [--cross PATH] [--scales PATH]` for two .y4m files.  Returns
+    (frames, unequal)."""
     opts = _opts(device, batch_frames)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_measure_y4m_files_modes(str(noisy).encode(), str(clean).encode(), str(output).encode(), _path(temporal_output),
-                                               _path(cross_output), C.byref(opts), C.byref(unequal), err, len(err))
+    n = _lib.lib().g1s_measure_y4m_files_scales(str(noisy).encode(), str(clean).encode(), str(output).encode(), _path(temporal_output),
+                                                _path(cross_output), _path(scales_output), C.byref(opts), C.byref(unequal), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:
@@ -273,16 +340,16 @@ def measure_y4m_files(noisy: str, clean: str, output: str, *, device: int = -1, 
 
 def check_y4m_files(source: str, denoised: str, table: str, output: str, *, device: int = -1, batch_frames: int = 0,
                     clip_to_restricted_range: bool = False, temporal_output: Optional[str] = None,
-                    cross_output: Optional[str] = None) -> Tuple[int, bool]:
-    """`check SOURCE DENOISED -g TABLE -o REPORT [--temporal PATH] [--cross PATH]`: source - denoised beside
+                    cross_output: Optional[str] = None, scales_output: Optional[str] = None) -> Tuple[int, bool]:
+    """`check SOURCE DENOISED -g TABLE -o REPORT [--temporal PATH] [--cross PATH] [--scales PATH]`: source - denoised beside
     render(denoised, table) - denoised.  Returns (frames, unequal)."""
     opts = _opts(device, batch_frames)
     gopts = G1SGrainOpts(C.sizeof(G1SGrainOpts), device, batch_frames, int(clip_to_restricted_range), 0)
     err = C.create_string_buffer(512)
     unequal = C.c_int(0)
-    n = _lib.lib().g1s_check_y4m_files_modes(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(),
-                                             _path(temporal_output), _path(cross_output), C.byref(opts), C.byref(gopts), C.byref(unequal), err,
-                                             len(err))
+    n = _lib.lib().g1s_check_y4m_files_scales(str(source).encode(), str(denoised).encode(), str(table).encode(), str(output).encode(),
+                                              _path(temporal_output), _path(cross_output), _path(scales_output), C.byref(opts), C.byref(gopts),
+                                              C.byref(unequal), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     if unequal.value:

@@ -909,6 +909,28 @@ int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, c
  *      one plane.  EVERY pair has a cross record: no predecessor is needed.  A clip's record is the checked 64-bit sum
  *      (g1s_measure_sum_cross).  Everything is exact within rule 5's bounds.
  *  17. Report.  g1s_format_measure_cross writes plain text; the grammar is at its declaration.
+ * A scales meter (g1s_measure_new_scales) also looks further than 3 samples: how the variance of the residual summed over
+ * 2^k x 2^k boxes grows with k.  White grain grows by 4^k; grain with a correlation length grows faster and then runs
+ * parallel to 4^k; a residual whose low frequencies a denoiser kept grows slower.  For a pair as in rules 1 - 2, every plane
+ * c of size pw x ph and every scale k = 1 .. 5 with L = 2^k:
+ *  18. Boxes.  Boxes are aligned at the plane's origin: box (i, j) holds x in [iL, iL + L), y in [jL, jL + L), for
+ *      i < pw >> k and j < ph >> k.  A box that is not whole is skipped, not clamped; a plane narrower or lower than L has
+ *      no boxes at that scale.
+ *  19. Box sum and box bin.  B = the sum over the box of d(p) of rule 1: |B| <= 4^k (2^B - 1) < 2^22.  C = the sum over the
+ *      box of I(p), rule 2's intensity of each sample as it stands: for chroma the per-sample averageLuma with its own
+ *      + 1 >> 1, then summed -- not a sum of luma samples.  The bin is K = min(C >> (2k + B - 5), 31): the floor of the box
+ *      mean's bin.  There is no rounding: a box of three samples on a bin's lower edge and one sample one below it lies in
+ *      the lower bin.
+ *  20. Sums.  Per plane, scale and bin, over the boxes with that K: n the count (u64), s1 = sum of B (i64), s2 = sum of
+ *      B^2 (u64), every square formed in 64 bits.
+ *  21. Record and bound.  g1s_measure_srecord_t, 11 520 bytes; scale index 0 is k = 1; zeros for the planes the frame does
+ *      not have.  s2 <= 4^k (2^B - 1)^2 pw ph, which at k = 5 stays below 2^64 for every plane the checks admit but a 12-bit
+ *      plane of more than 2^30 samples: on a scales meter such a pair is refused from its geometry alone, before any sample
+ *      is read (G1S_ERR_INVALID, "a scales meter takes 12-bit planes of at most 2^30 samples", sticky like the meter's other
+ *      geometry refusals).  Scale 0 is not stored: it is the plain record.
+ *  22. Sum.  A clip's scale record is the checked 64-bit sum of its pairs' records (g1s_measure_sum_scales): an overflow is
+ *      a refusal, not a wrap.
+ *  23. Report.  g1s_format_measure_scales writes plain text; the grammar is at its declaration.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes) and a small summing launch, on the meter's own stream.  Errors are sticky (g1s_measure_last_error). */
 typedef struct {
@@ -1089,6 +1111,67 @@ int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const 
 int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
                                   const char *out_xreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err,
                                   size_t cap);
+
+/* -- the scales meter (rules 18 - 23 above) -- */
+typedef struct {
+  uint64_t n[3][5][32]; /* [plane][k - 1][bin] */
+  int64_t s1[3][5][32];
+  uint64_t s2[3][5][32];
+} g1s_measure_srecord_t;
+/* g1s_measure_new_modes(bit_depth, opts, modes) with the same refusals in the same order (bit 4 and above are unknown mode
+ * bits here too), plus the scale record for every pair: one km_measure_s launch a plane class and one summing launch a batch,
+ * behind the meter's other launches on its stream.  g1s_measure_opts_t is not extended.  A scale job reads only the planes of
+ * its own pair: the lifetime rules are those of the meter's modes.  A pair with a 12-bit plane of more than 2^30 samples is
+ * refused (rule 21).  A meter not made by this call launches what it launched and returns the bytes it returned. */
+g1s_measure_t *g1s_measure_new_scales(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes);
+/* As g1s_measure_finish_cross, for the scale records: one per pair since the last hand-over, in order.  G1S_ERR_CAPACITY is
+ * not sticky and the records stay.  Each of the four finish calls flushes; each keeps the others' records until they are
+ * fetched.  On a meter not made by g1s_measure_new_scales: G1S_ERR_INVALID, the text names g1s_measure_new_scales; not
+ * sticky, the meter goes on working. */
+int g1s_measure_finish_scales(g1s_measure_t *, g1s_measure_srecord_t *per_pair, size_t cap, size_t *n_out);
+/* Rule 22 (host only, needs no device): *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_measure_sum_scales(const g1s_measure_srecord_t *recs, size_t n, g1s_measure_srecord_t *total);
+/* Rule 23 (host only): plain text from a clip's PLAIN record `total` (rule 6) and its SCALE record `stotal` of `frames`
+ * frames.  synth == NULL and ssynth == NULL: one value column; both given: two (total = source - denoised, synth =
+ * rendered - denoised); one of them alone is G1S_ERR_INVALID.  Every value is formed in f64 from the exact integers in
+ * exactly the order written here, without fused multiply-add, and printed "%.4f"; "-" where undefined.
+ *   grainscales1
+ *   frames N bit_depth B planes P
+ *   plane c                                   for c in 0 .. P - 1; with frames = 0 nothing stands under it
+ *   scale k boxes m sigma gain [sigma' gain'] k = 1 .. 5; m = the u64 sum over the bins of n[k] (total's);
+ *                                             sigma = sqrt(max(V_k, 0)) / 2^k, "-" when the column's own m = 0;
+ *                                             gain = V_k / (4^k * V_0), "-" when the column's m = 0, its m_0 = 0 or V_0 <= 0
+ *   sbin k j n sigma [sigma']                 after the five scale lines, k = 1 .. 5 and within k the bins j with n > 0 (n is
+ *                                             total's): mean = (double)s1 / (double)n, sigma = sqrt(max((double)s2 / (double)n -
+ *                                             mean * mean, 0)) / 2^k; sigma' is "-" where the second column's n is 0
+ *   gain_ratio k v                            (two columns) after the sbin lines, k = 1 .. 5: gain' / gain, "-" unless both
+ *                                             exist and gain > 0
+ * The pooled variance: V_k = S / (double)m, S the sum in bin order over the bins j with n_j > 0 of
+ * (double)s2_j - ((double)s1_j * (double)s1_j) / (double)n_j: the WITHIN-bin variance, so that a bias that differs from bin to
+ * bin does not read as coarse grain.  V_0 and m_0 are the same expressions over n, s1, s2 of the plane in the plain record.
+ * What the numbers mean: sigma is the per-sample-equivalent size of the grain at that scale; white grain reads the same at
+ * every scale and its gain is 1.  Correlated grain has a gain above 1 that levels off once the box is wider than the
+ * correlation (a 3 x 3 box filter of white noise: ((9 L - 8) / (3 L))^2 -- 2.78, 5.44, 7.11, 8.03, 8.51).  A gain that is still
+ * rising at k = 4 and 5 where the rendered column has levelled off is grain coarser than a lag-3 table can say: measure at a
+ * lower resolution.  A gain below the rendered column's, most at small k, is a denoiser that kept the coarse part of the grain
+ * in its "clean" frame.  The rendered column's largest scales are statistics of ONE usable 64 x 64 template a frame -- a luma
+ * box at k = 5 is exactly one grain block -- so that column needs a clip, not a frame, to settle.  There is no verdict and no
+ * threshold.  Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for nplanes other than 1 and 3). */
+long g1s_format_measure_scales(const g1s_measure_record_t *total, const g1s_measure_srecord_t *stotal, const g1s_measure_record_t *synth,
+                               const g1s_measure_srecord_t *ssynth, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, char *buf, size_t cap);
+/* HIP-event time of km_measure_s and its summing launch in the batches g1s_measure_set_timing had timed, milliseconds, and
+ * the scale records they made.  tools/bench_measure.py --scales. */
+int g1s_measure_scales_timing(g1s_measure_t *, double *ms_kernel, uint64_t *pairs);
+/* g1s_measure_y4m_files_modes that also writes the clip's scale report to out_sreport (one record a frame).
+ * out_sreport == NULL is exactly g1s_measure_y4m_files_modes. */
+int64_t g1s_measure_y4m_files_scales(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
+                                     const char *out_sreport, const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap);
+/* g1s_check_y4m_files_modes that also writes the two-column scale report: total = source - denoised, synth = rendered -
+ * denoised.  Nothing extra crosses PCIe and the rendered frame stays on the device.  out_sreport == NULL is exactly
+ * g1s_check_y4m_files_modes. */
+int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
+                                   const char *out_xreport, const char *out_sreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts,
+                                   int *unequal, char *err, size_t cap);
 
 /* ---- decoder surfaces: NV12, P010 / P012 / P016 and MSB-aligned planes, to and from g1s_frame_t on the device ----
  * A hardware decoder (and an encoder on the same device) does not hold planar frames with the sample in the low bits: it

@@ -18,7 +18,14 @@ tools/bench_measure.py --cross [repeats]: a plain, a temporal and a cross meter 
 one process, in the order plain, temporal, cross, twice.  Per format one JSON line: km_measure_x's time a cross record (the
 launch and its summing launch), the plain CHROMA launch (km_measure on Cb and Cr) and km_measure_t's CHROMA launch -- the
 yardstick: the cross kernel does 75 lag products a chroma sample against its 50 and reads the full-resolution luma of both
-frames in addition -- their ratios, and the cross kernel's bytes (both frames of the pair, once) / time."""
+frames in addition -- their ratios, and the cross kernel's bytes (both frames of the pair, once) / time.
+
+tools/bench_measure.py --scales [repeats]: a plain and a scales meter on both formats, in one process, in the order plain,
+scales, twice, on the plane-distinct content, on a clean frame of one intensity (one key a round of the bin sums: the best case)
+and on a clean luma of random samples (the 2 x 2 boxes of a round spread over many bins: the worst).  Per format and content one
+JSON line: km_measure's time a frame from the plain meter (the yardstick) and from the scales meter's own ordinary launches,
+km_measure_s's time a scale record (its launches and the summing launch), their ratio, and the scale kernel's bytes (both
+frames of the pair once, and for chroma the clean luma once more) / time."""
 import json, os, statistics, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +37,7 @@ from grav1synth_amd.measure import GrainMeter
 from tests import content as CT
 
 assert torch.cuda.is_available(), "bench_measure.py needs a GPU"
-argv = [a for a in sys.argv[1:] if a not in ("--temporal", "--cross")]
+argv = [a for a in sys.argv[1:] if a not in ("--temporal", "--cross", "--scales")]
 repeats = int(argv[0]) if argv else 7
 BATCH, PEAK = 32, 8e12
 
@@ -134,6 +141,65 @@ def cross_bench():
         out["km_measure_x_fraction_of_8TBps"] = 2 * frame_bytes / (med(us["cross"]) * 1e-6) / PEAK
         print(json.dumps(out), flush=True)
 
+
+def scales_bench():
+    for name, (w, h, bd) in (("3840x2160 10-bit 4:2:0", (3840, 2160, 10)), ("1920x1080 8-bit 4:2:0", (1920, 1080, 8))):
+        pairs = [CT.make_frames("distinct", w, h, bd, 1, 1, frame=k) for k in range(4)]
+        for content in ("distinct", "one intensity", "random luma"):
+            noisy, clean = [], []
+            for k, (src, den) in enumerate(pairs):
+                if content != "distinct":  # the same residuals on another clean frame
+                    if content == "one intensity":
+                        other = [np.full(p.shape, (100 + 20 * c) << (bd - 8), p.dtype) for c, p in enumerate(den)]
+                    else:
+                        other = [np.random.default_rng([k, c]).integers(0, 1 << bd, p.shape).astype(p.dtype) for c, p in enumerate(den)]
+                    src = [np.clip(f.astype(np.int64) + s.astype(np.int64) - d.astype(np.int64), 0, (1 << bd) - 1).astype(d.dtype)
+                           for f, s, d in zip(other, src, den)]
+                    den = other
+                noisy.append(dev(src)), clean.append(dev(den))
+            torch.cuda.synchronize()
+            bps = 1 if bd == 8 else 2
+            frame_bytes = sum(p.numel() for p in noisy[0]) * bps
+            luma_bytes = noisy[0][0].numel() * bps
+            us = {"plain": [], "plain_in_scales_meter": [], "scales": []}
+            for rounds in range(2):
+                for scales in (False, True):
+                    m = GrainMeter(bd, batch_frames=BATCH, scales=scales)
+
+                    def batch():
+                        for k in range(BATCH):
+                            m.measure(noisy[k % 4], clean[k % 4], 1, 1)
+                        m.finish()
+                        if scales:
+                            m.finish_scales()
+
+                    batch()  # warm-up: code objects, buffers
+                    for _ in range(repeats):
+                        a0, n0 = m.kernel_times(True)
+                        s0, q0 = m.scales_kernel_times()
+                        batch()
+                        a1, n1 = m.kernel_times(False)
+                        s1, q1 = m.scales_kernel_times()
+                        assert n1 - n0 == BATCH
+                        us["plain_in_scales_meter" if scales else "plain"].append((a1 - a0) * 1e3 / BATCH)
+                        if scales:
+                            assert q1 - q0 == BATCH
+                            us["scales"].append((s1 - s0) * 1e3 / BATCH)
+                    m.close()
+            med = statistics.median
+            out = {"format": name, "content": content, "batch_frames": BATCH, "repeats": repeats, "order": "plain, scales, twice"}
+            for key, v in us.items():
+                out[f"{key}_us_median"], out[f"{key}_us_min"], out[f"{key}_us_max"] = med(v), min(v), max(v)
+            out["ratio_km_measure_s_over_km_measure"] = med(us["scales"]) / med(us["plain"])
+            out["km_measure_s_bytes_per_record"] = 2 * frame_bytes + luma_bytes
+            out["km_measure_s_TBps"] = (2 * frame_bytes + luma_bytes) / (med(us["scales"]) * 1e-6) / 1e12
+            out["km_measure_s_fraction_of_8TBps"] = (2 * frame_bytes + luma_bytes) / (med(us["scales"]) * 1e-6) / PEAK
+            print(json.dumps(out), flush=True)
+
+
+if "--scales" in sys.argv[1:]:
+    scales_bench()
+    sys.exit(0)
 
 if "--cross" in sys.argv[1:]:
     cross_bench()
