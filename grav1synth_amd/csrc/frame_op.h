@@ -1,7 +1,8 @@
 // frame_op.h -- the host scaffold the frame operations share (render: grain.hip, denoise: denoise.hip, estimate:
 // estimate.hip, measure: measure.hip; the generator, engine.hip, takes the owners and the addressing predicate).  Host code only.  The first part -- plane geometry, the two layouts of a
 // frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP and builds with a host compiler
-// alone; the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro and the
+// alone (measure_report.cpp, which needs a chroma plane's size and nothing else of this, has it as a local helper and does
+// not include this file); the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro and the
 // base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
 #pragma once
 #include <stdint.h>

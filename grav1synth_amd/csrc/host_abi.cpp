@@ -1,7 +1,7 @@
 // host_abi.cpp -- the part of the C ABI (include/g1s_diff.h) that needs no device: the worker pools, the record accessors,
 // the messages of the frame-shard protocol and their ordered merge, the stand-alone fold handle, latest-state blobs from
-// records, the .tbl calls, the sum and the report of `measure`'s scale records and the thread's global error text.  Builds with a host compiler; what takes a g1s_diff_t * is
-// in engine.hip.
+// records, the .tbl calls and the thread's global error text.  Builds with a host compiler; what takes a g1s_diff_t * is
+// in engine.hip, and what `measure` does with its records on the host is in measure_report.cpp.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -548,124 +548,6 @@ long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uin
                              size_t cap) {
   if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
   const std::string s = g1s_nl::report(*total, frames, bit_depth, nplanes, min_count);
-  if (s.size() > cap) return G1S_ERR_CAPACITY;
-  std::memcpy(buf, s.data(), s.size());
-  return (long)s.size();
-}
-
-}  // extern "C"
-
-// the scales meter, rules 22 and 23 of `measure`: what is done with the records needs no device
-namespace {
-
-struct ScaleColumn {
-  bool has_sigma[5], has_gain[5];
-  double sigma[5], gain[5];
-};
-
-// S / m of rule 23 over `bins` bins (n, s1, s2 of one plane and scale, or of a plane of the plain record); false: m = 0
-bool pooled_variance(const uint64_t *n, const int64_t *s1, const uint64_t *s2, uint64_t *m_out, double *v) {
-  uint64_t m = 0;
-  double S = 0.0;
-  for (int j = 0; j < 32; ++j) {
-    if (!n[j]) continue;
-    m += n[j];
-    const double sq = (double)s1[j] * (double)s1[j];
-    const double part = sq / (double)n[j];
-    S = S + ((double)s2[j] - part);
-  }
-  *m_out = m;
-  if (m) *v = S / (double)m;
-  return m != 0;
-}
-
-ScaleColumn scale_column(const g1s_measure_record_t &t, const g1s_measure_srecord_t &s, int c) {
-  ScaleColumn col{};
-  uint64_t m0 = 0, m = 0;
-  double v0 = 0.0, v = 0.0;
-  const bool has0 = pooled_variance(t.n[c], t.s1[c], t.s2[c], &m0, &v0);
-  for (int k = 0; k < 5; ++k) {
-    col.has_sigma[k] = pooled_variance(s.n[c][k], s.s1[c][k], s.s2[c][k], &m, &v);
-    if (!col.has_sigma[k]) continue;
-    const double L = (double)(2u << k);
-    col.sigma[k] = std::sqrt(v > 0.0 ? v : 0.0) / L;
-    col.has_gain[k] = has0 && v0 > 0.0;
-    if (col.has_gain[k]) {
-      const double den = (L * L) * v0;
-      col.gain[k] = v / den;
-    }
-  }
-  return col;
-}
-
-std::string scale_value(bool defined, double v) {
-  if (!defined) return "-";
-  char s[64];
-  snprintf(s, sizeof s, "%.4f", v);
-  return s;
-}
-
-}  // namespace
-
-extern "C" {
-
-int g1s_measure_sum_scales(const g1s_measure_srecord_t *recs, size_t n, g1s_measure_srecord_t *total) {
-  if (!total || (n && !recs)) return G1S_ERR_INVALID;
-  g1s_measure_srecord_t t;
-  std::memset(&t, 0, sizeof t);
-  bool ok = true;
-  for (size_t f = 0; f < n; ++f)
-    for (int c = 0; c < 3; ++c)
-      for (int k = 0; k < 5; ++k)
-        for (int j = 0; j < 32; ++j)
-          ok = !__builtin_add_overflow(t.n[c][k][j], recs[f].n[c][k][j], &t.n[c][k][j]) &&
-               !__builtin_add_overflow(t.s1[c][k][j], recs[f].s1[c][k][j], &t.s1[c][k][j]) &&
-               !__builtin_add_overflow(t.s2[c][k][j], recs[f].s2[c][k][j], &t.s2[c][k][j]) && ok;
-  if (!ok) return G1S_ERR_INVALID;
-  *total = t;
-  return G1S_OK;
-}
-
-long g1s_format_measure_scales(const g1s_measure_record_t *total, const g1s_measure_srecord_t *stotal, const g1s_measure_record_t *synth,
-                               const g1s_measure_srecord_t *ssynth, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, char *buf, size_t cap) {
-  if (!total || !stotal || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (synth == nullptr) != (ssynth == nullptr)) return G1S_ERR_INVALID;
-  std::string s = "grainscales1\n";
-  s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
-  for (int c = 0; c < (int)nplanes; ++c) {
-    s += "plane " + std::to_string(c) + "\n";
-    if (!frames) continue;
-    const ScaleColumn a = scale_column(*total, *stotal, c);
-    ScaleColumn b{};
-    if (synth) b = scale_column(*synth, *ssynth, c);
-    for (int k = 0; k < 5; ++k) {
-      uint64_t m = 0;
-      for (int j = 0; j < 32; ++j) m += stotal->n[c][k][j];
-      s += "scale " + std::to_string(k + 1) + " boxes " + std::to_string(m) + " " + scale_value(a.has_sigma[k], a.sigma[k]) + " " +
-           scale_value(a.has_gain[k], a.gain[k]);
-      if (synth) s += " " + scale_value(b.has_sigma[k], b.sigma[k]) + " " + scale_value(b.has_gain[k], b.gain[k]);
-      s += "\n";
-    }
-    // a bin's own sigma at a scale
-    auto bin_sigma = [](const g1s_measure_srecord_t &r, int c_, int k, int j) {
-      const double n = (double)r.n[c_][k][j];
-      const double mean = (double)r.s1[c_][k][j] / n;
-      const double var = (double)r.s2[c_][k][j] / n - mean * mean;
-      return std::sqrt(var > 0.0 ? var : 0.0) / (double)(2u << k);
-    };
-    for (int k = 0; k < 5; ++k)
-      for (int j = 0; j < 32; ++j) {
-        if (!stotal->n[c][k][j]) continue;
-        s += "sbin " + std::to_string(k + 1) + " " + std::to_string(j) + " " + std::to_string(stotal->n[c][k][j]) + " " +
-             scale_value(true, bin_sigma(*stotal, c, k, j));
-        if (synth) s += " " + scale_value(ssynth->n[c][k][j] != 0, ssynth->n[c][k][j] ? bin_sigma(*ssynth, c, k, j) : 0.0);
-        s += "\n";
-      }
-    if (synth)
-      for (int k = 0; k < 5; ++k) {
-        const bool both = a.has_gain[k] && b.has_gain[k] && a.gain[k] > 0.0;
-        s += "gain_ratio " + std::to_string(k + 1) + " " + scale_value(both, both ? b.gain[k] / a.gain[k] : 0.0) + "\n";
-      }
-  }
   if (s.size() > cap) return G1S_ERR_CAPACITY;
   std::memcpy(buf, s.data(), s.size());
   return (long)s.size();

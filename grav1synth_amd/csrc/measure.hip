@@ -11,9 +11,15 @@
 //                    (and the clean luma a chroma sample is binned by).  The workgroup's partial record goes out with
 //                    plain stores.
 //   km_tail          a workgroup per (plane, frame pair) sums the partial records into the pair's record.
-// A temporal meter (rules 7 - 11) runs km_measure_t and km_tail_t behind them: they stand below km_tail with their own notes.
-// A cross meter (rules 12 - 17) runs km_measure_x and km_tail_t behind those: below km_tail_t.
+// A temporal meter (rules 7 - 11) runs km_measure_t and km_tail<4> behind them: they stand below km_tail with their own notes.
+// A cross meter (rules 12 - 17) runs km_measure_x and km_tail<4> behind those: below km_measure_t.
 // A scales meter (rules 18 - 23) runs km_measure_s and km_tail_s behind those: below km_measure_x, with their own notes.
+// What the kernels share stands in front of them: the parameters of a launch over a plane class (ClassParams) and the bin of a
+// sample (clean_bin); km_tail is one template for the plain and the temporal layout.  lag_pass, the 5 x 5 row loop of
+// km_measure_x's three pairings, stands before km_measure_t, which has the same loop written out: calling lag_pass from it,
+// and one epilogue helper for the waves' accumulators, gave km_measure, km_measure_s and km_measure_t other code than what
+// was measured before, and timing rows above it (profiles/measure_refactor.txt).  The kernels compile to that code again.  The host engine below them keeps a RecordLane a record kind.  What is done
+// with the records on the host -- the sums and the four reports -- needs no device and is in measure_report.cpp.
 //
 // The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
 //   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
@@ -27,11 +33,11 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/g1s_diff.h"
@@ -47,21 +53,26 @@ constexpr int kWaves = 4, kThreads = 64 * kWaves, kRowsPerWave = kTH / kWaves;
 constexpr int kBins = 32, kLags = 25;
 constexpr int kEntries = 3 * kBins + kLags;  // a partial record: n[32], s1[32], s2[32], r[25]
 constexpr int kNoBin = 0xff;
-constexpr int kTailGroups = 4;
+constexpr int kTailThreads = 512;
 static_assert(kRowsPerWave <= 127, "a 32-bit lag sum holds 127 products of 12-bit residuals");
+static_assert(sizeof(g1s_measure_record_t) == 8 * 3 * kEntries, "km_tail<3> writes the record as 64-bit words");
 
 struct MeasureJob {
   const uint8_t *a[3], *b[3];
   uint32_t a_stride[3], b_stride[3];  // bytes
 };
 
-struct MeasureParams {
-  const MeasureJob *jobs;
-  unsigned long long *partials;  // [pair][tiles_frame][kEntries]
-  int pw, ph, tiles_x;           // the class's plane size
+// A launch over a plane class (km_measure, km_measure_t; km_measure_s has ScaleParams, the same with the luma height): luma
+// alone, or both chroma planes as grid.y.  A workgroup takes a unit of a plane -- a tile, or km_measure_s's strip of tiles --
+// for job blockIdx.z.
+template <class Job>
+struct ClassParams {
+  const Job *jobs;
+  unsigned long long *partials;  // [job][units_frame][the kernel's entries]
+  int pw, ph, units_x;           // the class's plane size, the units across it
   int plane0;                    // first plane of the class: 0 luma, 1 chroma
   int W, xdec, ydec, shift;      // luma width, chroma decimation, B - 5
-  uint32_t tiles_frame, tile_base, tiles_plane;
+  uint32_t units_frame, unit_base, units_plane;
 };
 
 struct TailParams {
@@ -76,15 +87,31 @@ __device__ __forceinline__ int sample(const uint8_t *plane, uint32_t stride, int
   return BPS == 2 ? (int)reinterpret_cast<const uint16_t *>(row)[x] : (int)row[x];
 }
 
+// (clean_bin takes a launch's parameters as values, not as the struct: a kernel that hands the address of its parameter
+// struct to a function, a member function included, loses the compiler's knowledge that the planes are global memory, and
+// its sample loads become flat loads.)
+// the bin of the sample at (x, y) of plane c whose clean value is b: by the clean frame's luma (py, W samples wide), for
+// chroma its averageLuma
 template <int BPS>
-__global__ __launch_bounds__(kThreads) void km_measure(MeasureParams p) {
+__device__ __forceinline__ int clean_bin(int c, int b, const uint8_t *py, uint32_t sy, int x, int y, int W, int xdec, int ydec, int shift) {
+  int I = b;
+  if (c) {
+    const int xs = x << xdec, ys = y << ydec;
+    I = sample<BPS>(py, sy, xs, ys);
+    if (xdec) I = (I + sample<BPS>(py, sy, min(xs + 1, W - 1), ys) + 1) >> 1;
+  }
+  return min(I >> shift, kBins - 1);  // (a sample above the depth's maximum: the caller's error, not a wild index)
+}
+
+template <int BPS>
+__global__ __launch_bounds__(kThreads) void km_measure(ClassParams<MeasureJob> p) {
   __shared__ int16_t s_d[kLH * kLW];
   __shared__ uint8_t s_bin[kTH * kTW];
   __shared__ unsigned long long s_acc[kWaves][kEntries];  // (two's complement: the signed sums are added as unsigned)
   const MeasureJob &job = p.jobs[blockIdx.z];
   const int c = p.plane0 + (int)blockIdx.y;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const int ty = (int)blockIdx.x / p.units_x, tx = (int)blockIdx.x - ty * p.units_x;
   const int x0 = tx * kTW, y0 = ty * kTH;
   const uint8_t *pa = job.a[c], *pb = job.b[c], *py = job.b[0];
   const uint32_t sa = job.a_stride[c], sb = job.b_stride[c], sy = job.b_stride[0];
@@ -100,15 +127,7 @@ __global__ __launch_bounds__(kThreads) void km_measure(MeasureParams p) {
     if (inside) {
       const int b = sample<BPS>(pb, sb, x, y);
       d = sample<BPS>(pa, sa, x, y) - b;
-      if (own) {
-        int I = b;
-        if (c) {  // averageLuma of the clean frame
-          const int xs = x << p.xdec, ys = y << p.ydec;
-          I = sample<BPS>(py, sy, xs, ys);
-          if (p.xdec) I = (I + sample<BPS>(py, sy, min(xs + 1, p.W - 1), ys) + 1) >> 1;
-        }
-        bin = min(I >> p.shift, kBins - 1);  // (a sample above the depth's maximum: the caller's error, not a wild index)
-      }
+      if (own) bin = clean_bin<BPS>(c, b, py, sy, x, y, p.W, p.xdec, p.ydec, p.shift);
     }
     s_d[i] = (int16_t)d;
     if (own) s_bin[(ly - kHalo) * kTW + (lx - kHalo)] = (uint8_t)bin;
@@ -179,27 +198,33 @@ __global__ __launch_bounds__(kThreads) void km_measure(MeasureParams p) {
     unsigned long long t = 0;
 #pragma unroll
     for (int v = 0; v < kWaves; ++v) t += s_acc[v][tid];
-    const size_t at = (size_t)blockIdx.z * p.tiles_frame + p.tile_base + (size_t)blockIdx.y * p.tiles_plane + blockIdx.x;
+    const size_t at = (size_t)blockIdx.z * p.units_frame + p.unit_base + (size_t)blockIdx.y * p.units_plane + blockIdx.x;
     p.partials[at * kEntries + tid] = t;
   }
 }
 
-// the pair's record from its workgroups' partial records: grid (plane, pair)
-__global__ __launch_bounds__(128 * kTailGroups) void km_tail(TailParams p) {
-  __shared__ unsigned long long s_sum[kTailGroups][128];
-  const int c = (int)blockIdx.x, i = (int)threadIdx.x & 127, g = (int)threadIdx.x >> 7;
-  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kEntries;
+// The job's record from its workgroups' partial records: grid (plane, job).  FIELDS bin fields of 32 and 25 offsets a
+// partial record and a plane of the record: km_tail<3> writes g1s_measure_record_t (n, s1, s2, r) with 4 groups of 128
+// threads, km_tail<4> g1s_measure_trecord_t (n, x, u, v, c) with 2 groups of 256; a thread of a group an entry, a group
+// every GROUPS-th partial record.
+template <int FIELDS>
+__global__ __launch_bounds__(kTailThreads) void km_tail(TailParams p) {
+  constexpr int N = FIELDS * kBins + kLags, WIDTH = N <= 128 ? 128 : 256, GROUPS = kTailThreads / WIDTH;
+  static_assert(N <= WIDTH, "km_tail gives an entry a thread of a group");
+  __shared__ unsigned long long s_sum[GROUPS][WIDTH];
+  const int c = (int)blockIdx.x, i = (int)threadIdx.x % WIDTH, g = (int)threadIdx.x / WIDTH;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * N;
   unsigned long long t = 0;
-  if (i < kEntries)
-    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += kTailGroups) t += src[(size_t)k * kEntries + i];
+  if (i < N)
+    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += GROUPS) t += src[(size_t)k * N + i];
   s_sum[g][i] = t;
   __syncthreads();
-  if (g == 0 && i < kEntries) {
-    for (int v = 1; v < kTailGroups; ++v) t += s_sum[v][i];
-    // g1s_measure_record_t as 64-bit words: n[3][32], s1[3][32], s2[3][32], r[3][25]
-    unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_record_t) / 8);
-    const int field = i < 3 * kBins ? i / kBins : 3, k = i - field * kBins;
-    rec[field < 3 ? field * 3 * kBins + c * kBins + k : 9 * kBins + c * kLags + k] = t;
+  if (g == 0 && i < N) {
+    for (int v = 1; v < GROUPS; ++v) t += s_sum[v][i];
+    // the record as 64-bit words: the bin fields [3][32] one after the other, then the offsets [3][25]
+    unsigned long long *rec = p.records + (size_t)blockIdx.y * (3 * N);
+    const int field = i < FIELDS * kBins ? i / kBins : FIELDS, k = i - field * kBins;
+    rec[field < FIELDS ? field * 3 * kBins + c * kBins + k : 3 * FIELDS * kBins + c * kLags + k] = t;
   }
 }
 
@@ -209,7 +234,7 @@ __global__ __launch_bounds__(128 * kTailGroups) void km_tail(TailParams p) {
 //                      (zeros outside the plane: a skipped product is a product with 0); the tile's bins as bytes, from
 //                      pair t's clean frame; the waves' accumulators.  A wave walks its 32 rows, a lane a column, with the
 //                      5 x 5 window of d_{t-1} in registers: 5 LDS reads of d_{t-1} and 25 multiply-adds a sample.
-//   km_tail_t          km_tail for the partial records of km_measure_t.
+//   km_tail<4>         km_tail for the partial records of km_measure_t.
 // The 32-bit sums follow km_measure's schedule: a lane's 25 lag sums and its bin sums (n, x, u, v) take one product a row
 // for the wave's 32 rows at the most (below 2^29 in size) and go on in 64 bits through wave_sum_wide, which carries the
 // signed x and c as it carries km_measure's lag sums.
@@ -217,26 +242,75 @@ constexpr int kTHalo = 2, kTWin = 2 * kTHalo + 1;
 constexpr int kPW = kTW + 2 * kTHalo, kPH = kTH + 2 * kTHalo;  // the LDS tile of d_{t-1}
 constexpr int kTLags = kTWin * kTWin;
 constexpr int kTEntries = 4 * kBins + kTLags;  // a partial temporal record: n[32], x[32], u[32], v[32], c[25]
-constexpr int kTTailWidth = 256, kTTailGroups = 2;
 static_assert(kRowsPerWave <= 127, "a 32-bit sum of km_measure_t holds 127 products of 12-bit residuals, one a row");
-static_assert(kTLags == 25 && kTEntries <= kTTailWidth, "g1s_measure_trecord_t has 25 offsets; km_tail_t gives an entry a thread");
-static_assert(sizeof(g1s_measure_trecord_t) == 8 * 3 * kTEntries, "km_tail_t writes the record as 64-bit words");
+static_assert(kTLags == kLags, "g1s_measure_trecord_t has 25 offsets, as km_tail takes them");
+static_assert(sizeof(g1s_measure_trecord_t) == 8 * 3 * kTEntries, "km_tail<4> writes the record as 64-bit words");
 
 struct TemporalJob {
   MeasureJob cur, prev;  // pair t and pair t - 1 of the run
 };
 
-struct TemporalParams {
-  const TemporalJob *jobs;
-  unsigned long long *partials;  // [job][tiles_frame][kTEntries]
-  int pw, ph, tiles_x;
-  int plane0;
-  int W, xdec, ydec, shift;
-  uint32_t tiles_frame, tile_base, tiles_plane;
-};
+// The row loop of km_measure_x's pairings (km_measure_t below has it written out), over the wave's rows: a = the tile's own sample, from a plane
+// stored with the halo (HALO_A, kPW wide) or without (kTW wide); b = the 5 x 5 window round it in a plane with the halo.
+// Into `mine`: the bin sums n, x = sum a b, u = sum a^2, v = sum b^2 at offset (0, 0), then the 25 lag sums.
+template <bool HALO_A>
+__device__ __forceinline__ void lag_pass(const int16_t *s_a, const int16_t *s_b, const uint8_t *s_bin, unsigned long long *mine, int row0, int rows,
+                                         int lane) {
+  int acc[kTLags];
+#pragma unroll
+  for (int i = 0; i < kTLags; ++i) acc[i] = 0;
+  // the window: rows y - 2 .. y + 2 of b, columns x - 2 .. x + 2 (LDS row ly = tile row + 2 + dy, column lx = lane + 2 + dx)
+  int w[kTWin][kTWin];
+#pragma unroll
+  for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+    for (int k = 0; k < kTWin; ++k) w[q + 1][k] = s_b[(row0 + q) * kPW + lane + k];
+  int cur = -1, bn = 0, bx = 0, bu = 0, bv = 0;  // the bin the lane's column is in and its sums so far (cur < 0: none)
+  auto hand_on = [&](bool go) __attribute__((always_inline)) {
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
+    while (todo) {
+      const int b = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(todo));
+      const bool m = go && cur == b;
+      todo &= ~__builtin_amdgcn_ballot_w64(m);
+      const int n = wave_sum(m ? bn : 0);
+      const long long x = wave_sum_wide(m ? bx : 0), u = wave_sum_wide(m ? bu : 0), v = wave_sum_wide(m ? bv : 0);
+      if (lane == 0) {
+        mine[b] += (unsigned long long)(long long)n;
+        mine[kBins + b] += (unsigned long long)x;
+        mine[2 * kBins + b] += (unsigned long long)u;
+        mine[3 * kBins + b] += (unsigned long long)v;
+      }
+      if (m) cur = -1, bn = bx = bu = bv = 0;
+    }
+  };
+  for (int r = 0; r < rows; ++r) {
+#pragma unroll
+    for (int q = 0; q < kTWin - 1; ++q)
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) w[q][k] = w[q + 1][k];
+#pragma unroll
+    for (int k = 0; k < kTWin; ++k) w[kTWin - 1][k] = s_b[(row0 + r + kTWin - 1) * kPW + lane + k];
+    const int d = HALO_A ? (int)s_a[(row0 + r + kTHalo) * kPW + lane + kTHalo] : (int)s_a[(row0 + r) * kTW + lane];
+#pragma unroll
+    for (int q = 0; q < kTWin; ++q)
+#pragma unroll
+      for (int k = 0; k < kTWin; ++k) acc[q * kTWin + k] += __mul24(d, w[q][k]);
+    const int e = w[kTHalo][kTHalo];
+    const int k = s_bin[(row0 + r) * kTW + lane];
+    const bool change = cur >= 0 && k != cur;
+    if (__builtin_amdgcn_ballot_w64(change)) hand_on(change);
+    if (k != kNoBin) cur = k, bn += 1, bx += __mul24(d, e), bu += __mul24(d, d), bv += __mul24(e, e);
+  }
+  hand_on(cur >= 0);
+#pragma unroll
+  for (int i = 0; i < kTLags; ++i) {
+    const long long t = wave_sum_wide(acc[i]);
+    if (lane == 0) mine[4 * kBins + i] = (unsigned long long)t;
+  }
+}
 
 template <int BPS>
-__global__ __launch_bounds__(kThreads) void km_measure_t(TemporalParams p) {
+__global__ __launch_bounds__(kThreads) void km_measure_t(ClassParams<TemporalJob> p) {
   __shared__ int16_t s_d[kTH * kTW];
   __shared__ int16_t s_p[kPH * kPW];
   __shared__ uint8_t s_bin[kTH * kTW];
@@ -244,7 +318,7 @@ __global__ __launch_bounds__(kThreads) void km_measure_t(TemporalParams p) {
   const TemporalJob &job = p.jobs[blockIdx.z];
   const int c = p.plane0 + (int)blockIdx.y;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
+  const int ty = (int)blockIdx.x / p.units_x, tx = (int)blockIdx.x - ty * p.units_x;
   const int x0 = tx * kTW, y0 = ty * kTH;
   const uint8_t *pa = job.cur.a[c], *pb = job.cur.b[c], *py = job.cur.b[0], *qa = job.prev.a[c], *qb = job.prev.b[c];
   const uint32_t sa = job.cur.a_stride[c], sb = job.cur.b_stride[c], sy = job.cur.b_stride[0];
@@ -263,13 +337,7 @@ __global__ __launch_bounds__(kThreads) void km_measure_t(TemporalParams p) {
       if (own) {
         const int b = sample<BPS>(pb, sb, x, y);
         d = sample<BPS>(pa, sa, x, y) - b;
-        int I = b;
-        if (c) {  // averageLuma of pair t's clean frame
-          const int xs = x << p.xdec, ys = y << p.ydec;
-          I = sample<BPS>(py, sy, xs, ys);
-          if (p.xdec) I = (I + sample<BPS>(py, sy, min(xs + 1, p.W - 1), ys) + 1) >> 1;
-        }
-        bin = min(I >> p.shift, kBins - 1);
+        bin = clean_bin<BPS>(c, b, py, sy, x, y, p.W, p.xdec, p.ydec, p.shift);  // (pair t's clean frame)
       }
     }
     s_p[i] = (int16_t)e;
@@ -341,27 +409,8 @@ __global__ __launch_bounds__(kThreads) void km_measure_t(TemporalParams p) {
     unsigned long long t = 0;
 #pragma unroll
     for (int v = 0; v < kWaves; ++v) t += s_acc[v][tid];
-    const size_t at = (size_t)blockIdx.z * p.tiles_frame + p.tile_base + (size_t)blockIdx.y * p.tiles_plane + blockIdx.x;
+    const size_t at = (size_t)blockIdx.z * p.units_frame + p.unit_base + (size_t)blockIdx.y * p.units_plane + blockIdx.x;
     p.partials[at * kTEntries + tid] = t;
-  }
-}
-
-// the job's temporal record from its workgroups' partial records: grid (plane, job)
-__global__ __launch_bounds__(kTTailWidth * kTTailGroups) void km_tail_t(TailParams p) {
-  __shared__ unsigned long long s_sum[kTTailGroups][kTTailWidth];
-  const int c = (int)blockIdx.x, i = (int)threadIdx.x % kTTailWidth, g = (int)threadIdx.x / kTTailWidth;
-  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kTEntries;
-  unsigned long long t = 0;
-  if (i < kTEntries)
-    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += kTTailGroups) t += src[(size_t)k * kTEntries + i];
-  s_sum[g][i] = t;
-  __syncthreads();
-  if (g == 0 && i < kTEntries) {
-    for (int v = 1; v < kTTailGroups; ++v) t += s_sum[v][i];
-    // g1s_measure_trecord_t as 64-bit words: n[3][32], x[3][32], u[3][32], v[3][32], c[3][25]
-    unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_trecord_t) / 8);
-    const int field = i < 4 * kBins ? i / kBins : 4, k = i - field * kBins;
-    rec[field < 4 ? field * 3 * kBins + c * kBins + k : 12 * kBins + c * kTLags + k] = t;
   }
 }
 
@@ -372,14 +421,14 @@ __global__ __launch_bounds__(kTTailWidth * kTTailGroups) void km_tail_t(TailPara
 //                      halo of 2 on all four sides, zeros outside the chroma plane; the tile's bins as bytes; ONE set of the
 //                      waves' accumulators.  Everything is loaded once a tile; the three pairings (d_Cb, L), (d_Cr, L),
 //                      (d_Cb, d_Cr) then walk the tile one after another through one set of 25 lag accumulators and one set
-//                      of running bin sums (cross_pass<J>), and the workgroup's partial record of a pairing goes out with
+//                      of running bin sums (lag_pass), and the workgroup's partial record of a pairing goes out with
 //                      plain stores before the next one starts.
-//   km_tail_t          sums the partials unchanged: they lie as [pair][pairing][tile][kTEntries], so that a "plane" is a
+//   km_tail<4>         sums the partials unchanged: they lie as [pair][pairing][tile][kTEntries], so that a "plane" is a
 //                      pairing and all three tile counts are the chroma plane's.
 // The 32-bit sums are km_measure_t's: |L| <= 2^B - 1 (a rounded mean of residuals), so every product stays below 2^24.
 constexpr int kXLdsBytes = 2 * kTH * kTW + 2 * 2 * kPH * kPW + kTH * kTW + 8 * kWaves * kTEntries;
 static_assert(kRowsPerWave <= 127, "a 32-bit sum of km_measure_x holds 127 products of 12-bit residuals, one a row");
-static_assert(sizeof(g1s_measure_xrecord_t) == 8 * 3 * kTEntries, "km_tail_t writes the cross record as 64-bit words");
+static_assert(sizeof(g1s_measure_xrecord_t) == 8 * 3 * kTEntries, "km_tail<4> writes the cross record as 64-bit words");
 static_assert(kXLdsBytes == 65376 && kXLdsBytes <= 65536, "km_measure_x: 160 bytes under 64 KiB, two workgroups a CU");
 
 struct CrossParams {
@@ -389,64 +438,6 @@ struct CrossParams {
   int W, H, xdec, ydec, shift;   // the luma plane, chroma decimation, B - 5
   uint32_t tiles;                // of the chroma plane
 };
-
-// one pairing over the wave's rows: J = 0 (d_Cb, L), 1 (d_Cr, L), 2 (d_Cb, d_Cr).  km_measure_t's row loop: a = the tile's
-// own sample, b = the 5 x 5 window round it in a plane with a halo.
-template <int J>
-__device__ __forceinline__ void cross_pass(const int16_t *s_d, const int16_t *s_r, const int16_t *s_l, const uint8_t *s_bin,
-                                           unsigned long long *mine, int row0, int rows, int lane) {
-  const int16_t *s_b = J == 2 ? s_r : s_l;
-  int acc[kTLags];
-#pragma unroll
-  for (int i = 0; i < kTLags; ++i) acc[i] = 0;
-  int w[kTWin][kTWin];
-#pragma unroll
-  for (int q = 0; q < kTWin - 1; ++q)
-#pragma unroll
-    for (int k = 0; k < kTWin; ++k) w[q + 1][k] = s_b[(row0 + q) * kPW + lane + k];
-  int cur = -1, bn = 0, bx = 0, bu = 0, bv = 0;  // the bin the lane's column is in and its sums so far (cur < 0: none)
-  auto hand_on = [&](bool go) __attribute__((always_inline)) {
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(go);
-    while (todo) {
-      const int b = __builtin_amdgcn_readlane(cur, (int)__builtin_ctzll(todo));
-      const bool m = go && cur == b;
-      todo &= ~__builtin_amdgcn_ballot_w64(m);
-      const int n = wave_sum(m ? bn : 0);
-      const long long x = wave_sum_wide(m ? bx : 0), u = wave_sum_wide(m ? bu : 0), v = wave_sum_wide(m ? bv : 0);
-      if (lane == 0) {
-        mine[b] += (unsigned long long)(long long)n;
-        mine[kBins + b] += (unsigned long long)x;
-        mine[2 * kBins + b] += (unsigned long long)u;
-        mine[3 * kBins + b] += (unsigned long long)v;
-      }
-      if (m) cur = -1, bn = bx = bu = bv = 0;
-    }
-  };
-  for (int r = 0; r < rows; ++r) {
-#pragma unroll
-    for (int q = 0; q < kTWin - 1; ++q)
-#pragma unroll
-      for (int k = 0; k < kTWin; ++k) w[q][k] = w[q + 1][k];
-#pragma unroll
-    for (int k = 0; k < kTWin; ++k) w[kTWin - 1][k] = s_b[(row0 + r + kTWin - 1) * kPW + lane + k];
-    const int d = J == 1 ? (int)s_r[(row0 + r + kTHalo) * kPW + lane + kTHalo] : (int)s_d[(row0 + r) * kTW + lane];
-#pragma unroll
-    for (int q = 0; q < kTWin; ++q)
-#pragma unroll
-      for (int k = 0; k < kTWin; ++k) acc[q * kTWin + k] += __mul24(d, w[q][k]);
-    const int e = w[kTHalo][kTHalo];
-    const int k = s_bin[(row0 + r) * kTW + lane];
-    const bool change = cur >= 0 && k != cur;
-    if (__builtin_amdgcn_ballot_w64(change)) hand_on(change);
-    if (k != kNoBin) cur = k, bn += 1, bx += __mul24(d, e), bu += __mul24(d, d), bv += __mul24(e, e);
-  }
-  hand_on(cur >= 0);
-#pragma unroll
-  for (int i = 0; i < kTLags; ++i) {
-    const long long t = wave_sum_wide(acc[i]);
-    if (lane == 0) mine[4 * kBins + i] = (unsigned long long)t;
-  }
-}
 
 template <int BPS>
 __global__ __launch_bounds__(kThreads) void km_measure_x(CrossParams p) {
@@ -514,11 +505,12 @@ __global__ __launch_bounds__(kThreads) void km_measure_x(CrossParams p) {
     }
     __syncthreads();
   };
-  if (rows > 0) cross_pass<0>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  // the pairings (d_Cb, L), (d_Cr, L), (d_Cb, d_Cr): the second's own sample comes from the plane with the halo
+  if (rows > 0) lag_pass<false>(s_d, s_l, s_bin, s_acc[wave], row0, rows, lane);
   hand_over(0);
-  if (rows > 0) cross_pass<1>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  if (rows > 0) lag_pass<true>(s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
   hand_over(1);
-  if (rows > 0) cross_pass<2>(s_d, s_r, s_l, s_bin, s_acc[wave], row0, rows, lane);
+  if (rows > 0) lag_pass<false>(s_d, s_r, s_bin, s_acc[wave], row0, rows, lane);
   hand_over(2);
 }
 
@@ -548,18 +540,18 @@ __global__ __launch_bounds__(kThreads) void km_measure_x(CrossParams p) {
 constexpr int kScales = 5;
 constexpr int kSEntries = kScales * 3 * kBins;  // a partial scale record: [k - 1][n, s1, s2][bin]
 constexpr int kSTiles = 8, kSW = kTW * kSTiles;  // the strip of a workgroup
-constexpr int kSTailThreads = 512;
 static_assert(kRowsPerWave == 32 && kTW == 64, "a wave's band holds whole 32 x 32 boxes, a step is 8 lanes of 8 samples wide");
-static_assert(kSEntries <= kSTailThreads, "km_tail_s gives an entry a thread");
+static_assert(kSEntries <= kTailThreads, "km_tail_s gives an entry a thread");
 static_assert(sizeof(g1s_measure_srecord_t) == 8 * 3 * kSEntries, "km_tail_s writes the scale record as 64-bit words");
 
+// ClassParams for km_measure_s, which also needs the luma height (its own struct: the field stands beside the width)
 struct ScaleParams {
   const MeasureJob *jobs;
-  unsigned long long *partials;  // [pair][strips_frame][kSEntries]
-  int pw, ph, strips_x;          // the class's plane size
+  unsigned long long *partials;  // [pair][units_frame][kSEntries]
+  int pw, ph, units_x;           // the class's plane size, the strips across it
   int plane0;
   int W, H, xdec, ydec, shift;  // luma size, chroma decimation, B - 5
-  uint32_t strips_frame, strip_base, strips_plane;
+  uint32_t units_frame, unit_base, units_plane;
 };
 
 // the value of lane ^ M, every lane taking part
@@ -602,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void km_measure_s(ScaleParams p) {
   const MeasureJob &job = p.jobs[blockIdx.z];
   const int c = p.plane0 + (int)blockIdx.y;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ty = (int)blockIdx.x / p.strips_x, tx = (int)blockIdx.x - ty * p.strips_x;
+  const int ty = (int)blockIdx.x / p.units_x, tx = (int)blockIdx.x - ty * p.units_x;
   const int x0 = tx * kSW, yw = ty * kTH + wave * kRowsPerWave;  // the wave's band of the strip
   const uint8_t *pa = job.a[c], *pb = job.b[c], *py = job.b[0];
   const uint32_t sa = job.a_stride[c], sb = job.b_stride[c], sy = job.b_stride[0];
@@ -718,13 +710,15 @@ __global__ __launch_bounds__(kThreads) void km_measure_s(ScaleParams p) {
     unsigned long long t = 0;
 #pragma unroll
     for (int v = 0; v < kWaves; ++v) t += s_acc[v][i];
-    const size_t at = (size_t)blockIdx.z * p.strips_frame + p.strip_base + (size_t)blockIdx.y * p.strips_plane + blockIdx.x;
+    const size_t at = (size_t)blockIdx.z * p.units_frame + p.unit_base + (size_t)blockIdx.y * p.units_plane + blockIdx.x;
     p.partials[at * kSEntries + i] = t;
   }
 }
 
-// the pair's scale record from its workgroups' partial records: grid (plane, pair)
-__global__ __launch_bounds__(kSTailThreads) void km_tail_s(TailParams p) {
+// the pair's scale record from its workgroups' partial records: grid (plane, pair).  (Not an instance of km_tail: an entry
+// is (scale, field, bin) here and goes to [field][plane][scale][bin], a strip count needs no groups; one body for both would
+// branch on the record it writes.)
+__global__ __launch_bounds__(kTailThreads) void km_tail_s(TailParams p) {
   const int c = (int)blockIdx.x, i = (int)threadIdx.x;
   if (i >= kSEntries) return;
   const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kSEntries;
@@ -736,255 +730,245 @@ __global__ __launch_bounds__(kSTailThreads) void km_tail_s(TailParams p) {
   rec[(field * 3 + c) * kScales * kBins + scale * kBins + bin] = t;
 }
 
-// rule 8's offsets: raster order, (0, 0) is index 12
-void temporal_offset(int i, int *dx, int *dy) { *dy = i / kTWin - kTHalo, *dx = i % kTWin - kTHalo; }
-
-// rule 4's offsets in the table's coefficient order, (0, 0) last
-void lag_offset(int i, int *dx, int *dy) {
-  if (i == 24) *dx = 0, *dy = 0;
-  else *dy = i / 7 - 3, *dx = i % 7 - 3;
-}
-
 }  // namespace
 
 // =============================================================== host engine =====
 using namespace g1s_op;
 
-struct g1s_measure : BatchedOp {
-  Event ev[2];
-  std::vector<MeasureJob> jobs;  // the batch being filled
-  ParamSets<MeasureJob> p_jobs;
+namespace {
+
+// How a frame's planes are cut into the units workgroups take (km_measure's tiles, km_measure_s's strips; for the tail of
+// km_measure_x the pairings of the chroma tiles): a plane's count, where its partial records start in a job's, a job's count.
+struct Units {
+  uint32_t n[3] = {0, 0, 0}, base[3] = {0, 0, 0}, frame = 0;
+  // units of unit_w x kTH samples over the planes of g
+  void cut(const PlaneGeom &g, int unit_w) {
+    frame = 0;
+    for (int c = 0; c < 3; ++c) {
+      n[c] = c < g.nplanes ? (uint32_t)(((g.pw(c) + unit_w - 1) / unit_w) * ((g.ph(c) + kTH - 1) / kTH)) : 0u;
+      base[c] = frame;
+      frame += n[c];
+    }
+  }
+};
+
+// What a record kind (plain, temporal, cross, scales) owns in a meter, and the steps of a batch that are the same for all.
+template <class Rec>
+struct RecordLane {
+  bool on = false;  // does the meter make this kind?
+  Event ev[2];      // round the kind's launches, while timing
   DevBuf<unsigned long long> d_partials;
   size_t partials_cap = 0;
-  uint32_t tiles[3] = {0, 0, 0}, tile_base[3] = {0, 0, 0}, tiles_frame = 0;
-  DevBuf<g1s_measure_record_t> d_recs;
-  PinnedBuf<g1s_measure_record_t> h_recs;
-  std::vector<g1s_measure_record_t> records;  // since the last hand-over
-  double ms_kernel = 0;
-  uint64_t frames_timed = 0;
+  DevBuf<Rec> d_recs;  // a batch's records
+  PinnedBuf<Rec> h_recs;
+  std::vector<Rec> records;  // since the last hand-over
+  double ms = 0;             // in the kind's launches of the timed batches
+  uint64_t timed = 0;        // and the records those made
+
+  unsigned long long *words() const { return reinterpret_cast<unsigned long long *>(d_recs.p); }
+  // for batches of up to `batch` records (nothing for a kind the meter does not make)
+  bool alloc(uint32_t batch) {
+    if (!on) return true;
+    bool ok = true;
+    for (Event &e : ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    return ok && hipMalloc((void **)&d_recs.p, sizeof(Rec) * batch) == hipSuccess &&
+           hipHostMalloc((void **)&h_recs.p, sizeof(Rec) * batch, hipHostMallocDefault) == hipSuccess;
+  }
+  // room for `need` words of partial records
+  hipError_t size_partials(size_t need) {
+    if (!on || need <= partials_cap) return hipSuccess;
+    d_partials = DevBuf<unsigned long long>();
+    const hipError_t e = hipMalloc((void **)&d_partials.p, need * sizeof(unsigned long long));
+    if (e == hipSuccess) partials_cap = need;
+    return e;
+  }
+  // a batch of n records begins: zeros (the planes a frame does not have), the first event
+  hipError_t begin(uint32_t n, bool timing, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(d_recs, 0, sizeof(Rec) * n, s);
+    return e != hipSuccess || !timing ? e : hipEventRecord(ev[0], s);
+  }
+  // behind its launches: the second event, the records back
+  hipError_t end(uint32_t n, bool timing, hipStream_t s) {
+    const hipError_t e = timing ? hipEventRecord(ev[1], s) : hipSuccess;
+    return e != hipSuccess ? e : hipMemcpyAsync(h_recs, d_recs, sizeof(Rec) * n, hipMemcpyDeviceToHost, s);
+  }
+  // after the wait: the time between the events of a timed batch; then the records to those held
+  hipError_t clock(uint32_t n) {
+    float t = 0;
+    const hipError_t e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    if (e == hipSuccess) ms += t, timed += n;
+    return e;
+  }
+  void collect(uint32_t n) { records.insert(records.end(), h_recs.p, h_recs.p + n); }
+  // the records held into the caller's `cap` entries
+  int hand_over(Rec *out, size_t cap, size_t *n_out) {
+    if (n_out) *n_out = records.size();
+    if (records.size() > cap || (!out && !records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
+    if (!records.empty()) std::memcpy(out, records.data(), sizeof(Rec) * records.size());
+    records.clear();
+    return G1S_OK;
+  }
+};
+
+}  // namespace
+
+struct g1s_measure : BatchedOp {
+  std::vector<MeasureJob> jobs;  // the batch being filled
+  ParamSets<MeasureJob> p_jobs;
+  // pairings: km_measure_x's partial records as km_tail<4> reads them, a pairing where a plane is, the chroma plane's tiles each
+  Units tiles, strips, pairings;
+  RecordLane<g1s_measure_record_t> plain;      // always on
+  RecordLane<g1s_measure_trecord_t> temporal;  // rules 7 - 11: a record a temporal job
+  RecordLane<g1s_measure_xrecord_t> cross;     // rules 12 - 17: a record a pair, from the batch's own jobs
+  RecordLane<g1s_measure_srecord_t> scales;    // rules 18 - 23: likewise
   // a temporal meter: the run's last pair as the kernels read it (its planes: the caller's, or a slot of the input rings,
-  // which then have batch + 1 slots filled round-robin), the batch's temporal jobs, the temporal records
-  bool temporal = false, have_prev = false;
+  // which then have batch + 1 slots filled round-robin) and the batch's temporal jobs
+  bool have_prev = false;
   MeasureJob prev{};
   bool prev_staged[2] = {false, false};  // (are the planes of prev.a / prev.b the meter's own: a ring's or d_keep's?)
   uint32_t ring_at = 0;
   DevBuf<uint8_t> d_keep[2];  // a frame each: the caller's device planes of the run's last pair, kept over a hand-over
-  Event ev_t[2];
   std::vector<TemporalJob> tjobs;
   ParamSets<TemporalJob> p_tjobs;
-  DevBuf<unsigned long long> d_tpartials;
-  size_t tpartials_cap = 0;
-  DevBuf<g1s_measure_trecord_t> d_trecs;
-  PinnedBuf<g1s_measure_trecord_t> h_trecs;
-  std::vector<g1s_measure_trecord_t> trecords;  // since the last hand-over
-  double ms_tkernel = 0;
-  uint64_t pairs_timed = 0;
-  // a cross meter (rules 12 - 17): a cross record a pair, from the batch's own jobs
-  bool cross = false;
-  Event ev_x[2];
-  DevBuf<unsigned long long> d_xpartials;
-  size_t xpartials_cap = 0;
-  DevBuf<g1s_measure_xrecord_t> d_xrecs;
-  PinnedBuf<g1s_measure_xrecord_t> h_xrecs;
-  std::vector<g1s_measure_xrecord_t> xrecords;  // since the last hand-over
-  double ms_xkernel = 0;
-  uint64_t xpairs_timed = 0;
-  // a scales meter (rules 18 - 23): a scale record a pair, from the batch's own jobs
-  bool scales = false;
-  Event ev_s[2];
-  DevBuf<unsigned long long> d_spartials;
-  size_t spartials_cap = 0;
-  uint32_t strips[3] = {0, 0, 0}, strip_base[3] = {0, 0, 0}, strips_frame = 0;
-  DevBuf<g1s_measure_srecord_t> d_srecs;
-  PinnedBuf<g1s_measure_srecord_t> h_srecs;
-  std::vector<g1s_measure_srecord_t> srecords;  // since the last hand-over
-  double ms_skernel = 0;
-  uint64_t spairs_timed = 0;
   // the chroma launches alone, for tools/bench_measure.py --cross (recorded only while timing is on)
   Event ev_c[2], ev_tc[2];
   double ms_chroma = 0, ms_tchroma = 0;
 
   int set_geometry(const g1s_frame_t &f);
+  template <class Params, class Job>
+  Params class_params(const Job *d_jobs, unsigned long long *partials, int plane0, int unit_w, const Units &u) const;
+  template <class Params, class Job>
+  int launch_classes(void (*kernel)(Params), const Job *d_jobs, uint32_t n, unsigned long long *partials, int unit_w, const Units &u, Event *chroma_ev);
+  template <class Rec>
+  int launch_tail(void (*kernel)(TailParams), unsigned planes, uint32_t n, const RecordLane<Rec> &lane, const Units &u);
   int flush();
   int keep_prev();
+  template <class Rec>
+  int finish(RecordLane<Rec> &lane, Rec *out, size_t cap, size_t *n_out);
 };
 
 int g1s_measure::set_geometry(const g1s_frame_t &f) {
   set_frame_geometry(f);
-  tiles_frame = 0;
-  for (int c = 0; c < 3; ++c) {
-    tiles[c] = c < geom.nplanes ? (uint32_t)(((geom.pw(c) + kTW - 1) / kTW) * ((geom.ph(c) + kTH - 1) / kTH)) : 0u;
-    tile_base[c] = tiles_frame;
-    tiles_frame += tiles[c];
-  }
-  const size_t need = (size_t)tiles_frame * kEntries * batch;
-  if (need > partials_cap) {
-    d_partials = DevBuf<unsigned long long>();
-    G1S_OP_TRY(hipMalloc((void **)&d_partials.p, need * sizeof(unsigned long long)));
-    partials_cap = need;
-  }
-  const size_t tneed = temporal ? (size_t)tiles_frame * kTEntries * batch : 0;
-  if (tneed > tpartials_cap) {
-    d_tpartials = DevBuf<unsigned long long>();
-    G1S_OP_TRY(hipMalloc((void **)&d_tpartials.p, tneed * sizeof(unsigned long long)));
-    tpartials_cap = tneed;
-  }
-  const size_t xneed = cross && geom.nplanes == 3 ? (size_t)tiles[1] * 3 * kTEntries * batch : 0;
-  if (xneed > xpartials_cap) {
-    d_xpartials = DevBuf<unsigned long long>();
-    G1S_OP_TRY(hipMalloc((void **)&d_xpartials.p, xneed * sizeof(unsigned long long)));
-    xpartials_cap = xneed;
-  }
-  strips_frame = 0;
-  for (int c = 0; c < 3; ++c) {
-    strips[c] = scales && c < geom.nplanes ? (uint32_t)(((geom.pw(c) + kSW - 1) / kSW) * ((geom.ph(c) + kTH - 1) / kTH)) : 0u;
-    strip_base[c] = strips_frame;
-    strips_frame += strips[c];
-  }
-  const size_t sneed = (size_t)strips_frame * kSEntries * batch;
-  if (sneed > spartials_cap) {
-    d_spartials = DevBuf<unsigned long long>();
-    G1S_OP_TRY(hipMalloc((void **)&d_spartials.p, sneed * sizeof(unsigned long long)));
-    spartials_cap = sneed;
-  }
+  tiles.cut(geom, kTW), strips.cut(geom, kSW);
+  pairings.frame = 3 * tiles.n[1];
+  for (int j = 0; j < 3; ++j) pairings.n[j] = tiles.n[1], pairings.base[j] = (uint32_t)j * tiles.n[1];
+  G1S_OP_TRY(plain.size_partials((size_t)tiles.frame * kEntries * batch));
+  G1S_OP_TRY(temporal.size_partials((size_t)tiles.frame * kTEntries * batch));
+  G1S_OP_TRY(cross.size_partials(geom.nplanes == 3 ? (size_t)pairings.frame * kTEntries * batch : 0));
+  G1S_OP_TRY(scales.size_partials((size_t)strips.frame * kSEntries * batch));
   have_prev = false, ring_at = 0;  // (a new geometry ends the run; the rings are made again)
   d_keep[0] = DevBuf<uint8_t>(), d_keep[1] = DevBuf<uint8_t>();
   return G1S_OK;
 }
 
-// the queued pairs as one batch: a launch per plane class, the summing launch, the records back, all waited for
+// the parameters (ClassParams<Job>, or ScaleParams) of the launch over the plane class that begins at plane0, in units
+// unit_w samples wide
+template <class Params, class Job>
+Params g1s_measure::class_params(const Job *d_jobs, unsigned long long *partials, int plane0, int unit_w, const Units &u) const {
+  Params cp{};
+  cp.jobs = d_jobs, cp.partials = partials;
+  cp.pw = (int)geom.pw(plane0), cp.ph = (int)geom.ph(plane0), cp.units_x = (cp.pw + unit_w - 1) / unit_w, cp.plane0 = plane0;
+  cp.W = geom.W, cp.xdec = geom.subx, cp.ydec = geom.suby, cp.shift = (int)bit_depth - 5;
+  if constexpr (std::is_same<Params, ScaleParams>::value) cp.H = geom.H;
+  cp.units_frame = u.frame, cp.unit_base = u.base[plane0], cp.units_plane = u.n[plane0];
+  return cp;
+}
+
+// a kernel over n jobs, a launch a plane class: luma, then both chroma planes.  chroma_ev: the events round the chroma
+// launch while timing, or null
+template <class Params, class Job>
+int g1s_measure::launch_classes(void (*kernel)(Params), const Job *d_jobs, uint32_t n, unsigned long long *partials, int unit_w, const Units &u,
+                                Event *chroma_ev) {
+  for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
+    const bool mark = timing && plane0 && chroma_ev;
+    if (mark) G1S_OP_TRY(hipEventRecord(chroma_ev[0], stream));
+    hipLaunchKernelGGL(kernel, dim3(u.n[plane0], plane0 ? 2u : 1u, n), dim3(kThreads), 0, stream, class_params<Params>(d_jobs, partials, plane0, unit_w, u));
+    G1S_OP_TRY(hipGetLastError());
+    if (mark) G1S_OP_TRY(hipEventRecord(chroma_ev[1], stream));
+  }
+  return G1S_OK;
+}
+
+// the summing launch of a kind: its partial records, cut as `u`, into the n records of the batch
+template <class Rec>
+int g1s_measure::launch_tail(void (*kernel)(TailParams), unsigned planes, uint32_t n, const RecordLane<Rec> &lane, const Units &u) {
+  TailParams tp{};
+  tp.partials = lane.d_partials, tp.records = lane.words(), tp.tiles_frame = u.frame;
+  for (int c = 0; c < 3; ++c) tp.tiles[c] = u.n[c], tp.tile_base[c] = u.base[c];
+  hipLaunchKernelGGL(kernel, dim3(planes, n), dim3(kTailThreads), 0, stream, tp);
+  G1S_OP_TRY(hipGetLastError());
+  return G1S_OK;
+}
+
+// the queued pairs as one batch, kind after kind on the meter's stream: a launch per plane class, the summing launch, the
+// records back; then all waited for
 int g1s_measure::flush() {
-  const uint32_t B = (uint32_t)jobs.size();
+  const uint32_t B = (uint32_t)jobs.size(), T = (uint32_t)tjobs.size();
   if (!B) return G1S_OK;
   int set, rc = next_set(&set);
   if (rc) return rc;
+  const bool wide = bps == 2;
+  const unsigned planes = (unsigned)geom.nplanes;
   std::memcpy(p_jobs.h[set], jobs.data(), sizeof(MeasureJob) * B);
   G1S_OP_TRY(p_jobs.upload(set, B, stream));
-  G1S_OP_TRY(hipMemsetAsync(d_recs, 0, sizeof(g1s_measure_record_t) * B, stream));  // (the planes a frame does not have)
-  if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
-  for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
-    MeasureParams mp{};
-    mp.jobs = p_jobs.d[set], mp.partials = d_partials;
-    mp.pw = (int)geom.pw(plane0), mp.ph = (int)geom.ph(plane0), mp.tiles_x = (mp.pw + kTW - 1) / kTW, mp.plane0 = plane0;
-    mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
-    mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
-    const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, B);
-    if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_c[0], stream));
-    if (bps == 2) hipLaunchKernelGGL(km_measure<2>, grid, dim3(kThreads), 0, stream, mp);
-    else hipLaunchKernelGGL(km_measure<1>, grid, dim3(kThreads), 0, stream, mp);
-    G1S_OP_TRY(hipGetLastError());
-    if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_c[1], stream));
-  }
-  TailParams tp{};
-  tp.partials = d_partials, tp.records = reinterpret_cast<unsigned long long *>(d_recs.p), tp.tiles_frame = tiles_frame;
-  for (int c = 0; c < 3; ++c) tp.tiles[c] = tiles[c], tp.tile_base[c] = tile_base[c];
-  hipLaunchKernelGGL(km_tail, dim3((unsigned)geom.nplanes, B), dim3(128 * kTailGroups), 0, stream, tp);
-  G1S_OP_TRY(hipGetLastError());
-  if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
-  G1S_OP_TRY(hipMemcpyAsync(h_recs, d_recs, sizeof(g1s_measure_record_t) * B, hipMemcpyDeviceToHost, stream));
-  // the batch's temporal jobs behind it on the same stream: the same launches with km_measure_t and km_tail_t
-  const uint32_t T = (uint32_t)tjobs.size();
+  const MeasureJob *d_jobs = p_jobs.d[set];
+  G1S_OP_TRY(plain.begin(B, timing, stream));
+  if ((rc = launch_classes(wide ? km_measure<2> : km_measure<1>, d_jobs, B, plain.d_partials, kTW, tiles, ev_c)) != 0) return rc;
+  if ((rc = launch_tail(km_tail<3>, planes, B, plain, tiles)) != 0) return rc;
+  G1S_OP_TRY(plain.end(B, timing, stream));
+  // the batch's temporal jobs behind it: the same launches with km_measure_t and km_tail<4>
   if (T) {
     std::memcpy(p_tjobs.h[set], tjobs.data(), sizeof(TemporalJob) * T);
     G1S_OP_TRY(p_tjobs.upload(set, T, stream));
-    G1S_OP_TRY(hipMemsetAsync(d_trecs, 0, sizeof(g1s_measure_trecord_t) * T, stream));
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_t[0], stream));
-    for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
-      TemporalParams mp{};
-      mp.jobs = p_tjobs.d[set], mp.partials = d_tpartials;
-      mp.pw = (int)geom.pw(plane0), mp.ph = (int)geom.ph(plane0), mp.tiles_x = (mp.pw + kTW - 1) / kTW, mp.plane0 = plane0;
-      mp.W = geom.W, mp.xdec = geom.subx, mp.ydec = geom.suby, mp.shift = (int)bit_depth - 5;
-      mp.tiles_frame = tiles_frame, mp.tile_base = tile_base[plane0], mp.tiles_plane = tiles[plane0];
-      const dim3 grid(tiles[plane0], plane0 ? 2u : 1u, T);
-      if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_tc[0], stream));
-      if (bps == 2) hipLaunchKernelGGL(km_measure_t<2>, grid, dim3(kThreads), 0, stream, mp);
-      else hipLaunchKernelGGL(km_measure_t<1>, grid, dim3(kThreads), 0, stream, mp);
-      G1S_OP_TRY(hipGetLastError());
-      if (timing && plane0) G1S_OP_TRY(hipEventRecord(ev_tc[1], stream));
-    }
-    TailParams ttp = tp;
-    ttp.partials = d_tpartials, ttp.records = reinterpret_cast<unsigned long long *>(d_trecs.p);
-    hipLaunchKernelGGL(km_tail_t, dim3((unsigned)geom.nplanes, T), dim3(kTTailWidth * kTTailGroups), 0, stream, ttp);
-    G1S_OP_TRY(hipGetLastError());
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_t[1], stream));
-    G1S_OP_TRY(hipMemcpyAsync(h_trecs, d_trecs, sizeof(g1s_measure_trecord_t) * T, hipMemcpyDeviceToHost, stream));
+    G1S_OP_TRY(temporal.begin(T, timing, stream));
+    if ((rc = launch_classes(wide ? km_measure_t<2> : km_measure_t<1>, p_tjobs.d[set].p, T, temporal.d_partials, kTW, tiles, ev_tc)) != 0) return rc;
+    if ((rc = launch_tail(km_tail<4>, planes, T, temporal, tiles)) != 0) return rc;
+    G1S_OP_TRY(temporal.end(T, timing, stream));
   }
-  // a cross meter: the batch's own jobs once more, one km_measure_x launch and km_tail_t over its partials, where a pairing
+  // a cross meter: the batch's own jobs once more, one km_measure_x launch and km_tail<4> over its partials, where a pairing
   // stands for a plane (a pair with one plane keeps the zeros of the memset)
-  if (cross) {
-    G1S_OP_TRY(hipMemsetAsync(d_xrecs, 0, sizeof(g1s_measure_xrecord_t) * B, stream));
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_x[0], stream));
+  if (cross.on) {
+    G1S_OP_TRY(cross.begin(B, timing, stream));
     if (geom.nplanes == 3) {
       CrossParams xp{};
-      xp.jobs = p_jobs.d[set], xp.partials = d_xpartials;
+      xp.jobs = d_jobs, xp.partials = cross.d_partials;
       xp.cw = (int)geom.pw(1), xp.ch = (int)geom.ph(1), xp.tiles_x = (xp.cw + kTW - 1) / kTW;
       xp.W = geom.W, xp.H = (int)geom.ph(0), xp.xdec = geom.subx, xp.ydec = geom.suby, xp.shift = (int)bit_depth - 5;
-      xp.tiles = tiles[1];
-      if (bps == 2) hipLaunchKernelGGL(km_measure_x<2>, dim3(tiles[1], 1u, B), dim3(kThreads), 0, stream, xp);
-      else hipLaunchKernelGGL(km_measure_x<1>, dim3(tiles[1], 1u, B), dim3(kThreads), 0, stream, xp);
+      xp.tiles = tiles.n[1];
+      void (*const kernel)(CrossParams) = wide ? km_measure_x<2> : km_measure_x<1>;
+      hipLaunchKernelGGL(kernel, dim3(tiles.n[1], 1u, B), dim3(kThreads), 0, stream, xp);
       G1S_OP_TRY(hipGetLastError());
-      TailParams xtp{};
-      xtp.partials = d_xpartials, xtp.records = reinterpret_cast<unsigned long long *>(d_xrecs.p), xtp.tiles_frame = 3 * tiles[1];
-      for (int j = 0; j < 3; ++j) xtp.tiles[j] = tiles[1], xtp.tile_base[j] = (uint32_t)j * tiles[1];
-      hipLaunchKernelGGL(km_tail_t, dim3(3u, B), dim3(kTTailWidth * kTTailGroups), 0, stream, xtp);
-      G1S_OP_TRY(hipGetLastError());
+      if ((rc = launch_tail(km_tail<4>, 3u, B, cross, pairings)) != 0) return rc;
     }
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_x[1], stream));
-    G1S_OP_TRY(hipMemcpyAsync(h_xrecs, d_xrecs, sizeof(g1s_measure_xrecord_t) * B, hipMemcpyDeviceToHost, stream));
+    G1S_OP_TRY(cross.end(B, timing, stream));
   }
   // a scales meter: the batch's own jobs once more, a km_measure_s launch a plane class and km_tail_s over the strips' partials
-  if (scales) {
-    G1S_OP_TRY(hipMemsetAsync(d_srecs, 0, sizeof(g1s_measure_srecord_t) * B, stream));  // (the planes a frame does not have)
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_s[0], stream));
-    for (int plane0 = 0; plane0 < geom.nplanes; plane0 += plane0 ? 2 : 1) {
-      ScaleParams sp{};
-      sp.jobs = p_jobs.d[set], sp.partials = d_spartials;
-      sp.pw = (int)geom.pw(plane0), sp.ph = (int)geom.ph(plane0), sp.strips_x = (sp.pw + kSW - 1) / kSW, sp.plane0 = plane0;
-      sp.W = geom.W, sp.H = geom.H, sp.xdec = geom.subx, sp.ydec = geom.suby, sp.shift = (int)bit_depth - 5;
-      sp.strips_frame = strips_frame, sp.strip_base = strip_base[plane0], sp.strips_plane = strips[plane0];
-      const dim3 grid(strips[plane0], plane0 ? 2u : 1u, B);
-      if (bps == 2) hipLaunchKernelGGL(km_measure_s<2>, grid, dim3(kThreads), 0, stream, sp);
-      else hipLaunchKernelGGL(km_measure_s<1>, grid, dim3(kThreads), 0, stream, sp);
-      G1S_OP_TRY(hipGetLastError());
-    }
-    TailParams stp{};
-    stp.partials = d_spartials, stp.records = reinterpret_cast<unsigned long long *>(d_srecs.p), stp.tiles_frame = strips_frame;
-    for (int c = 0; c < 3; ++c) stp.tiles[c] = strips[c], stp.tile_base[c] = strip_base[c];
-    hipLaunchKernelGGL(km_tail_s, dim3((unsigned)geom.nplanes, B), dim3(kSTailThreads), 0, stream, stp);
-    G1S_OP_TRY(hipGetLastError());
-    if (timing) G1S_OP_TRY(hipEventRecord(ev_s[1], stream));
-    G1S_OP_TRY(hipMemcpyAsync(h_srecs, d_srecs, sizeof(g1s_measure_srecord_t) * B, hipMemcpyDeviceToHost, stream));
+  if (scales.on) {
+    G1S_OP_TRY(scales.begin(B, timing, stream));
+    if ((rc = launch_classes(wide ? km_measure_s<2> : km_measure_s<1>, d_jobs, B, scales.d_partials, kSW, strips, nullptr)) != 0) return rc;
+    if ((rc = launch_tail(km_tail_s, planes, B, scales, strips)) != 0) return rc;
+    G1S_OP_TRY(scales.end(B, timing, stream));
   }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
-  if (timing) {
-    float ms = 0;
-    G1S_OP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ms_kernel += ms, frames_timed += B;
-    if (T) {
-      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_t[0], ev_t[1]));
-      ms_tkernel += ms, pairs_timed += T;
-      if (geom.nplanes == 3) {
+  if (timing) {  // (every time is read before a record is appended: a failure here leaves the records as they were)
+    G1S_OP_TRY(plain.clock(B));
+    if (T) G1S_OP_TRY(temporal.clock(T));
+    if (cross.on) G1S_OP_TRY(cross.clock(B));
+    if (scales.on) G1S_OP_TRY(scales.clock(B));
+    if (geom.nplanes == 3) {
+      float ms = 0;
+      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_c[0], ev_c[1]));
+      ms_chroma += ms;
+      if (T) {
         G1S_OP_TRY(hipEventElapsedTime(&ms, ev_tc[0], ev_tc[1]));
         ms_tchroma += ms;
       }
     }
-    if (geom.nplanes == 3) {
-      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_c[0], ev_c[1]));
-      ms_chroma += ms;
-    }
-    if (cross) {
-      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_x[0], ev_x[1]));
-      ms_xkernel += ms, xpairs_timed += B;
-    }
-    if (scales) {
-      G1S_OP_TRY(hipEventElapsedTime(&ms, ev_s[0], ev_s[1]));
-      ms_skernel += ms, spairs_timed += B;
-    }
   }
-  records.insert(records.end(), h_recs.p, h_recs.p + B);
-  trecords.insert(trecords.end(), h_trecs.p, h_trecs.p + T);
-  if (cross) xrecords.insert(xrecords.end(), h_xrecs.p, h_xrecs.p + B);
-  if (scales) srecords.insert(srecords.end(), h_srecs.p, h_srecs.p + B);
+  plain.collect(B);
+  if (T) temporal.collect(T);
+  if (cross.on) cross.collect(B);
+  if (scales.on) scales.collect(B);
   jobs.clear();
   tjobs.clear();
   return G1S_OK;
@@ -1010,43 +994,16 @@ int g1s_measure::keep_prev() {
   return wait();
 }
 
+// g1s_measure_finish*: what is queued goes out, the run's last pair is kept, the kind's records are handed over
+template <class Rec>
+int g1s_measure::finish(RecordLane<Rec> &lane, Rec *out, size_t cap, size_t *n_out) {
+  (void)hipSetDevice(device);
+  int rc = flush();
+  if (rc || (rc = keep_prev()) != 0) return rc;
+  return lane.hand_over(out, cap, n_out);
+}
+
 namespace {
-
-bool checked_add(uint64_t &t, uint64_t v) { return !__builtin_add_overflow(t, v, &t); }
-bool checked_add(int64_t &t, int64_t v) { return !__builtin_add_overflow(t, v, &t); }
-
-// "%.4f" of v, or "-"
-std::string value(bool defined, double v) {
-  if (!defined) return "-";
-  char s[64];
-  snprintf(s, sizeof s, "%.4f", v);
-  return s;
-}
-
-struct Profile {
-  bool has[kBins];
-  double mean[kBins], sigma[kBins];
-  bool has_rho[24];
-  double rho[24];
-};
-
-// the printed values of plane c of a clip's record (one division or one square root a step, in this order)
-Profile profile_of(const g1s_measure_record_t &t, int c, const double terms[kLags]) {
-  Profile p{};
-  for (int k = 0; k < kBins; ++k) {
-    p.has[k] = t.n[c][k] > 0;
-    if (!p.has[k]) continue;
-    const double n = (double)t.n[c][k];
-    p.mean[k] = (double)t.s1[c][k] / n;
-    const double var = (double)t.s2[c][k] / n - p.mean[k] * p.mean[k];
-    p.sigma[k] = std::sqrt(var > 0.0 ? var : 0.0);
-  }
-  for (int i = 0; i < 24; ++i) {
-    p.has_rho[i] = t.r[c][24] != 0 && terms[i] > 0.0;
-    if (p.has_rho[i]) p.rho[i] = ((double)t.r[c][i] / terms[i]) / ((double)t.r[c][24] / terms[24]);
-  }
-  return p;
-}
 
 int refuse(char *err, size_t cap, int code, const std::string &m) {
   if (err && cap) snprintf(err, cap, "%s", m.c_str());
@@ -1063,174 +1020,130 @@ bool read_file(const char *path, std::string &text) {
   return true;
 }
 
-// the report of a clip's record(s) into a file.  "" when fine
-std::string write_report(const char *path, const g1s_measure_record_t &total, const g1s_measure_record_t *synth, uint64_t frames,
-                         const g1s_y4m_info_t &info) {
-  std::vector<char> buf(1 << 16);
-  const long n = g1s_format_measure(&total, synth, frames, info.bit_depth, info.width, info.height, info.xdec, info.ydec, info.nplanes, buf.data(),
-                                    buf.size());
-  if (n < 0) return "formatting the report failed";
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
-  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
-  return "";
-}
-
-// the temporal report of a clip's temporal record(s) into a file.  "" when fine
-std::string write_treport(const char *path, const g1s_measure_trecord_t &total, const g1s_measure_trecord_t *synth, uint64_t pairs,
-                          const g1s_y4m_info_t &info) {
-  std::vector<char> buf(1 << 16);
-  const long n = g1s_format_measure_temporal(&total, synth, pairs, info.bit_depth, info.width, info.height, info.xdec, info.ydec, info.nplanes,
-                                             buf.data(), buf.size());
-  if (n < 0) return "formatting the temporal report failed";
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
-  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
-  return "";
-}
-
-// the cross report of a clip's cross record(s) into a file.  "" when fine
-std::string write_xreport(const char *path, const g1s_measure_xrecord_t &total, const g1s_measure_xrecord_t *synth, uint64_t frames,
-                          const g1s_y4m_info_t &info) {
-  std::vector<char> buf(1 << 16);
-  const long n = g1s_format_measure_cross(&total, synth, frames, info.bit_depth, info.width, info.height, info.xdec, info.ydec, buf.data(), buf.size());
-  if (n < 0) return "formatting the cross report failed";
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
-  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
-  return "";
-}
-
 const char kCrossNeedsChroma[] = "--cross compares chroma with luma: the clip has no chroma planes";
 
 bool same_clip_shape(const g1s_y4m_info_t &a, const g1s_y4m_info_t &b) {
   return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.xdec == b.xdec && a.ydec == b.ydec && a.nplanes == b.nplanes;
 }
 
-// the records the meter holds, added to `total`.  "" when fine
-std::string take_records(g1s_measure_t *m, std::vector<g1s_measure_record_t> &scratch, g1s_measure_record_t &total) {
-  size_t n = 0;
-  int rc = g1s_measure_finish(m, nullptr, 0, &n);
-  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
-  scratch.resize(n + 1);
-  scratch[n] = total;
-  if (n && (rc = g1s_measure_finish(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
-  if (g1s_measure_sum(scratch.data(), n + 1, &total) != 0) return "the clip's sums leave 64 bits";
-  return "";
+// the meter is not of the kind the call is for: `maker` is the call that makes one
+int not_made_by(g1s_measure_t *m, const char *maker) {
+  m->err = std::string("the meter was not made by ") + maker;  // (not sticky: err_code stays 0)
+  return G1S_ERR_INVALID;
+}
+const char kTemporalMaker[] = "g1s_measure_new_temporal", kCrossMaker[] = "g1s_measure_new_modes with G1S_MEASURE_CROSS",
+           kScalesMaker[] = "g1s_measure_new_scales";
+
+// g1s_measure_finish and its three kin: the checks, then the lane's hand-over
+template <class Rec>
+int finish_kind(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, const char *maker, Rec *out, size_t cap, size_t *n_out) {
+  if (!m) return G1S_ERR_INVALID;
+  if (m->err_code) return m->err_code;
+  if (!(m->*lane).on) return not_made_by(m, maker);
+  return m->finish(m->*lane, out, cap, n_out);
 }
 
-// the temporal records the meter holds, added to `total` and counted in `pairs`.  "" when fine
-std::string take_trecords(g1s_measure_t *m, std::vector<g1s_measure_trecord_t> &scratch, g1s_measure_trecord_t &total, uint64_t &pairs) {
-  size_t n = 0;
-  int rc = g1s_measure_finish_temporal(m, nullptr, 0, &n);
-  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
-  scratch.resize(n + 1);
-  scratch[n] = total;
-  if (n && (rc = g1s_measure_finish_temporal(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
-  if (g1s_measure_sum_temporal(scratch.data(), n + 1, &total) != 0) return "the clip's temporal sums leave 64 bits";
-  pairs += n;
-  return "";
+// the four *_timing calls: the time in a kind's launches in the timed batches, the records those made
+template <class Rec>
+int kind_timing(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, double *ms, uint64_t *n) {
+  if (!m) return G1S_ERR_INVALID;
+  if (ms) *ms = (m->*lane).ms;
+  if (n) *n = (m->*lane).timed;
+  return G1S_OK;
 }
 
-// the cross records the meter holds, added to `total`.  "" when fine
-std::string take_xrecords(g1s_measure_t *m, std::vector<g1s_measure_xrecord_t> &scratch, g1s_measure_xrecord_t &total) {
-  size_t n = 0;
-  int rc = g1s_measure_finish_cross(m, nullptr, 0, &n);
-  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
-  scratch.resize(n + 1);
-  scratch[n] = total;
-  if (n && (rc = g1s_measure_finish_cross(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
-  if (g1s_measure_sum_cross(scratch.data(), n + 1, &total) != 0) return "the clip's cross sums leave 64 bits";
-  return "";
-}
-
-// the printed values of plane c of a clip's temporal record (one operation a step, in the order of the grammar)
-struct TProfile {
-  bool has_bin[kBins];
-  double bin[kBins];
-  bool has_lag[kTLags];
-  double lag[kTLags];
-  int peak;  // the lag of largest |rho|, the first on ties; -1: none is defined
+// ---- the file commands ----
+// where the reports of a clip go: the plain one always, the others where a path is given
+struct ReportPaths {
+  const char *plain, *temporal, *cross, *scales;
 };
 
-TProfile tprofile_of(const g1s_measure_trecord_t &t, int c, const double terms[kTLags]) {
-  TProfile p{};
-  uint64_t U = 0, V = 0;
-  for (int k = 0; k < kBins; ++k) {
-    U += t.u[c][k], V += t.v[c][k];
-    p.has_bin[k] = t.u[c][k] != 0 && t.v[c][k] != 0;
-    if (p.has_bin[k]) p.bin[k] = (double)t.x[c][k] / std::sqrt((double)t.u[c][k] * (double)t.v[c][k]);
+// a clip's total of one record kind: a meter's records pass through `scratch` and are counted
+template <class Rec>
+struct KindTotal {
+  Rec total;
+  std::vector<Rec> scratch;
+  uint64_t count = 0;
+  KindTotal() { std::memset(&total, 0, sizeof total); }
+  // the records of the kind that the meter holds, added to the total.  "" when fine; `kind`: "", "temporal " ... in the text
+  template <class Finish, class Sum>
+  std::string take(g1s_measure_t *m, Finish finish, Sum sum, const char *kind) {
+    size_t n = 0;
+    int rc = finish(m, nullptr, 0, &n);
+    if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
+    scratch.resize(n + 1);
+    scratch[n] = total;
+    if (n && (rc = finish(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
+    if (sum(scratch.data(), n + 1, &total) != 0) return std::string("the clip's ") + kind + "sums leave 64 bits";
+    count += n;
+    return "";
   }
-  const double T = terms[kTLags / 2];
-  p.peak = -1;
-  for (int i = 0; i < kTLags; ++i) {
-    p.has_lag[i] = U != 0 && V != 0 && terms[i] > 0.0;
-    if (!p.has_lag[i]) continue;
-    p.lag[i] = ((double)t.c[c][i] / terms[i]) / std::sqrt(((double)U / T) * ((double)V / T));
-    if (p.peak < 0 || std::fabs(p.lag[i]) > std::fabs(p.lag[p.peak])) p.peak = i;
+};
+
+// a clip's totals of the four kinds (temporal.count: the clip's pairs with a predecessor)
+struct ClipTotals {
+  KindTotal<g1s_measure_record_t> plain;
+  KindTotal<g1s_measure_trecord_t> temporal;
+  KindTotal<g1s_measure_xrecord_t> cross;
+  KindTotal<g1s_measure_srecord_t> scales;
+  // what the meter holds of every kind that has a report to go to.  "" when fine
+  std::string take(g1s_measure_t *m, const ReportPaths &out) {
+    std::string why = plain.take(m, g1s_measure_finish, g1s_measure_sum, "");
+    if (why.empty() && out.temporal) why = temporal.take(m, g1s_measure_finish_temporal, g1s_measure_sum_temporal, "temporal ");
+    if (why.empty() && out.cross) why = cross.take(m, g1s_measure_finish_cross, g1s_measure_sum_cross, "cross ");
+    if (why.empty() && out.scales) why = scales.take(m, g1s_measure_finish_scales, g1s_measure_sum_scales, "scale ");
+    return why;
   }
-  return p;
-}
+};
 
-std::string peak_text(const TProfile &p) {
-  if (p.peak < 0) return "- - -";
-  int dx, dy;
-  temporal_offset(p.peak, &dx, &dy);
-  return std::to_string(dx) + " " + std::to_string(dy) + " " + value(true, p.lag[p.peak]);
-}
-
-int not_temporal(g1s_measure_t *m) {
-  m->err = "the meter was not made by g1s_measure_new_temporal";  // (not sticky: err_code stays 0)
-  return G1S_ERR_INVALID;
-}
-
-int not_cross(g1s_measure_t *m) {
-  m->err = "the meter was not made by g1s_measure_new_modes with G1S_MEASURE_CROSS";  // (not sticky: err_code stays 0)
-  return G1S_ERR_INVALID;
-}
-
-int not_scales(g1s_measure_t *m) {
-  m->err = "the meter was not made by g1s_measure_new_scales";  // (not sticky: err_code stays 0)
-  return G1S_ERR_INVALID;
-}
-
-// the scale records the meter holds, added to `total`.  "" when fine
-std::string take_srecords(g1s_measure_t *m, std::vector<g1s_measure_srecord_t> &scratch, g1s_measure_srecord_t &total) {
-  size_t n = 0;
-  int rc = g1s_measure_finish_scales(m, nullptr, 0, &n);
-  if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
-  scratch.resize(n + 1);
-  scratch[n] = total;
-  if (n && (rc = g1s_measure_finish_scales(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
-  if (g1s_measure_sum_scales(scratch.data(), n + 1, &total) != 0) return "the clip's scale sums leave 64 bits";
-  return "";
-}
-
-// the scale report of a clip's plain and scale record(s) into a file.  "" when fine
-std::string write_sreport(const char *path, const g1s_measure_record_t &total, const g1s_measure_srecord_t &stotal, const g1s_measure_record_t *synth,
-                          const g1s_measure_srecord_t *ssynth, uint64_t frames, const g1s_y4m_info_t &info) {
-  std::vector<char> buf(1 << 16);
-  const long n = g1s_format_measure_scales(&total, &stotal, synth, ssynth, frames, info.bit_depth, info.nplanes, buf.data(), buf.size());
-  if (n < 0) return "formatting the scale report failed";
+// a report as a g1s_format_measure* call left it (n bytes of buf, n < 0: refused) into a file.  "" when fine
+std::string write_report(const char *path, const char *buf, long n, const char *kind) {
+  if (n < 0) return std::string("formatting the ") + kind + "report failed";
   FILE *f = std::fopen(path, "wb");
   if (!f) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(buf.data(), 1, (size_t)n, f) == (size_t)n;
+  const bool ok = std::fwrite(buf, 1, (size_t)n, f) == (size_t)n;
   if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
   return "";
 }
 
-// g1s_measure_new, g1s_measure_new_temporal, g1s_measure_new_modes and g1s_measure_new_scales: the same refusals, the same meter but for the buffers
-// of the modes
+// the reports of a clip's totals (beside `synth`'s, of the rendered clip, where there is one) into their files.  "" when fine
+std::string write_reports(const ReportPaths &out, const ClipTotals &t, const ClipTotals *synth, uint64_t frames, const g1s_y4m_info_t &i) {
+  std::vector<char> text(1 << 16);
+  char *buf = text.data();
+  const size_t cap = text.size();
+  const g1s_measure_record_t *plain2 = synth ? &synth->plain.total : nullptr;
+  long n = g1s_format_measure(&t.plain.total, plain2, frames, i.bit_depth, i.width, i.height, i.xdec, i.ydec, i.nplanes, buf, cap);
+  std::string why = write_report(out.plain, buf, n, "");
+  if (why.empty() && out.temporal) {
+    n = g1s_format_measure_temporal(&t.temporal.total, synth ? &synth->temporal.total : nullptr, t.temporal.count, i.bit_depth, i.width, i.height,
+                                    i.xdec, i.ydec, i.nplanes, buf, cap);
+    why = write_report(out.temporal, buf, n, "temporal ");
+  }
+  if (why.empty() && out.cross) {
+    n = g1s_format_measure_cross(&t.cross.total, synth ? &synth->cross.total : nullptr, frames, i.bit_depth, i.width, i.height, i.xdec, i.ydec, buf, cap);
+    why = write_report(out.cross, buf, n, "cross ");
+  }
+  if (why.empty() && out.scales) {
+    n = g1s_format_measure_scales(&t.plain.total, &t.scales.total, plain2, synth ? &synth->scales.total : nullptr, frames, i.bit_depth, i.nplanes, buf, cap);
+    why = write_report(out.scales, buf, n, "scale ");
+  }
+  return why;
+}
+
+// a meter for the kinds that have a report to go to
+g1s_measure_t *meter_for(const ReportPaths &out, uint32_t bit_depth, const g1s_measure_opts_t *opts) {
+  const uint32_t modes = (out.temporal ? G1S_MEASURE_TEMPORAL : 0u) | (out.cross ? G1S_MEASURE_CROSS : 0u);
+  return out.scales ? g1s_measure_new_scales(bit_depth, opts, modes) : g1s_measure_new_modes(bit_depth, opts, modes);
+}
+
+// g1s_measure_new, g1s_measure_new_temporal, g1s_measure_new_modes and g1s_measure_new_scales: the same refusals, the same
+// meter but for the lanes that are on
 g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes, bool scales = false) {
   g1s_set_global_error_("");
   if (modes & ~(uint32_t)(G1S_MEASURE_TEMPORAL | G1S_MEASURE_CROSS)) {
     g1s_set_global_error_("unknown mode bits: g1s_measure_new_modes takes G1S_MEASURE_TEMPORAL and G1S_MEASURE_CROSS");
     return nullptr;
   }
-  const bool temporal = (modes & G1S_MEASURE_TEMPORAL) != 0, cross = (modes & G1S_MEASURE_CROSS) != 0;
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
     g1s_set_global_error_("measure is defined for bit depths 8, 10 and 12");
     return nullptr;
@@ -1246,28 +1159,14 @@ g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, u
     return nullptr;
   }
   g1s_measure *m = new g1s_measure;
-  m->temporal = temporal, m->cross = cross, m->scales = scales;
+  m->plain.on = true, m->temporal.on = (modes & G1S_MEASURE_TEMPORAL) != 0, m->cross.on = (modes & G1S_MEASURE_CROSS) != 0, m->scales.on = scales;
   bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
   const uint32_t B = m->batch;
-  for (Event &e : m->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
   for (Event &e : m->ev_c) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  ok = ok && m->p_jobs.alloc(B) && hipMalloc((void **)&m->d_recs.p, sizeof(g1s_measure_record_t) * B) == hipSuccess &&
-       hipHostMalloc((void **)&m->h_recs.p, sizeof(g1s_measure_record_t) * B, hipHostMallocDefault) == hipSuccess;
-  if (temporal) {
-    for (Event &e : m->ev_t) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  ok = ok && m->p_jobs.alloc(B) && m->plain.alloc(B) && m->temporal.alloc(B) && m->cross.alloc(B) && m->scales.alloc(B);
+  if (m->temporal.on) {
     for (Event &e : m->ev_tc) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    ok = ok && m->p_tjobs.alloc(B) && hipMalloc((void **)&m->d_trecs.p, sizeof(g1s_measure_trecord_t) * B) == hipSuccess &&
-         hipHostMalloc((void **)&m->h_trecs.p, sizeof(g1s_measure_trecord_t) * B, hipHostMallocDefault) == hipSuccess;
-  }
-  if (cross) {
-    for (Event &e : m->ev_x) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    ok = ok && hipMalloc((void **)&m->d_xrecs.p, sizeof(g1s_measure_xrecord_t) * B) == hipSuccess &&
-         hipHostMalloc((void **)&m->h_xrecs.p, sizeof(g1s_measure_xrecord_t) * B, hipHostMallocDefault) == hipSuccess;
-  }
-  if (scales) {
-    for (Event &e : m->ev_s) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    ok = ok && hipMalloc((void **)&m->d_srecs.p, sizeof(g1s_measure_srecord_t) * B) == hipSuccess &&
-         hipHostMalloc((void **)&m->h_srecs.p, sizeof(g1s_measure_srecord_t) * B, hipHostMallocDefault) == hipSuccess;
+    ok = ok && m->p_tjobs.alloc(B);
   }
   if (!ok) {
     g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
@@ -1296,7 +1195,7 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
   const Refusal no = check_frame_pair(*noisy, *clean, m->bps, 65536u, "g1s_measure_new",
                                       "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)", "noisy and clean");
   if (no.code) return m->fail(no.code, no.text);
-  if (m->scales && !scales_size_ok(m->bit_depth, noisy->width, noisy->height)) return m->fail(G1S_ERR_INVALID, scales_refusal_text());
+  if (m->scales.on && !scales_size_ok(m->bit_depth, noisy->width, noisy->height)) return m->fail(G1S_ERR_INVALID, scales_refusal_text());
   int rc;
   if (m->have_geom && !m->geom.same_shape(*noisy)) {
     // a new geometry: what is queued goes out and finishes first, the buffers are sized again
@@ -1307,12 +1206,13 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
   MeasureJob job{};
   // a plain meter: the batch's slots; a temporal meter: rings of batch + 1 slots, so that the pair before the batch's first
   // pair is still there
-  const uint32_t slots = m->temporal ? m->batch + 1 : m->batch, slot = m->temporal ? m->ring_at : (uint32_t)m->jobs.size();
+  const bool temporal = m->temporal.on;
+  const uint32_t slots = temporal ? m->batch + 1 : m->batch, slot = temporal ? m->ring_at : (uint32_t)m->jobs.size();
   if ((rc = m->stage_in(*noisy, slot, slots, job.a, job.a_stride, 0)) != 0) return rc;
   if ((rc = m->stage_in(*clean, slot, slots, job.b, job.b_stride, 1)) != 0) return rc;
   if ((rc = m->wait_host_input(noisy->on_device == 0 ? *noisy : *clean)) != 0) return rc;
   m->jobs.push_back(job);
-  if (m->temporal) {
+  if (temporal) {
     if (m->have_prev) m->tjobs.push_back(TemporalJob{job, m->prev});
     m->prev = job, m->have_prev = true, m->ring_at = (slot + 1) % slots;
     m->prev_staged[0] = noisy->on_device != 1, m->prev_staged[1] = clean->on_device != 1;
@@ -1323,319 +1223,43 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
 int g1s_measure_cut(g1s_measure_t *m) {
   if (!m) return G1S_ERR_INVALID;
   if (m->err_code) return m->err_code;
-  if (!m->temporal) return not_temporal(m);
+  if (!m->temporal.on) return not_made_by(m, kTemporalMaker);
   (void)hipSetDevice(m->device);
   m->have_prev = false;
   return m->flush();
 }
 
+int g1s_measure_finish(g1s_measure_t *m, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out) {
+  return finish_kind(m, &g1s_measure::plain, "", per_frame, cap, n_out);
+}
+
 int g1s_measure_finish_temporal(g1s_measure_t *m, g1s_measure_trecord_t *per_pair, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  if (!m->temporal) return not_temporal(m);
-  (void)hipSetDevice(m->device);
-  int rc = m->flush();
-  if (rc || (rc = m->keep_prev()) != 0) return rc;
-  if (n_out) *n_out = m->trecords.size();
-  if (m->trecords.size() > cap || (!per_pair && !m->trecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-  if (!m->trecords.empty()) std::memcpy(per_pair, m->trecords.data(), sizeof(g1s_measure_trecord_t) * m->trecords.size());
-  m->trecords.clear();
-  return G1S_OK;
+  return finish_kind(m, &g1s_measure::temporal, kTemporalMaker, per_pair, cap, n_out);
 }
 
 int g1s_measure_finish_cross(g1s_measure_t *m, g1s_measure_xrecord_t *per_pair, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  if (!m->cross) return not_cross(m);
-  (void)hipSetDevice(m->device);
-  int rc = m->flush();
-  if (rc || (rc = m->keep_prev()) != 0) return rc;
-  if (n_out) *n_out = m->xrecords.size();
-  if (m->xrecords.size() > cap || (!per_pair && !m->xrecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-  if (!m->xrecords.empty()) std::memcpy(per_pair, m->xrecords.data(), sizeof(g1s_measure_xrecord_t) * m->xrecords.size());
-  m->xrecords.clear();
-  return G1S_OK;
+  return finish_kind(m, &g1s_measure::cross, kCrossMaker, per_pair, cap, n_out);
 }
 
 int g1s_measure_finish_scales(g1s_measure_t *m, g1s_measure_srecord_t *per_pair, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  if (!m->scales) return not_scales(m);
-  (void)hipSetDevice(m->device);
-  int rc = m->flush();
-  if (rc || (rc = m->keep_prev()) != 0) return rc;
-  if (n_out) *n_out = m->srecords.size();
-  if (m->srecords.size() > cap || (!per_pair && !m->srecords.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-  if (!m->srecords.empty()) std::memcpy(per_pair, m->srecords.data(), sizeof(g1s_measure_srecord_t) * m->srecords.size());
-  m->srecords.clear();
-  return G1S_OK;
+  return finish_kind(m, &g1s_measure::scales, kScalesMaker, per_pair, cap, n_out);
 }
 
-int g1s_measure_scales_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
-  if (!m) return G1S_ERR_INVALID;
-  if (ms_kernel) *ms_kernel = m->ms_skernel;
-  if (pairs) *pairs = m->spairs_timed;
-  return G1S_OK;
+int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {
+  if (m) m->timing = enable != 0;
+  return kind_timing(m, &g1s_measure::plain, ms_kernel, frames);
 }
 
-int g1s_measure_cross_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
-  if (!m) return G1S_ERR_INVALID;
-  if (ms_kernel) *ms_kernel = m->ms_xkernel;
-  if (pairs) *pairs = m->xpairs_timed;
-  return G1S_OK;
-}
+int g1s_measure_temporal_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) { return kind_timing(m, &g1s_measure::temporal, ms_kernel, pairs); }
+
+int g1s_measure_cross_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) { return kind_timing(m, &g1s_measure::cross, ms_kernel, pairs); }
+
+int g1s_measure_scales_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) { return kind_timing(m, &g1s_measure::scales, ms_kernel, pairs); }
 
 int g1s_measure_chroma_timing(g1s_measure_t *m, double *ms_chroma, double *ms_temporal_chroma) {
   if (!m) return G1S_ERR_INVALID;
   if (ms_chroma) *ms_chroma = m->ms_chroma;
   if (ms_temporal_chroma) *ms_temporal_chroma = m->ms_tchroma;
-  return G1S_OK;
-}
-
-int g1s_measure_temporal_timing(g1s_measure_t *m, double *ms_kernel, uint64_t *pairs) {
-  if (!m) return G1S_ERR_INVALID;
-  if (ms_kernel) *ms_kernel = m->ms_tkernel;
-  if (pairs) *pairs = m->pairs_timed;
-  return G1S_OK;
-}
-
-int g1s_measure_finish(g1s_measure_t *m, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  (void)hipSetDevice(m->device);
-  int rc = m->flush();
-  if (rc || (rc = m->keep_prev()) != 0) return rc;
-  if (n_out) *n_out = m->records.size();
-  if (m->records.size() > cap || (!per_frame && !m->records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-  if (!m->records.empty()) std::memcpy(per_frame, m->records.data(), sizeof(g1s_measure_record_t) * m->records.size());
-  m->records.clear();
-  return G1S_OK;
-}
-
-int g1s_measure_sum(const g1s_measure_record_t *recs, size_t n, g1s_measure_record_t *total) {
-  if (!total || (n && !recs)) return G1S_ERR_INVALID;
-  g1s_measure_record_t t;
-  std::memset(&t, 0, sizeof t);
-  bool ok = true;
-  for (size_t f = 0; f < n; ++f)
-    for (int c = 0; c < 3; ++c) {
-      for (int k = 0; k < kBins; ++k)
-        ok = checked_add(t.n[c][k], recs[f].n[c][k]) && checked_add(t.s1[c][k], recs[f].s1[c][k]) && checked_add(t.s2[c][k], recs[f].s2[c][k]) && ok;
-      for (int i = 0; i < kLags; ++i) ok = checked_add(t.r[c][i], recs[f].r[c][i]) && ok;
-    }
-  if (!ok) return G1S_ERR_INVALID;
-  *total = t;
-  return G1S_OK;
-}
-
-long g1s_format_measure(const g1s_measure_record_t *total, const g1s_measure_record_t *synth, uint64_t frames, uint32_t bit_depth, uint32_t width,
-                        uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap) {
-  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
-  g1s_frame_t shape{};
-  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = (uint8_t)nplanes;
-  const PlaneGeom g(shape, 1);
-  std::string s = "grainprofile1\n";
-  s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
-  for (int c = 0; c < (int)nplanes; ++c) {
-    s += "plane " + std::to_string(c) + "\n";
-    double terms[kLags];
-    for (int i = 0; i < kLags; ++i) {
-      int dx, dy;
-      lag_offset(i, &dx, &dy);
-      const int64_t tw = (int64_t)g.pw(c) - std::abs(dx), th = (int64_t)g.ph(c) - std::abs(dy);
-      terms[i] = tw > 0 && th > 0 ? (double)tw * (double)th * (double)frames : 0.0;
-    }
-    const Profile a = profile_of(*total, c, terms);
-    Profile b{};
-    if (synth) b = profile_of(*synth, c, terms);
-    for (int k = 0; k < kBins; ++k) {
-      if (!a.has[k]) continue;
-      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[c][k]) + " " + value(true, a.mean[k]) + " " + value(true, a.sigma[k]);
-      if (synth) s += " " + value(b.has[k], b.mean[k]) + " " + value(b.has[k], b.sigma[k]);
-      s += "\n";
-    }
-    for (int i = 0; i < 24; ++i) {
-      int dx, dy;
-      lag_offset(i, &dx, &dy);
-      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a.has_rho[i], a.rho[i]);
-      if (synth) s += " " + value(b.has_rho[i], b.rho[i]);
-      s += "\n";
-    }
-    if (synth) {
-      bool any = false;
-      double worst = 0.0, num = 0.0, den = 0.0;
-      for (int i = 0; i < 24; ++i)
-        if (a.has_rho[i] && b.has_rho[i]) {
-          const double e = std::fabs(b.rho[i] - a.rho[i]);
-          worst = !any || e > worst ? e : worst, any = true;
-        }
-      s += "max_rho_diff " + value(any, worst) + "\n";
-      for (int k = 0; k < kBins; ++k)
-        if (a.has[k] && b.has[k] && a.sigma[k] > 0.0 && b.sigma[k] > 0.0) {
-          const double n = (double)total->n[c][k];
-          num += n * (b.sigma[k] / a.sigma[k]), den += n;
-        }
-      s += "sigma_ratio " + value(den > 0.0, den > 0.0 ? num / den : 0.0) + "\n";
-    }
-  }
-  if (s.size() > cap) return G1S_ERR_CAPACITY;
-  std::memcpy(buf, s.data(), s.size());
-  return (long)s.size();
-}
-
-int g1s_measure_sum_temporal(const g1s_measure_trecord_t *recs, size_t n, g1s_measure_trecord_t *total) {
-  if (!total || (n && !recs)) return G1S_ERR_INVALID;
-  g1s_measure_trecord_t t;
-  std::memset(&t, 0, sizeof t);
-  bool ok = true;
-  for (size_t f = 0; f < n; ++f)
-    for (int c = 0; c < 3; ++c) {
-      for (int k = 0; k < kBins; ++k)
-        ok = checked_add(t.n[c][k], recs[f].n[c][k]) && checked_add(t.x[c][k], recs[f].x[c][k]) && checked_add(t.u[c][k], recs[f].u[c][k]) &&
-             checked_add(t.v[c][k], recs[f].v[c][k]) && ok;
-      for (int i = 0; i < kTLags; ++i) ok = checked_add(t.c[c][i], recs[f].c[c][i]) && ok;
-    }
-  if (!ok) return G1S_ERR_INVALID;
-  *total = t;
-  return G1S_OK;
-}
-
-long g1s_format_measure_temporal(const g1s_measure_trecord_t *total, const g1s_measure_trecord_t *synth, uint64_t pairs, uint32_t bit_depth,
-                                 uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, uint32_t nplanes, char *buf, size_t cap) {
-  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
-  g1s_frame_t shape{};
-  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = (uint8_t)nplanes;
-  const PlaneGeom g(shape, 1);
-  std::string s = "graintemporal1\n";
-  s += "pairs " + std::to_string(pairs) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
-  for (int c = 0; c < (int)nplanes; ++c) {
-    s += "plane " + std::to_string(c) + "\n";
-    if (!pairs) continue;
-    double terms[kTLags];
-    for (int i = 0; i < kTLags; ++i) {
-      int dx, dy;
-      temporal_offset(i, &dx, &dy);
-      const int64_t tw = (int64_t)g.pw(c) - std::abs(dx), th = (int64_t)g.ph(c) - std::abs(dy);
-      terms[i] = tw > 0 && th > 0 ? (double)pairs * (double)tw * (double)th : 0.0;
-    }
-    const TProfile a = tprofile_of(*total, c, terms);
-    TProfile b{};
-    if (synth) b = tprofile_of(*synth, c, terms);
-    for (int k = 0; k < kBins; ++k) {
-      if (!total->n[c][k]) continue;
-      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[c][k]) + " " + value(a.has_bin[k], a.bin[k]);
-      if (synth) s += " " + value(b.has_bin[k], b.bin[k]);
-      s += "\n";
-    }
-    for (int i = 0; i < kTLags; ++i) {
-      int dx, dy;
-      temporal_offset(i, &dx, &dy);
-      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a.has_lag[i], a.lag[i]);
-      if (synth) s += " " + value(b.has_lag[i], b.lag[i]);
-      s += "\n";
-    }
-    s += "temporal_rho " + value(a.has_lag[kTLags / 2], a.lag[kTLags / 2]);
-    if (synth) s += " " + value(b.has_lag[kTLags / 2], b.lag[kTLags / 2]);
-    s += "\npeak_rho " + peak_text(a);
-    if (synth) s += " " + peak_text(b);
-    s += "\n";
-  }
-  if (s.size() > cap) return G1S_ERR_CAPACITY;
-  std::memcpy(buf, s.data(), s.size());
-  return (long)s.size();
-}
-
-int g1s_measure_sum_cross(const g1s_measure_xrecord_t *recs, size_t n, g1s_measure_xrecord_t *total) {
-  return g1s_measure_sum_temporal(recs, n, total);  // (one type, one body: the pairing stands where the plane does)
-}
-
-long g1s_format_measure_cross(const g1s_measure_xrecord_t *total, const g1s_measure_xrecord_t *synth, uint64_t frames, uint32_t bit_depth,
-                              uint32_t width, uint32_t height, uint32_t xdec, uint32_t ydec, char *buf, size_t cap) {
-  if (!total || (!buf && cap) || xdec > 1 || ydec > xdec || width < 1 || height < 1) return G1S_ERR_INVALID;
-  g1s_frame_t shape{};
-  shape.width = width, shape.height = height, shape.xdec = (uint8_t)xdec, shape.ydec = (uint8_t)ydec, shape.nplanes = 3;
-  const PlaneGeom g(shape, 1);
-  static const char *const names[3] = {"cb_luma", "cr_luma", "cb_cr"};
-  std::string s = "graincross1\n";
-  s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + "\n";
-  double terms[kTLags];
-  for (int i = 0; i < kTLags; ++i) {
-    int dx, dy;
-    temporal_offset(i, &dx, &dy);
-    const int64_t tw = (int64_t)g.pw(1) - std::abs(dx), th = (int64_t)g.ph(1) - std::abs(dy);
-    terms[i] = tw > 0 && th > 0 ? (double)frames * (double)tw * (double)th : 0.0;
-  }
-  // the printed values of a pairing of a record: rule 11's profile (the layouts are one), the slopes beside it
-  struct XProfile {
-    TProfile t;
-    bool has_slope[kBins], has_beta;
-    double slope[kBins], beta;
-  };
-  auto xprofile_of = [&](const g1s_measure_xrecord_t &r, int j) {
-    XProfile p{};
-    p.t = tprofile_of(r, j, terms);
-    uint64_t V = 0;
-    for (int k = 0; k < kBins; ++k) {
-      V += r.v[j][k];
-      p.has_slope[k] = r.v[j][k] != 0;
-      if (p.has_slope[k]) p.slope[k] = (double)r.x[j][k] / (double)r.v[j][k];
-    }
-    p.has_beta = V != 0;
-    if (p.has_beta) p.beta = (double)r.c[j][kTLags / 2] / (double)V;
-    return p;
-  };
-  // partial_rho of the three zero_rho of a column
-  auto partial = [](const XProfile q[3]) {
-    const int z = kTLags / 2;
-    if (!q[0].t.has_lag[z] || !q[1].t.has_lag[z] || !q[2].t.has_lag[z]) return value(false, 0.0);
-    const double r0 = q[0].t.lag[z], r1 = q[1].t.lag[z], r2 = q[2].t.lag[z];
-    const double f0 = 1.0 - r0 * r0, f1 = 1.0 - r1 * r1;
-    if (f0 <= 0.0 || f1 <= 0.0) return value(false, 0.0);
-    return value(true, (r2 - r0 * r1) / std::sqrt(f0 * f1));
-  };
-  XProfile a[3], b[3];
-  for (int j = 0; j < 3; ++j) {
-    s += std::string("pairing ") + names[j] + "\n";
-    if (!frames) continue;
-    a[j] = xprofile_of(*total, j);
-    if (synth) b[j] = xprofile_of(*synth, j);
-    for (int k = 0; k < kBins; ++k) {
-      if (!total->n[j][k]) continue;
-      s += "bin " + std::to_string(k) + " " + std::to_string(total->n[j][k]) + " " + value(a[j].t.has_bin[k], a[j].t.bin[k]) + " " +
-           value(a[j].has_slope[k], a[j].slope[k]);
-      if (synth) s += " " + value(b[j].t.has_bin[k], b[j].t.bin[k]) + " " + value(b[j].has_slope[k], b[j].slope[k]);
-      s += "\n";
-    }
-    for (int i = 0; i < kTLags; ++i) {
-      int dx, dy;
-      temporal_offset(i, &dx, &dy);
-      s += "lag " + std::to_string(dx) + " " + std::to_string(dy) + " " + value(a[j].t.has_lag[i], a[j].t.lag[i]);
-      if (synth) s += " " + value(b[j].t.has_lag[i], b[j].t.lag[i]);
-      s += "\n";
-    }
-    s += "zero_rho " + value(a[j].t.has_lag[kTLags / 2], a[j].t.lag[kTLags / 2]);
-    if (synth) s += " " + value(b[j].t.has_lag[kTLags / 2], b[j].t.lag[kTLags / 2]);
-    s += "\npeak_rho " + peak_text(a[j].t);
-    if (synth) s += " " + peak_text(b[j].t);
-    s += "\nbeta " + value(a[j].has_beta, a[j].beta);
-    if (synth) s += " " + value(b[j].has_beta, b[j].beta);
-    s += "\n";
-    if (j == 2) {
-      s += "partial_rho " + partial(a);
-      if (synth) s += " " + partial(b);
-      s += "\n";
-    }
-  }
-  if (s.size() > cap) return G1S_ERR_CAPACITY;
-  std::memcpy(buf, s.data(), s.size());
-  return (long)s.size();
-}
-
-int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {
-  if (!m) return G1S_ERR_INVALID;
-  m->timing = enable != 0;
-  if (ms_kernel) *ms_kernel = m->ms_kernel;
-  if (frames) *frames = m->frames_timed;
   return G1S_OK;
 }
 
@@ -1675,24 +1299,11 @@ int64_t g1s_measure_y4m_files_scales(const char *noisy, const char *clean, const
   int rc = G1S_OK;
   std::string why;
   int64_t frames = 0;
-  g1s_measure_record_t total;
-  std::memset(&total, 0, sizeof total);
-  std::vector<g1s_measure_record_t> scratch;
-  g1s_measure_trecord_t ttotal;
-  std::memset(&ttotal, 0, sizeof ttotal);
-  std::vector<g1s_measure_trecord_t> tscratch;
-  uint64_t pairs = 0;
-  g1s_measure_xrecord_t xtotal;
-  std::memset(&xtotal, 0, sizeof xtotal);
-  std::vector<g1s_measure_xrecord_t> xscratch;
-  g1s_measure_srecord_t stotal;
-  std::memset(&stotal, 0, sizeof stotal);
-  std::vector<g1s_measure_srecord_t> sscratch;
-  const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
+  const ReportPaths out{out_report, out_treport, out_xreport, out_sreport};
+  ClipTotals totals;
   if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
   if (!rc && out_xreport && ia.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
-  if (!rc && !(m = out_sreport ? g1s_measure_new_scales(ia.bit_depth, opts, modes) : g1s_measure_new_modes(ia.bit_depth, opts, modes)))
-    rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && !(m = meter_for(out, ia.bit_depth, opts))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   while (!rc) {
     g1s_frame_t fa, fb;
     const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
@@ -1710,21 +1321,10 @@ int64_t g1s_measure_y4m_files_scales(const char *noisy, const char *clean, const
       break;
     }
     ++frames;
-    if (frames % m->batch == 0) {
-      if (!(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_sreport && !(why = take_srecords(m, sscratch, stotal)).empty()) rc = G1S_ERR_INVALID;
-    }
+    if (frames % m->batch == 0 && !(why = totals.take(m, out)).empty()) rc = G1S_ERR_INVALID;
   }
-  if (!rc && !(why = take_records(m, scratch, total)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_treport && !(why = take_trecords(m, tscratch, ttotal, pairs)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_xreport && !(why = take_xrecords(m, xscratch, xtotal)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_sreport && !(why = take_srecords(m, sscratch, stotal)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && !(why = write_report(out_report, total, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_treport && !(why = write_treport(out_treport, ttotal, nullptr, pairs, ia)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_sreport && !(why = write_sreport(out_sreport, total, stotal, nullptr, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && !(why = totals.take(m, out)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && !(why = write_reports(out, totals, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
   g1s_measure_free(m);
   g1s_y4m_close(ya);
   g1s_y4m_close(yb);
@@ -1781,24 +1381,11 @@ int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, con
   std::string why;
   int64_t frames = 0;
   uint32_t group = 0, in_group = 0;
-  g1s_measure_record_t total_s, total_r;
-  std::memset(&total_s, 0, sizeof total_s), std::memset(&total_r, 0, sizeof total_r);
-  std::vector<g1s_measure_record_t> scratch;
-  g1s_measure_trecord_t ttotal_s, ttotal_r;
-  std::memset(&ttotal_s, 0, sizeof ttotal_s), std::memset(&ttotal_r, 0, sizeof ttotal_r);
-  std::vector<g1s_measure_trecord_t> tscratch;
-  uint64_t pairs_s = 0, pairs_r = 0;
-  g1s_measure_xrecord_t xtotal_s, xtotal_r;
-  std::memset(&xtotal_s, 0, sizeof xtotal_s), std::memset(&xtotal_r, 0, sizeof xtotal_r);
-  std::vector<g1s_measure_xrecord_t> xscratch;
-  g1s_measure_srecord_t stotal_s, stotal_r;
-  std::memset(&stotal_s, 0, sizeof stotal_s), std::memset(&stotal_r, 0, sizeof stotal_r);
-  std::vector<g1s_measure_srecord_t> sscratch;
-  const uint32_t modes = (out_treport ? G1S_MEASURE_TEMPORAL : 0u) | (out_xreport ? G1S_MEASURE_CROSS : 0u);
-  auto meter = [&]() { return out_sreport ? g1s_measure_new_scales(id.bit_depth, opts, modes) : g1s_measure_new_modes(id.bit_depth, opts, modes); };
+  const ReportPaths out{out_report, out_treport, out_xreport, out_sreport};
+  ClipTotals total_s, total_r;
   if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
   if (!rc && out_xreport && id.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
-  if (!rc && (!(ms = meter()) || !(mr = meter()))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  if (!rc && (!(ms = meter_for(out, id.bit_depth, opts)) || !(mr = meter_for(out, id.bit_depth, opts)))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
   if (!rc) {
     g1s_grain_opts_t go{};
     if (gopts) go = *gopts;
@@ -1830,11 +1417,8 @@ int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, con
       else if ((rc = g1s_measure_frame(mr, &r, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(mr);
     }
     // (a temporal meter keeps a copy of the group's last pair on the device: the group's buffers are free again all the same)
-    for (int k = 0; k < 2 && !rc; ++k)
-      if (!(why = take_records(k ? mr : ms, scratch, k ? total_r : total_s)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_treport && !(why = take_trecords(k ? mr : ms, tscratch, k ? ttotal_r : ttotal_s, k ? pairs_r : pairs_s)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_xreport && !(why = take_xrecords(k ? mr : ms, xscratch, k ? xtotal_r : xtotal_s)).empty()) rc = G1S_ERR_INVALID;
-      else if (out_sreport && !(why = take_srecords(k ? mr : ms, sscratch, k ? stotal_r : stotal_s)).empty()) rc = G1S_ERR_INVALID;
+    if (!rc && !(why = total_s.take(ms, out)).empty()) rc = G1S_ERR_INVALID;
+    if (!rc && !(why = total_r.take(mr, out)).empty()) rc = G1S_ERR_INVALID;
     in_group = 0;
   };
   while (!rc) {
@@ -1870,10 +1454,7 @@ int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, con
     if (++in_group == group) end_group();
   }
   if (!rc && in_group) end_group();
-  if (!rc && !(why = write_report(out_report, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_treport && !(why = write_treport(out_treport, ttotal_s, &ttotal_r, pairs_s, id)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_xreport && !(why = write_xreport(out_xreport, xtotal_s, &xtotal_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_sreport && !(why = write_sreport(out_sreport, total_s, stotal_s, &total_r, &stotal_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && !(why = write_reports(out, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
   if (ms) (void)hipSetDevice(ms->device);
   g1s_grain_free(gr);
   g1s_measure_free(mr);

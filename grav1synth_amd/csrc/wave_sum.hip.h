@@ -1,5 +1,5 @@
 // wave_sum.hip.h -- integer sums across the 64 lanes of a wave in the VALU (DPP), every lane taking part: what the binned
-// kernels (km_measure in measure.hip, k_nlf in nlf.hip) hand a bin's sums on with.
+// kernels (km_measure, lag_pass and km_measure_s in measure.hip, k_nlf in nlf.hip) hand a bin's sums on with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -119,14 +119,18 @@ class GrainMeter(FrameOp):
         """Launches what is queued, waits, and returns the records since the last finish(), one a pair, in order.  The
         meter can be used again.  cap: the size of the buffer handed to the library (a test aid; too small raises
         G1S_ERR_CAPACITY and loses nothing)."""
+        return self._finish(self._L.g1s_measure_finish, RECORD, cap)
+
+    def _finish(self, fn, dtype: np.dtype, cap: Optional[int]) -> np.ndarray:
+        """A g1s_measure_finish* call: the size asked for first unless `cap` gives it, then the records."""
         n = C.c_size_t()
         if cap is None:
-            rc = self._L.g1s_measure_finish(self._h, None, 0, C.byref(n))
+            rc = fn(self._h, None, 0, C.byref(n))
             if rc not in (0, _lib.G1S_ERR_CAPACITY):
                 self._check(rc)
             cap = n.value
-        out = np.zeros(max(cap, 1), RECORD)
-        rc = self._L.g1s_measure_finish(self._h, out.ctypes.data, cap, C.byref(n))
+        out = np.zeros(max(cap, 1), dtype)
+        rc = fn(self._h, out.ctypes.data, cap, C.byref(n))
         if rc == _lib.G1S_ERR_CAPACITY:
             raise G1SError(rc, f"{n.value} records do not fit {cap}")
         self._check(rc)
@@ -141,65 +145,25 @@ class GrainMeter(FrameOp):
     def finish_temporal(self, cap: Optional[int] = None) -> np.ndarray:
         """As finish(), for the temporal records of a temporal meter: one for every pair that has a predecessor in its run,
         in order, since the last finish_temporal().  The ordinary records stay until finish() fetches them."""
-        n = C.c_size_t()
-        if cap is None:
-            rc = self._L.g1s_measure_finish_temporal(self._h, None, 0, C.byref(n))
-            if rc not in (0, _lib.G1S_ERR_CAPACITY):
-                self._check(rc)
-            cap = n.value
-        out = np.zeros(max(cap, 1), TRECORD)
-        rc = self._L.g1s_measure_finish_temporal(self._h, out.ctypes.data, cap, C.byref(n))
-        if rc == _lib.G1S_ERR_CAPACITY:
-            raise G1SError(rc, f"{n.value} records do not fit {cap}")
-        self._check(rc)
-        self._keep.clear()
-        return out[:n.value]
+        return self._finish(self._L.g1s_measure_finish_temporal, TRECORD, cap)
 
     def finish_cross(self, cap: Optional[int] = None) -> np.ndarray:
         """As finish(), for the cross records of a cross meter: one for every pair, in order, since the last finish_cross()
         (zeros for a pair with one plane).  The ordinary and the temporal records stay until their own calls fetch them."""
-        n = C.c_size_t()
-        if cap is None:
-            rc = self._L.g1s_measure_finish_cross(self._h, None, 0, C.byref(n))
-            if rc not in (0, _lib.G1S_ERR_CAPACITY):
-                self._check(rc)
-            cap = n.value
-        out = np.zeros(max(cap, 1), XRECORD)
-        rc = self._L.g1s_measure_finish_cross(self._h, out.ctypes.data, cap, C.byref(n))
-        if rc == _lib.G1S_ERR_CAPACITY:
-            raise G1SError(rc, f"{n.value} records do not fit {cap}")
-        self._check(rc)
-        self._keep.clear()
-        return out[:n.value]
+        return self._finish(self._L.g1s_measure_finish_cross, XRECORD, cap)
 
     def finish_scales(self, cap: Optional[int] = None) -> np.ndarray:
         """As finish(), for the scale records of a scales meter: one for every pair, in order, since the last finish_scales().
         The other records stay until their own calls fetch them."""
-        n = C.c_size_t()
-        if cap is None:
-            rc = self._L.g1s_measure_finish_scales(self._h, None, 0, C.byref(n))
-            if rc not in (0, _lib.G1S_ERR_CAPACITY):
-                self._check(rc)
-            cap = n.value
-        out = np.zeros(max(cap, 1), SRECORD)
-        rc = self._L.g1s_measure_finish_scales(self._h, out.ctypes.data, cap, C.byref(n))
-        if rc == _lib.G1S_ERR_CAPACITY:
-            raise G1SError(rc, f"{n.value} records do not fit {cap}")
-        self._check(rc)
-        self._keep.clear()
-        return out[:n.value]
+        return self._finish(self._L.g1s_measure_finish_scales, SRECORD, cap)
 
     def scales_kernel_times(self) -> Tuple[float, int]:
         """(ms in km_measure_s and its summing launch, scale records) of the batches kernel_times() had timed."""
-        a, n = C.c_double(), C.c_uint64()
-        self._L.g1s_measure_scales_timing(self._h, C.byref(a), C.byref(n))
-        return a.value, n.value
+        return self._times(self._L.g1s_measure_scales_timing)
 
     def cross_kernel_times(self) -> Tuple[float, int]:
         """(ms in km_measure_x and its summing launch, cross records) of the batches kernel_times() had timed."""
-        a, n = C.c_double(), C.c_uint64()
-        self._L.g1s_measure_cross_timing(self._h, C.byref(a), C.byref(n))
-        return a.value, n.value
+        return self._times(self._L.g1s_measure_cross_timing)
 
     def chroma_kernel_times(self) -> Tuple[float, float]:
         """(ms in km_measure's chroma launches, ms in km_measure_t's chroma launches) of the batches kernel_times() had timed."""
@@ -209,25 +173,32 @@ class GrainMeter(FrameOp):
 
     def temporal_kernel_times(self) -> Tuple[float, int]:
         """(ms in km_measure_t and km_tail_t, temporal records) of the batches kernel_times() had timed."""
-        a, n = C.c_double(), C.c_uint64()
-        self._L.g1s_measure_temporal_timing(self._h, C.byref(a), C.byref(n))
-        return a.value, n.value
+        return self._times(self._L.g1s_measure_temporal_timing)
 
     def kernel_times(self, enable: bool = True) -> Tuple[float, int]:
         """(ms in km_measure and km_tail, frames) of the timed batches so far (HIP events); enables / disables the timing."""
+        return self._times(self._L.g1s_measure_set_timing, int(enable))
+
+    def _times(self, fn, *args) -> Tuple[float, int]:
+        """A g1s_measure_*_timing call: (ms, records)."""
         a, n = C.c_double(), C.c_uint64()
-        self._L.g1s_measure_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
+        fn(self._h, *args, C.byref(a), C.byref(n))
         return a.value, n.value
+
+
+def _sum(fn, dtype: np.dtype, records: np.ndarray, what: str) -> np.ndarray:
+    """A g1s_measure_sum* call over records of `dtype`; `what`: "", "temporal " ... in the text of an overflow."""
+    records = np.ascontiguousarray(records, dtype).reshape(-1)
+    total = np.zeros((), dtype)
+    rc = fn(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, f"the clip's {what}sums leave 64 bits")
+    return total
 
 
 def sum_records(records: np.ndarray) -> np.ndarray:
     """Rule 6: a clip's record from its frames' (g1s_measure_sum; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, RECORD).reshape(-1)
-    total = np.zeros((), RECORD)
-    rc = _lib.lib().g1s_measure_sum(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
-    if rc:
-        raise G1SError(rc, "the clip's sums leave 64 bits")
-    return total
+    return _sum(_lib.lib().g1s_measure_sum, RECORD, records, "")
 
 
 def format_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1, nplanes: int = 3,
@@ -245,12 +216,7 @@ def format_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, h
 
 def sum_temporal_records(records: np.ndarray) -> np.ndarray:
     """Rule 10: a clip's temporal record from its pairs' (g1s_measure_sum_temporal; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, TRECORD).reshape(-1)
-    total = np.zeros((), TRECORD)
-    rc = _lib.lib().g1s_measure_sum_temporal(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
-    if rc:
-        raise G1SError(rc, "the clip's temporal sums leave 64 bits")
-    return total
+    return _sum(_lib.lib().g1s_measure_sum_temporal, TRECORD, records, "temporal ")
 
 
 def format_temporal_profile(total: np.ndarray, pairs: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1, nplanes: int = 3,
@@ -269,12 +235,7 @@ def format_temporal_profile(total: np.ndarray, pairs: int, bit_depth: int, width
 
 def sum_cross_records(records: np.ndarray) -> np.ndarray:
     """Rule 16: a clip's cross record from its pairs' (g1s_measure_sum_cross; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, XRECORD).reshape(-1)
-    total = np.zeros((), XRECORD)
-    rc = _lib.lib().g1s_measure_sum_cross(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
-    if rc:
-        raise G1SError(rc, "the clip's cross sums leave 64 bits")
-    return total
+    return _sum(_lib.lib().g1s_measure_sum_cross, XRECORD, records, "cross ")
 
 
 def format_cross_profile(total: np.ndarray, frames: int, bit_depth: int, width: int, height: int, xdec: int = 1, ydec: int = 1,
@@ -293,12 +254,7 @@ def format_cross_profile(total: np.ndarray, frames: int, bit_depth: int, width: 
 
 def sum_scale_records(records: np.ndarray) -> np.ndarray:
     """Rule 22: a clip's scale record from its pairs' (g1s_measure_sum_scales; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, SRECORD).reshape(-1)
-    total = np.zeros((), SRECORD)
-    rc = _lib.lib().g1s_measure_sum_scales(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
-    if rc:
-        raise G1SError(rc, "the clip's scale sums leave 64 bits")
-    return total
+    return _sum(_lib.lib().g1s_measure_sum_scales, SRECORD, records, "scale ")
 
 
 def format_scale_profile(total: np.ndarray, stotal: np.ndarray, frames: int, bit_depth: int, nplanes: int = 3,

@@ -390,3 +390,16 @@ def test_measure_and_check_scales_on_files(tmp_path):
     assert check_y4m_files(str(a), str(b), str(tbl), str(o2), batch_frames=2, scales_output=str(s2)) == (n, False)
     assert o2.read_bytes() == fit and s2.read_bytes() == swant
     assert check_y4m_files(str(a), str(b), str(tbl), str(o2)) == (n, False) and o2.read_bytes() == fit
+    # all four kinds in one run of either command, small batches: every report the bytes a run with that output alone writes
+    kinds = ("temporal_output", "cross_output", "scales_output")
+    for name, run in (("measure", lambda o, **kw: measure_y4m_files(str(a), str(b), str(o), **kw)),
+                      ("check", lambda o, **kw: check_y4m_files(str(a), str(b), str(tbl), str(o), **kw))):
+        plain = tmp_path / f"{name}_all.txt"
+        together = {k: tmp_path / f"{name}_all_{k}.txt" for k in kinds}
+        assert run(plain, batch_frames=2, **{k: str(v) for k, v in together.items()}) == (n, False)
+        assert plain.read_bytes() == (profile if name == "measure" else fit)
+        for k in kinds:
+            alone, alone_plain = tmp_path / f"{name}_alone_{k}.txt", tmp_path / f"{name}_alone_{k}_plain.txt"
+            assert run(alone_plain, **{k: str(alone)}) == (n, False)
+            assert alone_plain.read_bytes() == plain.read_bytes(), (name, k)
+            assert together[k].read_bytes() == alone.read_bytes() and len(alone.read_bytes()) > 100, (name, k)

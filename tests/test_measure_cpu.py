@@ -227,3 +227,97 @@ def test_measure_and_check_refuse_like_diff(tmp_path, caplog):
     assert (args.command, args.grain, args.overwrite, args.clip_restricted, args.device) == ("check", t, True, True, 2)
     args = cli.build_parser().parse_args(["measure", a, b, "-o", out])
     assert (args.command, args.noisy, args.clean, args.overwrite) == ("measure", a, b, False)
+
+
+# ------------------------------------------------------------------------------ the report code under the sanitizers
+def _edge_records(ref, sign):
+    """Two records of a kind whose entries sum to within a few hundred of the 64-bit edges, every entry another value; the
+    signed fields alternate in sign (from `sign` on)."""
+    a, b = ref.empty_record(), ref.empty_record()
+    for name in a:
+        k = np.arange(a[name].size, dtype=object).reshape(a[name].shape) % 97
+        if a[name].dtype == np.uint64:
+            a[name][...] = ((2 ** 64 - 1) - 3 * k).astype(np.uint64)
+            b[name][...] = (2 * k).astype(np.uint64)
+        else:
+            s = np.where((k + sign) % 2 == 0, 1, -1).astype(object)
+            a[name][...] = (s * ((2 ** 63 - 1) - 5 * k)).astype(np.int64)
+            b[name][...] = (s * 4 * k).astype(np.int64)
+    return [a, b]
+
+
+def _report_sets():
+    """(name, header fields, the records of the four kinds, the same for the second column or None)"""
+    from tests import measure_s_ref as S
+    from tests import measure_t_ref as T
+    from tests import measure_x_ref as X
+
+    def clip(seed):
+        pairs = [planes_of(45, 31, 10, "420", seed=seed + k, amp=30 + 10 * k) for k in range(3)]
+        return ([R.measure_frame(n, c, 10, 1, 1) for n, c in pairs], T.run_records(pairs, 10, 1, 1), [X.cross_frame(n, c, 10, 1, 1) for n, c in pairs],
+                [S.scale_frame(n, c, 10, 1, 1) for n, c in pairs])
+
+    refs = (R, T, X, S)
+    yield "designed", dict(frames=3, pairs=2, bd=10, w=45, h=31, xdec=1, ydec=1, nplanes=3), clip(40), clip(50)
+    yield "zero", dict(frames=0, pairs=0, bd=8, w=9, h=7, xdec=0, ydec=0, nplanes=1), tuple([m.empty_record()] for m in refs), None
+    yield ("edge", dict(frames=2, pairs=2, bd=12, w=64, h=48, xdec=1, ydec=0, nplanes=3), tuple(_edge_records(m, 0) for m in refs),
+           tuple(_edge_records(m, 1)[::-1] for m in refs))
+
+
+def test_the_report_code_under_the_sanitizers(tmp_path):
+    """csrc/measure_report.cpp with tests/measure_report_host.cpp, a program of its own: the sums and the four reports of three
+    record sets against the restatements and against the library's bytes, every report into a buffer of exactly its size and
+    refused by one a byte shorter, every sum refused on an overflowing pair."""
+    from grav1synth_amd import measure as M
+    from tests import measure_s_ref as S
+    from tests import measure_t_ref as T
+    from tests import measure_x_ref as X
+
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    exe = tmp_path / "measure_report_host"
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
+           os.path.join(ROOT, "tests", "measure_report_host.cpp"), os.path.join(ROOT, "grav1synth_amd", "csrc", "measure_report.cpp")]
+    # (the sanitizer's runtime inside the program where the compiler can do that: it then starts under any preloaded library)
+    if subprocess.call(cmd + ["-static-libasan"], stderr=subprocess.DEVNULL) != 0:
+        subprocess.check_call(cmd)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    refs, dtypes = (R, T, X, S), (M.RECORD, M.TRECORD, M.XRECORD, M.SRECORD)
+    sums = (M.sum_records, M.sum_temporal_records, M.sum_cross_records, M.sum_scale_records)
+    for name, g, first, second in _report_sets():
+        columns = [first] + ([second] if second is not None else [])
+        blob = np.array([g["frames"], g["pairs"], g["bd"], g["w"], g["h"], g["xdec"], g["ydec"], g["nplanes"]] + [len(k) for k in first] +
+                        [second is not None], "<u8").tobytes()
+        structs = [[np.array([m.to_struct(r, dt) for r in recs], dt) for m, dt, recs in zip(refs, dtypes, col)] for col in columns]
+        blob += b"".join(s.tobytes() for col in structs for s in col)
+        path = tmp_path / f"{name}.bin"
+        path.write_bytes(blob)
+        p = subprocess.run([str(exe), str(path)], env=env, capture_output=True, timeout=600)
+        assert p.returncode == 0, (name, p.stderr[-3000:].decode())
+        got, rest = {}, p.stdout
+        for kind in ("plain", "temporal", "cross", "scales"):
+            head, rest = rest.split(b"\n", 1)
+            word, k, size = head.split()
+            assert (word, k) == (b"report", kind.encode()), head
+            got[kind], rest = rest[:int(size)], rest[int(size):]
+        assert rest == b"refusals ok\n", rest
+        # the restatements, from their own sums
+        t = [[m.sum_records(recs) for m, recs in zip(refs, col)] for col in columns]
+        syn = t[1] if second is not None else [None] * 4
+        geom = (g["bd"], g["w"], g["h"], g["xdec"], g["ydec"])
+        want = dict(plain=R.format_profile(t[0][0], g["frames"], *geom, g["nplanes"], synth=syn[0]),
+                    temporal=T.format_temporal(t[0][1], g["pairs"], *geom, g["nplanes"], synth=syn[1]),
+                    cross=X.format_cross(t[0][2], g["frames"], *geom, synth=syn[2]),
+                    scales=S.format_scales(t[0][0], t[0][3], g["frames"], g["bd"], g["nplanes"], synth=syn[0], ssynth=syn[3]))
+        # the library's bytes, from its own sums
+        lt = [[f(s) for f, s in zip(sums, col)] for col in structs]
+        ls = lt[1] if second is not None else [None] * 4
+        lib = dict(plain=M.format_profile(lt[0][0], g["frames"], *geom, g["nplanes"], synth=ls[0]),
+                   temporal=M.format_temporal_profile(lt[0][1], g["pairs"], *geom, g["nplanes"], synth=ls[1]),
+                   cross=M.format_cross_profile(lt[0][2], g["frames"], *geom, synth=ls[2]),
+                   scales=M.format_scale_profile(lt[0][0], lt[0][3], g["frames"], g["bd"], g["nplanes"], synth=ls[0], ssynth=ls[3]))
+        for kind in got:
+            assert got[kind] == want[kind], (name, kind, got[kind][:600], want[kind][:600])
+            assert got[kind] == lib[kind], (name, kind)
+        assert len(got["plain"]) > 100 and got["cross"].startswith(b"graincross1\n")
