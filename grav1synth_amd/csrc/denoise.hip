@@ -2,28 +2,32 @@
 //
 // The filter is defined in include/g1s_diff.h ("denoise", rules 1 - 4); tests/denoise_ref.py restates it in numpy.  It is
 // this project's own definition of non-local means: ffmpeg's nlmeans and KNLMeansCL have the same structure, not the
-// same bits.  Two kernels, a workgroup per (tile, plane of the class, frame), the phases of denoise_tile.hip.h:
-// kd_nlm<S, BPS> for one frame on its own (temporal radius 0, rules 1 - 4) and kd_nlm_t<S, BPS>, which goes on over the
-// frames around it (rules 5 - 7).  A batch of frames goes out as one launch per plane class (luma; the two chroma planes)
-// on the denoiser's own stream.  Under G1S_DENOISE_JOINT_CHROMA (rules 8 - 11) the chroma launch is kd_nlm_j<S, BPS> or
-// kd_nlm_jt<S, BPS> instead: a workgroup per (chroma tile, frame) that filters both chroma planes with one weight.
+// same bits.  One filter kernel, kd_nlm<Form, S, BPS>, a workgroup per (tile, plane of the class, frame), the phases of
+// denoise_tile.hip.h: Form::kPlain is one frame on its own (temporal radius 0, rules 1 - 4), Form::kTemporal goes on over the
+// frames around it (rules 5 - 7), Form::kMotion reads them where kd_motion's vectors point (rules 16 - 20).  A batch of frames
+// goes out as one launch per plane class (luma; the two chroma planes) on the denoiser's own stream.  Under
+// G1S_DENOISE_JOINT_CHROMA (rules 8 - 11) the chroma launch is kd_nlm_j<Form, S, BPS> instead: a workgroup per (chroma tile,
+// frame) that filters both chroma planes with one weight; with a chroma gain (rules 21 - 24) kd_nlm_j<Form, S, BPS, GainArg>.
 // Planes are independent (under the flag the chroma launch also reads the luma input), but `out` must not overlap `in`: a
 // tile reads the halo its neighbours write.
 //
 // The engine numbers the frames handed over since the denoiser was made.  With temporal radius D a frame is launched once
 // the D frames after it are there (or the clip ends), so the queue holds the frames not yet launched and, in front of
 // them, the last D that were: their planes are the neighbours of what comes next.
+//
+// This file: the kernels, the engine and the per-frame ABI.  The file commands are denoise_file.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <sys/stat.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/g1s_diff.h"
@@ -31,11 +35,6 @@
 #include "curve_row.hip.h"
 #include "denoise_tile.hip.h"
 #include "frame_op.h"
-#include "nlf.h"
-
-extern "C" void g1s_diff_set_error_text_(g1s_diff_t *, const char *);
-extern "C" int32_t g1s_diff_device_(const g1s_diff_t *);
-extern "C" uint32_t g1s_diff_frames_in_flight_max_(const g1s_diff_t *);
 
 namespace {
 
@@ -47,50 +46,54 @@ struct DenoiseJob {
   uint32_t in_stride[3], out_stride[3];  // bytes
 };
 
-struct DenoiseParams {
-  const DenoiseJob *jobs;
-  const uint16_t *table;  // the class's 1024 weights
-  int q, A;
-  int W, H, tiles_x;  // the class's plane size
-  int plane0;         // first plane of the class: 0 luma, 1 chroma
-};
-
-// the temporal kernel's job: the frame and, per plane, the 2 D frames around it (null: the clip has no such frame)
+// the temporal kernels' job: the frame and, per plane, the 2 D frames around it (null: the clip has no such frame)
 struct DenoiseJobT {
   DenoiseJob f;
   const uint8_t *nb[3][2 * kMaxD];
   uint32_t nb_stride[3][2 * kMaxD];
 };
 
-struct DenoiseParamsT {
-  const DenoiseJobT *jobs;
-  const uint16_t *table;
-  int q, A;
-  int W, H, tiles_x;
-  int plane0;
-  int nnb;  // 2 D
-};
-
 // the same under motion (rules 16 - 20): the frame's vectors, per plane [2 D][blocks of the plane] pairs of int8 (mx, my);
-// kd_motion writes them, kd_nlm_tm and kd_nlm_jtm read them.  Under the joint flag mv[2] is mv[1].
+// kd_motion writes them, the filter kernels of Form::kMotion read them.  Under the joint flag mv[2] is mv[1].
 struct DenoiseJobTM {
   DenoiseJobT t;
   int8_t *mv[3];
 };
 
-struct DenoiseParamsTM {
-  const DenoiseJobTM *jobs;
-  const uint16_t *table;
+// a job begins with the job of the form before it: the host fills the widest and uploads the part a form's kernels index
+static_assert(std::is_standard_layout<DenoiseJob>::value && std::is_standard_layout<DenoiseJobT>::value && std::is_standard_layout<DenoiseJobTM>::value,
+              "the jobs are copied as bytes");
+static_assert(offsetof(DenoiseJobT, f) == 0 && offsetof(DenoiseJobTM, t) == 0, "a job is a prefix of the next form's");
+
+// what a filter kernel does beyond one frame on its own (rules 1 - 4): the frames around it (rules 5 - 7), those where
+// their tiles' vectors point (rules 16 - 20).  The form picks the job: jobs[] is indexed with the form's own stride.
+enum class Form { kPlain, kTemporal, kMotion };
+template <Form F>
+using JobOf = std::conditional_t<F == Form::kPlain, DenoiseJob, std::conditional_t<F == Form::kTemporal, DenoiseJobT, DenoiseJobTM>>;
+
+__device__ inline const DenoiseJob &frame_of(const DenoiseJob &j) { return j; }
+__device__ inline const DenoiseJob &frame_of(const DenoiseJobT &j) { return j.f; }
+__device__ inline const DenoiseJob &frame_of(const DenoiseJobTM &j) { return j.t.f; }
+__device__ inline const DenoiseJobT &around_of(const DenoiseJobT &j) { return j; }
+__device__ inline const DenoiseJobT &around_of(const DenoiseJobTM &j) { return j.t; }
+
+// the planes of a class, one at a time (kd_nlm).  nnb and blocks are read by the forms that have them.
+template <class Job>
+struct PlaneParams {
+  const Job *jobs;
+  const uint16_t *table;  // the class's 1024 weights
   int q, A;
-  int W, H, tiles_x;
-  int plane0;
-  int nnb;
-  int blocks;  // tiles of the class's plane
+  int W, H, tiles_x;  // the class's plane size
+  int plane0;         // first plane of the class: 0 luma, 1 chroma
+  int nnb;            // 2 D
+  int blocks;         // tiles of the class's plane
 };
 
-struct DenoiseParamsJTM {
-  const DenoiseJobTM *jobs;
-  const uint16_t *table;
+// the two chroma planes with one weight (kd_nlm_j)
+template <class Job>
+struct JointParams {
+  const Job *jobs;
+  const uint16_t *table;  // rule 10's 1024 weights
   int q, A;
   JointShape s;
   int tiles_x;
@@ -127,189 +130,88 @@ __global__ __launch_bounds__(kThreads) void kd_motion(MotionParams p) {
   dn_motion_tile<BPS, NA>((int)threadIdx.x, motion_geom(p.M, NA), dn_lds, cur, ref, p.W, p.H, tx, ty, [] { __syncthreads(); }, mv);
 }
 
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_tm(DenoiseParamsTM p) {
+// a workgroup per (tile, plane of the class, frame)
+template <Form F, int S, int BPS>
+__global__ __launch_bounds__(kThreads) void kd_nlm(PlaneParams<JobOf<F>> p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobTM &job = p.jobs[blockIdx.z];
+  const JobOf<F> &job = p.jobs[blockIdx.z];
+  const DenoiseJob &f = frame_of(job);
   const int c = p.plane0 + (int)blockIdx.y;
   const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
   const TileGeom g = tile_geom(p.A, S);
-  dn_tile_tm<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, job.t.f.in[c], job.t.f.in_stride[c], job.t.nb[c], job.t.nb_stride[c], p.nnb,
-                     job.mv[c] + 2 * (int)blockIdx.x, 2 * p.blocks, job.t.f.out[c], job.t.f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH,
-                     [] { __syncthreads(); });
+  if constexpr (F == Form::kPlain) {
+    dn_tile<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, f.in[c], f.in_stride[c], f.out[c], f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH,
+                    [] { __syncthreads(); });
+  } else if constexpr (F == Form::kTemporal) {
+    dn_tile_t<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, f.in[c], f.in_stride[c], job.nb[c], job.nb_stride[c], p.nnb, f.out[c], f.out_stride[c], p.W,
+                      p.H, tx * kTW, ty * kTH, [] { __syncthreads(); });
+  } else {
+    dn_tile_tm<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, f.in[c], f.in_stride[c], job.t.nb[c], job.t.nb_stride[c], p.nnb,
+                       job.mv[c] + 2 * (int)blockIdx.x, 2 * p.blocks, f.out[c], f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH, [] { __syncthreads(); });
+  }
 }
 
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_t(DenoiseParamsT p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobT &job = p.jobs[blockIdx.z];
-  const int c = p.plane0 + (int)blockIdx.y;
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  dn_tile_t<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, job.f.in[c], job.f.in_stride[c], job.nb[c], job.nb_stride[c], p.nnb, job.f.out[c],
-                    job.f.out_stride[c], p.W, p.H, tx * kTW, ty * kTH, [] { __syncthreads(); });
-}
-
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm(DenoiseParams p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJob &job = p.jobs[blockIdx.z];
-  const int c = p.plane0 + (int)blockIdx.y;
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  dn_tile<S, BPS>((int)threadIdx.x, g, dn_lds, p.table, p.q, job.in[c], job.in_stride[c], job.out[c], job.out_stride[c], p.W, p.H, tx * kTW,
-                  ty * kTH, [] { __syncthreads(); });
-}
-
-// the joint chroma kernels (rules 8 - 11t): a workgroup per (chroma tile, frame) filters Cb and Cr with one weight
-struct DenoiseParamsJ {
-  const DenoiseJob *jobs;
-  const uint16_t *table;  // rule 10's 1024 weights
-  int q, A;
-  JointShape s;
-  int tiles_x;
-};
-
-struct DenoiseParamsJT {
-  const DenoiseJobT *jobs;
-  const uint16_t *table;
-  int q, A;
-  JointShape s;
-  int tiles_x;
-  int nnb;  // 2 D
-};
-
-__device__ inline JointPlanes joint_planes(const DenoiseJob &f) { return JointPlanes{f.in[1], f.in[2], f.in[0], f.in_stride[1], f.in_stride[2], f.in_stride[0]}; }
-
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_j(DenoiseParamsJ p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJob &job = p.jobs[blockIdx.z];
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  dn_tile_j<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job), p.s, job.out[1], job.out_stride[1], job.out[2],
-                    job.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); });
-}
-
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_jt(DenoiseParamsJT p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobT &job = p.jobs[blockIdx.z];
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
-  dn_tile_jt<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, p.s, job.f.out[1], job.f.out_stride[1],
-                     job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); });
-}
-
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_jtm(DenoiseParamsJTM p) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobTM &jm = p.jobs[blockIdx.z];
-  const DenoiseJobT &job = jm.t;
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
-  dn_tile_jtm<S, BPS>((int)threadIdx.x, g, joint_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, jm.mv[1] + 2 * (int)blockIdx.x,
-                      2 * p.blocks, p.s, job.f.out[1], job.f.out_stride[1], job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH,
-                      [] { __syncthreads(); });
-}
-
-// the joint chroma kernels under a chroma gain (rules 21 - 24): the same tiles, the weight of a pair scaled by the gain at the
-// guide under both of its ends.  Kernels of their own, so that the ones above stay what they are.
+// the joint chroma kernels (rules 8 - 11t): a workgroup per (chroma tile, frame) filters Cb and Cr with one weight.  Under a
+// chroma gain (rules 21 - 24) the kernel takes a second argument: the same tiles in the gain's layout, the weight of a pair
+// scaled by the gain at the guide under both of its ends.
 struct GainArg {
   const uint16_t *table;  // m[256]
   int shift;              // B - 8
 };
 
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_jg(DenoiseParamsJ p, GainArg ga) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJob &job = p.jobs[blockIdx.z];
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  dn_tile_j<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job), p.s, job.out[1], job.out_stride[1], job.out[2],
-                    job.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift});
+__device__ inline JointPlanes joint_planes(const DenoiseJob &f) { return JointPlanes{f.in[1], f.in[2], f.in[0], f.in_stride[1], f.in_stride[2], f.in_stride[0]}; }
+
+template <class... G>
+__device__ inline auto joint_layout(const TileGeom &g) {
+  if constexpr (sizeof...(G) != 0) return joint_gain_geom(g);
+  else return joint_geom(g);
 }
 
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_jtg(DenoiseParamsJT p, GainArg ga) {
+template <Form F, int S, int BPS, class... G>  // G: nothing, or GainArg
+__global__ __launch_bounds__(kThreads) void kd_nlm_j(JointParams<JobOf<F>> p, G... ga) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobT &job = p.jobs[blockIdx.z];
+  const JobOf<F> &job = p.jobs[blockIdx.z];
+  const DenoiseJob &f = frame_of(job);
   const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
   const TileGeom g = tile_geom(p.A, S);
-  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
-  dn_tile_jt<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, p.s, job.f.out[1], job.f.out_stride[1],
-                     job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift});
+  if constexpr (F == Form::kPlain) {
+    dn_tile_j<S, BPS>((int)threadIdx.x, g, joint_layout<G...>(g), dn_lds, p.table, p.q, joint_planes(f), p.s, f.out[1], f.out_stride[1], f.out[2],
+                      f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift}...);
+  } else {
+    const DenoiseJobT &t = around_of(job);
+    auto nb = [&t](int k) { return JointPlanes{t.nb[1][k], t.nb[2][k], t.nb[0][k], t.nb_stride[1][k], t.nb_stride[2][k], t.nb_stride[0][k]}; };
+    if constexpr (F == Form::kTemporal) {
+      dn_tile_jt<S, BPS>((int)threadIdx.x, g, joint_layout<G...>(g), dn_lds, p.table, p.q, joint_planes(f), nb, p.nnb, p.s, f.out[1], f.out_stride[1],
+                         f.out[2], f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); }, Gain{ga.table, ga.shift}...);
+    } else {
+      dn_tile_jtm<S, BPS>((int)threadIdx.x, g, joint_layout<G...>(g), dn_lds, p.table, p.q, joint_planes(f), nb, p.nnb, job.mv[1] + 2 * (int)blockIdx.x,
+                          2 * p.blocks, p.s, f.out[1], f.out_stride[1], f.out[2], f.out_stride[2], tx * kTW, ty * kTH, [] { __syncthreads(); },
+                          Gain{ga.table, ga.shift}...);
+    }
+  }
 }
 
-template <int S, int BPS>
-__global__ __launch_bounds__(kThreads) void kd_nlm_jtmg(DenoiseParamsJTM p, GainArg ga) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t dn_lds[];
-  const DenoiseJobTM &jm = p.jobs[blockIdx.z];
-  const DenoiseJobT &job = jm.t;
-  const int ty = (int)blockIdx.x / p.tiles_x, tx = (int)blockIdx.x - ty * p.tiles_x;
-  const TileGeom g = tile_geom(p.A, S);
-  auto nb = [&job](int k) { return JointPlanes{job.nb[1][k], job.nb[2][k], job.nb[0][k], job.nb_stride[1][k], job.nb_stride[2][k], job.nb_stride[0][k]}; };
-  dn_tile_jtm<S, BPS>((int)threadIdx.x, g, joint_gain_geom(g), dn_lds, p.table, p.q, joint_planes(job.f), nb, p.nnb, jm.mv[1] + 2 * (int)blockIdx.x,
-                      2 * p.blocks, p.s, job.f.out[1], job.f.out_stride[1], job.f.out[2], job.f.out_stride[2], tx * kTW, ty * kTH,
-                      [] { __syncthreads(); }, Gain{ga.table, ga.shift});
-}
-
-// the kernel families as the host launches them: the parameters each takes and its instantiation for (S, BPS)
-struct Plain {
-  using Params = DenoiseParams;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
+// the kernel families as the host launches them: the arguments each takes and its instantiation for (S, BPS)
+template <Form F>
+struct Planes {
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const PlaneParams<JobOf<F>> &p) {
+    hipLaunchKernelGGL((kd_nlm<F, S, BPS>), grid, dim3(kThreads), lds, st, p);
+  }
 };
-struct Temporal {
-  using Params = DenoiseParamsT;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_t<S, BPS>), grid, dim3(kThreads), lds, st, p); }
-};
-
+template <Form F, class... G>
 struct Joint {
-  using Params = DenoiseParamsJ;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_j<S, BPS>), grid, dim3(kThreads), lds, st, p); }
-};
-struct JointTemporal {
-  using Params = DenoiseParamsJT;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jt<S, BPS>), grid, dim3(kThreads), lds, st, p); }
-};
-
-struct TemporalMotion {
-  using Params = DenoiseParamsTM;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_tm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
-};
-struct JointTemporalMotion {
-  using Params = DenoiseParamsJTM;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtm<S, BPS>), grid, dim3(kThreads), lds, st, p); }
-};
-
-// the same three under a chroma gain: the joint family's parameters and the gain beside them
-template <class P>
-struct WithGain {
-  P p;
-  GainArg ga;
-};
-struct JointGain {
-  using Params = WithGain<DenoiseParamsJ>;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
-};
-struct JointTemporalGain {
-  using Params = WithGain<DenoiseParamsJT>;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
-};
-struct JointTemporalMotionGain {
-  using Params = WithGain<DenoiseParamsJTM>;
-  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const Params &p) { hipLaunchKernelGGL((kd_nlm_jtmg<S, BPS>), grid, dim3(kThreads), lds, st, p.p, p.ga); }
+  template <int S, int BPS> static void launch(dim3 grid, size_t lds, hipStream_t st, const JointParams<JobOf<F>> &p, const G &...ga) {
+    hipLaunchKernelGGL((kd_nlm_j<F, S, BPS, G...>), grid, dim3(kThreads), lds, st, p, ga...);
+  }
 };
 
 // the family's kernel for patch radius S and `bps` bytes a sample; false: there is none
-template <class Family>
-bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t st, const typename Family::Params &p) {
+template <class Family, class... Args>
+bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t st, const Args &...args) {
   switch (S * 2 + (bps - 1)) {
-#define DN_CASE(s)                                                             \
-  case (s) * 2: Family::template launch<s, 1>(grid, lds, st, p); return true; \
-  case (s) * 2 + 1: Family::template launch<s, 2>(grid, lds, st, p); return true;
+#define DN_CASE(s)                                                                   \
+  case (s) * 2: Family::template launch<s, 1>(grid, lds, st, args...); return true; \
+  case (s) * 2 + 1: Family::template launch<s, 2>(grid, lds, st, args...); return true;
     DN_CASE(1)
     DN_CASE(2)
     DN_CASE(3)
@@ -350,8 +252,8 @@ using namespace g1s_op;
 struct g1s_denoise : BatchedOp {
   uint32_t A = 3, S = 2, D = 0;
   uint32_t M = 0;  // the motion range on the search plane (rules 16 - 20); 0: no motion, the launches of rules 1 - 15
-  bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j / kd_nlm_jt for their chroma
-  bool gain = false;          // a chroma gain (rules 21 - 24): the joint launch is kd_nlm_jg / kd_nlm_jtg / kd_nlm_jtmg
+  bool joint = false;         // G1S_DENOISE_JOINT_CHROMA: frames of three planes get kd_nlm_j for their chroma
+  bool gain = false;          // a chroma gain (rules 21 - 24): the joint launch is kd_nlm_j<.., GainArg>
   DevBuf<uint16_t> d_gain;    // m[256]
   uint32_t q[4] = {0, 0, 0, 0};  // luma, chroma, joint chroma, luma in the stabilised domain
   Event ev[3];
@@ -367,7 +269,7 @@ struct g1s_denoise : BatchedOp {
   // frames [first_queued, frames_in): what is not launched yet and, in front of it, up to D launched frames of the same clip
   std::deque<Queued> queue;
   uint64_t frames_in = 0, first_queued = 0, next_launch = 0, clip_first = 0, frames_complete = 0;
-  ParamSets<uint8_t> p_jobs;  // DenoiseJob or, with a temporal radius, DenoiseJobT
+  ParamSets<uint8_t> p_jobs;  // the form's jobs: JobOf<Form>
   DevBuf<uint16_t> d_tables;  // [4][1024]
   // a grain prior's curve (rules 12 - 15): luma goes forward into a ring of 12-bit u16 planes, one slot a frame of the
   // input ring, is filtered there into `batch` planes and comes back through the inverse
@@ -397,7 +299,14 @@ struct g1s_denoise : BatchedOp {
   int need_mv();
   int launch_motion(const DenoiseJobTM *jobs, const PlaneGeom &pg, uint32_t nframes, uint32_t nnb, int plane0, uint32_t bps_, hipStream_t st);
 
-  size_t job_bytes() const { return D ? (M ? sizeof(DenoiseJobTM) : sizeof(DenoiseJobT)) : sizeof(DenoiseJob); }
+  // the form of this denoiser's filter kernels, as a tag: the one place the choice among them is made
+  template <class Fn>
+  auto with_form(Fn &&fn) const {
+    if (D && M) return fn(std::integral_constant<Form, Form::kMotion>());
+    if (D) return fn(std::integral_constant<Form, Form::kTemporal>());
+    return fn(std::integral_constant<Form, Form::kPlain>());
+  }
+  size_t job_bytes() const { return with_form([](auto form) { return sizeof(JobOf<decltype(form)::value>); }); }
   // a parameter set: the batch's jobs and, with a curve, the luma launch's jobs in the stabilised planes, the forward
   // launch's (a first batch brings its D later neighbours along) and the inverse launch's
   size_t off_luma() const { return align_up(job_bytes() * batch, 16); }
@@ -417,32 +326,21 @@ struct g1s_denoise : BatchedOp {
   int end_clip();
 };
 
-// the planes of a class through kd_nlm / kd_nlm_t; `stabilised`: luma as the forward curve left it -- 12-bit u16 planes,
+// the planes of a class through kd_nlm; `stabilised`: luma as the forward curve left it -- 12-bit u16 planes,
 // the jobs that point into them and rule 14's table
 int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_class, bool stabilised) {
   const int W = (int)geom.pw(plane0), H = (int)geom.ph(plane0), tiles_x = (W + kTW - 1) / kTW;
   const int ti = stabilised ? 3 : plane0 ? 1 : 0;
   const uint32_t bps = stabilised ? 2u : this->bps;
-  auto fill = [&](auto &p) {
-    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p + (stabilised ? off_luma() : 0)), p.table = d_tables + ti * kTable, p.q = (int)q[ti], p.A = (int)A;
-    p.W = W, p.H = H, p.tiles_x = tiles_x, p.plane0 = plane0;
-  };
   const dim3 grid((unsigned)(tiles_x * ((H + kTH - 1) / kTH)), (unsigned)nplanes_in_class, nframes);
   const TileGeom tg = tile_geom((int)A, (int)S);
-  bool found;
-  if (D && M) {
-    DenoiseParamsTM t{};
-    fill(t), t.nnb = (int)(2 * D), t.blocks = (int)grid.x;
-    found = launch_family<TemporalMotion>(S, bps, grid, (size_t)tg.bytes_t, stream, t);
-  } else if (D) {
-    DenoiseParamsT t{};
-    fill(t), t.nnb = (int)(2 * D);
-    found = launch_family<Temporal>(S, bps, grid, (size_t)tg.bytes_t, stream, t);
-  } else {
-    DenoiseParams p{};
-    fill(p);
-    found = launch_family<Plain>(S, bps, grid, (size_t)tg.bytes, stream, p);
-  }
+  const bool found = with_form([&](auto form) {
+    constexpr Form F = decltype(form)::value;
+    PlaneParams<JobOf<F>> p{};
+    p.jobs = reinterpret_cast<const JobOf<F> *>(p_jobs.d[set].p + (stabilised ? off_luma() : 0)), p.table = d_tables + ti * kTable, p.q = (int)q[ti], p.A = (int)A;
+    p.W = W, p.H = H, p.tiles_x = tiles_x, p.plane0 = plane0, p.nnb = (int)(2 * D), p.blocks = (int)grid.x;
+    return launch_family<Planes<F>>(S, bps, grid, (size_t)(F == Form::kPlain ? tg.bytes : tg.bytes_t), stream, p);
+  });
   if (!found) return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
   G1S_OP_TRY(hipGetLastError());
   return G1S_OK;
@@ -451,40 +349,18 @@ int g1s_denoise::launch(int set, uint32_t nframes, int plane0, int nplanes_in_cl
 // both chroma planes of the batch's frames through the joint kernel: grid (tiles, 1, frames)
 int g1s_denoise::launch_joint(int set, uint32_t nframes) {
   const int cw = (int)geom.pw(1), ch = (int)geom.ph(1), tiles_x = (cw + kTW - 1) / kTW;
-  auto fill = [&](auto &p) {
-    p.jobs = reinterpret_cast<decltype(p.jobs)>(p_jobs.d[set].p), p.table = d_tables + 2 * kTable, p.q = (int)q[2], p.A = (int)A;
-    p.s = JointShape{geom.W, geom.H, geom.subx, geom.suby, cw, ch}, p.tiles_x = tiles_x;
-  };
   const dim3 grid((unsigned)(tiles_x * ((ch + kTH - 1) / kTH)), 1u, nframes);
   const TileGeom tg = tile_geom((int)A, (int)S);
   const JointGeom jg = gain ? joint_gain_geom(tg) : joint_geom(tg);  // (the gain's layout: the same fields, Mt between T and N)
   const GainArg ga{d_gain, (int)bit_depth - 8};
-  bool found;
-  if (gain && D && M) {
-    WithGain<DenoiseParamsJTM> t{{}, ga};
-    fill(t.p), t.p.nnb = (int)(2 * D), t.p.blocks = (int)grid.x;
-    found = launch_family<JointTemporalMotionGain>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
-  } else if (gain && D) {
-    WithGain<DenoiseParamsJT> t{{}, ga};
-    fill(t.p), t.p.nnb = (int)(2 * D);
-    found = launch_family<JointTemporalGain>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
-  } else if (gain) {
-    WithGain<DenoiseParamsJ> p{{}, ga};
-    fill(p.p);
-    found = launch_family<JointGain>(S, bps, grid, (size_t)jg.bytes, stream, p);
-  } else if (D && M) {
-    DenoiseParamsJTM t{};
-    fill(t), t.nnb = (int)(2 * D), t.blocks = (int)grid.x;
-    found = launch_family<JointTemporalMotion>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
-  } else if (D) {
-    DenoiseParamsJT t{};
-    fill(t), t.nnb = (int)(2 * D);
-    found = launch_family<JointTemporal>(S, bps, grid, (size_t)jg.bytes_t, stream, t);
-  } else {
-    DenoiseParamsJ p{};
-    fill(p);
-    found = launch_family<Joint>(S, bps, grid, (size_t)jg.bytes, stream, p);
-  }
+  const bool found = with_form([&](auto form) {
+    constexpr Form F = decltype(form)::value;
+    JointParams<JobOf<F>> p{};
+    p.jobs = reinterpret_cast<const JobOf<F> *>(p_jobs.d[set].p), p.table = d_tables + 2 * kTable, p.q = (int)q[2], p.A = (int)A;
+    p.s = JointShape{geom.W, geom.H, geom.subx, geom.suby, cw, ch}, p.tiles_x = tiles_x, p.nnb = (int)(2 * D), p.blocks = (int)grid.x;
+    const size_t lds = (size_t)(F == Form::kPlain ? jg.bytes : jg.bytes_t);
+    return gain ? launch_family<Joint<F, GainArg>>(S, bps, grid, lds, stream, p, ga) : launch_family<Joint<F>>(S, bps, grid, lds, stream, p);
+  });
   if (!found) return fail(G1S_ERR_INVALID, "no kernel for this patch radius");
   G1S_OP_TRY(hipGetLastError());
   return G1S_OK;
@@ -545,7 +421,9 @@ int g1s_denoise::flush(uint32_t nframes) {
   for (uint32_t i = 0; i < nframes; ++i) {
     const uint64_t n = next_launch + i;
     const Queued &f = frame(n);
-    DenoiseJob job{};
+    // the widest job, and one more for the luma launch under a curve; slot i of the set takes the part this form's kernels index
+    DenoiseJobTM tm{}, ltm{};
+    DenoiseJob &job = tm.t.f, &lj = ltm.t.f;
     for (int c = 0; c < geom.nplanes; ++c) {
       job.in[c] = f.in[c], job.in_stride[c] = f.in_stride[c];
       job.out[c] = f.host_out ? stage_out(i, c) : f.out[c];
@@ -554,39 +432,24 @@ int g1s_denoise::flush(uint32_t nframes) {
     host_outs = host_outs || f.host_out;
     // (rule 14) the luma launch's job: from the frame's slot into plane i of the filtered ones, which the inverse takes
     // to where the frame's luma goes
-    DenoiseJob lj{};
     if (curve) {
       lj.in[0] = stab_slot(n), lj.out[0] = d_filt + stab_plane * i, lj.in_stride[0] = lj.out_stride[0] = (uint32_t)stab_row;
       reinterpret_cast<g1s_cv::CurveJob *>(p_jobs.h[set].p + off_inv())[i] = g1s_cv::CurveJob{lj.out[0], job.out[0], (uint32_t)stab_row, job.out_stride[0]};
     }
-    if (!D) {
-      reinterpret_cast<DenoiseJob *>(p_jobs.h[set].p)[i] = job;
-      if (curve) reinterpret_cast<DenoiseJob *>(p_jobs.h[set].p + off_luma())[i] = lj;
-      continue;
-    }
-    DenoiseJobT t{}, lt{};
-    t.f = job, lt.f = lj;
     int k = 0;
     for (int64_t m = (int64_t)n - (int64_t)D; m <= (int64_t)(n + D); ++m) {
       if (m == (int64_t)n) continue;
       if (m >= (int64_t)clip_first && m < (int64_t)frames_in) {  // rule 5: the frames the clip has
-        for (int c = 0; c < geom.nplanes; ++c) t.nb[c][k] = frame((uint64_t)m).in[c], t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
-        if (curve) lt.nb[0][k] = stab_slot((uint64_t)m), lt.nb_stride[0][k] = (uint32_t)stab_row;
+        for (int c = 0; c < geom.nplanes; ++c) tm.t.nb[c][k] = frame((uint64_t)m).in[c], tm.t.nb_stride[c][k] = frame((uint64_t)m).in_stride[c];
+        if (curve) ltm.t.nb[0][k] = stab_slot((uint64_t)m), ltm.t.nb_stride[0][k] = (uint32_t)stab_row;
       }
       ++k;
     }
-    if (M) {
-      // (the stabilised luma's vectors are the luma's: one search, on the planes the filter filters -- rule 20)
-      DenoiseJobTM tm{}, ltm{};
-      tm.t = t, ltm.t = lt;
-      for (int c = 0; c < geom.nplanes; ++c) tm.mv[c] = d_mv[set] + mv_frame * i + mv_off[c];
-      ltm.mv[0] = tm.mv[0];
-      reinterpret_cast<DenoiseJobTM *>(p_jobs.h[set].p)[i] = tm;
-      if (curve) reinterpret_cast<DenoiseJobTM *>(p_jobs.h[set].p + off_luma())[i] = ltm;
-      continue;
-    }
-    reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p)[i] = t;
-    if (curve) reinterpret_cast<DenoiseJobT *>(p_jobs.h[set].p + off_luma())[i] = lt;
+    // (the stabilised luma's vectors are the luma's: one search, on the planes the filter filters -- rule 20)
+    for (int c = 0; M && c < geom.nplanes; ++c) tm.mv[c] = d_mv[set] + mv_frame * i + mv_off[c];
+    ltm.mv[0] = tm.mv[0];
+    std::memcpy(p_jobs.h[set].p + job_bytes() * i, &tm, job_bytes());
+    if (curve) std::memcpy(p_jobs.h[set].p + off_luma() + job_bytes() * i, &ltm, job_bytes());
   }
   G1S_OP_TRY(p_jobs.upload(set, curve ? set_bytes() : job_bytes() * nframes, stream));
   if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
@@ -648,77 +511,18 @@ int g1s_denoise::end_clip() {
   return G1S_OK;
 }
 
-// A grain prior as the file commands take it: the table at `path`, its segment `segment` alone or (negative) the mean of
-// all of them, range R (0 = the default).  load() reads and parses; make() is g1s_denoise_curve for the clip's depth.
-// measure() is the other way to one: the noise levels of the clip itself (rules N5 - N6) through g1s_denoise_curve_sigma.
-struct Prior {
-  std::vector<g1s_segment_t> segs;
-  uint32_t range = 0;
-  std::vector<uint16_t> pair_fwd, pair_inv;  // a curve that is there already (a measured prior): make() hands it on
-  bool chroma = false;         // the prior extends to chroma (rules 21 - 24): load() and measure() also make the gain
-  std::vector<uint16_t> gain;  // m[256] then; else empty
-  std::string load(const char *path, uint32_t range_, int32_t segment) {
-    range = range_;
-    std::string text;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return std::string("grain prior: cannot open ") + path;
-    char buf[65536];
-    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
-    std::fclose(f);
-    size_t nseg = 0;
-    char perr[256] = "";
-    segs.resize(64);
-    int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-    if (rc == G1S_ERR_CAPACITY) {
-      segs.resize(nseg);
-      rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-    }
-    if (rc) return std::string("grain prior: ") + perr;
-    segs.resize(nseg);
-    if (segment >= 0 && (size_t)segment >= nseg)
-      return "grain prior: segment " + std::to_string(segment) + " is not in the table (" + std::to_string(nseg) + " segments)";
-    if (segment >= 0) segs = {segs[(size_t)segment]};
-    if (chroma) {  // rule 22 on the segments in hand, rule 21
-      gain.assign(g1s_cv::kGainEntries, 0);
-      return g1s_cv::build_gain(segs.data(), segs.size(), range, gain.data());
-    }
-    return "";
-  }
-  std::string make(uint32_t bit_depth, std::vector<uint16_t> &fwd, std::vector<uint16_t> &inv) const {
-    if (!pair_fwd.empty()) {
-      fwd = pair_fwd, inv = pair_inv;
-      return "";
-    }
-    fwd.assign((size_t)1 << (bit_depth <= 12 ? bit_depth : 12), 0), inv.assign(g1s_cv::kInvEntries, 0);
-    return g1s_cv::build(segs.data(), segs.size(), bit_depth, range, fwd.data(), inv.data());
-  }
-  std::string measure(const g1s_nlf_record_t &total, uint32_t bit_depth, uint32_t range_, uint64_t min_count) {
-    std::string why = g1s_cv::check_depth_range(bit_depth, range_);
-    if (!why.empty()) return why;
-    std::vector<uint8_t> sg((size_t)1 << bit_depth);
-    if (!(why = g1s_nl::sigma(total, bit_depth, min_count, sg.data())).empty()) return why;
-    pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
-    if (!(why = g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data())).empty() || !chroma) return why;
-    uint8_t sc[g1s_cv::kGainEntries];  // rule 23 on the same record, rule 21
-    if (!(why = g1s_nl::chroma_sigma(total, min_count, sc)).empty()) return why;
-    gain.assign(g1s_cv::kGainEntries, 0);
-    return g1s_cv::gain_from_s(sc, range_, gain.data());
-  }
-  // the denoiser for a clip of this depth; NULL with the global error text set
-  g1s_denoise_t *open(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t D, uint32_t flags, uint32_t motion_range = 0) const {
-    std::vector<uint16_t> fwd, inv;
-    const std::string why = make(bit_depth, fwd, inv);
-    if (!why.empty()) {
-      g1s_set_global_error_(why.c_str());
-      return nullptr;
-    }
-    return g1s_denoise_new_gain(bit_depth, opts, D, flags, fwd.data(), inv.data(), motion_range, gain.empty() ? nullptr : gain.data());
-  }
+// what makes a denoiser beyond the opts; `curve`: with the pair (fwd, inv) of rules 12 - 15
+struct DenoiserSpec {
+  uint32_t temporal_radius = 0, flags = 0;
+  bool curve = false;
+  const uint16_t *fwd = nullptr, *inv = nullptr;
+  uint32_t motion_range = 0;
+  const uint16_t *chroma_gain = nullptr;
 };
 
-// what every g1s_denoise_new* call makes; `curve`: with the pair (fwd, inv) of rules 12 - 15
-static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, bool curve,
-                                 const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range = 0, const uint16_t *chroma_gain = nullptr) {
+// what every g1s_denoise_new* call makes
+static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, const DenoiserSpec &spec) {
+  const auto [temporal_radius, flags, curve, fwd, inv, motion_range, chroma_gain] = spec;
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -831,30 +635,34 @@ int g1s_denoise_weights_ex(uint32_t bit_depth, uint32_t patch_radius, double str
   return G1S_OK;
 }
 
-g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return g1s_denoise_new_temporal(bit_depth, opts, 0); }
+g1s_denoise_t *g1s_denoise_new(uint32_t bit_depth, const g1s_denoise_opts_t *opts) { return new_denoiser(bit_depth, opts, {}); }
 
 g1s_denoise_t *g1s_denoise_new_temporal(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius) {
-  return g1s_denoise_new_ex(bit_depth, opts, temporal_radius, 0);
+  return new_denoiser(bit_depth, opts, {temporal_radius});
 }
 
 g1s_denoise_t *g1s_denoise_new_ex(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags) {
-  return new_denoiser(bit_depth, opts, temporal_radius, flags, false, nullptr, nullptr);
+  return new_denoiser(bit_depth, opts, {temporal_radius, flags});
 }
 
 g1s_denoise_t *g1s_denoise_new_curve(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
                                      const uint16_t *inv) {
-  return new_denoiser(bit_depth, opts, temporal_radius, flags, true, fwd, inv);
+  return new_denoiser(bit_depth, opts, {temporal_radius, flags, true, fwd, inv});
 }
 
 g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
                                       const uint16_t *inv, uint32_t motion_range) {
-  return new_denoiser(bit_depth, opts, temporal_radius, flags, fwd || inv, fwd, inv, motion_range);
+  return new_denoiser(bit_depth, opts, {temporal_radius, flags, fwd || inv, fwd, inv, motion_range});
 }
 
 g1s_denoise_t *g1s_denoise_new_gain(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
                                     const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain) {
-  return new_denoiser(bit_depth, opts, temporal_radius, flags, fwd || inv, fwd, inv, motion_range, chroma_gain);
+  return new_denoiser(bit_depth, opts, {temporal_radius, flags, fwd || inv, fwd, inv, motion_range, chroma_gain});
 }
+
+// (denoise_file.cpp) what the file commands size their rings by
+uint32_t g1s_denoise_batch_(const g1s_denoise_t *g) { return g->batch; }
+uint32_t g1s_denoise_temporal_radius_(const g1s_denoise_t *g) { return g->D; }
 
 // stage 1 alone: both frames on the device (a host frame in an allocation of this call), luma through the forward curve
 // where there is one, one job with `ref` as its only neighbour, kd_motion, the vectors back
@@ -1017,432 +825,5 @@ int g1s_denoise_set_timing(g1s_denoise_t *g, int enable, double *ms_kernel, uint
 const char *g1s_denoise_last_error(const g1s_denoise_t *g) { return g ? g->err.c_str() : ""; }
 
 void g1s_denoise_free(g1s_denoise_t *g) { free_op(g); }
-
-int64_t g1s_denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, char *err, size_t cap) {
-  return g1s_denoise_y4m_file_temporal(in, out, opts, 0, err, cap);
-}
-
-int64_t g1s_denoise_y4m_file_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, char *err,
-                                      size_t cap) {
-  return g1s_denoise_y4m_file_ex(in, out, opts, temporal_radius, 0, err, cap);
-}
-
-int64_t g1s_denoise_y4m_file_ex(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, char *err,
-                                size_t cap) {
-  return g1s_denoise_y4m_file_curve(in, out, opts, temporal_radius, flags, nullptr, 0, -1, err, cap);
-}
-
-int64_t g1s_denoise_y4m_file_curve(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                   const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, char *err, size_t cap) {
-  return g1s_denoise_y4m_file_motion(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, 0, err, cap);
-}
-
-// what g1s_denoise_y4m_file_motion and g1s_denoise_y4m_file_auto do once they have their prior (or none)
-static int64_t denoise_y4m_file(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                const Prior *prior, uint32_t motion_range, char *err, size_t cap) {
-  // a ring of output frames in pinned memory: denoised, waited for, written.  The file is one clip: between two drains a
-  // batch is handed over, and the denoiser holds the last D frames back, so batch + D frames can be unwritten
-  struct Driver {
-    const g1s_denoise_opts_t *opts;
-    uint32_t D, flags;
-    const Prior *prior;
-    uint32_t Mr;
-    g1s_denoise_t *g = nullptr;
-    const int new_failed = G1S_ERR_INVALID;
-    bool open(const g1s_y4m_info_t &i) {
-      return (g = prior ? prior->open(i.bit_depth, opts, D, flags, Mr) : g1s_denoise_new_motion(i.bit_depth, opts, D, flags, nullptr, nullptr, Mr)) != nullptr;
-    }
-    uint32_t batch() const { return g->batch; }
-    uint32_t ring() const { return g->batch + g->D; }
-    int frame(int64_t, const g1s_frame_t *fin, g1s_frame_t *fout) { return g1s_denoise_frame(g, fin, fout); }
-    int drain(bool end, uint64_t *complete) { return end ? g1s_denoise_sync(g) : g1s_denoise_drain(g, complete); }
-    const char *last_error() const { return g1s_denoise_last_error(g); }
-    void close() { g1s_denoise_free(g); }
-  };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, temporal_radius, flags, prior, motion_range});
-}
-
-int64_t g1s_denoise_y4m_file_motion(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, char *err, size_t cap) {
-  Prior prior;
-  if (prior_tbl) {
-    const std::string why = prior.load(prior_tbl, prior_range, prior_segment);
-    if (!why.empty()) {
-      if (err && cap) snprintf(err, cap, "%s", why.c_str());
-      return G1S_ERR_INVALID;
-    }
-  }
-  return denoise_y4m_file(in, out, opts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range, err, cap);
-}
-
-// The pre-pass of the *_auto file commands: the refusals of the flags, the noise levels of the first profile_frames frames of
-// `source` on `device`, then the prior's curve into *prior (G1S_AUTO_PRIOR) and the two strengths into *d (G1S_AUTO_STRENGTH).
-// "" when fine.
-static std::string auto_prepass(const char *source, int32_t device, uint32_t auto_flags, uint64_t profile_frames, uint64_t min_count, const char *prior_tbl,
-                                uint32_t prior_range, Prior *prior, g1s_denoise_opts_t *d) {
-  if (auto_flags & ~(G1S_AUTO_PRIOR | G1S_AUTO_STRENGTH)) return "unknown auto flags";
-  if ((auto_flags & G1S_AUTO_PRIOR) && prior_tbl) return "an auto prior does not combine with a grain prior table";
-  if ((auto_flags & G1S_AUTO_STRENGTH) && (d->strength != 0.0 || d->chroma_strength != 0.0)) return "an auto strength does not combine with a given strength";
-  if (!source) return "null path";
-  struct stat st;
-  if (stat(source, &st) == 0 && !S_ISREG(st.st_mode)) return std::string(source) + " cannot be read twice (not a regular file): the auto flags need a pre-pass";
-  g1s_nlf_opts_t no{};
-  no.struct_size = sizeof no, no.device = device;
-  g1s_nlf_record_t total;
-  char err[512] = "";
-  const int64_t n = g1s_nlf_y4m_file(source, nullptr, &no, profile_frames, &total, err, sizeof err);
-  if (n < 0) return err;
-  g1s_y4m_t *y = g1s_y4m_open(source, err, sizeof err);
-  if (!y) return err;
-  g1s_y4m_info_t info;
-  g1s_y4m_get_info(y, &info);
-  g1s_y4m_close(y);
-  if (auto_flags & G1S_AUTO_PRIOR) {
-    const std::string why = prior->measure(total, info.bit_depth, prior_range, min_count);
-    if (!why.empty()) return why;
-  }
-  if (auto_flags & G1S_AUTO_STRENGTH) {
-    const std::string why = g1s_nl::strength(total, info.bit_depth, min_count, 0, &d->strength);
-    if (!why.empty()) return why;
-    double hc = 0;
-    if (g1s_nl::strength(total, info.bit_depth, min_count, 1, &hc).empty()) d->chroma_strength = hc;  // (else: the luma strength)
-  }
-  return "";
-}
-
-int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                  const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
-                                  uint64_t profile_frames, uint64_t min_count, char *err, size_t cap) {
-  if (!auto_flags) return g1s_denoise_y4m_file_motion(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, err, cap);
-  if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
-    if (err && cap) snprintf(err, cap, "%s", "g1s_denoise_opts_t.struct_size mismatch");
-    return G1S_ERR_INVALID;
-  }
-  Prior prior;
-  g1s_denoise_opts_t d{};
-  if (opts) d = *opts;
-  d.struct_size = sizeof d;
-  if (!opts) d.device = -1;
-  std::string why = auto_prepass(in, d.device, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
-  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
-  if (!why.empty()) {
-    if (err && cap) snprintf(err, cap, "%s", why.c_str());
-    return G1S_ERR_INVALID;
-  }
-  return denoise_y4m_file(in, out, &d, temporal_radius, flags, prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, err, cap);
-}
-
-// the refusals of a chroma prior that need neither the table nor the clip.  "" when fine.
-static std::string chroma_prior_refusal(uint32_t chroma_prior, uint32_t flags, const char *prior_tbl, uint32_t auto_flags) {
-  if (chroma_prior > 1) return "chroma_prior is 0 or 1";
-  if (!prior_tbl && !(auto_flags & G1S_AUTO_PRIOR)) return "a chroma prior needs a grain prior (a table or the clip's own levels)";
-  if (!(flags & G1S_DENOISE_JOINT_CHROMA)) return "a chroma gain needs joint chroma";
-  return "";
-}
-
-int64_t g1s_denoise_y4m_file_chroma(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
-                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
-                                    uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, char *err, size_t cap) {
-  if (!chroma_prior)
-    return g1s_denoise_y4m_file_auto(in, out, opts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames,
-                                     min_count, err, cap);
-  std::string why = chroma_prior_refusal(chroma_prior, flags, prior_tbl, auto_flags);
-  if (why.empty() && opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) why = "g1s_denoise_opts_t.struct_size mismatch";
-  Prior prior;
-  prior.chroma = true;
-  g1s_denoise_opts_t d{};
-  if (opts) d = *opts;
-  d.struct_size = sizeof d;
-  if (!opts) d.device = -1;
-  if (why.empty() && auto_flags) why = auto_prepass(in, d.device, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
-  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
-  if (!why.empty()) {
-    if (err && cap) snprintf(err, cap, "%s", why.c_str());
-    return G1S_ERR_INVALID;
-  }
-  return denoise_y4m_file(in, out, &d, temporal_radius, flags, &prior, motion_range, err, cap);
-}
-
-// `diff SOURCE --denoise -o TABLE`: the source is read once and copied to the device once; the denoiser writes its
-// output beside it and the generator takes the pair as device frames.  A pair's two buffers belong to the generator
-// until g1s_diff_frames_released() covers the frame, and its source buffer is a neighbour of the D frames after it until the
-// denoiser is past those; then they are used again.  The file is one clip: the denoiser is drained once a group, not
-// synchronised, and only the frames it has completed go on to the generator.
-int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                               const g1s_denoise_opts_t *dopts, uint64_t *frames_out, char *err, size_t cap) {
-  return g1s_diff_y4m_file_denoised_temporal(source, out_tbl, keep_denoised, opts, dopts, 0, frames_out, err, cap);
-}
-
-int g1s_diff_y4m_file_denoised_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                        const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint64_t *frames_out, char *err, size_t cap) {
-  return g1s_diff_y4m_file_denoised_ex(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, 0, frames_out, err, cap);
-}
-
-int g1s_diff_y4m_file_denoised_ex(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, uint64_t *frames_out, char *err,
-                                  size_t cap) {
-  return g1s_diff_y4m_file_denoised_curve(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, nullptr, 0, -1, frames_out, err, cap);
-}
-
-int g1s_diff_y4m_file_denoised_curve(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                     const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
-                                     uint32_t prior_range, int32_t prior_segment, uint64_t *frames_out, char *err, size_t cap) {
-  return g1s_diff_y4m_file_denoised_motion(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment, 0,
-                                           frames_out, err, cap);
-}
-
-static int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const Prior *prior_or_null,
-                                  uint32_t motion_range, uint64_t *frames_out, char *err, size_t cap);
-
-int g1s_diff_y4m_file_denoised_motion(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
-                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint64_t *frames_out, char *err,
-                                      size_t cap) {
-  auto refuse = [&](int code, const std::string &m) {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (frames_out) *frames_out = 0;
-  if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
-  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
-  Prior prior;
-  if (prior_tbl) {
-    const std::string no = prior.load(prior_tbl, prior_range, prior_segment);
-    if (!no.empty()) return refuse(G1S_ERR_INVALID, no);
-  }
-  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl ? &prior : nullptr, motion_range, frames_out,
-                                err, cap);
-}
-
-int g1s_diff_y4m_file_denoised_auto(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                    const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
-                                    uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
-                                    uint64_t min_count, uint64_t *frames_out, char *err, size_t cap) {
-  if (!auto_flags)
-    return g1s_diff_y4m_file_denoised_motion(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment,
-                                             motion_range, frames_out, err, cap);
-  auto refuse = [&](int code, const std::string &m) {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (frames_out) *frames_out = 0;
-  if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
-  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
-  if (dopts && dopts->struct_size != sizeof(g1s_denoise_opts_t)) return refuse(G1S_ERR_INVALID, "g1s_denoise_opts_t.struct_size mismatch");
-  Prior prior;
-  g1s_denoise_opts_t d{};
-  if (dopts) d = *dopts;
-  d.struct_size = sizeof d;
-  std::string why = auto_prepass(source, opts ? opts->device : -1, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
-  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
-  if (!why.empty()) return refuse(G1S_ERR_INVALID, why);
-  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, &d, temporal_radius, flags,
-                                prior_tbl || (auto_flags & G1S_AUTO_PRIOR) ? &prior : nullptr, motion_range, frames_out, err, cap);
-}
-
-int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
-                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
-                                      uint64_t min_count, uint32_t chroma_prior, uint64_t *frames_out, char *err, size_t cap) {
-  if (!chroma_prior)
-    return g1s_diff_y4m_file_denoised_auto(source, out_tbl, keep_denoised, opts, dopts, temporal_radius, flags, prior_tbl, prior_range, prior_segment,
-                                           motion_range, auto_flags, profile_frames, min_count, frames_out, err, cap);
-  auto refuse = [&](int code, const std::string &m) {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (frames_out) *frames_out = 0;
-  if (!source || !out_tbl) return refuse(G1S_ERR_INVALID, "null path");
-  if (flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(G1S_ERR_INVALID, "unknown denoise flags");
-  std::string why = chroma_prior_refusal(chroma_prior, flags, prior_tbl, auto_flags);
-  if (why.empty() && dopts && dopts->struct_size != sizeof(g1s_denoise_opts_t)) why = "g1s_denoise_opts_t.struct_size mismatch";
-  Prior prior;
-  prior.chroma = true;
-  g1s_denoise_opts_t d{};
-  if (dopts) d = *dopts;
-  d.struct_size = sizeof d;
-  if (why.empty() && auto_flags) why = auto_prepass(source, opts ? opts->device : -1, auto_flags, profile_frames, min_count, prior_tbl, prior_range, &prior, &d);
-  if (why.empty() && prior_tbl) why = prior.load(prior_tbl, prior_range, prior_segment);
-  if (!why.empty()) return refuse(G1S_ERR_INVALID, why);
-  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, &d, temporal_radius, flags, &prior, motion_range, frames_out, err, cap);
-}
-
-// what g1s_diff_y4m_file_denoised_motion and g1s_diff_y4m_file_denoised_auto do once they have their prior (or none)
-static int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
-                                  const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const Prior *prior_or_null,
-                                  uint32_t motion_range, uint64_t *frames_out, char *err, size_t cap) {
-  auto refuse = [&](int code, const std::string &m) {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  const std::string header = y4m_header_line(source);
-  g1s_y4m_t *y = g1s_y4m_open(source, err, cap);
-  if (!y) return G1S_ERR_INVALID;
-  g1s_y4m_info_t info;
-  g1s_y4m_get_info(y, &info);
-  const PlaneGeom pg(info);
-  const Layout lay = packed_layout(pg);
-  g1s_diff_t *g = nullptr;
-  g1s_denoise_t *dn = nullptr;
-  FILE *fk = nullptr;
-  PinnedBuf<uint8_t> kbuf;
-  struct Pair {
-    DevBuf<uint8_t> src, den;
-  };
-  std::vector<Pair> pairs;                          // every pair of buffers allocated so far
-  std::deque<std::pair<uint64_t, size_t>> lent;     // (frame index, pair) handed to the generator, oldest first
-  std::deque<size_t> held;                          // pairs of the frames the denoiser has not completed, oldest first
-  std::vector<size_t> spare;
-  size_t pair_cap = 0;
-  uint64_t frames = 0, taken = 0, complete = 0;     // frames handed to the generator; to the denoiser; completed by it
-  uint32_t D = 0;
-  int rc = G1S_OK;
-  std::string why;
-  std::vector<g1s_segment_t> segs(64);
-  size_t nseg = 0;
-
-  g = g1s_diff_new(info.fps_num, info.fps_den, info.bit_depth, info.bit_depth, opts);
-  if (!g) {
-    rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
-    goto done;
-  }
-  {
-    g1s_denoise_opts_t d{};
-    if (dopts) d = *dopts;
-    d.struct_size = sizeof d;
-    d.device = g1s_diff_device_(g);  // one device: the pair never leaves it
-    dn = prior_or_null ? prior_or_null->open(info.bit_depth, &d, temporal_radius, flags, motion_range)
-                       : g1s_denoise_new_motion(info.bit_depth, &d, temporal_radius, flags, nullptr, nullptr, motion_range);
-  }
-  if (!dn) {
-    rc = G1S_ERR_INVALID, why = g1s_last_global_error();
-    goto done;
-  }
-  (void)hipSetDevice(g1s_diff_device_(g));
-  if (keep_denoised) {
-    fk = std::fopen(keep_denoised, "wb");
-    if (!fk || std::fwrite(header.data(), 1, header.size(), fk) != header.size() ||
-        hipHostMalloc((void **)&kbuf.p, lay.frame, hipHostMallocDefault) != hipSuccess) {
-      rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
-      goto done;
-    }
-  }
-  // buffers for two groups until the generator has said how many frames it can hold (after the first hand-over), and for
-  // the window: the D frames the denoiser holds back and the D before them that are still their neighbours
-  D = dn->D;
-  pair_cap = 2 * (size_t)dn->batch + 2 * D;
-  for (bool eof = false; !eof && !rc;) {
-    // ---- one group: up to batch_frames frames to the device and to the denoiser
-    for (uint32_t in_group = 0; in_group < dn->batch; ++in_group) {
-      g1s_frame_t fin;
-      const int got = g1s_y4m_next(y, &fin);
-      if (got < 0) {
-        rc = got, why = "frame " + std::to_string(taken) + ": source reader failed (" + g1s_y4m_last_error(y) + ")";
-        break;
-      }
-      if (got == 0) {
-        eof = true;
-        break;
-      }
-      // a pair of buffers: one that the generator has released and the denoiser is past (frame t + D complete), a new one,
-      // or -- the ring is full -- wait for the generator
-      size_t k;
-      uint64_t released = g1s_diff_frames_released(g);
-      auto reclaim = [&] {
-        while (!lent.empty() && lent.front().first < released && lent.front().first + D < complete) spare.push_back(lent.front().second), lent.pop_front();
-      };
-      reclaim();
-      if (spare.empty() && pairs.size() >= pair_cap) {
-        rc = g1s_diff_sync(g);
-        if (rc) {
-          why = std::string("diff_frame: ") + g1s_diff_last_error(g);
-          break;
-        }
-        released = frames;
-        reclaim();
-      }
-      if (!spare.empty()) {
-        k = spare.back(), spare.pop_back();
-      } else {
-        Pair p;
-        if (hipMalloc((void **)&p.src.p, lay.frame) != hipSuccess || hipMalloc((void **)&p.den.p, lay.frame) != hipSuccess) {
-          rc = G1S_ERR_HIP, why = "hipMalloc of a frame pair failed";
-          break;
-        }
-        pairs.push_back(std::move(p)), k = pairs.size() - 1;
-      }
-      // the reader lends the frame until its next call: on the device before that
-      bool copied = true;
-      for (int c = 0; c < pg.nplanes; ++c)
-        copied = copied && hipMemcpy2D(pairs[k].src + lay.off[c], lay.row[c], fin.data[c], fin.stride_bytes[c], lay.row[c], pg.ph(c), hipMemcpyHostToDevice) == hipSuccess;
-      if (!copied) {
-        rc = G1S_ERR_HIP, why = "copy of a source frame to the device failed";
-        break;
-      }
-      g1s_frame_t s = fin, d = fin;
-      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
-      s.on_device = d.on_device = 1;
-      rc = g1s_denoise_frame(dn, &s, &d);
-      if (rc) {
-        why = "frame " + std::to_string(taken) + ": denoise: " + g1s_denoise_last_error(dn);
-        break;
-      }
-      held.push_back(k), ++taken;
-    }
-    if (rc) break;
-    // the end of the file is the end of the clip; before it the last D frames stay with the denoiser
-    rc = eof ? g1s_denoise_sync(dn) : g1s_denoise_drain(dn, &complete);
-    if (rc) {
-      why = std::string("denoise: ") + g1s_denoise_last_error(dn);
-      break;
-    }
-    if (eof) complete = taken;
-    // ---- the completed frames' pairs to the generator, the denoised frames to the kept file
-    while (frames < complete) {
-      const size_t k = held.front();
-      held.pop_front();
-      g1s_frame_t s{}, d{};
-      s.width = info.width, s.height = info.height, s.bytes_per_sample = info.bit_depth > 8 ? 2 : 1, s.xdec = (uint8_t)info.xdec, s.ydec = (uint8_t)info.ydec,
-      s.nplanes = (uint8_t)info.nplanes, s.on_device = 1;
-      d = s;
-      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
-      rc = g1s_diff_frame(g, &s, &d);
-      if (rc) {
-        why = "frame " + std::to_string(frames) + ": diff_frame: " + g1s_diff_last_error(g);
-        break;
-      }
-      lent.emplace_back(frames, k);
-      if (fk && (hipMemcpy(kbuf, pairs[k].den, lay.frame, hipMemcpyDeviceToHost) != hipSuccess || std::fwrite("FRAME\n", 1, 6, fk) != 6 ||
-                 std::fwrite(kbuf, 1, lay.frame, fk) != lay.frame)) {
-        rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
-        break;
-      }
-      ++frames;
-    }
-    if (rc) break;
-    if (const uint32_t inside = g1s_diff_frames_in_flight_max_(g)) pair_cap = std::max(pair_cap, (size_t)dn->batch + inside + inside / 4 + 2 * D);
-  }
-  if (rc) goto done;
-  rc = g1s_diff_finish(g, segs.data(), segs.size(), &nseg);
-  if (rc == G1S_ERR_CAPACITY) {
-    segs.resize(nseg);
-    rc = g1s_diff_finish(g, segs.data(), segs.size(), &nseg);
-  }
-  if (rc) {
-    why = g1s_diff_last_error(g);
-    goto done;
-  }
-  rc = g1s_write_tbl(out_tbl, segs.data(), nseg);
-  if (rc) why = std::string("cannot write ") + out_tbl;
-done:
-  if (fk && std::fclose(fk) != 0 && !rc) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
-  if (dn) g1s_denoise_free(dn);
-  if (g) g1s_diff_free(g);  // (waits for the kernels that read the pairs, which go when this call returns)
-  g1s_y4m_close(y);
-  if (frames_out) *frames_out = frames;
-  if (rc) return refuse(rc, why);
-  return G1S_OK;
-}
 
 }  // extern "C"

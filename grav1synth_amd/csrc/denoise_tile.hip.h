@@ -13,7 +13,7 @@
 // a sample p reads Wb at p for its neighbour p + d and at p - d for its neighbour p - d.  Per offset: dn_hsum, barrier,
 // dn_weights, barrier, dn_accumulate (into registers; the next dn_hsum writes Hb only, so no third barrier).
 //
-// The temporal filter (rules 5 - 7, kd_nlm_t) adds
+// The temporal filter (rules 5 - 7, kd_nlm<kTemporal>) adds
 //
 //   N   the same tile and halo of ONE neighbour frame, in the layout of L; the neighbours that take part are staged one
 //       after the other, so LDS does not grow with the temporal radius.
@@ -24,11 +24,11 @@
 // is no half plane to save, and the weight is read at p only.  Hb and Wb as sized for the frame itself are large enough.
 // The numerator of rule 7 needs 64 bits (dn_store over uint64_t).
 //
-// The joint chroma filter (rules 8 - 11t, kd_nlm_j and kd_nlm_jt) runs the same phases over three sample arrays and two output
+// The joint chroma filter (rules 8 - 11t, kd_nlm_j) runs the same phases over three sample arrays and two output
 // planes (JointGeom).  Every phase is written once, over NA sample arrays and NP output planes LP samples apart (one plane: NA =
 // NP = 1, LP = 0), as the source says (PlaneSrc, JointSrc); dn_spatial and dn_temporal run them; the tile functions own the registers.
 //
-// A chroma gain (rules 21 - 24, kd_nlm_jg, kd_nlm_jtg and kd_nlm_jtmg) adds, to the joint filter alone,
+// A chroma gain (rules 21 - 24, kd_nlm_j<.., GainArg>) adds, to the joint filter alone,
 //
 //   Mt  the 256-entry gain table m, u16, behind T; staged in T's loop, under the same first barrier.
 //
@@ -85,7 +85,7 @@ G1S_DN_HD TileGeom tile_geom(int A, int S) {
   return g;
 }
 
-// Luma-guided joint chroma (rules 8 - 11t, kd_nlm_j and kd_nlm_jt): Cb, Cr and the guide G as one weight.
+// Luma-guided joint chroma (rules 8 - 11t, kd_nlm_j): Cb, Cr and the guide G as one weight.
 //
 // Three sample arrays in the layout of L, JointGeom::LP samples apart: Cb, Cr, G.  G is the frame's input luma at chroma
 // resolution (rule 8), formed while staging.  Hb, Wb and T are the ones of tile_geom: the squared differences of the three
@@ -526,7 +526,7 @@ G1S_DN_HD void dn_temporal(int tid, const TileGeom &g, const Layout &o, uint8_t 
   }
 }
 
-// the four tile functions, start to end (what kd_nlm, kd_nlm_t, kd_nlm_j and kd_nlm_jt call); this one: one plane on its own
+// the four tile functions, start to end (what kd_nlm and kd_nlm_j call in their forms kPlain and kTemporal); this one: one plane on its own
 template <int S, int BPS, class Sync>
 G1S_DN_HD void dn_tile(int tid, const TileGeom &g, uint8_t *lds, const uint16_t *table, int q, const uint8_t *in, uint32_t in_stride, uint8_t *out,
                        uint32_t out_stride, int W, int H, int x0, int y0, Sync sync) {
@@ -710,7 +710,7 @@ G1S_DN_HD void dn_motion_tile(int tid, const MotionGeom &m, uint8_t *lds, const 
   }
 }
 
-// the temporal tile functions under motion (what kd_nlm_tm and kd_nlm_jtm call): `mv` is the tile's vectors, a pair of
+// the temporal tile functions under motion (what kd_nlm<kMotion> and kd_nlm_j<kMotion> call): `mv` is the tile's vectors, a pair of
 // int8 for each of the nnb neighbours, `mv_stride` bytes from one neighbour's to the next
 struct TileVectors {
   const int8_t *mv;

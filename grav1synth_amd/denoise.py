@@ -121,33 +121,18 @@ class Denoiser(FrameOp):
         self.joint_chroma = bool(joint_chroma)
         self.motion_range = motion_range
         opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
+        gain = fwd = inv = None  # a feature that is off: a null pointer to the last rung of g1s_denoise_new*
         if chroma_gain is not None:
             gain = np.ascontiguousarray(chroma_gain, np.uint16)
             if gain.shape != (256,) or not np.array_equal(gain, np.asarray(chroma_gain)):
                 raise G1SError(-1, "chroma gain: 256 entries in 1..16384")
-            fwd = inv = None
-            if curve is not None:
-                fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
-                if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
-                    raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
-            self._h = self._L.g1s_denoise_new_gain(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
-                                                   None if fwd is None else fwd.ctypes.data, None if inv is None else inv.ctypes.data,
-                                                   motion_range & 0xFFFFFFFF, gain.ctypes.data)
-        elif curve is None and motion_range:
-            self._h = self._L.g1s_denoise_new_motion(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), None, None,
-                                                     motion_range & 0xFFFFFFFF)
-        elif curve is None:
-            self._h = self._L.g1s_denoise_new_ex(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma))
-        else:
+        if curve is not None:
             fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
             if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
                 raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
-            if motion_range:
-                self._h = self._L.g1s_denoise_new_motion(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
-                                                         inv.ctypes.data, motion_range & 0xFFFFFFFF)
-            else:
-                self._h = self._L.g1s_denoise_new_curve(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), fwd.ctypes.data,
-                                                        inv.ctypes.data)
+        self._h = self._L.g1s_denoise_new_gain(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
+                                               None if fwd is None else fwd.ctypes.data, None if inv is None else inv.ctypes.data,
+                                               motion_range & 0xFFFFFFFF, None if gain is None else gain.ctypes.data)
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
@@ -207,7 +192,7 @@ class Denoiser(FrameOp):
         return a.value
 
     def kernel_times(self, enable: bool = True):
-        """(ms in kd_nlm / kd_nlm_t and their joint chroma forms -- with a curve also the two kd_curve launches -- , frames) of the timed batches
+        """(ms in kd_nlm and kd_nlm_j, whichever form -- with a curve also the two kd_curve launches -- , frames) of the timed batches
         so far (HIP events); enables / disables the timing."""
         a, n = C.c_double(), C.c_uint64()
         self._L.g1s_denoise_set_timing(self._h, int(enable), C.byref(a), C.byref(n))
@@ -232,20 +217,9 @@ def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames:
     if grain_prior is None and (prior_range or prior_segment is not None):
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
     prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
-    if chroma_prior:
-        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-        n = L.g1s_denoise_y4m_file_chroma(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                          motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1, err, len(err))
-    elif auto_prior or auto_strength:
-        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-        n = L.g1s_denoise_y4m_file_auto(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                        motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, err, len(err))
-    elif motion_range:
-        n = L.g1s_denoise_y4m_file_motion(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                          motion_range & 0xFFFFFFFF, err, len(err))
-    else:
-        n = L.g1s_denoise_y4m_file_curve(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                         err, len(err))
+    auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
+    n = L.g1s_denoise_y4m_file_chroma(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                      motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0, err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

@@ -132,18 +132,11 @@ def diff_y4m_file_denoised(source: str, output: str, *, keep_denoised: Optional[
     head = (str(source).encode(), str(output).encode(), str(keep_denoised).encode() if keep_denoised else None, C.byref(opts), C.byref(dopts),
             temporal_radius & 0xFFFFFFFF, _lib.G1S_DENOISE_JOINT_CHROMA if joint_chroma else 0,
             str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
-    if chroma_prior:
-        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-        rc = L.g1s_diff_y4m_file_denoised_chroma(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1, C.byref(frames), err, len(err))
-    elif auto_prior or auto_strength:
-        auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-        rc = L.g1s_diff_y4m_file_denoised_auto(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, C.byref(frames), err, len(err))
-    elif motion_range:
-        rc = L.g1s_diff_y4m_file_denoised_motion(*head, motion_range & 0xFFFFFFFF, C.byref(frames), err, len(err))
-    else:
-        rc = L.g1s_diff_y4m_file_denoised_curve(*head, C.byref(frames), err, len(err))
+    auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
+    rc = L.g1s_diff_y4m_file_denoised_chroma(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0,
+                                             C.byref(frames), err, len(err))
     if rc:
-        raise RuntimeError(err.value.decode() or f"g1s_diff_y4m_file_denoised_curve failed ({rc})")
+        raise RuntimeError(err.value.decode() or f"g1s_diff_y4m_file_denoised_chroma failed ({rc})")
     log.info("Computed diff for %d frames", frames.value)
     return int(frames.value)
 

@@ -1,6 +1,6 @@
 // denoise_gain_wg_host.cpp -- the gain instantiations of the three joint tile functions of
-// grav1synth_amd/csrc/denoise_tile.hip.h (dn_tile_j, dn_tile_jt and dn_tile_jtm with a Gain: what kd_nlm_jg, kd_nlm_jtg and
-// kd_nlm_jtmg call) on the host as they stand, with a real barrier for `sync` (tests/wg_host.h), as
+// grav1synth_amd/csrc/denoise_tile.hip.h (dn_tile_j, dn_tile_jt and dn_tile_jtm with a Gain: what the three forms of
+// kd_nlm_j<.., GainArg> call) on the host as they stand, with a real barrier for `sync` (tests/wg_host.h), as
 // tests/denoise_wg_host.cpp runs the tile functions without a gain -- and, in the same program, rule 24 of
 // include/g1s_diff.h as a plain loop over pairs, which the tiles' output is compared with.  tests/denoise_gain_wg.py builds it
 // with the address and undefined-behaviour sanitizers; tests/test_denoise_gain_schedule_cpu.py runs it.

@@ -1,5 +1,5 @@
 // denoise_motion_wg_host.cpp -- the motion tile functions of grav1synth_amd/csrc/denoise_tile.hip.h (dn_motion_tile, dn_tile_tm,
-// dn_tile_jtm: what kd_motion, kd_nlm_tm and kd_nlm_jtm call) on the host as they stand, with a real barrier for `sync`
+// dn_tile_jtm: what kd_motion, kd_nlm<kMotion> and kd_nlm_j<kMotion> call) on the host as they stand, with a real barrier for `sync`
 // (tests/wg_host.h), as tests/denoise_wg_host.cpp runs the four tile functions without motion.  tests/denoise_motion_wg.py
 // builds it with the address and undefined-behaviour sanitizers; tests/test_denoise_motion_schedule_cpu.py compares its output
 // with the numpy reference under every schedule and fill.

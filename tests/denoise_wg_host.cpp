@@ -1,5 +1,5 @@
 // denoise_wg_host.cpp -- the four tile functions of grav1synth_amd/csrc/denoise_tile.hip.h (dn_tile, dn_tile_t, dn_tile_j,
-// dn_tile_jt: what kd_nlm, kd_nlm_t, kd_nlm_j and kd_nlm_jt call) on the host as they stand, with a real barrier for `sync`
+// dn_tile_jt: what kd_nlm and kd_nlm_j call in their forms kPlain and kTemporal) on the host as they stand, with a real barrier for `sync`
 // (tests/wg_host.h): 256 logical threads a tile, run one at a time between two barriers in an order the caller names, the
 // LDS buffer filled with a pattern before every tile.  tests/denoise_wg.py builds it with the address and undefined-behaviour
 // sanitizers; tests/test_denoise_schedule_cpu.py compares its output with the numpy references under every schedule and fill

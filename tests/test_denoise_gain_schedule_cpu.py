@@ -1,5 +1,5 @@
 """The joint denoise tiles under a chroma gain (rules 21 - 24) with their real barriers, without a device: the gain
-instantiations of dn_tile_j, dn_tile_jt and dn_tile_jtm of denoise_tile.hip.h -- what kd_nlm_jg, kd_nlm_jtg and kd_nlm_jtmg
+instantiations of dn_tile_j, dn_tile_jt and dn_tile_jtm of denoise_tile.hip.h -- what the three forms of kd_nlm_j<.., GainArg>
 call -- run unmodified on a host workgroup (tests/wg_host.h, tests/denoise_gain_wg_host.cpp), as
 tests/test_denoise_schedule_cpu.py runs the tiles without a gain.  The program holds rule 24 as a plain loop over pairs and
 counts the samples that differ from it; the numpy restatement (tests/denoise_gain_ref.py) is compared with its bytes too.

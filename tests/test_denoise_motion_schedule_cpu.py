@@ -1,5 +1,5 @@
 """The motion tile functions with their real barriers, without a device: dn_motion_tile, dn_tile_tm and dn_tile_jtm of
-denoise_tile.hip.h -- what kd_motion, kd_nlm_tm and kd_nlm_jtm call -- run unmodified on a host workgroup (tests/wg_host.h,
+denoise_tile.hip.h -- what kd_motion, kd_nlm<kMotion> and kd_nlm_j<kMotion> call -- run unmodified on a host workgroup (tests/wg_host.h,
 tests/denoise_motion_wg_host.cpp) under the schedules and LDS fills of tests/test_denoise_schedule_cpu.py, against the numpy
 reference of rules 16 - 20 (tests/denoise_motion_ref.py).  The search adds three barriers (after staging, after the threads'
 keys, after the groups' keys); each is load-bearing, and some committed (schedule, fill) pair shows it.  The filter's tile

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernels kd_nlm and kd_nlm_t over
+"""tools/bench_denoise.py [batches] -- `denoise` on the GPU box: the non-local-means kernel kd_nlm (forms kPlain, kTemporal) over
 device-resident frames, 4K 10-bit 4:2:0 and 1080p 8-bit 4:2:0, batches of 64, at the defaults (A = 3, S = 2) and at A = 7, S = 3
 with temporal radius 0 and 1, and at the defaults with temporal radius 2; every case without and with joint chroma
-(kd_nlm_j / kd_nlm_jt take the chroma launch's place; "joint_chroma" in the line).  Per case: HIP-event time per batch around the two
+(kd_nlm_j in the same form takes the chroma launch's place; "joint_chroma" in the line).  Per case: HIP-event time per batch around the two
 launches (timed batches run alone and are waited for), frames a second from it, the kernel's arithmetic as the specification
 counts it -- samples x pairs: the unordered pairs A + A (2A + 1) of the frame itself and, per neighbour frame, the (2A + 1)^2
 one-sided pairs of rule 6 (a frame at the end of a clip has fewer; the runs are clips of many batches) -- and the job rate
