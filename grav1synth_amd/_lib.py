@@ -383,6 +383,15 @@ SYMBOLS = [
     ("g1s_diff_y4m_file_denoised_chroma", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32,
                                                     C.c_char_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
                                                     C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    ("g1s_denoise_new_levels", C.c_void_p, [C.c_uint32, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_uint32, C.c_double]),
+    ("g1s_denoise_level_time", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("g1s_denoise_level_kernel_time", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("g1s_denoise_y4m_file_levels", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int32,
+                                                C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised_levels", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32,
+                                                    C.c_char_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                    C.c_double, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("g1s_denoise_drain", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("g1s_denoise_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame), C.POINTER(G1SFrame)]),
     ("g1s_denoise_sync", C.c_int, [C.c_void_p]),

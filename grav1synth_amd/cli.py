@@ -41,6 +41,9 @@ DENOISE_ONE_DEVICE = "--denoise does not combine with --gpus / --devices (one de
 BAD_TEMPORAL_RADIUS = "--temporal-radius must be 0..3 (frames before and after the one in hand). Exiting."
 BAD_MOTION_RANGE = "--motion-range must be even and 0..64 (samples a tile may move between two frames). Exiting."
 MOTION_NEEDS_TEMPORAL = "--motion-range moves the neighbour frames of --temporal-radius: it needs a temporal radius above 0. Exiting."
+BAD_COARSE_LEVELS = "--coarse-levels must be 0..2 (box means of the frame that are filtered as well). Exiting."
+BAD_COARSE_RATIO = "--coarse-ratio must be 0.0625..4 (a coarse level's strength over that of the level above it; 0 = 1). Exiting."
+RATIO_NEEDS_LEVELS = "--coarse-ratio scales the strength of --coarse-levels: it needs a level above 0. Exiting."
 KEEP_NEEDS_DENOISE = "--keep-denoised writes the clip --denoise makes: it needs --denoise. Exiting."
 PRIOR_NEEDS_TABLE = "--prior-range and --prior-segment say how --grain-prior is used: they need --grain-prior. Exiting."
 PRIOR_12_BIT = ("--grain-prior filters luma in a 12-bit domain: a 12-bit input has no headroom there (8 and 10 bits are "
@@ -119,6 +122,11 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
                    help="with --joint-chroma and --grain-prior or --auto-prior: the chroma strength follows the grain at the luma under "
                         "each sample -- the table's chroma scaling functions, or the chroma noise the pre-pass measured per luma bin; "
                         "--prior-range 1..8 applies; 8-, 10-bit inputs; off by default")
+    p.add_argument("--coarse-levels", type=int, default=0, metavar="K",
+                   help="coarse levels K, 0..2 (default 0): the 2 x 2 box mean of every frame (K = 2: its box mean as well) goes through the "
+                        "same filter and replaces the low frequencies of the result; for grain coarser than a patch, also on a single frame")
+    p.add_argument("--coarse-ratio", type=float, default=0.0, metavar="R",
+                   help="with --coarse-levels: a level's strengths over those of the level above it, 0.0625..4 (default 1)")
 
 
 def _denoise_parameters(args) -> dict:
@@ -126,7 +134,8 @@ def _denoise_parameters(args) -> dict:
                 chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
                 grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range,
                 auto_prior=args.auto_prior, auto_strength=args.auto_strength, profile_frames=args.profile_frames,
-                levels_min_count=args.levels_min_count, chroma_prior=args.chroma_prior)
+                levels_min_count=args.levels_min_count, chroma_prior=args.chroma_prior, coarse_levels=args.coarse_levels,
+                coarse_ratio=args.coarse_ratio)
 
 
 def _auto_refused(input: str, parameters: dict) -> bool:
@@ -184,6 +193,21 @@ def _chroma_prior_refused(parameters: dict) -> bool:
         return True
     if not 0 <= parameters.get("prior_range", 0) <= 8:
         log.error(CHROMA_PRIOR_BAD_RANGE)
+        return True
+    return False
+
+
+def _levels_refused(parameters: dict) -> bool:
+    """The refusals of --coarse-levels / --coarse-ratio, each a logged line: True when one was logged."""
+    k, r = parameters.get("coarse_levels", 0), parameters.get("coarse_ratio", 0.0)
+    if not 0 <= k <= 2:
+        log.error(BAD_COARSE_LEVELS)
+        return True
+    if r != 0.0 and not 0.0625 <= r <= 4.0:
+        log.error(BAD_COARSE_RATIO)
+        return True
+    if r != 0.0 and not k:
+        log.error(RATIO_NEEDS_LEVELS)
         return True
     return False
 
@@ -328,7 +352,7 @@ def diff_denoise_command(source: str, output: str, overwrite: bool = False, devi
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
         return -1
-    if _motion_refused(parameters) or _chroma_prior_refused(parameters):
+    if _motion_refused(parameters) or _chroma_prior_refused(parameters) or _levels_refused(parameters):
         return -1
     if _same_path(source, output) or (keep_denoised is not None and (_same_path(source, keep_denoised) or _same_path(keep_denoised, output))):
         log.error(SAME_AS_OUTPUT)
@@ -438,7 +462,7 @@ def denoise_command(input: str, output: str, overwrite: bool = False, device: in
     if not 0 <= parameters.get("temporal_radius", 0) <= 3:
         log.error(BAD_TEMPORAL_RADIUS)
         return -1
-    if _motion_refused(parameters) or _chroma_prior_refused(parameters):
+    if _motion_refused(parameters) or _chroma_prior_refused(parameters) or _levels_refused(parameters):
         return -1
     if _same_path(input, output):
         log.error(SAME_AS_OUTPUT)

@@ -35,10 +35,13 @@
 #include "curve_row.hip.h"
 #include "denoise_tile.hip.h"
 #include "frame_op.h"
+#include "levels_row.hip.h"
 
 namespace {
 
 using namespace g1s_dn;
+
+constexpr int kMaxLevels = 2;  // coarse levels (rule 28)
 
 struct DenoiseJob {
   const uint8_t *in[3];
@@ -228,11 +231,23 @@ bool launch_family(uint32_t S, uint32_t bps, dim3 grid, size_t lds, hipStream_t 
     if (e_ != hipSuccess) return (g)->fail(G1S_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
   } while (0)
 
+// rule 3's bound on a strength and its text, and the strengths of level 0 as the opts give them (a zero field, or no opts: the
+// default): the one place either is said -- make_table, rule 28's levels and the commands' early look at them ask here
+constexpr const char *kStrengthBound = "strength must be greater than 0 and at most 1000";
+inline bool strength_ok(double h) { return h > 0.0 && h <= 1000.0; }
+struct Strengths {
+  double h, hc;
+};
+inline Strengths strengths_of(const g1s_denoise_opts_t *opts) {
+  const double h = opts && opts->strength != 0.0 ? opts->strength : 4.0;
+  return {h, opts && opts->chroma_strength != 0.0 ? opts->chroma_strength : h};
+}
+
 // rule 3, for patches of `planes` planes (rule 10: 3).  "" when fine.
 std::string make_table(uint32_t bit_depth, uint32_t S, double h, uint16_t T[kTable], uint32_t *q_out, uint32_t planes = 1) {
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return "denoise is defined for bit depths 8, 10 and 12";
   if (S < 1 || S > (uint32_t)kMaxS) return "patch_radius must be 1..4";
-  if (!(h > 0.0) || !(h <= 1000.0)) return "strength must be greater than 0 and at most 1000";
+  if (!strength_ok(h)) return kStrengthBound;
   const double n = (double)(planes * (2 * S + 1) * (2 * S + 1)), den = n * h * h * std::pow(4.0, (double)bit_depth - 8.0);
   auto entry = [&](int i, uint32_t q) { return std::floor(4096.0 * std::exp(-(((double)i + 0.5) * std::ldexp(1.0, (int)q)) / den) + 0.5); };
   uint32_t q = 0;
@@ -295,6 +310,28 @@ struct g1s_denoise : BatchedOp {
       off[c] = at, at += align_up((size_t)2 * nnb * (size_t)blocks_of(pg, c), 16);
     }
     return at;
+  }
+  // coarse levels (rules 25 - 29): level K - 1 is a whole denoiser on the coarse frames, made by new_denoiser with the scaled
+  // strengths and the halved motion range, on this denoiser's stream.  Its frames are device frames in three rings for the
+  // geometry in hand: coarse inputs (a slot a frame of the input ring), coarse outputs and d (a slot a frame of a batch).
+  uint32_t K = 0;
+  g1s_denoise *inner = nullptr;
+  bool borrowed_stream = false;  // an inner level's stream is its owner's
+  PlaneGeom cgeom;               // the coarse frame (rule 25)
+  Layout clay, dlay;             // a coarse frame; its d: the same planes as int16
+  DevBuf<uint8_t> d_cin, d_cout, d_d;
+  ParamSets<uint8_t> p_level;    // a set: the kd_down jobs (batch + D), then the merge's (batch)
+  uint64_t next_coarse = 0;      // the first frame whose coarse frame is not made and handed to the inner level yet
+  double ms_level = 0, ms_level_k = 0;  // of the timed batches: the three kernels and the inner level; the three kernels alone
+  Event evl[5];
+  size_t off_merge() const { return sizeof(g1s_lv::LevelJob) * (batch + D); }
+  size_t level_bytes() const { return off_merge() + sizeof(g1s_lv::LevelJob) * batch; }
+  int need_levels();
+  int coarse_level(int set, uint32_t nframes, uint32_t ndown, uint64_t first_down);
+  int merge(int set, uint32_t nframes);
+  ~g1s_denoise() {
+    delete inner;
+    if (borrowed_stream) stream.p = nullptr;
   }
   int need_mv();
   int launch_motion(const DenoiseJobTM *jobs, const PlaneGeom &pg, uint32_t nframes, uint32_t nnb, int plane0, uint32_t bps_, hipStream_t st);
@@ -384,6 +421,53 @@ int g1s_denoise::need_mv() {
   return G1S_OK;
 }
 
+// the three rings of a coarse level for the geometry in hand
+int g1s_denoise::need_levels() {
+  if (d_cin) return G1S_OK;
+  cgeom = geom, cgeom.W = (geom.W + 1) >> 1, cgeom.H = (geom.H + 1) >> 1;  // (rule 25: its chroma planes are the chroma planes' boxes)
+  PlaneGeom dg = cgeom;
+  dg.bps = 2;
+  clay = staging_layout(cgeom), dlay = staging_layout(dg);
+  if (hipMalloc((void **)&d_cin.p, clay.frame * ring()) != hipSuccess || hipMalloc((void **)&d_cout.p, clay.frame * batch) != hipSuccess ||
+      hipMalloc((void **)&d_d.p, dlay.frame * batch) != hipSuccess)
+    return fail(G1S_ERR_HIP, "hipMalloc of the coarse level's planes failed");
+  return G1S_OK;
+}
+
+// In front of a batch's fine launches: kd_down for the `ndown` frames from `first_down` on (the set's first jobs), those
+// frames handed to the inner level as device frames, and the inner level's launches for the batch's frames.  Everything
+// is ordered by the one stream.
+int g1s_denoise::coarse_level(int set, uint32_t nframes, uint32_t ndown, uint64_t first_down) {
+  G1S_OP_TRY(p_level.upload(set, level_bytes(), stream));
+  if (timing) G1S_OP_TRY(hipEventRecord(evl[0], stream));
+  const int W[3] = {(int)geom.pw(0), (int)geom.pw(1), (int)geom.pw(2)}, H[3] = {(int)geom.ph(0), (int)geom.ph(1), (int)geom.ph(2)};
+  G1S_OP_TRY(g1s_lv::launch_down((int)bps, reinterpret_cast<const g1s_lv::LevelJob *>(p_level.d[set].p), ndown, geom.nplanes, W, H, stream));
+  if (timing) G1S_OP_TRY(hipEventRecord(evl[4], stream));
+  for (uint64_t m = first_down; m < first_down + ndown; ++m) {
+    g1s_frame_t fi{}, fo{};
+    fi.width = (uint32_t)cgeom.W, fi.height = (uint32_t)cgeom.H, fi.bytes_per_sample = (uint8_t)bps, fi.xdec = (uint8_t)cgeom.subx, fi.ydec = (uint8_t)cgeom.suby;
+    fi.nplanes = (uint8_t)cgeom.nplanes, fi.on_device = 1;
+    fo = fi;
+    clay.point(fi, d_cin + clay.frame * (size_t)(m % ring()), cgeom.nplanes);
+    clay.point(fo, d_cout + clay.frame * (size_t)(m % batch), cgeom.nplanes);
+    if (g1s_denoise_frame(inner, &fi, &fo) != G1S_OK) return fail(inner->err_code, "coarse level: " + inner->err);
+  }
+  if (inner->launch_up_to(next_launch + nframes) != G1S_OK) return fail(inner->err_code, "coarse level: " + inner->err);
+  if (timing) G1S_OP_TRY(hipEventRecord(evl[1], stream));
+  return G1S_OK;
+}
+
+// Behind a batch's fine launches (rule 27): d = c - box(out), out += U(d) in place -- on the caller's plane or the staging slot
+int g1s_denoise::merge(int set, uint32_t nframes) {
+  const g1s_lv::LevelJob *jobs = reinterpret_cast<const g1s_lv::LevelJob *>(p_level.d[set].p + off_merge());
+  const int W[3] = {(int)geom.pw(0), (int)geom.pw(1), (int)geom.pw(2)}, H[3] = {(int)geom.ph(0), (int)geom.ph(1), (int)geom.ph(2)};
+  if (timing) G1S_OP_TRY(hipEventRecord(evl[2], stream));
+  G1S_OP_TRY(g1s_lv::launch_lowres((int)bps, jobs, nframes, geom.nplanes, W, H, stream));
+  G1S_OP_TRY(g1s_lv::launch_add((int)bps, (int)bit_depth, jobs, nframes, geom.nplanes, W, H, stream));
+  if (timing) G1S_OP_TRY(hipEventRecord(evl[3], stream));
+  return G1S_OK;
+}
+
 // kd_motion for the planes of a class (plane0 = 0: luma, in samples of bps_ bytes; 1: the chroma planes, or under the joint
 // flag the pair) of `nframes` jobs with nnb neighbours each
 int g1s_denoise::launch_motion(const DenoiseJobTM *jobs, const PlaneGeom &pg, uint32_t nframes, uint32_t nnb, int plane0, uint32_t bps_, hipStream_t st) {
@@ -418,6 +502,20 @@ int g1s_denoise::flush(uint32_t nframes) {
     for (const uint64_t upto = std::min<uint64_t>(frames_in, next_launch + nframes + D); next_stab < upto; ++next_stab)
       cf[nfwd++] = g1s_cv::CurveJob{frame(next_stab).in[0], stab_slot(next_stab), frame(next_stab).in_stride[0], (uint32_t)stab_row};
   }
+  // with coarse levels: the same for the coarse frames -- kd_down's jobs
+  uint32_t ndown = 0;
+  const uint64_t first_down = next_coarse;
+  if (K) {
+    g1s_lv::LevelJob *dj = reinterpret_cast<g1s_lv::LevelJob *>(p_level.h[set].p);
+    for (const uint64_t upto = std::min<uint64_t>(frames_in, next_launch + nframes + D); next_coarse < upto; ++next_coarse) {
+      g1s_lv::LevelJob &j = dj[ndown++];
+      j = g1s_lv::LevelJob{};
+      for (int c = 0; c < geom.nplanes; ++c) {
+        j.fine[c] = const_cast<uint8_t *>(frame(next_coarse).in[c]), j.fine_stride[c] = frame(next_coarse).in_stride[c];
+        j.coarse[c] = d_cin + clay.frame * (size_t)(next_coarse % ring()) + clay.off[c], j.coarse_stride[c] = (uint32_t)clay.row[c];
+      }
+    }
+  }
   for (uint32_t i = 0; i < nframes; ++i) {
     const uint64_t n = next_launch + i;
     const Queued &f = frame(n);
@@ -430,6 +528,15 @@ int g1s_denoise::flush(uint32_t nframes) {
       job.out_stride[c] = f.host_out ? (uint32_t)stage.row[c] : f.out_stride[c];
     }
     host_outs = host_outs || f.host_out;
+    if (K) {  // the merge's job: the coarse level's output of the frame, its d, and the planes the fine launch writes
+      g1s_lv::LevelJob &j = reinterpret_cast<g1s_lv::LevelJob *>(p_level.h[set].p + off_merge())[i];
+      j = g1s_lv::LevelJob{};
+      for (int c = 0; c < geom.nplanes; ++c) {
+        j.fine[c] = job.out[c], j.fine_stride[c] = job.out_stride[c];
+        j.coarse[c] = d_cout + clay.frame * (size_t)(n % batch) + clay.off[c], j.coarse_stride[c] = (uint32_t)clay.row[c];
+        j.d[c] = d_d + dlay.frame * (size_t)i + dlay.off[c], j.d_stride[c] = (uint32_t)dlay.row[c];
+      }
+    }
     // (rule 14) the luma launch's job: from the frame's slot into plane i of the filtered ones, which the inverse takes
     // to where the frame's luma goes
     if (curve) {
@@ -453,6 +560,7 @@ int g1s_denoise::flush(uint32_t nframes) {
   }
   G1S_OP_TRY(p_jobs.upload(set, curve ? set_bytes() : job_bytes() * nframes, stream));
   if (timing) G1S_OP_TRY(hipEventRecord(ev[0], stream));
+  if (K && (rc = coarse_level(set, nframes, ndown, first_down)) != 0) return rc;
   if (curve)
     G1S_OP_TRY(g1s_cv::launch_curve((int)bps, 2, reinterpret_cast<const g1s_cv::CurveJob *>(p_jobs.d[set].p + off_fwd()), nfwd, d_curve, 1u << bit_depth,
                                     (uint32_t)geom.W, (uint32_t)geom.H, stream));
@@ -477,6 +585,7 @@ int g1s_denoise::flush(uint32_t nframes) {
     return rc;
   }
   if (geom.nplanes == 3 && (rc = joint ? launch_joint(set, nframes) : launch(set, nframes, 1, 2)) != 0) return rc;
+  if (K && (rc = merge(set, nframes)) != 0) return rc;
   if (timing) G1S_OP_TRY(hipEventRecord(ev[1], stream));
   if ((rc = set_done(set)) != 0) return rc;
   for (uint32_t i = 0; host_outs && i < nframes; ++i)
@@ -486,6 +595,14 @@ int g1s_denoise::flush(uint32_t nframes) {
     float a = 0;
     G1S_OP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
     ms_kernel += a, frames_timed += nframes;
+    if (K) {
+      // evl: 0 in front of kd_down, 4 behind it, 1 behind the inner level's launches; 2 in front of kd_lowres, 3 behind kd_add
+      float front = 0, down = 0, merged = 0;
+      G1S_OP_TRY(hipEventElapsedTime(&front, evl[0], evl[1]));
+      G1S_OP_TRY(hipEventElapsedTime(&down, evl[0], evl[4]));
+      G1S_OP_TRY(hipEventElapsedTime(&merged, evl[2], evl[3]));
+      ms_level += front + merged, ms_level_k += down + merged;
+    }
   }
   next_launch += nframes;
   // what stays in front of the frames to come: the D frames before the next one to launch
@@ -507,7 +624,9 @@ int g1s_denoise::end_clip() {
   int rc = launch_up_to(frames_in);
   if (rc || (rc = wait()) != 0) return rc;
   queue.clear();
-  first_queued = clip_first = frames_complete = next_stab = frames_in;
+  first_queued = clip_first = frames_complete = next_stab = next_coarse = frames_in;
+  // (the coarse frames of a clip are a clip with the same ends)
+  if (inner && inner->end_clip() != G1S_OK) return fail(inner->err_code, "coarse level: " + inner->err);
   return G1S_OK;
 }
 
@@ -518,11 +637,29 @@ struct DenoiserSpec {
   const uint16_t *fwd = nullptr, *inv = nullptr;
   uint32_t motion_range = 0;
   const uint16_t *chroma_gain = nullptr;
+  uint32_t coarse_levels = 0;
+  double coarse_ratio = 0.0;
+  hipStream_t share = nullptr;  // (an inner level) the stream of the denoiser that owns this one
 };
+
+// rule 28: the refusals of K levels at ratio rho (0: 1.0) over the strengths h, hc of level 0, which passed rule 3's
+// bounds.  Level l's strengths are rho times level l - 1's.  "" when fine.
+static std::string levels_refusal(uint32_t K, double rho, double h, double hc) {
+  if (K > (uint32_t)kMaxLevels) return "coarse_levels must be 0..2";
+  if (rho != 0.0 && (!(rho >= 0.0625) || !(rho <= 4.0))) return "coarse_ratio must be 0.0625..4 (0 = 1)";
+  if (rho != 0.0 && !K) return "coarse_ratio needs coarse_levels";
+  const double r = rho != 0.0 ? rho : 1.0;
+  for (uint32_t l = 1; l <= K; ++l) {
+    h *= r, hc *= r;
+    if (!strength_ok(h)) return "level " + std::to_string(l) + " " + kStrengthBound;
+    if (!strength_ok(hc)) return "level " + std::to_string(l) + " chroma_" + kStrengthBound;
+  }
+  return "";
+}
 
 // what every g1s_denoise_new* call makes
 static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, const DenoiserSpec &spec) {
-  const auto [temporal_radius, flags, curve, fwd, inv, motion_range, chroma_gain] = spec;
+  const auto [temporal_radius, flags, curve, fwd, inv, motion_range, chroma_gain, coarse_levels, coarse_ratio, share] = spec;
   g1s_set_global_error_("");
   if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
     g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
@@ -530,7 +667,7 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   }
   // the parameters first: a refusal needs no device
   const uint32_t A = opts && opts->search_radius ? opts->search_radius : 3u, S = opts && opts->patch_radius ? opts->patch_radius : 2u;
-  const double h = opts && opts->strength != 0.0 ? opts->strength : 4.0, hc = opts && opts->chroma_strength != 0.0 ? opts->chroma_strength : h;
+  const auto [h, hc] = strengths_of(opts);
   if (A < 1 || A > (uint32_t)kMaxA) {
     g1s_set_global_error_("search_radius must be 1..7");
     return nullptr;
@@ -571,6 +708,7 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
     why = g1s_cv::check(bit_depth, fwd, inv);
     if (why.empty()) why = make_table(g1s_cv::kStabBits, S, h, tables.data() + 3 * kTable, &q[3]);
   }
+  if (why.empty()) why = levels_refusal(coarse_levels, coarse_ratio, h, hc);
   if (!why.empty()) {
     g1s_set_global_error_(why.c_str());
     return nullptr;
@@ -598,8 +736,30 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
   g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
   g->curve = curve, g->M = motion_range / 2, g->gain = chroma_gain != nullptr;
   for (int i = 0; i < 4; ++i) g->q[i] = q[i];
+  g->K = coarse_levels;
   bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
+  if (ok && share) {  // an inner level runs on its owner's stream: one order for kd_down, its launches and the merge
+    (void)hipStreamDestroy(g->stream.p);
+    g->stream.p = share, g->borrowed_stream = true;
+  }
   for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+  if (ok && coarse_levels) {
+    // rule 26: level K - 1 on the coarse frames -- the strengths times rho, Mr' = 2 ceil(Mr / 4), everything else the same
+    const double rho = coarse_ratio != 0.0 ? coarse_ratio : 1.0;
+    g1s_denoise_opts_t io{};
+    io.struct_size = sizeof io, io.device = device, io.batch_frames = g->batch, io.search_radius = A, io.patch_radius = S;
+    io.strength = rho * h, io.chroma_strength = rho * hc;
+    for (Event &e : g->evl) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    ok = ok && g->p_level.alloc(g->level_bytes());
+    if (ok) {
+      g->inner = new_denoiser(bit_depth, &io, {temporal_radius, flags, curve, fwd, inv, 2 * ((motion_range + 3) / 4), chroma_gain, coarse_levels - 1,
+                                               coarse_levels > 1 ? rho : 0.0, g->stream.p});
+      if (!g->inner) {  // (the parameters were checked above: a refusal here is the device's, with its text set)
+        free_op(g);
+        return nullptr;
+      }
+    }
+  }
   ok = ok && g->p_jobs.alloc(g->set_bytes()) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
        hipMemcpy(g->d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
   if (ok && curve) {
@@ -658,6 +818,21 @@ g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts
 g1s_denoise_t *g1s_denoise_new_gain(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
                                     const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain) {
   return new_denoiser(bit_depth, opts, {temporal_radius, flags, fwd || inv, fwd, inv, motion_range, chroma_gain});
+}
+
+g1s_denoise_t *g1s_denoise_new_levels(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags, const uint16_t *fwd,
+                                      const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain, uint32_t coarse_levels, double coarse_ratio) {
+  return new_denoiser(bit_depth, opts, {temporal_radius, flags, fwd || inv, fwd, inv, motion_range, chroma_gain, coarse_levels, coarse_ratio});
+}
+
+// (denoise_file.cpp) rule 28's refusals for a command that looks for its device before it makes the denoiser: the text into
+// err, or "" -- with the strengths as the opts give them (0 = the default; an auto strength is checked when the denoiser is made)
+void g1s_denoise_levels_refusal_(const g1s_denoise_opts_t *opts, uint32_t coarse_levels, double coarse_ratio, char *err, size_t cap) {
+  // (opts of another size, or strengths rule 3 refuses: the constructor says so; the levels are then looked at over the defaults)
+  Strengths s = strengths_of(opts && opts->struct_size == sizeof(g1s_denoise_opts_t) ? opts : nullptr);
+  if (!strength_ok(s.h) || !strength_ok(s.hc)) s = strengths_of(nullptr);
+  const std::string why = levels_refusal(coarse_levels, coarse_ratio, s.h, s.hc);
+  if (err && cap) snprintf(err, cap, "%s", why.c_str());
 }
 
 // (denoise_file.cpp) what the file commands size their rings by
@@ -741,6 +916,19 @@ int g1s_denoise_motion_time(g1s_denoise_t *g, double *ms_motion) {
   return G1S_OK;
 }
 
+int g1s_denoise_level_time(g1s_denoise_t *g, double *ms_level) {
+  if (!g || !ms_level) return G1S_ERR_INVALID;
+  *ms_level = g->ms_level;
+  return G1S_OK;
+}
+
+int g1s_denoise_level_kernel_time(g1s_denoise_t *g, double *ms_kernels) {
+  if (!g || !ms_kernels) return G1S_ERR_INVALID;
+  *ms_kernels = 0;
+  for (const g1s_denoise *l = g; l; l = l->inner) *ms_kernels += l->ms_level_k;
+  return G1S_OK;
+}
+
 int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out) {
   if (!g || !in || !out) return G1S_ERR_INVALID;
   if (g->err_code) return g->err_code;
@@ -754,8 +942,11 @@ int g1s_denoise_frame(g1s_denoise_t *g, const g1s_frame_t *in, g1s_frame_t *out)
     if ((rc = g->end_clip()) != 0) return rc;
     g->have_geom = false;
   }
-  if (!g->have_geom)
+  if (!g->have_geom) {
     g->set_frame_geometry(*in), g->d_stab = DevBuf<uint8_t>(), g->d_filt = DevBuf<uint8_t>(), g->d_mv[0] = DevBuf<int8_t>(), g->d_mv[1] = DevBuf<int8_t>();
+    g->d_cin = DevBuf<uint8_t>(), g->d_cout = DevBuf<uint8_t>(), g->d_d = DevBuf<uint8_t>();
+  }
+  if (g->K && (rc = g->need_levels()) != 0) return rc;
   if (g->curve && (rc = g->need_stab()) != 0) return rc;
   if (g->M && (rc = g->need_mv()) != 0) return rc;
   const PlaneGeom &gm = g->geom;
@@ -816,7 +1007,7 @@ int g1s_denoise_sync(g1s_denoise_t *g) {
 
 int g1s_denoise_set_timing(g1s_denoise_t *g, int enable, double *ms_kernel, uint64_t *frames) {
   if (!g) return G1S_ERR_INVALID;
-  g->timing = enable != 0;
+  for (g1s_denoise *l = g; l; l = l->inner) l->timing = enable != 0;  // (a timed inner level gives the three kernels' own time)
   if (ms_kernel) *ms_kernel = g->ms_kernel;
   if (frames) *frames = g->frames_timed;
   return G1S_OK;

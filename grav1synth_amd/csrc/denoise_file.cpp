@@ -21,6 +21,7 @@ extern "C" int32_t g1s_diff_device_(const g1s_diff_t *);
 extern "C" uint32_t g1s_diff_frames_in_flight_max_(const g1s_diff_t *);
 extern "C" uint32_t g1s_denoise_batch_(const g1s_denoise_t *);
 extern "C" uint32_t g1s_denoise_temporal_radius_(const g1s_denoise_t *);
+extern "C" void g1s_denoise_levels_refusal_(const g1s_denoise_opts_t *, uint32_t coarse_levels, double coarse_ratio, char *err, size_t cap);
 
 using namespace g1s_op;
 
@@ -41,6 +42,8 @@ struct FileSpec {
   uint32_t motion_range = 0, auto_flags = 0;
   uint64_t profile_frames = 0, min_count = 0;
   uint32_t chroma_prior = 0;
+  uint32_t coarse_levels = 0;
+  double coarse_ratio = 0.0;
 };
 
 // A grain prior as the file commands take it: the table at `path`, its segment `segment` alone or (negative) the mean of
@@ -181,8 +184,9 @@ struct Recipe {
       g1s_set_global_error_(why.c_str());
       return nullptr;
     }
-    return g1s_denoise_new_gain(bit_depth, device >= 0 ? &d : opts, s.temporal_radius, s.flags, has_prior ? fwd.data() : nullptr,
-                                has_prior ? inv.data() : nullptr, s.motion_range, prior.gain.empty() ? nullptr : prior.gain.data());
+    return g1s_denoise_new_levels(bit_depth, device >= 0 ? &d : opts, s.temporal_radius, s.flags, has_prior ? fwd.data() : nullptr,
+                                  has_prior ? inv.data() : nullptr, s.motion_range, prior.gain.empty() ? nullptr : prior.gain.data(), s.coarse_levels,
+                                  s.coarse_ratio);
   }
 };
 
@@ -218,6 +222,11 @@ int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *
   if (frames_out) *frames_out = 0;
   if (!source || !out_tbl) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   if (spec.flags & ~G1S_DENOISE_JOINT_CHROMA) return refuse(err, cap, G1S_ERR_INVALID, "unknown denoise flags");
+  {  // (rule 28's refusals need no device either; the generator is made before the denoiser, so they are looked at here)
+    char no[160] = "";
+    g1s_denoise_levels_refusal_(dopts, spec.coarse_levels, spec.coarse_ratio, no, sizeof no);
+    if (no[0]) return refuse(err, cap, G1S_ERR_INVALID, no);
+  }
   Recipe recipe{spec};
   const int32_t generator_device = opts ? opts->device : -1;
   std::string why = recipe.prepare(source, dopts, &generator_device);
@@ -427,6 +436,14 @@ int64_t g1s_denoise_y4m_file_chroma(const char *in, const char *out, const g1s_d
                                           chroma_prior}, err, cap);
 }
 
+int64_t g1s_denoise_y4m_file_levels(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                    uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, char *err,
+                                    size_t cap) {
+  return denoise_y4m_file(in, out, opts, {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count,
+                                          chroma_prior, coarse_levels, coarse_ratio}, err, cap);
+}
+
 int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                const g1s_denoise_opts_t *dopts, uint64_t *frames_out, char *err, size_t cap) {
   return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts, {}, frames_out, err, cap);
@@ -473,6 +490,17 @@ int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, c
                                       uint64_t min_count, uint32_t chroma_prior, uint64_t *frames_out, char *err, size_t cap) {
   return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts,
                                 {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count, chroma_prior},
+                                frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_levels(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                      uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, uint64_t *frames_out, char *err,
+                                      size_t cap) {
+  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts,
+                                {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count, chroma_prior,
+                                 coarse_levels, coarse_ratio},
                                 frames_out, err, cap);
 }
 

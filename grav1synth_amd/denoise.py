@@ -13,6 +13,7 @@ project's own definition of non-local means: the structure of ffmpeg's nlmeans a
 >>> Denoiser(10, temporal_radius=1, motion_range=32).denoise_clip(frames)   # a pan: each tile reads its neighbours where it finds them
 >>> Denoiser(10, joint_chroma=True, chroma_gain=chroma_gain(segments)).apply([y, u, v])   # chroma strength follows the grain at the luma under it
 >>> denoise_y4m_file("grainy.y4m", "clean.y4m", grain_prior="first_pass.tbl", joint_chroma=True, chroma_prior=True)
+>>> Denoiser(10, coarse_levels=2).apply([y, u, v])   # coarse grain: the 2 x 2 and 4 x 4 box means are filtered as well
 """
 from __future__ import annotations
 
@@ -104,7 +105,8 @@ class Denoiser(FrameOp):
 
     def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, search_radius: int = 0, patch_radius: int = 0,
                  strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
-                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None, motion_range: int = 0, chroma_gain: Optional[np.ndarray] = None):
+                 curve: Optional[Tuple[np.ndarray, np.ndarray]] = None, motion_range: int = 0, chroma_gain: Optional[np.ndarray] = None,
+                 coarse_levels: int = 0, coarse_ratio: float = 0.0):
         """temporal_radius D (0..3): the frames handed over between two sync() calls are a clip, and a frame's mean also
         runs over the D frames before and the D frames after it that the clip has.  joint_chroma: the two chroma planes
         share one weight, taken from Cb, Cr and the input luma at chroma resolution (rules 8 - 11 of include/g1s_diff.h);
@@ -114,7 +116,10 @@ class Denoiser(FrameOp):
         way towards every neighbour frame, found by a coarse search on the device, and reads the neighbour there (rules
         16 - 20); 0 is the filter without it.  chroma_gain: m[256] of chroma_gain() or estimate.noise_chroma_prior(), or any
         256 values in 1 .. 16384 (needs joint_chroma): the weight of a chroma pair is taken at its distance times the mean of
-        m at the guide under its two ends, over 256 (rules 21 - 24); luma never sees it."""
+        m at the guide under its two ends, over 256 (rules 21 - 24); luma never sees it.  coarse_levels K (0..2): the 2 x 2 box mean
+        of every frame goes through the same filter (K = 2: its box mean as well) and replaces the low frequencies of the
+        result, for grain coarser than a patch (rules 25 - 29); coarse_ratio: a level's strengths over those of the level above
+        it, 0.0625 .. 4, 0 = 1.  K = 0 is the filter without it."""
         self._L = _lib.lib()
         self.bit_depth = bit_depth
         self.temporal_radius = temporal_radius
@@ -130,9 +135,11 @@ class Denoiser(FrameOp):
             fwd, inv = (np.ascontiguousarray(a, np.uint16) for a in curve)
             if bit_depth in (8, 10) and (fwd.shape != (1 << bit_depth,) or inv.shape != (4096,)):
                 raise G1SError(-1, f"curve: fwd must have {1 << bit_depth} entries and inv 4096")
-        self._h = self._L.g1s_denoise_new_gain(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
-                                               None if fwd is None else fwd.ctypes.data, None if inv is None else inv.ctypes.data,
-                                               motion_range & 0xFFFFFFFF, None if gain is None else gain.ctypes.data)
+        self.coarse_levels = coarse_levels
+        self._h = self._L.g1s_denoise_new_levels(bit_depth, C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma),
+                                                 None if fwd is None else fwd.ctypes.data, None if inv is None else inv.ctypes.data,
+                                                 motion_range & 0xFFFFFFFF, None if gain is None else gain.ctypes.data,
+                                                 coarse_levels & 0xFFFFFFFF, float(coarse_ratio))
         if not self._h:
             raise G1SError(-1, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # (frame number, planes): what the queued kernels and the frames to come still read or write
@@ -191,6 +198,18 @@ class Denoiser(FrameOp):
         self._L.g1s_denoise_motion_time(self._h, C.byref(a))
         return a.value
 
+    def level_time(self) -> float:
+        """ms in kd_down, kd_lowres, kd_add and the coarse levels of the timed batches so far (a part of kernel_times()' first value)."""
+        a = C.c_double()
+        self._L.g1s_denoise_level_time(self._h, C.byref(a))
+        return a.value
+
+    def level_kernel_time(self) -> float:
+        """ms in kd_down, kd_lowres and kd_add alone, every level's, of the timed batches so far (a part of level_time())."""
+        a = C.c_double()
+        self._L.g1s_denoise_level_kernel_time(self._h, C.byref(a))
+        return a.value
+
     def kernel_times(self, enable: bool = True):
         """(ms in kd_nlm and kd_nlm_j, whichever form -- with a curve also the two kd_curve launches -- , frames) of the timed batches
         so far (HIP events); enables / disables the timing."""
@@ -203,14 +222,14 @@ def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames:
                      strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
                      grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0,
                      auto_prior: bool = False, auto_strength: bool = False, profile_frames: int = 0, levels_min_count: int = 0,
-                     chroma_prior: bool = False) -> int:
+                     chroma_prior: bool = False, coarse_levels: int = 0, coarse_ratio: float = 0.0) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
     function the luma strength follows (grain_curve() with prior_range and prior_segment).  motion_range: as Denoiser takes
     it.  auto_prior / auto_strength: the curve and the strengths from the clip's own noise levels (rules N5 - N7), measured
     in a pre-pass over its first profile_frames frames (0 = all) with levels_min_count as Nmin (0 = 4096).  chroma_prior: the
     job's prior also gives the joint chroma filter its gain (rules 21 - 24): from the table's chroma scaling functions, or from
-    the chroma levels the pre-pass measured; needs joint_chroma and one of grain_prior / auto_prior.  Returns the number of
-    frames."""
+    the chroma levels the pre-pass measured; needs joint_chroma and one of grain_prior / auto_prior.  coarse_levels, coarse_ratio: as
+    Denoiser takes them; an auto strength is level 0's.  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
@@ -218,8 +237,9 @@ def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames:
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
     prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
     auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-    n = L.g1s_denoise_y4m_file_chroma(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                      motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0, err, len(err))
+    n = L.g1s_denoise_y4m_file_levels(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
+                                      motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0,
+                                      coarse_levels & 0xFFFFFFFF, float(coarse_ratio), err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

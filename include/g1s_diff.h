@@ -675,6 +675,34 @@ int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, con
  *      pair.  Rules 2, 5 - 7, 9, 11, 11t and 19 - 20 are otherwise unchanged; (k = 0, d = 0) carries 4096.  With the flat gain
  *      the bytes are those of rules 8 - 11t: (D 256) >> (q + 8) = D >> q.  Luma never sees the gain, and a luma-only frame
  *      is filtered as without it.
+ * Coarse levels (g1s_denoise_new_levels): the filter compares patches of at most 9 x 9 samples and assumes white noise; film
+ * grain is correlated, so its coarse part stays in the "clean" clip.  With K coarse levels the 2 x 2 box mean of the frame is
+ * filtered as well -- grain of twice the size looks there like grain of the original size -- and that result takes the place of
+ * the low frequencies of the full-resolution result.  Integers throughout:
+ *  25. The coarse frame.  For a frame X with planes u_c of W_c x H_c samples, X' has the planes u'_c = rule 16's box of u_c, the
+ *      rounded 2 x 2 mean with the min(.., W-1) clamps, of ((W_c + 1) >> 1) x ((H_c + 1) >> 1) samples, and the same bit depth,
+ *      xdec and ydec.  X' is a valid frame of luma size W' = (W + 1) >> 1, H' = (H + 1) >> 1: its chroma width
+ *      (W' + xdec) >> xdec equals (cw + 1) >> 1 for cw = (W + xdec) >> xdec (xdec = 0: both are W'; xdec = 1: cw = W', and
+ *      (W' + 1) >> 1 on both sides), and likewise its height.
+ *  26. Levels.  F_0(X; h, hc, Mr) is the filter of rules 1 - 24 with every option the denoiser was made with.  For K >= 1:
+ *      F_K(X; h, hc, Mr) = Merge(F_0(X; h, hc, Mr), F_{K-1}(X'; rho h, rho hc, Mr')), Mr' = 2 ceil(Mr / 4) (64 -> 32 -> 16,
+ *      2 -> 2).  The strengths of level l are rho times those of level l - 1, the product formed in double precision level
+ *      by level.  A, S, D, the flags, the curve (fwd, inv) and the chroma gain m[256] are the same on every level: both are
+ *      indexed by intensity, which the box mean keeps.  The coarse frames of a clip are a clip with the same ends.  On a
+ *      coarse level rule 8's guide is made from the coarse frame's input luma, and with a curve the coarse level applies
+ *      the curve itself: Merge sees only finished B-bit outputs.
+ *  27. Merge, per plane: v the full-resolution output (W x H), c the coarse level's output (W' x H').  d = c - box(v), signed,
+ *      with the box of rule 16.  For the fine sample (x, y): xa = x >> 1, xb = clamp(xa + (x & 1 ? 1 : -1), 0, W' - 1), and
+ *      ya, yb likewise.  U = (9 d(xa, ya) + 3 d(xb, ya) + 3 d(xa, yb) + d(xb, yb) + 8) >> 4, an arithmetic shift (floor);
+ *      out = Clip3(0, 2^B - 1, v + U).  d = 0 gives out = v, and a constant plane stays constant.
+ *  28. K = coarse_levels in 0 .. 2; rho = coarse_ratio in 0.0625 .. 4, 0 = 1.0.  The default is 1, not the 1/2 that white
+ *      noise would ask for: the grain a coarse level is there for is as strong at the coarse scale as at the fine one.
+ *      Every level's strengths must pass rule 3's bounds; the refusal is rule 3's text with "level l " in front.
+ *  29. K = 0 is the filter of rules 1 - 24: the same launches, the same bytes.  A ratio given with K = 0 is refused.
+ *      g1s_denoise_motion_search is unaffected: it answers for level 0.
+ * More than two coarse levels, A or S per level, choosing K from a scales record of `measure`, and a merge fused into the filter
+ * kernel are not part of it.  A level keeps (3 batch_frames + 2 D) coarse frames on the device, two thirds of them at the clip's
+ * sample size and one third as int16: about (3 batch_frames + 2 D) / 4 frames of memory, and a quarter of that for the level under it.
  * No dithering.  Samples above the bit depth's maximum are the caller's error.
  * Frames queue up to batch_frames (0 = 32; at most 256) and go out as one kernel launch per plane class (luma; the two
  * chroma planes -- under the flag one workgroup filters both) on the denoiser's own stream.  A workgroup's LDS grows
@@ -722,6 +750,21 @@ g1s_denoise_t *g1s_denoise_new_motion(uint32_t bit_depth, const g1s_denoise_opts
  * g1s_denoise_motion_search is unaffected: the guide takes no part in the search. */
 g1s_denoise_t *g1s_denoise_new_gain(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                     const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain);
+/* The same with coarse levels (rules 25 - 29).  coarse_levels = 0 (and coarse_ratio = 0) is g1s_denoise_new_gain: the same
+ * launches, the same bytes.  Their refusals come after those of the parameters before them and before a device is looked for:
+ * "coarse_levels must be 0..2", "coarse_ratio must be 0.0625..4 (0 = 1)", "coarse_ratio needs coarse_levels", and for a level l
+ * whose scaled strength leaves rule 3's bounds "level l strength must be greater than 0 and at most 1000" (or "level l
+ * chroma_strength ...").  A level is a whole denoiser on the coarse frames, on the same stream; three small kernels (kd_down,
+ * kd_lowres, kd_add) stand around it, and the merge works in place on the planes the full-resolution launch wrote. */
+g1s_denoise_t *g1s_denoise_new_levels(uint32_t bit_depth, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                      const uint16_t *fwd, const uint16_t *inv, uint32_t motion_range, const uint16_t *chroma_gain,
+                                      uint32_t coarse_levels, double coarse_ratio);
+/* ms spent by the timed batches so far in kd_down, kd_lowres, kd_add and the coarse levels' own launches (a part of
+ * g1s_denoise_set_timing's ms_kernel); 0 for a denoiser without coarse levels. */
+int g1s_denoise_level_time(g1s_denoise_t *, double *ms_level);
+/* The part of g1s_denoise_level_time spent in kd_down, kd_lowres and kd_add themselves, over every level (the inner levels are
+ * timed with the outer one).  tools/bench_denoise.py --levels puts the bytes the three kernels move over it. */
+int g1s_denoise_level_kernel_time(g1s_denoise_t *, double *ms_kernels);
 /* Rules 22 + 21: the gain from both chroma planes of n >= 1 segments of a grain table, range R (0 = 4).  Host only.
  * G1S_ERR_INVALID (reason from g1s_last_global_error()) for n = 0, a range above 8 ("chroma gain range must be 1..8 (0 = the
  * default)"), and luma or chroma points whose values do not increase. */
@@ -814,6 +857,12 @@ int64_t g1s_denoise_y4m_file_auto(const char *in, const char *out, const g1s_den
 int64_t g1s_denoise_y4m_file_chroma(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
                                     const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
                                     uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, char *err, size_t cap);
+/* The same with coarse levels (rules 25 - 29, as g1s_denoise_new_levels takes them and refuses them); coarse_levels = 0 is
+ * g1s_denoise_y4m_file_chroma.  An auto strength is level 0's; the levels scale it. */
+int64_t g1s_denoise_y4m_file_levels(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                    const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                    uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio,
+                                    char *err, size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -851,6 +900,17 @@ int g1s_diff_y4m_file_denoised_chroma(const char *source, const char *out_tbl, c
                                       const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
                                       uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
                                       uint64_t min_count, uint32_t chroma_prior, uint64_t *frames, char *err, size_t cap);
+/* The same with coarse levels; coarse_levels = 0 is g1s_diff_y4m_file_denoised_chroma.  Their refusals are looked at with the
+ * flags', in front of the prior and the device (with the strengths of dopts, 0 = the default; an auto strength's levels are
+ * checked when the denoiser is made).  This rung makes the generator, on a device, before the denoiser, so here -- and only
+ * here -- they also come in front of the denoiser's older parameter refusals (search_radius, patch_radius, motion_range, the
+ * strengths), which g1s_denoise_new_levels and g1s_denoise_y4m_file_levels name first; a strength that rule 3 refuses, or opts
+ * of another size, is left to the constructor and the levels are looked at over the default strengths. */
+int g1s_diff_y4m_file_denoised_levels(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                      const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                      uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                      uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, uint64_t *frames, char *err,
+                                      size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

@@ -23,7 +23,14 @@ tools/bench_denoise.py [batches] --gain -- the cost of a chroma gain (rules 21 -
 (A 3, S 2, D 0), (A 7, S 3, D 0) and (A 3, S 2, D 1), without and with a gain ("chroma_gain" in the line) in one process, one
 denoiser after the other.  The gain is rule 21 at R = 8 on a steep scaling function, so that no entry is the flat gain's and no
 path is skipped.  The timed span holds the luma launch, which the gain does not touch, and the joint launch; "luma_only" cases
-(the same clip's luma planes alone) give the first, so "joint_launch_us_per_frame" = the span less that."""
+(the same clip's luma planes alone) give the first, so "joint_launch_us_per_frame" = the span less that.
+
+tools/bench_denoise.py [batches] --levels -- coarse levels (rules 25 - 29): both formats at the defaults with temporal radius 0
+and 1, K = 0, 1 and 2 in one process.  "level_us_per_frame" is g1s_denoise_level_time (kd_down, kd_lowres, kd_add and the coarse
+levels' own launches, a part of the span), "level_kernels_us_per_frame" the three kernels alone over all levels,
+"level_kernel_bytes_per_frame" what they move as the specification counts it (per level with frame bytes N and s samples: kd_down
+N + N / 4, kd_lowres N + N / 4 + s / 2, kd_add s / 2 + 2 N) and "level_kernels_GBps" the two together.  "copy_GBps" is a
+device-to-device copy of a quarter of a batch's such bytes (half read, half written), four times over, timed with HIP events in the same process."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,7 +41,8 @@ from grav1synth_amd.synth import SynthSpec, make_pair
 assert torch.cuda.is_available(), "bench_denoise.py needs a GPU"
 PRIOR = "--prior" in sys.argv[1:]
 GAIN = "--gain" in sys.argv[1:]
-args = [a for a in sys.argv[1:] if a not in ("--prior", "--gain")]
+LEVELS = "--levels" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--prior", "--gain", "--levels")]
 MOTION = None
 if "--motion-range" in args:
     i = args.index("--motion-range")
@@ -51,6 +59,9 @@ if PRIOR:
     CASES = [(3, 2, d, False, c) for d in (0, 1) for c in (False, True)]
 elif MOTION is not None:
     CASES = [(3, 2, 1, False, False, r) for r in MOTION]
+elif LEVELS:
+    # (A, S, D, joint, prior, motion range, what, K)
+    CASES = [(3, 2, d, False, False, 0, None, k) for d in (0, 1) for k in (0, 1, 2)]
 elif GAIN:
     import numpy as np
 
@@ -80,6 +91,9 @@ for name, spec in FORMATS[:1] if MOTION is not None else FORMATS:
         if what == "gain":
             kw["chroma_gain"] = STEEP_GAIN
         planes = slice(0, 1) if what == "luma" else slice(None)
+        K = rest[2] if len(rest) > 2 else 0
+        if K:  # (K = 0: the denoiser as the calls before the levels make it)
+            kw["coarse_levels"] = K
         dn = Denoiser(spec.bit_depth, batch_frames=BATCH, search_radius=A, patch_radius=S, temporal_radius=D, joint_chroma=joint, **kw)
 
         def run(nb):
@@ -95,11 +109,30 @@ for name, spec in FORMATS[:1] if MOTION is not None else FORMATS:
         run(batches)
         ms, fr = dn.kernel_times(False)
         ms_motion = dn.motion_time() if mr else 0.0
+        level = {}
+        if LEVELS:
+            ms_level, ms_lk = dn.level_time(), dn.level_kernel_time()
+            nbytes = sum(p.numel() * p.element_size() for p in ins[0])
+            moved = sum((4.5 * nbytes + samples) / 4 ** l for l in range(K))
+            level = {"coarse_levels": K, "level_us_per_frame": ms_level * 1e3 / fr, "level_share_of_span": ms_level / ms, "level_kernels_us_per_frame": ms_lk * 1e3 / fr,
+                     "level_kernel_bytes_per_frame": moved}
+            if K:
+                n = int(moved * BATCH) // 8  # (a copy of n bytes moves 2 n)
+                a, b = torch.empty(n, dtype=torch.uint8, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda")
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                b.copy_(a)
+                e0.record()
+                for _ in range(4):
+                    b.copy_(a)
+                e1.record()
+                torch.cuda.synchronize()
+                level.update({"level_kernels_GBps": moved * fr / (ms_lk * 1e6), "copy_GBps": 8 * n / (e0.elapsed_time(e1) * 1e6)})
+                del a, b
         dn.close()
         pairs, temporal_pairs = A + A * (2 * A + 1), 2 * D * (2 * A + 1) ** 2
         print(json.dumps({
             "format": name, "search_radius": A, "patch_radius": S, "temporal_radius": D, "joint_chroma": joint, **({"grain_prior": prior} if PRIOR else {}),
-            **({"chroma_gain": what == "gain", "luma_only": what == "luma"} if GAIN else {}), "batch_frames": BATCH, "timed_batches": fr / BATCH,
+            **({"chroma_gain": what == "gain", "luma_only": what == "luma"} if GAIN else {}), **level, "batch_frames": BATCH, "timed_batches": fr / BATCH,
             "samples_per_frame": samples, "unordered_pairs": pairs, "temporal_pairs": temporal_pairs,
             "kd_nlm_ms_per_batch": ms / (fr / BATCH), "kd_nlm_us_per_frame": ms * 1e3 / fr, "kernel_frames_per_s": fr / (ms * 1e-3),
             "sample_pairs_per_ns": samples * (pairs + temporal_pairs) * fr / (ms * 1e6),
