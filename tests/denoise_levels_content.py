@@ -87,3 +87,69 @@ def joint(gain: bool = False):
         kw["gain"] = steep_gain()
     # (4:2:2: at 4:2:0 rule 8's box is rule 16's, and the guide of the coarse luma is the box of the fine guide, sample for sample)
     return grainy(1, 65, 49, 10, "422", seed=6), 10, "422", kw
+
+
+# ---- the grid of the three level kernels: what tests/test_gpu_denoise_levels_grid.py runs on the device and what
+# tests/test_denoise_levels_grid_cpu.py shows, on the reference alone, to occupy the grid it claims --------------------------------
+TILE_COARSE = (256, 8)  # coarse samples a workgroup of kd_down / kd_lowres / kd_add covers (kTileW x kTileRows of levels_row.hip.h)
+TILE_FINE = (2 * TILE_COARSE[0], 2 * TILE_COARSE[1])
+
+
+def tiles(w: int, h: int, level: int = 0) -> Tuple[int, int]:
+    """(tile columns, tile rows) of the three kernels of level `level` on a plane of w x h samples at level 0."""
+    for _ in range(level):
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+    return -(-w // TILE_FINE[0]), -(-h // TILE_FINE[1])
+
+
+def _grid_case(name, w, h, bd, ss, seed, level0, level1, *, n=1, sigma=12.0, h8=12.0, Ks=(1, 2), batch=0, fewer=False, **form):
+    return dict(name=name, w=w, h=h, bd=bd, ss=ss, seed=seed, n=n, sigma=sigma, h8=h8, Ks=Ks, batch=batch, level0=level0, level1=level1, fewer=fewer, form=form)
+
+
+def grid_cases() -> List[dict]:
+    """The fixed cases.  level0 / level1: (tile columns, tile rows) of the luma and of a chroma plane that the case is there for;
+    fewer: workgroups counted on the luma plane find no chroma plane under them.  form: D, joint, gain, curve (flags; grid_kw()
+    makes the arguments).  sigma, h8 (the strength at 8 bits) and seed are chosen so that every tile of every plane has something
+    to do at K = 1 and at K = 2 (tests/test_denoise_levels_grid_cpu.py asserts it): at grainy()'s and the filter's defaults
+    the corner tiles of one and of six samples come out of a level unchanged for most seeds."""
+    return [
+        _grid_case("420 3 x 3", 1040, 36, 10, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], fewer=True),
+        _grid_case("422 thin column", 1026, 35, 8, "422", 70, [(3, 3), (2, 3)], [(2, 2), (1, 2)], fewer=True),
+        _grid_case("444 corner sample", 1025, 33, 10, "444", 70, [(3, 3), (3, 3)], [(2, 2), (2, 2)]),
+        _grid_case("mono 2 x 2", 1024, 32, 12, "mono", 70, [(2, 2)], [(1, 1)]),
+        _grid_case("mono one short", 1023, 31, 8, "mono", 70, [(2, 2)], [(1, 1)]),
+        _grid_case("420 clip", 1040, 36, 8, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], n=3, batch=2, fewer=True, D=1),
+        _grid_case("420 joint", 1026, 34, 10, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], fewer=True, joint=True),
+        _grid_case("420 joint gain", 1026, 34, 10, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], fewer=True, joint=True, gain=True),
+        _grid_case("mono curve", 1025, 33, 10, "mono", 70, [(3, 3)], [(2, 2)], curve=True),
+        _grid_case("420 views 8", 1040, 36, 8, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], fewer=True),
+        _grid_case("420 views 10", 1040, 36, 10, "420", 70, [(3, 3), (2, 2)], [(2, 2), (1, 1)], fewer=True),
+        _grid_case("420 wide", 2050, 20, 8, "420", 70, [(5, 2), (3, 1)], [(3, 1), (2, 1)], Ks=(2,), fewer=True),
+    ]
+
+
+def grid_case(name: str) -> dict:
+    return next(c for c in grid_cases() if c["name"] == name)
+
+
+def grid_frames(case: dict) -> List[List[np.ndarray]]:
+    return grainy(case["n"], case["w"], case["h"], case["bd"], case["ss"], seed=case["seed"], sigma=case["sigma"])
+
+
+def grid_kw(case: dict, K: int) -> dict:
+    """The denoiser's / the reference's arguments of a case at K levels: A = 1, S = 1."""
+    form = case["form"]
+    kw = dict(K=K, h=case["h8"], A=1, S=1)
+    if form.get("D"):
+        kw["D"] = form["D"]
+    if form.get("joint"):
+        kw["joint"] = True
+    if form.get("gain"):
+        from tests.test_gpu_denoise_gain import steep_gain
+
+        kw["gain"] = steep_gain()
+    if form.get("curve"):
+        from tests.test_gpu_denoise_curve import curve
+
+        kw["curve"] = curve("example", case["bd"])
+    return kw
