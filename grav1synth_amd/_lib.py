@@ -215,6 +215,14 @@ class G1SNlfRecord(C.Structure):
     ]
 
 
+class G1SNlfTRecord(C.Structure):
+    _fields_ = [
+        ("n", (C.c_uint64 * 32) * 3),
+        ("s", (C.c_int64 * 32) * 3),
+        ("q", (C.c_uint64 * 32) * 3),
+    ]
+
+
 class G1SSurface(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -326,6 +334,23 @@ SYMBOLS = [
     ("g1s_denoise_curve_sigma", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("g1s_format_noise_levels", C.c_long, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
     ("g1s_nlf_y4m_file", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SNlfOpts), C.c_uint64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_new_temporal", C.c_void_p, [C.c_uint32, C.POINTER(G1SNlfOpts)]),
+    ("g1s_nlf_cut", C.c_int, [C.c_void_p]),
+    ("g1s_nlf_finish_temporal", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_nlf_temporal_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_nlf_sum_temporal", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_nlf_sigma_temporal", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
+    ("g1s_nlf_chroma_sigma_temporal", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("g1s_nlf_strength_temporal", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),
+    ("g1s_format_noise_levels_temporal", C.c_long, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_y4m_file_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SNlfOpts), C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p,
+                                              C.c_size_t]),
+    ("g1s_denoise_y4m_file_auto_temporal", C.c_int64, [C.c_char_p, C.c_char_p, C.POINTER(G1SDenoiseOpts), C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32,
+                                                       C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double,
+                                                       C.c_uint32, C.c_char_p, C.c_size_t]),
+    ("g1s_diff_y4m_file_denoised_auto_temporal", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SOpts), C.POINTER(G1SDenoiseOpts), C.c_uint32,
+                                                           C.c_uint32, C.c_char_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                           C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("g1s_y4m_open", C.c_void_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
     ("g1s_y4m_get_info", C.c_int, [C.c_void_p, C.POINTER(G1SY4MInfo)]),
     ("g1s_y4m_next", C.c_int, [C.c_void_p, C.POINTER(G1SFrame)]),

@@ -51,6 +51,9 @@ PRIOR_12_BIT = ("--grain-prior filters luma in a 12-bit domain: a 12-bit input h
 AUTO_PRIOR_AND_TABLE = "--auto-prior measures the prior that --grain-prior would read from a table: they do not combine. Exiting."
 AUTO_STRENGTH_AND_STRENGTH = "--auto-strength measures what --strength and --chroma-strength would set: they do not combine. Exiting."
 AUTO_NEEDS_FLAG = "--profile-frames and --levels-min-count say how --auto-prior and --auto-strength measure: they need one of them. Exiting."
+AUTO_TEMPORAL_NEEDS_FLAG = "--auto-temporal says how --auto-prior and --auto-strength measure: it needs one of them. Exiting."
+AUTO_TEMPORAL_NEEDS_TWO = "--auto-temporal measures the difference of consecutive frames: --profile-frames 1 leaves none. Exiting."
+SAME_LEVELS_TEMPORAL = "--levels-temporal cannot be the same file as the output or --levels. Exiting."
 AUTO_BAD_NUMBER = "--profile-frames and --levels-min-count must not be negative. Exiting."
 AUTO_NEEDS_FILE = "--auto-prior and --auto-strength read the input twice: %s is not a regular file. Exiting."
 PRIOR_BAD_TABLE = "Invalid grain prior: %s. Exiting."
@@ -118,6 +121,10 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
                    help="with --auto-prior / --auto-strength: measure the first N frames only (default 0: all)")
     p.add_argument("--levels-min-count", type=int, default=0, metavar="N",
                    help="with --auto-prior / --auto-strength: smooth samples an intensity bin needs to take part (default 4096)")
+    p.add_argument("--auto-temporal", action="store_true",
+                   help="with --auto-prior / --auto-strength: measure the noise from the difference of consecutive frames where the "
+                        "picture stands still; holds on spatially correlated grain, which the single-frame measurement under-reads; "
+                        "motion reads as noise (an upper bound); the pre-pass needs two frames")
     p.add_argument("--chroma-prior", action="store_true",
                    help="with --joint-chroma and --grain-prior or --auto-prior: the chroma strength follows the grain at the luma under "
                         "each sample -- the table's chroma scaling functions, or the chroma noise the pre-pass measured per luma bin; "
@@ -130,7 +137,8 @@ def _add_denoise_parameters(p: argparse.ArgumentParser) -> None:
 
 
 def _denoise_parameters(args) -> dict:
-    return dict(search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
+    # (auto_temporal only where it is set: a job without the flag makes the call it made)
+    return dict(**(dict(auto_temporal=True) if getattr(args, "auto_temporal", False) else {}), search_radius=args.search_radius, patch_radius=args.patch_radius, strength=args.strength,
                 chroma_strength=args.chroma_strength, temporal_radius=args.temporal_radius, joint_chroma=args.joint_chroma,
                 grain_prior=args.grain_prior, prior_range=args.prior_range, prior_segment=args.prior_segment, motion_range=args.motion_range,
                 auto_prior=args.auto_prior, auto_strength=args.auto_strength, profile_frames=args.profile_frames,
@@ -147,6 +155,12 @@ def _auto_refused(input: str, parameters: dict) -> bool:
     frames, count = parameters.get("profile_frames", 0), parameters.get("levels_min_count", 0)
     if frames < 0 or count < 0:
         log.error(AUTO_BAD_NUMBER)
+        return True
+    if parameters.get("auto_temporal", False) and not prior and not strength:
+        log.error(AUTO_TEMPORAL_NEEDS_FLAG)
+        return True
+    if parameters.get("auto_temporal", False) and frames == 1:
+        log.error(AUTO_TEMPORAL_NEEDS_TWO)
         return True
     if not prior and not strength:
         if frames or count:
@@ -293,6 +307,10 @@ def build_parser() -> argparse.ArgumentParser:
     e.add_argument("--levels", metavar="PATH", default=None,
                    help="also write the clip's noise levels: sigma per intensity bin and plane and the strength they imply for "
                         "`denoise`, from the same read of the clip")
+    e.add_argument("--levels-temporal", metavar="PATH", default=None,
+                   help="also write the clip's temporal noise levels: sigma from the difference of consecutive frames where the "
+                        "picture stands still, its ratio to the single-frame sigma (above 1: correlated grain, or motion) and "
+                        "the strength it implies, from the same read of the clip")
     r = sub.add_parser("render", help="Synthesizes the film grain of a table onto a video (y4m input and output): what a decoder "
                                       "shows for the clip encoded with the table (AV1 specification, film grain synthesis process).")
     r.add_argument("input", help="The (denoised) file to put grain on.")
@@ -414,26 +432,33 @@ def diff_command(source: str, denoised: Optional[str], output: str, overwrite: b
 
 
 def estimate_command(source: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
-                     levels: Optional[str] = None) -> int:
+                     levels: Optional[str] = None, levels_temporal: Optional[str] = None) -> int:
     """Commands::Estimate (src/main.rs:534-608): the refusals of :541-560, one estimate_plane_noise per frame, "filmgrn1" and a
     "{:.3}" line per frame (-1 for None), "Done, wrote output file to ...".  --levels PATH is a second output, the clip's
-    noise levels.  Returns the frame count, -1 after a refusal."""
+    noise levels; --levels-temporal PATH a third, its temporal noise levels.  Returns the frame count, -1 after a refusal."""
     from .estimate import estimate_y4m_file
 
-    if _same_path(source, output) or (levels is not None and _same_path(source, levels)):
+    if _same_path(source, output) or any(p is not None and _same_path(source, p) for p in (levels, levels_temporal)):
         log.error(SAME_AS_OUTPUT)
         return -1
     if levels is not None and _same_path(output, levels):
         log.error(SAME_LEVELS)
         return -1
-    for path in (output, levels):
+    if levels_temporal is not None and (_same_path(output, levels_temporal) or (levels is not None and _same_path(levels, levels_temporal))):
+        log.error(SAME_LEVELS_TEMPORAL)
+        return -1
+    for path in (output, levels, levels_temporal):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
-    frames = estimate_y4m_file(source, output, device=device, levels=levels)
+    # (levels_temporal only where it is given: a job without the flag makes the call it made)
+    more = {} if levels_temporal is None else dict(levels_temporal=levels_temporal)
+    frames = estimate_y4m_file(source, output, device=device, levels=levels, **more)
     log.info("Done, wrote output file to %s", output)
     if levels is not None:
         log.info("Done, wrote noise levels to %s", levels)
+    if levels_temporal is not None:
+        log.info("Done, wrote temporal noise levels to %s", levels_temporal)
     return frames
 
 
@@ -627,7 +652,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             return 1
     elif args.command == "estimate":
         try:
-            estimate_command(args.source, args.output, args.overwrite, args.device, levels=args.levels)
+            estimate_command(args.source, args.output, args.overwrite, args.device, levels=args.levels,
+                             **({} if args.levels_temporal is None else dict(levels_temporal=args.levels_temporal)))
         except Exception as e:
             log.error("%s", e)
             return 1

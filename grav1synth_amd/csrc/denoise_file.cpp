@@ -44,6 +44,7 @@ struct FileSpec {
   uint32_t chroma_prior = 0;
   uint32_t coarse_levels = 0;
   double coarse_ratio = 0.0;
+  uint32_t auto_temporal = 0;
 };
 
 // A grain prior as the file commands take it: the table at `path`, its segment `segment` alone or (negative) the mean of
@@ -102,11 +103,24 @@ struct Prior {
     gain.assign(g1s_cv::kGainEntries, 0);
     return g1s_cv::gain_from_s(sc, range_, gain.data());
   }
+  // the same from the clip's temporal record (rule T7)
+  std::string measure_t(const g1s_nlf_trecord_t &total, uint32_t bit_depth, uint32_t range_, uint64_t min_count) {
+    std::string why = g1s_cv::check_depth_range(bit_depth, range_);
+    if (!why.empty()) return why;
+    std::vector<uint8_t> sg((size_t)1 << bit_depth);
+    if (!(why = g1s_nl::sigma_t(total, 0, bit_depth, min_count, sg.data())).empty()) return why;
+    pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
+    if (!(why = g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data())).empty() || !chroma) return why;
+    uint8_t sc[g1s_cv::kGainEntries];
+    if (!(why = g1s_nl::sigma_t(total, 1, 8, min_count, sc)).empty()) return why;
+    gain.assign(g1s_cv::kGainEntries, 0);
+    return g1s_cv::gain_from_s(sc, range_, gain.data());
+  }
 };
 
 // The pre-pass of the auto flags: their refusals, the noise levels of the first profile_frames frames of `source` on
 // `device`, then the prior's curve into *prior (G1S_AUTO_PRIOR) and the two strengths into *d (G1S_AUTO_STRENGTH).
-// "" when fine.
+// Under auto_temporal the meter is a temporal one and the values are rule T7's.  "" when fine.
 std::string auto_prepass(const char *source, int32_t device, const FileSpec &s, Prior *prior, g1s_denoise_opts_t *d) {
   if (s.auto_flags & ~(G1S_AUTO_PRIOR | G1S_AUTO_STRENGTH)) return "unknown auto flags";
   if ((s.auto_flags & G1S_AUTO_PRIOR) && s.prior_tbl) return "an auto prior does not combine with a grain prior table";
@@ -117,23 +131,29 @@ std::string auto_prepass(const char *source, int32_t device, const FileSpec &s, 
   g1s_nlf_opts_t no{};
   no.struct_size = sizeof no, no.device = device;
   g1s_nlf_record_t total;
+  g1s_nlf_trecord_t ttotal;
   char err[512] = "";
-  const int64_t n = g1s_nlf_y4m_file(source, nullptr, &no, s.profile_frames, &total, err, sizeof err);
+  const int64_t n = s.auto_temporal ? g1s_nlf_y4m_file_temporal(source, nullptr, nullptr, &no, s.profile_frames, nullptr, &ttotal, err, sizeof err)
+                                    : g1s_nlf_y4m_file(source, nullptr, &no, s.profile_frames, &total, err, sizeof err);
   if (n < 0) return err;
+  if (s.auto_temporal && n < 2) return "temporal noise levels need two frames";
   g1s_y4m_t *y = g1s_y4m_open(source, err, sizeof err);
   if (!y) return err;
   g1s_y4m_info_t info;
   g1s_y4m_get_info(y, &info);
   g1s_y4m_close(y);
   if (s.auto_flags & G1S_AUTO_PRIOR) {
-    const std::string why = prior->measure(total, info.bit_depth, s.prior_range, s.min_count);
+    const std::string why = s.auto_temporal ? prior->measure_t(ttotal, info.bit_depth, s.prior_range, s.min_count)
+                                            : prior->measure(total, info.bit_depth, s.prior_range, s.min_count);
     if (!why.empty()) return why;
   }
   if (s.auto_flags & G1S_AUTO_STRENGTH) {
-    const std::string why = g1s_nl::strength(total, info.bit_depth, s.min_count, 0, &d->strength);
+    const std::string why = s.auto_temporal ? g1s_nl::strength_t(ttotal, info.bit_depth, s.min_count, 0, &d->strength)
+                                            : g1s_nl::strength(total, info.bit_depth, s.min_count, 0, &d->strength);
     if (!why.empty()) return why;
-    double hc = 0;
-    if (g1s_nl::strength(total, info.bit_depth, s.min_count, 1, &hc).empty()) d->chroma_strength = hc;  // (else: the luma strength)
+    double hc = 0;  // (where the chroma strength is refused: the luma strength)
+    if ((s.auto_temporal ? g1s_nl::strength_t(ttotal, info.bit_depth, s.min_count, 1, &hc) : g1s_nl::strength(total, info.bit_depth, s.min_count, 1, &hc)).empty())
+      d->chroma_strength = hc;
   }
   return "";
 }
@@ -158,6 +178,8 @@ struct Recipe {
   // refusals, struct_size, the pre-pass with its refusals, the table.
   std::string prepare(const char *source, const g1s_denoise_opts_t *caller, const int32_t *prepass_device) {
     opts = caller, has_prior = s.prior_tbl || s.chroma_prior || (s.auto_flags & G1S_AUTO_PRIOR);
+    if (s.auto_temporal > 1) return "auto_temporal is 0 or 1";
+    if (s.auto_temporal && !s.auto_flags) return "temporal noise levels need an auto flag (an auto prior or an auto strength)";
     if (s.chroma_prior || s.auto_flags) {
       std::string why = s.chroma_prior ? chroma_prior_refusal(s) : "";
       if (!why.empty()) return why;
@@ -444,6 +466,14 @@ int64_t g1s_denoise_y4m_file_levels(const char *in, const char *out, const g1s_d
                                           chroma_prior, coarse_levels, coarse_ratio}, err, cap);
 }
 
+int64_t g1s_denoise_y4m_file_auto_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                           const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                           uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio,
+                                           uint32_t auto_temporal, char *err, size_t cap) {
+  return denoise_y4m_file(in, out, opts, {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count,
+                                          chroma_prior, coarse_levels, coarse_ratio, auto_temporal}, err, cap);
+}
+
 int g1s_diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
                                const g1s_denoise_opts_t *dopts, uint64_t *frames_out, char *err, size_t cap) {
   return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts, {}, frames_out, err, cap);
@@ -501,6 +531,17 @@ int g1s_diff_y4m_file_denoised_levels(const char *source, const char *out_tbl, c
   return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts,
                                 {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count, chroma_prior,
                                  coarse_levels, coarse_ratio},
+                                frames_out, err, cap);
+}
+
+int g1s_diff_y4m_file_denoised_auto_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                             const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                             uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                             uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, uint32_t auto_temporal,
+                                             uint64_t *frames_out, char *err, size_t cap) {
+  return diff_y4m_file_denoised(source, out_tbl, keep_denoised, opts, dopts,
+                                {temporal_radius, flags, prior_tbl, prior_range, prior_segment, motion_range, auto_flags, profile_frames, min_count, chroma_prior,
+                                 coarse_levels, coarse_ratio, auto_temporal},
                                 frames_out, err, cap);
 }
 

@@ -553,4 +553,38 @@ long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uin
   return (long)s.size();
 }
 
+// temporal noise levels, rules T5 - T8 (nlf.h): the same for a temporal record
+int g1s_nlf_sum_temporal(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total) {
+  if (!total || (n && !recs)) return G1S_ERR_INVALID;
+  return g1s_nl::sum_t(recs, n, total) ? G1S_OK : G1S_ERR_INVALID;
+}
+
+int g1s_nlf_sigma_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
+  std::string why = !total || !s ? std::string("g1s_nlf_sigma_temporal needs a record and the output table") : g1s_cv::check_depth_range(bit_depth, 0);
+  if (why.empty()) why = g1s_nl::sigma_t(*total, 0, bit_depth, min_count, s);
+  return gain_result(why);
+}
+
+int g1s_nlf_chroma_sigma_temporal(const g1s_nlf_trecord_t *total, uint64_t min_count, uint8_t s[256]) {
+  return gain_result(!total || !s ? std::string("g1s_nlf_chroma_sigma_temporal needs a record and the output table") : g1s_nl::sigma_t(*total, 1, 8, min_count, s));
+}
+
+int g1s_nlf_strength_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
+  std::string why;
+  if (!total || !h) why = "g1s_nlf_strength_temporal needs a record and the output value";
+  else if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) why = "noise levels are defined for bit depths 8, 10 and 12";
+  else if (plane_class > 1) why = "plane_class is 0 (luma) or 1 (chroma)";
+  else why = g1s_nl::strength_t(*total, bit_depth, min_count, plane_class, h);
+  return gain_result(why);
+}
+
+long g1s_format_noise_levels_temporal(const g1s_nlf_trecord_t *total, const g1s_nlf_record_t *ordinary, uint64_t pairs, uint32_t bit_depth,
+                                      uint32_t nplanes, uint64_t min_count, char *buf, size_t cap) {
+  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
+  const std::string s = g1s_nl::report_t(*total, ordinary, pairs, bit_depth, nplanes, min_count);
+  if (s.size() > cap) return G1S_ERR_CAPACITY;
+  std::memcpy(buf, s.data(), s.size());
+  return (long)s.size();
+}
+
 }  // extern "C"

@@ -222,14 +222,16 @@ def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames:
                      strength: float = 0.0, chroma_strength: float = 0.0, temporal_radius: int = 0, joint_chroma: bool = False,
                      grain_prior: Optional[str] = None, prior_range: int = 0, prior_segment: Optional[int] = None, motion_range: int = 0,
                      auto_prior: bool = False, auto_strength: bool = False, profile_frames: int = 0, levels_min_count: int = 0,
-                     chroma_prior: bool = False, coarse_levels: int = 0, coarse_ratio: float = 0.0) -> int:
+                     chroma_prior: bool = False, coarse_levels: int = 0, coarse_ratio: float = 0.0, auto_temporal: bool = False) -> int:
     """`denoise INPUT -o OUTPUT` for a .y4m input; the file is one clip.  grain_prior: a grain table whose luma scaling
     function the luma strength follows (grain_curve() with prior_range and prior_segment).  motion_range: as Denoiser takes
     it.  auto_prior / auto_strength: the curve and the strengths from the clip's own noise levels (rules N5 - N7), measured
     in a pre-pass over its first profile_frames frames (0 = all) with levels_min_count as Nmin (0 = 4096).  chroma_prior: the
     job's prior also gives the joint chroma filter its gain (rules 21 - 24): from the table's chroma scaling functions, or from
     the chroma levels the pre-pass measured; needs joint_chroma and one of grain_prior / auto_prior.  coarse_levels, coarse_ratio: as
-    Denoiser takes them; an auto strength is level 0's.  Returns the number of frames."""
+    Denoiser takes them; an auto strength is level 0's.  auto_temporal: the pre-pass measures temporal noise levels (rules T1 -
+    T7: the difference of consecutive frames, which holds on correlated grain) and the auto values are T7's; needs auto_prior or
+    auto_strength and a pre-pass of two frames.  Returns the number of frames."""
     L = _lib.lib()
     opts = denoise_opts(device, batch_frames, search_radius, patch_radius, strength, chroma_strength)
     err = C.create_string_buffer(512)
@@ -237,9 +239,12 @@ def denoise_y4m_file(input: str, output: str, *, device: int = -1, batch_frames:
         raise G1SError(-1, "prior_range and prior_segment need grain_prior")
     prior = (str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
     auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-    n = L.g1s_denoise_y4m_file_levels(input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior,
-                                      motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0,
-                                      coarse_levels & 0xFFFFFFFF, float(coarse_ratio), err, len(err))
+    args = (input.encode(), output.encode(), C.byref(opts), temporal_radius & 0xFFFFFFFF, _flags(joint_chroma), *prior, motion_range & 0xFFFFFFFF, auto,
+            profile_frames, levels_min_count, 1 if chroma_prior else 0, coarse_levels & 0xFFFFFFFF, float(coarse_ratio))
+    if auto_temporal:
+        n = L.g1s_denoise_y4m_file_auto_temporal(*args, 1, err, len(err))
+    else:
+        n = L.g1s_denoise_y4m_file_levels(*args, err, len(err))
     if n < 0:
         raise G1SError(int(n), err.value.decode())
     log.info("Denoised %d frames", n)

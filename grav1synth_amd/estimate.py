@@ -14,6 +14,15 @@ clip's record says about the clip -- the curve of a grain prior and the strength
 >>> fwd, inv = noise_prior(total, 10)           # rules N5 - N6 and the curve of rules 12 - 13
 >>> h_luma, h_chroma = auto_strength(total, 10) # rule N7
 >>> Denoiser(10, curve=(fwd, inv), strength=h_luma, chroma_strength=h_chroma or 0.0)
+
+Temporal noise levels (rules T1 - T8): the same from the difference of consecutive frames where the picture stands still,
+which holds on spatially correlated grain; motion reads as noise.
+
+>>> meter = NoiseLevelMeter(10, temporal=True)
+>>> for f in frames: meter.frame(f)             # meter.cut() where a scene ends
+>>> ttotal = noise_levels_sum_temporal(meter.finish_temporal())   # one record a frame with a predecessor: n, s, q
+>>> fwd, inv = noise_prior(ttotal, 10, temporal=True)
+>>> h_luma, h_chroma = auto_strength(ttotal, 10, temporal=True)
 """
 from __future__ import annotations
 
@@ -25,12 +34,15 @@ import numpy as np
 
 from . import _lib
 from ._frame_op import FrameOp
-from ._lib import G1SError, G1SNlfOpts, G1SNlfRecord
+from ._lib import G1SError, G1SNlfOpts, G1SNlfRecord, G1SNlfTRecord
 from .diff import Frame
 
 # g1s_nlf_record_t
 NLF_RECORD = np.dtype([("n", "<u8", (3, 32)), ("a", "<u8", (3, 32)), ("q", "<u8", (3, 32))])
 assert NLF_RECORD.itemsize == C.sizeof(G1SNlfRecord)
+# g1s_nlf_trecord_t
+NLF_TRECORD = np.dtype([("n", "<u8", (3, 32)), ("s", "<i8", (3, 32)), ("q", "<u8", (3, 32))])
+assert NLF_TRECORD.itemsize == C.sizeof(G1SNlfTRecord)
 
 log = logging.getLogger("grav1synth")
 
@@ -101,16 +113,32 @@ def format_estimates(estimates) -> bytes:
     return buf.raw[:w]
 
 
-def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Optional[str] = None) -> int:
-    """`grav1synth estimate SOURCE -o OUTPUT [--levels PATH]` for a .y4m input: with `levels` the noise-level report of
-    the clip is written there, from the same read of the clip.  Returns the number of frames."""
+def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Optional[str] = None, levels_temporal: Optional[str] = None) -> int:
+    """`grav1synth estimate SOURCE -o OUTPUT [--levels PATH] [--levels-temporal PATH]` for a .y4m input: with `levels` the
+    noise-level report of the clip is written there, with `levels_temporal` its temporal report (the file one run), from the
+    same read of the clip.  Returns the number of frames."""
     from .ingest import Y4MReader
 
     rd = Y4MReader(source)
     d = rd.details
     est = NoiseEstimator(d.bit_depth, device=device)
-    meter = NoiseLevelMeter(d.bit_depth, device=device) if levels is not None else None
-    total = np.zeros((), NLF_RECORD)
+    temporal = levels_temporal is not None
+    meter = NoiseLevelMeter(d.bit_depth, device=device, temporal=temporal) if levels is not None or temporal else None
+    total, ttotal = np.zeros((), NLF_RECORD), np.zeros((), NLF_TRECORD)
+    first = None  # the first frame's record: the one frame without a predecessor
+    pairs = 0
+
+    def take():
+        nonlocal total, ttotal, first, pairs
+        recs = meter.finish()
+        if first is None and len(recs):
+            first = recs[0].copy()
+        total = noise_levels_sum(np.concatenate([total.reshape(1), recs]))
+        if temporal:
+            trecs = meter.finish_temporal()
+            pairs += len(trecs)
+            ttotal = noise_levels_sum_temporal(np.concatenate([ttotal.reshape(1), trecs]))
+
     n = 0
     while True:
         planes = rd.get_frame()
@@ -120,14 +148,22 @@ def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Opt
         if meter is not None:
             meter.frame(planes, d.xdec, d.ydec)
             if (n + 1) % 32 == 0:
-                total = noise_levels_sum(np.concatenate([total.reshape(1), meter.finish()]))
+                take()
         n += 1
     with open(output, "wb") as f:
         f.write(format_estimates(est.finish()))
     if meter is not None:
-        total = noise_levels_sum(np.concatenate([total.reshape(1), meter.finish()]))
-        with open(levels, "wb") as f:
-            f.write(format_noise_levels(total, n, d.bit_depth, d.nplanes))
+        take()
+        if levels is not None:
+            with open(levels, "wb") as f:
+                f.write(format_noise_levels(total, n, d.bit_depth, d.nplanes))
+        if temporal:
+            later = total.copy()
+            if first is not None:
+                for name in ("n", "a", "q"):
+                    later[name] -= first[name]
+            with open(levels_temporal, "wb") as f:
+                f.write(format_noise_levels_temporal(ttotal, pairs, d.bit_depth, d.nplanes, ordinary=later))
         meter.close()
     est.close()
     rd.close()
@@ -135,14 +171,17 @@ def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Opt
 
 
 class NoiseLevelMeter(FrameOp):
-    """g1s_nlf_*: the noise level function of frames on the device (rules N1 - N4); no CPU fallback."""
+    """g1s_nlf_*: the noise level function of frames on the device (rules N1 - N4); no CPU fallback.  temporal = True: a
+    temporal meter (rules T1 - T5): the same records from finish(), and from finish_temporal() one record per frame with a
+    predecessor in its run; cut() ends a run."""
     _name = "nlf"
 
-    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0):
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False):
         self._L = _lib.lib()
         self.bit_depth = bit_depth
+        self.temporal = temporal
         opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
-        self._h = self._L.g1s_nlf_new(bit_depth, C.byref(opts))
+        self._h = (self._L.g1s_nlf_new_temporal if temporal else self._L.g1s_nlf_new)(bit_depth, C.byref(opts))
         if not self._h:
             raise G1SError(-5, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # planes the queued kernels still read
@@ -181,6 +220,34 @@ class NoiseLevelMeter(FrameOp):
         self._keep.clear()
         return out[:n.value]
 
+    def cut(self) -> None:
+        """Ends the run of a temporal meter: the next frame has no predecessor.  Waits for nothing."""
+        self._check(self._L.g1s_nlf_cut(self._h))
+
+    def finish_temporal(self, cap: Optional[int] = None) -> np.ndarray:
+        """finish() for the temporal records: one per frame with a predecessor since the last finish_temporal(), in order.  A
+        meter made without temporal = True refuses."""
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._L.g1s_nlf_finish_temporal(self._h, None, 0, C.byref(n))
+            if rc not in (0, _lib.G1S_ERR_CAPACITY):
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(max(cap, 1), NLF_TRECORD)
+        rc = self._L.g1s_nlf_finish_temporal(self._h, out.ctypes.data, cap, C.byref(n))
+        if rc == _lib.G1S_ERR_CAPACITY:
+            raise G1SError(rc, f"{n.value} records do not fit {cap}")
+        self._check(rc)
+        self._keep.clear()
+        return out[:n.value]
+
+    def kernel_times_temporal(self) -> Tuple[float, float, int]:
+        """(ms in the temporal luma launches, ms in the temporal chroma launches, pairs) of the batches kernel_times() had
+        timed (HIP events)."""
+        a, b, n = C.c_double(), C.c_double(), C.c_uint64()
+        self._L.g1s_nlf_temporal_times(self._h, C.byref(a), C.byref(b), C.byref(n))
+        return a.value, b.value, n.value
+
     def kernel_times(self, enable: bool = True) -> Tuple[float, float, int]:
         """(ms in the luma launches, ms in the chroma launches, frames) of the timed batches so far (HIP events)."""
         a, b, n = C.c_double(), C.c_double(), C.c_uint64()
@@ -198,22 +265,33 @@ def noise_levels_sum(records: np.ndarray) -> np.ndarray:
     return total
 
 
-def noise_sigma(record: np.ndarray, bit_depth: int, min_count: int = 0) -> np.ndarray:
-    """Rules N5 - N6: the scaling function s[1 << bit_depth] of a clip's record (g1s_nlf_sigma; host only)."""
+def noise_levels_sum_temporal(records: np.ndarray) -> np.ndarray:
+    """Rule T5: a clip's temporal record from its pairs' (g1s_nlf_sum_temporal; host only).  An overflow raises."""
+    records = np.ascontiguousarray(records, NLF_TRECORD).reshape(-1)
+    total = np.zeros((), NLF_TRECORD)
+    rc = _lib.lib().g1s_nlf_sum_temporal(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+    if rc:
+        raise G1SError(rc, "the clip's sums leave 64 bits")
+    return total
+
+
+def noise_sigma(record: np.ndarray, bit_depth: int, min_count: int = 0, *, temporal: bool = False) -> np.ndarray:
+    """Rules N5 - N6: the scaling function s[1 << bit_depth] of a clip's record (g1s_nlf_sigma; host only).  temporal: of a
+    clip's temporal record (rules T6 - T7), here and in the four below."""
     L = _lib.lib()
-    record = np.ascontiguousarray(record, NLF_RECORD)
+    record = np.ascontiguousarray(record, NLF_TRECORD if temporal else NLF_RECORD)
     s = np.zeros(1 << min(max(bit_depth, 0), 16), np.uint8)
-    rc = L.g1s_nlf_sigma(record.ctypes.data, bit_depth, min_count, s.ctypes.data)
+    rc = (L.g1s_nlf_sigma_temporal if temporal else L.g1s_nlf_sigma)(record.ctypes.data, bit_depth, min_count, s.ctypes.data)
     if rc:
         raise G1SError(rc, L.g1s_last_global_error().decode())
     return s
 
 
-def noise_prior(record: np.ndarray, bit_depth: int, range: int = 0, min_count: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+def noise_prior(record: np.ndarray, bit_depth: int, range: int = 0, min_count: int = 0, *, temporal: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """(fwd, inv): the variance-stabilising curve of a clip's record, rules N5 - N6 then rules 12 - 13 of `denoise`, as
     Denoiser(curve=...) takes it (host only)."""
     L = _lib.lib()
-    s = noise_sigma(record, bit_depth, min_count)
+    s = noise_sigma(record, bit_depth, min_count, temporal=temporal)
     fwd, inv = np.zeros(1 << bit_depth, np.uint16), np.zeros(4096, np.uint16)
     rc = L.g1s_denoise_curve_sigma(s.ctypes.data, bit_depth, range, fwd.ctypes.data, inv.ctypes.data)
     if rc:
@@ -221,23 +299,23 @@ def noise_prior(record: np.ndarray, bit_depth: int, range: int = 0, min_count: i
     return fwd, inv
 
 
-def noise_chroma_sigma(record: np.ndarray, min_count: int = 0) -> np.ndarray:
+def noise_chroma_sigma(record: np.ndarray, min_count: int = 0, *, temporal: bool = False) -> np.ndarray:
     """Rule N9: the chroma scaling function s[256] over the luma under it, from the two chroma planes of a clip's record
     pooled (g1s_nlf_chroma_sigma; host only).  The same for every bit depth."""
     L = _lib.lib()
-    record = np.ascontiguousarray(record, NLF_RECORD)
+    record = np.ascontiguousarray(record, NLF_TRECORD if temporal else NLF_RECORD)
     s = np.zeros(256, np.uint8)
-    rc = L.g1s_nlf_chroma_sigma(record.ctypes.data, min_count, s.ctypes.data)
+    rc = (L.g1s_nlf_chroma_sigma_temporal if temporal else L.g1s_nlf_chroma_sigma)(record.ctypes.data, min_count, s.ctypes.data)
     if rc:
         raise G1SError(rc, L.g1s_last_global_error().decode())
     return s
 
 
-def noise_chroma_prior(record: np.ndarray, range: int = 0, min_count: int = 0) -> np.ndarray:
+def noise_chroma_prior(record: np.ndarray, range: int = 0, min_count: int = 0, *, temporal: bool = False) -> np.ndarray:
     """m[256]: the chroma gain of a clip's record, rule N9 then rule 21 of `denoise`, as Denoiser(chroma_gain=...) takes it
     (host only)."""
     L = _lib.lib()
-    s = noise_chroma_sigma(record, min_count)
+    s = noise_chroma_sigma(record, min_count, temporal=temporal)
     gain = np.zeros(256, np.uint16)
     rc = L.g1s_denoise_chroma_gain_sigma(s.ctypes.data, range & 0xFFFFFFFF, gain.ctypes.data)
     if rc:
@@ -245,16 +323,17 @@ def noise_chroma_prior(record: np.ndarray, range: int = 0, min_count: int = 0) -
     return gain
 
 
-def auto_strength(record: np.ndarray, bit_depth: int, min_count: int = 0) -> Tuple[float, Optional[float]]:
+def auto_strength(record: np.ndarray, bit_depth: int, min_count: int = 0, *, temporal: bool = False) -> Tuple[float, Optional[float]]:
     """Rule N7: (h_luma, h_chroma) in 8-bit code values; h_chroma is None where the rule refuses (a luma-only clip); a
     refusal for luma raises (host only)."""
     L = _lib.lib()
-    record = np.ascontiguousarray(record, NLF_RECORD)
+    record = np.ascontiguousarray(record, NLF_TRECORD if temporal else NLF_RECORD)
+    strength = L.g1s_nlf_strength_temporal if temporal else L.g1s_nlf_strength
     h = C.c_double()
-    if L.g1s_nlf_strength(record.ctypes.data, bit_depth, min_count, 0, C.byref(h)):
+    if strength(record.ctypes.data, bit_depth, min_count, 0, C.byref(h)):
         raise G1SError(-1, L.g1s_last_global_error().decode())
     h_luma = h.value
-    h_chroma = None if L.g1s_nlf_strength(record.ctypes.data, bit_depth, min_count, 1, C.byref(h)) else h.value
+    h_chroma = None if strength(record.ctypes.data, bit_depth, min_count, 1, C.byref(h)) else h.value
     return h_luma, h_chroma
 
 
@@ -269,13 +348,38 @@ def format_noise_levels(total: np.ndarray, frames: int, bit_depth: int, nplanes:
     return buf.raw[:w]
 
 
+def format_noise_levels_temporal(total: np.ndarray, pairs: int, bit_depth: int, nplanes: int = 3, min_count: int = 0, *,
+                                 ordinary: Optional[np.ndarray] = None, cap: int = 1 << 16) -> bytes:
+    """The report of a clip's temporal record (g1s_format_noise_levels_temporal; host only).  ordinary: the ordinary record
+    of the frames with a predecessor, for the ratio lines ("-" without it).  cap: a test aid."""
+    total = np.ascontiguousarray(total, NLF_TRECORD)
+    if ordinary is not None:
+        ordinary = np.ascontiguousarray(ordinary, NLF_RECORD)
+    buf = C.create_string_buffer(max(cap, 1))
+    w = _lib.lib().g1s_format_noise_levels_temporal(total.ctypes.data, None if ordinary is None else ordinary.ctypes.data, pairs, bit_depth, nplanes,
+                                                    min_count, buf, cap)
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_noise_levels_temporal failed")
+    return buf.raw[:w]
+
+
 def noise_levels_y4m_file(source: str, output: Optional[str] = None, *, device: int = -1, batch_frames: int = 0,
-                          max_frames: int = 0) -> Tuple[int, np.ndarray]:
+                          max_frames: int = 0, temporal_report=None):
     """The noise levels of the first max_frames frames (0 = all) of a .y4m file (g1s_nlf_y4m_file): the report into
-    `output` when it is given.  Returns (frames, the clip's record)."""
+    `output` when it is given.  Returns (frames, the clip's record).  temporal_report: a path, or True for no file: the
+    meter is a temporal one (g1s_nlf_y4m_file_temporal), the temporal report goes there, and the clip's temporal record is
+    returned as a third value."""
     opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
     err = C.create_string_buffer(512)
     total = np.zeros((), NLF_RECORD)
+    if temporal_report is not None:
+        ttotal = np.zeros((), NLF_TRECORD)
+        n = _lib.lib().g1s_nlf_y4m_file_temporal(str(source).encode(), None if output is None else str(output).encode(),
+                                                 None if temporal_report is True else str(temporal_report).encode(), C.byref(opts), max_frames,
+                                                 total.ctypes.data, ttotal.ctypes.data, err, len(err))
+        if n < 0:
+            raise G1SError(int(n), err.value.decode())
+        return int(n), total, ttotal
     n = _lib.lib().g1s_nlf_y4m_file(str(source).encode(), None if output is None else str(output).encode(), C.byref(opts), max_frames,
                                     total.ctypes.data, err, len(err))
     if n < 0:

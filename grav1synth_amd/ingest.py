@@ -116,11 +116,11 @@ def diff_y4m_file_denoised(source: str, output: str, *, keep_denoised: Optional[
                            temporal_radius: int = 0, joint_chroma: bool = False, grain_prior: Optional[str] = None, prior_range: int = 0,
                            prior_segment: Optional[int] = None, motion_range: int = 0, auto_prior: bool = False, auto_strength: bool = False,
                            profile_frames: int = 0, levels_min_count: int = 0, chroma_prior: bool = False, coarse_levels: int = 0,
-                           coarse_ratio: float = 0.0) -> int:
+                           coarse_ratio: float = 0.0, auto_temporal: bool = False) -> int:
     """`diff SOURCE --denoise -o OUTPUT [--keep-denoised PATH]` for a .y4m input: the denoised frame is made on the device
     (grav1synth_amd.denoise; the file is one clip for its temporal radius; joint_chroma as there) and handed to the generator there.
     grain_prior, prior_range, prior_segment, motion_range, auto_prior, auto_strength, profile_frames, levels_min_count, chroma_prior, coarse_levels,
-    coarse_ratio: as grav1synth_amd.denoise.denoise_y4m_file takes them.  Returns the number of frames."""
+    coarse_ratio, auto_temporal: as grav1synth_amd.denoise.denoise_y4m_file takes them.  Returns the number of frames."""
     from .denoise import denoise_opts
 
     L = _lib.lib()
@@ -134,8 +134,11 @@ def diff_y4m_file_denoised(source: str, output: str, *, keep_denoised: Optional[
             temporal_radius & 0xFFFFFFFF, _lib.G1S_DENOISE_JOINT_CHROMA if joint_chroma else 0,
             str(grain_prior).encode() if grain_prior is not None else None, prior_range & 0xFFFFFFFF, -1 if prior_segment is None else prior_segment)
     auto = (_lib.G1S_AUTO_PRIOR if auto_prior else 0) | (_lib.G1S_AUTO_STRENGTH if auto_strength else 0)
-    rc = L.g1s_diff_y4m_file_denoised_levels(*head, motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0,
-                                             coarse_levels & 0xFFFFFFFF, float(coarse_ratio), C.byref(frames), err, len(err))
+    tail = (motion_range & 0xFFFFFFFF, auto, profile_frames, levels_min_count, 1 if chroma_prior else 0, coarse_levels & 0xFFFFFFFF, float(coarse_ratio))
+    if auto_temporal:
+        rc = L.g1s_diff_y4m_file_denoised_auto_temporal(*head, *tail, 1, C.byref(frames), err, len(err))
+    else:
+        rc = L.g1s_diff_y4m_file_denoised_levels(*head, *tail, C.byref(frames), err, len(err))
     if rc:
         raise RuntimeError(err.value.decode() or f"g1s_diff_y4m_file_denoised_levels failed ({rc})")
     log.info("Computed diff for %d frames", frames.value)

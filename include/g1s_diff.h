@@ -515,6 +515,96 @@ long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uin
 int64_t g1s_nlf_y4m_file(const char *source, const char *out_report, const g1s_nlf_opts_t *opts, uint64_t max_frames, g1s_nlf_record_t *total,
                          char *err, size_t cap);
 
+/* ---- temporal noise levels, rules T1 - T8: the noise of a clip from the difference of consecutive frames ----
+ * N5 says what the 3 x 3 mask assumes: white noise.  Film grain is not white, and on correlated grain the mask sees only the
+ * part of the grain's power at the highest frequencies: in a numpy run of N1, N3 and N7 on a 200 x 200 10-bit picture under
+ * Gaussian grain of sigma 16 it read 16.1 for white grain, 3.8 for 3 x 3 box-filtered and 2.5 for 5 x 5 box-filtered grain.
+ * Grain is independent from frame to frame and picture content is not: where the picture stands still, the difference of
+ * two consecutive frames has variance 2 sigma^2 whatever the grain's spatial correlation.  A meter made temporal
+ * (g1s_nlf_new_temporal) keeps its ordinary records, byte for byte, and adds for every frame of a run but the first a
+ * temporal record against the frame before.  A RUN is the sequence of frames given to one temporal meter with one geometry;
+ * a change of geometry or g1s_nlf_cut ends it.  Frame t of a run, t >= 1, has a temporal record against frame t - 1.  B, sh,
+ * half, the planes, the INTERIOR and the stencils are those of N1 - N2.  Everything is integer except where a rule says
+ * otherwise.  For plane c with samples u_t and u_(t-1):
+ *  T1. Difference.  e(p) = u_t(p) - u_(t-1)(p), signed, |e| < 2^B.
+ *  T2. Gate.  An interior p COUNTS iff N1's gate passes at p in frame t, N1's gate passes at p in frame t - 1, and
+ *      |S9_t(p) - S9_(t-1)(p)| < 144 2^sh, S9 the plain sum of the plane's own nine samples around p (luma and chroma
+ *      alike).  The first two exclude edges, where any motion shows; the third excludes what moved or changed anyway.  144 is
+ *      9 x 16: a box mean that moved by 16 eight-bit code values; for white grain of sigma 8 that is 4.2 standard deviations
+ *      of the box-mean difference.
+ *  T3. Bins, 32, symmetric in the two frames so that a bin does not select on one frame's noise.  Luma:
+ *      k = floor((S9_t + S9_(t-1)) / (18 2^(B - 5))).  Chroma: a_t and a_(t-1) N2's averageLuma at p, each from its own
+ *      frame's luma; k = (a_t + a_(t-1)) >> (B - 4).
+ *  T4. Sums.  Per plane and bin, over the counting p: n[k] (u64), s[k] = sum of e (i64), q[k] = sum of e^2 (u64).  One e^2 is
+ *      below 2^24; a plane of 65536 x 65536 keeps q below 2^56.
+ *  T5. Record.  g1s_nlf_trecord_t, zeros for the planes a frame lacks.  A clip's temporal record is the checked 64-bit sum
+ *      of its pairs' records (g1s_nlf_sum_temporal; s as a signed sum): an overflow is a refusal.
+ *  T6. Levels.  For a bin with n >= Nmin: t_T[k] = isqrt(floor(2^16 (n q - s^2) / (2 n^2))), the products formed in 128 bits
+ *      (n q - s^2 >= 0 for sums of integers; the quotient is taken as floor(floor(2^15 (n q - s^2) / n) / n), the same number,
+ *      which leaves 128 bits for no u64 sums).  That is 256 sigma with the bin's mean difference removed, so that a fade or a
+ *      flicker is not read as grain.
+ *  T7. Prior and strength.  N6 and N9 on t_T in the place of t, unchanged otherwise: the same refusals, the same texts (N9
+ *      pools n, s and q of planes 1 and 2 per bin; a pooled sum that leaves 64 bits is refused with T5's text).  h_luma =
+ *      sqrt(max(Q / N - (S / N)^2, 0)) / 2^(B - 8), N, S, Q plane 0's sums over all bins; the two quotients are formed in f64
+ *      from the exact integers, in that order.  This is sqrt(2) sigma, since the variance of e is 2 sigma^2.  h_chroma: the
+ *      same over planes 1 and 2 pooled.  N7's refusals apply.
+ *  T8. Report.  g1s_format_noise_levels_temporal writes plain text; the grammar is at its declaration.
+ * The gate is not tuned and not corrected for.  In a numpy run on the still picture above the estimate read 6.03 / 6.03 / 5.96
+ * at sigma 6 (white, 3 x 3 box, 5 x 5 box), 16.05 / 15.72 / 16.09 at sigma 16 and 31.9 / 29.0 / 26.9 at sigma 32: from about
+ * 8 eight-bit code values on T2's box condition cuts tails, minus 10 to 16 % on correlated grain.  Motion biases sigma_t
+ * upwards and is not compensated: on a pan of 2 samples a frame over that picture it read 9.6 at sigma 6 and 17.6 at sigma
+ * 16.  The vectors kd_motion finds are not used.  So N's estimate is a lower bound and T's an upper bound; they meet on
+ * white grain over a still picture.  Their ratio is reported (T8); no verdict is drawn from it, and choosing coarse levels
+ * from it is not part of this.  All of these are numpy runs on synthetic content.
+ * The predecessor of a batch's first frame is the last frame of the batch before.  Host and pinned frames are on the device
+ * already; of a device frame the meter keeps a copy when it is a batch's last, so the planes of a device frame stay the
+ * caller's to keep valid no longer than g1s_nlf_frame says. */
+typedef struct {
+  uint64_t n[3][32];
+  int64_t s[3][32];
+  uint64_t q[3][32];
+} g1s_nlf_trecord_t;
+/* g1s_nlf_new for a temporal meter: g1s_nlf_frame and g1s_nlf_finish as before, and the temporal records beside. */
+g1s_nlf_t *g1s_nlf_new_temporal(uint32_t bit_depth, const g1s_nlf_opts_t *opts);
+/* Ends the run: the next frame has no predecessor.  Waits for nothing; what is queued stays queued.  On a meter made by
+ * g1s_nlf_new it does nothing. */
+int g1s_nlf_cut(g1s_nlf_t *);
+/* g1s_nlf_finish for the temporal records: one per frame with a predecessor since the last hand-over, in order.  The
+ * ordinary records stay for g1s_nlf_finish.  Capacity as there.  On a meter made by g1s_nlf_new: G1S_ERR_INVALID, "not a
+ * temporal meter: make it with g1s_nlf_new_temporal" (not sticky). */
+int g1s_nlf_finish_temporal(g1s_nlf_t *, g1s_nlf_trecord_t *per_pair, size_t cap, size_t *n_out);
+/* HIP-event time of the temporal luma and chroma launches so far, milliseconds, and the pairs they covered; timed while
+ * g1s_nlf_set_timing has it enabled.  tools/bench_estimate.py --levels-temporal. */
+int g1s_nlf_temporal_times(g1s_nlf_t *, double *ms_luma, double *ms_chroma, uint64_t *pairs);
+/* The five below are host only: they need no device. */
+/* T5: *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_nlf_sum_temporal(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total);
+/* T6 - T7: g1s_nlf_sigma, g1s_nlf_chroma_sigma and g1s_nlf_strength on a clip's temporal record: the same outputs, the same
+ * refusals. */
+int g1s_nlf_sigma_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s);
+int g1s_nlf_chroma_sigma_temporal(const g1s_nlf_trecord_t *total, uint64_t min_count, uint8_t s[256]);
+int g1s_nlf_strength_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h);
+/* T8: the report of a clip's temporal record of `pairs` pairs.  `ordinary` (may be NULL) is the ordinary record of the same
+ * frames: those with a predecessor, of the same runs.  Values as in N8: f64 from the exact integers in the order written,
+ * "%.4f", code values of the clip's depth; "-" where a value is undefined.  Grammar:
+ *   noiselevels_t1
+ *   pairs N bit_depth B planes P
+ *   plane c                          for c in 0 .. P - 1
+ *   bin k n sigma_t                  the bins with n > 0: sigma_t = sqrt(max(((double)q / n - ((double)s / n)^2) / 2, 0))
+ *   plane_sigma_t v                  sigma_t of the plane's bins summed; "-" when no sample counts
+ *   ratio v                          plane_sigma_t over N8's plane_sigma of `ordinary`; "-" when either is undefined, when
+ *                                    plane_sigma is zero or without `ordinary`
+ *   auto_strength_t h_luma h_chroma  after the planes: T7's two values, each "-" where N7's refusals apply
+ * Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a bit depth or plane count the rules do not have). */
+long g1s_format_noise_levels_temporal(const g1s_nlf_trecord_t *total, const g1s_nlf_record_t *ordinary, uint64_t pairs, uint32_t bit_depth,
+                                      uint32_t nplanes, uint64_t min_count, char *buf, size_t cap);
+/* g1s_nlf_y4m_file with a temporal meter, the file one run: out_report and *total as there (all frames), the temporal report
+ * into out_treport (may be NULL; its ratio from the ordinary record of the frames after the first), the clip's temporal
+ * record into *ttotal (may be NULL).  A clip of one frame has no pair: a report of "-".  `estimate SOURCE --levels-temporal
+ * PATH`. */
+int64_t g1s_nlf_y4m_file_temporal(const char *source, const char *out_report, const char *out_treport, const g1s_nlf_opts_t *opts, uint64_t max_frames,
+                                  g1s_nlf_record_t *total, g1s_nlf_trecord_t *ttotal, char *err, size_t cap);
+
 /* ---- `render`: AV1 film grain synthesis on the device (the inverse of `diff`: a table's grain onto frames) ----
  * The film grain synthesis process of the AV1 specification (clause 7.18.3: random number process, generate grain
  * process, scaling lookup initialisation, add noise synthesis process), integer-exact, written from the standard.
@@ -863,6 +953,15 @@ int64_t g1s_denoise_y4m_file_levels(const char *in, const char *out, const g1s_d
                                     const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
                                     uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio,
                                     char *err, size_t cap);
+/* The same with the pre-pass made temporal (rules T1 - T7); auto_temporal = 0 is g1s_denoise_y4m_file_levels: the same
+ * launches, the same bytes.  1: the pre-pass meter is a temporal one, and G1S_AUTO_PRIOR, G1S_AUTO_STRENGTH and the chroma
+ * prior take T7's values in the place of N6's, N7's and N9's.  Refusals: a value other than 0 or 1 ("auto_temporal is 0 or
+ * 1"), 1 without an auto flag ("temporal noise levels need an auto flag (an auto prior or an auto strength)"), a pre-pass of
+ * fewer than two frames ("temporal noise levels need two frames").  The bits of auto_flags stay as they are. */
+int64_t g1s_denoise_y4m_file_auto_temporal(const char *in, const char *out, const g1s_denoise_opts_t *opts, uint32_t temporal_radius, uint32_t flags,
+                                           const char *prior_tbl, uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags,
+                                           uint64_t profile_frames, uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio,
+                                           uint32_t auto_temporal, char *err, size_t cap);
 /* `diff SOURCE --denoise -o OUT`: g1s_diff_y4m_files with the second file made on the device.  The source is read once
  * and copied to the device once; each frame is denoised there and the pair (source, denoised) goes to the generator as
  * device frames, in buffers that are used again once g1s_diff_frames_released() covers their frame.  The denoiser runs
@@ -911,6 +1010,13 @@ int g1s_diff_y4m_file_denoised_levels(const char *source, const char *out_tbl, c
                                       uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
                                       uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, uint64_t *frames, char *err,
                                       size_t cap);
+/* The same with auto_temporal as g1s_denoise_y4m_file_auto_temporal takes and refuses it; 0 is
+ * g1s_diff_y4m_file_denoised_levels. */
+int g1s_diff_y4m_file_denoised_auto_temporal(const char *source, const char *out_tbl, const char *keep_denoised, const g1s_opts_t *opts,
+                                             const g1s_denoise_opts_t *dopts, uint32_t temporal_radius, uint32_t flags, const char *prior_tbl,
+                                             uint32_t prior_range, int32_t prior_segment, uint32_t motion_range, uint32_t auto_flags, uint64_t profile_frames,
+                                             uint64_t min_count, uint32_t chroma_prior, uint32_t coarse_levels, double coarse_ratio, uint32_t auto_temporal,
+                                             uint64_t *frames, char *err, size_t cap);
 
 /* ---- `measure` and `check`: exact grain statistics of a frame pair (how well a table fits) ----
  * An AV1 grain table says how strong the grain is as a function of intensity and how it is correlated over the causal

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""tools/bench_estimate.py [frames] [--levels] -- N4 on the GPU box: `estimate`'s per-frame noise estimator over HBM-resident 4K 10-bit luma
+"""tools/bench_estimate.py [frames] [--levels] [--levels-temporal] -- N4 on the GPU box: `estimate`'s per-frame noise estimator over HBM-resident 4K 10-bit luma
 planes: whole-loop rate (FFI call per frame, one launch + one 16-byte D2H per batch of 32) and the kernel alone (HIP events),
 against the 8 TB/s HBM roofline (2 bytes per luma pixel: the plane is read once), with the oracle's scalar rate beside it.
 --levels: the two launches of the noise level function (k_nlf on luma; on both chroma planes with the luma under them) on the
 same 4:2:0 frames in the same process, beside k_estimate: microseconds a frame, the bytes each must read (luma once; luma
-again and both chroma planes) and the fraction of the HBM roofline that implies."""
+again and both chroma planes) and the fraction of the HBM roofline that implies.
+--levels-temporal: --levels, and in the same run a temporal meter over the same frames: the two launches of k_nlf_t, which read
+each plane of two frames, beside k_nlf's."""
 import json, os, sys, time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,8 +15,9 @@ from grav1synth_amd.estimate import NoiseEstimator
 from grav1synth_amd.synth import SynthSpec, make_pair
 from tests.oracle_binding import estimate_plane_noise
 
-args = [a for a in sys.argv[1:] if a != "--levels"]
-levels = "--levels" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a not in ("--levels", "--levels-temporal")]
+levels_temporal = "--levels-temporal" in sys.argv[1:]
+levels = "--levels" in sys.argv[1:] or levels_temporal
 n = int(args[0]) if args else 2048
 spec = SynthSpec(3840, 2160, 10)
 frames = [make_pair(spec, k, device="cuda")[0] for k in range(64)]
@@ -66,4 +69,26 @@ if levels:
     n0, a0 = int(recs[-1]["n"][0].sum()), int(recs[-1]["a"][0].sum())
     k_last = (n - 1) % 64
     assert float(a0) / float(6 * n0) * 1.2533141373155003 == got[k_last], "the luma totals are the estimator's sums"
+if levels_temporal:
+    for rep in range(3):
+        meter = NoiseLevelMeter(10, batch_frames=32, temporal=True)
+        meter.kernel_times(True)
+        for k in range(n):
+            meter.frame(frames[k % 64], spec.xdec, spec.ydec)
+            if (k + 1) % 256 == 0 or k + 1 == n:
+                recs_t, trecs = meter.finish(), meter.finish_temporal()
+        ms_tl, ms_tc, pairs = meter.kernel_times_temporal()
+        ms_l2, ms_c2, fr2 = meter.kernel_times(True)
+        meter.close()
+    assert pairs == n - 1 and recs_t[-1].tobytes() == recs[-1].tobytes(), "the ordinary records are a plain meter's"
+    out["levels_t_pairs"] = pairs
+    out["levels_t_luma_us_per_pair"] = ms_tl * 1e3 / pairs
+    out["levels_t_chroma_us_per_pair"] = ms_tc * 1e3 / pairs
+    out["levels_t_luma_bytes"], out["levels_t_chroma_bytes"] = 2 * luma_bytes, 2 * chroma_bytes
+    out["levels_t_luma_roofline_frac"] = 2 * luma_bytes * pairs / (ms_tl * 1e-3) / 1e9 / 8000.0
+    out["levels_t_chroma_roofline_frac"] = 2 * chroma_bytes * pairs / (ms_tc * 1e-3) / 1e9 / 8000.0
+    out["levels_t_luma_over_levels"] = out["levels_t_luma_us_per_pair"] / out["levels_luma_us_per_frame"]
+    out["levels_t_chroma_over_levels"] = out["levels_t_chroma_us_per_pair"] / out["levels_chroma_us_per_frame"]
+    out["levels_luma_us_per_frame_in_the_temporal_meter"] = ms_l2 * 1e3 / fr2
+    out["levels_t_counting_luma_last_pair"] = int(trecs[-1]["n"][0].sum())
 print(json.dumps(out))
