@@ -91,28 +91,18 @@ struct Prior {
     fwd.assign((size_t)1 << (bit_depth <= 12 ? bit_depth : 12), 0), inv.assign(g1s_cv::kInvEntries, 0);
     return g1s_cv::build(segs.data(), segs.size(), bit_depth, range, fwd.data(), inv.data());
   }
-  std::string measure(const g1s_nlf_record_t &total, uint32_t bit_depth, uint32_t range_, uint64_t min_count) {
+  // `luma_s(s)` and `chroma_s(s)`: the two scaling functions of the clip's record, the ordinary one's (N6, N9) or the
+  // temporal one's (T7)
+  template <class LumaS, class ChromaS>
+  std::string measure(uint32_t bit_depth, uint32_t range_, LumaS luma_s, ChromaS chroma_s) {
     std::string why = g1s_cv::check_depth_range(bit_depth, range_);
     if (!why.empty()) return why;
     std::vector<uint8_t> sg((size_t)1 << bit_depth);
-    if (!(why = g1s_nl::sigma(total, bit_depth, min_count, sg.data())).empty()) return why;
+    if (!(why = luma_s(sg.data())).empty()) return why;
     pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
     if (!(why = g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data())).empty() || !chroma) return why;
     uint8_t sc[g1s_cv::kGainEntries];  // rule 23 on the same record, rule 21
-    if (!(why = g1s_nl::chroma_sigma(total, min_count, sc)).empty()) return why;
-    gain.assign(g1s_cv::kGainEntries, 0);
-    return g1s_cv::gain_from_s(sc, range_, gain.data());
-  }
-  // the same from the clip's temporal record (rule T7)
-  std::string measure_t(const g1s_nlf_trecord_t &total, uint32_t bit_depth, uint32_t range_, uint64_t min_count) {
-    std::string why = g1s_cv::check_depth_range(bit_depth, range_);
-    if (!why.empty()) return why;
-    std::vector<uint8_t> sg((size_t)1 << bit_depth);
-    if (!(why = g1s_nl::sigma_t(total, 0, bit_depth, min_count, sg.data())).empty()) return why;
-    pair_fwd.assign((size_t)1 << bit_depth, 0), pair_inv.assign(g1s_cv::kInvEntries, 0);
-    if (!(why = g1s_cv::build_sigma(sg.data(), bit_depth, range_, pair_fwd.data(), pair_inv.data())).empty() || !chroma) return why;
-    uint8_t sc[g1s_cv::kGainEntries];
-    if (!(why = g1s_nl::sigma_t(total, 1, 8, min_count, sc)).empty()) return why;
+    if (!(why = chroma_s(sc)).empty()) return why;
     gain.assign(g1s_cv::kGainEntries, 0);
     return g1s_cv::gain_from_s(sc, range_, gain.data());
   }
@@ -142,18 +132,22 @@ std::string auto_prepass(const char *source, int32_t device, const FileSpec &s, 
   g1s_y4m_info_t info;
   g1s_y4m_get_info(y, &info);
   g1s_y4m_close(y);
+  const uint32_t bd = info.bit_depth;
+  const bool t = s.auto_temporal != 0;
   if (s.auto_flags & G1S_AUTO_PRIOR) {
-    const std::string why = s.auto_temporal ? prior->measure_t(ttotal, info.bit_depth, s.prior_range, s.min_count)
-                                            : prior->measure(total, info.bit_depth, s.prior_range, s.min_count);
+    const std::string why = prior->measure(
+        bd, s.prior_range, [&](uint8_t *sg) { return t ? g1s_nl::sigma_t(ttotal, 0, bd, s.min_count, sg) : g1s_nl::sigma(total, bd, s.min_count, sg); },
+        [&](uint8_t *sc) { return t ? g1s_nl::sigma_t(ttotal, 1, 8, s.min_count, sc) : g1s_nl::chroma_sigma(total, s.min_count, sc); });
     if (!why.empty()) return why;
   }
   if (s.auto_flags & G1S_AUTO_STRENGTH) {
-    const std::string why = s.auto_temporal ? g1s_nl::strength_t(ttotal, info.bit_depth, s.min_count, 0, &d->strength)
-                                            : g1s_nl::strength(total, info.bit_depth, s.min_count, 0, &d->strength);
+    auto strength = [&](uint32_t plane_class, double *h) {
+      return t ? g1s_nl::strength_t(ttotal, bd, s.min_count, plane_class, h) : g1s_nl::strength(total, bd, s.min_count, plane_class, h);
+    };
+    const std::string why = strength(0, &d->strength);
     if (!why.empty()) return why;
     double hc = 0;  // (where the chroma strength is refused: the luma strength)
-    if ((s.auto_temporal ? g1s_nl::strength_t(ttotal, info.bit_depth, s.min_count, 1, &hc) : g1s_nl::strength(total, info.bit_depth, s.min_count, 1, &hc)).empty())
-      d->chroma_strength = hc;
+    if (strength(1, &hc).empty()) d->chroma_strength = hc;
   }
   return "";
 }

@@ -7,7 +7,8 @@
 // (rounded to 8-bit scale) is averaged: sigma = accum / (6 count) * sqrt(pi / 2), None when fewer than 16 pixels are
 // smooth.  One pass over one plane, a 3x3 stencil and two integer sums: HBM bound (2 bytes per luma pixel at 10 bit).
 //
-// Kernel: a wave owns 62 x 8 output columns of a strip of rows and walks the strip top to bottom with the three rows
+// Kernel (k_estimate, the 32-bit form, from the pieces of strip_walk.hip.h that the noise-level kernels in nlf.hip are built
+// from too): a wave owns 62 x 8 output columns of a strip of rows and walks the strip top to bottom with the three rows
 // of the stencil in registers (each row is loaded once per strip, as one 8-sample word per lane: 16-byte loads at
 // 10 bit); lanes 0 and 63 only carry halo columns, the horizontal neighbours of a lane's word come from the adjacent
 // lanes.  Exact integers: the two sums of a frame are the same for any strip / wave / batch partition; the host turns
@@ -23,15 +24,10 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
-#include "est_load.hip.h"
+#include "strip_walk.hip.h"
 #include "frame_op.h"
 
 namespace {
-
-constexpr int kEdgeThreshold = 50;  // EDGE_THRESHOLD
-constexpr int kStripRows = 32;      // output rows per wave strip (+ 2 halo rows)
-constexpr int kWavesPerWg = 4;
-constexpr int kColsPerWave = 62 * 8;
 
 struct EstFrame {
   const uint8_t *y;
@@ -46,49 +42,30 @@ struct EstParams {
 };
 
 template <int BPS>
-__global__ __launch_bounds__(64 * kWavesPerWg) void k_estimate(EstParams ep) {
+__global__ __launch_bounds__(kStripThreads) void k_estimate(EstParams ep) {
   const int frame = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int strip = blockIdx.x * kWavesPerWg + wave;
   if (strip >= ep.col_strips * ep.row_strips) return;
-  const int cs = strip % ep.col_strips, rs = strip / ep.col_strips;
+  const StripCoords s = strip_coords(strip, ep.col_strips, lane, ep.H);
   const EstFrame fr = ep.frames[frame];
-  const int W = ep.W, H = ep.H, shift = ep.shift, half = shift ? 1 << (shift - 1) : 0;
-  // output columns of the wave: [cs * 496, cs * 496 + 496) (less the plane's first and last column); lane l holds the
-  // word at x0 = cs * 496 - 8 + 8 l -- a multiple of 8 samples: aligned 16-byte loads -- lanes 0 and 63 the halo words
-  const int x0 = cs * kColsPerWave - 8 + 8 * lane;
-  const int y_first = 1 + rs * kStripRows, y_last = min(y_first + kStripRows, H - 1);  // output rows [y_first, y_last)
-  int a[8], b[8], c[8];  // rows y - 1, y, y + 1
-  est_load<BPS>(fr.y + (size_t)(y_first - 1) * fr.stride, x0, W, true, a);
-  est_load<BPS>(fr.y + (size_t)y_first * fr.stride, x0, W, y_first < H, b);
+  const int W = ep.W, shift = ep.shift, half = shift ? 1 << (shift - 1) : 0;
+  RowWindow<BPS> w;
+  w.prime(fr.y, fr.stride, s.x0, W, ep.H, s.y_first);
   uint32_t accum = 0, count = 0;
-  const bool out_lane = lane >= 1 && lane <= 62;
-  for (int y = y_first; y < y_last; ++y) {
-    est_load<BPS>(fr.y + (size_t)(y + 1) * fr.stride, x0, W, y + 1 < H, c);
-    // the column left of the word (the neighbour lane's last sample) and right of it (its first), for the three rows
-    const int al = __shfl_up(a[7], 1), bl = __shfl_up(b[7], 1), cl = __shfl_up(c[7], 1);
-    const int ar = __shfl_down(a[0], 1), br = __shfl_down(b[0], 1), cr = __shfl_down(c[0], 1);
-    if (out_lane) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int x = x0 + k;
-        const int m00 = k ? a[k - 1] : al, m01 = a[k], m02 = k < 7 ? a[k + 1] : ar;
-        const int m10 = k ? b[k - 1] : bl, m11 = b[k], m12 = k < 7 ? b[k + 1] : br;
-        const int m20 = k ? c[k - 1] : cl, m21 = c[k], m22 = k < 7 ? c[k + 1] : cr;
-        const int gx = (m00 - m02) + (m20 - m22) + 2 * (m10 - m12);
-        const int gy = (m00 - m20) + (m02 - m22) + 2 * (m01 - m21);
-        const int ga = (abs(gx) + abs(gy) + half) >> shift;
-        const int v = 4 * m11 - 2 * (m01 + m21 + m10 + m12) + (m00 + m02 + m20 + m22);
-        const bool on = x >= 1 && x < W - 1 && ga < kEdgeThreshold;
+  for (int y = s.y_first; y < s.y_last; ++y) {
+    w.load(y);
+    w.fetch();
+    if (s.out_lane)
+      each_of_word([&](auto K) __attribute__((always_inline)) {
+        const Nine m = w.template at<decltype(K)::value>();
+        const int x = s.x0 + K;
+        const int ga = stencil_gate(m, half, shift), v = stencil_laplacian(m);
+        const bool on = (x >= 1) & (x < W - 1) & (ga < kEdgeThreshold);  // (`&`: no branch a condition)
         accum += on ? (uint32_t)((abs(v) + half) >> shift) : 0u;
         count += on ? 1u : 0u;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      a[k] = b[k];
-      b[k] = c[k];
-    }
+      });
+    w.rotate();
   }
   // wave sums -> one pair of atomics per wave
   for (int o = 32; o; o >>= 1) {
@@ -114,12 +91,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg) void k_estimate(EstParams ep) {
 // k_estimate (compared on every test case).  A lane holds one 8-sample word (4 dwords) of the row; the sample
 // left / right of the word comes from the neighbouring lane (DPP wave shifts).
 // ---------------------------------------------------------------------------------
-// (global address space: a pointer read from memory is `flat` to the compiler otherwise, and flat loads wait on the LDS counter too)
-#define EST_GLOBAL __attribute__((address_space(1)))
-typedef uint32_t est_u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t est_u32x4 __attribute__((ext_vector_type(4)));
-typedef const EST_GLOBAL uint8_t *est_gptr;
-__device__ __forceinline__ est_gptr est_global(const uint8_t *p) { return (est_gptr)(uintptr_t)p; }
+// (EST_GLOBAL, est_gptr, est_global and the load vectors est_u32x2, est_u32x4: strip_walk.hip.h)
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u16x2 as_u(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
@@ -284,21 +256,18 @@ __device__ __forceinline__ void est_strip(const EstFrame &fr, int W, int H, int 
 }
 
 template <int BPS>
-__global__ __launch_bounds__(64 * kWavesPerWg) void k_estimate_pk(EstParams ep) {
+__global__ __launch_bounds__(kStripThreads) void k_estimate_pk(EstParams ep) {
   const int frame = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int strip = blockIdx.x * kWavesPerWg + wave;
   if (strip >= ep.col_strips * ep.row_strips) return;
-  // (column strips are the fast index: the waves of a workgroup read adjacent kilobytes of the same rows)
-  const int cs = strip % ep.col_strips, rs = strip / ep.col_strips;
   const EstFrame fr = ep.frames[frame];
   const int W = ep.W, H = ep.H;
   const bool fast = (((uintptr_t)fr.y | fr.stride) & (BPS == 2 ? 15 : 7)) == 0 && (W & 7) == 0;  // (uniform)
-  const int x0 = cs * kColsPerWave - 8 + 8 * lane;
-  const int y_first = 1 + rs * ep.strip_rows, y_last = min(y_first + ep.strip_rows, H - 1);  // output rows [y_first, y_last)
+  const StripCoords s = strip_coords(strip, ep.col_strips, lane, H, ep.strip_rows);
   uint32_t accum = 0, count = 0;
-  if (fast) est_strip<BPS, true>(fr, W, H, ep.shift, x0, y_first, y_last, lane, accum, count);
-  else est_strip<BPS, false>(fr, W, H, ep.shift, x0, y_first, y_last, lane, accum, count);
+  if (fast) est_strip<BPS, true>(fr, W, H, ep.shift, s.x0, s.y_first, s.y_last, lane, accum, count);
+  else est_strip<BPS, false>(fr, W, H, ep.shift, s.x0, s.y_first, s.y_last, lane, accum, count);
   for (int o = 32; o; o >>= 1) {
     accum += __shfl_down(accum, o);
     count += __shfl_down(count, o);
@@ -364,8 +333,8 @@ int g1s_estimate::flush() {
     // whole resident rounds: k rounds of `resident` waves, the smallest k whose strips are at most kPkMaxStripRows rows
     int cus = 256, wgs_per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (bps == 2) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<2>, 64 * kWavesPerWg, 0);
-    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<1>, 64 * kWavesPerWg, 0);
+    if (bps == 2) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<2>, kStripThreads, 0);
+    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<1>, kStripThreads, 0);
     if (wgs_per_cu < 1) wgs_per_cu = 5;
     const long resident = (long)cus * wgs_per_cu * kWavesPerWg, cols = (long)ep.col_strips * B, rows = (long)H - 2;
     for (long k = 1;; ++k) {
@@ -380,10 +349,10 @@ int g1s_estimate::flush() {
   if (launch) {
     const dim3 grid((ep.col_strips * ep.row_strips + kWavesPerWg - 1) / kWavesPerWg, B);
     if (timing) G1S_OP_TRY(hipEventRecord(ev0, stream));
-    if (packed && bps == 2) hipLaunchKernelGGL(k_estimate_pk<2>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
-    else if (packed) hipLaunchKernelGGL(k_estimate_pk<1>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
-    else if (bps == 2) hipLaunchKernelGGL(k_estimate<2>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
-    else hipLaunchKernelGGL(k_estimate<1>, grid, dim3(64 * kWavesPerWg), 0, stream, ep);
+    if (packed && bps == 2) hipLaunchKernelGGL(k_estimate_pk<2>, grid, dim3(kStripThreads), 0, stream, ep);
+    else if (packed) hipLaunchKernelGGL(k_estimate_pk<1>, grid, dim3(kStripThreads), 0, stream, ep);
+    else if (bps == 2) hipLaunchKernelGGL(k_estimate<2>, grid, dim3(kStripThreads), 0, stream, ep);
+    else hipLaunchKernelGGL(k_estimate<1>, grid, dim3(kStripThreads), 0, stream, ep);
     if (timing) G1S_OP_TRY(hipEventRecord(ev1, stream));
   }
   G1S_OP_TRY(hipMemcpyAsync(h_sums, d_sums, sizeof(unsigned long long) * 2 * B, hipMemcpyDeviceToHost, stream));
@@ -413,7 +382,7 @@ g1s_estimate_t *g1s_estimate_new(uint32_t bit_depth, int32_t device, uint32_t ba
   e->device = device;
   e->bit_depth = bit_depth;
   e->bps = bit_depth > 8 ? 2 : 1;
-  e->batch = batch_frames ? std::min(batch_frames, 256u) : 32u;
+  e->batch = batch_of(batch_frames);
   if (!open_stream(device, e->stream) || hipMalloc((void **)&e->d_frames.p, sizeof(EstFrame) * e->batch) != hipSuccess ||
       hipMalloc((void **)&e->d_sums.p, sizeof(unsigned long long) * 2 * e->batch) != hipSuccess ||
       hipHostMalloc((void **)&e->h_sums.p, sizeof(unsigned long long) * 2 * e->batch, hipHostMallocDefault) != hipSuccess ||

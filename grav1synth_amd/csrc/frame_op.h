@@ -1,9 +1,12 @@
-// frame_op.h -- the host scaffold the frame operations share (render: grain.hip, denoise: denoise.hip, estimate:
-// estimate.hip, measure: measure.hip; the generator, engine.hip, takes the owners and the addressing predicate).  Host code only.  The first part -- plane geometry, the two layouts of a
-// frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP and builds with a host compiler
-// alone (measure_report.cpp, which needs a chroma plane's size and nothing else of this, has it as a local helper and does
-// not include this file); the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro and the
-// base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
+// frame_op.h -- the host scaffold the frame operations share.  Who uses what: render (grain.hip), denoise (denoise.hip),
+// measure (measure.hip), the noise levels (nlf.hip) and the surface converter (surface.hip) are BatchedOp's; the estimator
+// (estimate.hip: its copies are synchronous) takes the owners, pick_device, open_stream and batch_of, the generator
+// (engine.hip) the owners and the addressing predicate; of the file commands grain.hip's and denoise_file.cpp's go through
+// rewrite_y4m, nlf_file.cpp takes batch_of alone.  Host code only.  The first part -- the batch clamp,
+// plane geometry, the two layouts of a frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP
+// and builds with a host compiler alone (measure_report.cpp, which needs a chroma plane's size and nothing else of this,
+// has it as a local helper and does not include this file); the second part, under __HIPCC__, is the owners of HIP objects,
+// the TRY macro and the base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
 #pragma once
 #include <stdint.h>
 
@@ -20,6 +23,9 @@ extern "C" void g1s_set_global_error_(const char *);
 namespace g1s_op {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the frames a batched operation launches at once, from the batch_frames its caller gave: 0 = 32, at most 256
+inline uint32_t batch_of(uint32_t batch_frames) { return batch_frames ? (batch_frames < 256u ? batch_frames : 256u) : 32u; }
 
 // the planes of a frame: luma W x H, chroma decimated by (subx, suby) <= 1, `bps` bytes a sample
 struct PlaneGeom {
@@ -314,7 +320,7 @@ struct BatchedOp {
     return err_code;
   }
   bool open(int device_, uint32_t bit_depth_, uint32_t batch_frames) {
-    device = device_, bit_depth = bit_depth_, bps = bit_depth_ > 8 ? 2 : 1, batch = batch_frames ? (batch_frames < 256u ? batch_frames : 256u) : 32u;
+    device = device_, bit_depth = bit_depth_, bps = bit_depth_ > 8 ? 2 : 1, batch = batch_of(batch_frames);
     bool ok = open_stream(device, stream);
     for (Event &e : done) ok = ok && hipEventCreateWithFlags(&e.p, hipEventDisableTiming) == hipSuccess;
     return ok;

@@ -515,76 +515,73 @@ int g1s_nlf_chroma_sigma(const g1s_nlf_record_t *total, uint64_t min_count, uint
 
 int g1s_denoise_chroma_gain_sigma(const uint8_t s[256], uint32_t range, uint16_t gain[256]) { return gain_result(g1s_cv::gain_from_s(s, range, gain)); }
 
-// noise levels, rules N4 - N8 (nlf.h): what is done with a record needs no device
-int g1s_nlf_sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) {
+// noise levels, rules N4 - N8, and temporal noise levels, rules T5 - T8 (nlf.h): what is done with a record of either kind
+// needs no device.  A pair of wrappers a rule; the checks of the arguments and the way out are the pair's, `name` its own.
+}  // extern "C"
+
+template <class Record>
+static int nlf_sum(const Record *recs, size_t n, Record *total) {
   if (!total || (n && !recs)) return G1S_ERR_INVALID;
-  return g1s_nl::sum(recs, n, total) ? G1S_OK : G1S_ERR_INVALID;
+  return g1s_nl::sum_records(recs, n, total) ? G1S_OK : G1S_ERR_INVALID;
 }
 
-int g1s_nlf_sigma(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
-  std::string why = !total || !s ? std::string("g1s_nlf_sigma needs a record and the output table") : g1s_cv::check_depth_range(bit_depth, 0);
-  if (why.empty()) why = g1s_nl::sigma(*total, bit_depth, min_count, s);
-  if (!why.empty()) {
-    g1s_set_global_error_(why.c_str());
-    return G1S_ERR_INVALID;
-  }
-  return G1S_OK;
+template <class Sigma>
+static int nlf_sigma(const char *name, bool have, uint32_t bit_depth, Sigma sigma) {
+  std::string why = !have ? std::string(name) + " needs a record and the output table" : g1s_cv::check_depth_range(bit_depth, 0);
+  if (why.empty()) why = sigma();
+  return gain_result(why);
 }
 
-int g1s_nlf_strength(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
+template <class Strength>
+static int nlf_strength(const char *name, bool have, uint32_t bit_depth, uint32_t plane_class, Strength strength) {
   std::string why;
-  if (!total || !h) why = "g1s_nlf_strength needs a record and the output value";
+  if (!have) why = std::string(name) + " needs a record and the output value";
   else if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) why = "noise levels are defined for bit depths 8, 10 and 12";
   else if (plane_class > 1) why = "plane_class is 0 (luma) or 1 (chroma)";
-  else why = g1s_nl::strength(*total, bit_depth, min_count, plane_class, h);
-  if (!why.empty()) {
-    g1s_set_global_error_(why.c_str());
-    return G1S_ERR_INVALID;
-  }
-  return G1S_OK;
+  else why = strength();
+  return gain_result(why);
 }
 
-long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, uint64_t min_count, char *buf,
-                             size_t cap) {
-  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
-  const std::string s = g1s_nl::report(*total, frames, bit_depth, nplanes, min_count);
+template <class Report>
+static long nlf_report(bool have, uint32_t bit_depth, uint32_t nplanes, char *buf, size_t cap, Report report) {
+  if (!have || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
+  const std::string s = report();
   if (s.size() > cap) return G1S_ERR_CAPACITY;
   std::memcpy(buf, s.data(), s.size());
   return (long)s.size();
 }
 
-// temporal noise levels, rules T5 - T8 (nlf.h): the same for a temporal record
-int g1s_nlf_sum_temporal(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total) {
-  if (!total || (n && !recs)) return G1S_ERR_INVALID;
-  return g1s_nl::sum_t(recs, n, total) ? G1S_OK : G1S_ERR_INVALID;
-}
+extern "C" {
 
+int g1s_nlf_sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) { return nlf_sum(recs, n, total); }
+int g1s_nlf_sum_temporal(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total) { return nlf_sum(recs, n, total); }
+
+int g1s_nlf_sigma(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
+  return nlf_sigma("g1s_nlf_sigma", total && s, bit_depth, [&] { return g1s_nl::sigma(*total, bit_depth, min_count, s); });
+}
 int g1s_nlf_sigma_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint8_t *s) {
-  std::string why = !total || !s ? std::string("g1s_nlf_sigma_temporal needs a record and the output table") : g1s_cv::check_depth_range(bit_depth, 0);
-  if (why.empty()) why = g1s_nl::sigma_t(*total, 0, bit_depth, min_count, s);
-  return gain_result(why);
+  return nlf_sigma("g1s_nlf_sigma_temporal", total && s, bit_depth, [&] { return g1s_nl::sigma_t(*total, 0, bit_depth, min_count, s); });
 }
 
 int g1s_nlf_chroma_sigma_temporal(const g1s_nlf_trecord_t *total, uint64_t min_count, uint8_t s[256]) {
   return gain_result(!total || !s ? std::string("g1s_nlf_chroma_sigma_temporal needs a record and the output table") : g1s_nl::sigma_t(*total, 1, 8, min_count, s));
 }
 
+int g1s_nlf_strength(const g1s_nlf_record_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
+  return nlf_strength("g1s_nlf_strength", total && h, bit_depth, plane_class, [&] { return g1s_nl::strength(*total, bit_depth, min_count, plane_class, h); });
+}
 int g1s_nlf_strength_temporal(const g1s_nlf_trecord_t *total, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
-  std::string why;
-  if (!total || !h) why = "g1s_nlf_strength_temporal needs a record and the output value";
-  else if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) why = "noise levels are defined for bit depths 8, 10 and 12";
-  else if (plane_class > 1) why = "plane_class is 0 (luma) or 1 (chroma)";
-  else why = g1s_nl::strength_t(*total, bit_depth, min_count, plane_class, h);
-  return gain_result(why);
+  return nlf_strength("g1s_nlf_strength_temporal", total && h, bit_depth, plane_class,
+                      [&] { return g1s_nl::strength_t(*total, bit_depth, min_count, plane_class, h); });
 }
 
+long g1s_format_noise_levels(const g1s_nlf_record_t *total, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, uint64_t min_count, char *buf,
+                             size_t cap) {
+  return nlf_report(total, bit_depth, nplanes, buf, cap, [&] { return g1s_nl::report(*total, frames, bit_depth, nplanes, min_count); });
+}
 long g1s_format_noise_levels_temporal(const g1s_nlf_trecord_t *total, const g1s_nlf_record_t *ordinary, uint64_t pairs, uint32_t bit_depth,
                                       uint32_t nplanes, uint64_t min_count, char *buf, size_t cap) {
-  if (!total || (!buf && cap) || (nplanes != 1 && nplanes != 3) || (bit_depth != 8 && bit_depth != 10 && bit_depth != 12)) return G1S_ERR_INVALID;
-  const std::string s = g1s_nl::report_t(*total, ordinary, pairs, bit_depth, nplanes, min_count);
-  if (s.size() > cap) return G1S_ERR_CAPACITY;
-  std::memcpy(buf, s.data(), s.size());
-  return (long)s.size();
+  return nlf_report(total, bit_depth, nplanes, buf, cap, [&] { return g1s_nl::report_t(*total, ordinary, pairs, bit_depth, nplanes, min_count); });
 }
 
 }  // extern "C"

@@ -20,18 +20,37 @@ constexpr double kSqrtPiBy2 = 1.2533141373155003;  // SQRT_PI_BY_2, the estimato
 
 inline uint64_t min_count_of(uint64_t min_count) { return min_count ? min_count : kDefaultMinCount; }
 
-// N4: false when a sum leaves 64 bits (then *total is untouched)
-inline bool sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) {
-  g1s_nlf_record_t t;
+// the middle field of a record of either kind: a (sums of |L|, unsigned) or s (sums of e, signed)
+inline auto &mid(g1s_nlf_record_t &r) { return r.a; }
+inline auto &mid(const g1s_nlf_record_t &r) { return r.a; }
+inline auto &mid(g1s_nlf_trecord_t &r) { return r.s; }
+inline auto &mid(const g1s_nlf_trecord_t &r) { return r.s; }
+
+constexpr const char *kSumsLeave64 = "the clip's sums leave 64 bits";
+
+// N4 and T5: false when a sum leaves 64 bits (then *total is untouched)
+template <class Record>
+inline bool sum_records(const Record *recs, size_t n, Record *total) {
+  Record t;
   std::memset(&t, 0, sizeof t);
   bool ok = true;
   for (size_t f = 0; f < n; ++f)
     for (int c = 0; c < 3; ++c)
       for (int k = 0; k < kBins; ++k)
-        ok = !__builtin_add_overflow(t.n[c][k], recs[f].n[c][k], &t.n[c][k]) && !__builtin_add_overflow(t.a[c][k], recs[f].a[c][k], &t.a[c][k]) &&
+        ok = !__builtin_add_overflow(t.n[c][k], recs[f].n[c][k], &t.n[c][k]) && !__builtin_add_overflow(mid(t)[c][k], mid(recs[f])[c][k], &mid(t)[c][k]) &&
              !__builtin_add_overflow(t.q[c][k], recs[f].q[c][k], &t.q[c][k]) && ok;
   if (ok) *total = t;
   return ok;
+}
+inline bool sum(const g1s_nlf_record_t *recs, size_t n, g1s_nlf_record_t *total) { return sum_records(recs, n, total); }
+inline bool sum_t(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total) { return sum_records(recs, n, total); }
+
+// the ordinary record of the frames with a predecessor: a run's total less its first frame's
+inline g1s_nlf_record_t without_first(const g1s_nlf_record_t &total, const g1s_nlf_record_t &first) {
+  g1s_nlf_record_t later = total;
+  for (int c = 0; c < 3; ++c)
+    for (int k = 0; k < kBins; ++k) later.n[c][k] -= first.n[c][k], later.a[c][k] -= first.a[c][k], later.q[c][k] -= first.q[c][k];
+  return later;
 }
 
 // floor(sqrt(v)) of a 128-bit value whose root fits 64 bits
@@ -108,26 +127,35 @@ inline std::string chroma_sigma(const g1s_nlf_record_t &r, uint64_t min_count, u
   return sigma_of_bins(n, q, 8, min_count, s) ? "" : "no chroma bin has enough smooth samples for a prior";
 }
 
-// N7 for a plane class (0: luma; 1: the chroma planes pooled).  "" when fine, else the refusal.
-inline std::string strength(const g1s_nlf_record_t &r, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
-  unsigned __int128 Q = 0, N = 0;
-  for (int c = plane_class ? 1 : 0; c < (plane_class ? 3 : 1); ++c)
-    for (int k = 0; k < kBins; ++k) Q += r.q[c][k], N += r.n[c][k];
+// N7 and T7 behind the sums: the refusals, and rms() -- the strength in the clip's code values, asked for only where N
+// suffices -- scaled to 8-bit code values.  "" when fine, else the refusal.
+template <class Rms>
+inline std::string strength_of(unsigned __int128 N, uint32_t bit_depth, uint64_t min_count, Rms rms, double *h) {
   if (N < min_count_of(min_count)) return "too few smooth samples for a strength";
-  const double v = std::sqrt((2.0 * (double)Q) / (36.0 * (double)N)) / (double)(1u << (bit_depth - 8));
+  const double v = rms() / (double)(1u << (bit_depth - 8));
   if (!(v > 0.0 && v <= 1000.0)) return "the measured strength is outside 0 < h <= 1000";
   *h = v;
   return "";
 }
 
+// N7 for a plane class (0: luma; 1: the chroma planes pooled).  "" when fine, else the refusal.
+inline std::string strength(const g1s_nlf_record_t &r, uint32_t bit_depth, uint64_t min_count, uint32_t plane_class, double *h) {
+  unsigned __int128 Q = 0, N = 0;
+  for (int c = plane_class ? 1 : 0; c < (plane_class ? 3 : 1); ++c)
+    for (int k = 0; k < kBins; ++k) Q += r.q[c][k], N += r.n[c][k];
+  return strength_of(N, bit_depth, min_count, [&] { return std::sqrt((2.0 * (double)Q) / (36.0 * (double)N)); }, h);
+}
+
+// a value of a report, "-" where it is not defined
+inline std::string value(bool defined, double v) {
+  if (!defined) return "-";
+  char s[64];
+  snprintf(s, sizeof s, "%.4f", v);
+  return s;
+}
+
 // N8
 inline std::string report(const g1s_nlf_record_t &r, uint64_t frames, uint32_t bit_depth, uint32_t nplanes, uint64_t min_count) {
-  auto value = [](bool defined, double v) -> std::string {
-    if (!defined) return "-";
-    char s[64];
-    snprintf(s, sizeof s, "%.4f", v);
-    return s;
-  };
   std::string s = "noiselevels1\n";
   s += "frames " + std::to_string(frames) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
   const double scale = (double)(1u << (bit_depth - 8));
@@ -151,22 +179,6 @@ inline std::string report(const g1s_nlf_record_t &r, uint64_t frames, uint32_t b
 }
 
 // ---- temporal noise levels, rules T5 - T8: the same for a record of frame differences ----
-constexpr const char *kSumsLeave64 = "the clip's sums leave 64 bits";
-
-// T5: false when a sum leaves 64 bits (then *total is untouched)
-inline bool sum_t(const g1s_nlf_trecord_t *recs, size_t n, g1s_nlf_trecord_t *total) {
-  g1s_nlf_trecord_t t;
-  std::memset(&t, 0, sizeof t);
-  bool ok = true;
-  for (size_t f = 0; f < n; ++f)
-    for (int c = 0; c < 3; ++c)
-      for (int k = 0; k < kBins; ++k)
-        ok = !__builtin_add_overflow(t.n[c][k], recs[f].n[c][k], &t.n[c][k]) && !__builtin_add_overflow(t.s[c][k], recs[f].s[c][k], &t.s[c][k]) &&
-             !__builtin_add_overflow(t.q[c][k], recs[f].q[c][k], &t.q[c][k]) && ok;
-  if (ok) *total = t;
-  return ok;
-}
-
 // T6: t_T of a bin with sums n > 0, s, q
 inline uint64_t level_t(uint64_t n, int64_t s, uint64_t q) {
   const unsigned __int128 a = s < 0 ? (unsigned __int128)0 - (unsigned __int128)(__int128)s : (unsigned __int128)s;
@@ -219,22 +231,12 @@ inline std::string strength_t(const g1s_nlf_trecord_t &r, uint32_t bit_depth, ui
   unsigned __int128 Q = 0, N = 0;
   __int128 S = 0;
   for (int c = plane_class ? 1 : 0; c < (plane_class ? 3 : 1); ++c) plane_sums(r, c, N, S, Q);
-  if (N < min_count_of(min_count)) return "too few smooth samples for a strength";
-  const double v = std::sqrt(variance_of(N, S, Q)) / (double)(1u << (bit_depth - 8));
-  if (!(v > 0.0 && v <= 1000.0)) return "the measured strength is outside 0 < h <= 1000";
-  *h = v;
-  return "";
+  return strength_of(N, bit_depth, min_count, [&] { return std::sqrt(variance_of(N, S, Q)); }, h);
 }
 
 // T8; `ordinary`: the ordinary record of the frames with a predecessor, or null
 inline std::string report_t(const g1s_nlf_trecord_t &r, const g1s_nlf_record_t *ordinary, uint64_t pairs, uint32_t bit_depth, uint32_t nplanes,
                             uint64_t min_count) {
-  auto value = [](bool defined, double v) -> std::string {
-    if (!defined) return "-";
-    char s[64];
-    snprintf(s, sizeof s, "%.4f", v);
-    return s;
-  };
   std::string s = "noiselevels_t1\n";
   s += "pairs " + std::to_string(pairs) + " bit_depth " + std::to_string(bit_depth) + " planes " + std::to_string(nplanes) + "\n";
   for (int c = 0; c < (int)nplanes; ++c) {

@@ -1,0 +1,115 @@
+// nlf_file.cpp -- the file commands of the noise levels: `estimate --levels` (g1s_nlf_y4m_file) and `--levels-temporal`
+// (g1s_nlf_y4m_file_temporal), which are also the pre-pass of `denoise --auto-*`.  Host code above the per-frame ABI of
+// nlf.hip: it launches no kernel and sees the meter through g1s_nlf_* alone.  The records are taken after every batch of
+// frames (frame_op.h's batch_of: the meter's own batch), so the meter never holds more than a batch of them.
+#include <stdint.h>
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/g1s_diff.h"
+#include "frame_op.h"
+#include "nlf.h"
+
+namespace {
+
+int refuse(char *err, size_t cap, int code, const std::string &m) {
+  if (err && cap) snprintf(err, cap, "%s", m.c_str());
+  return code;
+}
+
+// the records of one kind the meter holds (`finish`: g1s_nlf_finish or g1s_nlf_finish_temporal), added to `total`; they
+// stay in `scratch`, behind them the total as it was.  "" when fine
+template <class Record, class Finish>
+std::string take_records(g1s_nlf_t *m, Finish finish, std::vector<Record> &scratch, Record &total) {
+  size_t n = 0;
+  int rc = finish(m, nullptr, 0, &n);
+  if (rc && rc != G1S_ERR_CAPACITY) return g1s_nlf_last_error(m);
+  scratch.resize(n + 1);
+  scratch[n] = total;
+  if (n && (rc = finish(m, scratch.data(), n, &n)) != 0) return g1s_nlf_last_error(m);
+  if (!g1s_nl::sum_records(scratch.data(), n + 1, &total)) return g1s_nl::kSumsLeave64;
+  return "";
+}
+
+std::string write_text(const char *path, const std::string &text) {
+  FILE *fo = std::fopen(path, "wb");
+  if (!fo) return std::string("cannot create ") + path;
+  const bool ok = std::fwrite(text.data(), 1, text.size(), fo) == text.size();
+  return std::fclose(fo) != 0 || !ok ? std::string("cannot write ") + path : "";
+}
+
+// a .y4m file through a meter (`temporal`: a temporal one, the file one run): the reports, the clip's records
+int64_t nlf_y4m_file(const char *source, const char *out_report, const char *out_treport, const g1s_nlf_opts_t *opts, uint64_t max_frames,
+                     g1s_nlf_record_t *total_out, g1s_nlf_trecord_t *ttotal_out, bool temporal, char *err, size_t cap) {
+  if (!source) return refuse(err, cap, G1S_ERR_INVALID, "null path");
+  g1s_y4m_t *y = g1s_y4m_open(source, err, cap);
+  if (!y) return G1S_ERR_INVALID;
+  g1s_y4m_info_t info;
+  g1s_y4m_get_info(y, &info);
+  int rc = G1S_OK;
+  std::string why;
+  int64_t frames = 0;
+  uint64_t pairs = 0;
+  g1s_nlf_record_t total, first;  // first: the clip's first frame alone, which has no predecessor
+  g1s_nlf_trecord_t ttotal;
+  std::memset(&total, 0, sizeof total), std::memset(&first, 0, sizeof first), std::memset(&ttotal, 0, sizeof ttotal);
+  bool have_first = false;
+  std::vector<g1s_nlf_record_t> scratch;
+  std::vector<g1s_nlf_trecord_t> tscratch;
+  const uint32_t batch = g1s_op::batch_of(opts ? opts->batch_frames : 0);
+  g1s_nlf_t *m = temporal ? g1s_nlf_new_temporal(info.bit_depth, opts) : g1s_nlf_new(info.bit_depth, opts);
+  auto take_all = [&]() -> std::string {
+    std::string no = take_records(m, g1s_nlf_finish, scratch, total);
+    if (no.empty() && !have_first && scratch.size() > 1) first = scratch[0], have_first = true;
+    if (no.empty() && temporal && (no = take_records(m, g1s_nlf_finish_temporal, tscratch, ttotal)).empty()) pairs += tscratch.size() - 1;
+    return no;
+  };
+  if (!m) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
+  while (!rc && (!max_frames || (uint64_t)frames < max_frames)) {
+    g1s_frame_t f;
+    const int got = g1s_y4m_next(y, &f);
+    if (got < 0) {
+      rc = got, why = "frame " + std::to_string(frames) + ": " + g1s_y4m_last_error(y);
+      break;
+    }
+    if (got == 0) break;
+    f.on_device = 0;  // (the reader lends the frame until its next call: copied before the call returns)
+    if ((rc = g1s_nlf_frame(m, &f)) != 0) {
+      why = "frame " + std::to_string(frames) + ": " + g1s_nlf_last_error(m);
+      break;
+    }
+    ++frames;
+    if (frames % batch == 0 && !(why = take_all()).empty()) rc = G1S_ERR_INVALID;
+  }
+  if (!rc && !(why = take_all()).empty()) rc = G1S_ERR_INVALID;
+  if (!rc && out_report && !(why = write_text(out_report, g1s_nl::report(total, (uint64_t)frames, info.bit_depth, info.nplanes, 0))).empty())
+    rc = G1S_ERR_INVALID;
+  if (!rc && out_treport) {
+    const g1s_nlf_record_t later = g1s_nl::without_first(total, first);
+    if (!(why = write_text(out_treport, g1s_nl::report_t(ttotal, &later, pairs, info.bit_depth, info.nplanes, 0))).empty()) rc = G1S_ERR_INVALID;
+  }
+  if (!rc && total_out) *total_out = total;
+  if (!rc && ttotal_out) *ttotal_out = ttotal;
+  g1s_nlf_free(m);
+  g1s_y4m_close(y);
+  return rc ? refuse(err, cap, rc, why) : frames;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t g1s_nlf_y4m_file(const char *source, const char *out_report, const g1s_nlf_opts_t *opts, uint64_t max_frames, g1s_nlf_record_t *total_out,
+                         char *err, size_t cap) {
+  return nlf_y4m_file(source, out_report, nullptr, opts, max_frames, total_out, nullptr, false, err, cap);
+}
+
+int64_t g1s_nlf_y4m_file_temporal(const char *source, const char *out_report, const char *out_treport, const g1s_nlf_opts_t *opts, uint64_t max_frames,
+                                  g1s_nlf_record_t *total_out, g1s_nlf_trecord_t *ttotal_out, char *err, size_t cap) {
+  return nlf_y4m_file(source, out_report, out_treport, opts, max_frames, total_out, ttotal_out, true, err, cap);
+}
+
+}  // extern "C"

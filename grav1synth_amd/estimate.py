@@ -203,22 +203,25 @@ class NoiseLevelMeter(FrameOp):
         self._keep.append(keep)
         self._check(self._L.g1s_nlf_frame(self._h, C.byref(f)))
 
-    def finish(self, cap: Optional[int] = None) -> np.ndarray:
-        """Launches what is queued, waits, and returns the records since the last finish(), one a frame, in order.  cap:
-        the size of the buffer handed to the library (a test aid; too small raises G1S_ERR_CAPACITY and loses nothing)."""
+    def _finish(self, call, dtype, cap: Optional[int]) -> np.ndarray:
         n = C.c_size_t()
         if cap is None:
-            rc = self._L.g1s_nlf_finish(self._h, None, 0, C.byref(n))
+            rc = call(self._h, None, 0, C.byref(n))
             if rc not in (0, _lib.G1S_ERR_CAPACITY):
                 self._check(rc)
             cap = n.value
-        out = np.zeros(max(cap, 1), NLF_RECORD)
-        rc = self._L.g1s_nlf_finish(self._h, out.ctypes.data, cap, C.byref(n))
+        out = np.zeros(max(cap, 1), dtype)
+        rc = call(self._h, out.ctypes.data, cap, C.byref(n))
         if rc == _lib.G1S_ERR_CAPACITY:
             raise G1SError(rc, f"{n.value} records do not fit {cap}")
         self._check(rc)
         self._keep.clear()
         return out[:n.value]
+
+    def finish(self, cap: Optional[int] = None) -> np.ndarray:
+        """Launches what is queued, waits, and returns the records since the last finish(), one a frame, in order.  cap:
+        the size of the buffer handed to the library (a test aid; too small raises G1S_ERR_CAPACITY and loses nothing)."""
+        return self._finish(self._L.g1s_nlf_finish, NLF_RECORD, cap)
 
     def cut(self) -> None:
         """Ends the run of a temporal meter: the next frame has no predecessor.  Waits for nothing."""
@@ -227,19 +230,7 @@ class NoiseLevelMeter(FrameOp):
     def finish_temporal(self, cap: Optional[int] = None) -> np.ndarray:
         """finish() for the temporal records: one per frame with a predecessor since the last finish_temporal(), in order.  A
         meter made without temporal = True refuses."""
-        n = C.c_size_t()
-        if cap is None:
-            rc = self._L.g1s_nlf_finish_temporal(self._h, None, 0, C.byref(n))
-            if rc not in (0, _lib.G1S_ERR_CAPACITY):
-                self._check(rc)
-            cap = n.value
-        out = np.zeros(max(cap, 1), NLF_TRECORD)
-        rc = self._L.g1s_nlf_finish_temporal(self._h, out.ctypes.data, cap, C.byref(n))
-        if rc == _lib.G1S_ERR_CAPACITY:
-            raise G1SError(rc, f"{n.value} records do not fit {cap}")
-        self._check(rc)
-        self._keep.clear()
-        return out[:n.value]
+        return self._finish(self._L.g1s_nlf_finish_temporal, NLF_TRECORD, cap)
 
     def kernel_times_temporal(self) -> Tuple[float, float, int]:
         """(ms in the temporal luma launches, ms in the temporal chroma launches, pairs) of the batches kernel_times() had
@@ -255,24 +246,23 @@ class NoiseLevelMeter(FrameOp):
         return a.value, b.value, n.value
 
 
-def noise_levels_sum(records: np.ndarray) -> np.ndarray:
-    """Rule N4: a clip's record from its frames' (g1s_nlf_sum; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, NLF_RECORD).reshape(-1)
-    total = np.zeros((), NLF_RECORD)
-    rc = _lib.lib().g1s_nlf_sum(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
+def _sum_records(call, dtype, records: np.ndarray) -> np.ndarray:
+    records = np.ascontiguousarray(records, dtype).reshape(-1)
+    total = np.zeros((), dtype)
+    rc = call(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
     if rc:
         raise G1SError(rc, "the clip's sums leave 64 bits")
     return total
+
+
+def noise_levels_sum(records: np.ndarray) -> np.ndarray:
+    """Rule N4: a clip's record from its frames' (g1s_nlf_sum; host only).  An overflow raises."""
+    return _sum_records(_lib.lib().g1s_nlf_sum, NLF_RECORD, records)
 
 
 def noise_levels_sum_temporal(records: np.ndarray) -> np.ndarray:
     """Rule T5: a clip's temporal record from its pairs' (g1s_nlf_sum_temporal; host only).  An overflow raises."""
-    records = np.ascontiguousarray(records, NLF_TRECORD).reshape(-1)
-    total = np.zeros((), NLF_TRECORD)
-    rc = _lib.lib().g1s_nlf_sum_temporal(records.ctypes.data if records.size else None, records.size, total.ctypes.data)
-    if rc:
-        raise G1SError(rc, "the clip's sums leave 64 bits")
-    return total
+    return _sum_records(_lib.lib().g1s_nlf_sum_temporal, NLF_TRECORD, records)
 
 
 def noise_sigma(record: np.ndarray, bit_depth: int, min_count: int = 0, *, temporal: bool = False) -> np.ndarray:

@@ -286,6 +286,38 @@ def test_batches_of_one_of_two_of_all_and_of_one_more(batch, where):
     plain.close()
 
 
+def test_the_ordinary_records_of_a_temporal_meter_over_several_strips():
+    """Three frames of 499 x 36, 10-bit 4:2:0, at batch_frames = 2: two column strips and two row strips in luma, one strip
+    in chroma, a pair across a batch boundary and a last batch that is short.  Host, device, host: the device frame is its
+    batch's last, so the meter keeps a copy of it (the tensor is overwritten once the batch has gone out).  The ordinary
+    records are a plain meter's byte for byte, and both kinds of record are the references'."""
+    from grav1synth_amd.estimate import NoiseLevelMeter
+
+    bd, n = 10, 3
+    frames = clip_frames(499, 36, bd, "420", seed=61, n=n)
+    assert -(-(499 - 1) // STRIP_COLS) == 2 and -(-(36 - 2) // STRIP_ROWS) == 2
+    m = NoiseLevelMeter(bd, batch_frames=2, temporal=True)
+    plain = NoiseLevelMeter(bd, batch_frames=2)
+    for k, planes in enumerate(frames):
+        handed = _to_dev(planes, bd) if k == 1 else [p.copy() for p in planes]
+        m.frame(handed, 1, 1)
+        plain.frame(planes, 1, 1)
+        if k == 1:
+            for p in handed:
+                p.fill_((1 << bd) - 1)
+    got, tgot, pgot = m.finish(), m.finish_temporal(), plain.finish()
+    assert len(got) == n and len(tgot) == n - 1 and len(pgot) == n
+    assert got.tobytes() == pgot.tobytes(), "the ordinary records are a plain meter's, byte for byte"
+    bad = []
+    for k in range(n):
+        bad += R.mismatches(got[k], R.nlf_frame(frames[k], bd, 1, 1), f"frame {k}")
+    for k, want in enumerate(T.run_records(frames, bd, 1, 1)):
+        bad += T.mismatches(tgot[k], want, f"pair {k}")
+    assert not bad, "\n".join(bad)
+    m.close()
+    plain.close()
+
+
 def test_capacity_a_geometry_change_a_cut_and_reuse():
     from grav1synth_amd.estimate import NLF_TRECORD, NoiseLevelMeter
 

@@ -328,6 +328,22 @@ def test_the_host_only_half_builds_with_a_host_compiler_and_has_the_headers_layo
     assert NLF_TRECORD.fields["s"][0].base == np.dtype("<i8")
 
 
+def test_the_file_commands_record_arithmetic_under_the_sanitizers(tmp_path):
+    """tests/nlf_file_host.cpp: a total taken batch by batch, and the total less the first frame's record."""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    exe = tmp_path / "nlf_file_host"
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
+           os.path.join(ROOT, "tests", "nlf_file_host.cpp")]
+    if subprocess.call(cmd + ["-static-libasan"], stderr=subprocess.DEVNULL) != 0:
+        subprocess.check_call(cmd)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    p = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert p.stdout.splitlines()[-1] == "ok"
+
+
 # ------------------------------------------------------------------------------------------------------------ refusals
 def test_no_gpu_means_the_temporal_meter_refuses():
     import torch
