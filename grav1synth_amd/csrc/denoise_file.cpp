@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "clip_file.h"
 #include "curve.h"
 #include "frame_op.h"
 #include "nlf.h"
@@ -24,13 +25,9 @@ extern "C" uint32_t g1s_denoise_temporal_radius_(const g1s_denoise_t *);
 extern "C" void g1s_denoise_levels_refusal_(const g1s_denoise_opts_t *, uint32_t coarse_levels, double coarse_ratio, char *err, size_t cap);
 
 using namespace g1s_op;
+using g1s_clip::refuse;
 
 namespace {
-
-int refuse(char *err, size_t cap, int code, const std::string &m) {
-  if (err && cap) snprintf(err, cap, "%s", m.c_str());
-  return code;
-}
 
 // what a file command takes beyond its paths and its opts: what the last rung of either ladder takes, with the values an
 // earlier rung stands for
@@ -58,22 +55,9 @@ struct Prior {
   std::vector<uint16_t> gain;  // m[256] then; else empty
   std::string load(const char *path, uint32_t range_, int32_t segment) {
     range = range_;
-    std::string text;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return std::string("grain prior: cannot open ") + path;
-    char buf[65536];
-    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
-    std::fclose(f);
-    size_t nseg = 0;
-    char perr[256] = "";
-    segs.resize(64);
-    int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-    if (rc == G1S_ERR_CAPACITY) {
-      segs.resize(nseg);
-      rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-    }
-    if (rc) return std::string("grain prior: ") + perr;
-    segs.resize(nseg);
+    std::string why;
+    if (g1s_clip::load_table(path, g1s_parse_tbl, segs, "grain prior: cannot open ", "grain prior: ", &why)) return why;
+    const size_t nseg = segs.size();
     if (segment >= 0 && (size_t)segment >= nseg)
       return "grain prior: segment " + std::to_string(segment) + " is not in the table (" + std::to_string(nseg) + " segments)";
     if (segment >= 0) segs = {segs[(size_t)segment]};
@@ -270,8 +254,6 @@ int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *
   uint64_t frames = 0, taken = 0, complete = 0;     // frames handed to the generator; to the denoiser; completed by it
   uint32_t D = 0, batch = 0;
   int rc = G1S_OK;
-  std::vector<g1s_segment_t> segs(64);
-  size_t nseg = 0;
 
   g = g1s_diff_new(info.fps_num, info.fps_den, info.bit_depth, info.bit_depth, opts);
   if (!g) {
@@ -337,16 +319,12 @@ int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *
         pairs.push_back(std::move(p)), k = pairs.size() - 1;
       }
       // the reader lends the frame until its next call: on the device before that
-      bool copied = true;
-      for (int c = 0; c < pg.nplanes; ++c)
-        copied = copied && hipMemcpy2D(pairs[k].src + lay.off[c], lay.row[c], fin.data[c], fin.stride_bytes[c], lay.row[c], pg.ph(c), hipMemcpyHostToDevice) == hipSuccess;
-      if (!copied) {
+      const g1s_frame_t s = device_frame(pg, lay, pairs[k].src);
+      g1s_frame_t d = device_frame(pg, lay, pairs[k].den);
+      if (!upload_frame(fin, s)) {
         rc = G1S_ERR_HIP, why = "copy of a source frame to the device failed";
         break;
       }
-      g1s_frame_t s = fin, d = fin;
-      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
-      s.on_device = d.on_device = 1;
       rc = g1s_denoise_frame(dn, &s, &d);
       if (rc) {
         why = "frame " + std::to_string(taken) + ": denoise: " + g1s_denoise_last_error(dn);
@@ -366,11 +344,7 @@ int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *
     while (frames < complete) {
       const size_t k = held.front();
       held.pop_front();
-      g1s_frame_t s{}, d{};
-      s.width = info.width, s.height = info.height, s.bytes_per_sample = info.bit_depth > 8 ? 2 : 1, s.xdec = (uint8_t)info.xdec, s.ydec = (uint8_t)info.ydec,
-      s.nplanes = (uint8_t)info.nplanes, s.on_device = 1;
-      d = s;
-      lay.point(s, pairs[k].src, pg.nplanes), lay.point(d, pairs[k].den, pg.nplanes);
+      const g1s_frame_t s = device_frame(pg, lay, pairs[k].src), d = device_frame(pg, lay, pairs[k].den);
       rc = g1s_diff_frame(g, &s, &d);
       if (rc) {
         why = "frame " + std::to_string(frames) + ": diff_frame: " + g1s_diff_last_error(g);
@@ -388,17 +362,8 @@ int diff_y4m_file_denoised(const char *source, const char *out_tbl, const char *
     if (const uint32_t inside = g1s_diff_frames_in_flight_max_(g)) pair_cap = std::max(pair_cap, (size_t)batch + inside + inside / 4 + 2 * D);
   }
   if (rc) goto done;
-  rc = g1s_diff_finish(g, segs.data(), segs.size(), &nseg);
-  if (rc == G1S_ERR_CAPACITY) {
-    segs.resize(nseg);
-    rc = g1s_diff_finish(g, segs.data(), segs.size(), &nseg);
-  }
-  if (rc) {
-    why = g1s_diff_last_error(g);
-    goto done;
-  }
-  rc = g1s_write_tbl(out_tbl, segs.data(), nseg);
-  if (rc) why = std::string("cannot write ") + out_tbl;
+  rc = g1s_clip::write_table(
+      out_tbl, [&](g1s_segment_t *out, size_t cap_, size_t *n) { return g1s_diff_finish(g, out, cap_, n); }, [&] { return g1s_diff_last_error(g); }, &why);
 done:
   if (fk && std::fclose(fk) != 0 && !rc) rc = G1S_ERR_INVALID, why = std::string("cannot write ") + keep_denoised;
   if (dn) g1s_denoise_free(dn);

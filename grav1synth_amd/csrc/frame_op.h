@@ -1,12 +1,14 @@
 // frame_op.h -- the host scaffold the frame operations share.  Who uses what: render (grain.hip), denoise (denoise.hip),
 // measure (measure.hip), the noise levels (nlf.hip) and the surface converter (surface.hip) are BatchedOp's; the estimator
 // (estimate.hip: its copies are synchronous) takes the owners, pick_device, open_stream and batch_of, the generator
-// (engine.hip) the owners and the addressing predicate; of the file commands grain.hip's and denoise_file.cpp's go through
-// rewrite_y4m, nlf_file.cpp takes batch_of alone.  Host code only.  The first part -- the batch clamp,
+// (engine.hip) the owners and the addressing predicate; of the file commands grain_file.cpp's and denoise_file.cpp's go
+// through rewrite_y4m, measure_file.cpp and denoise_file.cpp take device_frame and upload_frame, nlf_file.cpp batch_of alone
+// (what the file commands share among themselves is clip_file.h).  Host code only.  The first part -- the batch clamp,
 // plane geometry, the two layouts of a frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP
 // and builds with a host compiler alone (measure_report.cpp, which needs a chroma plane's size and nothing else of this,
 // has it as a local helper and does not include this file); the second part, under __HIPCC__, is the owners of HIP objects,
-// the TRY macro and the base of a batched operation with its parameter sets, its staging buffers and the .y4m rewrite loop.
+// the TRY macro, the base of a batched operation with its parameter sets and its staging buffers, a driver's device frames
+// and the .y4m rewrite loop.
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +18,7 @@
 #include <utility>
 
 #include "../../include/g1s_diff.h"
+#include "clip_file.h"
 
 // (host_abi.cpp) the text g1s_last_global_error() returns on this thread: what a *_new call that returns NULL sets
 extern "C" void g1s_set_global_error_(const char *);
@@ -290,6 +293,42 @@ inline HostPlanes host_planes(const g1s_surface_t &f) {
   return h;
 }
 
+// The device copies of host frames (Geom = PlaneGeom) or host surfaces (SurfaceGeom, whose interleaved plane has rows of
+// 2 cw samples) of one geometry: two input rings (the second for an operation that takes two frames a call) and an output
+// buffer, each a number of slots of the staging layout, made when the first host frame needs them.
+template <class Geom>
+struct Staging {
+  Geom geom;
+  Layout lay;
+  DevBuf<uint8_t> in[2], out;  // (after set(): sized again when they are next needed)
+  void set(const Geom &g) { geom = g, lay = staging_layout(g), in[0] = DevBuf<uint8_t>(), in[1] = DevBuf<uint8_t>(), out = DevBuf<uint8_t>(); }
+  // Where the kernels read `src` (a frame or a surface): the caller's device planes, or slot `slot` of input ring `ring` of
+  // `slots` slots, the copies queued on the stream.  Null when fine, else what failed.
+  template <class Src>
+  const char *stage_in(const Src &src, uint32_t slot, uint32_t slots, int ring, hipStream_t stream, const uint8_t *plane[3], uint32_t stride[3]) {
+    const bool theirs = src.on_device == 1;
+    if (!theirs && !in[ring] && hipMalloc((void **)&in[ring].p, lay.frame * slots) != hipSuccess) return "hipMalloc of the input staging buffer failed";
+    for (int c = 0; c < geom.nplanes; ++c) {
+      uint8_t *dst = theirs ? nullptr : in[ring] + lay.frame * slot + lay.off[c];
+      if (!theirs && hipMemcpy2DAsync(dst, lay.row[c], src.data[c], src.stride_bytes[c], geom.row_bytes(c), geom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
+        return "copy of an input plane to the device failed";
+      plane[c] = theirs ? static_cast<const uint8_t *>(src.data[c]) : dst, stride[c] = (uint32_t)(theirs ? src.stride_bytes[c] : lay.row[c]);
+    }
+    return nullptr;
+  }
+  const char *need_out(uint32_t slots) {
+    return !out && hipMalloc((void **)&out.p, lay.frame * slots) != hipSuccess ? "hipMalloc of the output staging buffer failed" : nullptr;
+  }
+  uint8_t *out_plane(uint32_t slot, int c) const { return out + lay.frame * slot + lay.off[c]; }
+  // slot `slot` of the output buffer back to the host planes, behind what the stream holds
+  hipError_t copy_back(uint32_t slot, const HostPlanes &h, hipStream_t stream) const {
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < geom.nplanes && e == hipSuccess; ++c)
+      e = hipMemcpy2DAsync(h.data[c], h.stride[c], out_plane(slot, c), lay.row[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToHost, stream);
+    return e;
+  }
+};
+
 // The base of an operation that takes frames one at a time and launches them a batch at a time on a stream of its own.
 // (The stream comes first: it goes last, after the wait in *_free and after everything that was used on it.)
 struct BatchedOp {
@@ -303,18 +342,16 @@ struct BatchedOp {
   // batch that read it has passed -- the next batch is filled while this one runs
   Event done[2];
   uint64_t batches = 0;
-  // the geometry of the frames so far and the device copies of host frames: an input ring (a second one for an operation
-  // that takes two frames a call) and an output buffer, made when the first such frame comes, each a number of slots of
-  // the staging layout
+  // the geometry of the frames so far and the device copies of host frames, made when the first such frame comes; beside
+  // them the surface side of a converter (surface.hip), set after the frame's.  `geom`, `stage`, `sgeom` and `sstage` are
+  // the names the operations know the two geometries and staging layouts by
   bool have_geom = false;
-  PlaneGeom geom;
-  Layout stage;
-  DevBuf<uint8_t> d_stage_in[2], d_stage_out;
-  // the surface side of a converter (surface.hip), set beside the frame's: its planes and their staging layout; a host
-  // surface that comes in takes input ring 0, one that goes out the output buffer, in the surface's layout
-  SurfaceGeom sgeom;
-  Layout sstage;
-
+  Staging<PlaneGeom> frames;
+  Staging<SurfaceGeom> surfaces;
+  PlaneGeom &geom = frames.geom;
+  Layout &stage = frames.lay;
+  SurfaceGeom &sgeom = surfaces.geom;
+  Layout &sstage = surfaces.lay;
   int fail(int code, const std::string &m) {
     if (!err_code) err_code = code, err = m;  // sticky: the first failure is the one reported from then on
     return err_code;
@@ -336,78 +373,28 @@ struct BatchedOp {
     G1S_OP_TRY(hipEventRecord(done[set], stream));
     return G1S_OK;
   }
-  // (a new geometry: nothing may be in flight; the staging buffers are sized again when they are next needed)
-  void set_frame_geometry(const g1s_frame_t &f) {
-    geom = PlaneGeom(f, bps), stage = staging_layout(geom), have_geom = true;
-    d_stage_in[0] = DevBuf<uint8_t>(), d_stage_in[1] = DevBuf<uint8_t>(), d_stage_out = DevBuf<uint8_t>();
-  }
-  // Where the kernels read `in`: the caller's device planes, or slot `slot` of input ring `ring` of `slots` slots, the copies
-  // queued on the stream.  Host planes are read before the call returns (wait_host_input); pinned planes are queued.
+  // (a new geometry: nothing may be in flight; the surface's comes after the frame's it corresponds to)
+  void set_frame_geometry(const g1s_frame_t &f) { frames.set(PlaneGeom(f, bps)), have_geom = true; }
+  void set_surface_geometry(const g1s_surface_t &s) { surfaces.set(SurfaceGeom(s, bps)); }
+  // Staging's five, for a frame and for a surface: a host frame takes input ring `ring`, a host surface ring 0
+  int staged(const char *no) { return no ? fail(G1S_ERR_HIP, no) : G1S_OK; }
   int stage_in(const g1s_frame_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3], int ring = 0) {
-    for (int c = 0; c < geom.nplanes; ++c) {
-      if (in.on_device == 1) {
-        plane[c] = static_cast<const uint8_t *>(in.data[c]), stride[c] = (uint32_t)in.stride_bytes[c];
-        continue;
-      }
-      if (!d_stage_in[ring] && hipMalloc((void **)&d_stage_in[ring].p, stage.frame * slots) != hipSuccess)
-        return fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
-      uint8_t *dst = d_stage_in[ring] + stage.frame * slot + stage.off[c];
-      if (hipMemcpy2DAsync(dst, stage.row[c], in.data[c], in.stride_bytes[c], geom.row_bytes(c), geom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
-      plane[c] = dst, stride[c] = (uint32_t)stage.row[c];
-    }
-    return G1S_OK;
+    return staged(frames.stage_in(in, slot, slots, ring, stream, plane, stride));
   }
-  int wait_host_input(const g1s_frame_t &in) {
-    if (in.on_device == 0 && hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, "copy of a host frame to the device failed");
-    return G1S_OK;
-  }
-  // (after set_frame_geometry of the frame the surface corresponds to)
-  void set_surface_geometry(const g1s_surface_t &s) { sgeom = SurfaceGeom(s, bps), sstage = staging_layout(sgeom); }
-  // stage_in for a surface: the interleaved plane's rows are 2 cw samples long
   int stage_in(const g1s_surface_t &in, uint32_t slot, uint32_t slots, const uint8_t *plane[3], uint32_t stride[3]) {
-    for (int c = 0; c < sgeom.nplanes; ++c) {
-      if (in.on_device == 1) {
-        plane[c] = static_cast<const uint8_t *>(in.data[c]), stride[c] = (uint32_t)in.stride_bytes[c];
-        continue;
-      }
-      if (!d_stage_in[0] && hipMalloc((void **)&d_stage_in[0].p, sstage.frame * slots) != hipSuccess)
-        return fail(G1S_ERR_HIP, "hipMalloc of the input staging buffer failed");
-      uint8_t *dst = d_stage_in[0] + sstage.frame * slot + sstage.off[c];
-      if (hipMemcpy2DAsync(dst, sstage.row[c], in.data[c], in.stride_bytes[c], sgeom.row_bytes(c), sgeom.ph(c), hipMemcpyHostToDevice, stream) != hipSuccess)
-        return fail(G1S_ERR_HIP, "copy of an input plane to the device failed");
-      plane[c] = dst, stride[c] = (uint32_t)sstage.row[c];
-    }
-    return G1S_OK;
+    return staged(surfaces.stage_in(in, slot, slots, 0, stream, plane, stride));
   }
-  int wait_host_input(const g1s_surface_t &in) {
-    if (in.on_device == 0 && hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, "copy of a host surface to the device failed");
-    return G1S_OK;
-  }
-  int need_stage_out(uint32_t slots) {
-    if (!d_stage_out && hipMalloc((void **)&d_stage_out.p, stage.frame * slots) != hipSuccess)
-      return fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
-    return G1S_OK;
-  }
-  uint8_t *stage_out(uint32_t slot, int c) const { return d_stage_out + stage.frame * slot + stage.off[c]; }
-  // slot `slot` of the output buffer back to the host planes, behind what the stream holds
-  int copy_back(uint32_t slot, const HostPlanes &h) {
-    for (int c = 0; c < geom.nplanes; ++c)
-      G1S_OP_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], stage_out(slot, c), stage.row[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToHost, stream));
-    return G1S_OK;
-  }
-  // the output buffer in the surface's layout, and a slot of it back to a host surface's planes
-  int need_surface_stage_out(uint32_t slots) {
-    if (!d_stage_out && hipMalloc((void **)&d_stage_out.p, sstage.frame * slots) != hipSuccess)
-      return fail(G1S_ERR_HIP, "hipMalloc of the output staging buffer failed");
-    return G1S_OK;
-  }
-  uint8_t *surface_stage_out(uint32_t slot, int c) const { return d_stage_out + sstage.frame * slot + sstage.off[c]; }
-  int copy_back_surface(uint32_t slot, const HostPlanes &h) {
-    for (int c = 0; c < sgeom.nplanes; ++c)
-      G1S_OP_TRY(hipMemcpy2DAsync(h.data[c], h.stride[c], surface_stage_out(slot, c), sstage.row[c], sgeom.row_bytes(c), sgeom.ph(c), hipMemcpyDeviceToHost, stream));
-    return G1S_OK;
-  }
+  // host planes are read before the call that brought them returns; pinned planes stay queued
+  int wait_host_input(int on_device, const char *text) { return on_device == 0 && hipStreamSynchronize(stream) != hipSuccess ? fail(G1S_ERR_HIP, text) : G1S_OK; }
+  int wait_host_input(const g1s_frame_t &in) { return wait_host_input(in.on_device, "copy of a host frame to the device failed"); }
+  int wait_host_input(const g1s_surface_t &in) { return wait_host_input(in.on_device, "copy of a host surface to the device failed"); }
+  int need_stage_out(uint32_t slots) { return staged(frames.need_out(slots)); }
+  int need_surface_stage_out(uint32_t slots) { return staged(surfaces.need_out(slots)); }
+  uint8_t *stage_out(uint32_t slot, int c) const { return frames.out_plane(slot, c); }
+  uint8_t *surface_stage_out(uint32_t slot, int c) const { return surfaces.out_plane(slot, c); }
+  int copied_back(hipError_t e) { return e == hipSuccess ? G1S_OK : fail(G1S_ERR_HIP, std::string("hipMemcpy2DAsync of an output plane to the host failed: ") + hipGetErrorString(e)); }
+  int copy_back(uint32_t slot, const HostPlanes &h) { return copied_back(frames.copy_back(slot, h, stream)); }
+  int copy_back_surface(uint32_t slot, const HostPlanes &h) { return copied_back(surfaces.copy_back(slot, h, stream)); }
   int wait() {
     if (hipStreamSynchronize(stream) != hipSuccess) return fail(G1S_ERR_HIP, std::string("hipStreamSynchronize failed: ") + hipGetErrorString(hipGetLastError()));
     return G1S_OK;
@@ -423,6 +410,23 @@ void free_op(Op *g) {
   delete g;
 }
 
+// A file driver's own device frames: a frame of geometry g whose planes lie from `base` on in layout `lay` ...
+inline g1s_frame_t device_frame(const PlaneGeom &g, const Layout &lay, uint8_t *base) {
+  g1s_frame_t f{};
+  f.width = (uint32_t)g.W, f.height = (uint32_t)g.H, f.bytes_per_sample = (uint8_t)g.bps, f.xdec = (uint8_t)g.subx, f.ydec = (uint8_t)g.suby;
+  f.nplanes = (uint8_t)g.nplanes, f.on_device = 1;
+  lay.point(f, base, g.nplanes);
+  return f;
+}
+// ... and a host frame of its shape (a reader lends one until its next call) copied into it before the call returns
+inline bool upload_frame(const g1s_frame_t &host, const g1s_frame_t &dev) {
+  const PlaneGeom g(dev, dev.bytes_per_sample);
+  bool ok = true;
+  for (int c = 0; c < g.nplanes; ++c)
+    ok = ok && hipMemcpy2D(const_cast<void *>(dev.data[c]), dev.stride_bytes[c], host.data[c], host.stride_bytes[c], g.row_bytes(c), g.ph(c), hipMemcpyHostToDevice) == hipSuccess;
+  return ok;
+}
+
 // A .y4m file through an operation into another .y4m file: the header line as it came, every frame handed over as a host
 // frame with a slot of a pinned ring of packed frames as its output, and after every `batch` frames and at the end the
 // completed frames written out.  `Driver` says what differs:
@@ -434,11 +438,8 @@ void free_op(Op *g) {
 // Returns the number of frames, or the code of what went wrong with its text in err.
 template <class Driver>
 int64_t rewrite_y4m(const char *in, const char *out, char *err, size_t cap, Driver &&op) {
-  auto refuse = [&](int code, const std::string &m) -> int64_t {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (!in || !out) return refuse(G1S_ERR_INVALID, "null path");
+  using g1s_clip::refuse;
+  if (!in || !out) return refuse(err, cap, G1S_ERR_INVALID, "null path");
   const std::string header = y4m_header_line(in);
   g1s_y4m_t *y = g1s_y4m_open(in, err, cap);
   if (!y) return G1S_ERR_INVALID;
@@ -446,13 +447,13 @@ int64_t rewrite_y4m(const char *in, const char *out, char *err, size_t cap, Driv
   g1s_y4m_get_info(y, &info);
   if (!op.open(info)) {
     g1s_y4m_close(y);
-    return refuse(op.new_failed, g1s_last_global_error());
+    return refuse(err, cap, op.new_failed, g1s_last_global_error());
   }
   FILE *fo = std::fopen(out, "wb");
   if (!fo) {
     op.close();
     g1s_y4m_close(y);
-    return refuse(G1S_ERR_INVALID, std::string("cannot create ") + out);
+    return refuse(err, cap, G1S_ERR_INVALID, std::string("cannot create ") + out);
   }
   const Layout lay = packed_layout(PlaneGeom(info));
   const uint32_t batch = op.batch(), ring = op.ring();
@@ -502,7 +503,7 @@ int64_t rewrite_y4m(const char *in, const char *out, char *err, size_t cap, Driv
   if (std::fclose(fo) != 0 && ok) ok = false, rc = G1S_ERR_INVALID, why = std::string("cannot write ") + out;
   op.close();
   g1s_y4m_close(y);
-  if (!ok) return refuse(rc ? rc : G1S_ERR_INVALID, why);
+  if (!ok) return refuse(err, cap, rc ? rc : G1S_ERR_INVALID, why);
   return frames;
 }
 

@@ -11,11 +11,11 @@
 //                every sample of the stripe's luma and chroma rows read once and written once, 8 samples a lane and turn.
 //
 // kg_apply reads `in` and writes `out`, which must not overlap: chroma is scaled by the co-located input luma.
+// The file command (`render`) stands above the per-frame calls in grain_file.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -23,7 +23,6 @@
 
 #include "../../include/g1s_diff.h"
 #include "av1_gaussian_sequence.h"
-#include "fold.h"
 #include "frame_op.h"
 
 namespace {
@@ -723,52 +722,5 @@ int g1s_grain_set_timing(g1s_grain_t *g, int enable, double *ms_template, double
 const char *g1s_grain_last_error(const g1s_grain_t *g) { return g ? g->err.c_str() : ""; }
 
 void g1s_grain_free(g1s_grain_t *g) { free_op(g); }
-
-int64_t g1s_grain_y4m_file(const char *in, const char *tbl, const char *out, const g1s_grain_opts_t *opts, char *err, size_t cap) {
-  auto refuse = [&](int code, const std::string &m) -> int64_t {
-    if (err && cap) snprintf(err, cap, "%s", m.c_str());
-    return code;
-  };
-  if (!in || !tbl || !out) return refuse(G1S_ERR_INVALID, "null path");
-  // the table
-  std::string text;
-  {
-    FILE *f = std::fopen(tbl, "rb");
-    if (!f) return refuse(G1S_ERR_INVALID, std::string("cannot open ") + tbl);
-    char buf[65536];
-    size_t n;
-    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-    std::fclose(f);
-  }
-  size_t nseg = 0;
-  char perr[256] = "";
-  std::vector<g1s_segment_t> segs(64);
-  int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-  if (rc == G1S_ERR_CAPACITY) {
-    segs.resize(nseg);
-    rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-  }
-  if (rc) return refuse(rc, std::string("grain table: ") + perr);
-  // a batch of output frames in pinned memory: rendered, waited for (everything handed over is then complete), written
-  struct Driver {
-    const g1s_grain_opts_t *opts;
-    std::vector<g1s_segment_t> &segs;
-    size_t nseg;
-    g1s_y4m_info_t info{};
-    g1s_grain_t *g = nullptr;
-    const int new_failed = G1S_ERR_NO_DEVICE;
-    bool open(const g1s_y4m_info_t &i) { return info = i, (g = g1s_grain_new(i.bit_depth, opts)) != nullptr; }
-    uint32_t batch() const { return g->batch; }
-    uint32_t ring() const { return g->batch; }
-    int frame(int64_t n, const g1s_frame_t *fin, g1s_frame_t *fout) {
-      const long si = g1s_tbl_segment_for(segs.data(), nseg, g1s::frame_time((uint64_t)n, info.fps_num, info.fps_den));
-      return g1s_grain_frame(g, si < 0 ? nullptr : &segs[(size_t)si], fin, fout);
-    }
-    int drain(bool, uint64_t *) { return g1s_grain_sync(g); }
-    const char *last_error() const { return g1s_grain_last_error(g); }
-    void close() { g1s_grain_free(g); }
-  };
-  return rewrite_y4m(in, out, err, cap, Driver{opts, segs, nseg});
-}
 
 }  // extern "C"

@@ -21,13 +21,11 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "clip_file.h"
+
+using g1s_clip::refuse;
 
 namespace {
-
-void set_err(char *err, size_t cap, const std::string &msg) {
-  if (!err || !cap) return;
-  std::snprintf(err, cap, "%s", msg.c_str());
-}
 
 struct PinnedBuf {
   uint8_t *p = nullptr;
@@ -61,6 +59,22 @@ static const int kReadThreads = [] {
   const int n = e ? atoi(e) : 3;  // (measured: 1 -> 22, 2 -> 25..32, 3 -> 31, 4 -> 28, 8 -> 26 GB/s through two readers)
   return n < 1 ? 1 : (n > kMaxReadThreads ? kMaxReadThreads : n);
 }();
+
+// what both `diff` file commands start from: the filter chain (src/main.rs:370-380: "Invalid filter chain: {e}", nothing is
+// opened), then the two readers; the chain goes, and the readers close, when the command returns
+struct DiffInputs {
+  g1s_filters_t *filters = nullptr;
+  g1s_clip::TwoClips clips;
+  ~DiffInputs() { g1s_filters_free(filters); }
+  // false: refused, the text in err
+  bool open(const char *filter_text, const char *source_path, const char *denoised_path, char *err, size_t errcap) {
+    if (filter_text && *filter_text) {
+      char ferr[256] = "";
+      if (!(filters = g1s_filters_new(filter_text, ferr, sizeof(ferr)))) return refuse(err, errcap, G1S_ERR_INVALID, std::string("Invalid filter chain: ") + ferr), false;
+    }
+    return clips.open(source_path, denoised_path, err, errcap);
+  }
+};
 
 }  // namespace
 
@@ -163,18 +177,18 @@ extern "C" {
 
 g1s_y4m_t *g1s_y4m_open(const char *path, char *err, size_t errcap) {
   if (!path) {
-    set_err(err, errcap, "y4m: null path");
+    refuse(err, errcap, G1S_ERR_INVALID, "y4m: null path");
     return nullptr;
   }
   FILE *f = std::fopen(path, "rb");
   if (!f) {
-    set_err(err, errcap, std::string("y4m: cannot open ") + path);
+    refuse(err, errcap, G1S_ERR_INVALID, std::string("y4m: cannot open ") + path);
     return nullptr;
   }
   char hdr[1024];
   if (!std::fgets(hdr, sizeof hdr, f) || std::strncmp(hdr, "YUV4MPEG2", 9) != 0) {
     std::fclose(f);
-    set_err(err, errcap, std::string("y4m: not a YUV4MPEG2 stream: ") + path);
+    refuse(err, errcap, G1S_ERR_INVALID, std::string("y4m: not a YUV4MPEG2 stream: ") + path);
     return nullptr;
   }
   g1s_y4m_info_t info{};
@@ -219,13 +233,13 @@ g1s_y4m_t *g1s_y4m_open(const char *path, char *err, size_t errcap) {
     else if (base.compare(0, 3, "444") == 0) info.xdec = 0, info.ydec = 0;
     else {
       std::fclose(f);
-      set_err(err, errcap, "y4m: unsupported colour space C" + cs);
+      refuse(err, errcap, G1S_ERR_INVALID, "y4m: unsupported colour space C" + cs);
       return nullptr;
     }
   }
   if (info.width == 0 || info.height == 0 || info.bit_depth < 8 || info.bit_depth > 16) {
     std::fclose(f);
-    set_err(err, errcap, "y4m: bad header (size or bit depth)");
+    refuse(err, errcap, G1S_ERR_INVALID, "y4m: bad header (size or bit depth)");
     return nullptr;
   }
   g1s_y4m *y = new g1s_y4m;
@@ -246,7 +260,7 @@ g1s_y4m_t *g1s_y4m_open(const char *path, char *err, size_t errcap) {
   for (auto &b : y->ring) {
     b.alloc(y->frame_bytes);
     if (!b.p) {
-      set_err(err, errcap, "y4m: out of memory");
+      refuse(err, errcap, G1S_ERR_INVALID, "y4m: out of memory");
       g1s_y4m_close(y);
       return nullptr;
     }
@@ -364,16 +378,14 @@ int g1s_diff_run_filtered(g1s_diff_t *g, g1s_next_frame_fn source, void *source_
     // get_filtered_frame_pair (src/main.rs:615-629): one frame from each reader, source first; the filter chain on
     // the source frame only
     g1s_frame_t s, d;
-    const int rs = source(source_user, &s);
-    const int rd = denoised(denoised_user, &d);
-    if (rs < 0 || rd < 0) {
-      rc = rs < 0 ? rs : rd;
-      note(std::string(rs < 0 ? "source" : "denoised") + " reader failed");
+    const g1s_clip::PairRead pair = g1s_clip::next_pair(source, source_user, denoised, denoised_user, &s, &d);
+    if (pair.got < 0) {
+      rc = pair.got;
+      note(std::string(pair.side()) + " reader failed");
       break;
     }
-    if (rs == 0 && rd == 0) break;  // (None, None)
-    if (rs == 0 || rd == 0) {       // "Videos did not have equal frame counts. Resulting grain table may
-      unequal = 1;                  //  not be as expected." -- a warning, then the loop ends (src/main.rs:449-455)
+    if (!pair.got) {  // (None, None), or one alone: "Videos did not have equal frame counts. Resulting grain table may not be
+      unequal = pair.unequal;  // as expected." -- a warning, then the loop ends (src/main.rs:449-455)
       break;
     }
     if (filters) {
@@ -429,35 +441,17 @@ int g1s_diff_y4m_files(const char *source_path, const char *denoised_path, const
 int g1s_diff_y4m_files_filtered(const char *source_path, const char *denoised_path, const char *out_tbl_path,
                                 const g1s_opts_t *opts, const char *filter_text, uint64_t *frames_out, int *unequal_out,
                                 char *err, size_t errcap) {
-  g1s_filters_t *filters = nullptr;
-  if (filter_text && *filter_text) {  // src/main.rs:370-380: "Invalid filter chain: {e}", nothing is opened
-    char ferr[256] = "";
-    filters = g1s_filters_new(filter_text, ferr, sizeof(ferr));
-    if (!filters) {
-      set_err(err, errcap, std::string("Invalid filter chain: ") + ferr);
-      return G1S_ERR_INVALID;
-    }
-  }
-  g1s_y4m_t *ys = g1s_y4m_open(source_path, err, errcap);
-  if (!ys) {
-    g1s_filters_free(filters);
-    return G1S_ERR_INVALID;
-  }
-  g1s_y4m_t *yd = g1s_y4m_open(denoised_path, err, errcap);
-  if (!yd) {
-    g1s_y4m_close(ys);
-    g1s_filters_free(filters);
-    return G1S_ERR_INVALID;
-  }
+  DiffInputs in;
+  if (!in.open(filter_text, source_path, denoised_path, err, errcap)) return G1S_ERR_INVALID;
+  g1s_y4m_t *const ys = in.clips.a, *const yd = in.clips.b;
+  g1s_filters_t *const filters = in.filters;
   int rc = G1S_OK;
   g1s_diff_t *g = nullptr;
-  std::vector<g1s_segment_t> segs(64);
-  size_t n = 0;
+  std::string why;
   // the frame rate and the bit depths come from the readers (src/main.rs:414-427)
   g = g1s_diff_new(ys->info.fps_num, ys->info.fps_den, ys->info.bit_depth, yd->info.bit_depth, opts);
   if (!g) {
-    set_err(err, errcap, g1s_last_global_error());
-    rc = G1S_ERR_NO_DEVICE;
+    rc = refuse(err, errcap, G1S_ERR_NO_DEVICE, g1s_last_global_error());
     goto done;
   }
   // the readers' pinned rings feed the generator directly: copies are queued, the loop goes on reading
@@ -471,26 +465,16 @@ int g1s_diff_y4m_files_filtered(const char *source_path, const char *denoised_pa
     std::string e = g1s_diff_last_error(g);  // "frame N: ..."
     if (ys->failed) e += " (" + ys->error + ")";
     else if (yd->failed) e += " (" + yd->error + ")";
-    set_err(err, errcap, e);
+    refuse(err, errcap, rc, e);
     goto done;
   }
-  rc = g1s_diff_finish(g, segs.data(), segs.size(), &n);
-  if (rc == G1S_ERR_CAPACITY) {  // more scene cuts than the first guess: the segments are still there, ask again
-    segs.resize(n);
-    rc = g1s_diff_finish(g, segs.data(), segs.size(), &n);
-  }
-  if (rc) {
-    set_err(err, errcap, g1s_diff_last_error(g));
-    goto done;
-  }
-  rc = g1s_write_tbl(out_tbl_path, segs.data(), n);
-  if (rc) set_err(err, errcap, std::string("cannot write ") + out_tbl_path);
+  // (more scene cuts than the first guess: the segments are still there, asked for again)
+  rc = g1s_clip::write_table(
+      out_tbl_path, [&](g1s_segment_t *out, size_t cap, size_t *n) { return g1s_diff_finish(g, out, cap, n); }, [&] { return g1s_diff_last_error(g); }, &why);
+  if (rc) refuse(err, errcap, rc, why);
 done:
-  g1s_filters_free(filters);
   if (g) g1s_diff_free(g);
-  g1s_y4m_close(ys);
-  g1s_y4m_close(yd);
-  return rc;
+  return rc;  // (the readers close behind the generator that their pinned rings fed)
 }
 
 
@@ -503,30 +487,11 @@ done:
 int g1s_diff_y4m_files_sharded(const char *source_path, const char *denoised_path, const char *out_tbl_path,
                                const g1s_opts_t *opts, const char *filter_text, const int32_t *devices, uint32_t n_devices,
                                uint64_t *frames_out, int *unequal_out, char *err, size_t errcap) {
-  if (!devices || n_devices == 0) {
-    set_err(err, errcap, "no devices");
-    return G1S_ERR_INVALID;
-  }
-  g1s_filters_t *filters = nullptr;
-  if (filter_text && *filter_text) {
-    char ferr[256] = "";
-    filters = g1s_filters_new(filter_text, ferr, sizeof(ferr));
-    if (!filters) {
-      set_err(err, errcap, std::string("Invalid filter chain: ") + ferr);
-      return G1S_ERR_INVALID;
-    }
-  }
-  g1s_y4m_t *ys = g1s_y4m_open(source_path, err, errcap);
-  if (!ys) {
-    g1s_filters_free(filters);
-    return G1S_ERR_INVALID;
-  }
-  g1s_y4m_t *yd = g1s_y4m_open(denoised_path, err, errcap);
-  if (!yd) {
-    g1s_y4m_close(ys);
-    g1s_filters_free(filters);
-    return G1S_ERR_INVALID;
-  }
+  if (!devices || n_devices == 0) return refuse(err, errcap, G1S_ERR_INVALID, "no devices");
+  DiffInputs in;
+  if (!in.open(filter_text, source_path, denoised_path, err, errcap)) return G1S_ERR_INVALID;
+  g1s_y4m_t *const ys = in.clips.a, *const yd = in.clips.b;
+  g1s_filters_t *const filters = in.filters;
   const uint32_t N = n_devices;
   g1s_opts_t o{};
   o.struct_size = sizeof(g1s_opts_t);
@@ -546,34 +511,27 @@ int g1s_diff_y4m_files_sharded(const char *source_path, const char *denoised_pat
   g1s_fold_t *fold = nullptr;
   const size_t msg_bytes = g1s_shard_msg_size(o.ar_coeff_lag, B);
   std::vector<uint8_t> msgs(msg_bytes * N);
-  std::vector<g1s_segment_t> segs(64);
-  size_t n = 0;
+  std::string why;
   bool ended = false;
   auto round = [&](int flush) -> int {  // every generator's message of the round, merged in global batch order
     for (uint32_t r = 0; r < N; ++r) {
       const int prc = g1s_shard_pack(gen[r], flush, msgs.data() + (size_t)r * msg_bytes, msg_bytes);
-      if (prc) {
-        set_err(err, errcap, std::string("generator ") + std::to_string(r) + ": " + g1s_diff_last_error(gen[r]));
-        return prc;
-      }
+      if (prc) return refuse(err, errcap, prc, std::string("generator ") + std::to_string(r) + ": " + g1s_diff_last_error(gen[r]));
     }
     const int mrc = g1s_shard_merge(fold, msgs.data(), msg_bytes, N);
-    if (mrc) set_err(err, errcap, std::string("merge: ") + g1s_fold_last_error(fold));
-    return mrc;
+    return mrc ? refuse(err, errcap, mrc, std::string("merge: ") + g1s_fold_last_error(fold)) : mrc;
   };
   for (uint32_t r = 0; r < N; ++r) {
     o.device = devices[r];
     gen[r] = g1s_diff_new(ys->info.fps_num, ys->info.fps_den, ys->info.bit_depth, yd->info.bit_depth, &o);
     if (!gen[r]) {
-      set_err(err, errcap, std::string("device ") + std::to_string(devices[r]) + ": " + g1s_last_global_error());
-      rc = G1S_ERR_NO_DEVICE;
+      rc = refuse(err, errcap, G1S_ERR_NO_DEVICE, std::string("device ") + std::to_string(devices[r]) + ": " + g1s_last_global_error());
       goto done;
     }
   }
   fold = g1s_fold_new(ys->info.fps_num, ys->info.fps_den, o.ar_coeff_lag);
   if (!fold) {
-    set_err(err, errcap, "g1s_fold_new failed");
-    rc = G1S_ERR_INVALID;
+    rc = refuse(err, errcap, G1S_ERR_INVALID, "g1s_fold_new failed");
     goto done;
   }
   // rounds: generator r takes batch (round * N + r) of the video -- B frame pairs read from the two files -- then every
@@ -582,15 +540,13 @@ int g1s_diff_y4m_files_sharded(const char *source_path, const char *denoised_pat
     for (uint32_t r = 0; r < N && !ended && rc == G1S_OK; ++r) {
       for (uint32_t i = 0; i < B; ++i) {
         g1s_frame_t s, d;
-        const int rs = g1s_y4m_next(ys, &s), rd = g1s_y4m_next(yd, &d);
-        if (rs < 0 || rd < 0) {
-          rc = rs < 0 ? rs : rd;
-          set_err(err, errcap, "frame " + std::to_string(frames) + ": " + (rs < 0 ? "source" : "denoised") + " reader failed (" +
-                                   (rs < 0 ? ys->error : yd->error) + ")");
+        const g1s_clip::PairRead pair = g1s_clip::next_pair(g1s_y4m_next, ys, g1s_y4m_next, yd, &s, &d);
+        if (pair.got < 0) {
+          rc = refuse(err, errcap, pair.got, "frame " + std::to_string(frames) + ": " + pair.side() + " reader failed (" + in.clips.last_error(pair) + ")");
           break;
         }
-        if (rs == 0 || rd == 0) {  // (None, None), or the warning of src/main.rs:449-455
-          unequal = (rs == 0) != (rd == 0);
+        if (!pair.got) {  // (None, None), or the warning of src/main.rs:449-455
+          unequal = pair.unequal;
           ended = true;
           break;
         }
@@ -598,20 +554,19 @@ int g1s_diff_y4m_files_sharded(const char *source_path, const char *denoised_pat
           char ferr[320] = "";
           g1s_frame_t cropped;
           if (g1s_filters_has_resize(filters)) {  // (one chain, one device: the sharded command does not resize)
-            rc = G1S_ERR_UNSUPPORTED;
-            set_err(err, errcap, "frame " + std::to_string(frames) + ": the resize filter is served on one device only (drop --gpus / --devices)");
+            rc = refuse(err, errcap, G1S_ERR_UNSUPPORTED, "frame " + std::to_string(frames) + ": the resize filter is served on one device only (drop --gpus / --devices)");
             break;
           }
           rc = g1s_filters_apply(filters, &s, &cropped, ferr, sizeof(ferr));
           if (rc) {
-            set_err(err, errcap, "frame " + std::to_string(frames) + ": " + ferr);
+            refuse(err, errcap, rc, "frame " + std::to_string(frames) + ": " + ferr);
             break;
           }
           s = cropped;
         }
         rc = g1s_diff_frame(gen[r], &s, &d);
         if (rc) {
-          set_err(err, errcap, "frame " + std::to_string(frames) + ": diff_frame: " + g1s_diff_last_error(gen[r]));
+          refuse(err, errcap, rc, "frame " + std::to_string(frames) + ": diff_frame: " + g1s_diff_last_error(gen[r]));
           break;
         }
         ++frames;
@@ -623,30 +578,18 @@ int g1s_diff_y4m_files_sharded(const char *source_path, const char *denoised_pat
   // its slots' worth of batches: a handful of rounds; the bound only stops a protocol error from spinning)
   for (int k = 0; k < 64 && rc == G1S_OK && g1s_fold_frames(fold) < frames; ++k) rc = round(1);
   if (rc == G1S_OK && g1s_fold_frames(fold) != frames) {
-    set_err(err, errcap, "sharded diff: " + std::to_string(g1s_fold_frames(fold)) + " of " + std::to_string(frames) + " frames merged after the flush rounds");
-    rc = G1S_ERR_STATE;
+    rc = refuse(err, errcap, G1S_ERR_STATE, "sharded diff: " + std::to_string(g1s_fold_frames(fold)) + " of " + std::to_string(frames) + " frames merged after the flush rounds");
   }
   if (rc) goto done;
-  rc = g1s_fold_finish(fold, segs.data(), segs.size(), &n);
-  if (rc == G1S_ERR_CAPACITY) {
-    segs.resize(n);
-    rc = g1s_fold_finish(fold, segs.data(), segs.size(), &n);
-  }
-  if (rc) {
-    set_err(err, errcap, g1s_fold_last_error(fold));
-    goto done;
-  }
-  rc = g1s_write_tbl(out_tbl_path, segs.data(), n);
-  if (rc) set_err(err, errcap, std::string("cannot write ") + out_tbl_path);
+  rc = g1s_clip::write_table(
+      out_tbl_path, [&](g1s_segment_t *out, size_t cap, size_t *n) { return g1s_fold_finish(fold, out, cap, n); }, [&] { return g1s_fold_last_error(fold); }, &why);
+  if (rc) refuse(err, errcap, rc, why);
 done:
   if (frames_out) *frames_out = frames;
   if (unequal_out) *unequal_out = unequal;
   for (g1s_diff_t *g : gen)
     if (g) g1s_diff_free(g);
   if (fold) g1s_fold_free(fold);
-  g1s_filters_free(filters);
-  g1s_y4m_close(ys);
-  g1s_y4m_close(yd);
   return rc;
 }
 

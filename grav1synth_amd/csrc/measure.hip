@@ -19,7 +19,8 @@
 // km_measure_x's three pairings, stands before km_measure_t, which has the same loop written out: calling lag_pass from it,
 // and one epilogue helper for the waves' accumulators, gave km_measure, km_measure_s and km_measure_t other code than what
 // was measured before, and timing rows above it (profiles/measure_refactor.txt).  The kernels compile to that code again.  The host engine below them keeps a RecordLane a record kind.  What is done
-// with the records on the host -- the sums and the four reports -- needs no device and is in measure_report.cpp.
+// with the records on the host -- the sums and the four reports -- needs no device and is in measure_report.cpp; the file
+// commands (`measure`, `check`) stand above the per-frame calls in measure_file.cpp.
 //
 // The 32-bit sums and why they hold at 12 bits (|d| <= 4095, a product below 2^24):
 //   * a lane's 25 lag sums take one product a row and are handed on after the wave's 32 rows: below 2^29.  Across the
@@ -33,7 +34,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -41,7 +41,6 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
-#include "fold.h"
 #include "frame_op.h"
 #include "wave_sum.hip.h"
 
@@ -1005,27 +1004,6 @@ int g1s_measure::finish(RecordLane<Rec> &lane, Rec *out, size_t cap, size_t *n_o
 
 namespace {
 
-int refuse(char *err, size_t cap, int code, const std::string &m) {
-  if (err && cap) snprintf(err, cap, "%s", m.c_str());
-  return code;
-}
-
-bool read_file(const char *path, std::string &text) {
-  FILE *f = std::fopen(path, "rb");
-  if (!f) return false;
-  char buf[65536];
-  size_t n;
-  while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
-  std::fclose(f);
-  return true;
-}
-
-const char kCrossNeedsChroma[] = "--cross compares chroma with luma: the clip has no chroma planes";
-
-bool same_clip_shape(const g1s_y4m_info_t &a, const g1s_y4m_info_t &b) {
-  return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.xdec == b.xdec && a.ydec == b.ydec && a.nplanes == b.nplanes;
-}
-
 // the meter is not of the kind the call is for: `maker` is the call that makes one
 int not_made_by(g1s_measure_t *m, const char *maker) {
   m->err = std::string("the meter was not made by ") + maker;  // (not sticky: err_code stays 0)
@@ -1050,90 +1028,6 @@ int kind_timing(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, double *ms
   if (ms) *ms = (m->*lane).ms;
   if (n) *n = (m->*lane).timed;
   return G1S_OK;
-}
-
-// ---- the file commands ----
-// where the reports of a clip go: the plain one always, the others where a path is given
-struct ReportPaths {
-  const char *plain, *temporal, *cross, *scales;
-};
-
-// a clip's total of one record kind: a meter's records pass through `scratch` and are counted
-template <class Rec>
-struct KindTotal {
-  Rec total;
-  std::vector<Rec> scratch;
-  uint64_t count = 0;
-  KindTotal() { std::memset(&total, 0, sizeof total); }
-  // the records of the kind that the meter holds, added to the total.  "" when fine; `kind`: "", "temporal " ... in the text
-  template <class Finish, class Sum>
-  std::string take(g1s_measure_t *m, Finish finish, Sum sum, const char *kind) {
-    size_t n = 0;
-    int rc = finish(m, nullptr, 0, &n);
-    if (rc && rc != G1S_ERR_CAPACITY) return g1s_measure_last_error(m);
-    scratch.resize(n + 1);
-    scratch[n] = total;
-    if (n && (rc = finish(m, scratch.data(), n, &n)) != 0) return g1s_measure_last_error(m);
-    if (sum(scratch.data(), n + 1, &total) != 0) return std::string("the clip's ") + kind + "sums leave 64 bits";
-    count += n;
-    return "";
-  }
-};
-
-// a clip's totals of the four kinds (temporal.count: the clip's pairs with a predecessor)
-struct ClipTotals {
-  KindTotal<g1s_measure_record_t> plain;
-  KindTotal<g1s_measure_trecord_t> temporal;
-  KindTotal<g1s_measure_xrecord_t> cross;
-  KindTotal<g1s_measure_srecord_t> scales;
-  // what the meter holds of every kind that has a report to go to.  "" when fine
-  std::string take(g1s_measure_t *m, const ReportPaths &out) {
-    std::string why = plain.take(m, g1s_measure_finish, g1s_measure_sum, "");
-    if (why.empty() && out.temporal) why = temporal.take(m, g1s_measure_finish_temporal, g1s_measure_sum_temporal, "temporal ");
-    if (why.empty() && out.cross) why = cross.take(m, g1s_measure_finish_cross, g1s_measure_sum_cross, "cross ");
-    if (why.empty() && out.scales) why = scales.take(m, g1s_measure_finish_scales, g1s_measure_sum_scales, "scale ");
-    return why;
-  }
-};
-
-// a report as a g1s_format_measure* call left it (n bytes of buf, n < 0: refused) into a file.  "" when fine
-std::string write_report(const char *path, const char *buf, long n, const char *kind) {
-  if (n < 0) return std::string("formatting the ") + kind + "report failed";
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(buf, 1, (size_t)n, f) == (size_t)n;
-  if (std::fclose(f) != 0 || !ok) return std::string("cannot write ") + path;
-  return "";
-}
-
-// the reports of a clip's totals (beside `synth`'s, of the rendered clip, where there is one) into their files.  "" when fine
-std::string write_reports(const ReportPaths &out, const ClipTotals &t, const ClipTotals *synth, uint64_t frames, const g1s_y4m_info_t &i) {
-  std::vector<char> text(1 << 16);
-  char *buf = text.data();
-  const size_t cap = text.size();
-  const g1s_measure_record_t *plain2 = synth ? &synth->plain.total : nullptr;
-  long n = g1s_format_measure(&t.plain.total, plain2, frames, i.bit_depth, i.width, i.height, i.xdec, i.ydec, i.nplanes, buf, cap);
-  std::string why = write_report(out.plain, buf, n, "");
-  if (why.empty() && out.temporal) {
-    n = g1s_format_measure_temporal(&t.temporal.total, synth ? &synth->temporal.total : nullptr, t.temporal.count, i.bit_depth, i.width, i.height,
-                                    i.xdec, i.ydec, i.nplanes, buf, cap);
-    why = write_report(out.temporal, buf, n, "temporal ");
-  }
-  if (why.empty() && out.cross) {
-    n = g1s_format_measure_cross(&t.cross.total, synth ? &synth->cross.total : nullptr, frames, i.bit_depth, i.width, i.height, i.xdec, i.ydec, buf, cap);
-    why = write_report(out.cross, buf, n, "cross ");
-  }
-  if (why.empty() && out.scales) {
-    n = g1s_format_measure_scales(&t.plain.total, &t.scales.total, plain2, synth ? &synth->scales.total : nullptr, frames, i.bit_depth, i.nplanes, buf, cap);
-    why = write_report(out.scales, buf, n, "scale ");
-  }
-  return why;
-}
-
-// a meter for the kinds that have a report to go to
-g1s_measure_t *meter_for(const ReportPaths &out, uint32_t bit_depth, const g1s_measure_opts_t *opts) {
-  const uint32_t modes = (out.temporal ? G1S_MEASURE_TEMPORAL : 0u) | (out.cross ? G1S_MEASURE_CROSS : 0u);
-  return out.scales ? g1s_measure_new_scales(bit_depth, opts, modes) : g1s_measure_new_modes(bit_depth, opts, modes);
 }
 
 // g1s_measure_new, g1s_measure_new_temporal, g1s_measure_new_modes and g1s_measure_new_scales: the same refusals, the same
@@ -1267,201 +1161,7 @@ const char *g1s_measure_last_error(const g1s_measure_t *m) { return m ? m->err.c
 
 void g1s_measure_free(g1s_measure_t *m) { free_op(m); }
 
-int64_t g1s_measure_y4m_files(const char *noisy, const char *clean, const char *out_report, const g1s_measure_opts_t *opts, int *unequal, char *err,
-                              size_t cap) {
-  return g1s_measure_y4m_files_temporal(noisy, clean, out_report, nullptr, opts, unequal, err, cap);
-}
-
-int64_t g1s_measure_y4m_files_temporal(const char *noisy, const char *clean, const char *out_report, const char *out_treport,
-                                       const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
-  return g1s_measure_y4m_files_modes(noisy, clean, out_report, out_treport, nullptr, opts, unequal, err, cap);
-}
-
-int64_t g1s_measure_y4m_files_modes(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
-                                    const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
-  return g1s_measure_y4m_files_scales(noisy, clean, out_report, out_treport, out_xreport, nullptr, opts, unequal, err, cap);
-}
-
-int64_t g1s_measure_y4m_files_scales(const char *noisy, const char *clean, const char *out_report, const char *out_treport, const char *out_xreport,
-                                     const char *out_sreport, const g1s_measure_opts_t *opts, int *unequal, char *err, size_t cap) {
-  if (unequal) *unequal = 0;
-  if (!noisy || !clean || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
-  g1s_y4m_t *ya = g1s_y4m_open(noisy, err, cap);
-  if (!ya) return G1S_ERR_INVALID;
-  g1s_y4m_t *yb = g1s_y4m_open(clean, err, cap);
-  if (!yb) {
-    g1s_y4m_close(ya);
-    return G1S_ERR_INVALID;
-  }
-  g1s_y4m_info_t ia, ib;
-  g1s_y4m_get_info(ya, &ia), g1s_y4m_get_info(yb, &ib);
-  g1s_measure_t *m = nullptr;
-  int rc = G1S_OK;
-  std::string why;
-  int64_t frames = 0;
-  const ReportPaths out{out_report, out_treport, out_xreport, out_sreport};
-  ClipTotals totals;
-  if (!same_clip_shape(ia, ib)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
-  if (!rc && out_xreport && ia.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
-  if (!rc && !(m = meter_for(out, ia.bit_depth, opts))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
-  while (!rc) {
-    g1s_frame_t fa, fb;
-    const int ga = g1s_y4m_next(ya, &fa), gb = g1s_y4m_next(yb, &fb);
-    if (ga < 0 || gb < 0) {
-      rc = ga < 0 ? ga : gb, why = "frame " + std::to_string(frames) + ": " + (ga < 0 ? g1s_y4m_last_error(ya) : g1s_y4m_last_error(yb));
-      break;
-    }
-    if (ga == 0 || gb == 0) {  // the shorter file ends the clip; one alone: the warning of `diff`
-      if (unequal) *unequal = (ga == 0) != (gb == 0);
-      break;
-    }
-    fa.on_device = fb.on_device = 0;  // (the readers lend the frames until their next call: copied before the call returns)
-    if ((rc = g1s_measure_frame(m, &fa, &fb)) != 0) {
-      why = "frame " + std::to_string(frames) + ": " + g1s_measure_last_error(m);
-      break;
-    }
-    ++frames;
-    if (frames % m->batch == 0 && !(why = totals.take(m, out)).empty()) rc = G1S_ERR_INVALID;
-  }
-  if (!rc && !(why = totals.take(m, out)).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && !(why = write_reports(out, totals, nullptr, (uint64_t)frames, ia)).empty()) rc = G1S_ERR_INVALID;
-  g1s_measure_free(m);
-  g1s_y4m_close(ya);
-  g1s_y4m_close(yb);
-  return rc ? refuse(err, cap, rc, why) : frames;
-}
-
-int64_t g1s_check_y4m_files(const char *source, const char *denoised, const char *tbl, const char *out_report, const g1s_measure_opts_t *opts,
-                            const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
-  return g1s_check_y4m_files_temporal(source, denoised, tbl, out_report, nullptr, opts, gopts, unequal, err, cap);
-}
-
-int64_t g1s_check_y4m_files_temporal(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
-                                     const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err, size_t cap) {
-  return g1s_check_y4m_files_modes(source, denoised, tbl, out_report, out_treport, nullptr, opts, gopts, unequal, err, cap);
-}
-
-int64_t g1s_check_y4m_files_modes(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
-                                  const char *out_xreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts, int *unequal, char *err,
-                                  size_t cap) {
-  return g1s_check_y4m_files_scales(source, denoised, tbl, out_report, out_treport, out_xreport, nullptr, opts, gopts, unequal, err, cap);
-}
-
-int64_t g1s_check_y4m_files_scales(const char *source, const char *denoised, const char *tbl, const char *out_report, const char *out_treport,
-                                   const char *out_xreport, const char *out_sreport, const g1s_measure_opts_t *opts, const g1s_grain_opts_t *gopts,
-                                   int *unequal, char *err, size_t cap) {
-  if (unequal) *unequal = 0;
-  if (!source || !denoised || !tbl || !out_report) return refuse(err, cap, G1S_ERR_INVALID, "null path");
-  // the table, as g1s_grain_y4m_file reads it
-  std::string text;
-  if (!read_file(tbl, text)) return refuse(err, cap, G1S_ERR_INVALID, std::string("cannot open ") + tbl);
-  size_t nseg = 0;
-  char perr[256] = "";
-  std::vector<g1s_segment_t> segs(64);
-  int rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-  if (rc == G1S_ERR_CAPACITY) {
-    segs.resize(nseg);
-    rc = g1s_parse_tbl(text.data(), text.size(), segs.data(), segs.size(), &nseg, perr, sizeof perr);
-  }
-  if (rc) return refuse(err, cap, rc, std::string("grain table: ") + perr);
-  g1s_y4m_t *ys = g1s_y4m_open(source, err, cap);
-  if (!ys) return G1S_ERR_INVALID;
-  g1s_y4m_t *yd = g1s_y4m_open(denoised, err, cap);
-  if (!yd) {
-    g1s_y4m_close(ys);
-    return G1S_ERR_INVALID;
-  }
-  g1s_y4m_info_t is, id;
-  g1s_y4m_get_info(ys, &is), g1s_y4m_get_info(yd, &id);
-  const PlaneGeom pg(id);
-  const Layout lay = staging_layout(pg);
-  g1s_measure_t *ms = nullptr, *mr = nullptr;  // source - denoised; rendered - denoised
-  g1s_grain_t *gr = nullptr;
-  DevBuf<uint8_t> d_src, d_den, d_ren;  // a group of frames each: the source, the denoised, the rendered
-  std::string why;
-  int64_t frames = 0;
-  uint32_t group = 0, in_group = 0;
-  const ReportPaths out{out_report, out_treport, out_xreport, out_sreport};
-  ClipTotals total_s, total_r;
-  if (!same_clip_shape(is, id)) rc = G1S_ERR_DIM_MISMATCH, why = "the two clips differ in geometry or bit depth";
-  if (!rc && out_xreport && id.nplanes != 3) rc = G1S_ERR_INVALID, why = kCrossNeedsChroma;
-  if (!rc && (!(ms = meter_for(out, id.bit_depth, opts)) || !(mr = meter_for(out, id.bit_depth, opts)))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
-  if (!rc) {
-    g1s_grain_opts_t go{};
-    if (gopts) go = *gopts;
-    go.struct_size = sizeof go, go.device = ms->device, go.batch_frames = ms->batch;  // one device, one group size
-    if (!(gr = g1s_grain_new(id.bit_depth, &go))) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
-  }
-  if (!rc) {
-    group = ms->batch;
-    (void)hipSetDevice(ms->device);
-    if (hipMalloc((void **)&d_src.p, lay.frame * group) != hipSuccess || hipMalloc((void **)&d_den.p, lay.frame * group) != hipSuccess ||
-        hipMalloc((void **)&d_ren.p, lay.frame * group) != hipSuccess)
-      rc = G1S_ERR_HIP, why = "hipMalloc of the frame buffers failed";
-  }
-  g1s_frame_t shape{};
-  shape.width = id.width, shape.height = id.height, shape.xdec = (uint8_t)id.xdec, shape.ydec = (uint8_t)id.ydec, shape.nplanes = (uint8_t)id.nplanes;
-  shape.bytes_per_sample = (uint8_t)pg.bps, shape.on_device = 1;
-  auto slot = [&](const DevBuf<uint8_t> &buf, uint32_t k) {
-    g1s_frame_t f = shape;
-    lay.point(f, buf + lay.frame * k, pg.nplanes);
-    return f;
-  };
-  // a group is through: its renders complete (the synthesizer has a stream of its own) before the meters read them, both
-  // meters' batches out and waited for, so that the group's buffers are free again
-  auto end_group = [&]() {
-    if ((rc = g1s_grain_sync(gr)) != 0) why = std::string("render: ") + g1s_grain_last_error(gr);
-    for (uint32_t k = 0; k < in_group && !rc; ++k) {
-      const g1s_frame_t s = slot(d_src, k), d = slot(d_den, k), r = slot(d_ren, k);
-      if ((rc = g1s_measure_frame(ms, &s, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(ms);
-      else if ((rc = g1s_measure_frame(mr, &r, &d)) != 0) why = std::string("measure: ") + g1s_measure_last_error(mr);
-    }
-    // (a temporal meter keeps a copy of the group's last pair on the device: the group's buffers are free again all the same)
-    if (!rc && !(why = total_s.take(ms, out)).empty()) rc = G1S_ERR_INVALID;
-    if (!rc && !(why = total_r.take(mr, out)).empty()) rc = G1S_ERR_INVALID;
-    in_group = 0;
-  };
-  while (!rc) {
-    g1s_frame_t fs, fd;
-    const int gs = g1s_y4m_next(ys, &fs), gd = g1s_y4m_next(yd, &fd);
-    if (gs < 0 || gd < 0) {
-      rc = gs < 0 ? gs : gd, why = "frame " + std::to_string(frames) + ": " + (gs < 0 ? g1s_y4m_last_error(ys) : g1s_y4m_last_error(yd));
-      break;
-    }
-    if (gs == 0 || gd == 0) {
-      if (unequal) *unequal = (gs == 0) != (gd == 0);
-      break;
-    }
-    // both frames to the device, once (the readers lend them until their next call)
-    const g1s_frame_t s = slot(d_src, in_group), d = slot(d_den, in_group);
-    g1s_frame_t r = slot(d_ren, in_group);
-    bool copied = true;
-    for (int c = 0; c < pg.nplanes; ++c)
-      copied = copied &&
-               hipMemcpy2D(const_cast<void *>(s.data[c]), lay.row[c], fs.data[c], fs.stride_bytes[c], pg.row_bytes(c), pg.ph(c), hipMemcpyHostToDevice) == hipSuccess &&
-               hipMemcpy2D(const_cast<void *>(d.data[c]), lay.row[c], fd.data[c], fd.stride_bytes[c], pg.row_bytes(c), pg.ph(c), hipMemcpyHostToDevice) == hipSuccess;
-    if (!copied) {
-      rc = G1S_ERR_HIP, why = "copy of a frame pair to the device failed";
-      break;
-    }
-    // the table's lookup at the frame's presentation time, as `render` makes it; no segment: rendered = denoised
-    const long si = g1s_tbl_segment_for(segs.data(), nseg, g1s::frame_time((uint64_t)frames, id.fps_num, id.fps_den));
-    if ((rc = g1s_grain_frame(gr, si < 0 ? nullptr : &segs[(size_t)si], &d, &r)) != 0) {
-      why = "frame " + std::to_string(frames) + ": render: " + g1s_grain_last_error(gr);
-      break;
-    }
-    ++frames;
-    if (++in_group == group) end_group();
-  }
-  if (!rc && in_group) end_group();
-  if (!rc && !(why = write_reports(out, total_s, &total_r, (uint64_t)frames, id)).empty()) rc = G1S_ERR_INVALID;
-  if (ms) (void)hipSetDevice(ms->device);
-  g1s_grain_free(gr);
-  g1s_measure_free(mr);
-  g1s_measure_free(ms);
-  g1s_y4m_close(ys);
-  g1s_y4m_close(yd);
-  return rc ? refuse(err, cap, rc, why) : frames;
-}
+// (measure_file.cpp) the device the file commands put their own buffers and the synthesizer on
+int32_t g1s_measure_device_(const g1s_measure_t *m) { return m->device; }
 
 }  // extern "C"

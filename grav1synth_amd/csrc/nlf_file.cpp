@@ -10,36 +10,23 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
+#include "clip_file.h"
 #include "frame_op.h"
 #include "nlf.h"
 
-namespace {
+using g1s_clip::refuse;
 
-int refuse(char *err, size_t cap, int code, const std::string &m) {
-  if (err && cap) snprintf(err, cap, "%s", m.c_str());
-  return code;
-}
+namespace {
 
 // the records of one kind the meter holds (`finish`: g1s_nlf_finish or g1s_nlf_finish_temporal), added to `total`; they
 // stay in `scratch`, behind them the total as it was.  "" when fine
 template <class Record, class Finish>
-std::string take_records(g1s_nlf_t *m, Finish finish, std::vector<Record> &scratch, Record &total) {
-  size_t n = 0;
-  int rc = finish(m, nullptr, 0, &n);
-  if (rc && rc != G1S_ERR_CAPACITY) return g1s_nlf_last_error(m);
-  scratch.resize(n + 1);
-  scratch[n] = total;
-  if (n && (rc = finish(m, scratch.data(), n, &n)) != 0) return g1s_nlf_last_error(m);
-  if (!g1s_nl::sum_records(scratch.data(), n + 1, &total)) return g1s_nl::kSumsLeave64;
-  return "";
+std::string take_from(g1s_nlf_t *m, Finish finish, std::vector<Record> &scratch, Record &total) {
+  return g1s_clip::take_records([&](Record *out, size_t cap, size_t *n) { return finish(m, out, cap, n); }, g1s_nl::sum_records<Record>,
+                                [&] { return g1s_nlf_last_error(m); }, g1s_nl::kSumsLeave64, scratch, total);
 }
 
-std::string write_text(const char *path, const std::string &text) {
-  FILE *fo = std::fopen(path, "wb");
-  if (!fo) return std::string("cannot create ") + path;
-  const bool ok = std::fwrite(text.data(), 1, text.size(), fo) == text.size();
-  return std::fclose(fo) != 0 || !ok ? std::string("cannot write ") + path : "";
-}
+std::string write_report(const char *path, const std::string &text) { return g1s_clip::write_text(path, text.data(), text.size()); }
 
 // a .y4m file through a meter (`temporal`: a temporal one, the file one run): the reports, the clip's records
 int64_t nlf_y4m_file(const char *source, const char *out_report, const char *out_treport, const g1s_nlf_opts_t *opts, uint64_t max_frames,
@@ -62,9 +49,9 @@ int64_t nlf_y4m_file(const char *source, const char *out_report, const char *out
   const uint32_t batch = g1s_op::batch_of(opts ? opts->batch_frames : 0);
   g1s_nlf_t *m = temporal ? g1s_nlf_new_temporal(info.bit_depth, opts) : g1s_nlf_new(info.bit_depth, opts);
   auto take_all = [&]() -> std::string {
-    std::string no = take_records(m, g1s_nlf_finish, scratch, total);
+    std::string no = take_from(m, g1s_nlf_finish, scratch, total);
     if (no.empty() && !have_first && scratch.size() > 1) first = scratch[0], have_first = true;
-    if (no.empty() && temporal && (no = take_records(m, g1s_nlf_finish_temporal, tscratch, ttotal)).empty()) pairs += tscratch.size() - 1;
+    if (no.empty() && temporal && (no = take_from(m, g1s_nlf_finish_temporal, tscratch, ttotal)).empty()) pairs += tscratch.size() - 1;
     return no;
   };
   if (!m) rc = G1S_ERR_NO_DEVICE, why = g1s_last_global_error();
@@ -85,11 +72,11 @@ int64_t nlf_y4m_file(const char *source, const char *out_report, const char *out
     if (frames % batch == 0 && !(why = take_all()).empty()) rc = G1S_ERR_INVALID;
   }
   if (!rc && !(why = take_all()).empty()) rc = G1S_ERR_INVALID;
-  if (!rc && out_report && !(why = write_text(out_report, g1s_nl::report(total, (uint64_t)frames, info.bit_depth, info.nplanes, 0))).empty())
+  if (!rc && out_report && !(why = write_report(out_report, g1s_nl::report(total, (uint64_t)frames, info.bit_depth, info.nplanes, 0))).empty())
     rc = G1S_ERR_INVALID;
   if (!rc && out_treport) {
     const g1s_nlf_record_t later = g1s_nl::without_first(total, first);
-    if (!(why = write_text(out_treport, g1s_nl::report_t(ttotal, &later, pairs, info.bit_depth, info.nplanes, 0))).empty()) rc = G1S_ERR_INVALID;
+    if (!(why = write_report(out_treport, g1s_nl::report_t(ttotal, &later, pairs, info.bit_depth, info.nplanes, 0))).empty()) rc = G1S_ERR_INVALID;
   }
   if (!rc && total_out) *total_out = total;
   if (!rc && ttotal_out) *ttotal_out = ttotal;

@@ -1,14 +1,16 @@
 // nlf_file_host.cpp -- the record arithmetic of the noise levels' file commands (grav1synth_amd/csrc/nlf_file.cpp) built with a
-// host compiler alone, as a stand-alone program: a clip's total taken a batch at a time with the total so far as one more
-// record (nlf.h's sum_records for either kind), and the ordinary record of the frames with a predecessor, the total less
-// the first frame's (without_first), which the temporal report's ratio lines are formed from.  tests/test_nlf_t_cpu.py
-// compiles it under the address and undefined-behaviour sanitizers.
+// host compiler alone, as a stand-alone program: a clip's total taken a batch at a time through clip_file.h's take_records
+// with nlf.h's sum_records (what that does with a sum that leaves 64 bits and with the signed temporal kind is checked in
+// tests/clip_file_host.cpp), and the ordinary record of the frames with a predecessor, the total less the first frame's
+// (without_first), which the temporal report's ratio lines are formed from.  tests/test_nlf_t_cpu.py compiles it under the
+// address and undefined-behaviour sanitizers.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "../grav1synth_amd/csrc/clip_file.h"
 #include "../grav1synth_amd/csrc/nlf.h"
 
 static void require(bool ok, const char *what) {
@@ -18,11 +20,17 @@ static void require(bool ok, const char *what) {
   }
 }
 
-// as nlf_file.cpp's take_records: the records of a batch, behind them the total so far, summed into the total
+// a batch of records held by a meter, taken as nlf_file.cpp takes them
 template <class Record>
 static bool take(std::vector<Record> batch, Record &total) {
-  batch.push_back(total);
-  return g1s_nl::sum_records(batch.data(), batch.size(), &total);
+  std::vector<Record> scratch;
+  auto finish = [&](Record *out, size_t cap, size_t *n) {
+    *n = batch.size();
+    if (cap < batch.size()) return (int)G1S_ERR_CAPACITY;
+    std::copy(batch.begin(), batch.end(), out);
+    return (int)G1S_OK;
+  };
+  return g1s_clip::take_records(finish, g1s_nl::sum_records<Record>, [] { return "the meter failed"; }, g1s_nl::kSumsLeave64, scratch, total).empty();
 }
 
 int main() {

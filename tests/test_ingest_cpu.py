@@ -2,12 +2,17 @@
 libav reader, src/reader.rs:37-212) hands out exactly the planes that were written, for every format
 the reference's reader accepts (8/10/12-bit, 4:2:0 / 4:2:2 / 4:4:4, src/reader.rs:51-85), signals
 end of stream as `None`, and reports malformed files instead of guessing."""
+import os
+import shutil
+import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from grav1synth_amd.ingest import Y4MReader, write_y4m
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _frames(n, w, h, bd, xdec, ydec, nplanes, seed=7):
@@ -94,7 +99,6 @@ def test_reader_takes_a_stream_from_a_pipe(tmp_path):
     """No libav in the image: what stands in for the reference's decoder is a decoder's output piped in --
     `ffmpeg -i in.mkv -f yuv4mpegpipe - > fifo`.  The reader must therefore work on something it cannot seek in or take the
     size of: a FIFO, written by another thread frame by frame, big frames included (the positional-read path needs a file)."""
-    import os
     import threading
 
     for (w, h, bd) in ((64, 48, 8), (2048, 1024, 10)):
@@ -125,3 +129,21 @@ def test_reader_takes_a_stream_from_a_pipe(tmp_path):
         r.close()
         t.join(timeout=10)
         assert not t.is_alive()
+
+
+def test_what_the_file_commands_share_under_the_sanitizers(tmp_path):
+    """tests/clip_file_host.cpp: the frame pair of two readers, a meter's records a batch at a time, the table loader, a text
+    into a file -- grav1synth_amd/csrc/clip_file.h with a host compiler alone."""
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    exe = tmp_path / "clip_file_host"
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
+           os.path.join(ROOT, "tests", "clip_file_host.cpp")]
+    # (the sanitizer's runtime inside the program where the compiler can do that: it then starts under any preloaded library)
+    if subprocess.call(cmd + ["-static-libasan"], stderr=subprocess.DEVNULL) != 0:
+        subprocess.check_call(cmd)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    p = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert p.stdout.splitlines()[-1] == "ok"
