@@ -207,6 +207,17 @@ class G1SNlfOpts(C.Structure):
     ]
 
 
+class G1SEstimateLaunch(C.Structure):
+    _fields_ = [
+        ("strip_rows", C.c_uint32),
+        ("row_strips", C.c_uint32),
+        ("packed", C.c_int32),
+        ("launched", C.c_int32),
+        ("cus", C.c_int32),
+        ("wgs_per_cu", C.c_int32),
+    ]
+
+
 class G1SNlfRecord(C.Structure):
     _fields_ = [
         ("n", (C.c_uint64 * 32) * 3),
@@ -319,6 +330,7 @@ SYMBOLS = [
     ("g1s_estimate_frame", C.c_int, [C.c_void_p, C.POINTER(G1SFrame)]),
     ("g1s_estimate_finish", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("g1s_estimate_set_timing", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_estimate_last_launch", C.c_int, [C.c_void_p, C.POINTER(G1SEstimateLaunch), C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("g1s_estimate_last_error", C.c_char_p, [C.c_void_p]),
     ("g1s_estimate_free", None, [C.c_void_p]),
     ("g1s_format_estimates", C.c_long, [C.POINTER(C.c_double), C.c_size_t, C.c_char_p, C.c_size_t]),

@@ -25,6 +25,7 @@
 
 #include "../../include/g1s_diff.h"
 #include "strip_walk.hip.h"
+#include "estimate_plan.h"
 #include "frame_op.h"
 
 namespace {
@@ -162,10 +163,10 @@ __device__ __forceinline__ void est_derive(const uint32_t (&c)[4], EstRow &r) {
   }
 }
 
-// Output rows per wave strip: chosen by the host so that the launch is a whole number of resident rounds (8 waves a SIMD:
-// 8192 waves on the chip): with 64-row strips a 32-frame 4K launch was 8704 waves -- 1.06 rounds, the last 6 % of the waves
-// alone on the chip for as long as the first 94 % took.
-constexpr int kPkMaxStripRows = 256;  // (the two 16-bit pixel counters of a lane hold 4 * rows each)
+// Output rows per wave strip: chosen by the host (estimate_plan.h: whole resident rounds, at most kPkMaxStripRows rows -- the
+// two 16-bit pixel counters of a lane hold 4 * rows each)
+using g1s_est::kPkMaxStripRows;
+static_assert(g1s_est::kPlanWavesPerWg == kWavesPerWg && g1s_est::kPlanColsPerWave == kColsPerWave, "estimate_plan.h restates strip_walk.hip.h");
 
 // the fast form: the lane's word lies inside the plane's rows or wholly outside (then any in-plane word will do: every
 // pixel it could reach is masked), the rows are 16-byte (8-byte) aligned: one unconditional vector load, nothing to wait for
@@ -297,6 +298,8 @@ struct g1s_estimate {
   DevBuf<uint8_t> d_stage;         // device copies of host frames: rows as in the staging layout, no gap between frames
   size_t stage_row = 0;
   std::vector<double> estimates;   // one per frame: sigma, or -1 (None)
+  std::vector<uint64_t> sums;      // beside them, from the same words: accum, count per frame
+  g1s_estimate_launch_t last = {};  // the last batch's launch (g1s_estimate_last_launch)
   std::string err;
   uint64_t frames_kernel = 0;
   double ms_kernel = 0;
@@ -325,27 +328,30 @@ int g1s_estimate::flush() {
   // depths up to 12 bits: the packed 16-bit kernel; deeper samples (or G1S_ESTIMATE=wide, a test aid): 32-bit arithmetic
   const char *mode = getenv("G1S_ESTIMATE");
   const bool packed = bit_depth <= 12 && !(mode && std::strcmp(mode, "wide") == 0);
-  ep.col_strips = ((int)W - 1 + kColsPerWave - 1) / kColsPerWave;
-  int strip_rows = kStripRows;
+  ep.col_strips = g1s_est::plan_col_strips((int)W);
+  ep.strip_rows = kStripRows;
+  ep.row_strips = ((int)H - 2 + kStripRows - 1) / kStripRows;
   // a plane without interior pixels (one or two samples wide or high; one sample wide: no column strip at all) launches nothing
   const bool launch = W >= 3 && H >= 3;
+  int cus = 256, wgs_per_cu = 0;
   if (packed && launch) {
-    // whole resident rounds: k rounds of `resident` waves, the smallest k whose strips are at most kPkMaxStripRows rows
-    int cus = 256, wgs_per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (bps == 2) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<2>, kStripThreads, 0);
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, k_estimate_pk<1>, kStripThreads, 0);
-    if (wgs_per_cu < 1) wgs_per_cu = 5;
-    const long resident = (long)cus * wgs_per_cu * kWavesPerWg, cols = (long)ep.col_strips * B, rows = (long)H - 2;
-    for (long k = 1;; ++k) {
-      const long rs = std::max(1L, k * resident / cols);  // row strips a frame
-      strip_rows = (int)((rows + rs - 1) / rs);
-      if (strip_rows <= kPkMaxStripRows) break;
-    }
-    strip_rows = std::max(strip_rows, 8);
+    // G1S_ESTIMATE_ROWS=N (a test and measurement aid, read at every batch): the packed launch takes strips of N rows, not the
+    // plan's; an N outside 8 .. 256 is clamped into that range (0 or no number: the plan's).  The 32-bit kernel's stay kStripRows.
+    const char *rows_env = getenv("G1S_ESTIMATE_ROWS");
+    const int forced = rows_env ? std::atoi(rows_env) : 0;
+    const g1s_est::StripPlan plan = g1s_est::plan_strips((int)H, ep.col_strips, (int)B, cus, wgs_per_cu, forced);
+    ep.strip_rows = plan.strip_rows;
+    ep.row_strips = plan.row_strips;
   }
-  ep.strip_rows = strip_rows;
-  ep.row_strips = ((int)H - 2 + strip_rows - 1) / strip_rows;
+  last.strip_rows = (uint32_t)ep.strip_rows;
+  last.row_strips = (uint32_t)std::max(ep.row_strips, 0);
+  last.packed = packed;
+  last.launched = launch;
+  last.cus = packed && launch ? cus : 0;
+  last.wgs_per_cu = packed && launch ? wgs_per_cu : 0;
   if (launch) {
     const dim3 grid((ep.col_strips * ep.row_strips + kWavesPerWg - 1) / kWavesPerWg, B);
     if (timing) G1S_OP_TRY(hipEventRecord(ev0, stream));
@@ -368,6 +374,8 @@ int g1s_estimate::flush() {
     const unsigned long long accum = h_sums[2 * i], count = h_sums[2 * i + 1];
     // (count < 16) ? None : accum as f64 / (6 * count) as f64 * SQRT_PI_BY_2
     estimates.push_back(count < 16 ? -1.0 : (double)accum / (double)(6 * count) * kSqrtPiBy2);
+    sums.push_back(accum);
+    sums.push_back(count);
   }
   h_frames.clear();
   return G1S_OK;
@@ -440,6 +448,17 @@ int g1s_estimate_set_timing(g1s_estimate_t *e, int enable, double *ms_kernel, ui
   e->timing = enable != 0;
   if (ms_kernel) *ms_kernel = e->ms_kernel;
   if (frames) *frames = e->frames_kernel;
+  return G1S_OK;
+}
+
+int g1s_estimate_last_launch(g1s_estimate_t *e, g1s_estimate_launch_t *launch, uint64_t *sums, size_t cap, size_t *n_out) {
+  if (!e) return G1S_ERR_INVALID;
+  if (launch) *launch = e->last;
+  const size_t n = e->sums.size() / 2;
+  if (n_out) *n_out = n;
+  if (!sums && !cap) return G1S_OK;  // the launch alone
+  if (n > cap || (!sums && n)) return e->fail(G1S_ERR_CAPACITY, "sums buffer too small");
+  if (n) std::memcpy(sums, e->sums.data(), sizeof(uint64_t) * 2 * n);
   return G1S_OK;
 }
 

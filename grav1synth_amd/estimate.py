@@ -89,6 +89,18 @@ class NoiseEstimator:
         self._L.g1s_estimate_set_timing(self._h, int(enable), C.byref(ms), C.byref(fr))
         return ms.value, fr.value
 
+    def last_launch(self) -> dict:
+        """g1s_estimate_last_launch (a test and measurement aid): strip_rows, row_strips, packed, launched, cus and wgs_per_cu
+        of the last batch's launch, and `sums`: (accum, count) of every frame finish() has an estimate for, in its order."""
+        info, n = _lib.G1SEstimateLaunch(), C.c_size_t()
+        self._check(self._L.g1s_estimate_last_launch(self._h, C.byref(info), None, 0, C.byref(n)))
+        buf = (C.c_uint64 * max(2 * n.value, 1))()
+        self._check(self._L.g1s_estimate_last_launch(self._h, None, buf, n.value, C.byref(n)))
+        out = {name: int(getattr(info, name)) for name, _ in info._fields_}
+        out["packed"], out["launched"] = bool(info.packed), bool(info.launched)
+        out["sums"] = [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n.value)]
+        return out
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._L.g1s_estimate_free(self._h)

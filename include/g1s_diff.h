@@ -403,6 +403,22 @@ int g1s_estimate_frame(g1s_estimate_t *, const g1s_frame_t *frame);
 int g1s_estimate_finish(g1s_estimate_t *, double *out, size_t cap, size_t *n_out);
 /* HIP-event time of the kernel launches so far (enable = 1 from the next batch on). */
 int g1s_estimate_set_timing(g1s_estimate_t *, int enable, double *ms_kernel, uint64_t *frames);
+/* What the last batch's launch was cut into, and the integers behind the estimates (a test and measurement aid).  Depths up to
+ * 12 bits take the packed kernel, whose strip height is chosen per launch from the plane, the batch, the device's compute
+ * units and the kernel's occupancy (csrc/estimate_plan.h), or given by G1S_ESTIMATE_ROWS=N (clamped into 8 .. 256); deeper
+ * samples and G1S_ESTIMATE=wide take the 32-bit kernel and strips of 32 rows. */
+typedef struct {
+  uint32_t strip_rows;  /* output rows a wave strip */
+  uint32_t row_strips;  /* strips down a plane */
+  int32_t packed;       /* 1: the packed kernel */
+  int32_t launched;     /* 0: the plane has no interior pixel, nothing ran */
+  int32_t cus;          /* what the plan was given: compute units and workgroups of the kernel a unit as the occupancy query */
+  int32_t wgs_per_cu;   /* answered (below 1: the plan took its fallback); both 0 for the 32-bit kernel */
+} g1s_estimate_launch_t;
+/* *launch (may be NULL): the last batch that held a frame.  sums: accum and count of every frame g1s_estimate_finish has an
+ * estimate for, in its order, two words a frame, from the same words the estimates were formed from; *n_out = the frames.
+ * sums NULL with cap 0: the launch alone.  Too small a cap: G1S_ERR_CAPACITY.  Frames still queued are not launched. */
+int g1s_estimate_last_launch(g1s_estimate_t *, g1s_estimate_launch_t *launch, uint64_t *sums, size_t cap, size_t *n_out);
 const char *g1s_estimate_last_error(const g1s_estimate_t *);
 void g1s_estimate_free(g1s_estimate_t *);
 /* The command's output (src/main.rs:596-603): "filmgrn1\n" then "{:.3}\n" per frame.  Bytes written or G1S_ERR_CAPACITY. */

@@ -16,7 +16,9 @@
 #define SQRT_PI_BY_2 1.2533141373155003
 #define ROUND_POWER_OF_TWO(value, n) (((value) + (((1 << (n)) >> 1))) >> (n))
 
-double orc_estimate_plane_noise(const void *plane, size_t stride_bytes, uint32_t width, uint32_t height, uint32_t bit_depth) {
+/* the two integer sums of the loop: what the estimate is formed from */
+void orc_estimate_plane_sums(const void *plane, size_t stride_bytes, uint32_t width, uint32_t height, uint32_t bit_depth, int64_t *accum_out,
+                             uint64_t *count_out) {
   const int shift = (int)bit_depth - 8;
   int64_t accum = 0;
   uint64_t count = 0;
@@ -39,5 +41,13 @@ double orc_estimate_plane_noise(const void *plane, size_t stride_bytes, uint32_t
       }
     }
   }
+  *accum_out = accum;
+  *count_out = count;
+}
+
+double orc_estimate_plane_noise(const void *plane, size_t stride_bytes, uint32_t width, uint32_t height, uint32_t bit_depth) {
+  int64_t accum;
+  uint64_t count;
+  orc_estimate_plane_sums(plane, stride_bytes, width, height, bit_depth, &accum, &count);
   return count < 16 ? -1.0 : (double)accum / (double)(6 * count) * SQRT_PI_BY_2;
 }

@@ -71,6 +71,9 @@ def build() -> None:
 def _prototypes(L):
     L.orc_estimate_plane_noise.restype = C.c_double
     L.orc_estimate_plane_noise.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32]
+    if hasattr(L, "orc_estimate_plane_sums"):  # (the pin-sensitivity variants are built from the same file)
+        L.orc_estimate_plane_sums.restype = None
+        L.orc_estimate_plane_sums.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
     L.orc_resize_plan.restype = C.c_int
     L.orc_resize_plan.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     L.orc_resize_plane.restype = C.c_int
@@ -121,7 +124,7 @@ def lib():
     if not os.path.exists(_LIB_PATH):
         build()
     L = C.CDLL(_LIB_PATH)
-    if not hasattr(L, "orc_estimate_plane_noise") or not hasattr(L, "orc_resize_plane") or not hasattr(L, "orc_diff_save"):  # a library from before these were added
+    if not hasattr(L, "orc_estimate_plane_sums") or not hasattr(L, "orc_resize_plane") or not hasattr(L, "orc_diff_save"):  # a library from before these were added
         del L
         build()
         L = C.CDLL(_LIB_PATH)
@@ -135,6 +138,15 @@ def estimate_plane_noise(plane: np.ndarray, bit_depth: int) -> Optional[float]:
     assert p.dtype == (np.uint8 if bit_depth == 8 else np.uint16)
     v = lib().orc_estimate_plane_noise(p.ctypes.data, p.strides[0], p.shape[1], p.shape[0], bit_depth)
     return None if v == -1.0 else float(v)
+
+
+def estimate_plane_sums(plane: np.ndarray, bit_depth: int):
+    """(accum, count): the two integer sums estimate_plane_noise forms its f64 from, out of the same loop."""
+    p = np.ascontiguousarray(plane)
+    assert p.dtype == (np.uint8 if bit_depth == 8 else np.uint16)
+    accum, count = C.c_int64(), C.c_uint64()
+    lib().orc_estimate_plane_sums(p.ctypes.data, p.strides[0], p.shape[1], p.shape[0], bit_depth, C.byref(accum), C.byref(count))
+    return int(accum.value), int(count.value)
 
 
 def resize_plan(alg: str, src: int, dst: int):

@@ -440,7 +440,8 @@ def other_geometry(c: dict):
 # ---- estimate -----------------------------------------------------------------------------------------------------------
 
 # k_estimate[_pk]: a wave owns 496 output columns (8 a lane, lanes 0 and 63 the halo words) of a strip of rows -- 32 rows, or for the
-# packed kernel 8 .. 256 rows chosen from the device's occupancy; the second column strip begins at W - 1 > 496.
+# packed kernel 8 .. 256 rows chosen from the device's occupancy; the second column strip begins at W - 1 > 496.  (At the sizes
+# drawn here the packed kernel's choice is 8 rows; its other heights, pinned: tests/test_gpu_estimate_strips.py.)
 EST_COLS, EST_ROWS = 496, 32
 
 

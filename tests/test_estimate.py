@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 from grav1synth_amd.synth import SynthSpec, make_pair
-from tests.oracle_binding import estimate_plane_noise
+from tests.oracle_binding import estimate_plane_noise, estimate_plane_sums
 
 
-def _numpy_estimate(p: np.ndarray, bd: int):
-    """sum over the interior of [Sobel magnitude < 50] * |Laplacian|, both rounded to 8-bit scale: array form."""
+def _numpy_sums(p: np.ndarray, bd: int):
+    """sum over the interior of [Sobel magnitude < 50] * |Laplacian|, both rounded to 8-bit scale: array form.  (accum, count)"""
     a = p.astype(np.int64)
     sh = bd - 8
     half = (1 << sh) >> 1
@@ -25,8 +25,11 @@ def _numpy_estimate(p: np.ndarray, bd: int):
     ga = (np.abs(gx) + np.abs(gy) + half) >> sh
     v = 4 * m(0, 0) - 2 * (m(-1, 0) + m(1, 0) + m(0, -1) + m(0, 1)) + (m(-1, -1) + m(-1, 1) + m(1, -1) + m(1, 1))
     on = ga < 50
-    accum = int((((np.abs(v) + half) >> sh) * on).sum())
-    count = int(on.sum())
+    return int((((np.abs(v) + half) >> sh) * on).sum()), int(on.sum())
+
+
+def _numpy_estimate(p: np.ndarray, bd: int):
+    accum, count = _numpy_sums(p, bd)
     return None if count < 16 else accum / (6 * count) * 1.2533141373155003
 
 
@@ -41,6 +44,7 @@ def test_oracle_estimator_equals_the_numpy_derivation(spec):
     for k in range(2):
         p = _plane(spec, k)
         assert estimate_plane_noise(p, spec.bit_depth) == _numpy_estimate(p, spec.bit_depth)
+        assert estimate_plane_sums(p, spec.bit_depth) == _numpy_sums(p, spec.bit_depth)  # the integers, not only their ratio
 
 
 def test_oracle_estimator_edge_cases():
