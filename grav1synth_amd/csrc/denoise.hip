@@ -659,38 +659,34 @@ static std::string levels_refusal(uint32_t K, double rho, double h, double hc) {
 
 // what every g1s_denoise_new* call makes
 static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *opts, const DenoiserSpec &spec) {
-  const auto [temporal_radius, flags, curve, fwd, inv, motion_range, chroma_gain, coarse_levels, coarse_ratio, share] = spec;
-  g1s_set_global_error_("");
-  if (opts && opts->struct_size != sizeof(g1s_denoise_opts_t)) {
-    g1s_set_global_error_("g1s_denoise_opts_t.struct_size mismatch");
-    return nullptr;
-  }
+  if (!opts_fit(opts, "g1s_denoise_opts_t")) return nullptr;
   // the parameters first: a refusal needs no device
   const uint32_t A = opts && opts->search_radius ? opts->search_radius : 3u, S = opts && opts->patch_radius ? opts->patch_radius : 2u;
-  const auto [h, hc] = strengths_of(opts);
+  const Strengths strengths = strengths_of(opts);
+  const double h = strengths.h, hc = strengths.hc;
   if (A < 1 || A > (uint32_t)kMaxA) {
     g1s_set_global_error_("search_radius must be 1..7");
     return nullptr;
   }
-  if (temporal_radius > (uint32_t)kMaxD) {
+  if (spec.temporal_radius > (uint32_t)kMaxD) {
     g1s_set_global_error_("temporal_radius must be 0..3");
     return nullptr;
   }
-  if (flags & ~G1S_DENOISE_JOINT_CHROMA) {
+  if (spec.flags & ~G1S_DENOISE_JOINT_CHROMA) {
     g1s_set_global_error_("unknown denoise flags");
     return nullptr;
   }
-  if ((motion_range & 1) || motion_range > 2u * (uint32_t)kMaxM) {
+  if ((spec.motion_range & 1) || spec.motion_range > 2u * (uint32_t)kMaxM) {
     g1s_set_global_error_("motion_range must be even and 0..64");
     return nullptr;
   }
-  if (motion_range && !temporal_radius) {
+  if (spec.motion_range && !spec.temporal_radius) {
     g1s_set_global_error_("motion_range needs a temporal radius");
     return nullptr;
   }
-  if (chroma_gain) {
-    const std::string no = g1s_cv::check_gain(chroma_gain);
-    if (!no.empty() || !(flags & G1S_DENOISE_JOINT_CHROMA)) {
+  if (spec.chroma_gain) {
+    const std::string no = g1s_cv::check_gain(spec.chroma_gain);
+    if (!no.empty() || !(spec.flags & G1S_DENOISE_JOINT_CHROMA)) {
       g1s_set_global_error_(no.empty() ? "a chroma gain needs joint chroma" : no.c_str());
       return nullptr;
     }
@@ -704,78 +700,69 @@ static g1s_denoise *new_denoiser(uint32_t bit_depth, const g1s_denoise_opts_t *o
     if (!why.empty()) why = "chroma_" + why;
   }
   // the curve: luma is filtered as a 12-bit plane with the luma strength (rule 14)
-  if (why.empty() && curve) {
-    why = g1s_cv::check(bit_depth, fwd, inv);
+  if (why.empty() && spec.curve) {
+    why = g1s_cv::check(bit_depth, spec.fwd, spec.inv);
     if (why.empty()) why = make_table(g1s_cv::kStabBits, S, h, tables.data() + 3 * kTable, &q[3]);
   }
-  if (why.empty()) why = levels_refusal(coarse_levels, coarse_ratio, h, hc);
+  if (why.empty()) why = levels_refusal(spec.coarse_levels, spec.coarse_ratio, h, hc);
   if (!why.empty()) {
     g1s_set_global_error_(why.c_str());
     return nullptr;
   }
-  int device = 0;
-  why = pick_device(opts ? opts->device : -1, "denoise", &device);
-  if (!why.empty()) {
-    g1s_set_global_error_(why.c_str());
-    return nullptr;
-  }
-  // the LDS a workgroup of the largest kernel these parameters select asks for, against what the device gives one
-  {
-    const TileGeom tg = tile_geom((int)A, (int)S);
-    const JointGeom jg = chroma_gain ? joint_gain_geom(tg) : joint_geom(tg);
-    const bool joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
-    const int need = temporal_radius ? (joint ? jg.bytes_t : tg.bytes_t) : (joint ? jg.bytes : tg.bytes);
-    int limit = 0;
-    if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || need > limit) {
-      g1s_set_global_error_(("these parameters need " + std::to_string(need) + " bytes of LDS a workgroup" + (joint ? " (joint chroma)" : "") +
-                             "; the device allows " + std::to_string(limit)).c_str());
-      return nullptr;
-    }
-  }
-  g1s_denoise *g = new g1s_denoise;
-  g->A = A, g->S = S, g->D = temporal_radius, g->joint = (flags & G1S_DENOISE_JOINT_CHROMA) != 0;
-  g->curve = curve, g->M = motion_range / 2, g->gain = chroma_gain != nullptr;
-  for (int i = 0; i < 4; ++i) g->q[i] = q[i];
-  g->K = coarse_levels;
-  bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
-  if (ok && share) {  // an inner level runs on its owner's stream: one order for kd_down, its launches and the merge
-    (void)hipStreamDestroy(g->stream.p);
-    g->stream.p = share, g->borrowed_stream = true;
-  }
-  for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  if (ok && coarse_levels) {
-    // rule 26: level K - 1 on the coarse frames -- the strengths times rho, Mr' = 2 ceil(Mr / 4), everything else the same
-    const double rho = coarse_ratio != 0.0 ? coarse_ratio : 1.0;
-    g1s_denoise_opts_t io{};
-    io.struct_size = sizeof io, io.device = device, io.batch_frames = g->batch, io.search_radius = A, io.patch_radius = S;
-    io.strength = rho * h, io.chroma_strength = rho * hc;
-    for (Event &e : g->evl) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    ok = ok && g->p_level.alloc(g->level_bytes());
-    if (ok) {
-      g->inner = new_denoiser(bit_depth, &io, {temporal_radius, flags, curve, fwd, inv, 2 * ((motion_range + 3) / 4), chroma_gain, coarse_levels - 1,
-                                               coarse_levels > 1 ? rho : 0.0, g->stream.p});
-      if (!g->inner) {  // (the parameters were checked above: a refusal here is the device's, with its text set)
-        free_op(g);
-        return nullptr;
+  // (the device's own refusal, of the LDS a workgroup asks for, is the first thing the allocation does)
+  return open_op<g1s_denoise>("denoise", opts, bit_depth, [&](g1s_denoise &g, std::string &refusal) {
+    // the LDS a workgroup of the largest kernel these parameters select asks for, against what the device gives one
+    const bool joint = (spec.flags & G1S_DENOISE_JOINT_CHROMA) != 0;
+    {
+      const TileGeom tg = tile_geom((int)A, (int)S);
+      const JointGeom jg = spec.chroma_gain ? joint_gain_geom(tg) : joint_geom(tg);
+      const int need = spec.temporal_radius ? (joint ? jg.bytes_t : tg.bytes_t) : (joint ? jg.bytes : tg.bytes);
+      int limit = 0;
+      if (hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, g.device) != hipSuccess || need > limit) {
+        refusal = "these parameters need " + std::to_string(need) + " bytes of LDS a workgroup" + (joint ? " (joint chroma)" : "") +
+                  "; the device allows " + std::to_string(limit);
+        return false;
       }
     }
-  }
-  ok = ok && g->p_jobs.alloc(g->set_bytes()) && hipMalloc((void **)&g->d_tables.p, tables.size() * 2) == hipSuccess &&
-       hipMemcpy(g->d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && curve) {
-    const size_t nf = (size_t)1 << bit_depth;
-    ok = hipMalloc((void **)&g->d_curve.p, (nf + g1s_cv::kInvEntries) * 2) == hipSuccess &&
-         hipMemcpy(g->d_curve, fwd, nf * 2, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(g->d_curve + nf, inv, g1s_cv::kInvEntries * 2, hipMemcpyHostToDevice) == hipSuccess;
-  }
-  if (ok && chroma_gain)
-    ok = hipMalloc((void **)&g->d_gain.p, kGain * 2) == hipSuccess && hipMemcpy(g->d_gain, chroma_gain, kGain * 2, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    free_op(g);
-    return nullptr;
-  }
-  return g;
+    g.A = A, g.S = S, g.D = spec.temporal_radius, g.joint = joint;
+    g.curve = spec.curve, g.M = spec.motion_range / 2, g.gain = spec.chroma_gain != nullptr;
+    for (int i = 0; i < 4; ++i) g.q[i] = q[i];
+    g.K = spec.coarse_levels;
+    if (spec.share) {  // an inner level runs on its owner's stream: one order for kd_down, its launches and the merge
+      (void)hipStreamDestroy(g.stream.p);
+      g.stream.p = spec.share, g.borrowed_stream = true;
+    }
+    bool ok = true;
+    for (Event &e : g.ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    if (ok && g.K) {
+      // rule 26: level K - 1 on the coarse frames -- the strengths times rho, Mr' = 2 ceil(Mr / 4), everything else the same
+      const double rho = spec.coarse_ratio != 0.0 ? spec.coarse_ratio : 1.0;
+      g1s_denoise_opts_t io{};
+      io.struct_size = sizeof io, io.device = g.device, io.batch_frames = g.batch, io.search_radius = A, io.patch_radius = S;
+      io.strength = rho * h, io.chroma_strength = rho * hc;
+      for (Event &e : g.evl) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+      ok = ok && g.p_level.alloc(g.level_bytes());
+      if (ok) {
+        g.inner = new_denoiser(bit_depth, &io, {spec.temporal_radius, spec.flags, spec.curve, spec.fwd, spec.inv, 2 * ((spec.motion_range + 3) / 4),
+                                                spec.chroma_gain, g.K - 1, g.K > 1 ? rho : 0.0, g.stream.p});
+        if (!g.inner) {  // (the parameters were checked above: a refusal here is the device's, and its text is this call's)
+          refusal = g1s_last_global_error();
+          return false;
+        }
+      }
+    }
+    ok = ok && g.p_jobs.alloc(g.set_bytes()) && hipMalloc((void **)&g.d_tables.p, tables.size() * 2) == hipSuccess &&
+         hipMemcpy(g.d_tables, tables.data(), tables.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && spec.curve) {
+      const size_t nf = (size_t)1 << bit_depth;
+      ok = hipMalloc((void **)&g.d_curve.p, (nf + g1s_cv::kInvEntries) * 2) == hipSuccess &&
+           hipMemcpy(g.d_curve, spec.fwd, nf * 2, hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(g.d_curve + nf, spec.inv, g1s_cv::kInvEntries * 2, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (ok && spec.chroma_gain)
+      ok = hipMalloc((void **)&g.d_gain.p, kGain * 2) == hipSuccess && hipMemcpy(g.d_gain, spec.chroma_gain, kGain * 2, hipMemcpyHostToDevice) == hipSuccess;
+    return ok;
+  });
 }
 
 extern "C" {

@@ -1,14 +1,16 @@
 // frame_op.h -- the host scaffold the frame operations share.  Who uses what: render (grain.hip), denoise (denoise.hip),
-// measure (measure.hip), the noise levels (nlf.hip) and the surface converter (surface.hip) are BatchedOp's; the estimator
-// (estimate.hip: its copies are synchronous) takes the owners, pick_device, open_stream and batch_of, the generator
-// (engine.hip) the owners and the addressing predicate; of the file commands grain_file.cpp's and denoise_file.cpp's go
-// through rewrite_y4m, measure_file.cpp and denoise_file.cpp take device_frame and upload_frame, nlf_file.cpp batch_of alone
-// (what the file commands share among themselves is clip_file.h).  Host code only.  The first part -- the batch clamp,
-// plane geometry, the two layouts of a frame, the checks of a frame pair, the overlap of two planes -- calls nothing of HIP
-// and builds with a host compiler alone (measure_report.cpp, which needs a chroma plane's size and nothing else of this,
-// has it as a local helper and does not include this file); the second part, under __HIPCC__, is the owners of HIP objects,
-// the TRY macro, the base of a batched operation with its parameter sets and its staging buffers, a driver's device frames
-// and the .y4m rewrite loop.
+// measure (measure.hip), the noise levels (nlf.hip) and the surface converter (surface.hip) are BatchedOp's made by
+// new_op; the two meters among them take take_shape and, on top of this file, meter_op.h (their record lanes, their
+// summing launch, a temporal meter's frame before); the estimator (estimate.hip: its copies are synchronous) takes the
+// owners, pick_device, open_stream and batch_of, the generator (engine.hip) the owners and the addressing predicate; of
+// the file commands grain_file.cpp's and denoise_file.cpp's go through rewrite_y4m, measure_file.cpp and denoise_file.cpp
+// take device_frame and upload_frame, nlf_file.cpp batch_of alone (what the file commands share among themselves is
+// clip_file.h).  Host code only.  The first part -- the batch clamp, plane geometry, the two layouts of a frame, the
+// checks of a frame pair, the overlap of two planes -- calls nothing of HIP and builds with a host compiler alone
+// (measure_report.cpp, which needs a chroma plane's size and nothing else of this, has it as a local helper and does not
+// include this file); the second part, under __HIPCC__, is the owners of HIP objects, the TRY macro, the base of a
+// batched operation with its parameter sets and its staging buffers, the steps of a *_new call (opts_fit, open_op,
+// new_op), a driver's device frames and the .y4m rewrite loop.
 #pragma once
 #include <stdint.h>
 
@@ -408,6 +410,52 @@ void free_op(Op *g) {
   (void)hipSetDevice(g->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   delete g;
+}
+
+// The geometry step in front of a frame, for an operation whose flush() also waits: a frame of a new shape sends out what is
+// queued and lets it finish, then op.set_geometry(f) sizes the buffers again, as it does for the first frame.  (The meters'
+// step: render, denoise and the converter end more than a batch there and spell their own.)
+template <class Op>
+int take_shape(Op &op, const g1s_frame_t &f) {
+  if (op.have_geom && !op.geom.same_shape(f)) {
+    const int rc = op.flush();
+    if (rc) return rc;
+    op.have_geom = false;
+  }
+  return op.have_geom ? G1S_OK : op.set_geometry(f);
+}
+
+// A *_new call refuses: the text for g1s_last_global_error(), NULL for the caller
+inline std::nullptr_t refuse_new(const std::string &text) { return g1s_set_global_error_(text.c_str()), nullptr; }
+
+// the first steps of a *_new call: the global error cleared, an options struct of another size (`opts_name` names it) refused
+template <class Opts>
+bool opts_fit(const Opts *opts, const char *opts_name) {
+  g1s_set_global_error_("");
+  if (opts && opts->struct_size != sizeof(Opts)) return refuse_new(std::string(opts_name) + ".struct_size mismatch"), false;
+  return true;
+}
+
+// What the *_new calls of the BatchedOp's do once their own parameters have passed.  open_op, behind opts_fit: the device
+// (`operation` names the operation where there is none), the operation opened for `bit_depth` and opts->batch_frames, then
+// `alloc(*op, refusal)`, the operation's own allocations (false: failed).  A failure is "HIP initialisation failed: ..."
+// unless alloc put a text of its own into `refusal`; the operation is freed and the call returns NULL.  new_op is the two
+// together, for an operation that reads nothing of its opts before it has a device.
+template <class Op, class Opts, class Alloc>
+Op *open_op(const char *operation, const Opts *opts, uint32_t bit_depth, Alloc &&alloc) {
+  int device = 0;
+  const std::string no_device = pick_device(opts ? opts->device : -1, operation, &device);
+  if (!no_device.empty()) return refuse_new(no_device);
+  Op *op = new Op;
+  std::string refusal;
+  if (op->open(device, bit_depth, opts ? opts->batch_frames : 0) && alloc(*op, refusal)) return op;
+  refuse_new(refusal.empty() ? std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError()) : refusal);
+  free_op(op);
+  return nullptr;
+}
+template <class Op, class Opts, class Alloc>
+Op *new_op(const char *operation, const Opts *opts, const char *opts_name, uint32_t bit_depth, Alloc &&alloc) {
+  return opts_fit(opts, opts_name) ? open_op<Op>(operation, opts, bit_depth, alloc) : nullptr;
 }
 
 // A file driver's own device frames: a frame of geometry g whose planes lie from `base` on in layout `lay` ...

@@ -583,45 +583,26 @@ extern "C" {
 const int16_t *g1s_grain_gaussian_sequence(void) { return kGaussHost; }
 
 g1s_grain_t *g1s_grain_new(uint32_t bit_depth, const g1s_grain_opts_t *opts) {
-  g1s_set_global_error_("");
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
-    g1s_set_global_error_("film grain synthesis is defined for bit depths 8, 10 and 12");
-    return nullptr;
-  }
-  if (opts && opts->struct_size != sizeof(g1s_grain_opts_t)) {
-    g1s_set_global_error_("g1s_grain_opts_t.struct_size mismatch");
-    return nullptr;
-  }
-  int device = 0;
-  const std::string no_device = pick_device(opts ? opts->device : -1, "film grain synthesis", &device);
-  if (!no_device.empty()) {
-    g1s_set_global_error_(no_device.c_str());
-    return nullptr;
-  }
-  g1s_grain *g = new g1s_grain;
-  g->clip_restricted = opts && opts->clip_to_restricted_range;
-  g->mc_identity = opts && opts->mc_identity;
-  // the jump table: column b of M^(24 l) is the register 24 l steps after the seed 1 << b
-  std::vector<uint16_t> jump((size_t)kThreads * 16);
-  for (int b = 0; b < 16; ++b) {
-    uint32_t r = 1u << b;
-    for (int l = 0; l < kThreads; ++l) {
-      jump[(size_t)l * 16 + b] = (uint16_t)r;
-      for (int k = 0; k < kDrawsPerLane; ++k) r = lfsr_step(r);
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return refuse_new("film grain synthesis is defined for bit depths 8, 10 and 12");
+  return new_op<g1s_grain>("film grain synthesis", opts, "g1s_grain_opts_t", bit_depth, [&](g1s_grain &g, std::string &) {
+    g.clip_restricted = opts && opts->clip_to_restricted_range;
+    g.mc_identity = opts && opts->mc_identity;
+    // the jump table: column b of M^(24 l) is the register 24 l steps after the seed 1 << b
+    std::vector<uint16_t> jump((size_t)kThreads * 16);
+    for (int b = 0; b < 16; ++b) {
+      uint32_t r = 1u << b;
+      for (int l = 0; l < kThreads; ++l) {
+        jump[(size_t)l * 16 + b] = (uint16_t)r;
+        for (int k = 0; k < kDrawsPerLane; ++k) r = lfsr_step(r);
+      }
     }
-  }
-  bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
-  const uint32_t B = g->batch;
-  for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  ok = ok && g->p_jobs.alloc(B) && g->p_segs.alloc(B) && hipMalloc((void **)&g->d_jump.p, jump.size() * 2) == hipSuccess &&
-       hipMalloc((void **)&g->d_tpl.p, sizeof(int16_t) * 3 * kTplSlot * B) == hipSuccess && hipMalloc((void **)&g->d_luts.p, (size_t)768 * B) == hipSuccess &&
-       hipMemcpy(g->d_jump, jump.data(), jump.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    g1s_grain_free(g);
-    return nullptr;
-  }
-  return g;
+    const uint32_t B = g.batch;
+    bool ok = true;
+    for (Event &e : g.ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    return ok && g.p_jobs.alloc(B) && g.p_segs.alloc(B) && hipMalloc((void **)&g.d_jump.p, jump.size() * 2) == hipSuccess &&
+           hipMalloc((void **)&g.d_tpl.p, sizeof(int16_t) * 3 * kTplSlot * B) == hipSuccess && hipMalloc((void **)&g.d_luts.p, (size_t)768 * B) == hipSuccess &&
+           hipMemcpy(g.d_jump, jump.data(), jump.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+  });
 }
 
 int g1s_grain_frame(g1s_grain_t *g, const g1s_segment_t *params, const g1s_frame_t *in, g1s_frame_t *out) {

@@ -18,7 +18,7 @@
 // sample (clean_bin); km_tail is one template for the plain and the temporal layout.  lag_pass, the 5 x 5 row loop of
 // km_measure_x's three pairings, stands before km_measure_t, which has the same loop written out: calling lag_pass from it,
 // and one epilogue helper for the waves' accumulators, gave km_measure, km_measure_s and km_measure_t other code than what
-// was measured before, and timing rows above it (profiles/measure_refactor.txt).  The kernels compile to that code again.  The host engine below them keeps a RecordLane a record kind.  What is done
+// was measured before, and timing rows above it (profiles/measure_refactor.txt).  The kernels compile to that code again.  The host engine below them keeps a RecordLane (meter_op.h, shared with the noise levels) a record kind.  What is done
 // with the records on the host -- the sums and the four reports -- needs no device and is in measure_report.cpp; the file
 // commands (`measure`, `check`) stand above the per-frame calls in measure_file.cpp.
 //
@@ -41,10 +41,12 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
-#include "frame_op.h"
+#include "meter_op.h"
 #include "wave_sum.hip.h"
 
 namespace {
+
+using g1s_op::TailParams;
 
 constexpr int kTW = 64, kTH = 128, kHalo = 3;
 constexpr int kLW = kTW + 2 * kHalo, kLH = kTH + kHalo;  // the LDS tile: halo left, right and above
@@ -72,12 +74,6 @@ struct ClassParams {
   int plane0;                    // first plane of the class: 0 luma, 1 chroma
   int W, xdec, ydec, shift;      // luma width, chroma decimation, B - 5
   uint32_t units_frame, unit_base, units_plane;
-};
-
-struct TailParams {
-  const unsigned long long *partials;
-  unsigned long long *records;  // [pair] g1s_measure_record_t
-  uint32_t tiles_frame, tiles[3], tile_base[3];
 };
 
 template <int BPS>
@@ -212,10 +208,10 @@ __global__ __launch_bounds__(kTailThreads) void km_tail(TailParams p) {
   static_assert(N <= WIDTH, "km_tail gives an entry a thread of a group");
   __shared__ unsigned long long s_sum[GROUPS][WIDTH];
   const int c = (int)blockIdx.x, i = (int)threadIdx.x % WIDTH, g = (int)threadIdx.x / WIDTH;
-  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * N;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.units_frame + p.unit_base[c]) * N;
   unsigned long long t = 0;
   if (i < N)
-    for (uint32_t k = (uint32_t)g; k < p.tiles[c]; k += GROUPS) t += src[(size_t)k * N + i];
+    for (uint32_t k = (uint32_t)g; k < p.units[c]; k += GROUPS) t += src[(size_t)k * N + i];
   s_sum[g][i] = t;
   __syncthreads();
   if (g == 0 && i < N) {
@@ -720,9 +716,9 @@ __global__ __launch_bounds__(kThreads) void km_measure_s(ScaleParams p) {
 __global__ __launch_bounds__(kTailThreads) void km_tail_s(TailParams p) {
   const int c = (int)blockIdx.x, i = (int)threadIdx.x;
   if (i >= kSEntries) return;
-  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.tiles_frame + p.tile_base[c]) * kSEntries;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.units_frame + p.unit_base[c]) * kSEntries;
   unsigned long long t = 0;
-  for (uint32_t k = 0; k < p.tiles[c]; ++k) t += src[(size_t)k * kSEntries + i];
+  for (uint32_t k = 0; k < p.units[c]; ++k) t += src[(size_t)k * kSEntries + i];
   // g1s_measure_srecord_t as 64-bit words: n[3][5][32], s1[3][5][32], s2[3][5][32]; entry i = (scale, field, bin)
   const int scale = i / (3 * kBins), field = (i / kBins) % 3, bin = i % kBins;
   unsigned long long *rec = p.records + (size_t)blockIdx.y * (sizeof(g1s_measure_srecord_t) / 8);
@@ -734,101 +730,21 @@ __global__ __launch_bounds__(kTailThreads) void km_tail_s(TailParams p) {
 // =============================================================== host engine =====
 using namespace g1s_op;
 
-namespace {
-
-// How a frame's planes are cut into the units workgroups take (km_measure's tiles, km_measure_s's strips; for the tail of
-// km_measure_x the pairings of the chroma tiles): a plane's count, where its partial records start in a job's, a job's count.
-struct Units {
-  uint32_t n[3] = {0, 0, 0}, base[3] = {0, 0, 0}, frame = 0;
-  // units of unit_w x kTH samples over the planes of g
-  void cut(const PlaneGeom &g, int unit_w) {
-    frame = 0;
-    for (int c = 0; c < 3; ++c) {
-      n[c] = c < g.nplanes ? (uint32_t)(((g.pw(c) + unit_w - 1) / unit_w) * ((g.ph(c) + kTH - 1) / kTH)) : 0u;
-      base[c] = frame;
-      frame += n[c];
-    }
-  }
-};
-
-// What a record kind (plain, temporal, cross, scales) owns in a meter, and the steps of a batch that are the same for all.
-template <class Rec>
-struct RecordLane {
-  bool on = false;  // does the meter make this kind?
-  Event ev[2];      // round the kind's launches, while timing
-  DevBuf<unsigned long long> d_partials;
-  size_t partials_cap = 0;
-  DevBuf<Rec> d_recs;  // a batch's records
-  PinnedBuf<Rec> h_recs;
-  std::vector<Rec> records;  // since the last hand-over
-  double ms = 0;             // in the kind's launches of the timed batches
-  uint64_t timed = 0;        // and the records those made
-
-  unsigned long long *words() const { return reinterpret_cast<unsigned long long *>(d_recs.p); }
-  // for batches of up to `batch` records (nothing for a kind the meter does not make)
-  bool alloc(uint32_t batch) {
-    if (!on) return true;
-    bool ok = true;
-    for (Event &e : ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    return ok && hipMalloc((void **)&d_recs.p, sizeof(Rec) * batch) == hipSuccess &&
-           hipHostMalloc((void **)&h_recs.p, sizeof(Rec) * batch, hipHostMallocDefault) == hipSuccess;
-  }
-  // room for `need` words of partial records
-  hipError_t size_partials(size_t need) {
-    if (!on || need <= partials_cap) return hipSuccess;
-    d_partials = DevBuf<unsigned long long>();
-    const hipError_t e = hipMalloc((void **)&d_partials.p, need * sizeof(unsigned long long));
-    if (e == hipSuccess) partials_cap = need;
-    return e;
-  }
-  // a batch of n records begins: zeros (the planes a frame does not have), the first event
-  hipError_t begin(uint32_t n, bool timing, hipStream_t s) {
-    const hipError_t e = hipMemsetAsync(d_recs, 0, sizeof(Rec) * n, s);
-    return e != hipSuccess || !timing ? e : hipEventRecord(ev[0], s);
-  }
-  // behind its launches: the second event, the records back
-  hipError_t end(uint32_t n, bool timing, hipStream_t s) {
-    const hipError_t e = timing ? hipEventRecord(ev[1], s) : hipSuccess;
-    return e != hipSuccess ? e : hipMemcpyAsync(h_recs, d_recs, sizeof(Rec) * n, hipMemcpyDeviceToHost, s);
-  }
-  // after the wait: the time between the events of a timed batch; then the records to those held
-  hipError_t clock(uint32_t n) {
-    float t = 0;
-    const hipError_t e = hipEventElapsedTime(&t, ev[0], ev[1]);
-    if (e == hipSuccess) ms += t, timed += n;
-    return e;
-  }
-  void collect(uint32_t n) { records.insert(records.end(), h_recs.p, h_recs.p + n); }
-  // the records held into the caller's `cap` entries
-  int hand_over(Rec *out, size_t cap, size_t *n_out) {
-    if (n_out) *n_out = records.size();
-    if (records.size() > cap || (!out && !records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-    if (!records.empty()) std::memcpy(out, records.data(), sizeof(Rec) * records.size());
-    records.clear();
-    return G1S_OK;
-  }
-};
-
-}  // namespace
-
+// A RecordLane (meter_op.h) a record kind: plain, temporal, cross, scales.
 struct g1s_measure : BatchedOp {
-  std::vector<MeasureJob> jobs;  // the batch being filled
-  ParamSets<MeasureJob> p_jobs;
-  // pairings: km_measure_x's partial records as km_tail<4> reads them, a pairing where a plane is, the chroma plane's tiles each
+  JobQueue<MeasureJob> pairs;  // the batch being filled: every kind but the temporal one reads it, uploaded once
+  // how a frame's planes are cut into the units workgroups take: km_measure's tiles, km_measure_s's strips; pairings:
+  // km_measure_x's partial records as km_tail<4> reads them, a pairing where a plane is, the chroma plane's tiles each
   Units tiles, strips, pairings;
   RecordLane<g1s_measure_record_t> plain;      // always on
   RecordLane<g1s_measure_trecord_t> temporal;  // rules 7 - 11: a record a temporal job
   RecordLane<g1s_measure_xrecord_t> cross;     // rules 12 - 17: a record a pair, from the batch's own jobs
   RecordLane<g1s_measure_srecord_t> scales;    // rules 18 - 23: likewise
-  // a temporal meter: the run's last pair as the kernels read it (its planes: the caller's, or a slot of the input rings,
-  // which then have batch + 1 slots filled round-robin) and the batch's temporal jobs
-  bool have_prev = false;
+  // a temporal meter: the run's last pair as the kernels read it (side 0 noisy, side 1 clean; the ring moves on with every
+  // pair; the caller's device planes are kept over a hand-over) and the batch's temporal jobs
   MeasureJob prev{};
-  bool prev_staged[2] = {false, false};  // (are the planes of prev.a / prev.b the meter's own: a ring's or d_keep's?)
-  uint32_t ring_at = 0;
-  DevBuf<uint8_t> d_keep[2];  // a frame each: the caller's device planes of the run's last pair, kept over a hand-over
-  std::vector<TemporalJob> tjobs;
-  ParamSets<TemporalJob> p_tjobs;
+  FrameBefore<2> before;
+  JobQueue<TemporalJob> tpairs;
   // the chroma launches alone, for tools/bench_measure.py --cross (recorded only while timing is on)
   Event ev_c[2], ev_tc[2];
   double ms_chroma = 0, ms_tchroma = 0;
@@ -838,25 +754,20 @@ struct g1s_measure : BatchedOp {
   Params class_params(const Job *d_jobs, unsigned long long *partials, int plane0, int unit_w, const Units &u) const;
   template <class Params, class Job>
   int launch_classes(void (*kernel)(Params), const Job *d_jobs, uint32_t n, unsigned long long *partials, int unit_w, const Units &u, Event *chroma_ev);
-  template <class Rec>
-  int launch_tail(void (*kernel)(TailParams), unsigned planes, uint32_t n, const RecordLane<Rec> &lane, const Units &u);
   int flush();
-  int keep_prev();
-  template <class Rec>
-  int finish(RecordLane<Rec> &lane, Rec *out, size_t cap, size_t *n_out);
+  int settle();
 };
 
 int g1s_measure::set_geometry(const g1s_frame_t &f) {
   set_frame_geometry(f);
-  tiles.cut(geom, kTW), strips.cut(geom, kSW);
-  pairings.frame = 3 * tiles.n[1];
-  for (int j = 0; j < 3; ++j) pairings.n[j] = tiles.n[1], pairings.base[j] = (uint32_t)j * tiles.n[1];
+  tiles.cut(geom, kTW, kTH), strips.cut(geom, kSW, kTH);
+  for (int j = 0; j < 3; ++j) pairings.n[j] = tiles.n[1];
+  pairings.lay();
   G1S_OP_TRY(plain.size_partials((size_t)tiles.frame * kEntries * batch));
   G1S_OP_TRY(temporal.size_partials((size_t)tiles.frame * kTEntries * batch));
   G1S_OP_TRY(cross.size_partials(geom.nplanes == 3 ? (size_t)pairings.frame * kTEntries * batch : 0));
   G1S_OP_TRY(scales.size_partials((size_t)strips.frame * kSEntries * batch));
-  have_prev = false, ring_at = 0;  // (a new geometry ends the run; the rings are made again)
-  d_keep[0] = DevBuf<uint8_t>(), d_keep[1] = DevBuf<uint8_t>();
+  before.reset(), before.next_slot = 0;  // (a new geometry ends the run; the rings are made again)
   return G1S_OK;
 }
 
@@ -888,40 +799,27 @@ int g1s_measure::launch_classes(void (*kernel)(Params), const Job *d_jobs, uint3
   return G1S_OK;
 }
 
-// the summing launch of a kind: its partial records, cut as `u`, into the n records of the batch
-template <class Rec>
-int g1s_measure::launch_tail(void (*kernel)(TailParams), unsigned planes, uint32_t n, const RecordLane<Rec> &lane, const Units &u) {
-  TailParams tp{};
-  tp.partials = lane.d_partials, tp.records = lane.words(), tp.tiles_frame = u.frame;
-  for (int c = 0; c < 3; ++c) tp.tiles[c] = u.n[c], tp.tile_base[c] = u.base[c];
-  hipLaunchKernelGGL(kernel, dim3(planes, n), dim3(kTailThreads), 0, stream, tp);
-  G1S_OP_TRY(hipGetLastError());
-  return G1S_OK;
-}
-
 // the queued pairs as one batch, kind after kind on the meter's stream: a launch per plane class, the summing launch, the
 // records back; then all waited for
 int g1s_measure::flush() {
-  const uint32_t B = (uint32_t)jobs.size(), T = (uint32_t)tjobs.size();
+  const uint32_t B = (uint32_t)pairs.jobs.size(), T = (uint32_t)tpairs.jobs.size();
   if (!B) return G1S_OK;
   int set, rc = next_set(&set);
   if (rc) return rc;
   const bool wide = bps == 2;
   const unsigned planes = (unsigned)geom.nplanes;
-  std::memcpy(p_jobs.h[set], jobs.data(), sizeof(MeasureJob) * B);
-  G1S_OP_TRY(p_jobs.upload(set, B, stream));
-  const MeasureJob *d_jobs = p_jobs.d[set];
+  G1S_OP_TRY(pairs.upload(set, stream));
+  const MeasureJob *d_jobs = pairs.sets.d[set];
   G1S_OP_TRY(plain.begin(B, timing, stream));
   if ((rc = launch_classes(wide ? km_measure<2> : km_measure<1>, d_jobs, B, plain.d_partials, kTW, tiles, ev_c)) != 0) return rc;
-  if ((rc = launch_tail(km_tail<3>, planes, B, plain, tiles)) != 0) return rc;
+  G1S_OP_TRY(plain.sum(km_tail<3>, planes, B, kTailThreads, tiles, stream));
   G1S_OP_TRY(plain.end(B, timing, stream));
   // the batch's temporal jobs behind it: the same launches with km_measure_t and km_tail<4>
   if (T) {
-    std::memcpy(p_tjobs.h[set], tjobs.data(), sizeof(TemporalJob) * T);
-    G1S_OP_TRY(p_tjobs.upload(set, T, stream));
+    G1S_OP_TRY(tpairs.upload(set, stream));
     G1S_OP_TRY(temporal.begin(T, timing, stream));
-    if ((rc = launch_classes(wide ? km_measure_t<2> : km_measure_t<1>, p_tjobs.d[set].p, T, temporal.d_partials, kTW, tiles, ev_tc)) != 0) return rc;
-    if ((rc = launch_tail(km_tail<4>, planes, T, temporal, tiles)) != 0) return rc;
+    if ((rc = launch_classes(wide ? km_measure_t<2> : km_measure_t<1>, tpairs.sets.d[set].p, T, temporal.d_partials, kTW, tiles, ev_tc)) != 0) return rc;
+    G1S_OP_TRY(temporal.sum(km_tail<4>, planes, T, kTailThreads, tiles, stream));
     G1S_OP_TRY(temporal.end(T, timing, stream));
   }
   // a cross meter: the batch's own jobs once more, one km_measure_x launch and km_tail<4> over its partials, where a pairing
@@ -937,7 +835,7 @@ int g1s_measure::flush() {
       void (*const kernel)(CrossParams) = wide ? km_measure_x<2> : km_measure_x<1>;
       hipLaunchKernelGGL(kernel, dim3(tiles.n[1], 1u, B), dim3(kThreads), 0, stream, xp);
       G1S_OP_TRY(hipGetLastError());
-      if ((rc = launch_tail(km_tail<4>, 3u, B, cross, pairings)) != 0) return rc;
+      G1S_OP_TRY(cross.sum(km_tail<4>, 3u, B, kTailThreads, pairings, stream));
     }
     G1S_OP_TRY(cross.end(B, timing, stream));
   }
@@ -945,7 +843,7 @@ int g1s_measure::flush() {
   if (scales.on) {
     G1S_OP_TRY(scales.begin(B, timing, stream));
     if ((rc = launch_classes(wide ? km_measure_s<2> : km_measure_s<1>, d_jobs, B, scales.d_partials, kSW, strips, nullptr)) != 0) return rc;
-    if ((rc = launch_tail(km_tail_s, planes, B, scales, strips)) != 0) return rc;
+    G1S_OP_TRY(scales.sum(km_tail_s, planes, B, kTailThreads, strips, stream));
     G1S_OP_TRY(scales.end(B, timing, stream));
   }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
@@ -968,64 +866,35 @@ int g1s_measure::flush() {
   if (T) temporal.collect(T);
   if (cross.on) cross.collect(B);
   if (scales.on) scales.collect(B);
-  jobs.clear();
-  tjobs.clear();
+  pairs.jobs.clear();
+  tpairs.jobs.clear();
   return G1S_OK;
 }
 
-// The run's last pair survives a hand-over: the planes of it that are the caller's are copied into a frame of the meter's
-// own, device to device, and read from there by the next pair's temporal job.  (After flush(): nothing is in flight.)
-int g1s_measure::keep_prev() {
-  if (!have_prev) return G1S_OK;
-  for (int side = 0; side < 2; ++side) {
-    if (prev_staged[side]) continue;
-    const uint8_t **plane = side ? prev.b : prev.a;
-    uint32_t *stride = side ? prev.b_stride : prev.a_stride;
-    if (!d_keep[side] && hipMalloc((void **)&d_keep[side].p, stage.frame) != hipSuccess)
-      return fail(G1S_ERR_HIP, "hipMalloc of the kept frame failed");
-    for (int c = 0; c < geom.nplanes; ++c) {
-      uint8_t *dst = d_keep[side] + stage.off[c];
-      G1S_OP_TRY(hipMemcpy2DAsync(dst, stage.row[c], plane[c], stride[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToDevice, stream));
-      plane[c] = dst, stride[c] = (uint32_t)stage.row[c];
-    }
-    prev_staged[side] = true;
-  }
-  return wait();
-}
-
-// g1s_measure_finish*: what is queued goes out, the run's last pair is kept, the kind's records are handed over
-template <class Rec>
-int g1s_measure::finish(RecordLane<Rec> &lane, Rec *out, size_t cap, size_t *n_out) {
-  (void)hipSetDevice(device);
+// A hand-over: what is queued goes out, and the run's last pair survives it -- the planes of it that are the caller's are
+// copied into frames of the meter's own and read from there by the next pair's temporal job.  (After flush(): nothing is in
+// flight.)
+int g1s_measure::settle() {
   int rc = flush();
-  if (rc || (rc = keep_prev()) != 0) return rc;
-  return lane.hand_over(out, cap, n_out);
+  if (rc || !before.have) return rc;
+  if (before.room(0, stage) != hipSuccess || before.room(1, stage) != hipSuccess) return fail(G1S_ERR_HIP, "hipMalloc of the kept frame failed");
+  G1S_OP_TRY(before.keep(0, geom, stage, prev.a, prev.a_stride, stream));
+  G1S_OP_TRY(before.keep(1, geom, stage, prev.b, prev.b_stride, stream));
+  return wait();
 }
 
 namespace {
 
-// the meter is not of the kind the call is for: `maker` is the call that makes one
-int not_made_by(g1s_measure_t *m, const char *maker) {
-  m->err = std::string("the meter was not made by ") + maker;  // (not sticky: err_code stays 0)
-  return G1S_ERR_INVALID;
-}
-const char kTemporalMaker[] = "g1s_measure_new_temporal", kCrossMaker[] = "g1s_measure_new_modes with G1S_MEASURE_CROSS",
-           kScalesMaker[] = "g1s_measure_new_scales";
-
-// g1s_measure_finish and its three kin: the checks, then the lane's hand-over
-template <class Rec>
-int finish_kind(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, const char *maker, Rec *out, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  if (!(m->*lane).on) return not_made_by(m, maker);
-  return m->finish(m->*lane, out, cap, n_out);
-}
+// what a meter without the kind says to the kind's calls
+const char kNotTemporal[] = "the meter was not made by g1s_measure_new_temporal",
+           kNotCross[] = "the meter was not made by g1s_measure_new_modes with G1S_MEASURE_CROSS",
+           kNotScales[] = "the meter was not made by g1s_measure_new_scales";
 
 // the four *_timing calls: the time in a kind's launches in the timed batches, the records those made
 template <class Rec>
 int kind_timing(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, double *ms, uint64_t *n) {
   if (!m) return G1S_ERR_INVALID;
-  if (ms) *ms = (m->*lane).ms;
+  if (ms) *ms = (m->*lane).ms[0];
   if (n) *n = (m->*lane).timed;
   return G1S_OK;
 }
@@ -1033,41 +902,21 @@ int kind_timing(g1s_measure_t *m, RecordLane<Rec> g1s_measure::*lane, double *ms
 // g1s_measure_new, g1s_measure_new_temporal, g1s_measure_new_modes and g1s_measure_new_scales: the same refusals, the same
 // meter but for the lanes that are on
 g1s_measure_t *measure_new(uint32_t bit_depth, const g1s_measure_opts_t *opts, uint32_t modes, bool scales = false) {
-  g1s_set_global_error_("");
-  if (modes & ~(uint32_t)(G1S_MEASURE_TEMPORAL | G1S_MEASURE_CROSS)) {
-    g1s_set_global_error_("unknown mode bits: g1s_measure_new_modes takes G1S_MEASURE_TEMPORAL and G1S_MEASURE_CROSS");
-    return nullptr;
-  }
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
-    g1s_set_global_error_("measure is defined for bit depths 8, 10 and 12");
-    return nullptr;
-  }
-  if (opts && opts->struct_size != sizeof(g1s_measure_opts_t)) {
-    g1s_set_global_error_("g1s_measure_opts_t.struct_size mismatch");
-    return nullptr;
-  }
-  int device = 0;
-  const std::string no_device = pick_device(opts ? opts->device : -1, "measure", &device);
-  if (!no_device.empty()) {
-    g1s_set_global_error_(no_device.c_str());
-    return nullptr;
-  }
-  g1s_measure *m = new g1s_measure;
-  m->plain.on = true, m->temporal.on = (modes & G1S_MEASURE_TEMPORAL) != 0, m->cross.on = (modes & G1S_MEASURE_CROSS) != 0, m->scales.on = scales;
-  bool ok = m->open(device, bit_depth, opts ? opts->batch_frames : 0);
-  const uint32_t B = m->batch;
-  for (Event &e : m->ev_c) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  ok = ok && m->p_jobs.alloc(B) && m->plain.alloc(B) && m->temporal.alloc(B) && m->cross.alloc(B) && m->scales.alloc(B);
-  if (m->temporal.on) {
-    for (Event &e : m->ev_tc) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    ok = ok && m->p_tjobs.alloc(B);
-  }
-  if (!ok) {
-    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    g1s_measure_free(m);
-    return nullptr;
-  }
-  return m;
+  if (modes & ~(uint32_t)(G1S_MEASURE_TEMPORAL | G1S_MEASURE_CROSS))
+    return refuse_new("unknown mode bits: g1s_measure_new_modes takes G1S_MEASURE_TEMPORAL and G1S_MEASURE_CROSS");
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return refuse_new("measure is defined for bit depths 8, 10 and 12");
+  return new_op<g1s_measure>("measure", opts, "g1s_measure_opts_t", bit_depth, [&](g1s_measure &m, std::string &) {
+    m.plain.on = true, m.temporal.on = (modes & G1S_MEASURE_TEMPORAL) != 0, m.cross.on = (modes & G1S_MEASURE_CROSS) != 0, m.scales.on = scales;
+    const uint32_t B = m.batch;
+    bool ok = true;
+    for (Event &e : m.ev_c) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    ok = ok && m.pairs.alloc(B) && m.plain.alloc(B) && m.temporal.alloc(B) && m.cross.alloc(B) && m.scales.alloc(B);
+    if (m.temporal.on) {
+      for (Event &e : m.ev_tc) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+      ok = ok && m.tpairs.alloc(B);
+    }
+    return ok;
+  });
 }
 
 }  // namespace
@@ -1090,53 +939,48 @@ int g1s_measure_frame(g1s_measure_t *m, const g1s_frame_t *noisy, const g1s_fram
                                       "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)", "noisy and clean");
   if (no.code) return m->fail(no.code, no.text);
   if (m->scales.on && !scales_size_ok(m->bit_depth, noisy->width, noisy->height)) return m->fail(G1S_ERR_INVALID, scales_refusal_text());
-  int rc;
-  if (m->have_geom && !m->geom.same_shape(*noisy)) {
-    // a new geometry: what is queued goes out and finishes first, the buffers are sized again
-    if ((rc = m->flush()) != 0) return rc;
-    m->have_geom = false;
-  }
-  if (!m->have_geom && (rc = m->set_geometry(*noisy)) != 0) return rc;
+  int rc = take_shape(*m, *noisy);
+  if (rc) return rc;
   MeasureJob job{};
   // a plain meter: the batch's slots; a temporal meter: rings of batch + 1 slots, so that the pair before the batch's first
   // pair is still there
   const bool temporal = m->temporal.on;
-  const uint32_t slots = temporal ? m->batch + 1 : m->batch, slot = temporal ? m->ring_at : (uint32_t)m->jobs.size();
+  const uint32_t slots = temporal ? m->before.slots(m->batch) : m->batch, slot = temporal ? m->before.next_slot : (uint32_t)m->pairs.jobs.size();
   if ((rc = m->stage_in(*noisy, slot, slots, job.a, job.a_stride, 0)) != 0) return rc;
   if ((rc = m->stage_in(*clean, slot, slots, job.b, job.b_stride, 1)) != 0) return rc;
   if ((rc = m->wait_host_input(noisy->on_device == 0 ? *noisy : *clean)) != 0) return rc;
-  m->jobs.push_back(job);
+  m->pairs.jobs.push_back(job);
   if (temporal) {
-    if (m->have_prev) m->tjobs.push_back(TemporalJob{job, m->prev});
-    m->prev = job, m->have_prev = true, m->ring_at = (slot + 1) % slots;
-    m->prev_staged[0] = noisy->on_device != 1, m->prev_staged[1] = clean->on_device != 1;
+    if (m->before.have) m->tpairs.jobs.push_back(TemporalJob{job, m->prev});
+    m->prev = job, m->before.have = true, m->before.advance(m->batch);
+    m->before.callers[0] = noisy->on_device == 1, m->before.callers[1] = clean->on_device == 1;
   }
-  return m->jobs.size() >= m->batch ? m->flush() : G1S_OK;
+  return m->pairs.jobs.size() >= m->batch ? m->flush() : G1S_OK;
 }
 
 int g1s_measure_cut(g1s_measure_t *m) {
   if (!m) return G1S_ERR_INVALID;
   if (m->err_code) return m->err_code;
-  if (!m->temporal.on) return not_made_by(m, kTemporalMaker);
+  if (!m->temporal.on) return not_made(m, kNotTemporal);
   (void)hipSetDevice(m->device);
-  m->have_prev = false;
+  m->before.have = false;
   return m->flush();
 }
 
 int g1s_measure_finish(g1s_measure_t *m, g1s_measure_record_t *per_frame, size_t cap, size_t *n_out) {
-  return finish_kind(m, &g1s_measure::plain, "", per_frame, cap, n_out);
+  return finish_kind(m, &g1s_measure::plain, kAlwaysMade, per_frame, cap, n_out);
 }
 
 int g1s_measure_finish_temporal(g1s_measure_t *m, g1s_measure_trecord_t *per_pair, size_t cap, size_t *n_out) {
-  return finish_kind(m, &g1s_measure::temporal, kTemporalMaker, per_pair, cap, n_out);
+  return finish_kind(m, &g1s_measure::temporal, kNotTemporal, per_pair, cap, n_out);
 }
 
 int g1s_measure_finish_cross(g1s_measure_t *m, g1s_measure_xrecord_t *per_pair, size_t cap, size_t *n_out) {
-  return finish_kind(m, &g1s_measure::cross, kCrossMaker, per_pair, cap, n_out);
+  return finish_kind(m, &g1s_measure::cross, kNotCross, per_pair, cap, n_out);
 }
 
 int g1s_measure_finish_scales(g1s_measure_t *m, g1s_measure_srecord_t *per_pair, size_t cap, size_t *n_out) {
-  return finish_kind(m, &g1s_measure::scales, kScalesMaker, per_pair, cap, n_out);
+  return finish_kind(m, &g1s_measure::scales, kNotScales, per_pair, cap, n_out);
 }
 
 int g1s_measure_set_timing(g1s_measure_t *m, int enable, double *ms_kernel, uint64_t *frames) {

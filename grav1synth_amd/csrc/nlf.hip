@@ -37,12 +37,14 @@
 #include <vector>
 
 #include "../../include/g1s_diff.h"
-#include "frame_op.h"
+#include "meter_op.h"
 #include "nlf.h"
 #include "strip_walk.hip.h"
 #include "wave_sum.hip.h"
 
 namespace {
+
+using g1s_op::TailParams;
 
 constexpr int kBins = g1s_nl::kBins, kEntries = 3 * kBins;  // a partial record: n[32], a[32], q[32]
 constexpr int kTailGroups = 4;
@@ -70,12 +72,6 @@ struct NlfParams {
   int W, H, xdec, ydec;          // luma size and chroma decimation (read by the chroma launch)
   int col_strips, row_strips;
   uint32_t wgs_frame, wg_base, wgs_plane;
-};
-
-struct TailParams {
-  const unsigned long long *partials;
-  unsigned long long *records;  // [frame] g1s_nlf_record_t
-  uint32_t wgs_frame, wgs[3], wg_base[3];
 };
 
 // A lane's run: the bin its samples are in and their sums so far (cur < 0: none), and the wave's sums in LDS they go to.
@@ -234,10 +230,10 @@ auto strip_kernel(const NlfParams<NlfTJob> &) { return &k_nlf_t<BPS, B, CHROMA>;
 __global__ __launch_bounds__(128 * kTailGroups) void k_nlf_tail(TailParams p) {
   __shared__ unsigned long long s_sum[kTailGroups][128];
   const int c = (int)blockIdx.x, i = (int)threadIdx.x & 127, g = (int)threadIdx.x >> 7;
-  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.wgs_frame + p.wg_base[c]) * kEntries;
+  const unsigned long long *src = p.partials + ((size_t)blockIdx.y * p.units_frame + p.unit_base[c]) * kEntries;
   unsigned long long t = 0;
   if (i < kEntries)
-    for (uint32_t k = (uint32_t)g; k < p.wgs[c]; k += kTailGroups) t += src[(size_t)k * kEntries + i];
+    for (uint32_t k = (uint32_t)g; k < p.units[c]; k += kTailGroups) t += src[(size_t)k * kEntries + i];
   s_sum[g][i] = t;
   __syncthreads();
   if (g == 0 && i < kEntries) {
@@ -255,75 +251,44 @@ __global__ __launch_bounds__(128 * kTailGroups) void k_nlf_tail(TailParams p) {
 using namespace g1s_op;
 
 // What the meter keeps per kind of record: frames (NlfJob, g1s_nlf_record_t, k_nlf) and pairs (NlfTJob, g1s_nlf_trecord_t,
-// k_nlf_t).  A batch of either goes through g1s_nlf::run.
+// k_nlf_t): a RecordLane (meter_op.h) with its queued jobs, timed as two intervals, luma and chroma.  A batch of either goes
+// through g1s_nlf::run.
 template <class Job, class Record>
-struct RecordLane {
-  using job_type = Job;
-  std::vector<Job> jobs;  // the batch being filled
-  ParamSets<Job> p_jobs;
-  DevBuf<unsigned long long> d_partials;
-  size_t partials_cap = 0;
-  DevBuf<Record> d_recs;
-  PinnedBuf<Record> h_recs;
-  std::vector<Record> records;  // since the last hand-over
-  Event ev[3];                  // before the luma launch, between the two, behind the chroma launch
-  double ms_luma = 0, ms_chroma = 0;
-  uint64_t timed = 0;
-  bool alloc(uint32_t B) {
-    bool ok = p_jobs.alloc(B) && hipMalloc((void **)&d_recs.p, sizeof(Record) * B) == hipSuccess &&
-              hipHostMalloc((void **)&h_recs.p, sizeof(Record) * B, hipHostMallocDefault) == hipSuccess;
-    for (Event &e : ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-    return ok;
-  }
-  void times(double *luma, double *chroma, uint64_t *n) const {
-    if (luma) *luma = ms_luma;
-    if (chroma) *chroma = ms_chroma;
-    if (n) *n = timed;
+struct Kind : RecordLane<Record, 2> {
+  JobQueue<Job> queue;
+  bool alloc(uint32_t B) { return !this->on || (queue.alloc(B) && RecordLane<Record, 2>::alloc(B)); }
+  int times(double *luma, double *chroma, uint64_t *n) const {
+    if (luma) *luma = this->ms[0];
+    if (chroma) *chroma = this->ms[1];
+    if (n) *n = this->timed;
+    return G1S_OK;
   }
 };
 
 struct g1s_nlf : BatchedOp {
-  RecordLane<NlfJob, g1s_nlf_record_t> frames;
+  Kind<NlfJob, g1s_nlf_record_t> frames;
   int col_strips[2] = {0, 0}, row_strips[2] = {0, 0};  // per plane class: luma, chroma
-  uint32_t wgs[3] = {0, 0, 0}, wg_base[3] = {0, 0, 0}, wgs_frame = 0;
-  // A temporal meter (rules T1 - T5) pairs every frame of a run but the first with the frame before.  Host frames then go
-  // round a ring of batch + 1 slots, so that the last frame of a batch is still there under the first of the next; of a
-  // caller's device frame that is a batch's last the flush keeps a copy (d_prev).
-  bool temporal = false;
-  RecordLane<NlfTJob, g1s_nlf_trecord_t> pairs;
-  uint64_t run_frames = 0;  // frames of the run so far
-  uint32_t next_slot = 0;   // of the input ring
-  NlfJob prev{};            // the frame before: where its planes are read
-  bool prev_is_callers = false;
-  DevBuf<uint8_t> d_prev;
+  Units wgs;                                           // the workgroups of a frame's planes
+  // A temporal meter (rules T1 - T5; pairs.on) pairs every frame of a run but the first with the frame before.  Host
+  // frames then go round the ring, which moves on with every frame that is not the caller's; of a caller's device frame that
+  // is a batch's last the flush keeps a copy.
+  Kind<NlfTJob, g1s_nlf_trecord_t> pairs;
+  NlfJob prev{};  // the frame before: where its planes are read
+  FrameBefore<1> before;
 
   int set_geometry(const g1s_frame_t &f);
   int flush();
-  int keep_prev();
-  template <class Lane>
-  int size_partials(Lane &l, size_t need);
-  template <class Lane>
-  int run(Lane &l, int set);
-  template <class Lane>
-  int collect(Lane &l);
-  template <class Lane, class Record>
-  int hand_over(Lane &l, Record *out, size_t cap, size_t *n_out);
+  int settle() { return flush(); }
+  template <class K>
+  int run(K &k, int set);
+  template <class K>
+  int collect(K &k);
   template <bool CHROMA, class Params>
   void launch(const Params &np, dim3 grid);
 };
 
-template <class Lane>
-int g1s_nlf::size_partials(Lane &l, size_t need) {
-  if (need <= l.partials_cap) return G1S_OK;
-  l.d_partials = DevBuf<unsigned long long>();
-  G1S_OP_TRY(hipMalloc((void **)&l.d_partials.p, need * sizeof(unsigned long long)));
-  l.partials_cap = need;
-  return G1S_OK;
-}
-
 int g1s_nlf::set_geometry(const g1s_frame_t &f) {
   set_frame_geometry(f);
-  wgs_frame = 0;
   for (int c = 0; c < 3; ++c) {
     const int cls = c ? 1 : 0;
     const long pw = c < geom.nplanes ? (long)geom.pw(c) : 0, ph = c < geom.nplanes ? (long)geom.ph(c) : 0;
@@ -331,15 +296,14 @@ int g1s_nlf::set_geometry(const g1s_frame_t &f) {
     const bool any = pw >= 3 && ph >= 3;
     col_strips[cls] = any ? (int)((pw - 1 + kColsPerWave - 1) / kColsPerWave) : 0;
     row_strips[cls] = any ? (int)((ph - 2 + kStripRows - 1) / kStripRows) : 0;
-    wgs[c] = (uint32_t)((col_strips[cls] * (long)row_strips[cls] + kWavesPerWg - 1) / kWavesPerWg);
-    wg_base[c] = wgs_frame;
-    wgs_frame += wgs[c];
+    wgs.n[c] = (uint32_t)((col_strips[cls] * (long)row_strips[cls] + kWavesPerWg - 1) / kWavesPerWg);
   }
-  const size_t need = (size_t)wgs_frame * kEntries * batch;
-  int rc = size_partials(frames, need);
-  if (rc) return rc;
-  run_frames = 0, d_prev = DevBuf<uint8_t>();
-  return temporal ? size_partials(pairs, need) : G1S_OK;
+  wgs.lay();
+  const size_t need = (size_t)wgs.frame * kEntries * batch;
+  G1S_OP_TRY(frames.size_partials(need));
+  G1S_OP_TRY(pairs.size_partials(need));
+  before.reset();
+  return G1S_OK;
 }
 
 template <bool CHROMA, class Params>
@@ -348,119 +312,71 @@ void g1s_nlf::launch(const Params &np, dim3 grid) {
   hipLaunchKernelGGL(kernel, grid, dim3(kStripThreads), 0, stream, np);
 }
 
-// the lane's queued jobs as one batch on the stream: the jobs up, a launch per plane class, the summing launch, the records back
-template <class Lane>
-int g1s_nlf::run(Lane &l, int set) {
-  const uint32_t B = (uint32_t)l.jobs.size();
+// the kind's queued jobs as one batch on the stream: the jobs up, a launch per plane class between the lane's three events,
+// the summing launch (which writes every word of a record: no zeros in front), the records back
+template <class K>
+int g1s_nlf::run(K &k, int set) {
+  const uint32_t B = (uint32_t)k.queue.jobs.size();
   if (!B) return G1S_OK;
-  std::memcpy(l.p_jobs.h[set], l.jobs.data(), sizeof(typename Lane::job_type) * B);
-  G1S_OP_TRY(l.p_jobs.upload(set, B, stream));
-  NlfParams<typename Lane::job_type> np{};
-  np.jobs = l.p_jobs.d[set], np.partials = l.d_partials;
-  np.W = geom.W, np.H = geom.H, np.xdec = geom.subx, np.ydec = geom.suby, np.wgs_frame = wgs_frame;
-  if (timing) G1S_OP_TRY(hipEventRecord(l.ev[0], stream));
-  if (wgs[0]) {
+  G1S_OP_TRY(k.queue.upload(set, stream));
+  NlfParams<typename decltype(k.queue.jobs)::value_type> np{};
+  np.jobs = k.queue.sets.d[set], np.partials = k.d_partials;
+  np.W = geom.W, np.H = geom.H, np.xdec = geom.subx, np.ydec = geom.suby, np.wgs_frame = wgs.frame;
+  G1S_OP_TRY(k.mark(0, timing, stream));
+  if (wgs.n[0]) {
     np.pw = geom.W, np.ph = geom.H, np.col_strips = col_strips[0], np.row_strips = row_strips[0];
-    np.wg_base = wg_base[0], np.wgs_plane = wgs[0];
-    launch<false>(np, dim3(wgs[0], 1u, B));
+    np.wg_base = wgs.base[0], np.wgs_plane = wgs.n[0];
+    launch<false>(np, dim3(wgs.n[0], 1u, B));
     G1S_OP_TRY(hipGetLastError());
   }
-  if (timing) G1S_OP_TRY(hipEventRecord(l.ev[1], stream));
-  if (wgs[1]) {
+  G1S_OP_TRY(k.mark(1, timing, stream));
+  if (wgs.n[1]) {
     np.pw = (int)geom.pw(1), np.ph = (int)geom.ph(1), np.col_strips = col_strips[1], np.row_strips = row_strips[1];
-    np.wg_base = wg_base[1], np.wgs_plane = wgs[1];
-    launch<true>(np, dim3(wgs[1], 2u, B));
+    np.wg_base = wgs.base[1], np.wgs_plane = wgs.n[1];
+    launch<true>(np, dim3(wgs.n[1], 2u, B));
     G1S_OP_TRY(hipGetLastError());
   }
-  if (timing) G1S_OP_TRY(hipEventRecord(l.ev[2], stream));
-  TailParams tp{};
-  tp.partials = l.d_partials, tp.records = reinterpret_cast<unsigned long long *>(l.d_recs.p), tp.wgs_frame = wgs_frame;
-  for (int c = 0; c < 3; ++c) tp.wgs[c] = wgs[c], tp.wg_base[c] = wg_base[c];
-  hipLaunchKernelGGL(k_nlf_tail, dim3(3u, B), dim3(128 * kTailGroups), 0, stream, tp);
-  G1S_OP_TRY(hipGetLastError());
-  G1S_OP_TRY(hipMemcpyAsync(l.h_recs, l.d_recs, sizeof(l.h_recs.p[0]) * B, hipMemcpyDeviceToHost, stream));
+  G1S_OP_TRY(k.mark(2, timing, stream));
+  G1S_OP_TRY(k.sum(k_nlf_tail, 3u, B, 128 * kTailGroups, wgs, stream));
+  G1S_OP_TRY(k.copy_back(B, stream));
   return G1S_OK;
 }
 
-// once the stream is through: the batch's times and records, the lane empty again
-template <class Lane>
-int g1s_nlf::collect(Lane &l) {
-  const size_t B = l.jobs.size();
-  if (timing && B) {
-    float ms = 0;
-    G1S_OP_TRY(hipEventElapsedTime(&ms, l.ev[0], l.ev[1]));
-    l.ms_luma += ms;
-    G1S_OP_TRY(hipEventElapsedTime(&ms, l.ev[1], l.ev[2]));
-    l.ms_chroma += ms, l.timed += B;
-  }
-  l.records.insert(l.records.end(), l.h_recs.p, l.h_recs.p + B);
-  l.jobs.clear();
+// once the stream is through: the batch's times and records, the queue empty again
+template <class K>
+int g1s_nlf::collect(K &k) {
+  const uint32_t B = (uint32_t)k.queue.jobs.size();
+  if (timing && B) G1S_OP_TRY(k.clock(B));
+  k.collect(B);
+  k.queue.jobs.clear();
   return G1S_OK;
 }
 
-// behind a temporal meter's batch: the copy of its last frame where that frame's planes are the caller's
-int g1s_nlf::keep_prev() {
-  if (!prev_is_callers) return G1S_OK;
-  if (!d_prev) G1S_OP_TRY(hipMalloc((void **)&d_prev.p, stage.frame));
-  for (int c = 0; c < geom.nplanes; ++c) {
-    G1S_OP_TRY(hipMemcpy2DAsync(d_prev + stage.off[c], stage.row[c], prev.p[c], prev.stride[c], geom.row_bytes(c), geom.ph(c), hipMemcpyDeviceToDevice, stream));
-    prev.p[c] = d_prev + stage.off[c], prev.stride[c] = (uint32_t)stage.row[c];
-  }
-  prev_is_callers = false;
-  return G1S_OK;
-}
-
-// the queued frames as one batch, behind them the queued pairs and the copy of the last frame, all waited for
+// the queued frames as one batch, behind them the queued pairs and, where the last frame's planes are the caller's, the copy
+// of it, all waited for
 int g1s_nlf::flush() {
-  if (frames.jobs.empty()) return G1S_OK;
+  if (frames.queue.jobs.empty()) return G1S_OK;
   int set, rc = next_set(&set);
   if (rc) return rc;
   if ((rc = run(frames, set)) != 0) return rc;
-  if (temporal && ((rc = run(pairs, set)) != 0 || (rc = keep_prev()) != 0)) return rc;
+  if (pairs.on) {
+    if ((rc = run(pairs, set)) != 0) return rc;
+    G1S_OP_TRY(before.room(0, stage));
+    G1S_OP_TRY(before.keep(0, geom, stage, prev.p, prev.stride, stream));
+  }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
   if ((rc = collect(frames)) != 0) return rc;
   return collect(pairs);
 }
 
-// *_finish of either kind: what is queued goes out, then the lane's records since the last hand-over
-template <class Lane, class Record>
-int g1s_nlf::hand_over(Lane &l, Record *out, size_t cap, size_t *n_out) {
-  (void)hipSetDevice(device);
-  const int rc = flush();
-  if (rc) return rc;
-  if (n_out) *n_out = l.records.size();
-  if (l.records.size() > cap || (!out && !l.records.empty())) return G1S_ERR_CAPACITY;  // (not sticky: the records stay)
-  if (!l.records.empty()) std::memcpy(out, l.records.data(), sizeof(Record) * l.records.size());
-  l.records.clear();
-  return G1S_OK;
-}
-
 namespace {
 
 g1s_nlf_t *nlf_new(uint32_t bit_depth, const g1s_nlf_opts_t *opts, bool temporal) {
-  g1s_set_global_error_("");
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) {
-    g1s_set_global_error_("noise levels are defined for bit depths 8, 10 and 12");
-    return nullptr;
-  }
-  if (opts && opts->struct_size != sizeof(g1s_nlf_opts_t)) {
-    g1s_set_global_error_("g1s_nlf_opts_t.struct_size mismatch");
-    return nullptr;
-  }
-  int device = 0;
-  const std::string no_device = pick_device(opts ? opts->device : -1, "noise levels", &device);
-  if (!no_device.empty()) {
-    g1s_set_global_error_(no_device.c_str());
-    return nullptr;
-  }
-  g1s_nlf *m = new g1s_nlf;
-  m->temporal = temporal;
-  if (!(m->open(device, bit_depth, opts ? opts->batch_frames : 0) && m->frames.alloc(m->batch) && (!temporal || m->pairs.alloc(m->batch)))) {
-    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    g1s_nlf_free(m);
-    return nullptr;
-  }
-  return m;
+  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return refuse_new("noise levels are defined for bit depths 8, 10 and 12");
+  return new_op<g1s_nlf>("noise levels", opts, "g1s_nlf_opts_t", bit_depth, [&](g1s_nlf &m, std::string &) {
+    m.frames.on = true, m.pairs.on = temporal;
+    return m.frames.alloc(m.batch) && m.pairs.alloc(m.batch);
+  });
 }
 
 }  // namespace
@@ -474,7 +390,7 @@ g1s_nlf_t *g1s_nlf_new_temporal(uint32_t bit_depth, const g1s_nlf_opts_t *opts) 
 int g1s_nlf_cut(g1s_nlf_t *m) {
   if (!m) return G1S_ERR_INVALID;
   if (m->err_code) return m->err_code;
-  m->run_frames = 0;
+  m->before.have = false;
   return G1S_OK;
 }
 
@@ -485,55 +401,39 @@ int g1s_nlf_frame(g1s_nlf_t *m, const g1s_frame_t *f) {
   const Refusal no = check_frame_pair(*f, *f, m->bps, 65536u, "g1s_nlf_new",
                                       "unsupported frame geometry (1 or 3 planes, 4:2:0 / 4:2:2 / 4:4:4, up to 65536 x 65536)");
   if (no.code) return m->fail(no.code, no.text);
-  int rc;
-  if (m->have_geom && !m->geom.same_shape(*f)) {
-    // a new geometry: what is queued goes out and finishes first, the buffers are sized again
-    if ((rc = m->flush()) != 0) return rc;
-    m->have_geom = false;
-  }
-  if (!m->have_geom && (rc = m->set_geometry(*f)) != 0) return rc;
+  int rc = take_shape(*m, *f);
+  if (rc) return rc;
   NlfJob job{};
   // (a temporal meter: the ring has a slot more than a batch, and the slots go round)
-  const uint32_t slots = m->temporal ? m->batch + 1 : m->batch, slot = m->temporal ? m->next_slot : (uint32_t)m->frames.jobs.size();
+  const bool temporal = m->pairs.on;
+  const uint32_t slots = temporal ? m->before.slots(m->batch) : m->batch, slot = temporal ? m->before.next_slot : (uint32_t)m->frames.queue.jobs.size();
   if ((rc = m->stage_in(*f, slot, slots, job.p, job.stride)) != 0) return rc;
   if ((rc = m->wait_host_input(*f)) != 0) return rc;
-  m->frames.jobs.push_back(job);
-  if (m->temporal) {
-    if (f->on_device != 1) m->next_slot = (slot + 1) % slots;
-    if (m->run_frames) m->pairs.jobs.push_back(NlfTJob{job, m->prev});
-    m->prev = job, m->prev_is_callers = f->on_device == 1;
-    ++m->run_frames;
+  m->frames.queue.jobs.push_back(job);
+  if (temporal) {
+    if (f->on_device != 1) m->before.advance(m->batch);
+    if (m->before.have) m->pairs.queue.jobs.push_back(NlfTJob{job, m->prev});
+    m->prev = job, m->before.have = true, m->before.callers[0] = f->on_device == 1;
   }
-  return m->frames.jobs.size() >= m->batch ? m->flush() : G1S_OK;
+  return m->frames.queue.jobs.size() >= m->batch ? m->flush() : G1S_OK;
 }
 
 int g1s_nlf_finish(g1s_nlf_t *m, g1s_nlf_record_t *per_frame, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  return m->hand_over(m->frames, per_frame, cap, n_out);
+  return finish_kind(m, &g1s_nlf::frames, kAlwaysMade, per_frame, cap, n_out);
 }
 
 int g1s_nlf_finish_temporal(g1s_nlf_t *m, g1s_nlf_trecord_t *per_pair, size_t cap, size_t *n_out) {
-  if (!m) return G1S_ERR_INVALID;
-  if (m->err_code) return m->err_code;
-  if (!m->temporal) {
-    m->err = "not a temporal meter: make it with g1s_nlf_new_temporal";  // (the text alone: not sticky)
-    return G1S_ERR_INVALID;
-  }
-  return m->hand_over(m->pairs, per_pair, cap, n_out);
+  return finish_kind(m, &g1s_nlf::pairs, "not a temporal meter: make it with g1s_nlf_new_temporal", per_pair, cap, n_out);
 }
 
 int g1s_nlf_temporal_times(g1s_nlf_t *m, double *ms_luma, double *ms_chroma, uint64_t *pairs) {
-  if (!m) return G1S_ERR_INVALID;
-  m->pairs.times(ms_luma, ms_chroma, pairs);
-  return G1S_OK;
+  return m ? m->pairs.times(ms_luma, ms_chroma, pairs) : G1S_ERR_INVALID;
 }
 
 int g1s_nlf_set_timing(g1s_nlf_t *m, int enable, double *ms_luma, double *ms_chroma, uint64_t *frames) {
   if (!m) return G1S_ERR_INVALID;
   m->timing = enable != 0;
-  m->frames.times(ms_luma, ms_chroma, frames);
-  return G1S_OK;
+  return m->frames.times(ms_luma, ms_chroma, frames);
 }
 
 const char *g1s_nlf_last_error(const g1s_nlf_t *m) { return m ? m->err.c_str() : ""; }

@@ -324,31 +324,12 @@ int g1s_surface_conv::convert(const g1s_surface_t &s, const g1s_frame_t &f, bool
 extern "C" {
 
 g1s_surface_conv_t *g1s_surface_new(uint32_t bit_depth, const g1s_surface_opts_t *opts) {
-  g1s_set_global_error_("");
-  if (bit_depth < 8 || bit_depth > 16) {
-    g1s_set_global_error_("a surface converter takes bit depths 8 to 16");
-    return nullptr;
-  }
-  if (opts && opts->struct_size != sizeof(g1s_surface_opts_t)) {
-    g1s_set_global_error_("g1s_surface_opts_t.struct_size mismatch");
-    return nullptr;
-  }
-  int device = 0;
-  const std::string no_device = pick_device(opts ? opts->device : -1, "the surface converter", &device);
-  if (!no_device.empty()) {
-    g1s_set_global_error_(no_device.c_str());
-    return nullptr;
-  }
-  g1s_surface_conv *g = new g1s_surface_conv;
-  bool ok = g->open(device, bit_depth, opts ? opts->batch_frames : 0);
-  for (Event &e : g->ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
-  ok = ok && g->p_jobs.alloc(g->batch);
-  if (!ok) {
-    g1s_set_global_error_((std::string("HIP initialisation failed: ") + hipGetErrorString(hipGetLastError())).c_str());
-    g1s_surface_free(g);
-    return nullptr;
-  }
-  return g;
+  if (bit_depth < 8 || bit_depth > 16) return refuse_new("a surface converter takes bit depths 8 to 16");
+  return new_op<g1s_surface_conv>("the surface converter", opts, "g1s_surface_opts_t", bit_depth, [](g1s_surface_conv &g, std::string &) {
+    bool ok = true;
+    for (Event &e : g.ev) ok = ok && hipEventCreate(&e.p) == hipSuccess;
+    return ok && g.p_jobs.alloc(g.batch);
+  });
 }
 
 int g1s_surface_unpack(g1s_surface_conv_t *g, const g1s_surface_t *in, g1s_frame_t *out) {
