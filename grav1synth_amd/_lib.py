@@ -234,6 +234,19 @@ class G1SNlfTRecord(C.Structure):
     ]
 
 
+class G1SNlfLRecord(C.Structure):
+    _fields_ = [
+        ("n", (C.c_uint64 * 46) * 3),
+        ("r", (C.c_int64 * 46) * 3),
+        ("s", C.c_int64 * 3),
+        ("xn", (C.c_uint64 * 25) * 2),
+        ("xr", (C.c_int64 * 25) * 2),
+        ("ln", C.c_uint64),
+        ("ls", C.c_int64),
+        ("l2", C.c_uint64),
+    ]
+
+
 class G1SSurface(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -351,6 +364,15 @@ SYMBOLS = [
     ("g1s_nlf_finish_temporal", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("g1s_nlf_temporal_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("g1s_nlf_sum_temporal", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_nlf_new_lags", C.c_void_p, [C.c_uint32, C.POINTER(G1SNlfOpts)]),
+    ("g1s_nlf_finish_lags", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("g1s_nlf_lag_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("g1s_nlf_sum_lags", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("g1s_nlf_table", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    ("g1s_format_noise_lags", C.c_long, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_y4m_file_table", C.c_int64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(G1SNlfOpts), C.c_uint64, C.c_uint32, C.c_uint64,
+                                           C.c_void_p, C.c_char_p, C.c_size_t]),
+    ("g1s_nlf_ar", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("g1s_nlf_sigma_temporal", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),
     ("g1s_nlf_chroma_sigma_temporal", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     ("g1s_nlf_strength_temporal", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]),

@@ -33,6 +33,10 @@ SAME_SCALES_OUTPUT = "--scales and -o name the same file: the two reports would 
 SAME_SCALES_TEMPORAL = "--scales and --temporal name the same file: the two reports would overwrite each other. Exiting."
 SAME_SCALES_CROSS = "--scales and --cross name the same file: the two reports would overwrite each other. Exiting."
 CROSS_NEEDS_CHROMA = "--cross compares chroma with luma: the clip has no chroma planes"
+SAME_TABLE = "--table and --lags cannot be the same file as the source, the output, a report or each other. Exiting."
+TABLE_BAD_LAG = "--table-lag must be 1, 2 or 3. Exiting."
+TABLE_NEEDS_FLAG = "--table-lag, --lags, --profile-frames and --levels-min-count say how --table is made: they need it. Exiting."
+TABLE_NEEDS_TWO = "a table needs two frames. Exiting."
 SAME_LEVELS = "--levels and -o name the same file: the two outputs would overwrite each other. Exiting."
 NO_DENOISED = "Neither a DENOISED file nor --denoise was given: there is nothing to compare the source with. Exiting."
 BOTH_DENOISED = "--denoise makes the denoised clip on the device: it does not combine with a DENOISED file. Exiting."
@@ -311,6 +315,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also write the clip's temporal noise levels: sigma from the difference of consecutive frames where the "
                         "picture stands still, its ratio to the single-frame sigma (above 1: correlated grain, or motion) and "
                         "the strength it implies, from the same read of the clip")
+    e.add_argument("--table", metavar="PATH", default=None,
+                   help="also write the clip's own grain table (.tbl): scaling functions from the temporal noise levels, AR "
+                        "coefficients from the lagged products of the frame differences where the picture stands still; no "
+                        "denoiser is involved")
+    e.add_argument("--lags", metavar="PATH", default=None,
+                   help="with --table: also write the lag report: per plane the correlation of the frame difference at the "
+                        "table's offsets, the coefficients before quantisation and the gain")
+    e.add_argument("--table-lag", type=int, default=None, metavar="L", help="with --table: the table's ar_coeff_lag, 1 .. 3 (default 3)")
+    e.add_argument("--profile-frames", type=int, default=None, metavar="N", help="with --table: measure the first N frames only (default: all)")
+    e.add_argument("--levels-min-count", type=int, default=None, metavar="N",
+                   help="with --table: the fewest samples a bin, and pairs a lag, must have (default 4096)")
     r = sub.add_parser("render", help="Synthesizes the film grain of a table onto a video (y4m input and output): what a decoder "
                                       "shows for the clip encoded with the table (AV1 specification, film grain synthesis process).")
     r.add_argument("input", help="The (denoised) file to put grain on.")
@@ -432,10 +447,14 @@ def diff_command(source: str, denoised: Optional[str], output: str, overwrite: b
 
 
 def estimate_command(source: str, output: str, overwrite: bool = False, device: int = -1, confirm=_confirm,
-                     levels: Optional[str] = None, levels_temporal: Optional[str] = None) -> int:
+                     levels: Optional[str] = None, levels_temporal: Optional[str] = None, table: Optional[str] = None,
+                     table_lag: Optional[int] = None, profile_frames: Optional[int] = None, levels_min_count: Optional[int] = None,
+                     lags: Optional[str] = None) -> int:
     """Commands::Estimate (src/main.rs:534-608): the refusals of :541-560, one estimate_plane_noise per frame, "filmgrn1" and a
     "{:.3}" line per frame (-1 for None), "Done, wrote output file to ...".  --levels PATH is a second output, the clip's
-    noise levels; --levels-temporal PATH a third, its temporal noise levels.  Returns the frame count, -1 after a refusal."""
+    noise levels; --levels-temporal PATH a third, its temporal noise levels; --table PATH the clip's own grain table (with
+    --table-lag, --profile-frames, --levels-min-count).  Returns the frame count, -1 after a refusal: a refusal logs its line
+    and writes nothing."""
     from .estimate import estimate_y4m_file
 
     if _same_path(source, output) or any(p is not None and _same_path(source, p) for p in (levels, levels_temporal)):
@@ -447,18 +466,50 @@ def estimate_command(source: str, output: str, overwrite: bool = False, device: 
     if levels_temporal is not None and (_same_path(output, levels_temporal) or (levels is not None and _same_path(levels, levels_temporal))):
         log.error(SAME_LEVELS_TEMPORAL)
         return -1
-    for path in (output, levels, levels_temporal):
+    if table is None and any(v is not None for v in (table_lag, profile_frames, levels_min_count, lags)):
+        log.error(TABLE_NEEDS_FLAG)
+        return -1
+    if table is not None:
+        if any(p is not None and _same_path(table, p) for p in (source, output, levels, levels_temporal, lags)) or \
+                (lags is not None and any(p is not None and _same_path(lags, p) for p in (source, output, levels, levels_temporal))):
+            log.error(SAME_TABLE)
+            return -1
+        if table_lag is not None and table_lag not in (1, 2, 3):
+            log.error(TABLE_BAD_LAG)
+            return -1
+        if (profile_frames or 0) < 0 or (levels_min_count or 0) < 0:
+            log.error(AUTO_BAD_NUMBER)
+            return -1
+    for path in (output, levels, levels_temporal, table, lags):
         if path is not None and os.path.exists(path) and not overwrite and not confirm(f"File {path} exists. Overwrite?"):
             log.warning(NOT_OVERWRITING)
             return -1
     # (levels_temporal only where it is given: a job without the flag makes the call it made)
     more = {} if levels_temporal is None else dict(levels_temporal=levels_temporal)
-    frames = estimate_y4m_file(source, output, device=device, levels=levels, **more)
+    if table is not None:
+        from ._lib import G1SError
+        from .estimate import TABLE_NEEDS_TWO_FRAMES
+
+        more.update(table=table, table_lag=table_lag or 3, max_frames=profile_frames or 0, min_count=levels_min_count or 0, lags=lags)
+        try:
+            frames = estimate_y4m_file(source, output, device=device, levels=levels, **more)
+        except G1SError as err:
+            if TABLE_NEEDS_TWO_FRAMES in str(err):
+                log.error(TABLE_NEEDS_TWO)
+            else:
+                log.error("%s. Exiting.", str(err).split(": ", 1)[-1])
+            return -1
+    else:
+        frames = estimate_y4m_file(source, output, device=device, levels=levels, **more)
     log.info("Done, wrote output file to %s", output)
     if levels is not None:
         log.info("Done, wrote noise levels to %s", levels)
     if levels_temporal is not None:
         log.info("Done, wrote temporal noise levels to %s", levels_temporal)
+    if table is not None:
+        log.info("Done, wrote the clip's grain table to %s", table)
+    if lags is not None:
+        log.info("Done, wrote the lag report to %s", lags)
     return frames
 
 
@@ -653,7 +704,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     elif args.command == "estimate":
         try:
             estimate_command(args.source, args.output, args.overwrite, args.device, levels=args.levels,
-                             **({} if args.levels_temporal is None else dict(levels_temporal=args.levels_temporal)))
+                             **({} if args.levels_temporal is None else dict(levels_temporal=args.levels_temporal)),
+                             **({} if all(v is None for v in (args.table, args.table_lag, args.profile_frames, args.levels_min_count, args.lags)) else
+                                dict(table=args.table, table_lag=args.table_lag, profile_frames=args.profile_frames, levels_min_count=args.levels_min_count,
+                                     lags=args.lags)))
         except Exception as e:
             log.error("%s", e)
             return 1

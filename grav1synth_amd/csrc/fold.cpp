@@ -1081,17 +1081,24 @@ void NoiseFold::finish(std::vector<g1s_segment_t> &out) {
 
 g1s_segment_t NoiseFold::grain_parameters(uint64_t start_ts, uint64_t end_ts) const {
   finalize_chroma();
+  const PlaneState *st[3] = {&combined_[0], &combined_[1], &combined_[2]};
+  return grain_parameters_of(st, lag_, start_ts, end_ts);
+}
+
+// The quantisation of three planes' states into a table's segment: what the fold ends a segment with, and what a table made
+// from a clip's lag and temporal records (nlf_table.cpp) goes through too.  A chroma plane's ar has lag's coefficients + 1.
+g1s_segment_t grain_parameters_of(const PlaneState *const st[3], uint32_t lag, uint64_t start_ts, uint64_t end_ts) {
   g1s_segment_t g;
   std::memset(&g, 0, sizeof(g));
   g.random_seed = start_ts == 0 ? kDefaultGrainSeed : 0;
   g.start_time = start_ts;
   g.end_time = end_ts;
-  g.ar_coeff_lag = (uint8_t)lag_;
+  g.ar_coeff_lag = (uint8_t)lag;
 
   std::vector<double> px[3], py[3];
-  combined_[0].strength.fit_piecewise(G1S_NUM_Y_POINTS, px[0], py[0]);
-  combined_[1].strength.fit_piecewise(G1S_NUM_UV_POINTS, px[1], py[1]);
-  combined_[2].strength.fit_piecewise(G1S_NUM_UV_POINTS, px[2], py[2]);
+  st[0]->strength.fit_piecewise(G1S_NUM_Y_POINTS, px[0], py[0]);
+  st[1]->strength.fit_piecewise(G1S_NUM_UV_POINTS, px[1], py[1]);
+  st[2]->strength.fit_piecewise(G1S_NUM_UV_POINTS, px[2], py[2]);
   double max_scaling_value = 1e-4;
   for (int c = 0; c < 3; ++c) {
     for (size_t i = 0; i < px[c].size(); ++i) {
@@ -1114,17 +1121,17 @@ g1s_segment_t NoiseFold::grain_parameters(uint64_t start_ts, uint64_t end_ts) co
     }
   }
 
-  const int n_coeff = n_;
+  const int n_coeff = (int)num_coeffs(lag);
   double max_coeff = 1e-4, min_coeff = -1e-4;
   double y_corr[2] = {0, 0};
   double avg_luma_strength = 0;
   for (int c = 0; c < 3; ++c) {
-    const LinearSystem &eq = combined_[c].ar;
+    const LinearSystem &eq = st[c]->ar;
     for (int i = 0; i < n_coeff; ++i) {
       if (eq.x[i] > max_coeff) max_coeff = eq.x[i];
       if (eq.x[i] < min_coeff) min_coeff = eq.x[i];
     }
-    const LinearSystem &se = combined_[c].strength.eq;
+    const LinearSystem &se = st[c]->strength.eq;
     double average_strength = 0, total_weight = 0;
     for (int i = 0; i < se.n; ++i) {
       double wgt = 0;
@@ -1153,7 +1160,7 @@ g1s_segment_t NoiseFold::grain_parameters(uint64_t start_ts, uint64_t end_ts) co
   const double scale_ar = 1 << g.ar_coeff_shift;
   int8_t *ar[3] = {g.ar_coeffs_y, g.ar_coeffs_cb, g.ar_coeffs_cr};
   for (int c = 0; c < 3; ++c) {
-    const LinearSystem &eq = combined_[c].ar;
+    const LinearSystem &eq = st[c]->ar;
     for (int i = 0; i < n_coeff; ++i)
       ar[c][i] = (int8_t)clampi((int)std::round(scale_ar * eq.x[i]), -128, 127);
     if (c > 0) ar[c][n_coeff] = (int8_t)clampi((int)std::round(scale_ar * y_corr[c - 1]), -128, 127);

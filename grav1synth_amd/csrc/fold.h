@@ -78,6 +78,9 @@ struct PlaneState {
   double ar_gain = 1.0;
 };
 
+// three planes' states as a table's segment [start_ts, end_ts) (fold.cpp; NoiseFold::grain_parameters is this on its combined states)
+g1s_segment_t grain_parameters_of(const PlaneState *const st[3], uint32_t lag, uint64_t start_ts, uint64_t end_ts);
+
 // Per-frame ("latest") noise state: depends on that frame's record only, so it
 // can be computed for many frames concurrently.
 struct FrameLatest {

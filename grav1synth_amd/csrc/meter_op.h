@@ -37,9 +37,12 @@ struct Units {
     frame = 0;
     for (int c = 0; c < 3; ++c) base[c] = frame, frame += n[c];
   }
-  // units of unit_w x unit_h samples over the planes of g
-  void cut(const PlaneGeom &g, int unit_w, int unit_h) {
-    for (int c = 0; c < 3; ++c) n[c] = c < g.nplanes ? (uint32_t)(((g.pw(c) + unit_w - 1) / unit_w) * ((g.ph(c) + unit_h - 1) / unit_h)) : 0u;
+  // units of unit_w x unit_h samples over the planes of g (unit_h_chroma: another height for planes 1 and 2; 0 = unit_h)
+  void cut(const PlaneGeom &g, int unit_w, int unit_h, int unit_h_chroma = 0) {
+    for (int c = 0; c < 3; ++c) {
+      const int uh = c && unit_h_chroma ? unit_h_chroma : unit_h;
+      n[c] = c < g.nplanes ? (uint32_t)(((g.pw(c) + unit_w - 1) / unit_w) * ((g.ph(c) + uh - 1) / uh)) : 0u;
+    }
     lay();
   }
 };
@@ -135,6 +138,13 @@ struct RecordLane : Records<Rec> {
     return hipSuccess;
   }
   void collect(uint32_t n) { Records<Rec>::collect(h_recs.p, n); }
+  // the first two intervals' times so far and the records they covered (the noise levels' luma and chroma)
+  int times(double *first, double *second, uint64_t *n) const {
+    if (first) *first = ms[0];
+    if (second) *second = ms[INTERVALS - 1 < 1 ? INTERVALS - 1 : 1];  // (a lane of one interval has no second: its only one)
+    if (n) *n = timed;
+    return G1S_OK;
+  }
 };
 
 // The frame before, of a temporal meter's run: SIDES frames a job (measure's noisy and clean, the noise levels' one).  Host

@@ -39,6 +39,7 @@
 #include "../../include/g1s_diff.h"
 #include "meter_op.h"
 #include "nlf.h"
+#include "nlf_lags.h"
 #include "strip_walk.hip.h"
 #include "wave_sum.hip.h"
 
@@ -53,15 +54,6 @@ static_assert(sizeof(g1s_nlf_trecord_t) == sizeof(g1s_nlf_record_t), "k_nlf_tail
 constexpr int kBoxGate = 144;  // T2: |S9_t - S9_(t-1)| < 144 2^sh
 static_assert((long long)kStripRows * 8 * 4095 * 64 < (1ll << 31), "a wave's sum of e over a strip fits int");
 static_assert((long long)kStripRows * 8 * 8 * 255 * 64 < (1ll << 31), "a wave's sum of a over a strip fits int");
-
-struct NlfJob {
-  const uint8_t *p[3];
-  uint32_t stride[3];  // bytes
-};
-// frame t and frame t - 1 of a pair
-struct NlfTJob {
-  NlfJob now, before;
-};
 
 // what a strip kernel is launched with; Job: NlfJob (k_nlf) or NlfTJob (k_nlf_t)
 template <class Job>
@@ -257,12 +249,6 @@ template <class Job, class Record>
 struct Kind : RecordLane<Record, 2> {
   JobQueue<Job> queue;
   bool alloc(uint32_t B) { return !this->on || (queue.alloc(B) && RecordLane<Record, 2>::alloc(B)); }
-  int times(double *luma, double *chroma, uint64_t *n) const {
-    if (luma) *luma = this->ms[0];
-    if (chroma) *chroma = this->ms[1];
-    if (n) *n = this->timed;
-    return G1S_OK;
-  }
 };
 
 struct g1s_nlf : BatchedOp {
@@ -275,12 +261,17 @@ struct g1s_nlf : BatchedOp {
   Kind<NlfTJob, g1s_nlf_trecord_t> pairs;
   NlfJob prev{};  // the frame before: where its planes are read
   FrameBefore<1> before;
+  // A lag meter (rules L1 - L5; lags.on) is a temporal meter that also keeps a lag record a pair: the pairs' queued jobs go
+  // through the two lag launches (nlf_lags.hip) behind k_nlf_t's, into a lane of their own.
+  RecordLane<g1s_nlf_lrecord_t, 2> lags;
+  Units lag_tiles;
 
   int set_geometry(const g1s_frame_t &f);
   int flush();
   int settle() { return flush(); }
   template <class K>
   int run(K &k, int set);
+  int run_lags(int set);
   template <class K>
   int collect(K &k);
   template <bool CHROMA, class Params>
@@ -302,6 +293,8 @@ int g1s_nlf::set_geometry(const g1s_frame_t &f) {
   const size_t need = (size_t)wgs.frame * kEntries * batch;
   G1S_OP_TRY(frames.size_partials(need));
   G1S_OP_TRY(pairs.size_partials(need));
+  g1s_nlf_lags::cut(geom, lag_tiles);
+  G1S_OP_TRY(lags.size_partials((size_t)lag_tiles.frame * g1s_nlf_lags::kEntries * batch));
   before.reset();
   return G1S_OK;
 }
@@ -342,6 +335,22 @@ int g1s_nlf::run(K &k, int set) {
   return G1S_OK;
 }
 
+// the pairs that run(pairs, set) sent up, through the lag launches: luma and chroma between the lane's three events, the
+// summing launch (which writes every word of a record), the records back
+int g1s_nlf::run_lags(int set) {
+  const uint32_t B = (uint32_t)pairs.queue.jobs.size();
+  if (!B) return G1S_OK;
+  const NlfTJob *jobs = pairs.queue.sets.d[set];
+  G1S_OP_TRY(lags.mark(0, timing, stream));
+  G1S_OP_TRY(g1s_nlf_lags::launch(false, jobs, B, lags.d_partials, geom, lag_tiles, bit_depth, stream));
+  G1S_OP_TRY(lags.mark(1, timing, stream));
+  G1S_OP_TRY(g1s_nlf_lags::launch(true, jobs, B, lags.d_partials, geom, lag_tiles, bit_depth, stream));
+  G1S_OP_TRY(lags.mark(2, timing, stream));
+  G1S_OP_TRY(lags.sum(g1s_nlf_lags::tail(), 3u, B, g1s_nlf_lags::kTailThreads, lag_tiles, stream));
+  G1S_OP_TRY(lags.copy_back(B, stream));
+  return G1S_OK;
+}
+
 // once the stream is through: the batch's times and records, the queue empty again
 template <class K>
 int g1s_nlf::collect(K &k) {
@@ -361,21 +370,27 @@ int g1s_nlf::flush() {
   if ((rc = run(frames, set)) != 0) return rc;
   if (pairs.on) {
     if ((rc = run(pairs, set)) != 0) return rc;
+    if (lags.on && (rc = run_lags(set)) != 0) return rc;
     G1S_OP_TRY(before.room(0, stage));
     G1S_OP_TRY(before.keep(0, geom, stage, prev.p, prev.stride, stream));
   }
   if ((rc = set_done(set)) != 0 || (rc = wait()) != 0) return rc;
   if ((rc = collect(frames)) != 0) return rc;
+  if (lags.on) {
+    const uint32_t B = (uint32_t)pairs.queue.jobs.size();
+    if (timing && B) G1S_OP_TRY(lags.clock(B));
+    lags.collect(B);
+  }
   return collect(pairs);
 }
 
 namespace {
 
-g1s_nlf_t *nlf_new(uint32_t bit_depth, const g1s_nlf_opts_t *opts, bool temporal) {
+g1s_nlf_t *nlf_new(uint32_t bit_depth, const g1s_nlf_opts_t *opts, bool temporal, bool lags = false) {
   if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return refuse_new("noise levels are defined for bit depths 8, 10 and 12");
   return new_op<g1s_nlf>("noise levels", opts, "g1s_nlf_opts_t", bit_depth, [&](g1s_nlf &m, std::string &) {
-    m.frames.on = true, m.pairs.on = temporal;
-    return m.frames.alloc(m.batch) && m.pairs.alloc(m.batch);
+    m.frames.on = true, m.pairs.on = temporal, m.lags.on = lags;
+    return m.frames.alloc(m.batch) && m.pairs.alloc(m.batch) && m.lags.alloc(m.batch);
   });
 }
 
@@ -386,6 +401,8 @@ extern "C" {
 g1s_nlf_t *g1s_nlf_new(uint32_t bit_depth, const g1s_nlf_opts_t *opts) { return nlf_new(bit_depth, opts, false); }
 
 g1s_nlf_t *g1s_nlf_new_temporal(uint32_t bit_depth, const g1s_nlf_opts_t *opts) { return nlf_new(bit_depth, opts, true); }
+
+g1s_nlf_t *g1s_nlf_new_lags(uint32_t bit_depth, const g1s_nlf_opts_t *opts) { return nlf_new(bit_depth, opts, true, true); }
 
 int g1s_nlf_cut(g1s_nlf_t *m) {
   if (!m) return G1S_ERR_INVALID;
@@ -428,6 +445,14 @@ int g1s_nlf_finish_temporal(g1s_nlf_t *m, g1s_nlf_trecord_t *per_pair, size_t ca
 
 int g1s_nlf_temporal_times(g1s_nlf_t *m, double *ms_luma, double *ms_chroma, uint64_t *pairs) {
   return m ? m->pairs.times(ms_luma, ms_chroma, pairs) : G1S_ERR_INVALID;
+}
+
+int g1s_nlf_finish_lags(g1s_nlf_t *m, g1s_nlf_lrecord_t *per_pair, size_t cap, size_t *n_out) {
+  return finish_kind(m, &g1s_nlf::lags, "not a lag meter: make it with g1s_nlf_new_lags", per_pair, cap, n_out);
+}
+
+int g1s_nlf_lag_times(g1s_nlf_t *m, double *ms_luma, double *ms_chroma, uint64_t *pairs) {
+  return m ? m->lags.times(ms_luma, ms_chroma, pairs) : G1S_ERR_INVALID;
 }
 
 int g1s_nlf_set_timing(g1s_nlf_t *m, int enable, double *ms_luma, double *ms_chroma, uint64_t *frames) {

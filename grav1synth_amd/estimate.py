@@ -34,7 +34,7 @@ import numpy as np
 
 from . import _lib
 from ._frame_op import FrameOp
-from ._lib import G1SError, G1SNlfOpts, G1SNlfRecord, G1SNlfTRecord
+from ._lib import G1SError, G1SNlfLRecord, G1SNlfOpts, G1SNlfRecord, G1SNlfTRecord
 from .diff import Frame
 
 # g1s_nlf_record_t
@@ -43,6 +43,10 @@ assert NLF_RECORD.itemsize == C.sizeof(G1SNlfRecord)
 # g1s_nlf_trecord_t
 NLF_TRECORD = np.dtype([("n", "<u8", (3, 32)), ("s", "<i8", (3, 32)), ("q", "<u8", (3, 32))])
 assert NLF_TRECORD.itemsize == C.sizeof(G1SNlfTRecord)
+# g1s_nlf_lrecord_t
+NLF_LRECORD = np.dtype([("n", "<u8", (3, 46)), ("r", "<i8", (3, 46)), ("s", "<i8", (3,)), ("xn", "<u8", (2, 25)), ("xr", "<i8", (2, 25)), ("ln", "<u8"),
+                        ("ls", "<i8"), ("l2", "<u8")])
+assert NLF_LRECORD.itemsize == C.sizeof(G1SNlfLRecord)
 
 log = logging.getLogger("grav1synth")
 
@@ -125,23 +129,33 @@ def format_estimates(estimates) -> bytes:
     return buf.raw[:w]
 
 
-def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Optional[str] = None, levels_temporal: Optional[str] = None) -> int:
+TABLE_NEEDS_TWO_FRAMES = "a table needs two frames"
+
+
+def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Optional[str] = None, levels_temporal: Optional[str] = None,
+                      table: Optional[str] = None, table_lag: int = 3, max_frames: int = 0, min_count: int = 0, lags: Optional[str] = None) -> int:
     """`grav1synth estimate SOURCE -o OUTPUT [--levels PATH] [--levels-temporal PATH]` for a .y4m input: with `levels` the
     noise-level report of the clip is written there, with `levels_temporal` its temporal report (the file one run), from the
-    same read of the clip.  Returns the number of frames."""
+    same read of the clip.  With `table` the clip's own grain table (rules L1 - L10: the file one run, made from its first
+    max_frames frames, 0 = all) is written there as a .tbl and with `lags` the lag report of those frames; the two level
+    reports stay those of the whole clip.  A refusal of the table (G1SError; fewer than two frames: TABLE_NEEDS_TWO_FRAMES) is
+    raised before anything is written.  Returns the number of frames."""
     from .ingest import Y4MReader
 
     rd = Y4MReader(source)
     d = rd.details
     est = NoiseEstimator(d.bit_depth, device=device)
-    temporal = levels_temporal is not None
-    meter = NoiseLevelMeter(d.bit_depth, device=device, temporal=temporal) if levels is not None or temporal else None
-    total, ttotal = np.zeros((), NLF_RECORD), np.zeros((), NLF_TRECORD)
+    temporal = levels_temporal is not None or table is not None
+    lag_kw = dict(lags=True) if table is not None else {}  # (a job without --table makes the calls it made)
+    meter = NoiseLevelMeter(d.bit_depth, device=device, temporal=temporal, **lag_kw) if levels is not None or temporal else None
+    total, ttotal, ltotal = np.zeros((), NLF_RECORD), np.zeros((), NLF_TRECORD), np.zeros((), NLF_LRECORD)
     first = None  # the first frame's record: the one frame without a predecessor
     pairs = 0
+    reports = levels is not None or levels_temporal is not None  # (they are of the whole clip, whatever the table is made from)
+    table_sums = None  # (ttotal, ltotal, pairs) of the table's frames: the first max_frames, or all
 
     def take():
-        nonlocal total, ttotal, first, pairs
+        nonlocal total, ttotal, ltotal, first, pairs
         recs = meter.finish()
         if first is None and len(recs):
             first = recs[0].copy()
@@ -150,50 +164,110 @@ def estimate_y4m_file(source: str, output: str, *, device: int = -1, levels: Opt
             trecs = meter.finish_temporal()
             pairs += len(trecs)
             ttotal = noise_levels_sum_temporal(np.concatenate([ttotal.reshape(1), trecs]))
+        if table is not None:
+            lrecs = meter.finish_lags()
+            if table_sums is None:  # (behind the table's frames the lag records are not wanted)
+                ltotal = noise_lags_sum(np.concatenate([ltotal.reshape(1), lrecs]))
 
-    n = 0
-    while True:
-        planes = rd.get_frame()
-        if planes is None:
-            break
-        est.estimate_frame(planes[0])
-        if meter is not None:
-            meter.frame(planes, d.xdec, d.ydec)
-            if (n + 1) % 32 == 0:
+    n = metered = 0
+    try:
+        while True:
+            planes = rd.get_frame()
+            if planes is None:
+                break
+            est.estimate_frame(planes[0])
+            if meter is not None and (table_sums is None or reports):
+                meter.frame(planes, d.xdec, d.ydec)
+                metered += 1
+                if table is not None and max_frames and metered == max_frames:  # the table's frames are in: its sums as they stand
+                    take()
+                    table_sums = (ttotal.copy(), ltotal.copy(), pairs)
+                elif (n + 1) % 32 == 0:
+                    take()
+            n += 1
+        segment = None
+        if table is not None:  # (before anything is written: a refusal writes nothing)
+            if table_sums is None:
                 take()
-        n += 1
-    with open(output, "wb") as f:
-        f.write(format_estimates(est.finish()))
-    if meter is not None:
-        take()
-        if levels is not None:
-            with open(levels, "wb") as f:
-                f.write(format_noise_levels(total, n, d.bit_depth, d.nplanes))
-        if temporal:
-            later = total.copy()
-            if first is not None:
-                for name in ("n", "a", "q"):
-                    later[name] -= first[name]
-            with open(levels_temporal, "wb") as f:
-                f.write(format_noise_levels_temporal(ttotal, pairs, d.bit_depth, d.nplanes, ordinary=later))
-        meter.close()
-    est.close()
-    rd.close()
+                table_sums = (ttotal.copy(), ltotal.copy(), pairs)
+            if min(metered, max_frames or metered) < 2:
+                raise G1SError(-1, TABLE_NEEDS_TWO_FRAMES)  # G1S_ERR_INVALID
+            segment = noise_table(table_sums[0], table_sums[1], d.bit_depth, d.xdec, d.ydec, d.nplanes, table_lag, min_count)
+            lag_report = None if lags is None else format_noise_lags(table_sums[1], table_sums[2], d.bit_depth, d.nplanes, table_lag, min_count)
+        with open(output, "wb") as f:
+            f.write(format_estimates(est.finish()))
+        if meter is not None:
+            take()
+            if levels is not None:
+                with open(levels, "wb") as f:
+                    f.write(format_noise_levels(total, n, d.bit_depth, d.nplanes))
+            if segment is not None:
+                from .diff import write_tbl
+
+                write_tbl(table, [segment])
+                if lags is not None:
+                    with open(lags, "wb") as f:
+                        f.write(lag_report)
+            if levels_temporal is not None:
+                later = total.copy()
+                if first is not None:
+                    for name in ("n", "a", "q"):
+                        later[name] -= first[name]
+                with open(levels_temporal, "wb") as f:
+                    f.write(format_noise_levels_temporal(ttotal, pairs, d.bit_depth, d.nplanes, ordinary=later))
+    finally:
+        if meter is not None:
+            meter.close()
+        est.close()
+        rd.close()
     return n
+
+
+def format_noise_lags(lags_total: np.ndarray, pairs: int, bit_depth: int, nplanes: int = 3, lag: int = 3, min_count: int = 0) -> bytes:
+    """Rule L10: the report of a clip's lag record (g1s_format_noise_lags; host only; the grammar is in include/g1s_diff.h)."""
+    L = _lib.lib()
+    record = np.ascontiguousarray(lags_total, NLF_LRECORD)
+    buf = C.create_string_buffer(1 << 14)
+    w = L.g1s_format_noise_lags(record.ctypes.data, pairs, bit_depth, nplanes, lag, min_count, buf, len(buf))
+    if w < 0:
+        raise G1SError(int(w), "g1s_format_noise_lags failed")
+    return buf.raw[:w]
+
+
+def noise_table_y4m_file(source: str, table: Optional[str] = None, *, levels: Optional[str] = None, levels_temporal: Optional[str] = None,
+                         lags: Optional[str] = None, device: int = -1, batch_frames: int = 0, max_frames: int = 0, lag: int = 3, min_count: int = 0):
+    """The clip's own grain table from the first max_frames frames (0 = all) of a .y4m file, the file one run
+    (g1s_nlf_y4m_file_table): the .tbl into `table`, and where they are given the noise levels, the temporal noise levels and
+    the lag report of those frames.  A refusal raises and writes nothing.  Returns (frames, the GrainTableSegment)."""
+    from ._lib import G1SSegment
+    from .diff import GrainTableSegment
+
+    enc = lambda p: None if p is None else str(p).encode()  # noqa: E731
+    opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
+    err = C.create_string_buffer(512)
+    seg = G1SSegment()
+    n = _lib.lib().g1s_nlf_y4m_file_table(enc(source), enc(table), enc(levels), enc(levels_temporal), enc(lags), C.byref(opts), max_frames, lag, min_count,
+                                          C.byref(seg), err, len(err))
+    if n < 0:
+        raise G1SError(int(n), err.value.decode())
+    return int(n), GrainTableSegment.from_c(seg)
 
 
 class NoiseLevelMeter(FrameOp):
     """g1s_nlf_*: the noise level function of frames on the device (rules N1 - N4); no CPU fallback.  temporal = True: a
     temporal meter (rules T1 - T5): the same records from finish(), and from finish_temporal() one record per frame with a
-    predecessor in its run; cut() ends a run."""
+    predecessor in its run; cut() ends a run.  lags = True: a lag meter (rules L1 - L5): a temporal meter that also keeps a
+    lag record a pair, from finish_lags()."""
     _name = "nlf"
 
-    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False):
+    def __init__(self, bit_depth: int, *, device: int = -1, batch_frames: int = 0, temporal: bool = False, lags: bool = False):
         self._L = _lib.lib()
         self.bit_depth = bit_depth
-        self.temporal = temporal
+        self.temporal = temporal or lags
+        self.lags = lags
         opts = G1SNlfOpts(C.sizeof(G1SNlfOpts), device, batch_frames)
-        self._h = (self._L.g1s_nlf_new_temporal if temporal else self._L.g1s_nlf_new)(bit_depth, C.byref(opts))
+        new = self._L.g1s_nlf_new_lags if lags else self._L.g1s_nlf_new_temporal if temporal else self._L.g1s_nlf_new
+        self._h = new(bit_depth, C.byref(opts))
         if not self._h:
             raise G1SError(-5, self._L.g1s_last_global_error().decode())
         self._keep: list = []  # planes the queued kernels still read
@@ -244,6 +318,17 @@ class NoiseLevelMeter(FrameOp):
         meter made without temporal = True refuses."""
         return self._finish(self._L.g1s_nlf_finish_temporal, NLF_TRECORD, cap)
 
+    def finish_lags(self, cap: Optional[int] = None) -> np.ndarray:
+        """finish() for the lag records (NLF_LRECORD): one per frame with a predecessor since the last finish_lags(), in
+        order.  A meter made without lags = True refuses."""
+        return self._finish(self._L.g1s_nlf_finish_lags, NLF_LRECORD, cap)
+
+    def kernel_times_lags(self) -> Tuple[float, float, int]:
+        """(ms in the luma lag launches, ms in the chroma lag launches, pairs) of the batches kernel_times() had timed."""
+        a, b, n = C.c_double(), C.c_double(), C.c_uint64()
+        self._L.g1s_nlf_lag_times(self._h, C.byref(a), C.byref(b), C.byref(n))
+        return a.value, b.value, n.value
+
     def kernel_times_temporal(self) -> Tuple[float, float, int]:
         """(ms in the temporal luma launches, ms in the temporal chroma launches, pairs) of the batches kernel_times() had
         timed (HIP events)."""
@@ -275,6 +360,39 @@ def noise_levels_sum(records: np.ndarray) -> np.ndarray:
 def noise_levels_sum_temporal(records: np.ndarray) -> np.ndarray:
     """Rule T5: a clip's temporal record from its pairs' (g1s_nlf_sum_temporal; host only).  An overflow raises."""
     return _sum_records(_lib.lib().g1s_nlf_sum_temporal, NLF_TRECORD, records)
+
+
+def noise_lags_sum(records: np.ndarray) -> np.ndarray:
+    """Rule L5: a clip's lag record from its pairs' (g1s_nlf_sum_lags; host only).  An overflow raises."""
+    return _sum_records(_lib.lib().g1s_nlf_sum_lags, NLF_LRECORD, records)
+
+
+def noise_ar(lags_total: np.ndarray, plane: int, bit_depth: int, xdec: int = 1, ydec: int = 1, lag: int = 3, min_count: int = 0) -> Tuple[np.ndarray, float]:
+    """Rules L6 - L7: (the AR coefficients of a plane before quantisation -- 2 lag (lag + 1) of them, on a chroma plane the luma
+    coefficient behind them --, the fold's gain) from a clip's lag record (g1s_nlf_ar; host only).  A refusal raises."""
+    L = _lib.lib()
+    record = np.ascontiguousarray(lags_total, NLF_LRECORD)
+    x, gain = (C.c_double * 25)(), C.c_double()
+    rc = L.g1s_nlf_ar(record.ctypes.data, plane, bit_depth, xdec, ydec, lag, min_count, x, C.byref(gain))
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    n = 2 * lag * (lag + 1) + (1 if plane else 0)
+    return np.array(x[:n], np.float64), gain.value
+
+
+def noise_table(ttotal: np.ndarray, lags_total: np.ndarray, bit_depth: int, xdec: int = 1, ydec: int = 1, nplanes: int = 3, lag: int = 3, min_count: int = 0):
+    """Rules L6 - L9: a GrainTableSegment from a clip's temporal record and its lag record (g1s_nlf_table; host only): the
+    clip's own grain table, no denoiser involved.  A refusal raises."""
+    from ._lib import G1SSegment
+    from .diff import GrainTableSegment
+
+    L = _lib.lib()
+    t, l = np.ascontiguousarray(ttotal, NLF_TRECORD), np.ascontiguousarray(lags_total, NLF_LRECORD)
+    out = G1SSegment()
+    rc = L.g1s_nlf_table(t.ctypes.data, l.ctypes.data, bit_depth, xdec, ydec, nplanes, lag, min_count, C.byref(out))
+    if rc:
+        raise G1SError(rc, L.g1s_last_global_error().decode())
+    return GrainTableSegment.from_c(out)
 
 
 def noise_sigma(record: np.ndarray, bit_depth: int, min_count: int = 0, *, temporal: bool = False) -> np.ndarray:

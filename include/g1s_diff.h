@@ -621,6 +621,120 @@ long g1s_format_noise_levels_temporal(const g1s_nlf_trecord_t *total, const g1s_
 int64_t g1s_nlf_y4m_file_temporal(const char *source, const char *out_report, const char *out_treport, const g1s_nlf_opts_t *opts, uint64_t max_frames,
                                   g1s_nlf_record_t *total, g1s_nlf_trecord_t *ttotal, char *err, size_t cap);
 
+/* ---- lagged noise levels, rules L1 - L10: the lagged products of a clip's frame differences ----
+ * T1 - T8 give the grain's size per intensity: a table's scaling function.  The other half of a table, its AR
+ * coefficients, is in the same difference: where the picture stands still e is grain and only grain, and the covariance of
+ * e(p) and e(p + d) is twice the grain's at lag d.  A meter made for lags (g1s_nlf_new_lags) is a temporal meter -- its
+ * ordinary and temporal records are those of g1s_nlf_new_temporal byte for byte -- that adds for every pair of a run a lag
+ * record: the sums from which the covariances at every lag an AR fit of lag 1 .. 3 needs are formed, and for chroma those
+ * against the luma difference under it.  No denoiser is involved.  B, sh, the planes, the INTERIOR, T1's e and T2's gate are
+ * as they stand.  Everything is integer.  For plane c of size pw x ph:
+ *  L1. Gate bit.  g_c(p) = 1 iff p is interior and COUNTS by T2, else 0.  It is 0 outside the plane.
+ *  L2. Lags.  46 offsets d_i = (dx, dy): dy = 0, dx = 0 .. 6 (i = 0 .. 6); dy = 1, 2, 3, dx = -6 .. 6
+ *      (i = 7 + 13 (dy - 1) + dx + 6).  These are the differences of two members of {the causal lag-3 neighbourhood,
+ *      (0, 0)}, one of each +- pair.
+ *  L3. Sums.  n[i] = the number of p with g(p) g(p + d_i) = 1 (u64), r[i] = the sum of e(p) e(p + d_i) over them (i64),
+ *      s = the sum of e(p) over g(p) = 1 (i64).  Pairs with an end outside the plane do not exist: skipped, not clamped.
+ *      One product is below 2^24, so a 65536 x 65536 plane stays below 2^56.  With the temporal record of the same pair:
+ *      n[0] = sum_k n_T[c][k], r[0] = sum_k q_T[c][k], s = sum_k s_T[c][k].
+ *  L4. Luma under chroma, for a frame of three planes.  Lbar(p), p on the chroma grid, is rule 12 of `measure` (the
+ *      specification's box, Round2 with an arithmetic shift, the clamp) on the luma difference e_0 -- e_0 itself, gated or
+ *      not.  gL(p) = 1 iff g_0 = 1 at every luma sample of that box, at the clamped coordinates.  delta_j are rule 4 of
+ *      `measure`'s 25 offsets: the 24 causal ones in the table's coefficient order, (0, 0) at index 24.  For c = 1, 2:
+ *      xn[c - 1][j] = the number of p with gL(p) g_c(p + delta_j) = 1, xr[c - 1][j] = the sum of Lbar(p) e_c(p + delta_j)
+ *      over them (i64); p and p + delta_j on the chroma grid, skipped where either is outside.  Once per frame, over the
+ *      chroma grid: ln = the number of p with gL(p) = 1, ls = the sum of Lbar over them (i64), l2 = the sum of Lbar^2
+ *      (u64).  At 4:4:4 Lbar = e_0 and gL = g_0.  A frame of one plane has zeros here.  The clamp bears on no record: a box
+ *      that needs it holds a sample of the luma plane's last column or row, which is not interior, so gL = 0 there whatever
+ *      Lbar is; it is stated so that Lbar is defined at every p.
+ *  L5. Record.  g1s_nlf_lrecord_t, zeros for the planes a frame lacks.  A clip's record is the checked 64-bit sum of its
+ *      pairs' (g1s_nlf_sum_lags; r, s, xr and ls as signed sums): an overflow is a refusal, as in T5.
+ * The gate's bias is T2's and is not corrected: in a numpy run on a 240 x 320 10-bit ramp under lag-3 AR grain (taps 0.45 /
+ * 0.40 / -0.15 / ...) a Yule-Walker fit on these sums returned the 24 coefficients within 0.011 at sigma = 8 code values
+ * (the gate kept 99 %; ungated: 0.012), and under a pan of 2 samples a frame still within 0.011 where the ungated fit was off
+ * by 0.235; at sigma = 24 the gate kept 49 % and cut tails: the large taps read 0.40 / 0.36 for 0.45 / 0.40.  Motion is
+ * gated, not compensated; the vectors kd_motion finds are not used.  These are numpy runs on synthetic content; nothing here
+ * has been run on real footage.
+ * The two lag launches (luma; both chroma planes) of a batch's pairs follow k_nlf_t's on the meter's stream. */
+typedef struct {
+  uint64_t n[3][46];
+  int64_t r[3][46];
+  int64_t s[3];
+  uint64_t xn[2][25];
+  int64_t xr[2][25];
+  uint64_t ln;
+  int64_t ls;
+  uint64_t l2;
+} g1s_nlf_lrecord_t;
+/* g1s_nlf_new_temporal for a lag meter: everything a temporal meter does, and the lag records beside.  Capacity, stickiness,
+ * g1s_nlf_cut, the copy of the frame before and the lifetime rules are the temporal meter's. */
+g1s_nlf_t *g1s_nlf_new_lags(uint32_t bit_depth, const g1s_nlf_opts_t *opts);
+/* g1s_nlf_finish for the lag records: one per frame with a predecessor since the last hand-over, in order.  The ordinary and
+ * temporal records stay for their own calls.  Capacity as there.  On a meter made otherwise: G1S_ERR_INVALID, "not a lag
+ * meter: make it with g1s_nlf_new_lags" (not sticky). */
+int g1s_nlf_finish_lags(g1s_nlf_t *, g1s_nlf_lrecord_t *per_pair, size_t cap, size_t *n_out);
+/* HIP-event time of the luma and chroma lag launches so far, milliseconds, and the pairs they covered; timed while
+ * g1s_nlf_set_timing has it enabled.  tools/bench_estimate.py --lags. */
+int g1s_nlf_lag_times(g1s_nlf_t *, double *ms_luma, double *ms_chroma, uint64_t *pairs);
+/* Host only.  L5: *total = the sum of recs[0 .. n).  G1S_ERR_INVALID when a sum leaves 64 bits. */
+int g1s_nlf_sum_lags(const g1s_nlf_lrecord_t *recs, size_t n, g1s_nlf_lrecord_t *total);
+/* Host only.  Rules L6 - L7: the AR coefficients of one plane from a clip's lag record, before quantisation.
+ *  L6. Covariances, f64 from the exact integers in the order written.  m = (double)s / n[0]; C(d_i) = (double)r[i] / n[i] -
+ *      m m, and C(-d) = C(d); mL = ls / ln, VL = l2 / ln - mL^2; X(delta_j) = xr[j] / xn[j] - mL m.  Nmin is min_count, 0 = 4096.
+ *      Refused with "too few static sample pairs for a table" when n of any lag the chosen `lag` needs is below Nmin; on a
+ *      chroma plane the same holds for xn and ln.
+ *  L7. AR system for lag L in 1 .. 3; o_1 .. o_m the table's causal offsets (dy = -L .. 0, dx = -L .. L, raster, stopping before
+ *      (0, 0)), m = 2 L (L + 1).  Luma: N = n[0], A[i][j] = N C(o_i - o_j), b[i] = N C(o_i).  Chroma adds row and column m:
+ *      A[i][m] = A[m][i] = N X(o_i), A[m][m] = N VL, b[m] = N X((0, 0)).  Every entry is divided by 4^(B - 8) 255^2: the fold
+ *      (`diff`) forms its normal equations from eight-bit code values over 255, and its solver's thresholds are in those
+ *      units.  Solved by the fold's own elimination, with its gain (the square root of the variance over the innovation's) and,
+ *      for a singular chroma system, its fallback: zero coefficients and the luma coefficient b[m] / A[m][m].  A singular luma
+ *      system is refused with the fold's text.
+ * x[0 .. m) are the coefficients in the table's order, x[m] on a chroma plane the luma coefficient, the rest zeros; *gain the
+ * fold's gain.  xdec and ydec are checked and otherwise unused (Lbar is a mean already).  G1S_ERR_INVALID with the reason from
+ * g1s_last_global_error().  The fit divides out what the gate does to the scale and keeps what it does to the shape: see the
+ * bias stated above. */
+int g1s_nlf_ar(const g1s_nlf_lrecord_t *ltotal, uint32_t plane, uint32_t bit_depth, uint32_t xdec, uint32_t ydec, uint32_t lag, uint64_t min_count,
+               double x[25], double *gain);
+/* Host only.  Rules L8 - L9: a table's segment from a clip's temporal record (the scaling functions) and its lag record (the AR
+ * coefficients): a grain table from the clip alone, no denoiser involved.
+ *  L8. Strength.  Per plane, for every bin k of the temporal record with n >= Nmin, in ascending k, one measurement goes into
+ *      the fold's strength solver: N6's bin centre in eight-bit code values (8 k + 4) and the bin's standard deviation,
+ *      sqrt(T6's variance of e / 2) / 2^(B - 8), divided by the plane's gain exactly as the fold's per-frame half does: luma
+ *      sqrt(v) / gain; chroma sqrt(max(v / 16, v - (x[m] g_0 y(8 k + 4))^2)) / gain, x[m] the plane's luma coefficient, g_0 the
+ *      luma gain and y the luma curve just solved.  No valid luma bin: N6's refusal.  A chroma plane without a valid bin gets
+ *      no points.
+ *  L9. Segment.  The three states go through the fold's own quantisation (the function `diff` ends a segment with): one
+ *      segment [0, INT64_MAX), the default seed, overlap_flag 1 and the fold's other constants, as a `diff` table has them.
+ * nplanes 1 or 3; lag 1 .. 3; min_count as in L6.  G1S_ERR_INVALID with the reason from g1s_last_global_error(): L6's and L7's
+ * refusals, N6's, "Solving latest noise strength failed!".  Closure, measured on the CPU (tests/test_nlf_lags_cpu.py,
+ * profiles/noise_lags.txt): the table made from five 256 x 192 frames of a lag-3 table's rendered grain, rendered again onto flat
+ * grey, has the original's sigma within 1.2 % / 0.7 % / 3.9 % (Y / Cb / Cr). */
+int g1s_nlf_table(const g1s_nlf_trecord_t *ttotal, const g1s_nlf_lrecord_t *ltotal, uint32_t bit_depth, uint32_t xdec, uint32_t ydec,
+                  uint32_t nplanes, uint32_t lag, uint64_t min_count, g1s_segment_t *out);
+/* Host only.  Rule L10: the report of a clip's lag record of `pairs` pairs at lag L.  Every value is formed in f64 from the exact
+ * integers in the order written and printed "%.4f"; "-" where L6 refuses.  Grammar:
+ *   noiselags1
+ *   pairs N bit_depth B planes P lag L
+ *   plane c                           for c in 0 .. P - 1
+ *   n0 n sigma_t v gain g             n = n[c][0]; v = sqrt(max(C(0), 0) / 2), code values of the clip's depth, "-" when n < Nmin;
+ *                                     g the fit's gain, "-" when L6 or L7 refuses the plane's fit at lag L
+ *   rho i dx dy v                     the causal offsets o_i = (dx, dy), i = 0 .. m - 1: v = C(o_i) / C(0); "-" when n[c][0] or the
+ *                                     lag's n is below Nmin or C(0) <= 0
+ *   coef i v                          i = 0 .. m - 1: the solved coefficients (L7), all "-" when the fit is refused
+ *   luma v                            planes 1 and 2 only: the luma coefficient, "-" when the fit is refused
+ * Bytes written, or G1S_ERR_CAPACITY (G1S_ERR_INVALID for a bit depth, plane count or lag the rules do not have). */
+long g1s_format_noise_lags(const g1s_nlf_lrecord_t *ltotal, uint64_t pairs, uint32_t bit_depth, uint32_t nplanes, uint32_t lag, uint64_t min_count,
+                           char *buf, size_t cap);
+/* `estimate SOURCE --table PATH` for a .y4m file through a lag meter, the file one run: the first max_frames frames (0 = all).
+ * The table (g1s_nlf_table at `lag`, `min_count`) is made first: a refusal ("a table needs two frames" for a clip of fewer, the
+ * host function's otherwise) writes nothing.  Then the .tbl through g1s_format_tbl into out_table, the lag report into out_lags,
+ * the noise levels into out_report and the temporal noise levels into out_treport (each may be NULL), the segment into
+ * *segment_out (may be NULL).  Returns the number of frames, or a negative G1S_ERR_* with the reason in err. */
+int64_t g1s_nlf_y4m_file_table(const char *source, const char *out_table, const char *out_report, const char *out_treport, const char *out_lags,
+                               const g1s_nlf_opts_t *opts, uint64_t max_frames, uint32_t lag, uint64_t min_count, g1s_segment_t *segment_out, char *err,
+                               size_t cap);
+
 /* ---- `render`: AV1 film grain synthesis on the device (the inverse of `diff`: a table's grain onto frames) ----
  * The film grain synthesis process of the AV1 specification (clause 7.18.3: random number process, generate grain
  * process, scaling lookup initialisation, add noise synthesis process), integer-exact, written from the standard.
